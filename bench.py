@@ -23,6 +23,9 @@ steps (one swap step = 2 attempted flips).  value = attempted flips/s over the w
                  line with "dry_run": true and value null
 --oversubscribe  ranks share the visible GPUs round-robin and reduce over gloo (lets the N-rank
                  path run on a 1-GPU box; the value is then not a scaling measurement)
+--dump-outputs DIR  after the timed steps, the state they left on rank 0's walkers as DIR/<name>.npy
+                 (enthalpy, features, counters of every walker; the occupancy of a seeded sample of
+                 512 walkers): the inputs are seeded, so two builds can be compared output for output
 """
 
 import argparse
@@ -704,6 +707,23 @@ def dry_run(args, rank, world):
         dist.destroy_process_group()
 
 
+DUMP_OCC_WALKERS = 512  # occupancy rows kept by --dump-outputs: 512 x 4096 sites x 4 B = 8 MB (all 4096 rows: 64 MB)
+
+
+def dump_outputs(path, state):
+    """--dump-outputs: what Engine.get_state hands a caller after the last timed launch, one float64 .npy per
+    array.  Per-walker arrays are written whole; the occupancy only for a fixed, seeded sample of walkers
+    (float32, walker indices in occupancy_walkers.npy).  The inputs are seeded, so two builds run with the same
+    arguments can be compared array by array."""
+    os.makedirs(path, exist_ok=True)
+    occ = state.pop("occupancy")
+    rows = np.sort(np.random.default_rng(0).choice(len(occ), min(len(occ), DUMP_OCC_WALKERS), replace=False))
+    np.save(os.path.join(path, "occupancy_sample.npy"), occ[rows].astype(np.float32))
+    np.save(os.path.join(path, "occupancy_walkers.npy"), rows.astype(np.float64))
+    for name, a in state.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -719,6 +739,8 @@ def main():
     ap.add_argument("--no-strong", action="store_true", help="skip the 4096-walkers-in-total measurement on N > 1 ranks")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--oversubscribe", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the state the timed launches left on rank 0's walkers to DIR/<name>.npy")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_child:
@@ -837,6 +859,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     s1 = eng.get_state(occupancy=False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng.get_state())
     acc_local = float((s1["n_accepted"] - s0["n_accepted"]).sum())
     stats = torch.tensor(
         [acc_local, float(s1["enthalpy"].sum()), float((s1["enthalpy"] ** 2).sum()), float(R),

@@ -8,6 +8,8 @@ import socket
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -68,3 +70,56 @@ def test_gpus_must_match_world_size():
     out = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--dry-run"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=120)
     assert out.returncode != 0 and "WORLD_SIZE=2" in out.stderr
+
+
+def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
+    """--dump-outputs at the headline's shape: every array of the state as float32 / float64, the occupancy of a
+    seeded sample of walkers, 64 MB at most."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    R, N, F = 4096, 4096, 8
+    rng = np.random.default_rng(3)
+    state = dict(occupancy=rng.integers(0, 2, (R, N), dtype=np.int32), features=rng.random((R, F)),
+                 enthalpy=rng.random(R), n_accepted=np.arange(R, dtype=np.uint64),
+                 n_steps=np.full(R, 10**6, dtype=np.uint64), accepted=rng.random(R) < 0.5)
+    dumps = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), dict(state))
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert set(a) == {"occupancy_sample", "occupancy_walkers", "features", "enthalpy", "n_accepted", "n_steps",
+                      "accepted"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in a) <= 64 * 2**20
+    rows = a["occupancy_walkers"].astype(np.int64)
+    assert len(rows) == bench.DUMP_OCC_WALKERS and len(set(rows)) == len(rows)
+    np.testing.assert_array_equal(a["occupancy_sample"], state["occupancy"][rows])
+    for k in ("features", "enthalpy", "n_accepted", "n_steps", "accepted"):
+        np.testing.assert_array_equal(a[k], state[k].astype(np.float64).reshape(a[k].shape))
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_state_after_the_timed_steps(tmp_path):
+    """Two runs with the same arguments dump the same arrays, and every walker has taken exactly (warmup + steps)
+    launches of --mc-per-step steps."""
+    import numpy as np
+
+    warmup, steps, mc = 1, 3, 2000
+    dumps = []
+    for d in ("a", "b"):
+        out = _run([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                    "--mc-per-step", str(mc), "--replicas", "256", "--no-other-configs", "--no-cpu-baseline",
+                    "--dump-outputs", str(tmp_path / d)])
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert _line(out)["steps"] == steps
+        dumps.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = dumps
+    assert (a["n_steps"] == (warmup + steps) * mc).all()
+    assert a["enthalpy"].shape == (256,) and a["occupancy_sample"].shape == (256, 4096)
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)

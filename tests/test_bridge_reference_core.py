@@ -1,12 +1,12 @@
 """The reference-side half of the boundary (smol_amd.bridge / tools/export_smol_model.py) run
-against stand-ins for smol's Python objects that hold the reference's REAL compiled classes.
+against stand-ins for smol's Python objects.
 
 smol.moca cannot be imported here (pymatgen / monty absent), but everything the exporter reads
-from a processor is either a plain attribute or lives inside a Cython ``ClusterSpaceEvaluator``.
-The evaluators below are instances of the reference's own extension type, built out of tree from
-/root/reference exactly as tests/golden/make_golden.py does, so attribute visibility (the orbit
-tuples are a private ``cdef tuple``) is the reference's.  Runs only where /root/reference exists
-(the build container); the GPU box never needs it."""
+from a processor is either a plain attribute or lives inside a Cython ``ClusterSpaceEvaluator``,
+which the bridge reads through one call: ``__reduce__`` (its orbit tuples are a private
+``cdef tuple``, container.pxd:22).  The evaluators below answer that call with the reply the
+reference's own compiled class gave for the same arguments, recorded in
+tests/golden/bridge_evaluator_reduce.npz by tests/golden/make_bridge_golden.py."""
 
 import os
 import sys
@@ -17,24 +17,57 @@ import pytest
 
 from smol_amd import bridge, capi, ewald, io, synth
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "smol", "utils", "cluster")),
-                                reason="needs the reference checkout (build container only)")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bridge_evaluator_reduce.npz")
+
+
+class RecordedEvaluator:
+    """Stands in for smol.utils.cluster.evaluator.ClusterSpaceEvaluator: ``__reduce__`` returns the recorded reply,
+    with the orbit tuples the evaluator was built from where the reference returns those; like the compiled class
+    it has no readable ``_orbit_data``."""
+
+    __slots__ = ("_reply",)
+
+    def __init__(self, reply):
+        self._reply = reply
+
+    def __reduce__(self):
+        return self._reply
 
 
 @pytest.fixture(scope="module")
-def core():
-    pytest.importorskip("Cython")
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import make_golden
+def gold():
+    g = dict(np.load(GOLD))
+    assert str(g["evaluator_type"]) == str(g["reply_type"]) == "smol.utils.cluster.evaluator.ClusterSpaceEvaluator"
+    # the reference keeps the evaluator's orbit tuples private (container.pxd:22): the exporter
+    # of round 1 read `_orbit_data` and could never have run
+    assert not g["has_orbit_data"]
+    return g
 
-    return make_golden.build_reference_core()
+
+def recorded_evaluators(gold, decomposition):
+    """make_evaluator(site, args) of smol_like_ensemble: the recorded reply of the reference's evaluator at ``site``."""
+    d = int(decomposition)
+    sites = [int(s) for s in gold[f"d{d}_sites"]]
+    assert (gold[f"d{d}_reply_len"] == 6).all() and gold[f"d{d}_orbit_data_is_input"].all()
+    sizes = np.split(gold[f"d{d}_interaction_sizes"], np.cumsum(gold[f"d{d}_interaction_counts"])[:-1])
+    flat = np.split(gold[f"d{d}_interactions"], np.cumsum(gold[f"d{d}_interaction_sizes"])[:-1])
+    first = np.cumsum([0] + [len(s) for s in sizes])
+    rest = {}
+    for i, s in enumerate(sites):
+        n_orb, n_corr, n_thr, offset = gold[f"d{d}_scalars"][i]
+        rest[s] = (int(n_orb), int(n_corr), int(n_thr), float(offset), tuple(flat[first[i]:first[i + 1]]))
+
+    def make_evaluator(site, args):
+        assert args[1:3] == rest[site][:2]
+        return RecordedEvaluator((RecordedEvaluator, (args[0],) + rest[site]))
+
+    return make_evaluator
 
 
-def _smol_like_ensemble(core, decomposition, with_ewald, with_mu):
+def smol_like_ensemble(make_evaluator, decomposition, with_ewald, with_mu):
     """Objects shaped like smol's, assembled the way its constructors do
-    (processor/expansion.py:104-156, :318-389; processor/ewald.py:76-101; composite.py)."""
-    ev, ct = core[0], core[1]
+    (processor/expansion.py:104-156, :318-389; processor/ewald.py:76-101; composite.py); the
+    evaluator of each site is ``make_evaluator(site, constructor arguments)``."""
     model = synth.build_cluster_model(synth.rocksalt_prim(), {2: 6.0, 3: 4.5})
     sc = synth.build_supercell(model, [3, 3, 3])
     coefs = synth.random_coefs(model, seed=9)
@@ -51,12 +84,12 @@ def _smol_like_ensemble(core, decomposition, with_ewald, with_mu):
             args += (1, itens[0], tuple(flat_it[pos] for pos, _, _ in data))
         rows = tuple(r for _, r, _ in data)
         by_site[site] = SimpleNamespace(
-            site_index=site, evaluator=ev.ClusterSpaceEvaluator(*args),
-            indices=SimpleNamespace(arrays=rows, container=ct.IntArray2DContainer(rows)),
+            site_index=site, evaluator=make_evaluator(site, args),
+            indices=SimpleNamespace(arrays=rows),
             cluster_ratio=np.array([r for _, _, r in data]))
     full = tuple(sc.full_indices)
     ce = SimpleNamespace(cluster_subspace=subspace, num_sites=sc.num_sites, size=sc.size,
-                         _indices=SimpleNamespace(arrays=full, container=ct.IntArray2DContainer(full)),
+                         _indices=SimpleNamespace(arrays=full),
                          _eval_data_by_sites=by_site,
                          coefs=model.orbit_multiplicities.astype(float) if decomposition else coefs)
     if decomposition:
@@ -83,13 +116,10 @@ def _smol_like_ensemble(core, decomposition, with_ewald, with_mu):
 
 @pytest.mark.parametrize("decomposition,with_ewald,with_mu", [(True, True, True), (False, False, False),
                                                                (True, False, True), (False, True, False)])
-def test_bridge_flattens_reference_objects_into_the_same_tables(core, decomposition, with_ewald, with_mu, tmp_path):
-    ensemble, want, by_site = _smol_like_ensemble(core, decomposition, with_ewald, with_mu)
-    some = next(iter(by_site.values())).evaluator
-    # the reference keeps the evaluator's orbit tuples private (container.pxd:22): the exporter
-    # of round 1 read `_orbit_data` and could never have run
-    assert not hasattr(some, "_orbit_data")
-    assert type(some).__module__ == "smol.utils.cluster.evaluator"
+def test_bridge_flattens_reference_objects_into_the_same_tables(gold, decomposition, with_ewald, with_mu, tmp_path):
+    ensemble, want, by_site = smol_like_ensemble(recorded_evaluators(gold, decomposition), decomposition, with_ewald,
+                                                 with_mu)
+    assert not hasattr(next(iter(by_site.values())).evaluator, "_orbit_data")
     got = bridge.tables_from_ensemble(ensemble)
     assert set(got._keep) == set(want._keep)
     # a ClusterExpansionProcessor carries no interaction tensors (the evaluator's default, the sum
@@ -117,8 +147,8 @@ def test_bridge_flattens_reference_objects_into_the_same_tables(core, decomposit
             np.testing.assert_array_equal(back._keep[k], v, err_msg=k)
 
 
-def test_unsupported_compositions_are_refused(core):
-    ensemble, _, _ = _smol_like_ensemble(core, True, True, False)
+def test_unsupported_compositions_are_refused(gold):
+    ensemble, _, _ = smol_like_ensemble(recorded_evaluators(gold, True), True, True, False)
     ensemble.processor.processors.append(SimpleNamespace(some_other_processor=True))
     with pytest.raises(NotImplementedError):
         bridge.tables_from_ensemble(ensemble)

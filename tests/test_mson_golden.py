@@ -58,7 +58,7 @@ def test_regenerated_cluster_indices_equal_the_models_cached_tables(lno):
     assert [o.multiplicity for o in sub.orbits] == [1, 1, 6, 3, 3, 6, 6, 6, 2, 2]
 
 
-@pytest.mark.parametrize("path", [CE, CE_EWALD])
+@pytest.mark.parametrize("path", [CE, CE_EWALD], ids=["lno_ce", "lno_ce_ewald"])
 def test_oracle_reproduces_the_reference_feature_matrix(path):
     """T1 + T2 + Ewald values: occupancy from (structure species, site mapping) as
     occupancy_from_structure builds it (clusterspace.py:834-856), full correlation vector by the

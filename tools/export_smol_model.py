@@ -7,8 +7,8 @@
 The file holds the flattened arrays of include/smolmc.h:smolmc_tables; smol_amd.io.load_tables
 reads it on the GPU box (no smol / pymatgen needed there).  The flattening itself is
 smol_amd.bridge.tables_from_ensemble, which only reads attributes of smol's objects (listed
-there with file:line); tests/test_bridge_reference_core.py runs it against stand-ins built from
-the reference's compiled Cython classes, so attribute visibility is the reference's.
+there with file:line); tests/test_bridge_reference_core.py runs it against stand-ins whose evaluators
+answer with the replies of the reference's compiled Cython class (tests/golden/bridge_evaluator_reduce.npz).
 """
 import os
 import sys
