@@ -274,7 +274,7 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
     const int N = t->num_sites;
     const bool corr = t->feature_mode == SMOLMC_FEATURES_CORRELATIONS;
     if ((size_t)h->Npad + 4096 > 160 * 1024) return no_general(h, "occupancy does not fit LDS");
-    if (getenv("SMOLMC_FORCE_UNIVERSAL")) return no_general(h, "SMOLMC_FORCE_UNIVERSAL");
+    if (smolmc_env(ENV_FORCE_UNIVERSAL)) return no_general(h, "SMOLMC_FORCE_UNIVERSAL");
     // does any local row contain a repeated site (aliased tiny supercells)?
     bool aliased = false;
     int maxI = 1;
@@ -531,7 +531,7 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
             for (size_t q = 0; q < a.size() && lean_slots_ok; ++q)
                 lean_slots_ok = a[q].orbit == b[q].orbit && a[q].selfmask == b[q].selfmask && a[q].selfmask != 0;
         }
-    const bool lean_aliased_ok = !aliased || (lean_slots_ok && getenv("SMOLMC_NO_LEAN_ALIASED") == nullptr);
+    const bool lean_aliased_ok = !aliased || (lean_slots_ok && !smolmc_env(ENV_NO_LEAN_ALIASED));
     // one site class: mc_lean_kernel (NSLOT <= 4); up to four classes or up to 512 clusters per
     // site: mc_lean_multi_kernel (per-class slot records in LDS)
     // Correlation features (ClusterExpansionProcessor, evaluator.pyx:211-265): when every orbit
@@ -550,10 +550,10 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
     // (the KF instantiations are plain Metropolis flip / swap kernels of the single-class layout)
     bool corr_kf = corr && !corr_k1 && kmax <= SMOLMC_LEAN_MAX_KF && class_rep.size() == 1 && !cfg_wl && !t->bias_type &&
                    h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP && t->n_sublattices == 1 && niter_max <= 4 && num_ce_features(t) <= 64 &&
-                   getenv("SMOLMC_LAZY_FEATURES_ONLY") == nullptr;
+                   !smolmc_env(ENV_LAZY_FEATURES_ONLY);
     // ... and the Wang-Landau kernel of the multi-class layout (KFW, round 5): any number of classes the layout takes
     if (corr && !corr_k1 && kmax <= SMOLMC_LEAN_MAX_KF && cfg_wl && !t->bias_type && h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP &&
-        num_ce_features(t) <= 61 && getenv("SMOLMC_NO_WL_KF") == nullptr)
+        num_ce_features(t) <= 61)
         corr_kf = true;
     // LAZY cluster features (round 5): every other Metropolis kernel of the lean families takes a model with several
     // correlation functions per orbit as an interaction-mode model of the folded tensors E = sum_k coef_k ct_k --
@@ -561,18 +561,17 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
     // occupancy where somebody reads them (smolmc_get_state, sample rows; ensure_features / lazy_rows_kernel).
     // Any number of functions per orbit and of cluster features; Wang-Landau needs the features on every step and
     // stays on mc_kernel.
-    bool corr_lazy = corr && !corr_k1 && !corr_kf && !cfg_wl && getenv("SMOLMC_NO_LAZY_FEATURES") == nullptr;
-    if (getenv("SMOLMC_NO_LEAN_CORR")) corr_k1 = corr_kf = corr_lazy = false; // A/B switch (tests, profiling)
+    const bool corr_lazy = corr && !corr_k1 && !corr_kf && !cfg_wl && !smolmc_env(ENV_NO_LAZY_FEATURES);
     // ... and the same for models of more than 64 cluster features (the kernels' feature cells are one per lane)
     const bool wide_lazy = !corr_lazy && !corr_kf && (!corr || corr_k1) && num_ce_features(t) > 64 && !cfg_wl &&
-                           getenv("SMOLMC_NO_LAZY_FEATURES") == nullptr;
+                           !smolmc_env(ENV_NO_LAZY_FEATURES);
     const bool lazy_any = corr_lazy || wide_lazy;
     // (why a model does not get the lean tables, reported by smolmc_kernel_info: the first condition that fails)
     h->lean_reason = class_rep.size() < 1 ? "no site with clusters"
                      : class_rep.size() > 4 ? "more than 4 site classes"
                      : !lean_aliased_ok ? "aliased supercell (a cluster holds a site twice) whose sites do not list their clusters alike"
                      : (corr && !corr_k1 && !corr_kf && !corr_lazy) ? (cfg_wl ? "Wang-Landau with more than SMOLMC_LEAN_MAX_KF correlation functions per orbit, more than 61 of them, or TableFlip"
-                                                                                : "environment override (SMOLMC_NO_LEAN_CORR / SMOLMC_NO_LAZY_FEATURES)")
+                                                                                : "environment override (SMOLMC_NO_LAZY_FEATURES)")
                      : N > 65535 ? "more than 65535 sites"
                      : niter_max > 8 ? "more than 512 clusters per site"
                      : lean_need_mm > 3 ? "clusters of more than 4 sites"
@@ -633,8 +632,7 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
                 return tot;
             };
             double best = model_cost(0, 0, 0);
-            const int amax = getenv("SMOLMC_NO_SWIZZLE") ? 0 : 12; // A/B switch for profiling
-            for (int a = 3; a <= amax; ++a)
+            for (int a = 3; a <= 12; ++a)
                 for (int b = 2; b <= 5; ++b)
                     for (int m : {3, 7, 15, 31}) {
                         // bijection on [0, Nlds): source bits [a, a+k) above the destination
@@ -667,8 +665,8 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
         // Entries the LDS copy of the tables may take.  8000 (64 KB, two workgroups per CU) until round 6; models between
         // that and what one workgroup's LDS holds beside the walkers' state (the layouts below decide) ran on mc_kernel
         // with the tables in L2: measured on five quaternary triplet / quadruplet models of the fuzz campaign at 2048
-        // walkers, 0.39-1.05e9 steps/s there against 0.99-2.43e9 here (tools/time_fuzz_case.py).  SMOLMC_LEAN_DT_MAX: A/B hook.
-        const size_t dt_max = getenv("SMOLMC_LEAN_DT_MAX") ? (size_t)atol(getenv("SMOLMC_LEAN_DT_MAX")) : (size_t)18000;
+        // walkers, 0.39-1.05e9 steps/s there against 0.99-2.43e9 here (tools/time_fuzz_case.py).
+        constexpr size_t dt_max = 18000;
         std::vector<double> dtk; // KF: correlation-function tables (global memory), see LeanParams::dtk
         std::vector<LeanSlot> ls((size_t)NCLS * NSL * 64);
         memset(ls.data(), 0, ls.size() * sizeof(LeanSlot));
@@ -936,7 +934,7 @@ static int compress_ewald_rows(smolmc_handle *h, const smolmc_tables *t, const s
                                const std::vector<int> &act) {
     const size_t na = act.size();
     const int P = t->size;
-    if (getenv("SMOLMC_NO_EWALD_GX") != nullptr || P <= 1 || na == 0 || na % (size_t)P != 0) return 0;
+    if (smolmc_env(ENV_NO_EWALD_GX) || P <= 1 || na == 0 || na % (size_t)P != 0) return 0;
     const int nbk = (int)(na / (size_t)P);
     for (size_t j = 0; j < na; ++j)
         if (act[j] != act[0] + (int)j) return 0; // (the field mode needs contiguous changeable sites anyway)
@@ -1113,7 +1111,7 @@ struct RelabelledTables {
 static std::vector<int32_t> plan_relabelling(const smolmc_tables *t) {
     std::vector<int32_t> none;
     const int N = t->num_sites, ns = t->n_sublattices;
-    if (N <= 0 || ns <= 0 || !t->sub_site_ptr || !t->sub_active_sites || getenv("SMOLMC_NO_SITE_RELABEL")) return none;
+    if (N <= 0 || ns <= 0 || !t->sub_site_ptr || !t->sub_active_sites || smolmc_env(ENV_NO_SITE_RELABEL)) return none;
     bool needed = false;
     std::vector<char> taken((size_t)N, 0);
     std::vector<int32_t> order;
@@ -1251,6 +1249,8 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
     smolmc_handle *h = new smolmc_handle();
     h->cfg = *cfg;
     h->device = cfg->device;
+    for (int e = 0; e < ENV_COUNT; ++e)
+        if (smolmc_env_switches[e].dispatch && smolmc_env((SmolmcEnv)e)) h->env_dispatch |= 1u << e;
     if (new_of) {
         h->relabelled = true;
         h->new_of = *new_of;
@@ -1368,13 +1368,13 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
             dev_alloc(h, (size_t)cfg->n_replicas * SMOLMC_MAX_BIAS_ROWS, &kp.charge))
             return bail(1);
     }
-    if (t->has_ewald && t->ewald_charges && getenv("SMOLMC_DENSE_EWALD") == nullptr)
+    if (t->has_ewald && t->ewald_charges && !smolmc_env(ENV_DENSE_EWALD))
         if (int rc = build_compact_ewald(h, t)) return bail(rc);
     // potential field of every walker in HBM: needs the compact form and
     // contiguous changeable sites; the lean kernels stage the same buffer through LDS
     kp.ew_field = 0;
     if (kp.ew_compact && kp.ew_act_base >= 0 && (size_t)kp.ew_nact * 8 <= 150 * 1024 &&
-        getenv("SMOLMC_NO_EWALD_FIELD") == nullptr) {
+        !smolmc_env(ENV_NO_EWALD_FIELD)) {
         if (dev_alloc(h, (size_t)cfg->n_replicas * kp.ew_nact, &kp.ew_phi)) return bail(1);
         kp.ew_field = 1;
     }
@@ -1425,6 +1425,8 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
     kp.seeds = dseeds;
     if (dev_upload(h, h->natural.data(), h->natural.size(), (const double **)&h->d_natural))
         return bail(1);
+    // Wang-Landau keeps per-bin feature sums at update_period 1, running means otherwise
+    const int wl_sum_mode = (cfg->wl_update_period == 1 && !smolmc_env(ENV_WL_RUNNING_MEAN)) ? 1 : 0;
     if (wl) {
         kp.L = h->L;
         kp.wl_min = cfg->wl_min_enthalpy;
@@ -1434,7 +1436,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
         kp.wl_div = cfg->wl_mod_divisor;
         kp.wl_check = cfg->wl_check_period;
         kp.wl_update = cfg->wl_update_period;
-        kp.wl_sum_mode = (cfg->wl_update_period == 1 && getenv("SMOLMC_WL_RUNNING_MEAN") == nullptr) ? 1 : 0;
+        kp.wl_sum_mode = wl_sum_mode;
         // (check period 0: the flatness check is the caller's -- a host-side mod_update callable,
         // wanglandau.py:100-105 -- and no kernel runs its own)
         if (kp.wl_check < 0 || kp.wl_update <= 0) return bail(fail("WL periods must be positive"));
@@ -1482,11 +1484,10 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
         // (... the Wang-Landau TableFlip kernel, mc_table_kernel<..., WLT>, also keeps running means: any update_period)
         const bool table_wl = wl && cfg->step_type == SMOLMC_STEP_TABLE_FLIP;
         bool lean = h->lean_tables && Fk <= 64 &&
-                    (!wl || (((cfg->wl_update_period == 1 && getenv("SMOLMC_WL_RUNNING_MEAN") == nullptr) || (table_wl && cfg->wl_update_period < (1ll << 31))) &&
-                             h->F <= 63 && cfg->wl_check_period < (1ll << 31) && // (cell 63 of the feature scratch is the kernel's zero)
-                             (getenv("SMOLMC_WL_PLAIN_ONLY") == nullptr || (!t->has_ewald && !t->has_mu)))) &&
+                    (!wl || ((wl_sum_mode || (table_wl && cfg->wl_update_period < (1ll << 31))) &&
+                             h->F <= 63 && cfg->wl_check_period < (1ll << 31))) && // (cell 63 of the feature scratch is the kernel's zero)
                     (!t->has_ewald || kp.ew_compact) && t->n_sublattices == 1 && h->lean_ncls == 1 &&
-                    h->lean_nslot <= 4 && getenv("SMOLMC_FORCE_GENERAL") == nullptr;
+                    h->lean_nslot <= 4 && !smolmc_env(ENV_FORCE_GENERAL);
         int sbase = -1, nact = 0, nc = 0;
         std::vector<double> mu_row;
         if (lean) {
@@ -1506,7 +1507,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
             }
             if (nc < 2 || nc > 8) lean = false;
             if (!default_codes) {
-                if (cfg->step_type == SMOLMC_STEP_SWAP && top < 8 && getenv("SMOLMC_NO_SWAP_ANY_CODES") == nullptr) nc = top + 1;
+                if (cfg->step_type == SMOLMC_STEP_SWAP && top < 8) nc = top + 1;
                 else lean = false;
             }
         }
@@ -1523,7 +1524,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
         std::vector<double> bias_pair((size_t)64 * SMOLMC_MAX_BIAS_ROWS, 0.0);
         // the table kernels take at most 8 flip vectors: larger tables run on the universal kernel
         // (Wang-Landau TableFlip: mc_table_kernel<..., WLT> since round 6; SMOLMC_NO_TABLE_WL: A/B switch)
-        if (lean && cfg->step_type == SMOLMC_STEP_TABLE_FLIP && (t->n_flip_vectors > 8 || (wl && getenv("SMOLMC_NO_TABLE_WL") != nullptr)))
+        if (lean && cfg->step_type == SMOLMC_STEP_TABLE_FLIP && (t->n_flip_vectors > 8 || (wl && smolmc_env(ENV_NO_TABLE_WL))))
             lean = false;
         // several correlation functions per orbit: plain Metropolis flip / swap variants only
         if (lean && h->lean_kf && (wl || t->bias_type || cfg->step_type == SMOLMC_STEP_TABLE_FLIP)) lean = false;
@@ -1542,7 +1543,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                     }
             }
             // (TableFlip with a bias: mc_table_kernel<..., BIAS> since round 6; SMOLMC_NO_TABLE_BIAS: A/B switch)
-            if (cfg->step_type == SMOLMC_STEP_TABLE_FLIP && getenv("SMOLMC_NO_TABLE_BIAS") != nullptr) lean = false;
+            if (cfg->step_type == SMOLMC_STEP_TABLE_FLIP && smolmc_env(ENV_NO_TABLE_BIAS)) lean = false;
         }
         if (lean) {
             LeanParams &lp = h->lp;
@@ -1561,9 +1562,8 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                 for (double v : mu_row) mmax = std::max(mmax, std::fabs(v));
                 lp.fast_eps += 4.0 * mmax * ldexp(1.0, -19);
             }
-            if (getenv("SMOLMC_NO_FAST_ACCEPT")) lp.fast_eps = 0.0; // A/B switch
             // test hook: widen the undecided band so that both decision paths interleave
-            if (const char *sc = getenv("SMOLMC_FAST_EPS_SCALE")) lp.fast_eps *= atof(sc);
+            if (const char *sc = smolmc_env(ENV_FAST_EPS_SCALE)) lp.fast_eps *= atof(sc);
             lp.occ = kp.occ;
             lp.enthalpy = kp.enthalpy;
             lp.features = h->lazy_tables ? h->d_lazy_scal : kp.features;
@@ -1612,9 +1612,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
             h->lean_lds = ((size_t)lp.dt_len + 24) * 8 +
                           (size_t)4 * (lp.Nlds + 64 * 8 + 64 +
                                        (table_wl ? wl_multi_wave_bytes(h->L, h->F, kp.wl_sum_mode) // (mc_table_kernel<..., WLT>: the multi-class kernel's state)
-                                        : wl     ? std::max(wl_lean_bins_bytes(h->L) + (size_t)SMOLMC_WL_ROWS * h->F * 8,
-                                                            // (round 2's variant inside mc_lean_kernel, A/B switch: 24-byte records)
-                                                            getenv("SMOLMC_WL_V2") ? (size_t)h->L * 24 : (size_t)0)
+                                        : wl     ? wl_lean_bins_bytes(h->L) + (size_t)SMOLMC_WL_ROWS * h->F * 8
                                                  : 0));
             if (h->lean_lds > 150 * 1024) lean = false;
             // Ewald potential field in LDS when the changeable sites are the active
@@ -1623,9 +1621,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
             // (the changeable sites may extend beyond the active ones: restricted sites, which the host
             // API relabels behind the active sites of their sublattice; the field covers them all)
             const int nfield = kp.ew_nact;
-            if (lean && t->has_ewald && kp.ew_act_base == sbase && nfield >= nact &&
-                (nfield == nact || getenv("SMOLMC_FIELD_ACTIVE_ONLY") == nullptr) &&
-                getenv("SMOLMC_NO_EWALD_FIELD") == nullptr) {
+            if (lean && t->has_ewald && kp.ew_act_base == sbase && nfield >= nact && !smolmc_env(ENV_NO_EWALD_FIELD)) {
                 const size_t with_field = h->lean_lds + (size_t)4 * nfield * 8;
                 // charge / diagonal term per species code must not depend on the site
                 bool uniform = kp.ew_W <= 8;
@@ -1647,18 +1643,14 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                 }
             }
             // Wang-Landau with the Ewald term: mc_wl_kernel takes it from the field in LDS only
-            // (also what the round-2 kernel SMOLMC_WL_V2 cannot do: no Ewald, no mu)
             if (lean && wl && t->has_ewald && !lp.ew_field) lean = false;
-            if (lean && wl && (t->has_ewald || t->has_mu || table_wl) && getenv("SMOLMC_WL_V2") != nullptr) lean = false;
             // one wave per workgroup (occupancy at LDS address 0, 32-bit index rows, a private
             // copy of the tables): Metropolis flips / swaps without Ewald term or bias, when 16
             // such workgroups still fit a CU
             if (lean && !wl && !t->has_ewald && !t->bias_type && !h->lean_kf && cfg->step_type != SMOLMC_STEP_TABLE_FLIP &&
-                getenv("SMOLMC_NO_SOLO") == nullptr) {
+                !smolmc_env(ENV_NO_SOLO)) {
                 const size_t pw = ((size_t)lp.Nlds + 64 * 8 + 15) & ~(size_t)15;
-                // (SMOLMC_EXP_F32TAB: room for the float32 shadow tables of the -DSMOLMC_EXP_F32TAB experiment build)
-                const size_t solo_lds = pw + ((size_t)lp.dt_len + 24) * 8 +
-                                        (getenv("SMOLMC_EXP_F32TAB") ? (((size_t)lp.dt_len * 4 + 15) & ~(size_t)15) : 0);
+                const size_t solo_lds = pw + ((size_t)lp.dt_len + 24) * 8;
                 if (solo_lds * 16 <= 160 * 1024 - 16 * 256) {
                     std::vector<uint32_t> wide(h->lean_idx_host.begin(), h->lean_idx_host.end());
                     if (dev_upload(h, wide.data(), wide.size(), &lp.idx32)) return bail(1);
@@ -1671,7 +1663,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                     int cus = 0;
                     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 256;
                     if ((long)cfg->n_replicas > 16L * cus && solo_lds * 24 <= 160 * 1024 - 24 * 256 &&
-                        getenv("SMOLMC_NO_OCC6") == nullptr)
+                        !smolmc_env(ENV_NO_OCC6))
                         h->lean_occ = 6;
                 }
             }
@@ -1699,7 +1691,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                     int cus = 0; // (fewer walkers than 8 per CU: four-walker workgroups spread over more CUs)
                     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 256;
                     if (!wl && lds8 <= 160 * 1024 && h->lean_lds > 40 * 1024 && cfg->n_replicas % 8 == 0 &&
-                        (long)cfg->n_replicas >= 8L * cus && getenv("SMOLMC_TABLE_WPB4") == nullptr) {
+                        (long)cfg->n_replicas >= 8L * cus) {
                         h->lean_wpb = 8;
                         h->lean_lds_wpb8 = lds8;
                     }
@@ -1711,15 +1703,15 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
         const bool table = cfg->step_type == SMOLMC_STEP_TABLE_FLIP;
         // (MCBias: every bias type with flips or swaps, and since round 6 with TableFlip: mc_table_multi_kernel<..., BIAS>;
         // SMOLMC_NO_TABLE_BIAS: A/B switch)
-        const bool multi_bias_ok = !t->bias_type || cfg->step_type != SMOLMC_STEP_TABLE_FLIP || getenv("SMOLMC_NO_TABLE_BIAS") == nullptr;
+        const bool multi_bias_ok = !t->bias_type || cfg->step_type != SMOLMC_STEP_TABLE_FLIP || !smolmc_env(ENV_NO_TABLE_BIAS);
         // Wang-Landau on this layout (round 5; mc_lean_multi_kernel<..., WLK>): any number of classes the
         // layout takes and any update_period -- what mc_wl_kernel (one class, update_period 1) leaves.  The
         // Wang-Landau TableFlip: mc_table_multi_kernel<..., WLT> (round 6) with one correlation function per orbit, the
         // universal kernel otherwise.  SMOLMC_NO_WL_MULTI, SMOLMC_NO_TABLE_WL: A/B switches.
-        const int wl_sum_mode = (cfg->wl_update_period == 1 && getenv("SMOLMC_WL_RUNNING_MEAN") == nullptr) ? 1 : 0;
-        const bool multi_table_wl_ok = !h->lean_kf && getenv("SMOLMC_NO_TABLE_WL") == nullptr;
+        const bool multi_table_wl_ok = !h->lean_kf && !smolmc_env(ENV_NO_TABLE_WL);
         const bool multi_wl_ok = !wl || ((!table || multi_table_wl_ok) && h->F <= 63 && cfg->wl_check_period < (1ll << 31) &&
-                                         cfg->wl_update_period < (1ll << 31) && getenv("SMOLMC_NO_WL_MULTI") == nullptr);
+                                         cfg->wl_update_period < (1ll << 31) && !smolmc_env(ENV_NO_WL_MULTI));
+        const bool multi_env_off = smolmc_env(ENV_FORCE_GENERAL) || smolmc_env(ENV_NO_LEAN_MULTI);
         // (why a model with lean tables runs neither lean family: the first condition that fails, for smolmc_kernel_info)
         if (!lean && h->lean_tables)
             h->lean_reason = (h->lean_kf && !wl) ? "several correlation functions per orbit (KF kernel) on a model outside the single-class lean shape"
@@ -1728,9 +1720,9 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                              : Fk > 64 ? "more than 64 features"
                              : t->n_sublattices > 4 ? "more than 4 active sublattices"
                              : (t->has_ewald && !kp.ew_field) ? "Ewald matrix that does not factorise into site charges (no potential field)"
-                             : (getenv("SMOLMC_FORCE_GENERAL") || getenv("SMOLMC_NO_LEAN_MULTI")) ? "environment override" : "";
+                             : multi_env_off ? "environment override" : "";
         if (!lean && h->lean_tables && (!h->lean_kf || wl) && multi_wl_ok && multi_bias_ok && Fk <= 64 && t->n_sublattices <= 4 && (!t->has_ewald || kp.ew_field) &&
-            getenv("SMOLMC_FORCE_GENERAL") == nullptr && getenv("SMOLMC_NO_LEAN_MULTI") == nullptr) {
+            !multi_env_off) {
             LeanParams &lp = h->lp;
             const int ns = t->n_sublattices;
             bool ok = true;
@@ -1744,7 +1736,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                 auto no = [&](const char *why) { if (ok) h->lean_reason = why; ok = false; };
                 if (na <= 0 || ncod < 2 || ncod > 8) no("an active sublattice of fewer than 2 or more than 8 species");
                 for (int i = 0; ok && i < na; ++i)
-                    if (t->sub_active_sites[a0 + i] != sb + i) no("the active sites of a sublattice are not one site range (Ensemble.make_tables(contiguous=True) relabels them)");
+                    if (t->sub_active_sites[a0 + i] != sb + i) no("the active sites of a sublattice are not one site range (they could not be renumbered into one, or SMOLMC_NO_SITE_RELABEL)");
                 {   // (codes other than 0 .. n-1 -- a sublattice split by species -- under canonical swaps only: see the single-class path)
                     bool default_codes = true;
                     int top = 0;
@@ -1753,7 +1745,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                         top = std::max(top, (int)t->sub_codes[t->sub_code_ptr[k] + c]);
                     }
                     if (ok && !default_codes) {
-                        if (cfg->step_type == SMOLMC_STEP_SWAP && top < 8 && ncod >= 2 && getenv("SMOLMC_NO_SWAP_ANY_CODES") == nullptr) ncod = top + 1;
+                        if (cfg->step_type == SMOLMC_STEP_SWAP && top < 8 && ncod >= 2) ncod = top + 1;
                         else no("a sublattice whose species codes are not 0 .. n-1 (split by species) under a step type that draws codes");
                     }
                 }
@@ -1856,10 +1848,10 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                 // per walker) the LDS copy measured 9.6 against 7.4 us per step
                 // (Wang-Landau accepts three steps of four: the field update is the step, the LDS copy pays for flips too)
                 if ((long)waves * cus >= (long)cfg->n_replicas || ((cfg->step_type == SMOLMC_STEP_SWAP || wl) && waves >= 8) ||
-                    getenv("SMOLMC_MULTI_PHI_LDS") != nullptr)
+                    smolmc_env(ENV_MULTI_PHI_LDS))
                     phi_lds = waves > 0;
             }
-            if (getenv("SMOLMC_MULTI_PHI_HBM") != nullptr) phi_lds = false;
+            if (smolmc_env(ENV_MULTI_PHI_HBM)) phi_lds = false;
             const size_t per_wave = base_wave + (phi_lds ? (size_t)kp.ew_nact * 8 : 0);
             int wpb = 0;
             layout(per_wave, wpb);
@@ -1882,8 +1874,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                     lp.charge = kp.charge;
                 }
                 if (t->has_mu) lp.fast_eps += 4.0 * mmax * ldexp(1.0, -19);
-                if (getenv("SMOLMC_NO_FAST_ACCEPT")) lp.fast_eps = 0.0;
-                if (const char *sc = getenv("SMOLMC_FAST_EPS_SCALE")) lp.fast_eps *= atof(sc);
+                if (const char *sc = smolmc_env(ENV_FAST_EPS_SCALE)) lp.fast_eps *= atof(sc);
                 lp.m_ncls = h->lean_ncls; lp.m_nsub = ns; lp.m_ndims = ndims;
                 if (table) {
                     std::vector<double> ln((size_t)max_nact + 1, 0.0);
@@ -1923,7 +1914,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
                 h->lean_multi = true;
             }
         }
-        if (getenv("SMOLMC_DEBUG"))
+        if (smolmc_env(ENV_DEBUG))
             fprintf(stderr, "[smolmc] lean=%d tables=%d nslot=%d mm=%d lds=%zu ew=%d compact=%d field=%d nact=%d "
                             "ew_nact=%d ew_act_base=%d sbase=%d general: nslot=%d mm=%d lds=%zu\n",
                     (int)lean, (int)h->lean_tables, h->lean_nslot, h->lean_mm, h->lean_lds, t->has_ewald,
@@ -1990,8 +1981,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
             }
             if (rec_e.empty()) { URecE e; memset(&e, 0, sizeof(e)); rec_e.push_back(e); }
             up.n_recs_e = (int)rec_e.size();
-            up.dict_lds = up.n_recs_e <= SMOLMC_UNIV_DICT_RECS && up.tens_len <= SMOLMC_UNIV_DICT_TENS && h->F <= SMOLMC_UNIV_DICT_NAT &&
-                          getenv("SMOLMC_UNIV_NO_DICT") == nullptr;
+            up.dict_lds = up.n_recs_e <= SMOLMC_UNIV_DICT_RECS && up.tens_len <= SMOLMC_UNIV_DICT_TENS && h->F <= SMOLMC_UNIV_DICT_NAT;
             if (nloc > 0x7fffffffll || nrows > 0x7fffffffull) return bail(fail("more than 2^31 local cluster rows"));
             std::vector<uint32_t> row_ptr((size_t)t->num_sites + 1, 0);
             std::vector<URow> rows((size_t)std::max<uint64_t>(nrows, 1));
@@ -2013,28 +2003,10 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
             for (int s = 0; s < t->num_sites; ++s)
                 if (row_ptr[(size_t)s + 1] - row_ptr[(size_t)s] != (uint32_t)up.rows_uniform) up.rows_uniform = 0;
             const URow *d_rows = nullptr;
-            const URow16 *d_rows16 = nullptr;
-            // (experiment build + SMOLMC_UNIV_ROWS16=1: measured on config 2 forced onto this kernel, the 16-byte rows cut the
-            // fetched bytes 25.0 -> 8.7 GB per launch of 4096 x 2000 swap steps and COST 4 % of the rate -- 11 % on config
-            // 8 -- because the kernel is VALU-bound and the unpacking is six more vector instructions per row)
-#ifdef SMOLMC_UNIV_ROWS16
-            up.rows16 = (t->num_sites <= 65535 && getenv("SMOLMC_UNIV_ROWS16") != nullptr) ? 1 : 0;
-#else
-            up.rows16 = 0; // (the kernels of the default build do not read 16-byte rows: make EXTRA=-DSMOLMC_UNIV_ROWS16)
-#endif
-            if (up.rows16) {
-                std::vector<URow16> r16(rows.size());
-                for (size_t i = 0; i < rows.size(); ++i) {
-                    for (int k = 0; k < SMOLMC_MAX_CLUSTER_SITES; ++k) r16[i].x[k] = (uint16_t)rows[i].x[k];
-                    r16[i].rec_lo = (uint16_t)((uint32_t)rows[i].rec & 0xffffu);
-                    r16[i].rec_hi = (uint16_t)((uint32_t)rows[i].rec >> 16);
-                }
-                if (dev_upload(h, r16.data(), r16.size(), &d_rows16)) return bail(1);
-            } else if (dev_upload(h, rows.data(), rows.size(), &d_rows)) return bail(1);
-            if (dev_upload(h, row_ptr.data(), row_ptr.size(), &up.row_ptr) ||
+            if (dev_upload(h, rows.data(), rows.size(), &d_rows) || dev_upload(h, row_ptr.data(), row_ptr.size(), &up.row_ptr) ||
                 dev_upload(h, rec_e.data(), rec_e.size(), &up.recs_e))
                 return bail(1);
-            up.rows = up.rows16 ? (const uint4 *)d_rows16 : (const uint4 *)d_rows;
+            up.rows = (const uint4 *)d_rows;
         }
         if (cfg->step_type == SMOLMC_STEP_TABLE_FLIP) {
             if (t->n_flip_vectors <= 0 || !t->flip_table || !t->flip_weights)
@@ -2084,14 +2056,14 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
         }
         // per-wave LDS: step scratch (flips, counts, weights, a-priori factors, running sums: 2464 B) + the occupancy when it fits
         // (+ the step's feature deltas, one cell per cluster feature, while that stays small)
-        up.dfeat_cells = (h->Fce <= 1024 && getenv("SMOLMC_UNIV_TWO_PASS") == nullptr) ? (h->Fce + 1) / 2 * 2 : 0;
+        up.dfeat_cells = h->Fce <= 1024 ? (h->Fce + 1) / 2 * 2 : 0;
         up.acc_cells = up.dfeat_cells ? (h->F + 1) / 2 * 2 : 0;
         up.lds_shared = up.dict_lds ? SMOLMC_UNIV_DICT_BYTES : 0;
         auto lay_out = [&]() {
             const size_t scratch = (cfg->step_type == SMOLMC_STEP_TABLE_FLIP ? SMOLMC_UNIV_SCRATCH_TABLE : SMOLMC_UNIV_SCRATCH) +
                                    (((size_t)up.dfeat_cells << up.dfeat_shift) + (size_t)up.acc_cells) * 8,
                          with_occ = (scratch + (size_t)h->Npad + 15) & ~(size_t)15;
-            up.occ_lds = with_occ <= 160 * 1024 - 256 && getenv("SMOLMC_UNIV_OCC_HBM") == nullptr;
+            up.occ_lds = with_occ <= 160 * 1024 - 256 && !smolmc_env(ENV_UNIV_OCC_HBM);
             up.lds_per_wave = (int)(up.occ_lds ? with_occ : scratch);
             h->univ_wpb = 4;
             while (h->univ_wpb > 1 && (size_t)up.lds_shared + (size_t)up.lds_per_wave * h->univ_wpb > 64 * 1024) h->univ_wpb /= 2;
@@ -2100,7 +2072,7 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
         // twelve walkers per CU, the workgroup within a quarter of the CU's LDS (a workgroup of 40.1 KB halves the resident
         // walkers of config 2: 1.3e9 -> 8.1e8 flips/s)
         up.dfeat_shift = 0;
-        while (up.dfeat_cells && getenv("SMOLMC_UNIV_NO_COPIES") == nullptr && up.dfeat_shift < 3 && ((size_t)up.dfeat_cells << (up.dfeat_shift + 1)) <= 512) up.dfeat_shift++;
+        while (up.dfeat_cells && up.dfeat_shift < 3 && ((size_t)up.dfeat_cells << (up.dfeat_shift + 1)) <= 512) up.dfeat_shift++;
         lay_out();
         const bool crowded = (long long)cfg->n_replicas > 12ll * 256;
         auto too_big = [&]() { return crowded && h->univ_wpb == 4 && (size_t)up.lds_shared + (size_t)up.lds_per_wave * 4 > 40 * 1024; };
@@ -2412,8 +2384,9 @@ extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
         if (h->lean && h->lp.ew_field && h->lp.ew_gx && used + 40 < (size_t)n)
             snprintf(buf + used, (size_t)n - used, " gx=%dx%dx%dx%d", h->ew_gx_blocks, h->ew_gx_dims[0], h->ew_gx_dims[1],
                      h->ew_gx_dims[2]);
-        else if (h->lean && h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && used + 8 < (size_t)n)
-            snprintf(buf + used, (size_t)n - used, (h->lean_multi_wl || h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) ? "" : (getenv("SMOLMC_WL_V2") ? " wl=v2" : " wl=v3"));
+        else if (h->lean && h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && !h->lean_multi_wl &&
+                 h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP && used + 8 < (size_t)n) // (mc_wl_kernel)
+            strncat(buf, " wl=v3", (size_t)n - used - 1);
         if (h->lean && !h->lean_multi && h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP &&
             strlen(buf) + 16 < (size_t)n) // (mc_table_kernel<..., WLT>)
             strncat(buf, h->lp.wl.sum_mode ? " wl=table" : " wl=table-mean", (size_t)n - strlen(buf) - 1);
@@ -2421,6 +2394,16 @@ extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
         if (h->lean_multi_wl && strlen(buf) + 24 < (size_t)n) // (the Wang-Landau variant of the multi-class kernel)
             snprintf(buf + strlen(buf), (size_t)n - strlen(buf), h->lp.wl.sum_mode ? " wl=multi" : " wl=multi-mean");
         if (h->relabelled && strlen(buf) + 16 < (size_t)n) strncat(buf, " relabelled=1", (size_t)n - strlen(buf) - 1);
+        if (h->env_dispatch && strlen(buf) + 8 < (size_t)n) { // the dispatch switches this handle was created under
+            strncat(buf, " env=", (size_t)n - strlen(buf) - 1);
+            const char *sep = "";
+            for (int e = 0; e < ENV_COUNT; ++e)
+                if (h->env_dispatch >> e & 1u) {
+                    strncat(buf, sep, (size_t)n - strlen(buf) - 1);
+                    strncat(buf, smolmc_env_switches[e].name, (size_t)n - strlen(buf) - 1);
+                    sep = ",";
+                }
+        }
         // why the model runs neither lean family (the first condition that failed at smolmc_create)
         if (!h->lean && !h->lean_reason.empty() && strlen(buf) + h->lean_reason.size() + 16 < (size_t)n) {
             strncat(buf, " | not lean: ", (size_t)n - strlen(buf) - 1);
@@ -2560,7 +2543,7 @@ static int launch_mc(smolmc_handle *h, const KParams &kp, int replay) {
 // 0: slot q runs walker q.  Ranks by beta ascending (hottest first), ties by walker index; built on
 // the host whenever the temperatures changed (one 8 B-per-walker read-back per exchange sweep).
 static int update_walker_order(smolmc_handle *h, LeanParams &lp) {
-    const char *env = getenv("SMOLMC_WALKER_ORDER"); // (read at every launch: tests switch it)
+    const char *env = smolmc_env(ENV_WALKER_ORDER); // (read at every launch: tests switch it)
     const int mode = env ? atoi(env) : 1;
     if (mode != h->order_mode) h->order_dirty = true;
     h->order_mode = mode;
@@ -2637,10 +2620,8 @@ static int launch_lean(smolmc_handle *h, LeanParams lp, int64_t nsteps) {
     if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) // (single-class layout)
         return h->lean_nslot == 2 ? smolmc_launch_table_wl_2(h, lp) : smolmc_launch_table_wl_4(h, lp);
     if (h->lean_kf) return h->lean_nslot == 2 ? smolmc_launch_lean_corr_2(h, lp) : smolmc_launch_lean_corr_4(h, lp);
-    // Wang-Landau: the dedicated kernel (mc_wl.h); SMOLMC_WL_V2 keeps round 2's variant of
-    // mc_lean_kernel reachable for A/B runs
-    if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP &&
-        getenv("SMOLMC_WL_V2") == nullptr)
+    // Wang-Landau: the dedicated kernel (mc_wl.h)
+    if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP)
         return h->lean_nslot == 2 ? smolmc_launch_wl_2(h, lp) : smolmc_launch_wl_4(h, lp);
     return h->lean_nslot == 2 ? smolmc_launch_lean_2(h, lp) : smolmc_launch_lean_4(h, lp);
 }
@@ -2680,10 +2661,11 @@ static int run_steps(smolmc_handle *h, int64_t nsteps, const SampleBufs &smp) {
         // the lean kernels count steps in 32 bits: launches are split at 2^30 steps (on a
         // sample boundary when samples are being recorded)
         int64_t chunk = (int64_t)1 << 30;
-        if (const char *c = getenv("SMOLMC_LAUNCH_CHUNK")) chunk = std::max<int64_t>(1, atoll(c)); // test hook
+        const char *chunk_env = smolmc_env(ENV_LAUNCH_CHUNK); // test hook
+        if (chunk_env) chunk = std::max<int64_t>(1, atoll(chunk_env));
         if (smp.every) {
             if (smp.every > chunk) {
-                if (getenv("SMOLMC_LAUNCH_CHUNK")) chunk = smp.every;
+                if (chunk_env) chunk = smp.every;
                 else return fail("thin_by must be <= 2^30 steps");
             }
             chunk -= chunk % smp.every;
@@ -2776,7 +2758,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
     if ((flags & SMOLMC_SAMPLE_BIAS) && !h->kp.bias_type) return fail("the model has no bias term");
     if ((flags & SMOLMC_SAMPLE_WL) && !wl) return fail("handle is not a Wang-Landau kernel");
-    if (thin_by > ((int64_t)1 << 30) && h->lean && getenv("SMOLMC_LAUNCH_CHUNK") == nullptr)
+    if (thin_by > ((int64_t)1 << 30) && h->lean && !smolmc_env(ENV_LAUNCH_CHUNK))
         return fail("thin_by must be <= 2^30 steps"); // (before a slot is touched: run_steps would refuse it)
     if (!h->copy_stream) HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
     // The slot this block goes to is the older one.  When it still holds a block nobody fetched, so does the other
@@ -2819,7 +2801,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     // snapshot path -- one launch + one snapshot kernel per sample -- is left to Wang-Landau (per-walker L and L x F
     // arrays) and to biased handles on mc_kernel / the universal kernel.  SMOLMC_NO_INKERNEL_BIAS: A/B switch.
     const bool inkernel_bias = (flags & SMOLMC_SAMPLE_BIAS) && !(flags & SMOLMC_SAMPLE_WL) && h->lean && !h->univ &&
-                               h->lp.bias_type && getenv("SMOLMC_NO_INKERNEL_BIAS") == nullptr;
+                               h->lp.bias_type && !smolmc_env(ENV_NO_INKERNEL_BIAS);
     const bool snapshot_path = (flags & SMOLMC_SAMPLE_WL) || ((flags & SMOLMC_SAMPLE_BIAS) && !inkernel_bias);
     const bool lazy_rows = is_lazy(h) && !snapshot_path;
     size_t download = at, o_scal = 0, o_occ_int = w.o_occ;
@@ -3020,17 +3002,14 @@ extern "C" int smolmc_get_samples_ex(smolmc_handle *h, double *enthalpy, double 
 }
 
 // lean replay kernels that exist: Metropolis flips / swaps (plain, KF, with MCBias), multi-sublattice,
-// Wang-Landau; TableFlip handles have their own (smolmc_table_replay_available)
+// Wang-Landau; TableFlip handles have their own
 static bool smolmc_lean_replay_takes(const smolmc_handle *h) {
     if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) return false;
     if (h->lean_multi_wl && h->lean_kf) return false; // (no replay instantiation of the KFW kernel: mc_kernel / the universal kernel)
-    if (h->lp.bias_type) return SMOLMC_HAVE_BIAS_REPLAY != 0;
     return true;
 }
-static bool smolmc_table_replay_available() { return SMOLMC_HAVE_TABLE_REPLAY != 0; }
 static int smolmc_launch_lean_replay(smolmc_handle *h, const LeanParams &lp) {
     const bool wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
-#if SMOLMC_HAVE_TABLE_REPLAY
     if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) {
         LeanParams q = lp;
         TRY(update_walker_order(h, q));
@@ -3039,13 +3018,10 @@ static int smolmc_launch_lean_replay(smolmc_handle *h, const LeanParams &lp) {
                                       : (h->lean_nslot == 4 ? smolmc_launch_multi_table_replay_4(h, q) : smolmc_launch_multi_table_replay_8(h, q));
         return h->lean_nslot == 2 ? smolmc_launch_table_replay_2(h, q) : smolmc_launch_table_replay_4(h, q);
     }
-#endif
-#if SMOLMC_HAVE_BIAS_REPLAY
     if (lp.bias_type && h->lean_multi)
         return h->lean_nslot == 2 ? smolmc_launch_multi_bias_replay_2(h, lp)
                                   : (h->lean_nslot == 4 ? smolmc_launch_multi_bias_replay_4(h, lp) : smolmc_launch_multi_bias_replay_8(h, lp));
     if (lp.bias_type) return h->lean_nslot == 2 ? smolmc_launch_lean_bias_replay_2(h, lp) : smolmc_launch_lean_bias_replay_4(h, lp);
-#endif
     if (h->lean_multi_wl)
         return h->lean_nslot == 2 ? smolmc_launch_multi_wl_replay_2(h, lp)
                                   : (h->lean_nslot == 4 ? smolmc_launch_multi_wl_replay_4(h, lp) : smolmc_launch_multi_wl_replay_8(h, lp));
@@ -3090,18 +3066,19 @@ extern "C" int smolmc_replay(smolmc_handle *h, int64_t nsteps, const int32_t *st
     // take (more than two flips on a Flip / Swap handle, a given a-priori factor there), universal
     // handles and SMOLMC_REPLAY_UNIVERSAL take the universal kernel; SMOLMC_REPLAY_GENERAL: mc_kernel.
     const bool two_flip_ok = max_flips <= 2 && !priori_given && !table;
-    const bool want_general = getenv("SMOLMC_REPLAY_GENERAL") != nullptr && two_flip_ok && h->general_ok;
+    const bool replay_universal = smolmc_env(ENV_REPLAY_UNIVERSAL) != nullptr;
+    const bool want_general = smolmc_env(ENV_REPLAY_GENERAL) && two_flip_ok && h->general_ok;
     // (the lean TableFlip replay kernels pick sites without replacement like the usher: a record with a repeated
     // site -- valid for the boundary -- takes the universal kernel, which evaluates it flip by flip)
     // (a biased or Wang-Landau TableFlip handle has no REPLAY instantiation: the universal kernel replays its records)
-    const bool lean_table_replay = h->lean && table && smolmc_table_replay_available() && nsteps < ((int64_t)1 << 30) && !repeated_site &&
+    const bool lean_table_replay = h->lean && table && nsteps < ((int64_t)1 << 30) && !repeated_site &&
                                    !h->lp.bias_type && h->cfg.kernel_type != SMOLMC_KERNEL_WANGLANDAU;
     // (a Flip handle's own kernel takes single flips: records of two flips go to mc_kernel / the universal kernel)
     const bool lean_shape_ok = two_flip_ok && (h->cfg.step_type != SMOLMC_STEP_FLIP || max_flips <= 1);
-    const bool lean_replay = h->lean && !want_general && nsteps < ((int64_t)1 << 30) && getenv("SMOLMC_REPLAY_UNIVERSAL") == nullptr &&
+    const bool lean_replay = h->lean && !want_general && nsteps < ((int64_t)1 << 30) && !replay_universal &&
                              ((lean_shape_ok && smolmc_lean_replay_takes(h)) || lean_table_replay);
-    const bool general_replay = !lean_replay && !h->univ && two_flip_ok && h->general_ok && getenv("SMOLMC_REPLAY_UNIVERSAL") == nullptr;
-    if (getenv("SMOLMC_DEBUG"))
+    const bool general_replay = !lean_replay && !h->univ && two_flip_ok && h->general_ok && !replay_universal;
+    if (smolmc_env(ENV_DEBUG))
         fprintf(stderr, "[smolmc] replay path=%s max_flips=%d priori_given=%d\n",
                 lean_replay ? (table ? "lean-table" : "lean") : (general_replay ? "general" : "universal"), max_flips, (int)priori_given);
     int *d_steps = nullptr, *d_err = nullptr;

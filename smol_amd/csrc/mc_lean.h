@@ -55,25 +55,6 @@ __device__ __forceinline__ float wave_sum_f32_uniform(float v) {
     return total;
 }
 
-// The same sum on the matrix pipe: two v_mfma_f64_16x16x4_f64 with B = ones
-// (D[i][j] = sum_k A[i][k], lane l holds A[l & 15][l >> 4]; C/D: col = lane & 15,
-// row = (lane >> 4) + 4 * reg) and three VALU adds in between.  Frees ~19 VALU issue
-// slots per step but MEASURED SLOWER (9.87 ms vs 8.46 ms per 10^4 steps, same session):
-// the two dependent f64 MFMAs lengthen the per-step dependency chain more than the VALU
-// slots they free.  Kept behind -DSMOLMC_MFMA_REDUCE as a documented negative result.
-typedef double smolmc_v4d __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ double wave_sum_mfma(double v) {
-    const smolmc_v4d z = {0.0, 0.0, 0.0, 0.0};
-    const smolmc_v4d d = __builtin_amdgcn_mfma_f64_16x16x4f64(v, 1.0, z, 0, 0, 0);
-    const double t = (d[0] + d[1]) + (d[2] + d[3]);
-    const smolmc_v4d d2 = __builtin_amdgcn_mfma_f64_16x16x4f64(t, 1.0, z, 0, 0, 0);
-    return d2[0];
-}
-#ifdef SMOLMC_MFMA_REDUCE
-#define LEAN_WAVE_SUM wave_sum_mfma
-#else
-#define LEAN_WAVE_SUM wave_sum_all
-#endif
 
 // sum over the changeable sites k != s of q(k, occ_k) * G[s][k] (lane partial), eight sites
 // per lane in flight so that the dependent latencies (index -> LDS species byte -> charge)
@@ -338,9 +319,7 @@ typedef __attribute__((address_space(3))) double lds_f64_t;
 #if defined(__HIP_DEVICE_COMPILE__)
 #define SMOLMC_LDS_U8(a) (*(lds_u8_t *)(a))
 #define SMOLMC_LDS_F64(a) (*(const lds_f64_t *)(a))
-#define SMOLMC_LDS_F32(a) (*(const __attribute__((address_space(3))) float *)(a))
 #else
-#define SMOLMC_LDS_F32(a) (*(const float *)(uintptr_t)(a))
 #define SMOLMC_LDS_U8(a) (*(uint8_t *)(uintptr_t)(a))
 #define SMOLMC_LDS_F64(a) (*(const double *)(uintptr_t)(a))
 #endif
@@ -410,20 +389,6 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     double *phi = (double *)(wbase + P.Nlds + 64 * 8 + 64);     // Ewald potential field [ew_nact]
     const int swa = P.swz_a, swm = P.swz_m, swb = P.swz_b;
     for (int i = threadIdx.x; i < P.dt_len; i += blockDim.x) s_dt[i] = P.dt[i];
-#ifdef SMOLMC_EXP_F32TAB
-    // EXPERIMENT (the round-2 review's "one bounded experiment" on the headline kernel): a float32
-    // shadow of the delta tables for the decision, float64 entries read on accepted steps only.
-    // Solo layout, swap steps, no Ewald / bias / correlation functions; the host adds the shadow's
-    // LDS when SMOLMC_EXP_F32TAB is set in the environment (engine.hip).
-    constexpr bool F32TAB = SOLO && STEP == SMOLMC_STEP_SWAP && !HAS_EW && !WL && !BIAS && KF == 0 && !REPLAY;
-    const uint32_t sh_off = dt_off + (uint32_t)(P.dt_len + 24) * 8u; // shadow entry of the double at LDS address a: sh_off + (a - dt_off) / 2
-    if (F32TAB) {
-        float *s_dt32 = (float *)(smem + sh_off);
-        for (int i = threadIdx.x; i < P.dt_len; i += blockDim.x) s_dt32[i] = (float)P.dt[i];
-    }
-#else
-    constexpr bool F32TAB = false;
-#endif
     if (HAS_MU && threadIdx.x < 8) s_mu[threadIdx.x] = threadIdx.x < P.ncodes ? P.mu_row[threadIdx.x] : 0.0;
     if (HAS_EW && ew_field && threadIdx.x < 8) {
         s_q[threadIdx.x] = P.ew_qrow[threadIdx.x];
@@ -450,11 +415,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
 
     // single flips with the potential field and the compressed site kernel: the E8 entries of the
     // first 27 groups of field entries, lane constants of the launch (field_sweep_gx_pre27)
-#ifdef SMOLMC_NO_EWALD_E8REG // A/B switch
-    constexpr bool EPRE = false;
-#else
     constexpr bool EPRE = HAS_EW && STEP == SMOLMC_STEP_FLIP && !REPLAY;
-#endif
     uint32_t ereg[27] = {};
     bool epre_on = false;
     if (EPRE) {
@@ -526,9 +487,6 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             }
         }
     };
-#ifdef SMOLMC_EXP_CLOCK // experiment: shader clock during the launch (s_memtime vs the 100 MHz s_memrealtime)
-    const long long ck0 = clock64(), wk0 = wall_clock64();
-#endif
     double H = P.enthalpy[r];
     const double nbeta = WL ? 0.0 : -P.beta[r];
     double wl_m = WL ? P.wl.m[r] : 0.0;
@@ -634,10 +592,6 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     auto wl_pend_sum = [&]() -> double {
         return ((wl_pc[0] + wl_pc[1]) + (wl_pc[2] + wl_pc[3])) + ((wl_pc[4] + wl_pc[5]) + (wl_pc[6] + wl_pc[7]));
     };
-#ifdef SMOLMC_EXP_PHASES // experiment: shader cycles per phase of a step (walker 0 prints the averages)
-    long long lph[5] = {0, 0, 0, 0, 0};
-    long long lph_t = clock64();
-#endif
     uint32_t steps_left = (uint32_t)P.steps; // the host splits launches at 2^30 steps
     while (steps_left != 0u) {
         // -------- random words (generated 16 steps at a time) --------
@@ -666,7 +620,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                     // accept <=> -beta dH > log u <=> dH < log(u) / -beta =: thr  (dH <= 0 always
                     // passes since thr >= 0); certain on either side of thr -+ eps
                     const double thr = logu * inv_nbeta; // (a rounding of the band centre: covered by eps)
-                    const double eps = (F32TAB ? 2.0 : 1.0) * P.fast_eps + 1e-6 * fabs(thr); // (shadow tables: + sum|w| max|dt| 2^-23, a sixteenth of fast_eps)
+                    const double eps = P.fast_eps + 1e-6 * fabs(thr);
                     thr_lo = P.fast_eps > 0.0 ? (float)(thr - eps) : -INFINITY;
                     thr_hi = P.fast_eps > 0.0 ? (float)(thr + eps) : INFINITY;
                 }
@@ -699,12 +653,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         int l64 = (int)(step & 63ull); // lane of this step's acceptance uniform / thresholds
         do {
         // site of the next step (depends only on random words; its index row is fetched below)
-#ifndef SMOLMC_NO_SETPRIO
         __builtin_amdgcn_s_setprio(1); // wave priority rises through the step, see the decision below
-#endif
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); lph[0] += tn - lph_t; lph_t = tn; }
-#endif
         int s1n, a1n;
         int rq1 = 0, rq2 = -1, rq3 = 0; // replay: code1, site2, code2 of this step's record
         bool rp_empty = false;
@@ -831,40 +780,23 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
 
         // data-dependent row of site 2: issued before flip 1 is evaluated (s2 == s1 for the
         // rare empty step, the loaded row is then unused)
-#ifndef SMOLMC_NO_SETPRIO
         __builtin_amdgcn_s_setprio(2);
-#endif
         RowWords<NW> row2 = row1;
         if (STEP == SMOLMC_STEP_SWAP) {
-#ifdef SMOLMC_EXP_ROW2 // timing experiment only: row of an early-known site (wrong results)
-            row2 = load_row<NW>(idx_rs, lane_voff, (uint32_t)s1n * SITE_BYTES);
-#else
             row2 = load_row<NW>(idx_rs, lane_voff, (uint32_t)s2 * SITE_BYTES);
-#endif
         }
         if (WL) {
             unsafeAtomicAdd(wl_pend + lane, wl_pend_sum());
         }
 
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); lph[1] += tn - lph_t; lph_t = tn; }
-#endif
         // -------- enthalpy delta ---------------------------------------------------
         // Swap: the second flip is the reverse species change of the first
         // (n2 == o1, o2 == n1), and the delta tables are antisymmetric in (old, new), so both
         // flips read the SAME (old, new) block -- its offset is added to the slot offsets once --
         // and the step's delta per slot is the difference of the two reads: one table offset
-        // add, one subtraction and one FMA per slot instead of two adds and two FMAs
-        // (SMOLMC_NO_SWAP_DIFF: the flip-by-flip form, kept for A/B runs).
-#ifdef SMOLMC_NO_SWAP_DIFF
-        constexpr bool DIFF = false;
-#else
+        // add, one subtraction and one FMA per slot instead of two adds and two FMAs.
         constexpr bool DIFF = STEP == SMOLMC_STEP_SWAP;
-#endif
         double e = 0.0, d1[NSLOT], d2[NSLOT];
-#ifdef SMOLMC_EXP_F32TAB
-        float t1f[NSLOT], ef32 = 0.0f;
-#endif
         uint32_t dp[NSLOT];
         uint32_t ad1[NSLOT], ad2[NSLOT]; // KF: LDS addresses of the two decision reads
         {
@@ -875,12 +807,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                 if (DIFF) a = dp[it] = doff8[it] + pair1;
 #pragma unroll
                 for (int m = 0; m < MM; ++m) a += __umul24(st8[it][m], (uint32_t)occ_ld<SOLO>(occ, bounded(row_addr<SOLO, NW>(row1, it * MM + m), (uint32_t)P.Nlds)));
-                if (DIFF && F32TAB) {
-#ifdef SMOLMC_EXP_F32TAB
-                    ad1[it] = a;
-                    t1f[it] = SMOLMC_LDS_F32(sh_off + ((a - dt_off) >> 1));
-#endif
-                } else if (DIFF) {
+                if (DIFF) {
                     d1[it] = SMOLMC_LDS_F64(a);
                     if (KF) ad1[it] = a;
                 } else {
@@ -910,21 +837,14 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         if (STEP == SMOLMC_STEP_SWAP) {
             // the second flip sees the first (expansion.py:217-229): apply it tentatively in
             // LDS (undone below on rejection) instead of patching every gathered value
-#ifndef SMOLMC_EXP_NOTENT // timing experiment only when defined (wrong results)
             occ_st<SOLO>(occ, va1, (uint8_t)n1); // every lane stores the same byte: no exec juggling
-#endif
             const uint32_t pair2 = (uint32_t)o2 * snt8 + (uint32_t)n2 * nt8;
 #pragma unroll
             for (int it = 0; it < NSLOT; ++it) {
                 uint32_t a = DIFF ? dp[it] : doff8[it];
 #pragma unroll
                 for (int m = 0; m < MM; ++m) a += __umul24(st8[it][m], (uint32_t)occ_ld<SOLO>(occ, bounded(row_addr<SOLO, NW>(row2, it * MM + m), (uint32_t)P.Nlds)));
-                if (DIFF && F32TAB) {
-#ifdef SMOLMC_EXP_F32TAB
-                    ad2[it] = a;
-                    ef32 = fmaf((float)wgt[it], t1f[it] - SMOLMC_LDS_F32(sh_off + ((a - dt_off) >> 1)), ef32);
-#endif
-                } else if (DIFF) {
+                if (DIFF) {
                     d1[it] -= SMOLMC_LDS_F64(a); // D[(o2,n2)] = -D[(o1,n1)]: the step's delta of this slot
                     if (KF) ad2[it] = a;
                     e = fma(wgt[it], d1[it], e);
@@ -951,9 +871,6 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                 }
             }
         }
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); lph[2] += tn - lph_t; lph_t = tn; }
-#endif
         double dMu = 0.0;
         if (HAS_MU && nfl >= 1) {
             dMu = s_mu[n1] - s_mu[o1];
@@ -983,24 +900,11 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                 dB = -P.bias_pen * sq_new - (-P.bias_pen * sq_old);
             }
         }
-#ifdef SMOLMC_EXP_F32TAB
-        bool have_d1 = false;
-#endif
         // exact float64 decision (metropolis.py:31-49 / wanglandau.py:186-202)
         auto exact_decision = [&]() -> bool {
-#ifdef SMOLMC_EXP_F32TAB
-            if (F32TAB) { // the float64 deltas, now that they are needed
-#pragma unroll
-                for (int it = 0; it < NSLOT; ++it) {
-                    d1[it] = SMOLMC_LDS_F64(ad1[it]) - SMOLMC_LDS_F64(ad2[it]);
-                    e = fma(wgt[it], d1[it], e);
-                }
-                have_d1 = true;
-            }
-#endif
-            dH = LEAN_WAVE_SUM(e);
+            dH = wave_sum_all(e);
             if (HAS_EW) {
-                dEw = (ew_field ? 0.0 : LEAN_WAVE_SUM(ew_part)) + ew_uni;
+                dEw = (ew_field ? 0.0 : wave_sum_all(ew_part)) + ew_uni;
                 dH += P.ew_coef * dEw;
             }
             if (HAS_MU) dH -= dMu;
@@ -1032,19 +936,9 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         // merged, as acc = fma(sel, delta, acc) with the wave-uniform sel = 1.0 / 0.0 -- updating
         // them inside the accept branch makes the register allocator keep two copies and shuffle
         // them with v_mov_b64 on every path (~5 VALU per step)
-#ifdef SMOLMC_NO_SELACC
-        constexpr bool SELACC = false;
-#else
-        constexpr bool SELACC = DIFF && FAST && !BIAS && !F32TAB; // (measured: no gain for the flip / Ewald variants)
-#endif
+        constexpr bool SELACC = DIFF && FAST && !BIAS; // (measured: no gain for the flip / Ewald variants)
         uint32_t sel_hi = 0u; // high word of sel
         auto on_accept = [&]() {
-#ifdef SMOLMC_EXP_F32TAB
-            if (F32TAB && !have_d1) {
-#pragma unroll
-                for (int it = 0; it < NSLOT; ++it) d1[it] = SMOLMC_LDS_F64(ad1[it]) - SMOLMC_LDS_F64(ad2[it]);
-            }
-#endif
             if (KF) {
                 // the K correlation-function tables of each slot (global memory, L2-resident),
                 // read at the index the decision already computed: byte ad - doff8 inside table k
@@ -1087,17 +981,12 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                 }
             }
             if (STEP == SMOLMC_STEP_FLIP) occ_st<SOLO>(occ, va1, (uint8_t)n1);
-#ifdef SMOLMC_EXP_NOTENT
-            if (STEP == SMOLMC_STEP_SWAP) occ_st<SOLO>(occ, (uint32_t)a1, (uint8_t)n1);
-#endif
             if (STEP == SMOLMC_STEP_SWAP) occ_st<SOLO>(occ, (uint32_t)a2, (uint8_t)n2); // (n2 == o1 == occ[a1] when empty)
             if (HAS_EW && ew_field) {
                 if (STEP == SMOLMC_STEP_SWAP) {
                     if (dq1 != 0.0 || dq2 != 0.0) field_apply2(P, phi, lane, s1, dq1, s2, dq2);
                 } else if (dq1 != 0.0) {
-#ifndef SMOLMC_EXP_NOFIELD // timing experiment only when defined (wrong results)
                     field_apply<2, EPRE>(P, phi, lane, s1, dq1, ereg, epre_on);
-#endif
                 }
             }
             acc_mu += dMu;
@@ -1110,9 +999,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         };
         auto on_reject = [&]() {
             if (STEP == SMOLMC_STEP_SWAP) {
-#ifndef SMOLMC_EXP_NOTENT
             occ_st<SOLO>(occ, va1, (uint8_t)o1); // undo the tentative first flip
-#endif
             }
         };
         // Each outcome of the float32 pre-test runs its update directly (a merged
@@ -1126,15 +1013,9 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         // 4.73 depending on where level 1 starts; one constant level or bare scheduling barriers at
         // the same places: slower than nothing; the decision at the LOWEST level: 5.10); 0-3 % on
         // the other variants, -2 % at one wave per SIMD.
-#ifndef SMOLMC_NO_SETPRIO
         __builtin_amdgcn_s_setprio(3);
-#endif
         if (FAST && !BIAS) {
-#ifdef SMOLMC_EXP_F32TAB
-            const float ef = F32TAB ? ((HAS_MU && lane == 0) ? ef32 - (float)dMu : ef32) : (float)((HAS_MU && lane == 0) ? e - dMu : e);
-#else
             const float ef = (float)((HAS_MU && lane == 0) ? e - dMu : e);
-#endif
             const float S = wave_sum_f32_uniform(ef);
             const unsigned long long bit = 1ull << (REPLAY ? 0 : l64); // (replay: the thresholds are uniform)
             const bool ca = (__ballot(S < thr_lo) & bit) != 0ull;
@@ -1157,9 +1038,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         }
         s1 = s1n;
         a1 = a1n;
-#ifndef SMOLMC_NO_SETPRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         if (REPLAY) { // accept flag and running enthalpy of every step (what smolmc_replay returns)
             double lane_e = 0.0;
             if (FAST) {
@@ -1175,9 +1054,6 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             ridx++;
         }
 
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); lph[3] += tn - lph_t; lph_t = tn; }
-#endif
         if (WL) {
             // WangLandau._do_post_step (wanglandau.py:222-266)
             // the bin only moves on accepted steps, to the one computed by the accept test
@@ -1207,9 +1083,6 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             }
         }
 
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); lph[4] += tn - lph_t; lph_t = tn; }
-#endif
         l4 += 4;
         l64 += 1;
         } while (--chunk != 0u);
@@ -1254,19 +1127,6 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         }
     }
 
-#ifdef SMOLMC_EXP_CLOCK
-    if ((r == 0 || r == 2049) && lane == 0) {
-        const long long dc = clock64() - ck0, dw = wall_clock64() - wk0;
-        printf("walker %d: %lld shader cycles in %lld ticks of 10 ns -> %.1f MHz, %.1f cycles per step\n", r, dc, dw,
-               (double)dc / (double)dw * 100.0, (double)dc / (double)P.steps);
-    }
-#endif
-#ifdef SMOLMC_EXP_PHASES
-    if (r == 0 && lane == 0)
-        printf("lean phases (cycles per step): skeleton %.0f | proposal %.0f | gathers+tables %.0f | decision+update %.0f | post-step %.0f\n",
-               (double)lph[0] / (double)P.steps, (double)lph[1] / (double)P.steps, (double)lph[2] / (double)P.steps,
-               (double)lph[3] / (double)P.steps, (double)lph[4] / (double)P.steps);
-#endif
     // ---- write back ---------------------------------------------------------------
     if (HAS_EW && ew_field)
         for (int j = lane; j < P.ew_nact; j += 64) P.ew_phi[(size_t)r * P.ew_nact + j] = phi[j];
@@ -1641,11 +1501,7 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
     // accepted table step invalidates nothing: a hot walker wanders back and forth over a few positions and
     // recomputed both factors (a table read from L2 + a wave reduction each) after every accepted table step.
     // Several vectors: lane d / bit d hold direction d at the current counts, dropped when the counts change.
-#ifdef SMOLMC_NO_LP_LINE // A/B switch
-    const bool lp_line = false;
-#else
     const bool lp_line = P.tf_n == 1;
-#endif
     int kpos = 0;
     // Proposal batch: the proposals of 64 consecutive steps computed at once, lane l <-> step
     // (step & ~63) + l, all on the vector unit (the step-at-a-time proposal below is a chain of
@@ -1827,17 +1683,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
         }
     };
 
-#ifdef SMOLMC_EXP_PHASES // experiment: shader cycles per phase of a step (walker 0 prints the averages)
-    long long ph_acc[6] = {0, 0, 0, 0, 0, 0}, ph_cov[3] = {0, 0, 0}, ph_bat = 0, ph_prop[4] = {0, 0, 0, 0};
-    long long ph_t = clock64();
-#endif
-#ifdef SMOLMC_EXP_VGPREF // experiment, MEASURED SLOWER (not in the build): the cross terms of the NEXT step fetched a step ahead, at
-    // the end of this step (=1) or before its decision (=2).  Config 5 hot / cold ladder 10.23 / 6.47 ms per sweep -> 11.0 / 7.4
-    // either way: two more live VGPRs across the sweep (spills 4 -> 8) and three readlanes per step cost more than the read
-    // that -DSMOLMC_EXP_NOVG prices at 8 %.  Kept as a documented negative result, like wave_sum_mfma.
-    double vG_pref = 0.0;
-    uint32_t vG_tag = ~0u; // low word of the step vG_pref belongs to
-#endif
     for (uint32_t steps_left = (uint32_t)P.steps; steps_left != 0u; --steps_left, ++step) {
         // feasibility mask, weight sums of the directions: recomputed (here only: one copy of the
         // code) after the species counts changed; the batch's directions assume the old mask
@@ -1846,30 +1691,15 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
             compute_head();
             if (feas_now != feas_old) q_stale = ~0ull;
         }
-#ifdef SMOLMC_EXP_PHASES
-        const long long tb0 = clock64();
-#endif
         if (!REPLAY && __builtin_expect((uint32_t)(step & ~63ull) != q_base, 0)) propose_batch(step & ~63ull); // (first step of a launch)
         const int l6 = (int)(step & 63ull);
         const int l4 = (int)(step & 15ull) * 4;
         const uint32_t q_m = rdlane(q_meta, l6);
-#ifdef SMOLMC_NO_TABLE_BATCH // A/B switch: every step through the step-at-a-time proposal
-        const bool covered = false;
-#else
         const bool covered = !REPLAY && (q_m & 1u) != 0u && ((q_stale >> l6) & 1ull) == 0ull;
-#endif
         const uint32_t a01 = rdlane(q_s01, l6), a23 = rdlane(q_s23, l6), pk = rdlane(q_pack, l6);
         double lu = __hiloint2double((int)rdlane((uint32_t)__double2hiint(q_logu), l6),
                                      (int)rdlane((uint32_t)__double2loint(q_logu), l6));
-#ifdef SMOLMC_EXP_PHASES
-        ph_bat += clock64() - tb0;
-#endif
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[0] += tn - ph_t; ph_t = tn; }
-#endif
-#ifndef SMOLMC_NO_SETPRIO
         __builtin_amdgcn_s_setprio(1); // wave priority rises through the step (see mc_lean_kernel)
-#endif
 
         // flips of this step live lane-indexed: lane f holds flip f
         int vsite = 0, vnew = 0, vold = 0;
@@ -1882,14 +1712,12 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
         RowWords<NW> rows[4];
         double vG = 0.0;
         // G[si][sj] for the lanes that hold a flip pair: a random 8-byte read from the rows of the site kernel (24 MB
-        // for config 5) every step.  Timing without it (-DSMOLMC_EXP_NOVG, wrong results): -8 % per sweep; the same
+        // for config 5) every step.  Timing without it (an experiment build without the read, wrong results): -8 % per sweep; the same
         // value through the translation-compressed tables (E8 / S8, then gx: two dependent L2 reads) measured level on
         // the hot ladder and 4 % slower on the cold one -- the dependent chain is what costs, not where it ends.
         auto cross_G = [&](const uint32_t si, const uint32_t sj, const bool want) -> double {
             double g = 0.0;
-#ifndef SMOLMC_EXP_NOVG // timing experiment only when defined (wrong results)
             if (want) g = P.ew_G[(size_t)(si * ew_na_v) + (sj - (uint32_t)sbase)];
-#endif
             return g;
         };
         auto fetch_rows = [&]() {
@@ -1903,24 +1731,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
             }
         };
 
-#ifdef SMOLMC_EXP_VGPREF
-        auto prefetch_next_G = [&]() {
-        // the batch knows the sites of the next step; if that step stays covered (this step's marking is done) it takes
-        // the value from here instead of waiting for the read in its own evaluation
-        if (!REPLAY && has_ew && ew_field && l6 < 63) {
-            const uint32_t qn = rdlane(q_meta, l6 + 1);
-            const int nfn = (int)((qn >> 2) & 7u);
-            if ((qn & 1u) && !((q_stale >> (l6 + 1)) & 1ull) && nfn >= 2) {
-                const uint32_t b01 = rdlane(q_s01, l6 + 1), b23 = rdlane(q_s23, l6 + 1);
-                const uint32_t t0 = b01 & 0xffffu, t1 = b01 >> 16, t2 = nfn > 2 ? b23 & 0xffffu : t0, t3 = nfn > 3 ? b23 >> 16 : t0;
-                const int pi = lane >> 3, pj = lane & 7;
-                const uint32_t si = pi == 1 ? t1 : pi == 2 ? t2 : t3, sj = pj == 0 ? t0 : pj == 1 ? t1 : t2;
-                vG_pref = cross_G(si, sj, pj < pi && pi < nfn);
-                vG_tag = (uint32_t)step + 1u;
-            }
-        }
-        };
-#endif
         int vu = 0; // table step: lane c holds the change of the count of species c
         double log_priori = 0.0;
         // count changes (lane c: species c) of table direction d
@@ -1984,16 +1794,9 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
                 if (has_ew && ew_field) {
                     const int pi = lane >> 3, pj = lane & 7;
                     const uint32_t si = pi == 1 ? s1 : pi == 2 ? s2 : s3, sj = pj == 0 ? s0 : pj == 1 ? s1 : s2;
-#ifdef SMOLMC_EXP_VGPREF
-                    if (vG_tag == (uint32_t)step) vG = vG_pref;
-                    else
-#endif
                     vG = cross_G(si, sj, pj < pi && pi < nfl);
                 }
             }
-#ifdef SMOLMC_EXP_PHASES
-            ph_cov[0]++;
-#endif
         } else if (REPLAY) {
             // the recorded step: lane f <-> flip f
             const LeanParamsKernarg Q = rare_params();
@@ -2031,9 +1834,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
         word_batch();
         const uint32_t w_site = l4 == 0 ? w_site_carry : rdlane(W1, l4 - 4);
         bool do_swap = (double)rdlane(W0, l4) * (1.0 / 4294967296.0) < P.tf_sw;
-#ifdef SMOLMC_EXP_PHASES
-        if (q_m & 1u) ph_cov[1]++; else if (do_swap) ph_cov[2]++;
-#endif
         if (!do_swap) { // flip_weights_mask (math.py:832-867) at the current counts
             // the species counts only change on accepted table steps: the feasibility mask, its
             // weight sum and the a-priori factor of every direction are kept until then
@@ -2099,9 +1899,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
                 dir = hit ? __ffs((int)hit) - 1 : last_feas;
             }
             set_direction(dir);
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[1] += tn - ph_t; ph_t = tn; }
-#endif
             // pick the sites of the depleted species from the candidate stream
             // c_t = W(step, 4 + t / 4, t % 4): 256 candidates per wave round, lane l holds
             // t = 256 round + 4 l + j.  The scan is scalar: per species four ballots (one per j),
@@ -2117,7 +1914,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
             // bit.  A site the stream names twice or a stream that needs more than 64 candidates
             // sends the step to the full scan below.)
             bool fast_done = false;
-#ifndef SMOLMC_NO_TABLE_FAST
             {
                 const philox_out o = philox_call((uint32_t)step, (uint32_t)(step >> 32), 4u + ((uint32_t)lane >> 2), key0, key1);
                 const uint32_t wsel = (lane & 3) == 0 ? o.w[0] : (lane & 3) == 1 ? o.w[1] : (lane & 3) == 2 ? o.w[2] : o.w[3];
@@ -2147,7 +1943,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
                 if (ok) fast_done = true;
                 else { vcol = 0; vcsp = 0; ncol = 0; } // stream exhausted or repeated site: full scan
             }
-#endif
             for (int c = 0; c < nc && !fast_done; ++c) {
                 int need = -(int)rdlane((uint32_t)vu, c);
                 unsigned long long B[4] = {0ull, 0ull, 0ull, 0ull};
@@ -2196,9 +1991,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
                     need--;
                 }
             }
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[2] += tn - ph_t; ph_t = tn; }
-#endif
             // The flips of the step are the picks in PICK order (site and old species are known from
             // the scan); their rows are fetched now.  The random assignment to the enriched species
             // (:627-631) then only has to say which pick gets which species: the oracle removes the
@@ -2232,9 +2024,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
             }
         }
         } // (step-at-a-time proposal)
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_prop[covered ? 0 : 1] += tn - ph_t; ph_prop[2] -= tn; }
-#endif
         if (REPLAY) {
             const LeanParamsKernarg Q = rare_params();
             const size_t krec = (size_t)r * (uint32_t)Q->steps + ((uint32_t)Q->steps - steps_left);
@@ -2242,16 +2031,8 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
             if (given == given) log_priori = nfl ? given : 0.0;
             else if (dir >= 0) priori_of(dir);
         } else if (dir >= 0) priori_of(dir);
-#ifdef SMOLMC_EXP_PHASES
-        ph_prop[2] += clock64();
-#endif
 
-#ifndef SMOLMC_NO_SETPRIO
         __builtin_amdgcn_s_setprio(2);
-#endif
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[3] += tn - ph_t; ph_t = tn; }
-#endif
         // -------- sequential evaluation of the flips of this step -----------------------
         double e = 0.0, pend[NSLOT], ew_part = 0.0, ew_uni = 0.0, dMu = 0.0;
         double vdq = 0.0; // lane f holds the charge change of flip f (potential-field mode)
@@ -2357,15 +2138,7 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
         else
             for (int f = 0; f < nfl; ++f)
                 eval_flip(f, load_row<NW>(idx_rs, lane_voff, rdlane((uint32_t)vsite, f) * SITE_BYTES));
-#ifndef SMOLMC_NO_SETPRIO
         __builtin_amdgcn_s_setprio(3);
-#endif
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[4] += tn - ph_t; ph_t = tn; }
-#endif
-#if defined(SMOLMC_EXP_VGPREF) && SMOLMC_EXP_VGPREF == 2
-        prefetch_next_G(); // (before the decision: more cover, but an accepted step's sweep queues behind it)
-#endif
         double dH = wave_sum_all(e);
         double dEw = 0.0;
         if (has_ew) {
@@ -2446,7 +2219,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
                 // directions is recomputed unless all were feasible and still are
                 const bool was_all = all_feasible(vcnt);
                 vcnt += vu;
-#ifndef SMOLMC_EXP_NOPRIORI // timing experiment only when defined (wrong results)
                 if (lp_line) {
                     // one position along the line; the two lanes whose positions leave the window of 62 around
                     // kpos are dropped (their residues now belong to positions on the other side)
@@ -2455,24 +2227,15 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
                 } else {
                     lp_valid = 0ull;
                 }
-#endif
                 if (!(was_all && all_feasible(vcnt))) head_valid = false;
             }
-#ifndef SMOLMC_EXP_NOSTALE // timing experiment only when defined (wrong results)
             if (!REPLAY) {
                 // batch lanes whose scan examined a site that has just changed are stale (all 32
                 // kept sites against every flipped site; unused slots hold 0xffff, no site)
                 const bool hit = batch_lane_examined(q_c, vsite, nfl);
-#ifdef SMOLMC_EXP_STALEIGN // timing experiment only when defined (wrong results): the marking is computed and dropped
-                if (__ballot(hit) == 0x123456789abcull) q_stale = ~0ull;
-#else
                 q_stale |= __ballot(hit);
-#endif
             }
-#endif
-#ifndef SMOLMC_EXP_NOFIELD // timing experiment only when defined (wrong results)
             if (ew_field) field_apply_flips<1, true>(phi, lane, nfl, vsite, vdq);
-#endif
             acc_mu += dMu;
             acc_ew += dEw;
             H += dH;
@@ -2482,9 +2245,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
             // are distinct, so the order of the stores does not matter)
             if (lane < nfl) occ[lean_swz(vsite, swa, swm, swb)] = (uint8_t)vold;
         }
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[5] += tn - ph_t; ph_t = tn; }
-#endif
         last_acc = accepted ? 1 : 0;
         if (WLT) { // WangLandau._do_post_step (wanglandau.py:222-266), accepted or not
             if (wl_sum_mode) {
@@ -2510,9 +2270,7 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
                                                Q->wl.L, Q->wl.flat, Q->wl.div, wl_m, lane);
             }
         }
-#ifndef SMOLMC_NO_SETPRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
         if (REPLAY && lane == 0) { // what smolmc_replay returns per step
             const LeanParamsKernarg Q = rare_params();
             const size_t krec = (size_t)r * (uint32_t)Q->steps + ((uint32_t)Q->steps - steps_left);
@@ -2520,9 +2278,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
             Q->rp_H[krec] = H;
             if (Q->rp_lp_out) Q->rp_lp_out[krec] = log_priori;
         }
-#if defined(SMOLMC_EXP_VGPREF) && SMOLMC_EXP_VGPREF != 2
-        prefetch_next_G(); // (at the end of the step)
-#endif
 
         if (--smp_countdown == 0) {
             const LeanParamsKernarg Q = rare_params(); // (sampling parameters: see rare_params)
@@ -2557,20 +2312,6 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
         }
     }
 
-#ifdef SMOLMC_EXP_PHASES
-    if ((r == 0 || r == P.R / 2 || r == P.R - 1) && lane == 0)
-        printf("phases (cycles per step): skeleton %.0f | head %.0f | picks %.0f | assign/swap %.0f | eval %.0f | decide %.0f\n",
-               (double)ph_acc[0] / (double)P.steps, (double)ph_acc[1] / (double)P.steps, (double)ph_acc[2] / (double)P.steps,
-               (double)ph_acc[3] / (double)P.steps, (double)ph_acc[4] / (double)P.steps, (double)ph_acc[5] / (double)P.steps);
-    if ((r == 0 || r == P.R / 2 || r == P.R - 1) && lane == 0)
-        printf("batch: covered %.3f of the steps, stale %.3f, swaps left out %.3f | batch %.0f cycles per step\n",
-               (double)ph_cov[0] / (double)P.steps, (double)ph_cov[1] / (double)P.steps, (double)ph_cov[2] / (double)P.steps,
-               (double)ph_bat / (double)P.steps);
-    if ((r == 0 || r == P.R / 2 || r == P.R - 1) && lane == 0)
-        printf("proposal: %.0f cycles per covered step, %.0f per step-at-a-time step; a-priori factor %.0f cycles per step\n",
-               (double)ph_prop[0] / (double)(ph_cov[0] ? ph_cov[0] : 1), (double)ph_prop[1] / (double)(P.steps - ph_cov[0] ? P.steps - ph_cov[0] : 1),
-               (double)ph_prop[2] / (double)P.steps);
-#endif
     if (ew_field)
         for (int j = lane; j < P.ew_nact; j += 64) P.ew_phi[(size_t)r * P.ew_nact + j] = phi[j];
     {
@@ -2645,6 +2386,9 @@ static int launch_lean_inst(smolmc_handle *h, const LeanParams &lp) {
 template <int NSLOT, int MM, int STEP>
 static int launch_lean_me(smolmc_handle *h, const LeanParams &lp) {
     const bool mu = lp.mu_row != nullptr, ew = lp.ew_G != nullptr;
+    // (round 2's Wang-Landau variant of this kernel: no longer dispatched, Wang-Landau runs on mc_wl_kernel.
+    // Its instantiations stay until the PMC entries of profiles/pmc_constants.json are re-stamped: without
+    // them every other kernel of lean_n{2,4}.hip moves in the code object, which changes its digest.)
     if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU)
         return launch_lean_inst<NSLOT, MM, STEP, false, 0, true>(h, lp);
     if (ew)

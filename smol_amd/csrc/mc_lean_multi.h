@@ -13,12 +13,6 @@
 #pragma once
 #include "mc_lean.h"
 
-#ifdef SMOLMC_NO_TABLE_FAST // A/B switch: every table step through the full candidate scan
-#define SMOLMC_TABLE_MULTI_FAST false
-#else
-#define SMOLMC_TABLE_MULTI_FAST true
-#endif
-
 // element k (< 4) of a kernel-argument array without dynamic indexing (which would go through scratch)
 __device__ __forceinline__ int sel4(const int (&a)[4], int k) {
     return k == 0 ? a[0] : (k == 1 ? a[1] : (k == 2 ? a[2] : a[3]));
@@ -270,12 +264,8 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
     // in the tables, so an entry never corrects its own site.  (Replay keeps the immediate update.)
     constexpr bool PEND = EWM == 2 && !REPLAY;
     const unsigned char *gxp = PEND ? (const unsigned char *)P.ew_gx : nullptr;
-#ifdef SMOLMC_NO_EWALD_PENDING // A/B switch
-    const bool pend_on = false;
-#else
     // (worth it from about 32 groups of 64 field entries on: LiNiO2 8^3, 16 groups, loses 15 %)
     const bool pend_on = PEND && gxp != nullptr && P.ew_nact >= 2048;
-#endif
     int npend = 0;
     uint32_t vps8 = 0;  // lane l: table offset of entry l & 3
     double vpdq = 0.0;  //         its charge change
@@ -309,11 +299,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
     // offsets of a lane's 16 entries are constants of the launch: kept in registers (round 6; the kernel runs one or two
     // waves per SIMD, registers are not what it is short of), the S8 offsets of a step's sites come with the proposal
     // batch, and ALL gathers of the sweep are issued at once: one round trip.
-#ifdef SMOLMC_NO_WL_E16 // A/B switch (tools/build_variant.sh)
-    constexpr bool WLE16 = false;
-#else
     constexpr bool WLE16 = WLK != 0 && EWM == 1 && !REPLAY; // (EWM 1: the field in LDS)
-#endif
     uint32_t e0w[16]; // (dead -- and removed by the compiler -- in the instantiations that do not take this sweep)
     bool have_e0w = false;
     uint32_t vS8s = 0, vS8c[4] = {0, 0, 0, 0}; // per batch: S8 of the lane's site / swap candidates
@@ -351,13 +337,6 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
         return v >= 0 ? v : P.m_sbase[0];
     };
     if (REPLAY && nsteps32) row1 = load_row<NW>(idx_rs, lane_voff, (uint32_t)rp_site(0u) * SITE_BYTES);
-#ifdef SMOLMC_EXP_PHASES // experiment: shader cycles per phase of a step (walker 0 prints the averages)
-    long long mph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long mph_t = clock64();
-#define MULTI_PHASE(i) { const long long tn = clock64(); mph[i] += tn - mph_t; mph_t = tn; }
-#else
-#define MULTI_PHASE(i)
-#endif
     for (uint32_t it_step = 0; it_step < nsteps32; ++it_step, ++step) {
         const unsigned long long base = step & ~15ull;
         if (!REPLAY && base != batch_base) {
@@ -440,9 +419,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
             row1 = load_row<NW>(idx_rs, lane_voff, rdlane((uint32_t)vsite, (int)(step & 15ull) * 4) * SITE_BYTES);
         }
         const int l4 = (int)(step & 15ull) * 4;
-#ifndef SMOLMC_NO_SETPRIO
         if (!ONE) __builtin_amdgcn_s_setprio(1); // wave priority rises through the step (see mc_lean_kernel; no gain for ONE)
-#endif
         int s1, a1, sub1;
         int rq1 = 0, rq2 = -1, rq3 = 0;
         bool rp_empty = false;
@@ -583,10 +560,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
 #undef SMOLMC_CAND_TAKE
             n1 = o2;
         }
-#ifndef SMOLMC_NO_SETPRIO
         if (!ONE) __builtin_amdgcn_s_setprio(2);
-#endif
-        MULTI_PHASE(0)
         // potential at the two sites (HBM copy of the field: global loads, issued AHEAD of the
         // partner's row so that the wait for that row does not cover them as well)
         double p1 = 0.0, p2 = 0.0;
@@ -662,9 +636,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
             dMu = s_mu[sub1 * 8 + n1] - s_mu[sub1 * 8 + o1];
             if (nfl == 2) dMu += s_mu[sub1 * 8 + n2] - s_mu[sub1 * 8 + o2];
         }
-#ifndef SMOLMC_NO_SETPRIO
         if (!ONE) __builtin_amdgcn_s_setprio(3);
-#endif
         // compute_bias_change against the original occupancy (kernel/base.py:307-311; bias.py)
         double dB = 0.0, dQ[SMOLMC_MAX_BIAS_ROWS] = {0.0, 0.0, 0.0, 0.0};
         if (BIAS && nfl >= 1) {
@@ -691,7 +663,6 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
         double dH = 0.0, dEw = HAS_EW ? ew_uni : 0.0;
         bool accepted = false, decided = false;
         int wnb = wb;
-        MULTI_PHASE(1)
         if (WLK) { // WangLandau._accept_step (wanglandau.py:186-202): exact float64 delta, exact floor division
             dH = wave_sum_all(e);
             if (HAS_EW) dH += P.ew_coef * dEw;
@@ -727,7 +698,6 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
             accepted = __ballot((exponent >= 0.0) || (exponent > lu)) != 0ull;
         }
         nacc_before = nacc_add;
-        MULTI_PHASE(2)
         if (accepted) {
             bias_acc += dB;
 #pragma unroll
@@ -735,7 +705,6 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
             if (WLK) {
                 // the state (bin, features) ends here: its post-steps go to the bin's row (sums)
                 if (wl_sum_mode) wl_flush_run();
-                MULTI_PHASE(6)
                 // _do_accept_step (wanglandau.py:204-220): features and enthalpy follow the step
                 const double *fsp = s_fs + ((size_t)cls1 * NSLOT) * 64 + lane;
                 const uint32_t *ftp = s_ft + ((size_t)cls1 * NSLOT) * 64 + lane;
@@ -785,7 +754,6 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
             }
             if (STEP == SMOLMC_STEP_FLIP) occ[a1] = (uint8_t)n1;
             if (STEP == SMOLMC_STEP_SWAP) occ[a2] = (uint8_t)n2;
-            MULTI_PHASE(3)
             if (HAS_EW) {
                 bool swept = false;
                 if constexpr (WLE16) {
@@ -834,7 +802,6 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
             acc_mu += dMu;
             acc_ew += dEw;
             nacc_add++;
-            MULTI_PHASE(4)
         } else if (STEP == SMOLMC_STEP_SWAP) {
             occ[a1] = (uint8_t)o1;
         }
@@ -863,10 +830,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
                                                Q->wl.L, Q->wl.flat, Q->wl.div, wl_m, lane);
             }
         }
-#ifndef SMOLMC_NO_SETPRIO
         if (!ONE) __builtin_amdgcn_s_setprio(0);
-#endif
-        MULTI_PHASE(5)
         if (REPLAY && WLK) {
             if (lane == 0) {
                 const size_t k = (size_t)r * nsteps32 + it_step;
@@ -925,13 +889,6 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
         }
     }
 
-#ifdef SMOLMC_EXP_PHASES
-    if (r == 0 && lane == 0)
-        printf("multi phases (cycles per step): skeleton+proposal %.0f | gathers+tables %.0f | decision %.0f | accept: features+occupancy %.0f | "
-               "field %.0f | post-step+rest %.0f | (row flush %.0f)\n",
-               (double)mph[0] / (double)nsteps32, (double)mph[1] / (double)nsteps32, (double)mph[2] / (double)nsteps32,
-               (double)mph[3] / (double)nsteps32, (double)mph[4] / (double)nsteps32, (double)mph[5] / (double)nsteps32, (double)mph[6] / (double)nsteps32);
-#endif
     // ---- write back ---------------------------------------------------------------
     if (pend_on && npend > 0) flush_pending(); // (phi in HBM is complete between launches)
     if (phi_lds)
@@ -1512,10 +1469,6 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
         q_sub = subs;
     };
 
-#ifdef SMOLMC_EXP_PHASES // experiment: shader cycles per phase of a step (walker 0 prints the averages)
-    long long ph_acc[5] = {0, 0, 0, 0, 0}, ph_cov = 0;
-    long long ph_t = clock64();
-#endif
     const uint32_t nsteps32 = (uint32_t)P.steps;
     for (uint32_t it_step = 0; it_step < nsteps32; ++it_step, ++step) {
         // the 16-step word batch of the step-at-a-time proposal (lane l = block l & 3 of step base + (l >> 2))
@@ -1545,15 +1498,8 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
         if (!REPLAY && __builtin_expect((uint32_t)(step & ~63ull) != q_base, 0)) propose_batch(step & ~63ull);
         const int l6 = (int)(step & 63ull);
         const uint32_t q_m = rdlane(q_meta, l6);
-#ifdef SMOLMC_NO_TABLE_BATCH // A/B switch: every step through the step-at-a-time proposal
-        const bool covered = false;
-#else
         const bool covered = !REPLAY && (q_m & 1u) != 0u && ((q_stale >> l6) & 1ull) == 0ull;
-#endif
         double lu_rp = 0.0; // replay: log of the recorded uniform
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[0] += tn - ph_t; ph_t = tn; if (covered) ph_cov++; }
-#endif
         // flips of this step, lane-indexed: lane f holds flip f (site, new / old code, sublattice)
         int vsite = 0, vnew = 0, vold = 0, vfsub = 0;
         int nfl = 0, dir = -1;
@@ -1691,9 +1637,6 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
 #pragma unroll
             for (int i = 0; i < 8; ++i) vu = (i == (dir >> 1)) ? vtf[i] : vu;
             vu *= (dir & 1) ? -1 : 1;
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[1] += tn - ph_t; ph_t = tn; }
-#endif
             // sites of the depleted species, sublattice by sublattice, from the candidate stream
             // c_t = W(step, 4 + t / 4, t % 4) (256 candidates per wave round, position kept across
             // species AND sublattices); then the random assignment to the enriched species
@@ -1705,7 +1648,7 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
                 cb_word = (tt & 3u) == 0u ? o.w[0] : (tt & 3u) == 1u ? o.w[1] : (tt & 3u) == 2u ? o.w[2] : o.w[3];
             }
             const int g32 = (int)(step & 1ull) * 32; // first lane of this step's candidates in the block
-            bool fast = SMOLMC_TABLE_MULTI_FAST; // first the candidate block; after a miss the full scan
+            bool fast = true; // first the candidate block; after a miss the full scan
             for (bool done = false; !done; fast = false) {
             nfl = 0;
             fast_ok = fast;
@@ -1862,9 +1805,6 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
             if (given == given) log_priori = nfl ? given : 0.0;
         }
 
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[2] += tn - ph_t; ph_t = tn; }
-#endif
         // -------- sequential evaluation of the flips of this step -----------------------
         double e = 0.0, ew_uni = 0.0, dMu = 0.0;
         double vdq = 0.0;
@@ -1976,11 +1916,9 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
             }
             two_phased = true;
         };
-#ifndef SMOLMC_NO_MULTI_TWO_PHASE
         if (TPF && nfl == 2) two_phase(std::integral_constant<int, 2>{});
         else if (TPF && nfl == 3) two_phase(std::integral_constant<int, 3>{});
         else
-#endif
         {
 #pragma unroll
             for (int f = 0; f < 4; ++f)
@@ -1988,9 +1926,6 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
             for (int f = 4; f < nfl; ++f)
                 eval_flip(f, load_row<NW>(idx_rs, lane_voff, rdlane((uint32_t)vsite, f) * SITE_BYTES));
         }
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[3] += tn - ph_t; ph_t = tn; }
-#endif
         double dH = wave_sum_all(e);
         const double dEw = has_ew ? ew_uni : 0.0;
         if (has_ew) dH += P.ew_coef * dEw;
@@ -2158,9 +2093,6 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
             }
         }
 
-#ifdef SMOLMC_EXP_PHASES
-        { const long long tn = clock64(); ph_acc[4] += tn - ph_t; ph_t = tn; }
-#endif
         if (--smp_countdown == 0) { // (sampling parameters: re-read from the kernel arguments, see rare_params)
             const LeanParamsKernarg Q = rare_params();
             smp_countdown = (uint32_t)Q->smp.every;
@@ -2202,12 +2134,6 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
         }
     }
 
-#ifdef SMOLMC_EXP_PHASES
-    if (r == 0 && lane == 0)
-        printf("multi phases (cycles per step): covered %.3f | skeleton %.0f | head %.0f | picks+assign/swap %.0f | eval %.0f | decide+update %.0f\n", (double)ph_cov / (double)P.steps,
-               (double)ph_acc[0] / (double)P.steps, (double)ph_acc[1] / (double)P.steps, (double)ph_acc[2] / (double)P.steps,
-               (double)ph_acc[3] / (double)P.steps, (double)ph_acc[4] / (double)P.steps);
-#endif
     if (phi_lds)
         for (int j = lane; j < P.ew_nact; j += 64) P.ew_phi[(size_t)r * P.ew_nact + j] = phi[j];
     {

@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
     const float hi32 = uni_f((float)span_b - tol32), hiout32 = uni_f((float)span_b + tol32);
     float xb32 = (float)(hoff * inv_bin);
     uint32_t since_sync = 0;
-    const bool never_fast = __ballot(!(P.fast_eps > 0.0)) != 0ull; // SMOLMC_NO_FAST_ACCEPT: every step exact
+    const bool never_fast = __ballot(!(P.fast_eps > 0.0)) != 0ull; // SMOLMC_FAST_EPS_SCALE=0: every step exact
     bool force_exact = never_fast;
     const long long wl_counter0 = P.wl.counter[r];
     // counter modulo the check period (the host refuses periods >= 2^31)
@@ -308,13 +308,6 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
         row1 = load_row<NW>(idx_rs, lane_voff, (uint32_t)s1 * SITE_BYTES);
     }
 
-#ifdef SMOLMC_EXP_PHASES // experiment: shader cycles per phase of a step (walker 0 prints the averages)
-    long long lph[6] = {0, 0, 0, 0, 0, 0};
-    long long lph_t = clock64();
-#define WL_PHASE(i) { const long long tn = clock64(); lph[i] += tn - lph_t; lph_t = tn; }
-#else
-#define WL_PHASE(i)
-#endif
     uint32_t steps_left = (uint32_t)P.steps; // the host splits launches at 2^30 steps
     while (steps_left != 0u) {
         // -------- random words (generated 16 steps at a time, see mc_lean_kernel) --------
@@ -351,7 +344,6 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
         int l64 = (int)(step & 63ull);
         do {
             __builtin_amdgcn_s_setprio(1);
-            WL_PHASE(0)
             int s1n, a1n;
             int rq1 = 0, rq2 = -1, rq3 = 0;
             bool rp_empty = false;
@@ -481,7 +473,6 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
                 dEw = uni_d(dEw);
             }
             __builtin_amdgcn_s_setprio(2);
-            WL_PHASE(1)
             RowWords<NW> row2 = row1;
             if (STEP == SMOLMC_STEP_SWAP) row2 = load_row<NW>(idx_rs, lane_voff, (uint32_t)s2 * SITE_BYTES);
             pend_commit(); // the run that ended with the previous step (its LDS reads have landed by now)
@@ -514,7 +505,6 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
                 }
             }
             __builtin_amdgcn_s_setprio(3);
-            WL_PHASE(2)
             // -------- WangLandau._accept_step (wanglandau.py:186-202) --------
             const double lu = REPLAY ? lu_rp
                                      : __hiloint2double((int)rdlane((uint32_t)__double2hiint(logu), l64),
@@ -570,7 +560,6 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
                     accepted = ((__ballot((ex >= 0.0) | (ex > lu)) >> 8) & 1ull) != 0ull;
                 }
             }
-            WL_PHASE(3)
             // -------- update (kernel/base.py:327-343; wanglandau.py:204-220) --------
             nacc_before = nacc_add;
             uint32_t sel_hi = 0u;
@@ -623,7 +612,6 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
             s1 = s1n;
             a1 = a1n;
             __builtin_amdgcn_s_setprio(0);
-            WL_PHASE(4)
             if (REPLAY) { // accept flag and running enthalpy of every step (what smolmc_replay returns)
                 const double Hnow = exact_enthalpy();
                 if (lane == 0) {
@@ -669,12 +657,6 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
         }
     }
 
-#ifdef SMOLMC_EXP_PHASES
-    if (r == 0 && lane == 0)
-        printf("wl phases (cycles per step): skeleton %.0f | proposal %.0f | gathers+tables %.0f | decision %.0f | update+post %.0f\n",
-               (double)lph[0] / (double)P.steps, (double)lph[1] / (double)P.steps, (double)lph[2] / (double)P.steps,
-               (double)lph[3] / (double)P.steps, (double)lph[4] / (double)P.steps);
-#endif
     // ---- write back ---------------------------------------------------------------
     pend_commit(); // a flush of the last step
     if (run_n != 0u) { // the unfinished run of the current bin
@@ -735,7 +717,7 @@ static int launch_wl_kern(smolmc_handle *h, const LeanParams &lp) {
     if (h->lean_lds > 64 * 1024)
         HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lean_lds));
     long C = 0;
-    if (!REPLAY && lp.smp.every == 0 && getenv("SMOLMC_NO_ROTATE") == nullptr) {
+    if (!REPLAY && lp.smp.every == 0 && !smolmc_env(ENV_NO_ROTATE)) {
         int per_cu = 0, cus = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, 256, h->lean_lds) == hipSuccess &&
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess)

@@ -56,6 +56,59 @@ static int fail(const std::string &m) {
 static const double SMOLMC_KB = 8.617333262145e-5; // smol/constants.py:4
 
 // ----------------------------------------------------------------------------
+// environment switches (host)
+// ----------------------------------------------------------------------------
+// Every SMOLMC_* variable the engine reads.  Each is a reference path or a hook that a test, bench.py or
+// the library relies on; the experiment switches of earlier rounds were removed (git history holds them).
+// smolmc_env reads the environment at every call: tests change these variables between calls, and
+// SMOLMC_WALKER_ORDER is read at every launch.  `dispatch`: read by smolmc_create to choose a kernel or
+// its layout -- smolmc_kernel_info names the ones that were set (" env=...").
+enum SmolmcEnv {
+    ENV_FORCE_GENERAL, ENV_FORCE_UNIVERSAL, ENV_DENSE_EWALD, ENV_LAZY_FEATURES_ONLY, ENV_NO_LAZY_FEATURES,
+    ENV_NO_LEAN_ALIASED, ENV_NO_LEAN_MULTI, ENV_NO_WL_MULTI, ENV_NO_TABLE_BIAS, ENV_NO_TABLE_WL, ENV_NO_EWALD_FIELD,
+    ENV_NO_EWALD_GX, ENV_NO_SOLO, ENV_NO_OCC6, ENV_NO_INKERNEL_BIAS, ENV_NO_SITE_RELABEL, ENV_MULTI_PHI_HBM,
+    ENV_MULTI_PHI_LDS, ENV_UNIV_OCC_HBM, ENV_REPLAY_GENERAL, ENV_REPLAY_UNIVERSAL, ENV_WL_RUNNING_MEAN,
+    ENV_WALKER_ORDER, ENV_LAUNCH_CHUNK, ENV_FAST_EPS_SCALE, ENV_NO_ROTATE, ENV_DEBUG,
+    ENV_COUNT
+};
+struct SmolmcEnvSwitch {
+    const char *name;
+    bool dispatch;
+    const char *purpose;
+};
+static constexpr SmolmcEnvSwitch smolmc_env_switches[] = {
+    {"SMOLMC_FORCE_GENERAL", true, "no lean family: mc_kernel, or the universal kernel where mc_kernel cannot run"},
+    {"SMOLMC_FORCE_UNIVERSAL", true, "no mc_kernel: what the lean families do not take runs on the universal kernel"},
+    {"SMOLMC_DENSE_EWALD", true, "keep the dense Ewald matrix (no compact site-charge form, no potential field)"},
+    {"SMOLMC_LAZY_FEATURES_ONLY", true, "several correlation functions per orbit: lazy features instead of the KF kernels"},
+    {"SMOLMC_NO_LAZY_FEATURES", true, "no lazy cluster features: such models leave the lean families"},
+    {"SMOLMC_NO_LEAN_ALIASED", true, "aliased supercells (a cluster holds a site twice) leave the lean families"},
+    {"SMOLMC_NO_LEAN_MULTI", true, "no multi-class lean kernels (mc_lean_multi_kernel, mc_table_multi_kernel)"},
+    {"SMOLMC_NO_WL_MULTI", true, "Wang-Landau leaves the multi-class lean kernels"},
+    {"SMOLMC_NO_TABLE_BIAS", true, "TableFlip with an MCBias term leaves the lean table kernels"},
+    {"SMOLMC_NO_TABLE_WL", true, "Wang-Landau TableFlip leaves the lean table kernels"},
+    {"SMOLMC_NO_EWALD_FIELD", true, "no Ewald potential field: per-proposal row sums instead"},
+    {"SMOLMC_NO_EWALD_GX", true, "no translation-compressed Ewald site kernel: the rows of G"},
+    {"SMOLMC_NO_SOLO", true, "no one-wave-per-workgroup layout of mc_lean_kernel"},
+    {"SMOLMC_NO_OCC6", true, "no six-waves-per-SIMD instantiation of the one-wave layout"},
+    {"SMOLMC_NO_INKERNEL_BIAS", false, "biased lean walkers record their sample rows through snapshots"},
+    {"SMOLMC_NO_SITE_RELABEL", true, "scattered active sites are not renumbered into one range"},
+    {"SMOLMC_MULTI_PHI_HBM", true, "multi-class lean kernels: the potential field stays in HBM"},
+    {"SMOLMC_MULTI_PHI_LDS", true, "multi-class lean kernels: the potential field in LDS whenever it fits"},
+    {"SMOLMC_UNIV_OCC_HBM", true, "universal kernel: the occupancy stays in HBM"},
+    {"SMOLMC_REPLAY_GENERAL", false, "smolmc_replay on mc_kernel where it can take the records"},
+    {"SMOLMC_REPLAY_UNIVERSAL", false, "smolmc_replay on the universal kernel"},
+    {"SMOLMC_WL_RUNNING_MEAN", true, "Wang-Landau keeps per-bin running means also at update_period 1"},
+    {"SMOLMC_WALKER_ORDER", false, "launch-slot order of the table kernels: 0 identity, 1 (default) / 2 hot-cold pairs"},
+    {"SMOLMC_LAUNCH_CHUNK", false, "lean launches split at this many steps instead of 2^30"},
+    {"SMOLMC_FAST_EPS_SCALE", false, "scales the band of the float32 accept pre-test (0: every step exact)"},
+    {"SMOLMC_NO_ROTATE", false, "mc_wl_kernel: no group rotation of launches beyond one round of walkers"},
+    {"SMOLMC_DEBUG", false, "dispatch and replay decisions printed to stderr"},
+};
+static_assert(sizeof(smolmc_env_switches) / sizeof(smolmc_env_switches[0]) == ENV_COUNT, "one entry per SmolmcEnv");
+static inline const char *smolmc_env(SmolmcEnv e) { return getenv(smolmc_env_switches[e].name); }
+
+// ----------------------------------------------------------------------------
 // device-side parameter block
 // ----------------------------------------------------------------------------
 // device-side sample recording (Sampler.sample + SampleContainer.save_sampled_trace,
@@ -361,14 +414,12 @@ __device__ __forceinline__ void field_sweep_gx_sized(double *phi, const uint32_t
                                                      int na, const uint32_t (&s8)[NF], const double (&dq)[NF], int gstart = 0) {
     const int ngf = na >> 6; // full groups of 64 entries
     int g = gstart;          // (groups below gstart: done by the caller, see field_sweep_gx_pre27)
-#ifndef SMOLMC_NO_SMALL_SWEEP // A/B switch (tools/build_variant.sh)
     // (flips and swaps only: the three- and four-flip sweeps of the TableFlip kernels keep the group-by-group form -- those
     // kernels sit at 256 VGPRs, and the extra batch moved their spills: config 5 at 12^3 lost 1 % for 23 % at 8^3)
     if (NF <= 2 && __builtin_expect(gstart == 0 && ngf < U, 0)) { // (uniform)
         field_sweep_gx_small<NF, 4>(phi, E8, gx, lane, na, s8, dq);
         return;
     }
-#endif
     // Chunks of up to NB batches of U groups: the E8 entries of the whole chunk are fetched first, then the
     // batches run, each one round trip to the tables.  When fewer than U groups are left the last batch is
     // shifted back so that it ends on the last full group; the groups it shares with the batch before are
@@ -614,16 +665,6 @@ struct URow {
     int32_t x[6];
     int32_t rec, pad;
 };
-// ... and in 16 bytes (round 6) for cells of at most 65535 sites: six u16 member sites + the record.  The rows are what
-// the kernel streams -- 230 of them per swap step of config 2, a 15 MB table against 4 MB of L2 per XCD: 3.0 KB of
-// Infinity-Cache / HBM fetches per step (round 5's PMC passes).  Measured: 25.0 -> 8.7 GB per launch (the 7.5 MB table
-// hits L2 more often), and 4-11 % SLOWER: the kernel is VALU-bound (0.65-0.68 issue) and the unpacking adds ~23 vector
-// instructions per step.  Behind -DSMOLMC_UNIV_ROWS16 (make EXTRA=..., then SMOLMC_UNIV_ROWS16=1): the default build has the
-// 32-byte rows only -- a never-taken uniform branch in the row loads cost the default path 3-4 %.
-struct URow16 {
-    uint16_t x[6];
-    uint16_t rec_lo, rec_hi;
-};
 
 // parameter block of the universal kernel (mc_univ.h)
 struct UParams {
@@ -656,7 +697,6 @@ struct UParams {
     int lds_per_wave;
     int lds_shared;          // bytes of workgroup-shared LDS in front of the per-wave blocks (the dictionaries)
     int wl;                  // Wang-Landau kernel
-    int rows16;              // rows are packed 16-byte records (u16 member sites: cells of <= 65535 sites) instead of URow
     // replay extras
     const double *rp_lp;     // [R][nsteps] a-priori factors (NaN = derive) or null
     double *rp_lp_out;       // [R][nsteps] or null
@@ -751,6 +791,7 @@ struct smolmc_handle {
     // site relabelling behind the boundary (engine.hip, plan_relabelling): the tables this handle was built from are
     // the caller's with the sites renumbered; occupancies and step records are translated at every entry point
     bool relabelled = false;
+    uint32_t env_dispatch = 0;         // dispatch switches set at smolmc_create: bit e <-> SmolmcEnv e
     std::vector<int32_t> new_of, old_of; // caller's site -> engine's site, and back
 };
 
@@ -813,13 +854,7 @@ int smolmc_launch_multi_table_bias_2(smolmc_handle *h, const LeanParams &lp); //
 int smolmc_launch_multi_table_bias_4(smolmc_handle *h, const LeanParams &lp);
 int smolmc_launch_multi_table_bias_8(smolmc_handle *h, const LeanParams &lp);
 int smolmc_launch_lean_4(smolmc_handle *h, const LeanParams &lp);
-// replay instantiations of the TableFlip / biased lean kernels (0: those replays take the universal / general kernel)
-#ifndef SMOLMC_HAVE_TABLE_REPLAY
-#define SMOLMC_HAVE_TABLE_REPLAY 1
-#endif
-#ifndef SMOLMC_HAVE_BIAS_REPLAY
-#define SMOLMC_HAVE_BIAS_REPLAY 1
-#endif
+// replay instantiations of the TableFlip / biased lean kernels
 int smolmc_launch_table_replay_2(smolmc_handle *h, const LeanParams &lp);
 int smolmc_launch_table_replay_4(smolmc_handle *h, const LeanParams &lp);
 int smolmc_launch_multi_table_replay_2(smolmc_handle *h, const LeanParams &lp);

@@ -12,5 +12,4 @@ run SMOLMC_FORCE_UNIVERSAL=1 python tools/bench_configs.py --config 2 --mc 500
 run SMOLMC_FORCE_UNIVERSAL=1 python tools/bench_configs.py --config 3 --mc 500
 run SMOLMC_FORCE_UNIVERSAL=1 python tools/bench_configs.py --config 5 --mc 200
 run SMOLMC_DENSE_EWALD=1 python tools/bench_configs.py --config 3 --mc 500
-run SMOLMC_WL_PLAIN_ONLY=1 python tools/bench_configs.py --config 10
 wc -l $out
