@@ -372,6 +372,47 @@ int smolmc_import_temperature_dev(smolmc_handle *h, const double *src_dev);
 int smolmc_exchange_dev(smolmc_handle *h, int n_total, int first, int parity, const double *enthalpy_all_dev,
                         const double *ladder_dev, const double *log_u_dev, int32_t *rung_of_dev, int64_t *stats_dev);
 
+/* ---- distance objective: special quasirandom structures ------------------ */
+/* The objective of smol's DistanceProcessor (smol/moca/processor/distance.py:20-182),
+ *     H = -w L + sum_k W_k |f_k - t_k|,
+ * f the INTENSIVE correlation vector (feature_mode SMOLMC_FEATURES_CORRELATIONS, CorrelationDistanceProcessor)
+ * or cluster-interaction vector (SMOLMC_FEATURES_INTERACTIONS with tables->interaction_tensors,
+ * ClusterInteractionDistanceProcessor, distance.py:392-412), t the target, L the largest diameter up to which
+ * every feature matches the target within match_tol (distance.py:307-332).
+ *
+ * A distance handle works with smolmc_set_state, get_state, set_temperature, set_counters, run, replay,
+ * run_sampled (SMOLMC_SAMPLE_OCCUPANCY), eval_full, eval_delta, natural_parameters and kernel_info.  Unlike the
+ * extensive convention above, the features it hands back are the reference's intensive DISTANCE vector
+ * [L or 0, |f_1 - t_1|, ..., |f_{F-1} - t_{F-1}|] (distance.py:133-182); eval_delta returns the difference of
+ * two such vectors (distance.py:156-182), and the enthalpy is H.  tables->ce_coefs is ignored. */
+#define SMOLMC_DIST_MAX_FEATURES 256 /* largest F of a distance handle */
+typedef struct smolmc_distance {
+    int32_t n_features;            /* F = num_corr (correlations) or num_orbits (interactions), incl. entry 0 */
+    const double *target;          /* [F] target_vector; entry 0 unused (distance.py:133-154) */
+    const double *weights;         /* [F-1] target_weights */
+    double match_weight;           /* w >= 0; natural parameters are [-w, weights...] (distance.py:95) */
+    double match_tol;              /* exact-match tolerance, `<=` (distance.py:307-332) */
+    int32_t n_groups;              /* distinct diameters rounded to 6 decimals, ascending */
+    const double *group_diameter;  /* [n_groups] (clusterspace.py:368-381 orbits_by_diameter) */
+    const int32_t *feature_group;  /* [F] group of every feature, -1 for entry 0 */
+    double kB;                     /* Boltzmann constant of this handle's temperatures (sqs.py:522-524 uses 1.0) */
+} smolmc_distance;
+
+/* Refused: Ewald tables (distance.py:76-77), mu_table, bias terms, Wang-Landau, TableFlip, match_weight < 0,
+ * F above SMOLMC_DIST_MAX_FEATURES, and models whose kernel state does not fit 64 KB of LDS per workgroup of four
+ * walkers: the feature mode's tensors (8 bytes per entry, shared) plus, per walker, 16 F + 8 x (row chunks of the
+ * busiest site: ceil(J / 4) per local record and function) + 2 x num_sites bytes.  smolmc_import_temperature_dev
+ * and smolmc_exchange_dev refuse a distance handle.  Metropolis with beta = 1 / (kB T) (metropolis.py:31-49). */
+int smolmc_create_distance(const smolmc_tables *t, const smolmc_distance *d,
+                           const smolmc_config *c, smolmc_handle **out);
+/* per walker: lowest running enthalpy seen (strictly lower replaces), its distance features,
+ * its occupancy, the step at which it was reached (the walker's n_steps then); any pointer may be NULL.
+ * smolmc_set_state starts the record at the initial state. */
+int smolmc_get_best(smolmc_handle *h, double *score /*R*/, double *features /*RxF*/,
+                    int32_t *occ /*RxN*/, uint64_t *step /*R*/);
+/* forget the record: it restarts at every walker's current state */
+int smolmc_reset_best(smolmc_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,49 @@ class smolmc_config(C.Structure):
     ]
 
 
+class smolmc_distance(C.Structure):
+    """Mirror of ``smolmc_distance`` (include/smolmc.h): the objective of a distance handle."""
+
+    _fields_ = [
+        ("n_features", C.c_int32),
+        ("target", _f64p),
+        ("weights", _f64p),
+        ("match_weight", C.c_double),
+        ("match_tol", C.c_double),
+        ("n_groups", C.c_int32),
+        ("group_diameter", _f64p),
+        ("feature_group", _i32p),
+        ("kB", C.c_double),
+    ]
+
+
+DIST_MAX_FEATURES = 256  # SMOLMC_DIST_MAX_FEATURES
+
+
+class DistanceSpec:
+    """Kept-alive arrays + the ``smolmc_distance`` struct of one distance objective.
+
+    target [F] (entry 0 unused), weights [F-1], groups: the diameter groups as
+    (group_diameter [G] ascending, feature_group [F], -1 for entry 0)."""
+
+    def __init__(self, target, weights, match_weight, match_tol, group_diameter, feature_group, kB):
+        self.target = _arr(target, np.float64, "target")
+        self.weights = _arr(weights, np.float64, "weights")
+        self.group_diameter = _arr(group_diameter, np.float64, "group_diameter")
+        self.feature_group = _arr(feature_group, np.int32, "feature_group")
+        s = smolmc_distance()
+        s.n_features = len(self.target)
+        s.target = _ptr(self.target, C.c_double)
+        s.weights = _ptr(self.weights, C.c_double)
+        s.match_weight = float(match_weight)
+        s.match_tol = float(match_tol)
+        s.n_groups = len(self.group_diameter)
+        s.group_diameter = _ptr(self.group_diameter, C.c_double)
+        s.feature_group = _ptr(self.feature_group, C.c_int32)
+        s.kB = float(kB)
+        self.struct = s
+
+
 def _arr(a, dtype, name):
     a = np.asarray(a)
     if a.dtype != dtype:

@@ -1,0 +1,4 @@
+// mc_dist_kernel instantiation (distance objective, native Philox stream), NSLOT = 1
+#include "mc_dist.h"
+
+int smolmc_launch_dist_1(smolmc_handle *h, const DistParams &P) { return launch_dist_nslot<1, false>(h, P); }

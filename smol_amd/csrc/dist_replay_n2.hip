@@ -1,0 +1,4 @@
+// mc_dist_kernel instantiation (distance objective, host-provided steps and uniforms), NSLOT = 2
+#include "mc_dist.h"
+
+int smolmc_launch_dist_replay_2(smolmc_handle *h, const DistParams &P) { return launch_dist_nslot<2, true>(h, P); }

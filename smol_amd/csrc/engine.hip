@@ -2093,6 +2093,7 @@ extern "C" int smolmc_destroy(smolmc_handle *h) {
     if (!h) return 0;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
+    smolmc_dist_free(h);
     for (void *p : h->allocs) hipFree(p);
     if (h->d_eval_occ) hipFree(h->d_eval_occ);
     free_samples(h);
@@ -2121,7 +2122,11 @@ extern "C" int smolmc_set_stream(smolmc_handle *h, void *stream) {
     return 0;
 }
 
-static int launch_eval_full(smolmc_handle *h, const uint8_t *d_occ8, int nocc, double *d_out, int ce_only = 0) {
+static int launch_eval_full(smolmc_handle *h, const uint8_t *d_occ8, int nocc, double *d_out, int ce_only = 0);
+int smolmc_eval_extensive(smolmc_handle *h, const uint8_t *d_occ8, int nocc, double *d_out) {
+    return launch_eval_full(h, d_occ8, nocc, d_out);
+}
+static int launch_eval_full(smolmc_handle *h, const uint8_t *d_occ8, int nocc, double *d_out, int ce_only) {
     // occupancies per block (see the kernel): four when the copies fit 60 KB of LDS and only the cluster features are
     // wanted, one with the scalar features (their loops take one occupancy), none staged beyond 60 KB
     int M = h->Npad <= 60 * 1024 ? 1 : 0;
@@ -2346,11 +2351,13 @@ extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint
                 return fail(msg);
             }
     }
+    if (h->dist) return smolmc_dist_after_set_state(h, temperature);
     return 0;
 }
 
 extern "C" int smolmc_set_temperature(smolmc_handle *h, const double *temperature) {
     if (!h || !temperature) return fail("null argument");
+    if (h->dist) return smolmc_dist_set_temperature(h, temperature);
     HIPCHK(hipSetDevice(h->device));
     std::vector<double> beta;
     set_betas(h, temperature, beta);
@@ -2369,6 +2376,7 @@ extern "C" int smolmc_sync(smolmc_handle *h) {
 
 extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
     if (!h || !buf || n <= 0) return fail("null argument");
+    if (h->dist) return smolmc_dist_kernel_info(h, buf, n);
     if (h->univ)
         snprintf(buf, (size_t)n, "universal occ=%s field=%d lds=%zu (%s)", h->up.occ_lds ? "lds" : "hbm", h->kp.ew_field,
                  (size_t)h->up.lds_shared + (size_t)h->up.lds_per_wave * h->univ_wpb, h->general_ok ? "TableFlip outside the lean families" : h->general_reason.c_str());
@@ -2648,6 +2656,7 @@ static UParams univ_block_of(smolmc_handle *h) {
 }
 
 static int run_steps(smolmc_handle *h, int64_t nsteps, const SampleBufs &smp) {
+    if (h->dist) return smolmc_dist_run(h, nsteps, smp);
     // (per-bin feature statistics as sums for the lean Wang-Landau kernel and for mc_kernel with
     // update_period 1, as running means for the universal kernel)
     TRY(wl_set_representation(h, h->univ ? false : (h->lean ? h->lp.wl.sum_mode != 0 : h->kp.wl_sum_mode != 0)));
@@ -3057,6 +3066,7 @@ extern "C" int smolmc_replay(smolmc_handle *h, int64_t nsteps, const int32_t *st
         }
         max_flips = std::max(max_flips, nf);
     }
+    if (h->dist) return smolmc_dist_replay(h, nsteps, steps, uniforms, log_priori, accepted_out, enthalpy_out, log_priori_out);
     bool priori_given = false; // a factor the Flip / Swap kernels do not model
     if (log_priori)
         for (size_t i = 0; i < n && !priori_given; ++i) priori_given = log_priori[i] == log_priori[i] && log_priori[i] != 0.0;
@@ -3208,6 +3218,7 @@ extern "C" int smolmc_eval_full(smolmc_handle *h, const int32_t *occ, int nocc, 
     hipFree(d_out);
     if (rc) return rc;
     if (e != hipSuccess) return fail(std::string("eval_full: ") + hipGetErrorString(e));
+    if (h->dist) return smolmc_dist_from_extensive(h, features, (size_t)nocc);
     return 0;
 }
 
@@ -3215,6 +3226,7 @@ extern "C" int smolmc_eval_delta(smolmc_handle *h, const int32_t *occ, const int
                                  double *dfeatures) {
     if (!h || !occ || !flips || !dfeatures) return fail("null argument");
     if (nstep <= 0) return 0;
+    if (h->dist) return smolmc_dist_eval_delta(h, occ, flips, nstep, dfeatures);
     HIPCHK(hipSetDevice(h->device));
     std::vector<int32_t> occ_engine, flips_engine;
     occ = occ_in(h, occ, 1, occ_engine);
@@ -3290,6 +3302,7 @@ extern "C" int smolmc_exchange_dev(smolmc_handle *h, int n_total, int first, int
                                    const double *ladder_dev, const double *log_u_dev, int32_t *rung_of_dev,
                                    int64_t *stats_dev) {
     if (!h || !enthalpy_all_dev || !ladder_dev || !log_u_dev || !rung_of_dev) return fail("null argument");
+    if (h->dist) return fail("a distance handle takes no replica exchange (its temperatures use the handle's kB)");
     if (n_total < 2 || n_total > 16384) return fail("exchange ladder must hold 2 .. 16384 walkers (the rung map lives in LDS)");
     if (first < 0 || first + h->R > n_total) return fail("this handle's walkers are out of range of the ladder");
     if (parity != 0 && parity != 1) return fail("parity must be 0 or 1");
@@ -3304,6 +3317,7 @@ extern "C" int smolmc_exchange_dev(smolmc_handle *h, int n_total, int first, int
 
 extern "C" int smolmc_import_temperature_dev(smolmc_handle *h, const double *src_dev) {
     if (!h || !src_dev) return fail("null argument");
+    if (h->dist) return fail("a distance handle takes no replica exchange (its temperatures use the handle's kB)");
     HIPCHK(hipSetDevice(h->device));
     hipLaunchKernelGGL(beta_from_T_kernel, dim3((h->R + 63) / 64), dim3(64), 0, h->stream, src_dev,
                        h->d_beta, h->R, SMOLMC_KB);

@@ -793,9 +793,23 @@ struct smolmc_handle {
     bool relabelled = false;
     uint32_t env_dispatch = 0;         // dispatch switches set at smolmc_create: bit e <-> SmolmcEnv e
     std::vector<int32_t> new_of, old_of; // caller's site -> engine's site, and back
+    // distance-objective handle (smolmc_create_distance, dist.hip): its kernels, objective and best records
+    struct DistState *dist = nullptr;
 };
 
 static void free_samples(smolmc_handle *h);
+// distance handles (dist.hip): the entry points of engine.hip hand such a handle over to these
+int smolmc_dist_free(smolmc_handle *h);
+int smolmc_dist_after_set_state(smolmc_handle *h, const double *temperature);
+int smolmc_dist_set_temperature(smolmc_handle *h, const double *temperature);
+int smolmc_dist_run(smolmc_handle *h, int64_t nsteps, const SampleBufs &smp);
+int smolmc_dist_replay(smolmc_handle *h, int64_t nsteps, const int32_t *steps_engine, const double *uniforms,
+                       const double *log_priori, uint8_t *accepted_out, double *enthalpy_out, double *log_priori_out);
+int smolmc_dist_from_extensive(const smolmc_handle *h, double *features, size_t nocc);
+int smolmc_dist_eval_delta(smolmc_handle *h, const int32_t *occ, const int32_t *flips, int nstep, double *dfeatures);
+int smolmc_dist_kernel_info(const smolmc_handle *h, char *buf, int n);
+// ... and engine.hip lends them its evaluation of extensive features (eval_full_kernel)
+int smolmc_eval_extensive(smolmc_handle *h, const uint8_t *d_occ8, int nocc, double *d_out);
 
 template <typename T>
 static int dev_upload(smolmc_handle *h, const T *src, size_t n, const T **dst) {

@@ -54,6 +54,10 @@ SYMBOLS = {
     "smolmc_set_stream": (C.c_int, [_HP, C.c_void_p]),
     "smolmc_export_enthalpy_dev": (C.c_int, [_HP, C.c_void_p]),
     "smolmc_import_temperature_dev": (C.c_int, [_HP, C.c_void_p]),
+    "smolmc_create_distance": (C.c_int, [C.POINTER(capi.smolmc_tables), C.POINTER(capi.smolmc_distance),
+                                         C.POINTER(capi.smolmc_config), C.POINTER(_HP)]),
+    "smolmc_get_best": (C.c_int, [_HP, _f64p, _f64p, _i32p, _u64p]),
+    "smolmc_reset_best": (C.c_int, [_HP]),
     "smolmc_exchange_dev": (C.c_int, [_HP, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
@@ -124,11 +128,15 @@ class RingFullError(EngineError):
 class Engine:
     """One engine handle = R walkers of one ensemble on one GPU."""
 
-    def __init__(self, tables: capi.TableSet, config: capi.smolmc_config):
+    def __init__(self, tables: capi.TableSet, config: capi.smolmc_config, distance: capi.DistanceSpec = None):
         self._lib = load_library()
-        self.tables, self.config = tables, config
+        self.tables, self.config, self.distance = tables, config, distance
         self._h = _HP()
-        rc = self._lib.smolmc_create(C.byref(tables.struct), C.byref(config), C.byref(self._h))
+        if distance is None:
+            rc = self._lib.smolmc_create(C.byref(tables.struct), C.byref(config), C.byref(self._h))
+        else:  # a distance-objective handle (smolmc_create_distance)
+            rc = self._lib.smolmc_create_distance(C.byref(tables.struct), C.byref(distance.struct), C.byref(config),
+                                                  C.byref(self._h))
         if rc:
             self._h = None
             self._chk(rc)
@@ -217,6 +225,19 @@ class Engine:
         )
         return dict(occupancy=occ, features=feat, enthalpy=H, n_accepted=na, n_steps=ns,
                     accepted=la.astype(bool))
+
+    def get_best(self):
+        """Distance handles: per walker the lowest enthalpy seen, its distance features, occupancy and step."""
+        score = np.empty(self.R)
+        feat = np.empty((self.R, self.F))
+        occ = np.empty((self.R, self.N), dtype=np.int32)
+        step = np.empty(self.R, dtype=np.uint64)
+        self._chk(self._lib.smolmc_get_best(self._h, _p(score, C.c_double), _p(feat, C.c_double),
+                                            _p(occ, C.c_int32), _p(step, C.c_uint64)))
+        return dict(score=score, features=feat, occupancy=occ, step=step)
+
+    def reset_best(self):
+        self._chk(self._lib.smolmc_reset_best(self._h))
 
     def get_enthalpy(self):
         """Current enthalpy of every walker (one device-to-host copy; the replica-exchange loop

@@ -380,6 +380,115 @@ class ClusterDecompositionProcessor(Processor):
         )
 
 
+class DistanceProcessor(Processor):
+    """Distance of the feature vector from a target (smol/moca/processor/distance.py:20-182):
+    ``d = -w L + ||W (f - f_T)||_1`` with L the largest diameter up to which every feature matches the target
+    within match_tol.  Features are the reference's intensive distance vector [L or 0, |f_1 - t_1|, ...].
+    ``supercell``: a supercell of the build's tables (synth / mson), or a cluster subspace together with
+    ``supercell_matrix`` (the reference's call shape).  Evaluated on a distance-objective engine handle
+    (smolmc_create_distance); an Ensemble / Sampler on such a processor runs the distance kernel."""
+
+    feature_mode = capi.FEATURES_CORRELATIONS
+
+    def __init__(self, supercell, supercell_matrix=None, target_vector=None, match_weight=1.0, match_tol=1e-5,
+                 target_weights=None, use_concentration=False):
+        if supercell_matrix is not None:  # (cluster_subspace, supercell_matrix)
+            from . import sqs
+
+            supercell, _ = sqs.distance_tables(supercell, supercell_matrix, self.feature_mode)
+        model = supercell.model
+        if len(getattr(model, "external_terms", []) or []) > 0:
+            raise ValueError("The given cluster subspace cannot have external terms.")  # distance.py:76-77
+        if use_concentration:
+            raise NotImplementedError("use_concentration: the build's tables carry the fitted site bases only")
+        if match_weight < 0:
+            raise ValueError("The match weight must be a positive number.")  # distance.py:79-80
+        if len(target_weights) != len(target_vector) - 1:  # distance.py:82-87
+            raise ValueError(
+                f"The length of target_weights must be equal to the length ofthe target vector minus one "
+                f"{len(target_vector) - 1}. \nGot {len(target_weights)} instead.")
+        self.target_vector = np.asarray(target_vector, dtype=np.float64)
+        self.match_tol = match_tol
+        super().__init__(supercell, np.concatenate([[-match_weight], target_weights]))  # distance.py:95
+        self._dist_engine = None
+
+    def distance_spec(self, kB=1.0):
+        """The capi.DistanceSpec of this objective (temperatures in units of kB)."""
+        from . import sqs
+
+        return sqs.distance_spec(self.cluster_subspace, self.feature_mode, self.target_vector, self.coefs[1:],
+                                 -self.coefs[0], self.match_tol, kB)
+
+    def _table_kwargs(self):
+        return dict(feature_mode=self.feature_mode,
+                    ce_coefs_expansion=np.ones(self.cluster_subspace.num_corr_functions),
+                    interaction_tensors=getattr(self, "_interaction_tensors", None))
+
+    def _engine(self):
+        if self._dist_engine is None:
+            self._eval_tables = self._make_tables()
+            self._dist_engine = Engine(self._eval_tables, capi.make_config(1, device=_eval_device()),
+                                       distance=self.distance_spec())
+        return self._dist_engine
+
+    def compute_feature_vector_distances(self, occupancy, flips):
+        """[distances before, distances after] the flips, entry 0 = 0 (evaluator.pyx:319-437)."""
+        occupancy = np.array(occupancy, dtype=np.int32)
+        occu_f = occupancy.copy()
+        for site, code in flips:
+            occu_f[site] = code
+        out = self._engine().eval_full(np.stack([occupancy, occu_f]))
+        out[:, 0] = 0.0
+        return out
+
+    def exact_match_max_diameter(self, distance_vector):
+        """Largest diameter for which all features are exactly matched (distance.py:307-332, :454-472)."""
+        from . import sqs
+
+        gd, fg = sqs.diameter_groups(self.cluster_subspace, self.feature_mode)
+        return sqs.exact_match_max_diameter(distance_vector, gd, fg, self.match_tol)
+
+
+class CorrelationDistanceProcessor(DistanceProcessor):
+    """Distance from a target correlation vector (distance.py:185-333)."""
+
+    feature_mode = capi.FEATURES_CORRELATIONS
+
+    def __init__(self, supercell, supercell_matrix=None, use_concentration=False, target_vector=None,
+                 match_weight=1.0, target_weights=None, match_tol=1e-5):
+        model = supercell.model if supercell_matrix is None else getattr(supercell, "subspace", supercell)
+        F = model.num_corr_functions
+        target_vector = np.zeros(F) if target_vector is None else target_vector
+        target_weights = np.ones(F - 1) if target_weights is None else target_weights
+        super().__init__(supercell, supercell_matrix, target_vector, match_weight, match_tol, target_weights,
+                         use_concentration)
+
+
+class ClusterInteractionDistanceProcessor(DistanceProcessor):
+    """Distance from a target cluster-interaction vector (distance.py:335-472); interaction tensors default to
+    those of every coefficient 1 (:392-404)."""
+
+    feature_mode = capi.FEATURES_INTERACTIONS
+
+    def __init__(self, supercell, supercell_matrix=None, interaction_tensors=None, use_concentration=False,
+                 target_vector=None, match_weight=1.0, target_weights=None, match_tol=1e-5):
+        model = supercell.model if supercell_matrix is None else getattr(supercell, "subspace", supercell)
+        F = model.num_orbits
+        target_vector = np.zeros(F) if target_vector is None else target_vector
+        target_weights = np.ones(F - 1) if target_weights is None else target_weights
+        if interaction_tensors is not None and len(interaction_tensors) != F:
+            raise ValueError(
+                f"The number of cluster interaction tensors must match the number  of orbits in the subspace. Got "
+                f"{len(interaction_tensors)} interaction tensors, but need {F}  for the given cluster_subspace.")
+        self._interaction_tensors = interaction_tensors
+        super().__init__(supercell, supercell_matrix, target_vector, match_weight, match_tol, target_weights,
+                         use_concentration)
+
+    @property
+    def interaction_tensors(self):
+        return self._interaction_tensors
+
+
 class EwaldProcessor(Processor):
     """Electrostatic feature (smol/moca/processor/ewald.py:26-203).
 
@@ -478,6 +587,8 @@ class Ensemble:
     """Thermodynamic ensemble (smol/moca/ensemble.py:102-430)."""
 
     def __init__(self, processor, sublattices=None, chemical_potentials=None):
+        if isinstance(processor, DistanceProcessor) and chemical_potentials is not None:
+            raise ValueError("a distance ensemble takes no chemical potentials")
         self._processor = processor
         self._sublattices = processor.get_sublattices() if sublattices is None else sublattices
         self.natural_parameters = np.array(processor.coefs, dtype=np.float64)  # ensemble.py:126
@@ -569,6 +680,8 @@ class Ensemble:
     def chemical_potentials(self, value):
         """ChemicalPotentialManager.__set__ (ensemble.py:35-73)."""
         had = self._chemical_potentials is not None
+        if value is not None and isinstance(self._processor, DistanceProcessor):
+            raise ValueError("a distance ensemble takes no chemical potentials")
         if value is None:
             if had:
                 self.natural_parameters = self.natural_parameters[:-1]
@@ -677,9 +790,15 @@ class Ensemble:
                      for s in self._sublattices))
         if getattr(self, "_eval_key", None) != key:
             self._eval_tables = self.make_tables()
-            self._eval_engine = Engine(self._eval_tables, capi.make_config(1, device=_eval_device()))
+            self._eval_engine = Engine(self._eval_tables, capi.make_config(1, device=_eval_device()),
+                                       distance=self.distance_spec())
             self._eval_key = key
         return self._eval_engine
+
+    def distance_spec(self, kB=1.0):
+        """The distance objective of an ensemble on a distance processor (None otherwise)."""
+        p = self._processor
+        return p.distance_spec(kB) if isinstance(p, DistanceProcessor) else None
 
     def compute_feature_vector(self, occupancy):
         """ensemble.py:323-351."""
@@ -1596,6 +1715,7 @@ class Sampler:
         for sub in ens.sublattices:
             h.update(np.ascontiguousarray(sub.active_sites, dtype=np.int64).tobytes() + b"|")
             h.update(np.ascontiguousarray(sub.encoding, dtype=np.int64).tobytes() + b"/")
+        h.update(repr(getattr(k0, "kB", None)).encode())  # (a distance handle's temperatures are in units of kB)
         if k0.bias is not None:
             h.update(np.ascontiguousarray(k0.bias._table).tobytes())
             h.update(repr((k0.bias.bias_type, k0.bias.penalty)).encode())
@@ -1615,6 +1735,13 @@ class Sampler:
         key = self._model_key()
         if self._engine is None or self._engine_key != key:
             tables = ens.make_tables(**k0.usher_kwargs)
+            dist = None
+            if isinstance(ens.processor, DistanceProcessor):
+                if not isinstance(k0, Metropolis):
+                    raise ValueError("a distance ensemble runs the Metropolis kernel only")
+                if k0.bias is not None:
+                    raise ValueError("a distance ensemble takes no bias term")
+                dist = ens.distance_spec(kB=k0.kB)
             if k0.bias is not None:
                 tables.set_bias(k0.bias.bias_type, k0.bias._table, k0.bias.penalty,
                                 intercepts=getattr(k0.bias, "intercepts", None))
@@ -1631,7 +1758,7 @@ class Sampler:
             else:
                 cfg = capi.make_config(len(self._kernels), capi.KERNEL_METROPOLIS,
                                        STEP_TYPES[k0.step_type], self._device)
-            self._engine = Engine(tables, cfg)
+            self._engine = Engine(tables, cfg, distance=dist)
             self._engine_key = key
             self._state_loaded = False
         return self._engine

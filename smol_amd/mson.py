@@ -200,9 +200,10 @@ def _pbc_match_all_pairs(points, targets, atol=SITE_TOL):
 class MsonOrbit:
     """One orbit of the serialized ClusterSubspace (orbit.py:564-600)."""
 
-    def __init__(self, d, oid, bit_id):
+    def __init__(self, d, oid, bit_id, lattice=None):
         self.id, self.bit_id = oid, bit_id
         self.frac_coords = np.asarray(d["sites"], dtype=np.float64)  # base cluster, prim basis
+        self.lattice = None if lattice is None else np.asarray(lattice, dtype=np.float64)
         self.bits = [list(b) for b in d["bits"]]
         self.symops = [np.asarray(s["matrix"], dtype=np.float64) for s in d["structure_symops"]]
         # site bases: rows phi_0 == 1, phi_1 .. phi_{S-1} (basis.py:207-222); the evaluator uses
@@ -216,6 +217,17 @@ class MsonOrbit:
         self._clusters = None
 
     num_sites = property(lambda self: len(self.frac_coords))
+
+    @property
+    def diameter(self):
+        """Largest pairwise Cartesian distance of the base cluster's sites (smol's Cluster.diameter), 0 for a
+        point cluster."""
+        if self.lattice is None:
+            raise AttributeError("orbit built without its lattice: no diameter")
+        cart = self.frac_coords @ self.lattice
+        if len(cart) < 2:
+            return 0.0
+        return float(np.max(np.linalg.norm(cart[:, None, :] - cart[None, :, :], axis=-1)))
     bit_combo_multiplicities = property(lambda self: [len(c) for c in self.bit_combos])
 
     def __len__(self):
@@ -289,7 +301,7 @@ class MsonSubspace:
         oid = bit = 1
         for size in sorted(d["orbits"], key=int):  # clusterspace.py:1303-1306
             for od in d["orbits"][size]:
-                orb = MsonOrbit(od, oid, bit)
+                orb = MsonOrbit(od, oid, bit, self.lattice)
                 self.orbits.append(orb)
                 oid += 1
                 bit += len(orb)
