@@ -26,6 +26,11 @@ steps (one swap step = 2 attempted flips).  value = attempted flips/s over the w
 --dump-outputs DIR  after the timed steps, the state they left on rank 0's walkers as DIR/<name>.npy
                  (enthalpy, features, counters of every walker; the occupancy of a seeded sample of
                  512 walkers): the inputs are seeded, so two builds can be compared output for output
+--full           also measure what the headline figure does not need, after its timed steps: the
+                 other configurations (`other_configs`), the CPU oracle (`cpu_baseline`), the live
+                 HBM probe of the roofline and, at N > 1 with --scaling weak, the 4096-walkers-in-total
+                 figure.  --no-other-configs, --no-cpu-baseline and --no-strong leave one of them out.
+                 Without --full a run sets up, warms up, times its steps, dumps and prints its line.
 """
 
 import argparse
@@ -275,7 +280,7 @@ def launch_ranks(args, argv):
 
 
 # --------------------------------------------------------------------------------------
-# other configurations (after the headline's timed region)
+# other configurations (--full: after the headline's timed region)
 #   one rank : configs 1, 3, 4, 5
 #   N ranks  : configs 4 and 5, the two BASELINE.json defines as N-rank workloads -- config 4 as
 #              1024 independent Wang-Landau walkers per rank, config 5 as ONE temperature ladder
@@ -734,9 +739,13 @@ def main():
                     help="walkers per GPU (weak) or in total (strong)")
     ap.add_argument("--mc-per-step", type=int, default=MC_PER_STEP)
     ap.add_argument("--features", choices=("interactions", "correlations"), default="interactions")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--no-strong", action="store_true", help="skip the 4096-walkers-in-total measurement on N > 1 ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run other_configs, cpu_baseline, the live HBM probe and (N > 1) "
+                         "the strong-scaling figure")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip other_configs")
+    ap.add_argument("--no-strong", action="store_true",
+                    help="with --full: skip the 4096-walkers-in-total measurement on N > 1 ranks")
     ap.add_argument("--dry-run", action="store_true")
     ap.add_argument("--oversubscribe", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -875,9 +884,9 @@ def main():
         dist.all_reduce(kms_lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(kms_hi, op=dist.ReduceOp.MAX)
     # north_star's "at 4096 replicas" next to the weak figure: 4096 walkers IN TOTAL, 4096 / N per GPU,
-    # the same number of launches (one rank: the headline measurement is that figure already)
+    # the same number of launches (one rank: the headline measurement is that figure already); --full only
     strong = None
-    if world > 1 and args.scaling == "weak" and not args.no_strong:
+    if world > 1 and args.scaling == "weak" and args.full and not args.no_strong:
         eng.close()
         f2, R2 = parallel.shard(N_REPLICAS, rank, world)
         wl2 = workloads.config2(f2, R2, feature_mode=mode, mc=args.mc_per_step)
@@ -913,8 +922,15 @@ def main():
 
         # the counters were collected on the kernel whose machine-code digest the entry carries (codeobj.py)
         pmc_stale = codeobj.isa_stale(pmc)
-        probe = measure_hbm_peak()
+        # the live probe is a run of its own (6 GiB of arrays): --full only, else the committed figure
+        probe = measure_hbm_peak() if args.full else None
         measured_peak = max(probe.values()) if probe else HBM_MEASURED_FALLBACK_GBS
+        if probe:
+            peak_source = "live read / triad probe over 2 GiB float64 arrays: " + json.dumps(probe)
+        elif args.full:
+            peak_source = "tools/hbm_triad.py figure on MI355X (live probe failed)"
+        else:
+            peak_source = "tools/hbm_triad.py figure on MI355X (the live probe runs with --full)"
         roof = {
             "bound": "hbm",
             "kernel": eng.kernel_info(),
@@ -923,8 +939,7 @@ def main():
             "unit": "GB/s",
             "frac": achieved / HBM_PEAK_GBS,
             "measured_peak": measured_peak,
-            "measured_peak_source": ("live read / triad probe over 2 GiB float64 arrays: " + json.dumps(probe))
-            if probe else "tools/hbm_triad.py figure of this pool (live probe failed)",
+            "measured_peak_source": peak_source,
             "frac_of_measured_peak": achieved / measured_peak,
             "pmc_stale": pmc_stale,
             "traffic": pmc.get("hbm_bytes_per_launch"),
@@ -982,7 +997,7 @@ def main():
         }
         assert int(n_walk) == total_walkers
     eng.close()
-    # Every rank takes part in the N-rank forms of configs 4 / 5 (rank 0 reports).  The headline
+    # With --full, every rank takes part in the N-rank forms of configs 4 / 5 (rank 0 reports).  The headline
     # line must survive whatever happens there: a rank that fails alone leaves the others inside a
     # collective, so on N ranks a watchdog ends every rank after OTHER_CONFIGS_TIMEOUT_S, rank 0
     # printing the line with what it has.
@@ -1000,15 +1015,16 @@ def main():
         emit()
         os._exit(0)
 
+    other_configs = args.full and not args.no_other_configs
     watchdog = None
-    if world > 1:
+    if world > 1 and other_configs:
         import threading
 
         watchdog = threading.Timer(OTHER_CONFIGS_TIMEOUT_S, bail)
         watchdog.daemon = True
         watchdog.start()
     other = None
-    if not args.no_other_configs:
+    if other_configs:
         try:
             other = time_other_configs(device, rank, world, red_dev)
         except Exception as exc:  # the headline measurement must not be lost with it
@@ -1018,7 +1034,7 @@ def main():
     if rank == 0:
         if other is not None:
             out["other_configs"] = other
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline()
                 out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]

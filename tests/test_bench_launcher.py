@@ -123,3 +123,28 @@ def test_dump_outputs_are_the_state_after_the_timed_steps(tmp_path):
     assert a["enthalpy"].shape == (256,) and a["occupancy_sample"].shape == (256, 4096)
     for k in a:
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone():
+    """Without --full the line is the headline and its roofline from the committed PMC figures: nothing that takes
+    runs of its own (other configurations, the CPU oracle, the live HBM probe)."""
+    out = _run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--mc-per-step", "2000",
+                "--replicas", "256"])
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = _line(out)
+    assert rec["unit"] == "attempted flips/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["steps"] == 2 and rec["warmup"] == 1
+    assert not {"other_configs", "cpu_baseline", "gpu_over_cpu"} & set(rec)
+    assert "runs with --full" in rec["roofline"]["measured_peak_source"]
+
+
+@pytest.mark.gpu
+def test_full_run_takes_the_live_hbm_probe():
+    """--full measures the HBM peak live; --no-other-configs / --no-cpu-baseline still leave those two out."""
+    out = _run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--mc-per-step", "2000",
+                "--replicas", "256", "--full", "--no-other-configs", "--no-cpu-baseline"])
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = _line(out)
+    assert rec["roofline"]["measured_peak_source"].startswith("live read / triad probe")
+    assert not {"other_configs", "cpu_baseline"} & set(rec)
