@@ -264,7 +264,7 @@ extern "C" int smolmc_create_distance(const smolmc_tables *t, const smolmc_dista
         smolmc_destroy(h);
         return rc;
     };
-    h->lean = h->univ = false; // (no other family runs on this handle)
+    h->family = K_GENERAL; // (no other family runs on this handle)
     DistState *Dp = new DistState();
     h->dist = Dp;
     DistState &D = *Dp;

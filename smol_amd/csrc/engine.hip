@@ -1239,6 +1239,909 @@ extern "C" int smolmc_create(const smolmc_tables *t, const smolmc_config *cfg, s
     return create_impl(&rt.t, cfg, out, &new_of); // (the engine copies every table at create: rt may go)
 }
 
+// ---- smolmc_create stage by stage.  Every stage returns 0 or the code of its fail(); create_impl lists them in
+// order and destroys the handle when one refuses.
+static bool is_wl(const smolmc_handle *h) { return h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU; }
+static bool is_table(const smolmc_handle *h) { return h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP; }
+// Wang-Landau keeps per-bin feature sums at update_period 1, running means otherwise
+static int wl_sum_mode_of(const smolmc_handle *h) { return (h->cfg.wl_update_period == 1 && !smolmc_env(ENV_WL_RUNNING_MEAN)) ? 1 : 0; }
+static int cu_count(const smolmc_handle *h) {
+    int cus = 0;
+    return hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess ? cus : 256;
+}
+// ln(k) for k <= top from the host libm (the oracle's log-factorial sums use the same); cell 0 is 0
+static std::vector<double> ln_table(int top) {
+    std::vector<double> ln((size_t)top + 1, 0.0);
+    for (int k = 1; k <= top; ++k) ln[k] = std::log((double)k);
+    return ln;
+}
+
+// dimensions, natural parameters and the Wang-Landau window
+static int create_dimensions(smolmc_handle *h, const smolmc_tables *t) {
+    const smolmc_config *cfg = &h->cfg;
+    h->R = cfg->n_replicas;
+    h->N = t->num_sites;
+    h->Npad = (t->num_sites + 15) / 16 * 16;
+    h->Fce = num_ce_features(t);
+    h->F = h->Fce + (t->has_ewald ? 1 : 0) + (t->has_mu ? 1 : 0);
+    h->natural.assign(t->ce_coefs, t->ce_coefs + h->Fce);
+    if (t->has_ewald) h->natural.push_back(t->ewald_coef);
+    if (t->has_mu) h->natural.push_back(-1.0);
+    if (is_wl(h)) {
+        if (cfg->wl_min_enthalpy > cfg->wl_max_enthalpy)
+            return fail("min_enthalpy can not be larger than max_enthalpy."); // wanglandau.py:82
+        if ((cfg->wl_max_enthalpy - cfg->wl_min_enthalpy) / cfg->wl_bin_size <= 1)
+            return fail("The values provided for min and max enthalpy and bin sizer result in a "
+                        "single bin!");
+        if (cfg->wl_mod_factor <= 0) return fail("mod_factor must be greater than 0.");
+        h->L = (int)ceil((cfg->wl_max_enthalpy - cfg->wl_min_enthalpy) / cfg->wl_bin_size);
+    }
+    memset(&h->kp, 0, sizeof(KParams));
+    return 0;
+}
+
+// (validate_tables(t) has passed: smolmc_create runs it on the caller's tables before any renaming)
+// species codes a site may carry: max_species by default, the largest sublattice code + 1 on
+// the sites of an active sublattice
+static int create_site_codes(smolmc_handle *h, const smolmc_tables *t) {
+    h->site_ncodes.assign((size_t)t->num_sites, (uint8_t)std::min(255, std::max(1, t->max_species)));
+    h->site_active.assign((size_t)t->num_sites, 0);
+    for (int k = 0; k < t->n_sublattices; ++k) {
+        int top = 0;
+        for (int64_t c = t->sub_code_ptr[k]; c < t->sub_code_ptr[k + 1]; ++c) top = std::max(top, t->sub_codes[c]);
+        for (int64_t i = t->sub_site_ptr[k]; i < t->sub_site_ptr[k + 1]; ++i) {
+            const int st = t->sub_active_sites[i];
+            if (st >= 0 && st < t->num_sites) {
+                h->site_ncodes[st] = (uint8_t)std::min(255, top + 1);
+                h->site_active[st] = 1;
+            }
+        }
+    }
+    // ... and on every other site the width of its site space as the cluster tensors see it: member m of
+    // an orbit's rows has prev_stride / stride species (see validate_tables); a code beyond that would
+    // index past the tensors
+    std::vector<int> seen((size_t)t->num_sites, 0);
+    for (int o = 0; o < t->n_orb; ++o) {
+        const int I = t->orb_nsites[o];
+        const int32_t *st = t->tensor_indices + t->orb_stride_off[o];
+        for (int64_t i = t->full_off[o]; i < t->full_off[o + 1]; ++i) {
+            const int m = (int)((i - t->full_off[o]) % I);
+            const int width = (int)((m == 0 ? t->orb_tensor_len[o] : st[m - 1]) / st[m]);
+            const int site = t->full_idx[i];
+            seen[site] = seen[site] ? std::min(seen[site], width) : width;
+        }
+    }
+    for (int s = 0; s < t->num_sites; ++s)
+        if (!h->site_active[s] && seen[s]) h->site_ncodes[s] = (uint8_t)std::min<int>(h->site_ncodes[s], std::min(255, seen[s]));
+    return 0;
+}
+
+// the model's part of mc_kernel's parameter block (the tables are in h->rt by now)
+static int create_model_params(smolmc_handle *h, const smolmc_tables *t) {
+    KParams &kp = h->kp;
+    kp.N = h->N;
+    kp.Npad = h->Npad;
+    kp.Fce = h->Fce;
+    kp.F = h->F;
+    kp.step_type = h->cfg.step_type;
+    kp.corr_mode = h->rt.corr_mode;
+    kp.has_ewald = t->has_ewald;
+    kp.has_mu = t->has_mu;
+    kp.ew_W = h->rt.ew_W;
+    kp.ew_M = h->rt.ew_M;
+    kp.mu_W = h->rt.mu_W;
+    kp.ew_inds = h->rt.ew_inds;
+    kp.ew_Mt = h->rt.ew_Mt;
+    kp.ew_coef = t->ewald_coef;
+    kp.mu = h->rt.mu;
+    return 0;
+}
+
+// MCBias (smol/moca/kernel/bias.py)
+static int create_bias(smolmc_handle *h, const smolmc_tables *t) {
+    if (!t->bias_type) return 0;
+    const smolmc_config *cfg = &h->cfg;
+    KParams &kp = h->kp;
+    if (t->bias_type != SMOLMC_BIAS_FUGACITY && t->bias_type != SMOLMC_BIAS_SQUARE_CHARGE &&
+        t->bias_type != SMOLMC_BIAS_SQUARE_HYPERPLANE)
+        return fail("unknown bias_type");
+    const int brows = t->bias_type == SMOLMC_BIAS_SQUARE_HYPERPLANE ? t->bias_rows : 1;
+    if (brows < 1 || brows > SMOLMC_MAX_BIAS_ROWS)
+        return fail("bias_rows must be in [1, SMOLMC_MAX_BIAS_ROWS]");
+    if (is_wl(h)) return fail("Cannot apply bias to Wang-Landau simulation!"); // wanglandau.py:127-128
+    if (!t->bias_table || t->bias_width < t->max_species)
+        return fail("bias_table must be [num_sites x >= max_species]");
+    if (t->bias_type != SMOLMC_BIAS_FUGACITY && !(t->bias_penalty > 0.0))
+        return fail("Penalty factor should be > 0!"); // bias.py:250-251, :328-329
+    h->bias_host.assign(t->bias_table, t->bias_table + (size_t)brows * t->num_sites * t->bias_width);
+    h->bias_icpt.assign(SMOLMC_MAX_BIAS_ROWS, 0.0);
+    if (t->bias_type == SMOLMC_BIAS_SQUARE_HYPERPLANE && t->bias_intercepts)
+        for (int k = 0; k < brows; ++k) h->bias_icpt[k] = t->bias_intercepts[k];
+    kp.bias_rows = brows;
+    kp.bias_row_stride = (size_t)t->num_sites * t->bias_width;
+    if (t->bias_type == SMOLMC_BIAS_FUGACITY)
+        for (double v : h->bias_host)
+            if (!(v > 0.0)) return fail("fugacity fractions must be positive");
+    kp.bias_type = t->bias_type;
+    kp.bias_W = t->bias_width;
+    kp.bias_pen = t->bias_penalty;
+    if (dev_upload(h, h->bias_host.data(), h->bias_host.size(), &kp.bias_tab)) return 1;
+    if (dev_alloc(h, (size_t)cfg->n_replicas, &kp.bias) ||
+        dev_alloc(h, (size_t)cfg->n_replicas * SMOLMC_MAX_BIAS_ROWS, &kp.charge))
+        return 1;
+    return 0;
+}
+
+// compact Ewald form and the potential field of every walker in HBM: the field needs the compact form
+// and contiguous changeable sites; the lean kernels stage the same buffer through LDS
+static int create_ewald_field(smolmc_handle *h, const smolmc_tables *t) {
+    KParams &kp = h->kp;
+    if (t->has_ewald && t->ewald_charges && !smolmc_env(ENV_DENSE_EWALD))
+        if (int rc = build_compact_ewald(h, t)) return rc;
+    kp.ew_field = 0;
+    if (kp.ew_compact && kp.ew_act_base >= 0 && (size_t)kp.ew_nact * 8 <= 150 * 1024 &&
+        !smolmc_env(ENV_NO_EWALD_FIELD)) {
+        if (dev_alloc(h, (size_t)h->cfg.n_replicas * kp.ew_nact, &kp.ew_phi)) return 1;
+        kp.ew_field = 1;
+    }
+    return 0;
+}
+
+// the active sites of sublattice k are one site range
+static bool lean_site_range(const smolmc_tables *t, int k) {
+    const int64_t a0 = t->sub_site_ptr[k], a1 = t->sub_site_ptr[k + 1];
+    for (int64_t i = a0; i < a1; ++i)
+        if (t->sub_active_sites[i] != t->sub_active_sites[a0] + (int)(i - a0)) return false;
+    return true;
+}
+static int create_sublattices(smolmc_handle *h, const smolmc_tables *t) {
+    KParams &kp = h->kp;
+    const int ns = t->n_sublattices;
+    if (ns <= 0) return fail("no active sublattice");
+    std::vector<int> ptr(ns + 1), cptr(ns + 1), base(ns);
+    std::vector<double> cum(ns);
+    double c = 0;
+    for (int s = 0; s <= ns; ++s) {
+        ptr[s] = (int)t->sub_site_ptr[s];
+        cptr[s] = (int)t->sub_code_ptr[s];
+    }
+    for (int s = 0; s < ns; ++s) {
+        c += t->sub_probs[s];
+        cum[s] = c;
+        const int a = ptr[s], b = ptr[s + 1];
+        if (b <= a) return fail("empty active sublattice");
+        base[s] = lean_site_range(t, s) ? t->sub_active_sites[a] : -1;
+        for (int i = a; i < b; ++i)
+            if (t->sub_active_sites[i] < 0 || t->sub_active_sites[i] >= t->num_sites)
+                return fail("sublattice site index out of range");
+    }
+    kp.nsub = ns;
+    if (dev_upload(h, ptr.data(), ptr.size(), &kp.sub_ptr) ||
+        dev_upload(h, t->sub_active_sites, (size_t)ptr[ns], &kp.sub_sites) ||
+        dev_upload(h, base.data(), base.size(), &kp.sub_base) ||
+        dev_upload(h, cptr.data(), cptr.size(), &kp.sub_code_ptr) ||
+        dev_upload(h, t->sub_codes, (size_t)cptr[ns], &kp.sub_codes) ||
+        dev_upload(h, cum.data(), cum.size(), &kp.sub_cum))
+        return 1;
+    return 0;
+}
+
+static int create_walker_state(smolmc_handle *h, const smolmc_tables *) {
+    KParams &kp = h->kp;
+    const size_t R = h->R;
+    kp.R = h->R;
+    double *dbeta = nullptr;
+    uint64_t *dseeds = nullptr;
+    if (dev_alloc(h, R * h->Npad, &kp.occ) || dev_alloc(h, R, &kp.enthalpy) ||
+        dev_alloc(h, R * h->F, &kp.features) || dev_alloc(h, R, &dbeta) || dev_alloc(h, R, &dseeds) ||
+        dev_alloc(h, R, &kp.nsteps) || dev_alloc(h, R, &kp.nacc) || dev_alloc(h, R, &kp.last_acc))
+        return 1;
+    kp.beta = dbeta;
+    h->d_beta = dbeta;
+    kp.seeds = dseeds;
+    if (dev_upload(h, h->natural.data(), h->natural.size(), (const double **)&h->d_natural))
+        return 1;
+    return 0;
+}
+
+static int create_wl_state(smolmc_handle *h, const smolmc_tables *) {
+    if (!is_wl(h)) return 0;
+    const smolmc_config *cfg = &h->cfg;
+    KParams &kp = h->kp;
+    const size_t R = h->R;
+    kp.L = h->L;
+    kp.wl_min = cfg->wl_min_enthalpy;
+    kp.wl_max = cfg->wl_max_enthalpy;
+    kp.wl_bin = cfg->wl_bin_size;
+    kp.wl_flat = cfg->wl_flatness;
+    kp.wl_div = cfg->wl_mod_divisor;
+    kp.wl_check = cfg->wl_check_period;
+    kp.wl_update = cfg->wl_update_period;
+    kp.wl_sum_mode = wl_sum_mode_of(h);
+    // (check period 0: the flatness check is the caller's -- a host-side mod_update callable,
+    // wanglandau.py:100-105 -- and no kernel runs its own)
+    if (kp.wl_check < 0 || kp.wl_update <= 0) return fail("WL periods must be positive");
+    // (the lane-indexed feature bookkeeping of mc_kernel / mc_wl_kernel holds 64 features; more -- the
+    // reference has no limit, wanglandau.py:117-118 -- take the universal kernel)
+    if (h->F > 64 && h->general_ok) no_general(h, "Wang-Landau with more than 64 features");
+    if (dev_alloc(h, R * h->L, &kp.wl_entropy) || dev_alloc(h, R * h->L, &kp.wl_hist) ||
+        dev_alloc(h, R * h->L, &kp.wl_occur) || dev_alloc(h, R * h->L * h->F + 64, &kp.wl_meanf) || // (+64: the lean kernel's all-lane atomic, see mc_lean.h)
+        dev_alloc(h, R, &kp.wl_m) || dev_alloc(h, R, &kp.wl_counter))
+        return 1;
+    std::vector<double> m0(R, cfg->wl_mod_factor);
+    if (hipMemcpy(kp.wl_m, m0.data(), R * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail("hipMemcpy failed");
+    return 0;
+}
+
+// LDS layout of mc_kernel
+static int create_general_layout(smolmc_handle *h, const smolmc_tables *) {
+    KParams &kp = h->kp;
+    size_t tb = (size_t)kp.nclasses * kp.Cpad * (16 + 16 + 8) + (size_t)(kp.xt_len + kp.ft_len) * 8 +
+                (size_t)((kp.nclasses + 3) & ~3) * 4 + (kp.nclasses > 1 ? (size_t)h->N : 0);
+    tb = (tb + 15) / 16 * 16;
+    size_t pw = (size_t)h->Npad;
+    if (is_wl(h))
+        pw += (size_t)h->L * 24 + (size_t)h->F * 8;
+    else {
+        const size_t by_feat = (size_t)h->Fce * 64 * 8;
+        const size_t by_slot = ((size_t)kp.nclasses * kp.Cpad + h->Fce) * 8;
+        kp.acc_by_slot = (!kp.corr_mode && by_slot < by_feat) ? 1 : 0;
+        pw += kp.acc_by_slot ? by_slot : by_feat;
+    }
+    pw = (pw + 15) / 16 * 16;
+    kp.lds_tables = (int)tb;
+    kp.lds_per_wave = (int)pw;
+    h->waves_per_block = 4;
+    while (h->waves_per_block > 1 && tb + pw * h->waves_per_block > 160 * 1024) h->waves_per_block /= 2;
+    h->lds_bytes = tb + pw * h->waves_per_block;
+    if (h->general_ok && h->lds_bytes > 160 * 1024)
+        no_general(h, "tables + one chain exceed the 160 KiB LDS budget of mc_kernel");
+    return 0;
+}
+
+// ---- the lean planners (everything they leave runs mc_kernel or the universal kernel).  Each first decides --
+// host arithmetic on the tables, the config, what the earlier stages left on the handle and the CU count -- and
+// only a planner that has said yes fills h->lp and uploads: a handle's LeanParams is written by one planner.
+
+// features the lean kernels carry (lazy cluster features: the scalar ones only -- Ewald energy, chemical work)
+static int lean_features(const smolmc_handle *h, const smolmc_tables *t) { return h->lazy_tables ? (t->has_ewald ? 1 : 0) + (t->has_mu ? 1 : 0) : h->F; }
+static const char *const lean_why_species = "an active sublattice of fewer than 2 or more than 8 species";
+static const char *const lean_why_codes = "a sublattice whose species codes are not 0 .. n-1 (split by species) under a step type that draws codes";
+// Species codes of sublattice k: 0 .. n-1, or -- canonical swaps only, which never draw a code: they exchange the
+// two sites' own -- any code list (a sublattice split by species, sublattice.py:109-186, keeps the site space's
+// codes: {1, 2} of three); the per-code rows (mu, charges, bias pairs) then run up to the largest code.
+// -> the number of codes those rows hold, or 0 with the reason in *why
+static int lean_code_count(const smolmc_handle *h, const smolmc_tables *t, int k, const char **why) {
+    const int32_t *codes = t->sub_codes + t->sub_code_ptr[k];
+    const int nc = (int)(t->sub_code_ptr[k + 1] - t->sub_code_ptr[k]);
+    bool default_codes = true;
+    int top = 0;
+    for (int c = 0; c < nc; ++c) {
+        default_codes = default_codes && codes[c] == c;
+        top = std::max(top, (int)codes[c]);
+    }
+    *why = (nc < 2 || nc > 8) ? lean_why_species : (!default_codes && !(h->cfg.step_type == SMOLMC_STEP_SWAP && top < 8)) ? lean_why_codes : nullptr;
+    return *why ? 0 : (default_codes ? nc : top + 1);
+}
+// the first ncol columns of a per-site table [site][width] are the same on the n sites from site0 on
+static bool row_uniform(const double *tab, int width, int site0, int n, int ncol) {
+    for (int i = 0; i < n; ++i)
+        for (int c = 0; c < ncol; ++c)
+            if (tab[(size_t)(site0 + i) * width + c] != tab[(size_t)site0 * width + c]) return false;
+    return true;
+}
+// Bias pair tables of one sublattice (sites sb .. sb + na - 1, nc codes): pairs[row * row_stride + old * 8 + new].
+// false: a bias row differs between its sites (the bias is defined per sublattice)
+static bool lean_bias_pairs(const smolmc_handle *h, const smolmc_tables *t, int brows, int sb, int na, int nc, double *pairs, size_t row_stride) {
+    const int W = t->bias_width;
+    for (int rw = 0; rw < brows; ++rw) {
+        const double *tabk = h->bias_host.data() + (size_t)rw * t->num_sites * W;
+        if (!row_uniform(tabk, W, sb, na, nc)) return false;
+        for (int o = 0; o < nc; ++o)
+            for (int n = 0; n < nc; ++n) {
+                const double a = tabk[(size_t)sb * W + n], b = tabk[(size_t)sb * W + o];
+                pairs[(size_t)rw * row_stride + o * 8 + n] = t->bias_type == SMOLMC_BIAS_FUGACITY ? std::log(a / b) : a - b;
+            }
+    }
+    return true;
+}
+// Charge / diagonal term per species code of the n sites from sb on (8 cells each): false when they depend on the site
+static bool lean_ewald_rows(const smolmc_handle *h, int sb, int n, double *q, double *dg) {
+    const int W = h->kp.ew_W;
+    if (W > 8 || !row_uniform(h->ew_qs_host.data(), W, sb, n, W) || !row_uniform(h->ew_dg_host.data(), W, sb, n, W)) return false;
+    std::copy_n(&h->ew_qs_host[(size_t)sb * W], W, q);
+    std::copy_n(&h->ew_dg_host[(size_t)sb * W], W, dg);
+    return true;
+}
+// the mu delta of a step joins the float32 sum (<= 2 flips * 2 |mu|): mmax = the largest |mu| of the rows in use
+static void lean_widen_fast_eps(const smolmc_tables *t, LeanParams &lp, double mmax) {
+    if (t->has_mu) lp.fast_eps += 4.0 * mmax * ldexp(1.0, -19);
+    // test hook: widen the undecided band so that both decision paths interleave
+    if (const char *sc = smolmc_env(ENV_FAST_EPS_SCALE)) lp.fast_eps *= atof(sc);
+}
+// the walker state, the bias and the Wang-Landau block of LeanParams (pointers and dimensions of mc_kernel's)
+static void lean_fill_state(const smolmc_handle *h, const smolmc_tables *t, LeanParams &lp, int bias_row_stride, int wl_sums) {
+    const KParams &kp = h->kp;
+    lp.occ = kp.occ; lp.enthalpy = kp.enthalpy; lp.features = h->lazy_tables ? h->d_lazy_scal : kp.features; lp.beta = kp.beta;
+    lp.seeds = kp.seeds; lp.nsteps = kp.nsteps; lp.nacc = kp.nacc; lp.last_acc = kp.last_acc;
+    lp.R = h->R; lp.N = h->N; lp.Npad = h->Npad; lp.F = lean_features(h, t); lp.Fce = h->lazy_tables ? 0 : h->Fce;
+    if (t->has_ewald) {
+        lp.ew_W = kp.ew_W; lp.ew_nact = kp.ew_nact; lp.ew_act_base = kp.ew_act_base;
+        lp.ew_G = kp.ew_G; lp.ew_coef = kp.ew_coef;
+        lp.ew_gx = kp.ew_gx; lp.ew_E8 = kp.ew_E8; lp.ew_S8 = kp.ew_S8;
+    }
+    if (t->bias_type) {
+        lp.bias_type = t->bias_type;
+        lp.bias_pen = t->bias_penalty;
+        lp.bias = kp.bias;
+        lp.charge = kp.charge;
+        lp.bias_rows = kp.bias_rows;
+        lp.bias_row_stride = bias_row_stride;
+    }
+    if (is_wl(h)) {
+        lp.wl.L = h->L;
+        lp.wl.vmin = kp.wl_min; lp.wl.vmax = kp.wl_max; lp.wl.bin = kp.wl_bin;
+        lp.wl.flat = kp.wl_flat; lp.wl.div = kp.wl_div;
+        lp.wl.check = kp.wl_check; lp.wl.update = kp.wl_update;
+        lp.wl.entropy = kp.wl_entropy; lp.wl.hist = kp.wl_hist; lp.wl.occur = kp.wl_occur;
+        lp.wl.meanf = kp.wl_meanf; lp.wl.m = kp.wl_m; lp.wl.counter = kp.wl_counter;
+        lp.wl.sum_mode = wl_sums;
+    }
+}
+// the flip table of a TableFlip handle (dims columns), its weights and ln(k) for k <= ln_top
+static int lean_fill_table(smolmc_handle *h, const smolmc_tables *t, LeanParams &lp, int dims, int ln_top, int ln_len) {
+    const std::vector<double> ln = ln_table(ln_top);
+    if (dev_upload(h, t->flip_table, (size_t)t->n_flip_vectors * dims, &lp.tf_table) ||
+        dev_upload(h, t->flip_weights, (size_t)2 * t->n_flip_vectors, &lp.tf_w) ||
+        dev_upload(h, ln.data(), ln.size(), &lp.tf_ln))
+        return 1;
+    lp.tf_n = t->n_flip_vectors;
+    lp.tf_sw = t->swap_weight;
+    lp.tf_ln_len = ln_len; // cells of tf_ln the kernel keeps in LDS
+    return 0;
+}
+
+// ---- one site class, one contiguous sublattice: mc_lean_kernel, mc_wl_kernel, mc_table_kernel
+struct LeanPlan {
+    bool take = false;
+    bool late = false;  // refused after the early checks, at the LDS stage (see plan_lean_multi: fast_eps)
+    int sbase = -1, nact = 0, nc = 0;
+    std::vector<double> mu_row, bias_pair, qrow, dgrow;
+    bool field = false; // potential field in LDS
+    bool solo = false;
+    int occ = 0, wpb = 4, tf_ln_len = 0;
+    size_t lds = 0, lds8 = 0;
+};
+static LeanPlan decide_lean(const smolmc_handle *h, const smolmc_tables *t) {
+    const smolmc_config *cfg = &h->cfg;
+    const KParams &kp = h->kp;
+    const LeanParams &lp = h->lp; // (build_mc_tables has left the table sizes there)
+    const bool wl = is_wl(h), table = is_table(h);
+    const int wl_sum_mode = wl_sum_mode_of(h), Fk = lean_features(h, t), brows = kp.bias_rows;
+    LeanPlan p;
+    // (lean Wang-Landau keeps per-bin feature SUMS: update_period 1 only, see WlParams)
+    // (... the Wang-Landau TableFlip kernel, mc_table_kernel<..., WLT>, also keeps running means: any update_period)
+    const bool table_wl = wl && table;
+    const bool lean = h->lean_tables && Fk <= 64 &&
+                (!wl || ((wl_sum_mode || (table_wl && cfg->wl_update_period < (1ll << 31))) &&
+                         h->F <= 63 && cfg->wl_check_period < (1ll << 31))) && // (cell 63 of the feature scratch is the kernel's zero)
+                (!t->has_ewald || kp.ew_compact) && t->n_sublattices == 1 && h->lean_ncls == 1 &&
+                h->lean_nslot <= 4 && !smolmc_env(ENV_FORCE_GENERAL);
+    if (!lean) return p;
+    const int nact = p.nact = (int)(t->sub_site_ptr[1] - t->sub_site_ptr[0]);
+    const int sbase = p.sbase = t->sub_active_sites[0];
+    const char *why = nullptr;
+    const int nc = p.nc = lean_code_count(h, t, 0, &why);
+    if (!lean_site_range(t, 0) || !nc) return p;
+    if (t->has_mu) {
+        if (t->mu_width < nc || !row_uniform(t->mu_table, t->mu_width, sbase, nact, nc)) return p;
+        p.mu_row.assign(t->mu_table + (size_t)sbase * t->mu_width, t->mu_table + (size_t)sbase * t->mu_width + nc);
+    }
+    // the table kernels take at most 8 flip vectors: larger tables run on the universal kernel
+    // (Wang-Landau TableFlip: mc_table_kernel<..., WLT>; SMOLMC_NO_TABLE_WL: A/B switch)
+    if (table && (t->n_flip_vectors > 8 || (wl && smolmc_env(ENV_NO_TABLE_WL)))) return p;
+    // several correlation functions per orbit: plain Metropolis flip / swap variants only
+    if (h->lean_kf && (wl || t->bias_type || table)) return p;
+    if (t->bias_type) {
+        // (pair tables of the bias: [row][old * 8 + new]; the bias row must be the same on every active site)
+        p.bias_pair.assign((size_t)64 * SMOLMC_MAX_BIAS_ROWS, 0.0);
+        if (!lean_bias_pairs(h, t, brows, sbase, nact, nc, p.bias_pair.data(), 64)) return p;
+        // (TableFlip with a bias: mc_table_kernel<..., BIAS>; SMOLMC_NO_TABLE_BIAS: A/B switch)
+        if (table && smolmc_env(ENV_NO_TABLE_BIAS)) return p;
+    }
+    p.late = true;
+    // (Wang-Landau: per-bin records and the cached rows of per-bin feature sums, mc_wl.h)
+    p.lds = ((size_t)lp.dt_len + 24) * 8 +
+            (size_t)4 * (lp.Nlds + 64 * 8 + 64 +
+                         (table_wl ? wl_multi_wave_bytes(h->L, h->F, kp.wl_sum_mode) // (mc_table_kernel<..., WLT>: the multi-class kernel's state)
+                          : wl     ? wl_lean_bins_bytes(h->L) + (size_t)SMOLMC_WL_ROWS * h->F * 8
+                                   : 0));
+    if (p.lds > 150 * 1024) return p;
+    // Ewald potential field in LDS when the changeable sites are the active
+    // sublattice and it fits beside the occupancies
+    // (the changeable sites may extend beyond the active ones: restricted sites, which the host
+    // API relabels behind the active sites of their sublattice; the field covers them all)
+    const int nfield = kp.ew_nact;
+    if (t->has_ewald && kp.ew_act_base == sbase && nfield >= nact && !smolmc_env(ENV_NO_EWALD_FIELD)) {
+        const size_t with_field = p.lds + (size_t)4 * nfield * 8;
+        p.qrow.assign(8, 0.0);
+        p.dgrow.assign(8, 0.0);
+        if (lean_ewald_rows(h, sbase, nfield, p.qrow.data(), p.dgrow.data()) && kp.ew_field && with_field <= 150 * 1024 && (size_t)nfield * 8 <= 64 * 1024) {
+            p.field = true;
+            p.lds = with_field;
+        }
+    }
+    // Wang-Landau with the Ewald term: mc_wl_kernel takes it from the field in LDS only
+    if (wl && t->has_ewald && !p.field) return p;
+    p.take = true;
+    // one wave per workgroup (occupancy at LDS address 0, 32-bit index rows, a private
+    // copy of the tables): Metropolis flips / swaps without Ewald term or bias, when 16
+    // such workgroups still fit a CU
+    if (!wl && !t->has_ewald && !t->bias_type && !h->lean_kf && !table && !smolmc_env(ENV_NO_SOLO)) {
+        const size_t pw = ((size_t)lp.Nlds + 64 * 8 + 15) & ~(size_t)15;
+        const size_t solo_lds = pw + ((size_t)lp.dt_len + 24) * 8;
+        if (solo_lds * 16 <= 160 * 1024 - 16 * 256) {
+            p.solo = true;
+            p.lds = solo_lds;
+            // More walkers than the default register allocation (4 waves per SIMD) keeps
+            // resident: the 6-waves-per-SIMD instantiation, when 24 workgroups fit a CU.
+            // Measured (headline model, 1e4 steps): 6144 walkers 8.74 -> 7.08 ms, 16384
+            // walkers 19.7 -> 17.6 ms; at <= 4 waves per SIMD it is 7 % slower.
+            if ((long)cfg->n_replicas > 16L * cu_count(h) && solo_lds * 24 <= 160 * 1024 - 24 * 256 &&
+                !smolmc_env(ENV_NO_OCC6))
+                p.occ = 6;
+        }
+    }
+    if (table) {
+        // block-shared flip table / weights (48 doubles) and, when it fits, ln(k) for k <= n_active
+        p.lds += 48 * 8;
+        // ... unless it would cost the second resident workgroup per CU (160 KiB / 2)
+        const size_t half = 80 * 1024, with_ln = p.lds + (size_t)(nact + 1) * 8;
+        if (with_ln <= 150 * 1024 && (with_ln <= half || p.lds > half)) {
+            p.tf_ln_len = nact + 1;
+            p.lds += (size_t)(nact + 1) * 8;
+        }
+        // Eight walkers per workgroup when two four-walker workgroups would share a CU
+        // anyway: waves w and w + 4 of a workgroup sit on the same SIMD, so that the
+        // launch order (update_walker_order) can pair a hot walker with a cold one there.
+        // (fewer walkers than 8 per CU: four-walker workgroups spread over more CUs)
+        const size_t per_wave = (size_t)lp.Nlds + 64 * 8 + 64 + (p.field ? (size_t)kp.ew_nact * 8 : 0);
+        const size_t lds8 = p.lds + 4 * per_wave;
+        if (!wl && lds8 <= 160 * 1024 && p.lds > 40 * 1024 && cfg->n_replicas % 8 == 0 &&
+            (long)cfg->n_replicas >= 8L * cu_count(h)) {
+            p.wpb = 8;
+            p.lds8 = lds8;
+        }
+    }
+    return p;
+}
+static int plan_lean(smolmc_handle *h, const smolmc_tables *t, LeanPlan &p) {
+    if (h->lazy_tables && dev_alloc(h, (size_t)h->R * 2, &h->d_lazy_scal)) return 1; // (for either planner's kernels)
+    p = decide_lean(h, t);
+    if (!p.take) return 0;
+    const KParams &kp = h->kp;
+    LeanParams &lp = h->lp;
+    if (t->has_mu && dev_upload(h, p.mu_row.data(), p.mu_row.size(), &lp.mu_row)) return 1;
+    if (t->bias_type && dev_upload(h, p.bias_pair.data(), p.bias_pair.size(), &lp.bias_pair)) return 1;
+    double mmax = 0.0;
+    for (double v : p.mu_row) mmax = std::max(mmax, std::fabs(v));
+    lean_widen_fast_eps(t, lp, mmax);
+    lean_fill_state(h, t, lp, 64, is_table(h) ? kp.wl_sum_mode : 1);
+    lp.sbase = p.sbase; lp.nact = p.nact; lp.ncodes = p.nc;
+    if (t->has_ewald) { lp.ew_act = kp.ew_act; lp.ew_qs = kp.ew_qs; lp.ew_dg = kp.ew_dg; lp.ew_frozen = kp.ew_frozen; }
+    lp.ew_field = 0;
+    if (p.field) {
+        if (dev_upload(h, p.qrow.data(), 8, &lp.ew_qrow) || dev_upload(h, p.dgrow.data(), 8, &lp.ew_dgrow)) return 1;
+        lp.ew_phi = kp.ew_phi;
+        lp.ew_field = 1;
+    }
+    if (p.solo) {
+        std::vector<uint32_t> wide(h->lean_idx_host.begin(), h->lean_idx_host.end());
+        if (dev_upload(h, wide.data(), wide.size(), &lp.idx32)) return 1;
+    }
+    if (is_table(h) && lean_fill_table(h, t, lp, p.nc, p.nact, p.tf_ln_len)) return 1;
+    h->lean_lds = p.lds;
+    h->lean_solo = p.solo;
+    h->lean_occ = p.occ;
+    h->lean_wpb = p.wpb;
+    h->lean_lds_wpb8 = p.lds8;
+    return 0;
+}
+
+// ---- several classes / sublattices (or > 256 clusters per site): mc_lean_multi_kernel, mc_table_multi_kernel
+struct LeanMultiPlan {
+    bool take = false;
+    std::string reason; // why not (the first condition that fails, for smolmc_kernel_info)
+    int sbase[4], nact[4], ncodes[4], cls[4];
+    double cum[4], mmax = 0.0;
+    std::vector<double> mu_rows, q_rows, dg_rows, bias_pairs;
+    int ndims = 0, max_nact = 0, wpb = 0;
+    bool phi_lds = false;
+    size_t lds = 0;
+};
+static LeanMultiPlan decide_lean_multi(const smolmc_handle *h, const smolmc_tables *t) {
+    const smolmc_config *cfg = &h->cfg;
+    const KParams &kp = h->kp;
+    const LeanParams &lp = h->lp; // (build_mc_tables has left the table sizes there)
+    const bool wl = is_wl(h), table = is_table(h);
+    const int wl_sum_mode = wl_sum_mode_of(h), Fk = lean_features(h, t), brows = kp.bias_rows;
+    LeanMultiPlan p;
+    // (MCBias: every bias type with flips or swaps, and with TableFlip: mc_table_multi_kernel<..., BIAS>;
+    // SMOLMC_NO_TABLE_BIAS: A/B switch)
+    const bool multi_bias_ok = !t->bias_type || !table || !smolmc_env(ENV_NO_TABLE_BIAS);
+    // Wang-Landau on this layout (mc_lean_multi_kernel<..., WLK>): any number of classes the
+    // layout takes and any update_period -- what mc_wl_kernel (one class, update_period 1) leaves.  The
+    // Wang-Landau TableFlip: mc_table_multi_kernel<..., WLT> with one correlation function per orbit, the
+    // universal kernel otherwise.  SMOLMC_NO_WL_MULTI, SMOLMC_NO_TABLE_WL: A/B switches.
+    const bool multi_table_wl_ok = !h->lean_kf && !smolmc_env(ENV_NO_TABLE_WL);
+    const bool multi_wl_ok = !wl || ((!table || multi_table_wl_ok) && h->F <= 63 && cfg->wl_check_period < (1ll << 31) &&
+                                     cfg->wl_update_period < (1ll << 31) && !smolmc_env(ENV_NO_WL_MULTI));
+    const bool multi_env_off = smolmc_env(ENV_FORCE_GENERAL) || smolmc_env(ENV_NO_LEAN_MULTI);
+    p.reason = (h->lean_kf && !wl) ? "several correlation functions per orbit (KF kernel) on a model outside the single-class lean shape"
+               : !multi_wl_ok ? "Wang-Landau with more than 63 features, or with TableFlip and several correlation functions per orbit"
+               : !multi_bias_ok ? "environment override (SMOLMC_NO_TABLE_BIAS)"
+               : Fk > 64 ? "more than 64 features"
+               : t->n_sublattices > 4 ? "more than 4 active sublattices"
+               : (t->has_ewald && !kp.ew_field) ? "Ewald matrix that does not factorise into site charges (no potential field)"
+               : multi_env_off ? "environment override" : "";
+    if (!((!h->lean_kf || wl) && multi_wl_ok && multi_bias_ok && Fk <= 64 && t->n_sublattices <= 4 && (!t->has_ewald || kp.ew_field) &&
+          !multi_env_off))
+        return p;
+    const int ns = t->n_sublattices;
+    bool ok = true;
+    auto no = [&](const char *why) { if (ok) p.reason = why; ok = false; };
+    p.mu_rows.assign(32, 0.0);
+    p.q_rows.assign(32, 0.0);
+    p.dg_rows.assign(32, 0.0);
+    p.bias_pairs.assign((size_t)256 * SMOLMC_MAX_BIAS_ROWS, 0.0);
+    double cum = 0.0;
+    for (int k = 0; k < ns && ok; ++k) {
+        const int na = (int)(t->sub_site_ptr[k + 1] - t->sub_site_ptr[k]);
+        const int sb = t->sub_active_sites[t->sub_site_ptr[k]];
+        const char *why = nullptr; // (codes other than 0 .. n-1 under canonical swaps only: lean_code_count)
+        const int ncod = lean_code_count(h, t, k, &why);
+        if (na <= 0 || why == lean_why_species) no(lean_why_species);
+        if (ok && !lean_site_range(t, k)) no("the active sites of a sublattice are not one site range (they could not be renumbered into one, or SMOLMC_NO_SITE_RELABEL)");
+        if (ok && why) no(why);
+        const int cls = ok ? h->site_class_host[sb] : 255;
+        if (ok && cls == 255) no("an active sublattice without clusters");
+        for (int i = 0; ok && i < na; ++i)
+            if (h->site_class_host[sb + i] != cls) no("sites of one sublattice in different site classes (cluster environments)"); // classes == sublattices
+        if (!ok) break;
+        p.sbase[k] = sb; p.nact[k] = na; p.ncodes[k] = ncod; p.cls[k] = cls;
+        cum += t->sub_probs[k];
+        p.cum[k] = cum;
+        if (t->has_mu) {
+            if (t->mu_width < ncod || !row_uniform(t->mu_table, t->mu_width, sb, na, ncod)) ok = false;
+            for (int c = 0; ok && c < ncod; ++c) {
+                const double v = p.mu_rows[k * 8 + c] = t->mu_table[(size_t)sb * t->mu_width + c];
+                p.mmax = std::max(p.mmax, std::fabs(v));
+            }
+        }
+        // one bias row per sublattice (rows of a hyperplane bias: [row][sublattice][old * 8 + new])
+        if (t->bias_type && (t->bias_width < ncod || !lean_bias_pairs(h, t, brows, sb, na, ncod, p.bias_pairs.data() + k * 64, 256))) ok = false;
+        if (t->has_ewald && (sb < kp.ew_act_base || sb + na > kp.ew_act_base + kp.ew_nact ||
+                             !lean_ewald_rows(h, sb, na, &p.q_rows[k * 8], &p.dg_rows[k * 8])))
+            ok = false;
+    }
+    for (int k = 0; k < ns && ok; ++k) { p.ndims += p.ncodes[k]; p.max_nact = std::max(p.max_nact, p.nact[k]); }
+    if (table && ok) {
+        if (t->n_flip_vectors <= 0 || !t->flip_table || !t->flip_weights) ok = false;
+        else if (t->n_flip_vectors > 8 || p.ndims > 16) ok = false;
+    }
+    // LDS: shared tables + slot records, per wave occupancy + scratch + accumulators (+ field)
+    const size_t nrec = (size_t)h->lean_ncls * h->lean_nslot * 64;
+    // (Wang-Landau: + feature scale and feature index of every slot record)
+    const size_t shared = ((size_t)lp.dt_len + 96 + (table ? 80 : 0)) * 8 + nrec * 24 + (wl ? nrec * 12 : 0);
+    // waves per workgroup: the shared tables are paid once per workgroup, so pick the size
+    // that keeps the most waves resident per CU (160 KiB of LDS)
+    // ... and, at equal residency, the size that spreads the walkers over the most CUs: 1024 walkers in
+    // eight-wave workgroups are 128 workgroups -- half the chip idle, two waves per SIMD on the other half
+    const int cus = cu_count(h);
+    auto layout = [&](size_t per_wave_bytes, int &wpb_out) {
+        int best_waves = 0;
+        long best_rounds = 0, best_busy = 0;
+        wpb_out = 0;
+        for (int w : {8, 4, 2, 1}) {
+            const size_t need = shared + per_wave_bytes * w;
+            if (need > 160 * 1024 - 512) continue;
+            const int waves = (int)((160 * 1024) / need) * w;
+            const long R_ = cfg->n_replicas, blocks = (R_ + w - 1) / w;
+            const long rounds = (R_ + (long)waves * cus - 1) / ((long)waves * cus);
+            const long busy = std::min<long>(blocks, cus); // CUs that get a workgroup in the first round
+            const bool better = wpb_out == 0 || rounds < best_rounds ||
+                                (rounds == best_rounds && (busy > best_busy || (busy == best_busy && waves > best_waves)));
+            if (better) { best_waves = waves; best_rounds = rounds; best_busy = busy; wpb_out = w; }
+        }
+        return best_waves;
+    };
+    // The potential field goes to LDS while it stays small beside the rest of the wave's
+    // state, when all walkers still fit the chip in one round with it there (an accepted
+    // flip then reads its G row only, no read-modify-write of phi through L2), or for
+    // canonical swaps whenever it fits; else the HBM copy is used in place (ew_field 2).  SMOLMC_MULTI_PHI_HBM / _LDS force either (test hooks).
+    // (Wang-Landau: entropies, step counts and cached rows instead of the accumulator cells)
+    const size_t base_wave = (size_t)lp.Nlds + 64 + 64 * 8 +
+                             (wl ? wl_multi_wave_bytes(h->L, h->F, wl_sum_mode) + (table ? nrec * 8 : 0) // (table: + pending cells)
+                                 : nrec * (table ? 16 : 8));
+    p.phi_lds = t->has_ewald && (size_t)kp.ew_nact * 8 <= base_wave / 2;
+    if (t->has_ewald && !p.phi_lds) {
+        int w = 0;
+        const int waves = layout(base_wave + (size_t)kp.ew_nact * 8, w);
+        // canonical swaps update the field at two sites per accepted step and gain from
+        // the LDS copy even when the walkers then need several rounds (LiNiO2 8^3, 4096
+        // walkers: 1.13e9 -> 1.58e9 steps/s); flips only while one round holds them all
+        // (beyond: 4.1e9 with the HBM field against 3.0e9)
+        // -- provided at least 8 waves per CU stay resident: at 3 (config 7, 27 KiB of field
+        // per walker) the LDS copy measured 9.6 against 7.4 us per step
+        // (Wang-Landau accepts three steps of four: the field update is the step, the LDS copy pays for flips too)
+        if ((long)waves * cus >= (long)cfg->n_replicas || ((cfg->step_type == SMOLMC_STEP_SWAP || wl) && waves >= 8) ||
+            smolmc_env(ENV_MULTI_PHI_LDS))
+            p.phi_lds = waves > 0;
+    }
+    if (smolmc_env(ENV_MULTI_PHI_HBM)) p.phi_lds = false;
+    const size_t per_wave = base_wave + (p.phi_lds ? (size_t)kp.ew_nact * 8 : 0);
+    layout(per_wave, p.wpb);
+    if (p.wpb == 0 && ok) { ok = false; p.reason = "walker state beyond the workgroup's LDS (multi-class layout)"; }
+    if (!ok && p.reason.empty())
+        p.reason = "sublattice layout (an active sublattice is not one site range of one class with codes 0..n-1, or per-site "
+                   "chemical potentials / bias / charges differ inside a sublattice), or a flip table beyond 8 vectors / 16 dims";
+    p.lds = shared + per_wave * p.wpb;
+    p.take = ok;
+    return p;
+}
+static int plan_lean_multi(smolmc_handle *h, const smolmc_tables *t, const LeanPlan &one, LeanMultiPlan &p) {
+    p = decide_lean_multi(h, t);
+    h->lean_reason = p.reason;
+    if (!p.take) return 0;
+    const KParams &kp = h->kp;
+    LeanParams &lp = h->lp;
+    const int ns = t->n_sublattices;
+    for (int k = 0; k < ns; ++k) {
+        lp.m_sbase[k] = p.sbase[k]; lp.m_nact[k] = p.nact[k]; lp.m_ncodes[k] = p.ncodes[k]; lp.m_cls[k] = p.cls[k];
+        lp.m_cum[k] = p.cum[k];
+    }
+    if (t->has_mu && dev_upload(h, p.mu_rows.data(), 32, &lp.m_mu)) return 1;
+    if (t->has_ewald &&
+        (dev_upload(h, p.q_rows.data(), 32, &lp.m_q) || dev_upload(h, p.dg_rows.data(), 32, &lp.m_dg)))
+        return 1;
+    if (t->bias_type && dev_upload(h, p.bias_pairs.data(), p.bias_pairs.size(), &lp.bias_pair)) return 1;
+    // KEPT FROM EARLIER VERSIONS, bit for bit: a model that the single-class planner refused at its LDS stage had
+    // been widened (and scaled) once there before this planner widened it again; NOTES.md lists it for removal
+    if (one.late) lean_widen_fast_eps(t, lp, p.mmax);
+    lean_widen_fast_eps(t, lp, p.mmax);
+    lp.m_ncls = h->lean_ncls; lp.m_nsub = ns; lp.m_ndims = p.ndims;
+    if (is_table(h) && lean_fill_table(h, t, lp, p.ndims, p.max_nact, 0)) return 1;
+    lean_fill_state(h, t, lp, 256, wl_sum_mode_of(h));
+    lp.ew_field = 0;
+    if (t->has_ewald) {
+        lp.ew_phi = kp.ew_phi;
+        lp.ew_field = p.phi_lds ? 1 : 2;
+        lp.sbase = kp.ew_act_base; // field_apply indexes phi relative to it
+    }
+    h->lean_lds = p.lds;
+    h->waves_per_block_lean = p.wpb;
+    return 0;
+}
+
+// ---- universal kernel (mc_univ.h): parameter block of every handle
+// the cluster records (URec) and, packed for the enthalpy pass, the cluster rows of every site (URow / URecE)
+static int univ_pack_records(smolmc_handle *h, const smolmc_tables *t) {
+    UParams &up = h->up;
+    memset(&up, 0, sizeof(up));
+    up.T = h->rt;
+    up.natural = h->d_natural;
+    up.wl = is_wl(h) ? 1 : 0;
+    const bool cm = t->feature_mode == SMOLMC_FEATURES_CORRELATIONS;
+    const int64_t nloc = t->site_ptr[t->num_sites];
+    std::vector<URec> recs((size_t)std::max<int64_t>(nloc, 1));
+    memset(recs.data(), 0, recs.size() * sizeof(URec));
+    for (int64_t r = 0; r < nloc; ++r) {
+        const int o = t->loc_orbit[r];
+        URec &u = recs[(size_t)r];
+        u.I = t->orb_nsites[o];
+        u.K = cm ? t->orb_nfunc[o] : 1;
+        u.Nt = t->orb_tensor_len[o];
+        u.J = t->loc_nrows[r];
+        for (int m = 0; m < u.I; ++m) u.st[m] = t->tensor_indices[t->orb_stride_off[o] + m];
+        u.feat = cm ? t->orb_bit_id[o] : t->orb_id[o];
+        u.idx_off = t->loc_off[r];
+        u.t_off = cm ? t->orb_ctensor_off[o] : t->orb_itensor_off[o];
+        u.scale = (double)t->size / t->loc_ratio[r] / (double)t->loc_nrows[r];
+        u.ratio = t->loc_ratio[r];
+    }
+    if (dev_upload(h, recs.data(), recs.size(), &up.recs)) return 1;
+    // the cluster rows of every site, packed for the enthalpy pass (URow / URecE); equal records once
+    std::vector<URecE> rec_e;
+    std::vector<int32_t> rec_of((size_t)std::max<int64_t>(nloc, 1), 0);
+    std::map<std::string, int32_t> rec_index;
+    up.max_I = 1;
+    up.all_k1 = 1;
+    up.tens_len = 0;
+    uint64_t nrows = 0;
+    for (int64_t r = 0; r < nloc; ++r) {
+        const URec &u = recs[(size_t)r];
+        URecE e;
+        memset(&e, 0, sizeof(e));
+        for (int m = 0; m < u.I; ++m) e.st[m] = u.st[m];
+        e.K = u.K; e.Nt = u.Nt; e.feat = u.feat; e.scale = u.scale;
+        e.nat0 = (u.feat >= 0 && u.feat < h->F) ? h->natural[(size_t)u.feat] : 0.0;
+        // (offsets inside one tensor, k * Nt + index, stay below the total checked here)
+        if ((uint64_t)u.t_off + (uint64_t)u.K * (uint64_t)u.Nt > 0xffffffffull)
+            return fail("cluster tensors of more than 2^32 entries");
+        e.t_off = (uint32_t)u.t_off;
+        up.tens_len = (int)std::min<uint64_t>(0x7fffffffull, std::max<uint64_t>((uint64_t)up.tens_len, (uint64_t)u.t_off + (uint64_t)u.K * (uint64_t)u.Nt));
+        up.max_I = std::max(up.max_I, (int)u.I);
+        if (u.K != 1) up.all_k1 = 0;
+        nrows += (uint64_t)u.J;
+        const std::string key((const char *)&e, sizeof(e));
+        auto it = rec_index.find(key);
+        if (it == rec_index.end()) {
+            it = rec_index.emplace(key, (int32_t)rec_e.size()).first;
+            rec_e.push_back(e);
+        }
+        rec_of[(size_t)r] = it->second;
+    }
+    if (rec_e.empty()) { URecE e; memset(&e, 0, sizeof(e)); rec_e.push_back(e); }
+    up.n_recs_e = (int)rec_e.size();
+    up.dict_lds = up.n_recs_e <= SMOLMC_UNIV_DICT_RECS && up.tens_len <= SMOLMC_UNIV_DICT_TENS && h->F <= SMOLMC_UNIV_DICT_NAT;
+    if (nloc > 0x7fffffffll || nrows > 0x7fffffffull) return fail("more than 2^31 local cluster rows");
+    std::vector<uint32_t> row_ptr((size_t)t->num_sites + 1, 0);
+    std::vector<URow> rows((size_t)std::max<uint64_t>(nrows, 1));
+    memset(rows.data(), 0, rows.size() * sizeof(URow));
+    size_t q = 0;
+    for (int s = 0; s < t->num_sites; ++s) {
+        for (int64_t r = t->site_ptr[s]; r < t->site_ptr[s + 1]; ++r) {
+            const int I = t->orb_nsites[t->loc_orbit[r]];
+            for (int j = 0; j < t->loc_nrows[r]; ++j) {
+                URow &w = rows[q++];
+                const int32_t *m = t->loc_idx + t->loc_off[r] + (int64_t)j * I;
+                for (int i = 0; i < SMOLMC_MAX_CLUSTER_SITES; ++i) w.x[i] = i < I ? m[i] : (I ? m[0] : s);
+                w.rec = rec_of[(size_t)r];
+            }
+        }
+        row_ptr[(size_t)s + 1] = (uint32_t)q;
+    }
+    up.rows_uniform = t->num_sites > 0 ? (int)row_ptr[1] : 0;
+    for (int s = 0; s < t->num_sites; ++s)
+        if (row_ptr[(size_t)s + 1] - row_ptr[(size_t)s] != (uint32_t)up.rows_uniform) up.rows_uniform = 0;
+    const URow *d_rows = nullptr;
+    if (dev_upload(h, rows.data(), rows.size(), &d_rows) || dev_upload(h, row_ptr.data(), row_ptr.size(), &up.row_ptr) ||
+        dev_upload(h, rec_e.data(), rec_e.size(), &up.recs_e))
+        return 1;
+    up.rows = (const uint4 *)d_rows;
+    return 0;
+}
+// the flip table of a TableFlip handle: checked here for every kernel family
+static int univ_flip_table(smolmc_handle *h, const smolmc_tables *t) {
+    if (!is_table(h)) return 0;
+    UParams &up = h->up;
+    if (t->n_flip_vectors <= 0 || !t->flip_table || !t->flip_weights)
+        return fail("TableFlip needs a flip table (CompositionSpace.flip_table, "
+                    "smol/moca/composition/space.py:404-429)");
+    if (!(t->swap_weight >= 0.0 && t->swap_weight < 1.0))
+        return fail("swap_weight must be in [0, 1)");
+    const int ns = t->n_sublattices, d = (int)t->sub_code_ptr[ns];
+    if (t->n_flip_vectors > SMOLMC_MAX_FLIP_VECTORS || d > SMOLMC_MAX_FLIP_DIMS)
+        return fail("flip table larger than SMOLMC_MAX_FLIP_VECTORS x SMOLMC_MAX_FLIP_DIMS");
+    std::vector<int> dim_sub(d);
+    int max_nact = 0;
+    for (int k = 0; k < ns; ++k) {
+        for (int64_t c = t->sub_code_ptr[k]; c < t->sub_code_ptr[k + 1]; ++c) dim_sub[c] = k;
+        max_nact = std::max(max_nact, (int)(t->sub_site_ptr[k + 1] - t->sub_site_ptr[k]));
+    }
+    h->max_step_flips = 2;
+    for (int v = 0; v < t->n_flip_vectors; ++v) {
+        // species are exchanged inside a sublattice (mcusher.py:612-634: "Sub-lattices can not
+        // cross", assert len(site_ids) == 0), a step flips the sites of the depleted species
+        int total = 0;
+        for (int k = 0; k < ns; ++k) {
+            int sum = 0, picks = 0;
+            for (int64_t c = t->sub_code_ptr[k]; c < t->sub_code_ptr[k + 1]; ++c) {
+                const int u = t->flip_table[(size_t)v * d + c];
+                sum += u;
+                picks += u < 0 ? -u : 0;
+            }
+            if (sum != 0) return fail("flip vector does not conserve the sites of a sublattice");
+            total += picks;
+        }
+        if (total == 0) return fail("flip vector without any flip");
+        if (total > SMOLMC_MAX_STEP_FLIPS) return fail("flip vector of more than SMOLMC_MAX_STEP_FLIPS flips");
+        h->max_step_flips = std::max(h->max_step_flips, total);
+    }
+    for (int i = 0; i < 2 * t->n_flip_vectors; ++i)
+        if (!(t->flip_weights[i] >= 0.0)) return fail("flip weights must be non-negative");
+    const std::vector<double> ln = ln_table(max_nact + 1);
+    if (dev_upload(h, t->flip_table, (size_t)t->n_flip_vectors * d, &up.tf_table) ||
+        dev_upload(h, t->flip_weights, (size_t)2 * t->n_flip_vectors, &up.tf_w) ||
+        dev_upload(h, ln.data(), ln.size(), &up.tf_ln) || dev_upload(h, dim_sub.data(), dim_sub.size(), &up.tf_dim_sub))
+        return 1;
+    up.tf_n = t->n_flip_vectors;
+    up.tf_d = d;
+    up.tf_sw = t->swap_weight;
+    return 0;
+}
+// per-wave LDS: step scratch (flips, counts, weights, a-priori factors, running sums: 2464 B) + the occupancy when it fits
+// (+ the step's feature deltas, one cell per cluster feature, while that stays small)
+static int univ_lds_layout(smolmc_handle *h, const smolmc_tables *) {
+    UParams &up = h->up;
+    up.dfeat_cells = h->Fce <= 1024 ? (h->Fce + 1) / 2 * 2 : 0;
+    up.acc_cells = up.dfeat_cells ? (h->F + 1) / 2 * 2 : 0;
+    up.lds_shared = up.dict_lds ? SMOLMC_UNIV_DICT_BYTES : 0;
+    auto lay_out = [&]() {
+        const size_t scratch = (is_table(h) ? SMOLMC_UNIV_SCRATCH_TABLE : SMOLMC_UNIV_SCRATCH) +
+                               (((size_t)up.dfeat_cells << up.dfeat_shift) + (size_t)up.acc_cells) * 8,
+                     with_occ = (scratch + (size_t)h->Npad + 15) & ~(size_t)15;
+        up.occ_lds = with_occ <= 160 * 1024 - 256 && !smolmc_env(ENV_UNIV_OCC_HBM);
+        up.lds_per_wave = (int)(up.occ_lds ? with_occ : scratch);
+        h->univ_wpb = 4;
+        while (h->univ_wpb > 1 && (size_t)up.lds_shared + (size_t)up.lds_per_wave * h->univ_wpb > 64 * 1024) h->univ_wpb /= 2;
+    };
+    // shadow copies of the step's feature cells: as many as keep them within 4 KB -- and, for launches of more than
+    // twelve walkers per CU, the workgroup within a quarter of the CU's LDS (a workgroup of 40.1 KB halves the resident
+    // walkers of config 2: 1.3e9 -> 8.1e8 flips/s)
+    up.dfeat_shift = 0;
+    while (up.dfeat_cells && up.dfeat_shift < 3 && ((size_t)up.dfeat_cells << (up.dfeat_shift + 1)) <= 512) up.dfeat_shift++;
+    lay_out();
+    const bool crowded = (long long)h->cfg.n_replicas > 12ll * 256;
+    auto too_big = [&]() { return crowded && h->univ_wpb == 4 && (size_t)up.lds_shared + (size_t)up.lds_per_wave * 4 > 40 * 1024; };
+    while (too_big() && up.dfeat_shift > 0) { up.dfeat_shift--; lay_out(); }
+    if (too_big() && up.dict_lds) {
+        up.dict_lds = 0;
+        up.lds_shared = 0;
+        lay_out();
+    }
+    return 0;
+}
+
+// The launchers of the lean families: the row of family f is lean_families[f - K_LEAN], a launcher for lean_nslot 2 / 4 /
+// 8 each (NULL: no such instantiation).  `replay` serves recorded flips and swaps, `table_replay` recorded TableFlip
+// steps; a family without them replays on mc_kernel or the universal kernel (smolmc_replay).
+typedef int (*LeanLauncher)(smolmc_handle *, const LeanParams &);
+struct LeanFamilyRow {
+    const char *name;                 // smolmc_kernel_info: the layout ...
+    const char *wl_sums, *wl_means;   // ... and the tag of the Wang-Landau kernel (per-bin feature sums / running means)
+    LeanLauncher run[3], replay[3], table_replay[3];
+};
+#define L2(f) {smolmc_launch_##f##_2, smolmc_launch_##f##_4, nullptr}
+#define L3(f) {smolmc_launch_##f##_2, smolmc_launch_##f##_4, smolmc_launch_##f##_8}
+#define NONE {nullptr, nullptr, nullptr}
+static const LeanFamilyRow lean_families[] = {
+    /* K_LEAN             */ {"lean", nullptr, nullptr, L2(lean), L2(lean_replay), L2(table_replay)},
+    /* K_LEAN_BIAS        */ {"lean", nullptr, nullptr, L2(lean_bias), L2(lean_bias_replay), NONE},
+    /* K_LEAN_CORR        */ {"lean", nullptr, nullptr, L2(lean_corr), L2(lean_replay), NONE}, // (KF: a template flag of the same launchers)
+    /* K_WL               */ {"lean", " wl=v3", " wl=v3", L2(wl), L2(wl_replay), NONE},
+    /* K_TABLE_BIAS       */ {"lean", nullptr, nullptr, L2(table_bias), NONE, NONE},
+    /* K_TABLE_WL         */ {"lean", " wl=table", " wl=table-mean", L2(table_wl), NONE, NONE},
+    /* K_MULTI            */ {"lean-multi", nullptr, nullptr, L3(multi), L3(multi_replay), L3(multi_table_replay)},
+    /* K_MULTI_BIAS       */ {"lean-multi", nullptr, nullptr, L3(multi_bias), L3(multi_bias_replay), NONE},
+    /* K_MULTI_WL         */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_wl), L3(multi_wl_replay), NONE},
+    /* K_MULTI_WL_KF      */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_wl_kf), NONE, NONE},
+    /* K_MULTI_TABLE_BIAS */ {"lean-multi", nullptr, nullptr, L3(multi_table_bias), NONE, NONE},
+    /* K_MULTI_TABLE_WL   */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_table_wl), NONE, NONE},
+};
+#undef L2
+#undef L3
+#undef NONE
+static_assert(sizeof(lean_families) / sizeof(lean_families[0]) == K_MULTI_TABLE_WL - K_LEAN + 1, "one row per lean family");
+static LeanLauncher lean_launcher(const smolmc_handle *h, bool replay) {
+    const LeanFamilyRow &row = lean_families[h->family - K_LEAN];
+    const int i = h->lean_nslot == 2 ? 0 : (h->lean_nslot == 4 ? 1 : 2);
+    return !replay ? row.run[i] : (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP ? row.table_replay[i] : row.replay[i]);
+}
+
+// The kernel family of the handle, decided once: what a planner took, else mc_kernel, else -- TableFlip outside the
+// lean families, or a model mc_kernel cannot run -- the universal kernel.
+static KernelFamily family_of(const smolmc_handle *h, const LeanPlan &one, const LeanMultiPlan &multi) {
+    const bool wl = is_wl(h), table = is_table(h), bias = h->kp.bias_type != 0;
+    if (one.take)
+        return bias ? (table ? K_TABLE_BIAS : K_LEAN_BIAS) : (wl && table) ? K_TABLE_WL : h->lean_kf ? K_LEAN_CORR : wl ? K_WL : K_LEAN;
+    if (multi.take)
+        return wl ? (h->lean_kf ? K_MULTI_WL_KF : table ? K_MULTI_TABLE_WL : K_MULTI_WL)
+                  : bias ? (table ? K_MULTI_TABLE_BIAS : K_MULTI_BIAS) : K_MULTI;
+    return (table || !h->general_ok) ? K_UNIVERSAL : K_GENERAL;
+}
+
 static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_handle **out, std::vector<int32_t> *new_of) {
     if (t->max_species > 255) return fail("more than 255 species codes per site");
     int ndev = 0;
@@ -1267,824 +2170,23 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
     h->own_stream = true;
     hipEventCreate(&h->ev0);
     hipEventCreate(&h->ev1);
-    h->R = cfg->n_replicas;
-    h->N = t->num_sites;
-    h->Npad = (t->num_sites + 15) / 16 * 16;
-    h->Fce = num_ce_features(t);
-    h->F = h->Fce + (t->has_ewald ? 1 : 0) + (t->has_mu ? 1 : 0);
-    h->natural.assign(t->ce_coefs, t->ce_coefs + h->Fce);
-    if (t->has_ewald) h->natural.push_back(t->ewald_coef);
-    if (t->has_mu) h->natural.push_back(-1.0);
-    const bool wl = cfg->kernel_type == SMOLMC_KERNEL_WANGLANDAU;
-    if (wl) {
-        if (cfg->wl_min_enthalpy > cfg->wl_max_enthalpy)
-            return bail(fail("min_enthalpy can not be larger than max_enthalpy.")); // wanglandau.py:82
-        if ((cfg->wl_max_enthalpy - cfg->wl_min_enthalpy) / cfg->wl_bin_size <= 1)
-            return bail(fail("The values provided for min and max enthalpy and bin sizer result in a "
-                             "single bin!"));
-        if (cfg->wl_mod_factor <= 0) return bail(fail("mod_factor must be greater than 0."));
-        h->L = (int)ceil((cfg->wl_max_enthalpy - cfg->wl_min_enthalpy) / cfg->wl_bin_size);
-    }
-    memset(&h->kp, 0, sizeof(KParams));
-    KParams &kp = h->kp;
-    // (validate_tables(t) has passed: smolmc_create runs it on the caller's tables before any renaming)
-    // species codes a site may carry: max_species by default, the largest sublattice code + 1 on
-    // the sites of an active sublattice
-    h->site_ncodes.assign((size_t)t->num_sites, (uint8_t)std::min(255, std::max(1, t->max_species)));
-    h->site_active.assign((size_t)t->num_sites, 0);
-    for (int k = 0; k < t->n_sublattices; ++k) {
-        int top = 0;
-        for (int64_t c = t->sub_code_ptr[k]; c < t->sub_code_ptr[k + 1]; ++c) top = std::max(top, t->sub_codes[c]);
-        for (int64_t i = t->sub_site_ptr[k]; i < t->sub_site_ptr[k + 1]; ++i) {
-            const int st = t->sub_active_sites[i];
-            if (st >= 0 && st < t->num_sites) {
-                h->site_ncodes[st] = (uint8_t)std::min(255, top + 1);
-                h->site_active[st] = 1;
-            }
-        }
-    }
-    // ... and on every other site the width of its site space as the cluster tensors see it: member m of
-    // an orbit's rows has prev_stride / stride species (see validate_tables); a code beyond that would
-    // index past the tensors
-    {
-        std::vector<int> seen((size_t)t->num_sites, 0);
-        for (int o = 0; o < t->n_orb; ++o) {
-            const int I = t->orb_nsites[o];
-            const int32_t *st = t->tensor_indices + t->orb_stride_off[o];
-            for (int64_t i = t->full_off[o]; i < t->full_off[o + 1]; ++i) {
-                const int m = (int)((i - t->full_off[o]) % I);
-                const int width = (int)((m == 0 ? t->orb_tensor_len[o] : st[m - 1]) / st[m]);
-                const int site = t->full_idx[i];
-                seen[site] = seen[site] ? std::min(seen[site], width) : width;
-            }
-        }
-        for (int s = 0; s < t->num_sites; ++s)
-            if (!h->site_active[s] && seen[s]) h->site_ncodes[s] = (uint8_t)std::min<int>(h->site_ncodes[s], std::min(255, seen[s]));
-    }
-    if (int rc = build_mc_tables(h, t)) return bail(rc);
-    if (int rc = build_ref_tables(h, t)) return bail(rc);
-    kp.N = h->N;
-    kp.Npad = h->Npad;
-    kp.Fce = h->Fce;
-    kp.F = h->F;
-    kp.step_type = cfg->step_type;
-    kp.corr_mode = h->rt.corr_mode;
-    kp.has_ewald = t->has_ewald;
-    kp.has_mu = t->has_mu;
-    kp.ew_W = h->rt.ew_W;
-    kp.ew_M = h->rt.ew_M;
-    kp.mu_W = h->rt.mu_W;
-    kp.ew_inds = h->rt.ew_inds;
-    kp.ew_Mt = h->rt.ew_Mt;
-    kp.ew_coef = t->ewald_coef;
-    kp.mu = h->rt.mu;
-    // MCBias (smol/moca/kernel/bias.py)
-    if (t->bias_type) {
-        if (t->bias_type != SMOLMC_BIAS_FUGACITY && t->bias_type != SMOLMC_BIAS_SQUARE_CHARGE &&
-            t->bias_type != SMOLMC_BIAS_SQUARE_HYPERPLANE)
-            return bail(fail("unknown bias_type"));
-        const int brows = t->bias_type == SMOLMC_BIAS_SQUARE_HYPERPLANE ? t->bias_rows : 1;
-        if (brows < 1 || brows > SMOLMC_MAX_BIAS_ROWS)
-            return bail(fail("bias_rows must be in [1, SMOLMC_MAX_BIAS_ROWS]"));
-        if (wl) return bail(fail("Cannot apply bias to Wang-Landau simulation!")); // wanglandau.py:127-128
-        if (!t->bias_table || t->bias_width < t->max_species)
-            return bail(fail("bias_table must be [num_sites x >= max_species]"));
-        if (t->bias_type != SMOLMC_BIAS_FUGACITY && !(t->bias_penalty > 0.0))
-            return bail(fail("Penalty factor should be > 0!")); // bias.py:250-251, :328-329
-        h->bias_host.assign(t->bias_table, t->bias_table + (size_t)brows * t->num_sites * t->bias_width);
-        h->bias_icpt.assign(SMOLMC_MAX_BIAS_ROWS, 0.0);
-        if (t->bias_type == SMOLMC_BIAS_SQUARE_HYPERPLANE && t->bias_intercepts)
-            for (int k = 0; k < brows; ++k) h->bias_icpt[k] = t->bias_intercepts[k];
-        kp.bias_rows = brows;
-        kp.bias_row_stride = (size_t)t->num_sites * t->bias_width;
-        if (t->bias_type == SMOLMC_BIAS_FUGACITY)
-            for (double v : h->bias_host)
-                if (!(v > 0.0)) return bail(fail("fugacity fractions must be positive"));
-        kp.bias_type = t->bias_type;
-        kp.bias_W = t->bias_width;
-        kp.bias_pen = t->bias_penalty;
-        if (dev_upload(h, h->bias_host.data(), h->bias_host.size(), &kp.bias_tab)) return bail(1);
-        if (dev_alloc(h, (size_t)cfg->n_replicas, &kp.bias) ||
-            dev_alloc(h, (size_t)cfg->n_replicas * SMOLMC_MAX_BIAS_ROWS, &kp.charge))
-            return bail(1);
-    }
-    if (t->has_ewald && t->ewald_charges && !smolmc_env(ENV_DENSE_EWALD))
-        if (int rc = build_compact_ewald(h, t)) return bail(rc);
-    // potential field of every walker in HBM: needs the compact form and
-    // contiguous changeable sites; the lean kernels stage the same buffer through LDS
-    kp.ew_field = 0;
-    if (kp.ew_compact && kp.ew_act_base >= 0 && (size_t)kp.ew_nact * 8 <= 150 * 1024 &&
-        !smolmc_env(ENV_NO_EWALD_FIELD)) {
-        if (dev_alloc(h, (size_t)cfg->n_replicas * kp.ew_nact, &kp.ew_phi)) return bail(1);
-        kp.ew_field = 1;
-    }
-    // sublattices
-    {
-        const int ns = t->n_sublattices;
-        if (ns <= 0) return bail(fail("no active sublattice"));
-        std::vector<int> ptr(ns + 1), cptr(ns + 1), base(ns);
-        std::vector<double> cum(ns);
-        double c = 0;
-        for (int s = 0; s <= ns; ++s) {
-            ptr[s] = (int)t->sub_site_ptr[s];
-            cptr[s] = (int)t->sub_code_ptr[s];
-        }
-        for (int s = 0; s < ns; ++s) {
-            c += t->sub_probs[s];
-            cum[s] = c;
-            const int a = ptr[s], b = ptr[s + 1];
-            if (b <= a) return bail(fail("empty active sublattice"));
-            bool contig = true;
-            for (int i = a + 1; i < b; ++i)
-                if (t->sub_active_sites[i] != t->sub_active_sites[a] + (i - a)) contig = false;
-            base[s] = contig ? t->sub_active_sites[a] : -1;
-            for (int i = a; i < b; ++i)
-                if (t->sub_active_sites[i] < 0 || t->sub_active_sites[i] >= t->num_sites)
-                    return bail(fail("sublattice site index out of range"));
-        }
-        kp.nsub = ns;
-        if (dev_upload(h, ptr.data(), ptr.size(), &kp.sub_ptr) ||
-            dev_upload(h, t->sub_active_sites, (size_t)ptr[ns], &kp.sub_sites) ||
-            dev_upload(h, base.data(), base.size(), &kp.sub_base) ||
-            dev_upload(h, cptr.data(), cptr.size(), &kp.sub_code_ptr) ||
-            dev_upload(h, t->sub_codes, (size_t)cptr[ns], &kp.sub_codes) ||
-            dev_upload(h, cum.data(), cum.size(), &kp.sub_cum))
-            return bail(1);
-    }
-    // walker state
-    const size_t R = h->R;
-    kp.R = h->R;
-    double *dbeta = nullptr;
-    uint64_t *dseeds = nullptr;
-    if (dev_alloc(h, R * h->Npad, &kp.occ) || dev_alloc(h, R, &kp.enthalpy) ||
-        dev_alloc(h, R * h->F, &kp.features) || dev_alloc(h, R, &dbeta) || dev_alloc(h, R, &dseeds) ||
-        dev_alloc(h, R, &kp.nsteps) || dev_alloc(h, R, &kp.nacc) || dev_alloc(h, R, &kp.last_acc))
-        return bail(1);
-    kp.beta = dbeta;
-    h->d_beta = dbeta;
-    kp.seeds = dseeds;
-    if (dev_upload(h, h->natural.data(), h->natural.size(), (const double **)&h->d_natural))
-        return bail(1);
-    // Wang-Landau keeps per-bin feature sums at update_period 1, running means otherwise
-    const int wl_sum_mode = (cfg->wl_update_period == 1 && !smolmc_env(ENV_WL_RUNNING_MEAN)) ? 1 : 0;
-    if (wl) {
-        kp.L = h->L;
-        kp.wl_min = cfg->wl_min_enthalpy;
-        kp.wl_max = cfg->wl_max_enthalpy;
-        kp.wl_bin = cfg->wl_bin_size;
-        kp.wl_flat = cfg->wl_flatness;
-        kp.wl_div = cfg->wl_mod_divisor;
-        kp.wl_check = cfg->wl_check_period;
-        kp.wl_update = cfg->wl_update_period;
-        kp.wl_sum_mode = wl_sum_mode;
-        // (check period 0: the flatness check is the caller's -- a host-side mod_update callable,
-        // wanglandau.py:100-105 -- and no kernel runs its own)
-        if (kp.wl_check < 0 || kp.wl_update <= 0) return bail(fail("WL periods must be positive"));
-        // (the lane-indexed feature bookkeeping of mc_kernel / mc_wl_kernel holds 64 features; more -- the
-        // reference has no limit, wanglandau.py:117-118 -- take the universal kernel)
-        if (h->F > 64 && h->general_ok) no_general(h, "Wang-Landau with more than 64 features");
-        if (dev_alloc(h, R * h->L, &kp.wl_entropy) || dev_alloc(h, R * h->L, &kp.wl_hist) ||
-            dev_alloc(h, R * h->L, &kp.wl_occur) || dev_alloc(h, R * h->L * h->F + 64, &kp.wl_meanf) || // (+64: the lean kernel's all-lane atomic, see mc_lean.h)
-            dev_alloc(h, R, &kp.wl_m) || dev_alloc(h, R, &kp.wl_counter))
-            return bail(1);
-        std::vector<double> m0(R, cfg->wl_mod_factor);
-        if (hipMemcpy(kp.wl_m, m0.data(), R * 8, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail("hipMemcpy failed"));
-    }
-    // LDS layout
-    size_t tb = (size_t)kp.nclasses * kp.Cpad * (16 + 16 + 8) + (size_t)(kp.xt_len + kp.ft_len) * 8 +
-                (size_t)((kp.nclasses + 3) & ~3) * 4 + (kp.nclasses > 1 ? (size_t)h->N : 0);
-    tb = (tb + 15) / 16 * 16;
-    size_t pw = (size_t)h->Npad;
-    if (wl)
-        pw += (size_t)h->L * 24 + (size_t)h->F * 8;
-    else {
-        const size_t by_feat = (size_t)h->Fce * 64 * 8;
-        const size_t by_slot = ((size_t)kp.nclasses * kp.Cpad + h->Fce) * 8;
-        kp.acc_by_slot = (!kp.corr_mode && by_slot < by_feat) ? 1 : 0;
-        pw += kp.acc_by_slot ? by_slot : by_feat;
-    }
-    pw = (pw + 15) / 16 * 16;
-    kp.lds_tables = (int)tb;
-    kp.lds_per_wave = (int)pw;
-    h->waves_per_block = 4;
-    while (h->waves_per_block > 1 && tb + pw * h->waves_per_block > 160 * 1024) h->waves_per_block /= 2;
-    h->lds_bytes = tb + pw * h->waves_per_block;
-    if (h->general_ok && h->lds_bytes > 160 * 1024)
-        no_general(h, "tables + one chain exceed the 160 KiB LDS budget of mc_kernel");
-    // lean-kernel eligibility (everything else runs mc_kernel)
-    {
-        // (lean Wang-Landau keeps per-bin feature SUMS: update_period 1 only, see WlParams)
-        // (lazy cluster features: the lean kernels see the scalar features only -- Ewald energy, chemical work)
-        const int nscal = (t->has_ewald ? 1 : 0) + (t->has_mu ? 1 : 0);
-        const int Fk = h->lazy_tables ? nscal : h->F;
-        if (h->lazy_tables) {
-            if (dev_alloc(h, (size_t)h->R * 2, &h->d_lazy_scal)) return bail(1);
-        }
-        // (... the Wang-Landau TableFlip kernel, mc_table_kernel<..., WLT>, also keeps running means: any update_period)
-        const bool table_wl = wl && cfg->step_type == SMOLMC_STEP_TABLE_FLIP;
-        bool lean = h->lean_tables && Fk <= 64 &&
-                    (!wl || ((wl_sum_mode || (table_wl && cfg->wl_update_period < (1ll << 31))) &&
-                             h->F <= 63 && cfg->wl_check_period < (1ll << 31))) && // (cell 63 of the feature scratch is the kernel's zero)
-                    (!t->has_ewald || kp.ew_compact) && t->n_sublattices == 1 && h->lean_ncls == 1 &&
-                    h->lean_nslot <= 4 && !smolmc_env(ENV_FORCE_GENERAL);
-        int sbase = -1, nact = 0, nc = 0;
-        std::vector<double> mu_row;
-        if (lean) {
-            nact = (int)(t->sub_site_ptr[1] - t->sub_site_ptr[0]);
-            nc = (int)(t->sub_code_ptr[1] - t->sub_code_ptr[0]);
-            sbase = t->sub_active_sites[0];
-            for (int i = 0; i < nact; ++i)
-                if (t->sub_active_sites[i] != sbase + i) lean = false;
-            // Species codes 0 .. n-1, or -- canonical swaps only, which never draw a code: they exchange the two sites'
-            // own -- any code list (a sublattice split by species, sublattice.py:109-186, keeps the site space's codes:
-            // {1, 2} of three); the per-code rows (mu, charges, bias pairs) then run up to the largest code.
-            bool default_codes = true;
-            int top = 0;
-            for (int c = 0; c < nc; ++c) {
-                default_codes = default_codes && t->sub_codes[c] == c;
-                top = std::max(top, (int)t->sub_codes[c]);
-            }
-            if (nc < 2 || nc > 8) lean = false;
-            if (!default_codes) {
-                if (cfg->step_type == SMOLMC_STEP_SWAP && top < 8) nc = top + 1;
-                else lean = false;
-            }
-        }
-        if (lean && t->has_mu) {
-            if (t->mu_width < nc) lean = false;
-            for (int c = 0; lean && c < nc; ++c) mu_row.push_back(t->mu_table[(size_t)sbase * t->mu_width + c]);
-            for (int i = 0; lean && i < nact; ++i)
-                for (int c = 0; c < nc; ++c)
-                    if (t->mu_table[(size_t)(sbase + i) * t->mu_width + c] != mu_row[c]) lean = false;
-        }
-        // (pair tables of the bias: [row][old * 8 + new], one row for Fugacity / SquareCharge, bias_rows rows for
-        // SquareHyperplaneBias -- on the lean kernels since round 5)
-        const int brows_l = t->bias_type == SMOLMC_BIAS_SQUARE_HYPERPLANE ? t->bias_rows : 1;
-        std::vector<double> bias_pair((size_t)64 * SMOLMC_MAX_BIAS_ROWS, 0.0);
-        // the table kernels take at most 8 flip vectors: larger tables run on the universal kernel
-        // (Wang-Landau TableFlip: mc_table_kernel<..., WLT> since round 6; SMOLMC_NO_TABLE_WL: A/B switch)
-        if (lean && cfg->step_type == SMOLMC_STEP_TABLE_FLIP && (t->n_flip_vectors > 8 || (wl && smolmc_env(ENV_NO_TABLE_WL))))
-            lean = false;
-        // several correlation functions per orbit: plain Metropolis flip / swap variants only
-        if (lean && h->lean_kf && (wl || t->bias_type || cfg->step_type == SMOLMC_STEP_TABLE_FLIP)) lean = false;
-        if (lean && t->bias_type) {
-            // the bias row must be the same on every active site (it is defined per sublattice)
-            const int W = t->bias_width;
-            for (int k = 0; k < brows_l; ++k) {
-                const double *tabk = h->bias_host.data() + (size_t)k * t->num_sites * W;
-                for (int i = 0; lean && i < nact; ++i)
-                    for (int c = 0; c < nc; ++c)
-                        if (tabk[(size_t)(sbase + i) * W + c] != tabk[(size_t)sbase * W + c]) lean = false;
-                for (int o = 0; lean && o < nc; ++o)
-                    for (int n = 0; n < nc; ++n) {
-                        const double a = tabk[(size_t)sbase * W + n], b = tabk[(size_t)sbase * W + o];
-                        bias_pair[(size_t)k * 64 + o * 8 + n] = t->bias_type == SMOLMC_BIAS_FUGACITY ? std::log(a / b) : a - b;
-                    }
-            }
-            // (TableFlip with a bias: mc_table_kernel<..., BIAS> since round 6; SMOLMC_NO_TABLE_BIAS: A/B switch)
-            if (cfg->step_type == SMOLMC_STEP_TABLE_FLIP && smolmc_env(ENV_NO_TABLE_BIAS)) lean = false;
-        }
-        if (lean) {
-            LeanParams &lp = h->lp;
-            if (t->has_mu && dev_upload(h, mu_row.data(), mu_row.size(), &lp.mu_row)) return bail(1);
-            if (t->bias_type) {
-                if (dev_upload(h, bias_pair.data(), bias_pair.size(), &lp.bias_pair)) return bail(1);
-                lp.bias_type = t->bias_type;
-                lp.bias_pen = t->bias_penalty;
-                lp.bias = kp.bias;
-                lp.charge = kp.charge;
-                lp.bias_rows = brows_l;
-                lp.bias_row_stride = 64;
-            }
-            if (t->has_mu) { // the mu delta of a step joins the float32 sum (<= 2 flips * 2 |mu|)
-                double mmax = 0.0;
-                for (double v : mu_row) mmax = std::max(mmax, std::fabs(v));
-                lp.fast_eps += 4.0 * mmax * ldexp(1.0, -19);
-            }
-            // test hook: widen the undecided band so that both decision paths interleave
-            if (const char *sc = smolmc_env(ENV_FAST_EPS_SCALE)) lp.fast_eps *= atof(sc);
-            lp.occ = kp.occ;
-            lp.enthalpy = kp.enthalpy;
-            lp.features = h->lazy_tables ? h->d_lazy_scal : kp.features;
-            lp.beta = kp.beta;
-            lp.seeds = kp.seeds;
-            lp.nsteps = kp.nsteps;
-            lp.nacc = kp.nacc;
-            lp.last_acc = kp.last_acc;
-            lp.R = h->R;
-            lp.N = h->N;
-            lp.Npad = h->Npad;
-            lp.F = Fk;
-            lp.Fce = h->lazy_tables ? 0 : h->Fce;
-            lp.sbase = sbase;
-            lp.nact = nact;
-            lp.ncodes = nc;
-            if (t->has_ewald) {
-                lp.ew_W = kp.ew_W;
-                lp.ew_nact = kp.ew_nact;
-                lp.ew_act_base = kp.ew_act_base;
-                lp.ew_act = kp.ew_act;
-                lp.ew_G = kp.ew_G;
-                lp.ew_qs = kp.ew_qs;
-                lp.ew_dg = kp.ew_dg;
-                lp.ew_frozen = kp.ew_frozen;
-                lp.ew_coef = kp.ew_coef;
-                lp.ew_gx = kp.ew_gx; lp.ew_E8 = kp.ew_E8; lp.ew_S8 = kp.ew_S8;
-            }
-            if (cfg->step_type == SMOLMC_STEP_TABLE_FLIP) {
-                if (dev_upload(h, t->flip_table, (size_t)t->n_flip_vectors * nc, &lp.tf_table) ||
-                    dev_upload(h, t->flip_weights, (size_t)2 * t->n_flip_vectors, &lp.tf_w))
-                    return bail(1);
-                lp.tf_n = t->n_flip_vectors;
-                lp.tf_sw = t->swap_weight;
-            }
-            if (wl) {
-                lp.wl.L = h->L;
-                lp.wl.vmin = kp.wl_min; lp.wl.vmax = kp.wl_max; lp.wl.bin = kp.wl_bin;
-                lp.wl.flat = kp.wl_flat; lp.wl.div = kp.wl_div;
-                lp.wl.check = kp.wl_check; lp.wl.update = kp.wl_update;
-                lp.wl.entropy = kp.wl_entropy; lp.wl.hist = kp.wl_hist; lp.wl.occur = kp.wl_occur;
-                lp.wl.meanf = kp.wl_meanf; lp.wl.m = kp.wl_m; lp.wl.counter = kp.wl_counter;
-                lp.wl.sum_mode = table_wl ? kp.wl_sum_mode : 1;
-            }
-            // (Wang-Landau: per-bin records and the cached rows of per-bin feature sums, mc_wl.h)
-            h->lean_lds = ((size_t)lp.dt_len + 24) * 8 +
-                          (size_t)4 * (lp.Nlds + 64 * 8 + 64 +
-                                       (table_wl ? wl_multi_wave_bytes(h->L, h->F, kp.wl_sum_mode) // (mc_table_kernel<..., WLT>: the multi-class kernel's state)
-                                        : wl     ? wl_lean_bins_bytes(h->L) + (size_t)SMOLMC_WL_ROWS * h->F * 8
-                                                 : 0));
-            if (h->lean_lds > 150 * 1024) lean = false;
-            // Ewald potential field in LDS when the changeable sites are the active
-            // sublattice and it fits beside the occupancies
-            lp.ew_field = 0;
-            // (the changeable sites may extend beyond the active ones: restricted sites, which the host
-            // API relabels behind the active sites of their sublattice; the field covers them all)
-            const int nfield = kp.ew_nact;
-            if (lean && t->has_ewald && kp.ew_act_base == sbase && nfield >= nact && !smolmc_env(ENV_NO_EWALD_FIELD)) {
-                const size_t with_field = h->lean_lds + (size_t)4 * nfield * 8;
-                // charge / diagonal term per species code must not depend on the site
-                bool uniform = kp.ew_W <= 8;
-                std::vector<double> qrow(8, 0.0), dgrow(8, 0.0);
-                for (int c = 0; uniform && c < kp.ew_W; ++c) {
-                    qrow[c] = h->ew_qs_host[(size_t)sbase * kp.ew_W + c];
-                    dgrow[c] = h->ew_dg_host[(size_t)sbase * kp.ew_W + c];
-                    for (int i = 0; i < nfield; ++i)
-                        if (h->ew_qs_host[(size_t)(sbase + i) * kp.ew_W + c] != qrow[c] ||
-                            h->ew_dg_host[(size_t)(sbase + i) * kp.ew_W + c] != dgrow[c])
-                            uniform = false;
-                }
-                if (uniform && kp.ew_field && with_field <= 150 * 1024 && (size_t)nfield * 8 <= 64 * 1024) {
-                    if (dev_upload(h, qrow.data(), 8, &lp.ew_qrow) || dev_upload(h, dgrow.data(), 8, &lp.ew_dgrow))
-                        return bail(1);
-                    lp.ew_phi = kp.ew_phi;
-                    lp.ew_field = 1;
-                    h->lean_lds = with_field;
-                }
-            }
-            // Wang-Landau with the Ewald term: mc_wl_kernel takes it from the field in LDS only
-            if (lean && wl && t->has_ewald && !lp.ew_field) lean = false;
-            // one wave per workgroup (occupancy at LDS address 0, 32-bit index rows, a private
-            // copy of the tables): Metropolis flips / swaps without Ewald term or bias, when 16
-            // such workgroups still fit a CU
-            if (lean && !wl && !t->has_ewald && !t->bias_type && !h->lean_kf && cfg->step_type != SMOLMC_STEP_TABLE_FLIP &&
-                !smolmc_env(ENV_NO_SOLO)) {
-                const size_t pw = ((size_t)lp.Nlds + 64 * 8 + 15) & ~(size_t)15;
-                const size_t solo_lds = pw + ((size_t)lp.dt_len + 24) * 8;
-                if (solo_lds * 16 <= 160 * 1024 - 16 * 256) {
-                    std::vector<uint32_t> wide(h->lean_idx_host.begin(), h->lean_idx_host.end());
-                    if (dev_upload(h, wide.data(), wide.size(), &lp.idx32)) return bail(1);
-                    h->lean_solo = true;
-                    h->lean_lds = solo_lds;
-                    // More walkers than the default register allocation (4 waves per SIMD) keeps
-                    // resident: the 6-waves-per-SIMD instantiation, when 24 workgroups fit a CU.
-                    // Measured (headline model, 1e4 steps): 6144 walkers 8.74 -> 7.08 ms, 16384
-                    // walkers 19.7 -> 17.6 ms; at <= 4 waves per SIMD it is 7 % slower.
-                    int cus = 0;
-                    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 256;
-                    if ((long)cfg->n_replicas > 16L * cus && solo_lds * 24 <= 160 * 1024 - 24 * 256 &&
-                        !smolmc_env(ENV_NO_OCC6))
-                        h->lean_occ = 6;
-                }
-            }
-            if (lean && cfg->step_type == SMOLMC_STEP_TABLE_FLIP) {
-                // block-shared flip table / weights (48 doubles) and, when it fits, ln(k) for
-                // k <= n_active from the host libm (the oracle's log-factorial sums use the same)
-                h->lean_lds += 48 * 8;
-                lp.tf_ln_len = 0;
-                // ... unless it would cost the second resident workgroup per CU (160 KiB / 2)
-                const size_t half = 80 * 1024, with_ln = h->lean_lds + (size_t)(nact + 1) * 8;
-                std::vector<double> ln((size_t)nact + 1, 0.0);
-                for (int k = 1; k <= nact; ++k) ln[k] = std::log((double)k);
-                if (dev_upload(h, ln.data(), ln.size(), &lp.tf_ln)) return bail(1);
-                if (with_ln <= 150 * 1024 && (with_ln <= half || h->lean_lds > half)) {
-                    lp.tf_ln_len = nact + 1;
-                    h->lean_lds += (size_t)(nact + 1) * 8;
-                }
-                // Eight walkers per workgroup when two four-walker workgroups would share a CU
-                // anyway: waves w and w + 4 of a workgroup sit on the same SIMD, so that the
-                // launch order (update_walker_order) can pair a hot walker with a cold one there.
-                {
-                    const size_t per_wave = (size_t)lp.Nlds + 64 * 8 + 64 + (lp.ew_field ? (size_t)kp.ew_nact * 8 : 0);
-                    const size_t lds8 = h->lean_lds + 4 * per_wave;
-                    h->lean_wpb = 4;
-                    int cus = 0; // (fewer walkers than 8 per CU: four-walker workgroups spread over more CUs)
-                    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 256;
-                    if (!wl && lds8 <= 160 * 1024 && h->lean_lds > 40 * 1024 && cfg->n_replicas % 8 == 0 &&
-                        (long)cfg->n_replicas >= 8L * cus) {
-                        h->lean_wpb = 8;
-                        h->lean_lds_wpb8 = lds8;
-                    }
-                }
-            }
-        }
-        h->lean = lean;
-        // ---- several classes / sublattices (or > 256 clusters per site): mc_lean_multi_kernel
-        const bool table = cfg->step_type == SMOLMC_STEP_TABLE_FLIP;
-        // (MCBias: every bias type with flips or swaps, and since round 6 with TableFlip: mc_table_multi_kernel<..., BIAS>;
-        // SMOLMC_NO_TABLE_BIAS: A/B switch)
-        const bool multi_bias_ok = !t->bias_type || cfg->step_type != SMOLMC_STEP_TABLE_FLIP || !smolmc_env(ENV_NO_TABLE_BIAS);
-        // Wang-Landau on this layout (round 5; mc_lean_multi_kernel<..., WLK>): any number of classes the
-        // layout takes and any update_period -- what mc_wl_kernel (one class, update_period 1) leaves.  The
-        // Wang-Landau TableFlip: mc_table_multi_kernel<..., WLT> (round 6) with one correlation function per orbit, the
-        // universal kernel otherwise.  SMOLMC_NO_WL_MULTI, SMOLMC_NO_TABLE_WL: A/B switches.
-        const bool multi_table_wl_ok = !h->lean_kf && !smolmc_env(ENV_NO_TABLE_WL);
-        const bool multi_wl_ok = !wl || ((!table || multi_table_wl_ok) && h->F <= 63 && cfg->wl_check_period < (1ll << 31) &&
-                                         cfg->wl_update_period < (1ll << 31) && !smolmc_env(ENV_NO_WL_MULTI));
-        const bool multi_env_off = smolmc_env(ENV_FORCE_GENERAL) || smolmc_env(ENV_NO_LEAN_MULTI);
-        // (why a model with lean tables runs neither lean family: the first condition that fails, for smolmc_kernel_info)
-        if (!lean && h->lean_tables)
-            h->lean_reason = (h->lean_kf && !wl) ? "several correlation functions per orbit (KF kernel) on a model outside the single-class lean shape"
-                             : !multi_wl_ok ? "Wang-Landau with more than 63 features, or with TableFlip and several correlation functions per orbit"
-                             : !multi_bias_ok ? "environment override (SMOLMC_NO_TABLE_BIAS)"
-                             : Fk > 64 ? "more than 64 features"
-                             : t->n_sublattices > 4 ? "more than 4 active sublattices"
-                             : (t->has_ewald && !kp.ew_field) ? "Ewald matrix that does not factorise into site charges (no potential field)"
-                             : multi_env_off ? "environment override" : "";
-        if (!lean && h->lean_tables && (!h->lean_kf || wl) && multi_wl_ok && multi_bias_ok && Fk <= 64 && t->n_sublattices <= 4 && (!t->has_ewald || kp.ew_field) &&
-            !multi_env_off) {
-            LeanParams &lp = h->lp;
-            const int ns = t->n_sublattices;
-            bool ok = true;
-            std::vector<double> mu_rows(32, 0.0), q_rows(32, 0.0), dg_rows(32, 0.0), bias_pairs((size_t)256 * SMOLMC_MAX_BIAS_ROWS, 0.0);
-            double cum = 0.0, mmax = 0.0;
-            for (int k = 0; k < ns && ok; ++k) {
-                const int64_t a0 = t->sub_site_ptr[k], a1 = t->sub_site_ptr[k + 1];
-                const int na = (int)(a1 - a0);
-                int ncod = (int)(t->sub_code_ptr[k + 1] - t->sub_code_ptr[k]);
-                const int sb = t->sub_active_sites[a0];
-                auto no = [&](const char *why) { if (ok) h->lean_reason = why; ok = false; };
-                if (na <= 0 || ncod < 2 || ncod > 8) no("an active sublattice of fewer than 2 or more than 8 species");
-                for (int i = 0; ok && i < na; ++i)
-                    if (t->sub_active_sites[a0 + i] != sb + i) no("the active sites of a sublattice are not one site range (they could not be renumbered into one, or SMOLMC_NO_SITE_RELABEL)");
-                {   // (codes other than 0 .. n-1 -- a sublattice split by species -- under canonical swaps only: see the single-class path)
-                    bool default_codes = true;
-                    int top = 0;
-                    for (int c = 0; c < ncod; ++c) {
-                        default_codes = default_codes && t->sub_codes[t->sub_code_ptr[k] + c] == c;
-                        top = std::max(top, (int)t->sub_codes[t->sub_code_ptr[k] + c]);
-                    }
-                    if (ok && !default_codes) {
-                        if (cfg->step_type == SMOLMC_STEP_SWAP && top < 8 && ncod >= 2) ncod = top + 1;
-                        else no("a sublattice whose species codes are not 0 .. n-1 (split by species) under a step type that draws codes");
-                    }
-                }
-                const int cls = ok ? h->site_class_host[sb] : 255;
-                if (ok && cls == 255) no("an active sublattice without clusters");
-                for (int i = 0; ok && i < na; ++i)
-                    if (h->site_class_host[sb + i] != cls) no("sites of one sublattice in different site classes (cluster environments)"); // classes == sublattices
-                if (!ok) break;
-                lp.m_sbase[k] = sb; lp.m_nact[k] = na; lp.m_ncodes[k] = ncod; lp.m_cls[k] = cls;
-                cum += t->sub_probs[k];
-                lp.m_cum[k] = cum;
-                if (t->has_mu) {
-                    if (t->mu_width < ncod) ok = false;
-                    for (int c = 0; ok && c < ncod; ++c) {
-                        const double v = t->mu_table[(size_t)sb * t->mu_width + c];
-                        mu_rows[k * 8 + c] = v;
-                        mmax = std::max(mmax, std::fabs(v));
-                        for (int i = 0; i < na; ++i)
-                            if (t->mu_table[(size_t)(sb + i) * t->mu_width + c] != v) ok = false;
-                    }
-                }
-                if (t->bias_type) { // one bias row per sublattice (it is defined per sublattice)
-                    const int W = t->bias_width;
-                    if (W < ncod) ok = false;
-                    for (int rw = 0; rw < brows_l; ++rw) { // (rows of a hyperplane bias: [row][sublattice][old * 8 + new])
-                        const double *tabk = h->bias_host.data() + (size_t)rw * t->num_sites * W;
-                        for (int i = 0; ok && i < na; ++i)
-                            for (int c = 0; c < ncod; ++c)
-                                if (tabk[(size_t)(sb + i) * W + c] != tabk[(size_t)sb * W + c]) ok = false;
-                        for (int o = 0; ok && o < ncod; ++o)
-                            for (int n = 0; n < ncod; ++n) {
-                                const double a = tabk[(size_t)sb * W + n], b = tabk[(size_t)sb * W + o];
-                                bias_pairs[(size_t)rw * 256 + k * 64 + o * 8 + n] = t->bias_type == SMOLMC_BIAS_FUGACITY ? std::log(a / b) : a - b;
-                            }
-                    }
-                }
-                if (t->has_ewald) {
-                    if (kp.ew_W > 8 || sb < kp.ew_act_base || sb + na > kp.ew_act_base + kp.ew_nact) ok = false;
-                    for (int c = 0; ok && c < kp.ew_W; ++c) {
-                        q_rows[k * 8 + c] = h->ew_qs_host[(size_t)sb * kp.ew_W + c];
-                        dg_rows[k * 8 + c] = h->ew_dg_host[(size_t)sb * kp.ew_W + c];
-                        for (int i = 0; i < na; ++i)
-                            if (h->ew_qs_host[(size_t)(sb + i) * kp.ew_W + c] != q_rows[k * 8 + c] ||
-                                h->ew_dg_host[(size_t)(sb + i) * kp.ew_W + c] != dg_rows[k * 8 + c])
-                                ok = false;
-                    }
-                }
-            }
-            int ndims = 0, max_nact = 0;
-            for (int k = 0; k < ns && ok; ++k) { ndims += lp.m_ncodes[k]; max_nact = std::max(max_nact, lp.m_nact[k]); }
-            if (table && ok) {
-                if (t->n_flip_vectors <= 0 || !t->flip_table || !t->flip_weights) ok = false;
-                else if (t->n_flip_vectors > 8 || ndims > 16) ok = false;
-            }
-            // LDS: shared tables + slot records, per wave occupancy + scratch + accumulators (+ field)
-            const size_t nrec = (size_t)h->lean_ncls * h->lean_nslot * 64;
-            // (Wang-Landau: + feature scale and feature index of every slot record)
-            const size_t shared = ((size_t)lp.dt_len + 96 + (table ? 80 : 0)) * 8 + nrec * 24 + (wl ? nrec * 12 : 0);
-            // waves per workgroup: the shared tables are paid once per workgroup, so pick the size
-            // that keeps the most waves resident per CU (160 KiB of LDS)
-            // ... and, at equal residency, the size that spreads the walkers over the most CUs: 1024 walkers in
-            // eight-wave workgroups are 128 workgroups -- half the chip idle, two waves per SIMD on the other half
-            int cus_l = 0;
-            if (hipDeviceGetAttribute(&cus_l, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus_l = 256;
-            auto layout = [&](size_t per_wave_bytes, int &wpb_out) {
-                int best_waves = 0;
-                long best_rounds = 0, best_busy = 0;
-                wpb_out = 0;
-                for (int w : {8, 4, 2, 1}) {
-                    const size_t need = shared + per_wave_bytes * w;
-                    if (need > 160 * 1024 - 512) continue;
-                    const int waves = (int)((160 * 1024) / need) * w;
-                    const long R_ = cfg->n_replicas, blocks = (R_ + w - 1) / w;
-                    const long rounds = (R_ + (long)waves * cus_l - 1) / ((long)waves * cus_l);
-                    const long busy = std::min<long>(blocks, cus_l); // CUs that get a workgroup in the first round
-                    const bool better = wpb_out == 0 || rounds < best_rounds ||
-                                        (rounds == best_rounds && (busy > best_busy || (busy == best_busy && waves > best_waves)));
-                    if (better) { best_waves = waves; best_rounds = rounds; best_busy = busy; wpb_out = w; }
-                }
-                return best_waves;
-            };
-            // The potential field goes to LDS while it stays small beside the rest of the wave's
-            // state, when all walkers still fit the chip in one round with it there (an accepted
-            // flip then reads its G row only, no read-modify-write of phi through L2), or for
-            // canonical swaps whenever it fits; else the HBM copy is used in place (ew_field 2).  SMOLMC_MULTI_PHI_HBM / _LDS force either (test hooks).
-            // (Wang-Landau: entropies, step counts and cached rows instead of the accumulator cells)
-            const size_t base_wave = (size_t)lp.Nlds + 64 + 64 * 8 +
-                                     (wl ? wl_multi_wave_bytes(h->L, h->F, wl_sum_mode) + (table ? nrec * 8 : 0) // (table: + pending cells)
-                                         : nrec * (table ? 16 : 8));
-            bool phi_lds = t->has_ewald && (size_t)kp.ew_nact * 8 <= base_wave / 2;
-            if (t->has_ewald && !phi_lds) {
-                int cus = 0, w = 0;
-                if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 256;
-                const int waves = layout(base_wave + (size_t)kp.ew_nact * 8, w);
-                // canonical swaps update the field at two sites per accepted step and gain from
-                // the LDS copy even when the walkers then need several rounds (LiNiO2 8^3, 4096
-                // walkers: 1.13e9 -> 1.58e9 steps/s); flips only while one round holds them all
-                // (beyond: 4.1e9 with the HBM field against 3.0e9)
-                // -- provided at least 8 waves per CU stay resident: at 3 (config 7, 27 KiB of field
-                // per walker) the LDS copy measured 9.6 against 7.4 us per step
-                // (Wang-Landau accepts three steps of four: the field update is the step, the LDS copy pays for flips too)
-                if ((long)waves * cus >= (long)cfg->n_replicas || ((cfg->step_type == SMOLMC_STEP_SWAP || wl) && waves >= 8) ||
-                    smolmc_env(ENV_MULTI_PHI_LDS))
-                    phi_lds = waves > 0;
-            }
-            if (smolmc_env(ENV_MULTI_PHI_HBM)) phi_lds = false;
-            const size_t per_wave = base_wave + (phi_lds ? (size_t)kp.ew_nact * 8 : 0);
-            int wpb = 0;
-            layout(per_wave, wpb);
-            if (wpb == 0 && ok) { ok = false; h->lean_reason = "walker state beyond the workgroup's LDS (multi-class layout)"; }
-            if (!ok && h->lean_reason.empty())
-                h->lean_reason = "sublattice layout (an active sublattice is not one site range of one class with codes 0..n-1, or per-site "
-                                 "chemical potentials / bias / charges differ inside a sublattice), or a flip table beyond 8 vectors / 16 dims";
-            if (ok) {
-                if (t->has_mu && dev_upload(h, mu_rows.data(), 32, &lp.m_mu)) return bail(1);
-                if (t->has_ewald &&
-                    (dev_upload(h, q_rows.data(), 32, &lp.m_q) || dev_upload(h, dg_rows.data(), 32, &lp.m_dg)))
-                    return bail(1);
-                if (t->bias_type) {
-                    if (dev_upload(h, bias_pairs.data(), bias_pairs.size(), &lp.bias_pair)) return bail(1);
-                    lp.bias_rows = brows_l;
-                    lp.bias_row_stride = 256;
-                    lp.bias_type = t->bias_type;
-                    lp.bias_pen = t->bias_penalty;
-                    lp.bias = kp.bias;
-                    lp.charge = kp.charge;
-                }
-                if (t->has_mu) lp.fast_eps += 4.0 * mmax * ldexp(1.0, -19);
-                if (const char *sc = smolmc_env(ENV_FAST_EPS_SCALE)) lp.fast_eps *= atof(sc);
-                lp.m_ncls = h->lean_ncls; lp.m_nsub = ns; lp.m_ndims = ndims;
-                if (table) {
-                    std::vector<double> ln((size_t)max_nact + 1, 0.0);
-                    for (int k = 1; k <= max_nact; ++k) ln[k] = std::log((double)k);
-                    if (dev_upload(h, t->flip_table, (size_t)t->n_flip_vectors * ndims, &lp.tf_table) ||
-                        dev_upload(h, t->flip_weights, (size_t)2 * t->n_flip_vectors, &lp.tf_w) ||
-                        dev_upload(h, ln.data(), ln.size(), &lp.tf_ln))
-                        return bail(1);
-                    lp.tf_n = t->n_flip_vectors;
-                    lp.tf_sw = t->swap_weight;
-                    lp.tf_ln_len = 0;
-                }
-                lp.occ = kp.occ; lp.enthalpy = kp.enthalpy; lp.features = h->lazy_tables ? h->d_lazy_scal : kp.features; lp.beta = kp.beta;
-                lp.seeds = kp.seeds; lp.nsteps = kp.nsteps; lp.nacc = kp.nacc; lp.last_acc = kp.last_acc;
-                lp.R = h->R; lp.N = h->N; lp.Npad = h->Npad; lp.F = Fk; lp.Fce = h->lazy_tables ? 0 : h->Fce;
-                if (wl) {
-                    lp.wl.L = h->L;
-                    lp.wl.vmin = kp.wl_min; lp.wl.vmax = kp.wl_max; lp.wl.bin = kp.wl_bin;
-                    lp.wl.flat = kp.wl_flat; lp.wl.div = kp.wl_div;
-                    lp.wl.check = kp.wl_check; lp.wl.update = kp.wl_update;
-                    lp.wl.entropy = kp.wl_entropy; lp.wl.hist = kp.wl_hist; lp.wl.occur = kp.wl_occur;
-                    lp.wl.meanf = kp.wl_meanf; lp.wl.m = kp.wl_m; lp.wl.counter = kp.wl_counter;
-                    lp.wl.sum_mode = wl_sum_mode;
-                    h->lean_multi_wl = true;
-                }
-                lp.ew_field = 0;
-                if (t->has_ewald) {
-                    lp.ew_W = kp.ew_W; lp.ew_nact = kp.ew_nact; lp.ew_act_base = kp.ew_act_base;
-                    lp.ew_G = kp.ew_G; lp.ew_coef = kp.ew_coef; lp.ew_phi = kp.ew_phi;
-                    lp.ew_gx = kp.ew_gx; lp.ew_E8 = kp.ew_E8; lp.ew_S8 = kp.ew_S8;
-                    lp.ew_field = phi_lds ? 1 : 2;
-                    lp.sbase = kp.ew_act_base; // field_apply indexes phi relative to it
-                }
-                h->lean_lds = shared + per_wave * wpb;
-                h->waves_per_block_lean = wpb;
-                h->lean = true;
-                h->lean_multi = true;
-            }
-        }
-        if (smolmc_env(ENV_DEBUG))
-            fprintf(stderr, "[smolmc] lean=%d tables=%d nslot=%d mm=%d lds=%zu ew=%d compact=%d field=%d nact=%d "
-                            "ew_nact=%d ew_act_base=%d sbase=%d general: nslot=%d mm=%d lds=%zu\n",
-                    (int)lean, (int)h->lean_tables, h->lean_nslot, h->lean_mm, h->lean_lds, t->has_ewald,
-                    kp.ew_compact, h->lp.ew_field, nact, kp.ew_nact, kp.ew_act_base, sbase, h->nslot, h->mm,
-                    h->lds_bytes);
-    }
-    // ---- universal kernel (mc_univ.h): parameter block of every handle; `univ` when nothing else serves
-    {
-        UParams &up = h->up;
-        memset(&up, 0, sizeof(up));
-        up.T = h->rt;
-        up.natural = h->d_natural;
-        up.wl = wl ? 1 : 0;
-        {
-            const bool cm = t->feature_mode == SMOLMC_FEATURES_CORRELATIONS;
-            const int64_t nloc = t->site_ptr[t->num_sites];
-            std::vector<URec> recs((size_t)std::max<int64_t>(nloc, 1));
-            memset(recs.data(), 0, recs.size() * sizeof(URec));
-            for (int64_t r = 0; r < nloc; ++r) {
-                const int o = t->loc_orbit[r];
-                URec &u = recs[(size_t)r];
-                u.I = t->orb_nsites[o];
-                u.K = cm ? t->orb_nfunc[o] : 1;
-                u.Nt = t->orb_tensor_len[o];
-                u.J = t->loc_nrows[r];
-                for (int m = 0; m < u.I; ++m) u.st[m] = t->tensor_indices[t->orb_stride_off[o] + m];
-                u.feat = cm ? t->orb_bit_id[o] : t->orb_id[o];
-                u.idx_off = t->loc_off[r];
-                u.t_off = cm ? t->orb_ctensor_off[o] : t->orb_itensor_off[o];
-                u.scale = (double)t->size / t->loc_ratio[r] / (double)t->loc_nrows[r];
-                u.ratio = t->loc_ratio[r];
-            }
-            if (dev_upload(h, recs.data(), recs.size(), &up.recs)) return bail(1);
-            // the cluster rows of every site, packed for the enthalpy pass (URow / URecE); equal records once
-            std::vector<URecE> rec_e;
-            std::vector<int32_t> rec_of((size_t)std::max<int64_t>(nloc, 1), 0);
-            std::map<std::string, int32_t> rec_index;
-            up.max_I = 1;
-            up.all_k1 = 1;
-            up.tens_len = 0;
-            uint64_t nrows = 0;
-            for (int64_t r = 0; r < nloc; ++r) {
-                const URec &u = recs[(size_t)r];
-                URecE e;
-                memset(&e, 0, sizeof(e));
-                for (int m = 0; m < u.I; ++m) e.st[m] = u.st[m];
-                e.K = u.K; e.Nt = u.Nt; e.feat = u.feat; e.scale = u.scale;
-                e.nat0 = (u.feat >= 0 && u.feat < h->F) ? h->natural[(size_t)u.feat] : 0.0;
-                // (offsets inside one tensor, k * Nt + index, stay below the total checked here)
-                if ((uint64_t)u.t_off + (uint64_t)u.K * (uint64_t)u.Nt > 0xffffffffull)
-                    return bail(fail("cluster tensors of more than 2^32 entries"));
-                e.t_off = (uint32_t)u.t_off;
-                up.tens_len = (int)std::min<uint64_t>(0x7fffffffull, std::max<uint64_t>((uint64_t)up.tens_len, (uint64_t)u.t_off + (uint64_t)u.K * (uint64_t)u.Nt));
-                up.max_I = std::max(up.max_I, (int)u.I);
-                if (u.K != 1) up.all_k1 = 0;
-                nrows += (uint64_t)u.J;
-                const std::string key((const char *)&e, sizeof(e));
-                auto it = rec_index.find(key);
-                if (it == rec_index.end()) {
-                    it = rec_index.emplace(key, (int32_t)rec_e.size()).first;
-                    rec_e.push_back(e);
-                }
-                rec_of[(size_t)r] = it->second;
-            }
-            if (rec_e.empty()) { URecE e; memset(&e, 0, sizeof(e)); rec_e.push_back(e); }
-            up.n_recs_e = (int)rec_e.size();
-            up.dict_lds = up.n_recs_e <= SMOLMC_UNIV_DICT_RECS && up.tens_len <= SMOLMC_UNIV_DICT_TENS && h->F <= SMOLMC_UNIV_DICT_NAT;
-            if (nloc > 0x7fffffffll || nrows > 0x7fffffffull) return bail(fail("more than 2^31 local cluster rows"));
-            std::vector<uint32_t> row_ptr((size_t)t->num_sites + 1, 0);
-            std::vector<URow> rows((size_t)std::max<uint64_t>(nrows, 1));
-            memset(rows.data(), 0, rows.size() * sizeof(URow));
-            size_t q = 0;
-            for (int s = 0; s < t->num_sites; ++s) {
-                for (int64_t r = t->site_ptr[s]; r < t->site_ptr[s + 1]; ++r) {
-                    const int I = t->orb_nsites[t->loc_orbit[r]];
-                    for (int j = 0; j < t->loc_nrows[r]; ++j) {
-                        URow &w = rows[q++];
-                        const int32_t *m = t->loc_idx + t->loc_off[r] + (int64_t)j * I;
-                        for (int i = 0; i < SMOLMC_MAX_CLUSTER_SITES; ++i) w.x[i] = i < I ? m[i] : (I ? m[0] : s);
-                        w.rec = rec_of[(size_t)r];
-                    }
-                }
-                row_ptr[(size_t)s + 1] = (uint32_t)q;
-            }
-            up.rows_uniform = t->num_sites > 0 ? (int)row_ptr[1] : 0;
-            for (int s = 0; s < t->num_sites; ++s)
-                if (row_ptr[(size_t)s + 1] - row_ptr[(size_t)s] != (uint32_t)up.rows_uniform) up.rows_uniform = 0;
-            const URow *d_rows = nullptr;
-            if (dev_upload(h, rows.data(), rows.size(), &d_rows) || dev_upload(h, row_ptr.data(), row_ptr.size(), &up.row_ptr) ||
-                dev_upload(h, rec_e.data(), rec_e.size(), &up.recs_e))
-                return bail(1);
-            up.rows = (const uint4 *)d_rows;
-        }
-        if (cfg->step_type == SMOLMC_STEP_TABLE_FLIP) {
-            if (t->n_flip_vectors <= 0 || !t->flip_table || !t->flip_weights)
-                return bail(fail("TableFlip needs a flip table (CompositionSpace.flip_table, "
-                                 "smol/moca/composition/space.py:404-429)"));
-            if (!(t->swap_weight >= 0.0 && t->swap_weight < 1.0))
-                return bail(fail("swap_weight must be in [0, 1)"));
-            const int ns = t->n_sublattices, d = (int)t->sub_code_ptr[ns];
-            if (t->n_flip_vectors > SMOLMC_MAX_FLIP_VECTORS || d > SMOLMC_MAX_FLIP_DIMS)
-                return bail(fail("flip table larger than SMOLMC_MAX_FLIP_VECTORS x SMOLMC_MAX_FLIP_DIMS"));
-            std::vector<int> dim_sub(d);
-            int max_nact = 0;
-            for (int k = 0; k < ns; ++k) {
-                for (int64_t c = t->sub_code_ptr[k]; c < t->sub_code_ptr[k + 1]; ++c) dim_sub[c] = k;
-                max_nact = std::max(max_nact, (int)(t->sub_site_ptr[k + 1] - t->sub_site_ptr[k]));
-            }
-            h->max_step_flips = 2;
-            for (int v = 0; v < t->n_flip_vectors; ++v) {
-                // species are exchanged inside a sublattice (mcusher.py:612-634: "Sub-lattices can not
-                // cross", assert len(site_ids) == 0), a step flips the sites of the depleted species
-                int total = 0;
-                for (int k = 0; k < ns; ++k) {
-                    int sum = 0, picks = 0;
-                    for (int64_t c = t->sub_code_ptr[k]; c < t->sub_code_ptr[k + 1]; ++c) {
-                        const int u = t->flip_table[(size_t)v * d + c];
-                        sum += u;
-                        picks += u < 0 ? -u : 0;
-                    }
-                    if (sum != 0) return bail(fail("flip vector does not conserve the sites of a sublattice"));
-                    total += picks;
-                }
-                if (total == 0) return bail(fail("flip vector without any flip"));
-                if (total > SMOLMC_MAX_STEP_FLIPS) return bail(fail("flip vector of more than SMOLMC_MAX_STEP_FLIPS flips"));
-                h->max_step_flips = std::max(h->max_step_flips, total);
-            }
-            for (int i = 0; i < 2 * t->n_flip_vectors; ++i)
-                if (!(t->flip_weights[i] >= 0.0)) return bail(fail("flip weights must be non-negative"));
-            std::vector<double> ln((size_t)max_nact + 2, 0.0);
-            for (int k = 1; k <= max_nact + 1; ++k) ln[k] = std::log((double)k);
-            if (dev_upload(h, t->flip_table, (size_t)t->n_flip_vectors * d, &up.tf_table) ||
-                dev_upload(h, t->flip_weights, (size_t)2 * t->n_flip_vectors, &up.tf_w) ||
-                dev_upload(h, ln.data(), ln.size(), &up.tf_ln) || dev_upload(h, dim_sub.data(), dim_sub.size(), &up.tf_dim_sub))
-                return bail(1);
-            up.tf_n = t->n_flip_vectors;
-            up.tf_d = d;
-            up.tf_sw = t->swap_weight;
-        }
-        // per-wave LDS: step scratch (flips, counts, weights, a-priori factors, running sums: 2464 B) + the occupancy when it fits
-        // (+ the step's feature deltas, one cell per cluster feature, while that stays small)
-        up.dfeat_cells = h->Fce <= 1024 ? (h->Fce + 1) / 2 * 2 : 0;
-        up.acc_cells = up.dfeat_cells ? (h->F + 1) / 2 * 2 : 0;
-        up.lds_shared = up.dict_lds ? SMOLMC_UNIV_DICT_BYTES : 0;
-        auto lay_out = [&]() {
-            const size_t scratch = (cfg->step_type == SMOLMC_STEP_TABLE_FLIP ? SMOLMC_UNIV_SCRATCH_TABLE : SMOLMC_UNIV_SCRATCH) +
-                                   (((size_t)up.dfeat_cells << up.dfeat_shift) + (size_t)up.acc_cells) * 8,
-                         with_occ = (scratch + (size_t)h->Npad + 15) & ~(size_t)15;
-            up.occ_lds = with_occ <= 160 * 1024 - 256 && !smolmc_env(ENV_UNIV_OCC_HBM);
-            up.lds_per_wave = (int)(up.occ_lds ? with_occ : scratch);
-            h->univ_wpb = 4;
-            while (h->univ_wpb > 1 && (size_t)up.lds_shared + (size_t)up.lds_per_wave * h->univ_wpb > 64 * 1024) h->univ_wpb /= 2;
-        };
-        // shadow copies of the step's feature cells: as many as keep them within 4 KB -- and, for launches of more than
-        // twelve walkers per CU, the workgroup within a quarter of the CU's LDS (a workgroup of 40.1 KB halves the resident
-        // walkers of config 2: 1.3e9 -> 8.1e8 flips/s)
-        up.dfeat_shift = 0;
-        while (up.dfeat_cells && up.dfeat_shift < 3 && ((size_t)up.dfeat_cells << (up.dfeat_shift + 1)) <= 512) up.dfeat_shift++;
-        lay_out();
-        const bool crowded = (long long)cfg->n_replicas > 12ll * 256;
-        auto too_big = [&]() { return crowded && h->univ_wpb == 4 && (size_t)up.lds_shared + (size_t)up.lds_per_wave * 4 > 40 * 1024; };
-        while (too_big() && up.dfeat_shift > 0) { up.dfeat_shift--; lay_out(); }
-        if (too_big() && up.dict_lds) {
-            up.dict_lds = 0;
-            up.lds_shared = 0;
-            lay_out();
-        }
-        const bool table = cfg->step_type == SMOLMC_STEP_TABLE_FLIP;
-        h->univ = !h->lean && (table || !h->general_ok);
-    }
+    for (auto stage : {create_dimensions, create_site_codes, build_mc_tables, build_ref_tables, create_model_params, create_bias,
+                       create_ewald_field, create_sublattices, create_walker_state, create_wl_state, create_general_layout})
+        if (int rc = stage(h, t)) return bail(rc);
+    LeanPlan one;
+    LeanMultiPlan multi;
+    if (int rc = plan_lean(h, t, one)) return bail(rc);
+    if (!one.take && h->lean_tables)
+        if (int rc = plan_lean_multi(h, t, one, multi)) return bail(rc);
+    if (smolmc_env(ENV_DEBUG))
+        fprintf(stderr, "[smolmc] lean=%d tables=%d nslot=%d mm=%d lds=%zu ew=%d compact=%d field=%d nact=%d "
+                        "ew_nact=%d ew_act_base=%d sbase=%d general: nslot=%d mm=%d lds=%zu\n",
+                (int)one.take, (int)h->lean_tables, h->lean_nslot, h->lean_mm, h->lean_lds, t->has_ewald,
+                h->kp.ew_compact, h->lp.ew_field, one.nact, h->kp.ew_nact, h->kp.ew_act_base, one.sbase, h->nslot, h->mm,
+                h->lds_bytes);
+    for (auto stage : {univ_pack_records, univ_flip_table, univ_lds_layout})
+        if (int rc = stage(h, t)) return bail(rc);
+    h->family = family_of(h, one, multi);
     *out = h;
     return 0;
 }
@@ -2141,7 +2243,7 @@ static int launch_eval_full(smolmc_handle *h, const uint8_t *d_occ8, int nocc, d
 // ---- lazy cluster features (build_mc_tables) ---------------------------------------------------------------
 // The lean kernels of such a handle carry the scalar features only (d_lazy_scal, row stride nscal); the cluster
 // part of kp.features is evaluated from the occupancies where it is read.
-static bool is_lazy(const smolmc_handle *h) { return h->lazy_tables && h->lean; }
+static bool is_lazy(const smolmc_handle *h) { return h->lazy_tables && h->lean(); }
 static int lazy_nscal(const smolmc_handle *h) { return (h->rt.has_ewald ? 1 : 0) + (h->rt.has_mu ? 1 : 0); }
 // rows of full feature vectors [n][F] <-> rows of scalar features [n][nscal]
 __global__ void lazy_scalars_kernel(double *features, double *scal, size_t n, int F, int Fce, int nscal, int to_scal) {
@@ -2377,11 +2479,12 @@ extern "C" int smolmc_sync(smolmc_handle *h) {
 extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
     if (!h || !buf || n <= 0) return fail("null argument");
     if (h->dist) return smolmc_dist_kernel_info(h, buf, n);
-    if (h->univ)
+    const LeanFamilyRow *row = h->lean() ? &lean_families[h->family - K_LEAN] : nullptr;
+    if (h->univ())
         snprintf(buf, (size_t)n, "universal occ=%s field=%d lds=%zu (%s)", h->up.occ_lds ? "lds" : "hbm", h->kp.ew_field,
                  (size_t)h->up.lds_shared + (size_t)h->up.lds_per_wave * h->univ_wpb, h->general_ok ? "TableFlip outside the lean families" : h->general_reason.c_str());
-    else if (h->lean)
-        snprintf(buf, (size_t)n, "%s nslot=%d mm=%d field=%d lds=%zu%s", h->lean_multi ? "lean-multi" : "lean",
+    else if (row)
+        snprintf(buf, (size_t)n, "%s nslot=%d mm=%d field=%d lds=%zu%s", row->name,
                  h->lean_nslot, h->lean_mm, h->lp.ew_field, h->lean_lds,
                  h->lean_solo ? (h->lean_occ ? " solo=1 occ=6" : " solo=1") : (h->lean_kf ? " kf=1" : ""));
     else
@@ -2389,18 +2492,14 @@ extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
                  h->lds_bytes);
     {   // suffixes: the translation-compressed Ewald kernel in use, the Wang-Landau kernel generation
         const size_t used = strlen(buf);
-        if (h->lean && h->lp.ew_field && h->lp.ew_gx && used + 40 < (size_t)n)
+        const bool gx = row && h->lp.ew_field && h->lp.ew_gx && used + 40 < (size_t)n;
+        if (gx)
             snprintf(buf + used, (size_t)n - used, " gx=%dx%dx%dx%d", h->ew_gx_blocks, h->ew_gx_dims[0], h->ew_gx_dims[1],
                      h->ew_gx_dims[2]);
-        else if (h->lean && h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && !h->lean_multi_wl &&
-                 h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP && used + 8 < (size_t)n) // (mc_wl_kernel)
-            strncat(buf, " wl=v3", (size_t)n - used - 1);
-        if (h->lean && !h->lean_multi && h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP &&
-            strlen(buf) + 16 < (size_t)n) // (mc_table_kernel<..., WLT>)
-            strncat(buf, h->lp.wl.sum_mode ? " wl=table" : " wl=table-mean", (size_t)n - strlen(buf) - 1);
+        // (mc_wl_kernel's tag gives way to the gx one)
+        const char *wl_tag = !row || (gx && h->family == K_WL) ? nullptr : (h->lp.wl.sum_mode ? row->wl_sums : row->wl_means);
+        if (wl_tag && strlen(buf) + 24 < (size_t)n) strncat(buf, wl_tag, (size_t)n - strlen(buf) - 1);
         if (is_lazy(h) && strlen(buf) + 16 < (size_t)n) strncat(buf, " lazy-features", (size_t)n - strlen(buf) - 1);
-        if (h->lean_multi_wl && strlen(buf) + 24 < (size_t)n) // (the Wang-Landau variant of the multi-class kernel)
-            snprintf(buf + strlen(buf), (size_t)n - strlen(buf), h->lp.wl.sum_mode ? " wl=multi" : " wl=multi-mean");
         if (h->relabelled && strlen(buf) + 16 < (size_t)n) strncat(buf, " relabelled=1", (size_t)n - strlen(buf) - 1);
         if (h->env_dispatch && strlen(buf) + 8 < (size_t)n) { // the dispatch switches this handle was created under
             strncat(buf, " env=", (size_t)n - strlen(buf) - 1);
@@ -2413,7 +2512,7 @@ extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
                 }
         }
         // why the model runs neither lean family (the first condition that failed at smolmc_create)
-        if (!h->lean && !h->lean_reason.empty() && strlen(buf) + h->lean_reason.size() + 16 < (size_t)n) {
+        if (!h->lean() && !h->lean_reason.empty() && strlen(buf) + h->lean_reason.size() + 16 < (size_t)n) {
             strncat(buf, " | not lean: ", (size_t)n - strlen(buf) - 1);
             strncat(buf, h->lean_reason.c_str(), (size_t)n - strlen(buf) - 1);
         }
@@ -2557,7 +2656,7 @@ static int update_walker_order(smolmc_handle *h, LeanParams &lp) {
     h->order_mode = mode;
     lp.order = nullptr;
     const int R = h->R, wpb = h->lean_wpb;
-    if (mode == 0 || h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP || h->lean_multi || R < 2 * wpb) return 0;
+    if (mode == 0 || h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP || h->lean_multi() || R < 2 * wpb) return 0;
     if (!h->d_order) {
         HIPCHK(hipMalloc((void **)&h->d_order, (size_t)R * sizeof(int)));
         h->allocs.push_back(h->d_order);
@@ -2603,35 +2702,7 @@ static int update_walker_order(smolmc_handle *h, LeanParams &lp) {
 static int launch_lean(smolmc_handle *h, LeanParams lp, int64_t nsteps) {
     lp.steps = nsteps;
     TRY(update_walker_order(h, lp));
-    if (h->lean_multi_wl && h->lean_kf) // several correlation functions per orbit (KFW)
-        return h->lean_nslot == 2 ? smolmc_launch_multi_wl_kf_2(h, lp)
-                                  : (h->lean_nslot == 4 ? smolmc_launch_multi_wl_kf_4(h, lp) : smolmc_launch_multi_wl_kf_8(h, lp));
-    if (h->lean_multi_wl && h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP)
-        return h->lean_nslot == 2 ? smolmc_launch_multi_table_wl_2(h, lp)
-                                  : (h->lean_nslot == 4 ? smolmc_launch_multi_table_wl_4(h, lp) : smolmc_launch_multi_table_wl_8(h, lp));
-    if (h->lean_multi_wl)
-        return h->lean_nslot == 2 ? smolmc_launch_multi_wl_2(h, lp)
-                                  : (h->lean_nslot == 4 ? smolmc_launch_multi_wl_4(h, lp) : smolmc_launch_multi_wl_8(h, lp));
-    if (h->lean_multi && lp.bias_type && h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP)
-        return h->lean_nslot == 2 ? smolmc_launch_multi_table_bias_2(h, lp)
-                                  : (h->lean_nslot == 4 ? smolmc_launch_multi_table_bias_4(h, lp) : smolmc_launch_multi_table_bias_8(h, lp));
-    if (h->lean_multi && lp.bias_type)
-        return h->lean_nslot == 2 ? smolmc_launch_multi_bias_2(h, lp)
-                                  : (h->lean_nslot == 4 ? smolmc_launch_multi_bias_4(h, lp) : smolmc_launch_multi_bias_8(h, lp));
-    if (h->lean_multi)
-        return h->lean_nslot == 2 ? smolmc_launch_multi_2(h, lp)
-                                  : (h->lean_nslot == 4 ? smolmc_launch_multi_4(h, lp) : smolmc_launch_multi_8(h, lp));
-    if (lp.bias_type && h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP)
-        return h->lean_nslot == 2 ? smolmc_launch_lean_bias_2(h, lp) : smolmc_launch_lean_bias_4(h, lp);
-    if (lp.bias_type) // TableFlip with an MCBias term (single-class layout)
-        return h->lean_nslot == 2 ? smolmc_launch_table_bias_2(h, lp) : smolmc_launch_table_bias_4(h, lp);
-    if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) // (single-class layout)
-        return h->lean_nslot == 2 ? smolmc_launch_table_wl_2(h, lp) : smolmc_launch_table_wl_4(h, lp);
-    if (h->lean_kf) return h->lean_nslot == 2 ? smolmc_launch_lean_corr_2(h, lp) : smolmc_launch_lean_corr_4(h, lp);
-    // Wang-Landau: the dedicated kernel (mc_wl.h)
-    if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP)
-        return h->lean_nslot == 2 ? smolmc_launch_wl_2(h, lp) : smolmc_launch_wl_4(h, lp);
-    return h->lean_nslot == 2 ? smolmc_launch_lean_2(h, lp) : smolmc_launch_lean_4(h, lp);
+    return lean_launcher(h, false)(h, lp);
 }
 
 static void free_samples(smolmc_handle *h) {
@@ -2651,7 +2722,7 @@ static void free_samples(smolmc_handle *h) {
 static UParams univ_block_of(smolmc_handle *h) {
     UParams up = h->up;
     up.K = h->kp;
-    if (h->lean && !h->lp.ew_field) up.K.ew_field = 0;
+    if (h->lean() && !h->lp.ew_field) up.K.ew_field = 0;
     return up;
 }
 
@@ -2659,14 +2730,14 @@ static int run_steps(smolmc_handle *h, int64_t nsteps, const SampleBufs &smp) {
     if (h->dist) return smolmc_dist_run(h, nsteps, smp);
     // (per-bin feature statistics as sums for the lean Wang-Landau kernel and for mc_kernel with
     // update_period 1, as running means for the universal kernel)
-    TRY(wl_set_representation(h, h->univ ? false : (h->lean ? h->lp.wl.sum_mode != 0 : h->kp.wl_sum_mode != 0)));
-    if (h->univ) {
+    TRY(wl_set_representation(h, h->univ() ? false : (h->lean() ? h->lp.wl.sum_mode != 0 : h->kp.wl_sum_mode != 0)));
+    if (h->univ()) {
         UParams up = univ_block_of(h);
         up.K.steps_to_run = nsteps;
         up.K.smp = smp;
         return smolmc_launch_univ(h, up, 0);
     }
-    if (h->lean) {
+    if (h->lean()) {
         // the lean kernels count steps in 32 bits: launches are split at 2^30 steps (on a
         // sample boundary when samples are being recorded)
         int64_t chunk = (int64_t)1 << 30;
@@ -2767,7 +2838,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
     if ((flags & SMOLMC_SAMPLE_BIAS) && !h->kp.bias_type) return fail("the model has no bias term");
     if ((flags & SMOLMC_SAMPLE_WL) && !wl) return fail("handle is not a Wang-Landau kernel");
-    if (thin_by > ((int64_t)1 << 30) && h->lean && !smolmc_env(ENV_LAUNCH_CHUNK))
+    if (thin_by > ((int64_t)1 << 30) && h->lean() && !smolmc_env(ENV_LAUNCH_CHUNK))
         return fail("thin_by must be <= 2^30 steps"); // (before a slot is touched: run_steps would refuse it)
     if (!h->copy_stream) HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
     // The slot this block goes to is the older one.  When it still holds a block nobody fetched, so does the other
@@ -2809,7 +2880,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     // running bias is a scalar the kernel carries anyway; LeanParams::smp_bias_off tells it where the column is).  The
     // snapshot path -- one launch + one snapshot kernel per sample -- is left to Wang-Landau (per-walker L and L x F
     // arrays) and to biased handles on mc_kernel / the universal kernel.  SMOLMC_NO_INKERNEL_BIAS: A/B switch.
-    const bool inkernel_bias = (flags & SMOLMC_SAMPLE_BIAS) && !(flags & SMOLMC_SAMPLE_WL) && h->lean && !h->univ &&
+    const bool inkernel_bias = (flags & SMOLMC_SAMPLE_BIAS) && !(flags & SMOLMC_SAMPLE_WL) && h->lean() && !h->univ() &&
                                h->lp.bias_type && !smolmc_env(ENV_NO_INKERNEL_BIAS);
     const bool snapshot_path = (flags & SMOLMC_SAMPLE_WL) || ((flags & SMOLMC_SAMPLE_BIAS) && !inkernel_bias);
     const bool lazy_rows = is_lazy(h) && !snapshot_path;
@@ -3010,35 +3081,11 @@ extern "C" int smolmc_get_samples_ex(smolmc_handle *h, double *enthalpy, double 
                             wl_occurrences, wl_mean_features, wl_mod_factor);
 }
 
-// lean replay kernels that exist: Metropolis flips / swaps (plain, KF, with MCBias), multi-sublattice,
-// Wang-Landau; TableFlip handles have their own
-static bool smolmc_lean_replay_takes(const smolmc_handle *h) {
-    if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) return false;
-    if (h->lean_multi_wl && h->lean_kf) return false; // (no replay instantiation of the KFW kernel: mc_kernel / the universal kernel)
-    return true;
-}
-static int smolmc_launch_lean_replay(smolmc_handle *h, const LeanParams &lp) {
-    const bool wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
-    if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) {
-        LeanParams q = lp;
-        TRY(update_walker_order(h, q));
-        if (h->lean_multi)
-            return h->lean_nslot == 2 ? smolmc_launch_multi_table_replay_2(h, q)
-                                      : (h->lean_nslot == 4 ? smolmc_launch_multi_table_replay_4(h, q) : smolmc_launch_multi_table_replay_8(h, q));
-        return h->lean_nslot == 2 ? smolmc_launch_table_replay_2(h, q) : smolmc_launch_table_replay_4(h, q);
-    }
-    if (lp.bias_type && h->lean_multi)
-        return h->lean_nslot == 2 ? smolmc_launch_multi_bias_replay_2(h, lp)
-                                  : (h->lean_nslot == 4 ? smolmc_launch_multi_bias_replay_4(h, lp) : smolmc_launch_multi_bias_replay_8(h, lp));
-    if (lp.bias_type) return h->lean_nslot == 2 ? smolmc_launch_lean_bias_replay_2(h, lp) : smolmc_launch_lean_bias_replay_4(h, lp);
-    if (h->lean_multi_wl)
-        return h->lean_nslot == 2 ? smolmc_launch_multi_wl_replay_2(h, lp)
-                                  : (h->lean_nslot == 4 ? smolmc_launch_multi_wl_replay_4(h, lp) : smolmc_launch_multi_wl_replay_8(h, lp));
-    if (h->lean_multi)
-        return h->lean_nslot == 2 ? smolmc_launch_multi_replay_2(h, lp)
-                                  : (h->lean_nslot == 4 ? smolmc_launch_multi_replay_4(h, lp) : smolmc_launch_multi_replay_8(h, lp));
-    return wl ? (h->lean_nslot == 2 ? smolmc_launch_wl_replay_2(h, lp) : smolmc_launch_wl_replay_4(h, lp))
-              : (h->lean_nslot == 2 ? smolmc_launch_lean_replay_2(h, lp) : smolmc_launch_lean_replay_4(h, lp));
+// lean replay kernels that exist: the replay entries of lean_families
+static bool smolmc_lean_replay_takes(const smolmc_handle *h) { return lean_launcher(h, true) != nullptr; }
+static int smolmc_launch_lean_replay(smolmc_handle *h, LeanParams lp) {
+    TRY(update_walker_order(h, lp)); // (a permutation for the TableFlip kernels only)
+    return lean_launcher(h, true)(h, lp);
 }
 
 extern "C" int smolmc_replay(smolmc_handle *h, int64_t nsteps, const int32_t *steps, const double *uniforms,
@@ -3081,13 +3128,12 @@ extern "C" int smolmc_replay(smolmc_handle *h, int64_t nsteps, const int32_t *st
     // (the lean TableFlip replay kernels pick sites without replacement like the usher: a record with a repeated
     // site -- valid for the boundary -- takes the universal kernel, which evaluates it flip by flip)
     // (a biased or Wang-Landau TableFlip handle has no REPLAY instantiation: the universal kernel replays its records)
-    const bool lean_table_replay = h->lean && table && nsteps < ((int64_t)1 << 30) && !repeated_site &&
-                                   !h->lp.bias_type && h->cfg.kernel_type != SMOLMC_KERNEL_WANGLANDAU;
+    const bool lean_table_replay = h->lean() && table && nsteps < ((int64_t)1 << 30) && !repeated_site && smolmc_lean_replay_takes(h);
     // (a Flip handle's own kernel takes single flips: records of two flips go to mc_kernel / the universal kernel)
     const bool lean_shape_ok = two_flip_ok && (h->cfg.step_type != SMOLMC_STEP_FLIP || max_flips <= 1);
-    const bool lean_replay = h->lean && !want_general && nsteps < ((int64_t)1 << 30) && !replay_universal &&
+    const bool lean_replay = h->lean() && !want_general && nsteps < ((int64_t)1 << 30) && !replay_universal &&
                              ((lean_shape_ok && smolmc_lean_replay_takes(h)) || lean_table_replay);
-    const bool general_replay = !lean_replay && !h->univ && two_flip_ok && h->general_ok && !replay_universal;
+    const bool general_replay = !lean_replay && !h->univ() && two_flip_ok && h->general_ok && !replay_universal;
     if (smolmc_env(ENV_DEBUG))
         fprintf(stderr, "[smolmc] replay path=%s max_flips=%d priori_given=%d\n",
                 lean_replay ? (table ? "lean-table" : "lean") : (general_replay ? "general" : "universal"), max_flips, (int)priori_given);

@@ -722,6 +722,12 @@ struct SampleSlot {
     hipEvent_t kernel_done = nullptr, copy_done = nullptr;
 };
 
+// The kernel a handle runs.  From K_LEAN on: the lean families, which launch through their row of lean_families
+// (engine.hip); from K_MULTI on: those of the multi-class layout.  K_LEAN / K_MULTI serve TableFlip without bias or
+// Wang-Landau too (mc_table_kernel / mc_table_multi_kernel behind the same launchers).
+enum KernelFamily { K_GENERAL, K_UNIVERSAL, K_LEAN, K_LEAN_BIAS, K_LEAN_CORR, K_WL, K_TABLE_BIAS, K_TABLE_WL,
+                    K_MULTI, K_MULTI_BIAS, K_MULTI_WL, K_MULTI_WL_KF, K_MULTI_TABLE_BIAS, K_MULTI_TABLE_WL };
+
 struct smolmc_handle {
     smolmc_config cfg;
     int device = 0;
@@ -737,17 +743,24 @@ struct smolmc_handle {
     RefTables rt;
     int R = 0, N = 0, Npad = 0, F = 0, Fce = 0, L = 0;
     std::vector<double> natural;
-    // dispatch
+    // dispatch: the kernel family every run of this handle launches (set once, at the end of smolmc_create; the
+    // rows of lean_families in engine.hip hold the launchers of the lean ones)
+    KernelFamily family = K_GENERAL;
+    bool lean() const { return family >= K_LEAN; }        // one of the lean families (h->lp is filled)
+    bool lean_multi() const { return family >= K_MULTI; } // ... on the multi-class layout (mc_lean_multi.h)
+    bool univ() const { return family == K_UNIVERSAL; }   // every launch takes the universal kernel
+    // launch geometry, by reader -- mc_kernel (mc_general.h): nslot, mm, generic, idx16, lds_bytes, waves_per_block;
+    // the lookup in lean_families: lean_nslot; every lean launcher: lean_mm, lean_lds; those of mc_lean_kernel
+    // (mc_lean.h): lean_solo, lean_occ, lean_kf; of mc_table_kernel (mc_lean.h, launch_table_ewm): lean_wpb,
+    // lean_lds_wpb8; of the multi-class kernels (mc_lean_multi.h): waves_per_block_lean
     int nslot = 0, mm = 0;
     bool generic = false, idx16 = false;
     size_t lds_bytes = 0;
     int waves_per_block = 4;
     int waves_per_block_lean = 4; // mc_lean_multi_kernel (LDS-sized)
     // lean kernel (single class / single contiguous sublattice / interactions / no ewald)
-    bool lean_tables = false, lean = false;
+    bool lean_tables = false;
     int lean_nslot = 0, lean_mm = 0, lean_ncls = 0;
-    bool lean_multi = false;            // dispatch to mc_lean_multi_kernel
-    bool lean_multi_wl = false;         // ... its Wang-Landau variant (WLK)
     bool lean_solo = false;             // mc_lean_kernel in its one-wave-per-workgroup layout
     int lean_occ = 0;                   // > 0: the solo instantiation held to this many waves per SIMD
     int lean_wpb = 4;          // TableFlip kernel: walkers (waves) per workgroup -- 8 when one such workgroup fills a CU's LDS (see launch_table_ewm)
@@ -775,9 +788,8 @@ struct smolmc_handle {
     int ew_gx_dims[3] = {0, 0, 0}, ew_gx_blocks = 0; // translation-compressed site kernel (0: none)
     std::vector<uint8_t> site_ncodes; // species codes allowed on each site (occupancy validation)
     std::vector<uint8_t> site_active; // 1 on the sites of the active sublattices (replay validation)
-    // universal kernel (mc_univ.h): always available; `univ` = every launch of this handle takes it
+    // universal kernel (mc_univ.h): always available (family K_UNIVERSAL: every launch of this handle takes it)
     UParams up;
-    bool univ = false;
     bool general_ok = true;      // mc_kernel can run this model (else: why not)
     std::string general_reason;
     // lazy cluster features (engine.hip, build_mc_tables): the lean kernels of this handle carry the scalar features
@@ -856,29 +868,22 @@ int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_4(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_8(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_16(smolmc_handle *h, const KParams &kp, int replay);
-int smolmc_launch_lean_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_table_bias_2(smolmc_handle *h, const LeanParams &lp); // TableFlip + MCBias (table_bias_n*.hip)
-int smolmc_launch_table_bias_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_table_wl_2(smolmc_handle *h, const LeanParams &lp); // Wang-Landau + TableFlip (table_wl_n*.hip)
-int smolmc_launch_table_wl_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_table_wl_2(smolmc_handle *h, const LeanParams &lp); // ... on the multi-class layout (multi_table_wl_n*.hip)
-int smolmc_launch_multi_table_wl_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_table_wl_8(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_table_bias_2(smolmc_handle *h, const LeanParams &lp); // TableFlip + MCBias on the multi-class layout (multi_table_bias_n*.hip)
-int smolmc_launch_multi_table_bias_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_table_bias_8(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_lean_4(smolmc_handle *h, const LeanParams &lp);
-// replay instantiations of the TableFlip / biased lean kernels
-int smolmc_launch_table_replay_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_table_replay_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_table_replay_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_table_replay_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_table_replay_8(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_lean_bias_replay_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_lean_bias_replay_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_bias_replay_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_bias_replay_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_bias_replay_8(smolmc_handle *h, const LeanParams &lp);
+// the lean families (rows of lean_families in engine.hip): smolmc_launch_<family>_<nslot>, one translation unit each
+// (<family>_n<nslot>.hip); nslot 8 on the multi-class layout only
+#define SMOLMC_LAUNCHERS2(f)                                            \
+    int smolmc_launch_##f##_2(smolmc_handle *h, const LeanParams &lp); \
+    int smolmc_launch_##f##_4(smolmc_handle *h, const LeanParams &lp);
+#define SMOLMC_LAUNCHERS3(f) SMOLMC_LAUNCHERS2(f) int smolmc_launch_##f##_8(smolmc_handle *h, const LeanParams &lp);
+SMOLMC_LAUNCHERS2(lean) SMOLMC_LAUNCHERS2(lean_replay) SMOLMC_LAUNCHERS2(table_replay)   // mc_lean_kernel, mc_table_kernel
+SMOLMC_LAUNCHERS2(lean_bias) SMOLMC_LAUNCHERS2(lean_bias_replay) SMOLMC_LAUNCHERS2(lean_corr) // ... with MCBias, KF
+SMOLMC_LAUNCHERS2(wl) SMOLMC_LAUNCHERS2(wl_replay)                                       // mc_wl_kernel
+SMOLMC_LAUNCHERS2(table_bias) SMOLMC_LAUNCHERS2(table_wl)                                // TableFlip + MCBias / Wang-Landau
+SMOLMC_LAUNCHERS3(multi) SMOLMC_LAUNCHERS3(multi_replay) SMOLMC_LAUNCHERS3(multi_table_replay) // mc_lean_multi_kernel, mc_table_multi_kernel
+SMOLMC_LAUNCHERS3(multi_bias) SMOLMC_LAUNCHERS3(multi_bias_replay)
+SMOLMC_LAUNCHERS3(multi_wl) SMOLMC_LAUNCHERS3(multi_wl_replay) SMOLMC_LAUNCHERS3(multi_wl_kf)
+SMOLMC_LAUNCHERS3(multi_table_bias) SMOLMC_LAUNCHERS3(multi_table_wl)
+#undef SMOLMC_LAUNCHERS2
+#undef SMOLMC_LAUNCHERS3
 #define SMOLMC_WL_ROWS 32  // mc_wl_kernel: cached rows of per-bin feature sums per walker (LDS)
 // per-walker LDS bytes of the Wang-Landau state of mc_lean_multi_kernel<..., WLK> (mc_lean_multi.h):
 // S f64 [L] | counted steps u32 [L] | sums: a log of SMOLMC_WLM_LOG finished runs [F] -- running means: occurrences at
@@ -891,31 +896,3 @@ __host__ __device__ inline size_t wl_multi_wave_bytes(int L, int F, int sum_mode
            (sum_mode ? (size_t)SMOLMC_WLM_LOG * F * 8 : (size_t)L * 8 + (size_t)SMOLMC_WL_ROWS * F * 8);
 }
 #define SMOLMC_LEAN_MAX_KF 6 // correlation functions per orbit served by the lean kernels (ternary triplets)
-int smolmc_launch_lean_corr_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_lean_corr_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_wl_replay_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_wl_replay_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_replay_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_replay_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_replay_8(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_lean_replay_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_lean_replay_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_wl_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_wl_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_lean_bias_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_lean_bias_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_8(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_wl_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_wl_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_wl_8(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_wl_kf_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_wl_kf_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_wl_kf_8(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_wl_replay_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_wl_replay_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_wl_replay_8(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_bias_2(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_bias_4(smolmc_handle *h, const LeanParams &lp);
-int smolmc_launch_multi_bias_8(smolmc_handle *h, const LeanParams &lp);
