@@ -260,7 +260,27 @@ static int num_ce_features(const smolmc_tables *t) {
     return t->feature_mode == SMOLMC_FEATURES_CORRELATIONS ? t->num_corr : t->num_orbits;
 }
 
-// Build the MC-optimised tables (classes, slot descriptors, member index rows).
+static bool is_wl(const smolmc_handle *h) { return h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU; }
+static bool is_table(const smolmc_handle *h) { return h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP; }
+// what one cluster of local record r weighs in an extensive feature: size / (cluster ratio * rows of the record)
+static double slot_scale(const smolmc_tables *t, int64_t r) { return (double)t->size / t->loc_ratio[r] / (double)t->loc_nrows[r]; }
+// Species of member a of orbit o's clusters as the cluster tensors see them: the strides are those of a row-major
+// tensor over the members' site spaces (orbit.py:268-275; validate_tables checks that they are)
+static int member_species(const smolmc_tables *t, int o, int a) {
+    const int32_t *st = t->tensor_indices + t->orb_stride_off[o];
+    return (a == 0 ? t->orb_tensor_len[o] : st[a - 1]) / st[a];
+}
+// site s carries exactly one Ewald species, at code 0 (outside the active sublattices: a charge that never changes)
+static bool single_ewald_species(const smolmc_tables *t, int s) {
+    const int32_t *inds = t->ewald_inds + (size_t)s * t->ewald_width;
+    int nvalid = 0;
+    for (int c = 0; c < t->ewald_width; ++c) nvalid += inds[c] >= 0;
+    return nvalid == 1 && inds[0] >= 0;
+}
+
+// ---- the MC-optimised tables: site classes, mc_kernel's slot tables (h->kp), the lean families' (h->lp) ---------
+// build_mc_tables, below, is the list of stages.  Every stage but general_tables and commit_lean_tables is host
+// arithmetic on its arguments: no device call, no write to the handle.
 // Models mc_kernel / the lean kernels cannot take (more than 1024 clusters per site, more than 255 site
 // classes, tensor strides beyond 16 bits, an occupancy that does not fit LDS) are not refused: the
 // handle notes why (general_reason) and every launch takes the universal kernel (mc_univ.h).
@@ -270,109 +290,160 @@ static int no_general(smolmc_handle *h, const char *why) {
     return 0;
 }
 
-static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
-    const int N = t->num_sites;
-    const bool corr = t->feature_mode == SMOLMC_FEATURES_CORRELATIONS;
-    if ((size_t)h->Npad + 4096 > 160 * 1024) return no_general(h, "occupancy does not fit LDS");
-    if (smolmc_env(ENV_FORCE_UNIVERSAL)) return no_general(h, "SMOLMC_FORCE_UNIVERSAL");
-    // does any local row contain a repeated site (aliased tiny supercells)?
-    bool aliased = false;
-    int maxI = 1;
-    for (int s = 0; s < N && !aliased; ++s)
-        for (int64_t r = t->site_ptr[s]; r < t->site_ptr[s + 1] && !aliased; ++r) {
-            const int o = t->loc_orbit[r], I = t->orb_nsites[o];
-            const int32_t *rows = t->loc_idx + t->loc_off[r];
-            for (int j = 0; j < t->loc_nrows[r] && !aliased; ++j)
-                for (int a = 0; a < I && !aliased; ++a)
-                    for (int b = a + 1; b < I; ++b)
-                        if (rows[j * I + a] == rows[j * I + b]) aliased = true;
+// What has to hold before any table is built, in the order in which it is reported
+struct GeneralLimits {
+    const char *universal = nullptr; // mc_kernel cannot run the model: why
+    const char *error = nullptr;     // no kernel can
+    // some local row holds a site twice (a supercell shorter than a cluster); some local row does not hold its own
+    // site at all (searched on unaliased cells only)
+    bool aliased = false, unnamed = false;
+    int maxI = 1;                    // sites of the largest cluster
+};
+static GeneralLimits general_limits(const smolmc_tables *t, int Npad) {
+    GeneralLimits g;
+    auto universal = [&](const char *why) { g.universal = why; return g; };
+    if ((size_t)Npad + 4096 > 160 * 1024) return universal("occupancy does not fit LDS");
+    if (smolmc_env(ENV_FORCE_UNIVERSAL)) return universal("SMOLMC_FORCE_UNIVERSAL");
+    for (int s = 0; s < t->num_sites && !g.aliased; ++s)
+        for (int64_t r = t->site_ptr[s]; r < t->site_ptr[s + 1] && !g.aliased; ++r) {
+            const int I = t->orb_nsites[t->loc_orbit[r]];
+            const int32_t *row = t->loc_idx + t->loc_off[r];
+            for (int j = 0; j < t->loc_nrows[r] && !g.aliased; ++j, row += I) {
+                bool named = false;
+                for (int a = 0; a < I; ++a) {
+                    named = named || row[a] == s;
+                    for (int b = a + 1; b < I; ++b) g.aliased = g.aliased || row[a] == row[b];
+                }
+                g.unnamed = g.unnamed || !named;
+            }
         }
-    for (int o = 0; o < t->n_orb; ++o) maxI = std::max(maxI, (int)t->orb_nsites[o]);
-    if (maxI > SMOLMC_MAX_CLUSTER_SITES) return fail("cluster larger than SMOLMC_MAX_CLUSTER_SITES");
+    for (int o = 0; o < t->n_orb; ++o) g.maxI = std::max(g.maxI, (int)t->orb_nsites[o]);
+    if (g.maxI > SMOLMC_MAX_CLUSTER_SITES) { g.error = "cluster larger than SMOLMC_MAX_CLUSTER_SITES"; return g; }
     for (int o = 0; o < t->n_orb; ++o)
         for (int i = 0; i < t->orb_nsites[o]; ++i)
-            if (t->tensor_indices[t->orb_stride_off[o] + i] > 65535)
-                return no_general(h, "tensor stride exceeds 16 bits");
-    h->generic = aliased;
-    const int need_mm = aliased ? maxI : std::max(1, maxI - 1);
+            if (t->tensor_indices[t->orb_stride_off[o] + i] > 65535) return universal("tensor stride exceeds 16 bits");
+    return g;
+}
 
-    // per-site slot lists: (orbit, self position p, row pointer, record r)
-    struct Slot {
-        int orbit, p, nmem;
-        int64_t rec;
-        const int32_t *row;
-    };
-    std::vector<std::vector<Slot>> slots(N);
-    std::vector<int> site_class(N, 255);
-    std::map<std::vector<long long>, int> class_of;
-    std::vector<int> class_rep; // representative site per class
-    for (int s = 0; s < N; ++s) {
-        if (t->site_ptr[s] == t->site_ptr[s + 1]) continue;
-        std::vector<Slot> &sl = slots[s];
-        std::vector<long long> sig;
-        for (int64_t r = t->site_ptr[s]; r < t->site_ptr[s + 1]; ++r) {
-            const int o = t->loc_orbit[r], I = t->orb_nsites[o], J = t->loc_nrows[r];
-            const int32_t *rows = t->loc_idx + t->loc_off[r];
-            std::vector<Slot> rec;
-            for (int j = 0; j < J; ++j) {
-                int p = 0;
-                if (!aliased)
-                    for (int a = 0; a < I; ++a)
-                        if (rows[j * I + a] == s) p = a;
-                rec.push_back(Slot{o, p, aliased ? I : I - 1, r, rows + (size_t)j * I});
-            }
-            std::stable_sort(rec.begin(), rec.end(), [](const Slot &a, const Slot &b) { return a.p < b.p; });
-            sig.push_back(o);
-            sig.push_back(J);
-            long long rb;
-            memcpy(&rb, &t->loc_ratio[r], 8);
-            sig.push_back(rb);
-            for (int a = 0; a < I; ++a) {
-                long long cnt = 0;
-                for (auto &q : rec) cnt += q.p == a;
-                sig.push_back(cnt);
-            }
-            sl.insert(sl.end(), rec.begin(), rec.end());
+// One cluster of a site as a kernel evaluates it: a row of one of the site's local records.  The positions of the row
+// that count as the site ITSELF (selfmask) are folded into the slot's table; the other members are gathered.
+struct Slot {
+    int orbit;
+    int64_t rec;        // local record
+    const int32_t *row; // the member sites (orb_nsites[orbit] of them)
+    uint32_t selfmask;
+    int pfirst, nother; // first self position (0: none), members gathered
+};
+// How a table reads a row.  ROWS_OWN: the self positions are where the row holds the site -- the lean families
+// everywhere, and mc_kernel too wherever every row holds its site exactly once: there both use ONE list.  mc_kernel
+// differs in two cases.  On an ALIASED cell (some row holds a site twice) it keeps generic rows: no self position, all
+// I members gathered, rows in the order of the record (ROWS_GENERIC).  And a row that does not hold its site at all --
+// validate_tables does not refuse one -- it reads as if member 0 were the site (ROWS_MEMBER0: p = 0, member 0 is not
+// gathered), where the lean tables gather all I members and get a delta table of zeros (selfmask 0).
+enum RowView { ROWS_OWN, ROWS_MEMBER0, ROWS_GENERIC };
+// The slots of site s, in the order both tables use: inside a record by first self position, then by mask -- the
+// order of the reference's rows (equivalent cluster major) at equal positions, which is the same on every site of a
+// translation class -- and the records' slots with most gathered members first, so that iterations are homogeneous.
+static std::vector<Slot> site_slots(const smolmc_tables *t, int s, RowView view) {
+    std::vector<Slot> sl;
+    for (int64_t r = t->site_ptr[s]; r < t->site_ptr[s + 1]; ++r) {
+        const int o = t->loc_orbit[r], I = t->orb_nsites[o];
+        const size_t first = sl.size();
+        const int32_t *row = t->loc_idx + t->loc_off[r];
+        for (int j = 0; j < t->loc_nrows[r]; ++j, row += I) {
+            uint32_t mask = 0;
+            for (int a = 0; a < I && view != ROWS_GENERIC; ++a)
+                if (row[a] == s) mask |= 1u << a;
+            if (view == ROWS_MEMBER0 && !mask) mask = 1u;
+            sl.push_back(Slot{o, r, row, mask, mask ? __builtin_ctz(mask) : 0, I - __builtin_popcount(mask)});
         }
-        // most members first so that iterations are homogeneous
-        std::stable_sort(sl.begin(), sl.end(), [](const Slot &a, const Slot &b) { return a.nmem > b.nmem; });
+        std::stable_sort(sl.begin() + first, sl.end(), [](const Slot &a, const Slot &b) {
+            return a.pfirst != b.pfirst ? a.pfirst < b.pfirst : a.selfmask < b.selfmask;
+        });
+    }
+    std::stable_sort(sl.begin(), sl.end(), [](const Slot &a, const Slot &b) { return a.nother > b.nother; });
+    return sl;
+}
+
+// Sites whose records agree (orbit, rows, ratio, rows per self position) form a class: they share slot descriptors.
+struct SiteClasses {
+    const char *universal = nullptr;           // mc_kernel cannot run the model: why
+    // per site: as mc_kernel reads the rows, and as the lean families do where that differs (else empty)
+    std::vector<std::vector<Slot>> slots, own_slots;
+    std::vector<int> site_class;               // 255: a site without clusters
+    std::vector<int> class_rep;                // representative site per class
+    int niter_max = 0, lean_need_mm = 1;       // groups of 64 slots of the largest class; most gathered members of a lean slot
+    bool lean_alike = true;                    // aliased cells: every site lists its lean slots as its class's representative does
+    const std::vector<Slot> &lean_slots(int s) const { return own_slots.empty() ? slots[s] : own_slots[s]; }
+};
+static SiteClasses site_classes(const smolmc_tables *t, const GeneralLimits &lim) {
+    const int N = t->num_sites;
+    SiteClasses sc;
+    sc.slots.resize(N);
+    sc.site_class.assign(N, 255);
+    std::map<std::vector<long long>, int> class_of;
+    for (int s = 0; s < N; ++s) {
+        const int64_t r0 = t->site_ptr[s], nrec = t->site_ptr[s + 1] - r0;
+        if (!nrec) continue;
+        sc.slots[s] = site_slots(t, s, lim.aliased ? ROWS_GENERIC : lim.unnamed ? ROWS_MEMBER0 : ROWS_OWN);
+        // signature: per record its orbit, rows and ratio, then the number of slots at each first self position
+        constexpr int W = 3 + SMOLMC_MAX_CLUSTER_SITES;
+        std::vector<long long> sig((size_t)nrec * W, 0);
+        for (int64_t r = r0; r < r0 + nrec; ++r) {
+            long long *g = &sig[(size_t)(r - r0) * W];
+            g[0] = t->loc_orbit[r];
+            g[1] = t->loc_nrows[r];
+            memcpy(&g[2], &t->loc_ratio[r], 8);
+        }
+        for (const Slot &k : sc.slots[s]) sig[(size_t)(k.rec - r0) * W + 3 + k.pfirst]++;
         auto itc = class_of.find(sig);
         if (itc == class_of.end()) {
-            if (class_rep.size() >= 255) return no_general(h, "more than 255 site classes");
-            itc = class_of.emplace(sig, (int)class_rep.size()).first;
-            class_rep.push_back(s);
+            if (sc.class_rep.size() >= 255) { sc.universal = "more than 255 site classes"; return sc; }
+            itc = class_of.emplace(std::move(sig), (int)sc.class_rep.size()).first;
+            sc.class_rep.push_back(s);
         }
-        site_class[s] = itc->second;
+        sc.site_class[s] = itc->second;
     }
-    const int nclasses = std::max<int>(1, (int)class_rep.size());
     size_t Cmax = 1;
-    for (int s : class_rep) Cmax = std::max(Cmax, slots[s].size());
-    const int niter_max = (int)((Cmax + 63) / 64);
-    h->nslot = niter_max <= 2 ? 2 : (niter_max <= 4 ? 4 : (niter_max <= 8 ? 8 : 16));
-    if (niter_max > 16) return no_general(h, "more than 1024 clusters per site");
+    for (int s : sc.class_rep) Cmax = std::max(Cmax, sc.slots[s].size());
+    sc.niter_max = (int)((Cmax + 63) / 64);
+    if (sc.niter_max > 16) { sc.universal = "more than 1024 clusters per site"; return sc; }
+    if (lim.aliased || lim.unnamed) {
+        sc.own_slots.resize(N);
+        for (int s = 0; s < N; ++s) sc.own_slots[s] = site_slots(t, s, ROWS_OWN);
+    }
+    for (int s = 0; s < N; ++s)
+        for (const Slot &k : sc.lean_slots(s)) sc.lean_need_mm = std::max(sc.lean_need_mm, k.nother);
+    // An aliased cell's classes were made from the generic rows: the lean slots are verified site by site
+    for (int s = 0; s < N && lim.aliased && sc.lean_alike; ++s) {
+        if (sc.site_class[s] == 255) continue;
+        const std::vector<Slot> &a = sc.lean_slots(s), &b = sc.lean_slots(sc.class_rep[sc.site_class[s]]);
+        sc.lean_alike = a.size() == b.size();
+        for (size_t q = 0; q < a.size() && sc.lean_alike; ++q)
+            sc.lean_alike = a[q].orbit == b[q].orbit && a[q].selfmask == b[q].selfmask && a[q].selfmask != 0;
+    }
+    return sc;
+}
+
+// mc_kernel's tables: decision tensors per class (xt), feature tensors (ft), slot descriptors, member index rows
+static int general_tables(smolmc_handle *h, const smolmc_tables *t, const GeneralLimits &lim, const SiteClasses &sc) {
+    const int N = t->num_sites;
+    const bool corr = t->feature_mode == SMOLMC_FEATURES_CORRELATIONS, aliased = lim.aliased;
+    const int nclasses = std::max<int>(1, (int)sc.class_rep.size()), niter_max = sc.niter_max;
+    const int nslot = niter_max <= 2 ? 2 : (niter_max <= 4 ? 4 : (niter_max <= 8 ? 8 : 16));
     // slot columns per class: the two-group kernels evaluate BOTH groups without a condition
     // (mc_general.h), so the padding goes up to their full width (padded slots add 0.0)
-    const int Cpad = 64 * (h->nslot <= 2 ? h->nslot : niter_max);
-    if (aliased)
-        h->mm = need_mm <= 3 ? 3 : 6;
-    else
-        h->mm = need_mm <= 2 ? 2 : (need_mm <= 3 ? 3 : 5);
-    const int MM = h->mm;
-    h->idx16 = (!aliased) && N <= 65535;
+    const int Cpad = 64 * (nslot <= 2 ? nslot : niter_max);
+    const int need_mm = aliased ? lim.maxI : std::max(1, lim.maxI - 1);
+    const int MM = aliased ? (need_mm <= 3 ? 3 : 6) : (need_mm <= 2 ? 2 : (need_mm <= 3 ? 3 : 5));
+    const bool idx16 = (!aliased) && N <= 65535;
 
-    // decision tensors per class, feature tensors shared
     std::vector<double> ft;
     std::vector<int> foff(t->n_orb);
     for (int o = 0; o < t->n_orb; ++o) {
         foff[o] = (int)ft.size();
-        const int Nt = t->orb_tensor_len[o];
-        if (corr) {
-            const double *ct = t->corr_tensors + t->orb_ctensor_off[o];
-            ft.insert(ft.end(), ct, ct + (size_t)t->orb_nfunc[o] * Nt);
-        } else {
-            const double *it = t->interaction_tensors + t->orb_itensor_off[o];
-            ft.insert(ft.end(), it, it + Nt);
-        }
+        const double *src = corr ? t->corr_tensors + t->orb_ctensor_off[o] : t->interaction_tensors + t->orb_itensor_off[o];
+        ft.insert(ft.end(), src, src + (size_t)(corr ? t->orb_nfunc[o] : 1) * t->orb_tensor_len[o]);
     }
     std::vector<double> xt;
     std::vector<uint4> descA((size_t)nclasses * Cpad, make_uint4(0, 0, 0, 0));
@@ -380,57 +451,40 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
     std::vector<double> slot_fs((size_t)nclasses * Cpad, 0.0);
     std::vector<int> cls_niter(nclasses, 0);
     xt.push_back(0.0); // padded slots read xt[0] - xt[0]
-    for (int c = 0; c < (int)class_rep.size(); ++c) {
-        const int s = class_rep[c];
-        const std::vector<Slot> &sl = slots[s];
+    for (int c = 0; c < (int)sc.class_rep.size(); ++c) {
+        const std::vector<Slot> &sl = sc.slots[sc.class_rep[c]];
         cls_niter[c] = (int)((sl.size() + 63) / 64);
         std::map<int64_t, int> xoff_of_rec;
         for (size_t q = 0; q < sl.size(); ++q) {
             const Slot &k = sl[q];
             const int o = k.orbit, I = t->orb_nsites[o], Nt = t->orb_tensor_len[o];
             const int32_t *st = t->tensor_indices + t->orb_stride_off[o];
-            const double scale = (double)t->size / t->loc_ratio[k.rec] / (double)t->loc_nrows[k.rec];
+            const double scale = slot_scale(t, k.rec);
             if (!xoff_of_rec.count(k.rec)) {
                 xoff_of_rec[k.rec] = (int)xt.size();
                 for (int i = 0; i < Nt; ++i) {
-                    double v;
-                    if (corr) {
-                        // energy tensor: sum_k coef[bit_id+k] * ct[k][i], times scale
-                        v = 0;
+                    double v = 0;
+                    if (corr) { // energy tensor: sum_k coef[bit_id+k] * ct[k][i], times scale
                         const double *ct = t->corr_tensors + t->orb_ctensor_off[o];
-                        for (int kk = 0; kk < t->orb_nfunc[o]; ++kk)
-                            v += t->ce_coefs[t->orb_bit_id[o] + kk] * ct[(size_t)kk * Nt + i];
+                        for (int kk = 0; kk < t->orb_nfunc[o]; ++kk) v += t->ce_coefs[t->orb_bit_id[o] + kk] * ct[(size_t)kk * Nt + i];
                         v *= scale;
                     } else {
-                        v = t->ce_coefs[t->orb_id[o]] * scale *
-                            t->interaction_tensors[t->orb_itensor_off[o] + i];
+                        v = t->ce_coefs[t->orb_id[o]] * scale * t->interaction_tensors[t->orb_itensor_off[o] + i];
                     }
                     xt.push_back(v);
                 }
             }
+            // strides: the self position first (generic rows have none), then the gathered members
             uint16_t sv[6] = {0, 0, 0, 0, 0, 0};
-            if (aliased) {
-                for (int a = 0; a < I; ++a) sv[a] = (uint16_t)st[a];
-            } else {
-                sv[0] = (uint16_t)st[k.p];
-                int m = 1;
-                for (int a = 0; a < I; ++a)
-                    if (a != k.p) sv[m++] = (uint16_t)st[a];
-            }
-            uint4 A;
-            A.x = (uint32_t)xoff_of_rec[k.rec];
-            A.y = sv[0] | ((uint32_t)sv[1] << 16);
-            A.z = sv[2] | ((uint32_t)sv[3] << 16);
-            A.w = sv[4] | ((uint32_t)sv[5] << 16);
-            descA[(size_t)c * Cpad + q] = A;
-            uint4 B;
-            B.x = (uint32_t)foff[o];
-            B.y = (uint32_t)Nt;
+            int m = 0;
+            if (k.selfmask) sv[m++] = (uint16_t)st[k.pfirst];
+            for (int a = 0; a < I; ++a)
+                if (!((k.selfmask >> a) & 1u)) sv[m++] = (uint16_t)st[a];
+            descA[(size_t)c * Cpad + q] = make_uint4((uint32_t)xoff_of_rec[k.rec], sv[0] | ((uint32_t)sv[1] << 16),
+                                                     sv[2] | ((uint32_t)sv[3] << 16), sv[4] | ((uint32_t)sv[5] << 16));
             const uint32_t feat = corr ? (uint32_t)t->orb_bit_id[o] : (uint32_t)t->orb_id[o];
             const uint32_t K = corr ? (uint32_t)t->orb_nfunc[o] : 1u;
-            B.z = feat | (K << 16);
-            B.w = 0;
-            descB[(size_t)c * Cpad + q] = B;
+            descB[(size_t)c * Cpad + q] = make_uint4((uint32_t)foff[o], (uint32_t)Nt, feat | (K << 16), 0);
             slot_fs[(size_t)c * Cpad + q] = scale;
         }
     }
@@ -442,32 +496,25 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
     for (int s = 0; s < N; ++s) {
         for (int m = 0; m < MM; ++m)
             for (int c = 0; c < Cpad; ++c) idx32[((size_t)s * MM + m) * Cpad + c] = s;
-        const std::vector<Slot> &sl = slots[s];
+        const std::vector<Slot> &sl = sc.slots[s];
         for (size_t q = 0; q < sl.size(); ++q) {
-            const Slot &k = sl[q];
-            const int I = t->orb_nsites[k.orbit];
             int m = 0;
-            for (int a = 0; a < I; ++a) {
-                if (!aliased && a == k.p) continue;
-                idx32[((size_t)s * MM + m) * Cpad + q] = k.row[a];
-                m++;
-            }
+            for (int a = 0; a < t->orb_nsites[sl[q].orbit]; ++a)
+                if (!((sl[q].selfmask >> a) & 1u)) idx32[((size_t)s * MM + m++) * Cpad + q] = sl[q].row[a];
         }
     }
     KParams &kp = h->kp;
-    if (h->idx16) {
-        std::vector<uint16_t> idx16(idx_n);
-        for (size_t i = 0; i < idx_n; ++i) idx16[i] = (uint16_t)idx32[i];
+    if (idx16) {
+        const std::vector<uint16_t> idx16v(idx32.begin(), idx32.end());
         const uint16_t *d;
-        TRY(dev_upload(h, idx16.data(), idx_n, &d));
+        TRY(dev_upload(h, idx16v.data(), idx_n, &d));
         kp.idx = d;
     } else {
         const int32_t *d;
         TRY(dev_upload(h, idx32.data(), idx_n, &d));
         kp.idx = d;
     }
-    std::vector<uint8_t> sc8(N);
-    for (int s = 0; s < N; ++s) sc8[s] = (uint8_t)site_class[s];
+    std::vector<uint8_t> sc8(sc.site_class.begin(), sc.site_class.end());
     TRY(dev_upload(h, sc8.data(), (size_t)N, &kp.site_class));
     TRY(dev_upload(h, descA.data(), descA.size(), &kp.descA));
     TRY(dev_upload(h, descB.data(), descB.size(), &kp.descB));
@@ -475,63 +522,31 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
     TRY(dev_upload(h, cls_niter.data(), cls_niter.size(), &kp.cls_niter));
     TRY(dev_upload(h, xt.data(), xt.size(), &kp.xt));
     TRY(dev_upload(h, ft.data(), ft.size(), &kp.ft));
-    kp.xt_len = (int)xt.size();
-    kp.ft_len = (int)ft.size();
-    kp.nclasses = nclasses;
-    kp.Cpad = Cpad;
-    kp.Mmax = MM;
+    kp.xt_len = (int)xt.size(); kp.ft_len = (int)ft.size(); kp.nclasses = nclasses; kp.Cpad = Cpad; kp.Mmax = MM;
+    h->nslot = nslot; h->mm = MM; h->generic = aliased; h->idx16 = idx16;
+    return 0;
+}
 
-    // ---- lean tables (see mc_lean_kernel) ------------------------------------------
-    memset(&h->lp, 0, sizeof(LeanParams));
-    // The lean families' view of a site's clusters: one slot per local row, the flipped site's OWN positions in the row
-    // folded into the slot's table (selfmask), the other members gathered.  On an unaliased cell a row holds the site
-    // once (selfmask = 1 << p): exactly the slots above.  On an ALIASED cell -- a supercell shorter than a cluster, so
-    // that a row holds a site twice; the reference keeps such rows (clusterspace.py:1353-1359) and its evaluator flips
-    // every position of the site at once (evaluator.pyx:258-259 read occu_f / occu_i through the whole row) -- the
-    // delta table of the slot does the same: D[(old, new)][b] = T[base(b) + (sum of the self strides) new] - T[... old]
-    // (round 6; until then such cells ran on mc_kernel's GENERIC rows).  Order inside a record: by first self position,
-    // then by mask -- the order of the reference's rows (equivalent cluster major) at equal positions, which is the same
-    // on every site of a translation class; the classes are verified slot by slot below.
-    struct LSlot {
-        int orbit, pfirst, nother;
-        uint32_t selfmask;
-        int64_t rec;
-        const int32_t *row;
-    };
-    std::vector<std::vector<LSlot>> lslots(N);
-    int lean_need_mm = 1;
-    for (int s = 0; s < N; ++s) {
-        std::vector<LSlot> &sl = lslots[s];
-        for (int64_t r = t->site_ptr[s]; r < t->site_ptr[s + 1]; ++r) {
-            const int o = t->loc_orbit[r], I = t->orb_nsites[o], J = t->loc_nrows[r];
-            const int32_t *rows = t->loc_idx + t->loc_off[r];
-            std::vector<LSlot> rec;
-            for (int j = 0; j < J; ++j) {
-                uint32_t mask = 0;
-                for (int a = 0; a < I; ++a)
-                    if (rows[j * I + a] == s) mask |= 1u << a;
-                const int pf = mask ? __builtin_ctz(mask) : 0;
-                rec.push_back(LSlot{o, pf, I - __builtin_popcount(mask), mask, r, rows + (size_t)j * I});
-            }
-            std::stable_sort(rec.begin(), rec.end(), [](const LSlot &a, const LSlot &b) {
-                return a.pfirst != b.pfirst ? a.pfirst < b.pfirst : a.selfmask < b.selfmask;
-            });
-            sl.insert(sl.end(), rec.begin(), rec.end());
-        }
-        std::stable_sort(sl.begin(), sl.end(), [](const LSlot &a, const LSlot &b) { return a.nother > b.nother; });
-        for (const LSlot &q : sl) lean_need_mm = std::max(lean_need_mm, q.nother);
-    }
-    // aliased cells: every site of a class must list the same slots as the class's representative
-    bool lean_slots_ok = true;
-    if (aliased)
-        for (int s = 0; s < N && lean_slots_ok; ++s) {
-            if (site_class[s] == 255) continue;
-            const std::vector<LSlot> &a = lslots[s], &b = lslots[class_rep[site_class[s]]];
-            lean_slots_ok = a.size() == b.size();
-            for (size_t q = 0; q < a.size() && lean_slots_ok; ++q)
-                lean_slots_ok = a[q].orbit == b[q].orbit && a[q].selfmask == b[q].selfmask && a[q].selfmask != 0;
-        }
-    const bool lean_aliased_ok = !aliased || (lean_slots_ok && !smolmc_env(ENV_NO_LEAN_ALIASED));
+// ---- lean tables (see mc_lean_kernel) ------------------------------------------
+// The lean families' view of a site's clusters: one slot per local row, the flipped site's OWN positions in the row
+// folded into the slot's table (selfmask), the other members gathered.  On an ALIASED cell -- a supercell shorter than
+// a cluster, so that a row holds a site twice; the reference keeps such rows (clusterspace.py:1353-1359) and its
+// evaluator flips every position of the site at once (evaluator.pyx:258-259 read occu_f / occu_i through the whole
+// row) -- the delta table of the slot does the same: D[(old, new)][b] = T[base(b) + (sum of the self strides) new] -
+// T[... old] (round 6; until then such cells ran on mc_kernel's GENERIC rows).
+
+// Which features the lean kernels carry, and why a model does not get the lean tables at all (reported by
+// smolmc_kernel_info: the first condition that fails; empty: the tables are built)
+struct LeanMode {
+    bool corr_kf = false, corr_lazy = false, wide_lazy = false;
+    const char *reason = "";
+    bool lazy() const { return corr_lazy || wide_lazy; }
+};
+static LeanMode lean_mode(const smolmc_handle *h, const smolmc_tables *t, const GeneralLimits &lim, const SiteClasses &sc) {
+    const bool corr = t->feature_mode == SMOLMC_FEATURES_CORRELATIONS, wl = is_wl(h);
+    const int N = t->num_sites, niter_max = sc.niter_max, nfeat = num_ce_features(t);
+    const size_t ncls = sc.class_rep.size();
+    LeanMode m;
     // one site class: mc_lean_kernel (NSLOT <= 4); up to four classes or up to 512 clusters per
     // site: mc_lean_multi_kernel (per-class slot records in LDS)
     // Correlation features (ClusterExpansionProcessor, evaluator.pyx:211-265): when every orbit
@@ -546,255 +561,279 @@ static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
     // tables follow it (mc_lean_kernel KF).
     int kmax = 1;
     for (int o = 0; o < t->n_orb; ++o) kmax = std::max(kmax, (int)t->orb_nfunc[o]);
-    const bool cfg_wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
     // (the KF instantiations are plain Metropolis flip / swap kernels of the single-class layout)
-    bool corr_kf = corr && !corr_k1 && kmax <= SMOLMC_LEAN_MAX_KF && class_rep.size() == 1 && !cfg_wl && !t->bias_type &&
-                   h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP && t->n_sublattices == 1 && niter_max <= 4 && num_ce_features(t) <= 64 &&
-                   !smolmc_env(ENV_LAZY_FEATURES_ONLY);
+    m.corr_kf = corr && !corr_k1 && kmax <= SMOLMC_LEAN_MAX_KF && ncls == 1 && !wl && !t->bias_type && !is_table(h) &&
+                t->n_sublattices == 1 && niter_max <= 4 && nfeat <= 64 && !smolmc_env(ENV_LAZY_FEATURES_ONLY);
     // ... and the Wang-Landau kernel of the multi-class layout (KFW, round 5): any number of classes the layout takes
-    if (corr && !corr_k1 && kmax <= SMOLMC_LEAN_MAX_KF && cfg_wl && !t->bias_type && h->cfg.step_type != SMOLMC_STEP_TABLE_FLIP &&
-        num_ce_features(t) <= 61)
-        corr_kf = true;
+    if (corr && !corr_k1 && kmax <= SMOLMC_LEAN_MAX_KF && wl && !t->bias_type && !is_table(h) && nfeat <= 61) m.corr_kf = true;
     // LAZY cluster features (round 5): every other Metropolis kernel of the lean families takes a model with several
     // correlation functions per orbit as an interaction-mode model of the folded tensors E = sum_k coef_k ct_k --
     // the decision needs nothing else -- and carries no cluster features at all: they are evaluated from the
     // occupancy where somebody reads them (smolmc_get_state, sample rows; ensure_features / lazy_rows_kernel).
     // Any number of functions per orbit and of cluster features; Wang-Landau needs the features on every step and
     // stays on mc_kernel.
-    const bool corr_lazy = corr && !corr_k1 && !corr_kf && !cfg_wl && !smolmc_env(ENV_NO_LAZY_FEATURES);
+    m.corr_lazy = corr && !corr_k1 && !m.corr_kf && !wl && !smolmc_env(ENV_NO_LAZY_FEATURES);
     // ... and the same for models of more than 64 cluster features (the kernels' feature cells are one per lane)
-    const bool wide_lazy = !corr_lazy && !corr_kf && (!corr || corr_k1) && num_ce_features(t) > 64 && !cfg_wl &&
-                           !smolmc_env(ENV_NO_LAZY_FEATURES);
-    const bool lazy_any = corr_lazy || wide_lazy;
-    // (why a model does not get the lean tables, reported by smolmc_kernel_info: the first condition that fails)
-    h->lean_reason = class_rep.size() < 1 ? "no site with clusters"
-                     : class_rep.size() > 4 ? "more than 4 site classes"
-                     : !lean_aliased_ok ? "aliased supercell (a cluster holds a site twice) whose sites do not list their clusters alike"
-                     : (corr && !corr_k1 && !corr_kf && !corr_lazy) ? (cfg_wl ? "Wang-Landau with more than SMOLMC_LEAN_MAX_KF correlation functions per orbit, more than 61 of them, or TableFlip"
-                                                                                : "environment override (SMOLMC_NO_LAZY_FEATURES)")
-                     : N > 65535 ? "more than 65535 sites"
-                     : niter_max > 8 ? "more than 512 clusters per site"
-                     : lean_need_mm > 3 ? "clusters of more than 4 sites"
-                     : (num_ce_features(t) > 64 && !lazy_any) ? "more than 64 cluster features (Wang-Landau or correlation functions on the KF kernels)" : "";
-    if (class_rep.size() >= 1 && class_rep.size() <= 4 && lean_aliased_ok && (!corr || corr_k1 || corr_kf || corr_lazy) && N <= 65535 &&
-        niter_max <= 8 && lean_need_mm <= 3 && (num_ce_features(t) <= 64 || lazy_any)) {
-        const int NSL = niter_max <= 2 ? 2 : (niter_max <= 4 ? 4 : 8);
-        const int NCLS = (int)class_rep.size();
-        const int MML = lean_need_mm <= 2 ? 2 : 3;
-        const int ROW = NSL * MML;
-        std::vector<uint16_t> lidx((size_t)N * 64 * ROW);
-        for (int s = 0; s < N; ++s) {
-            for (int q = 0; q < 64 * ROW; ++q) lidx[(size_t)s * 64 * ROW + q] = (uint16_t)s;
-            const std::vector<LSlot> &sl = lslots[s];
-            for (size_t q = 0; q < sl.size(); ++q) {
-                const LSlot &k = sl[q];
-                const int I = t->orb_nsites[k.orbit];
-                const int it = (int)(q / 64), ln = (int)(q % 64);
-                int m = 0;
-                for (int a = 0; a < I; ++a) {
-                    if ((k.selfmask >> a) & 1u) continue; // (the site's own positions are folded into the slot's table)
-                    lidx[(((size_t)s * 64 + ln) * NSL + it) * MML + m] = (uint16_t)k.row[a];
-                    m++;
-                }
-            }
-        }
-        // ---- LDS bank swizzle: pick the address permutation s ^ (((s >> a) & m) << b) that
-        // minimises the modelled bank-conflict cycles of the occupancy gathers (each
-        // ds_read_u8 is served in two 32-lane groups; a group costs the max number of
-        // distinct dwords on one of the 32 banks).  See tools/lds_conflict_model.py.
-        int Nlds = 16;
-        while (Nlds < h->Npad) Nlds <<= 1;
-        int best_a = 0, best_m = 0, best_b = 0;
-        {
-            auto model_cost = [&](int a, int m, int b) {
-                double tot = 0;
-                const int nsamp = std::min(N, 48);
-                for (int k = 0; k < nsamp; ++k) {
-                    const int s = (int)(((long long)k * 2654435761ll) % N);
-                    if (lslots[s].empty()) continue;
-                    for (int q = 0; q < ROW; ++q)
-                        for (int g = 0; g < 2; ++g) {
-                            int cnt[32] = {0};
-                            int seen[32];
-                            int nseen = 0;
-                            for (int ln = 32 * g; ln < 32 * g + 32; ++ln) {
-                                const int x = lidx[((size_t)s * 64 + ln) * ROW + q];
-                                const int dw = (x ^ (((x >> a) & m) << b)) >> 2;
-                                bool dup = false;
-                                for (int z = 0; z < nseen; ++z) dup |= seen[z] == dw;
-                                if (!dup) { seen[nseen++] = dw; cnt[dw & 31]++; }
-                            }
-                            int mx = 0;
-                            for (int z = 0; z < 32; ++z) mx = std::max(mx, cnt[z]);
-                            tot += mx;
-                        }
-                }
-                return tot;
-            };
-            double best = model_cost(0, 0, 0);
-            for (int a = 3; a <= 12; ++a)
-                for (int b = 2; b <= 5; ++b)
-                    for (int m : {3, 7, 15, 31}) {
-                        // bijection on [0, Nlds): source bits [a, a+k) above the destination
-                        // bits [b, b+k) and inside the (power-of-two) array
-                        const int k = m == 3 ? 2 : (m == 7 ? 3 : (m == 15 ? 4 : 5));
-                        if (a < b + k || (1 << (a + k)) > Nlds) continue;
-                        const double c = model_cost(a, m, b);
-                        if (c < best * 0.97) { best = c; best_a = a; best_m = m; best_b = b; }
-                    }
-        }
-        if (best_m == 0) Nlds = h->Npad; // identity: no power-of-two padding needed
-        for (size_t i = 0; i < lidx.size(); ++i) {
-            const int x = lidx[i];
-            lidx[i] = (uint16_t)(x ^ (((x >> best_a) & best_m) << best_b));
-        }
-        h->lp.swz_a = best_a; h->lp.swz_m = best_m; h->lp.swz_b = best_b; h->lp.Nlds = Nlds;
+    m.wide_lazy = !m.corr_lazy && !m.corr_kf && (!corr || corr_k1) && nfeat > 64 && !wl && !smolmc_env(ENV_NO_LAZY_FEATURES);
+    const bool aliased_ok = !lim.aliased || (sc.lean_alike && !smolmc_env(ENV_NO_LEAN_ALIASED));
+    m.reason = ncls < 1 ? "no site with clusters"
+               : ncls > 4 ? "more than 4 site classes"
+               : !aliased_ok ? "aliased supercell (a cluster holds a site twice) whose sites do not list their clusters alike"
+               : (corr && !corr_k1 && !m.corr_kf && !m.corr_lazy) ? (wl ? "Wang-Landau with more than SMOLMC_LEAN_MAX_KF correlation functions per orbit, more than 61 of them, or TableFlip"
+                                                                      : "environment override (SMOLMC_NO_LAZY_FEATURES)")
+               : N > 65535 ? "more than 65535 sites"
+               : niter_max > 8 ? "more than 512 clusters per site"
+               : sc.lean_need_mm > 3 ? "clusters of more than 4 sites"
+               : (nfeat > 64 && !m.lazy()) ? "more than 64 cluster features (Wang-Landau or correlation functions on the KF kernels)" : "";
+    return m;
+}
 
-        // delta tables, one per (orbit, self position): D[(old, new)][b] with the COMPACT base
-        // index b = sum_m S^m * species(member m) over the other members of the cluster (S =
-        // max species per site), padded to a common [S*S][NTP], NTP = S^MML.  Symmetric
-        // clusters give bitwise-equal tables for several self positions: those are shared.
-        const int SMAX = t->max_species;
-        int NTP = 1;
-        for (int m = 0; m < MML; ++m) NTP *= SMAX;
-        // the stride between tables is padded so that it is not a multiple of the 64-dword LDS
-        // bank period (lanes of one wave read the same (pair, base) entry of DIFFERENT tables)
-        size_t tlen = (size_t)SMAX * SMAX * NTP;
-        if ((tlen & 1) == 0) tlen += 1;
-        std::vector<double> dt(tlen, 0.0); // table 0 = zeros, used by padded slots
-        // Entries the LDS copy of the tables may take.  8000 (64 KB, two workgroups per CU) until round 6; models between
-        // that and what one workgroup's LDS holds beside the walkers' state (the layouts below decide) ran on mc_kernel
-        // with the tables in L2: measured on five quaternary triplet / quadruplet models of the fuzz campaign at 2048
-        // walkers, 0.39-1.05e9 steps/s there against 0.99-2.43e9 here (tools/time_fuzz_case.py).
-        constexpr size_t dt_max = 18000;
-        std::vector<double> dtk; // KF: correlation-function tables (global memory), see LeanParams::dtk
-        std::vector<LeanSlot> ls((size_t)NCLS * NSL * 64);
-        memset(ls.data(), 0, ls.size() * sizeof(LeanSlot));
-        std::map<std::pair<int, int>, uint32_t> doff_of;
-        bool ok = true;
-        double sum_abs_max = 0.0;
-        for (int cls = 0; cls < NCLS && ok; ++cls) {
-        const std::vector<LSlot> &sl = lslots[class_rep[cls]];
-        double sum_abs = 0.0;
-        for (size_t q = 0; q < sl.size() && ok; ++q) {
-            const LSlot &k = sl[q];
-            const int o = k.orbit, I = t->orb_nsites[o], Nt = t->orb_tensor_len[o];
-            const int32_t *st = t->tensor_indices + t->orb_stride_off[o];
-            const double *T = corr ? t->corr_tensors + t->orb_ctensor_off[o] // K == 1: the one function
-                                   : t->interaction_tensors + t->orb_itensor_off[o];
-            const int feat = corr ? t->orb_bit_id[o] : t->orb_id[o];
-            const int K = corr_kf ? t->orb_nfunc[o] : 1;
-            const int Kfold = (corr_kf || corr_lazy) ? t->orb_nfunc[o] : 1;
-            std::vector<double> Efold; // KF / lazy: folded tensor sum_k coef_k ct_k (decision table source)
-            if (corr_kf || corr_lazy) {
-                Efold.assign((size_t)Nt, 0.0);
-                for (int kk = 0; kk < Kfold; ++kk)
-                    for (int i = 0; i < Nt; ++i) Efold[i] += t->ce_coefs[feat + kk] * T[(size_t)kk * Nt + i];
-            }
-            // the site's own positions: their strides add up (one position on an unaliased cell), its site space is
-            // that of the first of them
-            int ss = 0;
-            for (int a = 0; a < I; ++a)
-                if ((k.selfmask >> a) & 1u) ss += st[a];
-            const int Sself = k.pfirst == 0 ? Nt / st[0] : st[k.pfirst - 1] / st[k.pfirst];
-            const int nother = k.nother;
-            const auto key = std::make_pair(o, (int)k.selfmask);
-            if (!doff_of.count(key)) {
-                // tables of the slot: the decision table (LDS) and, in KF mode, K correlation-function
-                // tables (global memory, read on accepted steps only)
-                const int ntab = corr_kf ? 1 + K : 1;
-                std::vector<double> D((size_t)ntab * tlen, 0.0);
-                int nb = 1;
-                for (int a = 0; a < nother; ++a) nb *= SMAX;
-                for (int tb = 0; tb < ntab; ++tb) {
-                const double *Tsrc = corr_lazy ? Efold.data() : !corr_kf ? T : (tb == 0 ? Efold.data() : T + (size_t)(tb - 1) * Nt);
-                double *Dt = D.data() + (size_t)tb * tlen;
-                for (int b = 0; b < nb; ++b) {
-                    // decode b into the species of the other members -> tensor base index
-                    long base = 0;
-                    int rem = b;
-                    bool valid = true;
-                    for (int a = 0; a < I; ++a) {
-                        if ((k.selfmask >> a) & 1u) continue;
-                        const int v = rem % SMAX;
-                        rem /= SMAX;
-                        const int Sa = a == 0 ? Nt / st[0] : st[a - 1] / st[a];
-                        if (v >= Sa) valid = false;
-                        base += (long)st[a] * v;
-                    }
-                    if (!valid) continue;
-                    for (int oldc = 0; oldc < Sself; ++oldc)
-                        for (int newc = 0; newc < Sself; ++newc)
-                            Dt[((size_t)oldc * SMAX + newc) * NTP + b] =
-                                Tsrc[base + (long)ss * newc] - Tsrc[base + (long)ss * oldc];
-                }
-                }
-                uint32_t at = 0; // (identical tables are shared; KF: decision AND function tables identical)
-                for (size_t off = tlen; off + tlen <= dt.size() && !at; off += tlen) {
-                    if (memcmp(dt.data() + off, D.data(), (size_t)tlen * sizeof(double)) != 0) continue;
-                    if (corr_kf) {
-                        std::vector<double> want((size_t)SMOLMC_LEAN_MAX_KF * tlen, 0.0);
-                        std::copy(D.begin() + tlen, D.end(), want.begin());
-                        if (memcmp(dtk.data() + off * SMOLMC_LEAN_MAX_KF, want.data(), want.size() * sizeof(double)) != 0)
-                            continue;
-                    }
-                    at = (uint32_t)off;
-                }
-                if (!at) {
-                    at = (uint32_t)dt.size();
-                    dt.insert(dt.end(), D.begin(), D.begin() + tlen);
-                    if (corr_kf) {
-                        dtk.resize(dt.size() * SMOLMC_LEAN_MAX_KF, 0.0);
-                        std::copy(D.begin() + tlen, D.end(), dtk.begin() + (size_t)at * SMOLMC_LEAN_MAX_KF);
-                    }
-                }
-                doff_of[key] = at;
-            }
-            const double scale = (double)t->size / t->loc_ratio[k.rec] / (double)t->loc_nrows[k.rec];
-            LeanSlot &L = ls[((size_t)cls * NSL + q / 64) * 64 + (q % 64)];
-            L.doff8 = doff_of[key] * 8u;
-            {
-                uint32_t cs = 8u;
-                for (int m = 0; m < nother; ++m, cs *= (uint32_t)SMAX) L.stride8[m] = cs;
-            }
-            L.feat = lazy_any ? 0u : (uint32_t)feat; // (lazy: the kernels' feature cells are never read)
-            L.live = (uint32_t)K;
-            L.w = (corr_kf || corr_lazy) ? scale : t->ce_coefs[feat] * scale; // (KF / lazy: the coefficients are folded into the table)
-            L.fs = scale;
-            if (dt.size() > dt_max) { ok = false; h->lean_reason = "delta tables beyond 18000 entries (species^(cluster size - 1) x species^2 per distinct table)"; } // keep the LDS tables within budget
-            double dmax = 0.0;
-            {
-                const double *D = dt.data() + doff_of[key];
-                for (size_t z = 0; z < tlen; ++z) dmax = std::max(dmax, std::fabs(D[z]));
-            }
-            sum_abs += std::fabs(L.w) * dmax;
-        }
-        sum_abs_max = std::max(sum_abs_max, sum_abs);
-        }
-        // float32 pre-test of the accept decision: a step sums at most two flips' worth of
-        // |w * d| over the slots, a float32 conversion + 6-level tree adds at most
-        // 7 * 2^-24 of that; 2^-19 leaves a 4.5x margin.
-        h->lp.fast_eps = 2.0 * sum_abs_max * ldexp(1.0, -19);
-        h->lp.ktab8 = (uint32_t)tlen * 8u;
-        h->lean_kf = corr_kf ? SMOLMC_LEAN_MAX_KF : 0;
-        h->lazy_tables = lazy_any;
-        h->lp.nt8 = (uint32_t)NTP * 8u;
-        h->lp.snt8 = (uint32_t)NTP * 8u * (uint32_t)SMAX;
-        if (ok) {
-            TRY(dev_upload(h, lidx.data(), lidx.size(), &h->lp.idx));
-            h->lean_idx_host = std::move(lidx);
-            TRY(dev_upload(h, dt.data(), dt.size(), &h->lp.dt));
-            if (corr_kf) TRY(dev_upload(h, dtk.data(), dtk.size(), &h->lp.dtk));
-            TRY(dev_upload(h, ls.data(), ls.size(), &h->lp.slots));
-            h->lp.dt_len = (int)dt.size();
-            h->lean_tables = true;
-            h->lean_nslot = NSL;
-            h->lean_mm = MML;
-            h->lean_ncls = NCLS;
-            h->site_class_host = site_class;
+// lane-packed member rows [site][lane][NSL][MML] of the gathered members; padded entries point at the site itself
+static std::vector<uint16_t> lean_index_rows(const smolmc_tables *t, const SiteClasses &sc, int NSL, int MML) {
+    const int N = t->num_sites, ROW = NSL * MML;
+    std::vector<uint16_t> lidx((size_t)N * 64 * ROW);
+    for (int s = 0; s < N; ++s) {
+        for (int q = 0; q < 64 * ROW; ++q) lidx[(size_t)s * 64 * ROW + q] = (uint16_t)s;
+        const std::vector<Slot> &sl = sc.lean_slots(s);
+        for (size_t q = 0; q < sl.size(); ++q) {
+            const int it = (int)(q / 64), ln = (int)(q % 64);
+            int m = 0;
+            for (int a = 0; a < t->orb_nsites[sl[q].orbit]; ++a)
+                if (!((sl[q].selfmask >> a) & 1u)) lidx[(((size_t)s * 64 + ln) * NSL + it) * MML + m++] = (uint16_t)sl[q].row[a];
         }
     }
+    return lidx;
+}
+
+// LDS bank swizzle: the address permutation s ^ (((s >> a) & m) << b) that minimises the modelled
+// bank-conflict cycles of the occupancy gathers (each ds_read_u8 is served in two 32-lane groups; a
+// group costs the max number of distinct dwords on one of the 32 banks).  tools/lds_conflict_model.py
+// restates the model.
+struct Swizzle { int a = 0, m = 0, b = 0, Nlds = 0; };
+static Swizzle choose_swizzle(const std::vector<uint16_t> &lidx, const SiteClasses &sc, int N, int Npad, int ROW) {
+    auto model_cost = [&](int a, int m, int b) {
+        double tot = 0;
+        const int nsamp = std::min(N, 48);
+        for (int k = 0; k < nsamp; ++k) {
+            const int s = (int)(((long long)k * 2654435761ll) % N);
+            if (sc.lean_slots(s).empty()) continue;
+            for (int q = 0; q < ROW; ++q)
+                for (int g = 0; g < 2; ++g) {
+                    int cnt[32] = {0};
+                    int seen[32];
+                    int nseen = 0;
+                    for (int ln = 32 * g; ln < 32 * g + 32; ++ln) {
+                        const int x = lidx[((size_t)s * 64 + ln) * ROW + q];
+                        const int dw = (x ^ (((x >> a) & m) << b)) >> 2;
+                        bool dup = false;
+                        for (int z = 0; z < nseen; ++z) dup |= seen[z] == dw;
+                        if (!dup) { seen[nseen++] = dw; cnt[dw & 31]++; }
+                    }
+                    int mx = 0;
+                    for (int z = 0; z < 32; ++z) mx = std::max(mx, cnt[z]);
+                    tot += mx;
+                }
+        }
+        return tot;
+    };
+    Swizzle w;
+    w.Nlds = 16;
+    while (w.Nlds < Npad) w.Nlds <<= 1;
+    double best = model_cost(0, 0, 0);
+    for (int a = 3; a <= 12; ++a)
+        for (int b = 2; b <= 5; ++b)
+            for (int m : {3, 7, 15, 31}) {
+                // bijection on [0, Nlds): source bits [a, a+k) above the destination
+                // bits [b, b+k) and inside the (power-of-two) array
+                const int k = m == 3 ? 2 : (m == 7 ? 3 : (m == 15 ? 4 : 5));
+                if (a < b + k || (1 << (a + k)) > w.Nlds) continue;
+                const double c = model_cost(a, m, b);
+                if (c < best * 0.97) { best = c; w.a = a; w.m = m; w.b = b; }
+            }
+    if (w.m == 0) w.Nlds = Npad; // identity: no power-of-two padding needed
+    return w;
+}
+
+// Delta tables, one per (orbit, self positions): D[(old, new)][b] with the COMPACT base
+// index b = sum_m S^m * species(member m) over the other members of the cluster (S =
+// max species per site), padded to a common [S*S][NTP], NTP = S^MML.  Symmetric
+// clusters give bitwise-equal tables for several self positions: those are shared.
+struct LeanDeltaTables {
+    bool too_large = false;    // more entries than the LDS copy may take: nothing below is complete
+    size_t tlen = 0;           // entries of one table
+    int NTP = 1;
+    // table 0 = zeros, used by padded slots; KF: correlation-function tables (global memory), see LeanParams::dtk
+    std::vector<double> dt, dtk;
+    std::vector<LeanSlot> ls;  // [class][NSL][64]
+    double fast_eps = 0.0;
+};
+// The tables of one slot: the decision table (LDS) and, in KF mode, K correlation-function tables (global memory,
+// read on accepted steps only), tlen entries each
+static std::vector<double> slot_delta_tables(const smolmc_tables *t, const Slot &k, const LeanMode &mode, int NTP, size_t tlen) {
+    const bool corr = t->feature_mode == SMOLMC_FEATURES_CORRELATIONS, folded = mode.corr_kf || mode.corr_lazy;
+    const int o = k.orbit, I = t->orb_nsites[o], Nt = t->orb_tensor_len[o], SMAX = t->max_species;
+    const int32_t *st = t->tensor_indices + t->orb_stride_off[o];
+    const double *T = corr ? t->corr_tensors + t->orb_ctensor_off[o] // K == 1: the one function
+                           : t->interaction_tensors + t->orb_itensor_off[o];
+    const int feat = corr ? t->orb_bit_id[o] : t->orb_id[o];
+    std::vector<double> Efold; // KF / lazy: folded tensor sum_k coef_k ct_k (decision table source)
+    if (folded) {
+        Efold.assign((size_t)Nt, 0.0);
+        for (int kk = 0; kk < t->orb_nfunc[o]; ++kk)
+            for (int i = 0; i < Nt; ++i) Efold[i] += t->ce_coefs[feat + kk] * T[(size_t)kk * Nt + i];
+    }
+    // the site's own positions: their strides add up (one position on an unaliased cell), its site space is
+    // that of the first of them
+    int ss = 0;
+    for (int a = 0; a < I; ++a)
+        if ((k.selfmask >> a) & 1u) ss += st[a];
+    const int Sself = member_species(t, o, k.pfirst);
+    const int ntab = mode.corr_kf ? 1 + t->orb_nfunc[o] : 1;
+    std::vector<double> D((size_t)ntab * tlen, 0.0);
+    int nb = 1;
+    for (int a = 0; a < k.nother; ++a) nb *= SMAX;
+    for (int tb = 0; tb < ntab; ++tb) {
+        const double *Tsrc = mode.corr_lazy ? Efold.data() : !mode.corr_kf ? T : (tb == 0 ? Efold.data() : T + (size_t)(tb - 1) * Nt);
+        double *Dt = D.data() + (size_t)tb * tlen;
+        for (int b = 0; b < nb; ++b) {
+            // decode b into the species of the other members -> tensor base index
+            long base = 0;
+            int rem = b;
+            bool valid = true;
+            for (int a = 0; a < I; ++a) {
+                if ((k.selfmask >> a) & 1u) continue;
+                const int v = rem % SMAX;
+                rem /= SMAX;
+                if (v >= member_species(t, o, a)) valid = false;
+                base += (long)st[a] * v;
+            }
+            if (!valid) continue;
+            for (int oldc = 0; oldc < Sself; ++oldc)
+                for (int newc = 0; newc < Sself; ++newc)
+                    Dt[((size_t)oldc * SMAX + newc) * NTP + b] = Tsrc[base + (long)ss * newc] - Tsrc[base + (long)ss * oldc];
+        }
+    }
+    return D;
+}
+// where the tables D of a slot start in dt: identical tables are shared (KF: decision AND function tables identical)
+static uint32_t place_delta_tables(LeanDeltaTables &L, const std::vector<double> &D, bool kf) {
+    const size_t tlen = L.tlen;
+    for (size_t off = tlen; off + tlen <= L.dt.size(); off += tlen) {
+        if (memcmp(L.dt.data() + off, D.data(), tlen * sizeof(double)) != 0) continue;
+        if (kf) {
+            std::vector<double> want((size_t)SMOLMC_LEAN_MAX_KF * tlen, 0.0);
+            std::copy(D.begin() + tlen, D.end(), want.begin());
+            if (memcmp(L.dtk.data() + off * SMOLMC_LEAN_MAX_KF, want.data(), want.size() * sizeof(double)) != 0) continue;
+        }
+        return (uint32_t)off;
+    }
+    const uint32_t at = (uint32_t)L.dt.size();
+    L.dt.insert(L.dt.end(), D.begin(), D.begin() + tlen);
+    if (kf) {
+        L.dtk.resize(L.dt.size() * SMOLMC_LEAN_MAX_KF, 0.0);
+        std::copy(D.begin() + tlen, D.end(), L.dtk.begin() + (size_t)at * SMOLMC_LEAN_MAX_KF);
+    }
+    return at;
+}
+static LeanDeltaTables lean_delta_tables(const smolmc_tables *t, const SiteClasses &sc, const LeanMode &mode, int NSL, int MML) {
+    const bool corr = t->feature_mode == SMOLMC_FEATURES_CORRELATIONS, folded = mode.corr_kf || mode.corr_lazy;
+    const int SMAX = t->max_species, NCLS = (int)sc.class_rep.size();
+    LeanDeltaTables L;
+    for (int m = 0; m < MML; ++m) L.NTP *= SMAX;
+    // the stride between tables is padded so that it is not a multiple of the 64-dword LDS
+    // bank period (lanes of one wave read the same (pair, base) entry of DIFFERENT tables)
+    L.tlen = (size_t)SMAX * SMAX * L.NTP;
+    if ((L.tlen & 1) == 0) L.tlen += 1;
+    L.dt.assign(L.tlen, 0.0);
+    // Entries the LDS copy of the tables may take.  8000 (64 KB, two workgroups per CU) until round 6; models between
+    // that and what one workgroup's LDS holds beside the walkers' state (the layouts below decide) ran on mc_kernel
+    // with the tables in L2: measured on five quaternary triplet / quadruplet models of the fuzz campaign at 2048
+    // walkers, 0.39-1.05e9 steps/s there against 0.99-2.43e9 here (tools/time_fuzz_case.py).
+    constexpr size_t dt_max = 18000;
+    L.ls.resize((size_t)NCLS * NSL * 64);
+    memset(L.ls.data(), 0, L.ls.size() * sizeof(LeanSlot));
+    std::map<std::pair<int, int>, uint32_t> doff_of;
+    double sum_abs_max = 0.0;
+    for (int cls = 0; cls < NCLS; ++cls) {
+        const std::vector<Slot> &sl = sc.lean_slots(sc.class_rep[cls]);
+        double sum_abs = 0.0;
+        for (size_t q = 0; q < sl.size(); ++q) {
+            const Slot &k = sl[q];
+            const int feat = corr ? t->orb_bit_id[k.orbit] : t->orb_id[k.orbit];
+            const auto key = std::make_pair(k.orbit, (int)k.selfmask);
+            if (!doff_of.count(key)) doff_of[key] = place_delta_tables(L, slot_delta_tables(t, k, mode, L.NTP, L.tlen), mode.corr_kf);
+            if (L.dt.size() > dt_max) { L.too_large = true; return L; } // keep the LDS tables within budget
+            const double scale = slot_scale(t, k.rec);
+            LeanSlot &S = L.ls[((size_t)cls * NSL + q / 64) * 64 + (q % 64)];
+            S.doff8 = doff_of[key] * 8u;
+            uint32_t cs = 8u;
+            for (int m = 0; m < k.nother; ++m, cs *= (uint32_t)SMAX) S.stride8[m] = cs;
+            S.feat = mode.lazy() ? 0u : (uint32_t)feat; // (lazy: the kernels' feature cells are never read)
+            S.live = mode.corr_kf ? (uint32_t)t->orb_nfunc[k.orbit] : 1u;
+            S.w = folded ? scale : t->ce_coefs[feat] * scale; // (KF / lazy: the coefficients are folded into the table)
+            S.fs = scale;
+            double dmax = 0.0;
+            const double *D = L.dt.data() + doff_of[key];
+            for (size_t z = 0; z < L.tlen; ++z) dmax = std::max(dmax, std::fabs(D[z]));
+            sum_abs += std::fabs(S.w) * dmax;
+        }
+        sum_abs_max = std::max(sum_abs_max, sum_abs);
+    }
+    // float32 pre-test of the accept decision: a step sums at most two flips' worth of
+    // |w * d| over the slots, a float32 conversion + 6-level tree adds at most
+    // 7 * 2^-24 of that; 2^-19 leaves a 4.5x margin.
+    L.fast_eps = 2.0 * sum_abs_max * ldexp(1.0, -19);
+    return L;
+}
+
+// The lean tables are taken: the one place that writes them to the handle and the device
+static int commit_lean_tables(smolmc_handle *h, const smolmc_tables *t, const SiteClasses &sc, const LeanMode &mode, int NSL, int MML,
+                              const Swizzle &w, std::vector<uint16_t> &lidx, const LeanDeltaTables &L) {
+    LeanParams &lp = h->lp;
+    memset(&lp, 0, sizeof(LeanParams));
+    lp.swz_a = w.a; lp.swz_m = w.m; lp.swz_b = w.b; lp.Nlds = w.Nlds;
+    lp.fast_eps = L.fast_eps;
+    lp.ktab8 = (uint32_t)L.tlen * 8u;
+    lp.nt8 = (uint32_t)L.NTP * 8u;
+    lp.snt8 = (uint32_t)L.NTP * 8u * (uint32_t)t->max_species;
+    TRY(dev_upload(h, lidx.data(), lidx.size(), &lp.idx));
+    h->lean_idx_host = std::move(lidx);
+    TRY(dev_upload(h, L.dt.data(), L.dt.size(), &lp.dt));
+    if (mode.corr_kf) TRY(dev_upload(h, L.dtk.data(), L.dtk.size(), &lp.dtk));
+    TRY(dev_upload(h, L.ls.data(), L.ls.size(), &lp.slots));
+    lp.dt_len = (int)L.dt.size();
+    h->lean_kf = mode.corr_kf ? SMOLMC_LEAN_MAX_KF : 0;
+    h->lazy_tables = mode.lazy();
+    h->lean_tables = true;
+    h->lean_nslot = NSL; h->lean_mm = MML; h->lean_ncls = (int)sc.class_rep.size();
+    h->site_class_host = sc.site_class;
     return 0;
+}
+
+static int build_mc_tables(smolmc_handle *h, const smolmc_tables *t) {
+    const GeneralLimits lim = general_limits(t, h->Npad);
+    if (lim.error) return fail(lim.error);
+    if (lim.universal) return no_general(h, lim.universal);
+    const SiteClasses sc = site_classes(t, lim);
+    if (sc.universal) return no_general(h, sc.universal);
+    TRY(general_tables(h, t, lim, sc));
+    if (!h->general_ok) return 0;
+    // the lean tables are built exactly when nothing speaks against them
+    const LeanMode mode = lean_mode(h, t, lim, sc);
+    const char *why_not = mode.reason;
+    const int NSL = sc.niter_max <= 2 ? 2 : (sc.niter_max <= 4 ? 4 : 8), MML = sc.lean_need_mm <= 2 ? 2 : 3;
+    std::vector<uint16_t> lidx;
+    Swizzle w;
+    LeanDeltaTables L;
+    if (!*why_not) {
+        lidx = lean_index_rows(t, sc, NSL, MML);
+        w = choose_swizzle(lidx, sc, t->num_sites, h->Npad, NSL * MML);
+        for (uint16_t &x : lidx) x = (uint16_t)(x ^ (((x >> w.a) & w.m) << w.b));
+        L = lean_delta_tables(t, sc, mode, NSL, MML);
+        if (L.too_large) why_not = "delta tables beyond 18000 entries (species^(cluster size - 1) x species^2 per distinct table)";
+    }
+    h->lean_reason = why_not;
+    return *why_not ? 0 : commit_lean_tables(h, t, sc, mode, NSL, MML, w, lidx, L);
 }
 
 // Bounds checks of every gather index the kernels will use, done once at create (the
@@ -820,7 +859,7 @@ static int validate_tables(const smolmc_tables *t) {
             const int st = t->tensor_indices[t->orb_stride_off[o] + m];
             if (st <= 0) return fail("tensor stride must be positive");
             if (st > prev || prev % st != 0) return fail("tensor strides do not describe a row-major tensor");
-            reach += (prev / st - 1) * st;
+            reach += (long long)(member_species(t, o, m) - 1) * st;
             prev = st;
         }
         if (reach >= t->orb_tensor_len[o]) return fail("tensor strides reach beyond their tensor");
@@ -1049,16 +1088,13 @@ static int build_compact_ewald(smolmc_handle *h, const smolmc_tables *t) {
     // split sites into changeable ones and single-species ("frozen") ones
     std::vector<int> act;
     std::vector<char> frozen(N, 0);
+    std::vector<char> in_active(N, 0);
+    for (int64_t i = 0; i < t->sub_site_ptr[t->n_sublattices]; ++i)
+        if (t->sub_active_sites[i] >= 0 && t->sub_active_sites[i] < N) in_active[t->sub_active_sites[i]] = 1;
     for (int s = 0; s < N; ++s) {
-        int nvalid = 0, ncodes = 0;
-        for (int c = 0; c < W; ++c) nvalid += t->ewald_inds[(size_t)s * W + c] >= 0;
-        (void)ncodes;
         // a site is frozen when it is in no active sublattice (its code never changes) and
         // carries exactly one Ewald species (code 0)
-        bool in_active = false;
-        for (int64_t i = 0; i < t->sub_site_ptr[t->n_sublattices] && !in_active; ++i)
-            in_active = t->sub_active_sites[i] == s;
-        frozen[s] = (!in_active && nvalid == 1 && t->ewald_inds[(size_t)s * W] >= 0) ? 1 : 0;
+        frozen[s] = (!in_active[s] && single_ewald_species(t, s)) ? 1 : 0;
         if (!frozen[s]) act.push_back(s);
     }
     const size_t na = act.size();
@@ -1129,12 +1165,7 @@ static std::vector<int32_t> plan_relabelling(const smolmc_tables *t) {
     if (!needed) return none;
     // sites outside the active lists: changeable ones (more than one Ewald species, or a vacancy: what
     // build_compact_ewald does not fold into the frozen-site constants) before the single-species ones
-    auto frozen = [&](int s) {
-        if (!t->has_ewald || !t->ewald_inds) return true;
-        int nvalid = 0;
-        for (int c = 0; c < t->ewald_width; ++c) nvalid += t->ewald_inds[(size_t)s * t->ewald_width + c] >= 0;
-        return nvalid == 1 && t->ewald_inds[(size_t)s * t->ewald_width] >= 0;
-    };
+    auto frozen = [&](int s) { return !t->has_ewald || !t->ewald_inds || single_ewald_species(t, s); };
     for (int pass = 0; pass < 2; ++pass)
         for (int s = 0; s < N; ++s)
             if (!taken[s] && frozen(s) == (pass == 1)) order.push_back(s);
@@ -1241,8 +1272,6 @@ extern "C" int smolmc_create(const smolmc_tables *t, const smolmc_config *cfg, s
 
 // ---- smolmc_create stage by stage.  Every stage returns 0 or the code of its fail(); create_impl lists them in
 // order and destroys the handle when one refuses.
-static bool is_wl(const smolmc_handle *h) { return h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU; }
-static bool is_table(const smolmc_handle *h) { return h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP; }
 // Wang-Landau keeps per-bin feature sums at update_period 1, running means otherwise
 static int wl_sum_mode_of(const smolmc_handle *h) { return (h->cfg.wl_update_period == 1 && !smolmc_env(ENV_WL_RUNNING_MEAN)) ? 1 : 0; }
 static int cu_count(const smolmc_handle *h) {
@@ -1303,10 +1332,8 @@ static int create_site_codes(smolmc_handle *h, const smolmc_tables *t) {
     std::vector<int> seen((size_t)t->num_sites, 0);
     for (int o = 0; o < t->n_orb; ++o) {
         const int I = t->orb_nsites[o];
-        const int32_t *st = t->tensor_indices + t->orb_stride_off[o];
         for (int64_t i = t->full_off[o]; i < t->full_off[o + 1]; ++i) {
-            const int m = (int)((i - t->full_off[o]) % I);
-            const int width = (int)((m == 0 ? t->orb_tensor_len[o] : st[m - 1]) / st[m]);
+            const int width = member_species(t, o, (int)((i - t->full_off[o]) % I));
             const int site = t->full_idx[i];
             seen[site] = seen[site] ? std::min(seen[site], width) : width;
         }
@@ -1616,7 +1643,7 @@ struct LeanPlan {
 static LeanPlan decide_lean(const smolmc_handle *h, const smolmc_tables *t) {
     const smolmc_config *cfg = &h->cfg;
     const KParams &kp = h->kp;
-    const LeanParams &lp = h->lp; // (build_mc_tables has left the table sizes there)
+    const LeanParams &lp = h->lp; // (commit_lean_tables has left the table sizes there)
     const bool wl = is_wl(h), table = is_table(h);
     const int wl_sum_mode = wl_sum_mode_of(h), Fk = lean_features(h, t), brows = kp.bias_rows;
     LeanPlan p;
@@ -1763,7 +1790,7 @@ struct LeanMultiPlan {
 static LeanMultiPlan decide_lean_multi(const smolmc_handle *h, const smolmc_tables *t) {
     const smolmc_config *cfg = &h->cfg;
     const KParams &kp = h->kp;
-    const LeanParams &lp = h->lp; // (build_mc_tables has left the table sizes there)
+    const LeanParams &lp = h->lp; // (commit_lean_tables has left the table sizes there)
     const bool wl = is_wl(h), table = is_table(h);
     const int wl_sum_mode = wl_sum_mode_of(h), Fk = lean_features(h, t), brows = kp.bias_rows;
     LeanMultiPlan p;
@@ -1947,7 +1974,7 @@ static int univ_pack_records(smolmc_handle *h, const smolmc_tables *t) {
         u.feat = cm ? t->orb_bit_id[o] : t->orb_id[o];
         u.idx_off = t->loc_off[r];
         u.t_off = cm ? t->orb_ctensor_off[o] : t->orb_itensor_off[o];
-        u.scale = (double)t->size / t->loc_ratio[r] / (double)t->loc_nrows[r];
+        u.scale = slot_scale(t, r);
         u.ratio = t->loc_ratio[r];
     }
     if (dev_upload(h, recs.data(), recs.size(), &up.recs)) return 1;
@@ -2240,7 +2267,7 @@ static int launch_eval_full(smolmc_handle *h, const uint8_t *d_occ8, int nocc, d
     return 0;
 }
 
-// ---- lazy cluster features (build_mc_tables) ---------------------------------------------------------------
+// ---- lazy cluster features (lean_mode) ---------------------------------------------------------------------
 // The lean kernels of such a handle carry the scalar features only (d_lazy_scal, row stride nscal); the cluster
 // part of kp.features is evaluated from the occupancies where it is read.
 static bool is_lazy(const smolmc_handle *h) { return h->lazy_tables && h->lean(); }

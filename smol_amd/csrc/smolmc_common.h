@@ -792,7 +792,7 @@ struct smolmc_handle {
     UParams up;
     bool general_ok = true;      // mc_kernel can run this model (else: why not)
     std::string general_reason;
-    // lazy cluster features (engine.hip, build_mc_tables): the lean kernels of this handle carry the scalar features
+    // lazy cluster features (engine.hip, lean_mode): the lean kernels of this handle carry the scalar features
     // only (d_lazy_scal [R][2]: Ewald energy, chemical work); the cluster part of kp.features is evaluated from the
     // occupancies when it is read
     bool lazy_tables = false, lazy = false, ce_dirty = false;

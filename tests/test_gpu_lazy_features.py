@@ -1,4 +1,4 @@
-"""Lazy cluster features (engine.hip, build_mc_tables): Metropolis kernels of the lean families take
+"""Lazy cluster features (engine.hip, lean_mode): Metropolis kernels of the lean families take
 a correlation-mode model with several functions per orbit -- the reference's default ClusterExpansionProcessor on
 any site space of three or more species (evaluator.pyx:211-265) -- as an interaction-mode model of the folded
 tensors and evaluate the cluster features from the occupancy where they are read.  Against the oracle on

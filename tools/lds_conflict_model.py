@@ -4,7 +4,8 @@
 For a site s, the wave issues NSLOT*MM ds_read_u8 instructions; instruction (it, m) reads,
 in lane l, the byte of member m of the lane's slot it.  A ds_read_u8/b32 is serviced in two
 32-lane groups; each group costs max over the 32 banks of the number of DISTINCT dwords
-requested on that bank.  This script evaluates candidate site->LDS-address permutations."""
+requested on that bank.  This script evaluates candidate site->LDS-address permutations; the engine's own copy of
+the model is choose_swizzle in smol_amd/csrc/engine.hip."""
 import sys, os
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,7 +13,7 @@ from smol_amd import synth
 
 
 def lean_rows(sc):
-    """[N][64][NSLOT][MM] member sites in the kernel's slot order (mirrors build_mc_tables)."""
+    """[N][64][NSLOT][MM] member sites in the kernel's slot order (mirrors site_slots / lean_index_rows of engine.hip)."""
     loc = sc.local_tables()
     N = sc.num_sites
     rows_all = None
