@@ -785,44 +785,21 @@ __global__ void __launch_bounds__(256, (NSLOT <= 4 ? 4 : 2)) mc_kernel(const KPa
 #undef acc_by_slot
 #undef bias_type
 
-// ---- kernel dispatch ----------------------------------------------------------
-template <typename IdxT, int NSLOT, int MM, bool GENERIC, bool WL>
-static int launch_mc_inst(smolmc_handle *h, const KParams &kp, int replay) {
-    auto kern = mc_kernel<IdxT, NSLOT, MM, GENERIC, WL>;
-    if (h->lds_bytes > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h->lds_bytes));
-    const int wpb = h->waves_per_block;
-    const unsigned grid = (unsigned)((h->R + wpb - 1) / wpb);
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), h->lds_bytes, h->stream, kp, replay);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
-}
-
-template <typename IdxT, int NSLOT, bool GENERIC, bool WL>
-static int launch_mc_mm(smolmc_handle *h, const KParams &kp, int replay) {
-    if (GENERIC) {
-        if (h->mm == 3) return launch_mc_inst<IdxT, NSLOT, 3, GENERIC, WL>(h, kp, replay);
-        return launch_mc_inst<IdxT, NSLOT, 6, GENERIC, WL>(h, kp, replay);
-    }
-    if (h->mm == 2) return launch_mc_inst<IdxT, NSLOT, 2, GENERIC, WL>(h, kp, replay);
-    if (h->mm == 3) return launch_mc_inst<IdxT, NSLOT, 3, GENERIC, WL>(h, kp, replay);
-    return launch_mc_inst<IdxT, NSLOT, 5, GENERIC, WL>(h, kp, replay);
-}
-
-
-// all (index type, GENERIC, WL) combinations of one NSLOT
+// ---- kernel dispatch (launch.h) -------------------------------------------------
+// mc_kernel's template arguments after NSLOT and MM, as the flags of a variant word (GV_IDX16: uint16_t indices)
+enum : unsigned { GV_WL = 1, GV_GENERIC = 2, GV_IDX16 = 4 };
+// all (index type, GENERIC, WL) combinations of one NSLOT, then MM; both lists in code-object order (launch.h)
 template <int NSLOT> static int launch_general_nslot(smolmc_handle *h, const KParams &kp, int replay) {
-    const bool wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
-    if (h->generic)
-        return wl ? launch_mc_mm<int32_t, NSLOT, true, true>(h, kp, replay)
-                  : launch_mc_mm<int32_t, NSLOT, true, false>(h, kp, replay);
-    if (h->idx16)
-        return wl ? launch_mc_mm<uint16_t, NSLOT, false, true>(h, kp, replay)
-                  : launch_mc_mm<uint16_t, NSLOT, false, false>(h, kp, replay);
-    return wl ? launch_mc_mm<int32_t, NSLOT, false, true>(h, kp, replay)
-              : launch_mc_mm<int32_t, NSLOT, false, false>(h, kp, replay);
+    const int wpb = h->waves_per_block;
+    const dim3 grid((unsigned)((h->R + wpb - 1) / wpb)), block(64 * wpb);
+    const unsigned key = (h->generic ? GV_GENERIC : h->idx16 ? GV_IDX16 : 0) | (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU ? GV_WL : 0);
+    // (every combination has all four MM instantiated, though GENERIC runs 3 or 6 and the others 2, 3 or 5: the
+    // rest are never dispatched, and stay while the code object's other kernels must not move)
+    const int mm = h->generic ? (h->mm == 3 ? 3 : 6) : (h->mm == 2 || h->mm == 3 ? h->mm : 5);
+    return first_match<GV_GENERIC | GV_WL, GV_GENERIC, GV_IDX16 | GV_WL, GV_IDX16, GV_WL, 0u>(key, [&](auto v) {
+        return first_match<3, 6, 2, 5>(mm, [&](auto mm_c) {
+            using IdxT = std::conditional_t<bool(v & GV_IDX16), uint16_t, int32_t>;
+            return launch_timed(h, mc_kernel<IdxT, NSLOT, mm_c, bool(v & GV_GENERIC), bool(v & GV_WL)>, grid, block, h->lds_bytes, kp, replay);
+        });
+    });
 }

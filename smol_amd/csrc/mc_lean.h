@@ -2368,176 +2368,89 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
 
 #undef key0
 #undef key1
-template <int NSLOT, int MM, int STEP, bool MU, int EW, bool WL, bool BIAS = false, bool SOLO = false, int KF = 0,
-          int OCC = 0, bool REPLAY = false>
-static int launch_lean_inst(smolmc_handle *h, const LeanParams &lp) {
-    const unsigned grid = SOLO ? (unsigned)h->R : (unsigned)((h->R + 3) / 4);
-    auto kern = mc_lean_kernel<NSLOT, MM, STEP, MU, EW, WL, BIAS, SOLO, KF, OCC, REPLAY>;
-    if (h->lean_lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h->lean_lds));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SOLO ? 64 : 256), h->lean_lds, h->stream, lp);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+// ---- kernel dispatch (launch.h) -------------------------------------------------
+// mc_lean_kernel's template arguments after NSLOT, MM, STEP, as the flags of a variant word
+enum : unsigned {
+    LV_EW = 3, // (the Ewald mode itself: 0 absent, 1 the field in LDS, 2 in HBM)
+    LV_MU = 4, LV_WL = 8, LV_BIAS = 16, LV_SOLO = 32, LV_KF = 64 /* KF = SMOLMC_LEAN_MAX_KF */, LV_OCC6 = 128, LV_REPLAY = 256
+};
+template <int NSLOT, int MM, int STEP, unsigned V> static auto lean_variant() {
+    return mc_lean_kernel<NSLOT, MM, STEP, bool(V & LV_MU), int(V & LV_EW), bool(V & LV_WL), bool(V & LV_BIAS), bool(V & LV_SOLO),
+                          (V & LV_KF) ? SMOLMC_LEAN_MAX_KF : 0, (V & LV_OCC6) ? 6 : 0, bool(V & LV_REPLAY)>;
 }
-template <int NSLOT, int MM, int STEP>
-static int launch_lean_me(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.mu_row != nullptr, ew = lp.ew_G != nullptr;
-    // (round 2's Wang-Landau variant of this kernel: no longer dispatched, Wang-Landau runs on mc_wl_kernel.
-    // Its instantiations stay until the PMC entries of profiles/pmc_constants.json are re-stamped: without
-    // them every other kernel of lean_n{2,4}.hip moves in the code object, which changes its digest.)
-    if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU)
-        return launch_lean_inst<NSLOT, MM, STEP, false, 0, true>(h, lp);
-    if (ew)
-        return mu ? (lp.ew_field ? launch_lean_inst<NSLOT, MM, STEP, true, 2, false>(h, lp) : launch_lean_inst<NSLOT, MM, STEP, true, 1, false>(h, lp))
-                  : (lp.ew_field ? launch_lean_inst<NSLOT, MM, STEP, false, 2, false>(h, lp) : launch_lean_inst<NSLOT, MM, STEP, false, 1, false>(h, lp));
-    if (h->lean_solo && h->lean_occ == 6)
-        return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 0, false, false, true, 0, 6>(h, lp)
-                  : launch_lean_inst<NSLOT, MM, STEP, false, 0, false, false, true, 0, 6>(h, lp);
-    if (h->lean_solo) // Metropolis without Ewald: one wave per workgroup (see mc_lean_kernel)
-        return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 0, false, false, true>(h, lp)
-                  : launch_lean_inst<NSLOT, MM, STEP, false, 0, false, false, true>(h, lp);
-    return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 0, false>(h, lp)
-              : launch_lean_inst<NSLOT, MM, STEP, false, 0, false>(h, lp);
+// the runtime key of a lean handle: chemical potentials, Ewald mode, and -- where the family has them (SOLO) --
+// the one-wave-per-workgroup layouts, which only exist without Ewald
+static unsigned lean_key(const smolmc_handle *h, const LeanParams &lp, bool solo_variants) {
+    const unsigned mu = lp.mu_row != nullptr ? LV_MU : 0;
+    if (lp.ew_G != nullptr) return mu | (lp.ew_field ? 2u : 1u);
+    if (!solo_variants || !h->lean_solo) return mu;
+    return mu | LV_SOLO | (h->lean_occ == 6 ? LV_OCC6 : 0);
 }
-template <int NSLOT, int MM>
-static int launch_lean_nm(smolmc_handle *h, const LeanParams &lp) {
-    if (h->cfg.step_type == SMOLMC_STEP_SWAP) return launch_lean_me<NSLOT, MM, SMOLMC_STEP_SWAP>(h, lp);
-    return launch_lean_me<NSLOT, MM, SMOLMC_STEP_FLIP>(h, lp);
+// the variant of Vs (in code-object order, see launch.h) that key names
+template <int NSLOT, int MM, int STEP, unsigned... Vs>
+static int launch_lean_variant(smolmc_handle *h, const LeanParams &lp, unsigned key) {
+    return first_match<Vs...>(key, [&](auto v) {
+        constexpr bool SOLO = v & LV_SOLO; // (Metropolis without Ewald: one wave per workgroup, see mc_lean_kernel)
+        return launch_timed(h, lean_variant<NSLOT, MM, STEP, v>(), dim3(SOLO ? (unsigned)h->R : (unsigned)((h->R + 3) / 4)),
+                            dim3(SOLO ? 64 : 256), h->lean_lds, lp);
+    });
 }
-template <int NSLOT, int MM, int EWM, bool REPLAY = false, bool BIAS = false, bool WLT = false>
-static int launch_table_ewm(smolmc_handle *h, const LeanParams &lp) {
+// the families whose variants are (mu, Ewald mode) alone; B: the flags the family fixes
+template <int NSLOT, unsigned B> static int launch_lean_mu_ew(smolmc_handle *h, const LeanParams &lp) {
+    return with_mm_step(h, [&](auto mm, auto step) {
+        return launch_lean_variant<NSLOT, mm, step, B | LV_MU | 2, B | LV_MU | 1, B | 2, B | 1, B | LV_MU, B>(h, lp, B | lean_key(h, lp, false));
+    });
+}
+// (instantiated in lean_bias_n*.hip, lean_bias_replay_n*.hip, lean_corr_n*.hip only)
+template <int NSLOT> static int launch_lean_bias_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_lean_mu_ew<NSLOT, LV_BIAS>(h, lp); }
+template <int NSLOT> static int launch_lean_bias_replay_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_lean_mu_ew<NSLOT, LV_BIAS | LV_REPLAY>(h, lp); }
+template <int NSLOT> static int launch_lean_corr_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_lean_mu_ew<NSLOT, LV_KF>(h, lp); }
+
+// mc_table_kernel's template arguments after NSLOT, MM and the Ewald mode (shared with mc_table_multi_kernel)
+enum : unsigned { TV_REPLAY = 1, TV_BIAS = 2, TV_WL = 4 };
+// (T = 0 in lean_n*.hip; TV_WL, TV_BIAS, TV_REPLAY in table_wl_n*.hip, table_bias_n*.hip, table_replay_n*.hip only)
+template <int NSLOT, unsigned T> static int launch_table_nslot(smolmc_handle *h, const LeanParams &lp) {
     const int wpb = h->lean_wpb;
     const size_t lds = wpb == 8 ? h->lean_lds_wpb8 : h->lean_lds;
-    const unsigned grid = (unsigned)((h->R + wpb - 1) / wpb);
-    auto kern = mc_table_kernel<NSLOT, MM, EWM, REPLAY, BIAS, WLT>;
-    if (lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), lds, h->stream, lp);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+    const dim3 grid((unsigned)((h->R + wpb - 1) / wpb)), block(64 * wpb);
+    const int ewm = lp.ew_G == nullptr ? 0 : ((T & TV_WL) || lp.ew_field) ? 2 : 1; // (Wang-Landau: the Ewald term from the field only)
+    return first_match<2, 3>(h->lean_mm, [&](auto mm) {
+        auto launch = [&](auto ew) {
+            return launch_timed(h, mc_table_kernel<NSLOT, mm, ew, bool(T & TV_REPLAY), bool(T & TV_BIAS), bool(T & TV_WL)>, grid, block, lds, lp);
+        };
+        if constexpr (T & TV_WL) return first_match<0, 2>(ewm, launch);
+        else return first_match<0, 2, 1>(ewm, launch);
+    });
 }
-
-
-template <int NSLOT, int MM, bool REPLAY = false, bool BIAS = false, bool WLT = false>
-static int launch_table_inst(smolmc_handle *h, const LeanParams &lp) {
-    if (lp.ew_G == nullptr) return launch_table_ewm<NSLOT, MM, 0, REPLAY, BIAS, WLT>(h, lp);
-    if constexpr (WLT) return launch_table_ewm<NSLOT, MM, 2, REPLAY, BIAS, WLT>(h, lp); // (Wang-Landau: the Ewald term from the field only)
-    else return lp.ew_field ? launch_table_ewm<NSLOT, MM, 2, REPLAY, BIAS>(h, lp) : launch_table_ewm<NSLOT, MM, 1, REPLAY, BIAS>(h, lp);
-}
-// (instantiated in table_wl_n*.hip only)
-template <int NSLOT> static int launch_table_wl_nslot(smolmc_handle *h, const LeanParams &lp) {
-    return h->lean_mm == 2 ? launch_table_inst<NSLOT, 2, false, false, true>(h, lp) : launch_table_inst<NSLOT, 3, false, false, true>(h, lp);
-}
-// (instantiated in table_bias_n*.hip only)
-template <int NSLOT> static int launch_table_bias_nslot(smolmc_handle *h, const LeanParams &lp) {
-    return h->lean_mm == 2 ? launch_table_inst<NSLOT, 2, false, true>(h, lp) : launch_table_inst<NSLOT, 3, false, true>(h, lp);
-}
-// (instantiated in table_replay_n*.hip only)
-template <int NSLOT> static int launch_table_replay_nslot(smolmc_handle *h, const LeanParams &lp) {
-    return h->lean_mm == 2 ? launch_table_inst<NSLOT, 2, true>(h, lp) : launch_table_inst<NSLOT, 3, true>(h, lp);
-}
-
-// biased Metropolis variants (instantiated in lean_bias_n*.hip only)
-template <int NSLOT, int MM, int STEP>
-static int launch_lean_bias_me(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.mu_row != nullptr, ew = lp.ew_G != nullptr;
-    if (ew)
-        return mu ? (lp.ew_field ? launch_lean_inst<NSLOT, MM, STEP, true, 2, false, true>(h, lp) : launch_lean_inst<NSLOT, MM, STEP, true, 1, false, true>(h, lp))
-                  : (lp.ew_field ? launch_lean_inst<NSLOT, MM, STEP, false, 2, false, true>(h, lp) : launch_lean_inst<NSLOT, MM, STEP, false, 1, false, true>(h, lp));
-    return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 0, false, true>(h, lp)
-              : launch_lean_inst<NSLOT, MM, STEP, false, 0, false, true>(h, lp);
-}
-template <int NSLOT> static int launch_lean_bias_nslot(smolmc_handle *h, const LeanParams &lp) {
-    const bool swap = h->cfg.step_type == SMOLMC_STEP_SWAP;
-    if (h->lean_mm == 2)
-        return swap ? launch_lean_bias_me<NSLOT, 2, SMOLMC_STEP_SWAP>(h, lp)
-                    : launch_lean_bias_me<NSLOT, 2, SMOLMC_STEP_FLIP>(h, lp);
-    return swap ? launch_lean_bias_me<NSLOT, 3, SMOLMC_STEP_SWAP>(h, lp)
-                : launch_lean_bias_me<NSLOT, 3, SMOLMC_STEP_FLIP>(h, lp);
-}
-
-// biased replay variants (instantiated in lean_bias_replay_n*.hip only)
-template <int NSLOT, int MM, int STEP>
-static int launch_lean_bias_replay_me(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.mu_row != nullptr, ew = lp.ew_G != nullptr;
-    if (ew)
-        return mu ? (lp.ew_field ? launch_lean_inst<NSLOT, MM, STEP, true, 2, false, true, false, 0, 0, true>(h, lp) : launch_lean_inst<NSLOT, MM, STEP, true, 1, false, true, false, 0, 0, true>(h, lp))
-                  : (lp.ew_field ? launch_lean_inst<NSLOT, MM, STEP, false, 2, false, true, false, 0, 0, true>(h, lp) : launch_lean_inst<NSLOT, MM, STEP, false, 1, false, true, false, 0, 0, true>(h, lp));
-    return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 0, false, true, false, 0, 0, true>(h, lp)
-              : launch_lean_inst<NSLOT, MM, STEP, false, 0, false, true, false, 0, 0, true>(h, lp);
-}
-template <int NSLOT> static int launch_lean_bias_replay_nslot(smolmc_handle *h, const LeanParams &lp) {
-    const bool swap = h->cfg.step_type == SMOLMC_STEP_SWAP;
-    if (h->lean_mm == 2)
-        return swap ? launch_lean_bias_replay_me<NSLOT, 2, SMOLMC_STEP_SWAP>(h, lp)
-                    : launch_lean_bias_replay_me<NSLOT, 2, SMOLMC_STEP_FLIP>(h, lp);
-    return swap ? launch_lean_bias_replay_me<NSLOT, 3, SMOLMC_STEP_SWAP>(h, lp)
-                : launch_lean_bias_replay_me<NSLOT, 3, SMOLMC_STEP_FLIP>(h, lp);
-}
-
-// correlation features with several functions per orbit (instantiated in lean_corr_n*.hip only)
-template <int NSLOT, int MM, int STEP>
-static int launch_lean_corr_me(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.mu_row != nullptr, ew = lp.ew_G != nullptr;
-    constexpr int KF = SMOLMC_LEAN_MAX_KF;
-    if (ew)
-        return mu ? (lp.ew_field ? launch_lean_inst<NSLOT, MM, STEP, true, 2, false, false, false, KF>(h, lp) : launch_lean_inst<NSLOT, MM, STEP, true, 1, false, false, false, KF>(h, lp))
-                  : (lp.ew_field ? launch_lean_inst<NSLOT, MM, STEP, false, 2, false, false, false, KF>(h, lp) : launch_lean_inst<NSLOT, MM, STEP, false, 1, false, false, false, KF>(h, lp));
-    return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 0, false, false, false, KF>(h, lp)
-              : launch_lean_inst<NSLOT, MM, STEP, false, 0, false, false, false, KF>(h, lp);
-}
-template <int NSLOT> static int launch_lean_corr_nslot(smolmc_handle *h, const LeanParams &lp) {
-    const bool swap = h->cfg.step_type == SMOLMC_STEP_SWAP;
-    if (h->lean_mm == 2)
-        return swap ? launch_lean_corr_me<NSLOT, 2, SMOLMC_STEP_SWAP>(h, lp)
-                    : launch_lean_corr_me<NSLOT, 2, SMOLMC_STEP_FLIP>(h, lp);
-    return swap ? launch_lean_corr_me<NSLOT, 3, SMOLMC_STEP_SWAP>(h, lp)
-                : launch_lean_corr_me<NSLOT, 3, SMOLMC_STEP_FLIP>(h, lp);
-}
+template <int NSLOT> static int launch_table_wl_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_nslot<NSLOT, TV_WL>(h, lp); }
+template <int NSLOT> static int launch_table_bias_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_nslot<NSLOT, TV_BIAS>(h, lp); }
+template <int NSLOT> static int launch_table_replay_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_nslot<NSLOT, TV_REPLAY>(h, lp); }
 
 template <int NSLOT> static int launch_lean_nslot(smolmc_handle *h, const LeanParams &lp) {
-    if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP)
-        return h->lean_mm == 2 ? launch_table_inst<NSLOT, 2>(h, lp) : launch_table_inst<NSLOT, 3>(h, lp);
-    return h->lean_mm == 2 ? launch_lean_nm<NSLOT, 2>(h, lp) : launch_lean_nm<NSLOT, 3>(h, lp);
+    if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) return launch_table_nslot<NSLOT, 0>(h, lp);
+    // (LV_WL, round 2's Wang-Landau variant of this kernel: no longer dispatched, Wang-Landau runs on mc_wl_kernel.
+    // Its instantiations stay until the PMC entries of profiles/pmc_constants.json are re-stamped: without
+    // them every other kernel of lean_n{2,4}.hip moves in the code object, which changes its digest.)
+    const unsigned key = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU ? (unsigned)LV_WL : lean_key(h, lp, true);
+    return with_mm_step(h, [&](auto mm, auto step) {
+        return launch_lean_variant<NSLOT, mm, step, LV_WL, LV_MU | 2, LV_MU | 1, 2, 1, LV_MU | LV_SOLO | LV_OCC6, LV_SOLO | LV_OCC6,
+                                   LV_MU | LV_SOLO, LV_SOLO, LV_MU, 0>(h, lp, key);
+    });
 }
 
 // replay variants (instantiated in lean_replay_n*.hip only): the handle's own layout (SOLO or four
 // walkers per workgroup), Ewald mode and mu row; correlation features with several functions per
-// orbit take the KF variant
-template <int NSLOT, int MM, int STEP, int KF>
-static int launch_lean_replay_me(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.mu_row != nullptr, ew = lp.ew_G != nullptr;
-    if (ew) {
-        if (lp.ew_field)
-            return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 2, false, false, false, KF, 0, true>(h, lp)
-                      : launch_lean_inst<NSLOT, MM, STEP, false, 2, false, false, false, KF, 0, true>(h, lp);
-        return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 1, false, false, false, KF, 0, true>(h, lp)
-                  : launch_lean_inst<NSLOT, MM, STEP, false, 1, false, false, false, KF, 0, true>(h, lp);
-    }
-    if constexpr (KF == 0) {
-        if (h->lean_solo)
-            return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 0, false, false, true, 0, 0, true>(h, lp)
-                      : launch_lean_inst<NSLOT, MM, STEP, false, 0, false, false, true, 0, 0, true>(h, lp);
-    }
-    return mu ? launch_lean_inst<NSLOT, MM, STEP, true, 0, false, false, false, KF, 0, true>(h, lp)
-              : launch_lean_inst<NSLOT, MM, STEP, false, 0, false, false, false, KF, 0, true>(h, lp);
+// orbit take the KF variant, which has no SOLO layout
+template <int NSLOT, unsigned B> static int launch_lean_replay_kf(smolmc_handle *h, const LeanParams &lp) {
+    const unsigned key = B | (lean_key(h, lp, !(B & LV_KF)) & ~(unsigned)LV_OCC6);
+    return with_mm_step(h, [&](auto mm, auto step) {
+        if constexpr (B & LV_KF)
+            return launch_lean_variant<NSLOT, mm, step, B | LV_MU | 2, B | 2, B | LV_MU | 1, B | 1, B | LV_MU, B>(h, lp, key);
+        else
+            return launch_lean_variant<NSLOT, mm, step, B | LV_MU | 2, B | 2, B | LV_MU | 1, B | 1, B | LV_MU | LV_SOLO, B | LV_SOLO,
+                                       B | LV_MU, B>(h, lp, key);
+    });
 }
 template <int NSLOT> static int launch_lean_replay_nslot(smolmc_handle *h, const LeanParams &lp) {
-    const bool swap = h->cfg.step_type == SMOLMC_STEP_SWAP;
-    constexpr int K = SMOLMC_LEAN_MAX_KF;
-    if (h->lean_kf) {
-        if (h->lean_mm == 2)
-            return swap ? launch_lean_replay_me<NSLOT, 2, SMOLMC_STEP_SWAP, K>(h, lp) : launch_lean_replay_me<NSLOT, 2, SMOLMC_STEP_FLIP, K>(h, lp);
-        return swap ? launch_lean_replay_me<NSLOT, 3, SMOLMC_STEP_SWAP, K>(h, lp) : launch_lean_replay_me<NSLOT, 3, SMOLMC_STEP_FLIP, K>(h, lp);
-    }
-    if (h->lean_mm == 2)
-        return swap ? launch_lean_replay_me<NSLOT, 2, SMOLMC_STEP_SWAP, 0>(h, lp) : launch_lean_replay_me<NSLOT, 2, SMOLMC_STEP_FLIP, 0>(h, lp);
-    return swap ? launch_lean_replay_me<NSLOT, 3, SMOLMC_STEP_SWAP, 0>(h, lp) : launch_lean_replay_me<NSLOT, 3, SMOLMC_STEP_FLIP, 0>(h, lp);
+    return h->lean_kf ? launch_lean_replay_kf<NSLOT, LV_REPLAY | LV_KF>(h, lp) : launch_lean_replay_kf<NSLOT, LV_REPLAY>(h, lp);
 }

@@ -951,83 +951,38 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
     if (REPLAY && lane == 0 && rp_bad) atomicOr(P.rp_err, 1);
 }
 
-template <int NSLOT, int MM, int STEP, bool MU, int EW, bool BIAS = false, bool REPLAY = false, int WLK = 0>
-static int launch_multi_inst(smolmc_handle *h, const LeanParams &lp) {
+// ---- kernel dispatch (launch.h) -------------------------------------------------
+// mc_lean_multi_kernel's template arguments after NSLOT, MM, STEP, as the flags of a variant word
+enum : unsigned {
+    MV_EW = 3, // (the Ewald mode itself: 0 absent, 1 the field in LDS, 2 in HBM)
+    MV_MU = 4, MV_REG = 8, MV_BIAS = 16, MV_REPLAY = 32,
+    MV_WL = 64, MV_WL_KF = 128 // (WLK 1 and 2: Wang-Landau, and with several correlation functions per orbit)
+};
+template <int NSLOT, int MM, int STEP, unsigned V> static auto multi_variant() {
+    return mc_lean_multi_kernel<NSLOT, MM, STEP, bool(V & MV_MU), int(V & MV_EW), bool(V & MV_REG), bool(V & MV_BIAS), bool(V & MV_REPLAY),
+                                (V & MV_WL_KF) ? 2 : (V & MV_WL) ? 1 : 0>;
+}
+// Every family of this kernel has the same variants, (mu, Ewald mode), in the same order (the order of the
+// kernels in the code object, see launch.h); B: the flags the family fixes
+template <int NSLOT, unsigned B> static int launch_multi_variant(smolmc_handle *h, const LeanParams &lp) {
     const unsigned wpb = (unsigned)h->waves_per_block_lean;
-    const unsigned grid = (unsigned)((h->R + wpb - 1) / wpb);
-    // one site class with more than 256 clusters per site: slot records in registers
-    auto kern = (NSLOT == 8 && lp.m_ncls == 1) ? mc_lean_multi_kernel<NSLOT, MM, STEP, MU, EW, NSLOT == 8, BIAS, REPLAY, WLK>
-                                               : mc_lean_multi_kernel<NSLOT, MM, STEP, MU, EW, false, BIAS, REPLAY, WLK>;
-    if (h->lean_lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h->lean_lds));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), h->lean_lds, h->stream, lp);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+    const dim3 grid((unsigned)((h->R + wpb - 1) / wpb)), block(64 * wpb);
+    const unsigned key = B | (lp.m_mu != nullptr ? MV_MU : 0) | (lp.ew_field == 1 ? 1u : lp.ew_field == 2 ? 2u : 0u);
+    return with_mm_step(h, [&](auto mm, auto step) {
+        return first_match<B | MV_MU | 1, B | 1, B | MV_MU | 2, B | 2, B | MV_MU, B>(key, [&](auto v) {
+            // one site class with more than 256 clusters per site: slot records in registers
+            auto kern = (NSLOT == 8 && lp.m_ncls == 1) ? multi_variant<NSLOT, mm, step, v | (NSLOT == 8 ? MV_REG : 0)>()
+                                                       : multi_variant<NSLOT, mm, step, v>();
+            return launch_timed(h, kern, grid, block, h->lean_lds, lp);
+        });
+    });
 }
-template <int NSLOT, int MM, int STEP, bool BIAS> static int launch_multi_me(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.m_mu != nullptr;
-    if (lp.ew_field == 1)
-        return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 1, BIAS>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 1, BIAS>(h, lp);
-    if (lp.ew_field == 2)
-        return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 2, BIAS>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 2, BIAS>(h, lp);
-    return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 0, BIAS>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 0, BIAS>(h, lp);
-}
-template <int NSLOT, int MM, bool BIAS = false> static int launch_multi_nm(smolmc_handle *h, const LeanParams &lp) {
-    if (h->cfg.step_type == SMOLMC_STEP_SWAP) return launch_multi_me<NSLOT, MM, SMOLMC_STEP_SWAP, BIAS>(h, lp);
-    return launch_multi_me<NSLOT, MM, SMOLMC_STEP_FLIP, BIAS>(h, lp);
-}
-// Wang-Landau variants (multi_wl_n*.hip, multi_wl_replay_n*.hip; W = 2: several correlation functions per orbit, multi_wl_kf_n*.hip)
-template <int NSLOT, int MM, int STEP, bool REPLAY, int W> static int launch_multi_wl_me(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.m_mu != nullptr;
-    if (lp.ew_field == 1)
-        return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 1, false, REPLAY, W>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 1, false, REPLAY, W>(h, lp);
-    if (lp.ew_field == 2)
-        return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 2, false, REPLAY, W>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 2, false, REPLAY, W>(h, lp);
-    return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 0, false, REPLAY, W>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 0, false, REPLAY, W>(h, lp);
-}
-template <int NSLOT, bool REPLAY = false, int W = 1> static int launch_multi_wl_nslot(smolmc_handle *h, const LeanParams &lp) {
-    const bool swap = h->cfg.step_type == SMOLMC_STEP_SWAP;
-    if (h->lean_mm == 2)
-        return swap ? launch_multi_wl_me<NSLOT, 2, SMOLMC_STEP_SWAP, REPLAY, W>(h, lp) : launch_multi_wl_me<NSLOT, 2, SMOLMC_STEP_FLIP, REPLAY, W>(h, lp);
-    return swap ? launch_multi_wl_me<NSLOT, 3, SMOLMC_STEP_SWAP, REPLAY, W>(h, lp) : launch_multi_wl_me<NSLOT, 3, SMOLMC_STEP_FLIP, REPLAY, W>(h, lp);
-}
-// replay variants (multi_replay_n*.hip)
-template <int NSLOT, int MM, int STEP> static int launch_multi_replay_me(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.m_mu != nullptr;
-    if (lp.ew_field == 1)
-        return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 1, false, true>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 1, false, true>(h, lp);
-    if (lp.ew_field == 2)
-        return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 2, false, true>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 2, false, true>(h, lp);
-    return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 0, false, true>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 0, false, true>(h, lp);
-}
-template <int NSLOT> static int launch_multi_replay_nslot(smolmc_handle *h, const LeanParams &lp) {
-    const bool swap = h->cfg.step_type == SMOLMC_STEP_SWAP;
-    if (h->lean_mm == 2)
-        return swap ? launch_multi_replay_me<NSLOT, 2, SMOLMC_STEP_SWAP>(h, lp) : launch_multi_replay_me<NSLOT, 2, SMOLMC_STEP_FLIP>(h, lp);
-    return swap ? launch_multi_replay_me<NSLOT, 3, SMOLMC_STEP_SWAP>(h, lp) : launch_multi_replay_me<NSLOT, 3, SMOLMC_STEP_FLIP>(h, lp);
-}
-// biased replay variants (multi_bias_replay_n*.hip)
-template <int NSLOT, int MM, int STEP> static int launch_multi_bias_replay_me(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.m_mu != nullptr;
-    if (lp.ew_field == 1)
-        return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 1, true, true>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 1, true, true>(h, lp);
-    if (lp.ew_field == 2)
-        return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 2, true, true>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 2, true, true>(h, lp);
-    return mu ? launch_multi_inst<NSLOT, MM, STEP, true, 0, true, true>(h, lp) : launch_multi_inst<NSLOT, MM, STEP, false, 0, true, true>(h, lp);
-}
-template <int NSLOT> static int launch_multi_bias_replay_nslot(smolmc_handle *h, const LeanParams &lp) {
-    const bool swap = h->cfg.step_type == SMOLMC_STEP_SWAP;
-    if (h->lean_mm == 2)
-        return swap ? launch_multi_bias_replay_me<NSLOT, 2, SMOLMC_STEP_SWAP>(h, lp) : launch_multi_bias_replay_me<NSLOT, 2, SMOLMC_STEP_FLIP>(h, lp);
-    return swap ? launch_multi_bias_replay_me<NSLOT, 3, SMOLMC_STEP_SWAP>(h, lp) : launch_multi_bias_replay_me<NSLOT, 3, SMOLMC_STEP_FLIP>(h, lp);
-}
-template <int NSLOT> static int launch_multi_bias_nslot(smolmc_handle *h, const LeanParams &lp) {
-    return h->lean_mm == 2 ? launch_multi_nm<NSLOT, 2, true>(h, lp) : launch_multi_nm<NSLOT, 3, true>(h, lp);
-}
+// (multi_bias_n*.hip, multi_replay_n*.hip, multi_bias_replay_n*.hip)
+template <int NSLOT> static int launch_multi_bias_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_multi_variant<NSLOT, MV_BIAS>(h, lp); }
+template <int NSLOT> static int launch_multi_replay_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_multi_variant<NSLOT, MV_REPLAY>(h, lp); }
+template <int NSLOT> static int launch_multi_bias_replay_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_multi_variant<NSLOT, MV_BIAS | MV_REPLAY>(h, lp); }
+// Wang-Landau variants: B = MV_WL (multi_wl_n*.hip), MV_WL | MV_REPLAY (multi_wl_replay_n*.hip), MV_WL_KF (multi_wl_kf_n*.hip)
+template <int NSLOT, unsigned B> static int launch_multi_wl_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_multi_variant<NSLOT, B>(h, lp); }
 
 
 // ----------------------------------------------------------------------------
@@ -2194,36 +2149,23 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
 
 #undef key0
 #undef key1
-template <int NSLOT, int MM, bool REPLAY = false, bool WLT = false, bool BIAS = false> static int launch_table_multi_inst(smolmc_handle *h, const LeanParams &lp) {
+// mc_table_multi_kernel: the flags of mc_table_kernel (TV_*, mc_lean.h), T = 0 in multi_n*.hip and TV_BIAS, TV_WL,
+// TV_REPLAY in multi_table_bias_n*.hip, multi_table_wl_n*.hip, multi_table_replay_n*.hip only
+template <int NSLOT, unsigned T> static int launch_table_multi_nslot(smolmc_handle *h, const LeanParams &lp) {
     const unsigned wpb = (unsigned)h->waves_per_block_lean;
-    const unsigned grid = (unsigned)((h->R + wpb - 1) / wpb);
-    auto kern = lp.ew_field == 1 ? mc_table_multi_kernel<NSLOT, MM, 1, REPLAY, WLT, BIAS>
-                                 : (lp.ew_field == 2 ? mc_table_multi_kernel<NSLOT, MM, 2, REPLAY, WLT, BIAS> : mc_table_multi_kernel<NSLOT, MM, 0, REPLAY, WLT, BIAS>);
-    if (h->lean_lds > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)h->lean_lds));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), h->lean_lds, h->stream, lp);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return 0;
+    const dim3 grid((unsigned)((h->R + wpb - 1) / wpb)), block(64 * wpb);
+    const int ewm = lp.ew_field == 1 || lp.ew_field == 2 ? lp.ew_field : 0;
+    return first_match<2, 3>(h->lean_mm, [&](auto mm) {
+        return first_match<2, 0, 1>(ewm, [&](auto ew) { // (code-object order, see launch.h)
+            return launch_timed(h, mc_table_multi_kernel<NSLOT, mm, ew, bool(T & TV_REPLAY), bool(T & TV_WL), bool(T & TV_BIAS)>, grid, block,
+                                h->lean_lds, lp);
+        });
+    });
 }
-
-// (instantiated in multi_table_bias_n*.hip only)
-template <int NSLOT> static int launch_table_multi_bias_nslot(smolmc_handle *h, const LeanParams &lp) {
-    return h->lean_mm == 2 ? launch_table_multi_inst<NSLOT, 2, false, false, true>(h, lp) : launch_table_multi_inst<NSLOT, 3, false, false, true>(h, lp);
-}
-// (instantiated in multi_table_wl_n*.hip only)
-template <int NSLOT> static int launch_table_multi_wl_nslot(smolmc_handle *h, const LeanParams &lp) {
-    return h->lean_mm == 2 ? launch_table_multi_inst<NSLOT, 2, false, true>(h, lp) : launch_table_multi_inst<NSLOT, 3, false, true>(h, lp);
-}
-// (instantiated in multi_table_replay_n*.hip only)
-template <int NSLOT> static int launch_table_multi_replay_nslot(smolmc_handle *h, const LeanParams &lp) {
-    return h->lean_mm == 2 ? launch_table_multi_inst<NSLOT, 2, true>(h, lp) : launch_table_multi_inst<NSLOT, 3, true>(h, lp);
-}
+template <int NSLOT> static int launch_table_multi_bias_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_multi_nslot<NSLOT, TV_BIAS>(h, lp); }
+template <int NSLOT> static int launch_table_multi_wl_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_multi_nslot<NSLOT, TV_WL>(h, lp); }
+template <int NSLOT> static int launch_table_multi_replay_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_multi_nslot<NSLOT, TV_REPLAY>(h, lp); }
 template <int NSLOT> static int launch_multi_nslot(smolmc_handle *h, const LeanParams &lp) {
-    if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP)
-        return h->lean_mm == 2 ? launch_table_multi_inst<NSLOT, 2>(h, lp) : launch_table_multi_inst<NSLOT, 3>(h, lp);
-    return h->lean_mm == 2 ? launch_multi_nm<NSLOT, 2>(h, lp) : launch_multi_nm<NSLOT, 3>(h, lp);
+    if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) return launch_table_multi_nslot<NSLOT, 0>(h, lp);
+    return launch_multi_variant<NSLOT, 0>(h, lp);
 }

@@ -702,6 +702,9 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
 
 static long wl_gcd(long a, long b) { while (b) { const long t = a % b; a = b; b = t; } return a; }
 
+// mc_wl_kernel's template arguments after NSLOT, MM, STEP, as the flags of a variant word
+enum : unsigned { WV_REPLAY = 1, WV_MU = 2, WV_EW = 4 };
+
 // Launch.  GROUP ROTATION (round 5): the kernel's residency is set by LDS -- config 4: three four-walker
 // workgroups per CU, 3072 walkers on 256 CUs -- and a step of this kernel takes as long at three waves per SIMD as
 // at one (latency, not issue).  4096 walkers in one launch are therefore a full round of 3072 followed by a round of
@@ -711,9 +714,11 @@ static long wl_gcd(long a, long b) { while (b) { const long t = a % b; a = b; b 
 // steps -- every group runs c times, every sub-launch fills the chip exactly: time R / C instead of ceil(R / C)
 // rounds.  Walkers are independent and carry their whole state through HBM between launches, so the chains are
 // the chains of one long launch (SMOLMC_NO_ROTATE: A/B switch; tests compare both against the oracle).
-template <int NSLOT, int MM, int STEP, bool REPLAY, bool MU, bool EW>
+// (not launch_timed: the sub-launches of the rotation all lie between the handle's two timing events)
+template <int NSLOT, int MM, int STEP, unsigned V>
 static int launch_wl_kern(smolmc_handle *h, const LeanParams &lp) {
-    auto kern = mc_wl_kernel<NSLOT, MM, STEP, REPLAY, MU, EW>;
+    constexpr bool REPLAY = V & WV_REPLAY;
+    auto kern = mc_wl_kernel<NSLOT, MM, STEP, REPLAY, bool(V & WV_MU), bool(V & WV_EW)>;
     if (h->lean_lds > 64 * 1024)
         HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lean_lds));
     long C = 0;
@@ -749,21 +754,13 @@ static int launch_wl_kern(smolmc_handle *h, const LeanParams &lp) {
     h->timed = true;
     return 0;
 }
-template <int NSLOT, int MM, int STEP, bool REPLAY = false>
-static int launch_wl_inst(smolmc_handle *h, const LeanParams &lp) {
-    const bool mu = lp.mu_row != nullptr, ew = lp.ew_G != nullptr; // (Ewald: only with the field in LDS, engine.hip)
-    if (ew) return mu ? launch_wl_kern<NSLOT, MM, STEP, REPLAY, true, true>(h, lp) : launch_wl_kern<NSLOT, MM, STEP, REPLAY, false, true>(h, lp);
-    return mu ? launch_wl_kern<NSLOT, MM, STEP, REPLAY, true, false>(h, lp) : launch_wl_kern<NSLOT, MM, STEP, REPLAY, false, false>(h, lp);
+// B = 0 in wl_n*.hip's smolmc_launch_wl_*, WV_REPLAY in its smolmc_launch_wl_replay_*; the list in code-object order (launch.h)
+template <int NSLOT, unsigned B> static int launch_wl_variant(smolmc_handle *h, const LeanParams &lp) {
+    // (Ewald: only with the field in LDS, engine.hip)
+    const unsigned key = B | (lp.mu_row != nullptr ? WV_MU : 0) | (lp.ew_G != nullptr ? WV_EW : 0);
+    return with_mm_step(h, [&](auto mm, auto step) {
+        return first_match<B | WV_MU | WV_EW, B | WV_EW, B | WV_MU, B>(key, [&](auto v) { return launch_wl_kern<NSLOT, mm, step, v>(h, lp); });
+    });
 }
-template <int NSLOT> static int launch_wl_nslot(smolmc_handle *h, const LeanParams &lp) {
-    const bool swap = h->cfg.step_type == SMOLMC_STEP_SWAP;
-    if (h->lean_mm == 2)
-        return swap ? launch_wl_inst<NSLOT, 2, SMOLMC_STEP_SWAP>(h, lp) : launch_wl_inst<NSLOT, 2, SMOLMC_STEP_FLIP>(h, lp);
-    return swap ? launch_wl_inst<NSLOT, 3, SMOLMC_STEP_SWAP>(h, lp) : launch_wl_inst<NSLOT, 3, SMOLMC_STEP_FLIP>(h, lp);
-}
-template <int NSLOT> static int launch_wl_replay_nslot(smolmc_handle *h, const LeanParams &lp) {
-    const bool swap = h->cfg.step_type == SMOLMC_STEP_SWAP;
-    if (h->lean_mm == 2)
-        return swap ? launch_wl_inst<NSLOT, 2, SMOLMC_STEP_SWAP, true>(h, lp) : launch_wl_inst<NSLOT, 2, SMOLMC_STEP_FLIP, true>(h, lp);
-    return swap ? launch_wl_inst<NSLOT, 3, SMOLMC_STEP_SWAP, true>(h, lp) : launch_wl_inst<NSLOT, 3, SMOLMC_STEP_FLIP, true>(h, lp);
-}
+template <int NSLOT> static int launch_wl_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_wl_variant<NSLOT, 0>(h, lp); }
+template <int NSLOT> static int launch_wl_replay_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_wl_variant<NSLOT, WV_REPLAY>(h, lp); }

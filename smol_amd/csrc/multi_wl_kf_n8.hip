@@ -1,4 +1,4 @@
 // mc_lean_multi_kernel Wang-Landau instantiations with several correlation functions per orbit (KFW), NSLOT = 8
 #include "mc_lean_multi.h"
 
-int smolmc_launch_multi_wl_kf_8(smolmc_handle *h, const LeanParams &lp) { return launch_multi_wl_nslot<8, false, 2>(h, lp); }
+int smolmc_launch_multi_wl_kf_8(smolmc_handle *h, const LeanParams &lp) { return launch_multi_wl_nslot<8, MV_WL_KF>(h, lp); }

@@ -896,3 +896,4 @@ __host__ __device__ inline size_t wl_multi_wave_bytes(int L, int F, int sum_mode
            (sum_mode ? (size_t)SMOLMC_WLM_LOG * F * 8 : (size_t)L * 8 + (size_t)SMOLMC_WL_ROWS * F * 8);
 }
 #define SMOLMC_LEAN_MAX_KF 6 // correlation functions per orbit served by the lean kernels (ternary triplets)
+#include "launch.h"
