@@ -224,6 +224,22 @@ int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint64_t *seeds
                      const double *temperature, int reset_aux);
 /* ThermalKernelMixin.temperature setter (kernel/base.py:418-422), per walker */
 int smolmc_set_temperature(smolmc_handle *h, const double *temperature /*R*/);
+/* Per-walker chemical potentials: a mu-T grid in one semigrand handle (the reference assigns
+ * ensemble.chemical_potentials and runs again, ensemble.py:35-73; here walker r has its own row, as it has its own
+ * temperature).  mu [R x n_sublattices x mu_width] in the caller's numbering: the active sublattices in the order of
+ * smolmc_tables, the columns the species codes exactly as in mu_table at smolmc_create.  NULL returns the handle to
+ * the table it was created with.  The chemical-work feature (the last of F, natural parameter -1) and the enthalpy
+ * of every walker are re-priced on the device from its current occupancy at its new row, so a call between two
+ * smolmc_run is a mu sweep that carries the configurations along; smolmc_set_state prices the initial trace with the
+ * walker's own row, and the rows survive it.  smolmc_eval_full and smolmc_eval_delta keep the create-time table.
+ * Valid on a handle created with has_mu that runs a lean kernel family; refused, each with its reason, on handles
+ * without has_mu, distance handles, Wang-Landau handles (one density of states per Hamiltonian) and handles on
+ * mc_kernel / the universal kernel; while rows are set smolmc_replay, smolmc_exchange_dev and
+ * smolmc_import_temperature_dev are refused (an exchange of temperatures alone is no valid move between different
+ * Hamiltonians) and smolmc_kernel_info appends " walker_mu=1 mu_max=<largest |mu| over all walkers>". */
+int smolmc_set_walker_mu(smolmc_handle *h, const double *mu /* R x n_sublattices x mu_width, or NULL */);
+/* ... the rows in the same shape: those of the last call, the create-time rows when none are set */
+int smolmc_get_walker_mu(smolmc_handle *h, double *mu /* R x n_sublattices x mu_width */);
 /* any output pointer may be NULL */
 int smolmc_get_state(smolmc_handle *h, int32_t *occ /*RxN*/, double *features /*RxF*/,
                      double *enthalpy /*R*/, uint64_t *n_accepted /*R*/,

@@ -406,6 +406,12 @@ class TableSet:
             p.append(-1.0)
         return np.array(p)
 
+    def active_sites(self):
+        """The active sites of every active sublattice, in the order of the struct (the order of the rows of
+        smolmc_set_walker_mu)."""
+        ptr = self._keep["sub_site_ptr"]
+        return [np.asarray(self._keep["sub_active_sites"][ptr[k]:ptr[k + 1]], dtype=np.int64) for k in range(len(ptr) - 1)]
+
     def set_bias(self, bias_type, table=None, penalty=0.0, intercepts=None):
         """Attach (or clear) an MCBias term (smol/moca/kernel/bias.py): ``table`` is the
         reference's per-(site, species code) table -- fugacity fractions (BIAS_FUGACITY,

@@ -1582,10 +1582,18 @@ static bool lean_ewald_rows(const smolmc_handle *h, int sb, int n, double *q, do
     return true;
 }
 // the mu delta of a step joins the float32 sum (<= 2 flips * 2 |mu|): mmax = the largest |mu| of the rows in use
-static void lean_widen_fast_eps(const smolmc_tables *t, LeanParams &lp, double mmax) {
-    if (t->has_mu) lp.fast_eps += 4.0 * mmax * ldexp(1.0, -19);
+static void lean_widen_fast_eps(int has_mu, LeanParams &lp, double mmax) {
+    if (has_mu) lp.fast_eps += 4.0 * mmax * ldexp(1.0, -19);
     // test hook: widen the undecided band so that both decision paths interleave
     if (const char *sc = smolmc_env(ENV_FAST_EPS_SCALE)) lp.fast_eps *= atof(sc);
+}
+// The bound of the handle for rows whose largest |mu| is mmax, from the un-widened one kept on the handle: at create
+// with the table's rows, at every smolmc_set_walker_mu with the maximum over ALL walkers' rows (a stale bound would
+// make about one decision in 1e5 wrong, which no test finds by chance: smolmc_kernel_info prints mu_max)
+static void lean_set_fast_eps(smolmc_handle *h, double mmax) {
+    h->lp.fast_eps = h->fast_eps_plain;
+    for (int i = 0; i < h->fast_eps_widenings; ++i) lean_widen_fast_eps(h->rt.has_mu, h->lp, mmax);
+    h->mu_max = mmax;
 }
 // the walker state, the bias and the Wang-Landau block of LeanParams (pointers and dimensions of mc_kernel's)
 static void lean_fill_state(const smolmc_handle *h, const smolmc_tables *t, LeanParams &lp, int bias_row_stride, int wl_sums) {
@@ -1749,11 +1757,13 @@ static int plan_lean(smolmc_handle *h, const smolmc_tables *t, LeanPlan &p) {
     if (!p.take) return 0;
     const KParams &kp = h->kp;
     LeanParams &lp = h->lp;
+    p.mu_row.resize(8, 0.0); // (a whole cell: the re-pricing of per-walker rows reads all eight)
     if (t->has_mu && dev_upload(h, p.mu_row.data(), p.mu_row.size(), &lp.mu_row)) return 1;
     if (t->bias_type && dev_upload(h, p.bias_pair.data(), p.bias_pair.size(), &lp.bias_pair)) return 1;
     double mmax = 0.0;
     for (double v : p.mu_row) mmax = std::max(mmax, std::fabs(v));
-    lean_widen_fast_eps(t, lp, mmax);
+    h->fast_eps_plain = lp.fast_eps; h->fast_eps_widenings = 1; h->mu_max_create = mmax; h->d_mu_create = lp.mu_row;
+    lean_set_fast_eps(h, mmax);
     lean_fill_state(h, t, lp, 64, is_table(h) ? kp.wl_sum_mode : 1);
     lp.sbase = p.sbase; lp.nact = p.nact; lp.ncodes = p.nc;
     if (t->has_ewald) { lp.ew_act = kp.ew_act; lp.ew_qs = kp.ew_qs; lp.ew_dg = kp.ew_dg; lp.ew_frozen = kp.ew_frozen; }
@@ -1935,8 +1945,8 @@ static int plan_lean_multi(smolmc_handle *h, const smolmc_tables *t, const LeanP
     if (t->bias_type && dev_upload(h, p.bias_pairs.data(), p.bias_pairs.size(), &lp.bias_pair)) return 1;
     // KEPT FROM EARLIER VERSIONS, bit for bit: a model that the single-class planner refused at its LDS stage had
     // been widened (and scaled) once there before this planner widened it again; NOTES.md lists it for removal
-    if (one.late) lean_widen_fast_eps(t, lp, p.mmax);
-    lean_widen_fast_eps(t, lp, p.mmax);
+    h->fast_eps_plain = lp.fast_eps; h->fast_eps_widenings = one.late ? 2 : 1; h->mu_max_create = p.mmax; h->d_mu_create = lp.m_mu;
+    lean_set_fast_eps(h, p.mmax);
     lp.m_ncls = h->lean_ncls; lp.m_nsub = ns; lp.m_ndims = p.ndims;
     if (is_table(h) && lean_fill_table(h, t, lp, p.ndims, p.max_nact, 0)) return 1;
     lean_fill_state(h, t, lp, 256, wl_sum_mode_of(h));
@@ -2129,23 +2139,24 @@ struct LeanFamilyRow {
     const char *name;                 // smolmc_kernel_info: the layout ...
     const char *wl_sums, *wl_means;   // ... and the tag of the Wang-Landau kernel (per-bin feature sums / running means)
     LeanLauncher run[3], replay[3], table_replay[3];
+    LeanLauncher walker_mu[3];        // `run` while per-walker chemical potentials are set (smolmc_set_walker_mu)
 };
 #define L2(f) {smolmc_launch_##f##_2, smolmc_launch_##f##_4, nullptr}
 #define L3(f) {smolmc_launch_##f##_2, smolmc_launch_##f##_4, smolmc_launch_##f##_8}
 #define NONE {nullptr, nullptr, nullptr}
 static const LeanFamilyRow lean_families[] = {
-    /* K_LEAN             */ {"lean", nullptr, nullptr, L2(lean), L2(lean_replay), L2(table_replay)},
-    /* K_LEAN_BIAS        */ {"lean", nullptr, nullptr, L2(lean_bias), L2(lean_bias_replay), NONE},
-    /* K_LEAN_CORR        */ {"lean", nullptr, nullptr, L2(lean_corr), L2(lean_replay), NONE}, // (KF: a template flag of the same launchers)
-    /* K_WL               */ {"lean", " wl=v3", " wl=v3", L2(wl), L2(wl_replay), NONE},
-    /* K_TABLE_BIAS       */ {"lean", nullptr, nullptr, L2(table_bias), NONE, NONE},
-    /* K_TABLE_WL         */ {"lean", " wl=table", " wl=table-mean", L2(table_wl), NONE, NONE},
-    /* K_MULTI            */ {"lean-multi", nullptr, nullptr, L3(multi), L3(multi_replay), L3(multi_table_replay)},
-    /* K_MULTI_BIAS       */ {"lean-multi", nullptr, nullptr, L3(multi_bias), L3(multi_bias_replay), NONE},
-    /* K_MULTI_WL         */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_wl), L3(multi_wl_replay), NONE},
-    /* K_MULTI_WL_KF      */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_wl_kf), NONE, NONE},
-    /* K_MULTI_TABLE_BIAS */ {"lean-multi", nullptr, nullptr, L3(multi_table_bias), NONE, NONE},
-    /* K_MULTI_TABLE_WL   */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_table_wl), NONE, NONE},
+    /* K_LEAN             */ {"lean", nullptr, nullptr, L2(lean), L2(lean_replay), L2(table_replay), L2(lean_wmu)},
+    /* K_LEAN_BIAS        */ {"lean", nullptr, nullptr, L2(lean_bias), L2(lean_bias_replay), NONE, L2(lean_bias_wmu)},
+    /* K_LEAN_CORR        */ {"lean", nullptr, nullptr, L2(lean_corr), L2(lean_replay), NONE, L2(lean_corr_wmu)}, // (KF: a template flag of the same launchers)
+    /* K_WL               */ {"lean", " wl=v3", " wl=v3", L2(wl), L2(wl_replay), NONE, NONE},
+    /* K_TABLE_BIAS       */ {"lean", nullptr, nullptr, L2(table_bias), NONE, NONE, L2(table_bias_wmu)},
+    /* K_TABLE_WL         */ {"lean", " wl=table", " wl=table-mean", L2(table_wl), NONE, NONE, NONE},
+    /* K_MULTI            */ {"lean-multi", nullptr, nullptr, L3(multi), L3(multi_replay), L3(multi_table_replay), L3(multi_wmu)},
+    /* K_MULTI_BIAS       */ {"lean-multi", nullptr, nullptr, L3(multi_bias), L3(multi_bias_replay), NONE, L3(multi_bias_wmu)},
+    /* K_MULTI_WL         */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_wl), L3(multi_wl_replay), NONE, NONE},
+    /* K_MULTI_WL_KF      */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_wl_kf), NONE, NONE, NONE},
+    /* K_MULTI_TABLE_BIAS */ {"lean-multi", nullptr, nullptr, L3(multi_table_bias), NONE, NONE, L3(multi_table_bias_wmu)},
+    /* K_MULTI_TABLE_WL   */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_table_wl), NONE, NONE, NONE},
 };
 #undef L2
 #undef L3
@@ -2154,6 +2165,7 @@ static_assert(sizeof(lean_families) / sizeof(lean_families[0]) == K_MULTI_TABLE_
 static LeanLauncher lean_launcher(const smolmc_handle *h, bool replay) {
     const LeanFamilyRow &row = lean_families[h->family - K_LEAN];
     const int i = h->lean_nslot == 2 ? 0 : (h->lean_nslot == 4 ? 1 : 2);
+    if (!replay && h->lp.mu_stride) return row.walker_mu[i];
     return !replay ? row.run[i] : (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP ? row.table_replay[i] : row.replay[i]);
 }
 
@@ -2382,6 +2394,103 @@ static void set_betas(smolmc_handle *h, const double *temperature, std::vector<d
     }
 }
 
+// ---- per-walker chemical potentials (smolmc_set_walker_mu) ------------------------------------------------------
+// A mu-T grid in one handle: walker r reads its chemical potentials from row r of a device array in the kernels'
+// layout (LeanParams::mu_stride) instead of the one row the handle was created with.  The chemical work is the last
+// feature, natural parameter -1; a change of rows re-prices it on the device from the current occupancies
+// (smolmc_walker_mu_reprice, walker_mu.hip: a kernel of its own translation unit, so that no kernel of this one moves).
+// why a handle takes no per-walker rows (null: it does)
+static int walker_mu_refused(const smolmc_handle *h) {
+    if (h->dist) return fail("per-walker chemical potentials: a distance handle has none (its objective is a distance to a target, no chemical work)");
+    if (!h->rt.has_mu) return fail("per-walker chemical potentials: the handle was created without has_mu (no chemical-work feature to price)");
+    if (is_wl(h)) return fail("per-walker chemical potentials: a Wang-Landau handle estimates one density of states, of one Hamiltonian");
+    if (!h->lean())
+        return fail("per-walker chemical potentials: only the lean kernel families take them, this handle runs " +
+                    std::string(h->univ() ? "the universal kernel" : "mc_kernel") + " | not lean: " +
+                    (h->lean_reason.empty() ? std::string("single-class planner refused the model") : h->lean_reason));
+    return 0;
+}
+// sublattices and species codes per sublattice of the rows' cells in the kernels' layout
+static int walker_mu_shape(const smolmc_handle *h, int *ncodes) {
+    const int ns = h->lean_multi() ? h->lp.m_nsub : 1;
+    for (int k = 0; k < ns; ++k) ncodes[k] = std::min(h->lean_multi() ? h->lp.m_ncodes[k] : h->lp.ncodes, h->rt.mu_W);
+    return ns;
+}
+
+extern "C" int smolmc_set_walker_mu(smolmc_handle *h, const double *mu) {
+    if (!h) return fail("null handle");
+    TRY(walker_mu_refused(h));
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    LeanParams &lp = h->lp;
+    const bool multi = h->lean_multi();
+    const int stride = multi ? 32 : 8, W = h->rt.mu_W;
+    const size_t R = (size_t)h->R;
+    int ncodes[4];
+    const int ns = walker_mu_shape(h, ncodes);
+    const double *rows_old = multi ? lp.m_mu : lp.mu_row;
+    const int stride_old = lp.mu_stride;
+    const double *rows_new = h->d_mu_create;
+    double mmax = h->mu_max_create;
+    if (mu) {
+        // the per-wave cells go behind the workgroup's LDS: the launch must still fit a CU's 160 KiB
+        const int wpb = multi ? h->waves_per_block_lean : is_table(h) ? h->lean_wpb : h->lean_solo ? 1 : 4;
+        const size_t lds = ((!multi && is_table(h) && wpb == 8 ? h->lean_lds_wpb8 : h->lean_lds) + 7) & ~(size_t)7;
+        if (lds + walker_mu_lds(stride, wpb) > 160 * 1024)
+            return fail("per-walker chemical potentials: no LDS left for the walkers' row cells on this handle");
+        std::vector<double> rows(R * stride, 0.0);
+        mmax = 0.0;
+        for (size_t r = 0; r < R; ++r)
+            for (int k = 0; k < ns; ++k)
+                for (int c = 0; c < ncodes[k]; ++c) {
+                    const double v = mu[(r * ns + k) * W + c];
+                    if (!std::isfinite(v)) return fail("per-walker chemical potentials must be finite");
+                    rows[r * stride + k * 8 + c] = v;
+                    mmax = std::max(mmax, std::fabs(v));
+                }
+        if (!h->d_walker_mu[0])
+            for (int i = 0; i < 2; ++i) TRY(dev_alloc(h, R * stride, &h->d_walker_mu[i]));
+        // (d_walker_mu[0] is the copy in use: the new rows go to the other one, the two swap after the re-pricing)
+        HIPCHK(hipMemcpy(h->d_walker_mu[1], rows.data(), rows.size() * 8, hipMemcpyHostToDevice));
+        rows_new = h->d_walker_mu[1];
+        lp.mu_cell_off = (uint32_t)lds;
+    }
+    // (lazy cluster features: lp.features are the scalar features' rows, the chemical work their last entry too)
+    TRY(smolmc_walker_mu_reprice(h, rows_old, stride_old, rows_new, mu ? stride : 0, lp.features, lp.F, h->kp.enthalpy));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (is_lazy(h)) h->ce_dirty = true; // (kp.features takes its scalar entries from the lean kernels' rows when it is read)
+    if (mu) {
+        std::swap(h->d_walker_mu[0], h->d_walker_mu[1]);
+        h->walker_mu.assign(mu, mu + R * ns * W);
+    } else {
+        h->walker_mu.clear();
+    }
+    (multi ? lp.m_mu : lp.mu_row) = rows_new;
+    lp.mu_stride = mu ? stride : 0;
+    lean_set_fast_eps(h, mmax);
+    return 0;
+}
+
+extern "C" int smolmc_get_walker_mu(smolmc_handle *h, double *mu) {
+    if (!h) return fail("null handle");
+    TRY(walker_mu_refused(h));
+    if (!mu) return fail("null argument");
+    int ncodes[4];
+    const int ns = walker_mu_shape(h, ncodes), W = h->rt.mu_W;
+    const size_t R = (size_t)h->R;
+    if (!h->walker_mu.empty()) {
+        memcpy(mu, h->walker_mu.data(), h->walker_mu.size() * 8);
+        return 0;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> row(h->lean_multi() ? 32 : 8, 0.0); // the create-time row: [8], or [4][8], in the kernels' layout
+    HIPCHK(hipMemcpy(row.data(), h->d_mu_create, row.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < R; ++r)
+        for (int k = 0; k < ns; ++k)
+            for (int c = 0; c < W; ++c) mu[(r * ns + k) * W + c] = c < ncodes[k] ? row[k * 8 + c] : 0.0;
+    return 0;
+}
+
 extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint64_t *seeds,
                                 const double *temperature, int reset_aux) {
     if (!h || !occ) return fail("null argument");
@@ -2446,6 +2555,8 @@ extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint
         HIPCHK(hipGetLastError());
     }
     TRY(launch_eval_full(h, kp.occ, (int)R, kp.features));
+    // (per-walker chemical potentials: the chemical work of the initial trace at the walker's own row)
+    if (!h->walker_mu.empty()) TRY(smolmc_walker_mu_reprice(h, h->d_mu_create, 0, h->d_walker_mu[0], h->lp.mu_stride, kp.features, h->F, nullptr));
     hipLaunchKernelGGL(dot_features_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, h->stream,
                        kp.features, h->d_natural, kp.enthalpy, (int)R, h->F);
     HIPCHK(hipGetLastError());
@@ -2528,6 +2639,8 @@ extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
         if (wl_tag && strlen(buf) + 24 < (size_t)n) strncat(buf, wl_tag, (size_t)n - strlen(buf) - 1);
         if (is_lazy(h) && strlen(buf) + 16 < (size_t)n) strncat(buf, " lazy-features", (size_t)n - strlen(buf) - 1);
         if (h->relabelled && strlen(buf) + 16 < (size_t)n) strncat(buf, " relabelled=1", (size_t)n - strlen(buf) - 1);
+        if (!h->walker_mu.empty() && strlen(buf) + 48 < (size_t)n) // (the largest |mu| over all walkers: what the float32 accept bound was widened by)
+            snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " walker_mu=1 mu_max=%.17g", h->mu_max);
         if (h->env_dispatch && strlen(buf) + 8 < (size_t)n) { // the dispatch switches this handle was created under
             strncat(buf, " env=", (size_t)n - strlen(buf) - 1);
             const char *sep = "";
@@ -2729,7 +2842,9 @@ static int update_walker_order(smolmc_handle *h, LeanParams &lp) {
 static int launch_lean(smolmc_handle *h, LeanParams lp, int64_t nsteps) {
     lp.steps = nsteps;
     TRY(update_walker_order(h, lp));
-    return lean_launcher(h, false)(h, lp);
+    const LeanLauncher launch = lean_launcher(h, false);
+    if (!launch) return fail("internal: no kernel of this family takes per-walker chemical potentials"); // (smolmc_set_walker_mu refuses those)
+    return launch(h, lp);
 }
 
 static void free_samples(smolmc_handle *h) {
@@ -3119,6 +3234,7 @@ extern "C" int smolmc_replay(smolmc_handle *h, int64_t nsteps, const int32_t *st
                              const double *log_priori, uint8_t *accepted_out, double *enthalpy_out,
                              double *log_priori_out) {
     if (!h || !steps || !uniforms) return fail("null argument");
+    if (!h->walker_mu.empty()) return fail("smolmc_replay while per-walker chemical potentials are set: the replay kernels price every walker with the handle's own table (smolmc_set_walker_mu(h, NULL) first)");
     if (nsteps <= 0) return 0;
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)h->R * nsteps;
@@ -3376,6 +3492,7 @@ extern "C" int smolmc_exchange_dev(smolmc_handle *h, int n_total, int first, int
                                    int64_t *stats_dev) {
     if (!h || !enthalpy_all_dev || !ladder_dev || !log_u_dev || !rung_of_dev) return fail("null argument");
     if (h->dist) return fail("a distance handle takes no replica exchange (its temperatures use the handle's kB)");
+    if (!h->walker_mu.empty()) return fail("smolmc_exchange_dev while per-walker chemical potentials are set: an exchange of temperatures alone is no valid move between walkers of different Hamiltonians");
     if (n_total < 2 || n_total > 16384) return fail("exchange ladder must hold 2 .. 16384 walkers (the rung map lives in LDS)");
     if (first < 0 || first + h->R > n_total) return fail("this handle's walkers are out of range of the ladder");
     if (parity != 0 && parity != 1) return fail("parity must be 0 or 1");
@@ -3391,6 +3508,7 @@ extern "C" int smolmc_exchange_dev(smolmc_handle *h, int n_total, int first, int
 extern "C" int smolmc_import_temperature_dev(smolmc_handle *h, const double *src_dev) {
     if (!h || !src_dev) return fail("null argument");
     if (h->dist) return fail("a distance handle takes no replica exchange (its temperatures use the handle's kB)");
+    if (!h->walker_mu.empty()) return fail("smolmc_import_temperature_dev while per-walker chemical potentials are set: an exchange of temperatures alone is no valid move between walkers of different Hamiltonians");
     HIPCHK(hipSetDevice(h->device));
     hipLaunchKernelGGL(beta_from_T_kernel, dim3((h->R + 63) / 64), dim3(64), 0, h->stream, src_dev,
                        h->d_beta, h->R, SMOLMC_KB);

@@ -352,7 +352,11 @@ template <bool ABS> __device__ __forceinline__ void occ_st(uint8_t *occ, uint32_
 // Philox stream: the reference-order golden trajectories then drive this kernel's own evaluation --
 // index rows, gathers, delta tables, swap antisymmetry, float32 pre-test, potential field -- and
 // not only the general kernel's.  Separate instantiations (lean_replay_n*.hip).
-template <int NSLOT, int MM, int STEP, bool HAS_MU, int EWM, bool WL, bool BIAS = false, bool SOLO = false,
+// EWX bit 2 (value 4; lean_wmu_n*.hip / multi_wmu_n*.hip only): per-walker chemical potentials
+// (smolmc_set_walker_mu) -- walker r reads its row from P.mu_row / P.m_mu + r * P.mu_stride into a cell of its own WAVE,
+// P.mu_cell_off bytes into the workgroup's LDS behind everything else; the step loop reads s_mu as before, from a base
+// computed before the loop.  Separate instantiations, so that no other kernel's bytes move; the low bits are EWM.
+template <int NSLOT, int MM, int STEP, bool HAS_MU, int EWX, bool WL, bool BIAS = false, bool SOLO = false,
           int KF = 0, int OCC = 0, bool REPLAY = false>
 // OCC: waves per SIMD the register allocation is held to (0 = the compiler's choice, which is 4
 // for the headline instantiation at 113 VGPRs).  OCC = 6 (80 VGPRs, a few spills) is launched
@@ -362,6 +366,9 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     static_assert(KF == 0 || (!WL && !BIAS && !SOLO), "correlation-function tables: plain Metropolis layouts only");
     static_assert(!REPLAY || (!WL && OCC == 0), "replay: Metropolis variants (Wang-Landau: mc_wl_kernel)");
     constexpr int NACC = KF ? KF : 1;
+    constexpr int EWM = EWX & 3;
+    constexpr bool WMU = (EWX & 4) != 0;
+    static_assert(!WMU || (HAS_MU && !WL && !REPLAY), "per-walker chemical potentials: semigrand Metropolis variants");
     // EWM: 0 = no Ewald term, 1 = compact Ewald with per-proposal row sums, 2 = potential field in
     // LDS.  A template parameter (not the runtime flag ew_field): both variants' pointers and code
     // otherwise stay live across the step loop and the kernel spills SGPRs.
@@ -389,7 +396,11 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     double *phi = (double *)(wbase + P.Nlds + 64 * 8 + 64);     // Ewald potential field [ew_nact]
     const int swa = P.swz_a, swm = P.swz_m, swb = P.swz_b;
     for (int i = threadIdx.x; i < P.dt_len; i += blockDim.x) s_dt[i] = P.dt[i];
-    if (HAS_MU && threadIdx.x < 8) s_mu[threadIdx.x] = threadIdx.x < P.ncodes ? P.mu_row[threadIdx.x] : 0.0;
+    if (HAS_MU && !WMU && threadIdx.x < 8) s_mu[threadIdx.x] = threadIdx.x < P.ncodes ? P.mu_row[threadIdx.x] : 0.0;
+    if (WMU) {
+        s_mu = (double *)(smem + P.mu_cell_off) + uni(wave * 8);
+        if (lane < 8 && r < P.R) s_mu[lane] = lane < P.ncodes ? P.mu_row[(size_t)r * 8 + lane] : 0.0;
+    }
     if (HAS_EW && ew_field && threadIdx.x < 8) {
         s_q[threadIdx.x] = P.ew_qrow[threadIdx.x];
         s_dg[threadIdx.x] = P.ew_dgrow[threadIdx.x];
@@ -1241,8 +1252,12 @@ __device__ __noinline__ void wl_multi_row_swap(double *grows, double *crow, int 
 // state (entropies, counted steps, the log of finished runs) is mc_lean_multi_kernel's (mc_lean_multi.h: WLK) behind
 // the potential field in LDS; the current feature vector lives in the lanes of one register and the enthalpy is
 // carried as the reference carries it (:216-218).
-template <int NSLOT, int MM, int EWM, bool REPLAY = false, bool BIAS = false, bool WLT = false>
+// EWX = EWM, + 4: per-walker chemical potentials (see mc_lean_kernel)
+template <int NSLOT, int MM, int EWX, bool REPLAY = false, bool BIAS = false, bool WLT = false>
 __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // (four or eight walkers per workgroup, two waves per SIMD)
+    constexpr int EWM = EWX & 3;
+    constexpr bool WMU = (EWX & 4) != 0;
+    static_assert(!WMU || (!WLT && !REPLAY), "per-walker chemical potentials: semigrand Metropolis variants");
     static_assert(!(WLT && BIAS), "Cannot apply bias to Wang-Landau simulation (wanglandau.py:127-128)");
     static_assert(!(WLT && REPLAY), "Wang-Landau TableFlip replays take the universal kernel");
     constexpr bool has_ew = EWM != 0, ew_field = EWM == 2;
@@ -1277,7 +1292,11 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
     const int swa = P.swz_a, swm = P.swz_m, swb = P.swz_b;
     const bool has_mu = P.mu_row != nullptr;
     for (int i = threadIdx.x; i < P.dt_len; i += blockDim.x) s_dt[i] = P.dt[i];
-    if (threadIdx.x < 8) s_mu[threadIdx.x] = (has_mu && threadIdx.x < P.ncodes) ? P.mu_row[threadIdx.x] : 0.0;
+    if (!WMU && threadIdx.x < 8) s_mu[threadIdx.x] = (has_mu && threadIdx.x < P.ncodes) ? P.mu_row[threadIdx.x] : 0.0;
+    if (WMU) {
+        s_mu = (double *)(smem + P.mu_cell_off) + uni(wave * 8);
+        if (lane < 8 && r < P.R) s_mu[lane] = lane < P.ncodes ? P.mu_row[(size_t)r * 8 + lane] : 0.0;
+    }
     if (ew_field && threadIdx.x < 8) {
         s_q[threadIdx.x] = P.ew_qrow[threadIdx.x];
         s_dg[threadIdx.x] = P.ew_dgrow[threadIdx.x];
@@ -2372,10 +2391,11 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
 // mc_lean_kernel's template arguments after NSLOT, MM, STEP, as the flags of a variant word
 enum : unsigned {
     LV_EW = 3, // (the Ewald mode itself: 0 absent, 1 the field in LDS, 2 in HBM)
-    LV_MU = 4, LV_WL = 8, LV_BIAS = 16, LV_SOLO = 32, LV_KF = 64 /* KF = SMOLMC_LEAN_MAX_KF */, LV_OCC6 = 128, LV_REPLAY = 256
+    LV_MU = 4, LV_WL = 8, LV_BIAS = 16, LV_SOLO = 32, LV_KF = 64 /* KF = SMOLMC_LEAN_MAX_KF */, LV_OCC6 = 128, LV_REPLAY = 256,
+    LV_WMU = 512 // per-walker chemical potentials (bit 2 of the kernel's EWX)
 };
 template <int NSLOT, int MM, int STEP, unsigned V> static auto lean_variant() {
-    return mc_lean_kernel<NSLOT, MM, STEP, bool(V & LV_MU), int(V & LV_EW), bool(V & LV_WL), bool(V & LV_BIAS), bool(V & LV_SOLO),
+    return mc_lean_kernel<NSLOT, MM, STEP, bool(V & LV_MU), int(V & LV_EW) | ((V & LV_WMU) ? 4 : 0), bool(V & LV_WL), bool(V & LV_BIAS), bool(V & LV_SOLO),
                           (V & LV_KF) ? SMOLMC_LEAN_MAX_KF : 0, (V & LV_OCC6) ? 6 : 0, bool(V & LV_REPLAY)>;
 }
 // the runtime key of a lean handle: chemical potentials, Ewald mode, and -- where the family has them (SOLO) --
@@ -2392,7 +2412,7 @@ static int launch_lean_variant(smolmc_handle *h, const LeanParams &lp, unsigned 
     return first_match<Vs...>(key, [&](auto v) {
         constexpr bool SOLO = v & LV_SOLO; // (Metropolis without Ewald: one wave per workgroup, see mc_lean_kernel)
         return launch_timed(h, lean_variant<NSLOT, MM, STEP, v>(), dim3(SOLO ? (unsigned)h->R : (unsigned)((h->R + 3) / 4)),
-                            dim3(SOLO ? 64 : 256), h->lean_lds, lp);
+                            dim3(SOLO ? 64 : 256), h->lean_lds + walker_mu_lds(lp, SOLO ? 1 : 4), lp);
     });
 }
 // the families whose variants are (mu, Ewald mode) alone; B: the flags the family fixes
@@ -2407,16 +2427,17 @@ template <int NSLOT> static int launch_lean_bias_replay_nslot(smolmc_handle *h, 
 template <int NSLOT> static int launch_lean_corr_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_lean_mu_ew<NSLOT, LV_KF>(h, lp); }
 
 // mc_table_kernel's template arguments after NSLOT, MM and the Ewald mode (shared with mc_table_multi_kernel)
-enum : unsigned { TV_REPLAY = 1, TV_BIAS = 2, TV_WL = 4 };
+enum : unsigned { TV_REPLAY = 1, TV_BIAS = 2, TV_WL = 4, TV_WMU = 8 /* per-walker chemical potentials: bit 2 of the kernel's EWX */ };
 // (T = 0 in lean_n*.hip; TV_WL, TV_BIAS, TV_REPLAY in table_wl_n*.hip, table_bias_n*.hip, table_replay_n*.hip only)
 template <int NSLOT, unsigned T> static int launch_table_nslot(smolmc_handle *h, const LeanParams &lp) {
     const int wpb = h->lean_wpb;
-    const size_t lds = wpb == 8 ? h->lean_lds_wpb8 : h->lean_lds;
+    const size_t lds = (wpb == 8 ? h->lean_lds_wpb8 : h->lean_lds) + walker_mu_lds(lp, wpb);
     const dim3 grid((unsigned)((h->R + wpb - 1) / wpb)), block(64 * wpb);
     const int ewm = lp.ew_G == nullptr ? 0 : ((T & TV_WL) || lp.ew_field) ? 2 : 1; // (Wang-Landau: the Ewald term from the field only)
     return first_match<2, 3>(h->lean_mm, [&](auto mm) {
         auto launch = [&](auto ew) {
-            return launch_timed(h, mc_table_kernel<NSLOT, mm, ew, bool(T & TV_REPLAY), bool(T & TV_BIAS), bool(T & TV_WL)>, grid, block, lds, lp);
+            constexpr int ewx = decltype(ew)::value | ((T & TV_WMU) ? 4 : 0);
+            return launch_timed(h, mc_table_kernel<NSLOT, mm, ewx, bool(T & TV_REPLAY), bool(T & TV_BIAS), bool(T & TV_WL)>, grid, block, lds, lp);
         };
         if constexpr (T & TV_WL) return first_match<0, 2>(ewm, launch);
         else return first_match<0, 2, 1>(ewm, launch);
@@ -2437,6 +2458,25 @@ template <int NSLOT> static int launch_lean_nslot(smolmc_handle *h, const LeanPa
                                    LV_MU | LV_SOLO, LV_SOLO, LV_MU, 0>(h, lp, key);
     });
 }
+
+// per-walker chemical potentials (instantiated in lean_wmu_n*.hip only): the variants WITH mu of the plain family in
+// its layouts, of the biased and the KF family, and the TableFlip kernels; F: the flags the family fixes
+template <int NSLOT> static int launch_lean_wmu_nslot(smolmc_handle *h, const LeanParams &lp) {
+    if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) return launch_table_nslot<NSLOT, TV_WMU>(h, lp);
+    constexpr unsigned B = LV_WMU | LV_MU;
+    return with_mm_step(h, [&](auto mm, auto step) {
+        return launch_lean_variant<NSLOT, mm, step, B | 2, B | 1, B | LV_SOLO | LV_OCC6, B | LV_SOLO, B>(h, lp, LV_WMU | lean_key(h, lp, true));
+    });
+}
+template <int NSLOT, unsigned F> static int launch_lean_wmu_mu_ew(smolmc_handle *h, const LeanParams &lp) {
+    constexpr unsigned B = F | LV_WMU | LV_MU;
+    return with_mm_step(h, [&](auto mm, auto step) {
+        return launch_lean_variant<NSLOT, mm, step, B | 2, B | 1, B>(h, lp, F | LV_WMU | lean_key(h, lp, false));
+    });
+}
+template <int NSLOT> static int launch_lean_bias_wmu_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_lean_wmu_mu_ew<NSLOT, LV_BIAS>(h, lp); }
+template <int NSLOT> static int launch_lean_corr_wmu_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_lean_wmu_mu_ew<NSLOT, LV_KF>(h, lp); }
+template <int NSLOT> static int launch_table_bias_wmu_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_nslot<NSLOT, TV_BIAS | TV_WMU>(h, lp); }
 
 // replay variants (instantiated in lean_replay_n*.hip only): the handle's own layout (SOLO or four
 // walkers per workgroup), Ewald mode and mu row; correlation features with several functions per

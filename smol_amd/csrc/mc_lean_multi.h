@@ -76,8 +76,13 @@ __device__ __noinline__ void wl_multi_row_swap(double *grows, double *crow, int 
 // several correlation functions per orbit (evaluator.pyx:211-265): the decision reads the slot's FOLDED table
 // E = sum_k coef_k ct_k as every other slot does; an accepted step reads the slot's K function tables (global memory,
 // LeanParams::dtk, at the table index the decision computed) and adds K feature deltas.
-template <int NSLOT, int MM, int STEP, bool HAS_MU, int EWM, bool ONE = false, bool BIAS = false, bool REPLAY = false, int WLK = 0>
+// EWX = EWM, + 4 (multi_wmu_n*.hip only): per-walker chemical potentials, the [4][8] rows of walker r in a cell of its
+// own wave (see mc_lean_kernel)
+template <int NSLOT, int MM, int STEP, bool HAS_MU, int EWX, bool ONE = false, bool BIAS = false, bool REPLAY = false, int WLK = 0>
 __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) {
+    constexpr int EWM = EWX & 3;
+    constexpr bool WMU = (EWX & 4) != 0;
+    static_assert(!WMU || (HAS_MU && !WLK && !REPLAY), "per-walker chemical potentials: semigrand Metropolis variants");
     static_assert(!(WLK && BIAS), "Cannot apply bias to Wang-Landau simulation (wanglandau.py:127-128)");
     constexpr bool KFW = WLK == 2;
     constexpr bool HAS_EW = EWM != 0;
@@ -116,9 +121,13 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
     const int swa = P.swz_a, swm = P.swz_m, swb = P.swz_b;
     for (int i = threadIdx.x; i < P.dt_len; i += blockDim.x) s_dt[i] = P.dt[i];
     if (threadIdx.x < 32) {
-        s_mu[threadIdx.x] = HAS_MU ? P.m_mu[threadIdx.x] : 0.0;
+        if (!WMU) s_mu[threadIdx.x] = HAS_MU ? P.m_mu[threadIdx.x] : 0.0;
         s_q[threadIdx.x] = HAS_EW ? P.m_q[threadIdx.x] : 0.0;
         s_dg[threadIdx.x] = HAS_EW ? P.m_dg[threadIdx.x] : 0.0;
+    }
+    if (WMU) {
+        s_mu = (double *)(smem + P.mu_cell_off) + uni(wave * 32);
+        if (lane < 32 && r < P.R) s_mu[lane] = P.m_mu[(size_t)r * 32 + lane];
     }
     for (int i = threadIdx.x; i < nrec; i += blockDim.x) {
         const LeanSlot sl = P.slots[i];
@@ -956,10 +965,11 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
 enum : unsigned {
     MV_EW = 3, // (the Ewald mode itself: 0 absent, 1 the field in LDS, 2 in HBM)
     MV_MU = 4, MV_REG = 8, MV_BIAS = 16, MV_REPLAY = 32,
-    MV_WL = 64, MV_WL_KF = 128 // (WLK 1 and 2: Wang-Landau, and with several correlation functions per orbit)
+    MV_WL = 64, MV_WL_KF = 128, // (WLK 1 and 2: Wang-Landau, and with several correlation functions per orbit)
+    MV_WMU = 256 // per-walker chemical potentials (bit 2 of the kernel's EWX)
 };
 template <int NSLOT, int MM, int STEP, unsigned V> static auto multi_variant() {
-    return mc_lean_multi_kernel<NSLOT, MM, STEP, bool(V & MV_MU), int(V & MV_EW), bool(V & MV_REG), bool(V & MV_BIAS), bool(V & MV_REPLAY),
+    return mc_lean_multi_kernel<NSLOT, MM, STEP, bool(V & MV_MU), int(V & MV_EW) | ((V & MV_WMU) ? 4 : 0), bool(V & MV_REG), bool(V & MV_BIAS), bool(V & MV_REPLAY),
                                 (V & MV_WL_KF) ? 2 : (V & MV_WL) ? 1 : 0>;
 }
 // Every family of this kernel has the same variants, (mu, Ewald mode), in the same order (the order of the
@@ -974,6 +984,20 @@ template <int NSLOT, unsigned B> static int launch_multi_variant(smolmc_handle *
             auto kern = (NSLOT == 8 && lp.m_ncls == 1) ? multi_variant<NSLOT, mm, step, v | (NSLOT == 8 ? MV_REG : 0)>()
                                                        : multi_variant<NSLOT, mm, step, v>();
             return launch_timed(h, kern, grid, block, h->lean_lds, lp);
+        });
+    });
+}
+// per-walker chemical potentials (multi_wmu_n*.hip only): the variants WITH mu, in the same order; B: MV_BIAS or nothing
+template <int NSLOT, unsigned F> static int launch_multi_wmu_variant(smolmc_handle *h, const LeanParams &lp) {
+    constexpr unsigned B = F | MV_WMU | MV_MU;
+    const unsigned wpb = (unsigned)h->waves_per_block_lean;
+    const dim3 grid((unsigned)((h->R + wpb - 1) / wpb)), block(64 * wpb);
+    const unsigned key = B | (lp.ew_field == 1 ? 1u : lp.ew_field == 2 ? 2u : 0u);
+    return with_mm_step(h, [&](auto mm, auto step) {
+        return first_match<B | 1, B | 2, B>(key, [&](auto v) {
+            auto kern = (NSLOT == 8 && lp.m_ncls == 1) ? multi_variant<NSLOT, mm, step, v | (NSLOT == 8 ? MV_REG : 0)>()
+                                                       : multi_variant<NSLOT, mm, step, v>();
+            return launch_timed(h, kern, grid, block, h->lean_lds + walker_mu_lds(lp, (int)wpb), lp);
         });
     });
 }
@@ -1002,8 +1026,12 @@ template <int NSLOT, unsigned B> static int launch_multi_wl_nslot(smolmc_handle 
 // state of mc_lean_multi_kernel's WLK variant in place of the accumulator cells.
 // BIAS (round 6; multi_table_bias_n*.hip): an MCBias term in the exponent (metropolis.py:43-44), one pair table per
 // sublattice and bias row, bias_pair[row][sublattice][old * 8 + new] (see mc_table_kernel).
-template <int NSLOT, int MM, int EWM, bool REPLAY = false, bool WLT = false, bool BIAS = false>
+// EWX = EWM, + 4: per-walker chemical potentials (see mc_lean_multi_kernel)
+template <int NSLOT, int MM, int EWX, bool REPLAY = false, bool WLT = false, bool BIAS = false>
 __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P) {
+    constexpr int EWM = EWX & 3;
+    constexpr bool WMU = (EWX & 4) != 0;
+    static_assert(!WMU || (!WLT && !REPLAY), "per-walker chemical potentials: semigrand Metropolis variants");
     static_assert(!(WLT && REPLAY), "Wang-Landau TableFlip replays take the universal kernel");
     static_assert(!(WLT && BIAS), "Cannot apply bias to Wang-Landau simulation (wanglandau.py:127-128)");
     static_assert(!(BIAS && REPLAY), "biased TableFlip replays take the universal kernel");
@@ -1048,9 +1076,13 @@ __global__ void __launch_bounds__(512) mc_table_multi_kernel(const LeanParams P)
     const int D = P.m_ndims;
     for (int i = threadIdx.x; i < P.dt_len; i += blockDim.x) s_dt[i] = P.dt[i];
     if (threadIdx.x < 32) {
-        s_mu[threadIdx.x] = has_mu ? P.m_mu[threadIdx.x] : 0.0;
+        if (!WMU) s_mu[threadIdx.x] = has_mu ? P.m_mu[threadIdx.x] : 0.0;
         s_q[threadIdx.x] = has_ew ? P.m_q[threadIdx.x] : 0.0;
         s_dg[threadIdx.x] = has_ew ? P.m_dg[threadIdx.x] : 0.0;
+    }
+    if (WMU) {
+        s_mu = (double *)(smem + P.mu_cell_off) + uni(wave * 32);
+        if (lane < 32 && r < P.R) s_mu[lane] = P.m_mu[(size_t)r * 32 + lane];
     }
     for (int i = threadIdx.x; i < 2 * P.tf_n; i += blockDim.x) s_tfw[i] = P.tf_w[i];
     for (int i = threadIdx.x; i < P.tf_n * D; i += blockDim.x) s_tf[i] = P.tf_table[i];
@@ -2157,14 +2189,21 @@ template <int NSLOT, unsigned T> static int launch_table_multi_nslot(smolmc_hand
     const int ewm = lp.ew_field == 1 || lp.ew_field == 2 ? lp.ew_field : 0;
     return first_match<2, 3>(h->lean_mm, [&](auto mm) {
         return first_match<2, 0, 1>(ewm, [&](auto ew) { // (code-object order, see launch.h)
-            return launch_timed(h, mc_table_multi_kernel<NSLOT, mm, ew, bool(T & TV_REPLAY), bool(T & TV_WL), bool(T & TV_BIAS)>, grid, block,
-                                h->lean_lds, lp);
+            constexpr int ewx = decltype(ew)::value | ((T & TV_WMU) ? 4 : 0);
+            return launch_timed(h, mc_table_multi_kernel<NSLOT, mm, ewx, bool(T & TV_REPLAY), bool(T & TV_WL), bool(T & TV_BIAS)>, grid, block,
+                                h->lean_lds + walker_mu_lds(lp, (int)wpb), lp);
         });
     });
 }
 template <int NSLOT> static int launch_table_multi_bias_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_multi_nslot<NSLOT, TV_BIAS>(h, lp); }
 template <int NSLOT> static int launch_table_multi_wl_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_multi_nslot<NSLOT, TV_WL>(h, lp); }
 template <int NSLOT> static int launch_table_multi_replay_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_multi_nslot<NSLOT, TV_REPLAY>(h, lp); }
+template <int NSLOT> static int launch_multi_wmu_nslot(smolmc_handle *h, const LeanParams &lp) {
+    if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) return launch_table_multi_nslot<NSLOT, TV_WMU>(h, lp);
+    return launch_multi_wmu_variant<NSLOT, 0>(h, lp);
+}
+template <int NSLOT> static int launch_multi_bias_wmu_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_multi_wmu_variant<NSLOT, MV_BIAS>(h, lp); }
+template <int NSLOT> static int launch_table_multi_bias_wmu_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_table_multi_nslot<NSLOT, TV_BIAS | TV_WMU>(h, lp); }
 template <int NSLOT> static int launch_multi_nslot(smolmc_handle *h, const LeanParams &lp) {
     if (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP) return launch_table_multi_nslot<NSLOT, 0>(h, lp);
     return launch_multi_variant<NSLOT, 0>(h, lp);

@@ -534,7 +534,7 @@ struct LeanParams {
     const uint32_t *idx32; // the same entries as 32-bit words (one-wave-per-workgroup layout)
     const double *dt;      // delta tables, all padded to a common [S*S][NTP] shape
     const LeanSlot *slots; // [NSLOT][64]
-    const double *mu_row;  // [ncodes] chemical potentials of the active sublattice (or null)
+    const double *mu_row;  // [ncodes] chemical potentials of the active sublattice (or null); with mu_stride: row r * mu_stride
     // MCBias on the single active sublattice: bias_pair[old * 8 + new] = log(f_new / f_old)
     // (FugacityBias) or q_new - q_old (SquareChargeBias); running bias / net charge per walker.
     // mc_lean_multi_kernel: one such table per sublattice, bias_pair[sub * 64 + old * 8 + new].
@@ -570,6 +570,11 @@ struct LeanParams {
     SampleBufs smp;
     // compact Ewald term (see build_compact_ewald); feature index Fce, coefficient ew_coef
     int ew_W, ew_nact, ew_act_base;
+    // (in the padding behind ew_act_base, and mu_cell_off in that behind ew_field: no other offset of this block moves)
+    // per-walker chemical potentials (smolmc_set_walker_mu): walker r reads its row -- [8] at mu_row, [4][8] at m_mu --
+    // mu_stride doubles behind walker r - 1's, into a cell of its own wave, mu_cell_off bytes into the workgroup's LDS
+    // (behind everything else, wave w's cell w * mu_stride doubles further).  0: one row for all, in the shared cell.
+    int mu_stride;
     const int *ew_act;
     const double *ew_G, *ew_qs, *ew_dg, *ew_frozen;
     double ew_coef;
@@ -577,6 +582,7 @@ struct LeanParams {
     // lives in LDS for the launch (HBM copy between launches): a proposal costs O(1), an
     // accepted flip one row update
     int ew_field;
+    uint32_t mu_cell_off;    // (see mu_stride)
     double *ew_phi;          // [R][ew_nact]  (includes the frozen-site sums)
     const double *ew_qrow, *ew_dgrow; // [8] charge / diagonal term per species code (field mode:
                                       // identical for every active site, checked at create)
@@ -611,6 +617,10 @@ struct LeanParams {
 };
 
 __device__ __forceinline__ int lean_swz(int s, int a, int m, int b) { return s ^ (((s >> a) & m) << b); }
+// LDS the per-wave chemical-potential cells of a launch with `waves` waves per workgroup add behind lds (see mu_stride)
+// (+ 8: the cells start at the next multiple of 8 bytes)
+static inline size_t walker_mu_lds(int mu_stride, int waves) { return mu_stride ? (size_t)waves * (size_t)mu_stride * 8 + 8 : 0; }
+static inline size_t walker_mu_lds(const LeanParams &lp, int waves) { return walker_mu_lds(lp.mu_stride, waves); }
 
 
 struct RefTables { // device copies of the smolmc_tables arrays
@@ -770,6 +780,14 @@ struct smolmc_handle {
     std::vector<int> site_class_host;   // site -> class (255 = no clusters)
     size_t lean_lds = 0;
     LeanParams lp;
+    // per-walker chemical potentials (smolmc_set_walker_mu, engine.hip): the rows in the caller's layout while they are
+    // set, two device copies in the kernels' layout (the one in use and the one the next call fills), the row the
+    // handle was created with, and what the float32 accept bound is rebuilt from at every call
+    std::vector<double> walker_mu;
+    double *d_walker_mu[2] = {nullptr, nullptr};
+    const double *d_mu_create = nullptr;
+    double mu_max = 0.0, mu_max_create = 0.0, fast_eps_plain = 0.0;
+    int fast_eps_widenings = 1;
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
     SampleSlot slots[2];
@@ -863,6 +881,10 @@ __device__ __forceinline__ LeanParamsKernarg rare_params() {
     return p;
 }
 #endif
+// walker_mu.hip: chemical work and enthalpy of every walker from rows_old to rows_new ([R][stride], stride 0: one row for
+// all; the chemical work is features[r * F + F - 1]; enthalpy may be null), queued on the handle's stream
+int smolmc_walker_mu_reprice(smolmc_handle *h, const double *rows_old, int stride_old, const double *rows_new, int stride_new,
+                             double *features, int F, double *enthalpy);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);
 int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_4(smolmc_handle *h, const KParams &kp, int replay);
@@ -882,6 +904,9 @@ SMOLMC_LAUNCHERS3(multi) SMOLMC_LAUNCHERS3(multi_replay) SMOLMC_LAUNCHERS3(multi
 SMOLMC_LAUNCHERS3(multi_bias) SMOLMC_LAUNCHERS3(multi_bias_replay)
 SMOLMC_LAUNCHERS3(multi_wl) SMOLMC_LAUNCHERS3(multi_wl_replay) SMOLMC_LAUNCHERS3(multi_wl_kf)
 SMOLMC_LAUNCHERS3(multi_table_bias) SMOLMC_LAUNCHERS3(multi_table_wl)
+// per-walker chemical potentials (lean_wmu_n*.hip, multi_wmu_n*.hip)
+SMOLMC_LAUNCHERS2(lean_wmu) SMOLMC_LAUNCHERS2(lean_bias_wmu) SMOLMC_LAUNCHERS2(lean_corr_wmu) SMOLMC_LAUNCHERS2(table_bias_wmu)
+SMOLMC_LAUNCHERS3(multi_wmu) SMOLMC_LAUNCHERS3(multi_bias_wmu) SMOLMC_LAUNCHERS3(multi_table_bias_wmu)
 #undef SMOLMC_LAUNCHERS2
 #undef SMOLMC_LAUNCHERS3
 #define SMOLMC_WL_ROWS 32  // mc_wl_kernel: cached rows of per-bin feature sums per walker (LDS)

@@ -33,6 +33,8 @@ SYMBOLS = {
     "smolmc_natural_parameters": (C.c_int, [_HP, _f64p]),
     "smolmc_set_state": (C.c_int, [_HP, _i32p, _u64p, _f64p, C.c_int]),
     "smolmc_set_temperature": (C.c_int, [_HP, _f64p]),
+    "smolmc_set_walker_mu": (C.c_int, [_HP, _f64p]),
+    "smolmc_get_walker_mu": (C.c_int, [_HP, _f64p]),
     "smolmc_get_state": (C.c_int, [_HP, _i32p, _f64p, _f64p, _u64p, _u64p, _u8p]),
     "smolmc_get_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
     "smolmc_set_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
@@ -117,6 +119,19 @@ def _p(a, ct):
     return None if a is None else a.ctypes.data_as(C.POINTER(ct))
 
 
+def chemical_work(tables, occupancies, mu_rows):
+    """The chemical-work feature (the last one of a semigrand model) on the host: sum over the active sites of
+    mu[sublattice][species code], for occupancies (n, N) and rows (n, n_sublattices, mu_width) in the layout of
+    smolmc_set_walker_mu."""
+    occ = np.asarray(occupancies).reshape(-1, tables.struct.num_sites)
+    sites_of = tables.active_sites()
+    rows = np.asarray(mu_rows, dtype=np.float64).reshape(len(occ), len(sites_of), -1)
+    out = np.zeros(len(occ))
+    for k, sites in enumerate(sites_of):
+        out += np.take_along_axis(rows[:, k, :], occ[:, sites].astype(np.int64), axis=1).sum(axis=1)
+    return out
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -147,6 +162,7 @@ class Engine:
         self.N = tables.struct.num_sites
         self.F = self._lib.smolmc_num_features(self._h)
         self.L = self._lib.smolmc_wl_num_levels(self._h)
+        self.walker_mu_set = False  # per-walker chemical potentials in force (set_walker_mu)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -209,6 +225,35 @@ class Engine:
     def set_temperature(self, temperature):
         temp = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, float), (self.R,)))
         self._chk(self._lib.smolmc_set_temperature(self._h, _p(temp, C.c_double)))
+
+    # ---- per-walker chemical potentials ---------------------------------------------
+    def _mu_shape(self):
+        return (self.R, self.tables.struct.n_sublattices, self.tables.struct.mu_width)
+
+    def set_walker_mu(self, rows):
+        """Chemical potentials of every walker (smolmc_set_walker_mu): ``rows`` (R, n_sublattices, mu_width) -- the
+        active sublattices in the tables' order, the columns the species codes as in the tables' ``mu_table`` -- or
+        None for the table the handle was created with.  Chemical work and enthalpy of every walker are re-priced on
+        the device from its current occupancy; between two ``run`` calls this is a mu sweep."""
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.float64)
+            if rows.shape != self._mu_shape():
+                raise ValueError(f"expected chemical potentials of shape {self._mu_shape()} "
+                                 f"(walkers, active sublattices, mu_width), got {rows.shape}")
+        self._chk(self._lib.smolmc_set_walker_mu(self._h, _p(rows, C.c_double)))
+        self.walker_mu_set = rows is not None
+
+    def get_walker_mu(self):
+        """(R, n_sublattices, mu_width): the rows of the last ``set_walker_mu``, the create-time rows when none are set."""
+        out = np.zeros(self._mu_shape())
+        self._chk(self._lib.smolmc_get_walker_mu(self._h, _p(out, C.c_double)))
+        return out
+
+    def chemical_work(self, occupancies, mu_rows):
+        """The last feature of a semigrand handle, on the host: sum over the active sites of mu[sublattice][species
+        code] for occupancies (n, N) and rows (n, n_sublattices, mu_width) -- what ``set_walker_mu`` prices on the
+        device (``eval_full`` keeps the create-time table)."""
+        return chemical_work(self.tables, self._occ32(occupancies, (-1, self.N)), mu_rows)
 
     def get_state(self, occupancy=True):
         occ = np.empty((self.R, self.N), dtype=np.int32) if occupancy else None

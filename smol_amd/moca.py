@@ -704,6 +704,39 @@ class Ensemble:
         self._mu_table = table
         self.thermo_boundaries["chemical_potentials"] = value
 
+    def walker_chemical_potentials(self, values):
+        """Per-walker chemical potentials as a list of R dicts species -> value, from a sequence of R dicts or one
+        dict species -> array of length R; every dict is held to the species of the active sublattices as the
+        ``chemical_potentials`` setter holds its value."""
+        if isinstance(values, dict):
+            cols = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in values.items()}
+            lengths = {len(v) for v in cols.values()}
+            if len(lengths) != 1:
+                raise ValueError("per-walker chemical potentials: every species needs one value per walker")
+            values = [{k: v[r] for k, v in cols.items()} for r in range(lengths.pop())]
+        out = []
+        for value in values:
+            value = {k: float(v) for k, v in value.items() if k in self.species}
+            if set(value) != set(self.species):
+                raise ValueError(
+                    "Chemical potentials given are missing species. Values must be given for each of "
+                    f"the following: {self.species}"
+                )
+            out.append(value)
+        return out
+
+    def walker_mu_rows(self, values):
+        """Per-walker chemical potentials in the layout of ``Engine.set_walker_mu`` -- (R, active sublattices, columns
+        of the chemical-potential table) -- through the sublattices' species / encoding, the mapping the
+        ``chemical_potentials`` setter builds its table with."""
+        dicts = self.walker_chemical_potentials(values)
+        num_cols = max(max(s.encoding) for s in self._sublattices) + 1
+        act = self.active_sublattices
+        rows = np.zeros((len(dicts), len(act), num_cols))
+        for k, s in enumerate(act):
+            rows[:, k, s.encoding] = [[d[sp] for sp in s.species] for d in dicts]
+        return rows
+
     def restrict_sites(self, sites):
         for s in self._sublattices:
             s.restrict_sites(sites)
@@ -996,6 +1029,8 @@ class MCKernel:
                 table_ergodic=kwargs.get("table_ergodic", False),
             ).flip_table
         self._seed = seed if seed is not None else np.random.SeedSequence().entropy
+        # the walker's own chemical potentials (Sampler.set_chemical_potentials), else the ensemble's
+        self.chemical_potentials = ensemble.chemical_potentials
         self.spec = dict(kernel=self.__class__.__name__, seed=self._seed, step=step_type)
         self._bias = None
         if bias_type is not None:  # kernel/base.py:229-235
@@ -1404,8 +1439,23 @@ class SampleContainer:
     def to_npz(self, path):
         """Checkpoint (.npz stand-in for to_hdf5, container.py:615): one array per trace name +
         nsamples / total_mc_steps, like the HDF5 'trace' group."""
+        extra = {}
+        wmu = self.metadata.get("walker_chemical_potentials")
+        if wmu is not None:  # per-walker chemical potentials (Sampler.set_chemical_potentials)
+            extra = {"meta/walker_mu_species": np.array(wmu["species"]), "meta/walker_mu_values": np.asarray(wmu["values"], dtype=np.float64)}
         np.savez_compressed(path, nsamples=self.num_samples, total_mc_steps=self._total_steps,
-                            **{f"trace/{k}": v for k, v in self._all().items()})
+                            **{f"trace/{k}": v for k, v in self._all().items()}, **extra)
+
+    def get_chemical_potentials(self):
+        """(walkers, species of the active sublattices): the chemical potentials every walker was sampled at -- the
+        per-walker values of ``Sampler.set_chemical_potentials``, else the ensemble's for every walker."""
+        wmu = self.metadata.get("walker_chemical_potentials")
+        if wmu is not None:
+            return np.asarray(wmu["values"], dtype=np.float64)
+        mu = self._ensemble.chemical_potentials
+        if mu is None:
+            raise ValueError("the ensemble has no chemical potentials")
+        return np.tile([mu[sp] for sp in self._ensemble.species], (self.shape[0], 1))
 
     def get_sampled_species(self, indices, flat=True):
         """Species of every site for the samples ``indices`` -- what ``get_sampled_structures``
@@ -1493,6 +1543,9 @@ class SampleContainer:
         c = cls(ensemble, Trace(**{k: v[:0] for k, v in arrays.items()}))
         c.append_block(arrays, 0)
         c._total_steps = int(d["total_mc_steps"])
+        if "meta/walker_mu_values" in d.files:
+            c.metadata["walker_chemical_potentials"] = dict(species=[str(s) for s in d["meta/walker_mu_species"]],
+                                                            values=d["meta/walker_mu_values"].tolist())
         return c
 
 
@@ -1616,10 +1669,12 @@ class Sampler:
         self._state_loaded = False  # walker states uploaded to the engine at least once
         self._resume_at = None      # (container, its sample count) the device state equals, see _load_state
         self._kept_last = False     # the container holds the one sample a streamed run kept (keep_last_chunk)
+        self._walker_mu = None      # per-walker chemical potentials of this rank's walkers (list of dicts), or None
+        self._walker_mu_dirty = False  # ... not yet on the engine
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
-                      nwalkers=1, rank=None, world_size=None, device=None, **kwargs):
+                      nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
         'swap'; default kernel Metropolis; one kernel (seed) per walker."""
         from . import parallel
@@ -1642,7 +1697,52 @@ class Sampler:
         container.metadata["walker_range"] = (first, count, nwalkers)
         if device is None:
             device = parallel.local_device(rank)
-        return cls(kernels, container, walker_range=(first, count), device=device, world_size=world_size)
+        sampler = cls(kernels, container, walker_range=(first, count), device=device, world_size=world_size)
+        if chemical_potentials is not None:
+            sampler.set_chemical_potentials(chemical_potentials)
+        return sampler
+
+    @property
+    def walker_chemical_potentials(self):
+        """The chemical potentials of this rank's walkers (a list of dicts species -> value), None: the ensemble's."""
+        return self._walker_mu
+
+    def set_chemical_potentials(self, values):
+        """Per-walker chemical potentials: a mu-T grid in one engine handle.  ``values``: a sequence of dicts
+        species -> value or one dict species -> array, indexed by GLOBAL walker like seeds (or by this rank's
+        walkers), so walker g runs the same chain at any world size; None: the ensemble's own again.  The ensemble
+        must have chemical potentials (they are the table the handle is created with).  Between two ``run`` calls
+        this is a mu sweep: the walkers continue from their last samples, re-priced at their new values."""
+        ens = self._kernels[0].ensemble
+        if values is None:
+            self._walker_mu, self._walker_mu_dirty = None, self._walker_mu is not None
+            self.samples.metadata.pop("walker_chemical_potentials", None)
+            for k in self._kernels:
+                k.chemical_potentials = ens.chemical_potentials
+            return
+        if ens.chemical_potentials is None:
+            raise ValueError("per-walker chemical potentials need a semigrand ensemble: set ensemble.chemical_potentials first")
+        if not isinstance(self._kernels[0], Metropolis) or isinstance(self._kernels[0], WangLandau):
+            raise ValueError("per-walker chemical potentials run the Metropolis kernel only")
+        dicts = ens.walker_chemical_potentials(values)
+        first, count = self._walker_range
+        nglobal = self.samples.metadata.get("walker_range", (0, count, count))[2]
+        if len(dicts) == nglobal:
+            dicts = dicts[first:first + count]
+        elif len(dicts) != count:
+            raise ValueError(f"expected chemical potentials for {nglobal} walkers (or this rank's {count}), got {len(dicts)}")
+        self._walker_mu, self._walker_mu_dirty = dicts, True
+        for k, d in zip(self._kernels, dicts):
+            k.chemical_potentials = d
+        self.samples.metadata["walker_chemical_potentials"] = dict(
+            species=list(ens.species), values=[[d[sp] for sp in ens.species] for d in dicts])
+
+    def _apply_walker_mu(self, eng):
+        """The rows on the engine before its state is loaded or continued (a new handle starts without them)."""
+        if self._walker_mu_dirty:
+            ens = self._kernels[0].ensemble
+            eng.set_walker_mu(None if self._walker_mu is None else ens.walker_mu_rows(self._walker_mu))
+            self._walker_mu_dirty = False
 
     @staticmethod
     def _container_for(ensemble, k0, count):
@@ -1761,6 +1861,7 @@ class Sampler:
             self._engine = Engine(tables, cfg, distance=dist)
             self._engine_key = key
             self._state_loaded = False
+            self._walker_mu_dirty = self._walker_mu is not None
         return self._engine
 
     def _temperatures(self):
@@ -1795,6 +1896,7 @@ class Sampler:
         last run (the steps after the last sample of a run are never taken), so nothing is
         uploaded -- only the temperatures are refreshed (anneal changes them between runs)."""
         eng = self._get_engine()
+        self._apply_walker_mu(eng)
         if initial_occupancies is None:
             if self._state_loaded and self._resume_at == (id(self.samples), self.samples.num_samples):
                 eng.set_temperature(self._temperatures())

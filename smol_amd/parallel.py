@@ -266,6 +266,15 @@ def geometric_ladder(t_min, t_max, n):
     return np.geomspace(t_min, t_max, n)
 
 
+def _refuse_walker_mu(target):
+    """An exchange that permutes temperatures only is no valid move between walkers of different Hamiltonians: engines
+    and samplers with per-walker chemical potentials are refused."""
+    eng = getattr(target, "_engine", target)  # (a moca.Sampler, or an Engine)
+    if getattr(target, "walker_chemical_potentials", None) is not None or getattr(eng, "walker_mu_set", False):
+        raise ValueError("replica exchange with per-walker chemical potentials: an exchange of temperatures alone is "
+                         "no valid move between walkers of different Hamiltonians")
+
+
 def run_replica_exchange(engine, rex, n_exchanges, steps_between, device=None, collective=None, device_decide=None):
     """Alternate ``steps_between`` MC steps on every walker with one exchange attempt.
 
@@ -285,6 +294,7 @@ def run_replica_exchange(engine, rex, n_exchanges, steps_between, device=None, c
     `attempted` / `accepted` are brought back when read (`rex.sync_from_device()`)."""
     import os
 
+    _refuse_walker_mu(engine)
     if device_decide is None:
         device_decide = os.environ.get("SMOLMC_REX_DEVICE_DECIDE") == "1"
     dist = _dist()

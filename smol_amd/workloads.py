@@ -317,5 +317,31 @@ def config13(**kw):
     return w
 
 
+CONFIG14_NMU = 64                      # chemical-potential points of config 14's grid (the walkers' fastest index)
+CONFIG14_T = (20000.0, 80000.0)        # its temperatures, geometric (config 3's 40000 K in the middle)
+CONFIG14_DMU = 2.0                     # mu(Mn3+) runs from -DMU to +DMU eV around the frozen draw
+
+
+def config14(first=0, count=2048, dim=12, mc=2000, total=None):
+    """(not in BASELINE.json) config 3 as a T x mu grid in ONE handle (smolmc_set_walker_mu): global walker g sits at
+    temperature g // 64 of a geometric ladder and at chemical potentials = the frozen CONFIG3_MU draw with mu(Mn3+)
+    shifted by point g % 64 of linspace(-2, 2, 64) eV.  ``extras['walker_mu']`` are this rank's rows in the layout
+    of Engine.set_walker_mu; the handle is created with the draw itself."""
+    w = config3(first=first, count=count, dim=dim, mc=mc)
+    total = total or count
+    if total % CONFIG14_NMU:
+        raise ValueError(f"config 14 wants a multiple of {CONFIG14_NMU} walkers")
+    g = np.arange(first, first + count)
+    ladder = np.geomspace(CONFIG14_T[0], CONFIG14_T[1], total // CONFIG14_NMU)
+    base = _mu_rows(w.sc, CONFIG3_MU)[0]
+    rows = np.repeat(base[None, None, :], count, axis=0)
+    rows[:, 0, 1] += np.linspace(-CONFIG14_DMU, CONFIG14_DMU, CONFIG14_NMU)[g % CONFIG14_NMU]
+    w.key, w.temperature = 14, ladder[g // CONFIG14_NMU].copy()
+    w.name = (f"config14: config 3 as a {len(ladder)} T x {CONFIG14_NMU} mu grid in one handle (per-walker chemical potentials), "
+              f"T={CONFIG14_T[0]:g}-{CONFIG14_T[1]:g}K, mu(Mn3+) +-{CONFIG14_DMU:g} eV")
+    w.extras.update(walker_mu=rows, grid=(len(ladder), CONFIG14_NMU))
+    return w
+
+
 BUILDERS = {1: config1, 2: config2, 3: config3, 4: config4, 5: config5, 6: config6, 7: config7,
-            8: config8, 9: config9, 10: config10, 11: config11, 12: config12, 13: config13}
+            8: config8, 9: config9, 10: config10, 11: config11, 12: config12, 13: config13, 14: config14}

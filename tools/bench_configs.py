@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--ladder", default="", help="config 5: lowest,highest temperature of the exchange ladder")
     ap.add_argument("--sampled", type=int, default=0, help="also time blocks of the device ring with this thin_by (wall clock, "
                                                             "features recorded, no occupancies): what lazy cluster features cost")
+    ap.add_argument("--uniform-rows", action="store_true", help="semigrand configs: give every walker a copy of the handle's own "
+                                                                "chemical potentials through set_walker_mu (same chains, the per-walker kernels)")
     a = ap.parse_args()
     kw = {}
     if a.ladder:
@@ -49,6 +51,10 @@ def main():
         probe.close()
         wl = workloads.BUILDERS[a.config](h0=h0, **kw)
     eng = Engine(wl.tables, wl.make_config())
+    if "walker_mu" in wl.extras:  # config 14: a T x mu grid in one handle
+        eng.set_walker_mu(wl.extras["walker_mu"])
+    elif a.uniform_rows:
+        eng.set_walker_mu(eng.get_walker_mu())
     T = a.temperature if a.temperature > 0 else wl.temperature
     eng.set_state(wl.occupancy, wl.seeds, T)
     R, mc = wl.n_walkers, wl.mc_per_launch
