@@ -786,6 +786,57 @@ static LeanDeltaTables lean_delta_tables(const smolmc_tables *t, const SiteClass
     return L;
 }
 
+// ---- solo rows (mc_lean.h: ROWS): per-slot gather widths, index rows in LDS-address order
+// The clusters of a site, sorted by gathered members (most first, stable), fill the two slots of a solo handle; a slot
+// then gathers what its widest lane needs.  Taken when that is two members in slot 0 and one in slot 1 (shape 21:
+// triplets that fit one slot beside pairs) or one in both (11: pairs only); anything else keeps the plain solo kernel.
+// (site_slots already lists a site's clusters with most gathered members first, so on tables built here the
+// permutation is the identity; it is derived from the slot records all the same, so that the rows do not depend on it.)
+struct SoloRowsPlan {
+    int shape = 0;                // the kernel's MM: 21, 11, or 0 (not taken)
+    int row_len = 0;              // entries per lane of a row
+    std::vector<int> perm;        // position (slot * 64 + lane) in the new order -> position in the lean row
+    std::vector<uint32_t> rows;   // [Nlds][64][row_len]: the row of site s at lean_swz(s); other addresses: self-references
+    std::vector<LeanSlot> slots;  // [2][64]: the slot records in the new order
+};
+// lidx: the lean rows [N][64][NSL][MML], entries swizzled; ls: the slot records [NSL][64] of the one site class
+static SoloRowsPlan solo_rows_plan(const std::vector<uint16_t> &lidx, const LeanSlot *ls, int N, int NSL, int MML, const Swizzle &w) {
+    SoloRowsPlan p;
+    if (NSL != 2 || MML != 2 || w.Nlds < N || lidx.size() != (size_t)N * 64 * NSL * MML) return p;
+    const int NQ = 64 * NSL;
+    // gathered members of a position: its strides (padded positions and the point cluster have none)
+    int nm[128];
+    for (int q = 0; q < NQ; ++q) {
+        nm[q] = 0;
+        for (int m = 0; m < MML; ++m)
+            if (ls[q].live && ls[q].stride8[m]) nm[q] = m + 1;
+    }
+    p.perm.resize(NQ);
+    for (int q = 0; q < NQ; ++q) p.perm[q] = q;
+    std::stable_sort(p.perm.begin(), p.perm.end(), [&](int a, int b) { return nm[a] > nm[b]; });
+    const int mm0 = nm[p.perm[0]], mm1 = nm[p.perm[64]]; // (sorted: a slot's first lane is its widest)
+    if (mm0 > 2 || mm1 > 1) return p;
+    const int w0 = mm0 == 2 ? 2 : 1;
+    p.shape = w0 * 10 + 1;
+    p.row_len = w0 + 1;
+    const int RL = p.row_len, width[2] = {w0, 1}, off[2] = {0, w0};
+    p.slots.resize(NQ);
+    for (int q = 0; q < NQ; ++q) p.slots[q] = ls[p.perm[q]];
+    p.rows.resize((size_t)w.Nlds * 64 * RL);
+    for (int a = 0; a < w.Nlds; ++a)
+        for (int k = 0; k < 64 * RL; ++k) p.rows[(size_t)a * 64 * RL + k] = (uint32_t)a;
+    for (int s = 0; s < N; ++s) {
+        const int a = s ^ (((s >> w.a) & w.m) << w.b);
+        for (int q = 0; q < NQ; ++q) {
+            const int it = q / 64, ln = q % 64, oit = p.perm[q] / 64, oln = p.perm[q] % 64;
+            // (a lane with fewer members than its slot gathers keeps the lean row's padding: the site itself, stride 0)
+            for (int m = 0; m < width[it]; ++m)
+                p.rows[((size_t)a * 64 + ln) * RL + off[it] + m] = lidx[(((size_t)s * 64 + oln) * NSL + oit) * MML + m];
+        }
+    }
+    return p;
+}
+
 // The lean tables are taken: the one place that writes them to the handle and the device
 static int commit_lean_tables(smolmc_handle *h, const smolmc_tables *t, const SiteClasses &sc, const LeanMode &mode, int NSL, int MML,
                               const Swizzle &w, std::vector<uint16_t> &lidx, const LeanDeltaTables &L) {
@@ -801,6 +852,7 @@ static int commit_lean_tables(smolmc_handle *h, const smolmc_tables *t, const Si
     TRY(dev_upload(h, L.dt.data(), L.dt.size(), &lp.dt));
     if (mode.corr_kf) TRY(dev_upload(h, L.dtk.data(), L.dtk.size(), &lp.dtk));
     TRY(dev_upload(h, L.ls.data(), L.ls.size(), &lp.slots));
+    h->lean_slots_host = L.ls;
     lp.dt_len = (int)L.dt.size();
     h->lean_kf = mode.corr_kf ? SMOLMC_LEAN_MAX_KF : 0;
     h->lazy_tables = mode.lazy();
@@ -1257,6 +1309,54 @@ extern "C" void *smolmc_debug_relabel(const smolmc_tables *t, int32_t *new_of_ou
 }
 extern "C" void smolmc_debug_relabel_free(void *p) { delete (RelabelledTables *)p; }
 
+// ... and the solo rows plan (solo_rows_plan) of a Metropolis handle on these tables, from the lean tables as
+// build_mc_tables makes them.  Host code only (tests/test_solo_rows_host.py).  The leading members are plain data a
+// ctypes.Structure mirrors; shape 0: the tables get no lean rows, or the clusters fall into neither shape.
+struct SoloRowsDebug {
+    int shape, row_len, N, Nlds, swz_a, swz_m, swz_b, nslot, mm;
+    const int *perm;             // [64 * nslot]
+    const uint32_t *rows;        // [Nlds][64][row_len]
+    const LeanSlot *slots;       // [nslot][64], new order
+    const uint16_t *lean_rows;   // [N][64][nslot][mm], swizzled: what lp.idx holds
+    const LeanSlot *lean_slots;  // [nslot][64]: what lp.slots holds
+    SoloRowsPlan plan;
+    std::vector<uint16_t> lidx;
+    std::vector<LeanSlot> ls;
+};
+// (smolmc_debug_solo_rows) the lean tables of build_mc_tables without a device, and the solo rows plan on them
+static void build_mc_tables_host(const smolmc_tables *t, const smolmc_config *cfg, SoloRowsDebug &d) {
+    smolmc_handle h; // (never reaches a device: the planners below read its configuration only)
+    h.cfg = *cfg;
+    h.Npad = (t->num_sites + 15) / 16 * 16;
+    d.N = t->num_sites;
+    const GeneralLimits lim = general_limits(t, h.Npad);
+    if (lim.error || lim.universal) return;
+    const SiteClasses sc = site_classes(t, lim);
+    if (sc.universal) return;
+    const LeanMode mode = lean_mode(&h, t, lim, sc);
+    if (*mode.reason || mode.corr_kf) return;
+    const int NSL = sc.niter_max <= 2 ? 2 : (sc.niter_max <= 4 ? 4 : 8), MML = sc.lean_need_mm <= 2 ? 2 : 3;
+    d.nslot = NSL; d.mm = MML;
+    d.lidx = lean_index_rows(t, sc, NSL, MML);
+    const Swizzle w = choose_swizzle(d.lidx, sc, t->num_sites, h.Npad, NSL * MML);
+    for (uint16_t &x : d.lidx) x = (uint16_t)(x ^ (((x >> w.a) & w.m) << w.b));
+    d.Nlds = w.Nlds; d.swz_a = w.a; d.swz_m = w.m; d.swz_b = w.b;
+    const LeanDeltaTables L = lean_delta_tables(t, sc, mode, NSL, MML);
+    if (L.too_large) return;
+    d.ls = L.ls;
+    if (sc.class_rep.size() == 1) d.plan = solo_rows_plan(d.lidx, d.ls.data(), t->num_sites, NSL, MML, w);
+}
+extern "C" void *smolmc_debug_solo_rows(const smolmc_tables *t, const smolmc_config *cfg) {
+    if (!t || !cfg || validate_tables(t)) return nullptr;
+    SoloRowsDebug *d = new SoloRowsDebug();
+    build_mc_tables_host(t, cfg, *d);
+    d->shape = d->plan.shape; d->row_len = d->plan.row_len;
+    d->perm = d->plan.perm.data(); d->rows = d->plan.rows.data(); d->slots = d->plan.slots.data();
+    d->lean_rows = d->lidx.data(); d->lean_slots = d->ls.data();
+    return d;
+}
+extern "C" void smolmc_debug_solo_rows_free(void *p) { delete (SoloRowsDebug *)p; }
+
 extern "C" int smolmc_create(const smolmc_tables *t, const smolmc_config *cfg, smolmc_handle **out) {
     if (!t || !cfg || !out) return fail("null argument");
     if (cfg->n_replicas <= 0) return fail("n_replicas must be positive");
@@ -1647,6 +1747,7 @@ struct LeanPlan {
     bool solo = false;
     int occ = 0, wpb = 4, tf_ln_len = 0;
     size_t lds = 0, lds8 = 0;
+    SoloRowsPlan rows;  // solo: the rows variant, where the site's clusters fall into one of its shapes
 };
 static LeanPlan decide_lean(const smolmc_handle *h, const smolmc_tables *t) {
     const smolmc_config *cfg = &h->cfg;
@@ -1726,6 +1827,10 @@ static LeanPlan decide_lean(const smolmc_handle *h, const smolmc_tables *t) {
             if ((long)cfg->n_replicas > 16L * cu_count(h) && solo_lds * 24 <= 160 * 1024 - 24 * 256 &&
                 !smolmc_env(ENV_NO_OCC6))
                 p.occ = 6;
+            // (SMOLMC_NO_SOLO_ROWS: A/B switch, keeps the handle on the plain solo kernel)
+            if (!smolmc_env(ENV_NO_SOLO_ROWS))
+                p.rows = solo_rows_plan(h->lean_idx_host, h->lean_slots_host.data(), t->num_sites, h->lean_nslot, h->lean_mm,
+                                        Swizzle{lp.swz_a, lp.swz_m, lp.swz_b, lp.Nlds});
         }
     }
     if (table) {
@@ -1776,11 +1881,15 @@ static int plan_lean(smolmc_handle *h, const smolmc_tables *t, LeanPlan &p) {
     if (p.solo) {
         std::vector<uint32_t> wide(h->lean_idx_host.begin(), h->lean_idx_host.end());
         if (dev_upload(h, wide.data(), wide.size(), &lp.idx32)) return 1;
+        if (p.rows.shape && (dev_upload(h, p.rows.rows.data(), p.rows.rows.size(), &h->d_rows_idx32) ||
+                             dev_upload(h, p.rows.slots.data(), p.rows.slots.size(), &h->d_rows_slots)))
+            return 1;
     }
     if (is_table(h) && lean_fill_table(h, t, lp, p.nc, p.nact, p.tf_ln_len)) return 1;
     h->lean_lds = p.lds;
     h->lean_solo = p.solo;
     h->lean_occ = p.occ;
+    h->solo_rows = p.solo ? p.rows.shape : 0;
     h->lean_wpb = p.wpb;
     h->lean_lds_wpb8 = p.lds8;
     return 0;
@@ -2166,6 +2275,9 @@ static LeanLauncher lean_launcher(const smolmc_handle *h, bool replay) {
     const LeanFamilyRow &row = lean_families[h->family - K_LEAN];
     const int i = h->lean_nslot == 2 ? 0 : (h->lean_nslot == 4 ? 1 : 2);
     if (!replay && h->lp.mu_stride) return row.walker_mu[i];
+    // (the solo rows variants: runs of the plain family's solo handles whose clusters fall into one of their shapes;
+    // replays and per-walker chemical potentials stay on the kernels above, which read the site-ordered rows)
+    if (!replay && h->family == K_LEAN && h->solo_rows && h->lean_nslot == 2) return smolmc_launch_lean_rows_2;
     return !replay ? row.run[i] : (h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP ? row.table_replay[i] : row.replay[i]);
 }
 
@@ -2621,10 +2733,14 @@ extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
     if (h->univ())
         snprintf(buf, (size_t)n, "universal occ=%s field=%d lds=%zu (%s)", h->up.occ_lds ? "lds" : "hbm", h->kp.ew_field,
                  (size_t)h->up.lds_shared + (size_t)h->up.lds_per_wave * h->univ_wpb, h->general_ok ? "TableFlip outside the lean families" : h->general_reason.c_str());
-    else if (row)
+    else if (row) {
         snprintf(buf, (size_t)n, "%s nslot=%d mm=%d field=%d lds=%zu%s", row->name,
                  h->lean_nslot, h->lean_mm, h->lp.ew_field, h->lean_lds,
                  h->lean_solo ? (h->lean_occ ? " solo=1 occ=6" : " solo=1") : (h->lean_kf ? " kf=1" : ""));
+        // (the solo rows variants; not while per-walker chemical potentials keep the handle on the plain solo kernel)
+        if (h->family == K_LEAN && h->solo_rows && !h->lp.mu_stride && strlen(buf) + 12 < (size_t)n)
+            snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " rows=%d", h->solo_rows);
+    }
     else
         snprintf(buf, (size_t)n, "general nslot=%d mm=%d field=%d lds=%zu", h->nslot, h->mm, h->kp.ew_field,
                  h->lds_bytes);

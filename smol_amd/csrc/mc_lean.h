@@ -337,6 +337,15 @@ template <bool ABS> __device__ __forceinline__ void occ_st(uint8_t *occ, uint32_
     else occ[a] = v;
 }
 
+// Solo ROWS variants (lean_rows_n2.hip): MM >= 10 spells the gathered members of EACH slot as decimal digits, slot 0
+// first -- MM = 21: two members in slot 0, one in slot 1; MM = 11: one in both.  A lane's index row then holds
+// lean_row_len entries, slot it's at lean_row_off.  Plain MM: every slot gathers MM members.
+constexpr bool lean_rows(int MM) { return MM >= 10; }
+constexpr int lean_mm_of(int MM, int it) { return !lean_rows(MM) ? MM : (it == 0 ? MM / 10 : MM % 10); }
+constexpr int lean_mm_max(int MM) { return !lean_rows(MM) ? MM : (MM / 10 > MM % 10 ? MM / 10 : MM % 10); }
+constexpr int lean_row_off(int MM, int it) { return !lean_rows(MM) ? it * MM : (it == 0 ? 0 : MM / 10); }
+constexpr int lean_row_len(int MM, int NSLOT) { return !lean_rows(MM) ? NSLOT * MM : MM / 10 + MM % 10; }
+
 // SOLO: one wave per workgroup with the walker's occupancy at LDS address 0 and the block-shared
 // tables behind it.  The index rows then hold 32-bit LDS addresses that go into ds_read_u8 as
 // they are -- no per-gather "wave base + unpack u16" instruction (8 VALU per swap step) -- and
@@ -356,6 +365,13 @@ template <bool ABS> __device__ __forceinline__ void occ_st(uint8_t *occ, uint32_
 // (smolmc_set_walker_mu) -- walker r reads its row from P.mu_row / P.m_mu + r * P.mu_stride into a cell of its own WAVE,
 // P.mu_cell_off bytes into the workgroup's LDS behind everything else; the step loop reads s_mu as before, from a base
 // computed before the loop.  Separate instantiations, so that no other kernel's bytes move; the low bits are EWM.
+// ROWS (MM >= 10, see lean_rows; lean_rows_n2.hip only): the SOLO layout with three pieces of per-step work removed.
+// Each slot gathers as many members as its widest lane has (the host sorts the site's clusters by member count, so
+// that the headline model's 60 triplets + 54 pairs + point gather 2 + 1 members per lane and flip, not 2 + 2).  The
+// index rows (P.idx32) are stored in LDS-ADDRESS order -- the row of site s at lean_swz(s) -- so a row is addressed by
+// the swizzled address the step reads anyway and the kernel carries no site numbers at all (no readlane of the next
+// site, none of the partner).  And the species of site 1 stays in the VGPR its ds_read_u8 left it in for the undo
+// store and the accepted swap's store at the partner (the uniform copy costs a v_mov on both outcome paths).
 template <int NSLOT, int MM, int STEP, bool HAS_MU, int EWX, bool WL, bool BIAS = false, bool SOLO = false,
           int KF = 0, int OCC = 0, bool REPLAY = false>
 // OCC: waves per SIMD the register allocation is held to (0 = the compiler's choice, which is 4
@@ -369,6 +385,10 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     constexpr int EWM = EWX & 3;
     constexpr bool WMU = (EWX & 4) != 0;
     static_assert(!WMU || (HAS_MU && !WL && !REPLAY), "per-walker chemical potentials: semigrand Metropolis variants");
+    constexpr bool ROWS = lean_rows(MM);
+    constexpr int MMX = lean_mm_max(MM);
+    // (Ewald, replay, the KF tables and Wang-Landau all use the site NUMBER, which the ROWS variants do not carry)
+    static_assert(!ROWS || (SOLO && NSLOT == 2 && EWX == 0 && !REPLAY && KF == 0 && !WL && !BIAS), "solo rows: plain Metropolis, solo layout");
     // EWM: 0 = no Ewald term, 1 = compact Ewald with per-proposal row sums, 2 = potential field in
     // LDS.  A template parameter (not the runtime flag ew_field): both variants' pointers and code
     // otherwise stay live across the step loop and the kernel spills SGPRs.
@@ -440,7 +460,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     }
 
     // per-lane slot constants (registers for the whole launch)
-    uint32_t doff8[NSLOT], st8[NSLOT][MM], sfeat[NSLOT];
+    uint32_t doff8[NSLOT], st8[NSLOT][MMX], sfeat[NSLOT];
     double wgt[NSLOT], acc[NSLOT], sfs[NSLOT];
     double accK[NSLOT][NACC]; // KF: per correlation function (acc then only carries the enthalpy)
     uint32_t kslot[NSLOT];    // KF: number of correlation functions of the slot's orbit
@@ -452,7 +472,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         sfs[it] = sl.live ? sl.fs : 0.0;
         kslot[it] = sl.live;
 #pragma unroll
-        for (int m = 0; m < MM; ++m) st8[it][m] = sl.stride8[m];
+        for (int m = 0; m < (ROWS ? lean_mm_of(MM, it) : MM); ++m) st8[it][m] = sl.stride8[m];
         wgt[it] = sl.w;
         acc[it] = 0.0;
 #pragma unroll
@@ -547,7 +567,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     double logu = 0.0; // log of the acceptance uniform of step (step & ~63) + lane
     unsigned long long batch64_base = ~0ull;
     unsigned long long batch_base = ~0ull;
-    constexpr int ROW = NSLOT * MM; // entries per lane per site (u16, SOLO: u32)
+    constexpr int ROW = lean_row_len(MM, NSLOT); // entries per lane per site (u16, SOLO: u32)
     constexpr int NW = SOLO ? ROW : ROW / 2;          // dwords per lane per site
     constexpr uint32_t ENT = SOLO ? 4u : 2u;
     constexpr uint32_t SITE_BYTES = 64u * ROW * ENT;
@@ -578,7 +598,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             s1 = sbase + (int)__umulhi(w, nact);
         }
         a1 = lean_swz(s1, swa, swm, swb);
-        row1 = load_row<NW>(idx_rs, lane_voff, (uint32_t)s1 * SITE_BYTES);
+        row1 = load_row<NW>(idx_rs, lane_voff, (uint32_t)(ROWS ? a1 : s1) * SITE_BYTES);
     }
 
     // Loop skeleton: the steps run in chunks that end at the next random-batch boundary, the
@@ -691,7 +711,8 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         // SGPR -> VGPR move in every block that touches the site)
         uint32_t va1 = (uint32_t)a1;
         asm volatile("" : "+v"(va1));
-        const int o1 = uni((int)occ_ld<SOLO>(occ, va1));
+        const int vo1 = (int)occ_ld<SOLO>(occ, va1); // (ROWS: the stores of this species take it from here)
+        const int o1 = uni(vo1);
         int nfl, s2, a2, n1, n2 = 0, o2 = 0; // (swap: s2 / a2 / o2 are set by every proposal outcome)
         if (STEP != SMOLMC_STEP_SWAP) { s2 = s1; a2 = a1; }
         int fb = -1; // swap: lane of a first-round candidate hit (prefetched Ewald cross term)
@@ -761,13 +782,13 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                                 for (int j = 3; j >= 0; --j) {
                                     const int cs = sbase + (int)__umulhi(o.w[j], nact);
                                     const int v = (int)occ[lean_swz(cs, swa, swm, swb)];
-                                    if (v != o1) { selsite = cs; selv = v; }
+                                    if (v != o1) { selsite = ROWS ? lean_swz(cs, swa, swm, swb) : cs; selv = v; } // (ROWS: the address stands for the site)
                                 }
                                 const unsigned long long m = __ballot(selsite >= 0);
                                 if (m) {
                                     const int b = __ffsll((long long)m) - 1;
                                     s2 = (int)rdlane((uint32_t)selsite, b);
-                                    a2 = lean_swz(s2, swa, swm, swb);
+                                    a2 = ROWS ? s2 : lean_swz(s2, swa, swm, swb);
                                     o2 = (int)rdlane((uint32_t)selv, b);
                                     hit = true;
                                     break;
@@ -794,7 +815,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         __builtin_amdgcn_s_setprio(2);
         RowWords<NW> row2 = row1;
         if (STEP == SMOLMC_STEP_SWAP) {
-            row2 = load_row<NW>(idx_rs, lane_voff, (uint32_t)s2 * SITE_BYTES);
+            row2 = load_row<NW>(idx_rs, lane_voff, (uint32_t)(ROWS ? a2 : s2) * SITE_BYTES);
         }
         if (WL) {
             unsafeAtomicAdd(wl_pend + lane, wl_pend_sum());
@@ -817,7 +838,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                 uint32_t a = doff8[it];
                 if (DIFF) a = dp[it] = doff8[it] + pair1;
 #pragma unroll
-                for (int m = 0; m < MM; ++m) a += __umul24(st8[it][m], (uint32_t)occ_ld<SOLO>(occ, bounded(row_addr<SOLO, NW>(row1, it * MM + m), (uint32_t)P.Nlds)));
+                for (int m = 0; m < (ROWS ? lean_mm_of(MM, it) : MM); ++m) a += __umul24(st8[it][m], (uint32_t)occ_ld<SOLO>(occ, bounded(row_addr<SOLO, NW>(row1, (ROWS ? lean_row_off(MM, it) : it * MM) + m), (uint32_t)P.Nlds)));
                 if (DIFF) {
                     d1[it] = SMOLMC_LDS_F64(a);
                     if (KF) ad1[it] = a;
@@ -830,7 +851,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         }
         // index row of the NEXT step's site, straight into row1: its last use (the gathers above)
         // has been issued, so no second register set and no copy at the end of the step
-        row1 = load_row<NW>(idx_rs, lane_voff, (uint32_t)s1n * SITE_BYTES);
+        row1 = load_row<NW>(idx_rs, lane_voff, (uint32_t)(ROWS ? a1n : s1n) * SITE_BYTES);
         double ew_part = 0.0, ew_uni = 0.0; // lane-partial / uniform parts of the Ewald delta
         double dq1 = 0.0, dq2 = 0.0;
         if (HAS_EW) {
@@ -854,7 +875,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             for (int it = 0; it < NSLOT; ++it) {
                 uint32_t a = DIFF ? dp[it] : doff8[it];
 #pragma unroll
-                for (int m = 0; m < MM; ++m) a += __umul24(st8[it][m], (uint32_t)occ_ld<SOLO>(occ, bounded(row_addr<SOLO, NW>(row2, it * MM + m), (uint32_t)P.Nlds)));
+                for (int m = 0; m < (ROWS ? lean_mm_of(MM, it) : MM); ++m) a += __umul24(st8[it][m], (uint32_t)occ_ld<SOLO>(occ, bounded(row_addr<SOLO, NW>(row2, (ROWS ? lean_row_off(MM, it) : it * MM) + m), (uint32_t)P.Nlds)));
                 if (DIFF) {
                     d1[it] -= SMOLMC_LDS_F64(a); // D[(o2,n2)] = -D[(o1,n1)]: the step's delta of this slot
                     if (KF) ad2[it] = a;
@@ -992,7 +1013,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                 }
             }
             if (STEP == SMOLMC_STEP_FLIP) occ_st<SOLO>(occ, va1, (uint8_t)n1);
-            if (STEP == SMOLMC_STEP_SWAP) occ_st<SOLO>(occ, (uint32_t)a2, (uint8_t)n2); // (n2 == o1 == occ[a1] when empty)
+            if (STEP == SMOLMC_STEP_SWAP) occ_st<SOLO>(occ, (uint32_t)a2, (uint8_t)(ROWS ? vo1 : n2)); // (n2 == o1 == occ[a1] when empty)
             if (HAS_EW && ew_field) {
                 if (STEP == SMOLMC_STEP_SWAP) {
                     if (dq1 != 0.0 || dq2 != 0.0) field_apply2(P, phi, lane, s1, dq1, s2, dq2);
@@ -1010,7 +1031,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         };
         auto on_reject = [&]() {
             if (STEP == SMOLMC_STEP_SWAP) {
-            occ_st<SOLO>(occ, va1, (uint8_t)o1); // undo the tentative first flip
+            occ_st<SOLO>(occ, va1, (uint8_t)(ROWS ? vo1 : o1)); // undo the tentative first flip
             }
         };
         // Each outcome of the float32 pre-test runs its update directly (a merged
@@ -2493,4 +2514,19 @@ template <int NSLOT, unsigned B> static int launch_lean_replay_kf(smolmc_handle 
 }
 template <int NSLOT> static int launch_lean_replay_nslot(smolmc_handle *h, const LeanParams &lp) {
     return h->lean_kf ? launch_lean_replay_kf<NSLOT, LV_REPLAY | LV_KF>(h, lp) : launch_lean_replay_kf<NSLOT, LV_REPLAY>(h, lp);
+}
+
+// solo rows variants (instantiated in lean_rows_n2.hip only; engine.hip: solo_rows_plan): the plain family's solo
+// layouts with per-slot member counts h->solo_rows (21 or 11, see lean_rows above), launched on the handle's
+// address-ordered index rows and the slot records in their order
+template <int NSLOT> static int launch_lean_rows_nslot(smolmc_handle *h, const LeanParams &lp) {
+    LeanParams q = lp;
+    q.idx32 = h->d_rows_idx32;
+    q.slots = h->d_rows_slots;
+    const unsigned key = lean_key(h, q, true);
+    return first_match<21, 11>(h->solo_rows, [&](auto mm) {
+        return first_match<SMOLMC_STEP_SWAP, SMOLMC_STEP_FLIP>(h->cfg.step_type, [&](auto step) {
+            return launch_lean_variant<NSLOT, mm, step, LV_SOLO, LV_MU | LV_SOLO, LV_SOLO | LV_OCC6, LV_MU | LV_SOLO | LV_OCC6>(h, q, key);
+        });
+    });
 }

@@ -66,7 +66,7 @@ static const double SMOLMC_KB = 8.617333262145e-5; // smol/constants.py:4
 enum SmolmcEnv {
     ENV_FORCE_GENERAL, ENV_FORCE_UNIVERSAL, ENV_DENSE_EWALD, ENV_LAZY_FEATURES_ONLY, ENV_NO_LAZY_FEATURES,
     ENV_NO_LEAN_ALIASED, ENV_NO_LEAN_MULTI, ENV_NO_WL_MULTI, ENV_NO_TABLE_BIAS, ENV_NO_TABLE_WL, ENV_NO_EWALD_FIELD,
-    ENV_NO_EWALD_GX, ENV_NO_SOLO, ENV_NO_OCC6, ENV_NO_INKERNEL_BIAS, ENV_NO_SITE_RELABEL, ENV_MULTI_PHI_HBM,
+    ENV_NO_EWALD_GX, ENV_NO_SOLO, ENV_NO_OCC6, ENV_NO_SOLO_ROWS, ENV_NO_INKERNEL_BIAS, ENV_NO_SITE_RELABEL, ENV_MULTI_PHI_HBM,
     ENV_MULTI_PHI_LDS, ENV_UNIV_OCC_HBM, ENV_REPLAY_GENERAL, ENV_REPLAY_UNIVERSAL, ENV_WL_RUNNING_MEAN,
     ENV_WALKER_ORDER, ENV_LAUNCH_CHUNK, ENV_FAST_EPS_SCALE, ENV_NO_ROTATE, ENV_DEBUG,
     ENV_COUNT
@@ -91,6 +91,7 @@ static constexpr SmolmcEnvSwitch smolmc_env_switches[] = {
     {"SMOLMC_NO_EWALD_GX", true, "no translation-compressed Ewald site kernel: the rows of G"},
     {"SMOLMC_NO_SOLO", true, "no one-wave-per-workgroup layout of mc_lean_kernel"},
     {"SMOLMC_NO_OCC6", true, "no six-waves-per-SIMD instantiation of the one-wave layout"},
+    {"SMOLMC_NO_SOLO_ROWS", true, "one-wave layout: no per-slot gather widths / address-ordered index rows (lean_rows_n2.hip)"},
     {"SMOLMC_NO_INKERNEL_BIAS", false, "biased lean walkers record their sample rows through snapshots"},
     {"SMOLMC_NO_SITE_RELABEL", true, "scattered active sites are not renumbered into one range"},
     {"SMOLMC_MULTI_PHI_HBM", true, "multi-class lean kernels: the potential field stays in HBM"},
@@ -773,6 +774,13 @@ struct smolmc_handle {
     int lean_nslot = 0, lean_mm = 0, lean_ncls = 0;
     bool lean_solo = false;             // mc_lean_kernel in its one-wave-per-workgroup layout
     int lean_occ = 0;                   // > 0: the solo instantiation held to this many waves per SIMD
+    // solo rows variants (mc_lean.h: ROWS; engine.hip: solo_rows_plan): the per-slot member counts as the kernel's MM
+    // spells them (21 / 11; 0: the plain solo kernels), the index rows in LDS-address order and the slot records in the
+    // rows' lane order -- lp.idx32 and lp.slots stay what the other kernels of the handle read
+    int solo_rows = 0;
+    const uint32_t *d_rows_idx32 = nullptr;
+    const LeanSlot *d_rows_slots = nullptr;
+    std::vector<LeanSlot> lean_slots_host; // the slot records [class][NSLOT][64] as uploaded to lp.slots
     int lean_wpb = 4;          // TableFlip kernel: walkers (waves) per workgroup -- 8 when one such workgroup fills a CU's LDS (see launch_table_ewm)
     size_t lean_lds_wpb8 = 0;  // its dynamic LDS with 8 waves
     int lean_kf = 0;                    // > 0: correlation features with up to lean_kf functions per orbit
@@ -904,6 +912,8 @@ SMOLMC_LAUNCHERS3(multi) SMOLMC_LAUNCHERS3(multi_replay) SMOLMC_LAUNCHERS3(multi
 SMOLMC_LAUNCHERS3(multi_bias) SMOLMC_LAUNCHERS3(multi_bias_replay)
 SMOLMC_LAUNCHERS3(multi_wl) SMOLMC_LAUNCHERS3(multi_wl_replay) SMOLMC_LAUNCHERS3(multi_wl_kf)
 SMOLMC_LAUNCHERS3(multi_table_bias) SMOLMC_LAUNCHERS3(multi_table_wl)
+// solo rows variants of the plain lean family (lean_rows_n2.hip)
+int smolmc_launch_lean_rows_2(smolmc_handle *h, const LeanParams &lp);
 // per-walker chemical potentials (lean_wmu_n*.hip, multi_wmu_n*.hip)
 SMOLMC_LAUNCHERS2(lean_wmu) SMOLMC_LAUNCHERS2(lean_bias_wmu) SMOLMC_LAUNCHERS2(lean_corr_wmu) SMOLMC_LAUNCHERS2(table_bias_wmu)
 SMOLMC_LAUNCHERS3(multi_wmu) SMOLMC_LAUNCHERS3(multi_bias_wmu) SMOLMC_LAUNCHERS3(multi_table_bias_wmu)
