@@ -236,10 +236,34 @@ int smolmc_set_temperature(smolmc_handle *h, const double *temperature /*R*/);
  * without has_mu, distance handles, Wang-Landau handles (one density of states per Hamiltonian) and handles on
  * mc_kernel / the universal kernel; while rows are set smolmc_replay, smolmc_exchange_dev and
  * smolmc_import_temperature_dev are refused (an exchange of temperatures alone is no valid move between different
- * Hamiltonians) and smolmc_kernel_info appends " walker_mu=1 mu_max=<largest |mu| over all walkers>". */
+ * Hamiltonians) and smolmc_kernel_info appends " walker_mu=1 mu_max=<largest |mu| over all walkers>".  The valid
+ * exchange move between such walkers is smolmc_exchange_grid, which swaps temperature and row together. */
 int smolmc_set_walker_mu(smolmc_handle *h, const double *mu /* R x n_sublattices x mu_width, or NULL */);
-/* ... the rows in the same shape: those of the last call, the create-time rows when none are set */
+/* ... the rows in the same shape: each walker's current row (those of the last call, moved by the exchanges of
+ * smolmc_exchange_grid since), the create-time rows when none are set */
 int smolmc_get_walker_mu(smolmc_handle *h, double *mu /* R x n_sublattices x mu_width */);
+/* Replica exchange across the mu-T grid (hyper-parallel tempering), decided and applied on the device.  State point p
+ * is the (temperature, row of chemical potentials) walker p held at the latest smolmc_set_state,
+ * smolmc_set_temperature or smolmc_set_walker_mu: each of those calls makes the current assignment the new identity
+ * map.  For every pair (s, t) of state points, with walker a at s, walker b at t, beta = 1 / (kB T), H the current
+ * enthalpies, n the species counts per (active sublattice, code) and d = row_t - row_s:
+ *     Delta = (beta_s - beta_t) (Hb - Ha) + beta_s (n_b . d) - beta_t (n_a . d),  accept iff -Delta >= 0 or log_u < -Delta
+ * (from H_s(x) = E0(x) - n(x) . row_s; with d = 0 the temperature exchange of smolmc_exchange_dev).  On acceptance the
+ * two walkers swap their state points: temperatures and rows change places, the chemical work and the enthalpy of
+ * both are re-priced, occupancies do not move.  The pairs of one call must be disjoint; log_u is finite or -inf
+ * (-inf accepts every pair).  Queued on the handle's stream; stats, when given, gains 1 per attempted pair in
+ * stats[2 p] and 1 per accepted pair in stats[2 p + 1] (this waits for the kernel; with NULL nothing is copied back).
+ * A handle created with has_mu on a lean kernel family whose rows are not set exchanges temperatures only.  Refused,
+ * each with its reason: handles without has_mu, distance handles, Wang-Landau handles, handles on mc_kernel / the
+ * universal kernel, and handles whose state points have no temperatures: before the first smolmc_set_state /
+ * smolmc_set_temperature, and after smolmc_exchange_dev / smolmc_import_temperature_dev moved the temperatures last
+ * (they name no points; a handle that exchanged temperatures that way calls smolmc_set_temperature with its current
+ * temperatures once, then exchanges with this call). */
+int smolmc_exchange_grid(smolmc_handle *h, int npairs, const int32_t *pairs /* npairs x 2 state points, host */,
+                         const double *log_u /* npairs, host */, int64_t *stats /* npairs x 2 in/out, host, or NULL */);
+/* ... the state point every walker is at, and its temperature: the value the point was named with, not 1 / (kB beta)
+ * recomputed.  Either pointer may be NULL. */
+int smolmc_get_state_points(smolmc_handle *h, int32_t *point_of /* R */, double *temperature /* R */);
 /* any output pointer may be NULL */
 int smolmc_get_state(smolmc_handle *h, int32_t *occ /*RxN*/, double *features /*RxF*/,
                      double *enthalpy /*R*/, uint64_t *n_accepted /*R*/,

@@ -2512,12 +2512,12 @@ static void set_betas(smolmc_handle *h, const double *temperature, std::vector<d
 // feature, natural parameter -1; a change of rows re-prices it on the device from the current occupancies
 // (smolmc_walker_mu_reprice, walker_mu.hip: a kernel of its own translation unit, so that no kernel of this one moves).
 // why a handle takes no per-walker rows (null: it does)
-static int walker_mu_refused(const smolmc_handle *h) {
-    if (h->dist) return fail("per-walker chemical potentials: a distance handle has none (its objective is a distance to a target, no chemical work)");
-    if (!h->rt.has_mu) return fail("per-walker chemical potentials: the handle was created without has_mu (no chemical-work feature to price)");
-    if (is_wl(h)) return fail("per-walker chemical potentials: a Wang-Landau handle estimates one density of states, of one Hamiltonian");
+static int walker_mu_refused(const smolmc_handle *h, const std::string &what = "per-walker chemical potentials") {
+    if (h->dist) return fail(what + ": a distance handle has none (its objective is a distance to a target, no chemical work)");
+    if (!h->rt.has_mu) return fail(what + ": the handle was created without has_mu (no chemical-work feature to price)");
+    if (is_wl(h)) return fail(what + ": a Wang-Landau handle estimates one density of states, of one Hamiltonian");
     if (!h->lean())
-        return fail("per-walker chemical potentials: only the lean kernel families take them, this handle runs " +
+        return fail(what + ": only the lean kernel families take them, this handle runs " +
                     std::string(h->univ() ? "the universal kernel" : "mc_kernel") + " | not lean: " +
                     (h->lean_reason.empty() ? std::string("single-class planner refused the model") : h->lean_reason));
     return 0;
@@ -2527,6 +2527,49 @@ static int walker_mu_shape(const smolmc_handle *h, int *ncodes) {
     const int ns = h->lean_multi() ? h->lp.m_nsub : 1;
     for (int k = 0; k < ns; ++k) ncodes[k] = std::min(h->lean_multi() ? h->lp.m_ncodes[k] : h->lp.ncodes, h->rt.mu_W);
     return ns;
+}
+
+// ---- exchange across the mu-T grid: the state points (smolmc_exchange_grid, below) ---------------------------------
+// walker -> state point after the exchanges so far (the identity when none ran since the points were named)
+static int grid_point_of(smolmc_handle *h, std::vector<int32_t> &point_of) {
+    point_of.resize(h->R);
+    if (!h->grid_permuted) {
+        for (int r = 0; r < h->R; ++r) point_of[r] = r;
+        return 0;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(point_of.data(), h->d_point_of, (size_t)h->R * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+// the current assignment becomes the identity map: state point p is what walker p holds now (every call that names
+// temperatures or rows starts with this; the device arrays the kernels read already are in walker order)
+static int grid_rebase(smolmc_handle *h) {
+    if (!h->grid_permuted) return 0;
+    std::vector<int32_t> po;
+    TRY(grid_point_of(h, po));
+    const size_t R = (size_t)h->R;
+    if (h->point_T.size() == R) {
+        std::vector<double> T(R);
+        for (size_t r = 0; r < R; ++r) T[r] = h->point_T[po[r]];
+        h->point_T.swap(T);
+    }
+    if (!h->walker_mu.empty()) {
+        const size_t w = h->walker_mu.size() / R;
+        std::vector<double> rows(h->walker_mu.size());
+        for (size_t r = 0; r < R; ++r) std::copy_n(h->walker_mu.begin() + (size_t)po[r] * w, w, rows.begin() + r * w);
+        h->walker_mu.swap(rows);
+    }
+    for (size_t r = 0; r < R; ++r) po[r] = (int32_t)r;
+    HIPCHK(hipMemcpy(h->d_point_of, po.data(), R * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_walker_at, po.data(), R * 4, hipMemcpyHostToDevice));
+    h->grid_permuted = false;
+    return 0;
+}
+static void grid_name_temperatures(smolmc_handle *h, const double *temperature) {
+    h->point_T.resize(h->R);
+    for (int r = 0; r < h->R; ++r) h->point_T[r] = temperature ? temperature[r] : 0.0;
+    h->point_T_stale = false;
 }
 
 extern "C" int smolmc_set_walker_mu(smolmc_handle *h, const double *mu) {
@@ -2567,6 +2610,7 @@ extern "C" int smolmc_set_walker_mu(smolmc_handle *h, const double *mu) {
         rows_new = h->d_walker_mu[1];
         lp.mu_cell_off = (uint32_t)lds;
     }
+    TRY(grid_rebase(h)); // (past the refusals: the temperatures of the state points follow their walkers)
     // (lazy cluster features: lp.features are the scalar features' rows, the chemical work their last entry too)
     TRY(smolmc_walker_mu_reprice(h, rows_old, stride_old, rows_new, mu ? stride : 0, lp.features, lp.F, h->kp.enthalpy));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2590,8 +2634,11 @@ extern "C" int smolmc_get_walker_mu(smolmc_handle *h, double *mu) {
     int ncodes[4];
     const int ns = walker_mu_shape(h, ncodes), W = h->rt.mu_W;
     const size_t R = (size_t)h->R;
-    if (!h->walker_mu.empty()) {
-        memcpy(mu, h->walker_mu.data(), h->walker_mu.size() * 8);
+    if (!h->walker_mu.empty()) { // (the rows of the state points, each walker's current one: smolmc_exchange_grid)
+        std::vector<int32_t> po;
+        TRY(grid_point_of(h, po));
+        const size_t w = (size_t)ns * W;
+        for (size_t r = 0; r < R; ++r) memcpy(mu + r * w, h->walker_mu.data() + (size_t)po[r] * w, w * 8);
         return 0;
     }
     HIPCHK(hipSetDevice(h->device));
@@ -2614,6 +2661,8 @@ extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint
     TRY(upload_occ(h, occ, R, kp.occ));
     std::vector<double> beta;
     set_betas(h, temperature, beta);
+    TRY(grid_rebase(h));
+    grid_name_temperatures(h, temperature);
     HIPCHK(hipMemcpy(h->d_beta, beta.data(), R * 8, hipMemcpyHostToDevice));
     h->order_dirty = true;
     if (reset_aux) {
@@ -2714,6 +2763,8 @@ extern "C" int smolmc_set_temperature(smolmc_handle *h, const double *temperatur
     std::vector<double> beta;
     set_betas(h, temperature, beta);
     HIPCHK(hipStreamSynchronize(h->stream));
+    TRY(grid_rebase(h));
+    grid_name_temperatures(h, temperature);
     HIPCHK(hipMemcpy(h->d_beta, beta.data(), (size_t)h->R * 8, hipMemcpyHostToDevice));
     h->order_dirty = true;
     return 0;
@@ -3618,6 +3669,7 @@ extern "C" int smolmc_exchange_dev(smolmc_handle *h, int n_total, int first, int
                        SMOLMC_KB);
     HIPCHK(hipGetLastError());
     h->order_dirty = true; // (the launch order of the TableFlip kernels follows the temperatures)
+    h->point_T_stale = true;
     return 0;
 }
 
@@ -3631,5 +3683,82 @@ extern "C" int smolmc_import_temperature_dev(smolmc_handle *h, const double *src
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
     h->order_dirty = true;
+    h->point_T_stale = true;
+    return 0;
+}
+
+// ---- exchange across the mu-T grid (hyper-parallel tempering) ------------------------------------------------------
+// The walkers at the state points pairs[p][0] and pairs[p][1] attempt to swap their points -- temperature and row of
+// chemical potentials together, the valid move between walkers of different Hamiltonians -- decided and applied by
+// grid_exchange_kernel (grid_exchange.hip; the formula is spelled out there).  A permutation leaves the largest |mu|
+// over all rows alone: fast_eps and mu_max stay.  A handle without rows exchanges temperatures only.
+static int grid_exchange_refused(const smolmc_handle *h, const char *what) {
+    TRY(walker_mu_refused(h, what));
+    if (h->point_T_stale || h->point_T.size() != (size_t)h->R)
+        return fail(std::string(what) + ": the state points have no temperatures (smolmc_set_state or smolmc_set_temperature names them; "
+                    "smolmc_exchange_dev and smolmc_import_temperature_dev move temperatures without naming points)");
+    return 0;
+}
+
+extern "C" int smolmc_exchange_grid(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int64_t *stats) {
+    if (!h) return fail("null handle");
+    TRY(grid_exchange_refused(h, "smolmc_exchange_grid"));
+    if (npairs < 0 || (npairs > 0 && (!pairs || !log_u))) return fail("null argument");
+    const int R = h->R;
+    {
+        std::vector<uint8_t> seen(R, 0);
+        for (int i = 0; i < 2 * npairs; ++i) {
+            const int p = pairs[i];
+            if (p < 0 || p >= R) return fail("smolmc_exchange_grid: state point " + std::to_string(p) + " of pair " + std::to_string(i / 2) + " is out of range 0 .. " + std::to_string(R - 1));
+            if (seen[p]) return fail("smolmc_exchange_grid: state point " + std::to_string(p) + " appears in two pairs of one call (the pairs of a call are decided at once: they must be disjoint)");
+            seen[p] = 1;
+        }
+        for (int i = 0; i < npairs; ++i)
+            if (!std::isfinite(log_u[i]) && !(std::isinf(log_u[i]) && log_u[i] < 0))
+                return fail("smolmc_exchange_grid: log_u must be finite or -inf (pair " + std::to_string(i) + ")");
+    }
+    if (npairs == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t half = (size_t)R / 2; // (disjoint pairs: npairs <= R / 2)
+    if (!h->d_point_of) {
+        std::vector<int32_t> id(R);
+        for (int r = 0; r < R; ++r) id[r] = r;
+        TRY(dev_alloc(h, (size_t)R, &h->d_point_of));
+        TRY(dev_alloc(h, (size_t)R, &h->d_walker_at));
+        TRY(dev_alloc(h, 2 * half + half / 2 + 1, &h->d_gx_stage)); // log u [half] f64 | pairs [half][2] i32 | accept flags [half] i32
+        HIPCHK(hipMemcpy(h->d_point_of, id.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_walker_at, id.data(), (size_t)R * 4, hipMemcpyHostToDevice));
+    }
+    double *d_log_u = h->d_gx_stage;
+    int32_t *d_pairs = (int32_t *)(h->d_gx_stage + half), *d_acc = (int32_t *)(h->d_gx_stage + 2 * half);
+    // (pageable sources: the runtime has read them -- into its staging memory, or to the device -- when hipMemcpyAsync
+    // returns, so the caller may free them at once; the copies wait for the work queued before them on the stream)
+    HIPCHK(hipMemcpyAsync(d_log_u, log_u, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_pairs, pairs, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
+    TRY(smolmc_grid_exchange_launch(h, npairs, d_pairs, d_log_u, d_acc, h->d_point_of, h->d_walker_at));
+    h->grid_permuted = true;
+    h->order_dirty = true;              // (as smolmc_set_temperature: the launch order of the TableFlip kernels follows the temperatures)
+    if (is_lazy(h)) h->ce_dirty = true; // (as smolmc_set_walker_mu: kp.features takes its scalar entries from the lean kernels' rows)
+    if (stats) {
+        std::vector<int32_t> acc(npairs);
+        HIPCHK(hipMemcpyAsync(acc.data(), d_acc, (size_t)npairs * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (int i = 0; i < npairs; ++i) {
+            stats[2 * i] += 1;
+            stats[2 * i + 1] += acc[i];
+        }
+    }
+    return 0;
+}
+
+extern "C" int smolmc_get_state_points(smolmc_handle *h, int32_t *point_of, double *temperature) {
+    if (!h) return fail("null handle");
+    TRY(grid_exchange_refused(h, "smolmc_get_state_points"));
+    std::vector<int32_t> po;
+    TRY(grid_point_of(h, po));
+    for (int r = 0; r < h->R; ++r) {
+        if (point_of) point_of[r] = po[r];
+        if (temperature) temperature[r] = h->point_T[po[r]];
+    }
     return 0;
 }

@@ -796,6 +796,15 @@ struct smolmc_handle {
     const double *d_mu_create = nullptr;
     double mu_max = 0.0, mu_max_create = 0.0, fast_eps_plain = 0.0;
     int fast_eps_widenings = 1;
+    // exchange across the mu-T grid (smolmc_exchange_grid, engine.hip).  State point p is the (temperature, row) walker
+    // p held at the latest smolmc_set_state / smolmc_set_temperature / smolmc_set_walker_mu: point_T its temperature as
+    // given there, `walker_mu` above its row.  The walker -> point map and its inverse live on the device (allocated
+    // at the first exchange, with the staging of a call behind them: log u | pairs | accept flags); grid_permuted:
+    // exchanges ran since the identity map; point_T_stale: another call moved the temperatures on the device since.
+    std::vector<double> point_T;
+    int32_t *d_point_of = nullptr, *d_walker_at = nullptr;
+    double *d_gx_stage = nullptr;
+    bool grid_permuted = false, point_T_stale = false;
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
     SampleSlot slots[2];
@@ -893,6 +902,10 @@ __device__ __forceinline__ LeanParamsKernarg rare_params() {
 // all; the chemical work is features[r * F + F - 1]; enthalpy may be null), queued on the handle's stream
 int smolmc_walker_mu_reprice(smolmc_handle *h, const double *rows_old, int stride_old, const double *rows_new, int stride_new,
                              double *features, int F, double *enthalpy);
+// grid_exchange.hip: one exchange attempt between the walkers at the state points pairs[p][0] and pairs[p][1] (device
+// arrays; the pairs disjoint), decided and applied on the device, queued on the handle's stream
+int smolmc_grid_exchange_launch(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int32_t *accepted,
+                                int32_t *point_of, int32_t *walker_at);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);
 int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_4(smolmc_handle *h, const KParams &kp, int replay);

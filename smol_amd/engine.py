@@ -35,6 +35,8 @@ SYMBOLS = {
     "smolmc_set_temperature": (C.c_int, [_HP, _f64p]),
     "smolmc_set_walker_mu": (C.c_int, [_HP, _f64p]),
     "smolmc_get_walker_mu": (C.c_int, [_HP, _f64p]),
+    "smolmc_exchange_grid": (C.c_int, [_HP, C.c_int, _i32p, _f64p, _i64p]),
+    "smolmc_get_state_points": (C.c_int, [_HP, _i32p, _f64p]),
     "smolmc_get_state": (C.c_int, [_HP, _i32p, _f64p, _f64p, _u64p, _u64p, _u8p]),
     "smolmc_get_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
     "smolmc_set_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
@@ -129,6 +131,20 @@ def chemical_work(tables, occupancies, mu_rows):
     out = np.zeros(len(occ))
     for k, sites in enumerate(sites_of):
         out += np.take_along_axis(rows[:, k, :], occ[:, sites].astype(np.int64), axis=1).sum(axis=1)
+    return out
+
+
+def species_counts(tables, occupancies, width=None):
+    """Species counts per (active sublattice, species code), (n, n_sublattices, width) int64, of occupancies (n, N):
+    the n(x) of the chemical work n(x) . mu (``width`` defaults to the tables' mu_width)."""
+    occ = np.asarray(occupancies).reshape(-1, tables.struct.num_sites)
+    sites_of = tables.active_sites()
+    W = int(tables.struct.mu_width if width is None else width)
+    out = np.zeros((len(occ), len(sites_of), W), dtype=np.int64)
+    for k, sites in enumerate(sites_of):
+        sub = occ[:, sites]
+        for c in range(W):
+            out[:, k, c] = (sub == c).sum(axis=1)
     return out
 
 
@@ -244,10 +260,38 @@ class Engine:
         self.walker_mu_set = rows is not None
 
     def get_walker_mu(self):
-        """(R, n_sublattices, mu_width): the rows of the last ``set_walker_mu``, the create-time rows when none are set."""
+        """(R, n_sublattices, mu_width): every walker's current row -- those of the last ``set_walker_mu``, moved by the
+        exchanges of ``exchange_grid`` since -- the create-time rows when none are set."""
         out = np.zeros(self._mu_shape())
         self._chk(self._lib.smolmc_get_walker_mu(self._h, _p(out, C.c_double)))
         return out
+
+    def exchange_grid(self, pairs, log_u, stats=None):
+        """One exchange attempt across the mu-T grid, decided and applied on the device (smolmc_exchange_grid): for
+        every pair (s, t) of ``pairs`` (npairs, 2) the walkers at the state points s and t swap temperature and row
+        together when the move is accepted against ``log_u`` (npairs).  ``stats`` (npairs, 2) int64, when given, gains
+        the attempts in column 0 and the acceptances in column 1 (this waits for the kernel); without it the call only
+        queues work on the handle's stream."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        log_u = np.ascontiguousarray(log_u, dtype=np.float64).reshape(-1)
+        if len(log_u) != len(pairs):
+            raise ValueError(f"expected one log_u per pair: {len(pairs)} pairs, {len(log_u)} values")
+        if stats is not None and not (isinstance(stats, np.ndarray) and stats.dtype == np.int64 and stats.flags.c_contiguous
+                                      and stats.shape == (len(pairs), 2)):
+            raise ValueError(f"stats must be a C-contiguous int64 array of shape ({len(pairs)}, 2)")
+        self._chk(self._lib.smolmc_exchange_grid(self._h, len(pairs), _p(pairs, C.c_int32), _p(log_u, C.c_double),
+                                                 _p(stats, C.c_int64)))
+
+    def state_points(self):
+        """(point_of (R,) int32, temperature (R,)): the state point every walker is at after the exchanges so far, and
+        that point's temperature as it was set (smolmc_get_state_points)."""
+        point_of, temp = np.empty(self.R, dtype=np.int32), np.empty(self.R)
+        self._chk(self._lib.smolmc_get_state_points(self._h, _p(point_of, C.c_int32), _p(temp, C.c_double)))
+        return point_of, temp
+
+    def species_counts(self, occupancies):
+        """Species counts per (active sublattice, code) of occupancies (n, N), in the layout of ``set_walker_mu``."""
+        return species_counts(self.tables, self._occ32(occupancies, (-1, self.N)))
 
     def chemical_work(self, occupancies, mu_rows):
         """The last feature of a semigrand handle, on the host: sum over the active sites of mu[sublattice][species

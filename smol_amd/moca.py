@@ -737,6 +737,12 @@ class Ensemble:
             rows[:, k, s.encoding] = [[d[sp] for sp in s.species] for d in dicts]
         return rows
 
+    def walker_mu_dicts(self, rows):
+        """The inverse of ``walker_mu_rows``: rows (R, active sublattices, columns) -> R dicts species -> value."""
+        rows = np.asarray(rows, dtype=np.float64)
+        return [{sp: float(row[k, c]) for k, s in enumerate(self.active_sublattices) for sp, c in zip(s.species, s.encoding)}
+                for row in rows]
+
     def restrict_sites(self, sites):
         for s in self._sublattices:
             s.restrict_sites(sites)
@@ -1271,6 +1277,9 @@ class SampleContainer:
         self._blocks = [{k: v for k, v in sample_trace.items()}] if len(sample_trace.occupancy) else []
         self._joined = {}
         self._total_steps = 0
+        # walker -> state point after the last exchange attempt (Sampler.run_exchange keeps it): what a block without
+        # the state_point trace is filled with; None: the last sample's
+        self._state_point_now = None
 
     # ---- block store ---------------------------------------------------------------
     def append_block(self, block, thinned_by):
@@ -1278,6 +1287,13 @@ class SampleContainer:
         n = len(block["occupancy"])
         entry = {}
         for name, (dtype, shape) in self._schema.items():
+            if name == "state_point" and name not in block:  # (a plain run after run_exchange: nobody moves)
+                now = self._state_point_now
+                if now is None:  # (a restored container: where the last sample left the walkers)
+                    if not self._blocks:
+                        raise ValueError("a block without state_point for a container that traces it and holds no sample yet")
+                    now = self._blocks[-1]["state_point"][-1]
+                block = dict(block, state_point=np.broadcast_to(now, (n,) + shape))
             arr = np.asarray(block[name], dtype=dtype)
             entry[name] = arr.reshape((n,) + shape)
         self._blocks.append(entry)
@@ -1362,6 +1378,20 @@ class SampleContainer:
     def get_temperatures(self, discard=0, thin_by=1):
         return self.get_trace_value("temperature", discard, thin_by)
 
+    def by_state_point(self, name, discard=0):
+        """A traced value regrouped by the state point it was sampled at (``Sampler.run_exchange``): (npoints,
+        nsamples, ...) instead of (nsamples, nwalkers, ...).  Every sample holds each point once, so nothing is
+        dropped: row p is the chain of point p, whichever walker was there."""
+        if "state_point" not in self._schema:
+            raise ValueError("these samples carry no state_point trace: they were not taken by Sampler.run_exchange")
+        point = self._col("state_point")[discard:, :, 0].astype(np.int64)
+        vals = self._col(name)[discard:]
+        if name == "occupancy":
+            vals = vals.astype(np.int32)
+        out = np.empty_like(vals)
+        out[np.arange(len(point))[:, None], point] = vals
+        return np.swapaxes(out, 0, 1)
+
     def get_energies(self, discard=0, thin_by=1, flat=True):
         """Energy = natural parameters . features over the energy coefficients only
         (the chemical work / bias terms are not part of it, container.py:217-233)."""
@@ -1443,6 +1473,12 @@ class SampleContainer:
         wmu = self.metadata.get("walker_chemical_potentials")
         if wmu is not None:  # per-walker chemical potentials (Sampler.set_chemical_potentials)
             extra = {"meta/walker_mu_species": np.array(wmu["species"]), "meta/walker_mu_values": np.asarray(wmu["values"], dtype=np.float64)}
+        pts = self.metadata.get("state_points")
+        if pts is not None:  # the mu-T grid of Sampler.run_exchange
+            extra.update({"meta/state_point_species": np.array(pts["species"]),
+                          "meta/state_point_temperatures": np.asarray(pts["temperatures"], dtype=np.float64),
+                          "meta/state_point_values": np.asarray(pts["chemical_potentials"], dtype=np.float64),
+                          "meta/state_point_shape": np.asarray(pts["shape"], dtype=np.int64)})
         np.savez_compressed(path, nsamples=self.num_samples, total_mc_steps=self._total_steps,
                             **{f"trace/{k}": v for k, v in self._all().items()}, **extra)
 
@@ -1546,6 +1582,11 @@ class SampleContainer:
         if "meta/walker_mu_values" in d.files:
             c.metadata["walker_chemical_potentials"] = dict(species=[str(s) for s in d["meta/walker_mu_species"]],
                                                             values=d["meta/walker_mu_values"].tolist())
+        if "meta/state_point_values" in d.files:
+            c.metadata["state_points"] = dict(species=[str(s) for s in d["meta/state_point_species"]],
+                                              temperatures=d["meta/state_point_temperatures"].tolist(),
+                                              chemical_potentials=d["meta/state_point_values"].tolist(),
+                                              shape=[int(x) for x in d["meta/state_point_shape"]])
         return c
 
 
@@ -2115,6 +2156,82 @@ class Sampler:
                 self._kept_last = True
         # the device now holds the last recorded sample (see _load_state)
         self._resume_at = (id(self.samples), self.samples.num_samples)
+
+    def run_exchange(self, n_exchanges, steps_between, initial_occupancies=None, thin_by=None, grid=None):
+        """Sampling with replica exchange across a mu-T grid (hyper-parallel tempering): ``n_exchanges`` times
+        ``steps_between`` steps on every walker, then one exchange attempt, decided and applied on the device
+        (``Engine.exchange_grid``); the four moves of the grid take turns.  ``grid``: a ``parallel.GridExchange`` whose
+        rows are ``ensemble.walker_mu_rows(...)`` of the chemical potentials along the mu axis, or a dict
+        ``temperatures=, chemical_potentials= (a list of dicts), replicas=1, seed=0`` to build one; None: the grid of
+        the last call.  Walker w starts at point ``grid.point_of[w]`` (a new grid: point w) and swaps points, never
+        occupancies: each sample's ``temperature`` is the walker's temperature at that time, the int32 trace
+        ``state_point`` says where it was (``samples.by_state_point`` regroups), ``samples.metadata["state_points"]``
+        holds the grid, and afterwards the kernels' ``temperature`` / ``chemical_potentials`` and
+        ``walker_chemical_potentials`` are the current assignment.  ``thin_by`` defaults to ``steps_between``."""
+        from . import parallel
+
+        if self._world > 1:
+            raise ValueError("run_exchange on a sampler sharded over several ranks: the exchange across a mu-T grid runs "
+                             "inside one engine handle (an exchange across ranks would gather counts as well as enthalpies)")
+        ens = self._kernels[0].ensemble
+        if not isinstance(self._kernels[0], Metropolis) or isinstance(self._kernels[0], WangLandau):
+            raise ValueError("run_exchange runs the Metropolis kernel only")
+        if ens.chemical_potentials is None:
+            raise ValueError("run_exchange needs a semigrand ensemble: set ensemble.chemical_potentials first")
+        if isinstance(grid, dict):
+            spec = dict(grid)
+            grid = parallel.GridExchange(spec.pop("temperatures"), ens.walker_mu_rows(spec.pop("chemical_potentials")), **spec)
+        gx = grid if grid is not None else getattr(self, "_grid", None)
+        if gx is None:
+            raise ValueError("run_exchange needs a grid of state points")
+        nw = len(self._kernels)
+        if gx.npoints != nw:
+            raise ValueError(f"the grid has {gx.npoints} state points, the sampler {nw} walkers")
+        thin_by = int(steps_between if thin_by is None else thin_by)
+        if "state_point" not in self.samples._schema:
+            if self.samples.num_samples:
+                raise ValueError("the container holds samples without a state_point trace: clear_samples() first")
+            self.samples._schema["state_point"] = (np.dtype(np.int32), (nw, 1))
+        self._grid = gx
+        dicts = ens.walker_mu_dicts(gx.rows)
+        self.samples.metadata["state_points"] = dict(
+            species=list(ens.species), temperatures=[float(t) for t in gx.temperatures],
+            chemical_potentials=[[d[sp] for sp in ens.species] for d in dicts], shape=[gx.replicas, gx.nT, gx.nMu])
+
+        def assign(dirty):
+            """the kernels and this sampler's per-walker values follow gx.point_of"""
+            j = np.asarray(gx.point_of) % gx.nMu
+            self.set_chemical_potentials([dicts[k] for k in j])
+            self._walker_mu_dirty = dirty
+            for k, T in zip(self._kernels, gx.point_temperatures[gx.point_of]):
+                k.temperature = T
+            self.samples._state_point_now = np.asarray(gx.point_of, dtype=np.int32).reshape(nw, 1)
+
+        assign(True)
+        if initial_occupancies is None and self.samples.num_samples == 0:
+            raise RuntimeError("There are no saved samples to obtain the initial occupancies."
+                               "These must be provided.")
+        self._load_state(initial_occupancies)
+        eng = self._get_engine()
+        # (the engine's state point q is what walker q holds now: the grid's point base[q])
+        base = np.asarray(gx.point_of, dtype=np.int64).copy()
+        engine_point = np.empty(nw, dtype=np.int64)
+        engine_point[base] = np.arange(nw)
+        for _ in range(int(n_exchanges)):
+            for block in self._sample_blocks(steps_between, None, thin_by, state_loaded=True):
+                n = len(block["occupancy"])
+                block["state_point"] = np.broadcast_to(np.asarray(gx.point_of, dtype=np.int32).reshape(1, nw, 1), (n, nw, 1))
+                self.samples.append_block(block, thinned_by=thin_by)
+            move = gx.move_of(gx.calls)
+            pairs = gx.pairs(move)
+            stats = np.zeros((len(pairs), 2), dtype=np.int64)
+            eng.exchange_grid(engine_point[pairs], gx.log_u(gx.calls, len(pairs)), stats)
+            gx.record(move, stats[:, 1])
+            gx.calls += 1
+            gx.point_of = base[eng.state_points()[0]]
+            assign(False)  # (the engine holds them already)
+        self._resume_at = (id(self.samples), self.samples.num_samples)
+        return gx
 
     def anneal(self, temperatures, mcmc_steps, initial_occupancies=None, thin_by=1, progress=False,
                **kwargs):

@@ -345,3 +345,148 @@ def run_replica_exchange(engine, rex, n_exchanges, steps_between, device=None, c
     if on_device and device_decide and hasattr(engine, "sync"):
         engine.sync()  # (the last attempt's temperatures are in place when this returns)
     return rex
+
+
+# ---- exchange across a mu-T grid (hyper-parallel tempering, smolmc_exchange_grid) -------------------------------------
+class GridExchange:
+    """Bookkeeping of replica exchange across a grid of temperatures x rows of chemical potentials, in one handle.
+
+    State point ``p = (rep * nT + i) * nMu + j`` is (``temperatures[i]``, ``rows[j]``) of replica set ``rep``;
+    ``rows`` is (nMu, n_sublattices, mu_width) in the layout of ``Engine.set_walker_mu``.  ``point_of[w]`` is the point
+    walker w samples at.  The four moves -- ``("T", 0)``, ``("T", 1)``, ``("mu", 0)``, ``("mu", 1)`` -- pair the
+    neighbours along one axis at even or odd offsets, inside one replica set, so the pairs of a move are disjoint.
+
+    Walker a at s = (beta_s, row_s), walker b at t, H_s(x) = E0(x) - n(x) . row_s, d = row_t - row_s:
+
+        Delta = (beta_s - beta_t) (Hb - Ha) + beta_s (n_b . d) - beta_t (n_a . d);   accept iff -Delta >= 0 or log u < -Delta
+
+    which is (beta_k - beta_k+1) (H_a - H_b) of ``ReplicaExchange`` when d = 0.  On acceptance the walkers swap their
+    points; the chemical work of a gains n_a . d and its enthalpy loses it, b the other way round with n_b . d.
+    ``decide`` is this move in NumPy, in the operation order of the device kernel (grid_exchange.hip)."""
+
+    MOVES = (("T", 0), ("T", 1), ("mu", 0), ("mu", 1))
+
+    def __init__(self, temperatures, rows, replicas=1, seed=0):
+        self.temperatures = np.asarray(temperatures, dtype=np.float64).reshape(-1)
+        rows = np.asarray(rows, dtype=np.float64)
+        if rows.ndim != 3:
+            raise ValueError(f"expected rows of shape (points along mu, active sublattices, mu_width), got {rows.shape}")
+        self.rows = np.ascontiguousarray(rows)
+        self.nT, self.nMu, self.replicas, self.seed = len(self.temperatures), len(self.rows), int(replicas), int(seed)
+        self.npoints = self.replicas * self.nT * self.nMu
+        _, i, j = np.unravel_index(np.arange(self.npoints), (self.replicas, self.nT, self.nMu))
+        self.point_temperatures = self.temperatures[i]  # (npoints,)
+        self.point_rows = self.rows[j]                  # (npoints, n_sublattices, mu_width)
+        self.point_of = np.arange(self.npoints)         # walker -> point
+        self.calls = 0
+        self._pairs = {move: self._make_pairs(*move) for move in self.MOVES}
+        self.attempted = {move: np.zeros(len(p), dtype=np.int64) for move, p in self._pairs.items()}
+        self.accepted = {move: np.zeros(len(p), dtype=np.int64) for move, p in self._pairs.items()}
+
+    def _make_pairs(self, axis, offset):
+        grid = np.arange(self.npoints).reshape(self.replicas, self.nT, self.nMu)
+        if axis == "T":
+            lo, hi = grid[:, offset:self.nT - 1:2, :], grid[:, offset + 1:self.nT:2, :]
+        elif axis == "mu":
+            lo, hi = grid[:, :, offset:self.nMu - 1:2], grid[:, :, offset + 1:self.nMu:2]
+        else:
+            raise ValueError(f"unknown exchange axis {axis!r}")
+        return np.stack([lo.reshape(-1), hi.reshape(-1)], axis=1).astype(np.int32).reshape(-1, 2)
+
+    def pairs(self, move):
+        """(npairs, 2) state points of one of the four moves."""
+        return self._pairs[tuple(move)]
+
+    def move_of(self, attempt):
+        return self.MOVES[int(attempt) % len(self.MOVES)]
+
+    def log_u(self, attempt, npairs):
+        """log of the ``npairs`` uniforms of attempt ``attempt`` (a pure function of the seed and the attempt)."""
+        with np.errstate(divide="ignore"):
+            return np.log(_philox_uniforms(self.seed, attempt, max(int(npairs), 1))[:npairs])
+
+    def record(self, move, accept):
+        move = tuple(move)
+        self.attempted[move] += 1
+        self.accepted[move] += np.asarray(accept, dtype=np.int64)
+
+    @property
+    def acceptance(self):
+        """Accepted / attempted over all pairs of all moves."""
+        att = sum(int(a.sum()) for a in self.attempted.values())
+        return sum(int(a.sum()) for a in self.accepted.values()) / max(att, 1)
+
+    def decide(self, enthalpy, counts, point_of, move, attempt, log_u=None, record=True):
+        """One attempt of ``move`` on the host: enthalpy (R,), species counts (R, n_sublattices, mu_width) and the
+        walker -> point map in; returns dict(pairs, exponent (-Delta per pair), accept, point_of (new), work_delta
+        (what each walker's chemical work gains; its enthalpy loses it), enthalpy (re-priced)).  The definition the
+        device kernel is tested against: beta = 1 / (kB T), every product and sum rounded on its own, n . d summed
+        over the cells sublattice by sublattice, code by code."""
+        enthalpy = np.asarray(enthalpy, dtype=np.float64)
+        point_of = np.asarray(point_of, dtype=np.int64)
+        counts = np.asarray(counts).reshape(self.npoints, -1).astype(np.float64)
+        cells = self.point_rows.reshape(self.npoints, -1)
+        pairs = self.pairs(move)
+        walker_at = np.empty(self.npoints, dtype=np.int64)
+        walker_at[point_of] = np.arange(self.npoints)
+        s, t = pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64)
+        a, b = walker_at[s], walker_at[t]
+        beta = 1.0 / (kB * self.point_temperatures)
+        wa, wb = np.zeros(len(pairs)), np.zeros(len(pairs))
+        for c in range(cells.shape[1]):  # (written out: np.dot sums in another order)
+            d = cells[t, c] - cells[s, c]
+            wa = wa + counts[a, c] * d
+            wb = wb + counts[b, c] * d
+        delta = ((beta[s] - beta[t]) * (enthalpy[b] - enthalpy[a]) + beta[s] * wb) - beta[t] * wa
+        if log_u is None:
+            log_u = self.log_u(attempt, len(pairs))
+        log_u = np.asarray(log_u, dtype=np.float64)
+        accept = (-delta >= 0) | (log_u < -delta)
+        new_point_of = point_of.copy()
+        new_point_of[a[accept]] = t[accept]
+        new_point_of[b[accept]] = s[accept]
+        work = np.zeros(self.npoints)
+        work[a[accept]] = wa[accept]
+        work[b[accept]] = -wb[accept]
+        if record:
+            self.record(move, accept)
+        return dict(pairs=pairs, exponent=-delta, accept=accept, point_of=new_point_of, work_delta=work,
+                    enthalpy=enthalpy - work)
+
+
+def run_grid_exchange(engine, gx, n_exchanges, steps_between, host_decide=False, history=None):
+    """Alternate ``steps_between`` MC steps on every walker with one exchange attempt across the mu-T grid ``gx``,
+    cycling its four moves.  ``engine`` holds ``gx.npoints`` walkers with their state loaded; walker w starts at point
+    ``gx.point_of[w]``.  Default: the attempt is decided and applied on the device (``Engine.exchange_grid``), nothing
+    but the accept flags comes back.  ``host_decide=True``: the state is read back, ``gx.decide`` takes the decisions
+    and ``set_temperature`` + ``set_walker_mu`` apply them -- the cross-check of the device path, and what it is timed
+    against.  ``history``: a list that receives ``gx.point_of`` after every attempt."""
+    if engine.R != gx.npoints:
+        raise ValueError(f"the grid has {gx.npoints} state points, the engine {engine.R} walkers")
+    base = np.asarray(gx.point_of, dtype=np.int64).copy()  # walker -> point now: the engine's point q is the grid's base[q]
+    engine_point = np.empty(gx.npoints, dtype=np.int64)
+    engine_point[base] = np.arange(gx.npoints)
+    engine.set_walker_mu(gx.point_rows[base])
+    engine.set_temperature(gx.point_temperatures[base])
+    for _ in range(int(n_exchanges)):
+        engine.run(steps_between)
+        move = gx.move_of(gx.calls)
+        pairs = gx.pairs(move)
+        if host_decide:
+            st = engine.get_state()
+            res = gx.decide(st["enthalpy"], engine.species_counts(st["occupancy"]), gx.point_of, move, gx.calls)
+            gx.point_of = res["point_of"]
+            engine.set_temperature(gx.point_temperatures[gx.point_of])
+            engine.set_walker_mu(gx.point_rows[gx.point_of])
+        else:
+            stats = np.zeros((len(pairs), 2), dtype=np.int64)
+            engine.exchange_grid(engine_point[pairs], gx.log_u(gx.calls, len(pairs)), stats)
+            gx.record(move, stats[:, 1])
+            if history is not None:
+                gx.point_of = base[engine.state_points()[0]]
+        gx.calls += 1
+        if history is not None:
+            history.append(np.array(gx.point_of))
+    if not host_decide:
+        gx.point_of = base[engine.state_points()[0]]
+    return gx
