@@ -264,6 +264,39 @@ int smolmc_exchange_grid(smolmc_handle *h, int npairs, const int32_t *pairs /* n
 /* ... the state point every walker is at, and its temperature: the value the point was named with, not 1 / (kB beta)
  * recomputed.  Either pointer may be NULL. */
 int smolmc_get_state_points(smolmc_handle *h, int32_t *point_of /* R */, double *temperature /* R */);
+/* Per-walker Wang-Landau windows: replica-exchange Wang-Landau (Vogel, Li, Wuest, Landau, PRL 110, 210603) in one
+ * handle.  Walker r samples the window [vmin[r], vmax[r]) with the handle's bin size instead of the one window of
+ * smolmc_config.  Every window must give the handle's number of levels by the rule of smolmc_create,
+ * ceil((vmax - vmin) / wl_bin_size) == smolmc_wl_num_levels(h); otherwise the call is refused and names the first
+ * offending walker (create the handle with any one of the windows as wl_min_enthalpy / wl_max_enthalpy).
+ * ESTIMATORS: the Wang-Landau arrays (entropy, histogram, occurrences, mean features, modification factor) belong to
+ * an estimator; estimator e is the window and density-of-states copy walker e held at the latest
+ * smolmc_set_wl_windows.  smolmc_exchange_wl moves estimators between walkers; a walker always updates the arrays of
+ * the estimator it holds, while its step counter, random stream and configuration stay its own.  smolmc_get_wl and
+ * smolmc_set_wl are in ESTIMATOR order (walker order while no exchange was accepted, and always without windows).
+ * This call and smolmc_set_state(reset_aux != 0) reset the walker -> estimator map to the identity; a continuation
+ * (reset_aux == 0) keeps it; the windows survive smolmc_set_state, which checks every start enthalpy against the
+ * window its walker holds.  The call itself leaves the Wang-Landau arrays alone.  NULL, NULL: back to the config's
+ * window.  Valid on Wang-Landau handles that run mc_wl_kernel or the Wang-Landau variant of mc_lean_multi_kernel;
+ * refused, each naming its kernel family, on the KF and TableFlip Wang-Landau kernels, on mc_kernel and the universal
+ * kernel, and on handles that are not Wang-Landau.  While windows are set smolmc_replay and the SMOLMC_SAMPLE_WL
+ * column of smolmc_run_sampled are refused, and smolmc_kernel_info appends " wl_windows=1". */
+int smolmc_set_wl_windows(smolmc_handle *h, const double *vmin /* R, or NULL */, const double *vmax /* R, or NULL */);
+/* ... the window every walker holds now and the estimator it belongs to (the config's window and the identity while
+ * none are set).  Any pointer may be NULL. */
+int smolmc_get_wl_windows(smolmc_handle *h, double *vmin /* R */, double *vmax /* R */, int32_t *estimator_of /* R */);
+/* Replica exchange between energy windows, decided and applied on the device.  For every pair (s, t) of estimators,
+ * with walker a holding s, walker b holding t, Ea / Eb the enthalpies smolmc_get_state returns, S the entropies:
+ * the pair is rejected, whatever log_u, unless Ea lies in [vmin_t, vmax_t) and Eb in [vmin_s, vmax_s); else, with
+ * ia(E) = floor((E - vmin_s) / bin), ib(E) = floor((E - vmin_t) / bin) (the exact floor division of the sampling step),
+ *     ex = ((S_s[ia(Ea)] - S_s[ia(Eb)]) + S_t[ib(Eb)]) - S_t[ib(Ea)],  accept iff ex >= 0 or log_u < ex.
+ * On acceptance the two walkers swap estimators (window and row of every Wang-Landau array); occupancies, features,
+ * enthalpies, Ewald fields, counters and the arrays themselves do not move, and nothing is recorded: the next sampling
+ * step's post-step records each walker in its new estimator.  The pairs of one call must be disjoint; log_u is finite
+ * or -inf (-inf accepts every in-window pair).  Queued on the handle's stream; stats as in smolmc_exchange_grid.
+ * Refused like smolmc_set_wl_windows, and while no windows are set. */
+int smolmc_exchange_wl(smolmc_handle *h, int npairs, const int32_t *pairs /* npairs x 2 estimators, host */,
+                       const double *log_u /* npairs, host */, int64_t *stats /* npairs x 2 in/out, host, or NULL */);
 /* any output pointer may be NULL */
 int smolmc_get_state(smolmc_handle *h, int32_t *occ /*RxN*/, double *features /*RxF*/,
                      double *enthalpy /*R*/, uint64_t *n_accepted /*R*/,

@@ -1593,8 +1593,11 @@ static int create_wl_state(smolmc_handle *h, const smolmc_tables *) {
     if (h->F > 64 && h->general_ok) no_general(h, "Wang-Landau with more than 64 features");
     if (dev_alloc(h, R * h->L, &kp.wl_entropy) || dev_alloc(h, R * h->L, &kp.wl_hist) ||
         dev_alloc(h, R * h->L, &kp.wl_occur) || dev_alloc(h, R * h->L * h->F + 64, &kp.wl_meanf) || // (+64: the lean kernel's all-lane atomic, see mc_lean.h)
-        dev_alloc(h, R, &kp.wl_m) || dev_alloc(h, R, &kp.wl_counter))
+        // (m heads one arena: behind it the walkers' window records and the estimator -> walker map, smolmc_set_wl_windows)
+        dev_alloc(h, R + (R * sizeof(WlWindow) + R * 4 + 7) / 8, &kp.wl_m) || dev_alloc(h, R, &kp.wl_counter))
         return 1;
+    h->d_wl_win = (WlWindow *)(kp.wl_m + R);
+    h->d_wl_walker_at = (int32_t *)(h->d_wl_win + R);
     std::vector<double> m0(R, cfg->wl_mod_factor);
     if (hipMemcpy(kp.wl_m, m0.data(), R * 8, hipMemcpyHostToDevice) != hipSuccess)
         return fail("hipMemcpy failed");
@@ -2249,6 +2252,7 @@ struct LeanFamilyRow {
     const char *wl_sums, *wl_means;   // ... and the tag of the Wang-Landau kernel (per-bin feature sums / running means)
     LeanLauncher run[3], replay[3], table_replay[3];
     LeanLauncher walker_mu[3];        // `run` while per-walker chemical potentials are set (smolmc_set_walker_mu)
+    LeanLauncher wl_win[3];           // `run` while per-walker Wang-Landau windows are set (smolmc_set_wl_windows)
 };
 #define L2(f) {smolmc_launch_##f##_2, smolmc_launch_##f##_4, nullptr}
 #define L3(f) {smolmc_launch_##f##_2, smolmc_launch_##f##_4, smolmc_launch_##f##_8}
@@ -2257,12 +2261,12 @@ static const LeanFamilyRow lean_families[] = {
     /* K_LEAN             */ {"lean", nullptr, nullptr, L2(lean), L2(lean_replay), L2(table_replay), L2(lean_wmu)},
     /* K_LEAN_BIAS        */ {"lean", nullptr, nullptr, L2(lean_bias), L2(lean_bias_replay), NONE, L2(lean_bias_wmu)},
     /* K_LEAN_CORR        */ {"lean", nullptr, nullptr, L2(lean_corr), L2(lean_replay), NONE, L2(lean_corr_wmu)}, // (KF: a template flag of the same launchers)
-    /* K_WL               */ {"lean", " wl=v3", " wl=v3", L2(wl), L2(wl_replay), NONE, NONE},
+    /* K_WL               */ {"lean", " wl=v3", " wl=v3", L2(wl), L2(wl_replay), NONE, NONE, L2(wl_win)},
     /* K_TABLE_BIAS       */ {"lean", nullptr, nullptr, L2(table_bias), NONE, NONE, L2(table_bias_wmu)},
     /* K_TABLE_WL         */ {"lean", " wl=table", " wl=table-mean", L2(table_wl), NONE, NONE, NONE},
     /* K_MULTI            */ {"lean-multi", nullptr, nullptr, L3(multi), L3(multi_replay), L3(multi_table_replay), L3(multi_wmu)},
     /* K_MULTI_BIAS       */ {"lean-multi", nullptr, nullptr, L3(multi_bias), L3(multi_bias_replay), NONE, L3(multi_bias_wmu)},
-    /* K_MULTI_WL         */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_wl), L3(multi_wl_replay), NONE, NONE},
+    /* K_MULTI_WL         */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_wl), L3(multi_wl_replay), NONE, NONE, L3(multi_wl_win)},
     /* K_MULTI_WL_KF      */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_wl_kf), NONE, NONE, NONE},
     /* K_MULTI_TABLE_BIAS */ {"lean-multi", nullptr, nullptr, L3(multi_table_bias), NONE, NONE, L3(multi_table_bias_wmu)},
     /* K_MULTI_TABLE_WL   */ {"lean-multi", " wl=multi", " wl=multi-mean", L3(multi_table_wl), NONE, NONE, NONE},
@@ -2275,6 +2279,7 @@ static LeanLauncher lean_launcher(const smolmc_handle *h, bool replay) {
     const LeanFamilyRow &row = lean_families[h->family - K_LEAN];
     const int i = h->lean_nslot == 2 ? 0 : (h->lean_nslot == 4 ? 1 : 2);
     if (!replay && h->lp.mu_stride) return row.walker_mu[i];
+    if (!replay && h->lp.wl.win_off) return row.wl_win[i];
     // (the solo rows variants: runs of the plain family's solo handles whose clusters fall into one of their shapes;
     // replays and per-walker chemical potentials stay on the kernels above, which read the site-ordered rows)
     if (!replay && h->family == K_LEAN && h->solo_rows && h->lean_nslot == 2) return smolmc_launch_lean_rows_2;
@@ -2650,6 +2655,133 @@ extern "C" int smolmc_get_walker_mu(smolmc_handle *h, double *mu) {
     return 0;
 }
 
+// ---- per-walker Wang-Landau windows (smolmc_set_wl_windows) and their exchange (smolmc_exchange_wl) ------------------
+// Replica-exchange Wang-Landau in one handle: walker r samples the window of the ESTIMATOR it holds and updates that
+// estimator's arrays (WlWindow, smolmc_common.h; the window variants of mc_wl_kernel and mc_lean_multi_kernel read the
+// record, every other kernel family is refused here).  Estimator e is the window and density-of-states copy walker e
+// held at the latest smolmc_set_wl_windows; wl_exchange_kernel (wl_exchange.hip) swaps the records of two walkers.
+static int wl_windows_refused(const smolmc_handle *h, const char *what) {
+    const std::string w(what);
+    if (h->dist || h->cfg.kernel_type != SMOLMC_KERNEL_WANGLANDAU)
+        return fail(w + ": the handle is not a Wang-Landau kernel (only those have an energy window)");
+    if (!h->lean())
+        return fail(w + ": only mc_wl_kernel and the Wang-Landau variant of mc_lean_multi_kernel take per-walker windows, this handle runs " +
+                    std::string(h->univ() ? "the universal kernel" : "mc_kernel") + " | not lean: " +
+                    (h->lean_reason.empty() ? std::string(smolmc_env(ENV_FORCE_GENERAL) ? "SMOLMC_FORCE_GENERAL" : "single-class planner refused the model") : h->lean_reason));
+    if (h->family != K_WL && h->family != K_MULTI_WL)
+        return fail(w + ": only mc_wl_kernel and the Wang-Landau variant of mc_lean_multi_kernel take per-walker windows, this handle runs " +
+                    (h->family == K_MULTI_WL_KF ? "the KF variant (several correlation functions per orbit)" : "a TableFlip Wang-Landau kernel"));
+    return 0;
+}
+// the walkers' records: estimator r with its window to walker r (the identity map); nothing while no windows are set
+static int wl_windows_upload(smolmc_handle *h) {
+    if (h->wl_win_min.empty()) return 0;
+    const size_t R = (size_t)h->R;
+    std::vector<WlWindow> win(R);
+    std::vector<int32_t> id(R);
+    for (size_t r = 0; r < R; ++r) {
+        win[r].vmin = h->wl_win_min[r]; win[r].vmax = h->wl_win_max[r];
+        win[r].est = (int32_t)r; win[r].pad = 0;
+        id[r] = (int32_t)r;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(h->d_wl_win, win.data(), R * sizeof(WlWindow), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_wl_walker_at, id.data(), R * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+// ... as the walkers hold them now (after the exchanges so far); empty while no windows are set
+static int wl_windows_download(smolmc_handle *h, std::vector<WlWindow> &win) {
+    win.clear();
+    if (h->wl_win_min.empty()) return 0;
+    win.resize(h->R);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(win.data(), h->d_wl_win, (size_t)h->R * sizeof(WlWindow), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int smolmc_set_wl_windows(smolmc_handle *h, const double *vmin, const double *vmax) {
+    if (!h) return fail("null handle");
+    TRY(wl_windows_refused(h, "smolmc_set_wl_windows"));
+    if ((vmin == nullptr) != (vmax == nullptr)) return fail("smolmc_set_wl_windows: vmin and vmax are given together, or both NULL");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t R = (size_t)h->R;
+    if (!vmin) { // back to the config's window
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->wl_win_min.clear();
+        h->wl_win_max.clear();
+        h->lp.wl.win_off = 0;
+        return 0;
+    }
+    for (size_t r = 0; r < R; ++r) {
+        if (!std::isfinite(vmin[r]) || !std::isfinite(vmax[r]) || !(vmax[r] > vmin[r]))
+            return fail("smolmc_set_wl_windows: window of walker " + std::to_string(r) + " is not a finite range vmin < vmax");
+        // (the rule of smolmc_create: the LDS layout of the kernels is sized by L)
+        const int L = (int)ceil((vmax[r] - vmin[r]) / h->cfg.wl_bin_size);
+        if (L != h->L)
+            return fail("smolmc_set_wl_windows: window of walker " + std::to_string(r) + " has " + std::to_string(L) +
+                        " bins, the handle has L = " + std::to_string(h->L) + " (every window must give ceil((vmax - vmin) / bin_size) == L)");
+    }
+    h->wl_win_min.assign(vmin, vmin + R);
+    h->wl_win_max.assign(vmax, vmax + R);
+    TRY(wl_windows_upload(h));
+    h->lp.wl.win_off = (uint32_t)((const unsigned char *)h->d_wl_win - (const unsigned char *)h->kp.wl_m);
+    return 0;
+}
+
+extern "C" int smolmc_get_wl_windows(smolmc_handle *h, double *vmin, double *vmax, int32_t *estimator_of) {
+    if (!h) return fail("null handle");
+    TRY(wl_windows_refused(h, "smolmc_get_wl_windows"));
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<WlWindow> win;
+    TRY(wl_windows_download(h, win));
+    for (int r = 0; r < h->R; ++r) {
+        if (vmin) vmin[r] = win.empty() ? h->cfg.wl_min_enthalpy : win[r].vmin;
+        if (vmax) vmax[r] = win.empty() ? h->cfg.wl_max_enthalpy : win[r].vmax;
+        if (estimator_of) estimator_of[r] = win.empty() ? r : win[r].est;
+    }
+    return 0;
+}
+
+extern "C" int smolmc_exchange_wl(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int64_t *stats) {
+    if (!h) return fail("null handle");
+    TRY(wl_windows_refused(h, "smolmc_exchange_wl"));
+    if (h->wl_win_min.empty()) return fail("smolmc_exchange_wl: no per-walker windows are set (smolmc_set_wl_windows first)");
+    if (npairs < 0 || (npairs > 0 && (!pairs || !log_u))) return fail("null argument");
+    const int R = h->R;
+    {
+        std::vector<uint8_t> seen(R, 0);
+        for (int i = 0; i < 2 * npairs; ++i) {
+            const int p = pairs[i];
+            if (p < 0 || p >= R) return fail("smolmc_exchange_wl: estimator " + std::to_string(p) + " of pair " + std::to_string(i / 2) + " is out of range 0 .. " + std::to_string(R - 1));
+            if (seen[p]) return fail("smolmc_exchange_wl: estimator " + std::to_string(p) + " appears in two pairs of one call (the pairs of a call are decided at once: they must be disjoint)");
+            seen[p] = 1;
+        }
+        for (int i = 0; i < npairs; ++i)
+            if (!std::isfinite(log_u[i]) && !(std::isinf(log_u[i]) && log_u[i] < 0))
+                return fail("smolmc_exchange_wl: log_u must be finite or -inf (pair " + std::to_string(i) + ")");
+    }
+    if (npairs == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    const size_t half = (size_t)R / 2; // (disjoint pairs: npairs <= R / 2)
+    if (!h->d_wlx_stage) TRY(dev_alloc(h, 2 * half + half / 2 + 1, &h->d_wlx_stage)); // log u [half] f64 | pairs [half][2] i32 | accept flags [half] i32
+    double *d_log_u = h->d_wlx_stage;
+    int32_t *d_pairs = (int32_t *)(h->d_wlx_stage + half), *d_acc = (int32_t *)(h->d_wlx_stage + 2 * half);
+    // (pageable sources, as in smolmc_exchange_grid: the caller may free them when the call returns)
+    HIPCHK(hipMemcpyAsync(d_log_u, log_u, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_pairs, pairs, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
+    TRY(smolmc_wl_exchange_launch(h, npairs, d_pairs, d_log_u, d_acc));
+    if (stats) {
+        std::vector<int32_t> acc(npairs);
+        HIPCHK(hipMemcpyAsync(acc.data(), d_acc, (size_t)npairs * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (int i = 0; i < npairs; ++i) {
+            stats[2 * i] += 1;
+            stats[2 * i + 1] += acc[i];
+        }
+    }
+    return 0;
+}
+
 extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint64_t *seeds,
                                 const double *temperature, int reset_aux) {
     if (!h || !occ) return fail("null argument");
@@ -2722,6 +2854,7 @@ extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint
                        kp.features, h->d_natural, kp.enthalpy, (int)R, h->F);
     HIPCHK(hipGetLastError());
     TRY(lazy_scalars_from_features(h));
+    if (reset_aux) TRY(wl_windows_upload(h)); // (the estimators go back to the walkers they were given to; a continuation keeps the map)
     if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && reset_aux) {
         const size_t RL = R * h->L;
         HIPCHK(hipMemsetAsync(kp.wl_entropy, 0, RL * 8, h->stream));
@@ -2742,15 +2875,19 @@ extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint
         // (negative Python index, wanglandau.py:175-180); here both are refused up front.
         std::vector<double> H0(R);
         HIPCHK(hipMemcpy(H0.data(), kp.enthalpy, R * 8, hipMemcpyDeviceToHost));
-        for (size_t r = 0; r < R; ++r)
-            if (!(H0[r] >= h->cfg.wl_min_enthalpy && H0[r] < h->cfg.wl_max_enthalpy)) {
-                char msg[200];
+        std::vector<WlWindow> win; // (per-walker windows: the window the walker holds)
+        TRY(wl_windows_download(h, win));
+        for (size_t r = 0; r < R; ++r) {
+            const double wmin = win.empty() ? h->cfg.wl_min_enthalpy : win[r].vmin, wmax = win.empty() ? h->cfg.wl_max_enthalpy : win[r].vmax;
+            if (!(H0[r] >= wmin && H0[r] < wmax)) {
+                char msg[240];
                 snprintf(msg, sizeof msg,
                          "initial enthalpy %.6f of walker %zu is outside the Wang-Landau window "
-                         "[min_enthalpy, max_enthalpy) = [%.6f, %.6f)",
-                         H0[r], r, h->cfg.wl_min_enthalpy, h->cfg.wl_max_enthalpy);
+                         "[min_enthalpy, max_enthalpy) = [%.6f, %.6f)%s",
+                         H0[r], r, wmin, wmax, win.empty() ? "" : " the walker holds (smolmc_set_wl_windows)");
                 return fail(msg);
             }
+        }
     }
     if (h->dist) return smolmc_dist_after_set_state(h, temperature);
     return 0;
@@ -2808,6 +2945,7 @@ extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
         if (h->relabelled && strlen(buf) + 16 < (size_t)n) strncat(buf, " relabelled=1", (size_t)n - strlen(buf) - 1);
         if (!h->walker_mu.empty() && strlen(buf) + 48 < (size_t)n) // (the largest |mu| over all walkers: what the float32 accept bound was widened by)
             snprintf(buf + strlen(buf), (size_t)n - strlen(buf), " walker_mu=1 mu_max=%.17g", h->mu_max);
+        if (h->lp.wl.win_off && strlen(buf) + 16 < (size_t)n) strncat(buf, " wl_windows=1", (size_t)n - strlen(buf) - 1);
         if (h->env_dispatch && strlen(buf) + 8 < (size_t)n) { // the dispatch switches this handle was created under
             strncat(buf, " env=", (size_t)n - strlen(buf) - 1);
             const char *sep = "";
@@ -3147,6 +3285,8 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
     if ((flags & SMOLMC_SAMPLE_BIAS) && !h->kp.bias_type) return fail("the model has no bias term");
     if ((flags & SMOLMC_SAMPLE_WL) && !wl) return fail("handle is not a Wang-Landau kernel");
+    if ((flags & SMOLMC_SAMPLE_WL) && !h->wl_win_min.empty())
+        return fail("SMOLMC_SAMPLE_WL while per-walker windows are set: the snapshot rows are walker-indexed, the Wang-Landau arrays estimator-indexed (smolmc_get_wl between runs, or smolmc_set_wl_windows(h, NULL, NULL) first)");
     if (thin_by > ((int64_t)1 << 30) && h->lean() && !smolmc_env(ENV_LAUNCH_CHUNK))
         return fail("thin_by must be <= 2^30 steps"); // (before a slot is touched: run_steps would refuse it)
     if (!h->copy_stream) HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
@@ -3402,6 +3542,7 @@ extern "C" int smolmc_replay(smolmc_handle *h, int64_t nsteps, const int32_t *st
                              double *log_priori_out) {
     if (!h || !steps || !uniforms) return fail("null argument");
     if (!h->walker_mu.empty()) return fail("smolmc_replay while per-walker chemical potentials are set: the replay kernels price every walker with the handle's own table (smolmc_set_walker_mu(h, NULL) first)");
+    if (!h->wl_win_min.empty()) return fail("smolmc_replay while per-walker windows are set: the replay kernels give every walker the config's window (smolmc_set_wl_windows(h, NULL, NULL) first)");
     if (nsteps <= 0) return 0;
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)h->R * nsteps;

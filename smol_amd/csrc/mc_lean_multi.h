@@ -78,10 +78,16 @@ __device__ __noinline__ void wl_multi_row_swap(double *grows, double *crow, int 
 // LeanParams::dtk, at the table index the decision computed) and adds K feature deltas.
 // EWX = EWM, + 4 (multi_wmu_n*.hip only): per-walker chemical potentials, the [4][8] rows of walker r in a cell of its
 // own wave (see mc_lean_kernel)
-template <int NSLOT, int MM, int STEP, bool HAS_MU, int EWX, bool ONE = false, bool BIAS = false, bool REPLAY = false, int WLK = 0>
+// WLX = WLK, + 4 (multi_wl_win_n*.hip only): per-walker Wang-Landau windows (smolmc_set_wl_windows) -- the walker reads its
+// record {vmin, vmax, estimator} once, and every Wang-Landau array row (entropy, histogram, occurrences, feature rows,
+// modification factor) is the ESTIMATOR's, not the walker's; counter, Philox stream and configuration stay the walker's
+template <int NSLOT, int MM, int STEP, bool HAS_MU, int EWX, bool ONE = false, bool BIAS = false, bool REPLAY = false, int WLX = 0>
 __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) {
     constexpr int EWM = EWX & 3;
     constexpr bool WMU = (EWX & 4) != 0;
+    constexpr int WLK = WLX & 3;
+    constexpr bool WWIN = (WLX & 4) != 0;
+    static_assert(!WWIN || (WLK == 1 && !REPLAY), "per-walker windows: the plain Wang-Landau variants");
     static_assert(!WMU || (HAS_MU && !WLK && !REPLAY), "per-walker chemical potentials: semigrand Metropolis variants");
     static_assert(!(WLK && BIAS), "Cannot apply bias to Wang-Landau simulation (wanglandau.py:127-128)");
     constexpr bool KFW = WLK == 2;
@@ -91,6 +97,11 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
     const int wave = threadIdx.x >> 6;
     const int nwaves = blockDim.x >> 6;
     const int r = uni(blockIdx.x * nwaves + wave);
+    // (WWIN) the walker's window record; wr: the row of the Wang-Landau arrays this walker updates
+    const WlWindow *const wwin = WWIN ? wl_window_of(P, r < P.R ? r : 0) : nullptr;
+    // (a macro, not a variable: a second name for r in the kernels without windows changes the code of some of them)
+    const int west = WWIN ? uni(wwin->est) : 0;
+#define wr (WWIN ? west : r)
     const int NC = P.m_ncls, NS = P.m_nsub;
     // block-shared: delta tables | mu rows [4][8] | q rows [4][8] | dg rows [4][8] | slot records
     double *s_dt = (double *)smem;
@@ -151,9 +162,9 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
             for (int i = lane; i < nrec; i += 64) s_acc[i] = 0.0;
         if (WLK) {
             for (int i = lane; i < P.wl.L; i += 64) {
-                wl_S[i] = P.wl.entropy[(size_t)r * P.wl.L + i];
+                wl_S[i] = P.wl.entropy[(size_t)wr * P.wl.L + i];
                 wl_cnt[i] = 0u;
-                if (!wl_sum_mode) wl_occb[i] = (double)P.wl.occur[(size_t)r * P.wl.L + i];
+                if (!wl_sum_mode) wl_occb[i] = (double)P.wl.occur[(size_t)wr * P.wl.L + i];
             }
             if (!wl_sum_mode)
                 for (int i = lane; i < SMOLMC_WL_ROWS * P.F; i += 64) s_rows[i] = 0.0;
@@ -185,8 +196,9 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
     // ---- Wang-Landau state (WLK) ----
     double fcur = base_feat;                  // lane f < F: the walker's current feature vector (_current_features)
     double Hcur = H;                          // _current_enthalpy (wanglandau.py:216-218)
-    const double wl_vmin = WLK ? P.wl.vmin : 0.0, wl_bin = WLK ? P.wl.bin : 1.0, wl_inv_bin = 1.0 / wl_bin;
-    double wl_m = WLK ? P.wl.m[r] : 0.0;
+    const double wl_vmin = WWIN ? uni_d(wwin->vmin) : WLK ? P.wl.vmin : 0.0, wl_bin = WLK ? P.wl.bin : 1.0, wl_inv_bin = 1.0 / wl_bin;
+    const double wl_vmax_w = WWIN ? uni_d(wwin->vmax) : 0.0;
+    double wl_m = WLK ? P.wl.m[wr] : 0.0;
     int wb = 0;                               // current bin (walkers start inside the window: smolmc_set_state)
     if (WLK) wb = min(max(uni((int)floordiv_exact(Hcur - wl_vmin, wl_bin)), 0), P.wl.L - 1);
     const long long wl_counter0 = WLK ? P.wl.counter[r] : 0;
@@ -211,7 +223,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
         double *crow = s_rows + (uint32_t)slot * (uint32_t)P.F;
         if (tag != bin) {
             const LeanParamsKernarg Q = rare_params();
-            wl_multi_row_swap(Q->wl.meanf + (size_t)r * Q->wl.L * Q->F, crow, tag, bin, Q->F, lane, wl_sum_mode);
+            wl_multi_row_swap(Q->wl.meanf + (size_t)wr * Q->wl.L * Q->F, crow, tag, bin, Q->F, lane, wl_sum_mode);
             vtag = lane == slot ? bin : vtag;
         }
         return crow;
@@ -228,7 +240,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
     const int wl_epi = max(1, 64 / max(P.F, 1)), wl_lane_e = lane / max(P.F, 1), wl_lane_f = lane - wl_lane_e * P.F;
     auto wl_log_flush = [&]() {
         const LeanParamsKernarg Q = rare_params();
-        double *grows = Q->wl.meanf + (size_t)r * Q->wl.L * Q->F;
+        double *grows = Q->wl.meanf + (size_t)wr * Q->wl.L * Q->F;
         const int qF = Q->F;
         for (int base = 0; base < wl_nlog; base += wl_epi) {
             const int e = base + wl_lane_e;
@@ -680,7 +692,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
                                      : __hiloint2double((int)rdlane((uint32_t)__double2hiint(logu), l4),
                                                         (int)rdlane((uint32_t)__double2loint(logu), l4));
             const double new_h = Hcur + dH;
-            if (__ballot(!(new_h < wl_vmin || new_h >= P.wl.vmax)) != 0ull) {
+            if (__ballot(!(new_h < wl_vmin || new_h >= (WWIN ? wl_vmax_w : P.wl.vmax))) != 0ull) {
                 wnb = uni((int)floordiv_exact_inv(new_h - wl_vmin, wl_bin, wl_inv_bin));
                 const double ex = wl_S[wb] - wl_S[wnb] + 0.0; // (+ log a-priori factor: 0 for flips / swaps)
                 accepted = __ballot((ex >= 0.0) || (ex > lu)) != 0ull;
@@ -834,7 +846,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
             if (++wl_rem_check == wl_check) wl_rem_check = 0u;
             if (wl_rem_check == 0u) {
                 const LeanParamsKernarg Q = rare_params();
-                const size_t o = (size_t)r * Q->wl.L;
+                const size_t o = (size_t)wr * Q->wl.L;
                 wl_m = wl_multi_flatness_check(wl_S, wl_cnt, wl_sum_mode ? nullptr : wl_occb, Q->wl.hist + o, Q->wl.occur + o,
                                                Q->wl.L, Q->wl.flat, Q->wl.div, wl_m, lane);
             }
@@ -915,11 +927,11 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
             for (int slot = 0; slot < SMOLMC_WL_ROWS; ++slot) { // cached rows (running means) back to HBM
                 const int tag = (int)rdlane((uint32_t)vtag, slot);
                 if (tag >= 0 && lane < P.F)
-                    P.wl.meanf[((size_t)r * P.wl.L + tag) * P.F + lane] = s_rows[(uint32_t)slot * (uint32_t)P.F + lane];
+                    P.wl.meanf[((size_t)wr * P.wl.L + tag) * P.F + lane] = s_rows[(uint32_t)slot * (uint32_t)P.F + lane];
             }
         }
         for (int i = lane; i < P.wl.L; i += 64) {
-            const size_t o = (size_t)r * P.wl.L + i;
+            const size_t o = (size_t)wr * P.wl.L + i;
             P.wl.entropy[o] = wl_S[i];
             P.wl.hist[o] += (long long)wl_cnt[i];
             P.wl.occur[o] += (long long)wl_cnt[i];
@@ -927,7 +939,7 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
         if (lane < P.F) featp[lane] = fcur;
         H = Hcur;
         if (lane == 0) {
-            P.wl.m[r] = wl_m;
+            P.wl.m[wr] = wl_m;
             P.wl.counter[r] = wl_counter0 + (long long)nsteps32;
         }
     } else {
@@ -960,17 +972,20 @@ __global__ void __launch_bounds__(512) mc_lean_multi_kernel(const LeanParams P) 
     if (REPLAY && lane == 0 && rp_bad) atomicOr(P.rp_err, 1);
 }
 
+#undef wr
+
 // ---- kernel dispatch (launch.h) -------------------------------------------------
 // mc_lean_multi_kernel's template arguments after NSLOT, MM, STEP, as the flags of a variant word
 enum : unsigned {
     MV_EW = 3, // (the Ewald mode itself: 0 absent, 1 the field in LDS, 2 in HBM)
     MV_MU = 4, MV_REG = 8, MV_BIAS = 16, MV_REPLAY = 32,
     MV_WL = 64, MV_WL_KF = 128, // (WLK 1 and 2: Wang-Landau, and with several correlation functions per orbit)
-    MV_WMU = 256 // per-walker chemical potentials (bit 2 of the kernel's EWX)
+    MV_WMU = 256, // per-walker chemical potentials (bit 2 of the kernel's EWX)
+    MV_WWIN = 512 // per-walker Wang-Landau windows (bit 2 of the kernel's WLX)
 };
 template <int NSLOT, int MM, int STEP, unsigned V> static auto multi_variant() {
     return mc_lean_multi_kernel<NSLOT, MM, STEP, bool(V & MV_MU), int(V & MV_EW) | ((V & MV_WMU) ? 4 : 0), bool(V & MV_REG), bool(V & MV_BIAS), bool(V & MV_REPLAY),
-                                (V & MV_WL_KF) ? 2 : (V & MV_WL) ? 1 : 0>;
+                                ((V & MV_WL_KF) ? 2 : (V & MV_WL) ? 1 : 0) | ((V & MV_WWIN) ? 4 : 0)>;
 }
 // Every family of this kernel has the same variants, (mu, Ewald mode), in the same order (the order of the
 // kernels in the code object, see launch.h); B: the flags the family fixes
@@ -1007,6 +1022,8 @@ template <int NSLOT> static int launch_multi_replay_nslot(smolmc_handle *h, cons
 template <int NSLOT> static int launch_multi_bias_replay_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_multi_variant<NSLOT, MV_BIAS | MV_REPLAY>(h, lp); }
 // Wang-Landau variants: B = MV_WL (multi_wl_n*.hip), MV_WL | MV_REPLAY (multi_wl_replay_n*.hip), MV_WL_KF (multi_wl_kf_n*.hip)
 template <int NSLOT, unsigned B> static int launch_multi_wl_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_multi_variant<NSLOT, B>(h, lp); }
+// ... with per-walker windows (multi_wl_win_n*.hip only)
+template <int NSLOT> static int launch_multi_wl_win_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_multi_variant<NSLOT, MV_WL | MV_WWIN>(h, lp); }
 
 
 // ----------------------------------------------------------------------------

@@ -68,8 +68,14 @@ __device__ __noinline__ void wl_evict_row(double *grow, double *crow, int F, int
 // EWF: Ewald term from the walker's potential field in LDS: O(1) per proposal, one field
 // sweep per accepted step; these steps take the exact float64 decision (the Ewald delta is of the
 // order of eV and would have to be carried through the float32 error bound).
-template <int NSLOT, int MM, int STEP, bool REPLAY = false, bool HAS_MU = false, bool EWF = false>
+// STEPX = STEP, + 16 (wl_win_n*.hip only): per-walker windows (smolmc_set_wl_windows) -- the walker reads its record
+// {vmin, vmax, estimator} once, and every Wang-Landau array row (entropy, histogram, occurrences, feature sums,
+// modification factor) is the ESTIMATOR's, not the walker's; counter, Philox stream and configuration stay the walker's
+template <int NSLOT, int MM, int STEPX, bool REPLAY = false, bool HAS_MU = false, bool EWF = false>
 __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
+    constexpr int STEP = STEPX & 15;
+    constexpr bool WWIN = (STEPX & 16) != 0;
+    static_assert(!WWIN || !REPLAY, "per-walker windows: no replay variant");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = uni((int)(threadIdx.x >> 6));
@@ -77,6 +83,11 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
     const int slot = uni(blockIdx.x * nwaves + wave);
     // (group rotation, see launch_wl_kern: the walker of a launch slot)
     const int r = P.launch_slots ? ((P.rot_j + slot / P.rot_s) % P.rot_g) * P.rot_s + slot % P.rot_s : slot;
+    // (WWIN) the walker's window record; wr: the row of the Wang-Landau arrays this walker updates
+    const WlWindow *const wwin = WWIN ? wl_window_of(P, r < P.R ? r : 0) : nullptr;
+    // (a macro, not a variable: a second name for r in the kernels without windows changes the code of some of them)
+    const int west = WWIN ? uni(wwin->est) : 0;
+#define wr (WWIN ? west : r)
     const size_t per_wave = (size_t)P.Nlds + 64 * 8 + 64 + wl_lean_bins_bytes(P.wl.L) + (size_t)WL_ROWS * P.F * 8 +
                             (EWF ? (size_t)P.ew_nact * 8 : 0);
     double *s_dt = (double *)smem;
@@ -111,7 +122,7 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
             *(uint32_t *)(occ + lean_swz(4 * i, swa, swm, swb)) = src[i];
         s_cell[lane] = 0.0;
         for (int i = lane; i < P.wl.L; i += 64) {
-            wl_S[i] = P.wl.entropy[(size_t)r * P.wl.L + i];
+            wl_S[i] = P.wl.entropy[(size_t)wr * P.wl.L + i];
             wl_cnt[i] = 0u;
         }
         if (lane < 2) wl_S[lane ? P.wl.L : -1] = 0.0;
@@ -161,10 +172,11 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
     double *featp = P.features + (size_t)r * P.F;
     const double f0 = lane < P.F ? featp[lane] : 0.0; // feature vector at launch start
     const double H0 = P.enthalpy[r];
-    const double vmin = P.wl.vmin, span = P.wl.vmax - P.wl.vmin, bin = P.wl.bin;
+    const double vmax_w = WWIN ? uni_d(wwin->vmax) : 0.0;
+    const double vmin = WWIN ? uni_d(wwin->vmin) : P.wl.vmin, span = (WWIN ? vmax_w : P.wl.vmax) - vmin, bin = P.wl.bin;
     const double inv_bin = 1.0 / bin;
     const int Lm1 = P.wl.L - 1;
-    double wl_m = P.wl.m[r];
+    double wl_m = P.wl.m[wr];
     // current bin (walkers start inside the window: smolmc_set_state refuses anything else);
     // uniform values are kept visibly uniform (readfirstlane / ballot) so that the bookkeeping
     // below compiles to scalar code and scalar branches
@@ -237,7 +249,7 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
         if (tag != pend_bin) {
             if (tag >= 0) {
                 const LeanParamsKernarg Q = rare_params();
-                wl_evict_row(Q->wl.meanf + ((size_t)r * Q->wl.L + tag) * Q->F, crow, Q->F, lane);
+                wl_evict_row(Q->wl.meanf + ((size_t)wr * Q->wl.L + tag) * Q->F, crow, Q->F, lane);
             }
             vtag = lane == slot ? pend_bin : vtag;
         }
@@ -554,7 +566,7 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
                 since_sync = 0;
                 force_exact = never_fast;
                 dHa = dH;
-                if (__ballot(!(new_h < vmin || new_h >= P.wl.vmax)) != 0ull) {
+                if (__ballot(!(new_h < vmin || new_h >= (WWIN ? vmax_w : P.wl.vmax))) != 0ull) {
                     nb = uni((int)floordiv_exact_inv(new_h - vmin, bin, inv_bin));
                     const double ex = win - *WL_LDS_F64P(rec0 + 8u * (uint32_t)nb) + 0.0;
                     accepted = ((__ballot((ex >= 0.0) | (ex > lu)) >> 8) & 1ull) != 0ull;
@@ -623,7 +635,7 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
             }
             if (wl_rem_check == 0) {
                 const LeanParamsKernarg Q = rare_params();
-                const size_t o = (size_t)r * Q->wl.L;
+                const size_t o = (size_t)wr * Q->wl.L;
                 wl_m = wl_multi_flatness_check(wl_S, wl_cnt, nullptr, Q->wl.hist + o, Q->wl.occur + o, Q->wl.L, Q->wl.flat,
                                                Q->wl.div, wl_m, lane);
             }
@@ -666,7 +678,7 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
     for (int slot = 0; slot < WL_ROWS; ++slot) { // write the cached rows back
         const int tag = (int)rdlane((uint32_t)vtag, slot);
         if (tag >= 0 && lane < P.F)
-            unsafeAtomicAdd(P.wl.meanf + ((size_t)r * P.wl.L + tag) * P.F + lane, s_rows[(uint32_t)slot * rowF + lane]);
+            unsafeAtomicAdd(P.wl.meanf + ((size_t)wr * P.wl.L + tag) * P.F + lane, s_rows[(uint32_t)slot * rowF + lane]);
     }
     {
         uint32_t *dst = (uint32_t *)(P.occ + (size_t)r * P.Npad);
@@ -680,7 +692,7 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
     if (EWF)
         for (int j = lane; j < P.ew_nact; j += 64) P.ew_phi[(size_t)r * P.ew_nact + j] = phi[j];
     for (int i = lane; i < P.wl.L; i += 64) {
-        const size_t o = (size_t)r * P.wl.L + i;
+        const size_t o = (size_t)wr * P.wl.L + i;
         P.wl.entropy[o] = wl_S[i];
         P.wl.hist[o] += (long long)wl_cnt[i];
         P.wl.occur[o] += (long long)wl_cnt[i];
@@ -688,7 +700,7 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
     if (REPLAY && lane == 0 && rp_bad) atomicOr(P.rp_err, 1);
     const double Hend = exact_enthalpy();
     if (lane == 0) {
-        P.wl.m[r] = wl_m;
+        P.wl.m[wr] = wl_m;
         P.wl.counter[r] = wl_counter0 + (long long)(uint32_t)P.steps;
         P.enthalpy[r] = Hend;
         P.nsteps[r] = step;
@@ -699,11 +711,12 @@ __global__ void __launch_bounds__(256) mc_wl_kernel(const LeanParams P) {
 
 #undef key0
 #undef key1
+#undef wr
 
 static long wl_gcd(long a, long b) { while (b) { const long t = a % b; a = b; b = t; } return a; }
 
 // mc_wl_kernel's template arguments after NSLOT, MM, STEP, as the flags of a variant word
-enum : unsigned { WV_REPLAY = 1, WV_MU = 2, WV_EW = 4 };
+enum : unsigned { WV_REPLAY = 1, WV_MU = 2, WV_EW = 4, WV_WIN = 8 }; // (WV_WIN: per-walker windows, bit 4 of the kernel's STEPX)
 
 // Launch.  GROUP ROTATION (round 5): the kernel's residency is set by LDS -- config 4: three four-walker
 // workgroups per CU, 3072 walkers on 256 CUs -- and a step of this kernel takes as long at three waves per SIMD as
@@ -718,7 +731,7 @@ enum : unsigned { WV_REPLAY = 1, WV_MU = 2, WV_EW = 4 };
 template <int NSLOT, int MM, int STEP, unsigned V>
 static int launch_wl_kern(smolmc_handle *h, const LeanParams &lp) {
     constexpr bool REPLAY = V & WV_REPLAY;
-    auto kern = mc_wl_kernel<NSLOT, MM, STEP, REPLAY, bool(V & WV_MU), bool(V & WV_EW)>;
+    auto kern = mc_wl_kernel<NSLOT, MM, STEP | ((V & WV_WIN) ? 16 : 0), REPLAY, bool(V & WV_MU), bool(V & WV_EW)>;
     if (h->lean_lds > 64 * 1024)
         HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lean_lds));
     long C = 0;
@@ -764,3 +777,5 @@ template <int NSLOT, unsigned B> static int launch_wl_variant(smolmc_handle *h, 
 }
 template <int NSLOT> static int launch_wl_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_wl_variant<NSLOT, 0>(h, lp); }
 template <int NSLOT> static int launch_wl_replay_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_wl_variant<NSLOT, WV_REPLAY>(h, lp); }
+// ... with per-walker windows (wl_win_n*.hip only)
+template <int NSLOT> static int launch_wl_win_nslot(smolmc_handle *h, const LeanParams &lp) { return launch_wl_variant<NSLOT, WV_WIN>(h, lp); }

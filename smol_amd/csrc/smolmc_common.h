@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -505,6 +506,10 @@ __device__ __forceinline__ void field_sweep_gx_multi(double *phi, const uint32_t
 // ----------------------------------------------------------------------------
 struct WlParams { // Wang-Landau state of the walkers (kernel/wanglandau.py:107-122)
     int L;
+    // (in the padding behind L: no other offset of this block moves) per-walker windows (smolmc_set_wl_windows): the
+    // walkers' records, WlWindow [R], start this many bytes behind m[0] -- m heads the arena that holds them.  Read by
+    // the window variants of the kernels only (wl_win_n*.hip, multi_wl_win_n*.hip); 0: no windows set.
+    uint32_t win_off;
     double vmin, vmax, bin, flat, div;
     long long check, update;
     double *entropy;     // [R][L]
@@ -515,6 +520,14 @@ struct WlParams { // Wang-Landau state of the walkers (kernel/wanglandau.py:107-
                          // read-modify-write round trip per step; converted when read)
     double *m;           // [R]
     long long *counter;  // [R]
+};
+
+static_assert(sizeof(WlParams) == 120 && offsetof(WlParams, vmin) == 8, "WlParams keeps its size and offsets");
+// Per-walker Wang-Landau window: walker r samples [vmin, vmax) with the handle's bin size and updates the arrays of
+// estimator `est` (rows est of entropy / hist / occur / meanf, m[est]).  wl_exchange_kernel swaps two walkers' records.
+struct WlWindow {
+    double vmin, vmax;
+    int32_t est, pad;
 };
 
 struct LeanSlot {
@@ -618,6 +631,9 @@ struct LeanParams {
 };
 
 __device__ __forceinline__ int lean_swz(int s, int a, int m, int b) { return s ^ (((s >> a) & m) << b); }
+__device__ __forceinline__ const WlWindow *wl_window_of(const LeanParams &P, int r) {
+    return (const WlWindow *)((const unsigned char *)P.wl.m + P.wl.win_off) + r;
+}
 // LDS the per-wave chemical-potential cells of a launch with `waves` waves per workgroup add behind lds (see mu_stride)
 // (+ 8: the cells start at the next multiple of 8 bytes)
 static inline size_t walker_mu_lds(int mu_stride, int waves) { return mu_stride ? (size_t)waves * (size_t)mu_stride * 8 + 8 : 0; }
@@ -805,6 +821,14 @@ struct smolmc_handle {
     int32_t *d_point_of = nullptr, *d_walker_at = nullptr;
     double *d_gx_stage = nullptr;
     bool grid_permuted = false, point_T_stale = false;
+    // per-walker Wang-Landau windows (smolmc_set_wl_windows, engine.hip): the windows in ESTIMATOR order as given there
+    // (empty: none set, every walker has the config's window).  On the device, behind kp.wl_m in one arena: the walkers'
+    // records WlWindow [R] (lp.wl.win_off) and the inverse map estimator -> walker, int32 [R] (d_wl_walker_at); behind
+    // them the staging of an exchange call (log u | pairs | accept flags, allocated at the first one).
+    std::vector<double> wl_win_min, wl_win_max;
+    WlWindow *d_wl_win = nullptr;
+    int32_t *d_wl_walker_at = nullptr;
+    double *d_wlx_stage = nullptr;
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
     SampleSlot slots[2];
@@ -906,6 +930,9 @@ int smolmc_walker_mu_reprice(smolmc_handle *h, const double *rows_old, int strid
 // arrays; the pairs disjoint), decided and applied on the device, queued on the handle's stream
 int smolmc_grid_exchange_launch(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int32_t *accepted,
                                 int32_t *point_of, int32_t *walker_at);
+// wl_exchange.hip: one exchange attempt between the walkers that hold the estimators pairs[p][0] and pairs[p][1]
+// (device arrays; the pairs disjoint), decided and applied on the device, queued on the handle's stream
+int smolmc_wl_exchange_launch(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int32_t *accepted);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);
 int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_4(smolmc_handle *h, const KParams &kp, int replay);
@@ -930,6 +957,8 @@ int smolmc_launch_lean_rows_2(smolmc_handle *h, const LeanParams &lp);
 // per-walker chemical potentials (lean_wmu_n*.hip, multi_wmu_n*.hip)
 SMOLMC_LAUNCHERS2(lean_wmu) SMOLMC_LAUNCHERS2(lean_bias_wmu) SMOLMC_LAUNCHERS2(lean_corr_wmu) SMOLMC_LAUNCHERS2(table_bias_wmu)
 SMOLMC_LAUNCHERS3(multi_wmu) SMOLMC_LAUNCHERS3(multi_bias_wmu) SMOLMC_LAUNCHERS3(multi_table_bias_wmu)
+// per-walker Wang-Landau windows (wl_win_n*.hip, multi_wl_win_n*.hip)
+SMOLMC_LAUNCHERS2(wl_win) SMOLMC_LAUNCHERS3(multi_wl_win)
 #undef SMOLMC_LAUNCHERS2
 #undef SMOLMC_LAUNCHERS3
 #define SMOLMC_WL_ROWS 32  // mc_wl_kernel: cached rows of per-bin feature sums per walker (LDS)

@@ -37,6 +37,9 @@ SYMBOLS = {
     "smolmc_get_walker_mu": (C.c_int, [_HP, _f64p]),
     "smolmc_exchange_grid": (C.c_int, [_HP, C.c_int, _i32p, _f64p, _i64p]),
     "smolmc_get_state_points": (C.c_int, [_HP, _i32p, _f64p]),
+    "smolmc_set_wl_windows": (C.c_int, [_HP, _f64p, _f64p]),
+    "smolmc_get_wl_windows": (C.c_int, [_HP, _f64p, _f64p, _i32p]),
+    "smolmc_exchange_wl": (C.c_int, [_HP, C.c_int, _i32p, _f64p, _i64p]),
     "smolmc_get_state": (C.c_int, [_HP, _i32p, _f64p, _f64p, _u64p, _u64p, _u8p]),
     "smolmc_get_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
     "smolmc_set_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
@@ -288,6 +291,43 @@ class Engine:
         point_of, temp = np.empty(self.R, dtype=np.int32), np.empty(self.R)
         self._chk(self._lib.smolmc_get_state_points(self._h, _p(point_of, C.c_int32), _p(temp, C.c_double)))
         return point_of, temp
+
+    # ---- per-walker Wang-Landau windows -----------------------------------------------
+    def set_wl_windows(self, vmin, vmax):
+        """Per-walker energy windows of a Wang-Landau handle (smolmc_set_wl_windows): walker r samples
+        ``[vmin[r], vmax[r])`` with the handle's bin size; every window must give the handle's ``L`` by the rule
+        ``ceil((vmax - vmin) / bin_size)``.  Estimator e is the window and density-of-states copy walker e holds after
+        this call; ``get_wl`` / ``set_wl`` are in estimator order.  ``None, None`` returns to the config's window."""
+        if (vmin is None) != (vmax is None):
+            raise ValueError("vmin and vmax are given together, or both None")
+        if vmin is not None:
+            vmin = np.ascontiguousarray(vmin, dtype=np.float64).reshape(-1)
+            vmax = np.ascontiguousarray(vmax, dtype=np.float64).reshape(-1)
+            if len(vmin) != self.R or len(vmax) != self.R:
+                raise ValueError(f"expected one window per walker: {self.R} walkers, {len(vmin)} / {len(vmax)} values")
+        self._chk(self._lib.smolmc_set_wl_windows(self._h, _p(vmin, C.c_double), _p(vmax, C.c_double)))
+
+    def wl_windows(self):
+        """(vmin (R,), vmax (R,), estimator_of (R,) int32): the window every walker holds now and the estimator it
+        belongs to (smolmc_get_wl_windows); the config's window and the identity while no windows are set."""
+        vmin, vmax, est = np.empty(self.R), np.empty(self.R), np.empty(self.R, dtype=np.int32)
+        self._chk(self._lib.smolmc_get_wl_windows(self._h, _p(vmin, C.c_double), _p(vmax, C.c_double), _p(est, C.c_int32)))
+        return vmin, vmax, est
+
+    def exchange_wl(self, pairs, log_u, stats=None):
+        """One replica-exchange attempt between energy windows, decided and applied on the device
+        (smolmc_exchange_wl): for every pair (s, t) of ``pairs`` (npairs, 2) the walkers that hold the estimators s and
+        t swap them when both enthalpies lie in both windows and the move is accepted against ``log_u`` (npairs).
+        ``stats`` as in ``exchange_grid``."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        log_u = np.ascontiguousarray(log_u, dtype=np.float64).reshape(-1)
+        if len(log_u) != len(pairs):
+            raise ValueError(f"expected one log_u per pair: {len(pairs)} pairs, {len(log_u)} values")
+        if stats is not None and not (isinstance(stats, np.ndarray) and stats.dtype == np.int64 and stats.flags.c_contiguous
+                                      and stats.shape == (len(pairs), 2)):
+            raise ValueError(f"stats must be a C-contiguous int64 array of shape ({len(pairs)}, 2)")
+        self._chk(self._lib.smolmc_exchange_wl(self._h, len(pairs), _p(pairs, C.c_int32), _p(log_u, C.c_double),
+                                               _p(stats, C.c_int64)))
 
     def species_counts(self, occupancies):
         """Species counts per (active sublattice, code) of occupancies (n, N), in the layout of ``set_walker_mu``."""

@@ -1712,13 +1712,24 @@ class Sampler:
         self._kept_last = False     # the container holds the one sample a streamed run kept (keep_last_chunk)
         self._walker_mu = None      # per-walker chemical potentials of this rank's walkers (list of dicts), or None
         self._walker_mu_dirty = False  # ... not yet on the engine
+        self._wl_windows = None     # replica-exchange Wang-Landau: the parallel.WLWindows of this sampler's walkers
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
-                      nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, **kwargs):
+                      nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, windows=None,
+                      **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
-        'swap'; default kernel Metropolis; one kernel (seed) per walker."""
+        'swap'; default kernel Metropolis; one kernel (seed) per walker.
+
+        ``windows``: a ``parallel.WLWindows`` -- replica-exchange Wang-Landau.  ``min_enthalpy``, ``max_enthalpy``
+        and ``bin_size`` are then the GLOBAL range the windows cut up; kernel w is estimator w of ``windows`` and is
+        built with that estimator's window (its ``levels`` / ``entropy`` / ``histogram`` are the estimator's, whichever
+        walker updates it), ``nwalkers`` defaults to ``windows.R``, and ``run_exchange`` samples with exchanges."""
         from . import parallel
+
+        if windows is not None:
+            return cls._from_ensemble_windows(ensemble, windows, *args, step_type=step_type, kernel_type=kernel_type, seeds=seeds,
+                                              nwalkers=nwalkers, rank=rank, world_size=world_size, device=device, **kwargs)
 
         if step_type is None:
             step_type = "flip" if ensemble.chemical_potentials is not None else "swap"
@@ -1741,6 +1752,49 @@ class Sampler:
         sampler = cls(kernels, container, walker_range=(first, count), device=device, world_size=world_size)
         if chemical_potentials is not None:
             sampler.set_chemical_potentials(chemical_potentials)
+        return sampler
+
+    @classmethod
+    def _from_ensemble_windows(cls, ensemble, wx, *args, step_type=None, kernel_type=None, seeds=None, nwalkers=1, rank=None,
+                               world_size=None, device=None, min_enthalpy=None, max_enthalpy=None, bin_size=None, **kwargs):
+        from . import parallel
+
+        if min_enthalpy is None and len(args) >= 3:  # (the reference's positional spelling)
+            min_enthalpy, max_enthalpy, bin_size, args = args[0], args[1], args[2], args[3:]
+        if min_enthalpy is None or max_enthalpy is None or bin_size is None:
+            raise ValueError("windows= needs min_enthalpy, max_enthalpy and bin_size: the global range the windows cut up")
+        if KERNELS.get(str(kernel_type).lower().replace("_", "")) is not WangLandau:
+            raise ValueError("windows= needs kernel_type='Wang-Landau'")
+        if (float(min_enthalpy), float(max_enthalpy), float(bin_size)) != (wx.min_enthalpy, wx.max_enthalpy, wx.bin_size):
+            raise ValueError(f"min_enthalpy, max_enthalpy, bin_size = {(min_enthalpy, max_enthalpy, bin_size)} are not the "
+                             f"global range of the windows, {(wx.min_enthalpy, wx.max_enthalpy, wx.bin_size)}")
+        if nwalkers in (1, None):
+            nwalkers = wx.R
+        if nwalkers != wx.R:
+            raise ValueError(f"the windows have {wx.R} estimators, the sampler {nwalkers} walkers")
+        if rank is None or world_size is None:
+            rank, world_size = parallel.rank_and_world()
+        if world_size != 1:
+            raise ValueError("replica-exchange Wang-Landau runs inside one engine handle: no sharding over ranks")
+        if seeds is not None and len(seeds) != nwalkers:
+            raise ValueError("Number of seeds does not match number of kernels!")
+        if step_type is None:
+            step_type = "flip" if ensemble.chemical_potentials is not None else "swap"
+        kernels = []
+        for e in range(wx.R):
+            k = WangLandau(ensemble, step_type, float(wx.vmin[e]), float(wx.vmax[e]), wx.bin_size, *args,
+                           seed=None if seeds is None else seeds[e], **kwargs)
+            k._levels = wx.vmin[e] + np.arange(wx.Lw) * wx.bin_size  # (exactly Lw levels, as the engine counts them)
+            k.spec.update(levels=k._levels.tolist(), window=int(wx.window_of[e]), copy=int(wx.copy_of[e]))
+            kernels.append(k)
+        container = cls._container_for(ensemble, kernels[0], wx.R)
+        container._schema["wl_estimator"] = (np.dtype(np.int32), (wx.R, 1))
+        container.metadata["walker_range"] = (0, wx.R, wx.R)
+        container.metadata["wl_windows"] = dict(min_enthalpy=wx.min_enthalpy, max_enthalpy=wx.max_enthalpy, bin_size=wx.bin_size,
+                                                n_windows=wx.n_windows, copies=wx.copies, window_bins=wx.Lw, stride_bins=wx.Ls)
+        sampler = cls(kernels, container, walker_range=(0, wx.R), device=parallel.local_device(rank) if device is None else device,
+                      world_size=1)
+        sampler._wl_windows = wx
         return sampler
 
     @property
@@ -1900,6 +1954,8 @@ class Sampler:
                 cfg = capi.make_config(len(self._kernels), capi.KERNEL_METROPOLIS,
                                        STEP_TYPES[k0.step_type], self._device)
             self._engine = Engine(tables, cfg, distance=dist)
+            if self._wl_windows is not None:  # (kernel e was built with estimator e's window: cfg holds window 0)
+                self._engine.set_wl_windows(self._wl_windows.vmin, self._wl_windows.vmax)
             self._engine_key = key
             self._state_loaded = False
             self._walker_mu_dirty = self._walker_mu is not None
@@ -1996,9 +2052,22 @@ class Sampler:
         if is_wl and k0._mod_callable is not None:
             # a callable mod_update (wanglandau.py:100-105): the flatness checks run on the host between
             # launches, so these samples come back one launch at a time
+            if self._wl_windows is not None:
+                raise ValueError("a callable mod_update with per-walker windows: the host-side check is walker-indexed")
             for _ in range(nsamples):
                 self._wl_run_with_host_checks(eng, thin_by)
                 yield {k: v[None] for k, v in self._current_trace(eng).items()}
+            return
+        if is_wl and self._wl_windows is not None:
+            # per-walker windows: the Wang-Landau arrays are estimator-indexed and the ring's snapshot rows
+            # walker-indexed (smolmc_run_sampled refuses that column), so these samples too come back one launch at a
+            # time; occupancy, features, enthalpy: by walker; the Wang-Landau arrays: by ESTIMATOR; wl_estimator: the
+            # estimator every walker holds
+            for _ in range(nsamples):
+                eng.run(thin_by)
+                tr = {k: v[None] for k, v in self._current_trace(eng).items()}
+                tr["wl_estimator"] = eng.wl_windows()[2].reshape(1, -1, 1)
+                yield tr
             return
         nw, N = len(self._kernels), k0.ensemble.num_sites
         # bytes of one sample of all walkers in the ring: occupancy bytes + features (+ the Wang-Landau trace:
@@ -2157,8 +2226,45 @@ class Sampler:
         # the device now holds the last recorded sample (see _load_state)
         self._resume_at = (id(self.samples), self.samples.num_samples)
 
-    def run_exchange(self, n_exchanges, steps_between, initial_occupancies=None, thin_by=None, grid=None):
-        """Sampling with replica exchange across a mu-T grid (hyper-parallel tempering): ``n_exchanges`` times
+    def _run_exchange_wl(self, n_exchanges, steps_between, initial_occupancies, thin_by, wx):
+        """run_exchange for replica-exchange Wang-Landau, see there."""
+        if wx is not self._wl_windows:
+            raise ValueError("run_exchange(windows=) takes the WLWindows this sampler was built with (Sampler.from_ensemble(windows=))")
+        thin_by = int(steps_between if thin_by is None else thin_by)
+        if initial_occupancies is None and self.samples.num_samples == 0:
+            raise RuntimeError("There are no saved samples to obtain the initial occupancies."
+                               "These must be provided.")
+        self._load_state(initial_occupancies)
+        eng = self._get_engine()
+        for _ in range(int(n_exchanges)):
+            for block in self._sample_blocks(steps_between, None, thin_by, state_loaded=True):
+                self.samples.append_block(block, thinned_by=thin_by)
+            move = wx.move_of(wx.calls)
+            pairs = wx.pairs(move)
+            stats = np.zeros((len(pairs), 2), dtype=np.int64)
+            eng.exchange_wl(pairs, wx.log_u(wx.calls, len(pairs)), stats)
+            wx.record(move, stats[:, 1])
+            wx.calls += 1
+        wx.estimator_of = eng.wl_windows()[2].astype(np.int64)
+        self._resume_at = None  # (the last sample precedes the last exchange: a continuation reloads nothing it could trust)
+        return wx
+
+    def wl_joined_entropy(self):
+        """(levels (L,), ln g (L,), visited (L,) bool) over the GLOBAL bin grid of a sampler built with ``windows=``:
+        ``windows.join`` of the estimators' entropies as they are on the device now."""
+        if self._wl_windows is None:
+            raise ValueError("wl_joined_entropy needs a sampler built with Sampler.from_ensemble(..., windows=)")
+        ln_g, _, visited = self._wl_windows.join(self._get_engine().get_wl()["entropy"])
+        return self._wl_windows.levels(), ln_g, visited
+
+    def run_exchange(self, n_exchanges, steps_between, initial_occupancies=None, thin_by=None, grid=None, windows=None):
+        """``windows`` (a ``parallel.WLWindows``, the one of ``Sampler.from_ensemble(windows=)``): replica-exchange
+        Wang-Landau -- ``n_exchanges`` times ``steps_between`` steps on every walker, then one exchange attempt between
+        neighbouring windows (``Engine.exchange_wl``), the even and the odd move taking turns.  Walkers swap ESTIMATORS,
+        never occupancies: the int32 trace ``wl_estimator`` says which estimator each walker held at every sample, the
+        Wang-Landau traces (entropy, histogram, ...) are in estimator order.  Returns ``windows``.  Otherwise:
+
+        Sampling with replica exchange across a mu-T grid (hyper-parallel tempering): ``n_exchanges`` times
         ``steps_between`` steps on every walker, then one exchange attempt, decided and applied on the device
         (``Engine.exchange_grid``); the four moves of the grid take turns.  ``grid``: a ``parallel.GridExchange`` whose
         rows are ``ensemble.walker_mu_rows(...)`` of the chemical potentials along the mu axis, or a dict
@@ -2170,6 +2276,9 @@ class Sampler:
         ``walker_chemical_potentials`` are the current assignment.  ``thin_by`` defaults to ``steps_between``."""
         from . import parallel
 
+        if windows is not None or (grid is None and self._wl_windows is not None):
+            return self._run_exchange_wl(n_exchanges, steps_between, initial_occupancies, thin_by,
+                                         windows if windows is not None else self._wl_windows)
         if self._world > 1:
             raise ValueError("run_exchange on a sampler sharded over several ranks: the exchange across a mu-T grid runs "
                              "inside one engine handle (an exchange across ranks would gather counts as well as enthalpies)")

@@ -15,6 +15,8 @@ on ROCm; "gloo" in the CPU tests) is used only for
 
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 kB = 8.617333262145e-5  # smol/constants.py:4
@@ -490,3 +492,261 @@ def run_grid_exchange(engine, gx, n_exchanges, steps_between, host_decide=False,
     if not host_decide:
         gx.point_of = base[engine.state_points()[0]]
     return gx
+
+
+# ---- replica-exchange Wang-Landau: overlapping energy windows in one handle (smolmc_exchange_wl) ----------------------
+def wl_num_levels(vmin, vmax, bin_size):
+    """Number of Wang-Landau levels of a window by the engine's rule (smolmc_create): ceil((vmax - vmin) / bin_size)."""
+    return int(math.ceil((float(vmax) - float(vmin)) / float(bin_size)))
+
+
+class WLWindows:
+    """Bookkeeping of replica-exchange Wang-Landau (Vogel, Li, Wuest, Landau, PRL 110, 210603) in one handle.
+
+    The global range ``[min_enthalpy, max_enthalpy)`` has ``L = ceil((max - min) / bin_size)`` bins.  It is cut into
+    ``n_windows`` aligned windows of ``Lw`` bins at a stride of ``Ls`` bins, ``(n_windows - 1) Ls + Lw == L``:
+    ``vmin_k = min + k Ls bin``, ``vmax_k = min + (k Ls + Lw) bin``.  ``overlap`` is the requested ``1 - Ls / Lw``
+    (``window_bins`` / ``stride_bins`` name Lw / Ls outright).  Every window exists ``copies`` times; estimator
+    ``e = k * copies + i`` is copy i of window k, in the order of ``Engine.set_wl_windows(wx.vmin, wx.vmax)``.
+    ``estimator_of[w]`` is the estimator walker w holds.  Move 0 pairs the windows (0, 1), (2, 3), ..., move 1 the
+    windows (1, 2), (3, 4), ..., copy i with copy i, so the pairs of a move are disjoint.
+
+    Walker a holds estimator s, walker b estimator t; the pair is rejected unless Ea lies in t's window and Eb in s's.
+    With ia(E) = (E - vmin_s) // bin, ib(E) = (E - vmin_t) // bin:
+
+        ex = ((S_s[ia(Ea)] - S_s[ia(Eb)]) + S_t[ib(Eb)]) - S_t[ib(Ea)];   accept iff ex >= 0 or log u < ex
+
+    and the walkers swap estimators.  ``decide`` is this move in NumPy, in the operation order of the device kernel
+    (wl_exchange.hip); ``join`` makes one ln g of the pieces."""
+
+    MOVES = (0, 1)
+
+    def __init__(self, min_enthalpy, max_enthalpy, bin_size, n_windows, overlap=0.5, copies=1, seed=0,
+                 window_bins=None, stride_bins=None):
+        self.min_enthalpy, self.max_enthalpy, self.bin_size = float(min_enthalpy), float(max_enthalpy), float(bin_size)
+        self.n_windows, self.copies, self.philox_seed = int(n_windows), int(copies), int(seed)  # (seed: the method below)
+        if self.n_windows < 1 or self.copies < 1 or not (0.0 <= overlap < 1.0) or not self.bin_size > 0:
+            raise ValueError("WLWindows needs n_windows >= 1, copies >= 1, 0 <= overlap < 1 and bin_size > 0")
+        self.L = wl_num_levels(self.min_enthalpy, self.max_enthalpy, self.bin_size)
+        n = self.n_windows
+        if window_bins is None or stride_bins is None:
+            lw0 = self.L / (1.0 + (n - 1) * (1.0 - overlap))
+            stride_bins = max(1, int(math.floor(lw0 * (1.0 - overlap) + 1e-9))) if n > 1 else 0
+            window_bins = self.L - (n - 1) * stride_bins
+        self.Lw, self.Ls = int(window_bins), int(stride_bins)
+        if self.Lw < 1 or (n - 1) * self.Ls + self.Lw != self.L or (n > 1 and not 1 <= self.Ls <= self.Lw):
+            raise ValueError(f"{n} windows of {self.Lw} bins at a stride of {self.Ls} do not tile the {self.L} global bins")
+        k = np.arange(n, dtype=np.float64)
+        wmin = self.min_enthalpy + k * self.Ls * self.bin_size
+        wmax = self.min_enthalpy + (k * self.Ls + self.Lw) * self.bin_size
+        for j in range(n):
+            # the engine sizes a window by ceil((vmax - vmin) / bin): a top edge that rounding put an ulp too high
+            # would count one bin more, so it is stepped down until the rule gives Lw (a sliver of < 1e-15 relative)
+            for _ in range(64):
+                if wl_num_levels(wmin[j], wmax[j], self.bin_size) <= self.Lw:
+                    break
+                wmax[j] = np.nextafter(wmax[j], -np.inf)
+            if wl_num_levels(wmin[j], wmax[j], self.bin_size) != self.Lw:
+                raise ValueError(f"window {j} = [{wmin[j]!r}, {wmax[j]!r}) does not give {self.Lw} levels at bin size "
+                                 f"{self.bin_size!r} by the engine's rule ceil((vmax - vmin) / bin)")
+        self.window_min, self.window_max = wmin, wmax
+        self.window_of = np.repeat(np.arange(n), self.copies)          # estimator -> window
+        self.copy_of = np.tile(np.arange(self.copies), n)              # estimator -> copy
+        self.vmin, self.vmax = wmin[self.window_of], wmax[self.window_of]  # (R,) in estimator order
+        self.R = n * self.copies
+        self.estimator_of = np.arange(self.R)
+        self.calls = 0
+        self._pairs = {m: self._make_pairs(m) for m in self.MOVES}
+        self.attempted = {m: np.zeros(len(p), dtype=np.int64) for m, p in self._pairs.items()}
+        self.accepted = {m: np.zeros(len(p), dtype=np.int64) for m, p in self._pairs.items()}
+
+    def _make_pairs(self, move):
+        lo = np.arange(int(move), self.n_windows - 1, 2)
+        i = np.arange(self.copies)
+        s = (lo[:, None] * self.copies + i[None, :]).reshape(-1)
+        return np.stack([s, s + self.copies], axis=1).astype(np.int32).reshape(-1, 2)
+
+    def pairs(self, move):
+        """(npairs, 2) estimators of move 0 (even neighbouring windows) or 1 (odd)."""
+        return self._pairs[int(move)]
+
+    def move_of(self, attempt):
+        return self.MOVES[int(attempt) % len(self.MOVES)]
+
+    def log_u(self, attempt, npairs):
+        """log of the ``npairs`` uniforms of attempt ``attempt`` (a pure function of the seed and the attempt)."""
+        with np.errstate(divide="ignore"):
+            return np.log(_philox_uniforms(self.philox_seed, attempt, max(int(npairs), 1))[:npairs])
+
+    def record(self, move, accept):
+        self.attempted[int(move)] += 1
+        self.accepted[int(move)] += np.asarray(accept, dtype=np.int64)
+
+    @property
+    def acceptance(self):
+        """Accepted / attempted over all pairs of both moves."""
+        att = sum(int(a.sum()) for a in self.attempted.values())
+        return sum(int(a.sum()) for a in self.accepted.values()) / max(att, 1)
+
+    def bins(self, enthalpy, vmin):
+        """Bin of ``enthalpy`` in the window that starts at ``vmin``: the exact floor division of the sampling step,
+        held inside 0 .. Lw - 1 (the clamp changes no index of an in-window enthalpy)."""
+        q = np.floor_divide(np.asarray(enthalpy, dtype=np.float64) - vmin, self.bin_size)
+        return np.clip(q, 0, self.Lw - 1).astype(np.int64)
+
+    def decide(self, enthalpy, entropy, estimator_of, move, attempt, log_u=None, record=True, pairs=None):
+        """One attempt of ``move`` (or of the disjoint ``pairs`` given outright, not recorded) on the host: enthalpy (R,)
+        by walker, entropy (R, Lw) by ESTIMATOR and the walker -> estimator map in; returns dict(pairs, in_window,
+        exponent, accept, estimator_of (new)).  The definition the
+        device kernel is tested against: three roundings of the exponent in the order written in the class docstring."""
+        enthalpy = np.asarray(enthalpy, dtype=np.float64)
+        S = np.asarray(entropy, dtype=np.float64).reshape(self.R, self.Lw)
+        estimator_of = np.asarray(estimator_of, dtype=np.int64)
+        record = record and pairs is None
+        pairs = self.pairs(move) if pairs is None else np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+        walker_at = np.empty(self.R, dtype=np.int64)
+        walker_at[estimator_of] = np.arange(self.R)
+        s, t = pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64)
+        a, b = walker_at[s], walker_at[t]
+        Ea, Eb = enthalpy[a], enthalpy[b]
+        in_window = (Ea >= self.vmin[t]) & (Ea < self.vmax[t]) & (Eb >= self.vmin[s]) & (Eb < self.vmax[s])
+        iaa, iab = self.bins(Ea, self.vmin[s]), self.bins(Eb, self.vmin[s])
+        iba, ibb = self.bins(Ea, self.vmin[t]), self.bins(Eb, self.vmin[t])
+        ex = ((S[s, iaa] - S[s, iab]) + S[t, ibb]) - S[t, iba]
+        if log_u is None:
+            log_u = self.log_u(attempt, len(pairs))
+        log_u = np.asarray(log_u, dtype=np.float64)
+        accept = in_window & ((ex >= 0) | (log_u < ex))
+        new = estimator_of.copy()
+        new[a[accept]] = t[accept]
+        new[b[accept]] = s[accept]
+        if record:
+            self.record(move, accept)
+        return dict(pairs=pairs, in_window=in_window, exponent=ex, accept=accept, estimator_of=new)
+
+    def levels(self):
+        """Lower edges of the L global bins."""
+        return self.min_enthalpy + np.arange(self.L) * self.bin_size
+
+    def join(self, entropy):
+        """One ln g over the global bin grid from the estimators' entropies (R, Lw), estimator order.  Per copy index:
+        window after window is shifted by the mean difference over the bins that it and the part already joined have
+        both visited (S > 0), and bins covered by several windows take the mean of the shifted values of the windows
+        that visited them.  The copies are brought to copy 0's constant the same way and averaged.  Returns
+        (ln g (L,), per-copy ln g (copies, L), visited (L,) bool); unvisited bins hold 0."""
+        S = np.asarray(entropy, dtype=np.float64).reshape(self.n_windows, self.copies, self.Lw)
+        per_copy = np.zeros((self.copies, self.L))
+        seen = np.zeros((self.copies, self.L), dtype=bool)
+        for i in range(self.copies):
+            total, count = np.zeros(self.L), np.zeros(self.L)
+            for k in range(self.n_windows):
+                piece, sl = S[k, i], slice(k * self.Ls, k * self.Ls + self.Lw)
+                vis = piece > 0
+                if not vis.any():
+                    continue
+                have = count[sl] > 0
+                shift = 0.0
+                if have.any():
+                    common = have & vis
+                    if not common.any():
+                        raise ValueError(f"copy {i}: window {k} shares no visited bin with the windows below it")
+                    shift = float(np.mean((total[sl][common] / count[sl][common]) - piece[common]))
+                total[sl] += np.where(vis, piece + shift, 0.0)
+                count[sl] += vis
+            seen[i] = count > 0
+            per_copy[i, seen[i]] = total[seen[i]] / count[seen[i]]
+        total, count = np.zeros(self.L), np.zeros(self.L)
+        for i in range(self.copies):
+            if not seen[i].any():
+                continue
+            have = count > 0
+            shift = 0.0
+            if have.any():
+                common = have & seen[i]
+                if not common.any():
+                    raise ValueError(f"copy {i} shares no visited bin with the copies before it")
+                shift = float(np.mean(total[common] / count[common] - per_copy[i, common]))
+            per_copy[i, seen[i]] += shift
+            total += np.where(seen[i], per_copy[i], 0.0)
+            count += seen[i]
+        visited = count > 0
+        ln_g = np.zeros(self.L)
+        ln_g[visited] = total[visited] / count[visited]
+        return ln_g, per_copy, visited
+
+    def seed(self, engine, occ0, chunk, max_chunks, temperature=None):
+        """Start occupancies (R, N), one inside every estimator's window.  ``engine`` is a Wang-Landau handle of R
+        walkers that still has the GLOBAL window it was created with (a second, short-lived handle: plain Wang-Landau
+        walks the whole range); it is started from ``occ0`` ((N,) or (R, N)) and run in chunks of ``chunk`` steps.
+        After every chunk each estimator that has none yet takes the occupancy of a walker whose enthalpy lies in its
+        window (walkers not used before first).  Raises, naming the windows never reached, after ``max_chunks``."""
+        if engine.R != self.R:
+            raise ValueError(f"the windows have {self.R} estimators, the engine {engine.R} walkers")
+        occ0 = np.asarray(occ0)
+        occ0 = np.broadcast_to(occ0, (self.R, occ0.shape[-1]))
+        engine.set_state(occ0, np.arange(self.R, dtype=np.uint64) + np.uint64(self.philox_seed * self.R + 1), temperature)
+        out = np.zeros((self.R, occ0.shape[-1]), dtype=np.int32)
+        missing = np.ones(self.R, dtype=bool)
+        used = np.zeros(self.R, dtype=bool)
+        for c in range(int(max_chunks) + 1):
+            if c:
+                engine.run(int(chunk), sync=True)
+            st = engine.get_state()
+            H = st["enthalpy"]
+            for e in np.flatnonzero(missing):
+                inside = (H >= self.vmin[e]) & (H < self.vmax[e])
+                cand = np.flatnonzero(inside & ~used)
+                if not len(cand):
+                    cand = np.flatnonzero(inside)
+                if len(cand):
+                    out[e] = st["occupancy"][cand[0]]
+                    used[cand[0]] = True
+                    missing[e] = False
+            if not missing.any():
+                return out
+        never = sorted(set(int(k) for k in self.window_of[missing]))
+        raise RuntimeError(f"no walker reached window(s) {never} in {int(max_chunks)} chunks of {int(chunk)} steps: "
+                           + ", ".join(f"[{self.window_min[k]:.6g}, {self.window_max[k]:.6g})" for k in never))
+
+
+def run_wl_exchange(engine, wx, n_exchanges, steps_between, host_decide=False, history=None):
+    """Alternate ``steps_between`` Wang-Landau steps on every walker with one exchange attempt between the windows of
+    ``wx``, alternating its even and odd move.  ``engine`` holds ``wx.R`` walkers with ``set_wl_windows(wx.vmin,
+    wx.vmax)`` in force and their state loaded.  Default: the attempt is decided and applied on the device
+    (``Engine.exchange_wl``: the walkers swap estimators), nothing but the accept flags comes back.
+    ``host_decide=True``: state and entropies are read back, ``wx.decide`` takes the decisions, and an accepted pair
+    swaps its two CONFIGURATIONS through ``set_state(..., reset_aux=False)`` -- the estimators stay with their walkers;
+    the cross-check of the device path, and what it is timed against.  ``history``: a list that receives the walker
+    (host: configuration) -> estimator map after every attempt."""
+    if engine.R != wx.R:
+        raise ValueError(f"the windows have {wx.R} estimators, the engine {engine.R} walkers")
+    identity = np.arange(wx.R)
+    if host_decide:
+        wx.estimator_of = np.asarray(wx.estimator_of).copy()  # configuration -> estimator (= the walker it sits on)
+    for _ in range(int(n_exchanges)):
+        engine.run(steps_between)
+        move = wx.move_of(wx.calls)
+        pairs = wx.pairs(move)
+        if host_decide:
+            st = engine.get_state()
+            res = wx.decide(st["enthalpy"], engine.get_wl()["entropy"], identity, move, wx.calls)
+            if res["accept"].any():
+                occ = st["occupancy"].copy()
+                s, t = pairs[res["accept"], 0], pairs[res["accept"], 1]
+                occ[s], occ[t] = st["occupancy"][t], st["occupancy"][s]
+                engine.set_state(occ, None, None, reset_aux=False)
+                conf_at = np.empty(wx.R, dtype=np.int64)
+                conf_at[wx.estimator_of] = identity
+                wx.estimator_of[conf_at[s]], wx.estimator_of[conf_at[t]] = t, s
+        else:
+            stats = np.zeros((len(pairs), 2), dtype=np.int64)
+            engine.exchange_wl(pairs, wx.log_u(wx.calls, len(pairs)), stats)
+            wx.record(move, stats[:, 1])
+            if history is not None:
+                wx.estimator_of = engine.wl_windows()[2].astype(np.int64)
+        wx.calls += 1
+        if history is not None:
+            history.append(np.array(wx.estimator_of))
+    if not host_decide:
+        wx.estimator_of = engine.wl_windows()[2].astype(np.int64)
+    return wx

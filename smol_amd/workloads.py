@@ -343,5 +343,35 @@ def config14(first=0, count=2048, dim=12, mc=2000, total=None):
     return w
 
 
+CONFIG15_WINDOWS, CONFIG15_OVERLAP = 16, 0.75  # config 15: windows over config 4's global range, and their overlap
+
+
+def config15(first=0, count=1024, dim=16, mc=5000, h0=None):
+    """Config 4 as replica-exchange Wang-Landau: its Hamiltonian and its global window (512 bins of 0.5 eV) cut into 16
+    windows at 75 % overlap, count / 16 copies of each (64 at 1024 walkers), per-walker windows in one handle.  ``h0`` as in
+    config 4.  The handle is created with window 0 (its L is the window's); ``extras["wl_windows"]`` is the
+    ``parallel.WLWindows`` (set_wl_windows(wx.vmin, wx.vmax)), ``extras["global_window"]`` config 4's config keywords: the
+    start occupancies of the windows come from ``wx.seed`` on a short-lived handle with that global window (the caller's
+    business: nothing here touches the GPU)."""
+    from . import parallel
+
+    if first != 0:
+        raise ValueError("config 15 runs inside one engine handle: no sharding over ranks")
+    if count % CONFIG15_WINDOWS:
+        raise ValueError(f"config 15 wants a multiple of {CONFIG15_WINDOWS} walkers")
+    w = config4(first, count, dim, mc, h0)
+    w.key = 15
+    w.name = (f"config15: config 4 as replica-exchange Wang-Landau, {CONFIG15_WINDOWS} windows x {count // CONFIG15_WINDOWS} copies, "
+              f"{CONFIG15_OVERLAP:.0%} overlap")
+    if h0 is not None:
+        kw = w.config_kwargs
+        wx = parallel.WLWindows(kw["min_enthalpy"], kw["max_enthalpy"], kw["bin_size"], CONFIG15_WINDOWS, overlap=CONFIG15_OVERLAP,
+                                copies=count // CONFIG15_WINDOWS, seed=15)
+        w.extras.update(wl_windows=wx, global_window=dict(kw))
+        w.config_kwargs = dict(kw, min_enthalpy=float(wx.vmin[0]), max_enthalpy=float(wx.vmax[0]))
+        w.name += f" ({wx.Lw} bins per window, stride {wx.Ls})"
+    return w
+
+
 BUILDERS = {1: config1, 2: config2, 3: config3, 4: config4, 5: config5, 6: config6, 7: config7,
-            8: config8, 9: config9, 10: config10, 11: config11, 12: config12, 13: config13, 14: config14}
+            8: config8, 9: config9, 10: config10, 11: config11, 12: config12, 13: config13, 14: config14, 15: config15}

@@ -19,6 +19,22 @@ from smol_amd import capi, parallel, workloads  # noqa: E402
 from smol_amd.engine import Engine  # noqa: E402
 
 
+def windowed_engine(wl, chunk=20000, max_chunks=150):
+    """Config 15: the handle with per-walker windows and every estimator started inside its window.  The starts come from
+    a second, short-lived handle with config 4's global window (parallel.WLWindows.seed: plain Wang-Landau walks the
+    whole range); returns (engine, windows, steps per walker the seeding took)."""
+    wx = wl.extras["wl_windows"]
+    g = dict(wl.extras["global_window"])
+    seeder = Engine(wl.tables, capi.make_config(wl.n_walkers, g.pop("kernel"), g.pop("step"), 0, **g))
+    occ = wx.seed(seeder, wl.occupancy, chunk, max_chunks)
+    seed_steps = int(seeder.get_state(occupancy=False)["n_steps"][0])
+    seeder.close()
+    eng = Engine(wl.tables, wl.make_config())
+    eng.set_wl_windows(wx.vmin, wx.vmax)
+    eng.set_state(occ, wl.seeds, wl.temperature)
+    return eng, wx, seed_steps
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, required=True, choices=sorted(workloads.BUILDERS))
@@ -43,20 +59,25 @@ def main():
     if a.mc:
         kw["mc"] = a.mc
     wl = workloads.BUILDERS[a.config](**kw)
-    if a.config in (4, 10, 11):  # the window is centred on the starting enthalpy, evaluated on the engine
+    if a.config in (4, 10, 11, 15):  # the window is centred on the starting enthalpy, evaluated on the engine
         probe = Engine(wl.tables, capi.make_config(1))
         h0 = float(probe.natural_parameters @ probe.eval_full(wl.occupancy[:1])[0])
         if a.config == 11:  # random starts with a long upper tail: the window's upper edge 30 eV above the highest
             h0 = float((probe.eval_full(wl.occupancy) @ probe.natural_parameters).max()) + 30.0 - 95.63
         probe.close()
         wl = workloads.BUILDERS[a.config](h0=h0, **kw)
-    eng = Engine(wl.tables, wl.make_config())
+    T = a.temperature if a.temperature > 0 else wl.temperature
+    seed_steps = None
+    if "wl_windows" in wl.extras:  # config 15: per-walker windows, every estimator seeded inside its window
+        eng, _, seed_steps = windowed_engine(wl)
+    else:
+        eng = Engine(wl.tables, wl.make_config())
     if "walker_mu" in wl.extras:  # config 14: a T x mu grid in one handle
         eng.set_walker_mu(wl.extras["walker_mu"])
     elif a.uniform_rows:
         eng.set_walker_mu(eng.get_walker_mu())
-    T = a.temperature if a.temperature > 0 else wl.temperature
-    eng.set_state(wl.occupancy, wl.seeds, T)
+    if seed_steps is None:
+        eng.set_state(wl.occupancy, wl.seeds, T)
     R, mc = wl.n_walkers, wl.mc_per_launch
     rex = None
     if a.config == 5:
@@ -95,7 +116,7 @@ def main():
         us_per_step_per_walker=k_ms * 1e3 / mc,
         acceptance=float((s1["n_accepted"] - s0["n_accepted"]).sum()) / (a.launches * steps),
         exchange_acceptance_mean=None if rex is None else float(rex.acceptance.mean()),
-        sampled=sampled,
+        sampled=sampled, seed_steps_per_walker=seed_steps,
     )))
 
 
