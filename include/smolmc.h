@@ -297,6 +297,28 @@ int smolmc_get_wl_windows(smolmc_handle *h, double *vmin /* R */, double *vmax /
  * Refused like smolmc_set_wl_windows, and while no windows are set. */
 int smolmc_exchange_wl(smolmc_handle *h, int npairs, const int32_t *pairs /* npairs x 2 estimators, host */,
                        const double *log_u /* npairs, host */, int64_t *stats /* npairs x 2 in/out, host, or NULL */);
+/* Population annealing (Hukushima & Iba 2003; Machta, PRE 82, 026704): resample and clone walkers on the device.
+ * smolmc_resample clones by an explicit map (host, R entries): slot m takes the state of slot parent[m] -- occupancy,
+ * features, enthalpy, accepted flag, bias and Ewald field; every source must map to itself (parent[parent[m]] ==
+ * parent[m]: the copy is in place); step counters, seeds and temperatures stay with the slot, so clones diverge from
+ * the next step on without reseeding.  Queued on the handle's stream.
+ * Both calls are refused, naming the reason, on Wang-Landau and distance handles, while per-walker chemical potentials
+ * are set, for a parent out of range or a source that is a destination, for npop that does not divide R and for a
+ * population whose walkers are not at one temperature. */
+int smolmc_resample(smolmc_handle *h, const int32_t *parent /* R, host */);
+/* ... one population-annealing step: npop populations of n = R / npop walkers (contiguous slots), population p goes
+ * from its inverse temperature beta to beta' = 1 / (kB temperature_new[p]), db = beta' - beta of either sign:
+ *     H_ref = min H (db > 0) or max H;  w_j = exp(-(db * (H_j - H_ref)));  q_j = (uint64) floor(w_j * 2^40);  Q = sum q_j
+ *     off = (offset_word[p] * Q) >> 64;  C_j = q_0 + ... + q_j
+ *     child m (0 <= m < n) descends from the smallest j with n * C_j > m * Q + off   (systematic resampling)
+ *     survivors keep their slot; the k-th slot without a child takes the k-th surplus copy, parents ascending
+ * then the walkers are cloned as by smolmc_resample and the new temperatures are in force.  n <= 2^22.
+ * ln(Q / (n 2^40)) - db * H_ref estimates ln Z(beta') - ln Z(beta).  Outputs (host) may be NULL: without them the call
+ * only queues work on the handle's stream; with any it waits for the kernels.  parent_out holds slot numbers of the
+ * handle. */
+int smolmc_anneal_resample(smolmc_handle *h, int npop, const double *temperature_new /* npop */,
+                           const uint64_t *offset_word /* npop */, int32_t *parent_out /* R */, uint64_t *q_out /* R */,
+                           uint64_t *qsum_out /* npop */, double *href_out /* npop */);
 /* any output pointer may be NULL */
 int smolmc_get_state(smolmc_handle *h, int32_t *occ /*RxN*/, double *features /*RxF*/,
                      double *enthalpy /*R*/, uint64_t *n_accepted /*R*/,

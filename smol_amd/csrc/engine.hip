@@ -3903,3 +3903,94 @@ extern "C" int smolmc_get_state_points(smolmc_handle *h, int32_t *point_of, doub
     }
     return 0;
 }
+
+// ---- population annealing: resample and clone walkers on the device (pop_anneal.hip) --------------------------------
+// The move is spelled out in pop_anneal.hip and DESIGN 4.14; parallel.PopulationAnnealing is its definition in NumPy.
+// It touches nothing but HBM state between launches, so every Metropolis kernel family is served.  (A lazy handle: the
+// scalar rows and kp.features move together, and cluster features that were stale before a clone are stale for source and
+// copy alike: ce_dirty stays what it was.)
+static int resample_refused(const smolmc_handle *h, const char *what) {
+    if (h->dist) return fail(std::string(what) + ": a distance handle keeps best records per walker, its walkers are not resampled");
+    if (is_wl(h)) return fail(std::string(what) + ": a Wang-Landau handle samples no Boltzmann weight (its walkers build one density of states, no population at a temperature)");
+    if (!h->walker_mu.empty()) return fail(std::string(what) + " while per-walker chemical potentials are set: walkers of different Hamiltonians are no population");
+    return 0; // (Wang-Landau windows exist on Wang-Landau handles only)
+}
+static int pop_scratch(smolmc_handle *h) {
+    if (h->pop.parent) return 0;
+    const size_t R = (size_t)h->R;
+    uint64_t *arena = nullptr; // six arrays of 8 bytes, four of 4 bytes per walker
+    TRY(dev_alloc(h, 8 * R, &arena));
+    SmolmcPopScratch &S = h->pop;
+    S.q = arena; S.qsum = arena + R; S.word = arena + 2 * R; S.C = arena + 3 * R;
+    S.href = (double *)(arena + 4 * R); S.beta_new = (double *)(arena + 5 * R);
+    S.cnt = (uint32_t *)(arena + 6 * R); S.sur = S.cnt + R; S.drank = S.cnt + 2 * R;
+    S.parent = (int32_t *)(S.cnt + 3 * R);
+    return 0;
+}
+
+extern "C" int smolmc_resample(smolmc_handle *h, const int32_t *parent) {
+    if (!h || !parent) return fail("null argument");
+    TRY(resample_refused(h, "smolmc_resample"));
+    const int R = h->R;
+    for (int m = 0; m < R; ++m)
+        if (parent[m] < 0 || parent[m] >= R)
+            return fail("smolmc_resample: parent " + std::to_string(parent[m]) + " of slot " + std::to_string(m) + " is out of range 0 .. " + std::to_string(R - 1));
+    for (int m = 0; m < R; ++m)
+        if (parent[parent[m]] != parent[m])
+            return fail("smolmc_resample: slot " + std::to_string(parent[m]) + " is a source (of slot " + std::to_string(m) + ") and a destination (of slot " +
+                        std::to_string(parent[parent[m]]) + "): every source must map to itself, the copy is in place");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(pop_scratch(h));
+    // (a pageable source: read when hipMemcpyAsync returns, as in smolmc_exchange_grid)
+    HIPCHK(hipMemcpyAsync(h->pop.parent, parent, (size_t)R * 4, hipMemcpyHostToDevice, h->stream));
+    return smolmc_pop_clone_launch(h, h->pop.parent, 1, nullptr);
+}
+
+extern "C" int smolmc_anneal_resample(smolmc_handle *h, int npop, const double *temperature_new, const uint64_t *offset_word,
+                                      int32_t *parent_out, uint64_t *q_out, uint64_t *qsum_out, double *href_out) {
+    if (!h || !temperature_new || !offset_word) return fail("null argument");
+    TRY(resample_refused(h, "smolmc_anneal_resample"));
+    const int R = h->R;
+    if (npop < 1 || R % npop != 0)
+        return fail("smolmc_anneal_resample: " + std::to_string(npop) + " populations do not divide the " + std::to_string(R) + " walkers (populations are equal blocks of slots: R % npop must be 0)");
+    const int n = R / npop;
+    for (int p = 0; p < npop; ++p)
+        if (!(temperature_new[p] > 0.0) || !std::isfinite(temperature_new[p]))
+            return fail("smolmc_anneal_resample: the temperature of population " + std::to_string(p) + " must be positive and finite");
+    if (n > (1 << 22)) return fail("smolmc_anneal_resample: a population must be no larger than 2^22 walkers (the sum of the weights stays below 2^62)");
+    HIPCHK(hipSetDevice(h->device));
+    // the temperatures in force: as named by the latest call that set them, or read back where exchanges moved them
+    std::vector<double> T_old(R);
+    if (!h->point_T_stale && !h->grid_permuted && h->point_T.size() == (size_t)R) T_old = h->point_T;
+    else {
+        std::vector<double> beta(R);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpy(beta.data(), h->d_beta, (size_t)R * 8, hipMemcpyDeviceToHost));
+        for (int r = 0; r < R; ++r) T_old[r] = 1.0 / (SMOLMC_KB * beta[r]);
+    }
+    for (int r = 0; r < R; ++r)
+        if (T_old[r] != T_old[(r / n) * n])
+            return fail("smolmc_anneal_resample: the walkers of population " + std::to_string(r / n) + " are at different temperatures (walker " +
+                        std::to_string((r / n) * n) + ": " + std::to_string(T_old[(r / n) * n]) + ", walker " + std::to_string(r) + ": " + std::to_string(T_old[r]) +
+                        "); a population is reweighted from one temperature");
+    TRY(pop_scratch(h));
+    TRY(grid_rebase(h));
+    std::vector<double> T_new(R), beta_new(npop);
+    for (int r = 0; r < R; ++r) T_new[r] = temperature_new[r / n];
+    for (int p = 0; p < npop; ++p) beta_new[p] = 1.0 / (SMOLMC_KB * temperature_new[p]); // (as set_betas)
+    const SmolmcPopScratch &S = h->pop;
+    HIPCHK(hipMemcpyAsync(S.beta_new, beta_new.data(), (size_t)npop * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(S.word, offset_word, (size_t)npop * 8, hipMemcpyHostToDevice, h->stream));
+    TRY(smolmc_pop_parent_launch(h, npop, S));
+    TRY(smolmc_pop_clone_launch(h, S.parent, npop, S.beta_new));
+    grid_name_temperatures(h, T_new.data());
+    h->order_dirty = true; // (as smolmc_set_temperature: the launch order of the TableFlip kernels follows the temperatures)
+    if (parent_out || q_out || qsum_out || href_out) {
+        if (parent_out) HIPCHK(hipMemcpyAsync(parent_out, S.parent, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
+        if (q_out) HIPCHK(hipMemcpyAsync(q_out, S.q, (size_t)R * 8, hipMemcpyDeviceToHost, h->stream));
+        if (qsum_out) HIPCHK(hipMemcpyAsync(qsum_out, S.qsum, (size_t)npop * 8, hipMemcpyDeviceToHost, h->stream));
+        if (href_out) HIPCHK(hipMemcpyAsync(href_out, S.href, (size_t)npop * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}

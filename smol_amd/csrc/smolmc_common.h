@@ -755,6 +755,14 @@ struct SampleSlot {
 enum KernelFamily { K_GENERAL, K_UNIVERSAL, K_LEAN, K_LEAN_BIAS, K_LEAN_CORR, K_WL, K_TABLE_BIAS, K_TABLE_WL,
                     K_MULTI, K_MULTI_BIAS, K_MULTI_WL, K_MULTI_WL_KF, K_MULTI_TABLE_BIAS, K_MULTI_TABLE_WL };
 
+// pop_anneal.hip: the device arrays of a population-annealing step (all [R]; the per-population ones use the first npop)
+struct SmolmcPopScratch {
+    int32_t *parent = nullptr; // (null: not allocated yet)
+    uint64_t *q, *qsum, *word, *C;
+    double *href, *beta_new;
+    uint32_t *cnt, *sur, *drank;
+};
+
 struct smolmc_handle {
     smolmc_config cfg;
     int device = 0;
@@ -829,6 +837,9 @@ struct smolmc_handle {
     WlWindow *d_wl_win = nullptr;
     int32_t *d_wl_walker_at = nullptr;
     double *d_wlx_stage = nullptr;
+    // population annealing (smolmc_anneal_resample / smolmc_resample, engine.hip): one device arena, allocated at the
+    // first call, cut into the arrays of SmolmcPopScratch
+    SmolmcPopScratch pop;
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
     SampleSlot slots[2];
@@ -933,6 +944,12 @@ int smolmc_grid_exchange_launch(smolmc_handle *h, int npairs, const int32_t *pai
 // wl_exchange.hip: one exchange attempt between the walkers that hold the estimators pairs[p][0] and pairs[p][1]
 // (device arrays; the pairs disjoint), decided and applied on the device, queued on the handle's stream
 int smolmc_wl_exchange_launch(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int32_t *accepted);
+// ... weights, systematic resampling and the stable assignment of npop populations of R / npop walkers: S.parent, S.q,
+// S.qsum, S.href from the enthalpies, the temperatures in force, S.beta_new and S.word; queued on the handle's stream
+int smolmc_pop_parent_launch(smolmc_handle *h, int npop, const SmolmcPopScratch &S);
+// ... slot m takes every per-walker row of slot parent[m] (device array; parent[parent[m]] == parent[m]), and, with
+// beta_new (device, [npop]), walker m the inverse temperature beta_new[m / (R / npop)]; queued on the handle's stream
+int smolmc_pop_clone_launch(smolmc_handle *h, const int32_t *parent, int npop, const double *beta_new);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);
 int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_4(smolmc_handle *h, const KParams &kp, int replay);

@@ -40,6 +40,8 @@ SYMBOLS = {
     "smolmc_set_wl_windows": (C.c_int, [_HP, _f64p, _f64p]),
     "smolmc_get_wl_windows": (C.c_int, [_HP, _f64p, _f64p, _i32p]),
     "smolmc_exchange_wl": (C.c_int, [_HP, C.c_int, _i32p, _f64p, _i64p]),
+    "smolmc_resample": (C.c_int, [_HP, _i32p]),
+    "smolmc_anneal_resample": (C.c_int, [_HP, C.c_int, _f64p, _u64p, _i32p, _u64p, _u64p, _f64p]),
     "smolmc_get_state": (C.c_int, [_HP, _i32p, _f64p, _f64p, _u64p, _u64p, _u8p]),
     "smolmc_get_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
     "smolmc_set_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
@@ -328,6 +330,37 @@ class Engine:
             raise ValueError(f"stats must be a C-contiguous int64 array of shape ({len(pairs)}, 2)")
         self._chk(self._lib.smolmc_exchange_wl(self._h, len(pairs), _p(pairs, C.c_int32), _p(log_u, C.c_double),
                                                _p(stats, C.c_int64)))
+
+    # ---- population annealing ------------------------------------------------------------
+    def resample(self, parent):
+        """Clone walkers by an explicit map on the device (smolmc_resample): slot m takes the state of slot
+        ``parent[m]`` -- occupancy, features, enthalpy, accepted flag, bias, Ewald field.  Every source must map to
+        itself; counters, seeds and temperatures stay with the slot.  Queued on the handle's stream."""
+        parent = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+        if len(parent) != self.R:
+            raise ValueError(f"expected one parent per walker: {self.R} walkers, {len(parent)} entries")
+        self._chk(self._lib.smolmc_resample(self._h, _p(parent, C.c_int32)))
+
+    def anneal_resample(self, temperatures, offset_words, npop=1, outputs=True):
+        """One population-annealing step on the device (smolmc_anneal_resample): the ``npop`` populations (equal
+        blocks of slots) go to ``temperatures`` (npop,), are reweighted, resampled with one ``offset_words`` (npop,)
+        uint64 each and cloned; the new temperatures are in force afterwards.  Returns dict(parent (R,) int32 slot
+        numbers, q (R,) uint64, qsum (npop,) uint64, href (npop,)) -- or None with ``outputs=False``, when the call
+        only queues work on the handle's stream."""
+        npop = int(npop)
+        temp = np.ascontiguousarray(np.broadcast_to(np.asarray(temperatures, float), (npop,)))
+        words = np.ascontiguousarray(offset_words, dtype=np.uint64).reshape(-1)
+        if len(words) != npop:
+            raise ValueError(f"expected one offset word per population: {npop} populations, {len(words)} words")
+        out = None
+        if outputs:
+            out = dict(parent=np.empty(self.R, dtype=np.int32), q=np.empty(self.R, dtype=np.uint64),
+                       qsum=np.empty(npop, dtype=np.uint64), href=np.empty(npop))
+        self._chk(self._lib.smolmc_anneal_resample(
+            self._h, npop, _p(temp, C.c_double), _p(words, C.c_uint64),
+            _p(out["parent"], C.c_int32) if out else None, _p(out["q"], C.c_uint64) if out else None,
+            _p(out["qsum"], C.c_uint64) if out else None, _p(out["href"], C.c_double) if out else None))
+        return out
 
     def species_counts(self, occupancies):
         """Species counts per (active sublattice, code) of occupancies (n, N), in the layout of ``set_walker_mu``."""

@@ -1479,6 +1479,13 @@ class SampleContainer:
                           "meta/state_point_temperatures": np.asarray(pts["temperatures"], dtype=np.float64),
                           "meta/state_point_values": np.asarray(pts["chemical_potentials"], dtype=np.float64),
                           "meta/state_point_shape": np.asarray(pts["shape"], dtype=np.int64)})
+        pop = self.metadata.get("population_annealing")
+        if pop is not None:  # the record of Sampler.anneal_population
+            extra.update({"meta/pop_anneal_temperatures": np.asarray(pop["temperatures"], dtype=np.float64),
+                          "meta/pop_anneal_seed": np.asarray([pop["populations"], pop["seed"]], dtype=np.int64),
+                          "meta/pop_anneal_log_partition_ratio": np.asarray(pop["log_partition_ratio"], dtype=np.float64),
+                          "meta/pop_anneal_n_families": np.asarray(pop["n_families"], dtype=np.int64),
+                          "meta/pop_anneal_rho_t": np.asarray(pop["rho_t"], dtype=np.float64)})
         np.savez_compressed(path, nsamples=self.num_samples, total_mc_steps=self._total_steps,
                             **{f"trace/{k}": v for k, v in self._all().items()}, **extra)
 
@@ -1587,6 +1594,12 @@ class SampleContainer:
                                               temperatures=d["meta/state_point_temperatures"].tolist(),
                                               chemical_potentials=d["meta/state_point_values"].tolist(),
                                               shape=[int(x) for x in d["meta/state_point_shape"]])
+        if "meta/pop_anneal_temperatures" in d.files:
+            c.metadata["population_annealing"] = dict(
+                temperatures=d["meta/pop_anneal_temperatures"].tolist(),
+                populations=int(d["meta/pop_anneal_seed"][0]), seed=int(d["meta/pop_anneal_seed"][1]),
+                log_partition_ratio=d["meta/pop_anneal_log_partition_ratio"].tolist(),
+                n_families=d["meta/pop_anneal_n_families"].tolist(), rho_t=d["meta/pop_anneal_rho_t"].tolist())
         return c
 
 
@@ -2359,3 +2372,57 @@ class Sampler:
                 kernel.temperature = temperature
             self.run(mcmc_steps, initial_occupancies=start, thin_by=thin_by, progress=progress)
             start = None
+
+    def anneal_population(self, temperatures, mcmc_steps, initial_occupancies=None, populations=1, thin_by=1, seed=0):
+        """Population annealing (Hukushima & Iba 2003; Machta, PRE 82, 026704), the counterpart of ``anneal``: the
+        walkers are ``populations`` equal blocks that cool together.  ``mcmc_steps`` steps are sampled at
+        ``temperatures[0]``; at every later temperature each population is reweighted by exp(-dbeta H), resampled to
+        constant size and cloned on the device (``Engine.anneal_resample``), then sampled for ``mcmc_steps`` steps --
+        the sample layout of ``anneal``.  Returns the ``parallel.PopulationAnnealing`` that holds the running
+        ``log_q`` and the lineage; ``samples.metadata["population_annealing"]`` records, per temperature and
+        population, ``log_partition_ratio`` (ln Z(T) - ln Z(temperatures[0]), 0 in the first row), ``n_families`` and
+        ``rho_t``, and survives ``to_npz`` / ``from_npz``."""
+        from . import parallel
+
+        if not isinstance(self._kernels[0], Metropolis):
+            raise AttributeError("anneal_population is only available for samplers with a thermal kernel")
+        temperatures = [float(t) for t in temperatures]
+        if len(temperatures) < 1:
+            raise ValueError("anneal_population needs at least one temperature")
+        if temperatures[0] < temperatures[-1]:
+            raise ValueError(
+                "End temperature is greater than start temperature "
+                f"{temperatures[-1]:.2f} > {temperatures[0]:.2f}."
+            )
+        nw, P = len(self._kernels), int(populations)
+        if P < 1 or nw % P:
+            raise ValueError(f"{P} populations do not divide the sampler's {nw} walkers into equal blocks")
+        if self._world > 1:
+            raise ValueError("anneal_population on a sampler sharded over several ranks: a population is resampled "
+                             "inside one engine handle")
+        if self._walker_mu is not None:
+            raise ValueError("anneal_population with per-walker chemical potentials: walkers of different "
+                             "Hamiltonians are no population")
+        if initial_occupancies is None and self.samples.num_samples == 0:
+            raise RuntimeError("There are no saved samples to obtain the initial occupancies."
+                               "These must be provided.")
+        pa = parallel.PopulationAnnealing(temperatures, populations=P, seed=seed)
+        n = nw // P
+        lpr, nfam, rho = [[0.0] * P], [[n] * P], [[1.0] * P]
+        for k, temperature in enumerate(temperatures):
+            for kernel in self._kernels:
+                kernel.temperature = temperature
+            if k == 0:
+                self._load_state(initial_occupancies)
+            else:
+                res = self._get_engine().anneal_resample(np.full(P, temperature), pa.offset_words(k - 1), npop=P)
+                pa.record(res["parent"], res["qsum"], res["href"], k - 1)
+                lpr.append(pa.log_partition_ratio().tolist())
+                nfam.append(pa.n_families[-1].tolist())
+                rho.append(pa.rho_t[-1].tolist())
+            for block in self._sample_blocks(mcmc_steps, None, thin_by, state_loaded=True):
+                self.samples.append_block(block, thinned_by=thin_by)
+        self.samples.metadata["population_annealing"] = dict(
+            temperatures=temperatures, populations=P, seed=int(seed), log_partition_ratio=lpr, n_families=nfam, rho_t=rho)
+        self._resume_at = (id(self.samples), self.samples.num_samples)
+        return pa

@@ -750,3 +750,185 @@ def run_wl_exchange(engine, wx, n_exchanges, steps_between, host_decide=False, h
     if not host_decide:
         wx.estimator_of = engine.wl_windows()[2].astype(np.int64)
     return wx
+
+
+# ---- population annealing: reweight, resample and clone a population of walkers (smolmc_anneal_resample) ------------
+class PopulationAnnealing:
+    """Bookkeeping and definition of population annealing (Hukushima & Iba 2003; Machta, PRE 82, 026704) in one handle.
+
+    ``temperatures`` (K + 1,) is the schedule T_0 .. T_K; the R walkers of a handle are ``populations`` contiguous
+    blocks of n = R / populations walkers that are annealed independently.  Step k takes every population from
+    beta = 1 / (kB T_k) to beta' = 1 / (kB T_{k+1}), db = beta' - beta of either sign, by a move defined in integers:
+
+        H_ref = min H (db > 0) or max H;   w_j = exp(-(db * (H_j - H_ref)));   q_j = floor(w_j 2^40);   Q = sum q_j
+        off = (word * Q) >> 64,  word = uint64(u 2^53) << 11 with u one Philox uniform per population and step
+        C_j = q_0 + ... + q_j;   child m (0 <= m < n) descends from the smallest j with n C_j > m Q + off
+        every survivor keeps its slot; the k-th slot without a child takes the k-th surplus copy, of the donors
+        repeat(arange(n), max(cnt - 1, 0)):  parent[m], and parent[parent[m]] == parent[m]
+        ln Q_p = log(Q / (n 2^40)) - db * H_ref
+
+    The sum of ln Q_p over the steps estimates ln Z(beta_K) - ln Z(beta_0).  ``weights`` and ``parent_map`` are the
+    definition the device kernels (pop_anneal.hip) are tested against: q up to the last bit of exp, the map exactly.
+    ``family[w]`` is the walker of the start population that walker w descends from."""
+
+    SCALE_BITS = 40
+    MAX_POPULATION = 1 << 22  # Q < 2^62
+
+    def __init__(self, temperatures, populations=1, seed=0):
+        self.temperatures = np.ascontiguousarray(temperatures, dtype=np.float64).reshape(-1)
+        self.populations, self.philox_seed = int(populations), int(seed)
+        if len(self.temperatures) < 1 or not np.all(self.temperatures > 0) or not np.all(np.isfinite(self.temperatures)):
+            raise ValueError("PopulationAnnealing needs a schedule of positive, finite temperatures")
+        if self.populations < 1:
+            raise ValueError("PopulationAnnealing needs populations >= 1")
+        self.betas = 1.0 / (kB * self.temperatures)
+        self.calls = 0
+        self.log_q = np.zeros((0, self.populations))  # (steps taken, P): ln Q_p of every step
+        self.n_families = np.zeros((0, self.populations), dtype=np.int64)
+        self.rho_t = np.zeros((0, self.populations))
+        self.family = None  # (R,) set by the first step: the identity before it
+
+    @property
+    def n_steps(self):
+        """Resampling steps of the schedule."""
+        return len(self.temperatures) - 1
+
+    def offset_words(self, attempt):
+        """The uint64 offset word of every population at step ``attempt`` (a pure function of the seed and the step)."""
+        u = _philox_uniforms(self.philox_seed, attempt, self.populations)
+        return (u * 2.0 ** 53).astype(np.uint64) << np.uint64(11)
+
+    @classmethod
+    def weights(cls, enthalpy, beta_old, beta_new):
+        """(q (n,) uint64, Q int, H_ref) of one population."""
+        H = np.asarray(enthalpy, dtype=np.float64).reshape(-1)
+        db = np.float64(beta_new) - np.float64(beta_old)
+        href = H.min() if db > 0 else H.max()
+        w = np.exp(-(db * (H - href)))
+        q = np.floor(w * 2.0 ** cls.SCALE_BITS).astype(np.uint64)
+        return q, int(sum(int(x) for x in q)), float(href)
+
+    @staticmethod
+    def children(q, word):
+        """cnt (n,) int64: the children of every walker of one population under systematic resampling."""
+        q = [int(x) for x in np.asarray(q).reshape(-1)]
+        n, Q = len(q), sum(q)
+        if Q <= 0:
+            raise ValueError("the weights of a population sum to zero")
+        off = (int(word) * Q) >> 64
+        C = np.cumsum(np.asarray(q, dtype=np.uint64), dtype=np.uint64)  # (Q < 2^62: exact)
+        # n C_j > m Q + off  <=>  C_j > (m Q + off) // n, both sides integers: the first j is a sorted search
+        thr = np.array([(m * Q + off) // n for m in range(n)], dtype=np.uint64)
+        anc = np.searchsorted(C, thr, side="right")
+        return np.bincount(anc, minlength=n).astype(np.int64)
+
+    @classmethod
+    def parent_map(cls, q, word):
+        """parent (n,) int64 of one population: slot m takes the state of slot parent[m]."""
+        cnt = cls.children(q, word)
+        n = len(cnt)
+        parent = np.arange(n)
+        parent[cnt == 0] = np.repeat(np.arange(n), np.maximum(cnt - 1, 0))
+        return parent
+
+    def log_q_of(self, qsum, href, beta_old, beta_new, n):
+        """ln Q_p of a step from the sum of the weights and H_ref of every population."""
+        db = np.float64(beta_new) - np.float64(beta_old)
+        ratio = np.array([int(Q) / (n * 2.0 ** self.SCALE_BITS) for Q in np.asarray(qsum).reshape(-1)])
+        return np.log(ratio) - db * np.asarray(href, dtype=np.float64).reshape(-1)
+
+    def record(self, parent, qsum, href, attempt):
+        """Take a step's outcome into the running sums and the lineage: ``parent`` (R,) slot numbers, ``qsum`` and
+        ``href`` (P,).  Returns ln Q_p (P,)."""
+        parent = np.asarray(parent, dtype=np.int64).reshape(-1)
+        P, R = self.populations, len(parent)
+        n = R // P
+        lq = self.log_q_of(qsum, href, self.betas[attempt], self.betas[attempt + 1], n)
+        if self.family is None:
+            self.family = np.arange(R)
+        self.family = self.family[parent]
+        fam = self.family.reshape(P, n)
+        nf, rho = np.zeros(P, dtype=np.int64), np.zeros(P)
+        for p in range(P):
+            _, sizes = np.unique(fam[p], return_counts=True)
+            nf[p], rho[p] = len(sizes), float(np.sum(sizes.astype(np.float64) ** 2)) / n  # rho_t = n sum f_i^2
+        self.log_q = np.vstack([self.log_q, lq[None]])
+        self.n_families = np.vstack([self.n_families, nf[None]])
+        self.rho_t = np.vstack([self.rho_t, rho[None]])
+        self.calls = int(attempt) + 1
+        return lq
+
+    def step(self, enthalpy, attempt, record=True):
+        """The whole move of step ``attempt`` over all populations on the host: enthalpy (R,) in; returns dict(parent
+        (R,) slot numbers, q (R,) uint64, qsum (P,) uint64, href (P,), log_q (P,))."""
+        H = np.asarray(enthalpy, dtype=np.float64).reshape(-1)
+        P, R = self.populations, len(H)
+        if R % P or R // P > self.MAX_POPULATION:
+            raise ValueError(f"{P} populations do not divide the {R} walkers into blocks of at most 2^22")
+        n = R // P
+        b0, b1 = self.betas[attempt], self.betas[attempt + 1]
+        words = self.offset_words(attempt)
+        parent, q = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.uint64)
+        qsum, href = np.zeros(P, dtype=np.uint64), np.zeros(P)
+        for p in range(P):
+            sl = slice(p * n, (p + 1) * n)
+            q[sl], Q, href[p] = self.weights(H[sl], b0, b1)
+            qsum[p] = Q
+            parent[sl] = p * n + self.parent_map(q[sl], words[p])
+        lq = self.record(parent, qsum, href, attempt) if record else self.log_q_of(qsum, href, b0, b1, n)
+        return dict(parent=parent, q=q, qsum=qsum, href=href, log_q=lq)
+
+    def log_partition_ratio(self):
+        """(P,): the sum of ln Q_p over the steps taken, the estimate of ln Z(beta_now) - ln Z(beta_0)."""
+        return self.log_q.sum(axis=0)
+
+    def free_energy(self, log_z0=0.0):
+        """(steps taken, P): -ln Z(beta_k) / beta_k along the schedule, k = 1 .., with ln Z(beta_0) = ``log_z0``."""
+        k = len(self.log_q)
+        return -(log_z0 + np.cumsum(self.log_q, axis=0)) / self.betas[1:k + 1, None]
+
+    def population_weights(self):
+        """(P,) normalised exp(sum ln Q_p): the weight of a population in an average over populations."""
+        lpr = self.log_partition_ratio()
+        w = np.exp(lpr - lpr.max())
+        return w / w.sum()
+
+    def combine(self, values):
+        """The exp(sum ln Q)-weighted average across populations of per-population ``values`` (P, ...)."""
+        v = np.asarray(values, dtype=np.float64)
+        return np.tensordot(self.population_weights(), v, axes=(0, 0))
+
+    def combined_log_partition_ratio(self):
+        """ln of the mean over populations of exp(sum ln Q_p): the populations' joint estimate of ln Z / Z_0."""
+        lpr = self.log_partition_ratio()
+        return float(lpr.max() + np.log(np.mean(np.exp(lpr - lpr.max()))))
+
+
+def run_population_annealing(engine, pa, steps_per_temperature, host_decide=False, history=None):
+    """Anneal the walkers of ``engine`` along ``pa.temperatures``: at every step of the schedule the populations are
+    reweighted, resampled and cloned, then every walker runs ``steps_per_temperature`` Metropolis steps at the new
+    temperature.  ``engine`` holds R walkers (R a multiple of ``pa.populations``) with their state loaded at
+    ``pa.temperatures[0]``.  Default: the move runs on the device (``Engine.anneal_resample``), only the map, the
+    weights' sums and H_ref come back.  ``host_decide=True`` (also on ``oracle.OracleMC``): the state is read back,
+    ``pa.step`` decides, and the clones go through ``set_state(occupancy[parent], reset_aux=False)`` -- enthalpies are
+    then evaluated afresh, so the two paths agree statistically, not bit for bit.  ``history``: a list that receives
+    the parent map of every step."""
+    R, P = int(engine.R), pa.populations
+    if R % P:
+        raise ValueError(f"{P} populations do not divide the engine's {R} walkers")
+    for k in range(pa.calls, pa.n_steps):
+        t_new = pa.temperatures[k + 1]
+        if host_decide:
+            st = engine.get_state()
+            res = pa.step(st["enthalpy"], k)
+            parent = res["parent"]
+            engine.set_state(st["occupancy"][parent], np.zeros(R, dtype=np.uint64), np.full(R, t_new), reset_aux=False)
+            engine.set_counters(st["n_steps"], st["n_accepted"])
+        else:
+            res = engine.anneal_resample(np.full(P, t_new), pa.offset_words(k), npop=P)
+            parent = res["parent"]
+            pa.record(parent, res["qsum"], res["href"], k)
+        if history is not None:
+            history.append(np.array(parent))
+        engine.run(int(steps_per_temperature))
+    return pa

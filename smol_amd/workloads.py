@@ -373,5 +373,28 @@ def config15(first=0, count=1024, dim=16, mc=5000, h0=None):
     return w
 
 
+CONFIG16_T, CONFIG16_STEPS, CONFIG16_POPULATIONS = (3000.0, 300.0), 16, 4  # config 16: the schedule of the population annealing
+
+
+def config16(first=0, count=4096, dim=16, mc=10000):
+    """Config 2 cooled from 3000 K to 300 K under population annealing: its Hamiltonian and starts, a geometric schedule of
+    16 temperatures, 4 populations of count / 4 walkers (error bars), ``mc`` swap steps per walker and temperature.
+    ``extras["pop_anneal"]`` is the ``parallel.PopulationAnnealing`` (``parallel.run_population_annealing(engine, pa,
+    mc)``); the handle starts at the first temperature."""
+    from . import parallel
+
+    if first != 0:
+        raise ValueError("config 16 runs inside one engine handle: no sharding over ranks")
+    if count % CONFIG16_POPULATIONS:
+        raise ValueError(f"config 16 wants a multiple of {CONFIG16_POPULATIONS} walkers")
+    w = config2(first, count, dim, mc=mc)
+    w.key, w.temperature = 16, CONFIG16_T[0]
+    w.name = (f"config16: config 2 under population annealing, {CONFIG16_T[0]:g} K -> {CONFIG16_T[1]:g} K in {CONFIG16_STEPS} "
+              f"temperatures, {CONFIG16_POPULATIONS} populations x {count // CONFIG16_POPULATIONS} walkers")
+    w.extras.update(pop_anneal=parallel.PopulationAnnealing(np.geomspace(CONFIG16_T[0], CONFIG16_T[1], CONFIG16_STEPS),
+                                                            populations=CONFIG16_POPULATIONS, seed=16))
+    return w
+
+
 BUILDERS = {1: config1, 2: config2, 3: config3, 4: config4, 5: config5, 6: config6, 7: config7,
-            8: config8, 9: config9, 10: config10, 11: config11, 12: config12, 13: config13, 14: config14, 15: config15}
+            8: config8, 9: config9, 10: config10, 11: config11, 12: config12, 13: config13, 14: config14, 15: config15, 16: config16}

@@ -35,6 +35,34 @@ def windowed_engine(wl, chunk=20000, max_chunks=150):
     return eng, wx, seed_steps
 
 
+def population_annealing(wl, eng):
+    """Config 16: the whole schedule on the device, wall clock; the resampling steps timed on their own afterwards (each
+    waits for its outputs, so its time includes the kernels queued before it: a second pass with one step between)."""
+    import time
+
+    pa, mc = wl.extras["pop_anneal"], wl.mc_per_launch
+    t0 = time.perf_counter()
+    parallel.run_population_annealing(eng, pa, mc)
+    st = eng.get_state(occupancy=False)
+    wall = time.perf_counter() - t0
+    n = wl.n_walkers // pa.populations
+    H = st["enthalpy"].reshape(pa.populations, n)
+    eng.set_state(wl.occupancy, wl.seeds, wl.temperature)
+    eng.run(mc, sync=True)
+    t1 = time.perf_counter()
+    again = parallel.run_population_annealing(eng, parallel.PopulationAnnealing(pa.temperatures, pa.populations, pa.philox_seed), 1)
+    eng.sync()
+    resample_ms = (time.perf_counter() - t1) * 1e3 / again.n_steps
+    print(json.dumps(dict(
+        config=wl.name, kernel=eng.kernel_info(), replicas=wl.n_walkers, mc_steps_per_temperature=mc,
+        temperatures=[float(t) for t in pa.temperatures], wall_s=wall,
+        mc_steps_per_s=wl.n_walkers * mc * pa.n_steps / wall, resample_ms=resample_ms,
+        log_partition_ratio=pa.log_partition_ratio().tolist(), combined_log_partition_ratio=pa.combined_log_partition_ratio(),
+        n_families=pa.n_families[-1].tolist(), rho_t=pa.rho_t[-1].tolist(),
+        final_mean_enthalpy=H.mean(axis=1).tolist(), final_min_enthalpy=H.min(axis=1).tolist(),
+        acceptance=float(st["n_accepted"].sum()) / float(st["n_steps"].sum()))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, required=True, choices=sorted(workloads.BUILDERS))
@@ -78,6 +106,8 @@ def main():
         eng.set_walker_mu(eng.get_walker_mu())
     if seed_steps is None:
         eng.set_state(wl.occupancy, wl.seeds, T)
+    if "pop_anneal" in wl.extras:  # config 16: the annealing schedule instead of launches at one temperature
+        return population_annealing(wl, eng)
     R, mc = wl.n_walkers, wl.mc_per_launch
     rex = None
     if a.config == 5:
