@@ -387,6 +387,10 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     static_assert(!WMU || (HAS_MU && !WL && !REPLAY), "per-walker chemical potentials: semigrand Metropolis variants");
     constexpr bool ROWS = lean_rows(MM);
     constexpr int MMX = lean_mm_max(MM);
+    // STRAIGHT: the rows swap kernels at the compiler's occupancy lay the common step out in a straight line (proposal and
+    // decision below).  Measured per shape: the flip kernels lost 3-7 % with the select decision and keep the parent's
+    // form; the chemical-potential and OCC 6 kernels are not measured and keep it too (NOTES.md)
+    constexpr bool STRAIGHT = ROWS && STEP == SMOLMC_STEP_SWAP && OCC == 0 && !HAS_MU;
     // (Ewald, replay, the KF tables and Wang-Landau all use the site NUMBER, which the ROWS variants do not carry)
     static_assert(!ROWS || (SOLO && NSLOT == 2 && EWX == 0 && !REPLAY && KF == 0 && !WL && !BIAS), "solo rows: plain Metropolis, solo layout");
     // EWM: 0 = no Ewald term, 1 = compact Ewald with per-proposal row sums, 2 = potential field in
@@ -761,6 +765,60 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         if (J == 0) fb = b;                                                                        \
     }
             SMOLMC_CAND_MASK(0)
+            if constexpr (STRAIGHT) {
+                // straight-line first round: the hit (7 of 8 steps at 50/50) falls through to ONE take behind the
+                // merge; rounds 1-3 and the second-round fallback sit in a cold region behind the loop and leave
+                // their pick where the take reads it (the fallback in every lane, with mask 1)
+                unsigned long long mt = m0;
+                uint32_t ta = (uint32_t)canda[0];
+                int tv = v0;
+                if (__builtin_expect(m0 == 0ull, 0)) {
+                    SMOLMC_CAND_MASK(1)
+                    mt = m1; ta = (uint32_t)canda[1]; tv = v1;
+                    if (m1 == 0ull) {
+                        SMOLMC_CAND_MASK(2)
+                        mt = m2; ta = (uint32_t)canda[2]; tv = v2;
+                        if (m2 == 0ull) {
+                            SMOLMC_CAND_MASK(3)
+                            mt = m3; ta = (uint32_t)canda[3]; tv = v3;
+                            if (m3 == 0ull) {
+                                mt = 1ull; ta = va1; tv = o1; nfl = 0; // empty step unless a candidate is found
+                                // (second-round fallback: the same loop as in the nested chain below -- fix both)
+                                const unsigned long long cur = chunk_end - chunk; // this step (rare path)
+                                for (uint32_t q = 0;; ++q) {
+                                    const philox_out o = philox4x32_10((uint32_t)cur, (uint32_t)(cur >> 32),
+                                                                       4u + 64u * q + (uint32_t)lane, 0u, key0, key1);
+                                    int selsite = -1, selv = 0;
+#pragma unroll
+                                    for (int j = 3; j >= 0; --j) {
+                                        const int cs = sbase + (int)__umulhi(o.w[j], nact);
+                                        const int v = (int)occ[lean_swz(cs, swa, swm, swb)];
+                                        if (v != o1) { selsite = lean_swz(cs, swa, swm, swb); selv = v; } // (the address stands for the site)
+                                    }
+                                    const unsigned long long m = __ballot(selsite >= 0);
+                                    if (m) {
+                                        const int b = __ffsll((long long)m) - 1;
+                                        ta = rdlane((uint32_t)selsite, b);
+                                        tv = (int)rdlane((uint32_t)selv, b);
+                                        nfl = 2;
+                                        break;
+                                    }
+                                    if ((q & 63u) == 0) { // swap_options.size == 0 -> empty step
+                                        int any = 0;
+                                        for (uint32_t a = lane; a < nact; a += 64)
+                                            any |= ((int)occ[lean_swz(sbase + (int)a, swa, swm, swb)] != o1);
+                                        if (__ballot(any) == 0ull) break;
+                                    }
+                                }
+                            }
+                        }
+                    }
+                }
+                const int b = __ffsll((long long)mt) - 1;
+                a2 = (int)rdlane(ta, b);
+                o2 = (int)rdlane((uint32_t)tv, b);
+                s2 = a2; // (the rows variants carry no site numbers)
+            } else
             if (m0) SMOLMC_CAND_TAKE(0)
             else {
                 SMOLMC_CAND_MASK(1)
@@ -772,7 +830,7 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                         SMOLMC_CAND_MASK(3)
                         if (m3) SMOLMC_CAND_TAKE(3)
                         else {
-                            bool hit = false;
+                            bool hit = false; // (second-round fallback: the rows variants' straight form above repeats this loop -- fix both)
                             const unsigned long long cur = chunk_end - chunk; // this step (rare path)
                             for (uint32_t q = 0;; ++q) {
                                 const philox_out o = philox4x32_10((uint32_t)cur, (uint32_t)(cur >> 32),
@@ -1052,6 +1110,19 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             const unsigned long long bit = 1ull << (REPLAY ? 0 : l64); // (replay: the thresholds are uniform)
             const bool ca = (__ballot(S < thr_lo) & bit) != 0ull;
             const bool cr = (__ballot(S > thr_hi) & bit) != 0ull;
+            if constexpr (STRAIGHT) {
+                // decision by select: both outcomes end in the same store of the first site's species (accepted
+                // swap: at the partner; rejected: back at site 1) and in the SELACC updates below; the exact path is
+                // the one branch, out of line
+                bool ok = ca;
+                if (__builtin_expect(!(ca || cr), 0)) ok = exact_decision();
+                sel_hi = ok ? 0x3ff00000u : 0u;
+                // (the store takes the 32-bit value: stored as the byte the read returned, the read has a second user
+                // and the compiler widens it with a v_and 0xff at the head of the step's dependency chain)
+                uint32_t vst = (uint32_t)vo1;
+                asm("" : "+v"(vst));
+                occ_st<SOLO>(occ, ok ? (uint32_t)a2 : va1, (uint8_t)vst);
+            } else
             if (ca) on_accept();
             else if (cr) on_reject();
             else if (exact_decision()) on_accept();
