@@ -472,6 +472,7 @@ class TableSet:
         flip_table=None,
         flip_weights=None,
         swap_weight=0.1,
+        sublattice_probabilities=None,
     ):
         """Build from smol_amd.synth tables (SupercellTables + CE coefficients)."""
         model = sc.model
@@ -515,6 +516,7 @@ class TableSet:
             feature_mode,
             subs,
             nspecies_per_site=nsp,
+            sublattice_probabilities=sublattice_probabilities,
             ewald_inds=None if ewald is None else ewald[0],
             ewald_matrix=None if ewald is None else ewald[1],
             ewald_coef=ewald_coef,
