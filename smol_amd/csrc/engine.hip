@@ -2742,44 +2742,67 @@ extern "C" int smolmc_get_wl_windows(smolmc_handle *h, double *vmin, double *vma
     return 0;
 }
 
+// ---- one exchange attempt between disjoint pairs: what smolmc_exchange_wl (below) and smolmc_exchange_grid share -----
+// Either call takes npairs pairs of entries 0 .. R - 1 (`noun` says what an entry names) with one host-made log u per
+// pair, decides on the device and reads the accept flags back when `stats` is given.
+static int pair_exchange_check(const smolmc_handle *h, const char *fn, const char *noun, int npairs, const int32_t *pairs,
+                               const double *log_u) {
+    if (npairs < 0 || (npairs > 0 && (!pairs || !log_u))) return fail("null argument");
+    const int R = h->R;
+    std::vector<uint8_t> seen(R, 0);
+    for (int i = 0; i < 2 * npairs; ++i) {
+        const int p = pairs[i];
+        const auto entry = [&] { return std::string(fn) + ": " + noun + " " + std::to_string(p); };
+        if (p < 0 || p >= R) return fail(entry() + " of pair " + std::to_string(i / 2) + " is out of range 0 .. " + std::to_string(R - 1));
+        if (seen[p]) return fail(entry() + " appears in two pairs of one call (the pairs of a call are decided at once: they must be disjoint)");
+        seen[p] = 1;
+    }
+    for (int i = 0; i < npairs; ++i)
+        if (!std::isfinite(log_u[i]) && !(std::isinf(log_u[i]) && log_u[i] < 0))
+            return fail(std::string(fn) + ": log_u must be finite or -inf (pair " + std::to_string(i) + ")");
+    return 0;
+}
+// The staging of a call, h->d_pair_stage, allocated at the first one: log u [half] f64 | pairs [half][2] i32 | accept
+// flags [half] i32 with half = R / 2 (disjoint pairs: npairs <= R / 2).  Queues the uploads on the handle's stream.
+struct PairStage {
+    double *log_u;
+    int32_t *pairs, *acc;
+};
+static int pair_exchange_stage(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, PairStage &st) {
+    const size_t half = (size_t)h->R / 2;
+    if (!h->d_pair_stage) TRY(dev_alloc(h, 2 * half + half / 2 + 1, &h->d_pair_stage));
+    st.log_u = h->d_pair_stage;
+    st.pairs = (int32_t *)(h->d_pair_stage + half);
+    st.acc = (int32_t *)(h->d_pair_stage + 2 * half);
+    // (pageable sources: the runtime has read them -- into its staging memory, or to the device -- when hipMemcpyAsync
+    // returns, so the caller may free them at once; the copies wait for the work queued before them on the stream)
+    HIPCHK(hipMemcpyAsync(st.log_u, log_u, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(st.pairs, pairs, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+// stats [npairs][2] gains the attempts and the acceptances of the call (this waits for the kernel)
+static int pair_exchange_stats(smolmc_handle *h, int npairs, const int32_t *d_acc, int64_t *stats) {
+    std::vector<int32_t> acc(npairs);
+    HIPCHK(hipMemcpyAsync(acc.data(), d_acc, (size_t)npairs * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < npairs; ++i) {
+        stats[2 * i] += 1;
+        stats[2 * i + 1] += acc[i];
+    }
+    return 0;
+}
+
 extern "C" int smolmc_exchange_wl(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int64_t *stats) {
     if (!h) return fail("null handle");
     TRY(wl_windows_refused(h, "smolmc_exchange_wl"));
     if (h->wl_win_min.empty()) return fail("smolmc_exchange_wl: no per-walker windows are set (smolmc_set_wl_windows first)");
-    if (npairs < 0 || (npairs > 0 && (!pairs || !log_u))) return fail("null argument");
-    const int R = h->R;
-    {
-        std::vector<uint8_t> seen(R, 0);
-        for (int i = 0; i < 2 * npairs; ++i) {
-            const int p = pairs[i];
-            if (p < 0 || p >= R) return fail("smolmc_exchange_wl: estimator " + std::to_string(p) + " of pair " + std::to_string(i / 2) + " is out of range 0 .. " + std::to_string(R - 1));
-            if (seen[p]) return fail("smolmc_exchange_wl: estimator " + std::to_string(p) + " appears in two pairs of one call (the pairs of a call are decided at once: they must be disjoint)");
-            seen[p] = 1;
-        }
-        for (int i = 0; i < npairs; ++i)
-            if (!std::isfinite(log_u[i]) && !(std::isinf(log_u[i]) && log_u[i] < 0))
-                return fail("smolmc_exchange_wl: log_u must be finite or -inf (pair " + std::to_string(i) + ")");
-    }
+    TRY(pair_exchange_check(h, "smolmc_exchange_wl", "estimator", npairs, pairs, log_u));
     if (npairs == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
-    const size_t half = (size_t)R / 2; // (disjoint pairs: npairs <= R / 2)
-    if (!h->d_wlx_stage) TRY(dev_alloc(h, 2 * half + half / 2 + 1, &h->d_wlx_stage)); // log u [half] f64 | pairs [half][2] i32 | accept flags [half] i32
-    double *d_log_u = h->d_wlx_stage;
-    int32_t *d_pairs = (int32_t *)(h->d_wlx_stage + half), *d_acc = (int32_t *)(h->d_wlx_stage + 2 * half);
-    // (pageable sources, as in smolmc_exchange_grid: the caller may free them when the call returns)
-    HIPCHK(hipMemcpyAsync(d_log_u, log_u, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_pairs, pairs, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
-    TRY(smolmc_wl_exchange_launch(h, npairs, d_pairs, d_log_u, d_acc));
-    if (stats) {
-        std::vector<int32_t> acc(npairs);
-        HIPCHK(hipMemcpyAsync(acc.data(), d_acc, (size_t)npairs * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        for (int i = 0; i < npairs; ++i) {
-            stats[2 * i] += 1;
-            stats[2 * i + 1] += acc[i];
-        }
-    }
-    return 0;
+    PairStage st;
+    TRY(pair_exchange_stage(h, npairs, pairs, log_u, st));
+    TRY(smolmc_wl_exchange_launch(h, npairs, st.pairs, st.log_u, st.acc));
+    return stats ? pair_exchange_stats(h, npairs, st.acc, stats) : 0;
 }
 
 extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint64_t *seeds,
@@ -3844,52 +3867,25 @@ static int grid_exchange_refused(const smolmc_handle *h, const char *what) {
 extern "C" int smolmc_exchange_grid(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int64_t *stats) {
     if (!h) return fail("null handle");
     TRY(grid_exchange_refused(h, "smolmc_exchange_grid"));
-    if (npairs < 0 || (npairs > 0 && (!pairs || !log_u))) return fail("null argument");
-    const int R = h->R;
-    {
-        std::vector<uint8_t> seen(R, 0);
-        for (int i = 0; i < 2 * npairs; ++i) {
-            const int p = pairs[i];
-            if (p < 0 || p >= R) return fail("smolmc_exchange_grid: state point " + std::to_string(p) + " of pair " + std::to_string(i / 2) + " is out of range 0 .. " + std::to_string(R - 1));
-            if (seen[p]) return fail("smolmc_exchange_grid: state point " + std::to_string(p) + " appears in two pairs of one call (the pairs of a call are decided at once: they must be disjoint)");
-            seen[p] = 1;
-        }
-        for (int i = 0; i < npairs; ++i)
-            if (!std::isfinite(log_u[i]) && !(std::isinf(log_u[i]) && log_u[i] < 0))
-                return fail("smolmc_exchange_grid: log_u must be finite or -inf (pair " + std::to_string(i) + ")");
-    }
+    TRY(pair_exchange_check(h, "smolmc_exchange_grid", "state point", npairs, pairs, log_u));
     if (npairs == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
-    const size_t half = (size_t)R / 2; // (disjoint pairs: npairs <= R / 2)
     if (!h->d_point_of) {
+        const int R = h->R;
         std::vector<int32_t> id(R);
         for (int r = 0; r < R; ++r) id[r] = r;
         TRY(dev_alloc(h, (size_t)R, &h->d_point_of));
         TRY(dev_alloc(h, (size_t)R, &h->d_walker_at));
-        TRY(dev_alloc(h, 2 * half + half / 2 + 1, &h->d_gx_stage)); // log u [half] f64 | pairs [half][2] i32 | accept flags [half] i32
         HIPCHK(hipMemcpy(h->d_point_of, id.data(), (size_t)R * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->d_walker_at, id.data(), (size_t)R * 4, hipMemcpyHostToDevice));
     }
-    double *d_log_u = h->d_gx_stage;
-    int32_t *d_pairs = (int32_t *)(h->d_gx_stage + half), *d_acc = (int32_t *)(h->d_gx_stage + 2 * half);
-    // (pageable sources: the runtime has read them -- into its staging memory, or to the device -- when hipMemcpyAsync
-    // returns, so the caller may free them at once; the copies wait for the work queued before them on the stream)
-    HIPCHK(hipMemcpyAsync(d_log_u, log_u, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_pairs, pairs, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
-    TRY(smolmc_grid_exchange_launch(h, npairs, d_pairs, d_log_u, d_acc, h->d_point_of, h->d_walker_at));
+    PairStage st;
+    TRY(pair_exchange_stage(h, npairs, pairs, log_u, st));
+    TRY(smolmc_grid_exchange_launch(h, npairs, st.pairs, st.log_u, st.acc, h->d_point_of, h->d_walker_at));
     h->grid_permuted = true;
     h->order_dirty = true;              // (as smolmc_set_temperature: the launch order of the TableFlip kernels follows the temperatures)
     if (is_lazy(h)) h->ce_dirty = true; // (as smolmc_set_walker_mu: kp.features takes its scalar entries from the lean kernels' rows)
-    if (stats) {
-        std::vector<int32_t> acc(npairs);
-        HIPCHK(hipMemcpyAsync(acc.data(), d_acc, (size_t)npairs * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        for (int i = 0; i < npairs; ++i) {
-            stats[2 * i] += 1;
-            stats[2 * i + 1] += acc[i];
-        }
-    }
-    return 0;
+    return stats ? pair_exchange_stats(h, npairs, st.acc, stats) : 0;
 }
 
 extern "C" int smolmc_get_state_points(smolmc_handle *h, int32_t *point_of, double *temperature) {

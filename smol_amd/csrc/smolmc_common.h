@@ -823,20 +823,20 @@ struct smolmc_handle {
     // exchange across the mu-T grid (smolmc_exchange_grid, engine.hip).  State point p is the (temperature, row) walker
     // p held at the latest smolmc_set_state / smolmc_set_temperature / smolmc_set_walker_mu: point_T its temperature as
     // given there, `walker_mu` above its row.  The walker -> point map and its inverse live on the device (allocated
-    // at the first exchange, with the staging of a call behind them: log u | pairs | accept flags); grid_permuted:
-    // exchanges ran since the identity map; point_T_stale: another call moved the temperatures on the device since.
+    // at the first exchange); grid_permuted: exchanges ran since the identity map; point_T_stale: another call moved
+    // the temperatures on the device since.
     std::vector<double> point_T;
     int32_t *d_point_of = nullptr, *d_walker_at = nullptr;
-    double *d_gx_stage = nullptr;
     bool grid_permuted = false, point_T_stale = false;
     // per-walker Wang-Landau windows (smolmc_set_wl_windows, engine.hip): the windows in ESTIMATOR order as given there
     // (empty: none set, every walker has the config's window).  On the device, behind kp.wl_m in one arena: the walkers'
-    // records WlWindow [R] (lp.wl.win_off) and the inverse map estimator -> walker, int32 [R] (d_wl_walker_at); behind
-    // them the staging of an exchange call (log u | pairs | accept flags, allocated at the first one).
+    // records WlWindow [R] (lp.wl.win_off) and the inverse map estimator -> walker, int32 [R] (d_wl_walker_at).
     std::vector<double> wl_win_min, wl_win_max;
     WlWindow *d_wl_win = nullptr;
     int32_t *d_wl_walker_at = nullptr;
-    double *d_wlx_stage = nullptr;
+    // the staging of a call of smolmc_exchange_grid or smolmc_exchange_wl (a handle takes one of the two): log u | pairs
+    // | accept flags, allocated at the first call and cut up by pair_exchange_stage (engine.hip)
+    double *d_pair_stage = nullptr;
     // population annealing (smolmc_anneal_resample / smolmc_resample, engine.hip): one device arena, allocated at the
     // first call, cut into the arrays of SmolmcPopScratch
     SmolmcPopScratch pop;

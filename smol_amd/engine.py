@@ -271,12 +271,8 @@ class Engine:
         self._chk(self._lib.smolmc_get_walker_mu(self._h, _p(out, C.c_double)))
         return out
 
-    def exchange_grid(self, pairs, log_u, stats=None):
-        """One exchange attempt across the mu-T grid, decided and applied on the device (smolmc_exchange_grid): for
-        every pair (s, t) of ``pairs`` (npairs, 2) the walkers at the state points s and t swap temperature and row
-        together when the move is accepted against ``log_u`` (npairs).  ``stats`` (npairs, 2) int64, when given, gains
-        the attempts in column 0 and the acceptances in column 1 (this waits for the kernel); without it the call only
-        queues work on the handle's stream."""
+    def _exchange_pairs(self, fn, pairs, log_u, stats):
+        """The call both pair exchanges make: disjoint ``pairs`` (npairs, 2), one ``log_u`` per pair, ``stats`` or None."""
         pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         log_u = np.ascontiguousarray(log_u, dtype=np.float64).reshape(-1)
         if len(log_u) != len(pairs):
@@ -284,8 +280,15 @@ class Engine:
         if stats is not None and not (isinstance(stats, np.ndarray) and stats.dtype == np.int64 and stats.flags.c_contiguous
                                       and stats.shape == (len(pairs), 2)):
             raise ValueError(f"stats must be a C-contiguous int64 array of shape ({len(pairs)}, 2)")
-        self._chk(self._lib.smolmc_exchange_grid(self._h, len(pairs), _p(pairs, C.c_int32), _p(log_u, C.c_double),
-                                                 _p(stats, C.c_int64)))
+        self._chk(fn(self._h, len(pairs), _p(pairs, C.c_int32), _p(log_u, C.c_double), _p(stats, C.c_int64)))
+
+    def exchange_grid(self, pairs, log_u, stats=None):
+        """One exchange attempt across the mu-T grid, decided and applied on the device (smolmc_exchange_grid): for
+        every pair (s, t) of ``pairs`` (npairs, 2) the walkers at the state points s and t swap temperature and row
+        together when the move is accepted against ``log_u`` (npairs).  ``stats`` (npairs, 2) int64, when given, gains
+        the attempts in column 0 and the acceptances in column 1 (this waits for the kernel); without it the call only
+        queues work on the handle's stream."""
+        self._exchange_pairs(self._lib.smolmc_exchange_grid, pairs, log_u, stats)
 
     def state_points(self):
         """(point_of (R,) int32, temperature (R,)): the state point every walker is at after the exchanges so far, and
@@ -321,15 +324,7 @@ class Engine:
         (smolmc_exchange_wl): for every pair (s, t) of ``pairs`` (npairs, 2) the walkers that hold the estimators s and
         t swap them when both enthalpies lie in both windows and the move is accepted against ``log_u`` (npairs).
         ``stats`` as in ``exchange_grid``."""
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        log_u = np.ascontiguousarray(log_u, dtype=np.float64).reshape(-1)
-        if len(log_u) != len(pairs):
-            raise ValueError(f"expected one log_u per pair: {len(pairs)} pairs, {len(log_u)} values")
-        if stats is not None and not (isinstance(stats, np.ndarray) and stats.dtype == np.int64 and stats.flags.c_contiguous
-                                      and stats.shape == (len(pairs), 2)):
-            raise ValueError(f"stats must be a C-contiguous int64 array of shape ({len(pairs)}, 2)")
-        self._chk(self._lib.smolmc_exchange_wl(self._h, len(pairs), _p(pairs, C.c_int32), _p(log_u, C.c_double),
-                                               _p(stats, C.c_int64)))
+        self._exchange_pairs(self._lib.smolmc_exchange_wl, pairs, log_u, stats)
 
     # ---- population annealing ------------------------------------------------------------
     def resample(self, parent):

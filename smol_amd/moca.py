@@ -2197,17 +2197,18 @@ class Sampler:
                 tr.occupancy = tr.occupancy.astype(np.int32)  # (trace.occupancy is int32 in the reference)
                 yield tr
 
+    def _need_start(self, initial_occupancies):
+        """A run starts from ``initial_occupancies`` or from the last saved sample: refuse when there is neither."""
+        if initial_occupancies is None and self.samples.num_samples == 0:
+            raise RuntimeError("There are no saved samples to obtain the initial occupancies."
+                               "These must be provided.")
+
     def run(self, nsteps, initial_occupancies=None, thin_by=1, progress=False, stream_chunk=0,
             stream_file=None, keep_last_chunk=False, swmr_mode=False):
         """sampler.py:212-301.  ``stream_chunk`` > 0 writes every chunk of samples to the streaming
         directory ``stream_file`` (see SampleContainer.get_backend) and keeps none in memory."""
-        if initial_occupancies is None:
-            if self.samples.num_samples == 0:
-                raise RuntimeError(
-                    "There are no saved samples to obtain the initial occupancies."
-                    "These must be provided."
-                )
-        elif self.samples.num_samples > 0:
+        self._need_start(initial_occupancies)
+        if initial_occupancies is not None and self.samples.num_samples > 0:
             warnings.warn(
                 "Initial occupancies where provided with a pre-existing set of samples.\n Make "
                 "real sure that is what you want. If not, reset the samples in the sampler.",
@@ -2244,20 +2245,13 @@ class Sampler:
         if wx is not self._wl_windows:
             raise ValueError("run_exchange(windows=) takes the WLWindows this sampler was built with (Sampler.from_ensemble(windows=))")
         thin_by = int(steps_between if thin_by is None else thin_by)
-        if initial_occupancies is None and self.samples.num_samples == 0:
-            raise RuntimeError("There are no saved samples to obtain the initial occupancies."
-                               "These must be provided.")
+        self._need_start(initial_occupancies)
         self._load_state(initial_occupancies)
         eng = self._get_engine()
         for _ in range(int(n_exchanges)):
             for block in self._sample_blocks(steps_between, None, thin_by, state_loaded=True):
                 self.samples.append_block(block, thinned_by=thin_by)
-            move = wx.move_of(wx.calls)
-            pairs = wx.pairs(move)
-            stats = np.zeros((len(pairs), 2), dtype=np.int64)
-            eng.exchange_wl(pairs, wx.log_u(wx.calls, len(pairs)), stats)
-            wx.record(move, stats[:, 1])
-            wx.calls += 1
+            wx.attempt(eng)
         wx.estimator_of = eng.wl_windows()[2].astype(np.int64)
         self._resume_at = None  # (the last sample precedes the last exchange: a continuation reloads nothing it could trust)
         return wx
@@ -2292,6 +2286,12 @@ class Sampler:
         if windows is not None or (grid is None and self._wl_windows is not None):
             return self._run_exchange_wl(n_exchanges, steps_between, initial_occupancies, thin_by,
                                          windows if windows is not None else self._wl_windows)
+        return self._run_exchange_grid(n_exchanges, steps_between, initial_occupancies, thin_by, grid)
+
+    def _run_exchange_grid(self, n_exchanges, steps_between, initial_occupancies, thin_by, grid):
+        """run_exchange across a mu-T grid, see there."""
+        from . import parallel
+
         if self._world > 1:
             raise ValueError("run_exchange on a sampler sharded over several ranks: the exchange across a mu-T grid runs "
                              "inside one engine handle (an exchange across ranks would gather counts as well as enthalpies)")
@@ -2330,27 +2330,17 @@ class Sampler:
             self.samples._state_point_now = np.asarray(gx.point_of, dtype=np.int32).reshape(nw, 1)
 
         assign(True)
-        if initial_occupancies is None and self.samples.num_samples == 0:
-            raise RuntimeError("There are no saved samples to obtain the initial occupancies."
-                               "These must be provided.")
+        self._need_start(initial_occupancies)
         self._load_state(initial_occupancies)
         eng = self._get_engine()
-        # (the engine's state point q is what walker q holds now: the grid's point base[q])
-        base = np.asarray(gx.point_of, dtype=np.int64).copy()
-        engine_point = np.empty(nw, dtype=np.int64)
-        engine_point[base] = np.arange(nw)
+        engine_point, read_back = gx.bind()
         for _ in range(int(n_exchanges)):
             for block in self._sample_blocks(steps_between, None, thin_by, state_loaded=True):
                 n = len(block["occupancy"])
                 block["state_point"] = np.broadcast_to(np.asarray(gx.point_of, dtype=np.int32).reshape(1, nw, 1), (n, nw, 1))
                 self.samples.append_block(block, thinned_by=thin_by)
-            move = gx.move_of(gx.calls)
-            pairs = gx.pairs(move)
-            stats = np.zeros((len(pairs), 2), dtype=np.int64)
-            eng.exchange_grid(engine_point[pairs], gx.log_u(gx.calls, len(pairs)), stats)
-            gx.record(move, stats[:, 1])
-            gx.calls += 1
-            gx.point_of = base[eng.state_points()[0]]
+            gx.attempt(eng, engine_point)
+            read_back(eng)
             assign(False)  # (the engine holds them already)
         self._resume_at = (id(self.samples), self.samples.num_samples)
         return gx
@@ -2403,9 +2393,7 @@ class Sampler:
         if self._walker_mu is not None:
             raise ValueError("anneal_population with per-walker chemical potentials: walkers of different "
                              "Hamiltonians are no population")
-        if initial_occupancies is None and self.samples.num_samples == 0:
-            raise RuntimeError("There are no saved samples to obtain the initial occupancies."
-                               "These must be provided.")
+        self._need_start(initial_occupancies)
         pa = parallel.PopulationAnnealing(temperatures, populations=P, seed=seed)
         n = nw // P
         lpr, nfam, rho = [[0.0] * P], [[n] * P], [[1.0] * P]

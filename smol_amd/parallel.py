@@ -349,8 +349,73 @@ def run_replica_exchange(engine, rex, n_exchanges, steps_between, device=None, c
     return rex
 
 
+# ---- exchanges between disjoint pairs, decided on the device: what the mu-T grid and the Wang-Landau windows share ------
+class PairExchange:
+    """Bookkeeping of an exchange whose attempt is one device call on disjoint pairs with one host-made ``log u`` per
+    pair (``Engine.exchange_grid``, ``Engine.exchange_wl``): the Philox seed, the attempt counter ``calls``, the pair
+    table of every move of ``MOVES`` and the ``attempted`` / ``accepted`` counts per move and pair.  A subclass names its
+    moves (``MOVES``), what makes a move the key of the tables (``_key``) and the engine's call (``ENGINE_CALL``), and
+    defines ``decide``."""
+
+    def _init_exchange(self, seed, pairs):
+        self.philox_seed, self.calls, self._pairs = int(seed), 0, pairs
+        self.attempted = {move: np.zeros(len(p), dtype=np.int64) for move, p in pairs.items()}
+        self.accepted = {move: np.zeros(len(p), dtype=np.int64) for move, p in pairs.items()}
+
+    def pairs(self, move):
+        """(npairs, 2) entries of one move: disjoint, so that an attempt decides them at once."""
+        return self._pairs[self._key(move)]
+
+    def move_of(self, attempt):
+        return self.MOVES[int(attempt) % len(self.MOVES)]
+
+    def log_u(self, attempt, npairs):
+        """log of the ``npairs`` uniforms of attempt ``attempt`` (a pure function of the seed and the attempt)."""
+        with np.errstate(divide="ignore"):
+            return np.log(_philox_uniforms(self.philox_seed, attempt, max(int(npairs), 1))[:npairs])
+
+    def record(self, move, accept):
+        self.attempted[self._key(move)] += 1
+        self.accepted[self._key(move)] += np.asarray(accept, dtype=np.int64)
+
+    @property
+    def acceptance(self):
+        """Accepted / attempted over all pairs of all moves."""
+        att = sum(int(a.sum()) for a in self.attempted.values())
+        return sum(int(a.sum()) for a in self.accepted.values()) / max(att, 1)
+
+    @staticmethod
+    def _holders(entry_of, pairs):
+        """(s, t, a, b) of ``decide``: the two entries of every pair and the walkers that hold them under the walker ->
+        entry map ``entry_of``."""
+        walker_at = np.empty(len(entry_of), dtype=np.int64)
+        walker_at[entry_of] = np.arange(len(entry_of))
+        s, t = pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64)
+        return s, t, walker_at[s], walker_at[t]
+
+    @staticmethod
+    def _swapped(entry_of, s, t, a, b, accept):
+        """The map after the accepted pairs swapped their entries."""
+        new = entry_of.copy()
+        new[a[accept]] = t[accept]
+        new[b[accept]] = s[accept]
+        return new
+
+    def attempt(self, engine, engine_entry=None):
+        """One attempt on the device: the move whose turn it is goes to ``engine`` with this attempt's ``log_u``, the
+        accept flags come back into ``record`` and ``calls`` moves on.  ``engine_entry``: the engine's number of every
+        entry, where it numbers them differently (``GridExchange.bind``)."""
+        move = self.move_of(self.calls)
+        pairs = self.pairs(move)
+        stats = np.zeros((len(pairs), 2), dtype=np.int64)
+        getattr(engine, self.ENGINE_CALL)(pairs if engine_entry is None else engine_entry[pairs],
+                                          self.log_u(self.calls, len(pairs)), stats)
+        self.record(move, stats[:, 1])
+        self.calls += 1
+
+
 # ---- exchange across a mu-T grid (hyper-parallel tempering, smolmc_exchange_grid) -------------------------------------
-class GridExchange:
+class GridExchange(PairExchange):
     """Bookkeeping of replica exchange across a grid of temperatures x rows of chemical potentials, in one handle.
 
     State point ``p = (rep * nT + i) * nMu + j`` is (``temperatures[i]``, ``rows[j]``) of replica set ``rep``;
@@ -367,6 +432,9 @@ class GridExchange:
     ``decide`` is this move in NumPy, in the operation order of the device kernel (grid_exchange.hip)."""
 
     MOVES = (("T", 0), ("T", 1), ("mu", 0), ("mu", 1))
+    ENGINE_CALL = "exchange_grid"
+    _key = staticmethod(tuple)
+    seed = property(lambda self: self.philox_seed)  # (under the constructor's name; WLWindows.seed is a method)
 
     def __init__(self, temperatures, rows, replicas=1, seed=0):
         self.temperatures = np.asarray(temperatures, dtype=np.float64).reshape(-1)
@@ -374,16 +442,13 @@ class GridExchange:
         if rows.ndim != 3:
             raise ValueError(f"expected rows of shape (points along mu, active sublattices, mu_width), got {rows.shape}")
         self.rows = np.ascontiguousarray(rows)
-        self.nT, self.nMu, self.replicas, self.seed = len(self.temperatures), len(self.rows), int(replicas), int(seed)
+        self.nT, self.nMu, self.replicas = len(self.temperatures), len(self.rows), int(replicas)
         self.npoints = self.replicas * self.nT * self.nMu
         _, i, j = np.unravel_index(np.arange(self.npoints), (self.replicas, self.nT, self.nMu))
         self.point_temperatures = self.temperatures[i]  # (npoints,)
         self.point_rows = self.rows[j]                  # (npoints, n_sublattices, mu_width)
         self.point_of = np.arange(self.npoints)         # walker -> point
-        self.calls = 0
-        self._pairs = {move: self._make_pairs(*move) for move in self.MOVES}
-        self.attempted = {move: np.zeros(len(p), dtype=np.int64) for move, p in self._pairs.items()}
-        self.accepted = {move: np.zeros(len(p), dtype=np.int64) for move, p in self._pairs.items()}
+        self._init_exchange(seed, {move: self._make_pairs(*move) for move in self.MOVES})
 
     def _make_pairs(self, axis, offset):
         grid = np.arange(self.npoints).reshape(self.replicas, self.nT, self.nMu)
@@ -395,28 +460,18 @@ class GridExchange:
             raise ValueError(f"unknown exchange axis {axis!r}")
         return np.stack([lo.reshape(-1), hi.reshape(-1)], axis=1).astype(np.int32).reshape(-1, 2)
 
-    def pairs(self, move):
-        """(npairs, 2) state points of one of the four moves."""
-        return self._pairs[tuple(move)]
+    def bind(self):
+        """For an engine whose walker q holds the point ``point_of[q]`` now, so that the engine's state point q is the
+        grid's point base[q]: (engine_point, the engine's number of every point, for ``attempt``; read_back(engine),
+        which sets ``point_of`` from the engine's walker -> point map)."""
+        base = np.asarray(self.point_of, dtype=np.int64).copy()
+        engine_point = np.empty(self.npoints, dtype=np.int64)
+        engine_point[base] = np.arange(self.npoints)
 
-    def move_of(self, attempt):
-        return self.MOVES[int(attempt) % len(self.MOVES)]
+        def read_back(engine):
+            self.point_of = base[engine.state_points()[0]]
 
-    def log_u(self, attempt, npairs):
-        """log of the ``npairs`` uniforms of attempt ``attempt`` (a pure function of the seed and the attempt)."""
-        with np.errstate(divide="ignore"):
-            return np.log(_philox_uniforms(self.seed, attempt, max(int(npairs), 1))[:npairs])
-
-    def record(self, move, accept):
-        move = tuple(move)
-        self.attempted[move] += 1
-        self.accepted[move] += np.asarray(accept, dtype=np.int64)
-
-    @property
-    def acceptance(self):
-        """Accepted / attempted over all pairs of all moves."""
-        att = sum(int(a.sum()) for a in self.attempted.values())
-        return sum(int(a.sum()) for a in self.accepted.values()) / max(att, 1)
+        return engine_point, read_back
 
     def decide(self, enthalpy, counts, point_of, move, attempt, log_u=None, record=True):
         """One attempt of ``move`` on the host: enthalpy (R,), species counts (R, n_sublattices, mu_width) and the
@@ -429,10 +484,7 @@ class GridExchange:
         counts = np.asarray(counts).reshape(self.npoints, -1).astype(np.float64)
         cells = self.point_rows.reshape(self.npoints, -1)
         pairs = self.pairs(move)
-        walker_at = np.empty(self.npoints, dtype=np.int64)
-        walker_at[point_of] = np.arange(self.npoints)
-        s, t = pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64)
-        a, b = walker_at[s], walker_at[t]
+        s, t, a, b = self._holders(point_of, pairs)
         beta = 1.0 / (kB * self.point_temperatures)
         wa, wb = np.zeros(len(pairs)), np.zeros(len(pairs))
         for c in range(cells.shape[1]):  # (written out: np.dot sums in another order)
@@ -444,9 +496,7 @@ class GridExchange:
             log_u = self.log_u(attempt, len(pairs))
         log_u = np.asarray(log_u, dtype=np.float64)
         accept = (-delta >= 0) | (log_u < -delta)
-        new_point_of = point_of.copy()
-        new_point_of[a[accept]] = t[accept]
-        new_point_of[b[accept]] = s[accept]
+        new_point_of = self._swapped(point_of, s, t, a, b, accept)
         work = np.zeros(self.npoints)
         work[a[accept]] = wa[accept]
         work[b[accept]] = -wb[accept]
@@ -465,32 +515,27 @@ def run_grid_exchange(engine, gx, n_exchanges, steps_between, host_decide=False,
     against.  ``history``: a list that receives ``gx.point_of`` after every attempt."""
     if engine.R != gx.npoints:
         raise ValueError(f"the grid has {gx.npoints} state points, the engine {engine.R} walkers")
-    base = np.asarray(gx.point_of, dtype=np.int64).copy()  # walker -> point now: the engine's point q is the grid's base[q]
-    engine_point = np.empty(gx.npoints, dtype=np.int64)
-    engine_point[base] = np.arange(gx.npoints)
-    engine.set_walker_mu(gx.point_rows[base])
-    engine.set_temperature(gx.point_temperatures[base])
+    engine_point, read_back = gx.bind()
+    engine.set_walker_mu(gx.point_rows[gx.point_of])
+    engine.set_temperature(gx.point_temperatures[gx.point_of])
     for _ in range(int(n_exchanges)):
         engine.run(steps_between)
-        move = gx.move_of(gx.calls)
-        pairs = gx.pairs(move)
         if host_decide:
+            move = gx.move_of(gx.calls)
             st = engine.get_state()
             res = gx.decide(st["enthalpy"], engine.species_counts(st["occupancy"]), gx.point_of, move, gx.calls)
             gx.point_of = res["point_of"]
             engine.set_temperature(gx.point_temperatures[gx.point_of])
             engine.set_walker_mu(gx.point_rows[gx.point_of])
+            gx.calls += 1
         else:
-            stats = np.zeros((len(pairs), 2), dtype=np.int64)
-            engine.exchange_grid(engine_point[pairs], gx.log_u(gx.calls, len(pairs)), stats)
-            gx.record(move, stats[:, 1])
+            gx.attempt(engine, engine_point)
             if history is not None:
-                gx.point_of = base[engine.state_points()[0]]
-        gx.calls += 1
+                read_back(engine)
         if history is not None:
             history.append(np.array(gx.point_of))
     if not host_decide:
-        gx.point_of = base[engine.state_points()[0]]
+        read_back(engine)
     return gx
 
 
@@ -500,7 +545,7 @@ def wl_num_levels(vmin, vmax, bin_size):
     return int(math.ceil((float(vmax) - float(vmin)) / float(bin_size)))
 
 
-class WLWindows:
+class WLWindows(PairExchange):
     """Bookkeeping of replica-exchange Wang-Landau (Vogel, Li, Wuest, Landau, PRL 110, 210603) in one handle.
 
     The global range ``[min_enthalpy, max_enthalpy)`` has ``L = ceil((max - min) / bin_size)`` bins.  It is cut into
@@ -520,11 +565,13 @@ class WLWindows:
     (wl_exchange.hip); ``join`` makes one ln g of the pieces."""
 
     MOVES = (0, 1)
+    ENGINE_CALL = "exchange_wl"
+    _key = staticmethod(int)
 
     def __init__(self, min_enthalpy, max_enthalpy, bin_size, n_windows, overlap=0.5, copies=1, seed=0,
                  window_bins=None, stride_bins=None):
         self.min_enthalpy, self.max_enthalpy, self.bin_size = float(min_enthalpy), float(max_enthalpy), float(bin_size)
-        self.n_windows, self.copies, self.philox_seed = int(n_windows), int(copies), int(seed)  # (seed: the method below)
+        self.n_windows, self.copies = int(n_windows), int(copies)
         if self.n_windows < 1 or self.copies < 1 or not (0.0 <= overlap < 1.0) or not self.bin_size > 0:
             raise ValueError("WLWindows needs n_windows >= 1, copies >= 1, 0 <= overlap < 1 and bin_size > 0")
         self.L = wl_num_levels(self.min_enthalpy, self.max_enthalpy, self.bin_size)
@@ -555,38 +602,13 @@ class WLWindows:
         self.vmin, self.vmax = wmin[self.window_of], wmax[self.window_of]  # (R,) in estimator order
         self.R = n * self.copies
         self.estimator_of = np.arange(self.R)
-        self.calls = 0
-        self._pairs = {m: self._make_pairs(m) for m in self.MOVES}
-        self.attempted = {m: np.zeros(len(p), dtype=np.int64) for m, p in self._pairs.items()}
-        self.accepted = {m: np.zeros(len(p), dtype=np.int64) for m, p in self._pairs.items()}
+        self._init_exchange(seed, {m: self._make_pairs(m) for m in self.MOVES})  # (philox_seed: `seed` is the method below)
 
     def _make_pairs(self, move):
         lo = np.arange(int(move), self.n_windows - 1, 2)
         i = np.arange(self.copies)
         s = (lo[:, None] * self.copies + i[None, :]).reshape(-1)
         return np.stack([s, s + self.copies], axis=1).astype(np.int32).reshape(-1, 2)
-
-    def pairs(self, move):
-        """(npairs, 2) estimators of move 0 (even neighbouring windows) or 1 (odd)."""
-        return self._pairs[int(move)]
-
-    def move_of(self, attempt):
-        return self.MOVES[int(attempt) % len(self.MOVES)]
-
-    def log_u(self, attempt, npairs):
-        """log of the ``npairs`` uniforms of attempt ``attempt`` (a pure function of the seed and the attempt)."""
-        with np.errstate(divide="ignore"):
-            return np.log(_philox_uniforms(self.philox_seed, attempt, max(int(npairs), 1))[:npairs])
-
-    def record(self, move, accept):
-        self.attempted[int(move)] += 1
-        self.accepted[int(move)] += np.asarray(accept, dtype=np.int64)
-
-    @property
-    def acceptance(self):
-        """Accepted / attempted over all pairs of both moves."""
-        att = sum(int(a.sum()) for a in self.attempted.values())
-        return sum(int(a.sum()) for a in self.accepted.values()) / max(att, 1)
 
     def bins(self, enthalpy, vmin):
         """Bin of ``enthalpy`` in the window that starts at ``vmin``: the exact floor division of the sampling step,
@@ -604,10 +626,7 @@ class WLWindows:
         estimator_of = np.asarray(estimator_of, dtype=np.int64)
         record = record and pairs is None
         pairs = self.pairs(move) if pairs is None else np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
-        walker_at = np.empty(self.R, dtype=np.int64)
-        walker_at[estimator_of] = np.arange(self.R)
-        s, t = pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64)
-        a, b = walker_at[s], walker_at[t]
+        s, t, a, b = self._holders(estimator_of, pairs)
         Ea, Eb = enthalpy[a], enthalpy[b]
         in_window = (Ea >= self.vmin[t]) & (Ea < self.vmax[t]) & (Eb >= self.vmin[s]) & (Eb < self.vmax[s])
         iaa, iab = self.bins(Ea, self.vmin[s]), self.bins(Eb, self.vmin[s])
@@ -617,12 +636,10 @@ class WLWindows:
             log_u = self.log_u(attempt, len(pairs))
         log_u = np.asarray(log_u, dtype=np.float64)
         accept = in_window & ((ex >= 0) | (log_u < ex))
-        new = estimator_of.copy()
-        new[a[accept]] = t[accept]
-        new[b[accept]] = s[accept]
         if record:
             self.record(move, accept)
-        return dict(pairs=pairs, in_window=in_window, exponent=ex, accept=accept, estimator_of=new)
+        return dict(pairs=pairs, in_window=in_window, exponent=ex, accept=accept,
+                    estimator_of=self._swapped(estimator_of, s, t, a, b, accept))
 
     def levels(self):
         """Lower edges of the L global bins."""
@@ -725,9 +742,9 @@ def run_wl_exchange(engine, wx, n_exchanges, steps_between, host_decide=False, h
         wx.estimator_of = np.asarray(wx.estimator_of).copy()  # configuration -> estimator (= the walker it sits on)
     for _ in range(int(n_exchanges)):
         engine.run(steps_between)
-        move = wx.move_of(wx.calls)
-        pairs = wx.pairs(move)
         if host_decide:
+            move = wx.move_of(wx.calls)
+            pairs = wx.pairs(move)
             st = engine.get_state()
             res = wx.decide(st["enthalpy"], engine.get_wl()["entropy"], identity, move, wx.calls)
             if res["accept"].any():
@@ -738,13 +755,11 @@ def run_wl_exchange(engine, wx, n_exchanges, steps_between, host_decide=False, h
                 conf_at = np.empty(wx.R, dtype=np.int64)
                 conf_at[wx.estimator_of] = identity
                 wx.estimator_of[conf_at[s]], wx.estimator_of[conf_at[t]] = t, s
+            wx.calls += 1
         else:
-            stats = np.zeros((len(pairs), 2), dtype=np.int64)
-            engine.exchange_wl(pairs, wx.log_u(wx.calls, len(pairs)), stats)
-            wx.record(move, stats[:, 1])
+            wx.attempt(engine)
             if history is not None:
                 wx.estimator_of = engine.wl_windows()[2].astype(np.int64)
-        wx.calls += 1
         if history is not None:
             history.append(np.array(wx.estimator_of))
     if not host_decide:
