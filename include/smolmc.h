@@ -378,6 +378,7 @@ int smolmc_sync(smolmc_handle *h);
 #define SMOLMC_SAMPLE_OCCUPANCY 1 /* flags bit 0 */
 #define SMOLMC_SAMPLE_BIAS 2      /* flags bit 1: trace.bias (error without an MCBias term) */
 #define SMOLMC_SAMPLE_WL 4        /* flags bit 2: the Wang-Landau trace (error on a Metropolis handle) */
+#define SMOLMC_SAMPLE_OBSERVABLES 8 /* flags bit 3: kind and pair counts of every row (see smolmc_set_observables) */
 int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t thin_by, int flags);
 /* The ring as the next smolmc_get_samples* call sees it (ABI 8): *n_pending = blocks queued and not fetched
  * (0..2), *nsamples / *flags = sample count and SMOLMC_SAMPLE_* flags of the block that call would deliver
@@ -404,6 +405,44 @@ int smolmc_get_samples_u8(smolmc_handle *h, double *enthalpy, double *features,
 int smolmc_get_samples_ex(smolmc_handle *h, double *enthalpy, double *features, uint8_t *accepted,
                           uint8_t *occupancy_u8, double *bias, double *wl_entropy, int64_t *wl_histogram,
                           int64_t *wl_occurrences, double *wl_mean_features, double *wl_mod_factor);
+/* ---- observables: species and pair counts of sampled states, reduced on the device ---------------------------
+ * (no reference counterpart: the reference's container scans the stored occupancies on the host,
+ * sampler/container.py:226-262).  Two int32 vectors per occupancy row:
+ *   counts[K]                 how many counted sites hold each KIND; the kind of (site, code) is kind_base[site] + code,
+ *                             kind_base[site] = -1 leaves the site out
+ *   pairs[n_shells][K][K]     for every bond (i, j) of a shell, as listed, cell (kind(i), kind(j)) gains 1; a bond with
+ *                             an end that is not counted is skipped; duplicate rows and i == j rows count as they stand
+ * Site numbers are the caller's.  The engine copies and uploads everything.  smolmc_eval_observables refuses a code that
+ * gives a kind >= K; in the walkers' own states that can only happen on a fixed site outside every cluster (the tables
+ * do not say how many codes such a site has), and such a site is then left out. */
+#define SMOLMC_MAX_OBS_CELLS 4096 /* most pair cells n_shells x K x K (16 KB of int32: with the row and the kind counts
+                                   * they share 64 KB of LDS of one workgroup) */
+typedef struct {
+    int n_kinds;              /* K, 1..254 */
+    const int32_t *kind_base; /* [N] */
+    int n_shells;
+    const int64_t *shell_ptr; /* [n_shells + 1], ascending from 0 */
+    const int32_t *bonds;     /* [shell_ptr[n_shells] x 2] */
+} smolmc_observables;
+/* Sets (NULL: removes) the observables of the handle.  Refused, each naming its reason: a bond out of range; a site with
+ * kind_base[s] + (species codes on s) > n_kinds; more than SMOLMC_MAX_OBS_CELLS cells; a row too long to stage in LDS
+ * next to the histograms; and while a block recorded with SMOLMC_SAMPLE_OBSERVABLES waits in the ring.  A refused call
+ * leaves the handle's observables as they were. */
+int smolmc_set_observables(smolmc_handle *h, const smolmc_observables *obs);
+/* K and n_shells in force (0, 0: none set) */
+int smolmc_observables_shape(smolmc_handle *h, int *n_kinds, int *n_shells);
+/* counts [nocc x K] and pairs [nocc x n_shells x K x K] of nocc occupancies (host, int32 like smolmc_eval_full), or, with
+ * occ == NULL, of the walkers' current states (nocc = R then).  Either output may be NULL. */
+int smolmc_eval_observables(smolmc_handle *h, const int32_t *occ /* nocc x N, or NULL */, int nocc, int32_t *counts,
+                            int32_t *pairs);
+/* With SMOLMC_SAMPLE_OBSERVABLES smolmc_run_sampled adds the two columns [rows x K] and [rows x n_shells x K x K] to the
+ * block, filled on the device from the block's occupancy rows when its launches are through; without
+ * SMOLMC_SAMPLE_OCCUPANCY those rows never leave the device.  The flag is refused while no observables are set.  This
+ * call reads the columns of the block the next smolmc_get_samples* call delivers ([nsamples x R x ...], either may be
+ * NULL) and does not mark it delivered, like smolmc_pending_samples; an error when that block was recorded without
+ * the flag. */
+int smolmc_get_sample_observables(smolmc_handle *h, int32_t *counts, int32_t *pairs);
+
 /* Same loop driven by host-provided proposals ("replay mode"): what
  * StandardSingleStepMixin.single_step (kernel/base.py:145-166) does after mcusher.propose_step
  * returned, with the numbers the reference's Generator produced.

@@ -26,6 +26,8 @@ BIAS_NONE, BIAS_FUGACITY, BIAS_SQUARE_CHARGE, BIAS_SQUARE_HYPERPLANE = 0, 1, 2, 
 ABI_VERSION = 8
 ERR_RING_FULL = 2  # SMOLMC_ERR_RING_FULL
 SAMPLE_OCCUPANCY, SAMPLE_BIAS, SAMPLE_WL = 1, 2, 4  # SMOLMC_SAMPLE_* flags of smolmc_run_sampled
+SAMPLE_OBSERVABLES = 8          # ... kind and pair counts of every row (smolmc_set_observables)
+MAX_OBS_CELLS = 4096            # SMOLMC_MAX_OBS_CELLS
 MAX_STEP_FLIPS = 8              # SMOLMC_MAX_STEP_FLIPS
 STEP_ROW = 2 * MAX_STEP_FLIPS   # SMOLMC_STEP_ROW: int32 per step record (site, code) x 8, -1 = no flip
 
@@ -127,6 +129,18 @@ class smolmc_distance(C.Structure):
 
 
 DIST_MAX_FEATURES = 256  # SMOLMC_DIST_MAX_FEATURES
+
+
+class smolmc_observables(C.Structure):
+    """Mirror of ``smolmc_observables`` (include/smolmc.h); ``observables.Observables.c_struct`` fills it."""
+
+    _fields_ = [
+        ("n_kinds", C.c_int),
+        ("kind_base", _i32p),
+        ("n_shells", C.c_int),
+        ("shell_ptr", _i64p),
+        ("bonds", _i32p),
+    ]
 
 
 class DistanceSpec:

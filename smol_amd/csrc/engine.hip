@@ -1440,6 +1440,8 @@ static int create_site_codes(smolmc_handle *h, const smolmc_tables *t) {
     }
     for (int s = 0; s < t->num_sites; ++s)
         if (!h->site_active[s] && seen[s]) h->site_ncodes[s] = (uint8_t)std::min<int>(h->site_ncodes[s], std::min(255, seen[s]));
+    h->site_width_known.assign((size_t)t->num_sites, 0);
+    for (int s = 0; s < t->num_sites; ++s) h->site_width_known[s] = h->site_active[s] || seen[s];
     return 0;
 }
 
@@ -2347,6 +2349,13 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
     return 0;
 }
 
+static void free_observables(SmolmcObs &O) {
+    if (O.d_kind_base) hipFree(O.d_kind_base);
+    if (O.d_shell_ptr) hipFree(O.d_shell_ptr);
+    if (O.d_bonds) hipFree(O.d_bonds);
+    O = SmolmcObs();
+}
+
 extern "C" int smolmc_destroy(smolmc_handle *h) {
     if (!h) return 0;
     hipSetDevice(h->device);
@@ -2354,6 +2363,9 @@ extern "C" int smolmc_destroy(smolmc_handle *h) {
     smolmc_dist_free(h);
     for (void *p : h->allocs) hipFree(p);
     if (h->d_eval_occ) hipFree(h->d_eval_occ);
+    free_observables(h->obs);
+    if (h->obs_ev0) hipEventDestroy(h->obs_ev0);
+    if (h->obs_ev1) hipEventDestroy(h->obs_ev1);
     free_samples(h);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -3308,6 +3320,8 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
     if ((flags & SMOLMC_SAMPLE_BIAS) && !h->kp.bias_type) return fail("the model has no bias term");
     if ((flags & SMOLMC_SAMPLE_WL) && !wl) return fail("handle is not a Wang-Landau kernel");
+    if ((flags & SMOLMC_SAMPLE_OBSERVABLES) && !h->obs.K)
+        return fail("SMOLMC_SAMPLE_OBSERVABLES without observables: call smolmc_set_observables first");
     if ((flags & SMOLMC_SAMPLE_WL) && !h->wl_win_min.empty())
         return fail("SMOLMC_SAMPLE_WL while per-walker windows are set: the snapshot rows are walker-indexed, the Wang-Landau arrays estimator-indexed (smolmc_get_wl between runs, or smolmc_set_wl_windows(h, NULL, NULL) first)");
     if (thin_by > ((int64_t)1 << 30) && h->lean() && !smolmc_env(ENV_LAUNCH_CHUNK))
@@ -3345,6 +3359,10 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
         w.o_wlf = take(rows * L * F * 8);
     }
     w.o_occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) ? take(rows * h->Npad) : 0;
+    // observables: two columns of the downloaded part, filled from the block's occupancy rows after its launches
+    const bool obs = (flags & SMOLMC_SAMPLE_OBSERVABLES) != 0;
+    w.o_cnt = obs ? take(rows * (size_t)h->obs.K * 4) : 0;
+    w.o_pair = obs ? take(rows * h->obs.cells * 4) : 0;
     // lazy cluster features, rows recorded in-kernel: the kernels write rows of scalar features and the occupancy of
     // every sample; the cluster features of the rows are evaluated from those when the launch is through.  What the
     // caller did not ask for sits behind the part of the arena that is downloaded.
@@ -3356,13 +3374,13 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
                                h->lp.bias_type && !smolmc_env(ENV_NO_INKERNEL_BIAS);
     const bool snapshot_path = (flags & SMOLMC_SAMPLE_WL) || ((flags & SMOLMC_SAMPLE_BIAS) && !inkernel_bias);
     const bool lazy_rows = is_lazy(h) && !snapshot_path;
-    size_t download = at, o_scal = 0, o_occ_int = w.o_occ;
-    if (lazy_rows) {
-        download = at;
-        o_scal = take(rows * (size_t)std::max(1, lazy_nscal(h)) * 8);
-        if (!(flags & SMOLMC_SAMPLE_OCCUPANCY)) o_occ_int = take(rows * h->Npad);
-    }
+    const size_t download = at;
+    size_t o_scal = 0, o_occ_int = w.o_occ;
+    if (lazy_rows) o_scal = take(rows * (size_t)std::max(1, lazy_nscal(h)) * 8);
+    // (... and so do the occupancy rows the observables are counted from)
+    if ((lazy_rows || obs) && !(flags & SMOLMC_SAMPLE_OCCUPANCY)) o_occ_int = take(rows * h->Npad);
     if (lazy_rows && rows > 0x7fffffffull) return fail("lazy cluster features: more than 2^31 sample rows in one block");
+    if (obs && rows > 0x7fffffffull) return fail("observables: more than 2^31 sample rows in one block");
     // the slot's previous block (delivered, or none) must have left the device before its arenas are reused
     if (sl.state != 0) HIPCHK(hipEventSynchronize(sl.copy_done));
     if (at > sl.cap) {
@@ -3381,7 +3399,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
         sl.cap = at;
         w.d = sl.d; w.hst = sl.hst; w.cap = sl.cap;
     }
-    w.used = lazy_rows ? download : at;
+    w.used = download;
     w.n = nsamples;
     w.flags = flags;
     SampleBufs smp;
@@ -3390,7 +3408,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     smp.H = (double *)(sl.d + w.o_H);
     smp.feat = (double *)(sl.d + (lazy_rows ? o_scal : w.o_feat));
     smp.acc = sl.d + w.o_acc;
-    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows ? sl.d + o_occ_int : nullptr;
+    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs ? sl.d + o_occ_int : nullptr;
     if (!snapshot_path) {
         if (inkernel_bias) {
             if ((w.o_bias - w.o_H) / 8 > 0xffffffffull) return fail("sample block too large for the in-kernel bias column");
@@ -3427,6 +3445,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
             HIPCHK(hipGetLastError());
         }
     }
+    if (obs) TRY(smolmc_obs_launch(h, sl.d + o_occ_int, rows, (int32_t *)(sl.d + w.o_cnt), (int32_t *)(sl.d + w.o_pair)));
     // download on the copy stream as soon as the block is complete; the next block's launches do not wait for it
     // (the mirror is about to be overwritten: from here the slot no longer holds its old block)
     sl.state = 0;
@@ -3453,6 +3472,12 @@ static SampleSlot *next_delivery(smolmc_handle *h) {
         for (SampleSlot &c : h->slots)
             if (c.state == 2 && (!sl || c.seq > sl->seq)) sl = &c;
     return sl;
+}
+// bytes of the block the next smolmc_get_samples* call delivers that its download moves (-1: none); a test hook like
+// smolmc_debug_relabel, not part of the C-ABI
+extern "C" long long smolmc_debug_block_bytes(smolmc_handle *h) {
+    const SampleSlot *sl = h ? next_delivery(h) : nullptr;
+    return sl ? (long long)sl->used : -1;
 }
 extern "C" int smolmc_pending_samples(smolmc_handle *h, int *n_pending, int64_t *nsamples, int *flags) {
     if (!h) return fail("null handle");
@@ -3739,6 +3764,147 @@ extern "C" int smolmc_eval_full(smolmc_handle *h, const int32_t *occ, int nocc, 
     if (rc) return rc;
     if (e != hipSuccess) return fail(std::string("eval_full: ") + hipGetErrorString(e));
     if (h->dist) return smolmc_dist_from_extensive(h, features, (size_t)nocc);
+    return 0;
+}
+
+// ---- observables: kind and pair counts of occupancy rows (the kernel: observables.hip) -------------------------------
+extern "C" int smolmc_set_observables(smolmc_handle *h, const smolmc_observables *obs) {
+    if (!h) return fail("null handle");
+    HIPCHK(hipSetDevice(h->device));
+    for (const SampleSlot &c : h->slots)
+        if (c.state == 1 && (c.flags & SMOLMC_SAMPLE_OBSERVABLES))
+            return fail("smolmc_set_observables while a block recorded with SMOLMC_SAMPLE_OBSERVABLES waits in the ring (call "
+                        "smolmc_get_samples* or smolmc_discard_samples first)");
+    SmolmcObs O;
+    if (obs) {
+        const int N = h->N, K = obs->n_kinds, S = obs->n_shells;
+        if (!obs->kind_base || S < 0 || (S > 0 && (!obs->shell_ptr || !obs->bonds))) return fail("observables: null argument");
+        if (K < 1 || K > 254) return fail("observables: n_kinds must be 1..254 (a kind is staged as one byte)");
+        const size_t cells = (size_t)S * K * K;
+        if (cells > SMOLMC_MAX_OBS_CELLS) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "observables: %d shells x %d x %d kinds = %zu cells, larger than SMOLMC_MAX_OBS_CELLS = %d", S, K, K,
+                     cells, SMOLMC_MAX_OBS_CELLS);
+            return fail(msg);
+        }
+        // kind_base in the engine's numbering; every code a site can hold must have a kind below K
+        std::vector<int32_t> kb((size_t)N);
+        for (int p = 0; p < N; ++p) {
+            const int s = h->relabelled ? h->new_of[p] : p;
+            const int32_t b = obs->kind_base[p];
+            // (a fixed site outside every cluster: the tables do not say how many codes it has, site_ncodes is the
+            // model's widest site there -- its block must hold one kind at least; the kernel leaves out a kind >= K)
+            const int width = h->site_width_known[s] ? (int)h->site_ncodes[s] : 1;
+            if (b >= 0 && b + width > K) {
+                char msg[200];
+                snprintf(msg, sizeof msg, "observables: kind_base[%d] + site_ncodes = %d + %d is larger than n_kinds = %d: kind out of range", p,
+                         (int)b, width, K);
+                return fail(msg);
+            }
+            kb[s] = b < 0 ? -1 : b;
+        }
+        const int64_t nb = S ? obs->shell_ptr[S] : 0;
+        for (int sidx = 0; sidx < S; ++sidx)
+            if (obs->shell_ptr[0] != 0 || obs->shell_ptr[sidx] > obs->shell_ptr[sidx + 1])
+                return fail("observables: shell_ptr must be ascending from 0");
+        O.K = K; O.n_shells = S; O.cells = cells;
+        O.kind_base = kb;
+        O.pair_copies = smolmc_obs_pair_copies(cells);
+        O.lds = smolmc_obs_lds_bytes(h->Npad, K, cells, O.pair_copies);
+        if (O.lds > 64 * 1024) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "observables: a row of %d sites is too long to stage in LDS next to the histograms (%zu bytes, 65536 at most)",
+                     N, O.lds);
+            return fail(msg);
+        }
+        // (a row that fits LDS has fewer than 2^16 sites: a bond is one word)
+        std::vector<uint32_t> bw((size_t)nb);
+        for (int64_t b = 0; b < nb; ++b) {
+            const int32_t i = obs->bonds[2 * b], j = obs->bonds[2 * b + 1];
+            if (i < 0 || i >= N || j < 0 || j >= N) {
+                char msg[160];
+                snprintf(msg, sizeof msg, "observables: bond %lld = (%d, %d) out of range (%d sites)", (long long)b, (int)i, (int)j, N);
+                return fail(msg);
+            }
+            const uint32_t ei = (uint32_t)(h->relabelled ? h->new_of[i] : i), ej = (uint32_t)(h->relabelled ? h->new_of[j] : j);
+            bw[(size_t)b] = ei | (ej << 16);
+        }
+        hipError_t e = hipMalloc((void **)&O.d_kind_base, std::max<size_t>((size_t)N * 4, 16));
+        if (e == hipSuccess) e = hipMalloc((void **)&O.d_shell_ptr, ((size_t)S + 1) * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&O.d_bonds, std::max<size_t>((size_t)nb * 4, 16));
+        if (e == hipSuccess) e = hipMemcpy(O.d_kind_base, kb.data(), (size_t)N * 4, hipMemcpyHostToDevice);
+        const int64_t zero = 0;
+        if (e == hipSuccess) e = hipMemcpy(O.d_shell_ptr, S ? obs->shell_ptr : &zero, ((size_t)S + 1) * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && nb) e = hipMemcpy(O.d_bonds, bw.data(), (size_t)nb * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            free_observables(O);
+            return fail(std::string("observables upload: ") + hipGetErrorString(e));
+        }
+    }
+    // the kernels of queued blocks read the old tables: let them finish; delivered blocks of the old shape are forgotten
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (SampleSlot &c : h->slots)
+        if (c.state == 2 && (c.flags & SMOLMC_SAMPLE_OBSERVABLES)) c.state = 0;
+    free_observables(h->obs);
+    h->obs = O;
+    return 0;
+}
+
+extern "C" int smolmc_observables_shape(smolmc_handle *h, int *n_kinds, int *n_shells) {
+    if (!h) return fail("null handle");
+    if (n_kinds) *n_kinds = h->obs.K;
+    if (n_shells) *n_shells = h->obs.n_shells;
+    return 0;
+}
+
+extern "C" int smolmc_eval_observables(smolmc_handle *h, const int32_t *occ, int nocc, int32_t *counts, int32_t *pairs) {
+    if (!h) return fail("null handle");
+    if (!h->obs.K) return fail("no observables set: call smolmc_set_observables first");
+    HIPCHK(hipSetDevice(h->device));
+    const uint8_t *d_occ8 = h->kp.occ;
+    if (occ) {
+        if (nocc <= 0) return 0;
+        TRY(ensure_eval_occ(h, nocc));
+        std::vector<int32_t> occ_engine;
+        occ = occ_in(h, occ, (size_t)nocc, occ_engine);
+        for (size_t r = 0; r < (size_t)nocc; ++r)
+            for (int s = 0; s < h->N; ++s) {
+                const int32_t b = h->obs.kind_base[s], c = occ[r * h->N + s];
+                if (b >= 0 && c >= 0 && b + c >= h->obs.K) {
+                    char msg[200];
+                    snprintf(msg, sizeof msg, "observables: occupancy code %d on site %d gives kind %d, n_kinds = %d: kind out of range", (int)c,
+                             h->relabelled ? (int)h->old_of[s] : s, (int)(b + c), h->obs.K);
+                    return fail(msg);
+                }
+            }
+        TRY(upload_occ(h, occ, nocc, h->d_eval_occ));
+        d_occ8 = h->d_eval_occ;
+    } else {
+        nocc = h->R;
+    }
+    const size_t nc = (size_t)nocc * h->obs.K, np = (size_t)nocc * h->obs.cells;
+    int32_t *d_out = nullptr;
+    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>((nc + np) * 4, 16)));
+    int rc = smolmc_obs_launch(h, d_occ8, (size_t)nocc, d_out, d_out + nc);
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (!rc && e == hipSuccess && counts) e = hipMemcpy(counts, d_out, nc * 4, hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess && pairs && np) e = hipMemcpy(pairs, d_out + nc, np * 4, hipMemcpyDeviceToHost);
+    hipFree(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(std::string("eval_observables: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int smolmc_get_sample_observables(smolmc_handle *h, int32_t *counts, int32_t *pairs) {
+    if (!h) return fail("null handle");
+    SampleSlot *sl = next_delivery(h);
+    if (!sl) return fail("no samples recorded: call smolmc_run_sampled first");
+    if (!(sl->flags & SMOLMC_SAMPLE_OBSERVABLES)) return fail("the observables were not recorded (flags bit 3)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(sl->copy_done));
+    const size_t rows = (size_t)sl->n * h->R;
+    if (counts) host_copy(counts, sl->hst + sl->o_cnt, rows * (size_t)h->obs.K * 4);
+    if (pairs) host_copy(pairs, sl->hst + sl->o_pair, rows * h->obs.cells * 4);
     return 0;
 }
 

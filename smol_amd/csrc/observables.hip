@@ -1,0 +1,158 @@
+// Observables of recorded states (smolmc_set_observables, smolmc_eval_observables, SMOLMC_SAMPLE_OBSERVABLES; engine.hip):
+// kind counts and pair counts of occupancy rows, reduced on the device where the rows lie.  A translation unit of its own,
+// like pop_anneal.hip: a kernel added to engine.hip would move the descriptors of all of its kernels.
+//
+// The kind of (site, code) is kind_base[site] + code, kind_base[site] < 0 leaves the site out (DESIGN 4.15;
+// observables.Observables.evaluate is the same in NumPy).  Per row:
+//   counts[k]          = #{sites of kind k}
+//   pairs[s][ka][kb]  += 1 for every bond (i, j) of shell s, as listed, with ka = kind(i), kb = kind(j), both counted
+// Everything is int32: the order of summation is no concern, device and host agree entry for entry.
+//
+// One workgroup per row.  The row's Npad bytes go to LDS with 16-byte loads; one pass turns every byte into the site's
+// kind (0xff: not counted) in place and counts the kinds; then the threads stride over the bond table -- one 32-bit word
+// per bond, two 16-bit sites: the rows this kernel takes fit LDS, so their sites fit 16 bits -- and look both ends up in
+// LDS.  LDS atomics serialise per address and a binary alloy has four cells per shell, so the adds never go to one
+// shared histogram: with few cells (kinds, or cells of a shell, <= OBS_BALLOT_CELLS) a wave counts each cell by ballot
+// and lane c carries the sum of cell c in a register; with more, every wave adds into a histogram of its own (as long
+// as OBS_WAVES copies fit the cell limit).  The wave histograms are folded at the end, one plain store per entry.
+#include "smolmc_common.h"
+
+#define OBS_THREADS 256
+#define OBS_WAVES (OBS_THREADS / 64)
+#define OBS_BALLOT_CELLS 16
+#define OBS_NOKIND 0xffu
+
+struct ObsArgs {
+    const uint8_t *occ;        // rows of Npad bytes
+    const int32_t *kind_base;  // [N], engine numbering
+    const int64_t *shell_ptr;  // [n_shells + 1]
+    const uint32_t *bonds;     // [shell_ptr[n_shells]]: i | j << 16
+    int32_t *counts, *pairs;   // [rows x K], [rows x n_shells x K x K]
+    int N, Npad, K, n_shells;
+    int pair_copies;           // histograms of the pair cells in LDS: OBS_WAVES (one per wave) or 1
+};
+
+// LDS: kinds u8 [Npad] | counts i32 [OBS_WAVES][K] | pairs i32 [pair_copies][n_shells K K]
+size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies) {
+    return (size_t)Npad + ((size_t)OBS_WAVES * K + (size_t)pair_copies * cells) * 4;
+}
+int smolmc_obs_pair_copies(size_t cells) { return cells * OBS_WAVES <= SMOLMC_MAX_OBS_CELLS ? OBS_WAVES : 1; }
+
+__global__ void __launch_bounds__(OBS_THREADS) observables_kernel(const ObsArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char obs_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int N = A.N, Npad = A.Npad, K = A.K, KK = K * K;
+    const int cells = A.n_shells * KK;
+    uint8_t *kinds = obs_smem;
+    int32_t *cnt = (int32_t *)(obs_smem + Npad); // (Npad is a multiple of 16)
+    int32_t *hist = cnt + OBS_WAVES * K;
+    const size_t row = blockIdx.x;
+
+    {   // the row, 16 bytes a lane; the histograms start at zero
+        const uint4 *src = (const uint4 *)(A.occ + row * Npad);
+        uint4 *dst = (uint4 *)kinds;
+        for (int i = tid; i < Npad / 16; i += OBS_THREADS) dst[i] = src[i];
+        for (int i = tid; i < OBS_WAVES * K + A.pair_copies * cells; i += OBS_THREADS) cnt[i] = 0;
+    }
+    __syncthreads();
+
+    // codes -> kinds in place (every byte is read and written by one thread), and the kind counts
+    {
+        int acc = 0; // ballot form: lane c holds the count of kind c
+        for (int s0 = wave * 64; s0 < Npad; s0 += OBS_THREADS) { // (wave-uniform bounds: every lane takes part in the ballots)
+            const int s = s0 + lane;
+            unsigned k = OBS_NOKIND;
+            if (s < N) {
+                const int kb = A.kind_base[s];
+                if (kb >= 0) k = (unsigned)kb + kinds[s];
+                if (k >= (unsigned)K) k = OBS_NOKIND; // (a code the site's block has no kind for: only on a fixed site whose width the tables do not give)
+            }
+            if (s < Npad) kinds[s] = (uint8_t)k;
+            if (K <= OBS_BALLOT_CELLS) {
+                for (int c = 0; c < K; ++c) {
+                    const int n = __popcll(__ballot(k == (unsigned)c));
+                    if (lane == c) acc += n;
+                }
+            } else if (k != OBS_NOKIND) {
+                atomicAdd(&cnt[wave * K + (int)k], 1);
+            }
+        }
+        if (K <= OBS_BALLOT_CELLS && lane < K) cnt[wave * K + lane] = acc;
+    }
+    __syncthreads();
+
+    // the bonds, shell by shell
+    int32_t *mine = hist + (A.pair_copies > 1 ? wave * cells : 0);
+    for (int sh = 0; sh < A.n_shells; ++sh) {
+        const int64_t b0 = A.shell_ptr[sh], b1 = A.shell_ptr[sh + 1];
+        int acc = 0;
+        for (int64_t base = b0 + wave * 64; base < b1; base += OBS_THREADS) {
+            const int64_t b = base + lane;
+            int cell = -1;
+            if (b < b1) {
+                const uint32_t w = A.bonds[b];
+                const unsigned ka = kinds[w & 0xffffu], kb = kinds[w >> 16];
+                if (ka != OBS_NOKIND && kb != OBS_NOKIND) cell = (int)(ka * (unsigned)K + kb);
+            }
+            if (KK <= OBS_BALLOT_CELLS) {
+                for (int c = 0; c < KK; ++c) {
+                    const int n = __popcll(__ballot(cell == c));
+                    if (lane == c) acc += n;
+                }
+            } else if (cell >= 0) {
+                atomicAdd(&mine[sh * KK + cell], 1);
+            }
+        }
+        // (ballot form: pair_copies == OBS_WAVES whenever a shell has so few cells and the call was accepted with one
+        // copy only when cells * OBS_WAVES exceeds the limit -- then every wave adds its sums to the shared copy)
+        if (KK <= OBS_BALLOT_CELLS && lane < KK) {
+            if (A.pair_copies > 1) mine[sh * KK + lane] = acc;
+            else atomicAdd(&mine[sh * KK + lane], acc);
+        }
+    }
+    __syncthreads();
+
+    // fold the waves' copies: plain stores, one per entry
+    for (int k = tid; k < K; k += OBS_THREADS) {
+        int v = 0;
+#pragma unroll
+        for (int w = 0; w < OBS_WAVES; ++w) v += cnt[w * K + k];
+        A.counts[row * K + k] = v;
+    }
+    for (int c = tid; c < cells; c += OBS_THREADS) {
+        int v = 0;
+        for (int w = 0; w < A.pair_copies; ++w) v += hist[w * cells + c];
+        A.pairs[row * (size_t)cells + c] = v;
+    }
+}
+
+int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs) {
+    const SmolmcObs &O = h->obs;
+    if (!O.K) return fail("no observables set (smolmc_set_observables)");
+    if (!rows) return 0;
+    if (rows > 0x7fffffffull) return fail("observables: more than 2^31 rows in one launch");
+    ObsArgs A;
+    A.occ = d_occ8; A.kind_base = O.d_kind_base; A.shell_ptr = O.d_shell_ptr; A.bonds = O.d_bonds;
+    A.counts = d_counts; A.pairs = d_pairs;
+    A.N = h->N; A.Npad = h->Npad; A.K = O.K; A.n_shells = O.n_shells; A.pair_copies = O.pair_copies;
+    if (!h->obs_ev0) {
+        HIPCHK(hipEventCreate(&h->obs_ev0));
+        HIPCHK(hipEventCreate(&h->obs_ev1));
+    }
+    HIPCHK(hipEventRecord(h->obs_ev0, h->stream));
+    hipLaunchKernelGGL(observables_kernel, dim3((unsigned)rows), dim3(OBS_THREADS), O.lds, h->stream, A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->obs_ev1, h->stream));
+    return 0;
+}
+
+// elapsed device time of the last launch of the observables kernel in ms (tools/observables_timing.py); a measuring hook
+// like smolmc_debug_relabel, not part of the C-ABI
+extern "C" int smolmc_debug_obs_kernel_ms(smolmc_handle *h, float *ms) {
+    if (!h || !ms) return fail("null argument");
+    if (!h->obs_ev0) return fail("the observables kernel has not been launched yet");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(h->obs_ev1));
+    HIPCHK(hipEventElapsedTime(ms, h->obs_ev0, h->obs_ev1));
+    return 0;
+}

@@ -742,6 +742,7 @@ struct SampleSlot {
     size_t cap = 0;                             // bytes allocated (grow-only)
     size_t used = 0;                            // bytes of the recorded block
     size_t o_H = 0, o_feat = 0, o_acc = 0, o_occ = 0, o_bias = 0, o_wlm = 0, o_wlS = 0, o_wlh = 0, o_wlo = 0, o_wlf = 0;
+    size_t o_cnt = 0, o_pair = 0;               // SMOLMC_SAMPLE_OBSERVABLES: kind counts [rows x K], pair counts [rows x cells]
     long long n = 0;                            // samples in the block
     int flags = 0;                              // SMOLMC_SAMPLE_* the block was recorded with
     int state = 0;                              // 0 empty, 1 recorded and not yet delivered, 2 delivered
@@ -761,6 +762,18 @@ struct SmolmcPopScratch {
     uint64_t *q, *qsum, *word, *C;
     double *href, *beta_new;
     uint32_t *cnt, *sur, *drank;
+};
+
+// observables.hip: the observables of a handle (smolmc_set_observables) as the kernel reads them, engine numbering
+struct SmolmcObs {
+    int K = 0, n_shells = 0;   // (K == 0: none set)
+    size_t cells = 0;          // n_shells x K x K
+    int pair_copies = 1;       // histograms of the pair cells in LDS (one per wave, or one)
+    size_t lds = 0;            // dynamic LDS of a launch
+    std::vector<int32_t> kind_base; // host copy, engine numbering (validation of occupancies given by the caller)
+    int32_t *d_kind_base = nullptr;
+    int64_t *d_shell_ptr = nullptr;
+    uint32_t *d_bonds = nullptr; // one word per bond: i | j << 16
 };
 
 struct smolmc_handle {
@@ -840,6 +853,9 @@ struct smolmc_handle {
     // population annealing (smolmc_anneal_resample / smolmc_resample, engine.hip): one device arena, allocated at the
     // first call, cut into the arrays of SmolmcPopScratch
     SmolmcPopScratch pop;
+    // kind and pair counts of occupancy rows (smolmc_set_observables, engine.hip; the kernel in observables.hip)
+    SmolmcObs obs;
+    hipEvent_t obs_ev0 = nullptr, obs_ev1 = nullptr; // around the last launch of the observables kernel (created at the first)
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
     SampleSlot slots[2];
@@ -858,6 +874,7 @@ struct smolmc_handle {
     int ew_gx_dims[3] = {0, 0, 0}, ew_gx_blocks = 0; // translation-compressed site kernel (0: none)
     std::vector<uint8_t> site_ncodes; // species codes allowed on each site (occupancy validation)
     std::vector<uint8_t> site_active; // 1 on the sites of the active sublattices (replay validation)
+    std::vector<uint8_t> site_width_known; // site_ncodes[s] is the site's own width (an active site, or a member of a cluster), not just the model's
     // universal kernel (mc_univ.h): always available (family K_UNIVERSAL: every launch of this handle takes it)
     UParams up;
     bool general_ok = true;      // mc_kernel can run this model (else: why not)
@@ -950,6 +967,12 @@ int smolmc_pop_parent_launch(smolmc_handle *h, int npop, const SmolmcPopScratch 
 // ... slot m takes every per-walker row of slot parent[m] (device array; parent[parent[m]] == parent[m]), and, with
 // beta_new (device, [npop]), walker m the inverse temperature beta_new[m / (R / npop)]; queued on the handle's stream
 int smolmc_pop_clone_launch(smolmc_handle *h, const int32_t *parent, int npop, const double *beta_new);
+// observables.hip: kind counts [rows x K] and pair counts [rows x n_shells x K x K] of `rows` occupancy rows (Npad bytes
+// apart, device) into device arrays, queued on the handle's stream; the LDS a launch takes and the number of pair
+// histograms it keeps there
+int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs);
+size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies);
+int smolmc_obs_pair_copies(size_t cells);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);
 int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_4(smolmc_handle *h, const KParams &kp, int replay);

@@ -56,6 +56,10 @@ SYMBOLS = {
     "smolmc_get_samples": (C.c_int, [_HP, _f64p, _f64p, _u8p, _i32p]),
     "smolmc_get_samples_u8": (C.c_int, [_HP, _f64p, _f64p, _u8p, _u8p]),
     "smolmc_get_samples_ex": (C.c_int, [_HP, _f64p, _f64p, _u8p, _u8p, _f64p, _f64p, _i64p, _i64p, _f64p, _f64p]),
+    "smolmc_set_observables": (C.c_int, [_HP, C.POINTER(capi.smolmc_observables)]),
+    "smolmc_observables_shape": (C.c_int, [_HP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "smolmc_eval_observables": (C.c_int, [_HP, _i32p, C.c_int, _i32p, _i32p]),
+    "smolmc_get_sample_observables": (C.c_int, [_HP, _i32p, _i32p]),
     "smolmc_replay": (C.c_int, [_HP, C.c_int64, _i32p, _f64p, _f64p, _u8p, _f64p, _f64p]),
     "smolmc_last_kernel_ms": (C.c_int, [_HP, C.POINTER(C.c_float)]),
     "smolmc_eval_full": (C.c_int, [_HP, _i32p, C.c_int, _f64p]),
@@ -484,21 +488,71 @@ class Engine:
     def sync(self):
         self._chk(self._lib.smolmc_sync(self._h))
 
-    def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False):
+    # ---- observables: kind and pair counts on the device ----------------------------------
+    def set_observables(self, obs):
+        """The observables of this handle (smolmc_set_observables): an ``observables.Observables`` in the caller's site
+        numbering, or None to remove them.  The engine copies and uploads; it refuses, naming the reason, a bond out
+        of range, a kind beyond ``n_kinds``, more cells than ``capi.MAX_OBS_CELLS`` and a row too long for LDS."""
+        if obs is None:
+            self._chk(self._lib.smolmc_set_observables(self._h, None))
+        else:
+            if obs.num_sites != self.N:
+                raise ValueError(f"the observables are defined on {obs.num_sites} sites, the handle has {self.N}")
+            struct, keep = obs.c_struct()
+            self._chk(self._lib.smolmc_set_observables(self._h, C.byref(struct)))
+            del keep
+
+    def observables_shape(self):
+        """(n_kinds, n_shells) in force, (0, 0) when none are set (smolmc_observables_shape)."""
+        K, S = C.c_int(), C.c_int()
+        self._chk(self._lib.smolmc_observables_shape(self._h, C.byref(K), C.byref(S)))
+        return int(K.value), int(S.value)
+
+    def observables(self, occupancies=None):
+        """(counts (n, K) int32, pairs (n, n_shells, K, K) int32) of occupancies (n, N) evaluated on the device
+        (smolmc_eval_observables), or, with None, of the walkers' current states (n = R)."""
+        K, S = self.observables_shape()
+        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
+        n = self.R if occ is None else len(occ)
+        counts, pairs = np.zeros((n, K), dtype=np.int32), np.zeros((n, S, K, K), dtype=np.int32)
+        self._chk(self._lib.smolmc_eval_observables(self._h, _p(occ, C.c_int32), n, _p(counts, C.c_int32), _p(pairs, C.c_int32)))
+        return counts, pairs
+
+    def sample_observables(self):
+        """(species_counts (ns, R, K), pair_counts (ns, R, n_shells, K, K)) of the block ``fetch_samples`` would
+        deliver next; the block stays undelivered (smolmc_get_sample_observables)."""
+        K, S = self.observables_shape()
+        _, ns, _ = self.pending_samples()
+        counts, pairs = np.empty((ns, self.R, K), dtype=np.int32), np.empty((ns, self.R, S, K, K), dtype=np.int32)
+        self._chk(self._lib.smolmc_get_sample_observables(self._h, _p(counts, C.c_int32), _p(pairs, C.c_int32)))
+        return counts, pairs
+
+    def observables_kernel_ms(self):
+        """Device time of the last launch of the observables kernel in ms (HIP events; a measuring hook of the library,
+        not part of the C-ABI)."""
+        fn = self._lib.smolmc_debug_obs_kernel_ms
+        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
+        ms = C.c_float()
+        self._chk(fn(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False):
         """Advance nsamples*thin_by steps recording one sample per walker every thin_by steps
         on the device; returns dict(enthalpy (ns,R), features (ns,R,F), accepted (ns,R) bool,
-        occupancy (ns,R,N) or None[, bias (ns,R)][, the Wang-Landau trace]).  Occupancies come back as
-        int32 (the reference's trace dtype) or, with ``packed``, as the ring's own uint8 -- a quarter
-        of the transfer.  = ``run_sampled_async`` + ``fetch_samples``."""
-        self.run_sampled_async(nsamples, thin_by, occupancy=occupancy, bias=bias, wl=wl)
+        occupancy (ns,R,N) or None[, bias (ns,R)][, the Wang-Landau trace][, species_counts, pair_counts]).
+        Occupancies come back as int32 (the reference's trace dtype) or, with ``packed``, as the ring's own
+        uint8 -- a quarter of the transfer.  = ``run_sampled_async`` + ``fetch_samples``."""
+        self.run_sampled_async(nsamples, thin_by, occupancy=occupancy, bias=bias, wl=wl, observables=observables)
         return self.fetch_samples(packed=packed)
 
-    def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False):
+    def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False, observables=False):
         """Queue one block of the device ring (smolmc_run_sampled): returns at once.  The ring has two
         slots; queue block k + 1 BEFORE fetching block k and the download of k overlaps the kernel of
-        k + 1 (the order ``fetch_samples`` delivers in: oldest first)."""
+        k + 1 (the order ``fetch_samples`` delivers in: oldest first).  ``observables``: the kind and pair
+        counts of ``set_observables`` for every row, counted on the device; with ``occupancy=False`` the
+        occupancy rows they are counted from never leave it."""
         flags = ((capi.SAMPLE_OCCUPANCY if occupancy else 0) | (capi.SAMPLE_BIAS if bias else 0) |
-                 (capi.SAMPLE_WL if wl else 0))
+                 (capi.SAMPLE_WL if wl else 0) | (capi.SAMPLE_OBSERVABLES if observables else 0))
         self._chk(self._lib.smolmc_run_sampled(self._h, int(nsamples), int(thin_by), flags))
 
     def pending_samples(self):
@@ -522,7 +576,9 @@ class Engine:
         feat = np.empty((ns, self.R, self.F))
         acc = np.empty((ns, self.R), dtype=np.uint8)
         with_occ = bool(flags & capi.SAMPLE_OCCUPANCY)
-        extra = {}
+        extra, obs = {}, {}
+        if flags & capi.SAMPLE_OBSERVABLES:  # (read before the fetch marks the block delivered)
+            obs["species_counts"], obs["pair_counts"] = self.sample_observables()
         if flags & capi.SAMPLE_BIAS:
             extra["bias"] = np.empty((ns, self.R))
         if flags & capi.SAMPLE_WL:
@@ -542,7 +598,7 @@ class Engine:
             occ = np.empty((ns, self.R, self.N), dtype=np.int32) if with_occ else None
             self._chk(self._lib.smolmc_get_samples(self._h, _p(H, C.c_double), _p(feat, C.c_double),
                                                    _p(acc, C.c_uint8), _p(occ, C.c_int32)))
-        return dict(enthalpy=H, features=feat, accepted=acc.astype(bool), occupancy=occ, **extra)
+        return dict(enthalpy=H, features=feat, accepted=acc.astype(bool), occupancy=occ, **extra, **obs)
 
     def last_kernel_ms(self):
         ms = C.c_float()

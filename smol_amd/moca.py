@@ -1274,7 +1274,7 @@ class SampleContainer:
         self.metadata = dict(sampling_metadata or {})
         # name -> (dtype, per-sample shape): the schema of a block
         self._schema = {k: (v.dtype, tuple(v.shape[1:])) for k, v in sample_trace.items()}
-        self._blocks = [{k: v for k, v in sample_trace.items()}] if len(sample_trace.occupancy) else []
+        self._blocks = [{k: v for k, v in sample_trace.items()}] if len(sample_trace.enthalpy) else []
         self._joined = {}
         self._total_steps = 0
         # walker -> state point after the last exchange attempt (Sampler.run_exchange keeps it): what a block without
@@ -1284,7 +1284,7 @@ class SampleContainer:
     # ---- block store ---------------------------------------------------------------
     def append_block(self, block, thinned_by):
         """Append ``n`` consecutive samples: ``block[name]`` has shape (n, nwalkers, ...)."""
-        n = len(block["occupancy"])
+        n = len(block["enthalpy"])
         entry = {}
         for name, (dtype, shape) in self._schema.items():
             if name == "state_point" and name not in block:  # (a plain run after run_exchange: nobody moves)
@@ -1295,7 +1295,8 @@ class SampleContainer:
                     now = self._blocks[-1]["state_point"][-1]
                 block = dict(block, state_point=np.broadcast_to(now, (n,) + shape))
             arr = np.asarray(block[name], dtype=dtype)
-            entry[name] = arr.reshape((n,) + shape)
+            # (occupancy: a run with keep_occupancy=False stores that of its final sample only)
+            entry[name] = arr.reshape(((-1 if name == "occupancy" else n),) + shape)
         self._blocks.append(entry)
         self._joined = {}
         self._total_steps += n * int(thinned_by)
@@ -1340,10 +1341,22 @@ class SampleContainer:
         """Occupancies (nwalkers, N) of the most recent sample (no join of the blocks)."""
         return self._blocks[-1]["occupancy"][-1].astype(np.int32)
 
+    def set_last_occupancy(self, occupancy):
+        """The occupancy of the most recent sample, for a block that was recorded without occupancies
+        (``Sampler.run(keep_occupancy=False)``): ``last_occupancy`` and a continuation work as before."""
+        dt, shape = self._schema["occupancy"]
+        self._blocks[-1]["occupancy"] = np.asarray(occupancy, dtype=dt).reshape((1,) + shape)
+        self._joined.pop("occupancy", None)
+
+    def _need_occupancies(self):
+        if any(len(b["occupancy"]) != len(b["enthalpy"]) for b in self._blocks):
+            raise ValueError("these samples were taken with keep_occupancy=False: only the occupancy of the final sample of "
+                             "each run is stored (last_occupancy); sample with keep_occupancy=True for per-sample occupancies")
+
     # ---- bookkeeping -----------------------------------------------------------------
     ensemble = property(lambda self: self._ensemble)
     sublattices = property(lambda self: self._ensemble.sublattices)
-    num_samples = property(lambda self: sum(len(b["occupancy"]) for b in self._blocks))
+    num_samples = property(lambda self: sum(len(b["enthalpy"]) for b in self._blocks))
     total_mc_steps = property(lambda self: self._total_steps)
     shape = property(lambda self: self._schema["occupancy"][1])
     traced_values = property(lambda self: tuple(self._schema))
@@ -1361,6 +1374,8 @@ class SampleContainer:
     def _select(self, name, discard, thin_by):
         """Samples discard + thin_by - 1, discard + 2 thin_by - 1, ... of one traced value in
         its storage dtype (the reference's selection rule, container.py:181-199)."""
+        if name == "occupancy":
+            self._need_occupancies()
         return self._col(name)[discard + thin_by - 1:: thin_by]
 
     def get_trace_value(self, name, discard=0, thin_by=1, flat=True):
@@ -1385,6 +1400,8 @@ class SampleContainer:
         if "state_point" not in self._schema:
             raise ValueError("these samples carry no state_point trace: they were not taken by Sampler.run_exchange")
         point = self._col("state_point")[discard:, :, 0].astype(np.int64)
+        if name == "occupancy":
+            self._need_occupancies()
         vals = self._col(name)[discard:]
         if name == "occupancy":
             vals = vals.astype(np.int32)
@@ -1425,10 +1442,42 @@ class SampleContainer:
                 "Sublattice provided is not recognized.\n Provide one included in the sublattices "
                 "attribute of this SampleContainer."
             )
-        occ = self._select("occupancy", discard, thin_by)[..., sublattice.sites]
-        counts = np.stack([(occ == code).sum(axis=-1) for code in np.asarray(sublattice.encoding)],
-                          axis=-1).astype(float)
+        counts = self._counted_on_device(sublattice, discard, thin_by)
+        if counts is None:
+            occ = self._select("occupancy", discard, thin_by)[..., sublattice.sites]
+            counts = np.stack([(occ == code).sum(axis=-1) for code in np.asarray(sublattice.encoding)],
+                              axis=-1).astype(float)
         return _merge_walkers(counts) if flat else counts
+
+    def _counted_on_device(self, sublattice, discard, thin_by):
+        """The species counts of one sublattice read from the ``species_counts`` trace (counted on the device,
+        ``Sampler.from_ensemble(observables=)``) when the kinds are the default ones and the sublattice has a block of
+        its own; else None: the occupancies are scanned."""
+        obs = self.metadata.get("observables")
+        if "species_counts" not in self._schema or not obs or not obs.get("default_kinds"):
+            return None
+        from .observables import block_counts
+
+        picked = self._select("species_counts", discard, thin_by)
+        blk = block_counts(np.asarray(obs["kind_base"]), np.asarray(obs["site_ncodes"]), picked, sublattice.sites)
+        if blk is None or np.asarray(sublattice.encoding).max(initial=0) >= blk.shape[-1]:
+            return None
+        # (C order, like the scan's stack: the reductions then add in the same order and give the same bits)
+        return blk[..., np.asarray(sublattice.encoding)].astype(float, order="C")
+
+    def get_pair_counts(self, discard=0, thin_by=1, flat=True):
+        """The ``pair_counts`` trace: (..., n_shells, K, K) int32 cells of every sample, bonds as listed."""
+        return self.get_trace_value("pair_counts", discard, thin_by, flat)
+
+    def warren_cowley(self, discard=0, thin_by=1, flat=True):
+        """Warren-Cowley short-range order alpha_ab(shell) of every sample, (..., n_shells, K, K), from the
+        ``species_counts`` and ``pair_counts`` traces (``observables.warren_cowley``)."""
+        from .observables import warren_cowley
+
+        if "pair_counts" not in self._schema:
+            raise ValueError("these samples carry no pair_counts trace: sample with Sampler.from_ensemble(observables=)")
+        wc = warren_cowley(self._select("species_counts", discard, thin_by), self._select("pair_counts", discard, thin_by))
+        return wc.reshape((wc.shape[0] * wc.shape[1],) + wc.shape[2:]) if flat else wc
 
     def get_species_counts(self, discard=0, thin_by=1, flat=True):
         """Counts per species name summed over the sublattices that host it (container.py:336-347)."""
@@ -1486,6 +1535,11 @@ class SampleContainer:
                           "meta/pop_anneal_log_partition_ratio": np.asarray(pop["log_partition_ratio"], dtype=np.float64),
                           "meta/pop_anneal_n_families": np.asarray(pop["n_families"], dtype=np.int64),
                           "meta/pop_anneal_rho_t": np.asarray(pop["rho_t"], dtype=np.float64)})
+        obs = self.metadata.get("observables")
+        if obs is not None:  # the kinds of the species_counts / pair_counts traces
+            extra.update({"meta/obs_kind_base": np.asarray(obs["kind_base"], dtype=np.int32),
+                          "meta/obs_site_ncodes": np.asarray(obs["site_ncodes"], dtype=np.int32),
+                          "meta/obs_shape": np.asarray([obs["n_kinds"], obs["n_shells"], int(obs["default_kinds"])], dtype=np.int64)})
         np.savez_compressed(path, nsamples=self.num_samples, total_mc_steps=self._total_steps,
                             **{f"trace/{k}": v for k, v in self._all().items()}, **extra)
 
@@ -1594,6 +1648,11 @@ class SampleContainer:
                                               temperatures=d["meta/state_point_temperatures"].tolist(),
                                               chemical_potentials=d["meta/state_point_values"].tolist(),
                                               shape=[int(x) for x in d["meta/state_point_shape"]])
+        if "meta/obs_kind_base" in d.files:
+            K, S, default = (int(x) for x in d["meta/obs_shape"])
+            c.metadata["observables"] = dict(n_kinds=K, n_shells=S, default_kinds=bool(default),
+                                             kind_base=d["meta/obs_kind_base"].tolist(),
+                                             site_ncodes=d["meta/obs_site_ncodes"].tolist())
         if "meta/pop_anneal_temperatures" in d.files:
             c.metadata["population_annealing"] = dict(
                 temperatures=d["meta/pop_anneal_temperatures"].tolist(),
@@ -1726,20 +1785,26 @@ class Sampler:
         self._walker_mu = None      # per-walker chemical potentials of this rank's walkers (list of dicts), or None
         self._walker_mu_dirty = False  # ... not yet on the engine
         self._wl_windows = None     # replica-exchange Wang-Landau: the parallel.WLWindows of this sampler's walkers
+        self._observables = None    # observables.Observables counted on the device for every sample, or None
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
                       nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, windows=None,
-                      **kwargs):
+                      observables=None, **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
         'swap'; default kernel Metropolis; one kernel (seed) per walker.
 
         ``windows``: a ``parallel.WLWindows`` -- replica-exchange Wang-Landau.  ``min_enthalpy``, ``max_enthalpy``
         and ``bin_size`` are then the GLOBAL range the windows cut up; kernel w is estimator w of ``windows`` and is
         built with that estimator's window (its ``levels`` / ``entropy`` / ``histogram`` are the estimator's, whichever
-        walker updates it), ``nwalkers`` defaults to ``windows.R``, and ``run_exchange`` samples with exchanges."""
+        walker updates it), ``nwalkers`` defaults to ``windows.R``, and ``run_exchange`` samples with exchanges.
+
+        ``observables``: an ``observables.Observables`` -- its kind counts and pair counts are evaluated on the device
+        for every sample and traced as ``species_counts`` (K,) and ``pair_counts`` (n_shells, K, K), int32."""
         from . import parallel
 
+        if windows is not None and observables is not None:
+            raise ValueError("observables= with windows=: the samples of per-walker windows do not come from the sample ring")
         if windows is not None:
             return cls._from_ensemble_windows(ensemble, windows, *args, step_type=step_type, kernel_type=kernel_type, seeds=seeds,
                                               nwalkers=nwalkers, rank=rank, world_size=world_size, device=device, **kwargs)
@@ -1765,7 +1830,27 @@ class Sampler:
         sampler = cls(kernels, container, walker_range=(first, count), device=device, world_size=world_size)
         if chemical_potentials is not None:
             sampler.set_chemical_potentials(chemical_potentials)
+        if observables is not None:
+            sampler._set_observables(observables)
         return sampler
+
+    def _set_observables(self, obs):
+        """Trace ``obs`` with every sample: the container's schema gains the two traces, its metadata the kinds."""
+        nw, N = self.samples.shape
+        if obs.num_sites != N:
+            raise ValueError(f"the observables are defined on {obs.num_sites} sites, the ensemble has {N}")
+        if obs.site_ncodes is None:
+            raise ValueError("observables for a sampler need site_ncodes (Observables.from_supercell gives them)")
+        if self.samples.num_samples:
+            raise ValueError("the container holds samples without the observables' traces: clear_samples() first")
+        K, S = obs.n_kinds, obs.n_shells
+        self.samples._schema["species_counts"] = (np.dtype(np.int32), (nw, K))
+        self.samples._schema["pair_counts"] = (np.dtype(np.int32), (nw, S, K, K))
+        self.samples.metadata["observables"] = dict(n_kinds=K, n_shells=S, default_kinds=obs.default_kinds,
+                                                    kind_base=obs.kind_base.tolist(), site_ncodes=obs.site_ncodes.tolist())
+        self._observables = obs
+        if self._engine is not None:
+            self._engine.set_observables(obs)
 
     @classmethod
     def _from_ensemble_windows(cls, ensemble, wx, *args, step_type=None, kernel_type=None, seeds=None, nwalkers=1, rank=None,
@@ -1967,6 +2052,8 @@ class Sampler:
                 cfg = capi.make_config(len(self._kernels), capi.KERNEL_METROPOLIS,
                                        STEP_TYPES[k0.step_type], self._device)
             self._engine = Engine(tables, cfg, distance=dist)
+            if self._observables is not None:
+                self._engine.set_observables(self._observables)
             if self._wl_windows is not None:  # (kernel e was built with estimator e's window: cfg holds window 0)
                 self._engine.set_wl_windows(self._wl_windows.vmin, self._wl_windows.vmax)
             self._engine_key = key
@@ -2041,9 +2128,11 @@ class Sampler:
             tr.histogram, tr.occurrences, tr.entropy = wl["histogram"], wl["occurrences"], wl["entropy"]
             tr.cumulative_mean_features = wl["mean_features"]
             tr.mod_factor = wl["mod_factor"].reshape(nw, 1)
+        if self._observables is not None:
+            tr.species_counts, tr.pair_counts = eng.observables()
         return tr
 
-    def _sample_blocks(self, nsteps, initial_occupancies, thin_by, max_block=0, state_loaded=False):
+    def _sample_blocks(self, nsteps, initial_occupancies, thin_by, max_block=0, state_loaded=False, keep_occupancy=True):
         """Generator over blocks of thinned samples, dict name -> (n, nwalkers, ...): the unit
         the device ring delivers (``smolmc_run_sampled``): the samples of a block are recorded on
         the device -- inside one launch for Metropolis kernels, as launch + snapshot pairs queued without
@@ -2086,7 +2175,10 @@ class Sampler:
         # bytes of one sample of all walkers in the ring: occupancy bytes + features (+ the Wang-Landau trace:
         # entropy / histogram / occurrences [L] and the mean features [L x F] of every walker, wanglandau.py:247-251)
         F = len(k0.ensemble.natural_parameters)
-        per_sample = nw * (N + 8 * F + 17)
+        obs = self._observables
+        per_sample = nw * ((N if keep_occupancy else 0) + 8 * F + 17)
+        if obs is not None:
+            per_sample += nw * 4 * (obs.n_kinds + obs.n_shells * obs.n_kinds ** 2)
         if is_wl:
             L = len(k0._levels)
             per_sample += nw * L * (24 + 8 * F)
@@ -2101,7 +2193,7 @@ class Sampler:
         sizes = [min(per_block, nsamples - start) for start in range(0, nsamples, per_block)]
 
         def queue(n):
-            eng.run_sampled_async(n, thin_by, occupancy=True, bias=has_bias, wl=is_wl)
+            eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl, observables=obs is not None)
 
         # Block i + 1 is queued before block i is handed out, so a consumer that stops early -- a `break` out of
         # Sampler.sample(), an exception in run() between two blocks -- leaves a block on the (cached) engine's ring.
@@ -2121,7 +2213,8 @@ class Sampler:
             if i + 1 < len(sizes):
                 queue(sizes[i + 1])
             ring = eng.fetch_samples(packed=True)
-            block = dict(occupancy=ring["occupancy"], features=ring["features"],
+            occ = ring["occupancy"]  # (None: recorded without, see Sampler.run(keep_occupancy=False))
+            block = dict(occupancy=np.empty((0, nw, eng.N), dtype=np.uint8) if occ is None else occ, features=ring["features"],
                          enthalpy=ring["enthalpy"][..., None], temperature=np.broadcast_to(temps, (n, nw, 1)),
                          accepted=ring["accepted"][..., None])
             if not isinstance(k0, Metropolis):  # (UniformlyRandom, Wang-Landau: no temperature in the trace)
@@ -2131,6 +2224,8 @@ class Sampler:
             if is_wl:
                 block.update(histogram=ring["histogram"], occurrences=ring["occurrences"], entropy=ring["entropy"],
                              cumulative_mean_features=ring["mean_features"], mod_factor=ring["mod_factor"][..., None])
+            if "species_counts" in ring:
+                block.update(species_counts=ring["species_counts"], pair_counts=ring["pair_counts"])
             yield block
 
     def _wl_run_with_host_checks(self, eng, nsteps):
@@ -2192,7 +2287,7 @@ class Sampler:
     def sample(self, nsteps, initial_occupancies, thin_by=1, progress=False):
         """Generator over thinned traces, one Trace per sample (sampler.py:164-210)."""
         for block in self._sample_blocks(nsteps, initial_occupancies, thin_by):
-            for i in range(len(block["occupancy"])):
+            for i in range(len(block["enthalpy"])):
                 tr = Trace(**{k: np.asarray(v[i]) for k, v in block.items()})
                 tr.occupancy = tr.occupancy.astype(np.int32)  # (trace.occupancy is int32 in the reference)
                 yield tr
@@ -2204,9 +2299,19 @@ class Sampler:
                                "These must be provided.")
 
     def run(self, nsteps, initial_occupancies=None, thin_by=1, progress=False, stream_chunk=0,
-            stream_file=None, keep_last_chunk=False, swmr_mode=False):
+            stream_file=None, keep_last_chunk=False, swmr_mode=False, keep_occupancy=True):
         """sampler.py:212-301.  ``stream_chunk`` > 0 writes every chunk of samples to the streaming
-        directory ``stream_file`` (see SampleContainer.get_backend) and keeps none in memory."""
+        directory ``stream_file`` (see SampleContainer.get_backend) and keeps none in memory.
+
+        ``keep_occupancy=False`` (a sampler built with ``observables=`` only): the occupancies of the samples never
+        leave the device -- their species and pair counts do; the container stores the occupancy of the final
+        sample of this call alone, so ``last_occupancy`` and a continuation work as before."""
+        if not keep_occupancy:
+            if self._observables is None:
+                raise ValueError("keep_occupancy=False needs a sampler built with observables=: nothing else of the "
+                                 "occupancies would be recorded")
+            if stream_chunk > 0:
+                raise ValueError("keep_occupancy=False with stream_chunk: every part of a stream holds its occupancies")
         self._need_start(initial_occupancies)
         if initial_occupancies is not None and self.samples.num_samples > 0:
             warnings.warn(
@@ -2223,8 +2328,11 @@ class Sampler:
         if backend is not None and self._kept_last:
             self.samples.clear()  # the sample kept by the previous streamed run is already in its stream
         self._kept_last = False
-        for block in self._sample_blocks(nsteps, None, thin_by, max_block=stream_chunk, state_loaded=True):
+        recorded = False
+        without = {} if keep_occupancy else dict(keep_occupancy=False)
+        for block in self._sample_blocks(nsteps, None, thin_by, max_block=stream_chunk, state_loaded=True, **without):
             self.samples.append_block(block, thinned_by=thin_by)
+            recorded = True
             if backend is not None:
                 # the most recent sample, whether or not this block fills a chunk: the tail flush
                 # below must leave the FINAL recorded sample behind, not the end of the last full chunk
@@ -2237,6 +2345,8 @@ class Sampler:
             if keep_last_chunk and last is not None:  # the last sample stays in memory, e.g. to start the next run from it
                 self.samples.append_block(last, thinned_by=0)
                 self._kept_last = True
+        if not keep_occupancy and recorded:  # (the walkers' current states ARE the final sample)
+            self.samples.set_last_occupancy(self._get_engine().get_state()["occupancy"])
         # the device now holds the last recorded sample (see _load_state)
         self._resume_at = (id(self.samples), self.samples.num_samples)
 

@@ -5,7 +5,8 @@ composition isotherms, mu-T diagrams and hysteresis loops without one handle per
 Every grid point (T_i, mu_j) gets `--walkers` walkers.  The chemical potential of ONE species (`--scan
 sublattice:code`, or `--species NAME` on an .mson model) runs over `--mu lo:hi:n` as an offset to the model's own
 table; the walkers equilibrate, then record `--samples` samples `--thin` steps apart through the device ring.  One JSON
-line per grid point: T, mu, mean composition per active sublattice, acceptance.
+line per grid point: T, mu, mean composition per active sublattice, acceptance.  The compositions are counted on the
+device (smolmc_set_observables: one kind per active sublattice and species code); no occupancy is downloaded.
 
     python tools/mu_scan.py --config 3 --dim 6 --T 30000 40000 --mu=-2:2:16
     python tools/mu_scan.py --mson model.mson --supercell 6 --species Li+ --mu=-0.5:0.5:32 --T 600 900
@@ -107,6 +108,18 @@ def build(a, R):
     return ens.make_tables(), capi.STEP_FLIP, occ, hit[0]
 
 
+def composition_observables(tables, width):
+    """Kind = active sublattice q x ``width`` + species code on the sites of the active sublattices, no bond shells: the
+    species counts of every walker in the layout of its chemical-potential rows."""
+    from smol_amd.observables import Observables
+
+    sites = tables.active_sites()
+    kind_base = np.full(tables.struct.num_sites, -1, dtype=np.int32)
+    for q, st in enumerate(sites):
+        kind_base[st] = q * width
+    return Observables(kind_base, len(sites) * width)
+
+
 def main(argv=None):
     a = parse_args(argv)
     T, j = grid_of(a)
@@ -122,6 +135,7 @@ def main(argv=None):
     eng = Engine(tables, capi.make_config(R, capi.KERNEL_METROPOLIS, step))
     base = eng.get_walker_mu()
     sites = tables.active_sites()
+    eng.set_observables(composition_observables(tables, base.shape[2]))
     seeds = np.arange(R, dtype=np.uint64) + np.uint64(a.seed)
     for stage, col in enumerate(stages):
         rows = base.copy()
@@ -131,11 +145,11 @@ def main(argv=None):
             eng.set_state(occ, seeds, T)
         eng.run(a.equil)
         s0 = eng.get_state(occupancy=False)
-        smp = eng.run_sampled(a.samples, a.thin, occupancy=True, packed=True)
+        smp = eng.run_sampled(a.samples, a.thin, occupancy=False, observables=True)
         s1 = eng.get_state(occupancy=False)
         acc = (s1["n_accepted"] - s0["n_accepted"]) / float(a.samples * a.thin)
-        o = smp["occupancy"]  # (samples, R, N)
-        comp = [np.stack([(o[:, :, st] == c).mean(axis=(0, 2)) for c in range(base.shape[2])], axis=1) for st in sites]
+        n = smp["species_counts"].sum(axis=0).reshape(R, len(sites), base.shape[2])  # (R, sublattices, codes) over the samples
+        comp = [n[:, q, :] / float(a.samples * len(st)) for q, st in enumerate(sites)]
         npt = len(a.mu_values)
         for p in range(len(a.T) * npt):
             w = slice(p * a.walkers, (p + 1) * a.walkers)
