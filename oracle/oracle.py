@@ -147,6 +147,28 @@ class OracleEvaluator:
         )
         return out
 
+    def bind(self, occ):
+        """``change(nf, rec)`` -> the feature vector change of the first ``nf`` (site, code) pairs of the int32 record
+        ``rec`` from ONE state, with the state's buffers made once (``feature_vector_change`` copies the occupancy twice
+        per call); the returned array is overwritten by the next call.  ``change.move(nf, rec)`` makes the state take
+        the step, ``change.occ`` is the state (a copy of ``occ``)."""
+        occ = np.array(occ, dtype=np.int32)
+        wf, wi, out, fl = occ.copy(), occ.copy(), np.zeros(self.F), np.zeros(16, dtype=np.int32)
+        fn = lib().orc_feature_vector_change
+        head = (self.t, _p(occ, C.c_int32), _p(fl, C.c_int32))
+        tail = (_p(wf, C.c_int32), _p(wi, C.c_int32), _p(out, C.c_double))
+
+        def change(nf, rec):
+            fl[: 2 * nf] = rec[: 2 * nf]
+            fn(*head, nf, *tail)
+            return out
+
+        def move(nf, rec):
+            for q in range(nf):
+                occ[rec[2 * q]] = wf[rec[2 * q]] = wi[rec[2 * q]] = rec[2 * q + 1]
+        change.move, change.occ = move, occ
+        return change
+
     def bias(self, occ):
         """MCBias.compute_bias (bias.py:174-186, :264-277)."""
         return lib().orc_compute_bias(self.t, _p(self._occ(occ), C.c_int32))
@@ -262,6 +284,12 @@ class OracleMC:
         if lib().orc_mc_get_bias(self.h, _p(b, C.c_double)):
             raise RuntimeError("model has no bias term")
         return b
+
+    def proposer(self):
+        """``propose`` with its buffer made once: (r, step) -> (nf, rec), rec valid until the next call."""
+        rec = np.zeros(16, dtype=np.int32)
+        ptr, fn = _p(rec, C.c_int32), lib().orc_mc_propose
+        return lambda r, step: (fn(self.h, int(r), int(step), ptr, None), rec)
 
     def propose(self, r, step, with_priori=False):
         fl = np.zeros(16, dtype=np.int32)

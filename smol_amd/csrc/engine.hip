@@ -781,7 +781,10 @@ static LeanDeltaTables lean_delta_tables(const smolmc_tables *t, const SiteClass
     }
     // float32 pre-test of the accept decision: a step sums at most two flips' worth of
     // |w * d| over the slots, a float32 conversion + 6-level tree adds at most
-    // 7 * 2^-24 of that; 2^-19 leaves a 4.5x margin.
+    // 7 * 2^-24 of that; 2^-19 leaves a 4.5x margin.  (That is the derivation.  Measured with the threshold placed
+    // a hair from the exact dH on every tested step, tests/fast_band.py: no wrong decision at this band, the first at
+    // the band scaled by 2^-7 .. 2^-11 depending on the kernel family, i.e. a margin of 128x or more on every tested
+    // case -- profiles/fast_band_margin.jsonl)
     L.fast_eps = 2.0 * sum_abs_max * ldexp(1.0, -19);
     return L;
 }
