@@ -379,6 +379,7 @@ int smolmc_sync(smolmc_handle *h);
 #define SMOLMC_SAMPLE_BIAS 2      /* flags bit 1: trace.bias (error without an MCBias term) */
 #define SMOLMC_SAMPLE_WL 4        /* flags bit 2: the Wang-Landau trace (error on a Metropolis handle) */
 #define SMOLMC_SAMPLE_OBSERVABLES 8 /* flags bit 3: kind and pair counts of every row (see smolmc_set_observables) */
+#define SMOLMC_SAMPLE_MINIMA 16     /* flags bit 4: offer every row to the minima record (see smolmc_set_minima) */
 int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t thin_by, int flags);
 /* The ring as the next smolmc_get_samples* call sees it (ABI 8): *n_pending = blocks queued and not fetched
  * (0..2), *nsamples / *flags = sample count and SMOLMC_SAMPLE_* flags of the block that call would deliver
@@ -442,6 +443,55 @@ int smolmc_eval_observables(smolmc_handle *h, const int32_t *occ /* nocc x N, or
  * NULL) and does not mark it delivered, like smolmc_pending_samples; an error when that block was recorded without
  * the flag. */
 int smolmc_get_sample_observables(smolmc_handle *h, int32_t *counts, int32_t *pairs);
+/* ---- minima: the lowest recorded states, kept on the device ------------------------------------------------------
+ * (the reference's container takes an argmin over stored occupancies, sampler/container.py:306-334; here the rows of a
+ * block are reduced where they lie and only the record is ever downloaded).  A minima record is a table of n_slots
+ * entries that lives as long as the handle.  Every recorded sample is OFFERED to the entry its key selects:
+ *   n_axes == 0   one slot per walker, the key is the walker index (n_slots = R)
+ *   n_axes 1..4   the key comes from the sample's kind counts (the observables' counts[K]): on axis a
+ *                 d_a = sum_k axis_weights[a][k] * counts[k] (int64), c_a = floor(d_a / axis_bin[a]); the row is skipped
+ *                 unless 0 <= c_a < axis_extent[a] on every axis; the key is the mixed-radix number of the c_a, axis 0
+ *                 slowest (n_slots = product of the extents)
+ * The value that is minimised: the enthalpy (n_weights == 0), or sum_{i < n_weights} weights[i] * features[i] taken left
+ * to right, every product and every sum rounded on its own (no fused multiply-add).  Values are compared as v + 0.0
+ * (-0.0 and +0.0 are one value); a NaN never wins.  Offers are numbered from 0 since the last reset in launch order:
+ * each sample of a block recorded with SMOLMC_SAMPLE_MINIMA is one offer, each smolmc_update_minima call is one.  A
+ * strictly lower value replaces the entry; among equal values the earliest offer wins, within one offer the lowest
+ * walker.  An entry holds value, enthalpy, features [F], occupancy [N] (the caller's site numbering), counts [K] (zeros
+ * without observables), walker, sample (the offer number) and step (the walker's n_steps at that sample).  An empty
+ * entry reads value = +inf, walker = -1, sample = -1 and zeros elsewhere.
+ * smolmc_set_state and smolmc_discard_samples leave the record alone: it belongs to the handle, not to a block. */
+#define SMOLMC_MAX_MINIMA_AXES 4
+typedef struct {
+    int n_weights;               /* 0: the enthalpy column */
+    const double *weights;       /* [n_weights], n_weights <= F */
+    int n_axes;                  /* 0: one slot per walker */
+    const int32_t *axis_weights; /* [n_axes x K], K of the observables in force */
+    const int32_t *axis_bin;     /* [n_axes], each >= 1 */
+    const int32_t *axis_extent;  /* [n_axes], each >= 1 */
+} smolmc_minima;
+/* Sets the record (NULL: removes it); a new spec starts an empty record.  Refused, each naming its reason and leaving
+ * the handle as it was: n_axes > 0 without observables; n_weights > F; a bin or an extent below 1; more than 2^20 slots
+ * or a record of more than 1 GiB (n_slots x (Npad + 8 F + 4 K + 40) bytes).  While a keyed record is set,
+ * smolmc_set_observables is refused.  Waits for the handle's stream (queued blocks still write the record), like
+ * smolmc_reset_minima and smolmc_get_minima. */
+int smolmc_set_minima(smolmc_handle *h, const smolmc_minima *m);
+/* n_slots and n_axes in force (0, 0: none set) */
+int smolmc_minima_shape(smolmc_handle *h, int *n_slots, int *n_axes);
+/* Offers the walkers' CURRENT states, one offer (for callers of smolmc_run); a keyed record counts the kinds of the
+ * current states on the device first. */
+int smolmc_update_minima(smolmc_handle *h);
+/* Empties the record; the offer numbering restarts at 0. */
+int smolmc_reset_minima(smolmc_handle *h);
+/* The record: value, enthalpy, walker, sample, step [n_slots]; features [n_slots x F]; occ [n_slots x N]; counts
+ * [n_slots x K].  Any pointer may be NULL. */
+int smolmc_get_minima(smolmc_handle *h, double *value, double *enthalpy, double *features, int32_t *occ,
+                      int32_t *counts, int32_t *walker, int64_t *sample, uint64_t *step);
+/* A per-walker record also keeps the COMPANIONS of walker 0's entry: the occupancy of every walker at the offer that
+ * entry was taken from, occ [R x N] in the caller's numbering (zeros while the entry is empty).  It is what the
+ * reference's get_minimum_*_occupancy(flat=False) returns (sampler/container.py:316-318: every walker's occupancy at the
+ * sample where walker 0 was lowest).  Refused on a record keyed by composition.  Waits for the handle's stream. */
+int smolmc_get_minima_companions(smolmc_handle *h, int32_t *occ);
 
 /* Same loop driven by host-provided proposals ("replay mode"): what
  * StandardSingleStepMixin.single_step (kernel/base.py:145-166) does after mcusher.propose_step

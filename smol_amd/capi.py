@@ -28,6 +28,8 @@ ERR_RING_FULL = 2  # SMOLMC_ERR_RING_FULL
 SAMPLE_OCCUPANCY, SAMPLE_BIAS, SAMPLE_WL = 1, 2, 4  # SMOLMC_SAMPLE_* flags of smolmc_run_sampled
 SAMPLE_OBSERVABLES = 8          # ... kind and pair counts of every row (smolmc_set_observables)
 MAX_OBS_CELLS = 4096            # SMOLMC_MAX_OBS_CELLS
+SAMPLE_MINIMA = 16              # ... every row is offered to the minima record (smolmc_set_minima)
+MAX_MINIMA_AXES = 4             # SMOLMC_MAX_MINIMA_AXES
 MAX_STEP_FLIPS = 8              # SMOLMC_MAX_STEP_FLIPS
 STEP_ROW = 2 * MAX_STEP_FLIPS   # SMOLMC_STEP_ROW: int32 per step record (site, code) x 8, -1 = no flip
 
@@ -129,6 +131,19 @@ class smolmc_distance(C.Structure):
 
 
 DIST_MAX_FEATURES = 256  # SMOLMC_DIST_MAX_FEATURES
+
+
+class smolmc_minima(C.Structure):
+    """Mirror of ``smolmc_minima`` (include/smolmc.h); ``minima.Minima.c_struct`` fills it."""
+
+    _fields_ = [
+        ("n_weights", C.c_int),
+        ("weights", _f64p),
+        ("n_axes", C.c_int),
+        ("axis_weights", _i32p),
+        ("axis_bin", _i32p),
+        ("axis_extent", _i32p),
+    ]
 
 
 class smolmc_observables(C.Structure):

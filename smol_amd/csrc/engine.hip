@@ -2369,6 +2369,7 @@ extern "C" int smolmc_destroy(smolmc_handle *h) {
     free_observables(h->obs);
     if (h->obs_ev0) hipEventDestroy(h->obs_ev0);
     if (h->obs_ev1) hipEventDestroy(h->obs_ev1);
+    smolmc_min_free(h);
     free_samples(h);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -3325,6 +3326,8 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     if ((flags & SMOLMC_SAMPLE_WL) && !wl) return fail("handle is not a Wang-Landau kernel");
     if ((flags & SMOLMC_SAMPLE_OBSERVABLES) && !h->obs.K)
         return fail("SMOLMC_SAMPLE_OBSERVABLES without observables: call smolmc_set_observables first");
+    const bool minima = (flags & SMOLMC_SAMPLE_MINIMA) != 0;
+    if (minima && !h->minima.n_slots) return fail("SMOLMC_SAMPLE_MINIMA without a minima record: call smolmc_set_minima first");
     if ((flags & SMOLMC_SAMPLE_WL) && !h->wl_win_min.empty())
         return fail("SMOLMC_SAMPLE_WL while per-walker windows are set: the snapshot rows are walker-indexed, the Wang-Landau arrays estimator-indexed (smolmc_get_wl between runs, or smolmc_set_wl_windows(h, NULL, NULL) first)");
     if (thin_by > ((int64_t)1 << 30) && h->lean() && !smolmc_env(ENV_LAUNCH_CHUNK))
@@ -3381,7 +3384,16 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     size_t o_scal = 0, o_occ_int = w.o_occ;
     if (lazy_rows) o_scal = take(rows * (size_t)std::max(1, lazy_nscal(h)) * 8);
     // (... and so do the occupancy rows the observables are counted from)
-    if ((lazy_rows || obs) && !(flags & SMOLMC_SAMPLE_OCCUPANCY)) o_occ_int = take(rows * h->Npad);
+    // (... and the rows offered to the minima record, with their kind counts and the two scratch columns of the reduction)
+    const bool min_counts = minima && h->obs.K && h->obs.K == h->minima.K; // (a keyed record: always, see smolmc_set_observables)
+    if ((lazy_rows || obs || minima) && !(flags & SMOLMC_SAMPLE_OCCUPANCY)) o_occ_int = take(rows * h->Npad);
+    size_t o_min_cnt = w.o_cnt, o_min_key = 0, o_min_slot = 0;
+    if (minima) {
+        if (min_counts && !obs) o_min_cnt = take(rows * (size_t)h->obs.K * 4);
+        o_min_key = take(rows * 8);
+        o_min_slot = take(rows * 4);
+        if (rows > 0x7fffffffull) return fail("minima: more than 2^31 sample rows in one block");
+    }
     if (lazy_rows && rows > 0x7fffffffull) return fail("lazy cluster features: more than 2^31 sample rows in one block");
     if (obs && rows > 0x7fffffffull) return fail("observables: more than 2^31 sample rows in one block");
     // the slot's previous block (delivered, or none) must have left the device before its arenas are reused
@@ -3411,7 +3423,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     smp.H = (double *)(sl.d + w.o_H);
     smp.feat = (double *)(sl.d + (lazy_rows ? o_scal : w.o_feat));
     smp.acc = sl.d + w.o_acc;
-    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs ? sl.d + o_occ_int : nullptr;
+    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs || minima ? sl.d + o_occ_int : nullptr;
     if (!snapshot_path) {
         if (inkernel_bias) {
             if ((w.o_bias - w.o_H) / 8 > 0xffffffffull) return fail("sample block too large for the in-kernel bias column");
@@ -3449,6 +3461,12 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
         }
     }
     if (obs) TRY(smolmc_obs_launch(h, sl.d + o_occ_int, rows, (int32_t *)(sl.d + w.o_cnt), (int32_t *)(sl.d + w.o_pair)));
+    if (minima) {
+        if (min_counts && !obs) TRY(smolmc_obs_launch(h, sl.d + o_occ_int, rows, (int32_t *)(sl.d + o_min_cnt), nullptr));
+        TRY(smolmc_min_launch(h, (const double *)(sl.d + w.o_H), (const double *)(sl.d + w.o_feat), sl.d + o_occ_int,
+                              min_counts ? (const int32_t *)(sl.d + o_min_cnt) : nullptr, (uint64_t *)(sl.d + o_min_key),
+                              (int32_t *)(sl.d + o_min_slot), nsamples, thin_by));
+    }
     // download on the copy stream as soon as the block is complete; the next block's launches do not wait for it
     // (the mirror is about to be overwritten: from here the slot no longer holds its old block)
     sl.state = 0;
@@ -3779,6 +3797,9 @@ extern "C" int smolmc_set_observables(smolmc_handle *h, const smolmc_observables
             return fail("smolmc_set_observables while a block recorded with SMOLMC_SAMPLE_OBSERVABLES waits in the ring (call "
                         "smolmc_get_samples* or smolmc_discard_samples first)");
     SmolmcObs O;
+    if (h->minima.n_slots && h->minima.n_axes)
+        return fail("smolmc_set_observables while a minima record keyed by composition depends on the observables (call "
+                    "smolmc_set_minima(h, NULL) first)");
     if (obs) {
         const int N = h->N, K = obs->n_kinds, S = obs->n_shells;
         if (!obs->kind_base || S < 0 || (S > 0 && (!obs->shell_ptr || !obs->bonds))) return fail("observables: null argument");
@@ -3896,6 +3917,19 @@ extern "C" int smolmc_eval_observables(smolmc_handle *h, const int32_t *occ, int
     if (rc) return rc;
     if (e != hipSuccess) return fail(std::string("eval_observables: ") + hipGetErrorString(e));
     return 0;
+}
+
+// one offer of the walkers' current states to the minima record (minima.hip): what a caller of smolmc_run does where
+// smolmc_run_sampled offers the rows of its block
+extern "C" int smolmc_update_minima(smolmc_handle *h) {
+    if (!h) return fail("null handle");
+    SmolmcMin &M = h->minima;
+    if (!M.n_slots) return fail("no minima record set: call smolmc_set_minima first");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(ensure_features(h));
+    const bool counts = h->obs.K && h->obs.K == M.K;
+    if (counts) TRY(smolmc_obs_launch(h, h->kp.occ, (size_t)h->R, M.u_counts, nullptr));
+    return smolmc_min_launch(h, h->kp.enthalpy, h->kp.features, h->kp.occ, counts ? M.u_counts : nullptr, M.u_key, M.u_slot, 1, 1);
 }
 
 extern "C" int smolmc_get_sample_observables(smolmc_handle *h, int32_t *counts, int32_t *pairs) {

@@ -134,7 +134,8 @@ int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int3
     ObsArgs A;
     A.occ = d_occ8; A.kind_base = O.d_kind_base; A.shell_ptr = O.d_shell_ptr; A.bonds = O.d_bonds;
     A.counts = d_counts; A.pairs = d_pairs;
-    A.N = h->N; A.Npad = h->Npad; A.K = O.K; A.n_shells = O.n_shells; A.pair_copies = O.pair_copies;
+    A.N = h->N; A.Npad = h->Npad; A.K = O.K; A.pair_copies = O.pair_copies;
+    A.n_shells = d_pairs ? O.n_shells : 0; // (no shells: the kernel counts the kinds and never touches the pair arrays)
     if (!h->obs_ev0) {
         HIPCHK(hipEventCreate(&h->obs_ev0));
         HIPCHK(hipEventCreate(&h->obs_ev1));

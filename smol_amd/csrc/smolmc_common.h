@@ -776,6 +776,31 @@ struct SmolmcObs {
     uint32_t *d_bonds = nullptr; // one word per bond: i | j << 16
 };
 
+// minima.hip: the minima record of a handle (smolmc_set_minima): the spec and one device arena cut into the entry arrays
+// [n_slots (x ...)], the per-slot scratch of a reduction (cand, win: armed to all ones between launches) and the per-row
+// scratch of smolmc_update_minima
+struct SmolmcMin {
+    int n_slots = 0;           // (0: none set)
+    int n_axes = 0, n_weights = 0, K = 0; // K: the kinds of the observables in force when the record was set
+    int32_t bin[SMOLMC_MAX_MINIMA_AXES] = {1, 1, 1, 1}, extent[SMOLMC_MAX_MINIMA_AXES] = {1, 1, 1, 1};
+    long long offers = 0;      // offers since the last reset
+    unsigned char *arena = nullptr;
+    size_t arena_bytes = 0, entry_bytes = 0; // (entry_bytes: from value to the end of the entry arrays -- what a fetch copies)
+    double *value = nullptr, *enthalpy = nullptr, *features = nullptr;
+    uint64_t *step = nullptr;
+    int64_t *sample = nullptr;
+    int32_t *walker = nullptr, *counts = nullptr;
+    uint8_t *occ = nullptr;
+    uint8_t *companions = nullptr; // per-walker record: every walker's row at the offer entry 0 was taken from [R x Npad]
+    uint64_t *cand = nullptr;
+    uint32_t *win = nullptr;
+    double *weights = nullptr;
+    int32_t *axis_w = nullptr;
+    uint64_t *u_key = nullptr; // smolmc_update_minima: ordered values [R], slots [R], counts [R x K]
+    int32_t *u_slot = nullptr, *u_counts = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three passes of the last reduction
+};
+
 struct smolmc_handle {
     smolmc_config cfg;
     int device = 0;
@@ -856,6 +881,8 @@ struct smolmc_handle {
     // kind and pair counts of occupancy rows (smolmc_set_observables, engine.hip; the kernel in observables.hip)
     SmolmcObs obs;
     hipEvent_t obs_ev0 = nullptr, obs_ev1 = nullptr; // around the last launch of the observables kernel (created at the first)
+    // the lowest recorded states (smolmc_set_minima; minima.hip)
+    SmolmcMin minima;
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
     SampleSlot slots[2];
@@ -970,7 +997,15 @@ int smolmc_pop_clone_launch(smolmc_handle *h, const int32_t *parent, int npop, c
 // observables.hip: kind counts [rows x K] and pair counts [rows x n_shells x K x K] of `rows` occupancy rows (Npad bytes
 // apart, device) into device arrays, queued on the handle's stream; the LDS a launch takes and the number of pair
 // histograms it keeps there
+// (d_pairs == nullptr: the kind counts only)
 int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs);
+// minima.hip: offer `rows` = nsamples x R rows (enthalpy [rows], features [rows x F], occupancy rows Npad bytes apart,
+// counts [rows x K] or null; device) to the handle's record, three kernels queued on the handle's stream; d_key [rows]
+// and d_slot [rows] are scratch.  Row s * R + r is offer number offers + s of walker r, taken thin_by steps before row
+// (s + 1) * R + r; the last sample is the walkers' state now.  Counts the offers.
+int smolmc_min_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const uint8_t *d_occ8, const int32_t *d_counts,
+                      uint64_t *d_key, int32_t *d_slot, long long nsamples, long long thin_by);
+void smolmc_min_free(smolmc_handle *h);
 size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies);
 int smolmc_obs_pair_copies(size_t cells);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);

@@ -60,6 +60,12 @@ SYMBOLS = {
     "smolmc_observables_shape": (C.c_int, [_HP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "smolmc_eval_observables": (C.c_int, [_HP, _i32p, C.c_int, _i32p, _i32p]),
     "smolmc_get_sample_observables": (C.c_int, [_HP, _i32p, _i32p]),
+    "smolmc_set_minima": (C.c_int, [_HP, C.POINTER(capi.smolmc_minima)]),
+    "smolmc_minima_shape": (C.c_int, [_HP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "smolmc_update_minima": (C.c_int, [_HP]),
+    "smolmc_reset_minima": (C.c_int, [_HP]),
+    "smolmc_get_minima": (C.c_int, [_HP, _f64p, _f64p, _f64p, _i32p, _i32p, _i32p, _i64p, _u64p]),
+    "smolmc_get_minima_companions": (C.c_int, [_HP, _i32p]),
     "smolmc_replay": (C.c_int, [_HP, C.c_int64, _i32p, _f64p, _f64p, _u8p, _f64p, _f64p]),
     "smolmc_last_kernel_ms": (C.c_int, [_HP, C.POINTER(C.c_float)]),
     "smolmc_eval_full": (C.c_int, [_HP, _i32p, C.c_int, _f64p]),
@@ -188,6 +194,7 @@ class Engine:
         self.F = self._lib.smolmc_num_features(self._h)
         self.L = self._lib.smolmc_wl_num_levels(self._h)
         self.walker_mu_set = False  # per-walker chemical potentials in force (set_walker_mu)
+        self.minima_spec = None     # the spec of the minima record in force (set_minima)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -536,23 +543,84 @@ class Engine:
         self._chk(fn(self._h, C.byref(ms)))
         return float(ms.value)
 
-    def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False):
+    # ---- minima: the lowest recorded states, kept on the device ----------------------------
+    def set_minima(self, spec):
+        """The minima record of this handle (smolmc_set_minima): a ``minima.Minima``, or None to remove it.  A new spec
+        starts an empty record.  The record lives as long as the handle: ``set_state`` and ``discard_samples`` leave it
+        alone."""
+        if spec is None:
+            self._chk(self._lib.smolmc_set_minima(self._h, None))
+        else:
+            struct, keep = spec.c_struct()
+            self._chk(self._lib.smolmc_set_minima(self._h, C.byref(struct)))
+            del keep
+        self.minima_spec = spec
+
+    def minima_shape(self):
+        """(n_slots, n_axes) in force, (0, 0) when no record is set (smolmc_minima_shape)."""
+        n, a = C.c_int(), C.c_int()
+        self._chk(self._lib.smolmc_minima_shape(self._h, C.byref(n), C.byref(a)))
+        return int(n.value), int(a.value)
+
+    def update_minima(self):
+        """Offer the walkers' current states to the record, one offer (smolmc_update_minima): for callers of ``run``."""
+        self._chk(self._lib.smolmc_update_minima(self._h))
+
+    def reset_minima(self):
+        """Empty the record; the offer numbering restarts (smolmc_reset_minima)."""
+        self._chk(self._lib.smolmc_reset_minima(self._h))
+
+    def minima(self):
+        """The record as a ``minima.MinimaRecord`` (smolmc_get_minima; waits for the handle's stream)."""
+        from .minima import MinimaRecord
+
+        if self.minima_spec is None:
+            raise EngineError("no minima record set: call set_minima first")
+        K = self.observables_shape()[0]
+        rec = MinimaRecord(self.minima_spec, self.R, self.F, self.N, K)
+        n, _ = self.minima_shape()
+        if n != rec.n_slots:
+            raise EngineError(f"the handle's record has {n} slots, the spec gives {rec.n_slots}")
+        self._chk(self._lib.smolmc_get_minima(
+            self._h, _p(rec.value, C.c_double), _p(rec.enthalpy, C.c_double), _p(rec.features, C.c_double),
+            _p(rec.occupancy, C.c_int32), _p(rec.counts, C.c_int32) if K else None, _p(rec.walker, C.c_int32),
+            _p(rec.sample, C.c_int64), _p(rec.step, C.c_uint64)))
+        if rec.companions is not None:
+            self._chk(self._lib.smolmc_get_minima_companions(self._h, _p(rec.companions, C.c_int32)))
+        rec.offers = int(rec.sample.max(initial=-1)) + 1  # (at least: the engine keeps the count)
+        return rec
+
+    def minima_kernel_ms(self):
+        """Device times of the three passes of the last minima reduction in ms (HIP events; a measuring hook of the
+        library, not part of the C-ABI)."""
+        fn = self._lib.smolmc_debug_minima_kernel_ms
+        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
+        ms = (C.c_float * 3)()
+        self._chk(fn(self._h, ms))
+        return [float(x) for x in ms]
+
+    def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False,
+                    minima=False):
         """Advance nsamples*thin_by steps recording one sample per walker every thin_by steps
         on the device; returns dict(enthalpy (ns,R), features (ns,R,F), accepted (ns,R) bool,
         occupancy (ns,R,N) or None[, bias (ns,R)][, the Wang-Landau trace][, species_counts, pair_counts]).
         Occupancies come back as int32 (the reference's trace dtype) or, with ``packed``, as the ring's own
         uint8 -- a quarter of the transfer.  = ``run_sampled_async`` + ``fetch_samples``."""
-        self.run_sampled_async(nsamples, thin_by, occupancy=occupancy, bias=bias, wl=wl, observables=observables)
+        self.run_sampled_async(nsamples, thin_by, occupancy=occupancy, bias=bias, wl=wl, observables=observables,
+                               minima=minima)
         return self.fetch_samples(packed=packed)
 
-    def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False, observables=False):
+    def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False, observables=False, minima=False):
         """Queue one block of the device ring (smolmc_run_sampled): returns at once.  The ring has two
         slots; queue block k + 1 BEFORE fetching block k and the download of k overlaps the kernel of
         k + 1 (the order ``fetch_samples`` delivers in: oldest first).  ``observables``: the kind and pair
         counts of ``set_observables`` for every row, counted on the device; with ``occupancy=False`` the
-        occupancy rows they are counted from never leave it."""
+        occupancy rows they are counted from never leave it.  ``minima``: every row is offered to the record of
+        ``set_minima`` when the block's launches are through; what the reduction reads and the caller did not ask for
+        stays on the device."""
         flags = ((capi.SAMPLE_OCCUPANCY if occupancy else 0) | (capi.SAMPLE_BIAS if bias else 0) |
-                 (capi.SAMPLE_WL if wl else 0) | (capi.SAMPLE_OBSERVABLES if observables else 0))
+                 (capi.SAMPLE_WL if wl else 0) | (capi.SAMPLE_OBSERVABLES if observables else 0) |
+                 (capi.SAMPLE_MINIMA if minima else 0))
         self._chk(self._lib.smolmc_run_sampled(self._h, int(nsamples), int(thin_by), flags))
 
     def pending_samples(self):

@@ -1427,11 +1427,58 @@ class SampleContainer:
             return occ[where].astype(np.int32)
         return occ[where, np.arange(self.shape[0])][0].astype(np.int32)
 
+    def _minimum_from_record(self, energy, discard, thin_by, flat):
+        """The minimum-occupancy getters of samples taken with keep_occupancy=False: answered from the per-walker minima
+        record the sampler kept on the device (``Sampler.from_ensemble(minima=)``), or None when it cannot answer.  The
+        record holds every walker's lowest sample, earliest first among equals: the flat argmin is its lowest entry."""
+        rec = self.minima
+        if rec is None or rec.spec.n_axes or discard != 0 or thin_by != 1 or rec.offers != self.num_samples:
+            return None
+        n = self._num_energy_coefs
+        same = energy and len(self.natural_parameters) == n
+        if rec.spec.weights is None:
+            if energy and not same:
+                return None
+        elif not (energy or same) or not np.array_equal(rec.spec.weights, self.natural_parameters[:n]):
+            return None
+        if not rec.filled.any():
+            return None
+        if not flat:
+            # (container.py:316-318 takes EVERY walker's occupancy at the sample where walker 0 was lowest: the
+            # companions the record keeps next to walker 0's entry)
+            return None if rec.companions is None or rec.sample[0] < 0 else rec.companions.astype(np.int32)
+        order = np.lexsort((rec.walker, rec.sample, np.where(rec.filled, rec.value, np.inf)))
+        return rec.occupancy[order[0]].astype(np.int32)
+
+    def _minimum_occupancy(self, energy, discard, thin_by, flat):
+        if any(len(b["occupancy"]) != len(b["enthalpy"]) for b in self._blocks):
+            occ = self._minimum_from_record(energy, discard, thin_by, flat)
+            if occ is not None:
+                return occ
+            raise ValueError("these samples were taken with keep_occupancy=False and no minima record answers this call: "
+                             "sample with Sampler.from_ensemble(minima=Minima.per_walker(...)) for the quantity asked for "
+                             "(discard=0, thin_by=1), or with keep_occupancy=True")
+        values = self.get_energies(discard, thin_by, flat) if energy else self.get_enthalpies(discard, thin_by, flat)
+        return self._argmin_occupancy(values, discard, thin_by, flat)
+
     def get_minimum_enthalpy_occupancy(self, discard=0, thin_by=1, flat=True):
-        return self._argmin_occupancy(self.get_enthalpies(discard, thin_by, flat), discard, thin_by, flat)
+        return self._minimum_occupancy(False, discard, thin_by, flat)
 
     def get_minimum_energy_occupancy(self, discard=0, thin_by=1, flat=True):
-        return self._argmin_occupancy(self.get_energies(discard, thin_by, flat), discard, thin_by, flat)
+        return self._minimum_occupancy(True, discard, thin_by, flat)
+
+    @property
+    def minima(self):
+        """The ``minima.MinimaRecord`` the sampler stored after its last run (None: sampled without ``minima=``)."""
+        d = self.metadata.get("minima")
+        if d is None:
+            return None
+        from .minima import MinimaRecord
+
+        return MinimaRecord.from_dict(d)
+
+    def set_minima(self, record):
+        self.metadata["minima"] = record.as_dict()
 
     # ---- compositions --------------------------------------------------------------------
     def get_sublattice_species_counts(self, sublattice, discard=0, thin_by=1, flat=True):
@@ -1540,6 +1587,17 @@ class SampleContainer:
             extra.update({"meta/obs_kind_base": np.asarray(obs["kind_base"], dtype=np.int32),
                           "meta/obs_site_ncodes": np.asarray(obs["site_ncodes"], dtype=np.int32),
                           "meta/obs_shape": np.asarray([obs["n_kinds"], obs["n_shells"], int(obs["default_kinds"])], dtype=np.int64)})
+        rec = self.minima
+        if rec is not None:  # the minima record: its arrays, the spec and the two counters
+            spec = rec.spec
+            extra.update({f"meta/minima_{f}": getattr(rec, f) for f in
+                          ("value", "enthalpy", "features", "occupancy", "counts", "walker", "sample", "step")})
+            if rec.companions is not None:
+                extra["meta/minima_companions"] = rec.companions
+            extra.update({"meta/minima_shape": np.asarray([rec.offers, rec.n_walkers, spec.n_weights, spec.n_axes], dtype=np.int64),
+                          "meta/minima_weights": np.zeros(0) if spec.weights is None else spec.weights,
+                          "meta/minima_axis_weights": spec.axis_weights, "meta/minima_bins": spec.bins,
+                          "meta/minima_extents": spec.extents})
         np.savez_compressed(path, nsamples=self.num_samples, total_mc_steps=self._total_steps,
                             **{f"trace/{k}": v for k, v in self._all().items()}, **extra)
 
@@ -1653,6 +1711,15 @@ class SampleContainer:
             c.metadata["observables"] = dict(n_kinds=K, n_shells=S, default_kinds=bool(default),
                                              kind_base=d["meta/obs_kind_base"].tolist(),
                                              site_ncodes=d["meta/obs_site_ncodes"].tolist())
+        if "meta/minima_shape" in d.files:
+            offers, nw, n_weights, n_axes = (int(x) for x in d["meta/minima_shape"])
+            rec = {f: d[f"meta/minima_{f}"] for f in ("value", "enthalpy", "features", "occupancy", "counts", "walker", "sample", "step")}
+            rec.update(offers=offers, n_walkers=nw,
+                       companions=d["meta/minima_companions"] if "meta/minima_companions" in d.files else None,
+                       spec=dict(weights=d["meta/minima_weights"].tolist() if n_weights else None,
+                                 axis_weights=d["meta/minima_axis_weights"].tolist() if n_axes else None,
+                                 bins=d["meta/minima_bins"].tolist(), extents=d["meta/minima_extents"].tolist()))
+            c.metadata["minima"] = rec
         if "meta/pop_anneal_temperatures" in d.files:
             c.metadata["population_annealing"] = dict(
                 temperatures=d["meta/pop_anneal_temperatures"].tolist(),
@@ -1786,11 +1853,13 @@ class Sampler:
         self._walker_mu_dirty = False  # ... not yet on the engine
         self._wl_windows = None     # replica-exchange Wang-Landau: the parallel.WLWindows of this sampler's walkers
         self._observables = None    # observables.Observables counted on the device for every sample, or None
+        self._minima = None         # minima.Minima: the lowest samples are kept on the device, or None
+        self._minima_offers = 0     # samples offered to the record since it was last emptied
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
                       nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, windows=None,
-                      observables=None, **kwargs):
+                      observables=None, minima=None, **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
         'swap'; default kernel Metropolis; one kernel (seed) per walker.
 
@@ -1800,14 +1869,20 @@ class Sampler:
         walker updates it), ``nwalkers`` defaults to ``windows.R``, and ``run_exchange`` samples with exchanges.
 
         ``observables``: an ``observables.Observables`` -- its kind counts and pair counts are evaluated on the device
-        for every sample and traced as ``species_counts`` (K,) and ``pair_counts`` (n_shells, K, K), int32."""
+        for every sample and traced as ``species_counts`` (K,) and ``pair_counts`` (n_shells, K, K), int32.
+
+        ``minima``: a ``minima.Minima`` -- every recorded sample is offered to a minima record kept on the device
+        (``Sampler.minima``); a record keyed by composition needs ``observables`` too."""
         from . import parallel
 
         if windows is not None and observables is not None:
             raise ValueError("observables= with windows=: the samples of per-walker windows do not come from the sample ring")
         if windows is not None:
-            return cls._from_ensemble_windows(ensemble, windows, *args, step_type=step_type, kernel_type=kernel_type, seeds=seeds,
-                                              nwalkers=nwalkers, rank=rank, world_size=world_size, device=device, **kwargs)
+            sampler = cls._from_ensemble_windows(ensemble, windows, *args, step_type=step_type, kernel_type=kernel_type, seeds=seeds,
+                                                 nwalkers=nwalkers, rank=rank, world_size=world_size, device=device, **kwargs)
+            if minima is not None:
+                sampler._set_minima(minima)
+            return sampler
 
         if step_type is None:
             step_type = "flip" if ensemble.chemical_potentials is not None else "swap"
@@ -1832,7 +1907,47 @@ class Sampler:
             sampler.set_chemical_potentials(chemical_potentials)
         if observables is not None:
             sampler._set_observables(observables)
+        if minima is not None:
+            sampler._set_minima(minima)
         return sampler
+
+    def _set_minima(self, spec):
+        if spec.n_axes and self._observables is None:
+            raise ValueError("a minima record keyed by composition needs a sampler built with observables=")
+        self._minima, self._minima_offers = spec, 0
+        if self._engine is not None:
+            self._engine.set_minima(spec)
+
+    @property
+    def minima(self):
+        """The minima record of this sampler's walkers (a ``minima.MinimaRecord``), merged over the ranks of a sharded
+        sampler: lowest value, then rank order (a per-walker record: the walkers of all ranks)."""
+        from . import parallel
+        from .minima import MinimaRecord
+
+        if self._minima is None:
+            raise ValueError("this sampler keeps no minima record: build it with Sampler.from_ensemble(minima=)")
+        rec = self._local_minima()
+        if self._world > 1 and parallel.is_initialized():
+            import torch.distributed as dist
+
+            parts = [None] * self._world
+            dist.all_gather_object(parts, rec)
+            rec = MinimaRecord.merge(parts)
+        return rec
+
+    def _local_minima(self):
+        """The record of this rank's walkers, as the handle holds it."""
+        rec = self._get_engine().minima()
+        rec.offers = self._minima_offers
+        return rec
+
+    def reset_minima(self):
+        """Empty the record; ``clear_samples`` leaves it alone."""
+        if self._minima is None:
+            raise ValueError("this sampler keeps no minima record: build it with Sampler.from_ensemble(minima=)")
+        self._get_engine().reset_minima()
+        self._minima_offers = 0
 
     def _set_observables(self, obs):
         """Trace ``obs`` with every sample: the container's schema gains the two traces, its metadata the kinds."""
@@ -2054,6 +2169,9 @@ class Sampler:
             self._engine = Engine(tables, cfg, distance=dist)
             if self._observables is not None:
                 self._engine.set_observables(self._observables)
+            if self._minima is not None:  # (a new handle starts an empty record)
+                self._engine.set_minima(self._minima)
+                self._minima_offers = 0
             if self._wl_windows is not None:  # (kernel e was built with estimator e's window: cfg holds window 0)
                 self._engine.set_wl_windows(self._wl_windows.vmin, self._wl_windows.vmax)
             self._engine_key = key
@@ -2158,6 +2276,7 @@ class Sampler:
                 raise ValueError("a callable mod_update with per-walker windows: the host-side check is walker-indexed")
             for _ in range(nsamples):
                 self._wl_run_with_host_checks(eng, thin_by)
+                self._offer_current(eng)
                 yield {k: v[None] for k, v in self._current_trace(eng).items()}
             return
         if is_wl and self._wl_windows is not None:
@@ -2167,6 +2286,7 @@ class Sampler:
             # estimator every walker holds
             for _ in range(nsamples):
                 eng.run(thin_by)
+                self._offer_current(eng)
                 tr = {k: v[None] for k, v in self._current_trace(eng).items()}
                 tr["wl_estimator"] = eng.wl_windows()[2].reshape(1, -1, 1)
                 yield tr
@@ -2193,7 +2313,10 @@ class Sampler:
         sizes = [min(per_block, nsamples - start) for start in range(0, nsamples, per_block)]
 
         def queue(n):
-            eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl, observables=obs is not None)
+            eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl, observables=obs is not None,
+                                  minima=self._minima is not None)
+            if self._minima is not None:
+                self._minima_offers += n
 
         # Block i + 1 is queued before block i is handed out, so a consumer that stops early -- a `break` out of
         # Sampler.sample(), an exception in run() between two blocks -- leaves a block on the (cached) engine's ring.
@@ -2204,6 +2327,12 @@ class Sampler:
             yield from self._ring_blocks(eng, sizes, queue, temps, nw, k0, has_bias, is_wl)
         finally:
             eng.discard_samples()
+
+    def _offer_current(self, eng):
+        """The host-stepped paths offer the walkers' states themselves, so the record means the same on every path."""
+        if self._minima is not None:
+            eng.update_minima()
+            self._minima_offers += 1
 
     @staticmethod
     def _ring_blocks(eng, sizes, queue, temps, nw, k0, has_bias, is_wl):
@@ -2307,8 +2436,8 @@ class Sampler:
         leave the device -- their species and pair counts do; the container stores the occupancy of the final
         sample of this call alone, so ``last_occupancy`` and a continuation work as before."""
         if not keep_occupancy:
-            if self._observables is None:
-                raise ValueError("keep_occupancy=False needs a sampler built with observables=: nothing else of the "
+            if self._observables is None and self._minima is None:
+                raise ValueError("keep_occupancy=False needs a sampler built with observables= or minima=: nothing else of the "
                                  "occupancies would be recorded")
             if stream_chunk > 0:
                 raise ValueError("keep_occupancy=False with stream_chunk: every part of a stream holds its occupancies")
@@ -2347,6 +2476,8 @@ class Sampler:
                 self._kept_last = True
         if not keep_occupancy and recorded:  # (the walkers' current states ARE the final sample)
             self.samples.set_last_occupancy(self._get_engine().get_state()["occupancy"])
+        if self._minima is not None:  # (this rank's walkers, like everything else in its container)
+            self.samples.set_minima(self._local_minima())
         # the device now holds the last recorded sample (see _load_state)
         self._resume_at = (id(self.samples), self.samples.num_samples)
 
