@@ -380,6 +380,7 @@ int smolmc_sync(smolmc_handle *h);
 #define SMOLMC_SAMPLE_WL 4        /* flags bit 2: the Wang-Landau trace (error on a Metropolis handle) */
 #define SMOLMC_SAMPLE_OBSERVABLES 8 /* flags bit 3: kind and pair counts of every row (see smolmc_set_observables) */
 #define SMOLMC_SAMPLE_MINIMA 16     /* flags bit 4: offer every row to the minima record (see smolmc_set_minima) */
+#define SMOLMC_SAMPLE_STATISTICS 32 /* flags bit 5: offer every row to the statistics record (see smolmc_set_statistics) */
 int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t thin_by, int flags);
 /* The ring as the next smolmc_get_samples* call sees it (ABI 8): *n_pending = blocks queued and not fetched
  * (0..2), *nsamples / *flags = sample count and SMOLMC_SAMPLE_* flags of the block that call would deliver
@@ -492,6 +493,58 @@ int smolmc_get_minima(smolmc_handle *h, double *value, double *enthalpy, double 
  * reference's get_minimum_*_occupancy(flat=False) returns (sampler/container.py:316-318: every walker's occupancy at the
  * sample where walker 0 was lowest).  Refused on a record keyed by composition.  Waits for the handle's stream. */
 int smolmc_get_minima_companions(smolmc_handle *h, int32_t *occ);
+/* ---- statistics: running moments, blocking sums and a histogram of the samples, kept on the device -----------------
+ * A statistics record is a set of accumulators per KEY that lives as long as the handle.  Every recorded sample is
+ * OFFERED to it: each sample of a block recorded with SMOLMC_SAMPLE_STATISTICS is one offer, each
+ * smolmc_update_statistics call is one.  One offer gives every key exactly one row of C column values x[C] (both key
+ * modes are permutations of the walkers), and the key's accumulators take it in launch order:
+ *   if n == 0: shift[c] = x[c]                       (the key's first offered value)
+ *   d[c] = x[c] - shift[c];  s1[c] += d[c];  s2[a,b] += d[a] * d[b] for a <= b   (upper triangle, row-major)
+ *   blocking (Flyvbjerg & Petersen 1989), per column c:  carry = d[c]; for l = 0 .. n_levels - 1:
+ *       b2[l,c] += carry * carry; nb[l] += 1 (once per level);
+ *       bit l of has[c] clear: pend[l,c] = carry, set the bit, stop;   else carry = pend[l,c] + carry, clear the bit
+ *   histogram of column hist_column: q = floor((x - hist_min) / hist_bin), the exact floor division of the Wang-Landau
+ *       step; q < 0 counts in under, q >= n_bins or x not finite in over, else hist[q] += 1
+ *   n += 1
+ * Every product and every sum is rounded on its own (no fused multiply-add): smol_amd/statistics.py is the same in NumPy
+ * and the device matches it entry for entry.  smolmc_set_state and smolmc_discard_samples leave the record alone. */
+#define SMOLMC_STAT_BY_WALKER 0      /* n_keys = R, the key is the walker */
+#define SMOLMC_STAT_BY_STATE_POINT 1 /* n_keys = R, the key is the state point the walker holds when the reduction runs
+                                      * on the handle's stream (the identity while smolmc_exchange_grid has never run) */
+#define SMOLMC_MAX_STAT_COLUMNS 32
+#define SMOLMC_MAX_STAT_LEVELS 32
+#define SMOLMC_MAX_STAT_BINS 65536
+typedef struct smolmc_statistics {
+    int key;                /* SMOLMC_STAT_BY_WALKER or SMOLMC_STAT_BY_STATE_POINT */
+    int n_columns;          /* C, 1..32 */
+    const int32_t *columns; /* [C] sources, no duplicates: 0 the enthalpy, 1 + i feature i (i < F), 1 + F + k kind count k
+                             * of the observables in force (k < K, as a double), 1 + F + K the weighted sum below */
+    int n_weights;          /* the weighted sum: sum_{i < n_weights} weights[i] * features[i] left to right, the value of */
+    const double *weights;  /* a minima record (n_weights <= F) */
+    int n_levels;           /* blocking levels, 0..32 */
+    int hist_column;        /* an index into columns */
+    int n_bins;             /* 0: no histogram, else 1..65536 */
+    double hist_min, hist_bin; /* hist_bin > 0 */
+} smolmc_statistics;
+/* Sets the record (NULL: removes it); a new spec starts an empty record.  Refused, each naming its reason and leaving
+ * the handle as it was: a key other than the two; SMOLMC_STAT_BY_STATE_POINT on a Wang-Landau handle with per-walker
+ * windows; C outside 1..32, a source out of range or named twice; a count column without observables; n_weights > F;
+ * n_levels outside 0..32; n_bins outside 0..65536, hist_bin not a positive finite number, hist_column outside the
+ * columns; a record of more than 1 GiB.  While a record with count columns is set, smolmc_set_observables is refused.
+ * Waits for the handle's stream, like smolmc_reset_statistics and smolmc_get_statistics. */
+int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *s);
+/* the shape in force (all 0: none set) */
+int smolmc_statistics_shape(smolmc_handle *h, int *n_keys, int *n_columns, int *n_levels, int *n_bins);
+/* Offers the walkers' CURRENT states, one offer (for callers of smolmc_run); with count columns the kinds of the current
+ * states are counted on the device first. */
+int smolmc_update_statistics(smolmc_handle *h);
+/* Empties the record. */
+int smolmc_reset_statistics(smolmc_handle *h);
+/* The record: n, under, over [n_keys]; shift, s1 [n_keys x C]; s2 [n_keys x C (C + 1) / 2]; has [n_keys x C] (bit l:
+ * pend[l, c] holds a pending block); pend, b2 [n_keys x n_levels x C]; nb [n_keys x n_levels]; hist [n_keys x n_bins].
+ * Any pointer may be NULL. */
+int smolmc_get_statistics(smolmc_handle *h, int64_t *n, double *shift, double *s1, double *s2, uint64_t *has, double *pend,
+                          double *b2, int64_t *nb, int64_t *hist, int64_t *under, int64_t *over);
 
 /* Same loop driven by host-provided proposals ("replay mode"): what
  * StandardSingleStepMixin.single_step (kernel/base.py:145-166) does after mcusher.propose_step

@@ -30,6 +30,7 @@ SAMPLE_OBSERVABLES = 8          # ... kind and pair counts of every row (smolmc_
 MAX_OBS_CELLS = 4096            # SMOLMC_MAX_OBS_CELLS
 SAMPLE_MINIMA = 16              # ... every row is offered to the minima record (smolmc_set_minima)
 MAX_MINIMA_AXES = 4             # SMOLMC_MAX_MINIMA_AXES
+SAMPLE_STATISTICS = 32          # ... every row is offered to the statistics record (smolmc_set_statistics)
 MAX_STEP_FLIPS = 8              # SMOLMC_MAX_STEP_FLIPS
 STEP_ROW = 2 * MAX_STEP_FLIPS   # SMOLMC_STEP_ROW: int32 per step record (site, code) x 8, -1 = no flip
 
@@ -143,6 +144,23 @@ class smolmc_minima(C.Structure):
         ("axis_weights", _i32p),
         ("axis_bin", _i32p),
         ("axis_extent", _i32p),
+    ]
+
+
+class smolmc_statistics(C.Structure):
+    """Mirror of ``smolmc_statistics`` (include/smolmc.h); ``statistics.Statistics.c_struct`` fills it."""
+
+    _fields_ = [
+        ("key", C.c_int),
+        ("n_columns", C.c_int),
+        ("columns", _i32p),
+        ("n_weights", C.c_int),
+        ("weights", _f64p),
+        ("n_levels", C.c_int),
+        ("hist_column", C.c_int),
+        ("n_bins", C.c_int),
+        ("hist_min", C.c_double),
+        ("hist_bin", C.c_double),
     ]
 
 

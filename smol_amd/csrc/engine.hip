@@ -2370,6 +2370,7 @@ extern "C" int smolmc_destroy(smolmc_handle *h) {
     if (h->obs_ev0) hipEventDestroy(h->obs_ev0);
     if (h->obs_ev1) hipEventDestroy(h->obs_ev1);
     smolmc_min_free(h);
+    smolmc_stat_free(h);
     free_samples(h);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -3328,6 +3329,9 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
         return fail("SMOLMC_SAMPLE_OBSERVABLES without observables: call smolmc_set_observables first");
     const bool minima = (flags & SMOLMC_SAMPLE_MINIMA) != 0;
     if (minima && !h->minima.n_slots) return fail("SMOLMC_SAMPLE_MINIMA without a minima record: call smolmc_set_minima first");
+    const bool stats = (flags & SMOLMC_SAMPLE_STATISTICS) != 0;
+    if (stats && !h->stats.n_keys)
+        return fail("SMOLMC_SAMPLE_STATISTICS without a statistics record: call smolmc_set_statistics first");
     if ((flags & SMOLMC_SAMPLE_WL) && !h->wl_win_min.empty())
         return fail("SMOLMC_SAMPLE_WL while per-walker windows are set: the snapshot rows are walker-indexed, the Wang-Landau arrays estimator-indexed (smolmc_get_wl between runs, or smolmc_set_wl_windows(h, NULL, NULL) first)");
     if (thin_by > ((int64_t)1 << 30) && h->lean() && !smolmc_env(ENV_LAUNCH_CHUNK))
@@ -3386,7 +3390,9 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     // (... and so do the occupancy rows the observables are counted from)
     // (... and the rows offered to the minima record, with their kind counts and the two scratch columns of the reduction)
     const bool min_counts = minima && h->obs.K && h->obs.K == h->minima.K; // (a keyed record: always, see smolmc_set_observables)
-    if ((lazy_rows || obs || minima) && !(flags & SMOLMC_SAMPLE_OCCUPANCY)) o_occ_int = take(rows * h->Npad);
+    // (... and the rows whose kinds a statistics record with count columns reads)
+    const bool stat_counts = stats && h->stats.n_count_cols > 0; // (then obs.K == stats.K, see smolmc_set_observables)
+    if ((lazy_rows || obs || minima || stat_counts) && !(flags & SMOLMC_SAMPLE_OCCUPANCY)) o_occ_int = take(rows * h->Npad);
     size_t o_min_cnt = w.o_cnt, o_min_key = 0, o_min_slot = 0;
     if (minima) {
         if (min_counts && !obs) o_min_cnt = take(rows * (size_t)h->obs.K * 4);
@@ -3394,6 +3400,11 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
         o_min_slot = take(rows * 4);
         if (rows > 0x7fffffffull) return fail("minima: more than 2^31 sample rows in one block");
     }
+    // the statistics record reads the observables' count column, the minima record's hidden one, or one of its own
+    const bool stat_own_counts = stat_counts && !obs && !(min_counts);
+    size_t o_stat_cnt = obs ? w.o_cnt : o_min_cnt;
+    if (stat_own_counts) o_stat_cnt = take(rows * (size_t)h->obs.K * 4);
+    if (stats && rows > 0x7fffffffull) return fail("statistics: more than 2^31 sample rows in one block");
     if (lazy_rows && rows > 0x7fffffffull) return fail("lazy cluster features: more than 2^31 sample rows in one block");
     if (obs && rows > 0x7fffffffull) return fail("observables: more than 2^31 sample rows in one block");
     // the slot's previous block (delivered, or none) must have left the device before its arenas are reused
@@ -3423,7 +3434,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     smp.H = (double *)(sl.d + w.o_H);
     smp.feat = (double *)(sl.d + (lazy_rows ? o_scal : w.o_feat));
     smp.acc = sl.d + w.o_acc;
-    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs || minima ? sl.d + o_occ_int : nullptr;
+    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs || minima || stat_counts ? sl.d + o_occ_int : nullptr;
     if (!snapshot_path) {
         if (inkernel_bias) {
             if ((w.o_bias - w.o_H) / 8 > 0xffffffffull) return fail("sample block too large for the in-kernel bias column");
@@ -3466,6 +3477,11 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
         TRY(smolmc_min_launch(h, (const double *)(sl.d + w.o_H), (const double *)(sl.d + w.o_feat), sl.d + o_occ_int,
                               min_counts ? (const int32_t *)(sl.d + o_min_cnt) : nullptr, (uint64_t *)(sl.d + o_min_key),
                               (int32_t *)(sl.d + o_min_slot), nsamples, thin_by));
+    }
+    if (stats) {
+        if (stat_own_counts) TRY(smolmc_obs_launch(h, sl.d + o_occ_int, rows, (int32_t *)(sl.d + o_stat_cnt), nullptr));
+        TRY(smolmc_stat_launch(h, (const double *)(sl.d + w.o_H), (const double *)(sl.d + w.o_feat),
+                               stat_counts ? (const int32_t *)(sl.d + o_stat_cnt) : nullptr, nsamples));
     }
     // download on the copy stream as soon as the block is complete; the next block's launches do not wait for it
     // (the mirror is about to be overwritten: from here the slot no longer holds its old block)
@@ -3800,6 +3816,9 @@ extern "C" int smolmc_set_observables(smolmc_handle *h, const smolmc_observables
     if (h->minima.n_slots && h->minima.n_axes)
         return fail("smolmc_set_observables while a minima record keyed by composition depends on the observables (call "
                     "smolmc_set_minima(h, NULL) first)");
+    if (h->stats.n_keys && h->stats.n_count_cols)
+        return fail("smolmc_set_observables while a statistics record with count columns depends on the observables (call "
+                    "smolmc_set_statistics(h, NULL) first)");
     if (obs) {
         const int N = h->N, K = obs->n_kinds, S = obs->n_shells;
         if (!obs->kind_base || S < 0 || (S > 0 && (!obs->shell_ptr || !obs->bonds))) return fail("observables: null argument");
@@ -3930,6 +3949,18 @@ extern "C" int smolmc_update_minima(smolmc_handle *h) {
     const bool counts = h->obs.K && h->obs.K == M.K;
     if (counts) TRY(smolmc_obs_launch(h, h->kp.occ, (size_t)h->R, M.u_counts, nullptr));
     return smolmc_min_launch(h, h->kp.enthalpy, h->kp.features, h->kp.occ, counts ? M.u_counts : nullptr, M.u_key, M.u_slot, 1, 1);
+}
+
+// one offer of the walkers' current states to the statistics record (statistics.hip), as smolmc_update_minima
+extern "C" int smolmc_update_statistics(smolmc_handle *h) {
+    if (!h) return fail("null handle");
+    SmolmcStat &S = h->stats;
+    if (!S.n_keys) return fail("no statistics record set: call smolmc_set_statistics first");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(ensure_features(h));
+    const bool counts = S.n_count_cols > 0;
+    if (counts) TRY(smolmc_obs_launch(h, h->kp.occ, (size_t)h->R, S.u_counts, nullptr));
+    return smolmc_stat_launch(h, h->kp.enthalpy, h->kp.features, counts ? S.u_counts : nullptr, 1);
 }
 
 extern "C" int smolmc_get_sample_observables(smolmc_handle *h, int32_t *counts, int32_t *pairs) {

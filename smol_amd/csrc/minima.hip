@@ -70,12 +70,7 @@ __global__ void __launch_bounds__(MIN_THREADS) minima_rows_kernel(const MinArgs 
         if (A.n_weights == 0) {
             v = A.H[i];
         } else {
-            const double *f = A.feat + (size_t)i * A.F;
-            v = 0.0;
-            for (int j = 0; j < A.n_weights; ++j) {
-                const double p = A.weights[j] * f[j];
-                v = v + p;
-            }
+            v = weighted_value_rn(A.weights, A.feat + (size_t)i * A.F, A.n_weights);
         }
         v = v + 0.0; // (-0.0 -> +0.0)
         if (v == v) key = min_ordered(v);

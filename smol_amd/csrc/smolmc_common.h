@@ -262,6 +262,19 @@ __device__ __forceinline__ double uni_d(double v) {
     return __hiloint2double(hi, lo);
 }
 
+// sum_{i < n} w[i] * f[i] left to right, every product and every sum rounded on its own: the value of a minima record
+// and the weighted column of a statistics record (minima.weighted_value is the same in NumPy).  __dmul_rn / __dadd_rn do
+// not say that to this compiler (they came out as one v_fmac_f64); the pragma does.
+__device__ __forceinline__ double weighted_value_rn(const double *w, const double *f, int n) {
+#pragma clang fp contract(off)
+    double v = 0.0;
+    for (int j = 0; j < n; ++j) {
+        const double p = w[j] * f[j];
+        v = v + p;
+    }
+    return v;
+}
+
 // exact floor(x / y), y > 0 : Python's float // (wanglandau.py:180)
 __device__ __forceinline__ double floordiv_exact(double x, double y) {
     double q = floor(x / y);
@@ -801,6 +814,25 @@ struct SmolmcMin {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the three passes of the last reduction
 };
 
+// statistics.hip: the statistics record of a handle (smolmc_set_statistics): the spec and one device arena cut into the
+// accumulator arrays [n_keys (x ...)], the spec's arrays and the per-row scratch of smolmc_update_statistics
+struct SmolmcStat {
+    int n_keys = 0;            // (0: none set)
+    int key = 0, C = 0, L = 0, n_bins = 0, hist_column = 0, n_weights = 0;
+    int K = 0;                 // the kinds of the observables in force when the record was set
+    int n_count_cols = 0;      // columns that read the kind counts
+    double hist_min = 0.0, hist_bin = 1.0;
+    unsigned char *arena = nullptr;
+    size_t record_bytes = 0;   // from n to the end of the accumulator arrays: what a reset zeroes
+    long long *n = nullptr, *nb = nullptr, *hist = nullptr, *under = nullptr, *over = nullptr;
+    double *shift = nullptr, *s1 = nullptr, *s2 = nullptr, *pend = nullptr, *b2 = nullptr;
+    uint64_t *has = nullptr;
+    int32_t *columns = nullptr;
+    double *weights = nullptr;
+    int32_t *u_counts = nullptr; // smolmc_update_statistics: counts [R x K]
+    hipEvent_t ev[2] = {nullptr, nullptr}; // around the last reduction
+};
+
 struct smolmc_handle {
     smolmc_config cfg;
     int device = 0;
@@ -883,6 +915,8 @@ struct smolmc_handle {
     hipEvent_t obs_ev0 = nullptr, obs_ev1 = nullptr; // around the last launch of the observables kernel (created at the first)
     // the lowest recorded states (smolmc_set_minima; minima.hip)
     SmolmcMin minima;
+    // running moments, blocking sums and a histogram of the samples (smolmc_set_statistics; statistics.hip)
+    SmolmcStat stats;
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
     SampleSlot slots[2];
@@ -1006,6 +1040,11 @@ int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int3
 int smolmc_min_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const uint8_t *d_occ8, const int32_t *d_counts,
                       uint64_t *d_key, int32_t *d_slot, long long nsamples, long long thin_by);
 void smolmc_min_free(smolmc_handle *h);
+// statistics.hip: offer `nsamples` samples of R rows each (enthalpy [rows], features [rows x F], counts [rows x K] or
+// null; device) to the handle's record, one kernel queued on the handle's stream: a workgroup per key walks the samples in
+// order.  Sample s gives key k the row s * R + w, w the walker that holds k when the kernel runs.
+int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, long long nsamples);
+void smolmc_stat_free(smolmc_handle *h);
 size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies);
 int smolmc_obs_pair_copies(size_t cells);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);

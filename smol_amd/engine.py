@@ -66,6 +66,11 @@ SYMBOLS = {
     "smolmc_reset_minima": (C.c_int, [_HP]),
     "smolmc_get_minima": (C.c_int, [_HP, _f64p, _f64p, _f64p, _i32p, _i32p, _i32p, _i64p, _u64p]),
     "smolmc_get_minima_companions": (C.c_int, [_HP, _i32p]),
+    "smolmc_set_statistics": (C.c_int, [_HP, C.POINTER(capi.smolmc_statistics)]),
+    "smolmc_statistics_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 4),
+    "smolmc_update_statistics": (C.c_int, [_HP]),
+    "smolmc_reset_statistics": (C.c_int, [_HP]),
+    "smolmc_get_statistics": (C.c_int, [_HP, _i64p, _f64p, _f64p, _f64p, _u64p, _f64p, _f64p, _i64p, _i64p, _i64p, _i64p]),
     "smolmc_replay": (C.c_int, [_HP, C.c_int64, _i32p, _f64p, _f64p, _u8p, _f64p, _f64p]),
     "smolmc_last_kernel_ms": (C.c_int, [_HP, C.POINTER(C.c_float)]),
     "smolmc_eval_full": (C.c_int, [_HP, _i32p, C.c_int, _f64p]),
@@ -195,6 +200,7 @@ class Engine:
         self.L = self._lib.smolmc_wl_num_levels(self._h)
         self.walker_mu_set = False  # per-walker chemical potentials in force (set_walker_mu)
         self.minima_spec = None     # the spec of the minima record in force (set_minima)
+        self.statistics_spec = None  # the spec of the statistics record in force (set_statistics)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -599,28 +605,82 @@ class Engine:
         self._chk(fn(self._h, ms))
         return [float(x) for x in ms]
 
+    # ---- statistics: running moments, blocking sums and a histogram, kept on the device -----
+    def set_statistics(self, spec):
+        """The statistics record of this handle (smolmc_set_statistics): a ``statistics.Statistics``, or None to remove
+        it.  A new spec starts an empty record.  The record lives as long as the handle: ``set_state`` and
+        ``discard_samples`` leave it alone."""
+        if spec is None:
+            self._chk(self._lib.smolmc_set_statistics(self._h, None))
+        else:
+            struct, keep = spec.c_struct(self.F, self.observables_shape()[0])
+            self._chk(self._lib.smolmc_set_statistics(self._h, C.byref(struct)))
+            del keep
+        self.statistics_spec = spec
+
+    def statistics_shape(self):
+        """(n_keys, n_columns, n_levels, n_bins) in force, zeros when no record is set (smolmc_statistics_shape)."""
+        v = [C.c_int() for _ in range(4)]
+        self._chk(self._lib.smolmc_statistics_shape(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def update_statistics(self):
+        """Offer the walkers' current states to the record, one offer (smolmc_update_statistics): for callers of ``run``."""
+        self._chk(self._lib.smolmc_update_statistics(self._h))
+
+    def reset_statistics(self):
+        """Empty the record (smolmc_reset_statistics)."""
+        self._chk(self._lib.smolmc_reset_statistics(self._h))
+
+    def statistics(self):
+        """The record as a ``statistics.StatisticsRecord`` (smolmc_get_statistics; waits for the handle's stream)."""
+        from .statistics import StatisticsRecord
+
+        if self.statistics_spec is None:
+            raise EngineError("no statistics record set: call set_statistics first")
+        rec = StatisticsRecord(self.statistics_spec, self.R)
+        shape = self.statistics_shape()
+        want = (rec.n_keys, rec.spec.n_columns, rec.spec.n_levels, rec.spec.n_bins)
+        if shape != want:
+            raise EngineError(f"the handle's record has shape {shape}, the spec gives {want}")
+        self._chk(self._lib.smolmc_get_statistics(
+            self._h, _p(rec.n, C.c_int64), _p(rec.shift, C.c_double), _p(rec.s1, C.c_double), _p(rec.s2, C.c_double),
+            _p(rec.has, C.c_uint64), _p(rec.pend, C.c_double), _p(rec.b2, C.c_double), _p(rec.nb, C.c_int64),
+            _p(rec.hist, C.c_int64), _p(rec.under, C.c_int64), _p(rec.over, C.c_int64)))
+        return rec
+
+    def statistics_kernel_ms(self):
+        """Device time of the last statistics reduction in ms (HIP events; a measuring hook of the library, not part of
+        the C-ABI)."""
+        fn = self._lib.smolmc_debug_statistics_kernel_ms
+        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
+        ms = C.c_float()
+        self._chk(fn(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False,
-                    minima=False):
+                    minima=False, statistics=False):
         """Advance nsamples*thin_by steps recording one sample per walker every thin_by steps
         on the device; returns dict(enthalpy (ns,R), features (ns,R,F), accepted (ns,R) bool,
         occupancy (ns,R,N) or None[, bias (ns,R)][, the Wang-Landau trace][, species_counts, pair_counts]).
         Occupancies come back as int32 (the reference's trace dtype) or, with ``packed``, as the ring's own
         uint8 -- a quarter of the transfer.  = ``run_sampled_async`` + ``fetch_samples``."""
         self.run_sampled_async(nsamples, thin_by, occupancy=occupancy, bias=bias, wl=wl, observables=observables,
-                               minima=minima)
+                               minima=minima, statistics=statistics)
         return self.fetch_samples(packed=packed)
 
-    def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False, observables=False, minima=False):
+    def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False, observables=False, minima=False,
+                          statistics=False):
         """Queue one block of the device ring (smolmc_run_sampled): returns at once.  The ring has two
         slots; queue block k + 1 BEFORE fetching block k and the download of k overlaps the kernel of
         k + 1 (the order ``fetch_samples`` delivers in: oldest first).  ``observables``: the kind and pair
         counts of ``set_observables`` for every row, counted on the device; with ``occupancy=False`` the
         occupancy rows they are counted from never leave it.  ``minima``: every row is offered to the record of
         ``set_minima`` when the block's launches are through; what the reduction reads and the caller did not ask for
-        stays on the device."""
+        stays on the device.  ``statistics``: likewise every row is offered to the record of ``set_statistics``."""
         flags = ((capi.SAMPLE_OCCUPANCY if occupancy else 0) | (capi.SAMPLE_BIAS if bias else 0) |
                  (capi.SAMPLE_WL if wl else 0) | (capi.SAMPLE_OBSERVABLES if observables else 0) |
-                 (capi.SAMPLE_MINIMA if minima else 0))
+                 (capi.SAMPLE_MINIMA if minima else 0) | (capi.SAMPLE_STATISTICS if statistics else 0))
         self._chk(self._lib.smolmc_run_sampled(self._h, int(nsamples), int(thin_by), flags))
 
     def pending_samples(self):

@@ -1855,11 +1855,12 @@ class Sampler:
         self._observables = None    # observables.Observables counted on the device for every sample, or None
         self._minima = None         # minima.Minima: the lowest samples are kept on the device, or None
         self._minima_offers = 0     # samples offered to the record since it was last emptied
+        self._statistics = None     # statistics.Statistics: moments, blocking sums and a histogram kept on the device, or None
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
                       nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, windows=None,
-                      observables=None, minima=None, **kwargs):
+                      observables=None, minima=None, statistics=None, **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
         'swap'; default kernel Metropolis; one kernel (seed) per walker.
 
@@ -1872,7 +1873,11 @@ class Sampler:
         for every sample and traced as ``species_counts`` (K,) and ``pair_counts`` (n_shells, K, K), int32.
 
         ``minima``: a ``minima.Minima`` -- every recorded sample is offered to a minima record kept on the device
-        (``Sampler.minima``); a record keyed by composition needs ``observables`` too."""
+        (``Sampler.minima``); a record keyed by composition needs ``observables`` too.
+
+        ``statistics``: a ``statistics.Statistics`` -- every recorded sample is offered to a statistics record kept on the
+        device (``Sampler.statistics``): running moments, blocking sums and a histogram per walker or per state point,
+        whether the trace is kept or not; count columns need ``observables`` too."""
         from . import parallel
 
         if windows is not None and observables is not None:
@@ -1882,6 +1887,8 @@ class Sampler:
                                                  nwalkers=nwalkers, rank=rank, world_size=world_size, device=device, **kwargs)
             if minima is not None:
                 sampler._set_minima(minima)
+            if statistics is not None:
+                sampler._set_statistics(statistics)
             return sampler
 
         if step_type is None:
@@ -1909,7 +1916,31 @@ class Sampler:
             sampler._set_observables(observables)
         if minima is not None:
             sampler._set_minima(minima)
+        if statistics is not None:
+            sampler._set_statistics(statistics)
         return sampler
+
+    def _set_statistics(self, spec):
+        if spec.count_columns() and self._observables is None:
+            raise ValueError("a statistics record with count columns needs a sampler built with observables=")
+        self._statistics = spec
+        if self._engine is not None:
+            self._engine.set_statistics(spec)
+
+    @property
+    def statistics(self):
+        """The statistics record of THIS rank's walkers (a ``statistics.StatisticsRecord``) as the handle holds it.  The
+        ranks of a sharded sampler hold different walkers: their records stand side by side, they are not merged
+        (``StatisticsRecord.combine`` merges records of the same keys)."""
+        if self._statistics is None:
+            raise ValueError("this sampler keeps no statistics record: build it with Sampler.from_ensemble(statistics=)")
+        return self._get_engine().statistics()
+
+    def reset_statistics(self):
+        """Empty the record; ``clear_samples`` leaves it alone."""
+        if self._statistics is None:
+            raise ValueError("this sampler keeps no statistics record: build it with Sampler.from_ensemble(statistics=)")
+        self._get_engine().reset_statistics()
 
     def _set_minima(self, spec):
         if spec.n_axes and self._observables is None:
@@ -2172,6 +2203,8 @@ class Sampler:
             if self._minima is not None:  # (a new handle starts an empty record)
                 self._engine.set_minima(self._minima)
                 self._minima_offers = 0
+            if self._statistics is not None:  # (likewise)
+                self._engine.set_statistics(self._statistics)
             if self._wl_windows is not None:  # (kernel e was built with estimator e's window: cfg holds window 0)
                 self._engine.set_wl_windows(self._wl_windows.vmin, self._wl_windows.vmax)
             self._engine_key = key
@@ -2314,7 +2347,7 @@ class Sampler:
 
         def queue(n):
             eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl, observables=obs is not None,
-                                  minima=self._minima is not None)
+                                  minima=self._minima is not None, statistics=self._statistics is not None)
             if self._minima is not None:
                 self._minima_offers += n
 
@@ -2333,6 +2366,8 @@ class Sampler:
         if self._minima is not None:
             eng.update_minima()
             self._minima_offers += 1
+        if self._statistics is not None:
+            eng.update_statistics()
 
     @staticmethod
     def _ring_blocks(eng, sizes, queue, temps, nw, k0, has_bias, is_wl):

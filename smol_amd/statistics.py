@@ -1,0 +1,388 @@
+"""Running moments, blocking sums and a histogram of the recorded samples, per walker or per state point.
+
+This module is the DEFINITION: ``StatisticsRecord.offer`` in NumPy is what the device reduction (csrc/statistics.hip,
+``SMOLMC_SAMPLE_STATISTICS`` and ``smolmc_update_statistics``) matches entry for entry.
+
+A *statistics record* holds accumulators for ``n_keys = R`` keys.  One offer is one sample of all walkers; it gives each
+key exactly one row of ``C`` column values ``x`` (the key of a row is its walker, or the state point the walker holds:
+both are permutations), and the key's accumulators take the rows in order:
+
+    if n == 0: shift[c] = x[c]                      the key's first offered value
+    d[c] = x[c] - shift[c]
+    s1[c] += d[c]
+    s2[a,b] += d[a] * d[b]     for a <= b           upper triangle, row-major, C (C + 1) / 2 entries
+    blocking (Flyvbjerg & Petersen 1989), per column c, levels l = 0 .. n_levels - 1:
+        carry = d[c]
+        for l: b2[l,c] += carry * carry; nb[l] += 1 (once per level, not per column)
+               bit l of has[c] clear: pend[l,c] = carry, set the bit, stop
+               else carry = pend[l,c] + carry, clear the bit
+    histogram of column hist_column:
+        q = floor_divide(x - hist_min, hist_bin); under += q < 0; over += q >= n_bins or x not finite; else hist[q] += 1
+    n += 1
+
+Every product and every sum is rounded on its own.  ``b2[l]`` is the sum of squares of the block SUMS of 2^l consecutive
+samples (of d), ``nb[l]`` the number of complete blocks; ``pend[l]`` a block of 2^l samples that waits for its partner.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .minima import weighted_value
+
+BY_WALKER, BY_STATE_POINT = 0, 1   # SMOLMC_STAT_BY_WALKER, SMOLMC_STAT_BY_STATE_POINT
+MAX_COLUMNS = 32                   # SMOLMC_MAX_STAT_COLUMNS
+MAX_LEVELS = 32                    # SMOLMC_MAX_STAT_LEVELS
+MAX_BINS = 65536                   # SMOLMC_MAX_STAT_BINS
+KB = 8.617333262145e-5             # eV / K, SMOLMC_KB (smol/constants.py:4)
+
+_ARRAYS = ("n", "shift", "s1", "s2", "has", "pend", "b2", "nb", "hist", "under", "over")
+
+# ---- column sources: symbolic, resolved against a handle's (F, K) by Statistics.sources -------------------------------
+ENTHALPY = ("enthalpy",)
+ENERGY = ("energy",)       # the weighted sum of the features (``weights``): the energy of a semigrand run
+
+
+def feature(i):
+    return ("feature", int(i))
+
+
+def kind(observables, name_or_k):
+    """Count column of kind ``name_or_k`` of ``observables`` (an ``observables.Observables``): a kind number, or a name
+    looked up in ``observables.kind_names`` when it has them."""
+    if isinstance(name_or_k, (int, np.integer)):
+        k = int(name_or_k)
+    else:
+        names = [str(x) for x in getattr(observables, "kind_names", None) or []]
+        if str(name_or_k) not in names:
+            raise ValueError(f"no kind named {name_or_k!r} among {names}")
+        k = names.index(str(name_or_k))
+    K = int(getattr(observables, "n_kinds", observables))
+    if not 0 <= k < K:
+        raise ValueError(f"kind {k} outside 0..{K - 1}")
+    return ("kind", k)
+
+
+class Statistics:
+    """The spec of a record: how it is keyed, its columns, the weights of the ENERGY column, the blocking levels and the
+    histogram (``hist=(column, n_bins, hist_min, hist_bin)`` with ``column`` one of ``columns``)."""
+
+    def __init__(self, key=BY_WALKER, columns=(ENTHALPY,), weights=None, n_levels=0, hist=None):
+        self.key = int(key)
+        self.columns = [tuple(c) if not isinstance(c, (int, np.integer)) else ("source", int(c)) for c in columns]
+        self.weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        self.n_levels = int(n_levels)
+        if hist is None:
+            self.hist_column, self.n_bins, self.hist_min, self.hist_bin = 0, 0, 0.0, 1.0
+        else:
+            col, n_bins, hmin, hbin = hist
+            col = tuple(col) if not isinstance(col, (int, np.integer)) else ("source", int(col))
+            if col not in self.columns:
+                raise ValueError("the histogram's column must be one of the record's columns")
+            self.hist_column, self.n_bins, self.hist_min, self.hist_bin = self.columns.index(col), int(n_bins), float(hmin), float(hbin)
+        # (ranges, duplicates, sizes: the engine refuses them, naming the reason)
+
+    @classmethod
+    def per_walker(cls, columns=(ENTHALPY,), **kw):
+        return cls(BY_WALKER, columns, **kw)
+
+    @classmethod
+    def by_state_point(cls, columns=(ENTHALPY,), **kw):
+        return cls(BY_STATE_POINT, columns, **kw)
+
+    n_columns = property(lambda self: len(self.columns))
+    n_weights = property(lambda self: 0 if self.weights is None else len(self.weights))
+    n_pairs = property(lambda self: self.n_columns * (self.n_columns + 1) // 2)
+
+    def sources(self, n_features, n_kinds):
+        """int32 column sources of the C ABI: 0 enthalpy, 1 + i feature i, 1 + F + k kind k, 1 + F + K the weighted sum."""
+        F, K = int(n_features), int(n_kinds)
+        out = []
+        for c in self.columns:
+            if c[0] == "enthalpy":
+                out.append(0)
+            elif c[0] == "feature":
+                out.append(1 + c[1])
+            elif c[0] == "kind":
+                out.append(1 + F + c[1])
+            elif c[0] == "energy":
+                out.append(1 + F + K)
+            else:
+                out.append(c[1])
+        return np.asarray(out, dtype=np.int32)
+
+    def count_columns(self):
+        """Indices into ``columns`` of the kind counts, in order."""
+        return [i for i, c in enumerate(self.columns) if c[0] == "kind"]
+
+    def column_values(self, enthalpy, features, counts=None):
+        """x (..., C) float64 of rows with enthalpy (...), features (..., F), counts (..., K) or None."""
+        H = np.asarray(enthalpy, dtype=np.float64)
+        f = np.asarray(features, dtype=np.float64).reshape(H.shape + (-1,))
+        F = f.shape[-1]
+        K = 0 if counts is None else np.asarray(counts).shape[-1]
+        x = np.empty(H.shape + (self.n_columns,))
+        for j, src in enumerate(self.sources(F, K)):
+            if src == 0:
+                x[..., j] = H
+            elif src <= F:
+                x[..., j] = f[..., src - 1]
+            elif src <= F + K:
+                x[..., j] = np.asarray(counts).reshape(H.shape + (K,))[..., src - 1 - F].astype(np.float64)
+            elif src == 1 + F + K:
+                x[..., j] = weighted_value(self.weights if self.weights is not None else np.zeros(0), f)
+            else:
+                raise ValueError(f"column source {src} outside 0..{1 + F + K}")
+        return x
+
+    def c_struct(self, n_features, n_kinds):
+        """(capi.smolmc_statistics, the arrays it points to)."""
+        from . import capi
+
+        cols = self.sources(n_features, n_kinds)
+        keep = (cols, self.weights)
+        s = capi.smolmc_statistics(
+            self.key, len(cols), cols.ctypes.data_as(C.POINTER(C.c_int32)) if len(cols) else None, self.n_weights,
+            self.weights.ctypes.data_as(C.POINTER(C.c_double)) if self.n_weights else None, self.n_levels,
+            self.hist_column, self.n_bins, self.hist_min, self.hist_bin)
+        return s, keep
+
+
+def bin_of(x, hist_min, hist_bin):
+    """``floor_divide(x - hist_min, hist_bin)`` as float64: the exact floor division ``WLWindows.bins`` and the
+    Wang-Landau step use (NaN where x is not finite)."""
+    with np.errstate(invalid="ignore"):
+        return np.floor_divide(np.asarray(x, dtype=np.float64) - hist_min, hist_bin)
+
+
+class StatisticsRecord:
+    """The accumulators: n, under, over (n_keys,) int64; shift, s1 (n_keys, C); s2 (n_keys, C (C + 1) / 2); has (n_keys, C)
+    uint64; pend, b2 (n_keys, n_levels, C); nb (n_keys, n_levels) int64; hist (n_keys, n_bins) int64."""
+
+    def __init__(self, spec, n_keys):
+        self.spec = spec
+        nk, Cn, L, B = int(n_keys), spec.n_columns, spec.n_levels, spec.n_bins
+        self.n = np.zeros(nk, dtype=np.int64)
+        self.shift = np.zeros((nk, Cn))
+        self.s1 = np.zeros((nk, Cn))
+        self.s2 = np.zeros((nk, spec.n_pairs))
+        self.has = np.zeros((nk, Cn), dtype=np.uint64)
+        self.pend = np.zeros((nk, L, Cn))
+        self.b2 = np.zeros((nk, L, Cn))
+        self.nb = np.zeros((nk, L), dtype=np.int64)
+        self.hist = np.zeros((nk, B), dtype=np.int64)
+        self.under = np.zeros(nk, dtype=np.int64)
+        self.over = np.zeros(nk, dtype=np.int64)
+
+    n_keys = property(lambda self: len(self.n))
+
+    # ---- the definition ------------------------------------------------------------------------------------------
+    def offer(self, enthalpy, features, counts=None, key_of_row=None):
+        """Offer samples (ns, R) -- or one sample (R,) -- in order.  ``key_of_row`` (R,) or (ns, R): the key of every
+        row, a permutation of 0 .. R - 1 per sample (None: the walker).  Vectorised over the keys, a loop over samples."""
+        spec = self.spec
+        nk = self.n_keys
+        H = np.asarray(enthalpy, dtype=np.float64).reshape(-1, nk)
+        ns = len(H)
+        f = np.asarray(features, dtype=np.float64).reshape(ns, nk, -1)
+        cnt = None if counts is None else np.asarray(counts).reshape(ns, nk, -1)
+        x_all = spec.column_values(H, f, cnt)
+        if key_of_row is None:
+            keys = np.broadcast_to(np.arange(nk), (ns, nk))
+        else:
+            keys = np.broadcast_to(np.asarray(key_of_row, dtype=np.int64), (ns, nk))
+        Cn, L = spec.n_columns, spec.n_levels
+        ia, ib = np.triu_indices(Cn)
+        rows = np.arange(nk)
+        one = np.uint64(1)
+        for s in range(ns):
+            if not np.array_equal(np.sort(keys[s]), rows):
+                raise ValueError("key_of_row must be a permutation of the keys in every sample")
+            x = np.empty((nk, Cn))
+            x[keys[s]] = x_all[s]  # row r goes to key keys[s][r]
+            first = self.n == 0
+            self.shift[first] = x[first]
+            d = x - self.shift
+            self.s1 = self.s1 + d
+            self.s2 = self.s2 + d[:, ia] * d[:, ib]
+            carry = d.copy()
+            live = np.ones((nk, Cn), dtype=bool)  # (all columns of a key walk the same levels)
+            for l in range(L):
+                if not live.any():
+                    break
+                bit = one << np.uint64(l)
+                self.b2[:, l, :] = np.where(live, self.b2[:, l, :] + carry * carry, self.b2[:, l, :])
+                self.nb[:, l] += live[:, 0]
+                held = (self.has & bit) != 0
+                park = live & ~held
+                self.pend[:, l, :] = np.where(park, carry, self.pend[:, l, :])
+                self.has = np.where(park, self.has | bit, self.has)
+                go = live & held
+                carry = np.where(go, self.pend[:, l, :] + carry, carry)
+                self.has = np.where(go, self.has & ~bit, self.has)
+                live = go
+            if spec.n_bins:
+                xv = x[:, spec.hist_column]
+                q = bin_of(xv, spec.hist_min, spec.hist_bin)
+                bad = ~np.isfinite(xv) | np.isnan(q)
+                under = ~bad & (q < 0)
+                over = bad | (q >= spec.n_bins)
+                self.under += under
+                self.over += over
+                ok = ~(under | over)
+                self.hist[rows[ok], q[ok].astype(np.int64)] += 1
+            self.n += 1
+        return self
+
+    # ---- what users do with a record -------------------------------------------------------------------------------
+    def _full_s2(self):
+        Cn = self.spec.n_columns
+        ia, ib = np.triu_indices(Cn)
+        m = np.zeros((self.n_keys, Cn, Cn))
+        m[:, ia, ib] = self.s2
+        m[:, ib, ia] = self.s2
+        return m
+
+    def mean(self):
+        """(n_keys, C): shift + s1 / n (NaN for a key without samples)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.shift + self.s1 / self.n[:, None]
+
+    def covariance(self):
+        """(n_keys, C, C), the population covariance (ddof = 0): s2 / n - (s1 / n)(s1 / n)^T of the shifted values."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m1 = self.s1 / self.n[:, None]
+            return self._full_s2() / self.n[:, None, None] - m1[:, :, None] * m1[:, None, :]
+
+    def variance(self):
+        return np.einsum("kcc->kc", self.covariance())
+
+    def _column(self, col):
+        col = tuple(col)
+        if col not in self.spec.columns:
+            raise ValueError(f"the record has no column {col}")
+        return self.spec.columns.index(col)
+
+    def heat_capacity(self, temperature, column=ENTHALPY):
+        """var(H) / (kB T^2) per key, from the enthalpy column (``temperature`` a scalar or one per key)."""
+        T = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (self.n_keys,))
+        return self.variance()[:, self._column(column)] / (KB * T * T)
+
+    def susceptibility(self, temperature):
+        """beta x the covariance of the count columns, (n_keys, n_counts, n_counts)."""
+        idx = self.spec.count_columns()
+        if not idx:
+            raise ValueError("the record has no count columns")
+        T = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (self.n_keys,))
+        return self.covariance()[:, idx][:, :, idx] / (KB * T)[:, None, None]
+
+    def blocking(self):
+        """Per level l the error estimate of the mean from blocks of 2^l samples: (error (n_keys, L, C), its own
+        uncertainty (n_keys, L, C), nb (n_keys, L)).  The block means are the block sums / 2^l; their variance (ddof = 0)
+        is b2 / (4^l nb) - m_l^2, with m_l the mean over the samples of the nb complete blocks: s1 less the blocks that
+        still wait below level l, over nb 2^l.  The error is sqrt(var / (nb - 1)), its uncertainty
+        error / sqrt(2 (nb - 1)) (Flyvbjerg & Petersen, eq. 28).  NaN where nb < 2."""
+        L = self.spec.n_levels
+        size = (2.0 ** np.arange(L))[None, :, None]
+        nb = self.nb[:, :, None].astype(np.float64)
+        bits = ((self.has[:, None, :] >> np.arange(L, dtype=np.uint64)[None, :, None]) & np.uint64(1)).astype(bool)
+        waiting = np.where(bits, self.pend, 0.0)
+        below = np.cumsum(waiting, axis=1) - waiting  # (the pending blocks of the levels j < l)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = (self.s1[:, None, :] - below) / (nb * size)
+            var = self.b2 / (size * size * nb) - m * m
+            err = np.sqrt(np.maximum(var, 0.0) / (nb - 1.0))
+            unc = err / np.sqrt(2.0 * (nb - 1.0))
+        bad = np.broadcast_to(nb < 2, err.shape)
+        return np.where(bad, np.nan, err), np.where(bad, np.nan, unc), self.nb.copy()
+
+    def standard_error(self, min_blocks=16):
+        """(n_keys, C): the blocking error at the plateau.  The rule: the first level l whose estimate is not below the
+        next one by more than that level's own uncertainty (err[l + 1] - err[l] <= unc[l]), among levels with at least
+        ``min_blocks`` blocks; when no level qualifies, the largest estimate among the levels with ``min_blocks`` blocks
+        (a lower bound: the run is too short for a plateau).  Without blocking levels: the naive sqrt(var / (n - 1))."""
+        nk, Cn, L = self.n_keys, self.spec.n_columns, self.spec.n_levels
+        with np.errstate(invalid="ignore", divide="ignore"):
+            naive = np.sqrt(self.variance() / (self.n[:, None] - 1.0))
+        if L == 0:
+            return naive
+        err, unc, nb = self.blocking()
+        out = naive.copy()
+        for k in range(nk):
+            ok = np.flatnonzero(nb[k] >= min_blocks)
+            if not len(ok):
+                continue
+            for c in range(Cn):
+                pick = None
+                for l in ok:
+                    if l + 1 in ok and err[k, l + 1, c] - err[k, l, c] <= unc[k, l, c]:
+                        pick = err[k, l, c]
+                        break
+                out[k, c] = pick if pick is not None else np.nanmax(err[k, ok, c])
+        return out
+
+    def autocorrelation_time(self, min_blocks=16):
+        """(n_keys, C): the integrated autocorrelation time in samples, tau = (standard_error / naive error)^2 / 2
+        (0.5 for uncorrelated samples)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            naive = np.sqrt(self.variance() / (self.n[:, None] - 1.0))
+            return 0.5 * (self.standard_error(min_blocks) / naive) ** 2
+
+    @classmethod
+    def combine(cls, records):
+        """One record from those of several ranks or of the parts of a resumed run that hold the SAME keys: the pairwise
+        merge of Chan et al. of n / shift / s1 / s2 (the second record's sums are moved to the first one's shift) and the
+        sum of the histograms.  The blocking arrays are NOT merged (a block of 2^l samples does not span two records):
+        the result has n_levels = 0."""
+        records = list(records)
+        a = records[0]
+        spec = Statistics(a.spec.key, a.spec.columns, a.spec.weights, 0,
+                          None if not a.spec.n_bins else (a.spec.columns[a.spec.hist_column], a.spec.n_bins, a.spec.hist_min, a.spec.hist_bin))
+        out = cls(spec, a.n_keys)
+        for f in ("n", "shift", "s1", "s2", "hist", "under", "over"):
+            setattr(out, f, getattr(a, f).copy())
+        ia, ib = np.triu_indices(spec.n_columns)
+        for b in records[1:]:
+            empty = out.n == 0
+            out.shift[empty] = b.shift[empty]
+            # sums of (x - shift_out) from sums of (x - shift_b): x - shift_out = (x - shift_b) + delta
+            delta = b.shift - out.shift
+            nb = b.n[:, None].astype(np.float64)
+            out.s2 = out.s2 + (b.s2 + delta[:, ia] * b.s1[:, ib] + delta[:, ib] * b.s1[:, ia] + nb * delta[:, ia] * delta[:, ib])
+            out.s1 = out.s1 + (b.s1 + nb * delta)
+            out.n = out.n + b.n
+            out.hist = out.hist + b.hist
+            out.under = out.under + b.under
+            out.over = out.over + b.over
+        return out
+
+    def reweight(self, temperature_from, temperature_to):
+        """Single-histogram reweighting of the histogram's column (the enthalpy) from ``temperature_from`` to
+        ``temperature_to``: (mean (n_keys,), variance (n_keys,)) of the bin centres under the weights
+        hist x exp(-(beta_to - beta_from) E), the exponent shifted by its maximum."""
+        spec = self.spec
+        if not spec.n_bins:
+            raise ValueError("the record keeps no histogram")
+        Tf = np.broadcast_to(np.asarray(temperature_from, dtype=np.float64), (self.n_keys,))
+        Tt = np.broadcast_to(np.asarray(temperature_to, dtype=np.float64), (self.n_keys,))
+        centre = spec.hist_min + (np.arange(spec.n_bins) + 0.5) * spec.hist_bin
+        db = (1.0 / (KB * Tt) - 1.0 / (KB * Tf))[:, None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            logw = np.where(self.hist > 0, np.log(self.hist.astype(np.float64)), -np.inf) - db * centre[None, :]
+            logw = logw - logw.max(axis=1, keepdims=True)
+            w = np.exp(logw)
+            z = w.sum(axis=1)
+            mean = (w * centre).sum(axis=1) / z
+            var = (w * (centre[None, :] - mean[:, None]) ** 2).sum(axis=1) / z
+        return mean, var
+
+    def equals(self, other):
+        return all(np.array_equal(getattr(self, f), getattr(other, f), equal_nan=True) for f in _ARRAYS)
+
+    def copy(self):
+        out = StatisticsRecord(self.spec, self.n_keys)
+        for f in _ARRAYS:
+            setattr(out, f, getattr(self, f).copy())
+        return out
