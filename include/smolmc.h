@@ -381,6 +381,7 @@ int smolmc_sync(smolmc_handle *h);
 #define SMOLMC_SAMPLE_OBSERVABLES 8 /* flags bit 3: kind and pair counts of every row (see smolmc_set_observables) */
 #define SMOLMC_SAMPLE_MINIMA 16     /* flags bit 4: offer every row to the minima record (see smolmc_set_minima) */
 #define SMOLMC_SAMPLE_STATISTICS 32 /* flags bit 5: offer every row to the statistics record (see smolmc_set_statistics) */
+#define SMOLMC_SAMPLE_STRUCTURE 64  /* flags bit 6: structure-factor amplitudes and intensities of every row (see smolmc_set_structure) */
 int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t thin_by, int flags);
 /* The ring as the next smolmc_get_samples* call sees it (ABI 8): *n_pending = blocks queued and not fetched
  * (0..2), *nsamples / *flags = sample count and SMOLMC_SAMPLE_* flags of the block that call would deliver
@@ -518,7 +519,9 @@ typedef struct smolmc_statistics {
     int key;                /* SMOLMC_STAT_BY_WALKER or SMOLMC_STAT_BY_STATE_POINT */
     int n_columns;          /* C, 1..32 */
     const int32_t *columns; /* [C] sources, no duplicates: 0 the enthalpy, 1 + i feature i (i < F), 1 + F + k kind count k
-                             * of the observables in force (k < K, as a double), 1 + F + K the weighted sum below */
+                             * of the observables in force (k < K, as a double), 1 + F + K the weighted sum below,
+                             * 2 + F + K + i intensity i of the structure-factor spec in force (i < I, see
+                             * smolmc_set_structure; with no spec set the range ends at the weighted sum) */
     int n_weights;          /* the weighted sum: sum_{i < n_weights} weights[i] * features[i] left to right, the value of */
     const double *weights;  /* a minima record (n_weights <= F) */
     int n_levels;           /* blocking levels, 0..32 */
@@ -530,13 +533,14 @@ typedef struct smolmc_statistics {
  * the handle as it was: a key other than the two; SMOLMC_STAT_BY_STATE_POINT on a Wang-Landau handle with per-walker
  * windows; C outside 1..32, a source out of range or named twice; a count column without observables; n_weights > F;
  * n_levels outside 0..32; n_bins outside 0..65536, hist_bin not a positive finite number, hist_column outside the
- * columns; a record of more than 1 GiB.  While a record with count columns is set, smolmc_set_observables is refused.
+ * columns; a record of more than 1 GiB.  While a record with count columns is set, smolmc_set_observables is refused,
+ * and smolmc_set_structure while a record with intensity columns is set.
  * Waits for the handle's stream, like smolmc_reset_statistics and smolmc_get_statistics. */
 int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *s);
 /* the shape in force (all 0: none set) */
 int smolmc_statistics_shape(smolmc_handle *h, int *n_keys, int *n_columns, int *n_levels, int *n_bins);
 /* Offers the walkers' CURRENT states, one offer (for callers of smolmc_run); with count columns the kinds of the current
- * states are counted on the device first. */
+ * states are counted on the device first, with intensity columns their intensities are evaluated first. */
 int smolmc_update_statistics(smolmc_handle *h);
 /* Empties the record. */
 int smolmc_reset_statistics(smolmc_handle *h);
@@ -545,6 +549,53 @@ int smolmc_reset_statistics(smolmc_handle *h);
  * Any pointer may be NULL. */
 int smolmc_get_statistics(smolmc_handle *h, int64_t *n, double *shift, double *s1, double *s2, uint64_t *has, double *pend,
                           double *b2, int64_t *nb, int64_t *hist, int64_t *under, int64_t *over);
+
+/* ---- structure factors: fixed-point amplitudes and intensities of sampled states, reduced on the device ---------------
+ * (no reference counterpart).  Kinds as in smolmc_observables: the kind of (site, code) is kind_base[site] + code,
+ * kind_base[site] = -1 leaves the site out.  For every wave vector ("point") q every site j has a phase class
+ * phase[q][j] < n_phases, and every class the fixed-point pair table[q][m] = (cos, -sin) of its angle.  Per occupancy row
+ *   amp[q][k][c] = sum over counted sites j with kind(j) == k of table[q][phase[q][j]][c]            (int64, c = 0, 1)
+ *   inten[i]     = ((double)amp[q][a][0] * (double)amp[q][b][0] + (double)amp[q][a][1] * (double)amp[q][b][1]) * scale[i]
+ *                  for intensity[i] = (q, a, b)
+ * The sums are integer sums, so their order is of no concern; every floating product and sum of inten is rounded on its
+ * own (no fused multiply-add).  smol_amd/structure.py is the same in NumPy and the device matches it entry for entry.
+ * The engine knows no geometry: the caller supplies phase and table (structure.StructureFactor.from_supercell makes
+ * them).  Site numbers are the caller's.  The engine copies and uploads everything. */
+#define SMOLMC_MAX_STRUCT_POINTS 4096  /* Q: an amplitude column of a row is Q x K x 16 bytes and the phase table Q x N x 2
+                                        * bytes; with rows of at most 65535 sites the table stays below 512 MiB */
+#define SMOLMC_MAX_STRUCT_PHASES 65535 /* M: a phase class is a uint16 */
+#define SMOLMC_MAX_STRUCT_CELLS 12288  /* K x M, the (kind, phase class) counters of one point: 48 KB of int32, which
+                                        * share the 64 KB of LDS of one workgroup with the row */
+#define SMOLMC_MAX_STRUCT_INTENSITIES 4096 /* I: one thread pass of the epilogue per 256; keeps a row's column at 32 KB */
+typedef struct smolmc_structure {
+    int n_kinds;                   /* K, 1..254 */
+    const int32_t *kind_base;      /* [N] */
+    int n_points;                  /* Q, 1..SMOLMC_MAX_STRUCT_POINTS */
+    int n_phases;                  /* M, 1..SMOLMC_MAX_STRUCT_PHASES, K x M <= SMOLMC_MAX_STRUCT_CELLS */
+    const uint16_t *phase;         /* [Q x N], every entry < M */
+    const int64_t *table;          /* [Q x M x 2] */
+    int n_intensities;             /* I, 0..SMOLMC_MAX_STRUCT_INTENSITIES */
+    const int32_t *intensity;      /* [I x 3]: point q, kind a, kind b */
+    const double *intensity_scale; /* [I] */
+} smolmc_structure;
+/* Sets (NULL: removes) the structure-factor spec of the handle.  Refused, each naming its reason: a phase >= n_phases; a
+ * site with kind_base[s] + (species codes on s) > n_kinds (a fixed site outside every cluster needs one kind, as for the
+ * observables); Q, M, K, K x M or I beyond the limits above; a row too long to stage in LDS next to the counters;
+ * N_counted x max|table| >= 2^62 (a sum could overflow); an intensity naming a point or kind out of range; a scale that
+ * is not finite; while a block recorded with SMOLMC_SAMPLE_STRUCTURE waits in the ring; while a statistics record with
+ * intensity columns is set.  A refused call leaves the handle's spec as it was. */
+int smolmc_set_structure(smolmc_handle *h, const smolmc_structure *s);
+/* Q, K and I in force (all 0: none set) */
+int smolmc_structure_shape(smolmc_handle *h, int *n_points, int *n_kinds, int *n_intensities);
+/* amp [nocc x Q x K x 2] and inten [nocc x I] of nocc occupancies (host, int32 like smolmc_eval_full), or, with
+ * occ == NULL, of the walkers' current states (nocc = R then).  Either output may be NULL. */
+int smolmc_eval_structure(smolmc_handle *h, const int32_t *occ /* nocc x N, or NULL */, int nocc, int64_t *amp, double *inten);
+/* With SMOLMC_SAMPLE_STRUCTURE smolmc_run_sampled adds the two columns [rows x Q x K x 2] (int64) and [rows x I] (double)
+ * to the block, filled on the device from the block's occupancy rows when its launches are through; without
+ * SMOLMC_SAMPLE_OCCUPANCY those rows never leave the device.  The flag is refused while no spec is set.  This call reads
+ * the columns of the block the next smolmc_get_samples* call delivers ([nsamples x R x ...], either may be NULL) and does
+ * not mark it delivered, like smolmc_get_sample_observables; an error when that block was recorded without the flag. */
+int smolmc_get_sample_structure(smolmc_handle *h, int64_t *amp, double *inten);
 
 /* Same loop driven by host-provided proposals ("replay mode"): what
  * StandardSingleStepMixin.single_step (kernel/base.py:145-166) does after mcusher.propose_step

@@ -31,6 +31,29 @@ MAX_OBS_CELLS = 4096            # SMOLMC_MAX_OBS_CELLS
 SAMPLE_MINIMA = 16              # ... every row is offered to the minima record (smolmc_set_minima)
 MAX_MINIMA_AXES = 4             # SMOLMC_MAX_MINIMA_AXES
 SAMPLE_STATISTICS = 32          # ... every row is offered to the statistics record (smolmc_set_statistics)
+SAMPLE_STRUCTURE = 64           # ... structure-factor amplitudes and intensities of every row (smolmc_set_structure)
+MAX_STRUCT_POINTS = 4096        # SMOLMC_MAX_STRUCT_POINTS
+MAX_STRUCT_PHASES = 65535       # SMOLMC_MAX_STRUCT_PHASES
+MAX_STRUCT_CELLS = 12288        # SMOLMC_MAX_STRUCT_CELLS: n_kinds x n_phases
+MAX_STRUCT_INTENSITIES = 4096   # SMOLMC_MAX_STRUCT_INTENSITIES
+STRUCT_LDS_BYTES = 65536        # the LDS of one workgroup of the structure kernels (structure.hip)
+STRUCT_WAVES = 4                # counter kernel: its waves, a counter set per wave while they fit
+STRUCT_MASK_CELLS = 128         # most (kind, phase class) cells of a point the bit-mask kernel takes
+STRUCT_MASK_ROWS = 4            # ... the rows one of its workgroups takes: their kind masks share LDS
+
+
+def structure_plan(n_sites, npad, n_kinds, n_phases, n_points):
+    """The kernel a structure-factor spec takes on rows of ``n_sites`` sites in ``npad`` bytes (smolmc_sfac_plan in
+    csrc/structure.hip): ("mask",) -- the bit-mask kernel; ("counters", counter sets per point, points per pass) -- the
+    counter kernel; None when the row does not fit LDS next to the counters of one point."""
+    cells = n_kinds * n_phases
+    words = (n_sites + 63) // 64
+    if cells <= STRUCT_MASK_CELLS and STRUCT_MASK_ROWS * n_kinds * words * 8 <= STRUCT_LDS_BYTES:
+        return ("mask",)
+    if npad + 4 * cells > STRUCT_LDS_BYTES:
+        return None
+    copies = STRUCT_WAVES if npad + 4 * STRUCT_WAVES * cells <= STRUCT_LDS_BYTES else 1
+    return "counters", copies, min((STRUCT_LDS_BYTES - npad) // (4 * copies * cells), n_points)
 MAX_STEP_FLIPS = 8              # SMOLMC_MAX_STEP_FLIPS
 STEP_ROW = 2 * MAX_STEP_FLIPS   # SMOLMC_STEP_ROW: int32 per step record (site, code) x 8, -1 = no flip
 
@@ -161,6 +184,22 @@ class smolmc_statistics(C.Structure):
         ("n_bins", C.c_int),
         ("hist_min", C.c_double),
         ("hist_bin", C.c_double),
+    ]
+
+
+class smolmc_structure(C.Structure):
+    """Mirror of ``smolmc_structure`` (include/smolmc.h); ``structure.StructureFactor.c_struct`` fills it."""
+
+    _fields_ = [
+        ("n_kinds", C.c_int),
+        ("kind_base", _i32p),
+        ("n_points", C.c_int),
+        ("n_phases", C.c_int),
+        ("phase", C.POINTER(C.c_uint16)),
+        ("table", _i64p),
+        ("n_intensities", C.c_int),
+        ("intensity", _i32p),
+        ("intensity_scale", _f64p),
     ]
 
 

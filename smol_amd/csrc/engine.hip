@@ -2371,6 +2371,7 @@ extern "C" int smolmc_destroy(smolmc_handle *h) {
     if (h->obs_ev1) hipEventDestroy(h->obs_ev1);
     smolmc_min_free(h);
     smolmc_stat_free(h);
+    smolmc_sfac_free(h->sfac);
     free_samples(h);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -3332,6 +3333,9 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool stats = (flags & SMOLMC_SAMPLE_STATISTICS) != 0;
     if (stats && !h->stats.n_keys)
         return fail("SMOLMC_SAMPLE_STATISTICS without a statistics record: call smolmc_set_statistics first");
+    const bool sfac = (flags & SMOLMC_SAMPLE_STRUCTURE) != 0;
+    if (sfac && !h->sfac.Q)
+        return fail("SMOLMC_SAMPLE_STRUCTURE without a structure-factor spec: call smolmc_set_structure first");
     if ((flags & SMOLMC_SAMPLE_WL) && !h->wl_win_min.empty())
         return fail("SMOLMC_SAMPLE_WL while per-walker windows are set: the snapshot rows are walker-indexed, the Wang-Landau arrays estimator-indexed (smolmc_get_wl between runs, or smolmc_set_wl_windows(h, NULL, NULL) first)");
     if (thin_by > ((int64_t)1 << 30) && h->lean() && !smolmc_env(ENV_LAUNCH_CHUNK))
@@ -3373,6 +3377,10 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool obs = (flags & SMOLMC_SAMPLE_OBSERVABLES) != 0;
     w.o_cnt = obs ? take(rows * (size_t)h->obs.K * 4) : 0;
     w.o_pair = obs ? take(rows * h->obs.cells * 4) : 0;
+    // structure factors: likewise two columns, int64 amplitudes and double intensities
+    const size_t sf_amp = (size_t)h->sfac.Q * h->sfac.K * 2 * 8, sf_inten = (size_t)h->sfac.I * 8; // bytes per row
+    w.o_amp = sfac ? take(rows * sf_amp) : 0;
+    w.o_inten = sfac ? take(rows * sf_inten) : 0;
     // lazy cluster features, rows recorded in-kernel: the kernels write rows of scalar features and the occupancy of
     // every sample; the cluster features of the rows are evaluated from those when the launch is through.  What the
     // caller did not ask for sits behind the part of the arena that is downloaded.
@@ -3392,7 +3400,10 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool min_counts = minima && h->obs.K && h->obs.K == h->minima.K; // (a keyed record: always, see smolmc_set_observables)
     // (... and the rows whose kinds a statistics record with count columns reads)
     const bool stat_counts = stats && h->stats.n_count_cols > 0; // (then obs.K == stats.K, see smolmc_set_observables)
-    if ((lazy_rows || obs || minima || stat_counts) && !(flags & SMOLMC_SAMPLE_OCCUPANCY)) o_occ_int = take(rows * h->Npad);
+    // (... and the rows whose structure factors are asked for, or read by a statistics record with intensity columns)
+    const bool stat_inten = stats && h->stats.n_inten_cols > 0; // (then sfac.I == stats.I, see smolmc_set_structure)
+    if ((lazy_rows || obs || minima || stat_counts || sfac || stat_inten) && !(flags & SMOLMC_SAMPLE_OCCUPANCY))
+        o_occ_int = take(rows * h->Npad);
     size_t o_min_cnt = w.o_cnt, o_min_key = 0, o_min_slot = 0;
     if (minima) {
         if (min_counts && !obs) o_min_cnt = take(rows * (size_t)h->obs.K * 4);
@@ -3404,7 +3415,14 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool stat_own_counts = stat_counts && !obs && !(min_counts);
     size_t o_stat_cnt = obs ? w.o_cnt : o_min_cnt;
     if (stat_own_counts) o_stat_cnt = take(rows * (size_t)h->obs.K * 4);
+    // ... and the structure factors' intensity column, or hidden columns of its own
+    size_t o_stat_amp = w.o_amp, o_stat_inten = w.o_inten;
+    if (stat_inten && !sfac) {
+        o_stat_amp = take(rows * sf_amp);
+        o_stat_inten = take(rows * sf_inten);
+    }
     if (stats && rows > 0x7fffffffull) return fail("statistics: more than 2^31 sample rows in one block");
+    if (sfac && rows > 0x7fffffffull) return fail("structure factors: more than 2^31 sample rows in one block");
     if (lazy_rows && rows > 0x7fffffffull) return fail("lazy cluster features: more than 2^31 sample rows in one block");
     if (obs && rows > 0x7fffffffull) return fail("observables: more than 2^31 sample rows in one block");
     // the slot's previous block (delivered, or none) must have left the device before its arenas are reused
@@ -3434,7 +3452,8 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     smp.H = (double *)(sl.d + w.o_H);
     smp.feat = (double *)(sl.d + (lazy_rows ? o_scal : w.o_feat));
     smp.acc = sl.d + w.o_acc;
-    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs || minima || stat_counts ? sl.d + o_occ_int : nullptr;
+    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs || minima || stat_counts || sfac || stat_inten
+                  ? sl.d + o_occ_int : nullptr;
     if (!snapshot_path) {
         if (inkernel_bias) {
             if ((w.o_bias - w.o_H) / 8 > 0xffffffffull) return fail("sample block too large for the in-kernel bias column");
@@ -3478,10 +3497,14 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
                               min_counts ? (const int32_t *)(sl.d + o_min_cnt) : nullptr, (uint64_t *)(sl.d + o_min_key),
                               (int32_t *)(sl.d + o_min_slot), nsamples, thin_by));
     }
+    if (sfac) TRY(smolmc_sfac_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + w.o_amp), (double *)(sl.d + w.o_inten)));
     if (stats) {
         if (stat_own_counts) TRY(smolmc_obs_launch(h, sl.d + o_occ_int, rows, (int32_t *)(sl.d + o_stat_cnt), nullptr));
+        if (stat_inten && !sfac)
+            TRY(smolmc_sfac_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + o_stat_amp), (double *)(sl.d + o_stat_inten)));
         TRY(smolmc_stat_launch(h, (const double *)(sl.d + w.o_H), (const double *)(sl.d + w.o_feat),
-                               stat_counts ? (const int32_t *)(sl.d + o_stat_cnt) : nullptr, nsamples));
+                               stat_counts ? (const int32_t *)(sl.d + o_stat_cnt) : nullptr,
+                               stat_inten ? (const double *)(sl.d + o_stat_inten) : nullptr, nsamples));
     }
     // download on the copy stream as soon as the block is complete; the next block's launches do not wait for it
     // (the mirror is about to be overwritten: from here the slot no longer holds its old block)
@@ -3958,9 +3981,208 @@ extern "C" int smolmc_update_statistics(smolmc_handle *h) {
     if (!S.n_keys) return fail("no statistics record set: call smolmc_set_statistics first");
     HIPCHK(hipSetDevice(h->device));
     TRY(ensure_features(h));
-    const bool counts = S.n_count_cols > 0;
+    const bool counts = S.n_count_cols > 0, inten = S.n_inten_cols > 0;
     if (counts) TRY(smolmc_obs_launch(h, h->kp.occ, (size_t)h->R, S.u_counts, nullptr));
-    return smolmc_stat_launch(h, h->kp.enthalpy, h->kp.features, counts ? S.u_counts : nullptr, 1);
+    if (inten) TRY(smolmc_sfac_launch(h, h->kp.occ, (size_t)h->R, h->sfac.u_amp, h->sfac.u_inten));
+    return smolmc_stat_launch(h, h->kp.enthalpy, h->kp.features, counts ? S.u_counts : nullptr, inten ? h->sfac.u_inten : nullptr, 1);
+}
+
+// ---- structure factors: fixed-point amplitudes and intensities of occupancy rows (the kernel: structure.hip) ----------
+extern "C" int smolmc_set_structure(smolmc_handle *h, const smolmc_structure *sp) {
+    if (!h) return fail("null handle");
+    HIPCHK(hipSetDevice(h->device));
+    for (const SampleSlot &c : h->slots)
+        if (c.state == 1 && (c.flags & SMOLMC_SAMPLE_STRUCTURE))
+            return fail("smolmc_set_structure while a block recorded with SMOLMC_SAMPLE_STRUCTURE waits in the ring (call "
+                        "smolmc_get_samples* or smolmc_discard_samples first)");
+    if (h->stats.n_keys && h->stats.n_inten_cols)
+        return fail("smolmc_set_structure while a statistics record with intensity columns depends on the spec (call "
+                    "smolmc_set_statistics(h, NULL) first)");
+    SmolmcStruct S;
+    if (sp) {
+        const int N = h->N, K = sp->n_kinds, Q = sp->n_points, M = sp->n_phases, I = sp->n_intensities;
+        char msg[256];
+        if (!sp->kind_base || !sp->phase || !sp->table || (I > 0 && (!sp->intensity || !sp->intensity_scale)))
+            return fail("structure factors: null argument");
+        if (K < 1 || K > 254) return fail("structure factors: n_kinds must be 1..254 (a kind is staged as one byte)");
+        if (Q < 1 || Q > SMOLMC_MAX_STRUCT_POINTS) {
+            snprintf(msg, sizeof msg, "structure factors: n_points must be 1..%d, got %d", SMOLMC_MAX_STRUCT_POINTS, Q);
+            return fail(msg);
+        }
+        if (M < 1 || M > SMOLMC_MAX_STRUCT_PHASES) {
+            snprintf(msg, sizeof msg, "structure factors: n_phases must be 1..%d, got %d", SMOLMC_MAX_STRUCT_PHASES, M);
+            return fail(msg);
+        }
+        if ((size_t)K * M > SMOLMC_MAX_STRUCT_CELLS) {
+            snprintf(msg, sizeof msg, "structure factors: %d kinds x %d phase classes = %zu cells, larger than SMOLMC_MAX_STRUCT_CELLS = %d",
+                     K, M, (size_t)K * M, SMOLMC_MAX_STRUCT_CELLS);
+            return fail(msg);
+        }
+        if (I < 0 || I > SMOLMC_MAX_STRUCT_INTENSITIES) {
+            snprintf(msg, sizeof msg, "structure factors: n_intensities must be 0..%d, got %d", SMOLMC_MAX_STRUCT_INTENSITIES, I);
+            return fail(msg);
+        }
+        // kind_base in the engine's numbering; every code a site can hold must have a kind below K (as smolmc_set_observables)
+        std::vector<int32_t> kb((size_t)N);
+        size_t n_counted = 0;
+        for (int p = 0; p < N; ++p) {
+            const int s = h->relabelled ? h->new_of[p] : p;
+            const int32_t b = sp->kind_base[p];
+            const int width = h->site_width_known[s] ? (int)h->site_ncodes[s] : 1;
+            if (b >= 0 && b + width > K) {
+                snprintf(msg, sizeof msg, "structure factors: kind_base[%d] + site_ncodes = %d + %d is larger than n_kinds = %d: kind out of range",
+                         p, (int)b, width, K);
+                return fail(msg);
+            }
+            kb[s] = b < 0 ? -1 : b;
+            n_counted += b >= 0;
+        }
+        std::vector<uint16_t> ph((size_t)Q * N);
+        for (int q = 0; q < Q; ++q)
+            for (int p = 0; p < N; ++p) {
+                const uint16_t v = sp->phase[(size_t)q * N + p];
+                if (v >= M) {
+                    snprintf(msg, sizeof msg, "structure factors: phase[%d][%d] = %d, n_phases is %d: phase out of range", q, p, (int)v, M);
+                    return fail(msg);
+                }
+                ph[(size_t)q * N + (h->relabelled ? h->new_of[p] : p)] = v;
+            }
+        unsigned long long peak = 0;
+        for (size_t i = 0; i < (size_t)Q * M * 2; ++i) {
+            const int64_t v = sp->table[i];
+            const unsigned long long a = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
+            peak = std::max(peak, a);
+        }
+        if (n_counted && peak >= (1ull << 62) / n_counted + ((1ull << 62) % n_counted != 0)) {
+            snprintf(msg, sizeof msg, "structure factors: %zu counted sites x max|table| = %llu reaches 2^62: an amplitude could overflow",
+                     n_counted, peak);
+            return fail(msg);
+        }
+        for (int i = 0; i < I; ++i) {
+            const int32_t q = sp->intensity[3 * i], a = sp->intensity[3 * i + 1], b = sp->intensity[3 * i + 2];
+            if (q < 0 || q >= Q) {
+                snprintf(msg, sizeof msg, "structure factors: intensity %d names point %d, n_points is %d: point out of range", i, (int)q, Q);
+                return fail(msg);
+            }
+            if (a < 0 || a >= K || b < 0 || b >= K) {
+                snprintf(msg, sizeof msg, "structure factors: intensity %d names kinds (%d, %d), n_kinds is %d: kind out of range", i, (int)a,
+                         (int)b, K);
+                return fail(msg);
+            }
+            if (!std::isfinite(sp->intensity_scale[i])) {
+                snprintf(msg, sizeof msg, "structure factors: intensity_scale[%d] is not finite", i);
+                return fail(msg);
+            }
+        }
+        S.K = K; S.Q = Q; S.M = M; S.I = I;
+        S.W = (N + 63) / 64;
+        if (!smolmc_sfac_plan(N, h->Npad, K, M, Q, &S.mask, &S.copies, &S.chunk, &S.lds)) {
+            snprintf(msg, sizeof msg, "structure factors: a row of %d sites is too long to stage in LDS next to the %zu counters of a point "
+                     "(%zu bytes, 65536 at most)", N, (size_t)K * M, (size_t)h->Npad + (size_t)K * M * 4);
+            return fail(msg);
+        }
+        S.kind_base = kb;
+        // one arena: the spec's arrays, then the scratch of smolmc_update_statistics
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
+        const size_t R = (size_t)h->R;
+        const size_t o_kb = take((size_t)N * 4), o_ph = take((size_t)Q * N * 2), o_tb = take((size_t)Q * M * 16),
+                     o_it = take((size_t)I * 12), o_sc = take((size_t)I * 8), o_ua = take(R * Q * K * 16), o_ui = take(R * I * 8);
+        // the mask kernel's table: for every point and class the sites of the class as bits, words of one (word, class)
+        // side by side over the points
+        std::vector<unsigned long long> masks;
+        if (S.mask) {
+            masks.assign((size_t)S.W * M * Q, 0ull);
+            for (int q = 0; q < Q; ++q)
+                for (int s = 0; s < N; ++s)
+                    masks[((size_t)(s >> 6) * M + ph[(size_t)q * N + s]) * Q + q] |= 1ull << (s & 63);
+        }
+        const size_t o_mk = take(masks.size() * 8);
+        hipError_t e = hipMalloc((void **)&S.arena, at);
+        if (e != hipSuccess) return fail(std::string("structure factors: hipMalloc: ") + hipGetErrorString(e));
+        unsigned char *d = S.arena;
+        S.d_kind_base = (int32_t *)(d + o_kb); S.d_phase = (uint16_t *)(d + o_ph); S.d_table = (long long *)(d + o_tb);
+        S.d_intensity = (int32_t *)(d + o_it); S.d_scale = (double *)(d + o_sc);
+        S.u_amp = (long long *)(d + o_ua); S.u_inten = (double *)(d + o_ui);
+        S.d_masks = (unsigned long long *)(d + o_mk);
+        e = hipMemcpy(S.d_kind_base, kb.data(), (size_t)N * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(S.d_phase, ph.data(), (size_t)Q * N * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(S.d_table, sp->table, (size_t)Q * M * 16, hipMemcpyHostToDevice);
+        if (e == hipSuccess && I) e = hipMemcpy(S.d_intensity, sp->intensity, (size_t)I * 12, hipMemcpyHostToDevice);
+        if (e == hipSuccess && I) e = hipMemcpy(S.d_scale, sp->intensity_scale, (size_t)I * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !masks.empty()) e = hipMemcpy(S.d_masks, masks.data(), masks.size() * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            smolmc_sfac_free(S);
+            return fail(std::string("structure factors upload: ") + hipGetErrorString(e));
+        }
+    }
+    // the kernels of queued blocks read the old tables: let them finish; delivered blocks of the old shape are forgotten
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (SampleSlot &c : h->slots)
+        if (c.state == 2 && (c.flags & SMOLMC_SAMPLE_STRUCTURE)) c.state = 0;
+    smolmc_sfac_free(h->sfac);
+    h->sfac = S;
+    return 0;
+}
+
+extern "C" int smolmc_structure_shape(smolmc_handle *h, int *n_points, int *n_kinds, int *n_intensities) {
+    if (!h) return fail("null handle");
+    if (n_points) *n_points = h->sfac.Q;
+    if (n_kinds) *n_kinds = h->sfac.Q ? h->sfac.K : 0;
+    if (n_intensities) *n_intensities = h->sfac.I;
+    return 0;
+}
+
+extern "C" int smolmc_eval_structure(smolmc_handle *h, const int32_t *occ, int nocc, int64_t *amp, double *inten) {
+    if (!h) return fail("null handle");
+    const SmolmcStruct &S = h->sfac;
+    if (!S.Q) return fail("no structure-factor spec set: call smolmc_set_structure first");
+    HIPCHK(hipSetDevice(h->device));
+    const uint8_t *d_occ8 = h->kp.occ;
+    if (occ) {
+        if (nocc <= 0) return 0;
+        TRY(ensure_eval_occ(h, nocc));
+        std::vector<int32_t> occ_engine;
+        occ = occ_in(h, occ, (size_t)nocc, occ_engine);
+        for (size_t r = 0; r < (size_t)nocc; ++r)
+            for (int s = 0; s < h->N; ++s) {
+                const int32_t b = S.kind_base[s], c = occ[r * h->N + s];
+                if (b >= 0 && c >= 0 && b + c >= S.K) {
+                    char msg[200];
+                    snprintf(msg, sizeof msg, "structure factors: occupancy code %d on site %d gives kind %d, n_kinds = %d: kind out of range",
+                             (int)c, h->relabelled ? (int)h->old_of[s] : s, (int)(b + c), S.K);
+                    return fail(msg);
+                }
+            }
+        TRY(upload_occ(h, occ, nocc, h->d_eval_occ));
+        d_occ8 = h->d_eval_occ;
+    } else {
+        nocc = h->R;
+    }
+    const size_t na = (size_t)nocc * S.Q * S.K * 2, ni = (size_t)nocc * S.I;
+    unsigned char *d_out = nullptr;
+    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>((na + ni) * 8, 16)));
+    int rc = smolmc_sfac_launch(h, d_occ8, (size_t)nocc, (long long *)d_out, (double *)(d_out + na * 8));
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (!rc && e == hipSuccess && amp) e = hipMemcpy(amp, d_out, na * 8, hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess && inten && ni) e = hipMemcpy(inten, d_out + na * 8, ni * 8, hipMemcpyDeviceToHost);
+    hipFree(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(std::string("eval_structure: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int smolmc_get_sample_structure(smolmc_handle *h, int64_t *amp, double *inten) {
+    if (!h) return fail("null handle");
+    SampleSlot *sl = next_delivery(h);
+    if (!sl) return fail("no samples recorded: call smolmc_run_sampled first");
+    if (!(sl->flags & SMOLMC_SAMPLE_STRUCTURE)) return fail("the structure factors were not recorded (flags bit 6)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(sl->copy_done));
+    const size_t rows = (size_t)sl->n * h->R;
+    if (amp) host_copy(amp, sl->hst + sl->o_amp, rows * (size_t)h->sfac.Q * h->sfac.K * 16);
+    if (inten) host_copy(inten, sl->hst + sl->o_inten, rows * (size_t)h->sfac.I * 8);
+    return 0;
 }
 
 extern "C" int smolmc_get_sample_observables(smolmc_handle *h, int32_t *counts, int32_t *pairs) {

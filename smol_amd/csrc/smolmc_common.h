@@ -756,6 +756,7 @@ struct SampleSlot {
     size_t used = 0;                            // bytes of the recorded block
     size_t o_H = 0, o_feat = 0, o_acc = 0, o_occ = 0, o_bias = 0, o_wlm = 0, o_wlS = 0, o_wlh = 0, o_wlo = 0, o_wlf = 0;
     size_t o_cnt = 0, o_pair = 0;               // SMOLMC_SAMPLE_OBSERVABLES: kind counts [rows x K], pair counts [rows x cells]
+    size_t o_amp = 0, o_inten = 0;              // SMOLMC_SAMPLE_STRUCTURE: amplitudes [rows x Q x K x 2] int64, intensities [rows x I]
     long long n = 0;                            // samples in the block
     int flags = 0;                              // SMOLMC_SAMPLE_* the block was recorded with
     int state = 0;                              // 0 empty, 1 recorded and not yet delivered, 2 delivered
@@ -821,6 +822,8 @@ struct SmolmcStat {
     int key = 0, C = 0, L = 0, n_bins = 0, hist_column = 0, n_weights = 0;
     int K = 0;                 // the kinds of the observables in force when the record was set
     int n_count_cols = 0;      // columns that read the kind counts
+    int I = 0;                 // the intensities of the structure-factor spec in force when the record was set
+    int n_inten_cols = 0;      // columns that read the intensities
     double hist_min = 0.0, hist_bin = 1.0;
     unsigned char *arena = nullptr;
     size_t record_bytes = 0;   // from n to the end of the accumulator arrays: what a reset zeroes
@@ -831,6 +834,27 @@ struct SmolmcStat {
     double *weights = nullptr;
     int32_t *u_counts = nullptr; // smolmc_update_statistics: counts [R x K]
     hipEvent_t ev[2] = {nullptr, nullptr}; // around the last reduction
+};
+
+// structure.hip: the structure-factor spec of a handle (smolmc_set_structure) as the kernel reads it, engine numbering
+struct SmolmcStruct {
+    int K = 0, Q = 0, M = 0, I = 0; // (Q == 0: none set)
+    int mask = 0;                   // 1: the bit-mask kernel (few cells per point), 0: the counter kernel
+    int W = 0;                      // 64-site words of a row
+    int copies = 1;                 // counter kernel: counter sets of a point in LDS (one per wave, or one)
+    int chunk = 1;                  // ... points counted per pass
+    size_t lds = 0;                 // dynamic LDS of a launch
+    std::vector<int32_t> kind_base; // host copy, engine numbering (validation of occupancies given by the caller)
+    unsigned char *arena = nullptr; // one device allocation, cut into the arrays below
+    int32_t *d_kind_base = nullptr;
+    uint16_t *d_phase = nullptr;    // [Q x N], engine numbering
+    long long *d_table = nullptr;   // [Q x M x 2]
+    unsigned long long *d_masks = nullptr; // mask kernel: [W x M x Q], bit j of word w: site 64 w + j is in class m at point q
+    int32_t *d_intensity = nullptr; // [I x 3]
+    double *d_scale = nullptr;      // [I]
+    long long *u_amp = nullptr;     // smolmc_update_statistics: amplitudes [R x Q x K x 2] ...
+    double *u_inten = nullptr;      // ... and intensities [R x I] of the walkers' current states
+    hipEvent_t ev[2] = {nullptr, nullptr}; // around the last launch of the kernel
 };
 
 struct smolmc_handle {
@@ -917,6 +941,8 @@ struct smolmc_handle {
     SmolmcMin minima;
     // running moments, blocking sums and a histogram of the samples (smolmc_set_statistics; statistics.hip)
     SmolmcStat stats;
+    // structure-factor amplitudes and intensities of occupancy rows (smolmc_set_structure, engine.hip; structure.hip)
+    SmolmcStruct sfac;
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
     SampleSlot slots[2];
@@ -1043,8 +1069,16 @@ void smolmc_min_free(smolmc_handle *h);
 // statistics.hip: offer `nsamples` samples of R rows each (enthalpy [rows], features [rows x F], counts [rows x K] or
 // null; device) to the handle's record, one kernel queued on the handle's stream: a workgroup per key walks the samples in
 // order.  Sample s gives key k the row s * R + w, w the walker that holds k when the kernel runs.
-int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, long long nsamples);
+// (d_inten: intensities [rows x I] or null, read by a record with intensity columns)
+int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, const double *d_inten,
+                       long long nsamples);
 void smolmc_stat_free(smolmc_handle *h);
+// structure.hip: amplitudes [rows x Q x K x 2] and intensities [rows x I] of `rows` occupancy rows (Npad bytes apart,
+// device) into device arrays, queued on the handle's stream; the kernel a spec takes and the layout of its LDS (false:
+// the row does not fit next to the counters of one point); the spec's device arrays
+int smolmc_sfac_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, long long *d_amp, double *d_inten);
+bool smolmc_sfac_plan(int N, int Npad, int K, int M, int Q, int *mask, int *copies, int *chunk, size_t *lds);
+void smolmc_sfac_free(SmolmcStruct &S);
 size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies);
 int smolmc_obs_pair_copies(size_t cells);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);

@@ -71,6 +71,10 @@ SYMBOLS = {
     "smolmc_update_statistics": (C.c_int, [_HP]),
     "smolmc_reset_statistics": (C.c_int, [_HP]),
     "smolmc_get_statistics": (C.c_int, [_HP, _i64p, _f64p, _f64p, _f64p, _u64p, _f64p, _f64p, _i64p, _i64p, _i64p, _i64p]),
+    "smolmc_set_structure": (C.c_int, [_HP, C.POINTER(capi.smolmc_structure)]),
+    "smolmc_structure_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 3),
+    "smolmc_eval_structure": (C.c_int, [_HP, _i32p, C.c_int, _i64p, _f64p]),
+    "smolmc_get_sample_structure": (C.c_int, [_HP, _i64p, _f64p]),
     "smolmc_replay": (C.c_int, [_HP, C.c_int64, _i32p, _f64p, _f64p, _u8p, _f64p, _f64p]),
     "smolmc_last_kernel_ms": (C.c_int, [_HP, C.POINTER(C.c_float)]),
     "smolmc_eval_full": (C.c_int, [_HP, _i32p, C.c_int, _f64p]),
@@ -605,6 +609,55 @@ class Engine:
         self._chk(fn(self._h, ms))
         return [float(x) for x in ms]
 
+    # ---- structure factors: fixed-point amplitudes and intensities on the device -------------
+    def set_structure_factor(self, sf):
+        """The structure-factor spec of this handle (smolmc_set_structure): a ``structure.StructureFactor`` in the caller's
+        site numbering, or None to remove it.  The engine copies and uploads; it refuses, naming the reason, a phase or
+        kind out of range, sizes beyond the ``capi.MAX_STRUCT_*`` limits, a table large enough to overflow an amplitude,
+        and a row too long for LDS."""
+        if sf is None:
+            self._chk(self._lib.smolmc_set_structure(self._h, None))
+        else:
+            if sf.num_sites != self.N:
+                raise ValueError(f"the structure factors are defined on {sf.num_sites} sites, the handle has {self.N}")
+            struct, keep = sf.c_struct()
+            self._chk(self._lib.smolmc_set_structure(self._h, C.byref(struct)))
+            del keep
+
+    def structure_shape(self):
+        """(n_points, n_kinds, n_intensities) in force, zeros when no spec is set (smolmc_structure_shape)."""
+        v = [C.c_int() for _ in range(3)]
+        self._chk(self._lib.smolmc_structure_shape(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def structure_factor(self, occupancies=None):
+        """(amp (n, Q, K, 2) int64, inten (n, I) float64) of occupancies (n, N) evaluated on the device
+        (smolmc_eval_structure), or, with None, of the walkers' current states (n = R)."""
+        Q, K, I = self.structure_shape()
+        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
+        n = self.R if occ is None else len(occ)
+        amp, inten = np.zeros((n, Q, K, 2), dtype=np.int64), np.zeros((n, I), dtype=np.float64)
+        self._chk(self._lib.smolmc_eval_structure(self._h, _p(occ, C.c_int32), n, _p(amp, C.c_int64), _p(inten, C.c_double)))
+        return amp, inten
+
+    def sample_structure(self):
+        """(structure_amplitudes (ns, R, Q, K, 2), structure_intensities (ns, R, I)) of the block ``fetch_samples`` would
+        deliver next; the block stays undelivered (smolmc_get_sample_structure)."""
+        Q, K, I = self.structure_shape()
+        _, ns, _ = self.pending_samples()
+        amp, inten = np.empty((ns, self.R, Q, K, 2), dtype=np.int64), np.empty((ns, self.R, I), dtype=np.float64)
+        self._chk(self._lib.smolmc_get_sample_structure(self._h, _p(amp, C.c_int64), _p(inten, C.c_double)))
+        return amp, inten
+
+    def structure_kernel_ms(self):
+        """Device time of the last launch of the structure kernel in ms (HIP events; a measuring hook of the library,
+        not part of the C-ABI)."""
+        fn = self._lib.smolmc_debug_structure_kernel_ms
+        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
+        ms = C.c_float()
+        self._chk(fn(self._h, C.byref(ms)))
+        return float(ms.value)
+
     # ---- statistics: running moments, blocking sums and a histogram, kept on the device -----
     def set_statistics(self, spec):
         """The statistics record of this handle (smolmc_set_statistics): a ``statistics.Statistics``, or None to remove
@@ -613,7 +666,7 @@ class Engine:
         if spec is None:
             self._chk(self._lib.smolmc_set_statistics(self._h, None))
         else:
-            struct, keep = spec.c_struct(self.F, self.observables_shape()[0])
+            struct, keep = spec.c_struct(self.F, self.observables_shape()[0], self.structure_shape()[2])
             self._chk(self._lib.smolmc_set_statistics(self._h, C.byref(struct)))
             del keep
         self.statistics_spec = spec
@@ -659,28 +712,31 @@ class Engine:
         return float(ms.value)
 
     def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False,
-                    minima=False, statistics=False):
+                    minima=False, statistics=False, structure=False):
         """Advance nsamples*thin_by steps recording one sample per walker every thin_by steps
         on the device; returns dict(enthalpy (ns,R), features (ns,R,F), accepted (ns,R) bool,
-        occupancy (ns,R,N) or None[, bias (ns,R)][, the Wang-Landau trace][, species_counts, pair_counts]).
+        occupancy (ns,R,N) or None[, bias (ns,R)][, the Wang-Landau trace][, species_counts, pair_counts]
+        [, structure_amplitudes (ns,R,Q,K,2) int64, structure_intensities (ns,R,I)]).
         Occupancies come back as int32 (the reference's trace dtype) or, with ``packed``, as the ring's own
         uint8 -- a quarter of the transfer.  = ``run_sampled_async`` + ``fetch_samples``."""
         self.run_sampled_async(nsamples, thin_by, occupancy=occupancy, bias=bias, wl=wl, observables=observables,
-                               minima=minima, statistics=statistics)
+                               minima=minima, statistics=statistics, structure=structure)
         return self.fetch_samples(packed=packed)
 
     def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False, observables=False, minima=False,
-                          statistics=False):
+                          statistics=False, structure=False):
         """Queue one block of the device ring (smolmc_run_sampled): returns at once.  The ring has two
         slots; queue block k + 1 BEFORE fetching block k and the download of k overlaps the kernel of
         k + 1 (the order ``fetch_samples`` delivers in: oldest first).  ``observables``: the kind and pair
         counts of ``set_observables`` for every row, counted on the device; with ``occupancy=False`` the
         occupancy rows they are counted from never leave it.  ``minima``: every row is offered to the record of
         ``set_minima`` when the block's launches are through; what the reduction reads and the caller did not ask for
-        stays on the device.  ``statistics``: likewise every row is offered to the record of ``set_statistics``."""
+        stays on the device.  ``statistics``: likewise every row is offered to the record of ``set_statistics``.
+        ``structure``: the amplitudes and intensities of ``set_structure_factor`` for every row, like ``observables``."""
         flags = ((capi.SAMPLE_OCCUPANCY if occupancy else 0) | (capi.SAMPLE_BIAS if bias else 0) |
                  (capi.SAMPLE_WL if wl else 0) | (capi.SAMPLE_OBSERVABLES if observables else 0) |
-                 (capi.SAMPLE_MINIMA if minima else 0) | (capi.SAMPLE_STATISTICS if statistics else 0))
+                 (capi.SAMPLE_MINIMA if minima else 0) | (capi.SAMPLE_STATISTICS if statistics else 0) |
+                 (capi.SAMPLE_STRUCTURE if structure else 0))
         self._chk(self._lib.smolmc_run_sampled(self._h, int(nsamples), int(thin_by), flags))
 
     def pending_samples(self):
@@ -707,6 +763,8 @@ class Engine:
         extra, obs = {}, {}
         if flags & capi.SAMPLE_OBSERVABLES:  # (read before the fetch marks the block delivered)
             obs["species_counts"], obs["pair_counts"] = self.sample_observables()
+        if flags & capi.SAMPLE_STRUCTURE:
+            obs["structure_amplitudes"], obs["structure_intensities"] = self.sample_structure()
         if flags & capi.SAMPLE_BIAS:
             extra["bias"] = np.empty((ns, self.R))
         if flags & capi.SAMPLE_WL:

@@ -1856,11 +1856,12 @@ class Sampler:
         self._minima = None         # minima.Minima: the lowest samples are kept on the device, or None
         self._minima_offers = 0     # samples offered to the record since it was last emptied
         self._statistics = None     # statistics.Statistics: moments, blocking sums and a histogram kept on the device, or None
+        self._structure = None      # structure.StructureFactor evaluated on the device for every sample, or None
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
                       nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, windows=None,
-                      observables=None, minima=None, statistics=None, **kwargs):
+                      observables=None, minima=None, statistics=None, structure_factor=None, **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
         'swap'; default kernel Metropolis; one kernel (seed) per walker.
 
@@ -1877,11 +1878,16 @@ class Sampler:
 
         ``statistics``: a ``statistics.Statistics`` -- every recorded sample is offered to a statistics record kept on the
         device (``Sampler.statistics``): running moments, blocking sums and a histogram per walker or per state point,
-        whether the trace is kept or not; count columns need ``observables`` too."""
+        whether the trace is kept or not; count columns need ``observables`` too, intensity columns ``structure_factor``.
+
+        ``structure_factor``: a ``structure.StructureFactor`` -- its amplitudes and intensities are evaluated on the device
+        for every sample and traced as ``structure_amplitudes`` (Q, K, 2) int64 and ``structure_intensities`` (I,)."""
         from . import parallel
 
         if windows is not None and observables is not None:
             raise ValueError("observables= with windows=: the samples of per-walker windows do not come from the sample ring")
+        if windows is not None and structure_factor is not None:
+            raise ValueError("structure_factor= with windows=: the samples of per-walker windows do not come from the sample ring")
         if windows is not None:
             sampler = cls._from_ensemble_windows(ensemble, windows, *args, step_type=step_type, kernel_type=kernel_type, seeds=seeds,
                                                  nwalkers=nwalkers, rank=rank, world_size=world_size, device=device, **kwargs)
@@ -1914,6 +1920,8 @@ class Sampler:
             sampler.set_chemical_potentials(chemical_potentials)
         if observables is not None:
             sampler._set_observables(observables)
+        if structure_factor is not None:
+            sampler._set_structure_factor(structure_factor)
         if minima is not None:
             sampler._set_minima(minima)
         if statistics is not None:
@@ -1923,6 +1931,8 @@ class Sampler:
     def _set_statistics(self, spec):
         if spec.count_columns() and self._observables is None:
             raise ValueError("a statistics record with count columns needs a sampler built with observables=")
+        if spec.intensity_columns() and self._structure is None:
+            raise ValueError("a statistics record with intensity columns needs a sampler built with structure_factor=")
         self._statistics = spec
         if self._engine is not None:
             self._engine.set_statistics(spec)
@@ -1997,6 +2007,23 @@ class Sampler:
         self._observables = obs
         if self._engine is not None:
             self._engine.set_observables(obs)
+
+    def _set_structure_factor(self, sf):
+        """Trace ``sf`` with every sample: the container's schema gains the two traces, its metadata their shape."""
+        nw, N = self.samples.shape
+        if sf.num_sites != N:
+            raise ValueError(f"the structure factors are defined on {sf.num_sites} sites, the ensemble has {N}")
+        if self.samples.num_samples:
+            raise ValueError("the container holds samples without the structure factors' traces: clear_samples() first")
+        Q, K, I = sf.n_points, sf.n_kinds, sf.n_intensities
+        self.samples._schema["structure_amplitudes"] = (np.dtype(np.int64), (nw, Q, K, 2))
+        self.samples._schema["structure_intensities"] = (np.dtype(np.float64), (nw, I))
+        self.samples.metadata["structure_factor"] = dict(
+            n_points=Q, n_kinds=K, n_intensities=I, bits=sf.bits, intensities=sf.intensity.tolist(),
+            intensity_scale=sf.intensity_scale.tolist(), points=None if sf.points is None else sf.points.tolist())
+        self._structure = sf
+        if self._engine is not None:
+            self._engine.set_structure_factor(sf)
 
     @classmethod
     def _from_ensemble_windows(cls, ensemble, wx, *args, step_type=None, kernel_type=None, seeds=None, nwalkers=1, rank=None,
@@ -2203,6 +2230,8 @@ class Sampler:
             if self._minima is not None:  # (a new handle starts an empty record)
                 self._engine.set_minima(self._minima)
                 self._minima_offers = 0
+            if self._structure is not None:  # (before the statistics record: its intensity columns name this spec)
+                self._engine.set_structure_factor(self._structure)
             if self._statistics is not None:  # (likewise)
                 self._engine.set_statistics(self._statistics)
             if self._wl_windows is not None:  # (kernel e was built with estimator e's window: cfg holds window 0)
@@ -2281,6 +2310,8 @@ class Sampler:
             tr.mod_factor = wl["mod_factor"].reshape(nw, 1)
         if self._observables is not None:
             tr.species_counts, tr.pair_counts = eng.observables()
+        if self._structure is not None:
+            tr.structure_amplitudes, tr.structure_intensities = eng.structure_factor()
         return tr
 
     def _sample_blocks(self, nsteps, initial_occupancies, thin_by, max_block=0, state_loaded=False, keep_occupancy=True):
@@ -2332,6 +2363,9 @@ class Sampler:
         per_sample = nw * ((N if keep_occupancy else 0) + 8 * F + 17)
         if obs is not None:
             per_sample += nw * 4 * (obs.n_kinds + obs.n_shells * obs.n_kinds ** 2)
+        sf = self._structure
+        if sf is not None:
+            per_sample += nw * 8 * (2 * sf.n_points * sf.n_kinds + sf.n_intensities)
         if is_wl:
             L = len(k0._levels)
             per_sample += nw * L * (24 + 8 * F)
@@ -2347,7 +2381,8 @@ class Sampler:
 
         def queue(n):
             eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl, observables=obs is not None,
-                                  minima=self._minima is not None, statistics=self._statistics is not None)
+                                  minima=self._minima is not None, statistics=self._statistics is not None,
+                                  structure=sf is not None)
             if self._minima is not None:
                 self._minima_offers += n
 
@@ -2390,6 +2425,8 @@ class Sampler:
                              cumulative_mean_features=ring["mean_features"], mod_factor=ring["mod_factor"][..., None])
             if "species_counts" in ring:
                 block.update(species_counts=ring["species_counts"], pair_counts=ring["pair_counts"])
+            if "structure_amplitudes" in ring:
+                block.update(structure_amplitudes=ring["structure_amplitudes"], structure_intensities=ring["structure_intensities"])
             yield block
 
     def _wl_run_with_host_checks(self, eng, nsteps):
@@ -2471,8 +2508,8 @@ class Sampler:
         leave the device -- their species and pair counts do; the container stores the occupancy of the final
         sample of this call alone, so ``last_occupancy`` and a continuation work as before."""
         if not keep_occupancy:
-            if self._observables is None and self._minima is None:
-                raise ValueError("keep_occupancy=False needs a sampler built with observables= or minima=: nothing else of the "
+            if self._observables is None and self._minima is None and self._structure is None:
+                raise ValueError("keep_occupancy=False needs a sampler built with observables=, minima= or structure_factor=: nothing else of the "
                                  "occupancies would be recorded")
             if stream_chunk > 0:
                 raise ValueError("keep_occupancy=False with stream_chunk: every part of a stream holds its occupancies")

@@ -49,6 +49,11 @@ def feature(i):
     return ("feature", int(i))
 
 
+def intensity(i):
+    """Intensity ``i`` of the structure-factor spec in force (``structure.StructureFactor``)."""
+    return ("intensity", int(i))
+
+
 def kind(observables, name_or_k):
     """Count column of kind ``name_or_k`` of ``observables`` (an ``observables.Observables``): a kind number, or a name
     looked up in ``observables.kind_names`` when it has them."""
@@ -96,9 +101,10 @@ class Statistics:
     n_weights = property(lambda self: 0 if self.weights is None else len(self.weights))
     n_pairs = property(lambda self: self.n_columns * (self.n_columns + 1) // 2)
 
-    def sources(self, n_features, n_kinds):
-        """int32 column sources of the C ABI: 0 enthalpy, 1 + i feature i, 1 + F + k kind k, 1 + F + K the weighted sum."""
-        F, K = int(n_features), int(n_kinds)
+    def sources(self, n_features, n_kinds, n_intensities=0):
+        """int32 column sources of the C ABI: 0 enthalpy, 1 + i feature i, 1 + F + k kind k, 1 + F + K the weighted sum,
+        2 + F + K + i intensity i (i < ``n_intensities``)."""
+        F, K, I = int(n_features), int(n_kinds), int(n_intensities)
         out = []
         for c in self.columns:
             if c[0] == "enthalpy":
@@ -109,6 +115,10 @@ class Statistics:
                 out.append(1 + F + c[1])
             elif c[0] == "energy":
                 out.append(1 + F + K)
+            elif c[0] == "intensity":
+                if not 0 <= c[1] < I:
+                    raise ValueError(f"intensity {c[1]} outside the {I} intensities of the structure-factor spec")
+                out.append(2 + F + K + c[1])
             else:
                 out.append(c[1])
         return np.asarray(out, dtype=np.int32)
@@ -117,14 +127,20 @@ class Statistics:
         """Indices into ``columns`` of the kind counts, in order."""
         return [i for i, c in enumerate(self.columns) if c[0] == "kind"]
 
-    def column_values(self, enthalpy, features, counts=None):
-        """x (..., C) float64 of rows with enthalpy (...), features (..., F), counts (..., K) or None."""
+    def intensity_columns(self):
+        """Indices into ``columns`` of the intensities, in order."""
+        return [i for i, c in enumerate(self.columns) if c[0] == "intensity"]
+
+    def column_values(self, enthalpy, features, counts=None, intensities=None):
+        """x (..., C) float64 of rows with enthalpy (...), features (..., F), counts (..., K) or None, intensities
+        (..., I) or None."""
         H = np.asarray(enthalpy, dtype=np.float64)
         f = np.asarray(features, dtype=np.float64).reshape(H.shape + (-1,))
         F = f.shape[-1]
         K = 0 if counts is None else np.asarray(counts).shape[-1]
+        I = 0 if intensities is None else np.asarray(intensities).shape[-1]
         x = np.empty(H.shape + (self.n_columns,))
-        for j, src in enumerate(self.sources(F, K)):
+        for j, src in enumerate(self.sources(F, K, I)):
             if src == 0:
                 x[..., j] = H
             elif src <= F:
@@ -133,15 +149,17 @@ class Statistics:
                 x[..., j] = np.asarray(counts).reshape(H.shape + (K,))[..., src - 1 - F].astype(np.float64)
             elif src == 1 + F + K:
                 x[..., j] = weighted_value(self.weights if self.weights is not None else np.zeros(0), f)
+            elif src <= 1 + F + K + I:
+                x[..., j] = np.asarray(intensities, dtype=np.float64).reshape(H.shape + (I,))[..., src - 2 - F - K]
             else:
-                raise ValueError(f"column source {src} outside 0..{1 + F + K}")
+                raise ValueError(f"column source {src} outside 0..{1 + F + K + I}")
         return x
 
-    def c_struct(self, n_features, n_kinds):
+    def c_struct(self, n_features, n_kinds, n_intensities=0):
         """(capi.smolmc_statistics, the arrays it points to)."""
         from . import capi
 
-        cols = self.sources(n_features, n_kinds)
+        cols = self.sources(n_features, n_kinds, n_intensities)
         keep = (cols, self.weights)
         s = capi.smolmc_statistics(
             self.key, len(cols), cols.ctypes.data_as(C.POINTER(C.c_int32)) if len(cols) else None, self.n_weights,
@@ -179,7 +197,7 @@ class StatisticsRecord:
     n_keys = property(lambda self: len(self.n))
 
     # ---- the definition ------------------------------------------------------------------------------------------
-    def offer(self, enthalpy, features, counts=None, key_of_row=None):
+    def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None):
         """Offer samples (ns, R) -- or one sample (R,) -- in order.  ``key_of_row`` (R,) or (ns, R): the key of every
         row, a permutation of 0 .. R - 1 per sample (None: the walker).  Vectorised over the keys, a loop over samples."""
         spec = self.spec
@@ -188,7 +206,8 @@ class StatisticsRecord:
         ns = len(H)
         f = np.asarray(features, dtype=np.float64).reshape(ns, nk, -1)
         cnt = None if counts is None else np.asarray(counts).reshape(ns, nk, -1)
-        x_all = spec.column_values(H, f, cnt)
+        inten = None if intensities is None else np.asarray(intensities, dtype=np.float64).reshape(ns, nk, -1)
+        x_all = spec.column_values(H, f, cnt, inten)
         if key_of_row is None:
             keys = np.broadcast_to(np.arange(nk), (ns, nk))
         else:
