@@ -597,6 +597,61 @@ int smolmc_eval_structure(smolmc_handle *h, const int32_t *occ /* nocc x N, or N
  * not mark it delivered, like smolmc_get_sample_observables; an error when that block was recorded without the flag. */
 int smolmc_get_sample_structure(smolmc_handle *h, int64_t *amp, double *inten);
 
+/* ---- connectivity: connected components of sampled states and whether they span the cell, on the device ---------------
+ * (no reference counterpart).  Kinds as in smolmc_observables.  A spec holds G graphs.  Graph g has member kinds (bit k
+ * of the 256-bit row member_mask[g]) and the bonds bond_ptr[g] .. bond_ptr[g + 1]: bond (i, j, w) joins site i of the home
+ * cell to site j of the periodic image displaced by w[0] S_0 + w[1] S_1 + w[2] S_2, S_a the supercell vectors.  A site is
+ * a member when its kind is one; a bond is active when both ends are members.  Duplicate rows, rows i == j with w != 0 and
+ * rows that join the same sites by different images are legal.  Components are the connected components of the members
+ * under the active bonds; a component wraps axis a when the image sum over one of its closed paths has a nonzero entry a.
+ * Per occupancy row and graph: the SMOLMC_CONN_STATS numbers below, and per site the smallest site number of its
+ * component (-1: no member).  Everything is integer; smol_amd/connectivity.py is the same in NumPy and the device matches
+ * it entry for entry.  Site numbers are the caller's.  The engine copies and uploads everything. */
+#define SMOLMC_MAX_CONN_GRAPHS 8
+#define SMOLMC_MAX_CONN_IMAGE 7       /* |w[a]| of a bond */
+#define SMOLMC_MAX_CONN_PATH_SUM 32767 /* the kernel keeps the image sum of a path in 16 bits an axis: N x
+                                        * SMOLMC_MAX_CONN_IMAGE must not exceed it (N <= 4681) */
+#define SMOLMC_CONN_STATS 24          /* numbers per row and graph: */
+#define SMOLMC_CONN_N_MEMBERS 0
+#define SMOLMC_CONN_N_COMPONENTS 1
+#define SMOLMC_CONN_LARGEST 2         /* size of the largest component, 0 if none */
+#define SMOLMC_CONN_SUM_SQ 3          /* sum of size^2 */
+#define SMOLMC_CONN_N_WRAPPING 4      /* components that wrap any axis */
+#define SMOLMC_CONN_WRAPPING_SITES 5  /* members in wrapping components */
+#define SMOLMC_CONN_WRAP_AXES 6       /* OR over the components of their 3-bit axis mask */
+#define SMOLMC_CONN_LARGEST_WRAP_AXES 7 /* axis mask of the largest component; among equals the one with the smallest label */
+#define SMOLMC_CONN_HIST 8            /* 8 + b, b = 0..15: components with floor(log2 size) == b */
+typedef struct smolmc_connectivity {
+    int n_kinds;
+    const int32_t *kind_base;      /* [N] */
+    int n_graphs;
+    const uint64_t *member_mask;   /* [G x 4], bit k: kind k is a member */
+    const int64_t *bond_ptr;       /* [G + 1] */
+    const int32_t *bonds;          /* [nb x 2] */
+    const int8_t *images;          /* [nb x 3] */
+} smolmc_connectivity;
+/* Sets (NULL: removes) the connectivity spec of the handle.  Refused, each naming its reason: a bond out of range; a site
+ * with kind_base[s] + (species codes on s) > n_kinds, or a member kind >= n_kinds; n_kinds outside 1..254; G outside
+ * 1..SMOLMC_MAX_CONN_GRAPHS; an image beyond SMOLMC_MAX_CONN_IMAGE; N x SMOLMC_MAX_CONN_IMAGE > SMOLMC_MAX_CONN_PATH_SUM
+ * or a row whose labels, path sums and sizes do not fit the LDS of one workgroup (rows of 4096 sites fit); while a block
+ * recorded with SMOLMC_SAMPLE_CONNECTIVITY waits in the ring; while a statistics record with connectivity columns is set.
+ * A refused call leaves the handle's spec as it was. */
+int smolmc_set_connectivity(smolmc_handle *h, const smolmc_connectivity *s);
+/* G and K in force (both 0: none set) */
+int smolmc_connectivity_shape(smolmc_handle *h, int *n_graphs, int *n_kinds);
+/* stats [nocc x G x 24] and labels [nocc x G x N] of nocc occupancies (host, int32 like smolmc_eval_full), or, with
+ * occ == NULL, of the walkers' current states (nocc = R then).  Either output may be NULL. */
+int smolmc_eval_connectivity(smolmc_handle *h, const int32_t *occ /* nocc x N, or NULL */, int nocc, int64_t *stats, int32_t *labels);
+/* With SMOLMC_SAMPLE_CONNECTIVITY (128, flags bit 7) smolmc_run_sampled adds the column [rows x G x 24] (int64) to the
+ * block, filled on the device from the block's occupancy rows when its launches are through; without
+ * SMOLMC_SAMPLE_OCCUPANCY those rows never leave the device.  The ring carries no labels: smolmc_eval_connectivity gives
+ * them.  The flag is refused while no spec is set.  This call reads the column of the block the next smolmc_get_samples*
+ * call delivers ([nsamples x R x G x 24]) and does not mark it delivered, like smolmc_get_sample_structure; an error when
+ * that block was recorded without the flag.  In a statistics record the column sources 2 + F + K + I + 24 g + c read
+ * stats[g][c] as a double (with no spec set the range ends where it ends without). */
+#define SMOLMC_SAMPLE_CONNECTIVITY 128
+int smolmc_get_sample_connectivity(smolmc_handle *h, int64_t *stats);
+
 /* Same loop driven by host-provided proposals ("replay mode"): what
  * StandardSingleStepMixin.single_step (kernel/base.py:145-166) does after mcusher.propose_step
  * returned, with the numbers the reference's Generator produced.

@@ -54,6 +54,22 @@ def structure_plan(n_sites, npad, n_kinds, n_phases, n_points):
         return None
     copies = STRUCT_WAVES if npad + 4 * STRUCT_WAVES * cells <= STRUCT_LDS_BYTES else 1
     return "counters", copies, min((STRUCT_LDS_BYTES - npad) // (4 * copies * cells), n_points)
+SAMPLE_CONNECTIVITY = 128       # ... the connectivity stats of every row (smolmc_set_connectivity)
+MAX_CONN_GRAPHS = 8             # SMOLMC_MAX_CONN_GRAPHS
+MAX_CONN_IMAGE = 7              # SMOLMC_MAX_CONN_IMAGE
+MAX_CONN_PATH_SUM = 32767       # SMOLMC_MAX_CONN_PATH_SUM: n_sites x MAX_CONN_IMAGE must not exceed it
+CONN_STATS = 24                 # SMOLMC_CONN_STATS
+CONN_WAVES = 4                  # the waves of one workgroup of the connectivity kernel
+CONN_LDS_BYTES = 65536          # the LDS of one workgroup of the connectivity kernel (connectivity.hip)
+
+
+def connectivity_lds_bytes(n_sites, npad):
+    """The LDS a row of ``n_sites`` sites in ``npad`` bytes takes in the connectivity kernel (smolmc_conn_lds_bytes in
+    csrc/connectivity.hip): a 64-bit word, a 16-bit size and a mask byte per site next to the row, and the partial sums of
+    four waves; None when that is more than one workgroup has."""
+    up4 = lambda v: (v + 3) // 4 * 4  # noqa: E731
+    b = 8 * n_sites + npad + up4(2 * n_sites) + up4(n_sites) + (CONN_WAVES * CONN_STATS + 4) * 4
+    return b if b <= CONN_LDS_BYTES else None
 MAX_STEP_FLIPS = 8              # SMOLMC_MAX_STEP_FLIPS
 STEP_ROW = 2 * MAX_STEP_FLIPS   # SMOLMC_STEP_ROW: int32 per step record (site, code) x 8, -1 = no flip
 
@@ -200,6 +216,20 @@ class smolmc_structure(C.Structure):
         ("n_intensities", C.c_int),
         ("intensity", _i32p),
         ("intensity_scale", _f64p),
+    ]
+
+
+class smolmc_connectivity(C.Structure):
+    """Mirror of ``smolmc_connectivity`` (include/smolmc.h); ``connectivity.Connectivity.c_struct`` fills it."""
+
+    _fields_ = [
+        ("n_kinds", C.c_int),
+        ("kind_base", _i32p),
+        ("n_graphs", C.c_int),
+        ("member_mask", C.POINTER(C.c_uint64)),
+        ("bond_ptr", _i64p),
+        ("bonds", _i32p),
+        ("images", C.POINTER(C.c_int8)),
     ]
 
 

@@ -1,0 +1,378 @@
+"""Connectivity of sampled states: connected components of the sites of chosen kinds, and whether they span the cell.
+
+This module is the DEFINITION: ``Connectivity.evaluate`` in NumPy is what the device kernel (csrc/connectivity.hip,
+``smolmc_eval_connectivity`` and the ``SMOLMC_SAMPLE_CONNECTIVITY`` column of the sample ring) matches entry for entry.
+Everything is integer, so host and device agree bit for bit.
+
+The *kind* of (site, code) is ``kind_base[site] + code`` as in ``observables.Observables``; ``kind_base[site] = -1`` leaves
+the site out.  A spec holds 1..8 *graphs*.  A graph has a set of member kinds -- a site is a *member* in an occupancy when
+its kind is in the set -- and bonds ``(i, j, w)``: site i of the home cell is joined to site j of the periodic image
+displaced by ``w[0] S_0 + w[1] S_1 + w[2] S_2``, ``S_a`` the supercell vectors.  A bond is *active* when both ends are
+members.  Duplicate rows, rows ``i == j`` with ``w != 0`` (a site bonded to its own image, in aliased cells) and two rows
+joining the same sites by different images mean what they say.
+
+*Components* are the connected components of the members under the active bonds.  The *winding set* of a component is
+the set of image sums over its closed paths, a subgroup of Z^3; the component *wraps axis a* when an element of the set
+has a nonzero entry a.  However it is computed: give every site the image sum ``off`` along some path from one site of the
+component, form ``m = off[i] + w - off[j]`` for each active bond; axis a wraps iff some ``m[a] != 0``.
+
+    stats   (n, G, 24) int64   the columns below
+    labels  (n, G, N)  int32   the smallest site number of the site's component, -1 for a non-member
+"""
+
+from __future__ import annotations
+
+import itertools
+from collections import deque
+
+import numpy as np
+
+from .observables import MAX_KINDS, Observables
+
+MAX_GRAPHS = 8        # SMOLMC_MAX_CONN_GRAPHS
+MAX_IMAGE = 7         # SMOLMC_MAX_CONN_IMAGE: |w_a| of a bond
+MAX_PATH_SUM = 32767  # the device keeps a path sum per axis in 16 bits: N x MAX_IMAGE must stay at or below this
+N_STATS = 24          # SMOLMC_CONN_STATS
+SITE_TOL = 1e-6       # two distances (in units of the lattice's length) are the same within this
+
+# columns of stats
+N_MEMBERS, N_COMPONENTS, LARGEST, SUM_SQ, N_WRAPPING, WRAPPING_SITES, WRAP_AXES, LARGEST_WRAP_AXES, HIST0 = range(9)
+N_HIST = 16           # HIST0 + b: components with floor(log2 size) == b
+
+
+class Graph:
+    """One graph: ``members`` kinds, ``bonds`` (nb, 2) site pairs and ``images`` (nb, 3) of each bond."""
+
+    def __init__(self, members, bonds, images=None):
+        self.members = sorted({int(k) for k in members})
+        b = np.asarray(bonds)
+        if b.size == 0:
+            b = np.zeros((0, 2), dtype=np.int32)
+        if b.ndim != 2 or b.shape[1] != 2 or not np.issubdtype(b.dtype, np.integer):
+            raise ValueError("bonds must be an (nbonds, 2) integer array")
+        w = np.zeros((len(b), 3), dtype=np.int64) if images is None else np.asarray(images)
+        if w.size == 0:
+            w = np.zeros((0, 3), dtype=np.int64)
+        if w.shape != (len(b), 3) or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError("images must be an (nbonds, 3) integer array, one row per bond")
+        if np.abs(w).max(initial=0) > MAX_IMAGE:
+            raise ValueError(f"a bond's image reaches {int(np.abs(w).max())}, beyond MAX_IMAGE = {MAX_IMAGE}: image out of range")
+        self.bonds = np.ascontiguousarray(b, dtype=np.int32)
+        self.images = np.ascontiguousarray(w, dtype=np.int8)
+
+
+class Connectivity:
+    """Kinds and graphs of one supercell.
+
+    kind_base    (N,) integers, -1 = the site is in no graph
+    n_kinds      K
+    graphs       1..8 ``Graph`` objects, or dicts / tuples of their arguments (members, bonds, images)
+    site_ncodes  optional (N,): species codes each site can hold; with it every kind is checked to stay below K
+    """
+
+    def __init__(self, kind_base, n_kinds, graphs, site_ncodes=None):
+        kb = np.asarray(kind_base)
+        if kb.ndim != 1 or not np.issubdtype(kb.dtype, np.integer):
+            raise ValueError("kind_base must be a 1-D integer array, one entry per site")
+        self.kind_base = np.ascontiguousarray(np.where(kb < 0, -1, kb), dtype=np.int32)
+        self.num_sites = N = len(self.kind_base)
+        self.n_kinds = K = int(n_kinds)
+        if not 1 <= K <= MAX_KINDS:
+            raise ValueError(f"n_kinds must be 1..{MAX_KINDS}, got {K}")
+        if self.kind_base.max(initial=-1) >= K:
+            raise ValueError(f"kind_base holds {int(self.kind_base.max())}, n_kinds is {K}: kind out of range")
+        if N * MAX_IMAGE > MAX_PATH_SUM:
+            raise ValueError(f"{N} sites x MAX_IMAGE = {MAX_IMAGE} is larger than {MAX_PATH_SUM}: a path sum could overflow")
+        self.graphs = []
+        for g in graphs:
+            if isinstance(g, dict):
+                g = Graph(g["members"], g["bonds"], g.get("images"))
+            elif not isinstance(g, Graph):
+                g = Graph(*g)
+            self.graphs.append(g)
+        self.n_graphs = G = len(self.graphs)
+        if not 1 <= G <= MAX_GRAPHS:
+            raise ValueError(f"n_graphs must be 1..{MAX_GRAPHS}, got {G}")
+        for gi, g in enumerate(self.graphs):
+            if g.members and not 0 <= min(g.members) <= max(g.members) < K:
+                raise ValueError(f"graph {gi}: member kind {max(g.members) if max(g.members) >= K else min(g.members)}, "
+                                 f"n_kinds is {K}: kind out of range")
+            if g.bonds.min(initial=0) < 0 or g.bonds.max(initial=0) >= N:
+                raise ValueError(f"graph {gi}: bond out of range ({N} sites)")
+        self.site_ncodes = None
+        if site_ncodes is not None:
+            nc = np.asarray(site_ncodes, dtype=np.int64)
+            if nc.shape != (N,) or nc.min(initial=1) < 1:
+                raise ValueError("site_ncodes must hold one positive entry per site")
+            counted = self.kind_base >= 0
+            top = self.kind_base[counted] + nc[counted]
+            if top.max(initial=0) > K:
+                s = int(np.flatnonzero(counted)[np.argmax(top)])
+                raise ValueError(f"kind_base[{s}] + site_ncodes[{s}] = {int(self.kind_base[s])} + {int(nc[s])} is larger than "
+                                 f"n_kinds = {K}: kind out of range")
+            self.site_ncodes = nc.astype(np.int32)
+        self._adjacency = None
+
+    # ---- constructors -------------------------------------------------------------------------------------------
+    @classmethod
+    def from_supercell(cls, sc, graphs, site_classes=None, observables=None):
+        """Graphs built from the geometry of a ``synth`` or ``mson`` supercell.
+
+        Each graph is ``dict(members=[kinds or species names], cutoff=r)`` -- every pair of sites at most ``r`` apart is
+        bonded -- or ``dict(members=..., orbits=[pair orbit ids])`` -- the pairs at the distances of those orbits.  The
+        bonds come from the lattice, the fractional coordinates and ``scmatrix``, not from ``full_indices``: every
+        ``(i, j, w)`` with ``|r_j + w.S - r_i|`` equal to a wanted distance within ``SITE_TOL``, except ``i == j`` with
+        ``w == 0``.  Each undirected bond so appears in both directions; small and aliased cells get their self-image and
+        multi-image bonds.  Kinds: the default kinds of ``Observables.default_kind_base(sc)``, split by ``site_classes`` as
+        ``Observables.from_supercell`` does, or those of ``observables``.  A species name stands for its kind on every
+        sublattice that holds the species."""
+        if observables is not None:
+            if site_classes is not None:
+                raise ValueError("give site_classes or observables, not both")
+            kind_base, K, ncodes = observables.kind_base, observables.n_kinds, observables.site_ncodes
+        elif site_classes is not None:
+            o = Observables.from_supercell(sc, orbits=(), site_classes=site_classes)
+            kind_base, K, ncodes = o.kind_base, o.n_kinds, o.site_ncodes
+        else:
+            kind_base, K, ncodes = Observables.default_kind_base(sc)
+        prim = sc.model.prim
+        species = getattr(prim, "species", None)
+        site_b = np.asarray(sc.site_b, dtype=np.int64)
+        made = []
+        for gi, g in enumerate(graphs):
+            members = set()
+            for m in g["members"]:
+                if isinstance(m, str):
+                    hits = set()
+                    for s in range(sc.num_sites):
+                        names = species[int(site_b[s])] if species is not None else None
+                        if names is not None and m in names and kind_base[s] >= 0:
+                            hits.add(int(kind_base[s]) + list(names).index(m))
+                    if not hits:
+                        raise ValueError(f"graph {gi}: no counted site holds a species named {m!r}")
+                    members |= hits
+                else:
+                    members.add(int(m))
+            if ("cutoff" in g) == ("orbits" in g):
+                raise ValueError(f"graph {gi}: give cutoff= or orbits=, one of them")
+            if "cutoff" in g:
+                bonds, images = geometric_bonds(sc, cutoff=float(g["cutoff"]))
+            else:
+                want = []
+                for orb in sc.model.orbits:
+                    if orb.id in g["orbits"]:
+                        if getattr(orb, "size", None) != 2 and getattr(orb, "num_sites", 2) != 2:
+                            raise ValueError(f"graph {gi}: orbit {orb.id} is no pair orbit")
+                        want.append(float(orb.diameter))
+                if len(want) != len(set(g["orbits"])):
+                    raise ValueError(f"graph {gi}: orbits {sorted(g['orbits'])} are not all orbits of the model")
+                bonds, images = geometric_bonds(sc, distances=want)
+            made.append(Graph(members, bonds, images))
+        return cls(kind_base, K, made, site_ncodes=ncodes)
+
+    # ---- the definition ------------------------------------------------------------------------------------------
+    def kinds_of(self, occupancies):
+        """(..., N) int64 kinds of occupancies (..., N); -1 where the site is not counted."""
+        occ = np.asarray(occupancies)
+        if occ.shape[-1:] != (self.num_sites,) or not np.issubdtype(occ.dtype, np.integer):
+            raise ValueError(f"occupancies must be integer arrays with {self.num_sites} sites in the last axis")
+        kinds = np.where(self.kind_base >= 0, self.kind_base.astype(np.int64) + occ, -1)
+        if occ.min(initial=0) < 0 or kinds.max(initial=-1) >= self.n_kinds:
+            raise ValueError("an occupancy code gives a kind out of range")
+        return kinds
+
+    def _neighbours(self):
+        """Per graph, per site: the list of (neighbour, image as seen from the site) over the bonds, both ways."""
+        if self._adjacency is None:
+            self._adjacency = []
+            for g in self.graphs:
+                adj = [[] for _ in range(self.num_sites)]
+                for (i, j), w in zip(g.bonds.tolist(), g.images.tolist()):
+                    adj[i].append((j, w[0], w[1], w[2]))
+                    adj[j].append((i, -w[0], -w[1], -w[2]))
+                self._adjacency.append(adj)
+        return self._adjacency
+
+    def evaluate(self, occupancies):
+        """(stats (..., G, 24) int64, labels (..., G, N) int32) of occupancies (..., N): a breadth-first search from
+        every member not yet reached, in the order of the site numbers -- so the start is the component's label."""
+        kinds = self.kinds_of(occupancies)
+        lead = kinds.shape[:-1]
+        kinds = kinds.reshape(-1, self.num_sites)
+        n, G, N = len(kinds), self.n_graphs, self.num_sites
+        stats = np.zeros((n, G, N_STATS), dtype=np.int64)
+        labels = np.full((n, G, N), -1, dtype=np.int32)
+        for gi, (g, adj) in enumerate(zip(self.graphs, self._neighbours())):
+            is_member = np.zeros(self.n_kinds + 1, dtype=bool)
+            is_member[g.members] = True
+            for r in range(n):
+                member = is_member[kinds[r]].tolist()  # (kind -1 reads the spare entry: no member)
+                label, st = labels[r, gi], stats[r, gi]
+                off = [None] * N
+                best = (0, 0)  # (size, -label) of the largest component so far
+                for start in range(N):
+                    if not member[start] or off[start] is not None:
+                        continue
+                    off[start] = (0, 0, 0)
+                    queue, size, axes = deque([start]), 0, 0
+                    while queue:
+                        i = queue.popleft()
+                        label[i] = start
+                        size += 1
+                        oi = off[i]
+                        for j, wx, wy, wz in adj[i]:
+                            if not member[j]:
+                                continue
+                            reach = (oi[0] + wx, oi[1] + wy, oi[2] + wz)
+                            if off[j] is None:
+                                off[j] = reach
+                                queue.append(j)
+                            elif off[j] != reach:
+                                axes |= (reach[0] != off[j][0]) | (reach[1] != off[j][1]) << 1 | (reach[2] != off[j][2]) << 2
+                    st[N_MEMBERS] += size
+                    st[N_COMPONENTS] += 1
+                    st[SUM_SQ] += size * size
+                    st[HIST0 + size.bit_length() - 1] += 1
+                    if axes:
+                        st[N_WRAPPING] += 1
+                        st[WRAPPING_SITES] += size
+                        st[WRAP_AXES] |= axes
+                    if size > best[0]:  # (among equals the first, which has the smallest label)
+                        best = (size, -start)
+                        st[LARGEST] = size
+                        st[LARGEST_WRAP_AXES] = axes
+        return stats.reshape(lead + (G, N_STATS)), labels.reshape(lead + (G, N))
+
+    # ---- the C struct ------------------------------------------------------------------------------------------
+    def member_masks(self):
+        """(G, 4) uint64: bit k of the 256-bit row g says kind k is a member of graph g."""
+        mask = np.zeros((self.n_graphs, 4), dtype=np.uint64)
+        for gi, g in enumerate(self.graphs):
+            for k in g.members:
+                mask[gi, k >> 6] |= np.uint64(1) << np.uint64(k & 63)
+        return mask
+
+    def c_struct(self):
+        """(capi.smolmc_connectivity, the arrays it points at -- keep them alive during the call)."""
+        import ctypes as C
+
+        from . import capi
+
+        mask = self.member_masks()
+        ptr = np.concatenate(([0], np.cumsum([len(g.bonds) for g in self.graphs]))).astype(np.int64)
+        bonds = np.ascontiguousarray(np.concatenate([g.bonds for g in self.graphs]), dtype=np.int32)
+        images = np.ascontiguousarray(np.concatenate([g.images for g in self.graphs]), dtype=np.int8)
+        s = capi.smolmc_connectivity()
+        s.n_kinds, s.n_graphs = self.n_kinds, self.n_graphs
+        s.kind_base = self.kind_base.ctypes.data_as(C.POINTER(C.c_int32))
+        s.member_mask = mask.ctypes.data_as(C.POINTER(C.c_uint64))
+        s.bond_ptr = ptr.ctypes.data_as(C.POINTER(C.c_int64))
+        s.bonds = bonds.ctypes.data_as(C.POINTER(C.c_int32))
+        s.images = images.ctypes.data_as(C.POINTER(C.c_int8))
+        return s, (self.kind_base, mask, ptr, bonds, images)
+
+    def to_metadata(self):
+        """What a container's metadata keeps of the spec (``moca.Sampler``): its shape and the member kinds."""
+        return dict(n_graphs=self.n_graphs, n_kinds=self.n_kinds, members=[list(g.members) for g in self.graphs],
+                    n_bonds=[int(len(g.bonds)) for g in self.graphs])
+
+
+# ---- geometry -----------------------------------------------------------------------------------------------------------
+def geometric_bonds(sc, cutoff=None, distances=None):
+    """(bonds (nb, 2) int32, images (nb, 3) int8) of a ``synth`` or ``mson`` supercell: every (i, j, w) with
+    ``|r_j + w.S - r_i|`` at most ``cutoff`` -- or equal to one of ``distances`` -- within ``SITE_TOL``, except i == j
+    with w == 0; rows ordered by i, then by the displacement.  An image beyond ``MAX_IMAGE`` is refused."""
+    from .structure import lattice_points_of
+
+    prim = sc.model.prim
+    L = np.asarray(prim.lattice, dtype=np.float64)
+    tau = np.asarray(prim.frac_coords, dtype=np.float64)
+    S = np.asarray(sc.scmatrix, dtype=np.int64)
+    if S.ndim == 1:
+        S = np.diag(S)
+    n = lattice_points_of(sc)
+    P, N = len(n), int(sc.num_sites)
+    site_b = np.asarray(sc.site_b, dtype=np.int64)
+    site_t = np.asarray(getattr(sc, "site_t", np.arange(N) % P), dtype=np.int64)
+    Sinv = np.linalg.inv(S.astype(np.float64))
+    det = int(round(abs(np.linalg.det(S.astype(np.float64)))))
+
+    def cell_key(points):  # the class of a lattice point modulo the supercell, exact after rounding
+        k = np.rint((points.astype(np.float64) @ Sinv) * det).astype(np.int64) % det
+        return (k[:, 0] * det + k[:, 1]) * det + k[:, 2]
+
+    order = np.argsort(cell_key(n))
+    sorted_keys = cell_key(n)[order]
+    # site index of (basis b, lattice point index t)
+    site_of = np.full((len(tau), P), -1, dtype=np.int64)
+    site_of[site_b, site_t] = np.arange(N)
+    rmax = float(cutoff) if distances is None else max(distances, default=0.0)
+    want = None if distances is None else np.asarray(sorted(distances), dtype=np.float64)
+    Linv = np.linalg.inv(L)
+    reach = np.ceil((rmax + SITE_TOL) * np.linalg.norm(Linv, axis=0) + 1).astype(int)  # |d_a + dtau_a| <= r |col a of L^-1|
+    rows_b, rows_w = [], []
+    for b, b2 in itertools.product(range(len(tau)), repeat=2):
+        dtau = tau[b2] - tau[b]
+        box = [range(-int(reach[a]) - 1, int(reach[a]) + 2) for a in range(3)]
+        for d in itertools.product(*box):
+            r = float(np.linalg.norm((np.asarray(d, dtype=np.float64) + dtau) @ L))
+            if r < SITE_TOL:
+                continue  # the site itself; its images are handled below (d a supercell vector: r > 0)
+            if want is None:
+                if r > rmax + SITE_TOL:
+                    continue
+            elif not np.any(np.abs(want - r) <= SITE_TOL):
+                continue
+            target = n + np.asarray(d, dtype=np.int64)      # (P, 3): lattice point of the far end, for every t
+            pos = np.searchsorted(sorted_keys, cell_key(target))
+            t2 = order[pos]
+            w = np.rint((target - n[t2]).astype(np.float64) @ Sinv).astype(np.int64)
+            if np.any(w @ S != target - n[t2]):
+                raise RuntimeError("the far end of a bond is no lattice point of the supercell")
+            if np.abs(w).max(initial=0) > MAX_IMAGE:
+                raise ValueError(f"a bond of length {r:.6g} reaches image {int(np.abs(w).max())} of this supercell, beyond "
+                                 f"MAX_IMAGE = {MAX_IMAGE}: image out of range")
+            i, j = site_of[b, np.arange(P)], site_of[b2, t2]
+            rows_b.append(np.stack([i, j], axis=1))
+            rows_w.append(w)
+    if not rows_b:
+        return np.zeros((0, 2), dtype=np.int32), np.zeros((0, 3), dtype=np.int8)
+    bonds, images = np.concatenate(rows_b), np.concatenate(rows_w)
+    keep = np.lexsort((images[:, 2], images[:, 1], images[:, 0], bonds[:, 1], bonds[:, 0]))
+    return bonds[keep].astype(np.int32), images[keep].astype(np.int8)
+
+
+# ---- derived quantities (host, pure NumPy on stats) -----------------------------------------------------------------------
+def percolation_strength(stats):
+    """wrapping_sites / n_members (..., G): the fraction of the members that lies in wrapping components; NaN without a
+    member."""
+    s = np.asarray(stats)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return s[..., WRAPPING_SITES] / s[..., N_MEMBERS].astype(np.float64)
+
+
+def mean_finite_size(stats):
+    """(sum_sq - largest^2) / (n_members - largest) (..., G): the mean size of the component a member lies in, the
+    largest component left out.  The sum of the squared sizes of the WRAPPING components cannot be read from the columns
+    (only their number and their sites), so the largest component stands for the spanning one, as is usual in finite
+    cells; NaN when the largest component holds every member."""
+    s = np.asarray(stats).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (s[..., SUM_SQ] - s[..., LARGEST] ** 2) / (s[..., N_MEMBERS] - s[..., LARGEST])
+
+
+def wrapping_probability(stats, axes=None):
+    """The fraction of the rows (first axis) in which a component wraps: any axis (``axes=None``), or every axis of
+    ``axes`` (a 3-bit mask or a sequence of axis numbers) -- each possibly by another component.  (G,) or (..., G)."""
+    s = np.asarray(stats)
+    if axes is None:
+        hit = s[..., WRAP_AXES] != 0
+    else:
+        mask = int(axes) if np.isscalar(axes) else sum(1 << int(a) for a in axes)
+        hit = (s[..., WRAP_AXES] & mask) == mask
+    return hit.mean(axis=0)
+
+
+def size_distribution(stats):
+    """The size histogram (..., G, 16): components with floor(log2 size) == b."""
+    return np.asarray(stats)[..., HIST0:HIST0 + N_HIST]

@@ -1,0 +1,321 @@
+// Connectivity of recorded states (smolmc_set_connectivity, smolmc_eval_connectivity, SMOLMC_SAMPLE_CONNECTIVITY;
+// engine.hip): the connected components of the sites of chosen kinds under a bond list with periodic images, their sizes,
+// and whether they wrap the cell -- labelled on the device where the rows lie.  A translation unit of its own, like
+// observables.hip.
+//
+// The definition is connectivity.Connectivity.evaluate.  Everything is integer; the result does not depend on
+// the order in which the labels travel, so the device matches the host entry for entry.
+//
+// One workgroup of 256 threads per row (measured against 1024: a thread that walks more sites in one pass carries a label
+// further in it, and fewer passes won over more waves).  The row's Npad bytes go to LDS and are turned into kinds in place, as observables_kernel does.
+// Then, per graph, every site gets one 64-bit word in LDS:
+//     label << 48 | (off0 + 0x8000) << 32 | (off1 + 0x8000) << 16 | (off2 + 0x8000)
+// label is the CALLER's number of the smallest site known to be in the site's component (0xffff: no member), off the
+// image sum along a path from that site to this one.  Label and path sum move together in one aligned 64-bit LDS access:
+// no thread sees a torn pair.  A pass lets every member look at its neighbours (both directions of every bond, listed per
+// site by the host, duplicates removed, four to a 16-byte group and group k of all sites side by side: a wave reads the
+// groups of its 64 sites in one coalesced load) and adopt the word of the one with the smallest label below its own, the bond's
+// image subtracted.  A word is written by the one thread that owns the site and read by any; the passes work in place,
+// so a label crosses many sites in one pass when the sites' order allows.  At every moment a word (L, off) says: there is a
+// path from site L to this site with image sum off.  A site adopts a label once, from a site that had adopted it before:
+// the path is simple, has at most N - 1 bonds, and |off| <= (N - 1) x SMOLMC_MAX_CONN_IMAGE < 2^15 (checked at set time).
+// When a pass changes nothing every member's label is the smallest of its component.  Then every bond with ends of one
+// label whose path sums do not match, m = off[i] + w - off[j] != 0, ORs the axes of m into the mask at the label: m is the
+// image sum of a closed path, and if no bond has a mismatch on axis a, every closed path sums to zero on a.
+//
+// No barrier sits under a condition that differs between threads: the "changed" decision is read from LDS by the whole
+// workgroup after the barrier, and the pass loop ends after N + 1 passes whatever the data say.
+#include "smolmc_common.h"
+
+#define CN_THREADS 256
+#define CN_WAVES (CN_THREADS / 64)
+#define CN_NOKIND 0xffu
+#define CN_NOLABEL 0xffffu
+#define CN_BIAS 0x8000
+
+struct ConnArgs {
+    const uint8_t *occ;              // rows of Npad bytes
+    const int32_t *kind_base;        // [N], engine numbering
+    const unsigned long long *mask;  // [G x 4]
+    const uint16_t *caller_of;       // [N]
+    const uint4 *adj;                // neighbours, four to a group: group k of site s of graph g at adj_off[g] + k N + s
+    int adj_off[SMOLMC_MAX_CONN_GRAPHS], adj_groups[SMOLMC_MAX_CONN_GRAPHS];
+    long long *stats;                // [rows x G x 24]
+    int32_t *labels;                 // [rows x G x N], caller's numbering, or null
+    unsigned long long *passes;      // [2]: max and sum of the passes, or null
+    int N, Npad, K, G;
+};
+
+// LDS: words u64 [N] | kinds u8 [Npad] | size u16 [N] | axes u8 [N up to 4] | per-wave partial sums i32 [CN_WAVES][24] |
+// flags i32 [4]
+__host__ __device__ static inline size_t cn_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+size_t smolmc_conn_lds_bytes(int N, int Npad) {
+    const size_t b = (size_t)N * 8 + (size_t)Npad + cn_up((size_t)N * 2, 4) + cn_up((size_t)N, 4) + (CN_WAVES * SMOLMC_CONN_STATS + 4) * 4;
+    return b <= 65536 ? b : 0;
+}
+
+__device__ __forceinline__ unsigned long long cn_load(const unsigned long long *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void cn_store(unsigned long long *p, unsigned long long v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ int cn_wave_sum(int v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ int cn_wave_or(int v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v |= __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned cn_wave_max(unsigned v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, d, 64));
+    return v;
+}
+
+__global__ void __launch_bounds__(CN_THREADS) connectivity_kernel(const ConnArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char cn_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int N = A.N, Npad = A.Npad, K = A.K;
+    unsigned long long *word = (unsigned long long *)cn_smem;
+    uint8_t *kinds = cn_smem + (size_t)N * 8;                  // (8 N is a multiple of 8; the row is copied bytewise below)
+    uint16_t *size = (uint16_t *)(kinds + Npad);               // (Npad is a multiple of 16)
+    uint8_t *axes = (uint8_t *)size + cn_up((size_t)N * 2, 4);
+    int32_t *part = (int32_t *)(axes + cn_up((size_t)N, 4));   // [CN_WAVES][24]
+    int32_t *flag = part + CN_WAVES * SMOLMC_CONN_STATS;       // [3]: "a site changed" of pass p in flag[p % 3]
+    const size_t row = blockIdx.x;
+
+    {   // the row -> kinds (0xff: not counted), one thread per byte
+        const uint8_t *src = A.occ + row * Npad;
+        for (int s = tid; s < Npad; s += CN_THREADS) {
+            unsigned k = CN_NOKIND;
+            if (s < N) {
+                const int kb = A.kind_base[s];
+                if (kb >= 0) k = (unsigned)kb + src[s];
+                if (k >= (unsigned)K) k = CN_NOKIND; // (a code the site's block has no kind for, as in observables_kernel)
+            }
+            kinds[s] = (uint8_t)k;
+        }
+    }
+    __syncthreads();
+
+    for (int g = 0; g < A.G; ++g) {
+        const unsigned long long m0 = A.mask[4 * g], m1 = A.mask[4 * g + 1], m2 = A.mask[4 * g + 2], m3 = A.mask[4 * g + 3];
+        const uint4 *adj = A.adj + A.adj_off[g];
+        const int groups = A.adj_groups[g];
+        // members start as their own component, path sum zero
+        for (int s = tid; s < N; s += CN_THREADS) {
+            const unsigned k = kinds[s];
+            const unsigned long long mw = k < 64 ? m0 : k < 128 ? m1 : k < 192 ? m2 : m3;
+            const bool member = k != CN_NOKIND && ((mw >> (k & 63)) & 1ull);
+            const unsigned long long zero = ((unsigned long long)CN_BIAS << 32) | ((unsigned long long)CN_BIAS << 16) | CN_BIAS;
+            word[s] = ((unsigned long long)(member ? A.caller_of[s] : CN_NOLABEL) << 48) | zero;
+            size[s] = 0;
+            axes[s] = 0;
+        }
+        if (tid < 3) flag[tid] = 0;
+        __syncthreads();
+
+        // ---- the passes: at most N + 1 of them -----------------------------------------------------------------------------
+        int passes = 0;
+        for (int pass = 0; pass <= N; ++pass) {
+            bool changed = false;
+            for (int s = tid; s < N; s += CN_THREADS) {
+                const unsigned long long me = cn_load(&word[s]);
+                const unsigned mine = (unsigned)(me >> 48);
+                if (mine == CN_NOLABEL) continue;
+                unsigned best = mine;
+                unsigned long long take = 0;
+                uint32_t via = 0;
+                // four neighbours at a time: one 16-byte load that the lanes of a wave make side by side, then the four LDS
+                // loads in flight together (a list that ends early is filled up with the site itself, which changes nothing)
+                for (int k = 0; k < groups; ++k) {
+                    const uint4 q = adj[(size_t)k * N + s];
+                    const uint32_t a[4] = {q.x, q.y, q.z, q.w};
+                    unsigned long long o[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) o[i] = cn_load(&word[a[i] & 0xffffu]);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if ((unsigned)(o[i] >> 48) < best) {
+                            best = (unsigned)(o[i] >> 48);
+                            take = o[i];
+                            via = a[i];
+                        }
+                }
+                if (best < mine) {
+                    // the neighbour lies in image w of this site: off[this] = off[neighbour] - w, field by field (no
+                    // field leaves its 16 bits, see above)
+                    const unsigned long long w = ((unsigned long long)((via >> 16) & 15u) << 32) |
+                                                 ((unsigned long long)((via >> 20) & 15u) << 16) | (unsigned long long)((via >> 24) & 15u);
+                    const unsigned long long eight = (8ull << 32) | (8ull << 16) | 8ull;
+                    cn_store(&word[s], take + eight - w);
+                    changed = true;
+                }
+            }
+            if (changed) flag[pass % 3] = 1;
+            __syncthreads();
+            const int any = flag[pass % 3];          // (the same LDS word for every thread, written before the barrier)
+            if (tid == 0) flag[(pass + 2) % 3] = 0;  // (last read before this barrier, next written after the next one)
+            passes = pass + 1;
+            if (!any) break;
+        }
+        // (the break is taken by every thread or none; the writes of the last pass are behind its barrier)
+
+        // ---- the bonds whose path sums do not match: the axes of the mismatch go to the label's mask ----------------------
+        for (int s = tid; s < N; s += CN_THREADS) {
+            const unsigned long long me = word[s];
+            const unsigned mine = (unsigned)(me >> 48);
+            if (mine == CN_NOLABEL) continue;
+            unsigned bits = 0;
+            for (int k = 0; k < groups; ++k) {
+                const uint4 q = adj[(size_t)k * N + s];
+                const uint32_t av[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t a = av[i];
+                    const unsigned long long o = word[a & 0xffffu];
+                    if ((unsigned)(o >> 48) != mine) continue;
+                    const int d0 = (int)((me >> 32) & 0xffffu) + (int)((a >> 16) & 15u) - 8 - (int)((o >> 32) & 0xffffu);
+                    const int d1 = (int)((me >> 16) & 0xffffu) + (int)((a >> 20) & 15u) - 8 - (int)((o >> 16) & 0xffffu);
+                    const int d2 = (int)(me & 0xffffu) + (int)((a >> 24) & 15u) - 8 - (int)(o & 0xffffu);
+                    bits |= (d0 != 0 ? 1u : 0u) | (d1 != 0 ? 2u : 0u) | (d2 != 0 ? 4u : 0u);
+                }
+            }
+            // (sizes and masks are indexed by the label, a caller's site number: any one-to-one index would do)
+            if (bits) atomicOr((unsigned *)(axes + (mine & ~3u)), bits << (8 * (mine & 3u)));
+        }
+        // ---- the sizes at the labels: the lanes of a wave that share the first lane's label add once ---------------------
+        for (int s0 = wave * 64; s0 < N; s0 += CN_THREADS) { // (wave-uniform bounds: every lane takes part in the ballot)
+            const int s = s0 + lane;
+            const unsigned mine = s < N ? (unsigned)(word[s] >> 48) : CN_NOLABEL;
+            const unsigned long long live = __ballot(mine != CN_NOLABEL);
+            if (!live) continue;
+            const int first = __ffsll((long long)live) - 1;
+            const unsigned lead = (unsigned)__shfl((int)mine, first, 64);
+            const unsigned long long same = __ballot(mine == lead);
+            unsigned add = 0, at = mine;
+            if (lane == first) add = (unsigned)__popcll(same);
+            else if (mine != CN_NOLABEL && mine != lead) add = 1;
+            if (add) atomicAdd((unsigned *)((uint8_t *)size + ((at * 2) & ~3u)), add << (16 * (at & 1u)));
+        }
+        __syncthreads();
+
+        // ---- the 24 numbers: a component is found at the site that carries its own number ------------------------------------
+        int n_members = 0, n_comp = 0, n_wrap = 0, wrap_sites = 0, wrap_axes = 0, hist = 0;
+        unsigned sum_sq = 0, top = 0; // top: size << 16 | 0xffff - label -- the largest, among equals the smallest label
+        for (int s0 = wave * 64; s0 < N; s0 += CN_THREADS) {
+            const int s = s0 + lane;
+            int sz = 0, ax = 0;
+            unsigned lab = 0;
+            if (s < N) {
+                lab = A.caller_of[s];
+                if ((unsigned)(word[s] >> 48) == lab) { sz = size[lab]; ax = axes[lab]; }
+            }
+            if (sz) {
+                n_members += sz; n_comp += 1; sum_sq += (unsigned)sz * (unsigned)sz;
+                if (ax) { n_wrap += 1; wrap_sites += sz; wrap_axes |= ax; }
+                top = max(top, ((unsigned)sz << 16) | (0xffffu - lab));
+            }
+            const int bin = sz ? 31 - __clz(sz) : -1;
+            for (int b = 0; b < 16; ++b) { // lane b keeps the count of bin b
+                const int n = __popcll(__ballot(bin == b));
+                if (lane == b) hist += n;
+            }
+        }
+        n_members = cn_wave_sum(n_members); n_comp = cn_wave_sum(n_comp); n_wrap = cn_wave_sum(n_wrap);
+        wrap_sites = cn_wave_sum(wrap_sites); sum_sq = (unsigned)cn_wave_sum((int)sum_sq);
+        wrap_axes = cn_wave_or(wrap_axes); top = cn_wave_max(top);
+        int32_t *mine_part = part + wave * SMOLMC_CONN_STATS;
+        if (lane == 0) {
+            mine_part[0] = n_members; mine_part[1] = n_comp; mine_part[2] = (int32_t)top; mine_part[3] = (int32_t)sum_sq;
+            mine_part[4] = n_wrap; mine_part[5] = wrap_sites; mine_part[6] = wrap_axes; mine_part[7] = 0;
+        }
+        if (lane < 16) mine_part[SMOLMC_CONN_HIST + lane] = hist;
+        __syncthreads();
+        if (tid < SMOLMC_CONN_STATS) {
+            long long v = 0;
+            unsigned t = 0;
+            for (int w = 0; w < CN_WAVES; ++w) t = max(t, (unsigned)part[w * SMOLMC_CONN_STATS + 2]);
+            if (tid == SMOLMC_CONN_LARGEST) v = t >> 16;
+            else if (tid == SMOLMC_CONN_LARGEST_WRAP_AXES) v = t ? axes[0xffffu - (t & 0xffffu)] : 0;
+            else if (tid == SMOLMC_CONN_WRAP_AXES)
+                for (int w = 0; w < CN_WAVES; ++w) v |= part[w * SMOLMC_CONN_STATS + tid];
+            else if (tid == SMOLMC_CONN_SUM_SQ)
+                for (int w = 0; w < CN_WAVES; ++w) v += (unsigned)part[w * SMOLMC_CONN_STATS + tid];
+            else
+                for (int w = 0; w < CN_WAVES; ++w) v += part[w * SMOLMC_CONN_STATS + tid];
+            A.stats[(row * A.G + g) * SMOLMC_CONN_STATS + tid] = v;
+        }
+        if (A.labels) {
+            int32_t *out = A.labels + (row * A.G + g) * (size_t)N;
+            for (int s = tid; s < N; s += CN_THREADS) {
+                const unsigned lab = (unsigned)(word[s] >> 48);
+                out[A.caller_of[s]] = lab == CN_NOLABEL ? -1 : (int32_t)lab;
+            }
+        }
+        if (A.passes && tid == 0) {
+            atomicMax(&A.passes[0], (unsigned long long)passes);
+            atomicAdd(&A.passes[1], (unsigned long long)passes);
+        }
+        __syncthreads(); // (the next graph overwrites words, sizes, masks and partial sums)
+    }
+}
+
+int smolmc_conn_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, long long *d_stats, int32_t *d_labels) {
+    SmolmcConn &S = h->conn;
+    if (!S.G) return fail("no connectivity spec set (smolmc_set_connectivity)");
+    if (!rows) return 0;
+    if (rows > 0x7fffffffull) return fail("connectivity: more than 2^31 rows in one launch");
+    if (!d_stats) return fail("connectivity: null output");
+    ConnArgs A;
+    A.occ = d_occ8; A.kind_base = S.d_kind_base; A.mask = S.d_mask; A.caller_of = S.d_caller_of;
+    A.adj = (const uint4 *)S.d_adj;
+    for (int g = 0; g < SMOLMC_MAX_CONN_GRAPHS; ++g) { A.adj_off[g] = S.adj_off[g]; A.adj_groups[g] = S.adj_groups[g]; }
+    A.stats = d_stats; A.labels = d_labels; A.passes = S.d_passes;
+    A.N = h->N; A.Npad = h->Npad; A.K = S.K; A.G = S.G;
+    if (!S.ev[0])
+        for (hipEvent_t &e : S.ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipMemsetAsync(S.d_passes, 0, 16, h->stream));
+    HIPCHK(hipEventRecord(S.ev[0], h->stream));
+    hipLaunchKernelGGL(connectivity_kernel, dim3((unsigned)rows), dim3(CN_THREADS), S.lds, h->stream, A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.ev[1], h->stream));
+    return 0;
+}
+
+void smolmc_conn_free(SmolmcConn &S) {
+    if (S.arena) hipFree(S.arena);
+    for (hipEvent_t e : S.ev)
+        if (e) hipEventDestroy(e);
+    S = SmolmcConn();
+}
+
+// elapsed device time of the last launch of the connectivity kernel in ms (tools/connectivity_timing.py); a measuring hook
+// like smolmc_debug_obs_kernel_ms, not part of the C-ABI
+extern "C" int smolmc_debug_connectivity_kernel_ms(smolmc_handle *h, float *ms) {
+    if (!h || !ms) return fail("null argument");
+    const SmolmcConn &S = h->conn;
+    if (!S.ev[0]) return fail("the connectivity kernel has not been launched yet");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(S.ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, S.ev[0], S.ev[1]));
+    return 0;
+}
+
+// the passes of the last launch: the most a (row, graph) took and the sum over all of them; a measuring hook likewise
+extern "C" int smolmc_debug_connectivity_passes(smolmc_handle *h, long long *most, long long *sum) {
+    if (!h || !most || !sum) return fail("null argument");
+    const SmolmcConn &S = h->conn;
+    if (!S.ev[0]) return fail("the connectivity kernel has not been launched yet");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(S.ev[1]));
+    unsigned long long v[2];
+    HIPCHK(hipMemcpy(v, S.d_passes, 16, hipMemcpyDeviceToHost));
+    *most = (long long)v[0];
+    *sum = (long long)v[1];
+    return 0;
+}

@@ -2372,6 +2372,7 @@ extern "C" int smolmc_destroy(smolmc_handle *h) {
     smolmc_min_free(h);
     smolmc_stat_free(h);
     smolmc_sfac_free(h->sfac);
+    smolmc_conn_free(h->conn);
     free_samples(h);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -3336,6 +3337,9 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool sfac = (flags & SMOLMC_SAMPLE_STRUCTURE) != 0;
     if (sfac && !h->sfac.Q)
         return fail("SMOLMC_SAMPLE_STRUCTURE without a structure-factor spec: call smolmc_set_structure first");
+    const bool conn = (flags & SMOLMC_SAMPLE_CONNECTIVITY) != 0;
+    if (conn && !h->conn.G)
+        return fail("SMOLMC_SAMPLE_CONNECTIVITY without a connectivity spec: call smolmc_set_connectivity first");
     if ((flags & SMOLMC_SAMPLE_WL) && !h->wl_win_min.empty())
         return fail("SMOLMC_SAMPLE_WL while per-walker windows are set: the snapshot rows are walker-indexed, the Wang-Landau arrays estimator-indexed (smolmc_get_wl between runs, or smolmc_set_wl_windows(h, NULL, NULL) first)");
     if (thin_by > ((int64_t)1 << 30) && h->lean() && !smolmc_env(ENV_LAUNCH_CHUNK))
@@ -3381,6 +3385,9 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const size_t sf_amp = (size_t)h->sfac.Q * h->sfac.K * 2 * 8, sf_inten = (size_t)h->sfac.I * 8; // bytes per row
     w.o_amp = sfac ? take(rows * sf_amp) : 0;
     w.o_inten = sfac ? take(rows * sf_inten) : 0;
+    // connectivity: one column, the int64 stats of every graph
+    const size_t cn_stats = (size_t)h->conn.G * SMOLMC_CONN_STATS * 8; // bytes per row
+    w.o_conn = conn ? take(rows * cn_stats) : 0;
     // lazy cluster features, rows recorded in-kernel: the kernels write rows of scalar features and the occupancy of
     // every sample; the cluster features of the rows are evaluated from those when the launch is through.  What the
     // caller did not ask for sits behind the part of the arena that is downloaded.
@@ -3402,7 +3409,9 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     const bool stat_counts = stats && h->stats.n_count_cols > 0; // (then obs.K == stats.K, see smolmc_set_observables)
     // (... and the rows whose structure factors are asked for, or read by a statistics record with intensity columns)
     const bool stat_inten = stats && h->stats.n_inten_cols > 0; // (then sfac.I == stats.I, see smolmc_set_structure)
-    if ((lazy_rows || obs || minima || stat_counts || sfac || stat_inten) && !(flags & SMOLMC_SAMPLE_OCCUPANCY))
+    // (... and the rows whose components are asked for, or read by a statistics record with connectivity columns)
+    const bool stat_conn = stats && h->stats.n_conn_cols > 0; // (then 24 conn.G == stats.CS, see smolmc_set_connectivity)
+    if ((lazy_rows || obs || minima || stat_counts || sfac || stat_inten || conn || stat_conn) && !(flags & SMOLMC_SAMPLE_OCCUPANCY))
         o_occ_int = take(rows * h->Npad);
     size_t o_min_cnt = w.o_cnt, o_min_key = 0, o_min_slot = 0;
     if (minima) {
@@ -3421,7 +3430,11 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
         o_stat_amp = take(rows * sf_amp);
         o_stat_inten = take(rows * sf_inten);
     }
+    // ... and the connectivity column, or a hidden column of its own
+    size_t o_stat_conn = w.o_conn;
+    if (stat_conn && !conn) o_stat_conn = take(rows * cn_stats);
     if (stats && rows > 0x7fffffffull) return fail("statistics: more than 2^31 sample rows in one block");
+    if (conn && rows > 0x7fffffffull) return fail("connectivity: more than 2^31 sample rows in one block");
     if (sfac && rows > 0x7fffffffull) return fail("structure factors: more than 2^31 sample rows in one block");
     if (lazy_rows && rows > 0x7fffffffull) return fail("lazy cluster features: more than 2^31 sample rows in one block");
     if (obs && rows > 0x7fffffffull) return fail("observables: more than 2^31 sample rows in one block");
@@ -3452,7 +3465,7 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     smp.H = (double *)(sl.d + w.o_H);
     smp.feat = (double *)(sl.d + (lazy_rows ? o_scal : w.o_feat));
     smp.acc = sl.d + w.o_acc;
-    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs || minima || stat_counts || sfac || stat_inten
+    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs || minima || stat_counts || sfac || stat_inten || conn || stat_conn
                   ? sl.d + o_occ_int : nullptr;
     if (!snapshot_path) {
         if (inkernel_bias) {
@@ -3498,13 +3511,16 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
                               (int32_t *)(sl.d + o_min_slot), nsamples, thin_by));
     }
     if (sfac) TRY(smolmc_sfac_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + w.o_amp), (double *)(sl.d + w.o_inten)));
+    if (conn) TRY(smolmc_conn_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + w.o_conn), nullptr));
     if (stats) {
         if (stat_own_counts) TRY(smolmc_obs_launch(h, sl.d + o_occ_int, rows, (int32_t *)(sl.d + o_stat_cnt), nullptr));
+        if (stat_conn && !conn) TRY(smolmc_conn_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + o_stat_conn), nullptr));
         if (stat_inten && !sfac)
             TRY(smolmc_sfac_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + o_stat_amp), (double *)(sl.d + o_stat_inten)));
         TRY(smolmc_stat_launch(h, (const double *)(sl.d + w.o_H), (const double *)(sl.d + w.o_feat),
                                stat_counts ? (const int32_t *)(sl.d + o_stat_cnt) : nullptr,
-                               stat_inten ? (const double *)(sl.d + o_stat_inten) : nullptr, nsamples));
+                               stat_inten ? (const double *)(sl.d + o_stat_inten) : nullptr,
+                               stat_conn ? (const long long *)(sl.d + o_stat_conn) : nullptr, nsamples));
     }
     // download on the copy stream as soon as the block is complete; the next block's launches do not wait for it
     // (the mirror is about to be overwritten: from here the slot no longer holds its old block)
@@ -3981,10 +3997,209 @@ extern "C" int smolmc_update_statistics(smolmc_handle *h) {
     if (!S.n_keys) return fail("no statistics record set: call smolmc_set_statistics first");
     HIPCHK(hipSetDevice(h->device));
     TRY(ensure_features(h));
-    const bool counts = S.n_count_cols > 0, inten = S.n_inten_cols > 0;
+    const bool counts = S.n_count_cols > 0, inten = S.n_inten_cols > 0, conn = S.n_conn_cols > 0;
     if (counts) TRY(smolmc_obs_launch(h, h->kp.occ, (size_t)h->R, S.u_counts, nullptr));
     if (inten) TRY(smolmc_sfac_launch(h, h->kp.occ, (size_t)h->R, h->sfac.u_amp, h->sfac.u_inten));
-    return smolmc_stat_launch(h, h->kp.enthalpy, h->kp.features, counts ? S.u_counts : nullptr, inten ? h->sfac.u_inten : nullptr, 1);
+    if (conn) TRY(smolmc_conn_launch(h, h->kp.occ, (size_t)h->R, h->conn.u_stats, nullptr));
+    return smolmc_stat_launch(h, h->kp.enthalpy, h->kp.features, counts ? S.u_counts : nullptr, inten ? h->sfac.u_inten : nullptr,
+                              conn ? h->conn.u_stats : nullptr, 1);
+}
+
+// ---- connectivity: components of occupancy rows and whether they wrap the cell (the kernel: connectivity.hip) ----------
+extern "C" int smolmc_set_connectivity(smolmc_handle *h, const smolmc_connectivity *sp) {
+    if (!h) return fail("null handle");
+    HIPCHK(hipSetDevice(h->device));
+    for (const SampleSlot &c : h->slots)
+        if (c.state == 1 && (c.flags & SMOLMC_SAMPLE_CONNECTIVITY))
+            return fail("smolmc_set_connectivity while a block recorded with SMOLMC_SAMPLE_CONNECTIVITY waits in the ring (call "
+                        "smolmc_get_samples* or smolmc_discard_samples first)");
+    if (h->stats.n_keys && h->stats.n_conn_cols)
+        return fail("smolmc_set_connectivity while a statistics record with connectivity columns depends on the spec (call "
+                    "smolmc_set_statistics(h, NULL) first)");
+    SmolmcConn S;
+    if (sp) {
+        const int N = h->N, K = sp->n_kinds, G = sp->n_graphs;
+        char msg[256];
+        if (G < 1 || G > SMOLMC_MAX_CONN_GRAPHS) {
+            snprintf(msg, sizeof msg, "connectivity: n_graphs must be 1..%d, got %d", SMOLMC_MAX_CONN_GRAPHS, G);
+            return fail(msg);
+        }
+        if (!sp->kind_base || !sp->member_mask || !sp->bond_ptr) return fail("connectivity: null argument");
+        if (K < 1 || K > 254) return fail("connectivity: n_kinds must be 1..254 (a kind is staged as one byte)");
+        S.lds = smolmc_conn_lds_bytes(N, h->Npad);
+        if (!S.lds) {
+            snprintf(msg, sizeof msg, "connectivity: a row of %d sites is too long for the LDS plan: a label with its path sum, a size and "
+                     "a mask take 11 bytes a site next to the row's %d, 65536 at most", N, h->Npad);
+            return fail(msg);
+        }
+        if ((long long)N * SMOLMC_MAX_CONN_IMAGE > SMOLMC_MAX_CONN_PATH_SUM) {
+            snprintf(msg, sizeof msg, "connectivity: %d sites x SMOLMC_MAX_CONN_IMAGE = %d is larger than SMOLMC_MAX_CONN_PATH_SUM = %d: "
+                     "the image sum of a path could overflow its 16 bits", N, SMOLMC_MAX_CONN_IMAGE, SMOLMC_MAX_CONN_PATH_SUM);
+            return fail(msg);
+        }
+        // kind_base in the engine's numbering; every code a site can hold must have a kind below K (as smolmc_set_observables)
+        std::vector<int32_t> kb((size_t)N);
+        for (int p = 0; p < N; ++p) {
+            const int s = h->relabelled ? h->new_of[p] : p;
+            const int32_t b = sp->kind_base[p];
+            const int width = h->site_width_known[s] ? (int)h->site_ncodes[s] : 1;
+            if (b >= 0 && b + width > K) {
+                snprintf(msg, sizeof msg, "connectivity: kind_base[%d] + site_ncodes = %d + %d is larger than n_kinds = %d: kind out of range",
+                         p, (int)b, width, K);
+                return fail(msg);
+            }
+            kb[s] = b < 0 ? -1 : b;
+        }
+        for (int g = 0; g < G; ++g)
+            for (int k = K; k < 256; ++k)
+                if ((sp->member_mask[4 * g + (k >> 6)] >> (k & 63)) & 1ull) {
+                    snprintf(msg, sizeof msg, "connectivity: graph %d names member kind %d, n_kinds is %d: kind out of range", g, k, K);
+                    return fail(msg);
+                }
+        if (sp->bond_ptr[0] != 0) return fail("connectivity: bond_ptr[0] must be 0");
+        for (int g = 0; g < G; ++g)
+            if (sp->bond_ptr[g + 1] < sp->bond_ptr[g]) return fail("connectivity: bond_ptr must not decrease");
+        const int64_t nb = sp->bond_ptr[G];
+        if (nb > 0 && (!sp->bonds || !sp->images)) return fail("connectivity: null argument");
+        // the neighbours of every site: both directions of every bond, engine numbering, duplicates dropped (a bond listed
+        // twice joins what it joined once)
+        std::vector<uint32_t> adj;
+        std::vector<std::pair<int32_t, uint32_t>> ent;
+        for (int g = 0; g < G; ++g) {
+            ent.clear();
+            for (int64_t b = sp->bond_ptr[g]; b < sp->bond_ptr[g + 1]; ++b) {
+                const int32_t i = sp->bonds[2 * b], j = sp->bonds[2 * b + 1];
+                if (i < 0 || i >= N || j < 0 || j >= N) {
+                    snprintf(msg, sizeof msg, "connectivity: graph %d bond %lld = (%d, %d), %d sites: bond out of range", g,
+                             (long long)(b - sp->bond_ptr[g]), (int)i, (int)j, N);
+                    return fail(msg);
+                }
+                const int8_t *w = sp->images + 3 * b;
+                for (int a = 0; a < 3; ++a)
+                    if (w[a] < -SMOLMC_MAX_CONN_IMAGE || w[a] > SMOLMC_MAX_CONN_IMAGE) {
+                        snprintf(msg, sizeof msg, "connectivity: graph %d bond %lld has image (%d, %d, %d), beyond SMOLMC_MAX_CONN_IMAGE = %d: "
+                                 "image out of range", g, (long long)(b - sp->bond_ptr[g]), (int)w[0], (int)w[1], (int)w[2],
+                                 SMOLMC_MAX_CONN_IMAGE);
+                        return fail(msg);
+                    }
+                const int si = h->relabelled ? h->new_of[i] : i, sj = h->relabelled ? h->new_of[j] : j;
+                if (si == sj && !w[0] && !w[1] && !w[2]) continue; // (a site joined to itself in its own cell: no bond)
+                // seen from i the neighbour j lies in image w, seen from j the neighbour i lies in image -w
+                ent.push_back({si, (uint32_t)sj | (uint32_t)(w[0] + 8) << 16 | (uint32_t)(w[1] + 8) << 20 | (uint32_t)(w[2] + 8) << 24});
+                ent.push_back({sj, (uint32_t)si | (uint32_t)(8 - w[0]) << 16 | (uint32_t)(8 - w[1]) << 20 | (uint32_t)(8 - w[2]) << 24});
+            }
+            std::sort(ent.begin(), ent.end());
+            ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
+            // four to a group, group k of all sites side by side; a list that ends early is filled up with the site itself
+            std::vector<int> deg((size_t)N, 0);
+            int most = 0;
+            for (const auto &x : ent) most = std::max(most, ++deg[x.first]);
+            const int groups = (most + 3) / 4;
+            if ((adj.size() + (size_t)groups * N * 4) * 4 > ((size_t)1 << 30)) return fail("connectivity: the neighbour lists take more than 1 GiB");
+            S.adj_off[g] = (int)(adj.size() / 4);
+            S.adj_groups[g] = groups;
+            const size_t base = adj.size();
+            adj.resize(base + (size_t)groups * N * 4);
+            for (int k = 0; k < groups; ++k)
+                for (int s = 0; s < N; ++s)
+                    for (int i = 0; i < 4; ++i) adj[base + ((size_t)k * N + s) * 4 + i] = (uint32_t)s | 8u << 16 | 8u << 20 | 8u << 24;
+            std::fill(deg.begin(), deg.end(), 0);
+            for (const auto &x : ent) {
+                const int n = deg[x.first]++;
+                adj[base + ((size_t)(n / 4) * N + x.first) * 4 + (n & 3)] = x.second;
+            }
+        }
+        std::vector<uint16_t> caller_of((size_t)N);
+        for (int s = 0; s < N; ++s) caller_of[s] = (uint16_t)(h->relabelled ? h->old_of[s] : s);
+        S.K = K; S.G = G;
+        S.kind_base = kb;
+        // one arena: the spec's arrays, then the scratch of smolmc_update_statistics
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
+        const size_t o_kb = take((size_t)N * 4), o_mk = take((size_t)G * 32), o_co = take((size_t)N * 2),
+                     o_ad = take(adj.size() * 4),
+                     o_us = take((size_t)h->R * G * SMOLMC_CONN_STATS * 8), o_ps = take(16);
+        hipError_t e = hipMalloc((void **)&S.arena, at);
+        if (e != hipSuccess) return fail(std::string("connectivity: hipMalloc: ") + hipGetErrorString(e));
+        unsigned char *d = S.arena;
+        S.d_kind_base = (int32_t *)(d + o_kb); S.d_mask = (unsigned long long *)(d + o_mk); S.d_caller_of = (uint16_t *)(d + o_co);
+        S.d_adj = (uint32_t *)(d + o_ad); S.u_stats = (long long *)(d + o_us);
+        S.d_passes = (unsigned long long *)(d + o_ps);
+        e = hipMemcpy(S.d_kind_base, kb.data(), (size_t)N * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(S.d_mask, sp->member_mask, (size_t)G * 32, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(S.d_caller_of, caller_of.data(), (size_t)N * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !adj.empty()) e = hipMemcpy(S.d_adj, adj.data(), adj.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(S.d_passes, 0, 16);
+        if (e != hipSuccess) {
+            smolmc_conn_free(S);
+            return fail(std::string("connectivity upload: ") + hipGetErrorString(e));
+        }
+    }
+    // the kernels of queued blocks read the old tables: let them finish; delivered blocks of the old shape are forgotten
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (SampleSlot &c : h->slots)
+        if (c.state == 2 && (c.flags & SMOLMC_SAMPLE_CONNECTIVITY)) c.state = 0;
+    smolmc_conn_free(h->conn);
+    h->conn = S;
+    return 0;
+}
+
+extern "C" int smolmc_connectivity_shape(smolmc_handle *h, int *n_graphs, int *n_kinds) {
+    if (!h) return fail("null handle");
+    if (n_graphs) *n_graphs = h->conn.G;
+    if (n_kinds) *n_kinds = h->conn.G ? h->conn.K : 0;
+    return 0;
+}
+
+extern "C" int smolmc_eval_connectivity(smolmc_handle *h, const int32_t *occ, int nocc, int64_t *stats, int32_t *labels) {
+    if (!h) return fail("null handle");
+    const SmolmcConn &S = h->conn;
+    if (!S.G) return fail("no connectivity spec set: call smolmc_set_connectivity first");
+    HIPCHK(hipSetDevice(h->device));
+    const uint8_t *d_occ8 = h->kp.occ;
+    if (occ) {
+        if (nocc <= 0) return 0;
+        TRY(ensure_eval_occ(h, nocc));
+        std::vector<int32_t> occ_engine;
+        occ = occ_in(h, occ, (size_t)nocc, occ_engine);
+        for (size_t r = 0; r < (size_t)nocc; ++r)
+            for (int s = 0; s < h->N; ++s) {
+                const int32_t b = S.kind_base[s], c = occ[r * h->N + s];
+                if (b >= 0 && c >= 0 && b + c >= S.K) {
+                    char msg[200];
+                    snprintf(msg, sizeof msg, "connectivity: occupancy code %d on site %d gives kind %d, n_kinds = %d: kind out of range",
+                             (int)c, h->relabelled ? (int)h->old_of[s] : s, (int)(b + c), S.K);
+                    return fail(msg);
+                }
+            }
+        TRY(upload_occ(h, occ, nocc, h->d_eval_occ));
+        d_occ8 = h->d_eval_occ;
+    } else {
+        nocc = h->R;
+    }
+    const size_t ns = (size_t)nocc * S.G * SMOLMC_CONN_STATS, nl = labels ? (size_t)nocc * S.G * h->N : 0;
+    unsigned char *d_out = nullptr;
+    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>(ns * 8 + nl * 4, 16)));
+    int rc = smolmc_conn_launch(h, d_occ8, (size_t)nocc, (long long *)d_out, labels ? (int32_t *)(d_out + ns * 8) : nullptr);
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (!rc && e == hipSuccess && stats) e = hipMemcpy(stats, d_out, ns * 8, hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess && labels) e = hipMemcpy(labels, d_out + ns * 8, nl * 4, hipMemcpyDeviceToHost);
+    hipFree(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(std::string("eval_connectivity: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int smolmc_get_sample_connectivity(smolmc_handle *h, int64_t *stats) {
+    if (!h) return fail("null handle");
+    SampleSlot *sl = next_delivery(h);
+    if (!sl) return fail("no samples recorded: call smolmc_run_sampled first");
+    if (!(sl->flags & SMOLMC_SAMPLE_CONNECTIVITY)) return fail("the connectivity stats were not recorded (flags bit 7)");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(sl->copy_done));
+    const size_t rows = (size_t)sl->n * h->R;
+    if (stats) host_copy(stats, sl->hst + sl->o_conn, rows * (size_t)h->conn.G * SMOLMC_CONN_STATS * 8);
+    return 0;
 }
 
 // ---- structure factors: fixed-point amplitudes and intensities of occupancy rows (the kernel: structure.hip) ----------

@@ -757,6 +757,7 @@ struct SampleSlot {
     size_t o_H = 0, o_feat = 0, o_acc = 0, o_occ = 0, o_bias = 0, o_wlm = 0, o_wlS = 0, o_wlh = 0, o_wlo = 0, o_wlf = 0;
     size_t o_cnt = 0, o_pair = 0;               // SMOLMC_SAMPLE_OBSERVABLES: kind counts [rows x K], pair counts [rows x cells]
     size_t o_amp = 0, o_inten = 0;              // SMOLMC_SAMPLE_STRUCTURE: amplitudes [rows x Q x K x 2] int64, intensities [rows x I]
+    size_t o_conn = 0;                          // SMOLMC_SAMPLE_CONNECTIVITY: stats [rows x G x 24] int64
     long long n = 0;                            // samples in the block
     int flags = 0;                              // SMOLMC_SAMPLE_* the block was recorded with
     int state = 0;                              // 0 empty, 1 recorded and not yet delivered, 2 delivered
@@ -824,6 +825,8 @@ struct SmolmcStat {
     int n_count_cols = 0;      // columns that read the kind counts
     int I = 0;                 // the intensities of the structure-factor spec in force when the record was set
     int n_inten_cols = 0;      // columns that read the intensities
+    int CS = 0;                // 24 x the graphs of the connectivity spec in force when the record was set
+    int n_conn_cols = 0;       // columns that read the connectivity stats
     double hist_min = 0.0, hist_bin = 1.0;
     unsigned char *arena = nullptr;
     size_t record_bytes = 0;   // from n to the end of the accumulator arrays: what a reset zeroes
@@ -854,6 +857,24 @@ struct SmolmcStruct {
     double *d_scale = nullptr;      // [I]
     long long *u_amp = nullptr;     // smolmc_update_statistics: amplitudes [R x Q x K x 2] ...
     double *u_inten = nullptr;      // ... and intensities [R x I] of the walkers' current states
+    hipEvent_t ev[2] = {nullptr, nullptr}; // around the last launch of the kernel
+};
+
+// connectivity.hip: the connectivity spec of a handle (smolmc_set_connectivity) as the kernel reads it, engine numbering
+struct SmolmcConn {
+    int K = 0, G = 0;               // (G == 0: none set)
+    size_t lds = 0;                 // dynamic LDS of a launch
+    std::vector<int32_t> kind_base; // host copy, engine numbering (validation of occupancies given by the caller)
+    unsigned char *arena = nullptr; // one device allocation, cut into the arrays below
+    int32_t *d_kind_base = nullptr;
+    unsigned long long *d_mask = nullptr; // [G x 4]
+    uint16_t *d_caller_of = nullptr; // [N]: the caller's number of engine site s (the label a site starts with)
+    // the neighbours of engine site s in graph g, both directions of every bond, four to a group of 16 bytes: group k at
+    // (adj_off[g] + k N + s) x 4, k < adj_groups[g]; short lists are filled up with the site itself and image zero
+    uint32_t *d_adj = nullptr;      // neighbour | (w0 + 8) << 16 | (w1 + 8) << 20 | (w2 + 8) << 24, w its image seen from s
+    int adj_off[SMOLMC_MAX_CONN_GRAPHS] = {}, adj_groups[SMOLMC_MAX_CONN_GRAPHS] = {};
+    long long *u_stats = nullptr;   // smolmc_update_statistics: stats [R x G x 24] of the walkers' current states
+    unsigned long long *d_passes = nullptr; // [2]: most passes of a (row, graph) in the last launch, and their sum
     hipEvent_t ev[2] = {nullptr, nullptr}; // around the last launch of the kernel
 };
 
@@ -943,6 +964,8 @@ struct smolmc_handle {
     SmolmcStat stats;
     // structure-factor amplitudes and intensities of occupancy rows (smolmc_set_structure, engine.hip; structure.hip)
     SmolmcStruct sfac;
+    // connected components and percolation of occupancy rows (smolmc_set_connectivity, engine.hip; connectivity.hip)
+    SmolmcConn conn;
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
     SampleSlot slots[2];
@@ -1069,9 +1092,10 @@ void smolmc_min_free(smolmc_handle *h);
 // statistics.hip: offer `nsamples` samples of R rows each (enthalpy [rows], features [rows x F], counts [rows x K] or
 // null; device) to the handle's record, one kernel queued on the handle's stream: a workgroup per key walks the samples in
 // order.  Sample s gives key k the row s * R + w, w the walker that holds k when the kernel runs.
-// (d_inten: intensities [rows x I] or null, read by a record with intensity columns)
+// (d_inten: intensities [rows x I] or null, read by a record with intensity columns; d_conn: connectivity stats
+// [rows x G x 24] or null, read by a record with connectivity columns)
 int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, const double *d_inten,
-                       long long nsamples);
+                       const long long *d_conn, long long nsamples);
 void smolmc_stat_free(smolmc_handle *h);
 // structure.hip: amplitudes [rows x Q x K x 2] and intensities [rows x I] of `rows` occupancy rows (Npad bytes apart,
 // device) into device arrays, queued on the handle's stream; the kernel a spec takes and the layout of its LDS (false:
@@ -1079,6 +1103,12 @@ void smolmc_stat_free(smolmc_handle *h);
 int smolmc_sfac_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, long long *d_amp, double *d_inten);
 bool smolmc_sfac_plan(int N, int Npad, int K, int M, int Q, int *mask, int *copies, int *chunk, size_t *lds);
 void smolmc_sfac_free(SmolmcStruct &S);
+// connectivity.hip: stats [rows x G x 24] and labels [rows x G x N] (caller's numbering, or null) of `rows` occupancy rows
+// (Npad bytes apart, device) into device arrays, queued on the handle's stream; the LDS a row of N sites takes (0: it does
+// not fit); the spec's device arrays
+int smolmc_conn_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, long long *d_stats, int32_t *d_labels);
+size_t smolmc_conn_lds_bytes(int N, int Npad);
+void smolmc_conn_free(SmolmcConn &S);
 size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies);
 int smolmc_obs_pair_copies(size_t cells);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);

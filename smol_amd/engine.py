@@ -75,6 +75,10 @@ SYMBOLS = {
     "smolmc_structure_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 3),
     "smolmc_eval_structure": (C.c_int, [_HP, _i32p, C.c_int, _i64p, _f64p]),
     "smolmc_get_sample_structure": (C.c_int, [_HP, _i64p, _f64p]),
+    "smolmc_set_connectivity": (C.c_int, [_HP, C.POINTER(capi.smolmc_connectivity)]),
+    "smolmc_connectivity_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 2),
+    "smolmc_eval_connectivity": (C.c_int, [_HP, _i32p, C.c_int, _i64p, _i32p]),
+    "smolmc_get_sample_connectivity": (C.c_int, [_HP, _i64p]),
     "smolmc_replay": (C.c_int, [_HP, C.c_int64, _i32p, _f64p, _f64p, _u8p, _f64p, _f64p]),
     "smolmc_last_kernel_ms": (C.c_int, [_HP, C.POINTER(C.c_float)]),
     "smolmc_eval_full": (C.c_int, [_HP, _i32p, C.c_int, _f64p]),
@@ -658,6 +662,64 @@ class Engine:
         self._chk(fn(self._h, C.byref(ms)))
         return float(ms.value)
 
+    # ---- connectivity: connected components and percolation on the device --------------------
+    def set_connectivity(self, spec):
+        """The connectivity spec of this handle (smolmc_set_connectivity): a ``connectivity.Connectivity`` in the caller's
+        site numbering, or None to remove it.  The engine copies and uploads; it refuses, naming the reason, a bond, kind
+        or image out of range, more than ``capi.MAX_CONN_GRAPHS`` graphs and a row too long for the LDS plan."""
+        if spec is None:
+            self._chk(self._lib.smolmc_set_connectivity(self._h, None))
+        else:
+            if spec.num_sites != self.N:
+                raise ValueError(f"the connectivity spec is defined on {spec.num_sites} sites, the handle has {self.N}")
+            struct, keep = spec.c_struct()
+            self._chk(self._lib.smolmc_set_connectivity(self._h, C.byref(struct)))
+            del keep
+
+    def connectivity_shape(self):
+        """(n_graphs, n_kinds) in force, zeros when no spec is set (smolmc_connectivity_shape)."""
+        v = [C.c_int() for _ in range(2)]
+        self._chk(self._lib.smolmc_connectivity_shape(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def connectivity(self, occupancies=None, labels=False):
+        """stats (n, G, 24) int64 of occupancies (n, N) evaluated on the device (smolmc_eval_connectivity), or, with None,
+        of the walkers' current states (n = R); with ``labels`` the pair (stats, labels (n, G, N) int32)."""
+        G, _ = self.connectivity_shape()
+        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
+        n = self.R if occ is None else len(occ)
+        stats = np.zeros((n, G, capi.CONN_STATS), dtype=np.int64)
+        lab = np.full((n, G, self.N), -1, dtype=np.int32) if labels else None
+        self._chk(self._lib.smolmc_eval_connectivity(self._h, _p(occ, C.c_int32), n, _p(stats, C.c_int64), _p(lab, C.c_int32)))
+        return (stats, lab) if labels else stats
+
+    def sample_connectivity(self):
+        """connectivity (ns, R, G, 24) of the block ``fetch_samples`` would deliver next; the block stays undelivered
+        (smolmc_get_sample_connectivity)."""
+        G, _ = self.connectivity_shape()
+        _, ns, _ = self.pending_samples()
+        stats = np.empty((ns, self.R, G, capi.CONN_STATS), dtype=np.int64)
+        self._chk(self._lib.smolmc_get_sample_connectivity(self._h, _p(stats, C.c_int64)))
+        return stats
+
+    def connectivity_kernel_ms(self):
+        """Device time of the last launch of the connectivity kernel in ms (HIP events; a measuring hook of the library,
+        not part of the C-ABI)."""
+        fn = self._lib.smolmc_debug_connectivity_kernel_ms
+        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
+        ms = C.c_float()
+        self._chk(fn(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def connectivity_passes(self):
+        """(most passes a (row, graph) took, their sum over all of them) in the last launch of the connectivity kernel (a
+        measuring hook of the library, not part of the C-ABI)."""
+        fn = self._lib.smolmc_debug_connectivity_passes
+        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        most, total = C.c_longlong(), C.c_longlong()
+        self._chk(fn(self._h, C.byref(most), C.byref(total)))
+        return int(most.value), int(total.value)
+
     # ---- statistics: running moments, blocking sums and a histogram, kept on the device -----
     def set_statistics(self, spec):
         """The statistics record of this handle (smolmc_set_statistics): a ``statistics.Statistics``, or None to remove
@@ -666,7 +728,7 @@ class Engine:
         if spec is None:
             self._chk(self._lib.smolmc_set_statistics(self._h, None))
         else:
-            struct, keep = spec.c_struct(self.F, self.observables_shape()[0], self.structure_shape()[2])
+            struct, keep = spec.c_struct(self.F, self.observables_shape()[0], self.structure_shape()[2], self.connectivity_shape()[0])
             self._chk(self._lib.smolmc_set_statistics(self._h, C.byref(struct)))
             del keep
         self.statistics_spec = spec
@@ -712,19 +774,19 @@ class Engine:
         return float(ms.value)
 
     def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False,
-                    minima=False, statistics=False, structure=False):
+                    minima=False, statistics=False, structure=False, connectivity=False):
         """Advance nsamples*thin_by steps recording one sample per walker every thin_by steps
         on the device; returns dict(enthalpy (ns,R), features (ns,R,F), accepted (ns,R) bool,
         occupancy (ns,R,N) or None[, bias (ns,R)][, the Wang-Landau trace][, species_counts, pair_counts]
-        [, structure_amplitudes (ns,R,Q,K,2) int64, structure_intensities (ns,R,I)]).
+        [, structure_amplitudes (ns,R,Q,K,2) int64, structure_intensities (ns,R,I)][, connectivity (ns,R,G,24) int64]).
         Occupancies come back as int32 (the reference's trace dtype) or, with ``packed``, as the ring's own
         uint8 -- a quarter of the transfer.  = ``run_sampled_async`` + ``fetch_samples``."""
         self.run_sampled_async(nsamples, thin_by, occupancy=occupancy, bias=bias, wl=wl, observables=observables,
-                               minima=minima, statistics=statistics, structure=structure)
+                               minima=minima, statistics=statistics, structure=structure, connectivity=connectivity)
         return self.fetch_samples(packed=packed)
 
     def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False, observables=False, minima=False,
-                          statistics=False, structure=False):
+                          statistics=False, structure=False, connectivity=False):
         """Queue one block of the device ring (smolmc_run_sampled): returns at once.  The ring has two
         slots; queue block k + 1 BEFORE fetching block k and the download of k overlaps the kernel of
         k + 1 (the order ``fetch_samples`` delivers in: oldest first).  ``observables``: the kind and pair
@@ -732,11 +794,12 @@ class Engine:
         occupancy rows they are counted from never leave it.  ``minima``: every row is offered to the record of
         ``set_minima`` when the block's launches are through; what the reduction reads and the caller did not ask for
         stays on the device.  ``statistics``: likewise every row is offered to the record of ``set_statistics``.
-        ``structure``: the amplitudes and intensities of ``set_structure_factor`` for every row, like ``observables``."""
+        ``structure``: the amplitudes and intensities of ``set_structure_factor`` for every row, like ``observables``.
+        ``connectivity``: the stats of ``set_connectivity`` for every row, likewise."""
         flags = ((capi.SAMPLE_OCCUPANCY if occupancy else 0) | (capi.SAMPLE_BIAS if bias else 0) |
                  (capi.SAMPLE_WL if wl else 0) | (capi.SAMPLE_OBSERVABLES if observables else 0) |
                  (capi.SAMPLE_MINIMA if minima else 0) | (capi.SAMPLE_STATISTICS if statistics else 0) |
-                 (capi.SAMPLE_STRUCTURE if structure else 0))
+                 (capi.SAMPLE_STRUCTURE if structure else 0) | (capi.SAMPLE_CONNECTIVITY if connectivity else 0))
         self._chk(self._lib.smolmc_run_sampled(self._h, int(nsamples), int(thin_by), flags))
 
     def pending_samples(self):
@@ -765,6 +828,8 @@ class Engine:
             obs["species_counts"], obs["pair_counts"] = self.sample_observables()
         if flags & capi.SAMPLE_STRUCTURE:
             obs["structure_amplitudes"], obs["structure_intensities"] = self.sample_structure()
+        if flags & capi.SAMPLE_CONNECTIVITY:
+            obs["connectivity"] = self.sample_connectivity()
         if flags & capi.SAMPLE_BIAS:
             extra["bias"] = np.empty((ns, self.R))
         if flags & capi.SAMPLE_WL:

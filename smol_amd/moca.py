@@ -1587,6 +1587,13 @@ class SampleContainer:
             extra.update({"meta/obs_kind_base": np.asarray(obs["kind_base"], dtype=np.int32),
                           "meta/obs_site_ncodes": np.asarray(obs["site_ncodes"], dtype=np.int32),
                           "meta/obs_shape": np.asarray([obs["n_kinds"], obs["n_shells"], int(obs["default_kinds"])], dtype=np.int64)})
+        conn = self.metadata.get("connectivity")
+        if conn is not None:  # the graphs of the connectivity trace: member kinds and bond counts
+            members = conn["members"]
+            extra.update({"meta/conn_shape": np.asarray([conn["n_graphs"], conn["n_kinds"]], dtype=np.int64),
+                          "meta/conn_n_bonds": np.asarray(conn["n_bonds"], dtype=np.int64),
+                          "meta/conn_member_ptr": np.cumsum([0] + [len(m) for m in members]).astype(np.int64),
+                          "meta/conn_members": np.asarray([k for m in members for k in m], dtype=np.int32)})
         rec = self.minima
         if rec is not None:  # the minima record: its arrays, the spec and the two counters
             spec = rec.spec
@@ -1711,6 +1718,11 @@ class SampleContainer:
             c.metadata["observables"] = dict(n_kinds=K, n_shells=S, default_kinds=bool(default),
                                              kind_base=d["meta/obs_kind_base"].tolist(),
                                              site_ncodes=d["meta/obs_site_ncodes"].tolist())
+        if "meta/conn_shape" in d.files:
+            ptr, flat = d["meta/conn_member_ptr"], d["meta/conn_members"].tolist()
+            c.metadata["connectivity"] = dict(n_graphs=int(d["meta/conn_shape"][0]), n_kinds=int(d["meta/conn_shape"][1]),
+                                              members=[flat[int(a):int(b)] for a, b in zip(ptr[:-1], ptr[1:])],
+                                              n_bonds=d["meta/conn_n_bonds"].tolist())
         if "meta/minima_shape" in d.files:
             offers, nw, n_weights, n_axes = (int(x) for x in d["meta/minima_shape"])
             rec = {f: d[f"meta/minima_{f}"] for f in ("value", "enthalpy", "features", "occupancy", "counts", "walker", "sample", "step")}
@@ -1857,11 +1869,13 @@ class Sampler:
         self._minima_offers = 0     # samples offered to the record since it was last emptied
         self._statistics = None     # statistics.Statistics: moments, blocking sums and a histogram kept on the device, or None
         self._structure = None      # structure.StructureFactor evaluated on the device for every sample, or None
+        self._connectivity = None   # connectivity.Connectivity evaluated on the device for every sample, or None
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
                       nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, windows=None,
-                      observables=None, minima=None, statistics=None, structure_factor=None, **kwargs):
+                      observables=None, minima=None, statistics=None, structure_factor=None, connectivity=None,
+                      **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
         'swap'; default kernel Metropolis; one kernel (seed) per walker.
 
@@ -1881,13 +1895,19 @@ class Sampler:
         whether the trace is kept or not; count columns need ``observables`` too, intensity columns ``structure_factor``.
 
         ``structure_factor``: a ``structure.StructureFactor`` -- its amplitudes and intensities are evaluated on the device
-        for every sample and traced as ``structure_amplitudes`` (Q, K, 2) int64 and ``structure_intensities`` (I,)."""
+        for every sample and traced as ``structure_amplitudes`` (Q, K, 2) int64 and ``structure_intensities`` (I,).
+
+        ``connectivity``: a ``connectivity.Connectivity`` -- the components of its graphs are labelled on the device for every
+        sample and their 24 numbers per graph traced as ``connectivity`` (G, 24) int64; connectivity columns of a
+        statistics record need it."""
         from . import parallel
 
         if windows is not None and observables is not None:
             raise ValueError("observables= with windows=: the samples of per-walker windows do not come from the sample ring")
         if windows is not None and structure_factor is not None:
             raise ValueError("structure_factor= with windows=: the samples of per-walker windows do not come from the sample ring")
+        if windows is not None and connectivity is not None:
+            raise ValueError("connectivity= with windows=: the samples of per-walker windows do not come from the sample ring")
         if windows is not None:
             sampler = cls._from_ensemble_windows(ensemble, windows, *args, step_type=step_type, kernel_type=kernel_type, seeds=seeds,
                                                  nwalkers=nwalkers, rank=rank, world_size=world_size, device=device, **kwargs)
@@ -1922,6 +1942,8 @@ class Sampler:
             sampler._set_observables(observables)
         if structure_factor is not None:
             sampler._set_structure_factor(structure_factor)
+        if connectivity is not None:
+            sampler._set_connectivity(connectivity)
         if minima is not None:
             sampler._set_minima(minima)
         if statistics is not None:
@@ -1933,6 +1955,8 @@ class Sampler:
             raise ValueError("a statistics record with count columns needs a sampler built with observables=")
         if spec.intensity_columns() and self._structure is None:
             raise ValueError("a statistics record with intensity columns needs a sampler built with structure_factor=")
+        if spec.connectivity_columns() and self._connectivity is None:
+            raise ValueError("a statistics record with connectivity columns needs a sampler built with connectivity=")
         self._statistics = spec
         if self._engine is not None:
             self._engine.set_statistics(spec)
@@ -2024,6 +2048,19 @@ class Sampler:
         self._structure = sf
         if self._engine is not None:
             self._engine.set_structure_factor(sf)
+
+    def _set_connectivity(self, spec):
+        """Trace ``spec`` with every sample: the container's schema gains the trace, its metadata the spec's shape."""
+        nw, N = self.samples.shape
+        if spec.num_sites != N:
+            raise ValueError(f"the connectivity spec is defined on {spec.num_sites} sites, the ensemble has {N}")
+        if self.samples.num_samples:
+            raise ValueError("the container holds samples without the connectivity trace: clear_samples() first")
+        self.samples._schema["connectivity"] = (np.dtype(np.int64), (nw, spec.n_graphs, 24))
+        self.samples.metadata["connectivity"] = spec.to_metadata()
+        self._connectivity = spec
+        if self._engine is not None:
+            self._engine.set_connectivity(spec)
 
     @classmethod
     def _from_ensemble_windows(cls, ensemble, wx, *args, step_type=None, kernel_type=None, seeds=None, nwalkers=1, rank=None,
@@ -2232,6 +2269,8 @@ class Sampler:
                 self._minima_offers = 0
             if self._structure is not None:  # (before the statistics record: its intensity columns name this spec)
                 self._engine.set_structure_factor(self._structure)
+            if self._connectivity is not None:  # (likewise: its connectivity columns name this spec)
+                self._engine.set_connectivity(self._connectivity)
             if self._statistics is not None:  # (likewise)
                 self._engine.set_statistics(self._statistics)
             if self._wl_windows is not None:  # (kernel e was built with estimator e's window: cfg holds window 0)
@@ -2312,6 +2351,8 @@ class Sampler:
             tr.species_counts, tr.pair_counts = eng.observables()
         if self._structure is not None:
             tr.structure_amplitudes, tr.structure_intensities = eng.structure_factor()
+        if self._connectivity is not None:
+            tr.connectivity = eng.connectivity()
         return tr
 
     def _sample_blocks(self, nsteps, initial_occupancies, thin_by, max_block=0, state_loaded=False, keep_occupancy=True):
@@ -2366,6 +2407,9 @@ class Sampler:
         sf = self._structure
         if sf is not None:
             per_sample += nw * 8 * (2 * sf.n_points * sf.n_kinds + sf.n_intensities)
+        cn = self._connectivity
+        if cn is not None:
+            per_sample += nw * 8 * 24 * cn.n_graphs
         if is_wl:
             L = len(k0._levels)
             per_sample += nw * L * (24 + 8 * F)
@@ -2382,7 +2426,7 @@ class Sampler:
         def queue(n):
             eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl, observables=obs is not None,
                                   minima=self._minima is not None, statistics=self._statistics is not None,
-                                  structure=sf is not None)
+                                  structure=sf is not None, connectivity=cn is not None)
             if self._minima is not None:
                 self._minima_offers += n
 
@@ -2427,6 +2471,8 @@ class Sampler:
                 block.update(species_counts=ring["species_counts"], pair_counts=ring["pair_counts"])
             if "structure_amplitudes" in ring:
                 block.update(structure_amplitudes=ring["structure_amplitudes"], structure_intensities=ring["structure_intensities"])
+            if "connectivity" in ring:
+                block.update(connectivity=ring["connectivity"])
             yield block
 
     def _wl_run_with_host_checks(self, eng, nsteps):
@@ -2508,8 +2554,8 @@ class Sampler:
         leave the device -- their species and pair counts do; the container stores the occupancy of the final
         sample of this call alone, so ``last_occupancy`` and a continuation work as before."""
         if not keep_occupancy:
-            if self._observables is None and self._minima is None and self._structure is None:
-                raise ValueError("keep_occupancy=False needs a sampler built with observables=, minima= or structure_factor=: nothing else of the "
+            if self._observables is None and self._minima is None and self._structure is None and self._connectivity is None:
+                raise ValueError("keep_occupancy=False needs a sampler built with observables=, minima=, structure_factor= or connectivity=: nothing else of the "
                                  "occupancies would be recorded")
             if stream_chunk > 0:
                 raise ValueError("keep_occupancy=False with stream_chunk: every part of a stream holds its occupancies")

@@ -54,6 +54,14 @@ def intensity(i):
     return ("intensity", int(i))
 
 
+def connectivity(g, column):
+    """Number ``column`` (a column constant of ``smol_amd.connectivity``, 0..23) of graph ``g`` of the connectivity spec in
+    force (``connectivity.Connectivity``), read as a double."""
+    if not 0 <= int(column) < 24:
+        raise ValueError(f"connectivity column {column} outside 0..23")
+    return ("connectivity", int(g), int(column))
+
+
 def kind(observables, name_or_k):
     """Count column of kind ``name_or_k`` of ``observables`` (an ``observables.Observables``): a kind number, or a name
     looked up in ``observables.kind_names`` when it has them."""
@@ -101,10 +109,11 @@ class Statistics:
     n_weights = property(lambda self: 0 if self.weights is None else len(self.weights))
     n_pairs = property(lambda self: self.n_columns * (self.n_columns + 1) // 2)
 
-    def sources(self, n_features, n_kinds, n_intensities=0):
+    def sources(self, n_features, n_kinds, n_intensities=0, n_graphs=0):
         """int32 column sources of the C ABI: 0 enthalpy, 1 + i feature i, 1 + F + k kind k, 1 + F + K the weighted sum,
-        2 + F + K + i intensity i (i < ``n_intensities``)."""
-        F, K, I = int(n_features), int(n_kinds), int(n_intensities)
+        2 + F + K + i intensity i (i < ``n_intensities``), 2 + F + K + I + 24 g + c number c of graph g of the connectivity
+        spec (g < ``n_graphs``)."""
+        F, K, I, G = int(n_features), int(n_kinds), int(n_intensities), int(n_graphs)
         out = []
         for c in self.columns:
             if c[0] == "enthalpy":
@@ -119,6 +128,10 @@ class Statistics:
                 if not 0 <= c[1] < I:
                     raise ValueError(f"intensity {c[1]} outside the {I} intensities of the structure-factor spec")
                 out.append(2 + F + K + c[1])
+            elif c[0] == "connectivity":
+                if not 0 <= c[1] < G:
+                    raise ValueError(f"graph {c[1]} outside the {G} graphs of the connectivity spec")
+                out.append(2 + F + K + I + 24 * c[1] + c[2])
             else:
                 out.append(c[1])
         return np.asarray(out, dtype=np.int32)
@@ -131,16 +144,21 @@ class Statistics:
         """Indices into ``columns`` of the intensities, in order."""
         return [i for i, c in enumerate(self.columns) if c[0] == "intensity"]
 
-    def column_values(self, enthalpy, features, counts=None, intensities=None):
+    def connectivity_columns(self):
+        """Indices into ``columns`` of the connectivity numbers, in order."""
+        return [i for i, c in enumerate(self.columns) if c[0] == "connectivity"]
+
+    def column_values(self, enthalpy, features, counts=None, intensities=None, connectivity=None):
         """x (..., C) float64 of rows with enthalpy (...), features (..., F), counts (..., K) or None, intensities
-        (..., I) or None."""
+        (..., I) or None, connectivity stats (..., G, 24) or None."""
         H = np.asarray(enthalpy, dtype=np.float64)
         f = np.asarray(features, dtype=np.float64).reshape(H.shape + (-1,))
         F = f.shape[-1]
         K = 0 if counts is None else np.asarray(counts).shape[-1]
         I = 0 if intensities is None else np.asarray(intensities).shape[-1]
+        G = 0 if connectivity is None else np.asarray(connectivity).shape[-2]
         x = np.empty(H.shape + (self.n_columns,))
-        for j, src in enumerate(self.sources(F, K, I)):
+        for j, src in enumerate(self.sources(F, K, I, G)):
             if src == 0:
                 x[..., j] = H
             elif src <= F:
@@ -151,15 +169,17 @@ class Statistics:
                 x[..., j] = weighted_value(self.weights if self.weights is not None else np.zeros(0), f)
             elif src <= 1 + F + K + I:
                 x[..., j] = np.asarray(intensities, dtype=np.float64).reshape(H.shape + (I,))[..., src - 2 - F - K]
+            elif src <= 1 + F + K + I + 24 * G:
+                x[..., j] = np.asarray(connectivity).reshape(H.shape + (24 * G,))[..., src - 2 - F - K - I].astype(np.float64)
             else:
-                raise ValueError(f"column source {src} outside 0..{1 + F + K + I}")
+                raise ValueError(f"column source {src} outside 0..{1 + F + K + I + 24 * G}")
         return x
 
-    def c_struct(self, n_features, n_kinds, n_intensities=0):
+    def c_struct(self, n_features, n_kinds, n_intensities=0, n_graphs=0):
         """(capi.smolmc_statistics, the arrays it points to)."""
         from . import capi
 
-        cols = self.sources(n_features, n_kinds, n_intensities)
+        cols = self.sources(n_features, n_kinds, n_intensities, n_graphs)
         keep = (cols, self.weights)
         s = capi.smolmc_statistics(
             self.key, len(cols), cols.ctypes.data_as(C.POINTER(C.c_int32)) if len(cols) else None, self.n_weights,
@@ -197,7 +217,7 @@ class StatisticsRecord:
     n_keys = property(lambda self: len(self.n))
 
     # ---- the definition ------------------------------------------------------------------------------------------
-    def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None):
+    def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None, connectivity=None):
         """Offer samples (ns, R) -- or one sample (R,) -- in order.  ``key_of_row`` (R,) or (ns, R): the key of every
         row, a permutation of 0 .. R - 1 per sample (None: the walker).  Vectorised over the keys, a loop over samples."""
         spec = self.spec
@@ -207,7 +227,8 @@ class StatisticsRecord:
         f = np.asarray(features, dtype=np.float64).reshape(ns, nk, -1)
         cnt = None if counts is None else np.asarray(counts).reshape(ns, nk, -1)
         inten = None if intensities is None else np.asarray(intensities, dtype=np.float64).reshape(ns, nk, -1)
-        x_all = spec.column_values(H, f, cnt, inten)
+        conn = None if connectivity is None else np.asarray(connectivity).reshape(ns, nk, -1, 24)
+        x_all = spec.column_values(H, f, cnt, inten, conn)
         if key_of_row is None:
             keys = np.broadcast_to(np.arange(nk), (ns, nk))
         else:
