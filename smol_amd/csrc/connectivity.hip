@@ -1,5 +1,5 @@
-// Connectivity of recorded states (smolmc_set_connectivity, smolmc_eval_connectivity, SMOLMC_SAMPLE_CONNECTIVITY;
-// engine.hip): the connected components of the sites of chosen kinds under a bond list with periodic images, their sizes,
+// Connectivity of recorded states (smolmc_set_connectivity, smolmc_eval_connectivity, SMOLMC_SAMPLE_CONNECTIVITY):
+// the connected components of the sites of chosen kinds under a bond list with periodic images, their sizes,
 // and whether they wrap the cell -- labelled on the device where the rows lie.  A translation unit of its own, like
 // observables.hip.
 //
@@ -317,5 +317,164 @@ extern "C" int smolmc_debug_connectivity_passes(smolmc_handle *h, long long *mos
     HIPCHK(hipMemcpy(v, S.d_passes, 16, hipMemcpyDeviceToHost));
     *most = (long long)v[0];
     *sum = (long long)v[1];
+    return 0;
+}
+
+// ---- the C-ABI of the connectivity spec ----------------------------------------------------------------------------------
+extern "C" int smolmc_set_connectivity(smolmc_handle *h, const smolmc_connectivity *sp) {
+    if (!h) return fail("null handle");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(smolmc_ring_guard(h, SMOLMC_SAMPLE_CONNECTIVITY, "smolmc_set_connectivity", "SMOLMC_SAMPLE_CONNECTIVITY"));
+    if (h->stats.n_keys && h->stats.n_conn_cols)
+        return fail("smolmc_set_connectivity while a statistics record with connectivity columns depends on the spec (call "
+                    "smolmc_set_statistics(h, NULL) first)");
+    SmolmcConn S;
+    if (sp) {
+        const int N = h->N, K = sp->n_kinds, G = sp->n_graphs;
+        char msg[256];
+        if (G < 1 || G > SMOLMC_MAX_CONN_GRAPHS) {
+            snprintf(msg, sizeof msg, "connectivity: n_graphs must be 1..%d, got %d", SMOLMC_MAX_CONN_GRAPHS, G);
+            return fail(msg);
+        }
+        if (!sp->kind_base || !sp->member_mask || !sp->bond_ptr) return fail("connectivity: null argument");
+        if (K < 1 || K > 254) return fail("connectivity: n_kinds must be 1..254 (a kind is staged as one byte)");
+        S.lds = smolmc_conn_lds_bytes(N, h->Npad);
+        if (!S.lds) {
+            snprintf(msg, sizeof msg, "connectivity: a row of %d sites is too long for the LDS plan: a label with its path sum, a size and "
+                     "a mask take 11 bytes a site next to the row's %d, 65536 at most", N, h->Npad);
+            return fail(msg);
+        }
+        if ((long long)N * SMOLMC_MAX_CONN_IMAGE > SMOLMC_MAX_CONN_PATH_SUM) {
+            snprintf(msg, sizeof msg, "connectivity: %d sites x SMOLMC_MAX_CONN_IMAGE = %d is larger than SMOLMC_MAX_CONN_PATH_SUM = %d: "
+                     "the image sum of a path could overflow its 16 bits", N, SMOLMC_MAX_CONN_IMAGE, SMOLMC_MAX_CONN_PATH_SUM);
+            return fail(msg);
+        }
+        std::vector<int32_t> kb;
+        TRY(smolmc_kind_base_in(h, sp->kind_base, K, "connectivity", kb));
+        for (int g = 0; g < G; ++g)
+            for (int k = K; k < 256; ++k)
+                if ((sp->member_mask[4 * g + (k >> 6)] >> (k & 63)) & 1ull) {
+                    snprintf(msg, sizeof msg, "connectivity: graph %d names member kind %d, n_kinds is %d: kind out of range", g, k, K);
+                    return fail(msg);
+                }
+        if (sp->bond_ptr[0] != 0) return fail("connectivity: bond_ptr[0] must be 0");
+        for (int g = 0; g < G; ++g)
+            if (sp->bond_ptr[g + 1] < sp->bond_ptr[g]) return fail("connectivity: bond_ptr must not decrease");
+        const int64_t nb = sp->bond_ptr[G];
+        if (nb > 0 && (!sp->bonds || !sp->images)) return fail("connectivity: null argument");
+        // the neighbours of every site: both directions of every bond, engine numbering, duplicates dropped (a bond listed
+        // twice joins what it joined once)
+        std::vector<uint32_t> adj;
+        std::vector<std::pair<int32_t, uint32_t>> ent;
+        for (int g = 0; g < G; ++g) {
+            ent.clear();
+            for (int64_t b = sp->bond_ptr[g]; b < sp->bond_ptr[g + 1]; ++b) {
+                const int32_t i = sp->bonds[2 * b], j = sp->bonds[2 * b + 1];
+                if (i < 0 || i >= N || j < 0 || j >= N) {
+                    snprintf(msg, sizeof msg, "connectivity: graph %d bond %lld = (%d, %d), %d sites: bond out of range", g,
+                             (long long)(b - sp->bond_ptr[g]), (int)i, (int)j, N);
+                    return fail(msg);
+                }
+                const int8_t *w = sp->images + 3 * b;
+                for (int a = 0; a < 3; ++a)
+                    if (w[a] < -SMOLMC_MAX_CONN_IMAGE || w[a] > SMOLMC_MAX_CONN_IMAGE) {
+                        snprintf(msg, sizeof msg, "connectivity: graph %d bond %lld has image (%d, %d, %d), beyond SMOLMC_MAX_CONN_IMAGE = %d: "
+                                 "image out of range", g, (long long)(b - sp->bond_ptr[g]), (int)w[0], (int)w[1], (int)w[2],
+                                 SMOLMC_MAX_CONN_IMAGE);
+                        return fail(msg);
+                    }
+                const int si = h->relabelled ? h->new_of[i] : i, sj = h->relabelled ? h->new_of[j] : j;
+                if (si == sj && !w[0] && !w[1] && !w[2]) continue; // (a site joined to itself in its own cell: no bond)
+                // seen from i the neighbour j lies in image w, seen from j the neighbour i lies in image -w
+                ent.push_back({si, (uint32_t)sj | (uint32_t)(w[0] + 8) << 16 | (uint32_t)(w[1] + 8) << 20 | (uint32_t)(w[2] + 8) << 24});
+                ent.push_back({sj, (uint32_t)si | (uint32_t)(8 - w[0]) << 16 | (uint32_t)(8 - w[1]) << 20 | (uint32_t)(8 - w[2]) << 24});
+            }
+            std::sort(ent.begin(), ent.end());
+            ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
+            // four to a group, group k of all sites side by side; a list that ends early is filled up with the site itself
+            std::vector<int> deg((size_t)N, 0);
+            int most = 0;
+            for (const auto &x : ent) most = std::max(most, ++deg[x.first]);
+            const int groups = (most + 3) / 4;
+            if ((adj.size() + (size_t)groups * N * 4) * 4 > ((size_t)1 << 30)) return fail("connectivity: the neighbour lists take more than 1 GiB");
+            S.adj_off[g] = (int)(adj.size() / 4);
+            S.adj_groups[g] = groups;
+            const size_t base = adj.size();
+            adj.resize(base + (size_t)groups * N * 4);
+            for (int k = 0; k < groups; ++k)
+                for (int s = 0; s < N; ++s)
+                    for (int i = 0; i < 4; ++i) adj[base + ((size_t)k * N + s) * 4 + i] = (uint32_t)s | 8u << 16 | 8u << 20 | 8u << 24;
+            std::fill(deg.begin(), deg.end(), 0);
+            for (const auto &x : ent) {
+                const int n = deg[x.first]++;
+                adj[base + ((size_t)(n / 4) * N + x.first) * 4 + (n & 3)] = x.second;
+            }
+        }
+        std::vector<uint16_t> caller_of((size_t)N);
+        for (int s = 0; s < N; ++s) caller_of[s] = (uint16_t)(h->relabelled ? h->old_of[s] : s);
+        S.K = K; S.G = G;
+        S.kind_base = kb;
+        // one arena: the spec's arrays, then the scratch of smolmc_update_statistics
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
+        const size_t o_kb = take((size_t)N * 4), o_mk = take((size_t)G * 32), o_co = take((size_t)N * 2),
+                     o_ad = take(adj.size() * 4),
+                     o_us = take((size_t)h->R * G * SMOLMC_CONN_STATS * 8), o_ps = take(16);
+        hipError_t e = hipMalloc((void **)&S.arena, at);
+        if (e != hipSuccess) return fail(std::string("connectivity: hipMalloc: ") + hipGetErrorString(e));
+        unsigned char *d = S.arena;
+        S.d_kind_base = (int32_t *)(d + o_kb); S.d_mask = (unsigned long long *)(d + o_mk); S.d_caller_of = (uint16_t *)(d + o_co);
+        S.d_adj = (uint32_t *)(d + o_ad); S.u_stats = (long long *)(d + o_us);
+        S.d_passes = (unsigned long long *)(d + o_ps);
+        e = hipMemcpy(S.d_kind_base, kb.data(), (size_t)N * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(S.d_mask, sp->member_mask, (size_t)G * 32, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(S.d_caller_of, caller_of.data(), (size_t)N * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !adj.empty()) e = hipMemcpy(S.d_adj, adj.data(), adj.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(S.d_passes, 0, 16);
+        if (e != hipSuccess) {
+            smolmc_conn_free(S);
+            return fail(std::string("connectivity upload: ") + hipGetErrorString(e));
+        }
+    }
+    TRY(smolmc_ring_forget(h, SMOLMC_SAMPLE_CONNECTIVITY));
+    smolmc_conn_free(h->conn);
+    h->conn = S;
+    return 0;
+}
+
+extern "C" int smolmc_connectivity_shape(smolmc_handle *h, int *n_graphs, int *n_kinds) {
+    if (!h) return fail("null handle");
+    if (n_graphs) *n_graphs = h->conn.G;
+    if (n_kinds) *n_kinds = h->conn.G ? h->conn.K : 0;
+    return 0;
+}
+
+extern "C" int smolmc_eval_connectivity(smolmc_handle *h, const int32_t *occ, int nocc, int64_t *stats, int32_t *labels) {
+    if (!h) return fail("null handle");
+    const SmolmcConn &S = h->conn;
+    if (!S.G) return fail("no connectivity spec set: call smolmc_set_connectivity first");
+    HIPCHK(hipSetDevice(h->device));
+    const uint8_t *d_occ8;
+    size_t rows;
+    TRY(smolmc_eval_rows(h, occ, nocc, S.kind_base, S.K, "connectivity", &d_occ8, &rows));
+    if (!rows) return 0;
+    const size_t ns = rows * S.G * SMOLMC_CONN_STATS, nl = labels ? rows * S.G * h->N : 0;
+    unsigned char *d_out = nullptr;
+    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>(ns * 8 + nl * 4, 16)));
+    int rc = smolmc_conn_launch(h, d_occ8, rows, (long long *)d_out, labels ? (int32_t *)(d_out + ns * 8) : nullptr);
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (!rc && e == hipSuccess && stats) e = hipMemcpy(stats, d_out, ns * 8, hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess && labels) e = hipMemcpy(labels, d_out + ns * 8, nl * 4, hipMemcpyDeviceToHost);
+    hipFree(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(std::string("eval_connectivity: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int smolmc_get_sample_connectivity(smolmc_handle *h, int64_t *stats) {
+    const SampleSlot *sl;
+    size_t rows;
+    TRY(smolmc_sample_block(h, SMOLMC_SAMPLE_CONNECTIVITY, "the connectivity stats were not recorded (flags bit 7)", &sl, &rows));
+    if (stats) smolmc_host_copy(stats, sl->hst + sl->o_conn, rows * (size_t)h->conn.G * SMOLMC_CONN_STATS * 8);
     return 0;
 }

@@ -2352,13 +2352,6 @@ static int create_impl(const smolmc_tables *t, const smolmc_config *cfg, smolmc_
     return 0;
 }
 
-static void free_observables(SmolmcObs &O) {
-    if (O.d_kind_base) hipFree(O.d_kind_base);
-    if (O.d_shell_ptr) hipFree(O.d_shell_ptr);
-    if (O.d_bonds) hipFree(O.d_bonds);
-    O = SmolmcObs();
-}
-
 extern "C" int smolmc_destroy(smolmc_handle *h) {
     if (!h) return 0;
     hipSetDevice(h->device);
@@ -2366,7 +2359,7 @@ extern "C" int smolmc_destroy(smolmc_handle *h) {
     smolmc_dist_free(h);
     for (void *p : h->allocs) hipFree(p);
     if (h->d_eval_occ) hipFree(h->d_eval_occ);
-    free_observables(h->obs);
+    smolmc_obs_free(h->obs);
     if (h->obs_ev0) hipEventDestroy(h->obs_ev0);
     if (h->obs_ev1) hipEventDestroy(h->obs_ev1);
     smolmc_min_free(h);
@@ -3318,35 +3311,158 @@ __global__ void __launch_bounds__(256) sample_snapshot_kernel(const SnapshotArgs
     }
 }
 
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// Which derived columns exist for a set of SMOLMC_SAMPLE_* flags, and which record reads which: the one place that knows.
+// A quantity exists when its own flag asks for it or a record reads it; every reader reads the same column (the statistics
+// record the counts the observables' flag or the minima record asked for, else its own).
+struct ColumnUse {
+    bool min_counts, stat_counts, stat_inten, stat_conn; // what the records read
+    bool counts, pairs, sfac, conn;                      // what is derived: kind counts, pair counts (with the observables' flag
+                                                         // only), amplitudes with intensities, connectivity stats
+};
+static ColumnUse column_use(const smolmc_handle *h, int flags) {
+    const bool minima = (flags & SMOLMC_SAMPLE_MINIMA) != 0, stats = (flags & SMOLMC_SAMPLE_STATISTICS) != 0;
+    ColumnUse u;
+    u.min_counts = minima && h->obs.K && h->obs.K == h->minima.K; // (a keyed record: always, see smolmc_set_observables)
+    u.stat_counts = stats && h->stats.n_count_cols > 0;           // (then obs.K == stats.K, see smolmc_set_observables)
+    u.stat_inten = stats && h->stats.n_inten_cols > 0;            // (then sfac.I == stats.I, see smolmc_set_structure)
+    u.stat_conn = stats && h->stats.n_conn_cols > 0;              // (then 24 conn.G == stats.CS, see smolmc_set_connectivity)
+    u.pairs = (flags & SMOLMC_SAMPLE_OBSERVABLES) != 0;
+    u.counts = u.pairs || u.min_counts || u.stat_counts;
+    u.sfac = (flags & SMOLMC_SAMPLE_STRUCTURE) || u.stat_inten;
+    u.conn = (flags & SMOLMC_SAMPLE_CONNECTIVITY) || u.stat_conn;
+    return u;
+}
 
-extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t thin_by, int flags) {
-    if (!h) return fail("null handle");
-    if (nsamples <= 0 || thin_by <= 0) return fail("nsamples and thin_by must be positive");
-    HIPCHK(hipSetDevice(h->device));
-    const bool wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
+// `rows` = nsamples x R rows on the device and where what is derived from them goes: a block of the ring, or the walkers'
+// own states with the scratch of smolmc_update_minima / smolmc_update_statistics.  An output column_use does not ask for is
+// not read.
+struct RowSources {
+    size_t rows = 0;
+    const double *H = nullptr, *feat = nullptr;
+    const uint8_t *occ = nullptr;                     // rows of Npad bytes
+    int32_t *counts = nullptr, *pairs = nullptr;
+    long long *amp = nullptr;
+    double *inten = nullptr;
+    long long *conn = nullptr;
+    uint64_t *min_key = nullptr;                      // scratch of the minima reduction [rows]
+    int32_t *min_slot = nullptr;
+};
+static RowSources walker_rows(const smolmc_handle *h) {
+    RowSources s;
+    s.rows = (size_t)h->R;
+    s.H = h->kp.enthalpy; s.feat = h->kp.features; s.occ = h->kp.occ;
+    return s;
+}
+// the derived columns of the rows, in one fixed order, then the offers to the records `flags` names; all on the handle's stream
+static int derive_and_offer(smolmc_handle *h, const RowSources &s, int flags, long long nsamples, long long thin_by) {
+    const ColumnUse u = column_use(h, flags);
+    if (u.counts) TRY(smolmc_obs_launch(h, s.occ, s.rows, s.counts, u.pairs ? s.pairs : nullptr));
+    if (u.sfac) TRY(smolmc_sfac_launch(h, s.occ, s.rows, s.amp, s.inten));
+    if (u.conn) TRY(smolmc_conn_launch(h, s.occ, s.rows, s.conn, nullptr));
+    if (flags & SMOLMC_SAMPLE_MINIMA)
+        TRY(smolmc_min_launch(h, s.H, s.feat, s.occ, u.min_counts ? s.counts : nullptr, s.min_key, s.min_slot, nsamples, thin_by));
+    if (flags & SMOLMC_SAMPLE_STATISTICS)
+        TRY(smolmc_stat_launch(h, s.H, s.feat, u.stat_counts ? s.counts : nullptr, u.stat_inten ? s.inten : nullptr,
+                               u.stat_conn ? s.conn : nullptr, nsamples));
+    return 0;
+}
+
+// One block of smolmc_run_sampled: its columns in the slot's arenas and how its rows are recorded.
+struct BlockPlan {
+    size_t rows = 0;
+    SampleColumns col;      // every column the block has, downloaded or not
+    bool occ = false;       // occupancy rows are kept (at col.o_occ)
+    size_t o_scal = 0, o_min_key = 0, o_min_slot = 0; // never downloaded: the scalar features of lazy rows, the minima scratch
+    size_t download = 0, total = 0;                    // bytes in front of the download mark, bytes in all
+    // Biased Metropolis handles on the lean families record their rows in-kernel like the unbiased ones (round 6: the
+    // running bias is a scalar the kernel carries anyway; LeanParams::smp_bias_off tells it where the column is).  The
+    // snapshot path -- one launch + one snapshot kernel per sample -- is left to Wang-Landau (per-walker L and L x F
+    // arrays) and to biased handles on mc_kernel / the universal kernel.  SMOLMC_NO_INKERNEL_BIAS: A/B switch.
+    // Lazy cluster features, rows recorded in-kernel: the kernels write rows of scalar features and the occupancy of
+    // every sample; the cluster features of the rows are evaluated from those when the launch is through.
+    bool snapshot = false;  // the snapshot path; else the kernels record the rows themselves ...
+    bool bias_rows = false; // ... with the bias column
+    bool lazy_rows = false; // ... as rows of scalar features (at o_scal)
+};
+// Pure host arithmetic: nothing is allocated or launched.  A column lies in front of the download mark exactly when its own
+// SMOLMC_SAMPLE_* flag is set; what a derived column or a record needs and the caller did not ask for lies behind it.
+static int plan_block(const smolmc_handle *h, int64_t nsamples, int flags, BlockPlan &p) {
+    const size_t rows = (size_t)nsamples * h->R, F = (size_t)h->F, L = (size_t)h->L;
+    const ColumnUse u = column_use(h, flags);
+    p.bias_rows = (flags & SMOLMC_SAMPLE_BIAS) && !(flags & SMOLMC_SAMPLE_WL) && h->lean() && !h->univ() && h->lp.bias_type &&
+                  !smolmc_env(ENV_NO_INKERNEL_BIAS);
+    p.snapshot = (flags & SMOLMC_SAMPLE_WL) || ((flags & SMOLMC_SAMPLE_BIAS) && !p.bias_rows);
+    p.lazy_rows = is_lazy(h) && !p.snapshot;
+    const struct { bool applies; const char *noun; } too_many[] = {
+        {(flags & SMOLMC_SAMPLE_MINIMA) != 0, "minima"},          {(flags & SMOLMC_SAMPLE_STATISTICS) != 0, "statistics"},
+        {(flags & SMOLMC_SAMPLE_CONNECTIVITY) != 0, "connectivity"}, {(flags & SMOLMC_SAMPLE_STRUCTURE) != 0, "structure factors"},
+        {p.lazy_rows, "lazy cluster features"},                     {(flags & SMOLMC_SAMPLE_OBSERVABLES) != 0, "observables"}};
+    for (const auto &t : too_many)
+        if (t.applies && rows > 0x7fffffffull) return fail(std::string(t.noun) + ": more than 2^31 sample rows in one block");
+    p.rows = rows;
+    p.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || p.lazy_rows || u.counts || u.sfac || u.conn || (flags & SMOLMC_SAMPLE_MINIMA);
+    const size_t sf_amp = (size_t)h->sfac.Q * h->sfac.K * 2 * 8, sf_inten = (size_t)h->sfac.I * 8; // bytes per row
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += up256(bytes); return o; };
+    SampleColumns &c = p.col;
+    c.o_H = take(rows * 8);
+    c.o_feat = take(rows * F * 8);
+    c.o_acc = take(rows);
+    if (flags & SMOLMC_SAMPLE_BIAS) c.o_bias = take(rows * 8);
+    if (flags & SMOLMC_SAMPLE_WL) {
+        c.o_wlm = take(rows * 8);
+        c.o_wlS = take(rows * L * 8);
+        c.o_wlh = take(rows * L * 8);
+        c.o_wlo = take(rows * L * 8);
+        c.o_wlf = take(rows * L * F * 8);
+    }
+    // the columns with a flag of their own: first those whose flag is set, then, behind the download mark, the others
+    for (int hidden = 0; hidden < 2; ++hidden) {
+        auto here = [&](int flag) { return ((flags & flag) != 0) != (hidden != 0); };
+        if (p.occ && here(SMOLMC_SAMPLE_OCCUPANCY)) c.o_occ = take(rows * h->Npad);
+        if (u.counts && here(SMOLMC_SAMPLE_OBSERVABLES)) c.o_cnt = take(rows * (size_t)h->obs.K * 4);
+        if (u.pairs && !hidden) c.o_pair = take(rows * h->obs.cells * 4);
+        if (u.sfac && here(SMOLMC_SAMPLE_STRUCTURE)) {
+            c.o_amp = take(rows * sf_amp);
+            c.o_inten = take(rows * sf_inten);
+        }
+        if (u.conn && here(SMOLMC_SAMPLE_CONNECTIVITY)) c.o_conn = take(rows * (size_t)h->conn.G * SMOLMC_CONN_STATS * 8);
+        if (!hidden) p.download = at;
+    }
+    if (p.lazy_rows) p.o_scal = take(rows * (size_t)std::max(1, lazy_nscal(h)) * 8);
+    if (flags & SMOLMC_SAMPLE_MINIMA) {
+        p.o_min_key = take(rows * 8);
+        p.o_min_slot = take(rows * 4);
+    }
+    p.total = at;
+    return 0;
+}
+
+// what the flags ask of the handle
+static int sampled_check_flags(const smolmc_handle *h, int64_t thin_by, int flags) {
     if ((flags & SMOLMC_SAMPLE_BIAS) && !h->kp.bias_type) return fail("the model has no bias term");
-    if ((flags & SMOLMC_SAMPLE_WL) && !wl) return fail("handle is not a Wang-Landau kernel");
+    if ((flags & SMOLMC_SAMPLE_WL) && !is_wl(h)) return fail("handle is not a Wang-Landau kernel");
     if ((flags & SMOLMC_SAMPLE_OBSERVABLES) && !h->obs.K)
         return fail("SMOLMC_SAMPLE_OBSERVABLES without observables: call smolmc_set_observables first");
-    const bool minima = (flags & SMOLMC_SAMPLE_MINIMA) != 0;
-    if (minima && !h->minima.n_slots) return fail("SMOLMC_SAMPLE_MINIMA without a minima record: call smolmc_set_minima first");
-    const bool stats = (flags & SMOLMC_SAMPLE_STATISTICS) != 0;
-    if (stats && !h->stats.n_keys)
+    if ((flags & SMOLMC_SAMPLE_MINIMA) && !h->minima.n_slots)
+        return fail("SMOLMC_SAMPLE_MINIMA without a minima record: call smolmc_set_minima first");
+    if ((flags & SMOLMC_SAMPLE_STATISTICS) && !h->stats.n_keys)
         return fail("SMOLMC_SAMPLE_STATISTICS without a statistics record: call smolmc_set_statistics first");
-    const bool sfac = (flags & SMOLMC_SAMPLE_STRUCTURE) != 0;
-    if (sfac && !h->sfac.Q)
+    if ((flags & SMOLMC_SAMPLE_STRUCTURE) && !h->sfac.Q)
         return fail("SMOLMC_SAMPLE_STRUCTURE without a structure-factor spec: call smolmc_set_structure first");
-    const bool conn = (flags & SMOLMC_SAMPLE_CONNECTIVITY) != 0;
-    if (conn && !h->conn.G)
+    if ((flags & SMOLMC_SAMPLE_CONNECTIVITY) && !h->conn.G)
         return fail("SMOLMC_SAMPLE_CONNECTIVITY without a connectivity spec: call smolmc_set_connectivity first");
     if ((flags & SMOLMC_SAMPLE_WL) && !h->wl_win_min.empty())
         return fail("SMOLMC_SAMPLE_WL while per-walker windows are set: the snapshot rows are walker-indexed, the Wang-Landau arrays estimator-indexed (smolmc_get_wl between runs, or smolmc_set_wl_windows(h, NULL, NULL) first)");
     if (thin_by > ((int64_t)1 << 30) && h->lean() && !smolmc_env(ENV_LAUNCH_CHUNK))
         return fail("thin_by must be <= 2^30 steps"); // (before a slot is touched: run_steps would refuse it)
+    return 0;
+}
+
+// The slot the next block goes to is the older one.  When it still holds a block nobody fetched, so does the other
+// (it is younger): the ring is full and the call is refused -- ABI 7 dropped the older block here without a word.
+static int sampled_next_slot(smolmc_handle *h, SampleSlot **out) {
     if (!h->copy_stream) HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    // The slot this block goes to is the older one.  When it still holds a block nobody fetched, so does the other
-    // (it is younger): the ring is full and the call is refused -- ABI 7 dropped the older block here without a word.
     SampleSlot &sl = h->slots[h->next_slot];
     if (sl.state == 1) {
         fail("sample ring full: both slots hold blocks that were not fetched (call smolmc_get_samples* or "
@@ -3357,172 +3473,96 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
         HIPCHK(hipEventCreateWithFlags(&sl.kernel_done, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&sl.copy_done, hipEventDisableTiming));
     }
-    // layout of the block inside the slot's arenas: worked out on a COPY of the slot record, which replaces the
-    // record only when every launch of the block has been queued -- a call that fails on the way (an allocation, a
-    // launch) leaves the ring as it was: the slot keeps its delivered block, next_slot does not move
-    SampleSlot w = sl;
-    const size_t rows = (size_t)nsamples * h->R, F = (size_t)h->F, L = (size_t)h->L;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += up256(bytes); return o; };
-    w.o_H = take(rows * 8);
-    w.o_feat = take(rows * F * 8);
-    w.o_acc = take(rows);
-    w.o_bias = (flags & SMOLMC_SAMPLE_BIAS) ? take(rows * 8) : 0;
-    w.o_wlm = w.o_wlS = w.o_wlh = w.o_wlo = w.o_wlf = 0;
-    if (flags & SMOLMC_SAMPLE_WL) {
-        w.o_wlm = take(rows * 8);
-        w.o_wlS = take(rows * L * 8);
-        w.o_wlh = take(rows * L * 8);
-        w.o_wlo = take(rows * L * 8);
-        w.o_wlf = take(rows * L * F * 8);
-    }
-    w.o_occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) ? take(rows * h->Npad) : 0;
-    // observables: two columns of the downloaded part, filled from the block's occupancy rows after its launches
-    const bool obs = (flags & SMOLMC_SAMPLE_OBSERVABLES) != 0;
-    w.o_cnt = obs ? take(rows * (size_t)h->obs.K * 4) : 0;
-    w.o_pair = obs ? take(rows * h->obs.cells * 4) : 0;
-    // structure factors: likewise two columns, int64 amplitudes and double intensities
-    const size_t sf_amp = (size_t)h->sfac.Q * h->sfac.K * 2 * 8, sf_inten = (size_t)h->sfac.I * 8; // bytes per row
-    w.o_amp = sfac ? take(rows * sf_amp) : 0;
-    w.o_inten = sfac ? take(rows * sf_inten) : 0;
-    // connectivity: one column, the int64 stats of every graph
-    const size_t cn_stats = (size_t)h->conn.G * SMOLMC_CONN_STATS * 8; // bytes per row
-    w.o_conn = conn ? take(rows * cn_stats) : 0;
-    // lazy cluster features, rows recorded in-kernel: the kernels write rows of scalar features and the occupancy of
-    // every sample; the cluster features of the rows are evaluated from those when the launch is through.  What the
-    // caller did not ask for sits behind the part of the arena that is downloaded.
-    // Biased Metropolis handles on the lean families record their rows in-kernel like the unbiased ones (round 6: the
-    // running bias is a scalar the kernel carries anyway; LeanParams::smp_bias_off tells it where the column is).  The
-    // snapshot path -- one launch + one snapshot kernel per sample -- is left to Wang-Landau (per-walker L and L x F
-    // arrays) and to biased handles on mc_kernel / the universal kernel.  SMOLMC_NO_INKERNEL_BIAS: A/B switch.
-    const bool inkernel_bias = (flags & SMOLMC_SAMPLE_BIAS) && !(flags & SMOLMC_SAMPLE_WL) && h->lean() && !h->univ() &&
-                               h->lp.bias_type && !smolmc_env(ENV_NO_INKERNEL_BIAS);
-    const bool snapshot_path = (flags & SMOLMC_SAMPLE_WL) || ((flags & SMOLMC_SAMPLE_BIAS) && !inkernel_bias);
-    const bool lazy_rows = is_lazy(h) && !snapshot_path;
-    const size_t download = at;
-    size_t o_scal = 0, o_occ_int = w.o_occ;
-    if (lazy_rows) o_scal = take(rows * (size_t)std::max(1, lazy_nscal(h)) * 8);
-    // (... and so do the occupancy rows the observables are counted from)
-    // (... and the rows offered to the minima record, with their kind counts and the two scratch columns of the reduction)
-    const bool min_counts = minima && h->obs.K && h->obs.K == h->minima.K; // (a keyed record: always, see smolmc_set_observables)
-    // (... and the rows whose kinds a statistics record with count columns reads)
-    const bool stat_counts = stats && h->stats.n_count_cols > 0; // (then obs.K == stats.K, see smolmc_set_observables)
-    // (... and the rows whose structure factors are asked for, or read by a statistics record with intensity columns)
-    const bool stat_inten = stats && h->stats.n_inten_cols > 0; // (then sfac.I == stats.I, see smolmc_set_structure)
-    // (... and the rows whose components are asked for, or read by a statistics record with connectivity columns)
-    const bool stat_conn = stats && h->stats.n_conn_cols > 0; // (then 24 conn.G == stats.CS, see smolmc_set_connectivity)
-    if ((lazy_rows || obs || minima || stat_counts || sfac || stat_inten || conn || stat_conn) && !(flags & SMOLMC_SAMPLE_OCCUPANCY))
-        o_occ_int = take(rows * h->Npad);
-    size_t o_min_cnt = w.o_cnt, o_min_key = 0, o_min_slot = 0;
-    if (minima) {
-        if (min_counts && !obs) o_min_cnt = take(rows * (size_t)h->obs.K * 4);
-        o_min_key = take(rows * 8);
-        o_min_slot = take(rows * 4);
-        if (rows > 0x7fffffffull) return fail("minima: more than 2^31 sample rows in one block");
-    }
-    // the statistics record reads the observables' count column, the minima record's hidden one, or one of its own
-    const bool stat_own_counts = stat_counts && !obs && !(min_counts);
-    size_t o_stat_cnt = obs ? w.o_cnt : o_min_cnt;
-    if (stat_own_counts) o_stat_cnt = take(rows * (size_t)h->obs.K * 4);
-    // ... and the structure factors' intensity column, or hidden columns of its own
-    size_t o_stat_amp = w.o_amp, o_stat_inten = w.o_inten;
-    if (stat_inten && !sfac) {
-        o_stat_amp = take(rows * sf_amp);
-        o_stat_inten = take(rows * sf_inten);
-    }
-    // ... and the connectivity column, or a hidden column of its own
-    size_t o_stat_conn = w.o_conn;
-    if (stat_conn && !conn) o_stat_conn = take(rows * cn_stats);
-    if (stats && rows > 0x7fffffffull) return fail("statistics: more than 2^31 sample rows in one block");
-    if (conn && rows > 0x7fffffffull) return fail("connectivity: more than 2^31 sample rows in one block");
-    if (sfac && rows > 0x7fffffffull) return fail("structure factors: more than 2^31 sample rows in one block");
-    if (lazy_rows && rows > 0x7fffffffull) return fail("lazy cluster features: more than 2^31 sample rows in one block");
-    if (obs && rows > 0x7fffffffull) return fail("observables: more than 2^31 sample rows in one block");
+    *out = &sl;
+    return 0;
+}
+
+// the slot's arenas free for `bytes` of a new block
+static int sampled_reserve(SampleSlot &sl, SampleSlot &w, size_t bytes) {
     // the slot's previous block (delivered, or none) must have left the device before its arenas are reused
     if (sl.state != 0) HIPCHK(hipEventSynchronize(sl.copy_done));
-    if (at > sl.cap) {
-        // (growing frees the delivered block's mirror: the slot is empty from here on, whatever happens next)
-        sl.state = 0;
-        if (sl.d) hipFree(sl.d);
-        if (sl.hst) hipHostFree(sl.hst);
-        sl.d = sl.hst = nullptr;
-        sl.cap = 0;
-        HIPCHK(hipMalloc((void **)&sl.d, at));
-        if (hipHostMalloc((void **)&sl.hst, at, hipHostMallocDefault) != hipSuccess) {
-            hipFree(sl.d);
-            sl.d = nullptr;
-            return fail("hipHostMalloc failed (pinned mirror of the sample ring)");
-        }
-        sl.cap = at;
-        w.d = sl.d; w.hst = sl.hst; w.cap = sl.cap;
+    if (bytes <= sl.cap) return 0;
+    // (growing frees the delivered block's mirror: the slot is empty from here on, whatever happens next)
+    sl.state = 0;
+    if (sl.d) hipFree(sl.d);
+    if (sl.hst) hipHostFree(sl.hst);
+    sl.d = sl.hst = nullptr;
+    sl.cap = 0;
+    HIPCHK(hipMalloc((void **)&sl.d, bytes));
+    if (hipHostMalloc((void **)&sl.hst, bytes, hipHostMallocDefault) != hipSuccess) {
+        hipFree(sl.d);
+        sl.d = nullptr;
+        return fail("hipHostMalloc failed (pinned mirror of the sample ring)");
     }
-    w.used = download;
-    w.n = nsamples;
-    w.flags = flags;
+    sl.cap = bytes;
+    w.d = sl.d; w.hst = sl.hst; w.cap = sl.cap;
+    return 0;
+}
+
+// the rows of the block into the arena `d`: enthalpy, features, accepted flags, the columns of the bias and Wang-Landau
+// flags and, where the plan keeps them, the occupancy rows
+static int sampled_record(smolmc_handle *h, unsigned char *d, const BlockPlan &p, int64_t nsamples, int64_t thin_by, int flags) {
+    const SampleColumns &c = p.col;
     SampleBufs smp;
     memset(&smp, 0, sizeof(smp));
     smp.every = thin_by;
-    smp.H = (double *)(sl.d + w.o_H);
-    smp.feat = (double *)(sl.d + (lazy_rows ? o_scal : w.o_feat));
-    smp.acc = sl.d + w.o_acc;
-    smp.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || lazy_rows || obs || minima || stat_counts || sfac || stat_inten || conn || stat_conn
-                  ? sl.d + o_occ_int : nullptr;
-    if (!snapshot_path) {
-        if (inkernel_bias) {
-            if ((w.o_bias - w.o_H) / 8 > 0xffffffffull) return fail("sample block too large for the in-kernel bias column");
-            h->lp.smp_bias_off = (uint32_t)((w.o_bias - w.o_H) / 8);
+    smp.H = (double *)(d + c.o_H);
+    smp.feat = (double *)(d + (p.lazy_rows ? p.o_scal : c.o_feat));
+    smp.acc = d + c.o_acc;
+    smp.occ = p.occ ? d + c.o_occ : nullptr;
+    if (!p.snapshot) {
+        if (p.bias_rows) {
+            if ((c.o_bias - c.o_H) / 8 > 0xffffffffull) return fail("sample block too large for the in-kernel bias column");
+            h->lp.smp_bias_off = (uint32_t)((c.o_bias - c.o_H) / 8);
         }
         const int rc_run = run_steps(h, nsamples * thin_by, smp); // the kernels record the rows themselves, one launch
         h->lp.smp_bias_off = 0;
         if (rc_run) return rc_run;
-        if (lazy_rows) {
-            TRY(launch_eval_full(h, sl.d + o_occ_int, (int)rows, (double *)(sl.d + w.o_feat), 1));
-            TRY(lazy_scalars(h, (double *)(sl.d + w.o_feat), (double *)(sl.d + o_scal), rows, 0));
+        if (p.lazy_rows) {
+            TRY(launch_eval_full(h, d + c.o_occ, (int)p.rows, (double *)(d + c.o_feat), 1));
+            TRY(lazy_scalars(h, (double *)(d + c.o_feat), (double *)(d + p.o_scal), p.rows, 0));
         }
-    } else {
-        SampleBufs none;
-        memset(&none, 0, sizeof(none));
-        KParams &kp = h->kp;
-        SnapshotArgs A;
-        memset(&A, 0, sizeof(A));
-        A.occ = kp.occ; A.features = kp.features; A.enthalpy = kp.enthalpy; A.last_acc = kp.last_acc; A.bias = kp.bias;
-        A.wl_S = kp.wl_entropy; A.wl_hist = kp.wl_hist; A.wl_occ = kp.wl_occur; A.wl_mf = kp.wl_meanf; A.wl_m = kp.wl_m;
-        A.o_occ = smp.occ; A.o_feat = smp.feat; A.o_H = smp.H; A.o_acc = smp.acc;
-        A.o_bias = (flags & SMOLMC_SAMPLE_BIAS) ? (double *)(sl.d + w.o_bias) : nullptr;
-        if (flags & SMOLMC_SAMPLE_WL) {
-            A.o_wlm = (double *)(sl.d + w.o_wlm); A.o_wlS = (double *)(sl.d + w.o_wlS);
-            A.o_wlh = (long long *)(sl.d + w.o_wlh); A.o_wlo = (long long *)(sl.d + w.o_wlo);
-            A.o_wlf = (double *)(sl.d + w.o_wlf);
-        }
-        A.R = h->R; A.F = h->F; A.L = h->L; A.Npad = h->Npad;
-        for (int64_t j = 0; j < nsamples; ++j) {
-            TRY(run_steps(h, thin_by, none));
-            TRY(ensure_features(h)); // (lazy cluster features: the snapshot reads kp.features)
-            A.mf_is_sums = h->wl_sums ? 1 : 0; // (the representation the launch left the per-bin statistics in)
-            hipLaunchKernelGGL(sample_snapshot_kernel, dim3((unsigned)h->R), dim3(256), 0, h->stream, A, (long long)j);
-            HIPCHK(hipGetLastError());
-        }
+        return 0;
     }
-    if (obs) TRY(smolmc_obs_launch(h, sl.d + o_occ_int, rows, (int32_t *)(sl.d + w.o_cnt), (int32_t *)(sl.d + w.o_pair)));
-    if (minima) {
-        if (min_counts && !obs) TRY(smolmc_obs_launch(h, sl.d + o_occ_int, rows, (int32_t *)(sl.d + o_min_cnt), nullptr));
-        TRY(smolmc_min_launch(h, (const double *)(sl.d + w.o_H), (const double *)(sl.d + w.o_feat), sl.d + o_occ_int,
-                              min_counts ? (const int32_t *)(sl.d + o_min_cnt) : nullptr, (uint64_t *)(sl.d + o_min_key),
-                              (int32_t *)(sl.d + o_min_slot), nsamples, thin_by));
+    SampleBufs none;
+    memset(&none, 0, sizeof(none));
+    KParams &kp = h->kp;
+    SnapshotArgs A;
+    memset(&A, 0, sizeof(A));
+    A.occ = kp.occ; A.features = kp.features; A.enthalpy = kp.enthalpy; A.last_acc = kp.last_acc; A.bias = kp.bias;
+    A.wl_S = kp.wl_entropy; A.wl_hist = kp.wl_hist; A.wl_occ = kp.wl_occur; A.wl_mf = kp.wl_meanf; A.wl_m = kp.wl_m;
+    A.o_occ = smp.occ; A.o_feat = smp.feat; A.o_H = smp.H; A.o_acc = smp.acc;
+    A.o_bias = (flags & SMOLMC_SAMPLE_BIAS) ? (double *)(d + c.o_bias) : nullptr;
+    if (flags & SMOLMC_SAMPLE_WL) {
+        A.o_wlm = (double *)(d + c.o_wlm); A.o_wlS = (double *)(d + c.o_wlS);
+        A.o_wlh = (long long *)(d + c.o_wlh); A.o_wlo = (long long *)(d + c.o_wlo);
+        A.o_wlf = (double *)(d + c.o_wlf);
     }
-    if (sfac) TRY(smolmc_sfac_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + w.o_amp), (double *)(sl.d + w.o_inten)));
-    if (conn) TRY(smolmc_conn_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + w.o_conn), nullptr));
-    if (stats) {
-        if (stat_own_counts) TRY(smolmc_obs_launch(h, sl.d + o_occ_int, rows, (int32_t *)(sl.d + o_stat_cnt), nullptr));
-        if (stat_conn && !conn) TRY(smolmc_conn_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + o_stat_conn), nullptr));
-        if (stat_inten && !sfac)
-            TRY(smolmc_sfac_launch(h, sl.d + o_occ_int, rows, (long long *)(sl.d + o_stat_amp), (double *)(sl.d + o_stat_inten)));
-        TRY(smolmc_stat_launch(h, (const double *)(sl.d + w.o_H), (const double *)(sl.d + w.o_feat),
-                               stat_counts ? (const int32_t *)(sl.d + o_stat_cnt) : nullptr,
-                               stat_inten ? (const double *)(sl.d + o_stat_inten) : nullptr,
-                               stat_conn ? (const long long *)(sl.d + o_stat_conn) : nullptr, nsamples));
+    A.R = h->R; A.F = h->F; A.L = h->L; A.Npad = h->Npad;
+    for (int64_t j = 0; j < nsamples; ++j) {
+        TRY(run_steps(h, thin_by, none));
+        TRY(ensure_features(h)); // (lazy cluster features: the snapshot reads kp.features)
+        A.mf_is_sums = h->wl_sums ? 1 : 0; // (the representation the launch left the per-bin statistics in)
+        hipLaunchKernelGGL(sample_snapshot_kernel, dim3((unsigned)h->R), dim3(256), 0, h->stream, A, (long long)j);
+        HIPCHK(hipGetLastError());
     }
-    // download on the copy stream as soon as the block is complete; the next block's launches do not wait for it
+    return 0;
+}
+
+// the rows of a recorded block as the consumers read them
+static RowSources block_rows(unsigned char *d, const BlockPlan &p) {
+    const SampleColumns &c = p.col;
+    RowSources s;
+    s.rows = p.rows;
+    s.H = (const double *)(d + c.o_H); s.feat = (const double *)(d + c.o_feat); s.occ = d + c.o_occ;
+    s.counts = (int32_t *)(d + c.o_cnt); s.pairs = (int32_t *)(d + c.o_pair);
+    s.amp = (long long *)(d + c.o_amp); s.inten = (double *)(d + c.o_inten); s.conn = (long long *)(d + c.o_conn);
+    s.min_key = (uint64_t *)(d + p.o_min_key); s.min_slot = (int32_t *)(d + p.o_min_slot);
+    return s;
+}
+
+// download on the copy stream as soon as the block is complete; the next block's launches do not wait for it
+static int sampled_publish(smolmc_handle *h, SampleSlot &sl, SampleSlot &w) {
     // (the mirror is about to be overwritten: from here the slot no longer holds its old block)
     sl.state = 0;
     HIPCHK(hipEventRecord(sl.kernel_done, h->stream));
@@ -3536,6 +3576,29 @@ extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t th
     sl = w;
     h->next_slot ^= 1;
     return 0;
+}
+
+extern "C" int smolmc_run_sampled(smolmc_handle *h, int64_t nsamples, int64_t thin_by, int flags) {
+    if (!h) return fail("null handle");
+    if (nsamples <= 0 || thin_by <= 0) return fail("nsamples and thin_by must be positive");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(sampled_check_flags(h, thin_by, flags));
+    SampleSlot *sl;
+    TRY(sampled_next_slot(h, &sl));
+    BlockPlan p;
+    TRY(plan_block(h, nsamples, flags, p));
+    // the block is laid out on a COPY of the slot record, which replaces the record only when every launch of the block
+    // has been queued -- a call that fails on the way (an allocation, a launch) leaves the ring as it was: the slot keeps
+    // its delivered block, next_slot does not move
+    SampleSlot w = *sl;
+    TRY(sampled_reserve(*sl, w, p.total));
+    static_cast<SampleColumns &>(w) = p.col;
+    w.used = p.download;
+    w.n = nsamples;
+    w.flags = flags;
+    TRY(sampled_record(h, sl->d, p, nsamples, thin_by, flags));
+    TRY(derive_and_offer(h, block_rows(sl->d, p), flags, nsamples, thin_by));
+    return sampled_publish(h, *sl, w);
 }
 
 // The block the next smolmc_get_samples* call delivers (ABI 8): its sample count and flags, so that a caller can size
@@ -3579,7 +3642,7 @@ extern "C" int smolmc_discard_samples(smolmc_handle *h) {
 
 // host side of a delivery: pinned mirror -> the caller's arrays, a few threads for the big ones (the copy of a
 // block overlaps the kernel of the next one as long as it is shorter)
-static void host_copy(void *dst, const void *src, size_t bytes) {
+void smolmc_host_copy(void *dst, const void *src, size_t bytes) {
     const size_t big = (size_t)8 << 20;
     if (bytes < big) { memcpy(dst, src, bytes); return; }
     const int nt = 4;
@@ -3624,15 +3687,15 @@ static int get_samples_impl(smolmc_handle *h, double *enthalpy, double *features
     if (bias && !(sl->flags & SMOLMC_SAMPLE_BIAS)) return fail("the bias was not recorded (flags bit 1)");
     if ((wl_S || wl_hist || wl_occ || wl_mf || wl_m) && !(sl->flags & SMOLMC_SAMPLE_WL))
         return fail("the Wang-Landau trace was not recorded (flags bit 2)");
-    if (enthalpy) host_copy(enthalpy, sl->hst + sl->o_H, rows * 8);
-    if (features) host_copy(features, sl->hst + sl->o_feat, rows * F * 8);
-    if (accepted) host_copy(accepted, sl->hst + sl->o_acc, rows);
-    if (bias) host_copy(bias, sl->hst + sl->o_bias, rows * 8);
-    if (wl_m) host_copy(wl_m, sl->hst + sl->o_wlm, rows * 8);
-    if (wl_S) host_copy(wl_S, sl->hst + sl->o_wlS, rows * L * 8);
-    if (wl_hist) host_copy(wl_hist, sl->hst + sl->o_wlh, rows * L * 8);
-    if (wl_occ) host_copy(wl_occ, sl->hst + sl->o_wlo, rows * L * 8);
-    if (wl_mf) host_copy(wl_mf, sl->hst + sl->o_wlf, rows * L * F * 8);
+    if (enthalpy) smolmc_host_copy(enthalpy, sl->hst + sl->o_H, rows * 8);
+    if (features) smolmc_host_copy(features, sl->hst + sl->o_feat, rows * F * 8);
+    if (accepted) smolmc_host_copy(accepted, sl->hst + sl->o_acc, rows);
+    if (bias) smolmc_host_copy(bias, sl->hst + sl->o_bias, rows * 8);
+    if (wl_m) smolmc_host_copy(wl_m, sl->hst + sl->o_wlm, rows * 8);
+    if (wl_S) smolmc_host_copy(wl_S, sl->hst + sl->o_wlS, rows * L * 8);
+    if (wl_hist) smolmc_host_copy(wl_hist, sl->hst + sl->o_wlh, rows * L * 8);
+    if (wl_occ) smolmc_host_copy(wl_occ, sl->hst + sl->o_wlo, rows * L * 8);
+    if (wl_mf) smolmc_host_copy(wl_mf, sl->hst + sl->o_wlf, rows * L * F * 8);
     const int32_t *new_of = h->relabelled ? h->new_of.data() : nullptr;
     if (occ8) host_copy_occ<uint8_t>(occ8, sl->hst + sl->o_occ, rows, h->N, h->Npad, new_of);
     if (occ32) host_copy_occ<int32_t>(occ32, sl->hst + sl->o_occ, rows, h->N, h->Npad, new_of);
@@ -3843,137 +3906,79 @@ extern "C" int smolmc_eval_full(smolmc_handle *h, const int32_t *occ, int nocc, 
     return 0;
 }
 
-// ---- observables: kind and pair counts of occupancy rows (the kernel: observables.hip) -------------------------------
-extern "C" int smolmc_set_observables(smolmc_handle *h, const smolmc_observables *obs) {
-    if (!h) return fail("null handle");
-    HIPCHK(hipSetDevice(h->device));
+// ---- shared by the host code of the specs that read occupancy rows (observables.hip, structure.hip, connectivity.hip) ----
+int smolmc_ring_guard(const smolmc_handle *h, int flag, const char *fn, const char *flag_name) {
     for (const SampleSlot &c : h->slots)
-        if (c.state == 1 && (c.flags & SMOLMC_SAMPLE_OBSERVABLES))
-            return fail("smolmc_set_observables while a block recorded with SMOLMC_SAMPLE_OBSERVABLES waits in the ring (call "
-                        "smolmc_get_samples* or smolmc_discard_samples first)");
-    SmolmcObs O;
-    if (h->minima.n_slots && h->minima.n_axes)
-        return fail("smolmc_set_observables while a minima record keyed by composition depends on the observables (call "
-                    "smolmc_set_minima(h, NULL) first)");
-    if (h->stats.n_keys && h->stats.n_count_cols)
-        return fail("smolmc_set_observables while a statistics record with count columns depends on the observables (call "
-                    "smolmc_set_statistics(h, NULL) first)");
-    if (obs) {
-        const int N = h->N, K = obs->n_kinds, S = obs->n_shells;
-        if (!obs->kind_base || S < 0 || (S > 0 && (!obs->shell_ptr || !obs->bonds))) return fail("observables: null argument");
-        if (K < 1 || K > 254) return fail("observables: n_kinds must be 1..254 (a kind is staged as one byte)");
-        const size_t cells = (size_t)S * K * K;
-        if (cells > SMOLMC_MAX_OBS_CELLS) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "observables: %d shells x %d x %d kinds = %zu cells, larger than SMOLMC_MAX_OBS_CELLS = %d", S, K, K,
-                     cells, SMOLMC_MAX_OBS_CELLS);
-            return fail(msg);
-        }
-        // kind_base in the engine's numbering; every code a site can hold must have a kind below K
-        std::vector<int32_t> kb((size_t)N);
-        for (int p = 0; p < N; ++p) {
-            const int s = h->relabelled ? h->new_of[p] : p;
-            const int32_t b = obs->kind_base[p];
-            // (a fixed site outside every cluster: the tables do not say how many codes it has, site_ncodes is the
-            // model's widest site there -- its block must hold one kind at least; the kernel leaves out a kind >= K)
-            const int width = h->site_width_known[s] ? (int)h->site_ncodes[s] : 1;
-            if (b >= 0 && b + width > K) {
-                char msg[200];
-                snprintf(msg, sizeof msg, "observables: kind_base[%d] + site_ncodes = %d + %d is larger than n_kinds = %d: kind out of range", p,
-                         (int)b, width, K);
-                return fail(msg);
-            }
-            kb[s] = b < 0 ? -1 : b;
-        }
-        const int64_t nb = S ? obs->shell_ptr[S] : 0;
-        for (int sidx = 0; sidx < S; ++sidx)
-            if (obs->shell_ptr[0] != 0 || obs->shell_ptr[sidx] > obs->shell_ptr[sidx + 1])
-                return fail("observables: shell_ptr must be ascending from 0");
-        O.K = K; O.n_shells = S; O.cells = cells;
-        O.kind_base = kb;
-        O.pair_copies = smolmc_obs_pair_copies(cells);
-        O.lds = smolmc_obs_lds_bytes(h->Npad, K, cells, O.pair_copies);
-        if (O.lds > 64 * 1024) {
-            char msg[200];
-            snprintf(msg, sizeof msg, "observables: a row of %d sites is too long to stage in LDS next to the histograms (%zu bytes, 65536 at most)",
-                     N, O.lds);
-            return fail(msg);
-        }
-        // (a row that fits LDS has fewer than 2^16 sites: a bond is one word)
-        std::vector<uint32_t> bw((size_t)nb);
-        for (int64_t b = 0; b < nb; ++b) {
-            const int32_t i = obs->bonds[2 * b], j = obs->bonds[2 * b + 1];
-            if (i < 0 || i >= N || j < 0 || j >= N) {
-                char msg[160];
-                snprintf(msg, sizeof msg, "observables: bond %lld = (%d, %d) out of range (%d sites)", (long long)b, (int)i, (int)j, N);
-                return fail(msg);
-            }
-            const uint32_t ei = (uint32_t)(h->relabelled ? h->new_of[i] : i), ej = (uint32_t)(h->relabelled ? h->new_of[j] : j);
-            bw[(size_t)b] = ei | (ej << 16);
-        }
-        hipError_t e = hipMalloc((void **)&O.d_kind_base, std::max<size_t>((size_t)N * 4, 16));
-        if (e == hipSuccess) e = hipMalloc((void **)&O.d_shell_ptr, ((size_t)S + 1) * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&O.d_bonds, std::max<size_t>((size_t)nb * 4, 16));
-        if (e == hipSuccess) e = hipMemcpy(O.d_kind_base, kb.data(), (size_t)N * 4, hipMemcpyHostToDevice);
-        const int64_t zero = 0;
-        if (e == hipSuccess) e = hipMemcpy(O.d_shell_ptr, S ? obs->shell_ptr : &zero, ((size_t)S + 1) * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && nb) e = hipMemcpy(O.d_bonds, bw.data(), (size_t)nb * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            free_observables(O);
-            return fail(std::string("observables upload: ") + hipGetErrorString(e));
-        }
-    }
-    // the kernels of queued blocks read the old tables: let them finish; delivered blocks of the old shape are forgotten
+        if (c.state == 1 && (c.flags & flag))
+            return fail(std::string(fn) + " while a block recorded with " + flag_name +
+                        " waits in the ring (call smolmc_get_samples* or smolmc_discard_samples first)");
+    return 0;
+}
+
+int smolmc_ring_forget(smolmc_handle *h, int flag) {
     HIPCHK(hipStreamSynchronize(h->stream));
     for (SampleSlot &c : h->slots)
-        if (c.state == 2 && (c.flags & SMOLMC_SAMPLE_OBSERVABLES)) c.state = 0;
-    free_observables(h->obs);
-    h->obs = O;
+        if (c.state == 2 && (c.flags & flag)) c.state = 0;
     return 0;
 }
 
-extern "C" int smolmc_observables_shape(smolmc_handle *h, int *n_kinds, int *n_shells) {
-    if (!h) return fail("null handle");
-    if (n_kinds) *n_kinds = h->obs.K;
-    if (n_shells) *n_shells = h->obs.n_shells;
-    return 0;
-}
-
-extern "C" int smolmc_eval_observables(smolmc_handle *h, const int32_t *occ, int nocc, int32_t *counts, int32_t *pairs) {
-    if (!h) return fail("null handle");
-    if (!h->obs.K) return fail("no observables set: call smolmc_set_observables first");
-    HIPCHK(hipSetDevice(h->device));
-    const uint8_t *d_occ8 = h->kp.occ;
-    if (occ) {
-        if (nocc <= 0) return 0;
-        TRY(ensure_eval_occ(h, nocc));
-        std::vector<int32_t> occ_engine;
-        occ = occ_in(h, occ, (size_t)nocc, occ_engine);
-        for (size_t r = 0; r < (size_t)nocc; ++r)
-            for (int s = 0; s < h->N; ++s) {
-                const int32_t b = h->obs.kind_base[s], c = occ[r * h->N + s];
-                if (b >= 0 && c >= 0 && b + c >= h->obs.K) {
-                    char msg[200];
-                    snprintf(msg, sizeof msg, "observables: occupancy code %d on site %d gives kind %d, n_kinds = %d: kind out of range", (int)c,
-                             h->relabelled ? (int)h->old_of[s] : s, (int)(b + c), h->obs.K);
-                    return fail(msg);
-                }
-            }
-        TRY(upload_occ(h, occ, nocc, h->d_eval_occ));
-        d_occ8 = h->d_eval_occ;
-    } else {
-        nocc = h->R;
+int smolmc_kind_base_in(const smolmc_handle *h, const int32_t *kind_base, int K, const char *noun, std::vector<int32_t> &kb,
+                        size_t *n_counted) {
+    kb.assign((size_t)h->N, 0);
+    size_t counted = 0;
+    for (int p = 0; p < h->N; ++p) {
+        const int s = h->relabelled ? h->new_of[p] : p;
+        const int32_t b = kind_base[p];
+        // (a fixed site outside every cluster: the tables do not say how many codes it has, site_ncodes is the
+        // model's widest site there -- its block must hold one kind at least; the kernels leave out a kind >= K)
+        const int width = h->site_width_known[s] ? (int)h->site_ncodes[s] : 1;
+        if (b >= 0 && b + width > K) {
+            char msg[256];
+            snprintf(msg, sizeof msg, "%s: kind_base[%d] + site_ncodes = %d + %d is larger than n_kinds = %d: kind out of range", noun, p,
+                     (int)b, width, K);
+            return fail(msg);
+        }
+        kb[s] = b < 0 ? -1 : b;
+        counted += b >= 0;
     }
-    const size_t nc = (size_t)nocc * h->obs.K, np = (size_t)nocc * h->obs.cells;
-    int32_t *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>((nc + np) * 4, 16)));
-    int rc = smolmc_obs_launch(h, d_occ8, (size_t)nocc, d_out, d_out + nc);
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (!rc && e == hipSuccess && counts) e = hipMemcpy(counts, d_out, nc * 4, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && pairs && np) e = hipMemcpy(pairs, d_out + nc, np * 4, hipMemcpyDeviceToHost);
-    hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("eval_observables: ") + hipGetErrorString(e));
+    if (n_counted) *n_counted = counted;
+    return 0;
+}
+
+int smolmc_eval_rows(smolmc_handle *h, const int32_t *occ, int nocc, const std::vector<int32_t> &kind_base, int K, const char *noun,
+                     const uint8_t **d_occ8, size_t *rows) {
+    *d_occ8 = h->kp.occ;
+    *rows = (size_t)h->R;
+    if (!occ) return 0;
+    *rows = 0;
+    if (nocc <= 0) return 0;
+    TRY(ensure_eval_occ(h, nocc));
+    std::vector<int32_t> occ_engine;
+    occ = occ_in(h, occ, (size_t)nocc, occ_engine);
+    for (size_t r = 0; r < (size_t)nocc; ++r)
+        for (int s = 0; s < h->N; ++s) {
+            const int32_t b = kind_base[s], c = occ[r * h->N + s];
+            if (b >= 0 && c >= 0 && b + c >= K) {
+                char msg[256];
+                snprintf(msg, sizeof msg, "%s: occupancy code %d on site %d gives kind %d, n_kinds = %d: kind out of range", noun, (int)c,
+                         h->relabelled ? (int)h->old_of[s] : s, (int)(b + c), K);
+                return fail(msg);
+            }
+        }
+    TRY(upload_occ(h, occ, nocc, h->d_eval_occ));
+    *d_occ8 = h->d_eval_occ;
+    *rows = (size_t)nocc;
+    return 0;
+}
+
+int smolmc_sample_block(smolmc_handle *h, int flag, const char *not_recorded, const SampleSlot **sl, size_t *rows) {
+    if (!h) return fail("null handle");
+    *sl = next_delivery(h);
+    if (!*sl) return fail("no samples recorded: call smolmc_run_sampled first");
+    if (!((*sl)->flags & flag)) return fail(not_recorded);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize((*sl)->copy_done));
+    *rows = (size_t)(*sl)->n * h->R;
     return 0;
 }
 
@@ -3985,9 +3990,9 @@ extern "C" int smolmc_update_minima(smolmc_handle *h) {
     if (!M.n_slots) return fail("no minima record set: call smolmc_set_minima first");
     HIPCHK(hipSetDevice(h->device));
     TRY(ensure_features(h));
-    const bool counts = h->obs.K && h->obs.K == M.K;
-    if (counts) TRY(smolmc_obs_launch(h, h->kp.occ, (size_t)h->R, M.u_counts, nullptr));
-    return smolmc_min_launch(h, h->kp.enthalpy, h->kp.features, h->kp.occ, counts ? M.u_counts : nullptr, M.u_key, M.u_slot, 1, 1);
+    RowSources s = walker_rows(h);
+    s.counts = M.u_counts; s.min_key = M.u_key; s.min_slot = M.u_slot;
+    return derive_and_offer(h, s, SMOLMC_SAMPLE_MINIMA, 1, 1);
 }
 
 // one offer of the walkers' current states to the statistics record (statistics.hip), as smolmc_update_minima
@@ -3997,420 +4002,9 @@ extern "C" int smolmc_update_statistics(smolmc_handle *h) {
     if (!S.n_keys) return fail("no statistics record set: call smolmc_set_statistics first");
     HIPCHK(hipSetDevice(h->device));
     TRY(ensure_features(h));
-    const bool counts = S.n_count_cols > 0, inten = S.n_inten_cols > 0, conn = S.n_conn_cols > 0;
-    if (counts) TRY(smolmc_obs_launch(h, h->kp.occ, (size_t)h->R, S.u_counts, nullptr));
-    if (inten) TRY(smolmc_sfac_launch(h, h->kp.occ, (size_t)h->R, h->sfac.u_amp, h->sfac.u_inten));
-    if (conn) TRY(smolmc_conn_launch(h, h->kp.occ, (size_t)h->R, h->conn.u_stats, nullptr));
-    return smolmc_stat_launch(h, h->kp.enthalpy, h->kp.features, counts ? S.u_counts : nullptr, inten ? h->sfac.u_inten : nullptr,
-                              conn ? h->conn.u_stats : nullptr, 1);
-}
-
-// ---- connectivity: components of occupancy rows and whether they wrap the cell (the kernel: connectivity.hip) ----------
-extern "C" int smolmc_set_connectivity(smolmc_handle *h, const smolmc_connectivity *sp) {
-    if (!h) return fail("null handle");
-    HIPCHK(hipSetDevice(h->device));
-    for (const SampleSlot &c : h->slots)
-        if (c.state == 1 && (c.flags & SMOLMC_SAMPLE_CONNECTIVITY))
-            return fail("smolmc_set_connectivity while a block recorded with SMOLMC_SAMPLE_CONNECTIVITY waits in the ring (call "
-                        "smolmc_get_samples* or smolmc_discard_samples first)");
-    if (h->stats.n_keys && h->stats.n_conn_cols)
-        return fail("smolmc_set_connectivity while a statistics record with connectivity columns depends on the spec (call "
-                    "smolmc_set_statistics(h, NULL) first)");
-    SmolmcConn S;
-    if (sp) {
-        const int N = h->N, K = sp->n_kinds, G = sp->n_graphs;
-        char msg[256];
-        if (G < 1 || G > SMOLMC_MAX_CONN_GRAPHS) {
-            snprintf(msg, sizeof msg, "connectivity: n_graphs must be 1..%d, got %d", SMOLMC_MAX_CONN_GRAPHS, G);
-            return fail(msg);
-        }
-        if (!sp->kind_base || !sp->member_mask || !sp->bond_ptr) return fail("connectivity: null argument");
-        if (K < 1 || K > 254) return fail("connectivity: n_kinds must be 1..254 (a kind is staged as one byte)");
-        S.lds = smolmc_conn_lds_bytes(N, h->Npad);
-        if (!S.lds) {
-            snprintf(msg, sizeof msg, "connectivity: a row of %d sites is too long for the LDS plan: a label with its path sum, a size and "
-                     "a mask take 11 bytes a site next to the row's %d, 65536 at most", N, h->Npad);
-            return fail(msg);
-        }
-        if ((long long)N * SMOLMC_MAX_CONN_IMAGE > SMOLMC_MAX_CONN_PATH_SUM) {
-            snprintf(msg, sizeof msg, "connectivity: %d sites x SMOLMC_MAX_CONN_IMAGE = %d is larger than SMOLMC_MAX_CONN_PATH_SUM = %d: "
-                     "the image sum of a path could overflow its 16 bits", N, SMOLMC_MAX_CONN_IMAGE, SMOLMC_MAX_CONN_PATH_SUM);
-            return fail(msg);
-        }
-        // kind_base in the engine's numbering; every code a site can hold must have a kind below K (as smolmc_set_observables)
-        std::vector<int32_t> kb((size_t)N);
-        for (int p = 0; p < N; ++p) {
-            const int s = h->relabelled ? h->new_of[p] : p;
-            const int32_t b = sp->kind_base[p];
-            const int width = h->site_width_known[s] ? (int)h->site_ncodes[s] : 1;
-            if (b >= 0 && b + width > K) {
-                snprintf(msg, sizeof msg, "connectivity: kind_base[%d] + site_ncodes = %d + %d is larger than n_kinds = %d: kind out of range",
-                         p, (int)b, width, K);
-                return fail(msg);
-            }
-            kb[s] = b < 0 ? -1 : b;
-        }
-        for (int g = 0; g < G; ++g)
-            for (int k = K; k < 256; ++k)
-                if ((sp->member_mask[4 * g + (k >> 6)] >> (k & 63)) & 1ull) {
-                    snprintf(msg, sizeof msg, "connectivity: graph %d names member kind %d, n_kinds is %d: kind out of range", g, k, K);
-                    return fail(msg);
-                }
-        if (sp->bond_ptr[0] != 0) return fail("connectivity: bond_ptr[0] must be 0");
-        for (int g = 0; g < G; ++g)
-            if (sp->bond_ptr[g + 1] < sp->bond_ptr[g]) return fail("connectivity: bond_ptr must not decrease");
-        const int64_t nb = sp->bond_ptr[G];
-        if (nb > 0 && (!sp->bonds || !sp->images)) return fail("connectivity: null argument");
-        // the neighbours of every site: both directions of every bond, engine numbering, duplicates dropped (a bond listed
-        // twice joins what it joined once)
-        std::vector<uint32_t> adj;
-        std::vector<std::pair<int32_t, uint32_t>> ent;
-        for (int g = 0; g < G; ++g) {
-            ent.clear();
-            for (int64_t b = sp->bond_ptr[g]; b < sp->bond_ptr[g + 1]; ++b) {
-                const int32_t i = sp->bonds[2 * b], j = sp->bonds[2 * b + 1];
-                if (i < 0 || i >= N || j < 0 || j >= N) {
-                    snprintf(msg, sizeof msg, "connectivity: graph %d bond %lld = (%d, %d), %d sites: bond out of range", g,
-                             (long long)(b - sp->bond_ptr[g]), (int)i, (int)j, N);
-                    return fail(msg);
-                }
-                const int8_t *w = sp->images + 3 * b;
-                for (int a = 0; a < 3; ++a)
-                    if (w[a] < -SMOLMC_MAX_CONN_IMAGE || w[a] > SMOLMC_MAX_CONN_IMAGE) {
-                        snprintf(msg, sizeof msg, "connectivity: graph %d bond %lld has image (%d, %d, %d), beyond SMOLMC_MAX_CONN_IMAGE = %d: "
-                                 "image out of range", g, (long long)(b - sp->bond_ptr[g]), (int)w[0], (int)w[1], (int)w[2],
-                                 SMOLMC_MAX_CONN_IMAGE);
-                        return fail(msg);
-                    }
-                const int si = h->relabelled ? h->new_of[i] : i, sj = h->relabelled ? h->new_of[j] : j;
-                if (si == sj && !w[0] && !w[1] && !w[2]) continue; // (a site joined to itself in its own cell: no bond)
-                // seen from i the neighbour j lies in image w, seen from j the neighbour i lies in image -w
-                ent.push_back({si, (uint32_t)sj | (uint32_t)(w[0] + 8) << 16 | (uint32_t)(w[1] + 8) << 20 | (uint32_t)(w[2] + 8) << 24});
-                ent.push_back({sj, (uint32_t)si | (uint32_t)(8 - w[0]) << 16 | (uint32_t)(8 - w[1]) << 20 | (uint32_t)(8 - w[2]) << 24});
-            }
-            std::sort(ent.begin(), ent.end());
-            ent.erase(std::unique(ent.begin(), ent.end()), ent.end());
-            // four to a group, group k of all sites side by side; a list that ends early is filled up with the site itself
-            std::vector<int> deg((size_t)N, 0);
-            int most = 0;
-            for (const auto &x : ent) most = std::max(most, ++deg[x.first]);
-            const int groups = (most + 3) / 4;
-            if ((adj.size() + (size_t)groups * N * 4) * 4 > ((size_t)1 << 30)) return fail("connectivity: the neighbour lists take more than 1 GiB");
-            S.adj_off[g] = (int)(adj.size() / 4);
-            S.adj_groups[g] = groups;
-            const size_t base = adj.size();
-            adj.resize(base + (size_t)groups * N * 4);
-            for (int k = 0; k < groups; ++k)
-                for (int s = 0; s < N; ++s)
-                    for (int i = 0; i < 4; ++i) adj[base + ((size_t)k * N + s) * 4 + i] = (uint32_t)s | 8u << 16 | 8u << 20 | 8u << 24;
-            std::fill(deg.begin(), deg.end(), 0);
-            for (const auto &x : ent) {
-                const int n = deg[x.first]++;
-                adj[base + ((size_t)(n / 4) * N + x.first) * 4 + (n & 3)] = x.second;
-            }
-        }
-        std::vector<uint16_t> caller_of((size_t)N);
-        for (int s = 0; s < N; ++s) caller_of[s] = (uint16_t)(h->relabelled ? h->old_of[s] : s);
-        S.K = K; S.G = G;
-        S.kind_base = kb;
-        // one arena: the spec's arrays, then the scratch of smolmc_update_statistics
-        size_t at = 0;
-        auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
-        const size_t o_kb = take((size_t)N * 4), o_mk = take((size_t)G * 32), o_co = take((size_t)N * 2),
-                     o_ad = take(adj.size() * 4),
-                     o_us = take((size_t)h->R * G * SMOLMC_CONN_STATS * 8), o_ps = take(16);
-        hipError_t e = hipMalloc((void **)&S.arena, at);
-        if (e != hipSuccess) return fail(std::string("connectivity: hipMalloc: ") + hipGetErrorString(e));
-        unsigned char *d = S.arena;
-        S.d_kind_base = (int32_t *)(d + o_kb); S.d_mask = (unsigned long long *)(d + o_mk); S.d_caller_of = (uint16_t *)(d + o_co);
-        S.d_adj = (uint32_t *)(d + o_ad); S.u_stats = (long long *)(d + o_us);
-        S.d_passes = (unsigned long long *)(d + o_ps);
-        e = hipMemcpy(S.d_kind_base, kb.data(), (size_t)N * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(S.d_mask, sp->member_mask, (size_t)G * 32, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(S.d_caller_of, caller_of.data(), (size_t)N * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess && !adj.empty()) e = hipMemcpy(S.d_adj, adj.data(), adj.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(S.d_passes, 0, 16);
-        if (e != hipSuccess) {
-            smolmc_conn_free(S);
-            return fail(std::string("connectivity upload: ") + hipGetErrorString(e));
-        }
-    }
-    // the kernels of queued blocks read the old tables: let them finish; delivered blocks of the old shape are forgotten
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (SampleSlot &c : h->slots)
-        if (c.state == 2 && (c.flags & SMOLMC_SAMPLE_CONNECTIVITY)) c.state = 0;
-    smolmc_conn_free(h->conn);
-    h->conn = S;
-    return 0;
-}
-
-extern "C" int smolmc_connectivity_shape(smolmc_handle *h, int *n_graphs, int *n_kinds) {
-    if (!h) return fail("null handle");
-    if (n_graphs) *n_graphs = h->conn.G;
-    if (n_kinds) *n_kinds = h->conn.G ? h->conn.K : 0;
-    return 0;
-}
-
-extern "C" int smolmc_eval_connectivity(smolmc_handle *h, const int32_t *occ, int nocc, int64_t *stats, int32_t *labels) {
-    if (!h) return fail("null handle");
-    const SmolmcConn &S = h->conn;
-    if (!S.G) return fail("no connectivity spec set: call smolmc_set_connectivity first");
-    HIPCHK(hipSetDevice(h->device));
-    const uint8_t *d_occ8 = h->kp.occ;
-    if (occ) {
-        if (nocc <= 0) return 0;
-        TRY(ensure_eval_occ(h, nocc));
-        std::vector<int32_t> occ_engine;
-        occ = occ_in(h, occ, (size_t)nocc, occ_engine);
-        for (size_t r = 0; r < (size_t)nocc; ++r)
-            for (int s = 0; s < h->N; ++s) {
-                const int32_t b = S.kind_base[s], c = occ[r * h->N + s];
-                if (b >= 0 && c >= 0 && b + c >= S.K) {
-                    char msg[200];
-                    snprintf(msg, sizeof msg, "connectivity: occupancy code %d on site %d gives kind %d, n_kinds = %d: kind out of range",
-                             (int)c, h->relabelled ? (int)h->old_of[s] : s, (int)(b + c), S.K);
-                    return fail(msg);
-                }
-            }
-        TRY(upload_occ(h, occ, nocc, h->d_eval_occ));
-        d_occ8 = h->d_eval_occ;
-    } else {
-        nocc = h->R;
-    }
-    const size_t ns = (size_t)nocc * S.G * SMOLMC_CONN_STATS, nl = labels ? (size_t)nocc * S.G * h->N : 0;
-    unsigned char *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>(ns * 8 + nl * 4, 16)));
-    int rc = smolmc_conn_launch(h, d_occ8, (size_t)nocc, (long long *)d_out, labels ? (int32_t *)(d_out + ns * 8) : nullptr);
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (!rc && e == hipSuccess && stats) e = hipMemcpy(stats, d_out, ns * 8, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && labels) e = hipMemcpy(labels, d_out + ns * 8, nl * 4, hipMemcpyDeviceToHost);
-    hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("eval_connectivity: ") + hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" int smolmc_get_sample_connectivity(smolmc_handle *h, int64_t *stats) {
-    if (!h) return fail("null handle");
-    SampleSlot *sl = next_delivery(h);
-    if (!sl) return fail("no samples recorded: call smolmc_run_sampled first");
-    if (!(sl->flags & SMOLMC_SAMPLE_CONNECTIVITY)) return fail("the connectivity stats were not recorded (flags bit 7)");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipEventSynchronize(sl->copy_done));
-    const size_t rows = (size_t)sl->n * h->R;
-    if (stats) host_copy(stats, sl->hst + sl->o_conn, rows * (size_t)h->conn.G * SMOLMC_CONN_STATS * 8);
-    return 0;
-}
-
-// ---- structure factors: fixed-point amplitudes and intensities of occupancy rows (the kernel: structure.hip) ----------
-extern "C" int smolmc_set_structure(smolmc_handle *h, const smolmc_structure *sp) {
-    if (!h) return fail("null handle");
-    HIPCHK(hipSetDevice(h->device));
-    for (const SampleSlot &c : h->slots)
-        if (c.state == 1 && (c.flags & SMOLMC_SAMPLE_STRUCTURE))
-            return fail("smolmc_set_structure while a block recorded with SMOLMC_SAMPLE_STRUCTURE waits in the ring (call "
-                        "smolmc_get_samples* or smolmc_discard_samples first)");
-    if (h->stats.n_keys && h->stats.n_inten_cols)
-        return fail("smolmc_set_structure while a statistics record with intensity columns depends on the spec (call "
-                    "smolmc_set_statistics(h, NULL) first)");
-    SmolmcStruct S;
-    if (sp) {
-        const int N = h->N, K = sp->n_kinds, Q = sp->n_points, M = sp->n_phases, I = sp->n_intensities;
-        char msg[256];
-        if (!sp->kind_base || !sp->phase || !sp->table || (I > 0 && (!sp->intensity || !sp->intensity_scale)))
-            return fail("structure factors: null argument");
-        if (K < 1 || K > 254) return fail("structure factors: n_kinds must be 1..254 (a kind is staged as one byte)");
-        if (Q < 1 || Q > SMOLMC_MAX_STRUCT_POINTS) {
-            snprintf(msg, sizeof msg, "structure factors: n_points must be 1..%d, got %d", SMOLMC_MAX_STRUCT_POINTS, Q);
-            return fail(msg);
-        }
-        if (M < 1 || M > SMOLMC_MAX_STRUCT_PHASES) {
-            snprintf(msg, sizeof msg, "structure factors: n_phases must be 1..%d, got %d", SMOLMC_MAX_STRUCT_PHASES, M);
-            return fail(msg);
-        }
-        if ((size_t)K * M > SMOLMC_MAX_STRUCT_CELLS) {
-            snprintf(msg, sizeof msg, "structure factors: %d kinds x %d phase classes = %zu cells, larger than SMOLMC_MAX_STRUCT_CELLS = %d",
-                     K, M, (size_t)K * M, SMOLMC_MAX_STRUCT_CELLS);
-            return fail(msg);
-        }
-        if (I < 0 || I > SMOLMC_MAX_STRUCT_INTENSITIES) {
-            snprintf(msg, sizeof msg, "structure factors: n_intensities must be 0..%d, got %d", SMOLMC_MAX_STRUCT_INTENSITIES, I);
-            return fail(msg);
-        }
-        // kind_base in the engine's numbering; every code a site can hold must have a kind below K (as smolmc_set_observables)
-        std::vector<int32_t> kb((size_t)N);
-        size_t n_counted = 0;
-        for (int p = 0; p < N; ++p) {
-            const int s = h->relabelled ? h->new_of[p] : p;
-            const int32_t b = sp->kind_base[p];
-            const int width = h->site_width_known[s] ? (int)h->site_ncodes[s] : 1;
-            if (b >= 0 && b + width > K) {
-                snprintf(msg, sizeof msg, "structure factors: kind_base[%d] + site_ncodes = %d + %d is larger than n_kinds = %d: kind out of range",
-                         p, (int)b, width, K);
-                return fail(msg);
-            }
-            kb[s] = b < 0 ? -1 : b;
-            n_counted += b >= 0;
-        }
-        std::vector<uint16_t> ph((size_t)Q * N);
-        for (int q = 0; q < Q; ++q)
-            for (int p = 0; p < N; ++p) {
-                const uint16_t v = sp->phase[(size_t)q * N + p];
-                if (v >= M) {
-                    snprintf(msg, sizeof msg, "structure factors: phase[%d][%d] = %d, n_phases is %d: phase out of range", q, p, (int)v, M);
-                    return fail(msg);
-                }
-                ph[(size_t)q * N + (h->relabelled ? h->new_of[p] : p)] = v;
-            }
-        unsigned long long peak = 0;
-        for (size_t i = 0; i < (size_t)Q * M * 2; ++i) {
-            const int64_t v = sp->table[i];
-            const unsigned long long a = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
-            peak = std::max(peak, a);
-        }
-        if (n_counted && peak >= (1ull << 62) / n_counted + ((1ull << 62) % n_counted != 0)) {
-            snprintf(msg, sizeof msg, "structure factors: %zu counted sites x max|table| = %llu reaches 2^62: an amplitude could overflow",
-                     n_counted, peak);
-            return fail(msg);
-        }
-        for (int i = 0; i < I; ++i) {
-            const int32_t q = sp->intensity[3 * i], a = sp->intensity[3 * i + 1], b = sp->intensity[3 * i + 2];
-            if (q < 0 || q >= Q) {
-                snprintf(msg, sizeof msg, "structure factors: intensity %d names point %d, n_points is %d: point out of range", i, (int)q, Q);
-                return fail(msg);
-            }
-            if (a < 0 || a >= K || b < 0 || b >= K) {
-                snprintf(msg, sizeof msg, "structure factors: intensity %d names kinds (%d, %d), n_kinds is %d: kind out of range", i, (int)a,
-                         (int)b, K);
-                return fail(msg);
-            }
-            if (!std::isfinite(sp->intensity_scale[i])) {
-                snprintf(msg, sizeof msg, "structure factors: intensity_scale[%d] is not finite", i);
-                return fail(msg);
-            }
-        }
-        S.K = K; S.Q = Q; S.M = M; S.I = I;
-        S.W = (N + 63) / 64;
-        if (!smolmc_sfac_plan(N, h->Npad, K, M, Q, &S.mask, &S.copies, &S.chunk, &S.lds)) {
-            snprintf(msg, sizeof msg, "structure factors: a row of %d sites is too long to stage in LDS next to the %zu counters of a point "
-                     "(%zu bytes, 65536 at most)", N, (size_t)K * M, (size_t)h->Npad + (size_t)K * M * 4);
-            return fail(msg);
-        }
-        S.kind_base = kb;
-        // one arena: the spec's arrays, then the scratch of smolmc_update_statistics
-        size_t at = 0;
-        auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
-        const size_t R = (size_t)h->R;
-        const size_t o_kb = take((size_t)N * 4), o_ph = take((size_t)Q * N * 2), o_tb = take((size_t)Q * M * 16),
-                     o_it = take((size_t)I * 12), o_sc = take((size_t)I * 8), o_ua = take(R * Q * K * 16), o_ui = take(R * I * 8);
-        // the mask kernel's table: for every point and class the sites of the class as bits, words of one (word, class)
-        // side by side over the points
-        std::vector<unsigned long long> masks;
-        if (S.mask) {
-            masks.assign((size_t)S.W * M * Q, 0ull);
-            for (int q = 0; q < Q; ++q)
-                for (int s = 0; s < N; ++s)
-                    masks[((size_t)(s >> 6) * M + ph[(size_t)q * N + s]) * Q + q] |= 1ull << (s & 63);
-        }
-        const size_t o_mk = take(masks.size() * 8);
-        hipError_t e = hipMalloc((void **)&S.arena, at);
-        if (e != hipSuccess) return fail(std::string("structure factors: hipMalloc: ") + hipGetErrorString(e));
-        unsigned char *d = S.arena;
-        S.d_kind_base = (int32_t *)(d + o_kb); S.d_phase = (uint16_t *)(d + o_ph); S.d_table = (long long *)(d + o_tb);
-        S.d_intensity = (int32_t *)(d + o_it); S.d_scale = (double *)(d + o_sc);
-        S.u_amp = (long long *)(d + o_ua); S.u_inten = (double *)(d + o_ui);
-        S.d_masks = (unsigned long long *)(d + o_mk);
-        e = hipMemcpy(S.d_kind_base, kb.data(), (size_t)N * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(S.d_phase, ph.data(), (size_t)Q * N * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(S.d_table, sp->table, (size_t)Q * M * 16, hipMemcpyHostToDevice);
-        if (e == hipSuccess && I) e = hipMemcpy(S.d_intensity, sp->intensity, (size_t)I * 12, hipMemcpyHostToDevice);
-        if (e == hipSuccess && I) e = hipMemcpy(S.d_scale, sp->intensity_scale, (size_t)I * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && !masks.empty()) e = hipMemcpy(S.d_masks, masks.data(), masks.size() * 8, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            smolmc_sfac_free(S);
-            return fail(std::string("structure factors upload: ") + hipGetErrorString(e));
-        }
-    }
-    // the kernels of queued blocks read the old tables: let them finish; delivered blocks of the old shape are forgotten
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (SampleSlot &c : h->slots)
-        if (c.state == 2 && (c.flags & SMOLMC_SAMPLE_STRUCTURE)) c.state = 0;
-    smolmc_sfac_free(h->sfac);
-    h->sfac = S;
-    return 0;
-}
-
-extern "C" int smolmc_structure_shape(smolmc_handle *h, int *n_points, int *n_kinds, int *n_intensities) {
-    if (!h) return fail("null handle");
-    if (n_points) *n_points = h->sfac.Q;
-    if (n_kinds) *n_kinds = h->sfac.Q ? h->sfac.K : 0;
-    if (n_intensities) *n_intensities = h->sfac.I;
-    return 0;
-}
-
-extern "C" int smolmc_eval_structure(smolmc_handle *h, const int32_t *occ, int nocc, int64_t *amp, double *inten) {
-    if (!h) return fail("null handle");
-    const SmolmcStruct &S = h->sfac;
-    if (!S.Q) return fail("no structure-factor spec set: call smolmc_set_structure first");
-    HIPCHK(hipSetDevice(h->device));
-    const uint8_t *d_occ8 = h->kp.occ;
-    if (occ) {
-        if (nocc <= 0) return 0;
-        TRY(ensure_eval_occ(h, nocc));
-        std::vector<int32_t> occ_engine;
-        occ = occ_in(h, occ, (size_t)nocc, occ_engine);
-        for (size_t r = 0; r < (size_t)nocc; ++r)
-            for (int s = 0; s < h->N; ++s) {
-                const int32_t b = S.kind_base[s], c = occ[r * h->N + s];
-                if (b >= 0 && c >= 0 && b + c >= S.K) {
-                    char msg[200];
-                    snprintf(msg, sizeof msg, "structure factors: occupancy code %d on site %d gives kind %d, n_kinds = %d: kind out of range",
-                             (int)c, h->relabelled ? (int)h->old_of[s] : s, (int)(b + c), S.K);
-                    return fail(msg);
-                }
-            }
-        TRY(upload_occ(h, occ, nocc, h->d_eval_occ));
-        d_occ8 = h->d_eval_occ;
-    } else {
-        nocc = h->R;
-    }
-    const size_t na = (size_t)nocc * S.Q * S.K * 2, ni = (size_t)nocc * S.I;
-    unsigned char *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>((na + ni) * 8, 16)));
-    int rc = smolmc_sfac_launch(h, d_occ8, (size_t)nocc, (long long *)d_out, (double *)(d_out + na * 8));
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (!rc && e == hipSuccess && amp) e = hipMemcpy(amp, d_out, na * 8, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && inten && ni) e = hipMemcpy(inten, d_out + na * 8, ni * 8, hipMemcpyDeviceToHost);
-    hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("eval_structure: ") + hipGetErrorString(e));
-    return 0;
-}
-
-extern "C" int smolmc_get_sample_structure(smolmc_handle *h, int64_t *amp, double *inten) {
-    if (!h) return fail("null handle");
-    SampleSlot *sl = next_delivery(h);
-    if (!sl) return fail("no samples recorded: call smolmc_run_sampled first");
-    if (!(sl->flags & SMOLMC_SAMPLE_STRUCTURE)) return fail("the structure factors were not recorded (flags bit 6)");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipEventSynchronize(sl->copy_done));
-    const size_t rows = (size_t)sl->n * h->R;
-    if (amp) host_copy(amp, sl->hst + sl->o_amp, rows * (size_t)h->sfac.Q * h->sfac.K * 16);
-    if (inten) host_copy(inten, sl->hst + sl->o_inten, rows * (size_t)h->sfac.I * 8);
-    return 0;
-}
-
-extern "C" int smolmc_get_sample_observables(smolmc_handle *h, int32_t *counts, int32_t *pairs) {
-    if (!h) return fail("null handle");
-    SampleSlot *sl = next_delivery(h);
-    if (!sl) return fail("no samples recorded: call smolmc_run_sampled first");
-    if (!(sl->flags & SMOLMC_SAMPLE_OBSERVABLES)) return fail("the observables were not recorded (flags bit 3)");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipEventSynchronize(sl->copy_done));
-    const size_t rows = (size_t)sl->n * h->R;
-    if (counts) host_copy(counts, sl->hst + sl->o_cnt, rows * (size_t)h->obs.K * 4);
-    if (pairs) host_copy(pairs, sl->hst + sl->o_pair, rows * h->obs.cells * 4);
-    return 0;
+    RowSources s = walker_rows(h);
+    s.counts = S.u_counts; s.amp = h->sfac.u_amp; s.inten = h->sfac.u_inten; s.conn = h->conn.u_stats;
+    return derive_and_offer(h, s, SMOLMC_SAMPLE_STATISTICS, 1, 1);
 }
 
 extern "C" int smolmc_eval_delta(smolmc_handle *h, const int32_t *occ, const int32_t *flips, int nstep,

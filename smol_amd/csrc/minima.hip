@@ -245,8 +245,6 @@ static int min_clear(smolmc_handle *h) {
     return 0;
 }
 
-static size_t min_up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" int smolmc_set_minima(smolmc_handle *h, const smolmc_minima *m) {
     if (!h) return fail("null handle");
     if (h->dist) return fail("minima: a distance handle keeps its own best states (smolmc_get_best)");
@@ -293,7 +291,7 @@ extern "C" int smolmc_set_minima(smolmc_handle *h, const smolmc_minima *m) {
     M.n_slots = (int)n_slots; M.n_axes = m->n_axes; M.n_weights = m->n_weights; M.K = K;
     for (int a = 0; a < m->n_axes; ++a) { M.bin[a] = m->axis_bin[a]; M.extent[a] = m->axis_extent[a]; }
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += min_up256(std::max<size_t>(bytes, 16)); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
     const size_t R = (size_t)h->R;
     const size_t o_value = take(n_slots * 8), o_H = take(n_slots * 8), o_feat = take(n_slots * F * 8), o_step = take(n_slots * 8),
                  o_sample = take(n_slots * 8), o_walker = take(n_slots * 4), o_counts = take(n_slots * K * 4),

@@ -1,4 +1,4 @@
-// Observables of recorded states (smolmc_set_observables, smolmc_eval_observables, SMOLMC_SAMPLE_OBSERVABLES; engine.hip):
+// Observables of recorded states (smolmc_set_observables, smolmc_eval_observables, SMOLMC_SAMPLE_OBSERVABLES):
 // kind counts and pair counts of occupancy rows, reduced on the device where the rows lie.  A translation unit of its own,
 // like pop_anneal.hip: a kernel added to engine.hip would move the descriptors of all of its kernels.
 //
@@ -155,5 +155,118 @@ extern "C" int smolmc_debug_obs_kernel_ms(smolmc_handle *h, float *ms) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipEventSynchronize(h->obs_ev1));
     HIPCHK(hipEventElapsedTime(ms, h->obs_ev0, h->obs_ev1));
+    return 0;
+}
+
+void smolmc_obs_free(SmolmcObs &O) {
+    if (O.d_kind_base) hipFree(O.d_kind_base);
+    if (O.d_shell_ptr) hipFree(O.d_shell_ptr);
+    if (O.d_bonds) hipFree(O.d_bonds);
+    O = SmolmcObs();
+}
+
+// ---- the C-ABI of the observables --------------------------------------------------------------------------------------
+extern "C" int smolmc_set_observables(smolmc_handle *h, const smolmc_observables *obs) {
+    if (!h) return fail("null handle");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(smolmc_ring_guard(h, SMOLMC_SAMPLE_OBSERVABLES, "smolmc_set_observables", "SMOLMC_SAMPLE_OBSERVABLES"));
+    SmolmcObs O;
+    if (h->minima.n_slots && h->minima.n_axes)
+        return fail("smolmc_set_observables while a minima record keyed by composition depends on the observables (call "
+                    "smolmc_set_minima(h, NULL) first)");
+    if (h->stats.n_keys && h->stats.n_count_cols)
+        return fail("smolmc_set_observables while a statistics record with count columns depends on the observables (call "
+                    "smolmc_set_statistics(h, NULL) first)");
+    if (obs) {
+        const int N = h->N, K = obs->n_kinds, S = obs->n_shells;
+        if (!obs->kind_base || S < 0 || (S > 0 && (!obs->shell_ptr || !obs->bonds))) return fail("observables: null argument");
+        if (K < 1 || K > 254) return fail("observables: n_kinds must be 1..254 (a kind is staged as one byte)");
+        const size_t cells = (size_t)S * K * K;
+        if (cells > SMOLMC_MAX_OBS_CELLS) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "observables: %d shells x %d x %d kinds = %zu cells, larger than SMOLMC_MAX_OBS_CELLS = %d", S, K, K,
+                     cells, SMOLMC_MAX_OBS_CELLS);
+            return fail(msg);
+        }
+        std::vector<int32_t> kb;
+        TRY(smolmc_kind_base_in(h, obs->kind_base, K, "observables", kb));
+        const int64_t nb = S ? obs->shell_ptr[S] : 0;
+        for (int sidx = 0; sidx < S; ++sidx)
+            if (obs->shell_ptr[0] != 0 || obs->shell_ptr[sidx] > obs->shell_ptr[sidx + 1])
+                return fail("observables: shell_ptr must be ascending from 0");
+        O.K = K; O.n_shells = S; O.cells = cells;
+        O.kind_base = kb;
+        O.pair_copies = smolmc_obs_pair_copies(cells);
+        O.lds = smolmc_obs_lds_bytes(h->Npad, K, cells, O.pair_copies);
+        if (O.lds > 64 * 1024) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "observables: a row of %d sites is too long to stage in LDS next to the histograms (%zu bytes, 65536 at most)",
+                     N, O.lds);
+            return fail(msg);
+        }
+        // (a row that fits LDS has fewer than 2^16 sites: a bond is one word)
+        std::vector<uint32_t> bw((size_t)nb);
+        for (int64_t b = 0; b < nb; ++b) {
+            const int32_t i = obs->bonds[2 * b], j = obs->bonds[2 * b + 1];
+            if (i < 0 || i >= N || j < 0 || j >= N) {
+                char msg[160];
+                snprintf(msg, sizeof msg, "observables: bond %lld = (%d, %d) out of range (%d sites)", (long long)b, (int)i, (int)j, N);
+                return fail(msg);
+            }
+            const uint32_t ei = (uint32_t)(h->relabelled ? h->new_of[i] : i), ej = (uint32_t)(h->relabelled ? h->new_of[j] : j);
+            bw[(size_t)b] = ei | (ej << 16);
+        }
+        hipError_t e = hipMalloc((void **)&O.d_kind_base, std::max<size_t>((size_t)N * 4, 16));
+        if (e == hipSuccess) e = hipMalloc((void **)&O.d_shell_ptr, ((size_t)S + 1) * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&O.d_bonds, std::max<size_t>((size_t)nb * 4, 16));
+        if (e == hipSuccess) e = hipMemcpy(O.d_kind_base, kb.data(), (size_t)N * 4, hipMemcpyHostToDevice);
+        const int64_t zero = 0;
+        if (e == hipSuccess) e = hipMemcpy(O.d_shell_ptr, S ? obs->shell_ptr : &zero, ((size_t)S + 1) * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && nb) e = hipMemcpy(O.d_bonds, bw.data(), (size_t)nb * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            smolmc_obs_free(O);
+            return fail(std::string("observables upload: ") + hipGetErrorString(e));
+        }
+    }
+    TRY(smolmc_ring_forget(h, SMOLMC_SAMPLE_OBSERVABLES));
+    smolmc_obs_free(h->obs);
+    h->obs = O;
+    return 0;
+}
+
+extern "C" int smolmc_observables_shape(smolmc_handle *h, int *n_kinds, int *n_shells) {
+    if (!h) return fail("null handle");
+    if (n_kinds) *n_kinds = h->obs.K;
+    if (n_shells) *n_shells = h->obs.n_shells;
+    return 0;
+}
+
+extern "C" int smolmc_eval_observables(smolmc_handle *h, const int32_t *occ, int nocc, int32_t *counts, int32_t *pairs) {
+    if (!h) return fail("null handle");
+    if (!h->obs.K) return fail("no observables set: call smolmc_set_observables first");
+    HIPCHK(hipSetDevice(h->device));
+    const uint8_t *d_occ8;
+    size_t rows;
+    TRY(smolmc_eval_rows(h, occ, nocc, h->obs.kind_base, h->obs.K, "observables", &d_occ8, &rows));
+    if (!rows) return 0;
+    const size_t nc = rows * h->obs.K, np = rows * h->obs.cells;
+    int32_t *d_out = nullptr;
+    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>((nc + np) * 4, 16)));
+    int rc = smolmc_obs_launch(h, d_occ8, rows, d_out, d_out + nc);
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (!rc && e == hipSuccess && counts) e = hipMemcpy(counts, d_out, nc * 4, hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess && pairs && np) e = hipMemcpy(pairs, d_out + nc, np * 4, hipMemcpyDeviceToHost);
+    hipFree(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(std::string("eval_observables: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int smolmc_get_sample_observables(smolmc_handle *h, int32_t *counts, int32_t *pairs) {
+    const SampleSlot *sl;
+    size_t rows;
+    TRY(smolmc_sample_block(h, SMOLMC_SAMPLE_OBSERVABLES, "the observables were not recorded (flags bit 3)", &sl, &rows));
+    if (counts) smolmc_host_copy(counts, sl->hst + sl->o_cnt, rows * (size_t)h->obs.K * 4);
+    if (pairs) smolmc_host_copy(pairs, sl->hst + sl->o_pair, rows * h->obs.cells * 4);
     return 0;
 }

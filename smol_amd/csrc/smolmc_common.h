@@ -748,16 +748,20 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
-// One slot of the sample ring: `n` samples x R walkers recorded by one smolmc_run_sampled call.  Every array is a
-// range of ONE device arena and of ONE pinned host arena with the same offsets (a single asynchronous copy moves it).
-struct SampleSlot {
-    unsigned char *d = nullptr, *hst = nullptr; // device arena, pinned host mirror
-    size_t cap = 0;                             // bytes allocated (grow-only)
-    size_t used = 0;                            // bytes of the recorded block
+// The columns of a recorded block as offsets into its slot's arenas (engine.hip, plan_block): a column the block does not
+// have is at 0, one that exists without its flag lies behind the slot's `used` bytes and is never downloaded.
+struct SampleColumns {
     size_t o_H = 0, o_feat = 0, o_acc = 0, o_occ = 0, o_bias = 0, o_wlm = 0, o_wlS = 0, o_wlh = 0, o_wlo = 0, o_wlf = 0;
     size_t o_cnt = 0, o_pair = 0;               // SMOLMC_SAMPLE_OBSERVABLES: kind counts [rows x K], pair counts [rows x cells]
     size_t o_amp = 0, o_inten = 0;              // SMOLMC_SAMPLE_STRUCTURE: amplitudes [rows x Q x K x 2] int64, intensities [rows x I]
     size_t o_conn = 0;                          // SMOLMC_SAMPLE_CONNECTIVITY: stats [rows x G x 24] int64
+};
+// One slot of the sample ring: `n` samples x R walkers recorded by one smolmc_run_sampled call.  Every array is a
+// range of ONE device arena and of ONE pinned host arena with the same offsets (a single asynchronous copy moves it).
+struct SampleSlot : SampleColumns {
+    unsigned char *d = nullptr, *hst = nullptr; // device arena, pinned host mirror
+    size_t cap = 0;                             // bytes allocated (grow-only)
+    size_t used = 0;                            // bytes of the recorded block
     long long n = 0;                            // samples in the block
     int flags = 0;                              // SMOLMC_SAMPLE_* the block was recorded with
     int state = 0;                              // 0 empty, 1 recorded and not yet delivered, 2 delivered
@@ -955,16 +959,16 @@ struct smolmc_handle {
     // population annealing (smolmc_anneal_resample / smolmc_resample, engine.hip): one device arena, allocated at the
     // first call, cut into the arrays of SmolmcPopScratch
     SmolmcPopScratch pop;
-    // kind and pair counts of occupancy rows (smolmc_set_observables, engine.hip; the kernel in observables.hip)
+    // kind and pair counts of occupancy rows (smolmc_set_observables; observables.hip)
     SmolmcObs obs;
     hipEvent_t obs_ev0 = nullptr, obs_ev1 = nullptr; // around the last launch of the observables kernel (created at the first)
     // the lowest recorded states (smolmc_set_minima; minima.hip)
     SmolmcMin minima;
     // running moments, blocking sums and a histogram of the samples (smolmc_set_statistics; statistics.hip)
     SmolmcStat stats;
-    // structure-factor amplitudes and intensities of occupancy rows (smolmc_set_structure, engine.hip; structure.hip)
+    // structure-factor amplitudes and intensities of occupancy rows (smolmc_set_structure; structure.hip)
     SmolmcStruct sfac;
-    // connected components and percolation of occupancy rows (smolmc_set_connectivity, engine.hip; connectivity.hip)
+    // connected components and percolation of occupancy rows (smolmc_set_connectivity; connectivity.hip)
     SmolmcConn conn;
     // device-side samples (smolmc_run_sampled): two ring slots, each a device arena + a pinned host mirror; the
     // download of a slot runs on its own stream while the next block's kernel fills the other slot (see engine.hip)
@@ -1044,6 +1048,30 @@ template <typename T> static int dev_alloc(smolmc_handle *h, size_t n, T **dst, 
         if (int rc_ = (x)) return rc_;                                                    \
     } while (0)
 
+// columns of an arena start at multiples of 256 bytes
+static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// engine.hip: what the host code of the specs that read occupancy rows (observables.hip, structure.hip, connectivity.hip)
+// shares.  `noun` starts the messages: "observables", "structure factors", "connectivity".
+// smolmc_set_*: refused while a block recorded with the spec's flag waits in the ring ...
+int smolmc_ring_guard(const smolmc_handle *h, int flag, const char *fn, const char *flag_name);
+// ... and before the new spec takes over: the kernels of queued blocks read the old tables, let them finish; delivered
+// blocks of the old shape are forgotten
+int smolmc_ring_forget(smolmc_handle *h, int flag);
+// kind_base of the caller in the engine's numbering (kb [N]; every code a site can hold must have a kind below K);
+// returns through n_counted, when given, the number of sites with a kind
+int smolmc_kind_base_in(const smolmc_handle *h, const int32_t *kind_base, int K, const char *noun, std::vector<int32_t> &kb,
+                        size_t *n_counted = nullptr);
+// smolmc_eval_*: the device rows to evaluate and their number -- the caller's occupancies (translated, their kinds checked
+// against kind_base and K, uploaded; nocc <= 0: no rows) or, with occ == NULL, the walkers' own states
+int smolmc_eval_rows(smolmc_handle *h, const int32_t *occ, int nocc, const std::vector<int32_t> &kind_base, int K, const char *noun,
+                     const uint8_t **d_occ8, size_t *rows);
+// smolmc_get_sample_*: the block the next fetch delivers, downloaded, and its number of rows; refused with `not_recorded`
+// when the block was recorded without the flag
+int smolmc_sample_block(smolmc_handle *h, int flag, const char *not_recorded, const SampleSlot **sl, size_t *rows);
+// pinned mirror -> the caller's array
+void smolmc_host_copy(void *dst, const void *src, size_t bytes);
+
 
 // launchers defined in the per-NSLOT translation units
 
@@ -1111,6 +1139,7 @@ size_t smolmc_conn_lds_bytes(int N, int Npad);
 void smolmc_conn_free(SmolmcConn &S);
 size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies);
 int smolmc_obs_pair_copies(size_t cells);
+void smolmc_obs_free(SmolmcObs &O);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);
 int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_4(smolmc_handle *h, const KParams &kp, int replay);

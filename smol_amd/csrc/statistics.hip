@@ -208,8 +208,6 @@ void smolmc_stat_free(smolmc_handle *h) {
     S = SmolmcStat();
 }
 
-static size_t stat_up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *s) {
     if (!h) return fail("null handle");
     if (h->dist) return fail("statistics: a distance handle samples no thermodynamic ensemble");
@@ -292,7 +290,7 @@ extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *
     S.CS = CS; S.n_conn_cols = n_conn_cols;
     S.hist_min = B ? s->hist_min : 0.0; S.hist_bin = B ? s->hist_bin : 1.0;
     size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += stat_up256(std::max<size_t>(bytes, 16)); return o; };
+    auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
     const size_t o_n = take(nk * 8), o_under = take(nk * 8), o_over = take(nk * 8), o_shift = take(nk * C * 8),
                  o_s1 = take(nk * C * 8), o_s2 = take(nk * P * 8), o_has = take(nk * C * 8), o_pend = take(nk * L * C * 8),
                  o_b2 = take(nk * L * C * 8), o_nb = take(nk * L * 8), o_hist = take(nk * B * 8);

@@ -1,4 +1,4 @@
-// Structure factors of recorded states (smolmc_set_structure, smolmc_eval_structure, SMOLMC_SAMPLE_STRUCTURE; engine.hip):
+// Structure factors of recorded states (smolmc_set_structure, smolmc_eval_structure, SMOLMC_SAMPLE_STRUCTURE):
 // fixed-point amplitudes per wave vector ("point") and kind, and the intensities made of them, reduced on the device
 // where the occupancy rows lie.  A translation unit of its own, like observables.hip.
 //
@@ -263,5 +263,164 @@ extern "C" int smolmc_debug_structure_kernel_ms(smolmc_handle *h, float *ms) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipEventSynchronize(S.ev[1]));
     HIPCHK(hipEventElapsedTime(ms, S.ev[0], S.ev[1]));
+    return 0;
+}
+
+// ---- the C-ABI of the structure-factor spec -------------------------------------------------------------------------------
+extern "C" int smolmc_set_structure(smolmc_handle *h, const smolmc_structure *sp) {
+    if (!h) return fail("null handle");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(smolmc_ring_guard(h, SMOLMC_SAMPLE_STRUCTURE, "smolmc_set_structure", "SMOLMC_SAMPLE_STRUCTURE"));
+    if (h->stats.n_keys && h->stats.n_inten_cols)
+        return fail("smolmc_set_structure while a statistics record with intensity columns depends on the spec (call "
+                    "smolmc_set_statistics(h, NULL) first)");
+    SmolmcStruct S;
+    if (sp) {
+        const int N = h->N, K = sp->n_kinds, Q = sp->n_points, M = sp->n_phases, I = sp->n_intensities;
+        char msg[256];
+        if (!sp->kind_base || !sp->phase || !sp->table || (I > 0 && (!sp->intensity || !sp->intensity_scale)))
+            return fail("structure factors: null argument");
+        if (K < 1 || K > 254) return fail("structure factors: n_kinds must be 1..254 (a kind is staged as one byte)");
+        if (Q < 1 || Q > SMOLMC_MAX_STRUCT_POINTS) {
+            snprintf(msg, sizeof msg, "structure factors: n_points must be 1..%d, got %d", SMOLMC_MAX_STRUCT_POINTS, Q);
+            return fail(msg);
+        }
+        if (M < 1 || M > SMOLMC_MAX_STRUCT_PHASES) {
+            snprintf(msg, sizeof msg, "structure factors: n_phases must be 1..%d, got %d", SMOLMC_MAX_STRUCT_PHASES, M);
+            return fail(msg);
+        }
+        if ((size_t)K * M > SMOLMC_MAX_STRUCT_CELLS) {
+            snprintf(msg, sizeof msg, "structure factors: %d kinds x %d phase classes = %zu cells, larger than SMOLMC_MAX_STRUCT_CELLS = %d",
+                     K, M, (size_t)K * M, SMOLMC_MAX_STRUCT_CELLS);
+            return fail(msg);
+        }
+        if (I < 0 || I > SMOLMC_MAX_STRUCT_INTENSITIES) {
+            snprintf(msg, sizeof msg, "structure factors: n_intensities must be 0..%d, got %d", SMOLMC_MAX_STRUCT_INTENSITIES, I);
+            return fail(msg);
+        }
+        std::vector<int32_t> kb;
+        size_t n_counted = 0;
+        TRY(smolmc_kind_base_in(h, sp->kind_base, K, "structure factors", kb, &n_counted));
+        std::vector<uint16_t> ph((size_t)Q * N);
+        for (int q = 0; q < Q; ++q)
+            for (int p = 0; p < N; ++p) {
+                const uint16_t v = sp->phase[(size_t)q * N + p];
+                if (v >= M) {
+                    snprintf(msg, sizeof msg, "structure factors: phase[%d][%d] = %d, n_phases is %d: phase out of range", q, p, (int)v, M);
+                    return fail(msg);
+                }
+                ph[(size_t)q * N + (h->relabelled ? h->new_of[p] : p)] = v;
+            }
+        unsigned long long peak = 0;
+        for (size_t i = 0; i < (size_t)Q * M * 2; ++i) {
+            const int64_t v = sp->table[i];
+            const unsigned long long a = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
+            peak = std::max(peak, a);
+        }
+        if (n_counted && peak >= (1ull << 62) / n_counted + ((1ull << 62) % n_counted != 0)) {
+            snprintf(msg, sizeof msg, "structure factors: %zu counted sites x max|table| = %llu reaches 2^62: an amplitude could overflow",
+                     n_counted, peak);
+            return fail(msg);
+        }
+        for (int i = 0; i < I; ++i) {
+            const int32_t q = sp->intensity[3 * i], a = sp->intensity[3 * i + 1], b = sp->intensity[3 * i + 2];
+            if (q < 0 || q >= Q) {
+                snprintf(msg, sizeof msg, "structure factors: intensity %d names point %d, n_points is %d: point out of range", i, (int)q, Q);
+                return fail(msg);
+            }
+            if (a < 0 || a >= K || b < 0 || b >= K) {
+                snprintf(msg, sizeof msg, "structure factors: intensity %d names kinds (%d, %d), n_kinds is %d: kind out of range", i, (int)a,
+                         (int)b, K);
+                return fail(msg);
+            }
+            if (!std::isfinite(sp->intensity_scale[i])) {
+                snprintf(msg, sizeof msg, "structure factors: intensity_scale[%d] is not finite", i);
+                return fail(msg);
+            }
+        }
+        S.K = K; S.Q = Q; S.M = M; S.I = I;
+        S.W = (N + 63) / 64;
+        if (!smolmc_sfac_plan(N, h->Npad, K, M, Q, &S.mask, &S.copies, &S.chunk, &S.lds)) {
+            snprintf(msg, sizeof msg, "structure factors: a row of %d sites is too long to stage in LDS next to the %zu counters of a point "
+                     "(%zu bytes, 65536 at most)", N, (size_t)K * M, (size_t)h->Npad + (size_t)K * M * 4);
+            return fail(msg);
+        }
+        S.kind_base = kb;
+        // one arena: the spec's arrays, then the scratch of smolmc_update_statistics
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
+        const size_t R = (size_t)h->R;
+        const size_t o_kb = take((size_t)N * 4), o_ph = take((size_t)Q * N * 2), o_tb = take((size_t)Q * M * 16),
+                     o_it = take((size_t)I * 12), o_sc = take((size_t)I * 8), o_ua = take(R * Q * K * 16), o_ui = take(R * I * 8);
+        // the mask kernel's table: for every point and class the sites of the class as bits, words of one (word, class)
+        // side by side over the points
+        std::vector<unsigned long long> masks;
+        if (S.mask) {
+            masks.assign((size_t)S.W * M * Q, 0ull);
+            for (int q = 0; q < Q; ++q)
+                for (int s = 0; s < N; ++s)
+                    masks[((size_t)(s >> 6) * M + ph[(size_t)q * N + s]) * Q + q] |= 1ull << (s & 63);
+        }
+        const size_t o_mk = take(masks.size() * 8);
+        hipError_t e = hipMalloc((void **)&S.arena, at);
+        if (e != hipSuccess) return fail(std::string("structure factors: hipMalloc: ") + hipGetErrorString(e));
+        unsigned char *d = S.arena;
+        S.d_kind_base = (int32_t *)(d + o_kb); S.d_phase = (uint16_t *)(d + o_ph); S.d_table = (long long *)(d + o_tb);
+        S.d_intensity = (int32_t *)(d + o_it); S.d_scale = (double *)(d + o_sc);
+        S.u_amp = (long long *)(d + o_ua); S.u_inten = (double *)(d + o_ui);
+        S.d_masks = (unsigned long long *)(d + o_mk);
+        e = hipMemcpy(S.d_kind_base, kb.data(), (size_t)N * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(S.d_phase, ph.data(), (size_t)Q * N * 2, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(S.d_table, sp->table, (size_t)Q * M * 16, hipMemcpyHostToDevice);
+        if (e == hipSuccess && I) e = hipMemcpy(S.d_intensity, sp->intensity, (size_t)I * 12, hipMemcpyHostToDevice);
+        if (e == hipSuccess && I) e = hipMemcpy(S.d_scale, sp->intensity_scale, (size_t)I * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !masks.empty()) e = hipMemcpy(S.d_masks, masks.data(), masks.size() * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            smolmc_sfac_free(S);
+            return fail(std::string("structure factors upload: ") + hipGetErrorString(e));
+        }
+    }
+    TRY(smolmc_ring_forget(h, SMOLMC_SAMPLE_STRUCTURE));
+    smolmc_sfac_free(h->sfac);
+    h->sfac = S;
+    return 0;
+}
+
+extern "C" int smolmc_structure_shape(smolmc_handle *h, int *n_points, int *n_kinds, int *n_intensities) {
+    if (!h) return fail("null handle");
+    if (n_points) *n_points = h->sfac.Q;
+    if (n_kinds) *n_kinds = h->sfac.Q ? h->sfac.K : 0;
+    if (n_intensities) *n_intensities = h->sfac.I;
+    return 0;
+}
+
+extern "C" int smolmc_eval_structure(smolmc_handle *h, const int32_t *occ, int nocc, int64_t *amp, double *inten) {
+    if (!h) return fail("null handle");
+    const SmolmcStruct &S = h->sfac;
+    if (!S.Q) return fail("no structure-factor spec set: call smolmc_set_structure first");
+    HIPCHK(hipSetDevice(h->device));
+    const uint8_t *d_occ8;
+    size_t rows;
+    TRY(smolmc_eval_rows(h, occ, nocc, S.kind_base, S.K, "structure factors", &d_occ8, &rows));
+    if (!rows) return 0;
+    const size_t na = rows * S.Q * S.K * 2, ni = rows * S.I;
+    unsigned char *d_out = nullptr;
+    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>((na + ni) * 8, 16)));
+    int rc = smolmc_sfac_launch(h, d_occ8, rows, (long long *)d_out, (double *)(d_out + na * 8));
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (!rc && e == hipSuccess && amp) e = hipMemcpy(amp, d_out, na * 8, hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess && inten && ni) e = hipMemcpy(inten, d_out + na * 8, ni * 8, hipMemcpyDeviceToHost);
+    hipFree(d_out);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(std::string("eval_structure: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int smolmc_get_sample_structure(smolmc_handle *h, int64_t *amp, double *inten) {
+    const SampleSlot *sl;
+    size_t rows;
+    TRY(smolmc_sample_block(h, SMOLMC_SAMPLE_STRUCTURE, "the structure factors were not recorded (flags bit 6)", &sl, &rows));
+    if (amp) smolmc_host_copy(amp, sl->hst + sl->o_amp, rows * (size_t)h->sfac.Q * h->sfac.K * 16);
+    if (inten) smolmc_host_copy(inten, sl->hst + sl->o_inten, rows * (size_t)h->sfac.I * 8);
     return 0;
 }

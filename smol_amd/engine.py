@@ -176,6 +176,12 @@ def species_counts(tables, occupancies, width=None):
     return out
 
 
+# the keywords of ``run_sampled`` / ``run_sampled_async`` and the SMOLMC_SAMPLE_* flag each one sets
+SAMPLE_FLAGS = (("occupancy", capi.SAMPLE_OCCUPANCY), ("bias", capi.SAMPLE_BIAS), ("wl", capi.SAMPLE_WL),
+                ("observables", capi.SAMPLE_OBSERVABLES), ("minima", capi.SAMPLE_MINIMA), ("statistics", capi.SAMPLE_STATISTICS),
+                ("structure", capi.SAMPLE_STRUCTURE), ("connectivity", capi.SAMPLE_CONNECTIVITY))
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -509,19 +515,33 @@ class Engine:
     def sync(self):
         self._chk(self._lib.smolmc_sync(self._h))
 
+    def _set_spec(self, fn, spec, defined_on=None, *shape):
+        """The call every ``set_*`` makes: ``fn(handle, struct of spec)``, or ``fn(handle, NULL)`` for None.  A spec that
+        names its sites (``defined_on``: the words of the message) must have the handle's number; ``shape``: what the
+        spec's ``c_struct`` takes."""
+        if spec is None:
+            self._chk(fn(self._h, None))
+            return
+        if defined_on is not None and spec.num_sites != self.N:
+            raise ValueError(f"{defined_on} defined on {spec.num_sites} sites, the handle has {self.N}")
+        struct, keep = spec.c_struct(*shape)
+        self._chk(fn(self._h, C.byref(struct)))
+        del keep
+
+    def _kernel_ms(self, hook, n=1):
+        """The ``n`` floats of a ``smolmc_debug_*_kernel_ms`` hook of the library: one as a float, several as a list."""
+        fn = getattr(self._lib, hook)
+        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
+        ms = (C.c_float * n)()
+        self._chk(fn(self._h, ms))
+        return float(ms[0]) if n == 1 else [float(x) for x in ms]
+
     # ---- observables: kind and pair counts on the device ----------------------------------
     def set_observables(self, obs):
         """The observables of this handle (smolmc_set_observables): an ``observables.Observables`` in the caller's site
         numbering, or None to remove them.  The engine copies and uploads; it refuses, naming the reason, a bond out
         of range, a kind beyond ``n_kinds``, more cells than ``capi.MAX_OBS_CELLS`` and a row too long for LDS."""
-        if obs is None:
-            self._chk(self._lib.smolmc_set_observables(self._h, None))
-        else:
-            if obs.num_sites != self.N:
-                raise ValueError(f"the observables are defined on {obs.num_sites} sites, the handle has {self.N}")
-            struct, keep = obs.c_struct()
-            self._chk(self._lib.smolmc_set_observables(self._h, C.byref(struct)))
-            del keep
+        self._set_spec(self._lib.smolmc_set_observables, obs, "the observables are")
 
     def observables_shape(self):
         """(n_kinds, n_shells) in force, (0, 0) when none are set (smolmc_observables_shape)."""
@@ -551,23 +571,14 @@ class Engine:
     def observables_kernel_ms(self):
         """Device time of the last launch of the observables kernel in ms (HIP events; a measuring hook of the library,
         not part of the C-ABI)."""
-        fn = self._lib.smolmc_debug_obs_kernel_ms
-        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
-        ms = C.c_float()
-        self._chk(fn(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms("smolmc_debug_obs_kernel_ms")
 
     # ---- minima: the lowest recorded states, kept on the device ----------------------------
     def set_minima(self, spec):
         """The minima record of this handle (smolmc_set_minima): a ``minima.Minima``, or None to remove it.  A new spec
         starts an empty record.  The record lives as long as the handle: ``set_state`` and ``discard_samples`` leave it
         alone."""
-        if spec is None:
-            self._chk(self._lib.smolmc_set_minima(self._h, None))
-        else:
-            struct, keep = spec.c_struct()
-            self._chk(self._lib.smolmc_set_minima(self._h, C.byref(struct)))
-            del keep
+        self._set_spec(self._lib.smolmc_set_minima, spec)
         self.minima_spec = spec
 
     def minima_shape(self):
@@ -607,11 +618,7 @@ class Engine:
     def minima_kernel_ms(self):
         """Device times of the three passes of the last minima reduction in ms (HIP events; a measuring hook of the
         library, not part of the C-ABI)."""
-        fn = self._lib.smolmc_debug_minima_kernel_ms
-        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
-        ms = (C.c_float * 3)()
-        self._chk(fn(self._h, ms))
-        return [float(x) for x in ms]
+        return self._kernel_ms("smolmc_debug_minima_kernel_ms", 3)
 
     # ---- structure factors: fixed-point amplitudes and intensities on the device -------------
     def set_structure_factor(self, sf):
@@ -619,14 +626,7 @@ class Engine:
         site numbering, or None to remove it.  The engine copies and uploads; it refuses, naming the reason, a phase or
         kind out of range, sizes beyond the ``capi.MAX_STRUCT_*`` limits, a table large enough to overflow an amplitude,
         and a row too long for LDS."""
-        if sf is None:
-            self._chk(self._lib.smolmc_set_structure(self._h, None))
-        else:
-            if sf.num_sites != self.N:
-                raise ValueError(f"the structure factors are defined on {sf.num_sites} sites, the handle has {self.N}")
-            struct, keep = sf.c_struct()
-            self._chk(self._lib.smolmc_set_structure(self._h, C.byref(struct)))
-            del keep
+        self._set_spec(self._lib.smolmc_set_structure, sf, "the structure factors are")
 
     def structure_shape(self):
         """(n_points, n_kinds, n_intensities) in force, zeros when no spec is set (smolmc_structure_shape)."""
@@ -656,25 +656,14 @@ class Engine:
     def structure_kernel_ms(self):
         """Device time of the last launch of the structure kernel in ms (HIP events; a measuring hook of the library,
         not part of the C-ABI)."""
-        fn = self._lib.smolmc_debug_structure_kernel_ms
-        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
-        ms = C.c_float()
-        self._chk(fn(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms("smolmc_debug_structure_kernel_ms")
 
     # ---- connectivity: connected components and percolation on the device --------------------
     def set_connectivity(self, spec):
         """The connectivity spec of this handle (smolmc_set_connectivity): a ``connectivity.Connectivity`` in the caller's
         site numbering, or None to remove it.  The engine copies and uploads; it refuses, naming the reason, a bond, kind
         or image out of range, more than ``capi.MAX_CONN_GRAPHS`` graphs and a row too long for the LDS plan."""
-        if spec is None:
-            self._chk(self._lib.smolmc_set_connectivity(self._h, None))
-        else:
-            if spec.num_sites != self.N:
-                raise ValueError(f"the connectivity spec is defined on {spec.num_sites} sites, the handle has {self.N}")
-            struct, keep = spec.c_struct()
-            self._chk(self._lib.smolmc_set_connectivity(self._h, C.byref(struct)))
-            del keep
+        self._set_spec(self._lib.smolmc_set_connectivity, spec, "the connectivity spec is")
 
     def connectivity_shape(self):
         """(n_graphs, n_kinds) in force, zeros when no spec is set (smolmc_connectivity_shape)."""
@@ -705,11 +694,7 @@ class Engine:
     def connectivity_kernel_ms(self):
         """Device time of the last launch of the connectivity kernel in ms (HIP events; a measuring hook of the library,
         not part of the C-ABI)."""
-        fn = self._lib.smolmc_debug_connectivity_kernel_ms
-        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
-        ms = C.c_float()
-        self._chk(fn(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms("smolmc_debug_connectivity_kernel_ms")
 
     def connectivity_passes(self):
         """(most passes a (row, graph) took, their sum over all of them) in the last launch of the connectivity kernel (a
@@ -725,12 +710,8 @@ class Engine:
         """The statistics record of this handle (smolmc_set_statistics): a ``statistics.Statistics``, or None to remove
         it.  A new spec starts an empty record.  The record lives as long as the handle: ``set_state`` and
         ``discard_samples`` leave it alone."""
-        if spec is None:
-            self._chk(self._lib.smolmc_set_statistics(self._h, None))
-        else:
-            struct, keep = spec.c_struct(self.F, self.observables_shape()[0], self.structure_shape()[2], self.connectivity_shape()[0])
-            self._chk(self._lib.smolmc_set_statistics(self._h, C.byref(struct)))
-            del keep
+        shape = () if spec is None else (self.F, self.observables_shape()[0], self.structure_shape()[2], self.connectivity_shape()[0])
+        self._set_spec(self._lib.smolmc_set_statistics, spec, None, *shape)
         self.statistics_spec = spec
 
     def statistics_shape(self):
@@ -767,11 +748,7 @@ class Engine:
     def statistics_kernel_ms(self):
         """Device time of the last statistics reduction in ms (HIP events; a measuring hook of the library, not part of
         the C-ABI)."""
-        fn = self._lib.smolmc_debug_statistics_kernel_ms
-        fn.restype, fn.argtypes = C.c_int, [_HP, C.POINTER(C.c_float)]
-        ms = C.c_float()
-        self._chk(fn(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms("smolmc_debug_statistics_kernel_ms")
 
     def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False,
                     minima=False, statistics=False, structure=False, connectivity=False):
@@ -796,10 +773,9 @@ class Engine:
         stays on the device.  ``statistics``: likewise every row is offered to the record of ``set_statistics``.
         ``structure``: the amplitudes and intensities of ``set_structure_factor`` for every row, like ``observables``.
         ``connectivity``: the stats of ``set_connectivity`` for every row, likewise."""
-        flags = ((capi.SAMPLE_OCCUPANCY if occupancy else 0) | (capi.SAMPLE_BIAS if bias else 0) |
-                 (capi.SAMPLE_WL if wl else 0) | (capi.SAMPLE_OBSERVABLES if observables else 0) |
-                 (capi.SAMPLE_MINIMA if minima else 0) | (capi.SAMPLE_STATISTICS if statistics else 0) |
-                 (capi.SAMPLE_STRUCTURE if structure else 0) | (capi.SAMPLE_CONNECTIVITY if connectivity else 0))
+        asked = dict(occupancy=occupancy, bias=bias, wl=wl, observables=observables, minima=minima, statistics=statistics,
+                     structure=structure, connectivity=connectivity)
+        flags = sum(flag for keyword, flag in SAMPLE_FLAGS if asked[keyword])
         self._chk(self._lib.smolmc_run_sampled(self._h, int(nsamples), int(thin_by), flags))
 
     def pending_samples(self):
