@@ -1897,7 +1897,9 @@ __global__ void __launch_bounds__(512) mc_table_kernel(const LeanParams P) { // 
             }
             {
                 // rows and Ewald cross terms as in fetch_rows, the sites being scalars here
-                const uint32_t s0 = a01 & 0xffffu, s1 = a01 >> 16, s2 = nfl > 2 ? a23 & 0xffffu : s0, s3 = nfl > 3 ? a23 >> 16 : s0;
+                // (a table direction of ONE flip leaves slot 1 of the batch empty, 0xffff: its row lies 65535 sites past the
+                // index rows -- an unused load, but a read outside the allocation)
+                const uint32_t s0 = a01 & 0xffffu, s1 = nfl > 1 ? a01 >> 16 : s0, s2 = nfl > 2 ? a23 & 0xffffu : s0, s3 = nfl > 3 ? a23 >> 16 : s0;
                 rows[0] = load_row<NW>(idx_rs, lane_voff, s0 * SITE_BYTES);
                 rows[1] = load_row<NW>(idx_rs, lane_voff, s1 * SITE_BYTES);
                 rows[2] = load_row<NW>(idx_rs, lane_voff, s2 * SITE_BYTES);

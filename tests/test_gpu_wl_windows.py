@@ -10,6 +10,7 @@ import pytest
 from smol_amd import capi, parallel
 from tests import wl_windows_case as wc
 from tests.cases import load_case, tables_for
+from tests.wl_window_oracle import enthalpies as _enthalpies, one_walker_oracle as _oracle, same as _same, top as _top
 
 pytestmark = pytest.mark.gpu
 INT = capi.FEATURES_INTERACTIONS
@@ -29,47 +30,6 @@ def _engine(tab, cfg):
     from smol_amd.engine import Engine
 
     return Engine(tab, cfg)
-
-
-def _top(vmin, L, bin_size):
-    """vmin + L bins, an ulp lower where rounding would make the engine's ceil rule count L + 1."""
-    vmax = vmin + L * bin_size
-    while int(np.ceil((vmax - vmin) / bin_size)) > L:
-        vmax = np.nextafter(vmax, -np.inf)
-    assert int(np.ceil((vmax - vmin) / bin_size)) == L
-    return vmax
-
-
-def _enthalpies(tab, occ):
-    from oracle import oracle as orc
-
-    ev = orc.OracleEvaluator(tab)
-    nat = ev.natural_parameters()
-    return np.array([ev.feature_vector(o) @ nat for o in occ])
-
-
-def _oracle(tab, occ, seed, vmin, vmax, **kw):
-    """An unmodified one-walker oracle with the window [vmin, vmax)."""
-    from oracle import oracle as orc
-
-    o = orc.OracleMC(tab, capi.make_config(1, capi.KERNEL_WANGLANDAU, min_enthalpy=float(vmin), max_enthalpy=float(vmax), **kw))
-    o.set_state(np.asarray(occ).reshape(1, -1), np.array([seed], dtype=np.uint64), 0.0)
-    return o
-
-
-def _same(eng_state, eng_wl, walker, estimator, ora):
-    """Walker `walker` of the engine, which updates estimator `estimator`, against a one-walker oracle, as in
-    test_wang_landau_bin_pretest_is_decision_neutral."""
-    b, y = ora.get_state(), ora.get_wl()
-    assert np.array_equal(eng_state["occupancy"][walker], b["occupancy"][0])
-    assert eng_state["n_accepted"][walker] == b["n_accepted"][0] and eng_state["n_steps"][walker] == b["n_steps"][0]
-    np.testing.assert_allclose(eng_state["enthalpy"][walker], b["enthalpy"][0], rtol=1e-10, atol=1e-9)
-    np.testing.assert_allclose(eng_state["features"][walker], b["features"][0], rtol=1e-10, atol=1e-8)
-    np.testing.assert_allclose(eng_wl["entropy"][estimator], y["entropy"][0], rtol=0, atol=0)
-    assert np.array_equal(eng_wl["histogram"][estimator], y["histogram"][0])
-    assert np.array_equal(eng_wl["occurrences"][estimator], y["occurrences"][0])
-    np.testing.assert_allclose(eng_wl["mean_features"][estimator], y["mean_features"][0], rtol=1e-10, atol=1e-9)
-    np.testing.assert_allclose(eng_wl["mod_factor"][estimator], y["mod_factor"][0])
 
 
 def _rand_occ(sc, rng, R):
