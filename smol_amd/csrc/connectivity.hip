@@ -459,15 +459,13 @@ extern "C" int smolmc_eval_connectivity(smolmc_handle *h, const int32_t *occ, in
     TRY(smolmc_eval_rows(h, occ, nocc, S.kind_base, S.K, "connectivity", &d_occ8, &rows));
     if (!rows) return 0;
     const size_t ns = rows * S.G * SMOLMC_CONN_STATS, nl = labels ? rows * S.G * h->N : 0;
-    unsigned char *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>(ns * 8 + nl * 4, 16)));
-    int rc = smolmc_conn_launch(h, d_occ8, rows, (long long *)d_out, labels ? (int32_t *)(d_out + ns * 8) : nullptr);
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (!rc && e == hipSuccess && stats) e = hipMemcpy(stats, d_out, ns * 8, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && labels) e = hipMemcpy(labels, d_out + ns * 8, nl * 4, hipMemcpyDeviceToHost);
-    hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("eval_connectivity: ") + hipGetErrorString(e));
+    DevScratch out;
+    TRY(out.alloc(std::max<size_t>(ns * 8 + nl * 4, 16)));
+    unsigned char *d_out = out.as<unsigned char>();
+    TRY(smolmc_conn_launch(h, d_occ8, rows, (long long *)d_out, labels ? (int32_t *)(d_out + ns * 8) : nullptr));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (stats) HIPCHK(hipMemcpy(stats, d_out, ns * 8, hipMemcpyDeviceToHost));
+    if (labels) HIPCHK(hipMemcpy(labels, d_out + ns * 8, nl * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -124,30 +124,14 @@ int smolmc_dist_replay(smolmc_handle *h, int64_t nsteps, const int32_t *steps, c
         for (size_t i = 0; i < n; ++i)
             if (!std::isnan(log_priori[i]) && log_priori[i] != 0.0)
                 return fail("a distance handle takes no a-priori factor (Flip / Swap: 0, mcusher.py:118-134)");
-    int *d_steps = nullptr;
-    double *d_u = nullptr, *d_H = nullptr;
-    uint8_t *d_acc = nullptr;
-    hipError_t e = hipMalloc((void **)&d_steps, n * SMOLMC_STEP_ROW * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_u, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_H, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_acc, n);
-    if (e == hipSuccess) e = hipMemcpy(d_steps, steps, n * SMOLMC_STEP_ROW * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_u, uniforms, n * 8, hipMemcpyHostToDevice);
-    int rc = 0;
-    if (e == hipSuccess) {
-        SampleBufs none;
-        memset(&none, 0, sizeof(none));
-        rc = dist_launch(h, nsteps, none, 0, d_steps, d_u, d_acc, d_H);
-    }
-    if (e == hipSuccess && !rc) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess && !rc && accepted_out) e = hipMemcpy(accepted_out, d_acc, n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !rc && enthalpy_out) e = hipMemcpy(enthalpy_out, d_H, n * 8, hipMemcpyDeviceToHost);
-    hipFree(d_steps);
-    hipFree(d_u);
-    hipFree(d_H);
-    hipFree(d_acc);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("replay: ") + hipGetErrorString(e));
+    ReplayStage st; // (wide rows; no a-priori factors, no error word)
+    TRY(st.upload(n, steps, uniforms, false, false, nullptr));
+    SampleBufs none;
+    memset(&none, 0, sizeof(none));
+    TRY(dist_launch(h, nsteps, none, 0, st.steps.as<int>(), st.u.as<double>(), st.acc.as<uint8_t>(), st.H.as<double>()));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, st.acc.p, n, hipMemcpyDeviceToHost));
+    if (enthalpy_out) HIPCHK(hipMemcpy(enthalpy_out, st.H.p, n * 8, hipMemcpyDeviceToHost));
     if (log_priori_out) std::fill(log_priori_out, log_priori_out + n, 0.0);
     return 0;
 }

@@ -2500,18 +2500,14 @@ static int upload_occ(smolmc_handle *h, const int32_t *occ, size_t nocc, uint8_t
                      h->relabelled ? (size_t)h->old_of[s] : s, (int)lim[s]); // (the site in the caller's numbering)
             return fail(msg);
         }
-    int *d32 = nullptr;
-    HIPCHK(hipMalloc((void **)&d32, std::max<size_t>(n32 * 4, 16)));
-    hipError_t e = hipMemcpyAsync(d32, occ, n32 * 4, hipMemcpyHostToDevice, h->stream);
+    DevScratch d32;
+    TRY(d32.alloc(std::max<size_t>(n32 * 4, 16)));
+    HIPCHK(hipMemcpyAsync(d32.p, occ, n32 * 4, hipMemcpyHostToDevice, h->stream));
     const size_t total = nocc * h->Npad;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pack_occ_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
-                           d32, d_occ8, h->N, h->Npad, total);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d32);
-    if (e != hipSuccess) return fail(std::string("occupancy upload: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(pack_occ_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,
+                       d32.as<int>(), d_occ8, h->N, h->Npad, total);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
 }
 
@@ -2817,6 +2813,141 @@ extern "C" int smolmc_exchange_wl(smolmc_handle *h, int npairs, const int32_t *p
     return stats ? pair_exchange_stats(h, npairs, st.acc, stats) : 0;
 }
 
+// ---- smolmc_set_state in stages (the first one is shared with smolmc_set_temperature) --------------------------------
+// the temperatures of the call in force: the state points named after their walkers, the inverse temperatures uploaded
+static int apply_temperatures(smolmc_handle *h, const double *temperature) {
+    std::vector<double> beta;
+    set_betas(h, temperature, beta);
+    TRY(grid_rebase(h));
+    grid_name_temperatures(h, temperature);
+    HIPCHK(hipMemcpy(h->d_beta, beta.data(), (size_t)h->R * 8, hipMemcpyHostToDevice));
+    h->order_dirty = true;
+    return 0;
+}
+
+// seeds and step counters start over under reset_aux; the accepted flag always does
+static int reset_counters(smolmc_handle *h, const uint64_t *seeds, int reset_aux) {
+    KParams &kp = h->kp;
+    const size_t R = h->R;
+    if (reset_aux) {
+        std::vector<uint64_t> sd(R);
+        for (size_t r = 0; r < R; ++r) sd[r] = seeds ? seeds[r] : (uint64_t)r;
+        HIPCHK(hipMemcpy((void *)kp.seeds, sd.data(), R * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(kp.nsteps, 0, R * 8, h->stream));
+        HIPCHK(hipMemsetAsync(kp.nacc, 0, R * 8, h->stream));
+    }
+    HIPCHK(hipMemsetAsync(kp.last_acc, 1, R, h->stream));
+    return 0;
+}
+
+// MCBias.compute_bias of every initial occupancy (kernel/base.py:362-363), on the host: the occupancies are host
+// arrays here and this runs once per set_state.  occ [R][N] in the engine's numbering -> b0 [R], the bias, and
+// q0 [R][SMOLMC_MAX_BIAS_ROWS], the running sums of the hyperplane terms
+static void initial_bias(const smolmc_handle *h, const int32_t *occ, std::vector<double> &b0, std::vector<double> &q0) {
+    const KParams &kp = h->kp;
+    const size_t R = h->R;
+    const int N = h->N, W = kp.bias_W;
+    b0.assign(R, 0.0);
+    q0.assign(R * SMOLMC_MAX_BIAS_ROWS, 0.0);
+    for (size_t r = 0; r < R; ++r) {
+        const int32_t *o = occ + r * (size_t)N;
+        if (kp.bias_type == SMOLMC_BIAS_FUGACITY) {
+            double acc = 0.0;
+            for (int s = 0; s < N; ++s) acc += log(h->bias_host[(size_t)s * W + o[s]]); // bias.py:174-186
+            b0[r] = acc;
+        } else {
+            // SquareChargeBias (bias.py:264-277) = one hyperplane with intercept 0;
+            // SquareHyperplaneBias (bias.py:352-366): -penalty * sum_r (A_r . n - b_r)^2
+            double sq = 0.0;
+            for (int k = 0; k < kp.bias_rows; ++k) {
+                double acc = 0.0;
+                const double *tab = h->bias_host.data() + (size_t)k * kp.bias_row_stride;
+                for (int s = 0; s < N; ++s) acc += tab[(size_t)s * W + o[s]];
+                acc -= h->bias_icpt[k];
+                q0[r * SMOLMC_MAX_BIAS_ROWS + k] = acc;
+                sq += acc * acc;
+            }
+            b0[r] = -kp.bias_pen * sq;
+        }
+    }
+}
+
+// the potential field of the walkers' occupancies (kp.ew_phi), where the handle keeps one
+static int init_ewald_field(smolmc_handle *h) {
+    const KParams &kp = h->kp;
+    if (!kp.ew_field) return 0;
+    LeanParams fp;
+    memset(&fp, 0, sizeof(fp));
+    fp.occ = kp.occ; fp.Npad = h->Npad; fp.sbase = kp.ew_act_base; fp.ew_nact = kp.ew_nact;
+    fp.ew_W = kp.ew_W; fp.ew_qs = kp.ew_qs; fp.ew_G = kp.ew_G; fp.ew_frozen = kp.ew_frozen;
+    fp.ew_phi = kp.ew_phi;
+    const size_t shm = (size_t)kp.ew_nact * 8;
+    if (shm > 64 * 1024)
+        HIPCHK(hipFuncSetAttribute((const void *)ewald_field_init_kernel,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(ewald_field_init_kernel, dim3((unsigned)h->R), dim3(256), shm, h->stream, fp);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// features and enthalpy of the walkers' occupancies
+static int initial_trace(smolmc_handle *h) {
+    KParams &kp = h->kp;
+    const size_t R = h->R;
+    TRY(launch_eval_full(h, kp.occ, (int)R, kp.features));
+    // (per-walker chemical potentials: the chemical work of the initial trace at the walker's own row)
+    if (!h->walker_mu.empty()) TRY(smolmc_walker_mu_reprice(h, h->d_mu_create, 0, h->d_walker_mu[0], h->lp.mu_stride, kp.features, h->F, nullptr));
+    hipLaunchKernelGGL(dot_features_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, h->stream,
+                       kp.features, h->d_natural, kp.enthalpy, (int)R, h->F);
+    HIPCHK(hipGetLastError());
+    return lazy_scalars_from_features(h);
+}
+
+// reset_aux: the estimators go back to the walkers they were given to (a continuation keeps the map), and a
+// Wang-Landau handle starts its estimate over
+static int wl_reset(smolmc_handle *h) {
+    TRY(wl_windows_upload(h));
+    if (!is_wl(h)) return 0;
+    KParams &kp = h->kp;
+    const size_t R = h->R, RL = R * h->L;
+    HIPCHK(hipMemsetAsync(kp.wl_entropy, 0, RL * 8, h->stream));
+    HIPCHK(hipMemsetAsync(kp.wl_hist, 0, RL * 8, h->stream));
+    HIPCHK(hipMemsetAsync(kp.wl_occur, 0, RL * 8, h->stream));
+    HIPCHK(hipMemsetAsync(kp.wl_meanf, 0, RL * h->F * 8, h->stream));
+    h->wl_sums = false; // all zero: either representation
+    HIPCHK(hipMemsetAsync(kp.wl_counter, 0, R * 8, h->stream));
+    std::vector<double> m0(R, h->cfg.wl_mod_factor);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(kp.wl_m, m0.data(), R * 8, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// The bin of the CURRENT enthalpy indexes the entropy / histogram arrays unchecked in the
+// kernels (only proposed enthalpies are tested against the window, wanglandau.py:190-193).
+// The reference raises IndexError above the window and wraps to a wrong bin below it
+// (negative Python index, wanglandau.py:175-180); here both are refused up front.
+// (the stream is idle: the enthalpies of the initial trace are there)
+static int wl_check_window(smolmc_handle *h) {
+    if (!is_wl(h)) return 0;
+    const size_t R = h->R;
+    std::vector<double> H0(R);
+    HIPCHK(hipMemcpy(H0.data(), h->kp.enthalpy, R * 8, hipMemcpyDeviceToHost));
+    std::vector<WlWindow> win; // (per-walker windows: the window the walker holds)
+    TRY(wl_windows_download(h, win));
+    for (size_t r = 0; r < R; ++r) {
+        const double wmin = win.empty() ? h->cfg.wl_min_enthalpy : win[r].vmin, wmax = win.empty() ? h->cfg.wl_max_enthalpy : win[r].vmax;
+        if (!(H0[r] >= wmin && H0[r] < wmax)) {
+            char msg[240];
+            snprintf(msg, sizeof msg,
+                     "initial enthalpy %.6f of walker %zu is outside the Wang-Landau window "
+                     "[min_enthalpy, max_enthalpy) = [%.6f, %.6f)%s",
+                     H0[r], r, wmin, wmax, win.empty() ? "" : " the walker holds (smolmc_set_wl_windows)");
+            return fail(msg);
+        }
+    }
+    return 0;
+}
+
 extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint64_t *seeds,
                                 const double *temperature, int reset_aux) {
     if (!h || !occ) return fail("null argument");
@@ -2826,104 +2957,19 @@ extern "C" int smolmc_set_state(smolmc_handle *h, const int32_t *occ, const uint
     std::vector<int32_t> occ_engine;
     occ = occ_in(h, occ, R, occ_engine);
     TRY(upload_occ(h, occ, R, kp.occ));
-    std::vector<double> beta;
-    set_betas(h, temperature, beta);
-    TRY(grid_rebase(h));
-    grid_name_temperatures(h, temperature);
-    HIPCHK(hipMemcpy(h->d_beta, beta.data(), R * 8, hipMemcpyHostToDevice));
-    h->order_dirty = true;
-    if (reset_aux) {
-        std::vector<uint64_t> sd(R);
-        for (size_t r = 0; r < R; ++r) sd[r] = seeds ? seeds[r] : (uint64_t)r;
-        HIPCHK(hipMemcpy((void *)kp.seeds, sd.data(), R * 8, hipMemcpyHostToDevice));
-        HIPCHK(hipMemsetAsync(kp.nsteps, 0, R * 8, h->stream));
-        HIPCHK(hipMemsetAsync(kp.nacc, 0, R * 8, h->stream));
-    }
-    HIPCHK(hipMemsetAsync(kp.last_acc, 1, R, h->stream));
+    TRY(apply_temperatures(h, temperature));
+    TRY(reset_counters(h, seeds, reset_aux));
     if (kp.bias_type) {
-        // MCBias.compute_bias of every initial occupancy (kernel/base.py:362-363), on the host:
-        // the occupancies are host arrays here and this runs once per set_state
-        std::vector<double> b0(R), q0(R * SMOLMC_MAX_BIAS_ROWS, 0.0);
-        const int N = h->N, W = kp.bias_W;
-        for (size_t r = 0; r < R; ++r) {
-            const int32_t *o = occ + r * (size_t)N;
-            if (kp.bias_type == SMOLMC_BIAS_FUGACITY) {
-                double acc = 0.0;
-                for (int s = 0; s < N; ++s) acc += log(h->bias_host[(size_t)s * W + o[s]]); // bias.py:174-186
-                b0[r] = acc;
-            } else {
-                // SquareChargeBias (bias.py:264-277) = one hyperplane with intercept 0;
-                // SquareHyperplaneBias (bias.py:352-366): -penalty * sum_r (A_r . n - b_r)^2
-                double sq = 0.0;
-                for (int k = 0; k < kp.bias_rows; ++k) {
-                    double acc = 0.0;
-                    const double *tab = h->bias_host.data() + (size_t)k * kp.bias_row_stride;
-                    for (int s = 0; s < N; ++s) acc += tab[(size_t)s * W + o[s]];
-                    acc -= h->bias_icpt[k];
-                    q0[r * SMOLMC_MAX_BIAS_ROWS + k] = acc;
-                    sq += acc * acc;
-                }
-                b0[r] = -kp.bias_pen * sq;
-            }
-        }
+        std::vector<double> b0, q0;
+        initial_bias(h, occ, b0, q0);
         HIPCHK(hipMemcpy(kp.bias, b0.data(), R * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(kp.charge, q0.data(), q0.size() * 8, hipMemcpyHostToDevice));
     }
-    if (kp.ew_field) {
-        LeanParams fp;
-        memset(&fp, 0, sizeof(fp));
-        fp.occ = kp.occ; fp.Npad = h->Npad; fp.sbase = kp.ew_act_base; fp.ew_nact = kp.ew_nact;
-        fp.ew_W = kp.ew_W; fp.ew_qs = kp.ew_qs; fp.ew_G = kp.ew_G; fp.ew_frozen = kp.ew_frozen;
-        fp.ew_phi = kp.ew_phi;
-        const size_t shm = (size_t)kp.ew_nact * 8;
-        if (shm > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)ewald_field_init_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        hipLaunchKernelGGL(ewald_field_init_kernel, dim3((unsigned)R), dim3(256), shm, h->stream, fp);
-        HIPCHK(hipGetLastError());
-    }
-    TRY(launch_eval_full(h, kp.occ, (int)R, kp.features));
-    // (per-walker chemical potentials: the chemical work of the initial trace at the walker's own row)
-    if (!h->walker_mu.empty()) TRY(smolmc_walker_mu_reprice(h, h->d_mu_create, 0, h->d_walker_mu[0], h->lp.mu_stride, kp.features, h->F, nullptr));
-    hipLaunchKernelGGL(dot_features_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, h->stream,
-                       kp.features, h->d_natural, kp.enthalpy, (int)R, h->F);
-    HIPCHK(hipGetLastError());
-    TRY(lazy_scalars_from_features(h));
-    if (reset_aux) TRY(wl_windows_upload(h)); // (the estimators go back to the walkers they were given to; a continuation keeps the map)
-    if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU && reset_aux) {
-        const size_t RL = R * h->L;
-        HIPCHK(hipMemsetAsync(kp.wl_entropy, 0, RL * 8, h->stream));
-        HIPCHK(hipMemsetAsync(kp.wl_hist, 0, RL * 8, h->stream));
-        HIPCHK(hipMemsetAsync(kp.wl_occur, 0, RL * 8, h->stream));
-        HIPCHK(hipMemsetAsync(kp.wl_meanf, 0, RL * h->F * 8, h->stream));
-        h->wl_sums = false; // all zero: either representation
-        HIPCHK(hipMemsetAsync(kp.wl_counter, 0, R * 8, h->stream));
-        std::vector<double> m0(R, h->cfg.wl_mod_factor);
-        HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipMemcpy(kp.wl_m, m0.data(), R * 8, hipMemcpyHostToDevice));
-    }
+    TRY(init_ewald_field(h));
+    TRY(initial_trace(h));
+    if (reset_aux) TRY(wl_reset(h));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU) {
-        // The bin of the CURRENT enthalpy indexes the entropy / histogram arrays unchecked in the
-        // kernels (only proposed enthalpies are tested against the window, wanglandau.py:190-193).
-        // The reference raises IndexError above the window and wraps to a wrong bin below it
-        // (negative Python index, wanglandau.py:175-180); here both are refused up front.
-        std::vector<double> H0(R);
-        HIPCHK(hipMemcpy(H0.data(), kp.enthalpy, R * 8, hipMemcpyDeviceToHost));
-        std::vector<WlWindow> win; // (per-walker windows: the window the walker holds)
-        TRY(wl_windows_download(h, win));
-        for (size_t r = 0; r < R; ++r) {
-            const double wmin = win.empty() ? h->cfg.wl_min_enthalpy : win[r].vmin, wmax = win.empty() ? h->cfg.wl_max_enthalpy : win[r].vmax;
-            if (!(H0[r] >= wmin && H0[r] < wmax)) {
-                char msg[240];
-                snprintf(msg, sizeof msg,
-                         "initial enthalpy %.6f of walker %zu is outside the Wang-Landau window "
-                         "[min_enthalpy, max_enthalpy) = [%.6f, %.6f)%s",
-                         H0[r], r, wmin, wmax, win.empty() ? "" : " the walker holds (smolmc_set_wl_windows)");
-                return fail(msg);
-            }
-        }
-    }
+    TRY(wl_check_window(h));
     if (h->dist) return smolmc_dist_after_set_state(h, temperature);
     return 0;
 }
@@ -2932,14 +2978,8 @@ extern "C" int smolmc_set_temperature(smolmc_handle *h, const double *temperatur
     if (!h || !temperature) return fail("null argument");
     if (h->dist) return smolmc_dist_set_temperature(h, temperature);
     HIPCHK(hipSetDevice(h->device));
-    std::vector<double> beta;
-    set_betas(h, temperature, beta);
     HIPCHK(hipStreamSynchronize(h->stream));
-    TRY(grid_rebase(h));
-    grid_name_temperatures(h, temperature);
-    HIPCHK(hipMemcpy(h->d_beta, beta.data(), (size_t)h->R * 8, hipMemcpyHostToDevice));
-    h->order_dirty = true;
-    return 0;
+    return apply_temperatures(h, temperature);
 }
 
 extern "C" int smolmc_sync(smolmc_handle *h) {
@@ -3017,16 +3057,14 @@ extern "C" int smolmc_get_state(smolmc_handle *h, int32_t *occ, double *features
     const size_t R = h->R;
     KParams &kp = h->kp;
     if (occ) {
-        int *d32 = nullptr;
+        DevScratch d32;
         const size_t total = R * h->N;
-        HIPCHK(hipMalloc((void **)&d32, total * 4));
+        TRY(d32.alloc(total * 4));
         hipLaunchKernelGGL(unpack_occ_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                           h->stream, kp.occ, d32, h->N, h->Npad, total);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(occ, d32, total * 4, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        hipFree(d32);
-        if (e != hipSuccess) return fail(std::string("occupancy download: ") + hipGetErrorString(e));
+                           h->stream, kp.occ, d32.as<int>(), h->N, h->Npad, total);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(occ, d32.p, total * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
         occ_out(h, occ, R);
     }
     if (features) {
@@ -3724,6 +3762,144 @@ static int smolmc_launch_lean_replay(smolmc_handle *h, LeanParams lp) {
     return lean_launcher(h, true)(h, lp);
 }
 
+// ---- smolmc_replay in stages: scan the records, choose the route, stage, launch, read back ------------------------------
+struct ReplayFacts {
+    int max_flips = 0;          // flips of the longest record
+    bool repeated_site = false; // a record that flips one site twice (sequential-flip semantics, expansion.py:217-229)
+    bool priori_given = false;  // a factor the Flip / Swap kernels do not model (replay_priori_given)
+};
+// one pass over the records.  Every flip: a changeable site of an active sublattice (the lean kernels index their
+// tables relative to the active range; a code beyond the site's species would index past its tensors)
+static int replay_scan(const smolmc_handle *h, const int32_t *steps, size_t n, ReplayFacts &f) {
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t *st = steps + i * SMOLMC_STEP_ROW;
+        int nf = 0;
+        for (; nf < SMOLMC_MAX_STEP_FLIPS && st[2 * nf] >= 0; ++nf) {
+            const int32_t site = st[2 * nf], code = st[2 * nf + 1];
+            if (site >= h->N) return fail("replay step out of range");
+            if (!h->site_active[site]) return fail("replay step out of range: the site is not changeable (not on an active sublattice)");
+            if (code < 0 || code >= (int)h->site_ncodes[site]) return fail("replay step out of range (species code)");
+            for (int g = 0; g < nf; ++g) f.repeated_site |= st[2 * g] == site;
+        }
+        f.max_flips = std::max(f.max_flips, nf);
+    }
+    return 0;
+}
+// ... and over the a-priori factors (behind the distance hand-over: a distance handle has its own refusal): NaN asks
+// the kernel to derive the factor, 0 is what the Flip / Swap ushers give
+static bool replay_priori_given(const double *log_priori, size_t n) {
+    if (log_priori)
+        for (size_t i = 0; i < n; ++i)
+            if (log_priori[i] == log_priori[i] && log_priori[i] != 0.0) return true;
+    return false;
+}
+
+// Which kernel replays the records: a function of the handle, the scan's facts, nsteps and the two environment
+// switches (SMOLMC_REPLAY_GENERAL, SMOLMC_REPLAY_UNIVERSAL) only.
+// Lean handles replay on their own kernels (REPLAY instantiations of mc_lean_kernel,
+// mc_lean_multi_kernel, mc_wl_kernel, mc_table_kernel, mc_table_multi_kernel); steps those cannot
+// take (more than two flips on a Flip / Swap handle, a given a-priori factor there), universal
+// handles and SMOLMC_REPLAY_UNIVERSAL take the universal kernel; SMOLMC_REPLAY_GENERAL: mc_kernel.
+enum ReplayRoute { ROUTE_LEAN, ROUTE_LEAN_TABLE, ROUTE_GENERAL, ROUTE_UNIVERSAL };
+static const char *const replay_route_names[] = {"lean", "lean-table", "general", "universal"};
+static ReplayRoute replay_route(const smolmc_handle *h, const ReplayFacts &f, int64_t nsteps, bool env_general, bool env_universal) {
+    // what the two-flip kernels (the Flip / Swap lean kernels, mc_kernel) take
+    const bool two_flip_ok = f.max_flips <= 2 && !f.priori_given && !is_table(h);
+    // (a biased or Wang-Landau TableFlip handle has no REPLAY instantiation: the universal kernel replays its records)
+    if (h->lean() && !env_universal && nsteps < ((int64_t)1 << 30) && smolmc_lean_replay_takes(h)) {
+        // (the lean TableFlip replay kernels pick sites without replacement like the usher: a record with a repeated
+        // site -- valid for the boundary -- takes the universal kernel, which evaluates it flip by flip;
+        // SMOLMC_REPLAY_GENERAL is ignored: mc_kernel takes no table steps)
+        if (is_table(h)) {
+            if (!f.repeated_site) return ROUTE_LEAN_TABLE;
+        }
+        // (a Flip handle's own kernel takes single flips: records of two flips go to mc_kernel / the universal kernel)
+        else if (two_flip_ok && !(env_general && h->general_ok) && (h->cfg.step_type != SMOLMC_STEP_FLIP || f.max_flips <= 1))
+            return ROUTE_LEAN;
+    }
+    if (!h->univ() && two_flip_ok && h->general_ok && !env_universal) return ROUTE_GENERAL;
+    return ROUTE_UNIVERSAL;
+}
+
+int ReplayStage::upload(size_t n, const int32_t *steps_host, const double *uniforms, bool narrow, bool priori, const double *log_priori) {
+    // the two-flip kernels read records of four ints
+    std::vector<int32_t> packed;
+    if (narrow) {
+        packed.resize(n * 4);
+        for (size_t i = 0; i < n; ++i)
+            for (int k = 0; k < 4; ++k) packed[i * 4 + k] = steps_host[i * SMOLMC_STEP_ROW + k];
+    }
+    const size_t row_bytes = narrow ? 16 : SMOLMC_STEP_ROW * 4;
+    TRY(steps.alloc(n * row_bytes));
+    if (priori) TRY(err.alloc(16, true));
+    TRY(u.alloc(n * 8));
+    TRY(H.alloc(n * 8));
+    TRY(acc.alloc(n));
+    if (priori) TRY(lp_out.alloc(n * 8, true));
+    if (priori && log_priori) {
+        TRY(lp_in.alloc(n * 8));
+        HIPCHK(hipMemcpy(lp_in.p, log_priori, n * 8, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(steps.p, narrow ? packed.data() : steps_host, n * row_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(u.p, uniforms, n * 8, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// the handle's own REPLAY kernel (ROUTE_LEAN, ROUTE_LEAN_TABLE)
+static int replay_on_lean(smolmc_handle *h, int64_t nsteps, const ReplayStage &st) {
+    TRY(wl_set_representation(h, is_wl(h) && h->lp.wl.sum_mode));
+    LeanParams lp = h->lp;
+    memset(&lp.smp, 0, sizeof(lp.smp));
+    lp.steps = nsteps;
+    lp.rp_steps = st.steps.as<int>(); lp.rp_u = st.u.as<double>(); lp.rp_acc = st.acc.as<uint8_t>(); lp.rp_H = st.H.as<double>();
+    lp.rp_err = st.err.as<int>(); lp.rp_lp = st.lp_in.as<double>(); lp.rp_lp_out = st.lp_out.as<double>();
+    if (is_lazy(h)) h->ce_dirty = true;
+    return smolmc_launch_lean_replay(h, lp);
+}
+// mc_kernel (ROUTE_GENERAL)
+static int replay_on_general(smolmc_handle *h, int64_t nsteps, const ReplayStage &st) {
+    TRY(wl_set_representation(h, h->kp.wl_sum_mode != 0));
+    TRY(ensure_features(h)); // (mc_kernel updates the features incrementally)
+    KParams kp = h->kp;
+    kp.steps_to_run = nsteps;
+    kp.rp_steps = st.steps.as<int>(); kp.rp_u = st.u.as<double>(); kp.rp_acc = st.acc.as<uint8_t>(); kp.rp_H = st.H.as<double>();
+    TRY(launch_mc(h, kp, 1));
+    return lazy_scalars_from_features(h);
+}
+// the universal kernel (ROUTE_UNIVERSAL)
+static int replay_on_universal(smolmc_handle *h, int64_t nsteps, const ReplayStage &st) {
+    TRY(wl_set_representation(h, false));
+    TRY(ensure_features(h)); // (the universal kernel updates the features incrementally)
+    UParams up = univ_block_of(h);
+    up.K.steps_to_run = nsteps;
+    memset(&up.K.smp, 0, sizeof(up.K.smp));
+    up.K.rp_steps = st.steps.as<int>(); up.K.rp_u = st.u.as<double>(); up.K.rp_acc = st.acc.as<uint8_t>(); up.K.rp_H = st.H.as<double>();
+    up.rp_lp = st.lp_in.as<double>(); up.rp_lp_out = st.lp_out.as<double>(); up.rp_err = st.err.as<int>();
+    TRY(smolmc_launch_univ(h, up, 1));
+    return lazy_scalars_from_features(h);
+}
+
+static const char *const replay_not_in_table =
+    "replay: Step is not in flip table (neither a canonical swap nor +-(a row of flip_table)); "
+    "the walkers have been advanced -- set the state again";
+static const char *const replay_wrong_shape =
+    "replay step does not fit the handle's step type (a swap handle takes proper swaps: "
+    "code1 == species at site2, code2 == species at site1; a flip handle single flips); "
+    "the walkers have been advanced -- set the state again";
+// the kernel has finished: its error word (mc_kernel writes none) as a refusal, else the outputs
+static int replay_finish(ReplayRoute route, const ReplayStage &st, size_t n, uint8_t *accepted_out, double *enthalpy_out,
+                         double *log_priori_out) {
+    if (route != ROUTE_GENERAL) {
+        int bad = 0;
+        HIPCHK(hipMemcpy(&bad, st.err.p, 4, hipMemcpyDeviceToHost));
+        if (bad) return fail(route == ROUTE_LEAN ? replay_wrong_shape : replay_not_in_table);
+    }
+    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, st.acc.p, n, hipMemcpyDeviceToHost));
+    if (enthalpy_out) HIPCHK(hipMemcpy(enthalpy_out, st.H.p, n * 8, hipMemcpyDeviceToHost));
+    if (log_priori_out) HIPCHK(hipMemcpy(log_priori_out, st.lp_out.p, n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int smolmc_replay(smolmc_handle *h, int64_t nsteps, const int32_t *steps, const double *uniforms,
                              const double *log_priori, uint8_t *accepted_out, double *enthalpy_out,
                              double *log_priori_out) {
@@ -3735,134 +3911,25 @@ extern "C" int smolmc_replay(smolmc_handle *h, int64_t nsteps, const int32_t *st
     const size_t n = (size_t)h->R * nsteps;
     std::vector<int32_t> steps_engine;
     steps = steps_in(h, steps, n, steps_engine);
-    // every flip: a changeable site of an active sublattice (the lean kernels index their tables
-    // relative to the active range; a code beyond the site's species would index past its tensors)
-    int max_flips = 0;
-    bool repeated_site = false; // a record that flips one site twice (sequential-flip semantics, expansion.py:217-229)
-    for (size_t i = 0; i < n; ++i) {
-        const int32_t *st = steps + i * SMOLMC_STEP_ROW;
-        int nf = 0;
-        for (; nf < SMOLMC_MAX_STEP_FLIPS && st[2 * nf] >= 0; ++nf) {
-            const int32_t site = st[2 * nf], code = st[2 * nf + 1];
-            if (site >= h->N) return fail("replay step out of range");
-            if (!h->site_active[site]) return fail("replay step out of range: the site is not changeable (not on an active sublattice)");
-            if (code < 0 || code >= (int)h->site_ncodes[site]) return fail("replay step out of range (species code)");
-            for (int g = 0; g < nf; ++g) repeated_site |= st[2 * g] == site;
-        }
-        max_flips = std::max(max_flips, nf);
-    }
+    ReplayFacts facts;
+    TRY(replay_scan(h, steps, n, facts));
     if (h->dist) return smolmc_dist_replay(h, nsteps, steps, uniforms, log_priori, accepted_out, enthalpy_out, log_priori_out);
-    bool priori_given = false; // a factor the Flip / Swap kernels do not model
-    if (log_priori)
-        for (size_t i = 0; i < n && !priori_given; ++i) priori_given = log_priori[i] == log_priori[i] && log_priori[i] != 0.0;
-    const bool table = h->cfg.step_type == SMOLMC_STEP_TABLE_FLIP;
-    // Lean handles replay on their own kernels (REPLAY instantiations of mc_lean_kernel,
-    // mc_lean_multi_kernel, mc_wl_kernel, mc_table_kernel, mc_table_multi_kernel); steps those cannot
-    // take (more than two flips on a Flip / Swap handle, a given a-priori factor there), universal
-    // handles and SMOLMC_REPLAY_UNIVERSAL take the universal kernel; SMOLMC_REPLAY_GENERAL: mc_kernel.
-    const bool two_flip_ok = max_flips <= 2 && !priori_given && !table;
-    const bool replay_universal = smolmc_env(ENV_REPLAY_UNIVERSAL) != nullptr;
-    const bool want_general = smolmc_env(ENV_REPLAY_GENERAL) && two_flip_ok && h->general_ok;
-    // (the lean TableFlip replay kernels pick sites without replacement like the usher: a record with a repeated
-    // site -- valid for the boundary -- takes the universal kernel, which evaluates it flip by flip)
-    // (a biased or Wang-Landau TableFlip handle has no REPLAY instantiation: the universal kernel replays its records)
-    const bool lean_table_replay = h->lean() && table && nsteps < ((int64_t)1 << 30) && !repeated_site && smolmc_lean_replay_takes(h);
-    // (a Flip handle's own kernel takes single flips: records of two flips go to mc_kernel / the universal kernel)
-    const bool lean_shape_ok = two_flip_ok && (h->cfg.step_type != SMOLMC_STEP_FLIP || max_flips <= 1);
-    const bool lean_replay = h->lean() && !want_general && nsteps < ((int64_t)1 << 30) && !replay_universal &&
-                             ((lean_shape_ok && smolmc_lean_replay_takes(h)) || lean_table_replay);
-    const bool general_replay = !lean_replay && !h->univ() && two_flip_ok && h->general_ok && !replay_universal;
+    facts.priori_given = replay_priori_given(log_priori, n);
+    const ReplayRoute route = replay_route(h, facts, nsteps, smolmc_env(ENV_REPLAY_GENERAL) != nullptr,
+                                           smolmc_env(ENV_REPLAY_UNIVERSAL) != nullptr);
     if (smolmc_env(ENV_DEBUG))
-        fprintf(stderr, "[smolmc] replay path=%s max_flips=%d priori_given=%d\n",
-                lean_replay ? (table ? "lean-table" : "lean") : (general_replay ? "general" : "universal"), max_flips, (int)priori_given);
-    int *d_steps = nullptr, *d_err = nullptr;
-    double *d_u = nullptr, *d_H = nullptr, *d_lp = nullptr, *d_lpo = nullptr;
-    uint8_t *d_acc = nullptr;
-    // the two-flip kernels read records of four ints
-    std::vector<int32_t> packed;
-    const bool narrow = (lean_replay && !table) || general_replay;
-    if (narrow) {
-        packed.resize(n * 4);
-        for (size_t i = 0; i < n; ++i)
-            for (int k = 0; k < 4; ++k) packed[i * 4 + k] = steps[i * SMOLMC_STEP_ROW + k];
+        fprintf(stderr, "[smolmc] replay path=%s max_flips=%d priori_given=%d\n", replay_route_names[route], facts.max_flips,
+                (int)facts.priori_given);
+    ReplayStage st; // (freed on every way out; hipFree waits for the kernel)
+    TRY(st.upload(n, steps, uniforms, route == ROUTE_LEAN || route == ROUTE_GENERAL, true, log_priori));
+    switch (route) {
+    case ROUTE_LEAN:
+    case ROUTE_LEAN_TABLE: TRY(replay_on_lean(h, nsteps, st)); break;
+    case ROUTE_GENERAL: TRY(replay_on_general(h, nsteps, st)); break;
+    case ROUTE_UNIVERSAL: TRY(replay_on_universal(h, nsteps, st)); break;
     }
-    const size_t row_bytes = narrow ? 16 : SMOLMC_STEP_ROW * 4;
-    hipError_t e = hipMalloc((void **)&d_steps, n * row_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_err, 16);
-    if (e == hipSuccess) e = hipMemset(d_err, 0, 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_u, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_H, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_acc, n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_lpo, n * 8);
-    if (e == hipSuccess) e = hipMemset(d_lpo, 0, n * 8);
-    if (e == hipSuccess && log_priori) {
-        e = hipMalloc((void **)&d_lp, n * 8);
-        if (e == hipSuccess) e = hipMemcpy(d_lp, log_priori, n * 8, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(d_steps, narrow ? packed.data() : steps, n * row_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_u, uniforms, n * 8, hipMemcpyHostToDevice);
-    int rc = 0;
-    if (e == hipSuccess && lean_replay) {
-        const bool wl = h->cfg.kernel_type == SMOLMC_KERNEL_WANGLANDAU;
-        rc = wl_set_representation(h, wl && h->lp.wl.sum_mode);
-        LeanParams lp = h->lp;
-        memset(&lp.smp, 0, sizeof(lp.smp));
-        lp.steps = nsteps;
-        lp.rp_steps = d_steps; lp.rp_u = d_u; lp.rp_acc = d_acc; lp.rp_H = d_H; lp.rp_err = d_err;
-        lp.rp_lp = d_lp; lp.rp_lp_out = d_lpo;
-        if (!rc) rc = smolmc_launch_lean_replay(h, lp);
-        if (is_lazy(h)) h->ce_dirty = true;
-        if (!rc) e = hipStreamSynchronize(h->stream);
-        int bad = 0;
-        if (!rc && e == hipSuccess) e = hipMemcpy(&bad, d_err, 4, hipMemcpyDeviceToHost);
-        if (!rc && e == hipSuccess && bad)
-            rc = table ? fail("replay: Step is not in flip table (neither a canonical swap nor +-(a row of flip_table)); "
-                              "the walkers have been advanced -- set the state again")
-                       : fail("replay step does not fit the handle's step type (a swap handle takes proper swaps: "
-                              "code1 == species at site2, code2 == species at site1; a flip handle single flips); "
-                              "the walkers have been advanced -- set the state again");
-    } else if (e == hipSuccess && general_replay) {
-        rc = wl_set_representation(h, h->kp.wl_sum_mode != 0);
-        if (!rc) rc = ensure_features(h); // (mc_kernel updates the features incrementally)
-        KParams kp = h->kp;
-        kp.steps_to_run = nsteps;
-        kp.rp_steps = d_steps;
-        kp.rp_u = d_u;
-        kp.rp_acc = d_acc;
-        kp.rp_H = d_H;
-        if (!rc) rc = launch_mc(h, kp, 1);
-        if (!rc) rc = lazy_scalars_from_features(h);
-        if (!rc) e = hipStreamSynchronize(h->stream);
-    } else if (e == hipSuccess) {
-        rc = wl_set_representation(h, false);
-        if (!rc) rc = ensure_features(h); // (the universal kernel updates the features incrementally)
-        UParams up = univ_block_of(h);
-        up.K.steps_to_run = nsteps;
-        memset(&up.K.smp, 0, sizeof(up.K.smp));
-        up.K.rp_steps = d_steps; up.K.rp_u = d_u; up.K.rp_acc = d_acc; up.K.rp_H = d_H;
-        up.rp_lp = d_lp; up.rp_lp_out = d_lpo; up.rp_err = d_err;
-        if (!rc) rc = smolmc_launch_univ(h, up, 1);
-        if (!rc) rc = lazy_scalars_from_features(h);
-        if (!rc) e = hipStreamSynchronize(h->stream);
-        int bad = 0;
-        if (!rc && e == hipSuccess) e = hipMemcpy(&bad, d_err, 4, hipMemcpyDeviceToHost);
-        if (!rc && e == hipSuccess && bad)
-            rc = fail("replay: Step is not in flip table (neither a canonical swap nor +-(a row of flip_table)); "
-                      "the walkers have been advanced -- set the state again");
-    }
-    if (!rc && e == hipSuccess && accepted_out) e = hipMemcpy(accepted_out, d_acc, n, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && enthalpy_out) e = hipMemcpy(enthalpy_out, d_H, n * 8, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && log_priori_out) e = hipMemcpy(log_priori_out, d_lpo, n * 8, hipMemcpyDeviceToHost);
-    hipFree(d_steps);
-    hipFree(d_err);
-    hipFree(d_u);
-    hipFree(d_H);
-    hipFree(d_acc);
-    hipFree(d_lpo);
-    if (d_lp) hipFree(d_lp);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("replay: ") + hipGetErrorString(e));
-    return 0;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return replay_finish(route, st, n, accepted_out, enthalpy_out, log_priori_out);
 }
 
 extern "C" int smolmc_last_kernel_ms(smolmc_handle *h, float *ms) {
@@ -3894,14 +3961,11 @@ extern "C" int smolmc_eval_full(smolmc_handle *h, const int32_t *occ, int nocc, 
     std::vector<int32_t> occ_engine;
     occ = occ_in(h, occ, (size_t)nocc, occ_engine);
     TRY(upload_occ(h, occ, nocc, h->d_eval_occ));
-    double *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, (size_t)nocc * h->F * 8));
-    int rc = launch_eval_full(h, h->d_eval_occ, nocc, d_out);
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (!rc && e == hipSuccess) e = hipMemcpy(features, d_out, (size_t)nocc * h->F * 8, hipMemcpyDeviceToHost);
-    hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("eval_full: ") + hipGetErrorString(e));
+    DevScratch d_out;
+    TRY(d_out.alloc((size_t)nocc * h->F * 8));
+    TRY(launch_eval_full(h, h->d_eval_occ, nocc, d_out.as<double>()));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(features, d_out.p, (size_t)nocc * h->F * 8, hipMemcpyDeviceToHost));
     if (h->dist) return smolmc_dist_from_extensive(h, features, (size_t)nocc);
     return 0;
 }
@@ -4024,21 +4088,15 @@ extern "C" int smolmc_eval_delta(smolmc_handle *h, const int32_t *occ, const int
         }
     TRY(ensure_eval_occ(h, 1));
     TRY(upload_occ(h, occ, 1, h->d_eval_occ));
-    int *d_fl = nullptr;
-    double *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_fl, (size_t)nstep * SMOLMC_STEP_ROW * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)nstep * h->F * 8);
-    if (e == hipSuccess) e = hipMemcpy(d_fl, flips, (size_t)nstep * SMOLMC_STEP_ROW * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(eval_delta_kernel, dim3(nstep), dim3(64), 0, h->stream, h->rt, h->d_eval_occ,
-                           d_fl, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(dfeatures, d_out, (size_t)nstep * h->F * 8, hipMemcpyDeviceToHost);
-    hipFree(d_fl);
-    hipFree(d_out);
-    if (e != hipSuccess) return fail(std::string("eval_delta: ") + hipGetErrorString(e));
+    DevScratch d_fl, d_out;
+    TRY(d_fl.alloc((size_t)nstep * SMOLMC_STEP_ROW * 4));
+    TRY(d_out.alloc((size_t)nstep * h->F * 8));
+    HIPCHK(hipMemcpy(d_fl.p, flips, (size_t)nstep * SMOLMC_STEP_ROW * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(eval_delta_kernel, dim3(nstep), dim3(64), 0, h->stream, h->rt, h->d_eval_occ,
+                       d_fl.as<int>(), d_out.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(dfeatures, d_out.p, (size_t)nstep * h->F * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -250,15 +250,13 @@ extern "C" int smolmc_eval_observables(smolmc_handle *h, const int32_t *occ, int
     TRY(smolmc_eval_rows(h, occ, nocc, h->obs.kind_base, h->obs.K, "observables", &d_occ8, &rows));
     if (!rows) return 0;
     const size_t nc = rows * h->obs.K, np = rows * h->obs.cells;
-    int32_t *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>((nc + np) * 4, 16)));
-    int rc = smolmc_obs_launch(h, d_occ8, rows, d_out, d_out + nc);
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (!rc && e == hipSuccess && counts) e = hipMemcpy(counts, d_out, nc * 4, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && pairs && np) e = hipMemcpy(pairs, d_out + nc, np * 4, hipMemcpyDeviceToHost);
-    hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("eval_observables: ") + hipGetErrorString(e));
+    DevScratch out;
+    TRY(out.alloc(std::max<size_t>((nc + np) * 4, 16)));
+    int32_t *d_out = out.as<int32_t>();
+    TRY(smolmc_obs_launch(h, d_occ8, rows, d_out, d_out + nc));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (counts) HIPCHK(hipMemcpy(counts, d_out, nc * 4, hipMemcpyDeviceToHost));
+    if (pairs && np) HIPCHK(hipMemcpy(pairs, d_out + nc, np * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

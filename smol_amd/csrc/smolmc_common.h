@@ -743,9 +743,37 @@ struct UParams {
     int *rp_err;             // bit 0: step not in the flip table; bit 1: inactive site / impossible code
 };
 
-struct DevBuf {
+// A device buffer that lives for one call: freed when it goes out of scope (hipFree waits for the device, so a
+// function that returns early leaves no kernel behind that still reads it).  Handle-lifetime memory is not this:
+// h->allocs, the arenas and the sample slots stay with the handle.  No scratch in a scope that ends before its last
+// device use.
+struct DevScratch {
     void *p = nullptr;
-    size_t bytes = 0;
+    DevScratch() = default;
+    DevScratch(DevScratch &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevScratch &operator=(DevScratch &&o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    DevScratch(const DevScratch &) = delete;
+    DevScratch &operator=(const DevScratch &) = delete;
+    ~DevScratch() {
+        if (p) hipFree(p);
+    }
+    int alloc(size_t bytes, bool zero = false) {
+        HIPCHK(hipMalloc(&p, bytes));
+        if (zero) HIPCHK(hipMemset(p, 0, bytes));
+        return 0;
+    }
+    template <typename T> T *as() const { return (T *)p; }
+};
+
+// The device side of one smolmc_replay call (engine.hip; smolmc_dist_replay stages through it too): records, uniforms
+// and the per-step outputs.  `narrow`: the two-flip kernels read records of four ints, the others SMOLMC_STEP_ROW;
+// `priori`: with the error word and the a-priori factors out (zeroed) and, when log_priori is given, in.
+struct ReplayStage {
+    DevScratch steps, err, u, H, acc, lp_in, lp_out;
+    int upload(size_t n, const int32_t *steps_host, const double *uniforms, bool narrow, bool priori, const double *log_priori);
 };
 
 // The columns of a recorded block as offsets into its slot's arenas (engine.hip, plan_block): a column the block does not

@@ -404,15 +404,13 @@ extern "C" int smolmc_eval_structure(smolmc_handle *h, const int32_t *occ, int n
     TRY(smolmc_eval_rows(h, occ, nocc, S.kind_base, S.K, "structure factors", &d_occ8, &rows));
     if (!rows) return 0;
     const size_t na = rows * S.Q * S.K * 2, ni = rows * S.I;
-    unsigned char *d_out = nullptr;
-    HIPCHK(hipMalloc((void **)&d_out, std::max<size_t>((na + ni) * 8, 16)));
-    int rc = smolmc_sfac_launch(h, d_occ8, rows, (long long *)d_out, (double *)(d_out + na * 8));
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (!rc && e == hipSuccess && amp) e = hipMemcpy(amp, d_out, na * 8, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess && inten && ni) e = hipMemcpy(inten, d_out + na * 8, ni * 8, hipMemcpyDeviceToHost);
-    hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(std::string("eval_structure: ") + hipGetErrorString(e));
+    DevScratch out;
+    TRY(out.alloc(std::max<size_t>((na + ni) * 8, 16)));
+    unsigned char *d_out = out.as<unsigned char>();
+    TRY(smolmc_sfac_launch(h, d_occ8, rows, (long long *)d_out, (double *)(d_out + na * 8)));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (amp) HIPCHK(hipMemcpy(amp, d_out, na * 8, hipMemcpyDeviceToHost));
+    if (inten && ni) HIPCHK(hipMemcpy(inten, d_out + na * 8, ni * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 

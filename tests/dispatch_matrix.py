@@ -181,7 +181,12 @@ LEAN_FAMILIES = {
 
 class NoLeanLauncher(LookupError):
     """The family has no launcher for this request (a NULL of lean_families[]): smolmc_replay then takes mc_kernel or the
-    universal kernel, and smolmc_set_walker_mu / smolmc_set_wl_windows refuse the handle."""
+    universal kernel, and smolmc_set_walker_mu / smolmc_set_wl_windows refuse the handle.
+
+    Which kernel a replay cell runs is engine.hip's replay_route -- a function of the handle, the records' facts (longest
+    record, a repeated site, a given a-priori factor), nsteps and the two SMOLMC_REPLAY_* switches -- and
+    tests/test_gpu_replay_routes.py holds one case per row of it.  The replay cells here are the lean and lean-table
+    routes: the oracle's own trajectory, no switch set."""
 
 
 def family_of(k, f):

@@ -109,3 +109,25 @@ for n, thin in ((8 * 20000, 20000), (8 * 20000, 20000)):
     s4.clear_samples()
 k4 = kernel_rate(s4.engine, 20000, 2)
 print(f"config 4 kernel-only on the same handle ({s4.engine.kernel_info()}): {k4:.3e} steps/s", flush=True)
+
+# smolmc_replay of the first 200 TC_tf_int records (tests/v6_cases.py) on 64 walkers: the handle's own TableFlip kernel
+# and the universal kernel; the state is set again before every replay (the records are steps from the start), untimed
+from tests.v6_cases import T6, build  # noqa: E402
+
+tab_r, cfg_r, occ_r, temp_r = build("TC_tf_int", n_replicas=64)
+steps_r = np.ascontiguousarray(np.tile(T6["TC_tf_int_steps"][None, :200], (64, 1, 1)))
+us_r = np.tile(T6["TC_tf_int_u"][None, :200], (64, 1))
+eng_r = Engine(tab_r, cfg_r)
+for route, switch in (("lean-table", None), ("universal", "SMOLMC_REPLAY_UNIVERSAL")):
+    if switch:
+        os.environ[switch] = "1"
+    ms = []
+    for _ in range(12):
+        eng_r.set_state(np.tile(occ_r, (64, 1)), temperature=temp_r)
+        t = time.perf_counter()
+        eng_r.replay(steps_r, us_r)
+        ms.append((time.perf_counter() - t) * 1e3)
+    if switch:
+        del os.environ[switch]
+    print(f"replay 200 TC_tf_int records x 64 walkers on the {route} route: median {np.median(ms[2:]):.3f} ms "
+          f"(min {min(ms[2:]):.3f}, 10 calls)", flush=True)
