@@ -521,7 +521,9 @@ typedef struct smolmc_statistics {
     const int32_t *columns; /* [C] sources, no duplicates: 0 the enthalpy, 1 + i feature i (i < F), 1 + F + k kind count k
                              * of the observables in force (k < K, as a double), 1 + F + K the weighted sum below,
                              * 2 + F + K + i intensity i of the structure-factor spec in force (i < I, see
-                             * smolmc_set_structure; with no spec set the range ends at the weighted sum) */
+                             * smolmc_set_structure; with no spec set the range ends at the weighted sum); behind them
+                             * the connectivity numbers and the pattern cells (smolmc_get_sample_connectivity,
+                             * smolmc_get_sample_patterns) */
     int n_weights;          /* the weighted sum: sum_{i < n_weights} weights[i] * features[i] left to right, the value of */
     const double *weights;  /* a minima record (n_weights <= F) */
     int n_levels;           /* blocking levels, 0..32 */
@@ -651,6 +653,51 @@ int smolmc_eval_connectivity(smolmc_handle *h, const int32_t *occ /* nocc x N, o
  * stats[g][c] as a double (with no spec set the range ends where it ends without). */
 #define SMOLMC_SAMPLE_CONNECTIVITY 128
 int smolmc_get_sample_connectivity(smolmc_handle *h, int64_t *stats);
+
+/* ---- patterns: species patterns on site tuples of sampled states, counted on the device -----------------------------
+ * (no reference counterpart).  A pattern spec rests on the observables in force: the kind of (site, code) is
+ * kind_base[site] + code and there are K kinds.  The spec holds T sets.  Set t has an arity m_t, a class map
+ * class_of_kind[t][K] with values in 0 .. C_t - 1 or -1, and the site tuples tuple_ptr[t] .. tuple_ptr[t + 1] of m_t sites
+ * each.  Per occupancy row and set, for every tuple (i_0 .. i_{m-1}) as listed, with c_p = class_of_kind[t][kind(i_p)]:
+ *   cells[cell_ptr[t] + sum_p c_p * C_t^(m - 1 - p)] += 1        (row-major, the first position most significant)
+ * A tuple is skipped when one of its sites is not counted (kind_base < 0) or holds a kind whose class is -1.  Duplicate
+ * tuples and tuples that name a site twice count as they stand.  cell_ptr[t] = sum_{u < t} C_u^m_u, n_cells = cell_ptr[T].
+ * Everything is int32; smol_amd/patterns.py is the same in NumPy and the device matches it entry for entry.  The count
+ * runs in the observables' kernel: a block that asks for counts, pairs and patterns stages its rows once.  Site numbers
+ * are the caller's.  The engine copies and uploads everything. */
+#define SMOLMC_MAX_PATTERN_SETS 8
+#define SMOLMC_MAX_PATTERN_ARITY 8
+#define SMOLMC_MAX_PATTERN_CLASSES 255 /* C_t: a class is staged as one byte, 0xff marks a site that is skipped */
+#define SMOLMC_MAX_PATTERN_CELLS 4096  /* n_cells: 16 KB of int32 in LDS next to the row, its classes and the pair cells */
+typedef struct smolmc_patterns {
+    int n_sets;                   /* T, 1..SMOLMC_MAX_PATTERN_SETS */
+    const int32_t *arity;         /* [T], each 1..SMOLMC_MAX_PATTERN_ARITY */
+    const int32_t *n_classes;     /* [T], each 1..SMOLMC_MAX_PATTERN_CLASSES */
+    const int32_t *class_of_kind; /* [T x K], K of the observables in force; -1 .. n_classes[t] - 1 */
+    const int64_t *tuple_ptr;     /* [T + 1] tuples, ascending from 0 */
+    const int32_t *sites;         /* the tuples of set 0, then of set 1 ...: sum_t n_t x arity[t] sites */
+} smolmc_patterns;
+/* Sets (NULL: removes) the pattern spec of the handle.  Refused, each naming its reason: no observables set; T, an arity
+ * or a number of classes outside its range; a class outside -1 .. C_t - 1; a site out of range; more than
+ * SMOLMC_MAX_PATTERN_CELLS cells; a launch that does not fit the LDS of one workgroup; while a block recorded with
+ * SMOLMC_SAMPLE_PATTERNS waits in the ring; while a statistics record with pattern columns is set.  A refused call leaves
+ * the handle's spec as it was.  While a spec is set smolmc_set_observables is refused: K and the kinds are what the class
+ * maps index. */
+int smolmc_set_patterns(smolmc_handle *h, const smolmc_patterns *spec);
+/* T and n_cells in force (both 0: none set) */
+int smolmc_patterns_shape(smolmc_handle *h, int *n_sets, int *n_cells);
+/* cells [nocc x n_cells] of nocc occupancies (host, int32 like smolmc_eval_full), or, with occ == NULL, of the walkers'
+ * current states (nocc = R then). */
+int smolmc_eval_patterns(smolmc_handle *h, const int32_t *occ /* nocc x N, or NULL */, int nocc, int32_t *cells);
+/* With SMOLMC_SAMPLE_PATTERNS (256, flags bit 8) smolmc_run_sampled adds the column [rows x n_cells] (int32) to the block,
+ * filled on the device from the block's occupancy rows when its launches are through, by the launch that counts kinds and
+ * pairs; without SMOLMC_SAMPLE_OCCUPANCY those rows never leave the device.  The flag is refused while no spec is set.
+ * This call reads the column of the block the next smolmc_get_samples* call delivers ([nsamples x R x n_cells]) and does
+ * not mark it delivered, like smolmc_get_sample_observables; an error when that block was recorded without the flag.  In
+ * a statistics record the column sources 2 + F + K + I + 24 G + c read cell c as a double (with no spec set the range
+ * ends where it ends without); smolmc_update_statistics counts the patterns of the current states first. */
+#define SMOLMC_SAMPLE_PATTERNS 256
+int smolmc_get_sample_patterns(smolmc_handle *h, int32_t *cells);
 
 /* Same loop driven by host-provided proposals ("replay mode"): what
  * StandardSingleStepMixin.single_step (kernel/base.py:145-166) does after mcusher.propose_step

@@ -70,6 +70,11 @@ def connectivity_lds_bytes(n_sites, npad):
     up4 = lambda v: (v + 3) // 4 * 4  # noqa: E731
     b = 8 * n_sites + npad + up4(2 * n_sites) + up4(n_sites) + (CONN_WAVES * CONN_STATS + 4) * 4
     return b if b <= CONN_LDS_BYTES else None
+SAMPLE_PATTERNS = 256           # ... the pattern cells of every row (smolmc_set_patterns)
+MAX_PATTERN_SETS = 8            # SMOLMC_MAX_PATTERN_SETS
+MAX_PATTERN_ARITY = 8           # SMOLMC_MAX_PATTERN_ARITY
+MAX_PATTERN_CLASSES = 255       # SMOLMC_MAX_PATTERN_CLASSES
+MAX_PATTERN_CELLS = 4096        # SMOLMC_MAX_PATTERN_CELLS
 MAX_STEP_FLIPS = 8              # SMOLMC_MAX_STEP_FLIPS
 STEP_ROW = 2 * MAX_STEP_FLIPS   # SMOLMC_STEP_ROW: int32 per step record (site, code) x 8, -1 = no flip
 
@@ -230,6 +235,19 @@ class smolmc_connectivity(C.Structure):
         ("bond_ptr", _i64p),
         ("bonds", _i32p),
         ("images", C.POINTER(C.c_int8)),
+    ]
+
+
+class smolmc_patterns(C.Structure):
+    """Mirror of ``smolmc_patterns`` (include/smolmc.h); ``patterns.Patterns.c_struct`` fills it."""
+
+    _fields_ = [
+        ("n_sets", C.c_int),
+        ("arity", _i32p),
+        ("n_classes", _i32p),
+        ("class_of_kind", _i32p),
+        ("tuple_ptr", _i64p),
+        ("sites", _i32p),
     ]
 
 

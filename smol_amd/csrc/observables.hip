@@ -15,6 +15,14 @@
 // shared histogram: with few cells (kinds, or cells of a shell, <= OBS_BALLOT_CELLS) a wave counts each cell by ballot
 // and lane c carries the sum of cell c in a register; with more, every wave adds into a histogram of its own (as long
 // as OBS_WAVES copies fit the cell limit).  The wave histograms are folded at the end, one plain store per entry.
+//
+// Patterns (smolmc_set_patterns, smolmc_eval_patterns, SMOLMC_SAMPLE_PATTERNS; DESIGN 4.21, patterns.Patterns.evaluate is
+// the same in NumPy) are counted by the same launch, behind the shells: per set t and tuple (i_0 .. i_{m-1}), as listed,
+//   cells[cell_ptr[t] + sum_p class_t[kind(i_p)] C_t^(m-1-p)] += 1, skipped when a site has no kind or its kind no class
+// A second row in LDS holds every site's class in the set's map (one table lookup per site; sets with the map of the set
+// before share it).  A tuple is one record of 8 (arity <= 4) or 16 bytes of u16 sites, one record a lane.  Its cell is
+// counted like a pair cell where the set has more than OBS_BALLOT_CELLS cells; with fewer, in packed counters a lane keeps.
+// A launch without sets takes none of these branches.
 #include "smolmc_common.h"
 
 #define OBS_THREADS 256
@@ -30,13 +38,42 @@ struct ObsArgs {
     int32_t *counts, *pairs;   // [rows x K], [rows x n_shells x K x K]
     int N, Npad, K, n_shells;
     int pair_copies;           // histograms of the pair cells in LDS: OBS_WAVES (one per wave) or 1
+    // the pattern sets (n_sets == 0: none, nothing below is read)
+    const int32_t *sets;       // [n_sets x 8]: arity, classes, tuples, first cell, first record / 16 bytes, cells, new map, 0
+    const uint8_t *class_of;   // [n_sets x 256]: class of a kind, 0xff: skip
+    const unsigned char *recs; // records of 4 or 8 u16 sites
+    int32_t *cells;            // [rows x n_cells]
+    int n_sets, n_cells;
+    int pat_copies;            // histograms of the pattern cells in LDS: OBS_WAVES or 1
 };
 
 // LDS: kinds u8 [Npad] | counts i32 [OBS_WAVES][K] | pairs i32 [pair_copies][n_shells K K]
+//      | patterns i32 [pat_copies][n_cells] | classes u8 [Npad]      (the last two in a launch with pattern sets)
 size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies) {
     return (size_t)Npad + ((size_t)OBS_WAVES * K + (size_t)pair_copies * cells) * 4;
 }
 int smolmc_obs_pair_copies(size_t cells) { return cells * OBS_WAVES <= SMOLMC_MAX_OBS_CELLS ? OBS_WAVES : 1; }
+size_t smolmc_pat_lds_bytes(int Npad, size_t n_cells, int copies) { return (size_t)copies * n_cells * 4 + (size_t)Npad; }
+static int smolmc_pat_copies(size_t n_cells) { return n_cells * OBS_WAVES <= SMOLMC_MAX_PATTERN_CELLS ? OBS_WAVES : 1; }
+
+// four sites of a tuple record: the classes of all four are read (a short tuple is filled up with site 0), the first m
+// enter the cell, most significant first
+__device__ __forceinline__ void pat_unpack4(const uint8_t *cls, uint32_t lo, uint32_t hi, int m, unsigned C, unsigned &cell,
+                                            bool &skip) {
+    const unsigned c0 = cls[lo & 0xffffu], c1 = cls[lo >> 16], c2 = cls[hi & 0xffffu], c3 = cls[hi >> 16];
+    cell = cell * C + c0; skip |= c0 == OBS_NOKIND;
+    if (m > 1) { cell = cell * C + c1; skip |= c1 == OBS_NOKIND; }
+    if (m > 2) { cell = cell * C + c2; skip |= c2 == OBS_NOKIND; }
+    if (m > 3) { cell = cell * C + c3; skip |= c3 == OBS_NOKIND; }
+}
+
+// a lane's packed counts of a set of few cells into the histogram (LDS atomics: a wave's copy, or the shared one)
+__device__ __forceinline__ void pat_flush(int32_t *hist, int nc, unsigned long long pk0, unsigned long long pk1) {
+    for (int c = 0; c < nc; ++c) {
+        const int v = (int)(((c < 8 ? pk0 : pk1) >> ((c & 7) * 8)) & 0xffull);
+        if (v) atomicAdd(&hist[c], v);
+    }
+}
 
 __global__ void __launch_bounds__(OBS_THREADS) observables_kernel(const ObsArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char obs_smem[];
@@ -52,7 +89,7 @@ __global__ void __launch_bounds__(OBS_THREADS) observables_kernel(const ObsArgs 
         const uint4 *src = (const uint4 *)(A.occ + row * Npad);
         uint4 *dst = (uint4 *)kinds;
         for (int i = tid; i < Npad / 16; i += OBS_THREADS) dst[i] = src[i];
-        for (int i = tid; i < OBS_WAVES * K + A.pair_copies * cells; i += OBS_THREADS) cnt[i] = 0;
+        for (int i = tid; i < OBS_WAVES * K + A.pair_copies * cells + A.pat_copies * A.n_cells; i += OBS_THREADS) cnt[i] = 0;
     }
     __syncthreads();
 
@@ -110,15 +147,77 @@ __global__ void __launch_bounds__(OBS_THREADS) observables_kernel(const ObsArgs 
             else atomicAdd(&mine[sh * KK + lane], acc);
         }
     }
+
+    // the pattern sets: the classes of the sites in the set's map, then the tuples, one record a lane
+    int32_t *phist = hist + A.pair_copies * cells;
+    for (int t = 0; t < A.n_sets; ++t) {
+        const int32_t *S = A.sets + 8 * t; // (uniform: scalar loads)
+        const int m = S[0], n = S[2], nc = S[5];
+        const unsigned C = (unsigned)S[1];
+        uint8_t *cls = (uint8_t *)(phist + A.pat_copies * A.n_cells);
+        if (S[6]) { // another map than the set before had (set 0: always); every thread of the workgroup gets here
+            __syncthreads();
+            const uint8_t *tab = A.class_of + 256 * t;
+            for (int s = tid; s < Npad; s += OBS_THREADS) cls[s] = tab[kinds[s]];
+            __syncthreads();
+        }
+        const unsigned char *recs = A.recs + (size_t)S[4] * 16;
+        int32_t *pmine = phist + (A.pat_copies > 1 ? wave * A.n_cells : 0) + S[3];
+        // few cells: a lane counts its own tuples in 8-bit fields of two registers (cells 0..7, 8..15) and adds them to
+        // the histogram every 255 tuples and at the end -- measured 1.6x the ballot form of the pair cells on the
+        // headline shape, whose eight to sixteen ballots a tuple were most of the loop
+        const bool few = nc <= OBS_BALLOT_CELLS;
+        unsigned long long pk0 = 0, pk1 = 0;
+        int held = 0;
+        for (int base = wave * 64; base < n; base += OBS_THREADS) {
+            const int i = base + lane;
+            int cell = -1;
+            if (i < n) {
+                unsigned v = 0;
+                bool skip = false;
+                if (m <= 4) {
+                    const uint2 w = ((const uint2 *)recs)[i];
+                    pat_unpack4(cls, w.x, w.y, m, C, v, skip);
+                } else {
+                    const uint4 w = ((const uint4 *)recs)[i];
+                    pat_unpack4(cls, w.x, w.y, 4, C, v, skip);
+                    pat_unpack4(cls, w.z, w.w, m - 4, C, v, skip);
+                }
+                if (!skip) cell = (int)v;
+            }
+            if (few) {
+                if (cell >= 0) {
+                    const unsigned long long one = 1ull << ((cell & 7) * 8);
+                    if (cell < 8) pk0 += one;
+                    else pk1 += one;
+                }
+                if (++held == 255) { // (uniform over the wave: a field holds 255 at most)
+                    pat_flush(pmine, nc, pk0, pk1);
+                    pk0 = pk1 = 0;
+                    held = 0;
+                }
+            } else if (cell >= 0) {
+                atomicAdd(&pmine[cell], 1);
+            }
+        }
+        if (few) pat_flush(pmine, nc, pk0, pk1);
+    }
     __syncthreads();
 
     // fold the waves' copies: plain stores, one per entry
-    for (int k = tid; k < K; k += OBS_THREADS) {
-        int v = 0;
+    if (A.counts)
+        for (int k = tid; k < K; k += OBS_THREADS) {
+            int v = 0;
 #pragma unroll
-        for (int w = 0; w < OBS_WAVES; ++w) v += cnt[w * K + k];
-        A.counts[row * K + k] = v;
-    }
+            for (int w = 0; w < OBS_WAVES; ++w) v += cnt[w * K + k];
+            A.counts[row * K + k] = v;
+        }
+    if (A.n_sets)
+        for (int c = tid; c < A.n_cells; c += OBS_THREADS) {
+            int v = 0;
+            for (int w = 0; w < A.pat_copies; ++w) v += phist[w * A.n_cells + c];
+            A.cells[row * (size_t)A.n_cells + c] = v;
+        }
     for (int c = tid; c < cells; c += OBS_THREADS) {
         int v = 0;
         for (int w = 0; w < A.pair_copies; ++w) v += hist[w * cells + c];
@@ -126,9 +225,11 @@ __global__ void __launch_bounds__(OBS_THREADS) observables_kernel(const ObsArgs 
     }
 }
 
-int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs) {
+int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs, int32_t *d_cells) {
     const SmolmcObs &O = h->obs;
+    const SmolmcPat &P = O.pat;
     if (!O.K) return fail("no observables set (smolmc_set_observables)");
+    if (d_cells && !P.n_sets) return fail("no pattern spec set (smolmc_set_patterns)");
     if (!rows) return 0;
     if (rows > 0x7fffffffull) return fail("observables: more than 2^31 rows in one launch");
     ObsArgs A;
@@ -136,12 +237,15 @@ int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int3
     A.counts = d_counts; A.pairs = d_pairs;
     A.N = h->N; A.Npad = h->Npad; A.K = O.K; A.pair_copies = O.pair_copies;
     A.n_shells = d_pairs ? O.n_shells : 0; // (no shells: the kernel counts the kinds and never touches the pair arrays)
+    A.sets = P.d_sets; A.class_of = P.d_class; A.recs = P.d_recs; A.cells = d_cells;
+    A.n_sets = d_cells ? P.n_sets : 0;     // (no sets: the kernel never touches the pattern arrays)
+    A.n_cells = d_cells ? (int)P.n_cells : 0; A.pat_copies = P.copies;
     if (!h->obs_ev0) {
         HIPCHK(hipEventCreate(&h->obs_ev0));
         HIPCHK(hipEventCreate(&h->obs_ev1));
     }
     HIPCHK(hipEventRecord(h->obs_ev0, h->stream));
-    hipLaunchKernelGGL(observables_kernel, dim3((unsigned)rows), dim3(OBS_THREADS), O.lds, h->stream, A);
+    hipLaunchKernelGGL(observables_kernel, dim3((unsigned)rows), dim3(OBS_THREADS), O.lds + (d_cells ? P.lds : 0), h->stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->obs_ev1, h->stream));
     return 0;
@@ -162,7 +266,12 @@ void smolmc_obs_free(SmolmcObs &O) {
     if (O.d_kind_base) hipFree(O.d_kind_base);
     if (O.d_shell_ptr) hipFree(O.d_shell_ptr);
     if (O.d_bonds) hipFree(O.d_bonds);
+    smolmc_pat_free(O.pat);
     O = SmolmcObs();
+}
+void smolmc_pat_free(SmolmcPat &P) {
+    if (P.arena) hipFree(P.arena);
+    P = SmolmcPat();
 }
 
 // ---- the C-ABI of the observables --------------------------------------------------------------------------------------
@@ -171,6 +280,9 @@ extern "C" int smolmc_set_observables(smolmc_handle *h, const smolmc_observables
     HIPCHK(hipSetDevice(h->device));
     TRY(smolmc_ring_guard(h, SMOLMC_SAMPLE_OBSERVABLES, "smolmc_set_observables", "SMOLMC_SAMPLE_OBSERVABLES"));
     SmolmcObs O;
+    if (h->obs.pat.n_sets)
+        return fail("smolmc_set_observables while a pattern spec rests on the kinds of the observables (call "
+                    "smolmc_set_patterns(h, NULL) first)");
     if (h->minima.n_slots && h->minima.n_axes)
         return fail("smolmc_set_observables while a minima record keyed by composition depends on the observables (call "
                     "smolmc_set_minima(h, NULL) first)");
@@ -253,7 +365,7 @@ extern "C" int smolmc_eval_observables(smolmc_handle *h, const int32_t *occ, int
     DevScratch out;
     TRY(out.alloc(std::max<size_t>((nc + np) * 4, 16)));
     int32_t *d_out = out.as<int32_t>();
-    TRY(smolmc_obs_launch(h, d_occ8, rows, d_out, d_out + nc));
+    TRY(smolmc_obs_launch(h, d_occ8, rows, d_out, d_out + nc, nullptr));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (counts) HIPCHK(hipMemcpy(counts, d_out, nc * 4, hipMemcpyDeviceToHost));
     if (pairs && np) HIPCHK(hipMemcpy(pairs, d_out + nc, np * 4, hipMemcpyDeviceToHost));
@@ -266,5 +378,140 @@ extern "C" int smolmc_get_sample_observables(smolmc_handle *h, int32_t *counts, 
     TRY(smolmc_sample_block(h, SMOLMC_SAMPLE_OBSERVABLES, "the observables were not recorded (flags bit 3)", &sl, &rows));
     if (counts) smolmc_host_copy(counts, sl->hst + sl->o_cnt, rows * (size_t)h->obs.K * 4);
     if (pairs) smolmc_host_copy(pairs, sl->hst + sl->o_pair, rows * h->obs.cells * 4);
+    return 0;
+}
+
+// ---- the C-ABI of the pattern spec ---------------------------------------------------------------------------------------
+extern "C" int smolmc_set_patterns(smolmc_handle *h, const smolmc_patterns *sp) {
+    if (!h) return fail("null handle");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(smolmc_ring_guard(h, SMOLMC_SAMPLE_PATTERNS, "smolmc_set_patterns", "SMOLMC_SAMPLE_PATTERNS"));
+    if (h->stats.n_keys && h->stats.n_pat_cols)
+        return fail("smolmc_set_patterns while a statistics record with pattern columns depends on the spec (call "
+                    "smolmc_set_statistics(h, NULL) first)");
+    SmolmcPat P;
+    if (sp) {
+        const SmolmcObs &O = h->obs;
+        const int N = h->N, K = O.K, T = sp->n_sets;
+        char msg[256];
+        if (!K) return fail("patterns: no observables set: the class maps index their kinds (call smolmc_set_observables first)");
+        if (T < 1 || T > SMOLMC_MAX_PATTERN_SETS) {
+            snprintf(msg, sizeof msg, "patterns: n_sets must be 1..%d, got %d", SMOLMC_MAX_PATTERN_SETS, T);
+            return fail(msg);
+        }
+        if (!sp->arity || !sp->n_classes || !sp->class_of_kind || !sp->tuple_ptr) return fail("patterns: null argument");
+        if (sp->tuple_ptr[0] != 0) return fail("patterns: tuple_ptr[0] must be 0");
+        std::vector<int32_t> sets((size_t)T * 8, 0);
+        std::vector<uint8_t> tab((size_t)T * 256, (uint8_t)OBS_NOKIND);
+        std::vector<uint16_t> recs;
+        size_t n_cells = 0, site0 = 0;
+        for (int t = 0; t < T; ++t) {
+            const int m = sp->arity[t], C = sp->n_classes[t];
+            if (m < 1 || m > SMOLMC_MAX_PATTERN_ARITY) {
+                snprintf(msg, sizeof msg, "patterns: set %d has arity %d, outside 1..%d", t, m, SMOLMC_MAX_PATTERN_ARITY);
+                return fail(msg);
+            }
+            if (C < 1 || C > SMOLMC_MAX_PATTERN_CLASSES) {
+                snprintf(msg, sizeof msg, "patterns: set %d has %d classes, outside 1..%d", t, C, SMOLMC_MAX_PATTERN_CLASSES);
+                return fail(msg);
+            }
+            for (int k = 0; k < K; ++k) {
+                const int32_t c = sp->class_of_kind[(size_t)t * K + k];
+                if (c < -1 || c >= C) {
+                    snprintf(msg, sizeof msg, "patterns: set %d maps kind %d to class %d, outside -1..%d: class out of range", t, k, (int)c, C - 1);
+                    return fail(msg);
+                }
+                tab[(size_t)t * 256 + k] = c < 0 ? (uint8_t)OBS_NOKIND : (uint8_t)c;
+            }
+            size_t nc = 1;
+            for (int p = 0; p < m && nc <= SMOLMC_MAX_PATTERN_CELLS; ++p) nc *= (size_t)C;
+            if (n_cells + nc > SMOLMC_MAX_PATTERN_CELLS) {
+                snprintf(msg, sizeof msg, "patterns: set %d with %d classes on %d sites brings the spec to more than "
+                         "SMOLMC_MAX_PATTERN_CELLS = %d cells", t, C, m, SMOLMC_MAX_PATTERN_CELLS);
+                return fail(msg);
+            }
+            const int64_t n = sp->tuple_ptr[t + 1] - sp->tuple_ptr[t];
+            if (n < 0) return fail("patterns: tuple_ptr must not decrease");
+            if (n > 0 && !sp->sites) return fail("patterns: null argument");
+            const size_t width = m <= 4 ? 4 : 8; // u16 sites of a record
+            if ((recs.size() + (size_t)n * width) * 2 > ((size_t)1 << 30)) return fail("patterns: the tuple records take more than 1 GiB");
+            int32_t *S = &sets[(size_t)t * 8];
+            S[0] = m; S[1] = C; S[2] = (int32_t)n; S[3] = (int32_t)n_cells; S[4] = (int32_t)(recs.size() / 8); S[5] = (int32_t)nc;
+            S[6] = t == 0 || memcmp(&tab[(size_t)t * 256], &tab[(size_t)(t - 1) * 256], 256) != 0;
+            const size_t r0 = recs.size();
+            recs.resize(r0 + (((size_t)n * width + 7) & ~(size_t)7), 0); // (every set starts at a multiple of 16 bytes)
+            for (int64_t i = 0; i < n; ++i)
+                for (int p = 0; p < m; ++p) {
+                    const int32_t s = sp->sites[site0 + (size_t)i * m + p];
+                    if (s < 0 || s >= N) {
+                        snprintf(msg, sizeof msg, "patterns: set %d tuple %lld names site %d, %d sites: site out of range", t, (long long)i,
+                                 (int)s, N);
+                        return fail(msg);
+                    }
+                    recs[r0 + (size_t)i * width + p] = (uint16_t)(h->relabelled ? h->new_of[s] : s);
+                }
+            site0 += (size_t)n * m;
+            n_cells += nc;
+        }
+        P.n_sets = T; P.n_cells = n_cells;
+        P.copies = smolmc_pat_copies(n_cells);
+        P.lds = smolmc_pat_lds_bytes(h->Npad, n_cells, P.copies);
+        // (a row that fits LDS has fewer than 2^16 sites: a site of a record is 16 bits)
+        if (O.lds + P.lds > 64 * 1024) {
+            snprintf(msg, sizeof msg, "patterns: a launch takes %zu bytes of LDS for the row and the observables and %zu for the classes "
+                     "and %zu cells, 65536 at most", O.lds, P.lds, n_cells);
+            return fail(msg);
+        }
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
+        const size_t o_sets = take(sets.size() * 4), o_tab = take(tab.size()), o_recs = take(recs.size() * 2),
+                     o_u = take((size_t)h->R * n_cells * 4);
+        hipError_t e = hipMalloc((void **)&P.arena, at);
+        if (e != hipSuccess) return fail(std::string("patterns: hipMalloc: ") + hipGetErrorString(e));
+        unsigned char *d = P.arena;
+        P.d_sets = (int32_t *)(d + o_sets); P.d_class = d + o_tab; P.d_recs = d + o_recs; P.u_cells = (int32_t *)(d + o_u);
+        e = hipMemcpy(P.d_sets, sets.data(), sets.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(P.d_class, tab.data(), tab.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !recs.empty()) e = hipMemcpy(P.d_recs, recs.data(), recs.size() * 2, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            smolmc_pat_free(P);
+            return fail(std::string("patterns upload: ") + hipGetErrorString(e));
+        }
+    }
+    TRY(smolmc_ring_forget(h, SMOLMC_SAMPLE_PATTERNS));
+    smolmc_pat_free(h->obs.pat);
+    h->obs.pat = P;
+    return 0;
+}
+
+extern "C" int smolmc_patterns_shape(smolmc_handle *h, int *n_sets, int *n_cells) {
+    if (!h) return fail("null handle");
+    if (n_sets) *n_sets = h->obs.pat.n_sets;
+    if (n_cells) *n_cells = (int)h->obs.pat.n_cells;
+    return 0;
+}
+
+extern "C" int smolmc_eval_patterns(smolmc_handle *h, const int32_t *occ, int nocc, int32_t *cells) {
+    if (!h) return fail("null handle");
+    const SmolmcPat &P = h->obs.pat;
+    if (!P.n_sets) return fail("no pattern spec set: call smolmc_set_patterns first");
+    HIPCHK(hipSetDevice(h->device));
+    const uint8_t *d_occ8;
+    size_t rows;
+    TRY(smolmc_eval_rows(h, occ, nocc, h->obs.kind_base, h->obs.K, "patterns", &d_occ8, &rows));
+    if (!rows) return 0;
+    DevScratch out;
+    TRY(out.alloc(std::max<size_t>(rows * P.n_cells * 4, 16)));
+    TRY(smolmc_obs_launch(h, d_occ8, rows, nullptr, nullptr, out.as<int32_t>()));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (cells) HIPCHK(hipMemcpy(cells, out.p, rows * P.n_cells * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int smolmc_get_sample_patterns(smolmc_handle *h, int32_t *cells) {
+    const SampleSlot *sl;
+    size_t rows;
+    TRY(smolmc_sample_block(h, SMOLMC_SAMPLE_PATTERNS, "the patterns were not recorded (flags bit 8)", &sl, &rows));
+    if (cells) smolmc_host_copy(cells, sl->hst + sl->o_pat, rows * h->obs.pat.n_cells * 4);
     return 0;
 }

@@ -783,6 +783,7 @@ struct SampleColumns {
     size_t o_cnt = 0, o_pair = 0;               // SMOLMC_SAMPLE_OBSERVABLES: kind counts [rows x K], pair counts [rows x cells]
     size_t o_amp = 0, o_inten = 0;              // SMOLMC_SAMPLE_STRUCTURE: amplitudes [rows x Q x K x 2] int64, intensities [rows x I]
     size_t o_conn = 0;                          // SMOLMC_SAMPLE_CONNECTIVITY: stats [rows x G x 24] int64
+    size_t o_pat = 0;                           // SMOLMC_SAMPLE_PATTERNS: pattern cells [rows x n_cells]
 };
 // One slot of the sample ring: `n` samples x R walkers recorded by one smolmc_run_sampled call.  Every array is a
 // range of ONE device arena and of ONE pinned host arena with the same offsets (a single asynchronous copy moves it).
@@ -811,6 +812,19 @@ struct SmolmcPopScratch {
     uint32_t *cnt, *sur, *drank;
 };
 
+// observables.hip: the pattern spec of a handle (smolmc_set_patterns) as the observables' kernel reads it, engine numbering
+struct SmolmcPat {
+    int n_sets = 0;            // (0: none set)
+    size_t n_cells = 0;        // sum over the sets of C^arity
+    int copies = 1;            // histograms of the pattern cells in LDS (one per wave, or one)
+    size_t lds = 0;            // dynamic LDS a launch takes on top of SmolmcObs::lds: the class buffer and the histograms
+    unsigned char *arena = nullptr; // one device allocation, cut into the arrays below
+    int32_t *d_sets = nullptr; // [n_sets x 8]: arity, classes, tuples, first cell, first record / 16 bytes, cells, new map, 0
+    uint8_t *d_class = nullptr; // [n_sets x 256]: the class of a kind, 0xff: skip (entry 255, "not counted", is 0xff)
+    unsigned char *d_recs = nullptr; // the tuples as u16 sites in records of 8 (arity <= 4) or 16 bytes, set after set
+    int32_t *u_cells = nullptr; // smolmc_update_statistics: cells [R x n_cells] of the walkers' current states
+};
+
 // observables.hip: the observables of a handle (smolmc_set_observables) as the kernel reads them, engine numbering
 struct SmolmcObs {
     int K = 0, n_shells = 0;   // (K == 0: none set)
@@ -821,6 +835,7 @@ struct SmolmcObs {
     int32_t *d_kind_base = nullptr;
     int64_t *d_shell_ptr = nullptr;
     uint32_t *d_bonds = nullptr; // one word per bond: i | j << 16
+    SmolmcPat pat;             // the pattern spec that rests on these kinds
 };
 
 // minima.hip: the minima record of a handle (smolmc_set_minima): the spec and one device arena cut into the entry arrays
@@ -859,6 +874,8 @@ struct SmolmcStat {
     int n_inten_cols = 0;      // columns that read the intensities
     int CS = 0;                // 24 x the graphs of the connectivity spec in force when the record was set
     int n_conn_cols = 0;       // columns that read the connectivity stats
+    int PC = 0;                // the cells of the pattern spec in force when the record was set
+    int n_pat_cols = 0;        // columns that read the pattern cells
     double hist_min = 0.0, hist_bin = 1.0;
     unsigned char *arena = nullptr;
     size_t record_bytes = 0;   // from n to the end of the accumulator arrays: what a reset zeroes
@@ -1136,8 +1153,9 @@ int smolmc_pop_clone_launch(smolmc_handle *h, const int32_t *parent, int npop, c
 // observables.hip: kind counts [rows x K] and pair counts [rows x n_shells x K x K] of `rows` occupancy rows (Npad bytes
 // apart, device) into device arrays, queued on the handle's stream; the LDS a launch takes and the number of pair
 // histograms it keeps there
-// (d_pairs == nullptr: the kind counts only)
-int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs);
+// (d_pairs == nullptr: no pair counts; d_cells: the cells [rows x n_cells] of the pattern spec or null; d_counts may be
+// null when only the patterns are wanted)
+int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs, int32_t *d_cells);
 // minima.hip: offer `rows` = nsamples x R rows (enthalpy [rows], features [rows x F], occupancy rows Npad bytes apart,
 // counts [rows x K] or null; device) to the handle's record, three kernels queued on the handle's stream; d_key [rows]
 // and d_slot [rows] are scratch.  Row s * R + r is offer number offers + s of walker r, taken thin_by steps before row
@@ -1149,9 +1167,10 @@ void smolmc_min_free(smolmc_handle *h);
 // null; device) to the handle's record, one kernel queued on the handle's stream: a workgroup per key walks the samples in
 // order.  Sample s gives key k the row s * R + w, w the walker that holds k when the kernel runs.
 // (d_inten: intensities [rows x I] or null, read by a record with intensity columns; d_conn: connectivity stats
-// [rows x G x 24] or null, read by a record with connectivity columns)
+// [rows x G x 24] or null, read by a record with connectivity columns; d_pat: pattern cells [rows x n_cells] or null, read
+// by a record with pattern columns)
 int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, const double *d_inten,
-                       const long long *d_conn, long long nsamples);
+                       const long long *d_conn, const int32_t *d_pat, long long nsamples);
 void smolmc_stat_free(smolmc_handle *h);
 // structure.hip: amplitudes [rows x Q x K x 2] and intensities [rows x I] of `rows` occupancy rows (Npad bytes apart,
 // device) into device arrays, queued on the handle's stream; the kernel a spec takes and the layout of its LDS (false:
@@ -1167,6 +1186,8 @@ size_t smolmc_conn_lds_bytes(int N, int Npad);
 void smolmc_conn_free(SmolmcConn &S);
 size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies);
 int smolmc_obs_pair_copies(size_t cells);
+size_t smolmc_pat_lds_bytes(int Npad, size_t n_cells, int copies);
+void smolmc_pat_free(SmolmcPat &P);
 void smolmc_obs_free(SmolmcObs &O);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);
 int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);

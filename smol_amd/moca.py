@@ -1526,6 +1526,21 @@ class SampleContainer:
         wc = warren_cowley(self._select("species_counts", discard, thin_by), self._select("pair_counts", discard, thin_by))
         return wc.reshape((wc.shape[0] * wc.shape[1],) + wc.shape[2:]) if flat else wc
 
+    def get_pattern_counts(self, discard=0, thin_by=1, flat=True):
+        """The ``pattern_counts`` trace: (..., n_cells) int32 cells of every sample, tuples as listed; the metadata's
+        ``patterns`` entry says where every set's cells start (``cell_ptr``) and what its classes are."""
+        if "pattern_counts" not in self._schema:
+            raise ValueError("these samples carry no pattern_counts trace: sample with Sampler.from_ensemble(patterns=)")
+        return self.get_trace_value("pattern_counts", discard, thin_by, flat)
+
+    def pattern_probabilities(self, discard=0, thin_by=1, flat=True):
+        """Pattern probabilities of every sample, (..., n_cells): every set's cells over their sum
+        (``patterns.probabilities``)."""
+        from .patterns import probabilities
+
+        cells = self.get_pattern_counts(discard, thin_by, flat)
+        return probabilities(cells, [int(x) for x in self.metadata["patterns"]["cell_ptr"]])
+
     def get_species_counts(self, discard=0, thin_by=1, flat=True):
         """Counts per species name summed over the sublattices that host it (container.py:336-347)."""
         out = {}
@@ -1594,6 +1609,12 @@ class SampleContainer:
                           "meta/conn_n_bonds": np.asarray(conn["n_bonds"], dtype=np.int64),
                           "meta/conn_member_ptr": np.cumsum([0] + [len(m) for m in members]).astype(np.int64),
                           "meta/conn_members": np.asarray([k for m in members for k in m], dtype=np.int32)})
+        pat = self.metadata.get("patterns")
+        if pat is not None:  # the sets of the pattern_counts trace: their shapes and class maps
+            extra.update({"meta/pat_shape": np.asarray([pat["arity"], pat["n_classes"], pat["n_tuples"]], dtype=np.int64),
+                          "meta/pat_cell_ptr": np.asarray(pat["cell_ptr"], dtype=np.int64),
+                          "meta/pat_class_of_kind": np.asarray(pat["class_of_kind"], dtype=np.int32),
+                          "meta/pat_orbit_ids": np.asarray(pat["set_orbit_ids"] if pat["set_orbit_ids"] is not None else [], dtype=np.int64)})
         rec = self.minima
         if rec is not None:  # the minima record: its arrays, the spec and the two counters
             spec = rec.spec
@@ -1723,6 +1744,12 @@ class SampleContainer:
             c.metadata["connectivity"] = dict(n_graphs=int(d["meta/conn_shape"][0]), n_kinds=int(d["meta/conn_shape"][1]),
                                               members=[flat[int(a):int(b)] for a, b in zip(ptr[:-1], ptr[1:])],
                                               n_bonds=d["meta/conn_n_bonds"].tolist())
+        if "meta/pat_shape" in d.files:
+            arity, ncls, ntup = (d["meta/pat_shape"][i].tolist() for i in range(3))
+            ptr, ids = d["meta/pat_cell_ptr"].tolist(), d["meta/pat_orbit_ids"].tolist()
+            c.metadata["patterns"] = dict(n_sets=len(arity), n_cells=int(ptr[-1]), arity=arity, n_classes=ncls, n_tuples=ntup,
+                                          cell_ptr=ptr, class_of_kind=d["meta/pat_class_of_kind"].tolist(),
+                                          set_orbit_ids=ids if ids else None)
         if "meta/minima_shape" in d.files:
             offers, nw, n_weights, n_axes = (int(x) for x in d["meta/minima_shape"])
             rec = {f: d[f"meta/minima_{f}"] for f in ("value", "enthalpy", "features", "occupancy", "counts", "walker", "sample", "step")}
@@ -1870,12 +1897,13 @@ class Sampler:
         self._statistics = None     # statistics.Statistics: moments, blocking sums and a histogram kept on the device, or None
         self._structure = None      # structure.StructureFactor evaluated on the device for every sample, or None
         self._connectivity = None   # connectivity.Connectivity evaluated on the device for every sample, or None
+        self._patterns = None       # patterns.Patterns counted on the device for every sample, or None
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
                       nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, windows=None,
                       observables=None, minima=None, statistics=None, structure_factor=None, connectivity=None,
-                      **kwargs):
+                      patterns=None, **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
         'swap'; default kernel Metropolis; one kernel (seed) per walker.
 
@@ -1899,7 +1927,11 @@ class Sampler:
 
         ``connectivity``: a ``connectivity.Connectivity`` -- the components of its graphs are labelled on the device for every
         sample and their 24 numbers per graph traced as ``connectivity`` (G, 24) int64; connectivity columns of a
-        statistics record need it."""
+        statistics record need it.
+
+        ``patterns``: a ``patterns.Patterns`` on the ``observables`` given here -- the species patterns on its site tuples
+        are counted on the device for every sample, by the launch that counts the observables, and traced as
+        ``pattern_counts`` (n_cells,) int32; pattern columns of a statistics record need it."""
         from . import parallel
 
         if windows is not None and observables is not None:
@@ -1908,6 +1940,10 @@ class Sampler:
             raise ValueError("structure_factor= with windows=: the samples of per-walker windows do not come from the sample ring")
         if windows is not None and connectivity is not None:
             raise ValueError("connectivity= with windows=: the samples of per-walker windows do not come from the sample ring")
+        if windows is not None and patterns is not None:
+            raise ValueError("patterns= with windows=: the samples of per-walker windows do not come from the sample ring")
+        if patterns is not None and observables is None:
+            raise ValueError("patterns= needs observables=: the class maps of a pattern spec index the kinds of the observables")
         if windows is not None:
             sampler = cls._from_ensemble_windows(ensemble, windows, *args, step_type=step_type, kernel_type=kernel_type, seeds=seeds,
                                                  nwalkers=nwalkers, rank=rank, world_size=world_size, device=device, **kwargs)
@@ -1944,6 +1980,8 @@ class Sampler:
             sampler._set_structure_factor(structure_factor)
         if connectivity is not None:
             sampler._set_connectivity(connectivity)
+        if patterns is not None:
+            sampler._set_patterns(patterns)
         if minima is not None:
             sampler._set_minima(minima)
         if statistics is not None:
@@ -1957,6 +1995,8 @@ class Sampler:
             raise ValueError("a statistics record with intensity columns needs a sampler built with structure_factor=")
         if spec.connectivity_columns() and self._connectivity is None:
             raise ValueError("a statistics record with connectivity columns needs a sampler built with connectivity=")
+        if spec.pattern_columns() and self._patterns is None:
+            raise ValueError("a statistics record with pattern columns needs a sampler built with patterns=")
         self._statistics = spec
         if self._engine is not None:
             self._engine.set_statistics(spec)
@@ -2061,6 +2101,22 @@ class Sampler:
         self._connectivity = spec
         if self._engine is not None:
             self._engine.set_connectivity(spec)
+
+    def _set_patterns(self, spec):
+        """Trace ``spec`` with every sample: the container's schema gains the trace, its metadata the sets' shapes and
+        class maps."""
+        nw, N = self.samples.shape
+        if spec.num_sites != N:
+            raise ValueError(f"the pattern spec is defined on {spec.num_sites} sites, the ensemble has {N}")
+        if self._observables is None or spec.n_kinds != self._observables.n_kinds:
+            raise ValueError("the pattern spec must rest on the sampler's observables: its class maps index their kinds")
+        if self.samples.num_samples:
+            raise ValueError("the container holds samples without the pattern_counts trace: clear_samples() first")
+        self.samples._schema["pattern_counts"] = (np.dtype(np.int32), (nw, spec.n_cells))
+        self.samples.metadata["patterns"] = spec.describe()
+        self._patterns = spec
+        if self._engine is not None:
+            self._engine.set_patterns(spec)
 
     @classmethod
     def _from_ensemble_windows(cls, ensemble, wx, *args, step_type=None, kernel_type=None, seeds=None, nwalkers=1, rank=None,
@@ -2264,6 +2320,8 @@ class Sampler:
             self._engine = Engine(tables, cfg, distance=dist)
             if self._observables is not None:
                 self._engine.set_observables(self._observables)
+            if self._patterns is not None:  # (behind the observables it rests on, before the statistics record)
+                self._engine.set_patterns(self._patterns)
             if self._minima is not None:  # (a new handle starts an empty record)
                 self._engine.set_minima(self._minima)
                 self._minima_offers = 0
@@ -2353,6 +2411,8 @@ class Sampler:
             tr.structure_amplitudes, tr.structure_intensities = eng.structure_factor()
         if self._connectivity is not None:
             tr.connectivity = eng.connectivity()
+        if self._patterns is not None:
+            tr.pattern_counts = eng.patterns()
         return tr
 
     def _sample_blocks(self, nsteps, initial_occupancies, thin_by, max_block=0, state_loaded=False, keep_occupancy=True):
@@ -2410,6 +2470,9 @@ class Sampler:
         cn = self._connectivity
         if cn is not None:
             per_sample += nw * 8 * 24 * cn.n_graphs
+        pt = self._patterns
+        if pt is not None:
+            per_sample += nw * 4 * pt.n_cells
         if is_wl:
             L = len(k0._levels)
             per_sample += nw * L * (24 + 8 * F)
@@ -2426,7 +2489,7 @@ class Sampler:
         def queue(n):
             eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl, observables=obs is not None,
                                   minima=self._minima is not None, statistics=self._statistics is not None,
-                                  structure=sf is not None, connectivity=cn is not None)
+                                  structure=sf is not None, connectivity=cn is not None, patterns=pt is not None)
             if self._minima is not None:
                 self._minima_offers += n
 
@@ -2473,6 +2536,8 @@ class Sampler:
                 block.update(structure_amplitudes=ring["structure_amplitudes"], structure_intensities=ring["structure_intensities"])
             if "connectivity" in ring:
                 block.update(connectivity=ring["connectivity"])
+            if "pattern_counts" in ring:
+                block.update(pattern_counts=ring["pattern_counts"])
             yield block
 
     def _wl_run_with_host_checks(self, eng, nsteps):

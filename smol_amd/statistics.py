@@ -62,6 +62,14 @@ def connectivity(g, column):
     return ("connectivity", int(g), int(column))
 
 
+def pattern(c):
+    """Cell ``c`` of the pattern spec in force (``patterns.Patterns``; ``Patterns.cell`` gives the number of a pattern), read
+    as a double."""
+    if int(c) < 0:
+        raise ValueError(f"pattern cell {c} is negative")
+    return ("pattern", int(c))
+
+
 def kind(observables, name_or_k):
     """Count column of kind ``name_or_k`` of ``observables`` (an ``observables.Observables``): a kind number, or a name
     looked up in ``observables.kind_names`` when it has them."""
@@ -109,11 +117,11 @@ class Statistics:
     n_weights = property(lambda self: 0 if self.weights is None else len(self.weights))
     n_pairs = property(lambda self: self.n_columns * (self.n_columns + 1) // 2)
 
-    def sources(self, n_features, n_kinds, n_intensities=0, n_graphs=0):
+    def sources(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0):
         """int32 column sources of the C ABI: 0 enthalpy, 1 + i feature i, 1 + F + k kind k, 1 + F + K the weighted sum,
         2 + F + K + i intensity i (i < ``n_intensities``), 2 + F + K + I + 24 g + c number c of graph g of the connectivity
-        spec (g < ``n_graphs``)."""
-        F, K, I, G = int(n_features), int(n_kinds), int(n_intensities), int(n_graphs)
+        spec (g < ``n_graphs``), 2 + F + K + I + 24 G + c cell c of the pattern spec (c < ``n_cells``)."""
+        F, K, I, G, PC = int(n_features), int(n_kinds), int(n_intensities), int(n_graphs), int(n_cells)
         out = []
         for c in self.columns:
             if c[0] == "enthalpy":
@@ -132,6 +140,10 @@ class Statistics:
                 if not 0 <= c[1] < G:
                     raise ValueError(f"graph {c[1]} outside the {G} graphs of the connectivity spec")
                 out.append(2 + F + K + I + 24 * c[1] + c[2])
+            elif c[0] == "pattern":
+                if not 0 <= c[1] < PC:
+                    raise ValueError(f"cell {c[1]} outside the {PC} cells of the pattern spec")
+                out.append(2 + F + K + I + 24 * G + c[1])
             else:
                 out.append(c[1])
         return np.asarray(out, dtype=np.int32)
@@ -148,17 +160,22 @@ class Statistics:
         """Indices into ``columns`` of the connectivity numbers, in order."""
         return [i for i, c in enumerate(self.columns) if c[0] == "connectivity"]
 
-    def column_values(self, enthalpy, features, counts=None, intensities=None, connectivity=None):
+    def pattern_columns(self):
+        """Indices into ``columns`` of the pattern cells, in order."""
+        return [i for i, c in enumerate(self.columns) if c[0] == "pattern"]
+
+    def column_values(self, enthalpy, features, counts=None, intensities=None, connectivity=None, patterns=None):
         """x (..., C) float64 of rows with enthalpy (...), features (..., F), counts (..., K) or None, intensities
-        (..., I) or None, connectivity stats (..., G, 24) or None."""
+        (..., I) or None, connectivity stats (..., G, 24) or None, pattern cells (..., n_cells) or None."""
         H = np.asarray(enthalpy, dtype=np.float64)
         f = np.asarray(features, dtype=np.float64).reshape(H.shape + (-1,))
         F = f.shape[-1]
         K = 0 if counts is None else np.asarray(counts).shape[-1]
         I = 0 if intensities is None else np.asarray(intensities).shape[-1]
         G = 0 if connectivity is None else np.asarray(connectivity).shape[-2]
+        PC = 0 if patterns is None else np.asarray(patterns).shape[-1]
         x = np.empty(H.shape + (self.n_columns,))
-        for j, src in enumerate(self.sources(F, K, I, G)):
+        for j, src in enumerate(self.sources(F, K, I, G, PC)):
             if src == 0:
                 x[..., j] = H
             elif src <= F:
@@ -171,15 +188,17 @@ class Statistics:
                 x[..., j] = np.asarray(intensities, dtype=np.float64).reshape(H.shape + (I,))[..., src - 2 - F - K]
             elif src <= 1 + F + K + I + 24 * G:
                 x[..., j] = np.asarray(connectivity).reshape(H.shape + (24 * G,))[..., src - 2 - F - K - I].astype(np.float64)
+            elif src <= 1 + F + K + I + 24 * G + PC:
+                x[..., j] = np.asarray(patterns).reshape(H.shape + (PC,))[..., src - 2 - F - K - I - 24 * G].astype(np.float64)
             else:
-                raise ValueError(f"column source {src} outside 0..{1 + F + K + I + 24 * G}")
+                raise ValueError(f"column source {src} outside 0..{1 + F + K + I + 24 * G + PC}")
         return x
 
-    def c_struct(self, n_features, n_kinds, n_intensities=0, n_graphs=0):
+    def c_struct(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0):
         """(capi.smolmc_statistics, the arrays it points to)."""
         from . import capi
 
-        cols = self.sources(n_features, n_kinds, n_intensities, n_graphs)
+        cols = self.sources(n_features, n_kinds, n_intensities, n_graphs, n_cells)
         keep = (cols, self.weights)
         s = capi.smolmc_statistics(
             self.key, len(cols), cols.ctypes.data_as(C.POINTER(C.c_int32)) if len(cols) else None, self.n_weights,
@@ -217,7 +236,7 @@ class StatisticsRecord:
     n_keys = property(lambda self: len(self.n))
 
     # ---- the definition ------------------------------------------------------------------------------------------
-    def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None, connectivity=None):
+    def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None, connectivity=None, patterns=None):
         """Offer samples (ns, R) -- or one sample (R,) -- in order.  ``key_of_row`` (R,) or (ns, R): the key of every
         row, a permutation of 0 .. R - 1 per sample (None: the walker).  Vectorised over the keys, a loop over samples."""
         spec = self.spec
@@ -228,7 +247,8 @@ class StatisticsRecord:
         cnt = None if counts is None else np.asarray(counts).reshape(ns, nk, -1)
         inten = None if intensities is None else np.asarray(intensities, dtype=np.float64).reshape(ns, nk, -1)
         conn = None if connectivity is None else np.asarray(connectivity).reshape(ns, nk, -1, 24)
-        x_all = spec.column_values(H, f, cnt, inten, conn)
+        pat = None if patterns is None else np.asarray(patterns).reshape(ns, nk, -1)
+        x_all = spec.column_values(H, f, cnt, inten, conn, pat)
         if key_of_row is None:
             keys = np.broadcast_to(np.arange(nk), (ns, nk))
         else:
