@@ -639,8 +639,36 @@ typedef struct smolmc_connectivity {
  * recorded with SMOLMC_SAMPLE_CONNECTIVITY waits in the ring; while a statistics record with connectivity columns is set.
  * A refused call leaves the handle's spec as it was. */
 int smolmc_set_connectivity(smolmc_handle *h, const smolmc_connectivity *s);
+/* Gated bonds.  Bond row b (counted over all graphs, b < nb = bond_ptr[G]) may carry 0..SMOLMC_MAX_CONN_GATES gate sites
+ * gate_sites[gate_ptr[b] .. gate_ptr[b + 1]], caller's site numbers; an occupancy is periodic, so a gate site has no image.
+ * A gate site is blocked when its kind is not in the 256-bit row gate_mask[g] of the row's graph; a site listed twice in a
+ * row counts twice.  A row is open when both ends are members and at most max_blocked[g] of its gate sites are blocked; a
+ * row without gate sites is open whenever both ends are members.  The adjacency (i, j, w) with its reverse (j, i, -w) is
+ * active when at least one row that lists it, in either direction, is open: components, winding sets, the 24 numbers and
+ * the labels are those of the active adjacencies.  (The 0-TM channels of a disordered rocksalt: the rows of a Li-Li bond
+ * are its two tetrahedra, the gate sites the two other corners, gate_mask the kinds that are no transition metal,
+ * max_blocked = 0.)  A graph none of whose rows has a gate site is ungated: its results and its path through the kernel
+ * are those of smolmc_set_connectivity.  smolmc_set_connectivity(h, s) is smolmc_set_connectivity_gated(h, s, NULL).
+ * Refused besides what smolmc_set_connectivity refuses, each naming its reason and leaving the spec as it was: a gate site
+ * out of range or with kind_base < 0; more than SMOLMC_MAX_CONN_GATES gates on a row; gate_ptr not starting at 0 or
+ * decreasing; a gate kind >= n_kinds; max_blocked outside 0..SMOLMC_MAX_CONN_GATES; a gated graph in which a site has more
+ * than SMOLMC_MAX_CONN_GATED_NEIGHBOURS distinct (neighbour, image) entries; a row whose open bits (one per entry, four
+ * entries to a group) do not fit the LDS of one workgroup next to the rest (rows of 4096 sites with the 12 neighbours and
+ * two tetrahedra a bond of fcc fit). */
+#define SMOLMC_MAX_CONN_GATES 4
+#define SMOLMC_MAX_CONN_GATED_NEIGHBOURS 64
+typedef struct smolmc_conn_gates {
+    const uint64_t *gate_mask;    /* [G x 4], bit k: a gate site of kind k does not block */
+    const int32_t *max_blocked;   /* [G], 0..SMOLMC_MAX_CONN_GATES */
+    const int64_t *gate_ptr;      /* [nb + 1], nb = bond_ptr[G]: the gate sites of bond row b */
+    const int32_t *gate_sites;    /* [gate_ptr[nb]], caller's site numbers */
+} smolmc_conn_gates;
+int smolmc_set_connectivity_gated(smolmc_handle *h, const smolmc_connectivity *s, const smolmc_conn_gates *g);
 /* G and K in force (both 0: none set) */
 int smolmc_connectivity_shape(smolmc_handle *h, int *n_graphs, int *n_kinds);
+/* bit g of gated_graph_mask: graph g of the spec in force has a gate site; n_channels: the channel records the kernel
+ * walks, summed over the neighbour-list entries of the gated graphs (both 0: an ungated spec, or none).  Either may be NULL. */
+int smolmc_connectivity_gates(smolmc_handle *h, int *gated_graph_mask, int64_t *n_channels);
 /* stats [nocc x G x 24] and labels [nocc x G x N] of nocc occupancies (host, int32 like smolmc_eval_full), or, with
  * occ == NULL, of the walkers' current states (nocc = R then).  Either output may be NULL. */
 int smolmc_eval_connectivity(smolmc_handle *h, const int32_t *occ /* nocc x N, or NULL */, int nocc, int64_t *stats, int32_t *labels);

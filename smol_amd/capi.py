@@ -61,14 +61,23 @@ MAX_CONN_PATH_SUM = 32767       # SMOLMC_MAX_CONN_PATH_SUM: n_sites x MAX_CONN_I
 CONN_STATS = 24                 # SMOLMC_CONN_STATS
 CONN_WAVES = 4                  # the waves of one workgroup of the connectivity kernel
 CONN_LDS_BYTES = 65536          # the LDS of one workgroup of the connectivity kernel (connectivity.hip)
+MAX_CONN_GATES = 4              # SMOLMC_MAX_CONN_GATES: gate sites of a bond row
+MAX_CONN_GATED_NEIGHBOURS = 64  # the longest neighbour list of a site in a gated graph: 8 bytes of open bits a site
 
 
-def connectivity_lds_bytes(n_sites, npad):
+def connectivity_open_bytes(n_neighbours):
+    """The bytes of open bits a site takes in a gated graph whose longest neighbour list has ``n_neighbours`` entries (four
+    to a group, a bit an entry)."""
+    return (4 * ((n_neighbours + 3) // 4) + 7) // 8
+
+
+def connectivity_lds_bytes(n_sites, npad, open_bytes=0):
     """The LDS a row of ``n_sites`` sites in ``npad`` bytes takes in the connectivity kernel (smolmc_conn_lds_bytes in
-    csrc/connectivity.hip): a 64-bit word, a 16-bit size and a mask byte per site next to the row, and the partial sums of
-    four waves; None when that is more than one workgroup has."""
+    csrc/connectivity.hip): a 64-bit word, a 16-bit size and a mask byte per site next to the row, the partial sums of
+    four waves and, for a spec with a gated graph, ``open_bytes`` of open bits per site (the most a gated graph of the spec
+    needs); None when that is more than one workgroup has."""
     up4 = lambda v: (v + 3) // 4 * 4  # noqa: E731
-    b = 8 * n_sites + npad + up4(2 * n_sites) + up4(n_sites) + (CONN_WAVES * CONN_STATS + 4) * 4
+    b = 8 * n_sites + npad + up4(2 * n_sites) + up4(n_sites) + (CONN_WAVES * CONN_STATS + 4) * 4 + up4(open_bytes * n_sites)
     return b if b <= CONN_LDS_BYTES else None
 SAMPLE_PATTERNS = 256           # ... the pattern cells of every row (smolmc_set_patterns)
 MAX_PATTERN_SETS = 8            # SMOLMC_MAX_PATTERN_SETS
@@ -235,6 +244,17 @@ class smolmc_connectivity(C.Structure):
         ("bond_ptr", _i64p),
         ("bonds", _i32p),
         ("images", C.POINTER(C.c_int8)),
+    ]
+
+
+class smolmc_conn_gates(C.Structure):
+    """Mirror of ``smolmc_conn_gates`` (include/smolmc.h); ``connectivity.Connectivity.c_gates`` fills it."""
+
+    _fields_ = [
+        ("gate_mask", C.POINTER(C.c_uint64)),
+        ("max_blocked", _i32p),
+        ("gate_ptr", _i64p),
+        ("gate_sites", _i32p),
     ]
 
 

@@ -11,6 +11,14 @@ displaced by ``w[0] S_0 + w[1] S_1 + w[2] S_2``, ``S_a`` the supercell vectors. 
 members.  Duplicate rows, rows ``i == j`` with ``w != 0`` (a site bonded to its own image, in aliased cells) and two rows
 joining the same sites by different images mean what they say.
 
+A bond row may carry 0..4 *gate sites* (``Graph(gates=...)``, caller's site numbers; an occupancy is periodic, so a gate
+site has no image).  A gate site is *blocked* when its kind is not in the graph's ``gate_kinds``; a site listed twice in a
+row counts twice.  A row is *open* when both ends are members and at most ``max_blocked`` of its gate sites are blocked; a
+row without gate sites is open whenever both ends are members.  The adjacency ``(i, j, w)`` with its reverse
+``(j, i, -w)`` is active when at least one row that lists it, in either direction, is open: the two tetrahedra of an fcc
+nearest-neighbour bond are two rows of the same bond with different gates (the 0-TM channels of a disordered rocksalt,
+``max_blocked = 0``).  A graph none of whose rows has a gate site is *ungated*.
+
 *Components* are the connected components of the members under the active bonds.  The *winding set* of a component is
 the set of image sums over its closed paths, a subgroup of Z^3; the component *wraps axis a* when an element of the set
 has a nonzero entry a.  However it is computed: give every site the image sum ``off`` along some path from one site of the
@@ -31,6 +39,7 @@ from .observables import MAX_KINDS, Observables
 
 MAX_GRAPHS = 8        # SMOLMC_MAX_CONN_GRAPHS
 MAX_IMAGE = 7         # SMOLMC_MAX_CONN_IMAGE: |w_a| of a bond
+MAX_GATES = 4         # SMOLMC_MAX_CONN_GATES: gate sites of a bond row
 MAX_PATH_SUM = 32767  # the device keeps a path sum per axis in 16 bits: N x MAX_IMAGE must stay at or below this
 N_STATS = 24          # SMOLMC_CONN_STATS
 SITE_TOL = 1e-6       # two distances (in units of the lattice's length) are the same within this
@@ -41,9 +50,11 @@ N_HIST = 16           # HIST0 + b: components with floor(log2 size) == b
 
 
 class Graph:
-    """One graph: ``members`` kinds, ``bonds`` (nb, 2) site pairs and ``images`` (nb, 3) of each bond."""
+    """One graph: ``members`` kinds, ``bonds`` (nb, 2) site pairs and ``images`` (nb, 3) of each bond; optionally
+    ``gates`` (nb, m <= 4) gate sites of each bond row (-1: none; or a list of lists), the ``gate_kinds`` that do not block
+    and ``max_blocked``, the blocked gate sites an open row may have."""
 
-    def __init__(self, members, bonds, images=None):
+    def __init__(self, members, bonds, images=None, gates=None, gate_kinds=(), max_blocked=0):
         self.members = sorted({int(k) for k in members})
         b = np.asarray(bonds)
         if b.size == 0:
@@ -59,6 +70,38 @@ class Graph:
             raise ValueError(f"a bond's image reaches {int(np.abs(w).max())}, beyond MAX_IMAGE = {MAX_IMAGE}: image out of range")
         self.bonds = np.ascontiguousarray(b, dtype=np.int32)
         self.images = np.ascontiguousarray(w, dtype=np.int8)
+        self.gates = np.full((len(b), 0), -1, dtype=np.int32) if gates is None else _gate_array(gates, len(b))
+        self.gate_kinds = sorted({int(k) for k in gate_kinds})
+        self.max_blocked = int(max_blocked)
+        if not 0 <= self.max_blocked <= MAX_GATES:
+            raise ValueError(f"max_blocked must be 0..{MAX_GATES}, got {self.max_blocked}: max_blocked out of range")
+
+    @property
+    def gated(self):
+        """A row of the graph has a gate site."""
+        return bool((self.gates >= 0).any())
+
+    def gate_lists(self):
+        """(gate_ptr (nb + 1,) int64, gate_sites int32): the gate sites of row b are gate_sites[gate_ptr[b]:gate_ptr[b + 1]]."""
+        has = self.gates >= 0
+        ptr = np.concatenate(([0], np.cumsum(has.sum(axis=1)))).astype(np.int64)
+        return ptr, np.ascontiguousarray(self.gates[has], dtype=np.int32)
+
+
+def _gate_array(gates, nb):
+    """(nb, m) int32, -1 for no gate, of an integer array or a list of lists (rows of different lengths)."""
+    if not isinstance(gates, np.ndarray):
+        rows = [list(r) for r in gates]
+        m = max((len(r) for r in rows), default=0)
+        if m > MAX_GATES:
+            raise ValueError(f"a bond row has {m} gate sites, SMOLMC_MAX_CONN_GATES = {MAX_GATES}: too many gates on a row")
+        gates = np.array([r + [-1] * (m - len(r)) for r in rows], dtype=np.int64).reshape(len(rows), m)
+    g = np.asarray(gates)
+    if g.ndim != 2 or len(g) != nb or (g.size and not np.issubdtype(g.dtype, np.integer)):
+        raise ValueError("gates must be an (nbonds, m) integer array or a list of one list per bond row")
+    if g.shape[1] > MAX_GATES:
+        raise ValueError(f"a bond row has {g.shape[1]} gate sites, SMOLMC_MAX_CONN_GATES = {MAX_GATES}: too many gates on a row")
+    return np.ascontiguousarray(np.where(g < 0, -1, g), dtype=np.int32)
 
 
 class Connectivity:
@@ -66,7 +109,8 @@ class Connectivity:
 
     kind_base    (N,) integers, -1 = the site is in no graph
     n_kinds      K
-    graphs       1..8 ``Graph`` objects, or dicts / tuples of their arguments (members, bonds, images)
+    graphs       1..8 ``Graph`` objects, or dicts / tuples of their arguments (members, bonds, images[, gates, gate_kinds,
+                 max_blocked])
     site_ncodes  optional (N,): species codes each site can hold; with it every kind is checked to stay below K
     """
 
@@ -86,7 +130,7 @@ class Connectivity:
         self.graphs = []
         for g in graphs:
             if isinstance(g, dict):
-                g = Graph(g["members"], g["bonds"], g.get("images"))
+                g = Graph(g["members"], g["bonds"], g.get("images"), g.get("gates"), g.get("gate_kinds", ()), g.get("max_blocked", 0))
             elif not isinstance(g, Graph):
                 g = Graph(*g)
             self.graphs.append(g)
@@ -99,6 +143,15 @@ class Connectivity:
                                  f"n_kinds is {K}: kind out of range")
             if g.bonds.min(initial=0) < 0 or g.bonds.max(initial=0) >= N:
                 raise ValueError(f"graph {gi}: bond out of range ({N} sites)")
+            if g.gates.max(initial=-1) >= N:
+                raise ValueError(f"graph {gi}: gate site {int(g.gates.max())}, {N} sites: gate site out of range")
+            used = g.gates[g.gates >= 0]
+            if used.size and self.kind_base[used].min() < 0:
+                s = int(used[np.argmin(self.kind_base[used])])
+                raise ValueError(f"graph {gi}: gate site {s} has kind_base -1: a gate site must be a counted site")
+            if g.gate_kinds and not 0 <= min(g.gate_kinds) <= max(g.gate_kinds) < K:
+                raise ValueError(f"graph {gi}: gate kind {max(g.gate_kinds) if max(g.gate_kinds) >= K else min(g.gate_kinds)}, "
+                                 f"n_kinds is {K}: kind out of range")
         self.site_ncodes = None
         if site_ncodes is not None:
             nc = np.asarray(site_ncodes, dtype=np.int64)
@@ -139,9 +192,10 @@ class Connectivity:
         species = getattr(prim, "species", None)
         site_b = np.asarray(sc.site_b, dtype=np.int64)
         made = []
-        for gi, g in enumerate(graphs):
-            members = set()
-            for m in g["members"]:
+
+        def kinds_named(gi, listed):
+            kinds = set()
+            for m in listed:
                 if isinstance(m, str):
                     hits = set()
                     for s in range(sc.num_sites):
@@ -150,9 +204,13 @@ class Connectivity:
                             hits.add(int(kind_base[s]) + list(names).index(m))
                     if not hits:
                         raise ValueError(f"graph {gi}: no counted site holds a species named {m!r}")
-                    members |= hits
+                    kinds |= hits
                 else:
-                    members.add(int(m))
+                    kinds.add(int(m))
+            return kinds
+
+        for gi, g in enumerate(graphs):
+            members = kinds_named(gi, g["members"])
             if ("cutoff" in g) == ("orbits" in g):
                 raise ValueError(f"graph {gi}: give cutoff= or orbits=, one of them")
             if "cutoff" in g:
@@ -167,7 +225,15 @@ class Connectivity:
                 if len(want) != len(set(g["orbits"])):
                     raise ValueError(f"graph {gi}: orbits {sorted(g['orbits'])} are not all orbits of the model")
                 bonds, images = geometric_bonds(sc, distances=want)
-            made.append(Graph(members, bonds, images))
+            gate = g.get("gate")
+            if gate is None:
+                made.append(Graph(members, bonds, images))
+                continue
+            unknown = set(gate) - {"kinds", "corners", "max_blocked"}
+            if unknown or "kinds" not in gate:
+                raise ValueError(f"graph {gi}: gate=dict(kinds=..., corners=1|2, max_blocked=0), got the keys {sorted(gate)}")
+            bonds, images, gates = channel_rows(bonds, images, corners=int(gate.get("corners", 2)))
+            made.append(Graph(members, bonds, images, gates, kinds_named(gi, gate["kinds"]), int(gate.get("max_blocked", 0))))
         return cls(kind_base, K, made, site_ncodes=ncodes)
 
     # ---- the definition ------------------------------------------------------------------------------------------
@@ -182,21 +248,46 @@ class Connectivity:
         return kinds
 
     def _neighbours(self):
-        """Per graph, per site: the list of (neighbour, image as seen from the site) over the bonds, both ways."""
+        """Per graph, per site: the list of (neighbour, image as seen from the site, adjacency) over the bonds, both ways;
+        and per graph the adjacency of every bond row.  An *adjacency* is a number shared by the rows that list
+        ``(i, j, w)`` or its reverse ``(j, i, -w)``: what the gates of a gated graph open or close together."""
         if self._adjacency is None:
-            self._adjacency = []
+            self._adjacency, self._row_adjacency = [], []
             for g in self.graphs:
                 adj = [[] for _ in range(self.num_sites)]
+                ids, of_row = {}, []
                 for (i, j), w in zip(g.bonds.tolist(), g.images.tolist()):
-                    adj[i].append((j, w[0], w[1], w[2]))
-                    adj[j].append((i, -w[0], -w[1], -w[2]))
+                    fwd, back = (i, j, w[0], w[1], w[2]), (j, i, -w[0], -w[1], -w[2])
+                    a = ids.setdefault(min(fwd, back), len(ids))
+                    of_row.append(a)
+                    adj[i].append((j, w[0], w[1], w[2], a))
+                    adj[j].append((i, -w[0], -w[1], -w[2], a))
                 self._adjacency.append(adj)
+                self._row_adjacency.append((np.asarray(of_row, dtype=np.int64), len(ids)))
         return self._adjacency
+
+    def open_rows(self, occupancies, g):
+        """(..., nb_g) bool: the bond rows of graph ``g`` that are open in occupancies (..., N) -- both ends members and at
+        most ``max_blocked`` of the row's gate sites blocked, a site listed twice counted twice."""
+        kinds = self.kinds_of(occupancies)
+        gr = self.graphs[g]
+        is_member = np.zeros(self.n_kinds + 1, dtype=bool)  # (kind -1 reads the spare entry: no member, and it blocks)
+        is_member[gr.members] = True
+        member = is_member[kinds]
+        is_open = member[..., gr.bonds[:, 0]] & member[..., gr.bonds[:, 1]]
+        if gr.gates.shape[1]:
+            passes = np.zeros(self.n_kinds + 1, dtype=bool)
+            passes[gr.gate_kinds] = True
+            has = gr.gates >= 0
+            blocked = (has & ~passes[kinds[..., np.where(has, gr.gates, 0)]]).sum(axis=-1)
+            is_open &= blocked <= gr.max_blocked
+        return is_open
 
     def evaluate(self, occupancies):
         """(stats (..., G, 24) int64, labels (..., G, N) int32) of occupancies (..., N): a breadth-first search from
         every member not yet reached, in the order of the site numbers -- so the start is the component's label."""
         kinds = self.kinds_of(occupancies)
+        occupancies = np.asarray(occupancies)
         lead = kinds.shape[:-1]
         kinds = kinds.reshape(-1, self.num_sites)
         n, G, N = len(kinds), self.n_graphs, self.num_sites
@@ -205,8 +296,14 @@ class Connectivity:
         for gi, (g, adj) in enumerate(zip(self.graphs, self._neighbours())):
             is_member = np.zeros(self.n_kinds + 1, dtype=bool)
             is_member[g.members] = True
+            of_row, n_adjacencies = self._row_adjacency[gi]
             for r in range(n):
                 member = is_member[kinds[r]].tolist()  # (kind -1 reads the spare entry: no member)
+                active = None
+                if g.gated:  # an adjacency is active when one of its rows is open (both ends members then)
+                    hit = np.zeros(n_adjacencies, dtype=bool)
+                    hit[of_row[self.open_rows(occupancies.reshape(-1, N)[r], gi)]] = True
+                    active = hit.tolist()
                 label, st = labels[r, gi], stats[r, gi]
                 off = [None] * N
                 best = (0, 0)  # (size, -label) of the largest component so far
@@ -220,8 +317,8 @@ class Connectivity:
                         label[i] = start
                         size += 1
                         oi = off[i]
-                        for j, wx, wy, wz in adj[i]:
-                            if not member[j]:
+                        for j, wx, wy, wz, a in adj[i]:
+                            if not member[j] if active is None else not active[a]:
                                 continue
                             reach = (oi[0] + wx, oi[1] + wy, oi[2] + wz)
                             if off[j] is None:
@@ -271,10 +368,50 @@ class Connectivity:
         s.images = images.ctypes.data_as(C.POINTER(C.c_int8))
         return s, (self.kind_base, mask, ptr, bonds, images)
 
+    @property
+    def gated(self):
+        """A graph of the spec has a gate site."""
+        return any(g.gated for g in self.graphs)
+
+    def gate_masks(self):
+        """(G, 4) uint64: bit k of the 256-bit row g says a gate site of kind k does not block in graph g."""
+        mask = np.zeros((self.n_graphs, 4), dtype=np.uint64)
+        for gi, g in enumerate(self.graphs):
+            for k in g.gate_kinds:
+                mask[gi, k >> 6] |= np.uint64(1) << np.uint64(k & 63)
+        return mask
+
+    def c_gates(self):
+        """(capi.smolmc_conn_gates, the arrays it points at) of a gated spec -- what ``smolmc_set_connectivity_gated`` takes
+        next to ``c_struct()`` -- or None for a spec without gates."""
+        if not self.gated:
+            return None
+        import ctypes as C
+
+        from . import capi
+
+        mask = self.gate_masks()
+        most = np.asarray([g.max_blocked for g in self.graphs], dtype=np.int32)
+        lists = [g.gate_lists() for g in self.graphs]
+        counts = np.concatenate([np.diff(p) for p, _ in lists]) if lists else np.zeros(0, np.int64)
+        ptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+        sites = np.ascontiguousarray(np.concatenate([s for _, s in lists]), dtype=np.int32)
+        g = capi.smolmc_conn_gates()
+        g.gate_mask = mask.ctypes.data_as(C.POINTER(C.c_uint64))
+        g.max_blocked = most.ctypes.data_as(C.POINTER(C.c_int32))
+        g.gate_ptr = ptr.ctypes.data_as(C.POINTER(C.c_int64))
+        g.gate_sites = sites.ctypes.data_as(C.POINTER(C.c_int32))
+        return g, (mask, most, ptr, sites)
+
     def to_metadata(self):
-        """What a container's metadata keeps of the spec (``moca.Sampler``): its shape and the member kinds."""
-        return dict(n_graphs=self.n_graphs, n_kinds=self.n_kinds, members=[list(g.members) for g in self.graphs],
+        """What a container's metadata keeps of the spec (``moca.Sampler``): its shape and the member kinds; of a gated spec
+        also the gate kinds, ``max_blocked`` and the number of gated rows of every graph."""
+        meta = dict(n_graphs=self.n_graphs, n_kinds=self.n_kinds, members=[list(g.members) for g in self.graphs],
                     n_bonds=[int(len(g.bonds)) for g in self.graphs])
+        if self.gated:
+            meta.update(gate_kinds=[list(g.gate_kinds) for g in self.graphs], max_blocked=[int(g.max_blocked) for g in self.graphs],
+                        n_gated_rows=[int((g.gates >= 0).any(axis=1).sum()) for g in self.graphs])
+        return meta
 
 
 # ---- geometry -----------------------------------------------------------------------------------------------------------
@@ -342,7 +479,38 @@ def geometric_bonds(sc, cutoff=None, distances=None):
     return bonds[keep].astype(np.int32), images[keep].astype(np.int8)
 
 
-# ---- derived quantities (host, pure NumPy on stats) -----------------------------------------------------------------------
+def channel_rows(bonds, images, corners=2):
+    """(bonds, images, gates (nb', corners)): one row per *channel* of every bond row ``(i, j, w)`` of a bond list.  A channel
+    is a set of ``corners`` (1 or 2) further sites of the unfolded lattice that are bonded to i, to j in image w and, for two
+    corners, to each other, all by this bond list: the triangles and tetrahedra on the bond.  The gate sites are the
+    corners folded back; in small and aliased cells one may coincide with an end or with the other corner.  A bond without
+    a channel gets no row.  Rows keep the order of the bonds, the channels of a bond that of their corners."""
+    if corners not in (1, 2):
+        raise ValueError(f"corners must be 1 or 2, got {corners}: a channel is a triangle or a tetrahedron")
+    nbr = {}
+    for (i, j), w in zip(np.asarray(bonds).tolist(), np.asarray(images).tolist()):
+        nbr.setdefault(i, set()).add((j, w[0], w[1], w[2]))
+        nbr.setdefault(j, set()).add((i, -w[0], -w[1], -w[2]))
+    rows_b, rows_w, rows_g = [], [], []
+    for (i, j), w in zip(np.asarray(bonds).tolist(), np.asarray(images).tolist()):
+        far = nbr[j]
+        # the unfolded sites (k, u) bonded to both ends, the ends themselves left out
+        common = sorted(c for c in nbr[i] if (c[0], c[1] - w[0], c[2] - w[1], c[3] - w[2]) in far
+                        and c != (j, w[0], w[1], w[2]) and c != (i, 0, 0, 0))
+        if corners == 1:
+            channels = [(c[0],) for c in common]
+        else:
+            channels = [(c[0], d[0]) for n, c in enumerate(common) for d in common[n + 1:]
+                        if (d[0], d[1] - c[1], d[2] - c[2], d[3] - c[3]) in nbr[c[0]]]
+        for ch in channels:
+            rows_b.append((i, j))
+            rows_w.append(w)
+            rows_g.append(ch)
+    return (np.asarray(rows_b, dtype=np.int32).reshape(-1, 2), np.asarray(rows_w, dtype=np.int8).reshape(-1, 3),
+            np.asarray(rows_g, dtype=np.int32).reshape(-1, corners))
+
+
+# ---- derived quantities (host, pure NumPy on stats)-----------------------------------------------------------------------
 def percolation_strength(stats):
     """wrapping_sites / n_members (..., G): the fraction of the members that lies in wrapping components; NaN without a
     member."""

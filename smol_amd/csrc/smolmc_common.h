@@ -922,6 +922,15 @@ struct SmolmcConn {
     // (adj_off[g] + k N + s) x 4, k < adj_groups[g]; short lists are filled up with the site itself and image zero
     uint32_t *d_adj = nullptr;      // neighbour | (w0 + 8) << 16 | (w1 + 8) << 20 | (w2 + 8) << 24, w its image seen from s
     int adj_off[SMOLMC_MAX_CONN_GRAPHS] = {}, adj_groups[SMOLMC_MAX_CONN_GRAPHS] = {};
+    // gated graphs (smolmc_set_connectivity_gated): entry e = 4 k + i of site s (slot i of group k) has chan_per[g] channel
+    // records of 8 bytes (a power of two: the most an entry needs, rounded up), record c at
+    // chan_off[g] + (e x chan_per[g] + c) N + s: the records of one (e, c) of all sites side by side.  A record holds four 16-bit gate sites in engine numbering, 0xffff for none (four of them: always open);
+    // a first field of 0xfffe: no channel.  chan_per[g] == 0: graph g is ungated and has no records.
+    uint2 *d_chan = nullptr;
+    unsigned long long *d_gate_mask = nullptr; // [G x 4]
+    int chan_off[SMOLMC_MAX_CONN_GRAPHS] = {}, chan_per[SMOLMC_MAX_CONN_GRAPHS] = {}, max_blocked[SMOLMC_MAX_CONN_GRAPHS] = {};
+    int gated_mask = 0;             // bit g: graph g has a gate site
+    long long n_channels = 0;       // channel records with a channel in them, over the gated graphs
     long long *u_stats = nullptr;   // smolmc_update_statistics: stats [R x G x 24] of the walkers' current states
     unsigned long long *d_passes = nullptr; // [2]: most passes of a (row, graph) in the last launch, and their sum
     hipEvent_t ev[2] = {nullptr, nullptr}; // around the last launch of the kernel
@@ -1182,7 +1191,7 @@ void smolmc_sfac_free(SmolmcStruct &S);
 // (Npad bytes apart, device) into device arrays, queued on the handle's stream; the LDS a row of N sites takes (0: it does
 // not fit); the spec's device arrays
 int smolmc_conn_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, long long *d_stats, int32_t *d_labels);
-size_t smolmc_conn_lds_bytes(int N, int Npad);
+size_t smolmc_conn_lds_bytes(int N, int Npad, int open_bytes = 0); // (open_bytes: the open bits a site of a gated graph takes)
 void smolmc_conn_free(SmolmcConn &S);
 size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies);
 int smolmc_obs_pair_copies(size_t cells);

@@ -76,7 +76,9 @@ SYMBOLS = {
     "smolmc_eval_structure": (C.c_int, [_HP, _i32p, C.c_int, _i64p, _f64p]),
     "smolmc_get_sample_structure": (C.c_int, [_HP, _i64p, _f64p]),
     "smolmc_set_connectivity": (C.c_int, [_HP, C.POINTER(capi.smolmc_connectivity)]),
+    "smolmc_set_connectivity_gated": (C.c_int, [_HP, C.POINTER(capi.smolmc_connectivity), C.POINTER(capi.smolmc_conn_gates)]),
     "smolmc_connectivity_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 2),
+    "smolmc_connectivity_gates": (C.c_int, [_HP, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
     "smolmc_eval_connectivity": (C.c_int, [_HP, _i32p, C.c_int, _i64p, _i32p]),
     "smolmc_get_sample_connectivity": (C.c_int, [_HP, _i64p]),
     "smolmc_set_patterns": (C.c_int, [_HP, C.POINTER(capi.smolmc_patterns)]),
@@ -667,8 +669,26 @@ class Engine:
     def set_connectivity(self, spec):
         """The connectivity spec of this handle (smolmc_set_connectivity): a ``connectivity.Connectivity`` in the caller's
         site numbering, or None to remove it.  The engine copies and uploads; it refuses, naming the reason, a bond, kind
-        or image out of range, more than ``capi.MAX_CONN_GRAPHS`` graphs and a row too long for the LDS plan."""
-        self._set_spec(self._lib.smolmc_set_connectivity, spec, "the connectivity spec is")
+        or image out of range, more than ``capi.MAX_CONN_GRAPHS`` graphs and a row too long for the LDS plan.  A spec with
+        gate sites goes through smolmc_set_connectivity_gated, which refuses likewise a gate site or gate kind out of range
+        and a gated row whose open bits do not fit."""
+        gates = None if spec is None else spec.c_gates()
+        if gates is None:
+            self._set_spec(self._lib.smolmc_set_connectivity, spec, "the connectivity spec is")
+            return
+        if spec.num_sites != self.N:
+            raise ValueError(f"the connectivity spec is defined on {spec.num_sites} sites, the handle has {self.N}")
+        struct, keep = spec.c_struct()
+        self._chk(self._lib.smolmc_set_connectivity_gated(self._h, C.byref(struct), C.byref(gates[0])))
+        del keep, gates
+
+    def connectivity_gates(self):
+        """(the graphs of the spec in force that have gates, as a tuple of graph numbers; the channel records the kernel
+        walks, over all neighbour-list entries of those graphs) -- ``((), 0)`` for an ungated spec or none
+        (smolmc_connectivity_gates)."""
+        mask, n = C.c_int(), C.c_int64()
+        self._chk(self._lib.smolmc_connectivity_gates(self._h, C.byref(mask), C.byref(n)))
+        return tuple(g for g in range(capi.MAX_CONN_GRAPHS) if mask.value >> g & 1), int(n.value)
 
     def connectivity_shape(self):
         """(n_graphs, n_kinds) in force, zeros when no spec is set (smolmc_connectivity_shape)."""

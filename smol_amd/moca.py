@@ -1609,6 +1609,12 @@ class SampleContainer:
                           "meta/conn_n_bonds": np.asarray(conn["n_bonds"], dtype=np.int64),
                           "meta/conn_member_ptr": np.cumsum([0] + [len(m) for m in members]).astype(np.int64),
                           "meta/conn_members": np.asarray([k for m in members for k in m], dtype=np.int32)})
+            if "gate_kinds" in conn:  # a gated spec: the kinds that do not block, max_blocked and the gated rows per graph
+                kinds = conn["gate_kinds"]
+                extra.update({"meta/conn_gate_kind_ptr": np.cumsum([0] + [len(m) for m in kinds]).astype(np.int64),
+                              "meta/conn_gate_kinds": np.asarray([k for m in kinds for k in m], dtype=np.int32),
+                              "meta/conn_max_blocked": np.asarray(conn["max_blocked"], dtype=np.int64),
+                              "meta/conn_n_gated_rows": np.asarray(conn["n_gated_rows"], dtype=np.int64)})
         pat = self.metadata.get("patterns")
         if pat is not None:  # the sets of the pattern_counts trace: their shapes and class maps
             extra.update({"meta/pat_shape": np.asarray([pat["arity"], pat["n_classes"], pat["n_tuples"]], dtype=np.int64),
@@ -1744,6 +1750,11 @@ class SampleContainer:
             c.metadata["connectivity"] = dict(n_graphs=int(d["meta/conn_shape"][0]), n_kinds=int(d["meta/conn_shape"][1]),
                                               members=[flat[int(a):int(b)] for a, b in zip(ptr[:-1], ptr[1:])],
                                               n_bonds=d["meta/conn_n_bonds"].tolist())
+            if "meta/conn_gate_kinds" in d.files:
+                ptr, flat = d["meta/conn_gate_kind_ptr"], d["meta/conn_gate_kinds"].tolist()
+                c.metadata["connectivity"].update(gate_kinds=[flat[int(a):int(b)] for a, b in zip(ptr[:-1], ptr[1:])],
+                                                  max_blocked=d["meta/conn_max_blocked"].tolist(),
+                                                  n_gated_rows=d["meta/conn_n_gated_rows"].tolist())
         if "meta/pat_shape" in d.files:
             arity, ncls, ntup = (d["meta/pat_shape"][i].tolist() for i in range(3))
             ptr, ids = d["meta/pat_cell_ptr"].tolist(), d["meta/pat_orbit_ids"].tolist()

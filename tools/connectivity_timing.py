@@ -14,7 +14,15 @@ member fraction into profiles/connectivity_timing.jsonl:
            breadth-first search in Python, one thread), scaled to all rows; likewise scipy.sparse.csgraph.connected_components
            where scipy is present (sizes only: no wrapping)
 
-python tools/connectivity_timing.py [--fractions 0.5,0.2] [--samples 16] [--reps 3] [--out ...]"""
+With --gated the graph's bonds carry their tetrahedral gates (a nearest-neighbour bond is open when the two
+other corners of one of its two tetrahedra are members too, the 0-TM channel); the default fractions are then 0.45, 0.55
+and 0.65, around the threshold near 0.55, and the host path opens the rows before it searches.
+
+With --against LIB the tool measures instead whether the ungated graph pays for the gates: connectivity_kernel of this
+build against that of another build of the library (the parent commit's), on the same R rows, launches alternating in one
+process, and first the other build against a second handle of itself, which gives the spread of such a comparison.
+
+python tools/connectivity_timing.py [--gated] [--against LIB] [--fractions 0.5,0.2] [--samples 16] [--reps 3] [--out ...]"""
 import argparse
 import json
 import os
@@ -47,31 +55,98 @@ def scipy_sizes(spec, occ):
     g = spec.graphs[0]
     kinds = spec.kinds_of(occ)
     out = []
-    for row in kinds:
+    for row, occ_row in zip(kinds, occ):
         member = np.isin(row, g.members)
-        on = member[g.bonds[:, 0]] & member[g.bonds[:, 1]]
+        on = spec.open_rows(occ_row, 0)
         m = coo_matrix((np.ones(int(on.sum()), np.int8), (g.bonds[on, 0], g.bonds[on, 1])), shape=(len(row), len(row)))
         _, lab = connected_components(m, directed=False)
         out.append(int(np.bincount(lab[member]).max(initial=0)))
     return out
 
 
-def measure(fraction, args):
+def workload(args):
     kw = dict(count=args.replicas) if args.replicas else {}
     if args.dim:
         kw["dim"] = args.dim
-    wl = workloads.BUILDERS[2](**kw)
-    eng = Engine(wl.tables, wl.make_config())
-    R, N, ns = eng.R, eng.N, args.samples
-    thin = N  # one sweep
+    return workloads.BUILDERS[2](**kw)
+
+
+def start(wl, fraction):
+    """Exactly round(fraction N) sites of species 1 in every row: swaps keep it so."""
+    R, N = len(wl.seeds), wl.sc.num_sites
     rng = np.random.default_rng(7)
     n_members = int(round(fraction * N))
     occ = np.zeros((R, N), dtype=np.int32)
-    for r in range(R):  # exactly n_members sites of species 1 in every row: swaps keep it so
+    for r in range(R):
         occ[r, rng.permutation(N)[:n_members]] = 1
-    eng.set_state(occ, wl.seeds, wl.temperature)
+    return occ
+
+
+def graph_spec(wl, gated):
     a = float(np.linalg.norm(wl.sc.model.prim.lattice[0]))  # the fcc primitive vectors are nearest-neighbour vectors
-    spec = Connectivity.from_supercell(wl.sc, [dict(members=[1], cutoff=a * 1.01)])
+    graph = dict(members=[1], cutoff=a * 1.01)
+    if gated:
+        graph["gate"] = dict(kinds=[1], corners=2, max_blocked=0)
+    return Connectivity.from_supercell(wl.sc, [graph])
+
+
+def other_engine(path, wl):
+    """A handle served by another build of the library (one that may lack the newest entry points)."""
+    import ctypes as C
+
+    from smol_amd import engine
+
+    lib = C.CDLL(path)
+    for name, (res, argtypes) in engine.SYMBOLS.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, argtypes
+    ours, engine._LIB = engine.load_library(), lib
+    try:
+        return Engine(wl.tables, wl.make_config())
+    finally:
+        engine._LIB = ours
+
+
+def measure_against(fraction, args):
+    wl = workload(args)
+    spec, occ = graph_spec(wl, False), start(wl, fraction)
+    engines = dict(other=other_engine(args.against, wl), other_again=other_engine(args.against, wl), this=Engine(wl.tables, wl.make_config()))
+    N = wl.sc.num_sites
+    for eng in engines.values():  # the same chain in every handle: the same rows
+        eng.set_state(occ, wl.seeds, wl.temperature)
+        eng.set_connectivity(spec)
+        eng.run(20 * N, sync=True)
+    ms = {k: [] for k in engines}
+    ref = None
+    for rep in range(args.warmup + args.ab_reps):
+        for k, eng in engines.items():  # alternating: one launch each, R rows
+            stats = eng.connectivity()
+            ref = stats if ref is None else ref
+            assert np.array_equal(stats, ref), k
+            if rep >= args.warmup:
+                ms[k].append(eng.connectivity_kernel_ms())
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    most, total = engines["this"].connectivity_passes()
+    out = dict(what="connectivity_ungated_this_build_against_another", config=2, name=wl.name, against=os.path.basename(os.path.dirname(args.against)),
+               walkers=len(wl.seeds), sites=N, member_fraction=fraction, rows_per_launch=len(wl.seeds), launches_each=args.ab_reps,
+               kernel_ms=dict(this=med["this"], other=med["other"], other_again=med["other_again"],
+                              min=dict((k, float(np.min(v))) for k, v in ms.items())),
+               spread_other_against_itself=med["other_again"] / med["other"] - 1.0,
+               this_against_other=med["this"] / med["other"] - 1.0, passes_most=int(most), passes_mean=total / len(wl.seeds),
+               same_stats=True)
+    for eng in engines.values():
+        eng.close()
+    return out
+
+
+def measure(fraction, args):
+    wl = workload(args)
+    eng = Engine(wl.tables, wl.make_config())
+    R, N, ns = eng.R, eng.N, args.samples
+    thin = N  # one sweep
+    eng.set_state(start(wl, fraction), wl.seeds, wl.temperature)
+    spec = graph_spec(wl, args.gated)
     eng.set_connectivity(spec)
     eng.run(20 * N, sync=True)
 
@@ -103,8 +178,8 @@ def measure(fraction, args):
     st = D[-1]["stats"][..., 0, :]
     fetch_ms, eval_ms = (t1 - t0) * 1e3, (t2 - t1) * 1e3 * R / rows
     host_ms = fetch_ms + eval_ms
-    out = dict(what="connectivity", config=2, name=wl.name, kernel=eng.kernel_info(), walkers=R, sites=N, member_fraction=fraction,
-               n_bonds=int(len(spec.graphs[0].bonds)), samples_per_block=ns, thin_by=thin, reps=args.reps,
+    out = dict(what="connectivity_gated" if args.gated else "connectivity", config=2, name=wl.name, kernel=eng.kernel_info(), walkers=R, sites=N, member_fraction=fraction,
+               n_bonds=int(len(spec.graphs[0].bonds)), channels=eng.connectivity_gates()[1], samples_per_block=ns, thin_by=thin, reps=args.reps,
                device_equals_definition=same, rows_wrapping=float((st[..., cn.WRAP_AXES] != 0).mean()),
                mean_components=float(st[..., cn.N_COMPONENTS].mean()), mean_largest=float(st[..., cn.LARGEST].mean()),
                device=dict(per_sample=dev, connectivity_kernel_ms_per_block=float(np.median(k)),
@@ -123,7 +198,10 @@ def measure(fraction, args):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--fractions", default="0.5,0.2")
+    ap.add_argument("--fractions", default=None, help="member fractions (default 0.5,0.2; with --gated 0.45,0.55,0.65)")
+    ap.add_argument("--gated", action="store_true", help="the bonds carry their tetrahedral gates")
+    ap.add_argument("--against", default=None, help="another build of libsmolmc_hip.so: time the ungated kernel of this build against it")
+    ap.add_argument("--ab-reps", type=int, default=15, help="launches of each handle with --against")
     ap.add_argument("--replicas", type=int, default=0, help="walkers (default: the configuration's)")
     ap.add_argument("--dim", type=int, default=0, help="supercell size (default: the configuration's)")
     ap.add_argument("--samples", type=int, default=16, help="samples per block")
@@ -132,8 +210,9 @@ def main():
     ap.add_argument("--host-rows", type=int, default=32, help="rows of the one host sample the definition is run on")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "connectivity_timing.jsonl"))
     args = ap.parse_args()
-    for f in args.fractions.split(","):
-        line = json.dumps(measure(float(f), args))
+    fractions = args.fractions or ("0.45,0.55,0.65" if args.gated else "0.5,0.2")
+    for f in fractions.split(","):
+        line = json.dumps((measure_against if args.against else measure)(float(f), args))
         print(line, flush=True)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "a") as fh:
