@@ -319,6 +319,24 @@ int smolmc_resample(smolmc_handle *h, const int32_t *parent /* R, host */);
 int smolmc_anneal_resample(smolmc_handle *h, int npop, const double *temperature_new /* npop */,
                            const uint64_t *offset_word /* npop */, int32_t *parent_out /* R */, uint64_t *q_out /* R */,
                            uint64_t *qsum_out /* npop */, double *href_out /* npop */);
+/* ... the same step with the temperature chosen on the device: the largest step from the populations' common beta
+ * towards 1 / (kB temperature_limit), cooling or heating, at which the energy histograms at beta and beta' still overlap
+ * by overlap_target / 2^32 (Barash, Weigel, Borovsky, Janke, Shchur 2017).  For one population and a step db, with q_j and
+ * Q as above:
+ *     s = sum_j min(Q, n q_j) = c Q + n U  (c walkers with n q_j >= Q, U the sum of the other q_j);  ok iff s 2^32 >= t n Q
+ * (s / (n Q) is the expected share of distinct survivors of the resampling).  Per population: D = 1 / (kB
+ * temperature_limit) - beta if ok(D) (the limit is reached); else lo = 0, hi = D, at most n_iter times mid = 0.5 * (lo +
+ * hi), stop if mid equals lo or hi, lo = mid if ok(mid) else hi = mid; the step is lo, or hi while lo is still 0 (forced:
+ * the target is not met at this resolution, the schedule moves all the same).  All populations take the step of smallest
+ * magnitude (the first of equals): T' = temperature_limit if every population reached it, else 1 / (kB (beta + db)), and
+ * beta' = 1 / (kB T'), every operation rounded on its own.  temperature_out receives T', flags_out bit 0 `reached` and
+ * bit 1 `forced` (of the population whose step was taken).  The call always waits for its kernels.  Refused like
+ * smolmc_anneal_resample, and for overlap_target == 0, n_iter outside 1 .. 60, a limit that is not positive and finite,
+ * and populations that are not all at one temperature.  The other outputs as above (may be NULL). */
+int smolmc_anneal_adaptive(smolmc_handle *h, int npop, double temperature_limit, uint32_t overlap_target, int n_iter,
+                           const uint64_t *offset_word /* npop */, double *temperature_out /* 1 */,
+                           int32_t *flags_out /* 1: bit 0 reached, bit 1 forced */, int32_t *parent_out /* R */,
+                           uint64_t *q_out /* R */, uint64_t *qsum_out /* npop */, double *href_out /* npop */);
 /* any output pointer may be NULL */
 int smolmc_get_state(smolmc_handle *h, int32_t *occ /*RxN*/, double *features /*RxF*/,
                      double *enthalpy /*R*/, uint64_t *n_accepted /*R*/,

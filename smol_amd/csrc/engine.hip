@@ -4247,12 +4247,13 @@ static int resample_refused(const smolmc_handle *h, const char *what) {
 static int pop_scratch(smolmc_handle *h) {
     if (h->pop.parent) return 0;
     const size_t R = (size_t)h->R;
-    uint64_t *arena = nullptr; // six arrays of 8 bytes, four of 4 bytes per walker
-    TRY(dev_alloc(h, 8 * R, &arena));
+    uint64_t *arena = nullptr; // six arrays of 8 bytes, four of 4 bytes per walker; the two words of an adaptive step
+    TRY(dev_alloc(h, 8 * R + 2, &arena));
     SmolmcPopScratch &S = h->pop;
     S.q = arena; S.qsum = arena + R; S.word = arena + 2 * R; S.C = arena + 3 * R;
     S.href = (double *)(arena + 4 * R); S.beta_new = (double *)(arena + 5 * R);
     S.cnt = (uint32_t *)(arena + 6 * R); S.sur = S.cnt + R; S.drank = S.cnt + 2 * R;
+    S.T_new = (double *)(arena + 8 * R); S.flags = (int32_t *)(arena + 8 * R + 1);
     S.parent = (int32_t *)(S.cnt + 3 * R);
     return 0;
 }
@@ -4275,21 +4276,17 @@ extern "C" int smolmc_resample(smolmc_handle *h, const int32_t *parent) {
     return smolmc_pop_clone_launch(h, h->pop.parent, 1, nullptr);
 }
 
-extern "C" int smolmc_anneal_resample(smolmc_handle *h, int npop, const double *temperature_new, const uint64_t *offset_word,
-                                      int32_t *parent_out, uint64_t *q_out, uint64_t *qsum_out, double *href_out) {
-    if (!h || !temperature_new || !offset_word) return fail("null argument");
-    TRY(resample_refused(h, "smolmc_anneal_resample"));
+// what both annealing entries refuse, and the temperatures in force (T_old, R): as named by the latest call that set
+// them, or read back where exchanges moved them
+static int anneal_refused(smolmc_handle *h, const std::string &what, int npop, std::vector<double> &T_old) {
+    TRY(resample_refused(h, what.c_str()));
     const int R = h->R;
     if (npop < 1 || R % npop != 0)
-        return fail("smolmc_anneal_resample: " + std::to_string(npop) + " populations do not divide the " + std::to_string(R) + " walkers (populations are equal blocks of slots: R % npop must be 0)");
+        return fail(what + ": " + std::to_string(npop) + " populations do not divide the " + std::to_string(R) + " walkers (populations are equal blocks of slots: R % npop must be 0)");
     const int n = R / npop;
-    for (int p = 0; p < npop; ++p)
-        if (!(temperature_new[p] > 0.0) || !std::isfinite(temperature_new[p]))
-            return fail("smolmc_anneal_resample: the temperature of population " + std::to_string(p) + " must be positive and finite");
-    if (n > (1 << 22)) return fail("smolmc_anneal_resample: a population must be no larger than 2^22 walkers (the sum of the weights stays below 2^62)");
+    if (n > (1 << 22)) return fail(what + ": a population must be no larger than 2^22 walkers (the sum of the weights stays below 2^62)");
     HIPCHK(hipSetDevice(h->device));
-    // the temperatures in force: as named by the latest call that set them, or read back where exchanges moved them
-    std::vector<double> T_old(R);
+    T_old.resize(R);
     if (!h->point_T_stale && !h->grid_permuted && h->point_T.size() == (size_t)R) T_old = h->point_T;
     else {
         std::vector<double> beta(R);
@@ -4299,9 +4296,29 @@ extern "C" int smolmc_anneal_resample(smolmc_handle *h, int npop, const double *
     }
     for (int r = 0; r < R; ++r)
         if (T_old[r] != T_old[(r / n) * n])
-            return fail("smolmc_anneal_resample: the walkers of population " + std::to_string(r / n) + " are at different temperatures (walker " +
+            return fail(what + ": the walkers of population " + std::to_string(r / n) + " are at different temperatures (walker " +
                         std::to_string((r / n) * n) + ": " + std::to_string(T_old[(r / n) * n]) + ", walker " + std::to_string(r) + ": " + std::to_string(T_old[r]) +
                         "); a population is reweighted from one temperature");
+    return 0;
+}
+static int anneal_outputs(smolmc_handle *h, int npop, int32_t *parent_out, uint64_t *q_out, uint64_t *qsum_out, double *href_out) {
+    const SmolmcPopScratch &S = h->pop;
+    if (parent_out) HIPCHK(hipMemcpyAsync(parent_out, S.parent, (size_t)h->R * 4, hipMemcpyDeviceToHost, h->stream));
+    if (q_out) HIPCHK(hipMemcpyAsync(q_out, S.q, (size_t)h->R * 8, hipMemcpyDeviceToHost, h->stream));
+    if (qsum_out) HIPCHK(hipMemcpyAsync(qsum_out, S.qsum, (size_t)npop * 8, hipMemcpyDeviceToHost, h->stream));
+    if (href_out) HIPCHK(hipMemcpyAsync(href_out, S.href, (size_t)npop * 8, hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
+
+extern "C" int smolmc_anneal_resample(smolmc_handle *h, int npop, const double *temperature_new, const uint64_t *offset_word,
+                                      int32_t *parent_out, uint64_t *q_out, uint64_t *qsum_out, double *href_out) {
+    if (!h || !temperature_new || !offset_word) return fail("null argument");
+    std::vector<double> T_old;
+    TRY(anneal_refused(h, "smolmc_anneal_resample", npop, T_old));
+    const int R = h->R, n = R / npop;
+    for (int p = 0; p < npop; ++p)
+        if (!(temperature_new[p] > 0.0) || !std::isfinite(temperature_new[p]))
+            return fail("smolmc_anneal_resample: the temperature of population " + std::to_string(p) + " must be positive and finite");
     TRY(pop_scratch(h));
     TRY(grid_rebase(h));
     std::vector<double> T_new(R), beta_new(npop);
@@ -4310,16 +4327,53 @@ extern "C" int smolmc_anneal_resample(smolmc_handle *h, int npop, const double *
     const SmolmcPopScratch &S = h->pop;
     HIPCHK(hipMemcpyAsync(S.beta_new, beta_new.data(), (size_t)npop * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(S.word, offset_word, (size_t)npop * 8, hipMemcpyHostToDevice, h->stream));
-    TRY(smolmc_pop_parent_launch(h, npop, S));
+    TRY(smolmc_pop_parent_launch(h, npop, S, nullptr));
     TRY(smolmc_pop_clone_launch(h, S.parent, npop, S.beta_new));
     grid_name_temperatures(h, T_new.data());
     h->order_dirty = true; // (as smolmc_set_temperature: the launch order of the TableFlip kernels follows the temperatures)
     if (parent_out || q_out || qsum_out || href_out) {
-        if (parent_out) HIPCHK(hipMemcpyAsync(parent_out, S.parent, (size_t)R * 4, hipMemcpyDeviceToHost, h->stream));
-        if (q_out) HIPCHK(hipMemcpyAsync(q_out, S.q, (size_t)R * 8, hipMemcpyDeviceToHost, h->stream));
-        if (qsum_out) HIPCHK(hipMemcpyAsync(qsum_out, S.qsum, (size_t)npop * 8, hipMemcpyDeviceToHost, h->stream));
-        if (href_out) HIPCHK(hipMemcpyAsync(href_out, S.href, (size_t)npop * 8, hipMemcpyDeviceToHost, h->stream));
+        TRY(anneal_outputs(h, npop, parent_out, q_out, qsum_out, href_out));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
+    return 0;
+}
+
+// The adaptive step: pop_parent_kernel chooses beta' itself (the largest step towards the limit that keeps the target
+// overlap), then resamples; the clone kernel writes beta'.  The call waits: the points are named with the
+// temperature that comes back, and the driver stops at `reached`.
+extern "C" int smolmc_anneal_adaptive(smolmc_handle *h, int npop, double temperature_limit, uint32_t overlap_target, int n_iter,
+                                      const uint64_t *offset_word, double *temperature_out, int32_t *flags_out,
+                                      int32_t *parent_out, uint64_t *q_out, uint64_t *qsum_out, double *href_out) {
+    if (!h || !offset_word || !temperature_out || !flags_out) return fail("null argument");
+    std::vector<double> T_old;
+    TRY(anneal_refused(h, "smolmc_anneal_adaptive", npop, T_old));
+    if (overlap_target == 0) return fail("smolmc_anneal_adaptive: the overlap target must be positive (the target overlap is overlap_target / 2^32)");
+    if (n_iter < 1 || n_iter > 60) return fail("smolmc_anneal_adaptive: n_iter must lie in 1 .. 60 (the bisections of one step: a double has no more bits to halve)");
+    if (!(temperature_limit > 0.0) || !std::isfinite(temperature_limit))
+        return fail("smolmc_anneal_adaptive: the temperature limit must be positive and finite");
+    const int R = h->R;
+    for (int r = 1; r < R; ++r)
+        if (T_old[r] != T_old[0])
+            return fail("smolmc_anneal_adaptive: the populations are at different temperatures (walker 0: " + std::to_string(T_old[0]) + ", walker " +
+                        std::to_string(r) + ": " + std::to_string(T_old[r]) + "); the search of the step has one beta, the populations share one schedule");
+    TRY(pop_scratch(h));
+    TRY(grid_rebase(h));
+    const SmolmcPopScratch &S = h->pop;
+    SmolmcPopSearch search;
+    search.T_limit = temperature_limit;
+    search.beta_limit = 1.0 / (SMOLMC_KB * temperature_limit); // (as set_betas)
+    search.target = overlap_target;
+    search.n_iter = n_iter;
+    HIPCHK(hipMemcpyAsync(S.word, offset_word, (size_t)npop * 8, hipMemcpyHostToDevice, h->stream));
+    TRY(smolmc_pop_parent_launch(h, npop, S, &search));
+    TRY(smolmc_pop_clone_launch(h, S.parent, npop, S.beta_new));
+    h->order_dirty = true;
+    h->point_T_stale = true; // (until the temperature is back: a failure below leaves the handle reading d_beta)
+    HIPCHK(hipMemcpyAsync(temperature_out, S.T_new, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(flags_out, S.flags, 4, hipMemcpyDeviceToHost, h->stream));
+    TRY(anneal_outputs(h, npop, parent_out, q_out, qsum_out, href_out));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const std::vector<double> T_new((size_t)R, *temperature_out);
+    grid_name_temperatures(h, T_new.data());
     return 0;
 }

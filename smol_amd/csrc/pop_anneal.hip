@@ -1,4 +1,4 @@
-// Population annealing (smolmc_anneal_resample, smolmc_resample; engine.hip): the weights, the systematic resampling and
+// Population annealing (smolmc_anneal_resample, smolmc_anneal_adaptive, smolmc_resample; engine.hip): the weights, the systematic resampling and
 // the walker clone on the device.  A translation unit of its own, like grid_exchange.hip: a kernel added to engine.hip
 // would move the descriptors of all of its kernels.
 //
@@ -11,6 +11,9 @@
 //   donors repeat(arange(n), max(cnt - 1, 0)):  parent[m], with parent[parent[m]] == parent[m]
 // The only floating-point operations are the product, the negation, the exp and the exact scaling: with contraction
 // off (there is nothing to contract, the pragma says so) they round as NumPy's do, exp up to its last bit.
+//
+// An adaptive step (smolmc_anneal_adaptive) chooses beta' first, in a phase in front of the same kernel: the largest step
+// towards a limit at which the energy histograms at beta and beta' still overlap by a target (pa_choose_step below).
 #include "smolmc_common.h"
 
 #define PA_THREADS 256
@@ -26,6 +29,12 @@ struct PopParentArgs {
     uint64_t *C;                   // [R] scratch: inclusive sums of q
     uint32_t *cnt, *sur, *drank;   // [R] scratch: children, inclusive sums of the surplus copies, rank among the dead slots
     int n;                         // walkers per population
+    // the adaptive step (n_iter > 0): beta_new is chosen here, towards beta_limit = 1 / (kB T_limit)
+    int n_iter, npop;
+    uint32_t target;               // the target overlap is target / 2^32
+    double T_limit, beta_limit, kB;
+    double *beta_out, *T_out;      // [npop], [1] out, written by workgroup 0
+    int32_t *flags_out;            // [1] out: bit 0 reached, bit 1 forced
 };
 
 template <typename T> __device__ __forceinline__ T pa_wave_scan(T v, const int lane) {
@@ -54,21 +63,10 @@ template <typename T> __device__ __forceinline__ T pa_block_scan(T v, T *tot, T 
     return v + before;
 }
 
-// one workgroup per population
-__global__ void __launch_bounds__(PA_THREADS) pop_parent_kernel(const PopParentArgs A) {
-#pragma clang fp contract(off)
-    __shared__ double red_d[PA_WAVES];
-    __shared__ uint64_t red_q[PA_WAVES];
-    __shared__ uint32_t red_a[PA_WAVES], red_b[PA_WAVES];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = A.n;
-    const size_t base = (size_t)p * n;
-    const double *H = A.enthalpy + base;
-    uint64_t *q = A.q + base, *C = A.C + base;
-    uint32_t *cnt = A.cnt + base, *sur = A.sur + base, *drank = A.drank + base;
-    const double db = A.beta_new[p] - A.beta[base];
-    const bool cool = db > 0.0;
-
-    // H_ref: the enthalpy of the largest weight (a min / max: exact, whatever the order)
+// H_ref of one population: the enthalpy of the largest weight (a min / max: exact, whatever the order).  Every thread of
+// the workgroup calls it; red is free again once the workgroup has passed its next barrier.
+__device__ __forceinline__ double pa_block_ref(const double *H, const int n, const bool cool, double *red) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double ref = H[0];
     for (int j = tid; j < n; j += PA_THREADS) ref = cool ? fmin(ref, H[j]) : fmax(ref, H[j]);
 #pragma unroll
@@ -76,11 +74,125 @@ __global__ void __launch_bounds__(PA_THREADS) pop_parent_kernel(const PopParentA
         const double o = __shfl_xor(ref, d);
         ref = cool ? fmin(ref, o) : fmax(ref, o);
     }
-    if (lane == 0) red_d[wave] = ref;
+    if (lane == 0) red[wave] = ref;
     __syncthreads();
-    ref = red_d[0];
+    ref = red[0];
 #pragma unroll
-    for (int w = 1; w < PA_WAVES; ++w) ref = cool ? fmin(ref, red_d[w]) : fmax(ref, red_d[w]);
+    for (int w = 1; w < PA_WAVES; ++w) ref = cool ? fmin(ref, red[w]) : fmax(ref, red[w]);
+    return ref;
+}
+__device__ __forceinline__ uint64_t pa_weight(const double db, const double Hj, const double ref) {
+#pragma clang fp contract(off)
+    const double w = exp(-(db * (Hj - ref)));
+    return (uint64_t)(w * 1099511627776.0); // 2^40: the scaling is exact, the conversion truncates
+}
+
+// ---- the adaptive step: the largest step towards beta_limit that keeps the overlap of the energy histograms --------
+// overlap_ok(db) of one population, in integers (PopulationAnnealing.overlap_ok is the same in NumPy):
+//   s = sum_j min(Q, n q_j) = c Q + n U, c walkers with n q_j >= Q, U the sum of the other q_j;  ok iff s 2^32 >= t n Q
+// Q is needed before c and U: the first chunk's q_j stays in a register, those of later chunks are evaluated twice (the
+// enthalpies are read again, from L2).  The sums are integers: the same whatever the order.
+template <typename T> __device__ __forceinline__ T pa_block_sum(T v, T *tot) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    if (lane == 0) tot[wave] = v;
+    __syncthreads();
+    T all = 0;
+#pragma unroll
+    for (int w = 0; w < PA_WAVES; ++w) all += tot[w];
+    __syncthreads();
+    return all;
+}
+__device__ __forceinline__ bool pa_overlap_ok(const double *H, const int n, const double ref, const double db, const uint32_t target,
+                                              uint64_t *red_q, uint32_t *red_a) {
+    const int tid = threadIdx.x;
+    uint64_t q0 = 0, part = 0;
+    for (int j0 = 0; j0 < n; j0 += PA_THREADS) {
+        const int j = j0 + tid;
+        const uint64_t qj = j < n ? pa_weight(db, H[j], ref) : 0;
+        if (j0 == 0) q0 = qj;
+        part += qj; // (at most 2^14 terms of at most 2^40)
+    }
+    const uint64_t Q = pa_block_sum(part, red_q);
+    uint32_t c = 0;
+    uint64_t U = 0;
+    for (int j0 = 0; j0 < n; j0 += PA_THREADS) {
+        const int j = j0 + tid;
+        if (j < n) {
+            const uint64_t qj = j0 == 0 ? q0 : pa_weight(db, H[j], ref);
+            if ((uint64_t)n * qj >= Q) ++c; // (n <= 2^22: below 2^63)
+            else U += qj;
+        }
+    }
+    c = pa_block_sum(c, red_a);
+    U = pa_block_sum(U, red_q);
+    // uniform values from here on: every thread takes the same decision
+    const unsigned __int128 s = (unsigned __int128)c * Q + (unsigned __int128)(uint64_t)n * U; // < 2^85
+    return (s << 32) >= (unsigned __int128)((uint64_t)target * (uint64_t)n) * Q;             // both sides < 2^117
+}
+// The choice for all populations (PopulationAnnealing.next_temperature): per population the whole step D if it is ok,
+// else a bisection of [0, D] that keeps ok(lo) and not ok(hi); the step of smallest magnitude wins.  Every workgroup runs
+// the search of every population -- the same code on the same inputs, so all arrive at the same beta' without a
+// reduction across workgroups -- and writes nothing to global memory but workgroup 0, which owns the three outputs.
+// Returns beta'.
+__device__ __forceinline__ double pa_choose_step(const PopParentArgs &A, double *red_d, uint64_t *red_q, uint32_t *red_a) {
+#pragma clang fp contract(off)
+    const int n = A.n;
+    const double beta = A.beta[0]; // (one temperature over all populations: the host refuses anything else)
+    const double D = A.beta_limit - beta;
+    const bool cool = D > 0.0; // (every step that is evaluated has the sign of D)
+    double db = D;
+    bool reached = true, forced = false;
+    for (int pp = 0; pp < A.npop; ++pp) {
+        const double *H = A.enthalpy + (size_t)pp * n;
+        const double ref = pa_block_ref(H, n, cool, red_d);
+        double db_p = D;
+        bool forced_p = false;
+        if (!pa_overlap_ok(H, n, ref, D, A.target, red_q, red_a)) {
+            reached = false;
+            double lo = 0.0, hi = D;
+            for (int it = 0; it < A.n_iter; ++it) {
+                const double mid = 0.5 * (lo + hi);
+                if (mid == lo || mid == hi) break;
+                if (pa_overlap_ok(H, n, ref, mid, A.target, red_q, red_a)) lo = mid;
+                else hi = mid;
+            }
+            forced_p = lo == 0.0; // (the target is not met at this resolution: the schedule moves all the same)
+            db_p = forced_p ? hi : lo;
+        }
+        if (pp == 0 || fabs(db_p) < fabs(db)) {
+            db = db_p;
+            forced = forced_p;
+        }
+    }
+    const double T_new = reached ? A.T_limit : 1.0 / (A.kB * (beta + db));
+    const double b_new = 1.0 / (A.kB * T_new); // (as set_betas: d_beta == 1 / (kB point_T) stays true)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int pp = 0; pp < A.npop; ++pp) A.beta_out[pp] = b_new;
+        *A.T_out = T_new;
+        *A.flags_out = (reached ? 1 : 0) | (forced ? 2 : 0);
+    }
+    return b_new;
+}
+
+// one workgroup per population
+__global__ void __launch_bounds__(PA_THREADS) pop_parent_kernel(const PopParentArgs A) {
+#pragma clang fp contract(off)
+    __shared__ double red_d[PA_WAVES];
+    __shared__ uint64_t red_q[PA_WAVES];
+    __shared__ uint32_t red_a[PA_WAVES], red_b[PA_WAVES];
+    const int p = blockIdx.x, tid = threadIdx.x, n = A.n;
+    const size_t base = (size_t)p * n;
+    const double *H = A.enthalpy + base;
+    uint64_t *q = A.q + base, *C = A.C + base;
+    uint32_t *cnt = A.cnt + base, *sur = A.sur + base, *drank = A.drank + base;
+    // (A.n_iter is a launch argument: uniform over the grid; a fixed-schedule call reads the beta' it was given)
+    const double b_new = A.n_iter > 0 ? pa_choose_step(A, red_d, red_q, red_a) : A.beta_new[p];
+    const double db = b_new - A.beta[base];
+    const bool cool = db > 0.0;
+
+    const double ref = pa_block_ref(H, n, cool, red_d);
 
     // q_j and their inclusive sums, chunk by chunk
     uint64_t carry = 0;
@@ -88,8 +200,7 @@ __global__ void __launch_bounds__(PA_THREADS) pop_parent_kernel(const PopParentA
         const int j = j0 + tid;
         uint64_t qj = 0;
         if (j < n) {
-            const double w = exp(-(db * (H[j] - ref)));
-            qj = (uint64_t)(w * 1099511627776.0); // 2^40: the scaling is exact, the conversion truncates
+            qj = pa_weight(db, H[j], ref);
             q[j] = qj;
         }
         const uint64_t c = pa_block_scan(qj, red_q, carry);
@@ -215,12 +326,19 @@ __global__ void __launch_bounds__(PA_THREADS) pop_clone_kernel(const PopCloneArg
     }
 }
 
-int smolmc_pop_parent_launch(smolmc_handle *h, int npop, const SmolmcPopScratch &S) {
+int smolmc_pop_parent_launch(smolmc_handle *h, int npop, const SmolmcPopScratch &S, const SmolmcPopSearch *search) {
     PopParentArgs A;
+    memset(&A, 0, sizeof(A));
     A.enthalpy = h->kp.enthalpy; A.beta = h->d_beta; A.beta_new = S.beta_new; A.word = S.word;
     A.parent = S.parent; A.q = S.q; A.qsum = S.qsum; A.href = S.href;
     A.C = S.C; A.cnt = S.cnt; A.sur = S.sur; A.drank = S.drank;
     A.n = h->R / npop;
+    A.npop = npop;
+    if (search) {
+        A.n_iter = search->n_iter; A.target = search->target;
+        A.T_limit = search->T_limit; A.beta_limit = search->beta_limit; A.kB = SMOLMC_KB;
+        A.beta_out = S.beta_new; A.T_out = S.T_new; A.flags_out = S.flags;
+    }
     hipLaunchKernelGGL(pop_parent_kernel, dim3((unsigned)npop), dim3(PA_THREADS), 0, h->stream, A);
     HIPCHK(hipGetLastError());
     return 0;

@@ -810,6 +810,14 @@ struct SmolmcPopScratch {
     uint64_t *q, *qsum, *word, *C;
     double *href, *beta_new;
     uint32_t *cnt, *sur, *drank;
+    double *T_new;  // [1] the temperature an adaptive step chose
+    int32_t *flags; // [1] bit 0 reached, bit 1 forced
+};
+// the search of an adaptive step (smolmc_anneal_adaptive): towards beta_limit = 1 / (kB T_limit), target overlap t / 2^32
+struct SmolmcPopSearch {
+    double T_limit, beta_limit;
+    uint32_t target;
+    int n_iter;
 };
 
 // observables.hip: the pattern spec of a handle (smolmc_set_patterns) as the observables' kernel reads it, engine numbering
@@ -1154,8 +1162,9 @@ int smolmc_grid_exchange_launch(smolmc_handle *h, int npairs, const int32_t *pai
 // (device arrays; the pairs disjoint), decided and applied on the device, queued on the handle's stream
 int smolmc_wl_exchange_launch(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int32_t *accepted);
 // ... weights, systematic resampling and the stable assignment of npop populations of R / npop walkers: S.parent, S.q,
-// S.qsum, S.href from the enthalpies, the temperatures in force, S.beta_new and S.word; queued on the handle's stream
-int smolmc_pop_parent_launch(smolmc_handle *h, int npop, const SmolmcPopScratch &S);
+// S.qsum, S.href from the enthalpies, the temperatures in force, S.beta_new and S.word; queued on the handle's stream.
+// With `search` the kernel chooses the step first and writes S.beta_new, S.T_new and S.flags itself.
+int smolmc_pop_parent_launch(smolmc_handle *h, int npop, const SmolmcPopScratch &S, const SmolmcPopSearch *search);
 // ... slot m takes every per-walker row of slot parent[m] (device array; parent[parent[m]] == parent[m]), and, with
 // beta_new (device, [npop]), walker m the inverse temperature beta_new[m / (R / npop)]; queued on the handle's stream
 int smolmc_pop_clone_launch(smolmc_handle *h, const int32_t *parent, int npop, const double *beta_new);

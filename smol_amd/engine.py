@@ -42,6 +42,7 @@ SYMBOLS = {
     "smolmc_exchange_wl": (C.c_int, [_HP, C.c_int, _i32p, _f64p, _i64p]),
     "smolmc_resample": (C.c_int, [_HP, _i32p]),
     "smolmc_anneal_resample": (C.c_int, [_HP, C.c_int, _f64p, _u64p, _i32p, _u64p, _u64p, _f64p]),
+    "smolmc_anneal_adaptive": (C.c_int, [_HP, C.c_int, C.c_double, C.c_uint32, C.c_int, _u64p, _f64p, _i32p, _i32p, _u64p, _u64p, _f64p]),
     "smolmc_get_state": (C.c_int, [_HP, _i32p, _f64p, _f64p, _u64p, _u64p, _u8p]),
     "smolmc_get_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
     "smolmc_set_wl": (C.c_int, [_HP, _f64p, _i64p, _i64p, _f64p, _f64p]),
@@ -393,6 +394,30 @@ class Engine:
             self._h, npop, _p(temp, C.c_double), _p(words, C.c_uint64),
             _p(out["parent"], C.c_int32) if out else None, _p(out["q"], C.c_uint64) if out else None,
             _p(out["qsum"], C.c_uint64) if out else None, _p(out["href"], C.c_double) if out else None))
+        return out
+
+    def anneal_adaptive(self, temperature_limit, overlap, offset_words, npop=1, n_iter=16):
+        """One population-annealing step whose temperature the device chooses (smolmc_anneal_adaptive): the largest
+        step from the populations' common temperature towards ``temperature_limit`` that keeps the overlap of the energy
+        histograms at ``overlap`` in (0, 1) (the word t = int(overlap 2^32) decides), found with at most ``n_iter``
+        bisections per population; then the step of ``anneal_resample`` to that temperature.  Returns its dict plus
+        ``temperature`` (in force afterwards), ``reached`` (it is the limit) and ``forced`` (the target was not met at
+        the resolution of the search)."""
+        npop = int(npop)
+        words = np.ascontiguousarray(offset_words, dtype=np.uint64).reshape(-1)
+        if len(words) != npop:
+            raise ValueError(f"expected one offset word per population: {npop} populations, {len(words)} words")
+        t = int(float(overlap) * 2 ** 32)
+        if not 0 <= t < 2 ** 32:
+            raise ValueError(f"the target overlap must lie in (0, 1): {overlap}")
+        out = dict(parent=np.empty(self.R, dtype=np.int32), q=np.empty(self.R, dtype=np.uint64),
+                   qsum=np.empty(npop, dtype=np.uint64), href=np.empty(npop))
+        temp, flags = np.empty(1), np.empty(1, dtype=np.int32)
+        self._chk(self._lib.smolmc_anneal_adaptive(
+            self._h, npop, float(temperature_limit), t, int(n_iter), _p(words, C.c_uint64), _p(temp, C.c_double),
+            _p(flags, C.c_int32), _p(out["parent"], C.c_int32), _p(out["q"], C.c_uint64), _p(out["qsum"], C.c_uint64),
+            _p(out["href"], C.c_double)))
+        out.update(temperature=float(temp[0]), reached=bool(flags[0] & 1), forced=bool(flags[0] & 2))
         return out
 
     def species_counts(self, occupancies):

@@ -1597,6 +1597,8 @@ class SampleContainer:
                           "meta/pop_anneal_log_partition_ratio": np.asarray(pop["log_partition_ratio"], dtype=np.float64),
                           "meta/pop_anneal_n_families": np.asarray(pop["n_families"], dtype=np.int64),
                           "meta/pop_anneal_rho_t": np.asarray(pop["rho_t"], dtype=np.float64)})
+            if "overlap" in pop:  # an adaptive schedule: the target and the overlap of every step and population
+                extra["meta/pop_anneal_overlap"] = np.asarray(pop["overlap"], dtype=np.float64).reshape(len(pop["overlap"]), -1)
         obs = self.metadata.get("observables")
         if obs is not None:  # the kinds of the species_counts / pair_counts traces
             extra.update({"meta/obs_kind_base": np.asarray(obs["kind_base"], dtype=np.int32),
@@ -1776,6 +1778,8 @@ class SampleContainer:
                 populations=int(d["meta/pop_anneal_seed"][0]), seed=int(d["meta/pop_anneal_seed"][1]),
                 log_partition_ratio=d["meta/pop_anneal_log_partition_ratio"].tolist(),
                 n_families=d["meta/pop_anneal_n_families"].tolist(), rho_t=d["meta/pop_anneal_rho_t"].tolist())
+            if "meta/pop_anneal_overlap" in d.files:
+                c.metadata["population_annealing"]["overlap"] = d["meta/pop_anneal_overlap"].tolist()
         return c
 
 
@@ -2798,7 +2802,8 @@ class Sampler:
             self.run(mcmc_steps, initial_occupancies=start, thin_by=thin_by, progress=progress)
             start = None
 
-    def anneal_population(self, temperatures, mcmc_steps, initial_occupancies=None, populations=1, thin_by=1, seed=0):
+    def anneal_population(self, temperatures, mcmc_steps, initial_occupancies=None, populations=1, thin_by=1, seed=0,
+                          overlap=None, n_iter=16, max_steps=1000):
         """Population annealing (Hukushima & Iba 2003; Machta, PRE 82, 026704), the counterpart of ``anneal``: the
         walkers are ``populations`` equal blocks that cool together.  ``mcmc_steps`` steps are sampled at
         ``temperatures[0]``; at every later temperature each population is reweighted by exp(-dbeta H), resampled to
@@ -2806,7 +2811,13 @@ class Sampler:
         the sample layout of ``anneal``.  Returns the ``parallel.PopulationAnnealing`` that holds the running
         ``log_q`` and the lineage; ``samples.metadata["population_annealing"]`` records, per temperature and
         population, ``log_partition_ratio`` (ln Z(T) - ln Z(temperatures[0]), 0 in the first row), ``n_families`` and
-        ``rho_t``, and survives ``to_npz`` / ``from_npz``."""
+        ``rho_t``, and survives ``to_npz`` / ``from_npz``.
+
+        With ``overlap`` in (0, 1) the schedule is adaptive: ``temperatures`` names the two ends (T0, T_end), and every
+        step is the largest one at which the energy histograms of the two temperatures still overlap by ``overlap``,
+        chosen on the device from the populations themselves (``Engine.anneal_adaptive``, at most ``n_iter`` bisections
+        per step, at most ``max_steps`` steps).  The chosen ladder is the metadata's ``temperatures``, and ``overlap``
+        holds one row [target, overlap of population 0, 1, ...] per step."""
         from . import parallel
 
         if not isinstance(self._kernels[0], Metropolis):
@@ -2814,6 +2825,9 @@ class Sampler:
         temperatures = [float(t) for t in temperatures]
         if len(temperatures) < 1:
             raise ValueError("anneal_population needs at least one temperature")
+        if overlap is not None and len(temperatures) != 2:
+            raise ValueError("anneal_population with a target overlap chooses its own schedule: temperatures names the "
+                             f"two ends (T0, T_end), not {len(temperatures)} values")
         if temperatures[0] < temperatures[-1]:
             raise ValueError(
                 "End temperature is greater than start temperature "
@@ -2829,23 +2843,48 @@ class Sampler:
             raise ValueError("anneal_population with per-walker chemical potentials: walkers of different "
                              "Hamiltonians are no population")
         self._need_start(initial_occupancies)
-        pa = parallel.PopulationAnnealing(temperatures, populations=P, seed=seed)
+        if overlap is None:
+            pa = parallel.PopulationAnnealing(temperatures, populations=P, seed=seed)
+        else:
+            pa = parallel.PopulationAnnealing.adaptive(temperatures[0], temperatures[1], overlap, populations=P, seed=seed,
+                                                       n_iter=n_iter, max_steps=max_steps)
         n = nw // P
-        lpr, nfam, rho = [[0.0] * P], [[n] * P], [[1.0] * P]
-        for k, temperature in enumerate(temperatures):
-            for kernel in self._kernels:
-                kernel.temperature = temperature
+        lpr, nfam, rho, ovl = [[0.0] * P], [[n] * P], [[1.0] * P], []
+        k = 0
+        while True:
             if k == 0:
+                for kernel in self._kernels:
+                    kernel.temperature = temperatures[0]
                 self._load_state(initial_occupancies)
             else:
-                res = self._get_engine().anneal_resample(np.full(P, temperature), pa.offset_words(k - 1), npop=P)
+                if overlap is None:
+                    temperature = temperatures[k]
+                    for kernel in self._kernels:
+                        kernel.temperature = temperature
+                    res = self._get_engine().anneal_resample(np.full(P, temperature), pa.offset_words(k - 1), npop=P)
+                else:
+                    pa.check_room()
+                    res = self._get_engine().anneal_adaptive(pa.t_end, pa.overlap_value, pa.offset_words(k - 1), npop=P,
+                                                             n_iter=pa.n_iter)
+                    temperature = res["temperature"]
+                    pa.append(temperature, res["reached"], res["forced"],
+                              [pa.overlap(res["q"][p * n:(p + 1) * n]) for p in range(P)])
+                    ovl.append([pa.overlap_value] + pa.overlaps[-1].tolist())
+                    for kernel in self._kernels:  # (the engine holds the temperature already)
+                        kernel.temperature = temperature
                 pa.record(res["parent"], res["qsum"], res["href"], k - 1)
                 lpr.append(pa.log_partition_ratio().tolist())
                 nfam.append(pa.n_families[-1].tolist())
                 rho.append(pa.rho_t[-1].tolist())
             for block in self._sample_blocks(mcmc_steps, None, thin_by, state_loaded=True):
                 self.samples.append_block(block, thinned_by=thin_by)
-        self.samples.metadata["population_annealing"] = dict(
-            temperatures=temperatures, populations=P, seed=int(seed), log_partition_ratio=lpr, n_families=nfam, rho_t=rho)
+            k += 1
+            if pa.done if overlap is not None else k >= len(temperatures):
+                break
+        meta = dict(temperatures=[float(t) for t in pa.temperatures], populations=P, seed=int(seed), log_partition_ratio=lpr,
+                    n_families=nfam, rho_t=rho)
+        if overlap is not None:
+            meta["overlap"] = ovl
+        self.samples.metadata["population_annealing"] = meta
         self._resume_at = (id(self.samples), self.samples.num_samples)
         return pa

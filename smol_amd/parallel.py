@@ -784,10 +784,22 @@ class PopulationAnnealing:
 
     The sum of ln Q_p over the steps estimates ln Z(beta_K) - ln Z(beta_0).  ``weights`` and ``parent_map`` are the
     definition the device kernels (pop_anneal.hip) are tested against: q up to the last bit of exp, the map exactly.
-    ``family[w]`` is the walker of the start population that walker w descends from."""
+    ``family[w]`` is the walker of the start population that walker w descends from.
+
+    An adaptive schedule (``PopulationAnnealing.adaptive``) chooses every step from the population itself: the largest
+    step towards ``t_end`` whose energy histograms at beta and beta' overlap by a target (Barash et al. 2017), also in
+    integers.  For one population, a step db and a target t / 2^32 (0 < t < 2^32):
+
+        s = sum_j min(Q, n q_j) = c Q + n U:  c walkers have n q_j >= Q, U is the sum of the other q_j
+        (s / (n Q) = sum_j min(1 / n, q_j / Q): the expected share of distinct survivors of the resampling)
+        the step is ok iff s 2^32 >= t n Q
+
+    ``next_temperature`` bisects db between 0 and 1 / (kB T_limit) - beta per population and takes the db of smallest
+    magnitude; the step itself is the move above from beta to the beta' of the chosen temperature."""
 
     SCALE_BITS = 40
     MAX_POPULATION = 1 << 22  # Q < 2^62
+    MAX_ITER = 60
 
     def __init__(self, temperatures, populations=1, seed=0):
         self.temperatures = np.ascontiguousarray(temperatures, dtype=np.float64).reshape(-1)
@@ -802,11 +814,73 @@ class PopulationAnnealing:
         self.n_families = np.zeros((0, self.populations), dtype=np.int64)
         self.rho_t = np.zeros((0, self.populations))
         self.family = None  # (R,) set by the first step: the identity before it
+        self.adaptive_schedule = False  # (PopulationAnnealing.adaptive: the schedule grows as the steps are chosen)
+        self._reached = False
+
+    @classmethod
+    def adaptive(cls, t_start, t_end, overlap, populations=1, seed=0, n_iter=16, max_steps=1000):
+        """A schedule that is chosen as it is taken: from ``t_start`` towards ``t_end`` (cooling or heating) in steps
+        whose energy histograms overlap by ``overlap`` in (0, 1), each found with at most ``n_iter`` bisections
+        (``next_temperature``).  ``temperatures`` starts as [t_start] and gains every chosen temperature (``append``);
+        ``done`` turns true when ``t_end`` is reached, and a step beyond ``max_steps`` raises."""
+        pa = cls([t_start], populations=populations, seed=seed)
+        pa.t_end = float(t_end)
+        if not (pa.t_end > 0.0 and np.isfinite(pa.t_end)):
+            raise ValueError("PopulationAnnealing.adaptive needs a positive, finite end temperature")
+        pa.overlap_value, pa.overlap_target = float(overlap), cls.target_word(overlap)
+        pa.n_iter, pa.max_steps = int(n_iter), int(max_steps)
+        if not 1 <= pa.n_iter <= cls.MAX_ITER:
+            raise ValueError(f"PopulationAnnealing.adaptive needs n_iter in 1 .. {cls.MAX_ITER}")
+        pa.adaptive_schedule = True
+        pa.overlaps = np.zeros((0, pa.populations))  # (steps taken, P): the overlap achieved by every step
+        pa.forced = []  # per step: the target could not be met at the resolution of the bisection
+        return pa
+
+    @staticmethod
+    def target_word(overlap):
+        """t = int(overlap 2^32) of an overlap in (0, 1); 0 < t < 2^32."""
+        t = int(float(overlap) * 2 ** 32)
+        if not 0 < t < 2 ** 32:
+            raise ValueError(f"the target overlap must lie in (0, 1) and be at least 2^-32: {overlap}")
+        return t
+
+    def append(self, temperature, reached, forced=False, overlaps=None):
+        """Record the temperature an adaptive schedule chose for its next step (before ``record`` of that step)."""
+        self.check_room()
+        self.temperatures = np.append(self.temperatures, np.float64(temperature))
+        self.betas = 1.0 / (kB * self.temperatures)
+        self._reached = bool(reached)
+        self.forced.append(bool(forced))
+        row = np.full(self.populations, np.nan) if overlaps is None else np.asarray(overlaps, dtype=np.float64).reshape(-1)
+        self.overlaps = np.vstack([self.overlaps, row[None]])
+
+    def check_room(self):
+        """Raise unless an adaptive schedule may choose a further step."""
+        if not self.adaptive_schedule:
+            raise ValueError("a fixed schedule takes no further temperatures")
+        if self._reached:
+            raise ValueError("the adaptive schedule has reached its end temperature")
+        if self.n_steps >= self.max_steps:
+            raise RuntimeError(f"the adaptive schedule did not reach {self.t_end} K within max_steps = {self.max_steps} steps "
+                               f"(now at {self.temperatures[-1]} K)")
+
+    def choose(self, enthalpy):
+        """The next temperature of an adaptive schedule from the enthalpies (R,) on the host: ``next_temperature``,
+        recorded with ``append``.  Returns it."""
+        H = np.asarray(enthalpy, dtype=np.float64).reshape(self.populations, -1)
+        t_new, reached, forced, _ = self.next_temperature(H, self.betas[-1], self.t_end, self.overlap_target, self.n_iter)
+        self.append(t_new, reached, forced)
+        return t_new
 
     @property
     def n_steps(self):
-        """Resampling steps of the schedule."""
+        """Resampling steps of the schedule (of an adaptive one: those chosen so far)."""
         return len(self.temperatures) - 1
+
+    @property
+    def done(self):
+        """Every step of the schedule is taken (an adaptive one: its end temperature is reached and that step taken)."""
+        return self.calls >= self.n_steps and (self._reached or not self.adaptive_schedule)
 
     def offset_words(self, attempt):
         """The uint64 offset word of every population at step ``attempt`` (a pure function of the seed and the step)."""
@@ -816,12 +890,92 @@ class PopulationAnnealing:
     @classmethod
     def weights(cls, enthalpy, beta_old, beta_new):
         """(q (n,) uint64, Q int, H_ref) of one population."""
+        return cls.weights_of_step(enthalpy, np.float64(beta_new) - np.float64(beta_old))
+
+    @classmethod
+    def weights_of_step(cls, enthalpy, db):
+        """(q (n,) uint64, Q int, H_ref) of one population for a step ``db`` of beta."""
         H = np.asarray(enthalpy, dtype=np.float64).reshape(-1)
-        db = np.float64(beta_new) - np.float64(beta_old)
+        db = np.float64(db)
         href = H.min() if db > 0 else H.max()
         w = np.exp(-(db * (H - href)))
         q = np.floor(w * 2.0 ** cls.SCALE_BITS).astype(np.uint64)
-        return q, int(sum(int(x) for x in q)), float(href)
+        return q, int(q.sum(dtype=np.uint64)), float(href)  # (Q < 2^62: the uint64 sum is exact)
+
+    # ---- the adaptive step: the overlap of the energy histograms at beta and beta + db, in integers -----------------
+    @staticmethod
+    def overlap_terms(q):
+        """(n, Q, c, U) of the weights of one population: c walkers with n q_j >= Q, U the sum of the other q_j, so that
+        s = sum_j min(Q, n q_j) = c Q + n U.  (n q_j <= 2^62: uint64 holds it.)"""
+        q = np.asarray(q, dtype=np.uint64).reshape(-1)
+        n, Q = len(q), int(q.sum(dtype=np.uint64))
+        big = q * np.uint64(n) >= np.uint64(Q)
+        return n, Q, int(big.sum()), int(q[~big].sum(dtype=np.uint64))
+
+    @classmethod
+    def overlap(cls, q):
+        """s / (n Q) = sum_j min(1 / n, q_j / Q) as a float, for reporting (the decisions are ``overlap_ok``'s)."""
+        n, Q, c, U = cls.overlap_terms(q)
+        return (c * Q + n * U) / (n * Q)
+
+    @classmethod
+    def overlap_ok(cls, enthalpy, db, target, margin=False):
+        """Whether the step ``db`` keeps the overlap of one population at ``target`` / 2^32 or above: s 2^32 >= t n Q.
+        ``margin=True``: (ok, |s 2^32 - t n Q| >> 32) -- how far the decision is from turning."""
+        target = int(target)
+        if not 0 < target < 2 ** 32:
+            raise ValueError("the overlap target is a word t with 0 < t < 2^32 (the target is t / 2^32)")
+        q, _, _ = cls.weights_of_step(enthalpy, db)
+        n, Q, c, U = cls.overlap_terms(q)
+        lhs, rhs = (c * Q + n * U) << 32, target * n * Q
+        return (lhs >= rhs, abs(lhs - rhs) >> 32) if margin else lhs >= rhs
+
+    @classmethod
+    def search_step(cls, enthalpy, full_step, target, n_iter):
+        """The step of one population towards ``full_step`` = beta_limit - beta: (db, reached, forced, smallest margin,
+        lo, hi).  The whole step if it is ok; else the bisection of [0, full_step] that keeps ok(lo) and not ok(hi),
+        at most ``n_iter`` halvings, db = lo -- or hi where lo is still 0 (forced: the schedule moves all the same)."""
+        D = np.float64(full_step)
+        ok, margin = cls.overlap_ok(enthalpy, D, target, margin=True)
+        if ok:
+            return D, True, False, margin, D, D
+        lo, hi = np.float64(0.0), D
+        for _ in range(int(n_iter)):
+            mid = np.float64(0.5) * (lo + hi)
+            if mid == lo or mid == hi:
+                break
+            ok, m = cls.overlap_ok(enthalpy, mid, target, margin=True)
+            margin = min(margin, m)
+            if ok:
+                lo = mid
+            else:
+                hi = mid
+        forced = lo == 0.0
+        return (hi if forced else lo), False, bool(forced), margin, lo, hi
+
+    @classmethod
+    def next_temperature(cls, enthalpy, beta, temperature_limit, target, n_iter=16):
+        """One choice for all populations, enthalpy (P, n): (T', reached, forced, smallest margin of all decisions).
+        db is the population step (``search_step``) of smallest magnitude (the first of equals), ``reached`` holds iff
+        every population reached the limit, ``forced`` iff the chosen one was forced.  T' = T_limit when reached, else
+        1 / (kB (beta + db)), every operation rounded on its own; beta' is 1 / (kB T') as everywhere."""
+        H = np.asarray(enthalpy, dtype=np.float64)
+        H = H.reshape(1, -1) if H.ndim == 1 else H
+        if not 1 <= int(n_iter) <= cls.MAX_ITER:
+            raise ValueError(f"n_iter must lie in 1 .. {cls.MAX_ITER}")
+        T_limit, beta = np.float64(temperature_limit), np.float64(beta)
+        if not (T_limit > 0.0 and np.isfinite(T_limit)):
+            raise ValueError("the temperature limit must be positive and finite")
+        D = np.float64(1.0) / (np.float64(kB) * T_limit) - beta
+        db, reached, forced, margin = None, True, False, None
+        for p in range(len(H)):
+            db_p, reached_p, forced_p, margin_p, _, _ = cls.search_step(H[p], D, target, n_iter)
+            reached = reached and reached_p
+            margin = margin_p if margin is None else min(margin, margin_p)
+            if db is None or abs(db_p) < abs(db):
+                db, forced = db_p, forced_p
+        T_new = T_limit if reached else np.float64(1.0) / (np.float64(kB) * (beta + db))
+        return float(T_new), bool(reached), bool(forced), int(margin)
 
     @staticmethod
     def children(q, word):
@@ -931,6 +1085,8 @@ def run_population_annealing(engine, pa, steps_per_temperature, host_decide=Fals
     R, P = int(engine.R), pa.populations
     if R % P:
         raise ValueError(f"{P} populations do not divide the engine's {R} walkers")
+    if pa.adaptive_schedule:
+        return _run_adaptive_annealing(engine, pa, steps_per_temperature, host_decide, history)
     for k in range(pa.calls, pa.n_steps):
         t_new = pa.temperatures[k + 1]
         if host_decide:
@@ -943,6 +1099,38 @@ def run_population_annealing(engine, pa, steps_per_temperature, host_decide=Fals
             res = engine.anneal_resample(np.full(P, t_new), pa.offset_words(k), npop=P)
             parent = res["parent"]
             pa.record(parent, res["qsum"], res["href"], k)
+        if history is not None:
+            history.append(np.array(parent))
+        engine.run(int(steps_per_temperature))
+    return pa
+
+
+def _run_adaptive_annealing(engine, pa, steps_per_temperature, host_decide, history):
+    """``run_population_annealing`` of an adaptive schedule: every step is chosen from the population (on the device by
+    ``Engine.anneal_adaptive``, with ``host_decide`` by ``pa.choose`` on the enthalpies read back) until the end
+    temperature is reached."""
+    R, P = int(engine.R), pa.populations
+    n = R // P
+    while not pa.done:
+        k = pa.calls
+        if host_decide:
+            st = engine.get_state()
+            if pa.n_steps == k:  # (else: chosen already, the step itself is still to take)
+                pa.choose(st["enthalpy"])
+            t_new = pa.temperatures[k + 1]
+            res = pa.step(st["enthalpy"], k)
+            parent = res["parent"]
+            engine.set_state(st["occupancy"][parent], np.zeros(R, dtype=np.uint64), np.full(R, t_new), reset_aux=False)
+            engine.set_counters(st["n_steps"], st["n_accepted"])
+        else:
+            if pa.n_steps != k:
+                raise ValueError("the device chooses and takes a step in one call: this schedule has a chosen step that was not taken")
+            pa.check_room()
+            res = engine.anneal_adaptive(pa.t_end, pa.overlap_value, pa.offset_words(k), npop=P, n_iter=pa.n_iter)
+            parent = res["parent"]
+            pa.append(res["temperature"], res["reached"], res["forced"])
+            pa.record(parent, res["qsum"], res["href"], k)
+        pa.overlaps[k] = [pa.overlap(res["q"][p * n:(p + 1) * n]) for p in range(P)]
         if history is not None:
             history.append(np.array(parent))
         engine.run(int(steps_per_temperature))
