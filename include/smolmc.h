@@ -297,6 +297,27 @@ int smolmc_get_wl_windows(smolmc_handle *h, double *vmin /* R */, double *vmax /
  * Refused like smolmc_set_wl_windows, and while no windows are set. */
 int smolmc_exchange_wl(smolmc_handle *h, int npairs, const int32_t *pairs /* npairs x 2 estimators, host */,
                        const double *log_u /* npairs, host */, int64_t *stats /* npairs x 2 in/out, host, or NULL */);
+/* The second half of the method: the copies of a window go through the Wang-Landau stages together.  Entropy S,
+ * histogram and modification factor m are in ESTIMATOR order (smolmc_get_wl); group g is the estimators g * copies ..
+ * g * copies + copies - 1, G = R / copies groups.  Per group, in this order:
+ *   status 2  the copies' factors are not all bitwise equal: the group is left alone;
+ *   flat(e):  V = {i : S_e[i] > 0}, n = |V|; not flat if n < 2; mean = (double) (sum over V of hist_e[i], in integers) /
+ *             (double) n; thr = wl_flatness * mean (one rounding each); flat iff (double) hist_e[i] > thr for every i in V
+ *             (the criterion of the sampling kernels' own check);
+ *   status 0  some copy of the group is not flat: the group is left alone;
+ *   status 1  otherwise, for every bin i, also one no copy visited: a = S_e0[i], then a = a + S_e0+c[i] for c = 1 ..
+ *             copies - 1 in that order, and S_e[i] = a / (double) copies for every copy; the histogram of every copy
+ *             becomes 0 and the factor of every copy m / wl_mod_divisor.
+ * A bin that some copies never visited takes the plain mean with their zeros: every copy then sees it as visited.
+ * Occurrences, mean features, step counters and the walker -> estimator map are not touched.  Queued on the handle's
+ * stream: with both outputs NULL the call only queues work, with either it waits for the kernel.  Valid on EVERY
+ * Wang-Landau handle, with or without per-walker windows (without: every estimator has the config's window; copies = R
+ * is plain multi-walker Wang-Landau with one shared ln g).  Refused, naming the reason: on handles that are not
+ * Wang-Landau and on distance handles; for copies < 1 or copies that does not divide R; while windows are set and the
+ * estimators of a group do not have bitwise one [vmin, vmax) (names the group and the first offending estimator); and on
+ * a handle with wl_check_period != 0, whose kernels would reset single copies behind the merge (create it with 0). */
+int smolmc_wl_synchronise(smolmc_handle *h, int copies, int32_t *status_out /* R / copies, host, or NULL */,
+                          double *mod_factor_out /* R / copies, host, or NULL: the groups' factors after the call (copy 0's) */);
 /* Population annealing (Hukushima & Iba 2003; Machta, PRE 82, 026704): resample and clone walkers on the device.
  * smolmc_resample clones by an explicit map (host, R entries): slot m takes the state of slot parent[m] -- occupancy,
  * features, enthalpy, accepted flag, bias and Ewald field; every source must map to itself (parent[parent[m]] ==

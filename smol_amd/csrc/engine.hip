@@ -2813,6 +2813,46 @@ extern "C" int smolmc_exchange_wl(smolmc_handle *h, int npairs, const int32_t *p
     return stats ? pair_exchange_stats(h, npairs, st.acc, stats) : 0;
 }
 
+// ---- the merge of a window's copies (smolmc_wl_synchronise): the merge mode of wl_exchange_kernel ---------------------
+// Valid on every Wang-Landau family: entropy, histogram and factor are the same three arrays for all of them, in
+// estimator order; without windows every estimator has the config's window.
+static int wl_synchronise_refused(const smolmc_handle *h, int copies) {
+    const std::string w("smolmc_wl_synchronise");
+    if (h->dist || h->cfg.kernel_type != SMOLMC_KERNEL_WANGLANDAU)
+        return fail(w + ": the handle is not a Wang-Landau kernel (only those have entropies to merge)");
+    if (copies < 1 || h->R % copies)
+        return fail(w + ": copies = " + std::to_string(copies) + " is not a divisor of the handle's " + std::to_string(h->R) +
+                    " estimators (group g is the estimators g * copies .. g * copies + copies - 1)");
+    if (!h->wl_win_min.empty())
+        for (int e = 0; e < h->R; ++e) {
+            const int e0 = e - e % copies;
+            if (memcmp(&h->wl_win_min[e], &h->wl_win_min[e0], 8) || memcmp(&h->wl_win_max[e], &h->wl_win_max[e0], 8))
+                return fail(w + ": group " + std::to_string(e / copies) + " does not have one window: estimator " + std::to_string(e) +
+                            " differs from estimator " + std::to_string(e0) + " (only copies of one window [vmin, vmax) are merged)");
+        }
+    if (h->cfg.wl_check_period != 0)
+        return fail(w + ": the handle checks flatness inside the sampling kernels every " + std::to_string(h->cfg.wl_check_period) +
+                    " steps, which would reset single copies behind the merge (create the handle with check period 0)");
+    return 0;
+}
+
+extern "C" int smolmc_wl_synchronise(smolmc_handle *h, int copies, int32_t *status_out, double *mod_factor_out) {
+    if (!h) return fail("null handle");
+    TRY(wl_synchronise_refused(h, copies));
+    HIPCHK(hipSetDevice(h->device));
+    const size_t G = (size_t)(h->R / copies);
+    if (!status_out && !mod_factor_out) return smolmc_wl_merge_launch(h, copies, nullptr, nullptr);
+    DevScratch out; // factors [G] f64 | status words [G] i32 (d_pair_stage holds R / 2 entries: copies = 1 has R groups)
+    TRY(out.alloc(G * 12));
+    TRY(smolmc_wl_merge_launch(h, copies, (int32_t *)(out.as<double>() + G), out.as<double>()));
+    std::vector<unsigned char> host(G * 12);
+    HIPCHK(hipMemcpyAsync(host.data(), out.p, G * 12, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (mod_factor_out) memcpy(mod_factor_out, host.data(), G * 8);
+    if (status_out) memcpy(status_out, host.data() + G * 8, G * 4);
+    return 0;
+}
+
 // ---- smolmc_set_state in stages (the first one is shared with smolmc_set_temperature) --------------------------------
 // the temperatures of the call in force: the state points named after their walkers, the inverse temperatures uploaded
 static int apply_temperatures(smolmc_handle *h, const double *temperature) {

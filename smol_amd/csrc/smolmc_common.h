@@ -1161,6 +1161,9 @@ int smolmc_grid_exchange_launch(smolmc_handle *h, int npairs, const int32_t *pai
 // wl_exchange.hip: one exchange attempt between the walkers that hold the estimators pairs[p][0] and pairs[p][1]
 // (device arrays; the pairs disjoint), decided and applied on the device, queued on the handle's stream
 int smolmc_wl_exchange_launch(smolmc_handle *h, int npairs, const int32_t *pairs, const double *log_u, int32_t *accepted);
+// ... the kernel's merge mode: every group of `copies` estimators (copies divides R) that has one factor and only flat
+// copies takes the mean entropy, empty histograms and the next factor; status / factor [R / copies] device arrays or null
+int smolmc_wl_merge_launch(smolmc_handle *h, int copies, int32_t *status, double *factor);
 // ... weights, systematic resampling and the stable assignment of npop populations of R / npop walkers: S.parent, S.q,
 // S.qsum, S.href from the enthalpies, the temperatures in force, S.beta_new and S.word; queued on the handle's stream.
 // With `search` the kernel chooses the step first and writes S.beta_new, S.T_new and S.flags itself.

@@ -40,6 +40,7 @@ SYMBOLS = {
     "smolmc_set_wl_windows": (C.c_int, [_HP, _f64p, _f64p]),
     "smolmc_get_wl_windows": (C.c_int, [_HP, _f64p, _f64p, _i32p]),
     "smolmc_exchange_wl": (C.c_int, [_HP, C.c_int, _i32p, _f64p, _i64p]),
+    "smolmc_wl_synchronise": (C.c_int, [_HP, C.c_int, _i32p, _f64p]),
     "smolmc_resample": (C.c_int, [_HP, _i32p]),
     "smolmc_anneal_resample": (C.c_int, [_HP, C.c_int, _f64p, _u64p, _i32p, _u64p, _u64p, _f64p]),
     "smolmc_anneal_adaptive": (C.c_int, [_HP, C.c_int, C.c_double, C.c_uint32, C.c_int, _u64p, _f64p, _i32p, _i32p, _u64p, _u64p, _f64p]),
@@ -364,6 +365,21 @@ class Engine:
         t swap them when both enthalpies lie in both windows and the move is accepted against ``log_u`` (npairs).
         ``stats`` as in ``exchange_grid``."""
         self._exchange_pairs(self._lib.smolmc_exchange_wl, pairs, log_u, stats)
+
+    def wl_synchronise(self, copies, fetch=True):
+        """One merge attempt of the copies of every window on the device (smolmc_wl_synchronise): group g is the
+        estimators g * copies .. g * copies + copies - 1.  A group whose copies have one modification factor and are all
+        flat takes the mean of their entropies in every copy, empty histograms and the factor divided by the config's
+        divisor (``parallel.WLWindows.synchronise`` is the definition).  Valid on every Wang-Landau handle created with
+        check period 0, with or without per-walker windows.  Returns dict(status (R / copies,) int32: 0 not all flat, 1
+        merged, 2 factors differ; mod_factor (R / copies,): the groups' factors after the call) -- or None with
+        ``fetch=False``, when the call only queues work on the handle's stream."""
+        copies = int(copies)
+        groups = self.R // copies if copies >= 1 and self.R % copies == 0 else 0  # (else: the call refuses and says why)
+        out = dict(status=np.empty(groups, dtype=np.int32), mod_factor=np.empty(groups)) if fetch else None
+        self._chk(self._lib.smolmc_wl_synchronise(self._h, copies, _p(out["status"], C.c_int32) if out else None,
+                                                  _p(out["mod_factor"], C.c_double) if out else None))
+        return out
 
     # ---- population annealing ------------------------------------------------------------
     def resample(self, parent):

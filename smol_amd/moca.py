@@ -1906,6 +1906,7 @@ class Sampler:
         self._walker_mu = None      # per-walker chemical potentials of this rank's walkers (list of dicts), or None
         self._walker_mu_dirty = False  # ... not yet on the engine
         self._wl_windows = None     # replica-exchange Wang-Landau: the parallel.WLWindows of this sampler's walkers
+        self._wl_synchronise = False  # ... whose copies are merged between launches: the handle has check period 0
         self._observables = None    # observables.Observables counted on the device for every sample, or None
         self._minima = None         # minima.Minima: the lowest samples are kept on the device, or None
         self._minima_offers = 0     # samples offered to the record since it was last emptied
@@ -1918,7 +1919,7 @@ class Sampler:
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
                       nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, windows=None,
                       observables=None, minima=None, statistics=None, structure_factor=None, connectivity=None,
-                      patterns=None, **kwargs):
+                      patterns=None, synchronise=False, **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
         'swap'; default kernel Metropolis; one kernel (seed) per walker.
 
@@ -1926,6 +1927,10 @@ class Sampler:
         and ``bin_size`` are then the GLOBAL range the windows cut up; kernel w is estimator w of ``windows`` and is
         built with that estimator's window (its ``levels`` / ``entropy`` / ``histogram`` are the estimator's, whichever
         walker updates it), ``nwalkers`` defaults to ``windows.R``, and ``run_exchange`` samples with exchanges.
+        ``synchronise=True`` (with ``windows``): the copies of a window go through the Wang-Landau stages together --
+        the engine handle is created with check period 0 (the kernels' ``check_period`` keeps the value given), and
+        ``run_exchange(..., sync_every=k)`` merges them between launches (``Engine.wl_synchronise``); on such a sampler
+        nothing else checks flatness, so a run without ``sync_every`` keeps every factor where it is.
 
         ``observables``: an ``observables.Observables`` -- its kind counts and pair counts are evaluated on the device
         for every sample and traced as ``species_counts`` (K,) and ``pair_counts`` (n_shells, K, K), int32.
@@ -1959,9 +1964,15 @@ class Sampler:
             raise ValueError("patterns= with windows=: the samples of per-walker windows do not come from the sample ring")
         if patterns is not None and observables is None:
             raise ValueError("patterns= needs observables=: the class maps of a pattern spec index the kinds of the observables")
+        if synchronise and windows is None:
+            raise ValueError("synchronise=True needs windows=: the copies of a window are what is merged "
+                             "(parallel.WLWindows(n_windows=1, copies=nwalkers) for plain multi-walker Wang-Landau)")
         if windows is not None:
             sampler = cls._from_ensemble_windows(ensemble, windows, *args, step_type=step_type, kernel_type=kernel_type, seeds=seeds,
                                                  nwalkers=nwalkers, rank=rank, world_size=world_size, device=device, **kwargs)
+            if synchronise and sampler._kernels[0]._mod_callable is not None:
+                raise ValueError("synchronise=True with a callable mod_update: the merge divides the factor by a constant")
+            sampler._wl_synchronise = bool(synchronise)
             if minima is not None:
                 sampler._set_minima(minima)
             if statistics is not None:
@@ -2321,12 +2332,13 @@ class Sampler:
                                 intercepts=getattr(k0.bias, "intercepts", None))
             if isinstance(k0, WangLandau):
                 # (a callable mod_update: flatness checks on the host, check period 0 switches the
-                # device's own check off)
+                # device's own check off; synchronise=True likewise: the copies of a window are checked together,
+                # between launches, by Engine.wl_synchronise)
                 cfg = capi.make_config(
                     len(self._kernels), capi.KERNEL_WANGLANDAU, STEP_TYPES[k0.step_type], self._device,
                     min_enthalpy=k0._window[0], max_enthalpy=k0._window[1], bin_size=k0._window[2],
                     flatness=k0.flatness, mod_factor=k0._m0, mod_update=k0._mod_divisor,
-                    check_period=0 if k0._mod_callable is not None else k0.check_period,
+                    check_period=0 if (k0._mod_callable is not None or self._wl_synchronise) else k0.check_period,
                     update_period=k0.update_period,
                 )
             else:
@@ -2679,18 +2691,33 @@ class Sampler:
         # the device now holds the last recorded sample (see _load_state)
         self._resume_at = (id(self.samples), self.samples.num_samples)
 
-    def _run_exchange_wl(self, n_exchanges, steps_between, initial_occupancies, thin_by, wx):
+    def _run_exchange_wl(self, n_exchanges, steps_between, initial_occupancies, thin_by, wx, sync_every=None,
+                         final_mod_factor=None):
         """run_exchange for replica-exchange Wang-Landau, see there."""
         if wx is not self._wl_windows:
             raise ValueError("run_exchange(windows=) takes the WLWindows this sampler was built with (Sampler.from_ensemble(windows=))")
+        if sync_every is not None and not self._wl_synchronise:
+            raise ValueError("sync_every= needs a sampler built with Sampler.from_ensemble(..., windows=, synchronise=True): "
+                             "its handle has check period 0, so that no copy of a window leaves its stage alone")
+        if sync_every is not None and int(sync_every) < 1:
+            raise ValueError("sync_every must be at least 1")
+        if final_mod_factor is not None and sync_every is None:
+            raise ValueError("final_mod_factor= needs sync_every=: the windows' factors are those of the merge attempts")
         thin_by = int(steps_between if thin_by is None else thin_by)
         self._need_start(initial_occupancies)
         self._load_state(initial_occupancies)
         eng = self._get_engine()
-        for _ in range(int(n_exchanges)):
+        for i in range(int(n_exchanges)):
             for block in self._sample_blocks(steps_between, None, thin_by, state_loaded=True):
                 self.samples.append_block(block, thinned_by=thin_by)
             wx.attempt(eng)
+            if sync_every is not None and (i + 1) % int(sync_every) == 0:
+                wx.sync_attempt(eng)
+                if final_mod_factor is not None and wx.converged(final_mod_factor):
+                    break
+        if sync_every is not None:
+            self.samples.metadata["wl_synchronise"] = dict(sync_every=int(sync_every), merges=wx.merges.tolist(),
+                                                           mod_factor=wx.mod_factor.tolist())
         wx.estimator_of = eng.wl_windows()[2].astype(np.int64)
         self._resume_at = None  # (the last sample precedes the last exchange: a continuation reloads nothing it could trust)
         return wx
@@ -2703,12 +2730,17 @@ class Sampler:
         ln_g, _, visited = self._wl_windows.join(self._get_engine().get_wl()["entropy"])
         return self._wl_windows.levels(), ln_g, visited
 
-    def run_exchange(self, n_exchanges, steps_between, initial_occupancies=None, thin_by=None, grid=None, windows=None):
+    def run_exchange(self, n_exchanges, steps_between, initial_occupancies=None, thin_by=None, grid=None, windows=None,
+                     sync_every=None, final_mod_factor=None):
         """``windows`` (a ``parallel.WLWindows``, the one of ``Sampler.from_ensemble(windows=)``): replica-exchange
         Wang-Landau -- ``n_exchanges`` times ``steps_between`` steps on every walker, then one exchange attempt between
         neighbouring windows (``Engine.exchange_wl``), the even and the odd move taking turns.  Walkers swap ESTIMATORS,
         never occupancies: the int32 trace ``wl_estimator`` says which estimator each walker held at every sample, the
-        Wang-Landau traces (entropy, histogram, ...) are in estimator order.  Returns ``windows``.  Otherwise:
+        Wang-Landau traces (entropy, histogram, ...) are in estimator order.  ``sync_every=k`` (a sampler built with
+        ``synchronise=True``): after every k-th attempt the copies of every window are merged on the device when all of
+        them are flat (``windows.sync_attempt``); ``samples.metadata["wl_synchronise"]`` records ``sync_every``, the
+        ``merges`` per window and the windows' ``mod_factor``.  ``final_mod_factor``: the run ends at the merge attempt
+        after which every window's factor is at or below it.  Returns ``windows``.  Otherwise:
 
         Sampling with replica exchange across a mu-T grid (hyper-parallel tempering): ``n_exchanges`` times
         ``steps_between`` steps on every walker, then one exchange attempt, decided and applied on the device
@@ -2724,7 +2756,9 @@ class Sampler:
 
         if windows is not None or (grid is None and self._wl_windows is not None):
             return self._run_exchange_wl(n_exchanges, steps_between, initial_occupancies, thin_by,
-                                         windows if windows is not None else self._wl_windows)
+                                         windows if windows is not None else self._wl_windows, sync_every, final_mod_factor)
+        if sync_every is not None or final_mod_factor is not None:
+            raise ValueError("sync_every= / final_mod_factor= belong to replica-exchange Wang-Landau (windows=)")
         return self._run_exchange_grid(n_exchanges, steps_between, initial_occupancies, thin_by, grid)
 
     def _run_exchange_grid(self, n_exchanges, steps_between, initial_occupancies, thin_by, grid):

@@ -562,7 +562,9 @@ class WLWindows(PairExchange):
         ex = ((S_s[ia(Ea)] - S_s[ia(Eb)]) + S_t[ib(Eb)]) - S_t[ib(Ea)];   accept iff ex >= 0 or log u < ex
 
     and the walkers swap estimators.  ``decide`` is this move in NumPy, in the operation order of the device kernel
-    (wl_exchange.hip); ``join`` makes one ln g of the pieces."""
+    (wl_exchange.hip); ``join`` makes one ln g of the pieces.  ``synchronise`` is the second half of the method -- the
+    copies of a window pass the flatness check together and take the mean of their entropies -- ``sync_attempt`` runs it
+    on the device, ``merges`` and ``mod_factor`` keep its count and the factor per window."""
 
     MOVES = (0, 1)
     ENGINE_CALL = "exchange_wl"
@@ -603,6 +605,85 @@ class WLWindows(PairExchange):
         self.R = n * self.copies
         self.estimator_of = np.arange(self.R)
         self._init_exchange(seed, {m: self._make_pairs(m) for m in self.MOVES})  # (philox_seed: `seed` is the method below)
+        self.merges = np.zeros(n, dtype=np.int64)   # merges of every window's copies so far (sync_attempt)
+        self.mod_factor = np.full(n, np.nan)        # every window's modification factor at the latest sync_attempt
+
+    # ---- the second half of the method: the copies of a window go through the Wang-Landau stages together --------------
+    @staticmethod
+    def flat(entropy_row, histogram_row, flatness):
+        """The flatness criterion of one estimator, as the sampling kernels apply it (wl_multi_flatness_check): over the
+        visited bins V = {i: S[i] > 0}, n = |V| >= 2, every float(hist[i]) > flatness * (float(sum of hist over V) /
+        float(n)); the mean and the threshold are one rounding each."""
+        S, hist = np.asarray(entropy_row, dtype=np.float64), np.asarray(histogram_row, dtype=np.int64)
+        V = S > 0
+        n = int(V.sum())
+        if n < 2:
+            return False
+        mean = np.float64(int(hist[V].sum(dtype=np.int64))) / np.float64(n)
+        thr = np.float64(flatness) * mean
+        return bool(np.all(hist[V].astype(np.float64) > thr))
+
+    def synchronise(self, entropy, histogram, mod_factor, copies=None, flatness=0.8, divisor=2.0):
+        """The merge of the copies of every window (Vogel, Li, Wuest, Landau, PRL 110, 210603), on the host: entropy
+        (R, L) float64, histogram (R, L) int64, mod_factor (R,), all in ESTIMATOR order as ``Engine.get_wl`` returns
+        them; group g is the estimators g * copies .. g * copies + copies - 1 (``copies`` defaults to ``self.copies``:
+        group g is window g).  Per group, in this order:
+
+          status 2  the copies' factors are not all bitwise equal: the group is left alone;
+          status 0  some copy is not ``flat``: the group is left alone;
+          status 1  every bin i, visited or not: a = S_e0[i], a = a + S_e0+c[i] for c = 1 .. copies - 1 in that order,
+                    S_e[i] = a / float(copies) for every copy; every copy's histogram becomes 0, its factor m / divisor.
+
+        Returns dict(status (G,) int32, entropy, histogram, mod_factor): new arrays, the inputs are not written.  The
+        definition the merge mode of wl_exchange_kernel (``Engine.wl_synchronise``) is tested against, bit for bit."""
+        S = np.array(entropy, dtype=np.float64, ndmin=2)
+        hist = np.array(histogram, dtype=np.int64, ndmin=2)
+        m = np.array(mod_factor, dtype=np.float64).reshape(-1)
+        copies = self.copies if copies is None else int(copies)
+        R = len(m)
+        if S.shape != hist.shape or S.shape[0] != R:
+            raise ValueError(f"entropy {S.shape}, histogram {hist.shape} and mod_factor {m.shape} do not belong together")
+        if copies < 1 or R % copies:
+            raise ValueError(f"copies = {copies} does not divide the {R} estimators")
+        status = np.zeros(R // copies, dtype=np.int32)
+        for g in range(R // copies):
+            e0 = g * copies
+            if len(set(m[e0:e0 + copies].view(np.uint64).tolist())) != 1:
+                status[g] = 2
+                continue
+            if not all(self.flat(S[e], hist[e], flatness) for e in range(e0, e0 + copies)):
+                continue
+            a = S[e0].copy()
+            for c in range(1, copies):  # (written out: NumPy's pairwise reduction sums in another order)
+                a = a + S[e0 + c]
+            S[e0:e0 + copies] = a / np.float64(copies)
+            hist[e0:e0 + copies] = 0
+            m[e0:e0 + copies] = m[e0] / np.float64(divisor)
+            status[g] = 1
+        return dict(status=status, entropy=S, histogram=hist, mod_factor=m)
+
+    def sync_attempt(self, engine, host=False):
+        """One merge attempt of every window's copies on the device (``Engine.wl_synchronise``); ``merges`` counts the
+        windows that merged, ``mod_factor`` holds every window's factor after the call.  ``host=True``: the same through
+        the host -- ``get_wl``, ``synchronise``, ``set_wl`` -- the cross-check of the device path, and what it is timed
+        against.  Returns the status (n_windows,)."""
+        if host:
+            wl = engine.get_wl()
+            res = self.synchronise(wl["entropy"], wl["histogram"], wl["mod_factor"], flatness=engine.config.wl_flatness,
+                                   divisor=engine.config.wl_mod_divisor)
+            if (res["status"] == 1).any():
+                engine.set_wl(entropy=res["entropy"], histogram=res["histogram"], mod_factor=res["mod_factor"])
+            status, factor = res["status"], res["mod_factor"][::self.copies]
+        else:
+            res = engine.wl_synchronise(self.copies)
+            status, factor = res["status"], res["mod_factor"]
+        self.merges += status == 1
+        self.mod_factor = np.array(factor, dtype=np.float64)
+        return status
+
+    def converged(self, final_mod_factor):
+        """Whether every window's factor (at the latest ``sync_attempt``) is at or below ``final_mod_factor``."""
+        return bool(np.all(self.mod_factor <= float(final_mod_factor)))
 
     def _make_pairs(self, move):
         lo = np.arange(int(move), self.n_windows - 1, 2)
@@ -726,7 +807,8 @@ class WLWindows(PairExchange):
                            + ", ".join(f"[{self.window_min[k]:.6g}, {self.window_max[k]:.6g})" for k in never))
 
 
-def run_wl_exchange(engine, wx, n_exchanges, steps_between, host_decide=False, history=None):
+def run_wl_exchange(engine, wx, n_exchanges, steps_between, host_decide=False, history=None, sync_every=None,
+                    final_mod_factor=None):
     """Alternate ``steps_between`` Wang-Landau steps on every walker with one exchange attempt between the windows of
     ``wx``, alternating its even and odd move.  ``engine`` holds ``wx.R`` walkers with ``set_wl_windows(wx.vmin,
     wx.vmax)`` in force and their state loaded.  Default: the attempt is decided and applied on the device
@@ -734,13 +816,21 @@ def run_wl_exchange(engine, wx, n_exchanges, steps_between, host_decide=False, h
     ``host_decide=True``: state and entropies are read back, ``wx.decide`` takes the decisions, and an accepted pair
     swaps its two CONFIGURATIONS through ``set_state(..., reset_aux=False)`` -- the estimators stay with their walkers;
     the cross-check of the device path, and what it is timed against.  ``history``: a list that receives the walker
-    (host: configuration) -> estimator map after every attempt."""
+    (host: configuration) -> estimator map after every attempt.
+    ``sync_every=k``: after every k-th attempt the copies of every window are merged when all of them are flat
+    (``wx.sync_attempt``: on the device, with ``host_decide=True`` through ``get_wl`` / ``wx.synchronise`` / ``set_wl``);
+    the handle must have been created with check period 0, so that no copy leaves its stage alone.
+    ``final_mod_factor``: the loop ends after the merge attempt at which every window's factor is at or below it."""
     if engine.R != wx.R:
         raise ValueError(f"the windows have {wx.R} estimators, the engine {engine.R} walkers")
+    if final_mod_factor is not None and sync_every is None:
+        raise ValueError("final_mod_factor needs sync_every: the windows' factors are those of the merge attempts")
+    if sync_every is not None and int(sync_every) < 1:
+        raise ValueError("sync_every must be at least 1")
     identity = np.arange(wx.R)
     if host_decide:
         wx.estimator_of = np.asarray(wx.estimator_of).copy()  # configuration -> estimator (= the walker it sits on)
-    for _ in range(int(n_exchanges)):
+    for i in range(int(n_exchanges)):
         engine.run(steps_between)
         if host_decide:
             move = wx.move_of(wx.calls)
@@ -762,6 +852,10 @@ def run_wl_exchange(engine, wx, n_exchanges, steps_between, host_decide=False, h
                 wx.estimator_of = engine.wl_windows()[2].astype(np.int64)
         if history is not None:
             history.append(np.array(wx.estimator_of))
+        if sync_every is not None and (i + 1) % int(sync_every) == 0:
+            wx.sync_attempt(engine, host=host_decide)
+            if final_mod_factor is not None and wx.converged(final_mod_factor):
+                break
     if not host_decide:
         wx.estimator_of = engine.wl_windows()[2].astype(np.int64)
     return wx
