@@ -561,8 +561,9 @@ typedef struct smolmc_statistics {
                              * of the observables in force (k < K, as a double), 1 + F + K the weighted sum below,
                              * 2 + F + K + i intensity i of the structure-factor spec in force (i < I, see
                              * smolmc_set_structure; with no spec set the range ends at the weighted sum); behind them
-                             * the connectivity numbers and the pattern cells (smolmc_get_sample_connectivity,
-                             * smolmc_get_sample_patterns) */
+                             * the connectivity numbers, the pattern cells and the environment cells
+                             * (smolmc_get_sample_connectivity, smolmc_get_sample_patterns,
+                             * smolmc_get_sample_environments) */
     int n_weights;          /* the weighted sum: sum_{i < n_weights} weights[i] * features[i] left to right, the value of */
     const double *weights;  /* a minima record (n_weights <= F) */
     int n_levels;           /* blocking levels, 0..32 */
@@ -765,6 +766,61 @@ int smolmc_eval_patterns(smolmc_handle *h, const int32_t *occ /* nocc x N, or NU
  * ends where it ends without); smolmc_update_statistics counts the patterns of the current states first. */
 #define SMOLMC_SAMPLE_PATTERNS 256
 int smolmc_get_sample_patterns(smolmc_handle *h, int32_t *cells);
+
+/* ---- environments: coordination environments of sampled states, counted on the device ---------------------------------
+ * (no reference counterpart).  An environment spec rests on the observables in force: the kind of (site, code) is
+ * kind_base[site] + code and there are K kinds.  The spec holds E sets.  Set e has a width z_e, A_e centre classes and B_e
+ * neighbour classes, the maps centre_class_of_kind[e][K] (values -1 .. A_e - 1) and neigh_class_of_kind[e][K] (values
+ * -1 .. B_e - 1), and the centres centre_ptr[e] .. centre_ptr[e + 1], each a site with a row of z_e neighbour sites; a slot
+ * that holds -1 is empty.  Per occupancy row and set, for every centre as listed, with a = centre_class[kind(centre)]:
+ *   n_b = #{slots of its row that are not empty, whose site is counted and whose neighbour class is b}
+ *   code = a (z + 1)^B + sum_b n_b (z + 1)^(B - 1 - b)          (row-major, class 0 most significant)
+ *   cells[cell_ptr[e] + code] += 1
+ * A centre is skipped when it is not counted (kind_base < 0) or a == -1.  A slot whose site is not counted or has class -1
+ * adds to no n_b; it does not skip the centre.  Duplicate centres, slots that repeat a site and slots that name the centre
+ * count as they stand.  cell_ptr[e] = sum_{u < e} A_u (z_u + 1)^B_u, n_cells = cell_ptr[E]: the plain product, not the
+ * simplex.  Everything is int32; smol_amd/environments.py is the same in NumPy and the device matches it entry for entry.
+ * The count runs in the observables' kernel, behind the patterns.  Site numbers are the caller's.  The engine copies and
+ * uploads everything. */
+#define SMOLMC_MAX_ENV_SETS 8
+#define SMOLMC_MAX_ENV_WIDTH 64          /* z: a count of neighbours is an 8-bit field of one register */
+#define SMOLMC_MAX_ENV_CENTRE_CLASSES 15 /* A: the classes of a site are staged as two nibbles of one byte, 0xf: none */
+#define SMOLMC_MAX_ENV_NEIGH_CLASSES 4   /* B */
+#define SMOLMC_MAX_ENV_CELLS 4096        /* n_cells: 16 KB of int32 in LDS */
+typedef struct smolmc_environments {
+    int n_sets;                          /* E, 1..SMOLMC_MAX_ENV_SETS */
+    const int32_t *width;                /* [E], each 1..SMOLMC_MAX_ENV_WIDTH */
+    const int32_t *n_centre_classes;     /* [E], each 1..SMOLMC_MAX_ENV_CENTRE_CLASSES */
+    const int32_t *n_neigh_classes;      /* [E], each 1..SMOLMC_MAX_ENV_NEIGH_CLASSES */
+    const int32_t *centre_class_of_kind; /* [E x K], K of the observables in force; -1 .. n_centre_classes[e] - 1 */
+    const int32_t *neigh_class_of_kind;  /* [E x K]; -1 .. n_neigh_classes[e] - 1 */
+    const int64_t *centre_ptr;           /* [E + 1] centres, ascending from 0 */
+    const int32_t *centres;              /* [centre_ptr[E]] sites */
+    const int32_t *neighbours;           /* the rows of set 0, then of set 1 ...: sum_e n_e x width[e] sites, -1: empty */
+} smolmc_environments;
+/* Sets (NULL: removes) the environment spec of the handle.  Refused, each naming its reason: no observables set; E, a
+ * width or a number of classes outside its range; a class outside its range; a centre or a non-empty slot out of range;
+ * more than SMOLMC_MAX_ENV_CELLS cells; a launch (row, observables, patterns and environments together) that does not fit
+ * the 64 KB of LDS a workgroup takes; while a block recorded with SMOLMC_SAMPLE_ENVIRONMENTS waits in the ring; while a
+ * statistics record with environment columns is set.  A refused call leaves the handle's spec as it was.  While a spec is
+ * set smolmc_set_observables is refused, and smolmc_set_patterns checks the LDS of the launch with both. */
+int smolmc_set_environments(smolmc_handle *h, const smolmc_environments *spec);
+/* E, n_cells and the centres of all sets in force (all 0: none set) */
+int smolmc_environments_shape(smolmc_handle *h, int *n_sets, int *n_cells, int *n_centres);
+/* cells [nocc x n_cells] and codes [nocc x n_centres] (the set-local code of every centre, set after set, or -1 for a
+ * skipped centre) of nocc occupancies (host, int32 like smolmc_eval_full), or, with occ == NULL, of the walkers' current
+ * states (nocc = R then).  Either output may be NULL. */
+int smolmc_eval_environments(smolmc_handle *h, const int32_t *occ /* nocc x N, or NULL */, int nocc, int32_t *cells,
+                             int32_t *codes);
+/* With SMOLMC_SAMPLE_ENVIRONMENTS (512, flags bit 9) smolmc_run_sampled adds the column [rows x n_cells] (int32) to the
+ * block, filled on the device by the launch that counts kinds, pairs and patterns; without SMOLMC_SAMPLE_OCCUPANCY the rows
+ * never leave the device.  The flag is refused while no spec is set.  This call reads the column of the block the next
+ * smolmc_get_samples* call delivers ([nsamples x R x n_cells]) and does not mark it delivered, like
+ * smolmc_get_sample_patterns; an error when that block was recorded without the flag.  In a statistics record the column
+ * sources 2 + F + K + I + 24 G + P + c (P the pattern cells in force) read cell c as a double (with no spec set the range
+ * ends where it ends without); smolmc_update_statistics counts the environments of the current states first. */
+#define SMOLMC_SAMPLE_ENVIRONMENTS 512
+int smolmc_get_sample_environments(smolmc_handle *h, int32_t *cells);
 
 /* Same loop driven by host-provided proposals ("replay mode"): what
  * StandardSingleStepMixin.single_step (kernel/base.py:145-166) does after mcusher.propose_step

@@ -84,6 +84,12 @@ MAX_PATTERN_SETS = 8            # SMOLMC_MAX_PATTERN_SETS
 MAX_PATTERN_ARITY = 8           # SMOLMC_MAX_PATTERN_ARITY
 MAX_PATTERN_CLASSES = 255       # SMOLMC_MAX_PATTERN_CLASSES
 MAX_PATTERN_CELLS = 4096        # SMOLMC_MAX_PATTERN_CELLS
+SAMPLE_ENVIRONMENTS = 512       # ... the environment cells of every row (smolmc_set_environments)
+MAX_ENV_SETS = 8                # SMOLMC_MAX_ENV_SETS
+MAX_ENV_WIDTH = 64              # SMOLMC_MAX_ENV_WIDTH
+MAX_ENV_CENTRE_CLASSES = 15     # SMOLMC_MAX_ENV_CENTRE_CLASSES
+MAX_ENV_NEIGH_CLASSES = 4       # SMOLMC_MAX_ENV_NEIGH_CLASSES
+MAX_ENV_CELLS = 4096            # SMOLMC_MAX_ENV_CELLS
 MAX_STEP_FLIPS = 8              # SMOLMC_MAX_STEP_FLIPS
 STEP_ROW = 2 * MAX_STEP_FLIPS   # SMOLMC_STEP_ROW: int32 per step record (site, code) x 8, -1 = no flip
 
@@ -268,6 +274,22 @@ class smolmc_patterns(C.Structure):
         ("class_of_kind", _i32p),
         ("tuple_ptr", _i64p),
         ("sites", _i32p),
+    ]
+
+
+class smolmc_environments(C.Structure):
+    """Mirror of ``smolmc_environments`` (include/smolmc.h); ``environments.Environments.c_struct`` fills it."""
+
+    _fields_ = [
+        ("n_sets", C.c_int),
+        ("width", _i32p),
+        ("n_centre_classes", _i32p),
+        ("n_neigh_classes", _i32p),
+        ("centre_class_of_kind", _i32p),
+        ("neigh_class_of_kind", _i32p),
+        ("centre_ptr", _i64p),
+        ("centres", _i32p),
+        ("neighbours", _i32p),
     ]
 
 

@@ -3393,8 +3393,8 @@ __global__ void __launch_bounds__(256) sample_snapshot_kernel(const SnapshotArgs
 // A quantity exists when its own flag asks for it or a record reads it; every reader reads the same column (the statistics
 // record the counts the observables' flag or the minima record asked for, else its own).
 struct ColumnUse {
-    bool min_counts, stat_counts, stat_inten, stat_conn, stat_pat; // what the records read
-    bool counts, pairs, sfac, conn, pat;                 // what is derived: kind counts, pair counts (with the observables' flag
+    bool min_counts, stat_counts, stat_inten, stat_conn, stat_pat, stat_env; // what the records read
+    bool counts, pairs, sfac, conn, pat, env;               // what is derived: kind counts, pair counts (with the observables' flag
                                                          // only), amplitudes with intensities, connectivity stats, pattern cells
 };
 static ColumnUse column_use(const smolmc_handle *h, int flags) {
@@ -3410,6 +3410,8 @@ static ColumnUse column_use(const smolmc_handle *h, int flags) {
     u.conn = (flags & SMOLMC_SAMPLE_CONNECTIVITY) || u.stat_conn;
     u.stat_pat = stats && h->stats.n_pat_cols > 0;                // (then obs.pat.n_cells == stats.PC, see smolmc_set_patterns)
     u.pat = (flags & SMOLMC_SAMPLE_PATTERNS) || u.stat_pat;
+    u.stat_env = stats && h->stats.n_env_cols > 0;                // (then obs.env.n_cells == stats.EC, see smolmc_set_environments)
+    u.env = (flags & SMOLMC_SAMPLE_ENVIRONMENTS) || u.stat_env;
     return u;
 }
 
@@ -3425,6 +3427,7 @@ struct RowSources {
     double *inten = nullptr;
     long long *conn = nullptr;
     int32_t *pat = nullptr;
+    int32_t *env = nullptr;
     uint64_t *min_key = nullptr;                      // scratch of the minima reduction [rows]
     int32_t *min_slot = nullptr;
 };
@@ -3437,15 +3440,16 @@ static RowSources walker_rows(const smolmc_handle *h) {
 // the derived columns of the rows, in one fixed order, then the offers to the records `flags` names; all on the handle's stream
 static int derive_and_offer(smolmc_handle *h, const RowSources &s, int flags, long long nsamples, long long thin_by) {
     const ColumnUse u = column_use(h, flags);
-    if (u.counts || u.pat) // (one launch stages the rows for kind counts, pair counts and pattern cells)
-        TRY(smolmc_obs_launch(h, s.occ, s.rows, u.counts ? s.counts : nullptr, u.pairs ? s.pairs : nullptr, u.pat ? s.pat : nullptr));
+    if (u.counts || u.pat || u.env) // (one launch stages the rows for kind counts, pair counts, pattern and environment cells)
+        TRY(smolmc_obs_launch(h, s.occ, s.rows, u.counts ? s.counts : nullptr, u.pairs ? s.pairs : nullptr, u.pat ? s.pat : nullptr,
+                              u.env ? s.env : nullptr, nullptr));
     if (u.sfac) TRY(smolmc_sfac_launch(h, s.occ, s.rows, s.amp, s.inten));
     if (u.conn) TRY(smolmc_conn_launch(h, s.occ, s.rows, s.conn, nullptr));
     if (flags & SMOLMC_SAMPLE_MINIMA)
         TRY(smolmc_min_launch(h, s.H, s.feat, s.occ, u.min_counts ? s.counts : nullptr, s.min_key, s.min_slot, nsamples, thin_by));
     if (flags & SMOLMC_SAMPLE_STATISTICS)
         TRY(smolmc_stat_launch(h, s.H, s.feat, u.stat_counts ? s.counts : nullptr, u.stat_inten ? s.inten : nullptr,
-                               u.stat_conn ? s.conn : nullptr, u.stat_pat ? s.pat : nullptr, nsamples));
+                               u.stat_conn ? s.conn : nullptr, u.stat_pat ? s.pat : nullptr, u.stat_env ? s.env : nullptr, nsamples));
     return 0;
 }
 
@@ -3479,11 +3483,12 @@ static int plan_block(const smolmc_handle *h, int64_t nsamples, int flags, Block
         {(flags & SMOLMC_SAMPLE_MINIMA) != 0, "minima"},          {(flags & SMOLMC_SAMPLE_STATISTICS) != 0, "statistics"},
         {(flags & SMOLMC_SAMPLE_CONNECTIVITY) != 0, "connectivity"}, {(flags & SMOLMC_SAMPLE_STRUCTURE) != 0, "structure factors"},
         {p.lazy_rows, "lazy cluster features"},                     {(flags & SMOLMC_SAMPLE_OBSERVABLES) != 0, "observables"},
-        {(flags & SMOLMC_SAMPLE_PATTERNS) != 0, "patterns"}};
+        {(flags & SMOLMC_SAMPLE_PATTERNS) != 0, "patterns"},      {(flags & SMOLMC_SAMPLE_ENVIRONMENTS) != 0, "environments"}};
     for (const auto &t : too_many)
         if (t.applies && rows > 0x7fffffffull) return fail(std::string(t.noun) + ": more than 2^31 sample rows in one block");
     p.rows = rows;
-    p.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || p.lazy_rows || u.counts || u.sfac || u.conn || u.pat || (flags & SMOLMC_SAMPLE_MINIMA);
+    p.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || p.lazy_rows || u.counts || u.sfac || u.conn || u.pat || u.env ||
+            (flags & SMOLMC_SAMPLE_MINIMA);
     const size_t sf_amp = (size_t)h->sfac.Q * h->sfac.K * 2 * 8, sf_inten = (size_t)h->sfac.I * 8; // bytes per row
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t o = at; at += up256(bytes); return o; };
@@ -3511,6 +3516,7 @@ static int plan_block(const smolmc_handle *h, int64_t nsamples, int flags, Block
         }
         if (u.conn && here(SMOLMC_SAMPLE_CONNECTIVITY)) c.o_conn = take(rows * (size_t)h->conn.G * SMOLMC_CONN_STATS * 8);
         if (u.pat && here(SMOLMC_SAMPLE_PATTERNS)) c.o_pat = take(rows * h->obs.pat.n_cells * 4);
+        if (u.env && here(SMOLMC_SAMPLE_ENVIRONMENTS)) c.o_env = take(rows * h->obs.env.n_cells * 4);
         if (!hidden) p.download = at;
     }
     if (p.lazy_rows) p.o_scal = take(rows * (size_t)std::max(1, lazy_nscal(h)) * 8);
@@ -3538,6 +3544,8 @@ static int sampled_check_flags(const smolmc_handle *h, int64_t thin_by, int flag
         return fail("SMOLMC_SAMPLE_CONNECTIVITY without a connectivity spec: call smolmc_set_connectivity first");
     if ((flags & SMOLMC_SAMPLE_PATTERNS) && !h->obs.pat.n_sets)
         return fail("SMOLMC_SAMPLE_PATTERNS without a pattern spec: call smolmc_set_patterns first");
+    if ((flags & SMOLMC_SAMPLE_ENVIRONMENTS) && !h->obs.env.n_sets)
+        return fail("SMOLMC_SAMPLE_ENVIRONMENTS without an environment spec: call smolmc_set_environments first");
     if ((flags & SMOLMC_SAMPLE_WL) && !h->wl_win_min.empty())
         return fail("SMOLMC_SAMPLE_WL while per-walker windows are set: the snapshot rows are walker-indexed, the Wang-Landau arrays estimator-indexed (smolmc_get_wl between runs, or smolmc_set_wl_windows(h, NULL, NULL) first)");
     if (thin_by > ((int64_t)1 << 30) && h->lean() && !smolmc_env(ENV_LAUNCH_CHUNK))
@@ -3644,6 +3652,7 @@ static RowSources block_rows(unsigned char *d, const BlockPlan &p) {
     s.counts = (int32_t *)(d + c.o_cnt); s.pairs = (int32_t *)(d + c.o_pair);
     s.amp = (long long *)(d + c.o_amp); s.inten = (double *)(d + c.o_inten); s.conn = (long long *)(d + c.o_conn);
     s.pat = (int32_t *)(d + c.o_pat);
+    s.env = (int32_t *)(d + c.o_env);
     s.min_key = (uint64_t *)(d + p.o_min_key); s.min_slot = (int32_t *)(d + p.o_min_slot);
     return s;
 }
@@ -4118,6 +4127,7 @@ extern "C" int smolmc_update_statistics(smolmc_handle *h) {
     RowSources s = walker_rows(h);
     s.counts = S.u_counts; s.amp = h->sfac.u_amp; s.inten = h->sfac.u_inten; s.conn = h->conn.u_stats;
     s.pat = h->obs.pat.u_cells;
+    s.env = h->obs.env.u_cells;
     return derive_and_offer(h, s, SMOLMC_SAMPLE_STATISTICS, 1, 1);
 }
 

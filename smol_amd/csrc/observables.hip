@@ -23,6 +23,14 @@
 // before share it).  A tuple is one record of 8 (arity <= 4) or 16 bytes of u16 sites, one record a lane.  Its cell is
 // counted like a pair cell where the set has more than OBS_BALLOT_CELLS cells; with fewer, in packed counters a lane keeps.
 // A launch without sets takes none of these branches.
+//
+// Environments (smolmc_set_environments, smolmc_eval_environments, SMOLMC_SAMPLE_ENVIRONMENTS; DESIGN 4.23,
+// environments.Environments.evaluate is the same in NumPy) are counted behind the patterns: per set e and centre, as listed,
+//   cells[cell_ptr[e] + a (z+1)^B + sum_b n_b (z+1)^(B-1-b)] += 1, a the centre's class, n_b its neighbours of class b
+// One lane a centre.  The class row in LDS (the one the patterns use, rebuilt by the first set) holds a byte per site: the
+// neighbour class in the low nibble, the centre class in the high one, 0xf for none.  The neighbour table is slot-major
+// ([z][n] u16 sites, 0xffff an empty slot), so the lanes of a wave read consecutive addresses; n_b sits in 8-bit fields of
+// one register (z <= 64).  A launch without sets takes none of these branches.
 #include "smolmc_common.h"
 
 #define OBS_THREADS 256
@@ -45,16 +53,43 @@ struct ObsArgs {
     int32_t *cells;            // [rows x n_cells]
     int n_sets, n_cells;
     int pat_copies;            // histograms of the pattern cells in LDS: OBS_WAVES or 1
+    // the environment sets (env_hist == 0: none, nothing else below is read); the kernel reads them through obs_kernarg()
+    const int32_t *env_sets;   // [n_env_sets x 8]: width, neighbour classes, centres, first cell, first u16 of the sites,
+                               // first centre of the codes row, new map, 0
+    const uint8_t *env_class;  // [n_env_sets x 256]: neighbour class | centre class << 4 of a kind, a nibble of 0xf: none
+    const uint16_t *env_sites; // per set: the centres [n], then the neighbours [z][n], 0xffff: empty
+    int32_t *env_cells;        // [rows x n_env_cells] or null
+    int32_t *env_codes;        // [rows x n_env_centres] or null
+    int n_env_sets, n_env_cells, n_env_centres;
+    int env_copies;            // histograms of the environment cells in LDS: OBS_WAVES or 1
+    int env_hist;              // env_copies x n_env_cells: the ints of these histograms (0: a launch without environment sets)
 };
 
+// The environment arguments as the environment phase reads them: from the kernel argument segment, behind an opaque copy
+// of its address, so that the loads stay inside the phase.  Read through `A` they are loaded at the kernel's entry and
+// held in SGPRs across the bond and tuple loops: 94 SGPRs instead of 78, and measured 2.12 ms instead of 1.96 ms per block
+// for a launch without any set.
+typedef const __attribute__((address_space(4))) ObsArgs *ObsKernarg;
+__device__ __forceinline__ ObsKernarg obs_kernarg() {
+    ObsKernarg p = (ObsKernarg)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
 // LDS: kinds u8 [Npad] | counts i32 [OBS_WAVES][K] | pairs i32 [pair_copies][n_shells K K]
-//      | patterns i32 [pat_copies][n_cells] | classes u8 [Npad]      (the last two in a launch with pattern sets)
+//      | patterns i32 [pat_copies][n_cells] | environments i32 [env_copies][n_env_cells] | classes u8 [Npad]
+//      (the patterns in a launch with pattern sets, the environments in one with environment sets, the classes in either)
 size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies) {
     return (size_t)Npad + ((size_t)OBS_WAVES * K + (size_t)pair_copies * cells) * 4;
 }
 int smolmc_obs_pair_copies(size_t cells) { return cells * OBS_WAVES <= SMOLMC_MAX_OBS_CELLS ? OBS_WAVES : 1; }
 size_t smolmc_pat_lds_bytes(int Npad, size_t n_cells, int copies) { return (size_t)copies * n_cells * 4 + (size_t)Npad; }
 static int smolmc_pat_copies(size_t n_cells) { return n_cells * OBS_WAVES <= SMOLMC_MAX_PATTERN_CELLS ? OBS_WAVES : 1; }
+static int smolmc_envs_copies(size_t n_cells) { return n_cells * OBS_WAVES <= SMOLMC_MAX_ENV_CELLS ? OBS_WAVES : 1; }
+// the dynamic LDS of a launch that counts everything set: the pattern and the environment sets share the class row
+static size_t smolmc_obs_launch_lds(const SmolmcObs &O, const SmolmcPat &P, const SmolmcEnvSpec &E, int Npad) {
+    return O.lds + (P.n_sets ? P.lds : 0) + (E.n_sets ? E.lds : 0) - (P.n_sets && E.n_sets ? (size_t)Npad : 0);
+}
 
 // four sites of a tuple record: the classes of all four are read (a short tuple is filled up with site 0), the first m
 // enter the cell, most significant first
@@ -89,7 +124,9 @@ __global__ void __launch_bounds__(OBS_THREADS) observables_kernel(const ObsArgs 
         const uint4 *src = (const uint4 *)(A.occ + row * Npad);
         uint4 *dst = (uint4 *)kinds;
         for (int i = tid; i < Npad / 16; i += OBS_THREADS) dst[i] = src[i];
-        for (int i = tid; i < OBS_WAVES * K + A.pair_copies * cells + A.pat_copies * A.n_cells; i += OBS_THREADS) cnt[i] = 0;
+        for (int i = tid; i < OBS_WAVES * K + A.pair_copies * cells + A.pat_copies * A.n_cells + A.env_hist;
+             i += OBS_THREADS)
+            cnt[i] = 0;
     }
     __syncthreads();
 
@@ -150,11 +187,12 @@ __global__ void __launch_bounds__(OBS_THREADS) observables_kernel(const ObsArgs 
 
     // the pattern sets: the classes of the sites in the set's map, then the tuples, one record a lane
     int32_t *phist = hist + A.pair_copies * cells;
+    int32_t *ehist = phist + A.pat_copies * A.n_cells;
+    uint8_t *cls = (uint8_t *)(ehist + A.env_hist);
     for (int t = 0; t < A.n_sets; ++t) {
         const int32_t *S = A.sets + 8 * t; // (uniform: scalar loads)
         const int m = S[0], n = S[2], nc = S[5];
         const unsigned C = (unsigned)S[1];
-        uint8_t *cls = (uint8_t *)(phist + A.pat_copies * A.n_cells);
         if (S[6]) { // another map than the set before had (set 0: always); every thread of the workgroup gets here
             __syncthreads();
             const uint8_t *tab = A.class_of + 256 * t;
@@ -202,32 +240,82 @@ __global__ void __launch_bounds__(OBS_THREADS) observables_kernel(const ObsArgs 
         }
         if (few) pat_flush(pmine, nc, pk0, pk1);
     }
+
+    // the environment sets: the two classes of the sites in the set's maps, then the centres, one a lane
+    if (A.env_hist) {
+        const ObsKernarg E = obs_kernarg();
+        const int n_env_cells = E->n_env_cells;
+        for (int e = 0; e < E->n_env_sets; ++e) {
+            const int32_t *S = E->env_sets + 8 * e; // (uniform: scalar loads)
+            const int z = S[0], B = S[1], n = S[2];
+            if (S[6]) { // other maps than the set before had (set 0: always); every thread of the workgroup gets here
+                __syncthreads();
+                const uint8_t *tab = E->env_class + 256 * e;
+                for (int s = tid; s < Npad; s += OBS_THREADS) cls[s] = tab[kinds[s]];
+                __syncthreads();
+            }
+            const uint16_t *cen = E->env_sites + S[4], *nb = cen + n;
+            int32_t *emine = ehist + (E->env_copies > 1 ? wave * n_env_cells : 0) + S[3];
+            int32_t *codes = E->env_codes ? E->env_codes + row * (size_t)E->n_env_centres + S[5] : nullptr;
+            for (int i = tid; i < n; i += OBS_THREADS) {
+                const unsigned c = cls[cen[i]];
+                unsigned pk = 0; // n_b in bits 8 b .. 8 b + 7 (z <= 64)
+                for (int q = 0; q < z; ++q) { // (uniform trip count)
+                    const unsigned s = nb[(size_t)q * n + i];
+                    const unsigned b = cls[s == 0xffffu ? 0u : s] & 0xfu;
+                    pk += (s == 0xffffu || b == 0xfu) ? 0u : 1u << ((b & 3u) * 8);
+                }
+                unsigned code = c >> 4;
+                for (int b = 0; b < B; ++b) code = code * (unsigned)(z + 1) + ((pk >> (8 * b)) & 0xffu);
+                const bool skip = (c >> 4) == 0xfu;
+                if (!skip) atomicAdd(&emine[code], 1);
+                if (codes) codes[i] = skip ? -1 : (int)code;
+            }
+        }
+    }
     __syncthreads();
 
-    // fold the waves' copies: plain stores, one per entry
-    if (A.counts)
+    // fold the waves' copies: plain stores, one per entry (the output pointers are read here, see obs_kernarg)
+    const ObsKernarg F = obs_kernarg();
+    int32_t *const out_counts = F->counts, *const out_pairs = F->pairs, *const out_cells = F->cells;
+    if (out_counts)
         for (int k = tid; k < K; k += OBS_THREADS) {
             int v = 0;
 #pragma unroll
             for (int w = 0; w < OBS_WAVES; ++w) v += cnt[w * K + k];
-            A.counts[row * K + k] = v;
+            out_counts[row * K + k] = v;
         }
     if (A.n_sets)
         for (int c = tid; c < A.n_cells; c += OBS_THREADS) {
             int v = 0;
             for (int w = 0; w < A.pat_copies; ++w) v += phist[w * A.n_cells + c];
-            A.cells[row * (size_t)A.n_cells + c] = v;
+            out_cells[row * (size_t)A.n_cells + c] = v;
         }
+    if (A.env_hist) {
+        const ObsKernarg E = obs_kernarg();
+        int32_t *out = E->env_cells;
+        const int n_env_cells = E->n_env_cells, copies = E->env_copies;
+        if (out)
+            for (int c = tid; c < n_env_cells; c += OBS_THREADS) {
+                int v = 0;
+                for (int w = 0; w < copies; ++w) v += ehist[w * n_env_cells + c];
+                out[row * (size_t)n_env_cells + c] = v;
+            }
+    }
     for (int c = tid; c < cells; c += OBS_THREADS) {
         int v = 0;
         for (int w = 0; w < A.pair_copies; ++w) v += hist[w * cells + c];
-        A.pairs[row * (size_t)cells + c] = v;
+        out_pairs[row * (size_t)cells + c] = v;
     }
 }
 
-int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs, int32_t *d_cells) {
+int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs, int32_t *d_cells,
+                      int32_t *d_env, int32_t *d_codes) {
     const SmolmcObs &O = h->obs;
     const SmolmcPat &P = O.pat;
+    const SmolmcEnvSpec &E = O.env;
+    const bool env = d_env || d_codes;
+    if (env && !E.n_sets) return fail("no environment spec set (smolmc_set_environments)");
     if (!O.K) return fail("no observables set (smolmc_set_observables)");
     if (d_cells && !P.n_sets) return fail("no pattern spec set (smolmc_set_patterns)");
     if (!rows) return 0;
@@ -240,12 +328,18 @@ int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int3
     A.sets = P.d_sets; A.class_of = P.d_class; A.recs = P.d_recs; A.cells = d_cells;
     A.n_sets = d_cells ? P.n_sets : 0;     // (no sets: the kernel never touches the pattern arrays)
     A.n_cells = d_cells ? (int)P.n_cells : 0; A.pat_copies = P.copies;
+    A.env_sets = E.d_sets; A.env_class = E.d_class; A.env_sites = E.d_sites; A.env_cells = d_env; A.env_codes = d_codes;
+    A.n_env_sets = env ? E.n_sets : 0;     // (no sets: the kernel never touches the environment arrays)
+    A.n_env_cells = env ? (int)E.n_cells : 0; A.n_env_centres = (int)E.n_centres; A.env_copies = E.copies;
+    A.env_hist = A.env_copies * A.n_env_cells;
+    // (the class row is taken once, by the patterns or the environments)
+    const size_t lds = O.lds + (d_cells ? P.lds : 0) + (env ? E.lds : 0) - (d_cells && env ? (size_t)h->Npad : 0);
     if (!h->obs_ev0) {
         HIPCHK(hipEventCreate(&h->obs_ev0));
         HIPCHK(hipEventCreate(&h->obs_ev1));
     }
     HIPCHK(hipEventRecord(h->obs_ev0, h->stream));
-    hipLaunchKernelGGL(observables_kernel, dim3((unsigned)rows), dim3(OBS_THREADS), O.lds + (d_cells ? P.lds : 0), h->stream, A);
+    hipLaunchKernelGGL(observables_kernel, dim3((unsigned)rows), dim3(OBS_THREADS), lds, h->stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->obs_ev1, h->stream));
     return 0;
@@ -267,7 +361,12 @@ void smolmc_obs_free(SmolmcObs &O) {
     if (O.d_shell_ptr) hipFree(O.d_shell_ptr);
     if (O.d_bonds) hipFree(O.d_bonds);
     smolmc_pat_free(O.pat);
+    smolmc_envs_free(O.env);
     O = SmolmcObs();
+}
+void smolmc_envs_free(SmolmcEnvSpec &E) {
+    if (E.arena) hipFree(E.arena);
+    E = SmolmcEnvSpec();
 }
 void smolmc_pat_free(SmolmcPat &P) {
     if (P.arena) hipFree(P.arena);
@@ -283,6 +382,9 @@ extern "C" int smolmc_set_observables(smolmc_handle *h, const smolmc_observables
     if (h->obs.pat.n_sets)
         return fail("smolmc_set_observables while a pattern spec rests on the kinds of the observables (call "
                     "smolmc_set_patterns(h, NULL) first)");
+    if (h->obs.env.n_sets)
+        return fail("smolmc_set_observables while an environment spec rests on the kinds of the observables (call "
+                    "smolmc_set_environments(h, NULL) first)");
     if (h->minima.n_slots && h->minima.n_axes)
         return fail("smolmc_set_observables while a minima record keyed by composition depends on the observables (call "
                     "smolmc_set_minima(h, NULL) first)");
@@ -389,6 +491,9 @@ extern "C" int smolmc_set_patterns(smolmc_handle *h, const smolmc_patterns *sp) 
     if (h->stats.n_keys && h->stats.n_pat_cols)
         return fail("smolmc_set_patterns while a statistics record with pattern columns depends on the spec (call "
                     "smolmc_set_statistics(h, NULL) first)");
+    if (h->stats.n_keys && h->stats.n_env_cols)
+        return fail("smolmc_set_patterns while a statistics record with environment columns lies behind the pattern cells (call "
+                    "smolmc_set_statistics(h, NULL) first)");
     SmolmcPat P;
     if (sp) {
         const SmolmcObs &O = h->obs;
@@ -462,6 +567,12 @@ extern "C" int smolmc_set_patterns(smolmc_handle *h, const smolmc_patterns *sp) 
                      "and %zu cells, 65536 at most", O.lds, P.lds, n_cells);
             return fail(msg);
         }
+        if (smolmc_obs_launch_lds(O, P, O.env, h->Npad) > 64 * 1024) {
+            snprintf(msg, sizeof msg, "patterns: with the environment spec in force a launch takes %zu bytes of LDS (the row, the "
+                     "observables, the classes, %zu pattern and %zu environment cells), 65536 at most",
+                     smolmc_obs_launch_lds(O, P, O.env, h->Npad), n_cells, O.env.n_cells);
+            return fail(msg);
+        }
         size_t at = 0;
         auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
         const size_t o_sets = take(sets.size() * 4), o_tab = take(tab.size()), o_recs = take(recs.size() * 2),
@@ -513,5 +624,165 @@ extern "C" int smolmc_get_sample_patterns(smolmc_handle *h, int32_t *cells) {
     size_t rows;
     TRY(smolmc_sample_block(h, SMOLMC_SAMPLE_PATTERNS, "the patterns were not recorded (flags bit 8)", &sl, &rows));
     if (cells) smolmc_host_copy(cells, sl->hst + sl->o_pat, rows * h->obs.pat.n_cells * 4);
+    return 0;
+}
+
+// ---- the C-ABI of the environment spec -----------------------------------------------------------------------------------
+extern "C" int smolmc_set_environments(smolmc_handle *h, const smolmc_environments *sp) {
+    if (!h) return fail("null handle");
+    HIPCHK(hipSetDevice(h->device));
+    TRY(smolmc_ring_guard(h, SMOLMC_SAMPLE_ENVIRONMENTS, "smolmc_set_environments", "SMOLMC_SAMPLE_ENVIRONMENTS"));
+    if (h->stats.n_keys && h->stats.n_env_cols)
+        return fail("smolmc_set_environments while a statistics record with environment columns depends on the spec (call "
+                    "smolmc_set_statistics(h, NULL) first)");
+    SmolmcEnvSpec E;
+    if (sp) {
+        const SmolmcObs &O = h->obs;
+        const int N = h->N, K = O.K, T = sp->n_sets;
+        char msg[256];
+        if (!K) return fail("environments: no observables set: the class maps index their kinds (call smolmc_set_observables first)");
+        if (T < 1 || T > SMOLMC_MAX_ENV_SETS) {
+            snprintf(msg, sizeof msg, "environments: n_sets must be 1..%d, got %d", SMOLMC_MAX_ENV_SETS, T);
+            return fail(msg);
+        }
+        if (!sp->width || !sp->n_centre_classes || !sp->n_neigh_classes || !sp->centre_class_of_kind || !sp->neigh_class_of_kind ||
+            !sp->centre_ptr)
+            return fail("environments: null argument");
+        if (sp->centre_ptr[0] != 0) return fail("environments: centre_ptr[0] must be 0");
+        std::vector<int32_t> sets((size_t)T * 8, 0);
+        std::vector<uint8_t> tab((size_t)T * 256, (uint8_t)0xff);
+        std::vector<uint16_t> sites;
+        size_t n_cells = 0, slot0 = 0;
+        for (int t = 0; t < T; ++t) {
+            const int z = sp->width[t], A = sp->n_centre_classes[t], B = sp->n_neigh_classes[t];
+            if (z < 1 || z > SMOLMC_MAX_ENV_WIDTH) {
+                snprintf(msg, sizeof msg, "environments: set %d has width %d, outside 1..%d", t, z, SMOLMC_MAX_ENV_WIDTH);
+                return fail(msg);
+            }
+            if (A < 1 || A > SMOLMC_MAX_ENV_CENTRE_CLASSES) {
+                snprintf(msg, sizeof msg, "environments: set %d has %d centre classes, outside 1..%d", t, A, SMOLMC_MAX_ENV_CENTRE_CLASSES);
+                return fail(msg);
+            }
+            if (B < 1 || B > SMOLMC_MAX_ENV_NEIGH_CLASSES) {
+                snprintf(msg, sizeof msg, "environments: set %d has %d neighbour classes, outside 1..%d", t, B, SMOLMC_MAX_ENV_NEIGH_CLASSES);
+                return fail(msg);
+            }
+            for (int k = 0; k < K; ++k) {
+                const int32_t a = sp->centre_class_of_kind[(size_t)t * K + k], b = sp->neigh_class_of_kind[(size_t)t * K + k];
+                if (a < -1 || a >= A) {
+                    snprintf(msg, sizeof msg, "environments: set %d maps kind %d to centre class %d, outside -1..%d: class out of range", t, k,
+                             (int)a, A - 1);
+                    return fail(msg);
+                }
+                if (b < -1 || b >= B) {
+                    snprintf(msg, sizeof msg, "environments: set %d maps kind %d to neighbour class %d, outside -1..%d: class out of range", t,
+                             k, (int)b, B - 1);
+                    return fail(msg);
+                }
+                tab[(size_t)t * 256 + k] = (uint8_t)((b < 0 ? 0xf : b) | (a < 0 ? 0xf : a) << 4);
+            }
+            size_t nc = (size_t)A;
+            for (int b = 0; b < B && nc <= SMOLMC_MAX_ENV_CELLS; ++b) nc *= (size_t)(z + 1);
+            if (n_cells + nc > SMOLMC_MAX_ENV_CELLS) {
+                snprintf(msg, sizeof msg, "environments: set %d with %d centre classes, %d neighbour classes and width %d brings the spec "
+                         "to more than SMOLMC_MAX_ENV_CELLS = %d cells", t, A, B, z, SMOLMC_MAX_ENV_CELLS);
+                return fail(msg);
+            }
+            const int64_t c0 = sp->centre_ptr[t], n = sp->centre_ptr[t + 1] - c0;
+            if (n < 0) return fail("environments: centre_ptr must not decrease");
+            if (n > 0 && (!sp->centres || !sp->neighbours)) return fail("environments: null argument");
+            if ((sites.size() + (size_t)n * (z + 1)) * 2 > ((size_t)1 << 30) || sp->centre_ptr[t + 1] > 0x7fffffff)
+                return fail("environments: the neighbour tables take more than 1 GiB");
+            int32_t *S = &sets[(size_t)t * 8];
+            S[0] = z; S[1] = B; S[2] = (int32_t)n; S[3] = (int32_t)n_cells; S[4] = (int32_t)sites.size(); S[5] = (int32_t)c0;
+            S[6] = t == 0 || memcmp(&tab[(size_t)t * 256], &tab[(size_t)(t - 1) * 256], 256) != 0;
+            const size_t r0 = sites.size();
+            sites.resize(r0 + (size_t)n * (z + 1), 0xffff);
+            for (int64_t i = 0; i < n; ++i) {
+                const int32_t c = sp->centres[c0 + i];
+                if (c < 0 || c >= N) {
+                    snprintf(msg, sizeof msg, "environments: set %d centre %lld is site %d, %d sites: site out of range", t, (long long)i,
+                             (int)c, N);
+                    return fail(msg);
+                }
+                sites[r0 + (size_t)i] = (uint16_t)(h->relabelled ? h->new_of[c] : c);
+                for (int q = 0; q < z; ++q) {
+                    const int32_t s = sp->neighbours[slot0 + (size_t)i * z + q];
+                    if (s < -1 || s >= N) {
+                        snprintf(msg, sizeof msg, "environments: set %d centre %lld slot %d names site %d, %d sites: site out of range", t,
+                                 (long long)i, q, (int)s, N);
+                        return fail(msg);
+                    }
+                    if (s >= 0) sites[r0 + (size_t)(q + 1) * n + i] = (uint16_t)(h->relabelled ? h->new_of[s] : s);
+                }
+            }
+            slot0 += (size_t)n * z;
+            n_cells += nc;
+        }
+        E.n_sets = T; E.n_cells = n_cells; E.n_centres = (size_t)sp->centre_ptr[T];
+        E.copies = smolmc_envs_copies(n_cells);
+        E.lds = (size_t)E.copies * n_cells * 4 + (size_t)h->Npad;
+        // (a row that fits LDS has fewer than 2^16 - 1 sites: a site of the tables is 16 bits and 0xffff is free)
+        const size_t lds = smolmc_obs_launch_lds(O, O.pat, E, h->Npad);
+        if (lds > 64 * 1024) {
+            snprintf(msg, sizeof msg, "environments: a launch takes %zu bytes of LDS (the row, the observables, the classes, %zu "
+                     "pattern and %zu environment cells), 65536 at most", lds, O.pat.n_cells, n_cells);
+            return fail(msg);
+        }
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
+        const size_t o_sets = take(sets.size() * 4), o_tab = take(tab.size()), o_sites = take(sites.size() * 2),
+                     o_u = take((size_t)h->R * n_cells * 4);
+        hipError_t e = hipMalloc((void **)&E.arena, at);
+        if (e != hipSuccess) return fail(std::string("environments: hipMalloc: ") + hipGetErrorString(e));
+        unsigned char *d = E.arena;
+        E.d_sets = (int32_t *)(d + o_sets); E.d_class = d + o_tab; E.d_sites = (uint16_t *)(d + o_sites); E.u_cells = (int32_t *)(d + o_u);
+        e = hipMemcpy(E.d_sets, sets.data(), sets.size() * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(E.d_class, tab.data(), tab.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !sites.empty()) e = hipMemcpy(E.d_sites, sites.data(), sites.size() * 2, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            smolmc_envs_free(E);
+            return fail(std::string("environments upload: ") + hipGetErrorString(e));
+        }
+    }
+    TRY(smolmc_ring_forget(h, SMOLMC_SAMPLE_ENVIRONMENTS));
+    smolmc_envs_free(h->obs.env);
+    h->obs.env = E;
+    return 0;
+}
+
+extern "C" int smolmc_environments_shape(smolmc_handle *h, int *n_sets, int *n_cells, int *n_centres) {
+    if (!h) return fail("null handle");
+    if (n_sets) *n_sets = h->obs.env.n_sets;
+    if (n_cells) *n_cells = (int)h->obs.env.n_cells;
+    if (n_centres) *n_centres = (int)h->obs.env.n_centres;
+    return 0;
+}
+
+extern "C" int smolmc_eval_environments(smolmc_handle *h, const int32_t *occ, int nocc, int32_t *cells, int32_t *codes) {
+    if (!h) return fail("null handle");
+    const SmolmcEnvSpec &E = h->obs.env;
+    if (!E.n_sets) return fail("no environment spec set: call smolmc_set_environments first");
+    HIPCHK(hipSetDevice(h->device));
+    const uint8_t *d_occ8;
+    size_t rows;
+    TRY(smolmc_eval_rows(h, occ, nocc, h->obs.kind_base, h->obs.K, "environments", &d_occ8, &rows));
+    const size_t nc = cells ? rows * E.n_cells : 0, nk = codes ? rows * E.n_centres : 0;
+    if (!nc && !nk) return 0; // (nothing asked for, or the codes of a spec without centres)
+    DevScratch out;
+    TRY(out.alloc(std::max<size_t>((nc + nk) * 4, 16)));
+    int32_t *d_out = out.as<int32_t>();
+    TRY(smolmc_obs_launch(h, d_occ8, rows, nullptr, nullptr, nullptr, nc ? d_out : nullptr, nk ? d_out + nc : nullptr));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (cells) HIPCHK(hipMemcpy(cells, d_out, nc * 4, hipMemcpyDeviceToHost));
+    if (codes && nk) HIPCHK(hipMemcpy(codes, d_out + nc, nk * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int smolmc_get_sample_environments(smolmc_handle *h, int32_t *cells) {
+    const SampleSlot *sl;
+    size_t rows;
+    TRY(smolmc_sample_block(h, SMOLMC_SAMPLE_ENVIRONMENTS, "the environments were not recorded (flags bit 9)", &sl, &rows));
+    if (cells) smolmc_host_copy(cells, sl->hst + sl->o_env, rows * h->obs.env.n_cells * 4);
     return 0;
 }

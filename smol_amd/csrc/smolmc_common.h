@@ -784,6 +784,7 @@ struct SampleColumns {
     size_t o_amp = 0, o_inten = 0;              // SMOLMC_SAMPLE_STRUCTURE: amplitudes [rows x Q x K x 2] int64, intensities [rows x I]
     size_t o_conn = 0;                          // SMOLMC_SAMPLE_CONNECTIVITY: stats [rows x G x 24] int64
     size_t o_pat = 0;                           // SMOLMC_SAMPLE_PATTERNS: pattern cells [rows x n_cells]
+    size_t o_env = 0;                           // SMOLMC_SAMPLE_ENVIRONMENTS: environment cells [rows x n_cells]
 };
 // One slot of the sample ring: `n` samples x R walkers recorded by one smolmc_run_sampled call.  Every array is a
 // range of ONE device arena and of ONE pinned host arena with the same offsets (a single asynchronous copy moves it).
@@ -833,6 +834,22 @@ struct SmolmcPat {
     int32_t *u_cells = nullptr; // smolmc_update_statistics: cells [R x n_cells] of the walkers' current states
 };
 
+// observables.hip: the environment spec of a handle (smolmc_set_environments) as the observables' kernel reads it, engine
+// numbering
+struct SmolmcEnvSpec {
+    int n_sets = 0;            // (0: none set)
+    size_t n_cells = 0;        // sum over the sets of A (z + 1)^B
+    size_t n_centres = 0;      // centres of all sets: the width of a row of codes
+    int copies = 1;            // histograms of the environment cells in LDS (one per wave, or one)
+    size_t lds = 0;            // dynamic LDS a launch takes on top of SmolmcObs::lds: the class buffer and the histograms
+    unsigned char *arena = nullptr; // one device allocation, cut into the arrays below
+    int32_t *d_sets = nullptr; // [n_sets x 8]: width, neighbour classes, centres, first cell, first u16 of the set's sites,
+                               // first centre of the codes row, new map, 0
+    uint8_t *d_class = nullptr; // [n_sets x 256]: neighbour class | centre class << 4 of a kind, a nibble of 0xf: none
+    uint16_t *d_sites = nullptr; // per set: the centres [n], then the neighbour table slot-major [z][n], 0xffff an empty slot
+    int32_t *u_cells = nullptr; // smolmc_update_statistics: cells [R x n_cells] of the walkers' current states
+};
+
 // observables.hip: the observables of a handle (smolmc_set_observables) as the kernel reads them, engine numbering
 struct SmolmcObs {
     int K = 0, n_shells = 0;   // (K == 0: none set)
@@ -844,6 +861,7 @@ struct SmolmcObs {
     int64_t *d_shell_ptr = nullptr;
     uint32_t *d_bonds = nullptr; // one word per bond: i | j << 16
     SmolmcPat pat;             // the pattern spec that rests on these kinds
+    SmolmcEnvSpec env;             // the environment spec that rests on these kinds
 };
 
 // minima.hip: the minima record of a handle (smolmc_set_minima): the spec and one device arena cut into the entry arrays
@@ -884,6 +902,8 @@ struct SmolmcStat {
     int n_conn_cols = 0;       // columns that read the connectivity stats
     int PC = 0;                // the cells of the pattern spec in force when the record was set
     int n_pat_cols = 0;        // columns that read the pattern cells
+    int EC = 0;                // the cells of the environment spec in force when the record was set
+    int n_env_cols = 0;        // columns that read the environment cells
     double hist_min = 0.0, hist_bin = 1.0;
     unsigned char *arena = nullptr;
     size_t record_bytes = 0;   // from n to the end of the accumulator arrays: what a reset zeroes
@@ -1175,8 +1195,10 @@ int smolmc_pop_clone_launch(smolmc_handle *h, const int32_t *parent, int npop, c
 // apart, device) into device arrays, queued on the handle's stream; the LDS a launch takes and the number of pair
 // histograms it keeps there
 // (d_pairs == nullptr: no pair counts; d_cells: the cells [rows x n_cells] of the pattern spec or null; d_counts may be
-// null when only the patterns are wanted)
-int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs, int32_t *d_cells);
+// null when only the patterns are wanted; d_env: the cells [rows x n_cells] of the environment spec or null; d_codes: the
+// codes [rows x n_centres] of its centres or null)
+int smolmc_obs_launch(smolmc_handle *h, const uint8_t *d_occ8, size_t rows, int32_t *d_counts, int32_t *d_pairs, int32_t *d_cells,
+                      int32_t *d_env = nullptr, int32_t *d_codes = nullptr);
 // minima.hip: offer `rows` = nsamples x R rows (enthalpy [rows], features [rows x F], occupancy rows Npad bytes apart,
 // counts [rows x K] or null; device) to the handle's record, three kernels queued on the handle's stream; d_key [rows]
 // and d_slot [rows] are scratch.  Row s * R + r is offer number offers + s of walker r, taken thin_by steps before row
@@ -1189,9 +1211,10 @@ void smolmc_min_free(smolmc_handle *h);
 // order.  Sample s gives key k the row s * R + w, w the walker that holds k when the kernel runs.
 // (d_inten: intensities [rows x I] or null, read by a record with intensity columns; d_conn: connectivity stats
 // [rows x G x 24] or null, read by a record with connectivity columns; d_pat: pattern cells [rows x n_cells] or null, read
-// by a record with pattern columns)
+// by a record with pattern columns; d_env: environment cells [rows x n_cells] or null, read by a record with environment
+// columns)
 int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, const double *d_inten,
-                       const long long *d_conn, const int32_t *d_pat, long long nsamples);
+                       const long long *d_conn, const int32_t *d_pat, const int32_t *d_env, long long nsamples);
 void smolmc_stat_free(smolmc_handle *h);
 // structure.hip: amplitudes [rows x Q x K x 2] and intensities [rows x I] of `rows` occupancy rows (Npad bytes apart,
 // device) into device arrays, queued on the handle's stream; the kernel a spec takes and the layout of its LDS (false:
@@ -1209,6 +1232,7 @@ size_t smolmc_obs_lds_bytes(int Npad, int K, size_t cells, int pair_copies);
 int smolmc_obs_pair_copies(size_t cells);
 size_t smolmc_pat_lds_bytes(int Npad, size_t n_cells, int copies);
 void smolmc_pat_free(SmolmcPat &P);
+void smolmc_envs_free(SmolmcEnvSpec &E);
 void smolmc_obs_free(SmolmcObs &O);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);
 int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);

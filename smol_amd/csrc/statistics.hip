@@ -28,6 +28,7 @@ struct StatArgs {
     const double *inten;       // [rows x I] or null: the intensities of the structure-factor spec in force
     const long long *conn;     // [rows x CS] or null: the stats of the connectivity spec in force, 24 per graph
     const int32_t *pat;        // [rows x PC] or null: the cells of the pattern spec in force
+    const int32_t *env;        // [rows x EC] or null: the cells of the environment spec in force
     const int32_t *walker_at;  // key -> walker, or null: the identity
     // the record
     long long *n, *nb, *hist, *under, *over;
@@ -38,17 +39,18 @@ struct StatArgs {
     const double *weights;     // [n_weights]
     double hist_min, hist_bin;
     int C, L, n_bins, hist_column, n_weights;
-    int R, F, K, I, CS, PC;
+    int R, F, K, I, CS, PC, EC;
     long long nsamples;
 };
 
 // column source `src` of row `row`: 0 the enthalpy, 1 + i feature i, 1 + F + k kind count k, 1 + F + K the weighted sum,
 // 2 + F + K + i intensity i, 2 + F + K + I + c connectivity number c (24 per graph) as a double, 2 + F + K + I + CS + c
-// pattern cell c as a double
+// pattern cell c as a double, 2 + F + K + I + CS + PC + c environment cell c as a double
 __device__ __forceinline__ double stat_column(const StatArgs &A, size_t row, int src) {
     if (src == 0) return A.H[row];
     if (src <= A.F) return A.feat[row * A.F + (src - 1)];
     if (src <= A.F + A.K) return (double)A.counts[row * A.K + (src - 1 - A.F)];
+    if (src > 1 + A.F + A.K + A.I + A.CS + A.PC) return (double)A.env[row * A.EC + (src - 2 - A.F - A.K - A.I - A.CS - A.PC)];
     if (src > 1 + A.F + A.K + A.I + A.CS) return (double)A.pat[row * A.PC + (src - 2 - A.F - A.K - A.I - A.CS)];
     if (src > 1 + A.F + A.K + A.I) return (double)A.conn[row * A.CS + (src - 2 - A.F - A.K - A.I)];
     if (src > 1 + A.F + A.K) return A.inten[row * A.I + (src - 2 - A.F - A.K)];
@@ -174,26 +176,27 @@ __global__ void __launch_bounds__(ST_THREADS) statistics_kernel(const StatArgs A
 }
 
 int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, const double *d_inten,
-                       const long long *d_conn, const int32_t *d_pat, long long nsamples) {
+                       const long long *d_conn, const int32_t *d_pat, const int32_t *d_env, long long nsamples) {
     SmolmcStat &S = h->stats;
     if (!S.n_keys) return fail("no statistics record set (smolmc_set_statistics)");
     if (S.n_count_cols && !d_counts) return fail("statistics: a record with count columns needs the kind counts of the rows");
     if (S.n_inten_cols && !d_inten) return fail("statistics: a record with intensity columns needs the intensities of the rows");
     if (S.n_conn_cols && !d_conn) return fail("statistics: a record with connectivity columns needs the connectivity stats of the rows");
     if (S.n_pat_cols && !d_pat) return fail("statistics: a record with pattern columns needs the pattern cells of the rows");
+    if (S.n_env_cols && !d_env) return fail("statistics: a record with environment columns needs the environment cells of the rows");
     if (S.key == SMOLMC_STAT_BY_STATE_POINT && !h->wl_win_min.empty())
         return fail("statistics: a record keyed by state point on a Wang-Landau handle with per-walker windows");
     if (nsamples <= 0 || (size_t)nsamples * h->R > 0x7fffffffull) return fail("statistics: 1 .. 2^31 rows in one launch");
     StatArgs A;
     memset(&A, 0, sizeof(A));
-    A.H = d_H; A.feat = d_feat; A.counts = d_counts; A.inten = d_inten; A.conn = d_conn; A.pat = d_pat;
+    A.H = d_H; A.feat = d_feat; A.counts = d_counts; A.inten = d_inten; A.conn = d_conn; A.pat = d_pat; A.env = d_env;
     // (the maps exist once smolmc_exchange_grid has run; both are permutations of 0 .. R - 1 at every kernel boundary)
     A.walker_at = S.key == SMOLMC_STAT_BY_STATE_POINT ? h->d_walker_at : nullptr;
     A.n = S.n; A.nb = S.nb; A.hist = S.hist; A.under = S.under; A.over = S.over;
     A.shift = S.shift; A.s1 = S.s1; A.s2 = S.s2; A.pend = S.pend; A.b2 = S.b2; A.has = S.has;
     A.columns = S.columns; A.weights = S.weights; A.hist_min = S.hist_min; A.hist_bin = S.hist_bin;
     A.C = S.C; A.L = S.L; A.n_bins = S.n_bins; A.hist_column = S.hist_column; A.n_weights = S.n_weights;
-    A.R = h->R; A.F = h->F; A.K = S.K; A.I = S.I; A.CS = S.CS; A.PC = S.PC;
+    A.R = h->R; A.F = h->F; A.K = S.K; A.I = S.I; A.CS = S.CS; A.PC = S.PC; A.EC = S.EC;
     A.nsamples = nsamples;
     if (!S.ev[0])
         for (hipEvent_t &e : S.ev) HIPCHK(hipEventCreate(&e));
@@ -224,6 +227,7 @@ extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *
     const int K = h->obs.K, F = h->F, I = h->sfac.I; // (no structure-factor spec: I = 0, the range ends at the weighted sum)
     const int CS = h->conn.G * SMOLMC_CONN_STATS;    // (no connectivity spec: 0, the range ends where it ends without)
     const int PC = (int)h->obs.pat.n_cells;          // (no pattern spec: 0, likewise)
+    const int EC = (int)h->obs.env.n_cells;          // (no environment spec: 0, likewise)
     char msg[320];
     if (s->key != SMOLMC_STAT_BY_WALKER && s->key != SMOLMC_STAT_BY_STATE_POINT) {
         snprintf(msg, sizeof msg, "statistics: key must be 0 (by walker) or 1 (by state point), got %d", s->key);
@@ -243,17 +247,18 @@ extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *
         return fail(msg);
     }
     const int C = s->n_columns;
-    int n_count_cols = 0, n_inten_cols = 0, n_conn_cols = 0, n_pat_cols = 0;
+    int n_count_cols = 0, n_inten_cols = 0, n_conn_cols = 0, n_pat_cols = 0, n_env_cols = 0;
     for (int c = 0; c < C; ++c) {
         const int src = s->columns[c];
-        if (src < 0 || src > 1 + F + K + I + CS + PC) {
-            char tail[128] = "";
+        if (src < 0 || src > 1 + F + K + I + CS + PC + EC) {
+            char tail[176] = "";
             if (I && CS) snprintf(tail, sizeof tail, ", %d intensities, %d connectivity numbers", I, CS);
             else if (I) snprintf(tail, sizeof tail, ", %d intensities", I);
             else if (CS) snprintf(tail, sizeof tail, ", %d connectivity numbers", CS);
             if (PC) snprintf(tail + strlen(tail), sizeof tail - strlen(tail), ", %d pattern cells", PC);
+            if (EC) snprintf(tail + strlen(tail), sizeof tail - strlen(tail), ", %d environment cells", EC);
             snprintf(msg, sizeof msg, "statistics: column %d has source %d, outside 0..%d (the enthalpy, %d features, %d kinds, the "
-                     "weighted sum%s)%s", c, src, 1 + F + K + I + CS + PC, F, K, tail,
+                     "weighted sum%s)%s", c, src, 1 + F + K + I + CS + PC + EC, F, K, tail,
                      !K && src > 1 + F ? "; a kind count needs observables: call smolmc_set_observables first" : "");
             return fail(msg);
         }
@@ -265,7 +270,8 @@ extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *
         n_count_cols += src > F && src <= F + K;
         n_inten_cols += src > 1 + F + K && src <= 1 + F + K + I;
         n_conn_cols += src > 1 + F + K + I && src <= 1 + F + K + I + CS;
-        n_pat_cols += src > 1 + F + K + I + CS;
+        n_pat_cols += src > 1 + F + K + I + CS && src <= 1 + F + K + I + CS + PC;
+        n_env_cols += src > 1 + F + K + I + CS + PC;
     }
     if (s->n_levels < 0 || s->n_levels > SMOLMC_MAX_STAT_LEVELS) {
         snprintf(msg, sizeof msg, "statistics: n_levels must be 0..%d, got %d", SMOLMC_MAX_STAT_LEVELS, s->n_levels);
@@ -296,6 +302,7 @@ extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *
     S.I = I; S.n_inten_cols = n_inten_cols;
     S.CS = CS; S.n_conn_cols = n_conn_cols;
     S.PC = PC; S.n_pat_cols = n_pat_cols;
+    S.EC = EC; S.n_env_cols = n_env_cols;
     S.hist_min = B ? s->hist_min : 0.0; S.hist_bin = B ? s->hist_bin : 1.0;
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };

@@ -87,6 +87,10 @@ SYMBOLS = {
     "smolmc_patterns_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 2),
     "smolmc_eval_patterns": (C.c_int, [_HP, _i32p, C.c_int, _i32p]),
     "smolmc_get_sample_patterns": (C.c_int, [_HP, _i32p]),
+    "smolmc_set_environments": (C.c_int, [_HP, C.POINTER(capi.smolmc_environments)]),
+    "smolmc_environments_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 3),
+    "smolmc_eval_environments": (C.c_int, [_HP, _i32p, C.c_int, _i32p, _i32p]),
+    "smolmc_get_sample_environments": (C.c_int, [_HP, _i32p]),
     "smolmc_replay": (C.c_int, [_HP, C.c_int64, _i32p, _f64p, _f64p, _u8p, _f64p, _f64p]),
     "smolmc_last_kernel_ms": (C.c_int, [_HP, C.POINTER(C.c_float)]),
     "smolmc_eval_full": (C.c_int, [_HP, _i32p, C.c_int, _f64p]),
@@ -188,7 +192,7 @@ def species_counts(tables, occupancies, width=None):
 SAMPLE_FLAGS = (("occupancy", capi.SAMPLE_OCCUPANCY), ("bias", capi.SAMPLE_BIAS), ("wl", capi.SAMPLE_WL),
                 ("observables", capi.SAMPLE_OBSERVABLES), ("minima", capi.SAMPLE_MINIMA), ("statistics", capi.SAMPLE_STATISTICS),
                 ("structure", capi.SAMPLE_STRUCTURE), ("connectivity", capi.SAMPLE_CONNECTIVITY),
-                ("patterns", capi.SAMPLE_PATTERNS))
+                ("patterns", capi.SAMPLE_PATTERNS), ("environments", capi.SAMPLE_ENVIRONMENTS))
 
 
 class EngineError(RuntimeError):
@@ -807,13 +811,51 @@ class Engine:
         self._chk(self._lib.smolmc_get_sample_patterns(self._h, _p(cells, C.c_int32)))
         return cells
 
+    # ---- environments: coordination environments, counted by the observables' kernel ---------
+    def set_environments(self, spec):
+        """The environment spec of this handle (smolmc_set_environments): an ``environments.Environments`` in the caller's
+        site numbering, or None to remove it.  It rests on the observables in force, whose kinds its class maps index.
+        The engine copies and uploads; it refuses, naming the reason, a handle without observables, a site or class out of
+        range, more cells than ``capi.MAX_ENV_CELLS`` and a launch that does not fit LDS."""
+        if spec is not None and spec.n_kinds != self.observables_shape()[0]:
+            raise ValueError(f"the environment spec maps {spec.n_kinds} kinds, the observables in force have "
+                             f"{self.observables_shape()[0]} (call set_observables first)")
+        self._set_spec(self._lib.smolmc_set_environments, spec, "the environment spec is")
+
+    def environments_shape(self):
+        """(n_sets, n_cells, n_centres) in force, zeros when no spec is set (smolmc_environments_shape)."""
+        v = [C.c_int() for _ in range(3)]
+        self._chk(self._lib.smolmc_environments_shape(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def environments(self, occupancies=None, codes=False):
+        """cells (n, n_cells) int32 of occupancies (n, N) evaluated on the device (smolmc_eval_environments), or, with
+        None, of the walkers' current states (n = R).  ``codes``: (cells, codes (n, n_centres) int32), the set-local code
+        of every centre or -1 for a skipped one."""
+        _, nc, ncen = self.environments_shape()
+        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
+        n = self.R if occ is None else len(occ)
+        cells = np.zeros((n, nc), dtype=np.int32)
+        out = np.zeros((n, ncen), dtype=np.int32) if codes else None
+        self._chk(self._lib.smolmc_eval_environments(self._h, _p(occ, C.c_int32), n, _p(cells, C.c_int32), _p(out, C.c_int32)))
+        return (cells, out) if codes else cells
+
+    def sample_environments(self):
+        """environment_counts (ns, R, n_cells) of the block ``fetch_samples`` would deliver next; the block stays
+        undelivered (smolmc_get_sample_environments)."""
+        _, nc, _ = self.environments_shape()
+        _, ns, _ = self.pending_samples()
+        cells = np.empty((ns, self.R, nc), dtype=np.int32)
+        self._chk(self._lib.smolmc_get_sample_environments(self._h, _p(cells, C.c_int32)))
+        return cells
+
     # ---- statistics: running moments, blocking sums and a histogram, kept on the device -----
     def set_statistics(self, spec):
         """The statistics record of this handle (smolmc_set_statistics): a ``statistics.Statistics``, or None to remove
         it.  A new spec starts an empty record.  The record lives as long as the handle: ``set_state`` and
         ``discard_samples`` leave it alone."""
         shape = () if spec is None else (self.F, self.observables_shape()[0], self.structure_shape()[2], self.connectivity_shape()[0],
-                                             self.patterns_shape()[1])
+                                             self.patterns_shape()[1], self.environments_shape()[1])
         self._set_spec(self._lib.smolmc_set_statistics, spec, None, *shape)
         self.statistics_spec = spec
 
@@ -854,21 +896,21 @@ class Engine:
         return self._kernel_ms("smolmc_debug_statistics_kernel_ms")
 
     def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False,
-                    minima=False, statistics=False, structure=False, connectivity=False, patterns=False):
+                    minima=False, statistics=False, structure=False, connectivity=False, patterns=False, environments=False):
         """Advance nsamples*thin_by steps recording one sample per walker every thin_by steps
         on the device; returns dict(enthalpy (ns,R), features (ns,R,F), accepted (ns,R) bool,
         occupancy (ns,R,N) or None[, bias (ns,R)][, the Wang-Landau trace][, species_counts, pair_counts]
         [, structure_amplitudes (ns,R,Q,K,2) int64, structure_intensities (ns,R,I)][, connectivity (ns,R,G,24) int64]
-        [, pattern_counts (ns,R,n_cells) int32]).
+        [, pattern_counts (ns,R,n_cells) int32][, environment_counts (ns,R,n_cells) int32]).
         Occupancies come back as int32 (the reference's trace dtype) or, with ``packed``, as the ring's own
         uint8 -- a quarter of the transfer.  = ``run_sampled_async`` + ``fetch_samples``."""
         self.run_sampled_async(nsamples, thin_by, occupancy=occupancy, bias=bias, wl=wl, observables=observables,
                                minima=minima, statistics=statistics, structure=structure, connectivity=connectivity,
-                               patterns=patterns)
+                               patterns=patterns, environments=environments)
         return self.fetch_samples(packed=packed)
 
     def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False, observables=False, minima=False,
-                          statistics=False, structure=False, connectivity=False, patterns=False):
+                          statistics=False, structure=False, connectivity=False, patterns=False, environments=False):
         """Queue one block of the device ring (smolmc_run_sampled): returns at once.  The ring has two
         slots; queue block k + 1 BEFORE fetching block k and the download of k overlaps the kernel of
         k + 1 (the order ``fetch_samples`` delivers in: oldest first).  ``observables``: the kind and pair
@@ -878,9 +920,11 @@ class Engine:
         stays on the device.  ``statistics``: likewise every row is offered to the record of ``set_statistics``.
         ``structure``: the amplitudes and intensities of ``set_structure_factor`` for every row, like ``observables``.
         ``connectivity``: the stats of ``set_connectivity`` for every row, likewise.  ``patterns``: the cells of
-        ``set_patterns`` for every row, counted by the launch that counts the observables."""
+        ``set_patterns`` for every row, counted by the launch that counts the observables.  ``environments``: the cells of
+        ``set_environments`` for every row, by the same launch."""
         asked = dict(occupancy=occupancy, bias=bias, wl=wl, observables=observables, minima=minima, statistics=statistics,
-                     structure=structure, connectivity=connectivity, patterns=patterns)
+                     structure=structure, connectivity=connectivity, patterns=patterns,
+                     environments=environments)
         flags = sum(flag for keyword, flag in SAMPLE_FLAGS if asked[keyword])
         self._chk(self._lib.smolmc_run_sampled(self._h, int(nsamples), int(thin_by), flags))
 
@@ -914,6 +958,8 @@ class Engine:
             obs["connectivity"] = self.sample_connectivity()
         if flags & capi.SAMPLE_PATTERNS:
             obs["pattern_counts"] = self.sample_patterns()
+        if flags & capi.SAMPLE_ENVIRONMENTS:
+            obs["environment_counts"] = self.sample_environments()
         if flags & capi.SAMPLE_BIAS:
             extra["bias"] = np.empty((ns, self.R))
         if flags & capi.SAMPLE_WL:

@@ -1541,6 +1541,13 @@ class SampleContainer:
         cells = self.get_pattern_counts(discard, thin_by, flat)
         return probabilities(cells, [int(x) for x in self.metadata["patterns"]["cell_ptr"]])
 
+    def get_environment_counts(self, discard=0, thin_by=1, flat=True):
+        """The ``environment_counts`` trace: (..., n_cells) int32 cells of every sample; the metadata's ``environments``
+        entry says where every set's cells start (``cell_ptr``), its width and what its classes are."""
+        if "environment_counts" not in self._schema:
+            raise ValueError("these samples carry no environment_counts trace: sample with Sampler.from_ensemble(environments=)")
+        return self.get_trace_value("environment_counts", discard, thin_by, flat)
+
     def get_species_counts(self, discard=0, thin_by=1, flat=True):
         """Counts per species name summed over the sublattices that host it (container.py:336-347)."""
         out = {}
@@ -1623,6 +1630,13 @@ class SampleContainer:
                           "meta/pat_cell_ptr": np.asarray(pat["cell_ptr"], dtype=np.int64),
                           "meta/pat_class_of_kind": np.asarray(pat["class_of_kind"], dtype=np.int32),
                           "meta/pat_orbit_ids": np.asarray(pat["set_orbit_ids"] if pat["set_orbit_ids"] is not None else [], dtype=np.int64)})
+        env = self.metadata.get("environments")
+        if env is not None:  # the sets of the environment_counts trace: their shapes and class maps
+            extra.update({"meta/env_shape": np.asarray([env["width"], env["n_centre_classes"], env["n_neigh_classes"], env["n_centres"]],
+                                                       dtype=np.int64),
+                          "meta/env_cell_ptr": np.asarray(env["cell_ptr"], dtype=np.int64),
+                          "meta/env_centre_class_of_kind": np.asarray(env["centre_class_of_kind"], dtype=np.int32),
+                          "meta/env_neigh_class_of_kind": np.asarray(env["neigh_class_of_kind"], dtype=np.int32)})
         rec = self.minima
         if rec is not None:  # the minima record: its arrays, the spec and the two counters
             spec = rec.spec
@@ -1763,6 +1777,13 @@ class SampleContainer:
             c.metadata["patterns"] = dict(n_sets=len(arity), n_cells=int(ptr[-1]), arity=arity, n_classes=ncls, n_tuples=ntup,
                                           cell_ptr=ptr, class_of_kind=d["meta/pat_class_of_kind"].tolist(),
                                           set_orbit_ids=ids if ids else None)
+        if "meta/env_shape" in d.files:
+            width, na, nb, ncen = (d["meta/env_shape"][i].tolist() for i in range(4))
+            ptr = d["meta/env_cell_ptr"].tolist()
+            c.metadata["environments"] = dict(n_sets=len(width), n_cells=int(ptr[-1]), width=width, n_centre_classes=na,
+                                              n_neigh_classes=nb, n_centres=ncen, cell_ptr=ptr,
+                                              centre_class_of_kind=d["meta/env_centre_class_of_kind"].tolist(),
+                                              neigh_class_of_kind=d["meta/env_neigh_class_of_kind"].tolist())
         if "meta/minima_shape" in d.files:
             offers, nw, n_weights, n_axes = (int(x) for x in d["meta/minima_shape"])
             rec = {f: d[f"meta/minima_{f}"] for f in ("value", "enthalpy", "features", "occupancy", "counts", "walker", "sample", "step")}
@@ -1914,12 +1935,13 @@ class Sampler:
         self._structure = None      # structure.StructureFactor evaluated on the device for every sample, or None
         self._connectivity = None   # connectivity.Connectivity evaluated on the device for every sample, or None
         self._patterns = None       # patterns.Patterns counted on the device for every sample, or None
+        self._environments = None   # environments.Environments counted on the device for every sample, or None
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
                       nwalkers=1, rank=None, world_size=None, device=None, chemical_potentials=None, windows=None,
                       observables=None, minima=None, statistics=None, structure_factor=None, connectivity=None,
-                      patterns=None, synchronise=False, **kwargs):
+                      patterns=None, environments=None, synchronise=False, **kwargs):
         """sampler.py:52-139: default step 'flip' when chemical potentials are set else
         'swap'; default kernel Metropolis; one kernel (seed) per walker.
 
@@ -1951,7 +1973,12 @@ class Sampler:
 
         ``patterns``: a ``patterns.Patterns`` on the ``observables`` given here -- the species patterns on its site tuples
         are counted on the device for every sample, by the launch that counts the observables, and traced as
-        ``pattern_counts`` (n_cells,) int32; pattern columns of a statistics record need it."""
+        ``pattern_counts`` (n_cells,) int32; pattern columns of a statistics record need it.
+
+        ``environments``: an ``environments.Environments`` on the ``observables`` given here -- the coordination environments
+        of its centres are counted on the device for every sample, by the same launch, and traced as ``environment_counts``
+        (n_cells,) int32; environment columns of a statistics record need it.  With ``keep_occupancy=False`` the occupancies
+        stay on the device.  A sampler sharded across ranks is out of scope: every rank traces its own walkers."""
         from . import parallel
 
         if windows is not None and observables is not None:
@@ -1962,6 +1989,10 @@ class Sampler:
             raise ValueError("connectivity= with windows=: the samples of per-walker windows do not come from the sample ring")
         if windows is not None and patterns is not None:
             raise ValueError("patterns= with windows=: the samples of per-walker windows do not come from the sample ring")
+        if windows is not None and environments is not None:
+            raise ValueError("environments= with windows=: the samples of per-walker windows do not come from the sample ring")
+        if environments is not None and observables is None:
+            raise ValueError("environments= needs observables=: the class maps of an environment spec index the kinds of the observables")
         if patterns is not None and observables is None:
             raise ValueError("patterns= needs observables=: the class maps of a pattern spec index the kinds of the observables")
         if synchronise and windows is None:
@@ -2008,6 +2039,8 @@ class Sampler:
             sampler._set_connectivity(connectivity)
         if patterns is not None:
             sampler._set_patterns(patterns)
+        if environments is not None:
+            sampler._set_environments(environments)
         if minima is not None:
             sampler._set_minima(minima)
         if statistics is not None:
@@ -2023,6 +2056,8 @@ class Sampler:
             raise ValueError("a statistics record with connectivity columns needs a sampler built with connectivity=")
         if spec.pattern_columns() and self._patterns is None:
             raise ValueError("a statistics record with pattern columns needs a sampler built with patterns=")
+        if spec.environment_columns() and self._environments is None:
+            raise ValueError("a statistics record with environment columns needs a sampler built with environments=")
         self._statistics = spec
         if self._engine is not None:
             self._engine.set_statistics(spec)
@@ -2143,6 +2178,22 @@ class Sampler:
         self._patterns = spec
         if self._engine is not None:
             self._engine.set_patterns(spec)
+
+    def _set_environments(self, spec):
+        """Trace ``spec`` with every sample: the container's schema gains the trace, its metadata the sets' shapes and
+        class maps."""
+        nw, N = self.samples.shape
+        if spec.num_sites != N:
+            raise ValueError(f"the environment spec is defined on {spec.num_sites} sites, the ensemble has {N}")
+        if self._observables is None or spec.n_kinds != self._observables.n_kinds:
+            raise ValueError("the environment spec must rest on the sampler's observables: its class maps index their kinds")
+        if self.samples.num_samples:
+            raise ValueError("the container holds samples without the environment_counts trace: clear_samples() first")
+        self.samples._schema["environment_counts"] = (np.dtype(np.int32), (nw, spec.n_cells))
+        self.samples.metadata["environments"] = spec.describe()
+        self._environments = spec
+        if self._engine is not None:
+            self._engine.set_environments(spec)
 
     @classmethod
     def _from_ensemble_windows(cls, ensemble, wx, *args, step_type=None, kernel_type=None, seeds=None, nwalkers=1, rank=None,
@@ -2349,6 +2400,8 @@ class Sampler:
                 self._engine.set_observables(self._observables)
             if self._patterns is not None:  # (behind the observables it rests on, before the statistics record)
                 self._engine.set_patterns(self._patterns)
+            if self._environments is not None:
+                self._engine.set_environments(self._environments)
             if self._minima is not None:  # (a new handle starts an empty record)
                 self._engine.set_minima(self._minima)
                 self._minima_offers = 0
@@ -2440,6 +2493,8 @@ class Sampler:
             tr.connectivity = eng.connectivity()
         if self._patterns is not None:
             tr.pattern_counts = eng.patterns()
+        if self._environments is not None:
+            tr.environment_counts = eng.environments()
         return tr
 
     def _sample_blocks(self, nsteps, initial_occupancies, thin_by, max_block=0, state_loaded=False, keep_occupancy=True):
@@ -2500,6 +2555,9 @@ class Sampler:
         pt = self._patterns
         if pt is not None:
             per_sample += nw * 4 * pt.n_cells
+        ev = self._environments
+        if ev is not None:
+            per_sample += nw * 4 * ev.n_cells
         if is_wl:
             L = len(k0._levels)
             per_sample += nw * L * (24 + 8 * F)
@@ -2516,7 +2574,8 @@ class Sampler:
         def queue(n):
             eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl, observables=obs is not None,
                                   minima=self._minima is not None, statistics=self._statistics is not None,
-                                  structure=sf is not None, connectivity=cn is not None, patterns=pt is not None)
+                                  structure=sf is not None, connectivity=cn is not None, patterns=pt is not None,
+                                  environments=ev is not None)
             if self._minima is not None:
                 self._minima_offers += n
 
@@ -2565,6 +2624,8 @@ class Sampler:
                 block.update(connectivity=ring["connectivity"])
             if "pattern_counts" in ring:
                 block.update(pattern_counts=ring["pattern_counts"])
+            if "environment_counts" in ring:
+                block.update(environment_counts=ring["environment_counts"])
             yield block
 
     def _wl_run_with_host_checks(self, eng, nsteps):

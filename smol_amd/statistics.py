@@ -70,6 +70,14 @@ def pattern(c):
     return ("pattern", int(c))
 
 
+def environment(c):
+    """Cell ``c`` of the environment spec in force (``environments.Environments``; ``Environments.cell`` gives the number of
+    an environment), read as a double."""
+    if int(c) < 0:
+        raise ValueError(f"environment cell {c} is negative")
+    return ("environment", int(c))
+
+
 def kind(observables, name_or_k):
     """Count column of kind ``name_or_k`` of ``observables`` (an ``observables.Observables``): a kind number, or a name
     looked up in ``observables.kind_names`` when it has them."""
@@ -117,11 +125,13 @@ class Statistics:
     n_weights = property(lambda self: 0 if self.weights is None else len(self.weights))
     n_pairs = property(lambda self: self.n_columns * (self.n_columns + 1) // 2)
 
-    def sources(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0):
+    def sources(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0, n_env_cells=0):
         """int32 column sources of the C ABI: 0 enthalpy, 1 + i feature i, 1 + F + k kind k, 1 + F + K the weighted sum,
         2 + F + K + i intensity i (i < ``n_intensities``), 2 + F + K + I + 24 g + c number c of graph g of the connectivity
-        spec (g < ``n_graphs``), 2 + F + K + I + 24 G + c cell c of the pattern spec (c < ``n_cells``)."""
+        spec (g < ``n_graphs``), 2 + F + K + I + 24 G + c cell c of the pattern spec (c < ``n_cells``),
+        2 + F + K + I + 24 G + P + c cell c of the environment spec (P = ``n_cells``, c < ``n_env_cells``)."""
         F, K, I, G, PC = int(n_features), int(n_kinds), int(n_intensities), int(n_graphs), int(n_cells)
+        EC = int(n_env_cells)
         out = []
         for c in self.columns:
             if c[0] == "enthalpy":
@@ -144,6 +154,10 @@ class Statistics:
                 if not 0 <= c[1] < PC:
                     raise ValueError(f"cell {c[1]} outside the {PC} cells of the pattern spec")
                 out.append(2 + F + K + I + 24 * G + c[1])
+            elif c[0] == "environment":
+                if not 0 <= c[1] < EC:
+                    raise ValueError(f"cell {c[1]} outside the {EC} cells of the environment spec")
+                out.append(2 + F + K + I + 24 * G + PC + c[1])
             else:
                 out.append(c[1])
         return np.asarray(out, dtype=np.int32)
@@ -164,9 +178,15 @@ class Statistics:
         """Indices into ``columns`` of the pattern cells, in order."""
         return [i for i, c in enumerate(self.columns) if c[0] == "pattern"]
 
-    def column_values(self, enthalpy, features, counts=None, intensities=None, connectivity=None, patterns=None):
+    def environment_columns(self):
+        """Indices into ``columns`` of the environment cells, in order."""
+        return [i for i, c in enumerate(self.columns) if c[0] == "environment"]
+
+    def column_values(self, enthalpy, features, counts=None, intensities=None, connectivity=None, patterns=None,
+                      environments=None):
         """x (..., C) float64 of rows with enthalpy (...), features (..., F), counts (..., K) or None, intensities
-        (..., I) or None, connectivity stats (..., G, 24) or None, pattern cells (..., n_cells) or None."""
+        (..., I) or None, connectivity stats (..., G, 24) or None, pattern cells (..., n_cells) or None, environment cells
+        (..., n_env_cells) or None."""
         H = np.asarray(enthalpy, dtype=np.float64)
         f = np.asarray(features, dtype=np.float64).reshape(H.shape + (-1,))
         F = f.shape[-1]
@@ -174,8 +194,9 @@ class Statistics:
         I = 0 if intensities is None else np.asarray(intensities).shape[-1]
         G = 0 if connectivity is None else np.asarray(connectivity).shape[-2]
         PC = 0 if patterns is None else np.asarray(patterns).shape[-1]
+        EC = 0 if environments is None else np.asarray(environments).shape[-1]
         x = np.empty(H.shape + (self.n_columns,))
-        for j, src in enumerate(self.sources(F, K, I, G, PC)):
+        for j, src in enumerate(self.sources(F, K, I, G, PC, EC)):
             if src == 0:
                 x[..., j] = H
             elif src <= F:
@@ -190,15 +211,17 @@ class Statistics:
                 x[..., j] = np.asarray(connectivity).reshape(H.shape + (24 * G,))[..., src - 2 - F - K - I].astype(np.float64)
             elif src <= 1 + F + K + I + 24 * G + PC:
                 x[..., j] = np.asarray(patterns).reshape(H.shape + (PC,))[..., src - 2 - F - K - I - 24 * G].astype(np.float64)
+            elif src <= 1 + F + K + I + 24 * G + PC + EC:
+                x[..., j] = np.asarray(environments).reshape(H.shape + (EC,))[..., src - 2 - F - K - I - 24 * G - PC].astype(np.float64)
             else:
-                raise ValueError(f"column source {src} outside 0..{1 + F + K + I + 24 * G + PC}")
+                raise ValueError(f"column source {src} outside 0..{1 + F + K + I + 24 * G + PC + EC}")
         return x
 
-    def c_struct(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0):
+    def c_struct(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0, n_env_cells=0):
         """(capi.smolmc_statistics, the arrays it points to)."""
         from . import capi
 
-        cols = self.sources(n_features, n_kinds, n_intensities, n_graphs, n_cells)
+        cols = self.sources(n_features, n_kinds, n_intensities, n_graphs, n_cells, n_env_cells)
         keep = (cols, self.weights)
         s = capi.smolmc_statistics(
             self.key, len(cols), cols.ctypes.data_as(C.POINTER(C.c_int32)) if len(cols) else None, self.n_weights,
@@ -236,7 +259,8 @@ class StatisticsRecord:
     n_keys = property(lambda self: len(self.n))
 
     # ---- the definition ------------------------------------------------------------------------------------------
-    def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None, connectivity=None, patterns=None):
+    def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None, connectivity=None, patterns=None,
+              environments=None):
         """Offer samples (ns, R) -- or one sample (R,) -- in order.  ``key_of_row`` (R,) or (ns, R): the key of every
         row, a permutation of 0 .. R - 1 per sample (None: the walker).  Vectorised over the keys, a loop over samples."""
         spec = self.spec
@@ -248,7 +272,8 @@ class StatisticsRecord:
         inten = None if intensities is None else np.asarray(intensities, dtype=np.float64).reshape(ns, nk, -1)
         conn = None if connectivity is None else np.asarray(connectivity).reshape(ns, nk, -1, 24)
         pat = None if patterns is None else np.asarray(patterns).reshape(ns, nk, -1)
-        x_all = spec.column_values(H, f, cnt, inten, conn, pat)
+        env = None if environments is None else np.asarray(environments).reshape(ns, nk, -1)
+        x_all = spec.column_values(H, f, cnt, inten, conn, pat, env)
         if key_of_row is None:
             keys = np.broadcast_to(np.arange(nk), (ns, nk))
         else:
