@@ -2227,6 +2227,12 @@ static int univ_lds_layout(smolmc_handle *h, const smolmc_tables *) {
                                (((size_t)up.dfeat_cells << up.dfeat_shift) + (size_t)up.acc_cells) * 8,
                      with_occ = (scratch + (size_t)h->Npad + 15) & ~(size_t)15;
         up.occ_lds = with_occ <= 160 * 1024 - 256 && !smolmc_env(ENV_UNIV_OCC_HBM);
+        // the occupancy of one wave fits a CU's LDS alone but not behind the dictionaries: the dictionaries go (never a
+        // request above the 160 KiB a CU has), the occupancy stays
+        if (up.occ_lds && (size_t)up.lds_shared + with_occ > 160 * 1024) {
+            up.dict_lds = 0;
+            up.lds_shared = 0;
+        }
         up.lds_per_wave = (int)(up.occ_lds ? with_occ : scratch);
         h->univ_wpb = 4;
         while (h->univ_wpb > 1 && (size_t)up.lds_shared + (size_t)up.lds_per_wave * h->univ_wpb > 64 * 1024) h->univ_wpb /= 2;
@@ -3033,10 +3039,17 @@ extern "C" int smolmc_kernel_info(const smolmc_handle *h, char *buf, int n) {
     if (!h || !buf || n <= 0) return fail("null argument");
     if (h->dist) return smolmc_dist_kernel_info(h, buf, n);
     const LeanFamilyRow *row = h->lean() ? &lean_families[h->family - K_LEAN] : nullptr;
-    if (h->univ())
-        snprintf(buf, (size_t)n, "universal occ=%s field=%d lds=%zu (%s)", h->up.occ_lds ? "lds" : "hbm", h->kp.ew_field,
-                 (size_t)h->up.lds_shared + (size_t)h->up.lds_per_wave * h->univ_wpb, h->general_ok ? "TableFlip outside the lean families" : h->general_reason.c_str());
-    else if (row) {
+    if (h->univ()) {
+        // the layout (univ_lds_layout) and the instantiation (smolmc_univ_selector) of the handle's launches
+        const int sel = smolmc_univ_selector(h, h->up);
+        char cells[24];
+        if (h->up.dfeat_cells) snprintf(cells, sizeof(cells), "dshift=%d", h->up.dfeat_shift);
+        else snprintf(cells, sizeof(cells), "dcells=0");
+        snprintf(buf, (size_t)n, "universal occ=%s field=%d lds=%zu wpb=%d %s dict=%d k1=%d table=%d dense=%d (%s)",
+                 h->up.occ_lds ? "lds" : "hbm", h->kp.ew_field, (size_t)h->up.lds_shared + (size_t)h->up.lds_per_wave * h->univ_wpb,
+                 h->univ_wpb, cells, (sel & UNIV_SEL_DICT) ? 1 : 0, (sel & UNIV_SEL_K1) ? 1 : 0, (sel & UNIV_SEL_TABLE) ? 1 : 0,
+                 (sel & UNIV_SEL_DENSE) ? 1 : 0, h->general_ok ? "TableFlip outside the lean families" : h->general_reason.c_str());
+    } else if (row) {
         snprintf(buf, (size_t)n, "%s nslot=%d mm=%d field=%d lds=%zu%s", row->name,
                  h->lean_nslot, h->lean_mm, h->lp.ew_field, h->lean_lds,
                  h->lean_solo ? (h->lean_occ ? " solo=1 occ=6" : " solo=1") : (h->lean_kf ? " kf=1" : ""));

@@ -1235,6 +1235,9 @@ void smolmc_pat_free(SmolmcPat &P);
 void smolmc_envs_free(SmolmcEnvSpec &E);
 void smolmc_obs_free(SmolmcObs &O);
 int smolmc_launch_univ(smolmc_handle *h, const UParams &up, int replay);
+// the instantiation a launch of the universal kernel takes: UNIV_SEL_* bits (the launcher and smolmc_kernel_info read it)
+enum { UNIV_SEL_DENSE = 1, UNIV_SEL_TABLE = 2, UNIV_SEL_K1 = 4, UNIV_SEL_OCC_LDS = 8, UNIV_SEL_DICT = 16 };
+int smolmc_univ_selector(const smolmc_handle *h, const UParams &up);
 int smolmc_launch_general_2(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_4(smolmc_handle *h, const KParams &kp, int replay);
 int smolmc_launch_general_8(smolmc_handle *h, const KParams &kp, int replay);

@@ -360,8 +360,19 @@ def _general(k, f):  # launch_general_nslot (mc_general.h); engine.hip: general_
             "(KParams, int)"), key, variants
 
 
+def _universal(info):  # smolmc_univ_selector (univ.hip): kernel_info prints the selector's bits, univ_select names all sixteen
+    w = dict(re.findall(r" (\w+)=(\w+)", info.split(" (")[0]))
+    if not {"occ", "dict", "k1", "table", "dense"} <= set(w):
+        raise NoLeanLauncher(f"no prediction for the universal kernel: this kernel_info does not carry its selector: {info}")
+    occ, k1, table, dense, dl = w["occ"] == "lds", w["k1"] == "1", w["table"] == "1", w["dense"] == "1", w["dict"] == "1"
+    key = (8 if occ else 0) | (4 if k1 else 0) | (2 if table else 0) | (1 if dense else 0)
+    return (f"void mc_univ_kernel<{_b(occ)}, {_b(k1)}, {_b(table)}, {4 if dense else 2}, {_b(dl)}>(UParams, int)"), key, list(range(16))
+
+
 def trace(info, facts):
     """(symbol, key, variant list) of the launch: the key and the list it was matched against, for the fall-through check."""
+    if isinstance(info, str) and info.startswith("universal"):
+        return _universal(info)
     k = parse_info(info) if isinstance(info, str) else info
     if k.family == "general":
         return _general(k, facts)
@@ -387,7 +398,7 @@ NEVER_DISPATCHED = [
     ("lean LV_WL", lambda c: c.template == "mc_lean_kernel" and _has(c, "WL"),
      "round 2's Wang-Landau variant of mc_lean_kernel: family_of sends every single-class Wang-Landau handle to K_WL or K_TABLE_WL, "
      "so launch_lean_nslot never sees kernel_type == WANGLANDAU; kept so that the other kernels of lean_n*.hip do not move",
-     "smol_amd/csrc/mc_lean.h:2544 (and engine.hip:2299)"),
+     "smol_amd/csrc/mc_lean.h:2544 (and engine.hip:2305)"),
     ("mc_kernel MM outside its index type", lambda c: c.template == "mc_kernel" and c.mm in ((2, 5) if _has(c, "GENERIC") else (6,)),
      "GENERIC rows run MM 3 or 6, the others 2, 3 or 5; all four are instantiated for every combination",
      "smol_amd/csrc/mc_general.h:796-798"),
@@ -873,6 +884,11 @@ from tests.dispatch_targets import TARGETS  # noqa: E402
 
 CASES = [c for c in candidates() if c.id in TARGETS]
 assert len(CASES) == len(TARGETS), sorted(set(TARGETS) - {c.id for c in CASES})[:5]
+# the universal kernel's cells: the cases of tests/univ_layout.py (run by tests/test_gpu_univ_layout.py, which holds
+# predict() of their kernel_info() against these), each on the instantiation its layout selects
+from tests import univ_layout  # noqa: E402
+
+UNIV_TARGETS = {name: show(coords(univ_layout.case_layout(name).symbol())) for name in univ_layout.CASE_IDS}
 
 
 def coordinates_of(c):
@@ -882,8 +898,8 @@ def coordinates_of(c):
 
 def classify(symbols, cases=None):
     """{symbol: 'covered' | 'dispatchable, not in the reduced matrix' | 'never dispatched' | 'helper'}; a symbol that is
-    none of them raises.  ``cases``: the target strings of the cases that count (default: TARGETS)."""
-    covered = set(TARGETS.values() if cases is None else cases)
+    none of them raises.  ``cases``: the target strings of the cases that count (default: TARGETS and UNIV_TARGETS)."""
+    covered = set(TARGETS.values()) | set(UNIV_TARGETS.values()) if cases is None else set(cases)
     out = {}
     for s in symbols:
         c = coords(s)
@@ -937,14 +953,23 @@ UNREACHED = [
      "mc_kernel MM 6 at NSLOT 2: fcc {2: 5.0, 3: 4.2, 4: 3.0} in a 2x2x2 cell is aliased, but its quadruplets keep three distinct "
      "other sites (MM 3); MM 6 is covered at NSLOT 4, 8 and 16",
      "engine.hip:438 (aliased ? (need_mm <= 3 ? 3 : 6))"),
-    # NOT planner refusals: two families the matrix does not model.  With them UNREACHED holds 69 of the 550 required
-    # coordinates (12.5 %), above the 5 % the matrix was meant to keep; without them 25 of 506.
-    (lambda q: q[1] in ("univ", "univ-dict"),
-     "NOT MODELLED, 36 coordinates: the universal kernel's 32 instantiations.  SMOLMC_FORCE_UNIVERSAL and TableFlip outside the lean "
-     "families put any model on it, so handles are easy to make; what is missing is predict(): univ_select reads up.dict_lds and "
-     "up.all_k1 (univ_pack_records, engine.hip:2113-2141) and R > 2048 (univ.hip:10), and kernel_info() prints only occ= of these, so "
-     "a prediction would restate the record packing instead of the dispatch",
-     "smol_amd/csrc/univ.hip:11; tests/test_gpu_universal.py holds the kernel against the oracle on the release library"),
+    # NOT planner refusals.  The universal kernel's 32 instantiations have cells of their own (UNIV_TARGETS: 10 of them, every
+    # Flip / Swap instantiation with the occupancy in LDS); the two entries below are the other 22, which a switch or a flip table
+    # reaches on any model.  The distance kernels are not modelled.  With them UNREACHED holds 56 of the 550 required
+    # coordinates (10.2 %), above the 5 % the matrix was meant to keep; without the universal and distance entries 25 of 506.
+    (lambda q: q[1] in ("univ", "univ-dict") and q[0] == "FV" and "OCC_LDS" not in q[2].split("|") and (q[1], q[2]) != ("univ-dict", "K1|WPS4"),
+     "15 coordinates: the occupancy in HBM (SMOLMC_UNIV_OCC_HBM, or a cell beyond a CU's LDS) on every instantiation but the one "
+     "cell of the layout cases (dense-hbm).  Without the occupancy block the LDS layout has nothing left that these instantiations "
+     "vary, so the layout cases stop at one; tests/test_gpu_universal.py runs the HBM kernels on every golden model, TableFlip shape "
+     "and a 262 144-site cell (3 to 5 walkers, release library) without pinning their cells",
+     "smol_amd/csrc/univ.hip: smolmc_univ_selector (UNIV_SEL_OCC_LDS); engine.hip: univ_lds_layout"),
+    (lambda q: q[1] in ("univ", "univ-dict") and ((q[0] == "FV" and "TABLE" in q[2].split("|") and "OCC_LDS" in q[2].split("|")
+                                                   and (q[1], q[2]) != ("univ-dict", "OCC_LDS|K1|TABLE|WPS4")) or q == ("shape", "univ", 0, 0, "table")),
+     "8 coordinates: TableFlip handles with the occupancy in LDS beyond the one cell of the layout cases (crowded-table: K1, dense, "
+     "dictionaries).  The others need a flip table on a model with several functions per record, with more than 64 records or with "
+     "long tensors; tests/test_gpu_universal.py::test_table_flip_chains_on_the_universal_kernel runs nine TableFlip shapes of the "
+     "reference at 4 walkers (release library) without pinning their cells",
+     "smol_amd/csrc/univ.hip: smolmc_univ_selector (UNIV_SEL_TABLE)"),
     (lambda q: q[1] in ("dist", "dist-replay"),
      "NOT MODELLED, 8 coordinates: the distance-objective kernels' 6 instantiations (NSLOT 1 / 2 / 4, run and replay).  They are "
      "created by smolmc_create_distance, not by the planners above, and OracleMC has no distance objective to compare a stream with",

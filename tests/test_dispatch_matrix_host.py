@@ -32,7 +32,8 @@ def test_every_symbol_falls_into_exactly_one_class(symbols):
     # the classes partition the Monte-Carlo instantiations; a cell is one symbol
     shown = [dm.show(dm.coords(s)) for s in symbols if dm.coords(s) is not None]
     assert len(set(shown)) == len(shown)
-    assert count["covered"] == len(set(dm.TARGETS.values()))
+    assert count["covered"] == len(set(dm.TARGETS.values())) + len(set(dm.UNIV_TARGETS.values()))
+    assert not set(dm.TARGETS.values()) & set(dm.UNIV_TARGETS.values())
     # the entries of NEVER_DISPATCHED that name symbols of this library (the others guard against additions)
     named = collections.Counter(dm.never_dispatched(dm.coords(s)) for s in symbols if dm.coords(s) is not None)
     assert named["lean LV_WL"] == 8 and named["mc_kernel MM outside its index type"] == 32, named
@@ -47,6 +48,8 @@ def test_the_bounds_library_has_the_same_kernels(symbols):
 def test_every_case_names_a_kernel_of_the_library(symbols):
     by_show = {dm.show(dm.coords(s)): s for s in symbols if dm.coords(s) is not None}
     assert len({c.id for c in dm.CASES}) == len(dm.CASES)
+    for name, target in dm.UNIV_TARGETS.items():  # the universal kernel's cells: the layout cases
+        assert target in by_show and dm.coords(by_show[target]).template == "mc_univ_kernel", (name, target)
     for case in dm.CASES:
         target = dm.TARGETS[case.id]
         assert target in by_show, (case.id, target)
@@ -57,7 +60,8 @@ def test_coverage_rule_and_its_teeth(symbols):
     """Among dispatchable symbols every (F, V) pair and every (F, NSLOT, MM, STEP) tuple has a case or an UNREACHED entry;
     and the rule bites: without any one case that is the sole cover of a coordinate, the assertion fails."""
     need = dm.required(symbols)
-    targets = [dm.TARGETS[c.id] for c in dm.CASES]
+    targets = [dm.TARGETS[c.id] for c in dm.CASES] + sorted(set(dm.UNIV_TARGETS.values()))
+    names = [c.id for c in dm.CASES] + sorted(set(dm.UNIV_TARGETS.values()))
     cover = [dm.covered_by([t], symbols) for t in targets]  # (each case's two coordinates)
 
     def uncovered(covers):
@@ -67,14 +71,17 @@ def test_coverage_rule_and_its_teeth(symbols):
     left = need - set().union(*cover)
     mc = {q for q in need if q[1] not in ("univ", "univ-dict", "dist", "dist-replay")}
     print(f"required {len(need)}, covered {len(need) - len(left)}, unreached {len(left)} = {100.0 * len(left) / len(need):.1f} % "
-          f"({len(left - mc)} of them the universal and distance kernels, which the matrix does not model; {len(left & mc)} of {len(mc)} planner refusals)")
+          f"({len(left - mc)} of them on the universal kernel, whose cells are the layout cases, and the distance kernels, which the matrix "
+          f"does not model; {len(left & mc)} of {len(mc)} planner refusals)")
+    univ = {q for q in need if q[1] in ("univ", "univ-dict")}
+    assert len(univ) == 36 and len(univ & left) == 23  # (10 cells = 10 (F, V) pairs and 3 shapes; the rest by the two entries)
     # no case covers an UNREACHED coordinate: an entry that a case reaches must be deleted
     assert all(dm.unreached(q) is None for q in set().union(*cover)), "an UNREACHED entry is covered by a case"
     cover_count = collections.Counter(q for c in cover for q in c)
     sole = [i for i, c in enumerate(cover) if any(cover_count[q] == 1 for q in c)]
     assert len(sole) > len(targets) // 2  # (the matrix is a greedy cover: most cases are the only one on a coordinate)
     for i in sole:  # the rule on a copy of the cases without case i
-        assert uncovered(cover[:i] + cover[i + 1:]), dm.CASES[i].id
+        assert uncovered(cover[:i] + cover[i + 1:]), names[i]
 
 
 F = dm.Facts
@@ -167,8 +174,35 @@ def test_families_without_a_launcher_are_refused_not_guessed():
         dm.predict("lean nslot=2 mm=2 field=0 lds=9000", F(TABLE, bias=True, replay=True))
     with pytest.raises(dm.NoLeanLauncher):  # K_MULTI_WL_KF takes no windows
         dm.predict("lean-multi nslot=2 mm=2 field=0 lds=9000 kf=1 wl=multi wl_windows=1", F(SWAP, wl=True))
-    with pytest.raises(dm.NoLeanLauncher):
+    with pytest.raises(dm.NoLeanLauncher):  # (a text without the selector words is not guessed at)
         dm.predict("universal occ=lds field=0 lds=27392 (TableFlip outside the lean families)", F(TABLE))
+
+
+UNIV = "void mc_univ_kernel<%s>(UParams, int)"
+# smolmc_univ_selector's bits as kernel_info prints them -> mc_univ_kernel<OCC_LDS, K1, TABLE, WPS, DICT> (univ_select)
+UNIV_EXPECTED = [
+    ("universal occ=lds field=0 lds=27392 wpb=4 dshift=3 dict=1 k1=1 table=1 dense=0 (TableFlip outside the lean families)",
+     UNIV % "true, true, true, 2, true"),
+    ("universal occ=hbm field=2 lds=13312 wpb=4 dshift=2 dict=0 k1=0 table=0 dense=1 (more than 64 features) env=SMOLMC_UNIV_OCC_HBM",
+     UNIV % "false, false, false, 4, false"),
+    ("universal occ=lds field=0 lds=768 wpb=4 dcells=0 dict=0 k1=0 table=0 dense=0 (environment override) env=SMOLMC_FORCE_UNIVERSAL",
+     UNIV % "true, false, false, 2, false"),
+    ("universal occ=lds field=0 lds=160800 wpb=1 dshift=3 dict=0 k1=1 table=0 dense=0 (occupancy does not fit LDS)",
+     UNIV % "true, true, false, 2, false"),
+]
+
+
+@pytest.mark.parametrize("k", range(len(UNIV_EXPECTED)))
+def test_predict_the_universal_kernel_from_its_words(k, symbols):
+    info, want = UNIV_EXPECTED[k]
+    symbol, key, variants = dm.trace(info, F(SWAP))
+    assert symbol == want and want in symbols and not dm.falls_through(key, variants)
+
+
+def test_every_universal_instantiation_is_predicted_by_its_words(symbols):
+    reached = {dm.predict(f"universal occ={occ} field=0 lds=1 wpb=4 dshift=0 dict={dl} k1={k1} table={tb} dense={dn} (x)", F(SWAP))
+               for occ, dl, k1, tb, dn in itertools.product(("lds", "hbm"), *[(0, 1)] * 4)}
+    assert reached == {s for s in symbols if dm.template_of(s) == "mc_univ_kernel"} and len(reached) == 32
 
 
 def test_no_plausible_handle_reaches_an_else_or_leaves_the_library(symbols):

@@ -43,7 +43,7 @@ def do_list(args):
     for t in list(dm.MC_TEMPLATES) + ["(helpers)"]:
         print(f"{t:24s}" + "".join(f"{table[(t, c)]:24d}" for c in classes))
     need = dm.required(symbols)
-    left = need - dm.covered_by(dm.TARGETS.values(), symbols)
+    left = need - dm.covered_by(list(dm.TARGETS.values()) + list(dm.UNIV_TARGETS.values()), symbols)  # (+ the universal kernel's layout cases)
     print(f"\nrequired coordinates {len(need)}: covered {len(need) - len(left)}, unreached {len(left)}")
     for why, qs in sorted(collections.Counter(dm.unreached(q) or "NOT CLASSIFIED" for q in left).items(), key=lambda x: -x[1]):
         print(f"  {qs:4d}  {why[:150]}")
