@@ -413,6 +413,36 @@ class Connectivity:
                         n_gated_rows=[int((g.gates >= 0).any(axis=1).sum()) for g in self.graphs])
         return meta
 
+    @staticmethod
+    def metadata_to_npz(conn):
+        """The meta/* arrays of an .npz for the dict of ``to_metadata``: the ragged lists as values and offsets."""
+        members = conn["members"]
+        out = {"meta/conn_shape": np.asarray([conn["n_graphs"], conn["n_kinds"]], dtype=np.int64),
+               "meta/conn_n_bonds": np.asarray(conn["n_bonds"], dtype=np.int64),
+               "meta/conn_member_ptr": np.cumsum([0] + [len(m) for m in members]).astype(np.int64),
+               "meta/conn_members": np.asarray([k for m in members for k in m], dtype=np.int32)}
+        if "gate_kinds" in conn:  # a gated spec: the kinds that do not block, max_blocked and the gated rows per graph
+            kinds = conn["gate_kinds"]
+            out.update({"meta/conn_gate_kind_ptr": np.cumsum([0] + [len(m) for m in kinds]).astype(np.int64),
+                        "meta/conn_gate_kinds": np.asarray([k for m in kinds for k in m], dtype=np.int32),
+                        "meta/conn_max_blocked": np.asarray(conn["max_blocked"], dtype=np.int64),
+                        "meta/conn_n_gated_rows": np.asarray(conn["n_gated_rows"], dtype=np.int64)})
+        return out
+
+    @staticmethod
+    def metadata_from_npz(d):
+        """The dict of ``to_metadata`` from the arrays of ``metadata_to_npz``, None when ``d`` holds none."""
+        if "meta/conn_shape" not in d.files:
+            return None
+        ptr, flat = d["meta/conn_member_ptr"], d["meta/conn_members"].tolist()
+        meta = dict(n_graphs=int(d["meta/conn_shape"][0]), n_kinds=int(d["meta/conn_shape"][1]),
+                    members=[flat[int(a):int(b)] for a, b in zip(ptr[:-1], ptr[1:])], n_bonds=d["meta/conn_n_bonds"].tolist())
+        if "meta/conn_gate_kinds" in d.files:
+            ptr, flat = d["meta/conn_gate_kind_ptr"], d["meta/conn_gate_kinds"].tolist()
+            meta.update(gate_kinds=[flat[int(a):int(b)] for a, b in zip(ptr[:-1], ptr[1:])],
+                        max_blocked=d["meta/conn_max_blocked"].tolist(), n_gated_rows=d["meta/conn_n_gated_rows"].tolist())
+        return meta
+
 
 # ---- geometry -----------------------------------------------------------------------------------------------------------
 def geometric_bonds(sc, cutoff=None, distances=None):

@@ -13,6 +13,7 @@ import os
 import numpy as np
 
 from . import capi
+from .families import BY_NAME, FAMILIES, trace_shape
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsmolmc_hip.so")
@@ -190,9 +191,9 @@ def species_counts(tables, occupancies, width=None):
 
 # the keywords of ``run_sampled`` / ``run_sampled_async`` and the SMOLMC_SAMPLE_* flag each one sets
 SAMPLE_FLAGS = (("occupancy", capi.SAMPLE_OCCUPANCY), ("bias", capi.SAMPLE_BIAS), ("wl", capi.SAMPLE_WL),
-                ("observables", capi.SAMPLE_OBSERVABLES), ("minima", capi.SAMPLE_MINIMA), ("statistics", capi.SAMPLE_STATISTICS),
-                ("structure", capi.SAMPLE_STRUCTURE), ("connectivity", capi.SAMPLE_CONNECTIVITY),
-                ("patterns", capi.SAMPLE_PATTERNS), ("environments", capi.SAMPLE_ENVIRONMENTS))
+                ("minima", capi.SAMPLE_MINIMA), ("statistics", capi.SAMPLE_STATISTICS)
+                ) + tuple((fam.run_keyword, fam.flag) for fam in FAMILIES)
+_CTYPE = {np.dtype(np.int32): C.c_int32, np.dtype(np.int64): C.c_int64, np.dtype(np.float64): C.c_double}
 
 
 class EngineError(RuntimeError):
@@ -588,37 +589,69 @@ class Engine:
         self._chk(fn(self._h, ms))
         return float(ms[0]) if n == 1 else [float(x) for x in ms]
 
+    # ---- the per-sample families (families.FAMILIES): what their public methods below share ---------------------------
+    def _family_sizes(self, fam):
+        """What ``smolmc_<stem>_shape`` gives, by the names of ``fam.sizes``: zeros when no spec is set."""
+        v = [C.c_int() for _ in fam.sizes]
+        self._chk(getattr(self._lib, f"smolmc_{fam.stem}_shape")(self._h, *[C.byref(x) for x in v]))
+        return {name: int(x.value) for name, x in zip(fam.sizes, v)}
+
+    def _set_family(self, fam, spec):
+        """``smolmc_set_<stem>``; a spec that rests on another family must map that family's kinds in force."""
+        if spec is not None and fam.rests_on is not None:
+            K = self._family_sizes(BY_NAME[fam.rests_on])["n_kinds"]
+            if spec.n_kinds != K:
+                raise ValueError(f"{fam.noun} maps {spec.n_kinds} kinds, the {fam.rests_on} in force have {K} "
+                                 f"(call set_{fam.rests_on} first)")
+        self._set_spec(getattr(self._lib, f"smolmc_set_{fam.stem}"), spec, f"{fam.noun} {fam.verb}")
+
+    @staticmethod
+    def _family_arrays(fam, lead, sizes, make):
+        """One array per trace of ``fam``, ``lead`` + the trace's shape, from ``make`` (np.zeros, np.empty)."""
+        return [make(lead + trace_shape(dims, sizes), dtype=dtype) for _, dtype, dims in fam.traces]
+
+    def _eval_family(self, fam, occupancies, extra=None):
+        """``smolmc_eval_<stem>`` on occupancies (n, N), or on the walkers' current states: the traces of ``fam`` as a list
+        of arrays (n, ...).  Where the call takes one more pointer, ``extra(n, sizes)`` gives its int32 array, or None for
+        NULL; it is the last entry of the list."""
+        sizes = self._family_sizes(fam)
+        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
+        n = self.R if occ is None else len(occ)
+        out = self._family_arrays(fam, (n,), sizes, np.zeros)
+        more = [] if extra is None else [extra(n, sizes)]
+        self._chk(getattr(self._lib, f"smolmc_eval_{fam.stem}")(
+            self._h, _p(occ, C.c_int32), n, *[_p(a, _CTYPE[a.dtype]) for a in out], *[_p(a, C.c_int32) for a in more]))
+        return out + more
+
+    def _sample_family(self, fam):
+        """``smolmc_get_sample_<stem>``: the traces of ``fam``, (ns, R, ...) each, of the block ``fetch_samples`` would
+        deliver next."""
+        sizes = self._family_sizes(fam)
+        _, ns, _ = self.pending_samples()
+        out = self._family_arrays(fam, (ns, self.R), sizes, np.empty)
+        self._chk(getattr(self._lib, f"smolmc_get_sample_{fam.stem}")(self._h, *[_p(a, _CTYPE[a.dtype]) for a in out]))
+        return out
+
     # ---- observables: kind and pair counts on the device ----------------------------------
     def set_observables(self, obs):
         """The observables of this handle (smolmc_set_observables): an ``observables.Observables`` in the caller's site
         numbering, or None to remove them.  The engine copies and uploads; it refuses, naming the reason, a bond out
         of range, a kind beyond ``n_kinds``, more cells than ``capi.MAX_OBS_CELLS`` and a row too long for LDS."""
-        self._set_spec(self._lib.smolmc_set_observables, obs, "the observables are")
+        self._set_family(BY_NAME["observables"], obs)
 
     def observables_shape(self):
         """(n_kinds, n_shells) in force, (0, 0) when none are set (smolmc_observables_shape)."""
-        K, S = C.c_int(), C.c_int()
-        self._chk(self._lib.smolmc_observables_shape(self._h, C.byref(K), C.byref(S)))
-        return int(K.value), int(S.value)
+        return tuple(self._family_sizes(BY_NAME["observables"]).values())
 
     def observables(self, occupancies=None):
         """(counts (n, K) int32, pairs (n, n_shells, K, K) int32) of occupancies (n, N) evaluated on the device
         (smolmc_eval_observables), or, with None, of the walkers' current states (n = R)."""
-        K, S = self.observables_shape()
-        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
-        n = self.R if occ is None else len(occ)
-        counts, pairs = np.zeros((n, K), dtype=np.int32), np.zeros((n, S, K, K), dtype=np.int32)
-        self._chk(self._lib.smolmc_eval_observables(self._h, _p(occ, C.c_int32), n, _p(counts, C.c_int32), _p(pairs, C.c_int32)))
-        return counts, pairs
+        return tuple(self._eval_family(BY_NAME["observables"], occupancies))
 
     def sample_observables(self):
         """(species_counts (ns, R, K), pair_counts (ns, R, n_shells, K, K)) of the block ``fetch_samples`` would
         deliver next; the block stays undelivered (smolmc_get_sample_observables)."""
-        K, S = self.observables_shape()
-        _, ns, _ = self.pending_samples()
-        counts, pairs = np.empty((ns, self.R, K), dtype=np.int32), np.empty((ns, self.R, S, K, K), dtype=np.int32)
-        self._chk(self._lib.smolmc_get_sample_observables(self._h, _p(counts, C.c_int32), _p(pairs, C.c_int32)))
-        return counts, pairs
+        return tuple(self._sample_family(BY_NAME["observables"]))
 
     def observables_kernel_ms(self):
         """Device time of the last launch of the observables kernel in ms (HIP events; a measuring hook of the library,
@@ -678,32 +711,21 @@ class Engine:
         site numbering, or None to remove it.  The engine copies and uploads; it refuses, naming the reason, a phase or
         kind out of range, sizes beyond the ``capi.MAX_STRUCT_*`` limits, a table large enough to overflow an amplitude,
         and a row too long for LDS."""
-        self._set_spec(self._lib.smolmc_set_structure, sf, "the structure factors are")
+        self._set_family(BY_NAME["structure"], sf)
 
     def structure_shape(self):
         """(n_points, n_kinds, n_intensities) in force, zeros when no spec is set (smolmc_structure_shape)."""
-        v = [C.c_int() for _ in range(3)]
-        self._chk(self._lib.smolmc_structure_shape(self._h, *[C.byref(x) for x in v]))
-        return tuple(int(x.value) for x in v)
+        return tuple(self._family_sizes(BY_NAME["structure"]).values())
 
     def structure_factor(self, occupancies=None):
         """(amp (n, Q, K, 2) int64, inten (n, I) float64) of occupancies (n, N) evaluated on the device
         (smolmc_eval_structure), or, with None, of the walkers' current states (n = R)."""
-        Q, K, I = self.structure_shape()
-        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
-        n = self.R if occ is None else len(occ)
-        amp, inten = np.zeros((n, Q, K, 2), dtype=np.int64), np.zeros((n, I), dtype=np.float64)
-        self._chk(self._lib.smolmc_eval_structure(self._h, _p(occ, C.c_int32), n, _p(amp, C.c_int64), _p(inten, C.c_double)))
-        return amp, inten
+        return tuple(self._eval_family(BY_NAME["structure"], occupancies))
 
     def sample_structure(self):
         """(structure_amplitudes (ns, R, Q, K, 2), structure_intensities (ns, R, I)) of the block ``fetch_samples`` would
         deliver next; the block stays undelivered (smolmc_get_sample_structure)."""
-        Q, K, I = self.structure_shape()
-        _, ns, _ = self.pending_samples()
-        amp, inten = np.empty((ns, self.R, Q, K, 2), dtype=np.int64), np.empty((ns, self.R, I), dtype=np.float64)
-        self._chk(self._lib.smolmc_get_sample_structure(self._h, _p(amp, C.c_int64), _p(inten, C.c_double)))
-        return amp, inten
+        return tuple(self._sample_family(BY_NAME["structure"]))
 
     def structure_kernel_ms(self):
         """Device time of the last launch of the structure kernel in ms (HIP events; a measuring hook of the library,
@@ -719,7 +741,7 @@ class Engine:
         and a gated row whose open bits do not fit."""
         gates = None if spec is None else spec.c_gates()
         if gates is None:
-            self._set_spec(self._lib.smolmc_set_connectivity, spec, "the connectivity spec is")
+            self._set_family(BY_NAME["connectivity"], spec)
             return
         if spec.num_sites != self.N:
             raise ValueError(f"the connectivity spec is defined on {spec.num_sites} sites, the handle has {self.N}")
@@ -737,29 +759,20 @@ class Engine:
 
     def connectivity_shape(self):
         """(n_graphs, n_kinds) in force, zeros when no spec is set (smolmc_connectivity_shape)."""
-        v = [C.c_int() for _ in range(2)]
-        self._chk(self._lib.smolmc_connectivity_shape(self._h, *[C.byref(x) for x in v]))
-        return tuple(int(x.value) for x in v)
+        return tuple(self._family_sizes(BY_NAME["connectivity"]).values())
 
     def connectivity(self, occupancies=None, labels=False):
         """stats (n, G, 24) int64 of occupancies (n, N) evaluated on the device (smolmc_eval_connectivity), or, with None,
         of the walkers' current states (n = R); with ``labels`` the pair (stats, labels (n, G, N) int32)."""
-        G, _ = self.connectivity_shape()
-        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
-        n = self.R if occ is None else len(occ)
-        stats = np.zeros((n, G, capi.CONN_STATS), dtype=np.int64)
-        lab = np.full((n, G, self.N), -1, dtype=np.int32) if labels else None
-        self._chk(self._lib.smolmc_eval_connectivity(self._h, _p(occ, C.c_int32), n, _p(stats, C.c_int64), _p(lab, C.c_int32)))
+        stats, lab = self._eval_family(
+            BY_NAME["connectivity"], occupancies,
+            lambda n, sizes: np.full((n, sizes["n_graphs"], self.N), -1, dtype=np.int32) if labels else None)
         return (stats, lab) if labels else stats
 
     def sample_connectivity(self):
         """connectivity (ns, R, G, 24) of the block ``fetch_samples`` would deliver next; the block stays undelivered
         (smolmc_get_sample_connectivity)."""
-        G, _ = self.connectivity_shape()
-        _, ns, _ = self.pending_samples()
-        stats = np.empty((ns, self.R, G, capi.CONN_STATS), dtype=np.int64)
-        self._chk(self._lib.smolmc_get_sample_connectivity(self._h, _p(stats, C.c_int64)))
-        return stats
+        return self._sample_family(BY_NAME["connectivity"])[0]
 
     def connectivity_kernel_ms(self):
         """Device time of the last launch of the connectivity kernel in ms (HIP events; a measuring hook of the library,
@@ -781,35 +794,21 @@ class Engine:
         or None to remove it.  It rests on the observables in force, whose kinds its class maps index.  The engine copies
         and uploads; it refuses, naming the reason, a handle without observables, a site or class out of range, more
         cells than ``capi.MAX_PATTERN_CELLS`` and a launch that does not fit LDS."""
-        if spec is not None and spec.n_kinds != self.observables_shape()[0]:
-            raise ValueError(f"the pattern spec maps {spec.n_kinds} kinds, the observables in force have "
-                             f"{self.observables_shape()[0]} (call set_observables first)")
-        self._set_spec(self._lib.smolmc_set_patterns, spec, "the pattern spec is")
+        self._set_family(BY_NAME["patterns"], spec)
 
     def patterns_shape(self):
         """(n_sets, n_cells) in force, zeros when no spec is set (smolmc_patterns_shape)."""
-        v = [C.c_int() for _ in range(2)]
-        self._chk(self._lib.smolmc_patterns_shape(self._h, *[C.byref(x) for x in v]))
-        return tuple(int(x.value) for x in v)
+        return tuple(self._family_sizes(BY_NAME["patterns"]).values())
 
     def patterns(self, occupancies=None):
         """cells (n, n_cells) int32 of occupancies (n, N) evaluated on the device (smolmc_eval_patterns), or, with None, of
         the walkers' current states (n = R)."""
-        _, nc = self.patterns_shape()
-        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
-        n = self.R if occ is None else len(occ)
-        cells = np.zeros((n, nc), dtype=np.int32)
-        self._chk(self._lib.smolmc_eval_patterns(self._h, _p(occ, C.c_int32), n, _p(cells, C.c_int32)))
-        return cells
+        return self._eval_family(BY_NAME["patterns"], occupancies)[0]
 
     def sample_patterns(self):
         """pattern_counts (ns, R, n_cells) of the block ``fetch_samples`` would deliver next; the block stays undelivered
         (smolmc_get_sample_patterns)."""
-        _, nc = self.patterns_shape()
-        _, ns, _ = self.pending_samples()
-        cells = np.empty((ns, self.R, nc), dtype=np.int32)
-        self._chk(self._lib.smolmc_get_sample_patterns(self._h, _p(cells, C.c_int32)))
-        return cells
+        return self._sample_family(BY_NAME["patterns"])[0]
 
     # ---- environments: coordination environments, counted by the observables' kernel ---------
     def set_environments(self, spec):
@@ -817,45 +816,33 @@ class Engine:
         site numbering, or None to remove it.  It rests on the observables in force, whose kinds its class maps index.
         The engine copies and uploads; it refuses, naming the reason, a handle without observables, a site or class out of
         range, more cells than ``capi.MAX_ENV_CELLS`` and a launch that does not fit LDS."""
-        if spec is not None and spec.n_kinds != self.observables_shape()[0]:
-            raise ValueError(f"the environment spec maps {spec.n_kinds} kinds, the observables in force have "
-                             f"{self.observables_shape()[0]} (call set_observables first)")
-        self._set_spec(self._lib.smolmc_set_environments, spec, "the environment spec is")
+        self._set_family(BY_NAME["environments"], spec)
 
     def environments_shape(self):
         """(n_sets, n_cells, n_centres) in force, zeros when no spec is set (smolmc_environments_shape)."""
-        v = [C.c_int() for _ in range(3)]
-        self._chk(self._lib.smolmc_environments_shape(self._h, *[C.byref(x) for x in v]))
-        return tuple(int(x.value) for x in v)
+        return tuple(self._family_sizes(BY_NAME["environments"]).values())
 
     def environments(self, occupancies=None, codes=False):
         """cells (n, n_cells) int32 of occupancies (n, N) evaluated on the device (smolmc_eval_environments), or, with
         None, of the walkers' current states (n = R).  ``codes``: (cells, codes (n, n_centres) int32), the set-local code
         of every centre or -1 for a skipped one."""
-        _, nc, ncen = self.environments_shape()
-        occ = None if occupancies is None else self._occ32(occupancies, (-1, self.N))
-        n = self.R if occ is None else len(occ)
-        cells = np.zeros((n, nc), dtype=np.int32)
-        out = np.zeros((n, ncen), dtype=np.int32) if codes else None
-        self._chk(self._lib.smolmc_eval_environments(self._h, _p(occ, C.c_int32), n, _p(cells, C.c_int32), _p(out, C.c_int32)))
+        cells, out = self._eval_family(
+            BY_NAME["environments"], occupancies,
+            lambda n, sizes: np.zeros((n, sizes["n_centres"]), dtype=np.int32) if codes else None)
         return (cells, out) if codes else cells
 
     def sample_environments(self):
         """environment_counts (ns, R, n_cells) of the block ``fetch_samples`` would deliver next; the block stays
         undelivered (smolmc_get_sample_environments)."""
-        _, nc, _ = self.environments_shape()
-        _, ns, _ = self.pending_samples()
-        cells = np.empty((ns, self.R, nc), dtype=np.int32)
-        self._chk(self._lib.smolmc_get_sample_environments(self._h, _p(cells, C.c_int32)))
-        return cells
+        return self._sample_family(BY_NAME["environments"])[0]
 
     # ---- statistics: running moments, blocking sums and a histogram, kept on the device -----
     def set_statistics(self, spec):
         """The statistics record of this handle (smolmc_set_statistics): a ``statistics.Statistics``, or None to remove
         it.  A new spec starts an empty record.  The record lives as long as the handle: ``set_state`` and
         ``discard_samples`` leave it alone."""
-        shape = () if spec is None else (self.F, self.observables_shape()[0], self.structure_shape()[2], self.connectivity_shape()[0],
-                                             self.patterns_shape()[1], self.environments_shape()[1])
+        # (what ``statistics.segments`` takes: F, then every family's size in force, in the table's order)
+        shape = () if spec is None else (self.F,) + tuple(self._family_sizes(fam)[fam.stat[2]] for fam in FAMILIES)
         self._set_spec(self._lib.smolmc_set_statistics, spec, None, *shape)
         self.statistics_spec = spec
 
@@ -904,9 +891,8 @@ class Engine:
         [, pattern_counts (ns,R,n_cells) int32][, environment_counts (ns,R,n_cells) int32]).
         Occupancies come back as int32 (the reference's trace dtype) or, with ``packed``, as the ring's own
         uint8 -- a quarter of the transfer.  = ``run_sampled_async`` + ``fetch_samples``."""
-        self.run_sampled_async(nsamples, thin_by, occupancy=occupancy, bias=bias, wl=wl, observables=observables,
-                               minima=minima, statistics=statistics, structure=structure, connectivity=connectivity,
-                               patterns=patterns, environments=environments)
+        asked = locals()  # (the keywords as given: SAMPLE_FLAGS names them)
+        self.run_sampled_async(nsamples, thin_by, **{keyword: asked[keyword] for keyword, _ in SAMPLE_FLAGS})
         return self.fetch_samples(packed=packed)
 
     def run_sampled_async(self, nsamples, thin_by, occupancy=True, bias=False, wl=False, observables=False, minima=False,
@@ -922,9 +908,7 @@ class Engine:
         ``connectivity``: the stats of ``set_connectivity`` for every row, likewise.  ``patterns``: the cells of
         ``set_patterns`` for every row, counted by the launch that counts the observables.  ``environments``: the cells of
         ``set_environments`` for every row, by the same launch."""
-        asked = dict(occupancy=occupancy, bias=bias, wl=wl, observables=observables, minima=minima, statistics=statistics,
-                     structure=structure, connectivity=connectivity, patterns=patterns,
-                     environments=environments)
+        asked = locals()  # (the keywords as given: SAMPLE_FLAGS names them)
         flags = sum(flag for keyword, flag in SAMPLE_FLAGS if asked[keyword])
         self._chk(self._lib.smolmc_run_sampled(self._h, int(nsamples), int(thin_by), flags))
 
@@ -950,16 +934,9 @@ class Engine:
         acc = np.empty((ns, self.R), dtype=np.uint8)
         with_occ = bool(flags & capi.SAMPLE_OCCUPANCY)
         extra, obs = {}, {}
-        if flags & capi.SAMPLE_OBSERVABLES:  # (read before the fetch marks the block delivered)
-            obs["species_counts"], obs["pair_counts"] = self.sample_observables()
-        if flags & capi.SAMPLE_STRUCTURE:
-            obs["structure_amplitudes"], obs["structure_intensities"] = self.sample_structure()
-        if flags & capi.SAMPLE_CONNECTIVITY:
-            obs["connectivity"] = self.sample_connectivity()
-        if flags & capi.SAMPLE_PATTERNS:
-            obs["pattern_counts"] = self.sample_patterns()
-        if flags & capi.SAMPLE_ENVIRONMENTS:
-            obs["environment_counts"] = self.sample_environments()
+        for fam in FAMILIES:
+            if flags & fam.flag:  # (read before the fetch marks the block delivered)
+                obs.update(zip((name for name, _, _ in fam.traces), self._sample_family(fam)))
         if flags & capi.SAMPLE_BIAS:
             extra["bias"] = np.empty((ns, self.R))
         if flags & capi.SAMPLE_WL:

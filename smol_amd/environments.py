@@ -254,6 +254,26 @@ class Environments:
                     cell_ptr=self.cell_ptr.tolist(), centre_class_of_kind=[st.centre_class_of_kind.tolist() for st in self.sets],
                     neigh_class_of_kind=[st.neigh_class_of_kind.tolist() for st in self.sets])
 
+    @staticmethod
+    def metadata_to_npz(env):
+        """The meta/* arrays of an .npz for the dict of ``describe``."""
+        return {"meta/env_shape": np.asarray([env["width"], env["n_centre_classes"], env["n_neigh_classes"], env["n_centres"]],
+                                             dtype=np.int64),
+                "meta/env_cell_ptr": np.asarray(env["cell_ptr"], dtype=np.int64),
+                "meta/env_centre_class_of_kind": np.asarray(env["centre_class_of_kind"], dtype=np.int32),
+                "meta/env_neigh_class_of_kind": np.asarray(env["neigh_class_of_kind"], dtype=np.int32)}
+
+    @staticmethod
+    def metadata_from_npz(d):
+        """The dict of ``describe`` from the arrays of ``metadata_to_npz``, None when ``d`` holds none."""
+        if "meta/env_shape" not in d.files:
+            return None
+        width, na, nb, ncen = (d["meta/env_shape"][i].tolist() for i in range(4))
+        ptr = d["meta/env_cell_ptr"].tolist()
+        return dict(n_sets=len(width), n_cells=int(ptr[-1]), width=width, n_centre_classes=na, n_neigh_classes=nb,
+                    n_centres=ncen, cell_ptr=ptr, centre_class_of_kind=d["meta/env_centre_class_of_kind"].tolist(),
+                    neigh_class_of_kind=d["meta/env_neigh_class_of_kind"].tolist())
+
     # ---- derived quantities (host) ---------------------------------------------------------------------------------
     def distribution(self, cells, e):
         """The cells of set ``e`` as an array (..., A, z + 1, ..., z + 1): the centre class, then one axis per neighbour

@@ -35,6 +35,7 @@ import numpy as np
 
 from . import capi
 from .engine import Engine
+from .families import BY_NAME, FAMILIES, trace_shape
 
 kB = 8.617333262145e-5  # smol/constants.py:4
 
@@ -1606,37 +1607,10 @@ class SampleContainer:
                           "meta/pop_anneal_rho_t": np.asarray(pop["rho_t"], dtype=np.float64)})
             if "overlap" in pop:  # an adaptive schedule: the target and the overlap of every step and population
                 extra["meta/pop_anneal_overlap"] = np.asarray(pop["overlap"], dtype=np.float64).reshape(len(pop["overlap"]), -1)
-        obs = self.metadata.get("observables")
-        if obs is not None:  # the kinds of the species_counts / pair_counts traces
-            extra.update({"meta/obs_kind_base": np.asarray(obs["kind_base"], dtype=np.int32),
-                          "meta/obs_site_ncodes": np.asarray(obs["site_ncodes"], dtype=np.int32),
-                          "meta/obs_shape": np.asarray([obs["n_kinds"], obs["n_shells"], int(obs["default_kinds"])], dtype=np.int64)})
-        conn = self.metadata.get("connectivity")
-        if conn is not None:  # the graphs of the connectivity trace: member kinds and bond counts
-            members = conn["members"]
-            extra.update({"meta/conn_shape": np.asarray([conn["n_graphs"], conn["n_kinds"]], dtype=np.int64),
-                          "meta/conn_n_bonds": np.asarray(conn["n_bonds"], dtype=np.int64),
-                          "meta/conn_member_ptr": np.cumsum([0] + [len(m) for m in members]).astype(np.int64),
-                          "meta/conn_members": np.asarray([k for m in members for k in m], dtype=np.int32)})
-            if "gate_kinds" in conn:  # a gated spec: the kinds that do not block, max_blocked and the gated rows per graph
-                kinds = conn["gate_kinds"]
-                extra.update({"meta/conn_gate_kind_ptr": np.cumsum([0] + [len(m) for m in kinds]).astype(np.int64),
-                              "meta/conn_gate_kinds": np.asarray([k for m in kinds for k in m], dtype=np.int32),
-                              "meta/conn_max_blocked": np.asarray(conn["max_blocked"], dtype=np.int64),
-                              "meta/conn_n_gated_rows": np.asarray(conn["n_gated_rows"], dtype=np.int64)})
-        pat = self.metadata.get("patterns")
-        if pat is not None:  # the sets of the pattern_counts trace: their shapes and class maps
-            extra.update({"meta/pat_shape": np.asarray([pat["arity"], pat["n_classes"], pat["n_tuples"]], dtype=np.int64),
-                          "meta/pat_cell_ptr": np.asarray(pat["cell_ptr"], dtype=np.int64),
-                          "meta/pat_class_of_kind": np.asarray(pat["class_of_kind"], dtype=np.int32),
-                          "meta/pat_orbit_ids": np.asarray(pat["set_orbit_ids"] if pat["set_orbit_ids"] is not None else [], dtype=np.int64)})
-        env = self.metadata.get("environments")
-        if env is not None:  # the sets of the environment_counts trace: their shapes and class maps
-            extra.update({"meta/env_shape": np.asarray([env["width"], env["n_centre_classes"], env["n_neigh_classes"], env["n_centres"]],
-                                                       dtype=np.int64),
-                          "meta/env_cell_ptr": np.asarray(env["cell_ptr"], dtype=np.int64),
-                          "meta/env_centre_class_of_kind": np.asarray(env["centre_class_of_kind"], dtype=np.int32),
-                          "meta/env_neigh_class_of_kind": np.asarray(env["neigh_class_of_kind"], dtype=np.int32)})
+        for fam in FAMILIES:  # what the specs of the derived traces said of themselves
+            meta = self.metadata.get(fam.keyword)
+            if meta is not None and fam.saved:
+                extra.update(fam.spec.metadata_to_npz(meta))
         rec = self.minima
         if rec is not None:  # the minima record: its arrays, the spec and the two counters
             spec = rec.spec
@@ -1756,34 +1730,10 @@ class SampleContainer:
                                               temperatures=d["meta/state_point_temperatures"].tolist(),
                                               chemical_potentials=d["meta/state_point_values"].tolist(),
                                               shape=[int(x) for x in d["meta/state_point_shape"]])
-        if "meta/obs_kind_base" in d.files:
-            K, S, default = (int(x) for x in d["meta/obs_shape"])
-            c.metadata["observables"] = dict(n_kinds=K, n_shells=S, default_kinds=bool(default),
-                                             kind_base=d["meta/obs_kind_base"].tolist(),
-                                             site_ncodes=d["meta/obs_site_ncodes"].tolist())
-        if "meta/conn_shape" in d.files:
-            ptr, flat = d["meta/conn_member_ptr"], d["meta/conn_members"].tolist()
-            c.metadata["connectivity"] = dict(n_graphs=int(d["meta/conn_shape"][0]), n_kinds=int(d["meta/conn_shape"][1]),
-                                              members=[flat[int(a):int(b)] for a, b in zip(ptr[:-1], ptr[1:])],
-                                              n_bonds=d["meta/conn_n_bonds"].tolist())
-            if "meta/conn_gate_kinds" in d.files:
-                ptr, flat = d["meta/conn_gate_kind_ptr"], d["meta/conn_gate_kinds"].tolist()
-                c.metadata["connectivity"].update(gate_kinds=[flat[int(a):int(b)] for a, b in zip(ptr[:-1], ptr[1:])],
-                                                  max_blocked=d["meta/conn_max_blocked"].tolist(),
-                                                  n_gated_rows=d["meta/conn_n_gated_rows"].tolist())
-        if "meta/pat_shape" in d.files:
-            arity, ncls, ntup = (d["meta/pat_shape"][i].tolist() for i in range(3))
-            ptr, ids = d["meta/pat_cell_ptr"].tolist(), d["meta/pat_orbit_ids"].tolist()
-            c.metadata["patterns"] = dict(n_sets=len(arity), n_cells=int(ptr[-1]), arity=arity, n_classes=ncls, n_tuples=ntup,
-                                          cell_ptr=ptr, class_of_kind=d["meta/pat_class_of_kind"].tolist(),
-                                          set_orbit_ids=ids if ids else None)
-        if "meta/env_shape" in d.files:
-            width, na, nb, ncen = (d["meta/env_shape"][i].tolist() for i in range(4))
-            ptr = d["meta/env_cell_ptr"].tolist()
-            c.metadata["environments"] = dict(n_sets=len(width), n_cells=int(ptr[-1]), width=width, n_centre_classes=na,
-                                              n_neigh_classes=nb, n_centres=ncen, cell_ptr=ptr,
-                                              centre_class_of_kind=d["meta/env_centre_class_of_kind"].tolist(),
-                                              neigh_class_of_kind=d["meta/env_neigh_class_of_kind"].tolist())
+        for fam in FAMILIES:
+            meta = fam.spec.metadata_from_npz(d) if fam.saved else None
+            if meta is not None:
+                c.metadata[fam.keyword] = meta
         if "meta/minima_shape" in d.files:
             offers, nw, n_weights, n_axes = (int(x) for x in d["meta/minima_shape"])
             rec = {f: d[f"meta/minima_{f}"] for f in ("value", "enthalpy", "features", "occupancy", "counts", "walker", "sample", "step")}
@@ -1928,14 +1878,10 @@ class Sampler:
         self._walker_mu_dirty = False  # ... not yet on the engine
         self._wl_windows = None     # replica-exchange Wang-Landau: the parallel.WLWindows of this sampler's walkers
         self._wl_synchronise = False  # ... whose copies are merged between launches: the handle has check period 0
-        self._observables = None    # observables.Observables counted on the device for every sample, or None
+        self._traced = {}           # family name (families.FAMILIES) -> the spec evaluated on the device for every sample
         self._minima = None         # minima.Minima: the lowest samples are kept on the device, or None
         self._minima_offers = 0     # samples offered to the record since it was last emptied
         self._statistics = None     # statistics.Statistics: moments, blocking sums and a histogram kept on the device, or None
-        self._structure = None      # structure.StructureFactor evaluated on the device for every sample, or None
-        self._connectivity = None   # connectivity.Connectivity evaluated on the device for every sample, or None
-        self._patterns = None       # patterns.Patterns counted on the device for every sample, or None
-        self._environments = None   # environments.Environments counted on the device for every sample, or None
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
@@ -1981,20 +1927,15 @@ class Sampler:
         stay on the device.  A sampler sharded across ranks is out of scope: every rank traces its own walkers."""
         from . import parallel
 
-        if windows is not None and observables is not None:
-            raise ValueError("observables= with windows=: the samples of per-walker windows do not come from the sample ring")
-        if windows is not None and structure_factor is not None:
-            raise ValueError("structure_factor= with windows=: the samples of per-walker windows do not come from the sample ring")
-        if windows is not None and connectivity is not None:
-            raise ValueError("connectivity= with windows=: the samples of per-walker windows do not come from the sample ring")
-        if windows is not None and patterns is not None:
-            raise ValueError("patterns= with windows=: the samples of per-walker windows do not come from the sample ring")
-        if windows is not None and environments is not None:
-            raise ValueError("environments= with windows=: the samples of per-walker windows do not come from the sample ring")
-        if environments is not None and observables is None:
-            raise ValueError("environments= needs observables=: the class maps of an environment spec index the kinds of the observables")
-        if patterns is not None and observables is None:
-            raise ValueError("patterns= needs observables=: the class maps of a pattern spec index the kinds of the observables")
+        given = locals()  # (the family keywords as given: the table names them)
+        traced = {fam: given[fam.keyword] for fam in FAMILIES if given[fam.keyword] is not None}
+        if windows is not None and traced:
+            raise ValueError(f"{next(iter(traced)).keyword}= with windows=: the samples of per-walker windows do not come from the "
+                             "sample ring")
+        for fam in traced:
+            if fam.rests_on is not None and BY_NAME[fam.rests_on] not in traced:
+                raise ValueError(f"{fam.keyword}= needs {BY_NAME[fam.rests_on].keyword}=: the class maps of {fam.a_spec} index the "
+                                 f"kinds of the {fam.rests_on}")
         if synchronise and windows is None:
             raise ValueError("synchronise=True needs windows=: the copies of a window are what is merged "
                              "(parallel.WLWindows(n_windows=1, copies=nwalkers) for plain multi-walker Wang-Landau)")
@@ -2031,16 +1972,8 @@ class Sampler:
         sampler = cls(kernels, container, walker_range=(first, count), device=device, world_size=world_size)
         if chemical_potentials is not None:
             sampler.set_chemical_potentials(chemical_potentials)
-        if observables is not None:
-            sampler._set_observables(observables)
-        if structure_factor is not None:
-            sampler._set_structure_factor(structure_factor)
-        if connectivity is not None:
-            sampler._set_connectivity(connectivity)
-        if patterns is not None:
-            sampler._set_patterns(patterns)
-        if environments is not None:
-            sampler._set_environments(environments)
+        for fam, spec in traced.items():  # (in the table's order: a family comes after the one it rests on)
+            sampler._set_traced(fam, spec)
         if minima is not None:
             sampler._set_minima(minima)
         if statistics is not None:
@@ -2048,16 +1981,10 @@ class Sampler:
         return sampler
 
     def _set_statistics(self, spec):
-        if spec.count_columns() and self._observables is None:
-            raise ValueError("a statistics record with count columns needs a sampler built with observables=")
-        if spec.intensity_columns() and self._structure is None:
-            raise ValueError("a statistics record with intensity columns needs a sampler built with structure_factor=")
-        if spec.connectivity_columns() and self._connectivity is None:
-            raise ValueError("a statistics record with connectivity columns needs a sampler built with connectivity=")
-        if spec.pattern_columns() and self._patterns is None:
-            raise ValueError("a statistics record with pattern columns needs a sampler built with patterns=")
-        if spec.environment_columns() and self._environments is None:
-            raise ValueError("a statistics record with environment columns needs a sampler built with environments=")
+        for fam in FAMILIES:
+            tag, noun, _ = fam.stat
+            if spec.tagged_columns(tag) and fam.name not in self._traced:
+                raise ValueError(f"a statistics record with {noun} columns needs a sampler built with {fam.keyword}=")
         self._statistics = spec
         if self._engine is not None:
             self._engine.set_statistics(spec)
@@ -2078,7 +2005,7 @@ class Sampler:
         self._get_engine().reset_statistics()
 
     def _set_minima(self, spec):
-        if spec.n_axes and self._observables is None:
+        if spec.n_axes and "observables" not in self._traced:
             raise ValueError("a minima record keyed by composition needs a sampler built with observables=")
         self._minima, self._minima_offers = spec, 0
         if self._engine is not None:
@@ -2115,85 +2042,26 @@ class Sampler:
         self._get_engine().reset_minima()
         self._minima_offers = 0
 
-    def _set_observables(self, obs):
-        """Trace ``obs`` with every sample: the container's schema gains the two traces, its metadata the kinds."""
+    def _set_traced(self, fam, spec):
+        """Trace ``spec`` of the family ``fam`` with every sample: the container's schema gains the family's traces, its
+        metadata what the spec says of itself."""
         nw, N = self.samples.shape
-        if obs.num_sites != N:
-            raise ValueError(f"the observables are defined on {obs.num_sites} sites, the ensemble has {N}")
-        if obs.site_ncodes is None:
+        if spec.num_sites != N:
+            raise ValueError(f"{fam.noun} {fam.verb} defined on {spec.num_sites} sites, the ensemble has {N}")
+        if fam.name == "observables" and spec.site_ncodes is None:
             raise ValueError("observables for a sampler need site_ncodes (Observables.from_supercell gives them)")
+        if fam.rests_on is not None:
+            base = self._traced.get(fam.rests_on)
+            if base is None or spec.n_kinds != base.n_kinds:
+                raise ValueError(f"{fam.noun} must rest on the sampler's {fam.rests_on}: its class maps index their kinds")
         if self.samples.num_samples:
-            raise ValueError("the container holds samples without the observables' traces: clear_samples() first")
-        K, S = obs.n_kinds, obs.n_shells
-        self.samples._schema["species_counts"] = (np.dtype(np.int32), (nw, K))
-        self.samples._schema["pair_counts"] = (np.dtype(np.int32), (nw, S, K, K))
-        self.samples.metadata["observables"] = dict(n_kinds=K, n_shells=S, default_kinds=obs.default_kinds,
-                                                    kind_base=obs.kind_base.tolist(), site_ncodes=obs.site_ncodes.tolist())
-        self._observables = obs
+            raise ValueError(f"the container holds samples without {fam.traces_noun}: clear_samples() first")
+        for name, dtype, dims in fam.traces:
+            self.samples._schema[name] = (np.dtype(dtype), (nw,) + trace_shape(dims, spec))
+        self.samples.metadata[fam.keyword] = getattr(spec, fam.describe)()
+        self._traced[fam.name] = spec
         if self._engine is not None:
-            self._engine.set_observables(obs)
-
-    def _set_structure_factor(self, sf):
-        """Trace ``sf`` with every sample: the container's schema gains the two traces, its metadata their shape."""
-        nw, N = self.samples.shape
-        if sf.num_sites != N:
-            raise ValueError(f"the structure factors are defined on {sf.num_sites} sites, the ensemble has {N}")
-        if self.samples.num_samples:
-            raise ValueError("the container holds samples without the structure factors' traces: clear_samples() first")
-        Q, K, I = sf.n_points, sf.n_kinds, sf.n_intensities
-        self.samples._schema["structure_amplitudes"] = (np.dtype(np.int64), (nw, Q, K, 2))
-        self.samples._schema["structure_intensities"] = (np.dtype(np.float64), (nw, I))
-        self.samples.metadata["structure_factor"] = dict(
-            n_points=Q, n_kinds=K, n_intensities=I, bits=sf.bits, intensities=sf.intensity.tolist(),
-            intensity_scale=sf.intensity_scale.tolist(), points=None if sf.points is None else sf.points.tolist())
-        self._structure = sf
-        if self._engine is not None:
-            self._engine.set_structure_factor(sf)
-
-    def _set_connectivity(self, spec):
-        """Trace ``spec`` with every sample: the container's schema gains the trace, its metadata the spec's shape."""
-        nw, N = self.samples.shape
-        if spec.num_sites != N:
-            raise ValueError(f"the connectivity spec is defined on {spec.num_sites} sites, the ensemble has {N}")
-        if self.samples.num_samples:
-            raise ValueError("the container holds samples without the connectivity trace: clear_samples() first")
-        self.samples._schema["connectivity"] = (np.dtype(np.int64), (nw, spec.n_graphs, 24))
-        self.samples.metadata["connectivity"] = spec.to_metadata()
-        self._connectivity = spec
-        if self._engine is not None:
-            self._engine.set_connectivity(spec)
-
-    def _set_patterns(self, spec):
-        """Trace ``spec`` with every sample: the container's schema gains the trace, its metadata the sets' shapes and
-        class maps."""
-        nw, N = self.samples.shape
-        if spec.num_sites != N:
-            raise ValueError(f"the pattern spec is defined on {spec.num_sites} sites, the ensemble has {N}")
-        if self._observables is None or spec.n_kinds != self._observables.n_kinds:
-            raise ValueError("the pattern spec must rest on the sampler's observables: its class maps index their kinds")
-        if self.samples.num_samples:
-            raise ValueError("the container holds samples without the pattern_counts trace: clear_samples() first")
-        self.samples._schema["pattern_counts"] = (np.dtype(np.int32), (nw, spec.n_cells))
-        self.samples.metadata["patterns"] = spec.describe()
-        self._patterns = spec
-        if self._engine is not None:
-            self._engine.set_patterns(spec)
-
-    def _set_environments(self, spec):
-        """Trace ``spec`` with every sample: the container's schema gains the trace, its metadata the sets' shapes and
-        class maps."""
-        nw, N = self.samples.shape
-        if spec.num_sites != N:
-            raise ValueError(f"the environment spec is defined on {spec.num_sites} sites, the ensemble has {N}")
-        if self._observables is None or spec.n_kinds != self._observables.n_kinds:
-            raise ValueError("the environment spec must rest on the sampler's observables: its class maps index their kinds")
-        if self.samples.num_samples:
-            raise ValueError("the container holds samples without the environment_counts trace: clear_samples() first")
-        self.samples._schema["environment_counts"] = (np.dtype(np.int32), (nw, spec.n_cells))
-        self.samples.metadata["environments"] = spec.describe()
-        self._environments = spec
-        if self._engine is not None:
-            self._engine.set_environments(spec)
+            getattr(self._engine, fam.set)(spec)
 
     @classmethod
     def _from_ensemble_windows(cls, ensemble, wx, *args, step_type=None, kernel_type=None, seeds=None, nwalkers=1, rank=None,
@@ -2396,20 +2264,15 @@ class Sampler:
                 cfg = capi.make_config(len(self._kernels), capi.KERNEL_METROPOLIS,
                                        STEP_TYPES[k0.step_type], self._device)
             self._engine = Engine(tables, cfg, distance=dist)
-            if self._observables is not None:
-                self._engine.set_observables(self._observables)
-            if self._patterns is not None:  # (behind the observables it rests on, before the statistics record)
-                self._engine.set_patterns(self._patterns)
-            if self._environments is not None:
-                self._engine.set_environments(self._environments)
+            # the families in the table's order, a family behind the one it rests on; the two records behind all of them:
+            # their keys and columns name the specs in force
+            for fam in FAMILIES:
+                if fam.name in self._traced:
+                    getattr(self._engine, fam.set)(self._traced[fam.name])
             if self._minima is not None:  # (a new handle starts an empty record)
                 self._engine.set_minima(self._minima)
                 self._minima_offers = 0
-            if self._structure is not None:  # (before the statistics record: its intensity columns name this spec)
-                self._engine.set_structure_factor(self._structure)
-            if self._connectivity is not None:  # (likewise: its connectivity columns name this spec)
-                self._engine.set_connectivity(self._connectivity)
-            if self._statistics is not None:  # (likewise)
+            if self._statistics is not None:
                 self._engine.set_statistics(self._statistics)
             if self._wl_windows is not None:  # (kernel e was built with estimator e's window: cfg holds window 0)
                 self._engine.set_wl_windows(self._wl_windows.vmin, self._wl_windows.vmax)
@@ -2485,16 +2348,11 @@ class Sampler:
             tr.histogram, tr.occurrences, tr.entropy = wl["histogram"], wl["occurrences"], wl["entropy"]
             tr.cumulative_mean_features = wl["mean_features"]
             tr.mod_factor = wl["mod_factor"].reshape(nw, 1)
-        if self._observables is not None:
-            tr.species_counts, tr.pair_counts = eng.observables()
-        if self._structure is not None:
-            tr.structure_amplitudes, tr.structure_intensities = eng.structure_factor()
-        if self._connectivity is not None:
-            tr.connectivity = eng.connectivity()
-        if self._patterns is not None:
-            tr.pattern_counts = eng.patterns()
-        if self._environments is not None:
-            tr.environment_counts = eng.environments()
+        for fam in FAMILIES:
+            if fam.name in self._traced:
+                values = getattr(eng, fam.eval)()
+                for (name, _, _), v in zip(fam.traces, values if isinstance(values, tuple) else (values,)):
+                    setattr(tr, name, v)
         return tr
 
     def _sample_blocks(self, nsteps, initial_occupancies, thin_by, max_block=0, state_loaded=False, keep_occupancy=True):
@@ -2542,22 +2400,10 @@ class Sampler:
         # bytes of one sample of all walkers in the ring: occupancy bytes + features (+ the Wang-Landau trace:
         # entropy / histogram / occurrences [L] and the mean features [L x F] of every walker, wanglandau.py:247-251)
         F = len(k0.ensemble.natural_parameters)
-        obs = self._observables
         per_sample = nw * ((N if keep_occupancy else 0) + 8 * F + 17)
-        if obs is not None:
-            per_sample += nw * 4 * (obs.n_kinds + obs.n_shells * obs.n_kinds ** 2)
-        sf = self._structure
-        if sf is not None:
-            per_sample += nw * 8 * (2 * sf.n_points * sf.n_kinds + sf.n_intensities)
-        cn = self._connectivity
-        if cn is not None:
-            per_sample += nw * 8 * 24 * cn.n_graphs
-        pt = self._patterns
-        if pt is not None:
-            per_sample += nw * 4 * pt.n_cells
-        ev = self._environments
-        if ev is not None:
-            per_sample += nw * 4 * ev.n_cells
+        for name, spec in self._traced.items():  # (the derived traces: their cells at their width)
+            per_sample += nw * sum(np.dtype(dtype).itemsize * int(np.prod(trace_shape(dims, spec)))
+                                   for _, dtype, dims in BY_NAME[name].traces)
         if is_wl:
             L = len(k0._levels)
             per_sample += nw * L * (24 + 8 * F)
@@ -2571,11 +2417,11 @@ class Sampler:
         temps = self._temperatures().reshape(1, nw, 1)
         sizes = [min(per_block, nsamples - start) for start in range(0, nsamples, per_block)]
 
+        asked = {BY_NAME[name].run_keyword: True for name in self._traced}
+
         def queue(n):
-            eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl, observables=obs is not None,
-                                  minima=self._minima is not None, statistics=self._statistics is not None,
-                                  structure=sf is not None, connectivity=cn is not None, patterns=pt is not None,
-                                  environments=ev is not None)
+            eng.run_sampled_async(n, thin_by, occupancy=keep_occupancy, bias=has_bias, wl=is_wl,
+                                  minima=self._minima is not None, statistics=self._statistics is not None, **asked)
             if self._minima is not None:
                 self._minima_offers += n
 
@@ -2616,16 +2462,7 @@ class Sampler:
             if is_wl:
                 block.update(histogram=ring["histogram"], occurrences=ring["occurrences"], entropy=ring["entropy"],
                              cumulative_mean_features=ring["mean_features"], mod_factor=ring["mod_factor"][..., None])
-            if "species_counts" in ring:
-                block.update(species_counts=ring["species_counts"], pair_counts=ring["pair_counts"])
-            if "structure_amplitudes" in ring:
-                block.update(structure_amplitudes=ring["structure_amplitudes"], structure_intensities=ring["structure_intensities"])
-            if "connectivity" in ring:
-                block.update(connectivity=ring["connectivity"])
-            if "pattern_counts" in ring:
-                block.update(pattern_counts=ring["pattern_counts"])
-            if "environment_counts" in ring:
-                block.update(environment_counts=ring["environment_counts"])
+            block.update({name: ring[name] for fam in FAMILIES for name, _, _ in fam.traces if name in ring})
             yield block
 
     def _wl_run_with_host_checks(self, eng, nsteps):
@@ -2707,7 +2544,7 @@ class Sampler:
         leave the device -- their species and pair counts do; the container stores the occupancy of the final
         sample of this call alone, so ``last_occupancy`` and a continuation work as before."""
         if not keep_occupancy:
-            if self._observables is None and self._minima is None and self._structure is None and self._connectivity is None:
+            if not self._traced and self._minima is None:  # (a family that rests on the observables comes with them)
                 raise ValueError("keep_occupancy=False needs a sampler built with observables=, minima=, structure_factor= or connectivity=: nothing else of the "
                                  "occupancies would be recorded")
             if stream_chunk > 0:

@@ -179,6 +179,28 @@ class Observables:
         s.bonds = bonds.ctypes.data_as(C.POINTER(C.c_int32))
         return s, (self.kind_base, ptr, bonds)
 
+    # ---- what a container keeps of the spec ------------------------------------------------------------------------
+    def describe(self):
+        """The kinds of the species_counts / pair_counts traces (plain lists: it goes into a container's metadata)."""
+        return dict(n_kinds=self.n_kinds, n_shells=self.n_shells, default_kinds=self.default_kinds,
+                    kind_base=self.kind_base.tolist(), site_ncodes=self.site_ncodes.tolist())
+
+    @staticmethod
+    def metadata_to_npz(obs):
+        """The meta/* arrays of an .npz for the dict of ``describe``."""
+        return {"meta/obs_kind_base": np.asarray(obs["kind_base"], dtype=np.int32),
+                "meta/obs_site_ncodes": np.asarray(obs["site_ncodes"], dtype=np.int32),
+                "meta/obs_shape": np.asarray([obs["n_kinds"], obs["n_shells"], int(obs["default_kinds"])], dtype=np.int64)}
+
+    @staticmethod
+    def metadata_from_npz(d):
+        """The dict of ``describe`` from the arrays of ``metadata_to_npz``, None when ``d`` holds none."""
+        if "meta/obs_kind_base" not in d.files:
+            return None
+        K, S, default = (int(x) for x in d["meta/obs_shape"])
+        return dict(n_kinds=K, n_shells=S, default_kinds=bool(default), kind_base=d["meta/obs_kind_base"].tolist(),
+                    site_ncodes=d["meta/obs_site_ncodes"].tolist())
+
     # ---- derived quantities (host) ---------------------------------------------------------------------------------
     def species_counts(self, counts, sites):
         """The slice of ``counts`` (..., K) that belongs to the sites ``sites`` -- a sublattice -- in code order, or None

@@ -192,6 +192,24 @@ class Patterns:
                     cell_ptr=self.cell_ptr.tolist(), class_of_kind=[st.class_of_kind.tolist() for st in self.sets],
                     set_orbit_ids=self.set_orbit_ids)
 
+    @staticmethod
+    def metadata_to_npz(pat):
+        """The meta/* arrays of an .npz for the dict of ``describe``."""
+        return {"meta/pat_shape": np.asarray([pat["arity"], pat["n_classes"], pat["n_tuples"]], dtype=np.int64),
+                "meta/pat_cell_ptr": np.asarray(pat["cell_ptr"], dtype=np.int64),
+                "meta/pat_class_of_kind": np.asarray(pat["class_of_kind"], dtype=np.int32),
+                "meta/pat_orbit_ids": np.asarray(pat["set_orbit_ids"] if pat["set_orbit_ids"] is not None else [], dtype=np.int64)}
+
+    @staticmethod
+    def metadata_from_npz(d):
+        """The dict of ``describe`` from the arrays of ``metadata_to_npz``, None when ``d`` holds none."""
+        if "meta/pat_shape" not in d.files:
+            return None
+        arity, ncls, ntup = (d["meta/pat_shape"][i].tolist() for i in range(3))
+        ptr, ids = d["meta/pat_cell_ptr"].tolist(), d["meta/pat_orbit_ids"].tolist()
+        return dict(n_sets=len(arity), n_cells=int(ptr[-1]), arity=arity, n_classes=ncls, n_tuples=ntup, cell_ptr=ptr,
+                    class_of_kind=d["meta/pat_class_of_kind"].tolist(), set_orbit_ids=ids if ids else None)
+
     # ---- derived quantities (host) ---------------------------------------------------------------------------------
     def cells_of(self, cells, t):
         """The cells of set ``t`` as an array (..., C, ..., C), one axis per position."""

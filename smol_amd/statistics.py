@@ -94,6 +94,34 @@ def kind(observables, name_or_k):
     return ("kind", k)
 
 
+def segments(n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0, n_env_cells=0):
+    """The column sources of the C ABI as ordered segments (tag, first source, width), for the sizes in force
+    F, K, I, G, P (``n_cells``), E (``n_env_cells``):
+
+        0                              enthalpy
+        1 + i                          feature i
+        1 + F + k                      kind k of the observables
+        1 + F + K                      energy: the weighted sum of the features
+        2 + F + K + i                  intensity i of the structure-factor spec
+        2 + F + K + I + 24 g + c       connectivity: number c of graph g of the connectivity spec
+        2 + F + K + I + 24 G + c       pattern: cell c of the pattern spec
+        2 + F + K + I + 24 G + P + c   environment: cell c of the environment spec
+
+    The five segments of ``families.FAMILIES`` come in the table's order; a size is 0 when no spec is in force."""
+    out, first = [], 0
+    for tag, width in (("enthalpy", 1), ("feature", n_features), ("kind", n_kinds), ("energy", 1), ("intensity", n_intensities),
+                       ("connectivity", 24 * int(n_graphs)), ("pattern", n_cells), ("environment", n_env_cells)):
+        out.append((tag, first, int(width)))
+        first += int(width)
+    return tuple(out)
+
+
+# the tags whose range ``Statistics.sources`` checks: (what is counted, "... of the <which> spec", sources per unit)
+_CHECKED = {"intensity": ("intensity", "intensities of the structure-factor", 1),
+            "connectivity": ("graph", "graphs of the connectivity", 24),
+            "pattern": ("cell", "cells of the pattern", 1), "environment": ("cell", "cells of the environment", 1)}
+
+
 class Statistics:
     """The spec of a record: how it is keyed, its columns, the weights of the ENERGY column, the blocking levels and the
     histogram (``hist=(column, n_bins, hist_min, hist_bin)`` with ``column`` one of ``columns``)."""
@@ -126,61 +154,46 @@ class Statistics:
     n_pairs = property(lambda self: self.n_columns * (self.n_columns + 1) // 2)
 
     def sources(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0, n_env_cells=0):
-        """int32 column sources of the C ABI: 0 enthalpy, 1 + i feature i, 1 + F + k kind k, 1 + F + K the weighted sum,
-        2 + F + K + i intensity i (i < ``n_intensities``), 2 + F + K + I + 24 g + c number c of graph g of the connectivity
-        spec (g < ``n_graphs``), 2 + F + K + I + 24 G + c cell c of the pattern spec (c < ``n_cells``),
-        2 + F + K + I + 24 G + P + c cell c of the environment spec (P = ``n_cells``, c < ``n_env_cells``)."""
-        F, K, I, G, PC = int(n_features), int(n_kinds), int(n_intensities), int(n_graphs), int(n_cells)
-        EC = int(n_env_cells)
+        """int32 column sources of the C ABI (``segments``): a tagged column is its number within the segment of its tag,
+        24 g + c for number c of graph g of the connectivity spec; a plain number is a source as it stands."""
+        first_of = {tag: (first, width) for tag, first, width in
+                    segments(n_features, n_kinds, n_intensities, n_graphs, n_cells, n_env_cells)}
         out = []
         for c in self.columns:
-            if c[0] == "enthalpy":
-                out.append(0)
-            elif c[0] == "feature":
-                out.append(1 + c[1])
-            elif c[0] == "kind":
-                out.append(1 + F + c[1])
-            elif c[0] == "energy":
-                out.append(1 + F + K)
-            elif c[0] == "intensity":
-                if not 0 <= c[1] < I:
-                    raise ValueError(f"intensity {c[1]} outside the {I} intensities of the structure-factor spec")
-                out.append(2 + F + K + c[1])
-            elif c[0] == "connectivity":
-                if not 0 <= c[1] < G:
-                    raise ValueError(f"graph {c[1]} outside the {G} graphs of the connectivity spec")
-                out.append(2 + F + K + I + 24 * c[1] + c[2])
-            elif c[0] == "pattern":
-                if not 0 <= c[1] < PC:
-                    raise ValueError(f"cell {c[1]} outside the {PC} cells of the pattern spec")
-                out.append(2 + F + K + I + 24 * G + c[1])
-            elif c[0] == "environment":
-                if not 0 <= c[1] < EC:
-                    raise ValueError(f"cell {c[1]} outside the {EC} cells of the environment spec")
-                out.append(2 + F + K + I + 24 * G + PC + c[1])
-            else:
+            if c[0] == "source":
                 out.append(c[1])
+                continue
+            first, width = first_of[c[0]]
+            if c[0] in _CHECKED:  # (the other ranges: the engine refuses them)
+                one, many, unit = _CHECKED[c[0]]
+                if not 0 <= c[1] < width // unit:
+                    raise ValueError(f"{one} {c[1]} outside the {width // unit} {many} spec")
+            out.append(first + (0 if len(c) == 1 else c[1] if len(c) == 2 else 24 * c[1] + c[2]))
         return np.asarray(out, dtype=np.int32)
+
+    def tagged_columns(self, tag):
+        """Indices into ``columns`` of the columns with ``tag``, in order."""
+        return [i for i, c in enumerate(self.columns) if c[0] == tag]
 
     def count_columns(self):
         """Indices into ``columns`` of the kind counts, in order."""
-        return [i for i, c in enumerate(self.columns) if c[0] == "kind"]
+        return self.tagged_columns("kind")
 
     def intensity_columns(self):
         """Indices into ``columns`` of the intensities, in order."""
-        return [i for i, c in enumerate(self.columns) if c[0] == "intensity"]
+        return self.tagged_columns("intensity")
 
     def connectivity_columns(self):
         """Indices into ``columns`` of the connectivity numbers, in order."""
-        return [i for i, c in enumerate(self.columns) if c[0] == "connectivity"]
+        return self.tagged_columns("connectivity")
 
     def pattern_columns(self):
         """Indices into ``columns`` of the pattern cells, in order."""
-        return [i for i, c in enumerate(self.columns) if c[0] == "pattern"]
+        return self.tagged_columns("pattern")
 
     def environment_columns(self):
         """Indices into ``columns`` of the environment cells, in order."""
-        return [i for i, c in enumerate(self.columns) if c[0] == "environment"]
+        return self.tagged_columns("environment")
 
     def column_values(self, enthalpy, features, counts=None, intensities=None, connectivity=None, patterns=None,
                       environments=None):
@@ -189,32 +202,22 @@ class Statistics:
         (..., n_env_cells) or None."""
         H = np.asarray(enthalpy, dtype=np.float64)
         f = np.asarray(features, dtype=np.float64).reshape(H.shape + (-1,))
-        F = f.shape[-1]
-        K = 0 if counts is None else np.asarray(counts).shape[-1]
-        I = 0 if intensities is None else np.asarray(intensities).shape[-1]
-        G = 0 if connectivity is None else np.asarray(connectivity).shape[-2]
-        PC = 0 if patterns is None else np.asarray(patterns).shape[-1]
-        EC = 0 if environments is None else np.asarray(environments).shape[-1]
+        given = dict(kind=counts, intensity=intensities, connectivity=connectivity, pattern=patterns, environment=environments)
+        size = {tag: 0 if a is None else np.asarray(a).shape[-2 if tag == "connectivity" else -1] for tag, a in given.items()}
+        segs = segments(f.shape[-1], size["kind"], size["intensity"], size["connectivity"], size["pattern"], size["environment"])
         x = np.empty(H.shape + (self.n_columns,))
-        for j, src in enumerate(self.sources(F, K, I, G, PC, EC)):
-            if src == 0:
+        for j, src in enumerate(self.sources(f.shape[-1], *size.values())):
+            tag, first, width = next((s for s in segs if s[1] <= src < s[1] + s[2]), (None, 0, 0))
+            if tag is None:
+                raise ValueError(f"column source {src} outside 0..{segs[-1][1] + segs[-1][2] - 1}")
+            if tag == "enthalpy":
                 x[..., j] = H
-            elif src <= F:
-                x[..., j] = f[..., src - 1]
-            elif src <= F + K:
-                x[..., j] = np.asarray(counts).reshape(H.shape + (K,))[..., src - 1 - F].astype(np.float64)
-            elif src == 1 + F + K:
+            elif tag == "feature":
+                x[..., j] = f[..., src - first]
+            elif tag == "energy":
                 x[..., j] = weighted_value(self.weights if self.weights is not None else np.zeros(0), f)
-            elif src <= 1 + F + K + I:
-                x[..., j] = np.asarray(intensities, dtype=np.float64).reshape(H.shape + (I,))[..., src - 2 - F - K]
-            elif src <= 1 + F + K + I + 24 * G:
-                x[..., j] = np.asarray(connectivity).reshape(H.shape + (24 * G,))[..., src - 2 - F - K - I].astype(np.float64)
-            elif src <= 1 + F + K + I + 24 * G + PC:
-                x[..., j] = np.asarray(patterns).reshape(H.shape + (PC,))[..., src - 2 - F - K - I - 24 * G].astype(np.float64)
-            elif src <= 1 + F + K + I + 24 * G + PC + EC:
-                x[..., j] = np.asarray(environments).reshape(H.shape + (EC,))[..., src - 2 - F - K - I - 24 * G - PC].astype(np.float64)
-            else:
-                raise ValueError(f"column source {src} outside 0..{1 + F + K + I + 24 * G + PC + EC}")
+            else:  # (a family's segment: its values, flat per row, read as doubles)
+                x[..., j] = np.asarray(given[tag]).reshape(H.shape + (width,))[..., src - first].astype(np.float64)
         return x
 
     def c_struct(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0, n_env_cells=0):

@@ -289,6 +289,12 @@ class StructureFactor:
         s.intensity_scale = self.intensity_scale.ctypes.data_as(C.POINTER(C.c_double))
         return s, (self.kind_base, self.phase, self.table, self.intensity, self.intensity_scale)
 
+    def describe(self):
+        """What a container keeps of the spec: the shape of the two traces, what the intensities are and their scale."""
+        return dict(n_points=self.n_points, n_kinds=self.n_kinds, n_intensities=self.n_intensities, bits=self.bits,
+                    intensities=self.intensity.tolist(), intensity_scale=self.intensity_scale.tolist(),
+                    points=None if self.points is None else self.points.tolist())
+
     # ---- derived quantities (host) ---------------------------------------------------------------------------------
     def amplitudes(self, amp):
         """A_k(q) = sum_j exp(-i k . r_j) as complex128 (..., Q, K): ``amp 2^-bits``."""
