@@ -551,11 +551,14 @@ int smolmc_get_minima_companions(smolmc_handle *h, int32_t *occ);
 #define SMOLMC_STAT_BY_WALKER 0      /* n_keys = R, the key is the walker */
 #define SMOLMC_STAT_BY_STATE_POINT 1 /* n_keys = R, the key is the state point the walker holds when the reduction runs
                                       * on the handle's stream (the identity while smolmc_exchange_grid has never run) */
+#define SMOLMC_STAT_BY_BIN 2         /* n_keys bins of one of the columns (smolmc_set_statistics_binned, below) */
+#define SMOLMC_MAX_STAT_KEYS 65536   /* bins of a record keyed by bin */
 #define SMOLMC_MAX_STAT_COLUMNS 32
 #define SMOLMC_MAX_STAT_LEVELS 32
 #define SMOLMC_MAX_STAT_BINS 65536
 typedef struct smolmc_statistics {
-    int key;                /* SMOLMC_STAT_BY_WALKER or SMOLMC_STAT_BY_STATE_POINT */
+    int key;                /* SMOLMC_STAT_BY_WALKER or SMOLMC_STAT_BY_STATE_POINT; SMOLMC_STAT_BY_BIN only through
+                             * smolmc_set_statistics_binned */
     int n_columns;          /* C, 1..32 */
     const int32_t *columns; /* [C] sources, no duplicates: 0 the enthalpy, 1 + i feature i (i < F), 1 + F + k kind count k
                              * of the observables in force (k < K, as a double), 1 + F + K the weighted sum below,
@@ -579,6 +582,32 @@ typedef struct smolmc_statistics {
  * and smolmc_set_structure while a record with intensity columns is set.
  * Waits for the handle's stream, like smolmc_reset_statistics and smolmc_get_statistics. */
 int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *s);
+/* ---- statistics keyed by BINS of a column (SMOLMC_STAT_BY_BIN): microcanonical averages, averages per composition ----
+ * A key of this mode gathers several rows of a sample, or none.  The rows of an offer are taken SAMPLE BY SAMPLE, AND
+ * WITHIN A SAMPLE IN WALKER ORDER 0 .. R - 1.  For each row:
+ *   q = floor((x[key_column] - key_min) / key_bin), the exact floor division of the Wang-Landau step and of the record's
+ *       histogram
+ *   q < 0 counts in key_under, ONE int64 for the whole record; q >= n_keys, or a value that is not finite, counts in
+ *       key_over; neither row is offered to any key
+ *   every other row is offered to key q by the rule above: the key's first row is the shift, then s1, the s2 triangle,
+ *       the per-key histogram of hist_column with the key's under and over, and n += 1
+ * Blocking means nothing when successive rows of a key come from different walkers: n_levels must be 0, and the record's
+ * arrays keep their shapes with n_levels = 0.  Every product and every sum is rounded on its own, as above.  The
+ * walker-to-state-point map is not read.
+ * s->key must be SMOLMC_STAT_BY_BIN; key_column is an index into s->columns, like hist_column.  Makes every check
+ * smolmc_set_statistics makes and refuses further, each naming its reason and leaving the record in force untouched:
+ * n_levels != 0; n_keys outside 1..65536; key_bin not a positive finite number or key_min not finite; key_column outside
+ * the columns; a record of more than 1 GiB.  Allowed on a Wang-Landau handle with per-walker windows: the key is the
+ * row's value, not the walker.  smolmc_set_statistics itself keeps refusing key 2.  Everything else is the one record:
+ * smolmc_statistics_shape and smolmc_get_statistics report n_keys bins, SMOLMC_SAMPLE_STATISTICS blocks offer their rows,
+ * smolmc_update_statistics offers one sample of R rows, smolmc_reset_statistics also clears the two outside counters, and
+ * the refusals of smolmc_set_observables, smolmc_set_structure and the rest count the key column like any other. */
+int smolmc_set_statistics_binned(smolmc_handle *h, const smolmc_statistics *s, int key_column, int n_keys, double key_min,
+                                 double key_bin);
+/* The binned spec in force and its two outside counters; all zeros when the record in force is not binned (or none is
+ * set).  Any pointer may be NULL.  Waits for the handle's stream when a counter is asked for. */
+int smolmc_statistics_bins(smolmc_handle *h, int *key_column, int *n_keys, double *key_min, double *key_bin,
+                           int64_t *key_under, int64_t *key_over);
 /* the shape in force (all 0: none set) */
 int smolmc_statistics_shape(smolmc_handle *h, int *n_keys, int *n_columns, int *n_levels, int *n_bins);
 /* Offers the walkers' CURRENT states, one offer (for callers of smolmc_run); with count columns the kinds of the current

@@ -206,8 +206,13 @@ class smolmc_minima(C.Structure):
     ]
 
 
+STAT_BY_WALKER, STAT_BY_STATE_POINT, STAT_BY_BIN = 0, 1, 2  # SMOLMC_STAT_BY_*: the key modes of a statistics record
+MAX_STAT_KEYS = 65536  # SMOLMC_MAX_STAT_KEYS: the bins of a record keyed by bin (smolmc_set_statistics_binned)
+
+
 class smolmc_statistics(C.Structure):
-    """Mirror of ``smolmc_statistics`` (include/smolmc.h); ``statistics.Statistics.c_struct`` fills it."""
+    """Mirror of ``smolmc_statistics`` (include/smolmc.h); ``statistics.Statistics.c_struct`` fills it.  A record keyed
+    by bin passes its four extra scalars beside the struct (smolmc_set_statistics_binned; ``Statistics.c_bins``)."""
 
     _fields_ = [
         ("key", C.c_int),

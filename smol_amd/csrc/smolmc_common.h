@@ -913,7 +913,14 @@ struct SmolmcStat {
     int32_t *columns = nullptr;
     double *weights = nullptr;
     int32_t *u_counts = nullptr; // smolmc_update_statistics: counts [R x K]
-    hipEvent_t ev[2] = {nullptr, nullptr}; // around the last reduction
+    // a record keyed by bin (SMOLMC_STAT_BY_BIN): n_keys bins of column key_column
+    int key_column = 0;
+    double key_min = 0.0, key_bin = 1.0;
+    long long *outside = nullptr;  // key_under, key_over (in the arena, zeroed by a reset)
+    int32_t *bin_cnt = nullptr;    // [n_keys] rows per key of the launch under way (in the arena)
+    int32_t *row_key = nullptr;    // [row_cap] the key of every row of the launch: an allocation of its own that grows to
+    size_t row_cap = 0;            // the largest launch so far
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; // around the last reduction; ev[2] between the two launches of a binned one
 };
 
 // structure.hip: the structure-factor spec of a handle (smolmc_set_structure) as the kernel reads it, engine numbering

@@ -13,6 +13,22 @@
 //            c < C also owns s1[c] and column c's blocking chain (pend and b2 live in LDS for the launch; thread 0 counts
 //            nb); the last thread owns the histogram
 // d = x - shift is formed where it is used (one subtraction, the same bits everywhere).
+//
+// Keys by BINS of a column (SMOLMC_STAT_BY_BIN, smolmc_set_statistics_binned) gather several rows of a sample, or none.
+// The rows of an offer are taken sample by sample and within a sample in walker order, i.e. in ascending row number of
+// the launch; q = floor((x[key_column] - key_min) / key_bin) by floordiv_exact; q < 0 counts in key_under, q >= n_keys or
+// a value that is not finite in key_over (one int64 each for the record) and the row is offered to no key; every other
+// row is offered to key q by the rule above (no blocking: n_levels = 0).  Two more passes, each a MODE of
+// statistics_kernel (StatArgs::mode, uniform over the launch; the library gains no kernel symbol, as with the merge mode
+// of wl_exchange_kernel), launched one behind the other:
+//   stat_bin_keys      one thread per row: its key (or a negative sentinel) into a scratch array kept with the record,
+//                      the rows per key into cnt[n_keys], the two outside totals with one integer atomic per wave.
+//                      Integer atomics do not depend on order: nothing here can change a bit.
+//   statistics_binned  one workgroup per key; cnt == 0 exits at once.  It scans the row keys in order, 256 rows a pass,
+//                      and compacts the matching row numbers in ASCENDING order into an LDS queue (ballot, the lane's
+//                      prefix from the mask, per-wave offsets); whenever the queue holds ST_CHUNK rows, or the scan has
+//                      ended, their values are staged and consumed with the ownership above.  Its LDS is the kernel's:
+//                      the queue lies where the blocking arrays of the other modes do.
 #include "smolmc_common.h"
 
 #define ST_THREADS 256
@@ -20,6 +36,12 @@
 #define ST_MAXC SMOLMC_MAX_STAT_COLUMNS
 #define ST_MAXL SMOLMC_MAX_STAT_LEVELS
 #define ST_OWN 3    // s2 entries a thread owns at most: ceil(528 / 256)
+#define ST_WAVES (ST_THREADS / 64)
+#define ST_QUEUE 512 // row queue of the binned kernel, a ring: at most ST_CHUNK - 1 rows wait when a pass adds up to 256
+#define ST_KEY_UNDER (-1) // row keys of the rows outside the bins
+#define ST_KEY_OVER (-2)
+#define ST_MODE_KEYS 1   // StatArgs::mode: 0 the reduction by walker or state point, 1 stat_bin_keys, 2 statistics_binned
+#define ST_MODE_BINNED 2
 
 struct StatArgs {
     // the rows
@@ -41,6 +63,14 @@ struct StatArgs {
     int C, L, n_bins, hist_column, n_weights;
     int R, F, K, I, CS, PC, EC;
     long long nsamples;
+    // a record keyed by bin (modes 1 and 2; walker_at, nb, pend, b2, has are not read: L = 0)
+    int mode;
+    int key_column, n_keys;
+    double key_min, key_bin;
+    int32_t *row_key;            // [rows] scratch: the key of every row of the launch, ST_KEY_UNDER / ST_KEY_OVER outside
+    int32_t *cnt;                // [n_keys] rows per key in this launch (zeroed before it)
+    unsigned long long *outside; // key_under, key_over of the record
+    long long rows;              // nsamples x R
 };
 
 // column source `src` of row `row`: 0 the enthalpy, 1 + i feature i, 1 + F + k kind count k, 1 + F + K the weighted sum,
@@ -57,6 +87,148 @@ __device__ __forceinline__ double stat_column(const StatArgs &A, size_t row, int
     return weighted_value_rn(A.weights, A.feat + row * A.F, A.n_weights);
 }
 
+// ---- keys by bins of a column ---------------------------------------------------------------------------------------------
+// mode 1 of statistics_kernel: one thread per row of the launch
+__device__ __forceinline__ void stat_bin_keys(const StatArgs &B) {
+#pragma clang fp contract(off)
+    const long long row = (long long)blockIdx.x * ST_THREADS + threadIdx.x;
+    const bool live = row < B.rows;
+    bool is_under = false, is_over = false;
+    if (live) {
+        const double xv = stat_column(B, (size_t)row, B.columns[B.key_column]);
+        const double q = floordiv_exact(xv - B.key_min, B.key_bin);
+        int key;
+        if (!(fabs(xv) <= 1.7976931348623157e308) || !(q == q)) key = ST_KEY_OVER; // (not finite)
+        else if (q < 0.0) key = ST_KEY_UNDER;
+        else if (q >= (double)B.n_keys) key = ST_KEY_OVER;
+        else key = (int)q;
+        B.row_key[row] = key;
+        is_under = key == ST_KEY_UNDER;
+        is_over = key == ST_KEY_OVER;
+        if (key >= 0) atomicAdd(&B.cnt[key], 1);
+    }
+    // the two outside totals: one atomic per wave
+    const unsigned long long m_under = __ballot(is_under), m_over = __ballot(is_over);
+    if ((threadIdx.x & 63) == 0) {
+        if (m_under) atomicAdd(&B.outside[0], (unsigned long long)__popcll(m_under));
+        if (m_over) atomicAdd(&B.outside[1], (unsigned long long)__popcll(m_over));
+    }
+}
+
+// mode 2 of statistics_kernel: one workgroup per key; s_x [ST_CHUNK x ST_MAXC], s_shift [ST_MAXC], s_queue [ST_QUEUE] and
+// s_wcnt [ST_WAVES] are the kernel's LDS
+__device__ __forceinline__ void statistics_binned(const StatArgs &B, double *s_x, double *s_shift, int *s_queue, int *s_wcnt) {
+    // Every product and every sum is rounded on its own, as in the other modes.
+#pragma clang fp contract(off)
+    const StatArgs &A = B;
+    const int key = blockIdx.x, tid = threadIdx.x;
+    const int cnt = B.cnt[key];
+    if (cnt == 0) return; // (uniform over the workgroup) most keys of a wide grid
+    const int C = A.C, P = C * (C + 1) / 2;
+    const long long n0 = A.n[key];
+    double acc[ST_OWN];
+    int ia[ST_OWN], ib[ST_OWN];
+#pragma unroll
+    for (int j = 0; j < ST_OWN; ++j) {
+        const int p = tid + j * ST_THREADS;
+        ia[j] = -1;
+        ib[j] = 0;
+        acc[j] = 0.0;
+        if (p < P) { // entry p of the upper triangle, row-major: row a starts at a C - a (a - 1) / 2
+            int a = 0, q = p;
+            while (q >= C - a) {
+                q -= C - a;
+                ++a;
+            }
+            ia[j] = a;
+            ib[j] = a + q;
+            acc[j] = A.s2[(size_t)key * P + p];
+        }
+    }
+    double my_s1 = 0.0;
+    if (tid < C) {
+        s_shift[tid] = A.shift[(size_t)key * C + tid];
+        my_s1 = A.s1[(size_t)key * C + tid];
+    }
+    const bool hist_owner = tid == ST_THREADS - 1 && A.n_bins > 0;
+    long long under = 0, over = 0;
+    if (hist_owner) {
+        under = A.under[key];
+        over = A.over[key];
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+    int head = 0, tail = 0; // (uniform) rows consumed, rows found: the queue holds the rows head .. tail - 1 of the key
+    bool first = n0 == 0;
+    for (long long base = 0; tail < cnt && base < B.rows; base += ST_THREADS) {
+        // one pass of the scan: the matching rows of base .. base + 255 join the queue in ascending order
+        const long long row = base + tid;
+        const bool match = row < B.rows && B.row_key[row] == key;
+        const unsigned long long mask = __ballot(match);
+        if (lane == 0) s_wcnt[wave] = __popcll(mask);
+        __syncthreads(); // (also: the chunk before is consumed)
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < ST_WAVES; ++w) {
+            const int c = s_wcnt[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        if (match) s_queue[(tail + before + __popcll(mask & (((unsigned long long)1 << lane) - 1))) & (ST_QUEUE - 1)] = (int)row;
+        tail += total;
+        const bool ended = tail >= cnt || base + ST_THREADS >= B.rows;
+        while (tail - head >= ST_CHUNK || (ended && tail > head)) {
+            const int m = tail - head < ST_CHUNK ? tail - head : ST_CHUNK;
+            __syncthreads(); // (the queue is written; the chunk before is consumed)
+            for (int e = tid; e < m * C; e += ST_THREADS) {
+                const int s = e / C, c = e - s * C;
+                s_x[s * ST_MAXC + c] = stat_column(A, (size_t)s_queue[(head + s) & (ST_QUEUE - 1)], A.columns[c]);
+            }
+            __syncthreads();
+            if (first) { // (uniform over the workgroup) the key's first offered value
+                if (tid < C) s_shift[tid] = s_x[tid];
+                __syncthreads();
+                first = false;
+            }
+            for (int s = 0; s < m; ++s) {
+                const double *x = s_x + s * ST_MAXC;
+#pragma unroll
+                for (int j = 0; j < ST_OWN; ++j)
+                    if (ia[j] >= 0) {
+                        const double da = x[ia[j]] - s_shift[ia[j]], db = x[ib[j]] - s_shift[ib[j]];
+                        const double p = da * db;
+                        acc[j] = acc[j] + p;
+                    }
+                if (tid < C) {
+                    const double d = x[tid] - s_shift[tid];
+                    my_s1 = my_s1 + d;
+                }
+                if (hist_owner) {
+                    const double xv = x[A.hist_column];
+                    const double q = floordiv_exact(xv - A.hist_min, A.hist_bin);
+                    if (!(fabs(xv) <= 1.7976931348623157e308) || !(q == q)) ++over; // (not finite)
+                    else if (q < 0.0) ++under;
+                    else if (q >= (double)A.n_bins) ++over;
+                    else A.hist[(size_t)key * A.n_bins + (size_t)q] += 1;
+                }
+            }
+            head += m;
+        }
+        __syncthreads(); // (s_wcnt and the queue's consumed entries are free for the next pass)
+    }
+#pragma unroll
+    for (int j = 0; j < ST_OWN; ++j)
+        if (ia[j] >= 0) A.s2[(size_t)key * P + tid + j * ST_THREADS] = acc[j];
+    if (tid < C) {
+        A.shift[(size_t)key * C + tid] = s_shift[tid];
+        A.s1[(size_t)key * C + tid] = my_s1;
+    }
+    if (hist_owner) {
+        A.under[key] = under;
+        A.over[key] = over;
+    }
+    if (tid == 0) A.n[key] = n0 + head;
+}
+
 __global__ void __launch_bounds__(ST_THREADS) statistics_kernel(const StatArgs A) {
     // Every product and every sum is rounded on its own, as NumPy does it (see weighted_value_rn, smolmc_common.h).
 #pragma clang fp contract(off)
@@ -64,6 +236,15 @@ __global__ void __launch_bounds__(ST_THREADS) statistics_kernel(const StatArgs A
     __shared__ double s_shift[ST_MAXC];
     __shared__ double s_pend[ST_MAXL * ST_MAXC], s_b2[ST_MAXL * ST_MAXC];
     __shared__ long long s_nb[ST_MAXL];
+    static_assert(ST_QUEUE * sizeof(int) <= sizeof(s_pend) && ST_WAVES * sizeof(int) <= sizeof(s_nb), "the queue of the binned mode");
+    if (A.mode == ST_MODE_KEYS) { // (uniform over the launch)
+        stat_bin_keys(A);
+        return;
+    }
+    if (A.mode == ST_MODE_BINNED) {
+        statistics_binned(A, s_x, s_shift, reinterpret_cast<int *>(s_pend), reinterpret_cast<int *>(s_nb));
+        return;
+    }
     const int key = blockIdx.x, tid = threadIdx.x;
     const int C = A.C, L = A.L, P = C * (C + 1) / 2;
     const size_t walker = A.walker_at ? (size_t)A.walker_at[key] : (size_t)key;
@@ -175,6 +356,7 @@ __global__ void __launch_bounds__(ST_THREADS) statistics_kernel(const StatArgs A
     if (tid == 0) A.n[key] = n0 + A.nsamples;
 }
 
+
 int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, const double *d_inten,
                        const long long *d_conn, const int32_t *d_pat, const int32_t *d_env, long long nsamples) {
     SmolmcStat &S = h->stats;
@@ -200,6 +382,31 @@ int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat
     A.nsamples = nsamples;
     if (!S.ev[0])
         for (hipEvent_t &e : S.ev) HIPCHK(hipEventCreate(&e));
+    if (S.key == SMOLMC_STAT_BY_BIN) {
+        const size_t rows = (size_t)nsamples * h->R;
+        if (rows > S.row_cap) { // (the scratch grows to the largest launch so far; hipFree waits for the launches that read it)
+            if (S.row_key) HIPCHK(hipFree(S.row_key));
+            S.row_key = nullptr;
+            S.row_cap = 0;
+            HIPCHK(hipMalloc((void **)&S.row_key, rows * 4));
+            S.row_cap = rows;
+        }
+        A.row_key = S.row_key; A.cnt = S.bin_cnt; A.outside = (unsigned long long *)S.outside;
+        A.key_min = S.key_min; A.key_bin = S.key_bin; A.key_column = S.key_column; A.n_keys = S.n_keys;
+        A.rows = (long long)rows;
+        HIPCHK(hipMemsetAsync(S.bin_cnt, 0, (size_t)S.n_keys * 4, h->stream));
+        HIPCHK(hipEventRecord(S.ev[0], h->stream));
+        A.mode = ST_MODE_KEYS;
+        hipLaunchKernelGGL(statistics_kernel, dim3((unsigned)((rows + ST_THREADS - 1) / ST_THREADS)), dim3(ST_THREADS), 0,
+                           h->stream, A);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(S.ev[2], h->stream));
+        A.mode = ST_MODE_BINNED;
+        hipLaunchKernelGGL(statistics_kernel, dim3((unsigned)S.n_keys), dim3(ST_THREADS), 0, h->stream, A);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(S.ev[1], h->stream));
+        return 0;
+    }
     HIPCHK(hipEventRecord(S.ev[0], h->stream));
     hipLaunchKernelGGL(statistics_kernel, dim3((unsigned)S.n_keys), dim3(ST_THREADS), 0, h->stream, A);
     HIPCHK(hipGetLastError());
@@ -210,12 +417,20 @@ int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat
 void smolmc_stat_free(smolmc_handle *h) {
     SmolmcStat &S = h->stats;
     if (S.arena) hipFree(S.arena);
+    if (S.row_key) hipFree(S.row_key);
     for (hipEvent_t e : S.ev)
         if (e) hipEventDestroy(e);
     S = SmolmcStat();
 }
 
-extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *s) {
+// the binned part of a spec (smolmc_set_statistics_binned)
+struct StatBins {
+    int key_column, n_keys;
+    double key_min, key_bin;
+};
+
+// smolmc_set_statistics (bins null) and smolmc_set_statistics_binned: every check, then the arena
+static int stat_set(smolmc_handle *h, const smolmc_statistics *s, const StatBins *bins) {
     if (!h) return fail("null handle");
     if (h->dist) return fail("statistics: a distance handle samples no thermodynamic ensemble");
     HIPCHK(hipSetDevice(h->device));
@@ -229,7 +444,11 @@ extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *
     const int PC = (int)h->obs.pat.n_cells;          // (no pattern spec: 0, likewise)
     const int EC = (int)h->obs.env.n_cells;          // (no environment spec: 0, likewise)
     char msg[320];
-    if (s->key != SMOLMC_STAT_BY_WALKER && s->key != SMOLMC_STAT_BY_STATE_POINT) {
+    if (bins && s->key != SMOLMC_STAT_BY_BIN) {
+        snprintf(msg, sizeof msg, "statistics: a binned record has key 2 (by bin), got %d", s->key);
+        return fail(msg);
+    }
+    if (!bins && s->key != SMOLMC_STAT_BY_WALKER && s->key != SMOLMC_STAT_BY_STATE_POINT) {
         snprintf(msg, sizeof msg, "statistics: key must be 0 (by walker) or 1 (by state point), got %d", s->key);
         return fail(msg);
     }
@@ -289,7 +508,25 @@ extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *
             return fail(msg);
         }
     }
-    const size_t nk = (size_t)h->R, L = (size_t)s->n_levels, B = (size_t)s->n_bins, P = (size_t)C * (C + 1) / 2;
+    if (bins) { // (the key is the row's value, not the walker: per-walker Wang-Landau windows do not matter)
+        if (s->n_levels != 0) {
+            snprintf(msg, sizeof msg, "statistics: a record keyed by bin keeps no blocking sums (successive rows of a key come "
+                     "from different walkers): n_levels must be 0, got %d", s->n_levels);
+            return fail(msg);
+        }
+        if (bins->n_keys < 1 || bins->n_keys > SMOLMC_MAX_STAT_KEYS) {
+            snprintf(msg, sizeof msg, "statistics: n_keys must be 1..%d, got %d", SMOLMC_MAX_STAT_KEYS, bins->n_keys);
+            return fail(msg);
+        }
+        if (!(bins->key_bin > 0.0) || !std::isfinite(bins->key_bin) || !std::isfinite(bins->key_min))
+            return fail("statistics: key_bin must be a positive finite number and key_min finite");
+        if (bins->key_column < 0 || bins->key_column >= C) {
+            snprintf(msg, sizeof msg, "statistics: key_column = %d is no index into the %d columns", bins->key_column, C);
+            return fail(msg);
+        }
+    }
+    const size_t nk = bins ? (size_t)bins->n_keys : (size_t)h->R;
+    const size_t L = (size_t)s->n_levels, B = (size_t)s->n_bins, P = (size_t)C * (C + 1) / 2;
     const size_t per_key = 8 * (3 + 3 * (size_t)C + P + 2 * L * C + L + B);
     if (nk * per_key > ((size_t)1 << 30)) {
         snprintf(msg, sizeof msg, "statistics: a record of %zu keys x %zu bytes is larger than 1 GiB", nk, per_key);
@@ -304,19 +541,24 @@ extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *
     S.PC = PC; S.n_pat_cols = n_pat_cols;
     S.EC = EC; S.n_env_cols = n_env_cols;
     S.hist_min = B ? s->hist_min : 0.0; S.hist_bin = B ? s->hist_bin : 1.0;
+    if (bins) {
+        S.key_column = bins->key_column; S.key_min = bins->key_min; S.key_bin = bins->key_bin;
+    }
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t o = at; at += up256(std::max<size_t>(bytes, 16)); return o; };
     const size_t o_n = take(nk * 8), o_under = take(nk * 8), o_over = take(nk * 8), o_shift = take(nk * C * 8),
                  o_s1 = take(nk * C * 8), o_s2 = take(nk * P * 8), o_has = take(nk * C * 8), o_pend = take(nk * L * C * 8),
-                 o_b2 = take(nk * L * C * 8), o_nb = take(nk * L * 8), o_hist = take(nk * B * 8);
+                 o_b2 = take(nk * L * C * 8), o_nb = take(nk * L * 8), o_hist = take(nk * B * 8), o_outside = take(16);
     S.record_bytes = at;
-    const size_t o_col = take((size_t)C * 4), o_w = take((size_t)s->n_weights * 8), o_ucnt = take(nk * (size_t)K * 4);
+    const size_t o_col = take((size_t)C * 4), o_w = take((size_t)s->n_weights * 8), o_ucnt = take((size_t)h->R * (size_t)K * 4),
+                 o_bcnt = take(bins ? nk * 4 : 0);
     HIPCHK(hipMalloc((void **)&S.arena, at));
     unsigned char *d = S.arena;
     S.n = (long long *)(d + o_n); S.under = (long long *)(d + o_under); S.over = (long long *)(d + o_over);
     S.shift = (double *)(d + o_shift); S.s1 = (double *)(d + o_s1); S.s2 = (double *)(d + o_s2); S.has = (uint64_t *)(d + o_has);
     S.pend = (double *)(d + o_pend); S.b2 = (double *)(d + o_b2); S.nb = (long long *)(d + o_nb); S.hist = (long long *)(d + o_hist);
     S.columns = (int32_t *)(d + o_col); S.weights = (double *)(d + o_w); S.u_counts = (int32_t *)(d + o_ucnt);
+    S.outside = (long long *)(d + o_outside); S.bin_cnt = (int32_t *)(d + o_bcnt);
     hipError_t e = hipMemset(S.arena, 0, at); // (an empty record is all zeros)
     if (e == hipSuccess) e = hipMemcpy(S.columns, s->columns, (size_t)C * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && s->n_weights) e = hipMemcpy(S.weights, s->weights, (size_t)s->n_weights * 8, hipMemcpyHostToDevice);
@@ -327,6 +569,35 @@ extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *
     }
     smolmc_stat_free(h);
     h->stats = S;
+    return 0;
+}
+
+extern "C" int smolmc_set_statistics(smolmc_handle *h, const smolmc_statistics *s) { return stat_set(h, s, nullptr); }
+
+extern "C" int smolmc_set_statistics_binned(smolmc_handle *h, const smolmc_statistics *s, int key_column, int n_keys,
+                                            double key_min, double key_bin) {
+    if (!s) return fail("statistics: null spec (smolmc_set_statistics removes a record)");
+    const StatBins bins = {key_column, n_keys, key_min, key_bin};
+    return stat_set(h, s, &bins);
+}
+
+extern "C" int smolmc_statistics_bins(smolmc_handle *h, int *key_column, int *n_keys, double *key_min, double *key_bin,
+                                      int64_t *key_under, int64_t *key_over) {
+    if (!h) return fail("null handle");
+    const SmolmcStat &S = h->stats;
+    const bool binned = S.n_keys && S.key == SMOLMC_STAT_BY_BIN;
+    long long outside[2] = {0, 0};
+    if (binned && (key_under || key_over)) {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpy(outside, S.outside, 16, hipMemcpyDeviceToHost));
+    }
+    if (key_column) *key_column = binned ? S.key_column : 0;
+    if (n_keys) *n_keys = binned ? S.n_keys : 0;
+    if (key_min) *key_min = binned ? S.key_min : 0.0;
+    if (key_bin) *key_bin = binned ? S.key_bin : 0.0;
+    if (key_under) *key_under = outside[0];
+    if (key_over) *key_over = outside[1];
     return 0;
 }
 
@@ -382,5 +653,17 @@ extern "C" int smolmc_debug_statistics_kernel_ms(smolmc_handle *h, float *ms) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipEventSynchronize(S.ev[1]));
     HIPCHK(hipEventElapsedTime(ms, S.ev[0], S.ev[1]));
+    return 0;
+}
+
+// the same for a binned record, per launch: ms[0] the key pass (mode 1), ms[1] the reduction per key (mode 2)
+extern "C" int smolmc_debug_statistics_bins_kernel_ms(smolmc_handle *h, float *ms) {
+    if (!h || !ms) return fail("null argument");
+    const SmolmcStat &S = h->stats;
+    if (!S.ev[0] || S.key != SMOLMC_STAT_BY_BIN) return fail("the binned statistics kernels have not been launched yet");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(S.ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, S.ev[0], S.ev[2]));
+    HIPCHK(hipEventElapsedTime(ms + 1, S.ev[2], S.ev[1]));
     return 0;
 }

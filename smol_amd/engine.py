@@ -70,6 +70,9 @@ SYMBOLS = {
     "smolmc_get_minima": (C.c_int, [_HP, _f64p, _f64p, _f64p, _i32p, _i32p, _i32p, _i64p, _u64p]),
     "smolmc_get_minima_companions": (C.c_int, [_HP, _i32p]),
     "smolmc_set_statistics": (C.c_int, [_HP, C.POINTER(capi.smolmc_statistics)]),
+    "smolmc_set_statistics_binned": (C.c_int, [_HP, C.POINTER(capi.smolmc_statistics), C.c_int, C.c_int, C.c_double, C.c_double]),
+    "smolmc_statistics_bins": (C.c_int, [_HP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "smolmc_statistics_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 4),
     "smolmc_update_statistics": (C.c_int, [_HP]),
     "smolmc_reset_statistics": (C.c_int, [_HP]),
@@ -840,11 +843,26 @@ class Engine:
     def set_statistics(self, spec):
         """The statistics record of this handle (smolmc_set_statistics): a ``statistics.Statistics``, or None to remove
         it.  A new spec starts an empty record.  The record lives as long as the handle: ``set_state`` and
-        ``discard_samples`` leave it alone."""
+        ``discard_samples`` leave it alone.  A spec keyed by bin (``Statistics.by_bin``) goes through
+        smolmc_set_statistics_binned, which refuses likewise blocking levels, ``n_keys`` outside 1..65536, a bin width that
+        is not positive and finite and a key column outside the columns."""
         # (what ``statistics.segments`` takes: F, then every family's size in force, in the table's order)
         shape = () if spec is None else (self.F,) + tuple(self._family_sizes(fam)[fam.stat[2]] for fam in FAMILIES)
-        self._set_spec(self._lib.smolmc_set_statistics, spec, None, *shape)
+        bins = None if spec is None else spec.c_bins()
+        if bins is None:
+            self._set_spec(self._lib.smolmc_set_statistics, spec, None, *shape)
+        else:
+            struct, keep = spec.c_struct(*shape)
+            self._chk(self._lib.smolmc_set_statistics_binned(self._h, C.byref(struct), *bins))
+            del keep
         self.statistics_spec = spec
+
+    def statistics_bins(self):
+        """(key_column, n_keys, key_min, key_bin, key_under, key_over) of the binned record in force, all zeros when the
+        record in force is not binned or none is set (smolmc_statistics_bins; waits for the handle's stream)."""
+        col, nk, kmin, kbin, under, over = C.c_int(), C.c_int(), C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
+        self._chk(self._lib.smolmc_statistics_bins(self._h, *[C.byref(x) for x in (col, nk, kmin, kbin, under, over)]))
+        return int(col.value), int(nk.value), float(kmin.value), float(kbin.value), int(under.value), int(over.value)
 
     def statistics_shape(self):
         """(n_keys, n_columns, n_levels, n_bins) in force, zeros when no record is set (smolmc_statistics_shape)."""
@@ -875,12 +893,19 @@ class Engine:
             self._h, _p(rec.n, C.c_int64), _p(rec.shift, C.c_double), _p(rec.s1, C.c_double), _p(rec.s2, C.c_double),
             _p(rec.has, C.c_uint64), _p(rec.pend, C.c_double), _p(rec.b2, C.c_double), _p(rec.nb, C.c_int64),
             _p(rec.hist, C.c_int64), _p(rec.under, C.c_int64), _p(rec.over, C.c_int64)))
+        if rec.spec.binned:
+            rec.key_under, rec.key_over = self.statistics_bins()[4:]
         return rec
 
     def statistics_kernel_ms(self):
         """Device time of the last statistics reduction in ms (HIP events; a measuring hook of the library, not part of
         the C-ABI)."""
         return self._kernel_ms("smolmc_debug_statistics_kernel_ms")
+
+    def statistics_bins_kernel_ms(self):
+        """Device times of the two launches of the last reduction of a binned record in ms, [the row keys, the reduction per
+        key] (HIP events; a measuring hook of the library, not part of the C-ABI)."""
+        return self._kernel_ms("smolmc_debug_statistics_bins_kernel_ms", 2)
 
     def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False,
                     minima=False, statistics=False, structure=False, connectivity=False, patterns=False, environments=False):

@@ -1909,6 +1909,8 @@ class Sampler:
         ``statistics``: a ``statistics.Statistics`` -- every recorded sample is offered to a statistics record kept on the
         device (``Sampler.statistics``): running moments, blocking sums and a histogram per walker or per state point,
         whether the trace is kept or not; count columns need ``observables`` too, intensity columns ``structure_factor``.
+        A spec keyed by bins of a column (``Statistics.by_bin``, ``by_composition``, ``on_wl_levels``) keeps moments and a
+        histogram per bin instead: microcanonical averages, averages per composition (``Sampler.wl_canonical``).
 
         ``structure_factor``: a ``structure.StructureFactor`` -- its amplitudes and intensities are evaluated on the device
         for every sample and traced as ``structure_amplitudes`` (Q, K, 2) int64 and ``structure_intensities`` (I,).
@@ -2627,6 +2629,34 @@ class Sampler:
             raise ValueError("wl_joined_entropy needs a sampler built with Sampler.from_ensemble(..., windows=)")
         ln_g, _, visited = self._wl_windows.join(self._get_engine().get_wl()["entropy"])
         return self._wl_windows.levels(), ln_g, visited
+
+    def wl_entropy_on_levels(self):
+        """ln g (L,) on the bin grid of a Wang-Landau sampler's statistics record (``Statistics.on_wl_levels``), NaN on the
+        levels nobody visited: ``wl_joined_entropy`` when windows are set, otherwise the mean over the kernels of their
+        entropies on the levels each of them visited."""
+        if not isinstance(self._kernels[0], WangLandau):
+            raise ValueError("wl_entropy_on_levels needs a Wang-Landau sampler")
+        if self._wl_windows is not None:
+            _, ln_g, visited = self.wl_joined_entropy()
+            return np.where(visited, ln_g, np.nan)
+        S = self._get_engine().get_wl()["entropy"]  # (R, L)
+        seen = S > 0
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(seen.any(axis=0), np.where(seen, S, 0.0).sum(axis=0) / seen.sum(axis=0), np.nan)
+
+    def wl_canonical(self, temperatures):
+        """(nT, C): the canonical averages of the record's columns at ``temperatures`` from ONE Wang-Landau run,
+        ``record.canonical(wl_entropy_on_levels(), temperatures)``.  The sampler's record must be keyed by the enthalpy on
+        the handle's own levels (``Statistics.on_wl_levels`` with the kernels' min_enthalpy and bin_size, or the windows'
+        global grid)."""
+        spec = self._statistics
+        if spec is None or not spec.binned or spec.columns[spec.key_column] != ("enthalpy",):
+            raise ValueError("wl_canonical needs a sampler built with statistics=Statistics.on_wl_levels(...)")
+        ln_g = self.wl_entropy_on_levels()
+        if len(ln_g) != spec.n_keys:
+            raise ValueError(f"the record has {spec.n_keys} keys, the Wang-Landau handle {len(ln_g)} levels: build the record with "
+                             "Statistics.on_wl_levels on the handle's own (min_enthalpy, bin_size, number of levels)")
+        return self.statistics.canonical(ln_g, temperatures)
 
     def run_exchange(self, n_exchanges, steps_between, initial_occupancies=None, thin_by=None, grid=None, windows=None,
                      sync_every=None, final_mod_factor=None):

@@ -1,4 +1,5 @@
-"""Running moments, blocking sums and a histogram of the recorded samples, per walker or per state point.
+"""Running moments, blocking sums and a histogram of the recorded samples, per walker, per state point or per bin of a
+column.
 
 This module is the DEFINITION: ``StatisticsRecord.offer`` in NumPy is what the device reduction (csrc/statistics.hip,
 ``SMOLMC_SAMPLE_STATISTICS`` and ``smolmc_update_statistics``) matches entry for entry.
@@ -22,6 +23,24 @@ both are permutations), and the key's accumulators take the rows in order:
 
 Every product and every sum is rounded on its own.  ``b2[l]`` is the sum of squares of the block SUMS of 2^l consecutive
 samples (of d), ``nb[l]`` the number of complete blocks; ``pend[l]`` a block of 2^l samples that waits for its partner.
+
+Keys by BINS of a column (``BY_BIN``, ``Statistics.by_bin``; SMOLMC_STAT_BY_BIN, smolmc_set_statistics_binned) gather
+several rows of a sample, or none: microcanonical averages A(E) with the enthalpy as the key, averages per composition
+with a kind count.  The spec names ``key_column`` (an index into ``columns``, like ``hist_column``), ``n_keys`` in
+1..65536, ``key_min`` and ``key_bin`` > 0.  The rows of an offer are taken SAMPLE BY SAMPLE, AND WITHIN A SAMPLE IN
+WALKER ORDER 0 .. R - 1.  For each row:
+
+    q = floor_divide(x[key_column] - key_min, key_bin)     ``bin_of``: the bin function of the Wang-Landau step and of
+                                                           the histogram above
+    q < 0:                            key_under += 1       one int64 for the whole record
+    q >= n_keys or x not finite:      key_over += 1
+        (neither row is offered to any key)
+    else: the row is offered to key q by the rule above: the key's first row is the shift, then s1, the s2 triangle, the
+        per-key histogram of hist_column with the key's under and over, and n += 1
+
+Blocking means nothing when successive rows of a key come from different walkers: this mode refuses ``n_levels != 0``; the
+record's arrays keep their shapes with L = 0.  Every product and every sum is rounded on its own, as above.  The
+walker-to-state-point map is not read.  The ORDER of a key's offers is part of the definition: sums of doubles depend on it.
 """
 
 from __future__ import annotations
@@ -33,12 +52,15 @@ import numpy as np
 from .minima import weighted_value
 
 BY_WALKER, BY_STATE_POINT = 0, 1   # SMOLMC_STAT_BY_WALKER, SMOLMC_STAT_BY_STATE_POINT
+BY_BIN = 2                         # SMOLMC_STAT_BY_BIN: bins of a column (Statistics.by_bin)
+MAX_KEYS = 65536                   # SMOLMC_MAX_STAT_KEYS
 MAX_COLUMNS = 32                   # SMOLMC_MAX_STAT_COLUMNS
 MAX_LEVELS = 32                    # SMOLMC_MAX_STAT_LEVELS
 MAX_BINS = 65536                   # SMOLMC_MAX_STAT_BINS
 KB = 8.617333262145e-5             # eV / K, SMOLMC_KB (smol/constants.py:4)
 
 _ARRAYS = ("n", "shift", "s1", "s2", "has", "pend", "b2", "nb", "hist", "under", "over")
+_MODE_NAMES = {BY_WALKER: "by walker", BY_STATE_POINT: "by state point", BY_BIN: "by bin"}
 
 # ---- column sources: symbolic, resolved against a handle's (F, K) by Statistics.sources -------------------------------
 ENTHALPY = ("enthalpy",)
@@ -124,9 +146,11 @@ _CHECKED = {"intensity": ("intensity", "intensities of the structure-factor", 1)
 
 class Statistics:
     """The spec of a record: how it is keyed, its columns, the weights of the ENERGY column, the blocking levels and the
-    histogram (``hist=(column, n_bins, hist_min, hist_bin)`` with ``column`` one of ``columns``)."""
+    histogram (``hist=(column, n_bins, hist_min, hist_bin)`` with ``column`` one of ``columns``).  A record keyed by bin
+    (``by_bin``) also has ``bins=(column, n_keys, key_min, key_bin)``, ``column`` one of ``columns``; a spec with key
+    ``BY_BIN`` and no ``bins`` is not binned, and the engine refuses it."""
 
-    def __init__(self, key=BY_WALKER, columns=(ENTHALPY,), weights=None, n_levels=0, hist=None):
+    def __init__(self, key=BY_WALKER, columns=(ENTHALPY,), weights=None, n_levels=0, hist=None, bins=None):
         self.key = int(key)
         self.columns = [tuple(c) if not isinstance(c, (int, np.integer)) else ("source", int(c)) for c in columns]
         self.weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
@@ -139,6 +163,14 @@ class Statistics:
             if col not in self.columns:
                 raise ValueError("the histogram's column must be one of the record's columns")
             self.hist_column, self.n_bins, self.hist_min, self.hist_bin = self.columns.index(col), int(n_bins), float(hmin), float(hbin)
+        self.key_column, self.n_keys, self.key_min, self.key_bin = 0, 0, 0.0, 0.0
+        self.binned = bins is not None
+        if bins is not None:
+            col, n_keys, kmin, kbin = bins
+            col = tuple(col) if not isinstance(col, (int, np.integer)) else ("source", int(col))
+            if col not in self.columns:
+                raise ValueError("the key's column must be one of the record's columns")
+            self.key_column, self.n_keys, self.key_min, self.key_bin = self.columns.index(col), int(n_keys), float(kmin), float(kbin)
         # (ranges, duplicates, sizes: the engine refuses them, naming the reason)
 
     @classmethod
@@ -148,6 +180,35 @@ class Statistics:
     @classmethod
     def by_state_point(cls, columns=(ENTHALPY,), **kw):
         return cls(BY_STATE_POINT, columns, **kw)
+
+    @classmethod
+    def by_bin(cls, key, n_keys, key_min, key_bin, columns=(ENTHALPY,), weights=None, hist=None):
+        """Keyed by ``n_keys`` bins of width ``key_bin`` from ``key_min`` of the column ``key``, one of ``columns``."""
+        return cls(BY_BIN, columns, weights, 0, hist, bins=(key, n_keys, key_min, key_bin))
+
+    @classmethod
+    def by_composition(cls, obs, kind_name_or_k, num_sites, columns=None, **kw):
+        """Keyed by the count of one kind of ``obs`` (an ``observables.Observables``): bins of width 1, ``num_sites + 1``
+        keys, key k holds the rows with k sites of that kind.  ``columns`` defaults to the count and the enthalpy; the
+        count is put in front when ``columns`` leaves it out."""
+        key = kind(obs, kind_name_or_k)
+        cols = [key, ENTHALPY] if columns is None else [tuple(c) if not isinstance(c, (int, np.integer)) else ("source", int(c))
+                                                        for c in columns]
+        if key not in cols:
+            cols = [key] + cols
+        return cls.by_bin(key, int(num_sites) + 1, 0.0, 1.0, cols, **kw)
+
+    @classmethod
+    def on_wl_levels(cls, min_enthalpy, bin_size, n_levels, columns=(ENTHALPY,), **kw):
+        """Keyed by the enthalpy on a Wang-Landau handle's own ``(min_enthalpy, bin_size)`` with ``n_levels`` keys (the
+        number of its levels, not blocking levels).  On a handle without windows key k IS Wang-Landau level k: both
+        sides apply the same function to the same numbers.  With per-walker windows the record uses this GLOBAL grid;
+        nothing is claimed about a walker's local level numbers.  The enthalpy is put in front of ``columns`` when they
+        leave it out."""
+        cols = [tuple(c) if not isinstance(c, (int, np.integer)) else ("source", int(c)) for c in columns]
+        if ENTHALPY not in cols:
+            cols = [ENTHALPY] + cols
+        return cls.by_bin(ENTHALPY, int(n_levels), float(min_enthalpy), float(bin_size), cols, **kw)
 
     n_columns = property(lambda self: len(self.columns))
     n_weights = property(lambda self: 0 if self.weights is None else len(self.weights))
@@ -232,6 +293,11 @@ class Statistics:
             self.hist_column, self.n_bins, self.hist_min, self.hist_bin)
         return s, keep
 
+    def c_bins(self):
+        """The extra scalars of smolmc_set_statistics_binned (key_column, n_keys, key_min, key_bin), or None for a spec
+        that is not binned (``connectivity.Connectivity.c_gates`` is the same idea)."""
+        return (self.key_column, self.n_keys, self.key_min, self.key_bin) if self.binned else None
+
 
 def bin_of(x, hist_min, hist_bin):
     """``floor_divide(x - hist_min, hist_bin)`` as float64: the exact floor division ``WLWindows.bins`` and the
@@ -242,10 +308,14 @@ def bin_of(x, hist_min, hist_bin):
 
 class StatisticsRecord:
     """The accumulators: n, under, over (n_keys,) int64; shift, s1 (n_keys, C); s2 (n_keys, C (C + 1) / 2); has (n_keys, C)
-    uint64; pend, b2 (n_keys, n_levels, C); nb (n_keys, n_levels) int64; hist (n_keys, n_bins) int64."""
+    uint64; pend, b2 (n_keys, n_levels, C); nb (n_keys, n_levels) int64; hist (n_keys, n_bins) int64.  A binned record
+    (``spec.binned``) takes ``n_keys`` from the spec and counts the rows outside its bins in ``key_under`` and ``key_over``
+    (ints; 0 in the other modes)."""
 
-    def __init__(self, spec, n_keys):
+    def __init__(self, spec, n_keys=None):
         self.spec = spec
+        if spec.binned:
+            n_keys = spec.n_keys
         nk, Cn, L, B = int(n_keys), spec.n_columns, spec.n_levels, spec.n_bins
         self.n = np.zeros(nk, dtype=np.int64)
         self.shift = np.zeros((nk, Cn))
@@ -258,8 +328,20 @@ class StatisticsRecord:
         self.hist = np.zeros((nk, B), dtype=np.int64)
         self.under = np.zeros(nk, dtype=np.int64)
         self.over = np.zeros(nk, dtype=np.int64)
+        self.key_under = 0
+        self.key_over = 0
 
     n_keys = property(lambda self: len(self.n))
+
+    def _not_binned(self, what):
+        if self.spec.binned:
+            raise ValueError(f"{what} is not defined for a record keyed by bin (mode {BY_BIN}, {_MODE_NAMES[BY_BIN]}): successive "
+                             "rows of a key come from different walkers and state points")
+
+    def _only_binned(self, what):
+        if not self.spec.binned:
+            raise ValueError(f"{what} needs a record keyed by bin (Statistics.by_bin), this one is keyed "
+                             f"{_MODE_NAMES.get(self.spec.key, self.spec.key)}")
 
     # ---- the definition ------------------------------------------------------------------------------------------
     def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None, connectivity=None, patterns=None,
@@ -267,6 +349,10 @@ class StatisticsRecord:
         """Offer samples (ns, R) -- or one sample (R,) -- in order.  ``key_of_row`` (R,) or (ns, R): the key of every
         row, a permutation of 0 .. R - 1 per sample (None: the walker).  Vectorised over the keys, a loop over samples."""
         spec = self.spec
+        if spec.binned:
+            if key_of_row is not None:
+                raise ValueError("a record keyed by bin takes the key of a row from its key column, not from key_of_row")
+            return self._offer_binned(enthalpy, features, counts, intensities, connectivity, patterns, environments)
         nk = self.n_keys
         H = np.asarray(enthalpy, dtype=np.float64).reshape(-1, nk)
         ns = len(H)
@@ -324,6 +410,59 @@ class StatisticsRecord:
             self.n += 1
         return self
 
+    def _offer_binned(self, enthalpy, features, counts, intensities, connectivity, patterns, environments):
+        """The rule of the module docstring for samples (ns, R) -- or one sample (R,): the rows in sample-major,
+        walker-minor order.  Vectorised over the keys: round j offers the j-th row of every key."""
+        spec = self.spec
+        if spec.n_levels:
+            raise ValueError("a record keyed by bin keeps no blocking sums: n_levels must be 0")
+        H = np.asarray(enthalpy, dtype=np.float64)
+        H = H.reshape(1, -1) if H.ndim < 2 else H.reshape(len(H), -1)
+        ns, R = H.shape
+
+        def rows_of(a, dtype=None, tail=(-1,)):
+            return None if a is None else np.asarray(a, dtype=dtype).reshape((ns, R) + tail)
+
+        x = spec.column_values(H, rows_of(features, np.float64), rows_of(counts), rows_of(intensities, np.float64),
+                               rows_of(connectivity, None, (-1, 24)), rows_of(patterns), rows_of(environments))
+        x = x.reshape(ns * R, spec.n_columns)  # (row number = sample * R + walker: the order of the offers)
+        xk = x[:, spec.key_column]
+        q = bin_of(xk, spec.key_min, spec.key_bin)
+        bad = ~np.isfinite(xk) | np.isnan(q)
+        under = ~bad & (q < 0)
+        over = bad | (q >= spec.n_keys)
+        self.key_under += int(under.sum())
+        self.key_over += int(over.sum())
+        ok = ~(under | over)
+        x, key = x[ok], q[ok].astype(np.int64)
+        # the rank of a row among the rows of its key, in row order
+        order = np.argsort(key, kind="stable")
+        sk = key[order]
+        start = np.flatnonzero(np.r_[True, sk[1:] != sk[:-1]]) if len(sk) else np.zeros(0, dtype=np.int64)
+        rank = np.empty(len(key), dtype=np.int64)
+        rank[order] = np.arange(len(sk)) - np.repeat(start, np.diff(np.r_[start, len(sk)]))
+        ia, ib = np.triu_indices(spec.n_columns)
+        for j in range(int(rank.max()) + 1 if len(rank) else 0):
+            sel = rank == j
+            k, xj = key[sel], x[sel]  # (every key at most once)
+            first = self.n[k] == 0
+            self.shift[k[first]] = xj[first]
+            d = xj - self.shift[k]
+            self.s1[k] = self.s1[k] + d
+            self.s2[k] = self.s2[k] + d[:, ia] * d[:, ib]
+            if spec.n_bins:
+                xv = xj[:, spec.hist_column]
+                qh = bin_of(xv, spec.hist_min, spec.hist_bin)
+                hbad = ~np.isfinite(xv) | np.isnan(qh)
+                hunder = ~hbad & (qh < 0)
+                hover = hbad | (qh >= spec.n_bins)
+                self.under[k] += hunder
+                self.over[k] += hover
+                hok = ~(hunder | hover)
+                self.hist[k[hok], qh[hok].astype(np.int64)] += 1
+            self.n[k] += 1
+        return self
+
     # ---- what users do with a record -------------------------------------------------------------------------------
     def _full_s2(self):
         Cn = self.spec.n_columns
@@ -368,10 +507,11 @@ class StatisticsRecord:
 
     def blocking(self):
         """Per level l the error estimate of the mean from blocks of 2^l samples: (error (n_keys, L, C), its own
-        uncertainty (n_keys, L, C), nb (n_keys, L)).  The block means are the block sums / 2^l; their variance (ddof = 0)
+        uncertainty (n_keys, L, C), nb (n_keys, L)); a ValueError for a record keyed by bin.  The block means are the block sums / 2^l; their variance (ddof = 0)
         is b2 / (4^l nb) - m_l^2, with m_l the mean over the samples of the nb complete blocks: s1 less the blocks that
         still wait below level l, over nb 2^l.  The error is sqrt(var / (nb - 1)), its uncertainty
         error / sqrt(2 (nb - 1)) (Flyvbjerg & Petersen, eq. 28).  NaN where nb < 2."""
+        self._not_binned("blocking")
         L = self.spec.n_levels
         size = (2.0 ** np.arange(L))[None, :, None]
         nb = self.nb[:, :, None].astype(np.float64)
@@ -391,6 +531,7 @@ class StatisticsRecord:
         next one by more than that level's own uncertainty (err[l + 1] - err[l] <= unc[l]), among levels with at least
         ``min_blocks`` blocks; when no level qualifies, the largest estimate among the levels with ``min_blocks`` blocks
         (a lower bound: the run is too short for a plateau).  Without blocking levels: the naive sqrt(var / (n - 1))."""
+        self._not_binned("standard_error")
         nk, Cn, L = self.n_keys, self.spec.n_columns, self.spec.n_levels
         with np.errstate(invalid="ignore", divide="ignore"):
             naive = np.sqrt(self.variance() / (self.n[:, None] - 1.0))
@@ -414,6 +555,7 @@ class StatisticsRecord:
     def autocorrelation_time(self, min_blocks=16):
         """(n_keys, C): the integrated autocorrelation time in samples, tau = (standard_error / naive error)^2 / 2
         (0.5 for uncorrelated samples)."""
+        self._not_binned("autocorrelation_time")
         with np.errstate(invalid="ignore", divide="ignore"):
             naive = np.sqrt(self.variance() / (self.n[:, None] - 1.0))
             return 0.5 * (self.standard_error(min_blocks) / naive) ** 2
@@ -423,12 +565,21 @@ class StatisticsRecord:
         """One record from those of several ranks or of the parts of a resumed run that hold the SAME keys: the pairwise
         merge of Chan et al. of n / shift / s1 / s2 (the second record's sums are moved to the first one's shift) and the
         sum of the histograms.  The blocking arrays are NOT merged (a block of 2^l samples does not span two records):
-        the result has n_levels = 0."""
+        the result has n_levels = 0.  Binned records of ONE spec merge key by key in the same way and their outside
+        counters add; records of different modes, or binned ones of different bins, are refused."""
         records = list(records)
         a = records[0]
+        for b in records[1:]:
+            if b.spec.key != a.spec.key or b.spec.binned != a.spec.binned:
+                raise ValueError(f"combine: records of different key modes ({_MODE_NAMES.get(a.spec.key, a.spec.key)} and "
+                                 f"{_MODE_NAMES.get(b.spec.key, b.spec.key)})")
+            if a.spec.binned and a.spec.c_bins() != b.spec.c_bins():
+                raise ValueError(f"combine: binned records of different bins ({a.spec.c_bins()} and {b.spec.c_bins()})")
         spec = Statistics(a.spec.key, a.spec.columns, a.spec.weights, 0,
-                          None if not a.spec.n_bins else (a.spec.columns[a.spec.hist_column], a.spec.n_bins, a.spec.hist_min, a.spec.hist_bin))
+                          None if not a.spec.n_bins else (a.spec.columns[a.spec.hist_column], a.spec.n_bins, a.spec.hist_min, a.spec.hist_bin),
+                          bins=None if not a.spec.binned else (a.spec.columns[a.spec.key_column],) + a.spec.c_bins()[1:])
         out = cls(spec, a.n_keys)
+        out.key_under, out.key_over = a.key_under, a.key_over
         for f in ("n", "shift", "s1", "s2", "hist", "under", "over"):
             setattr(out, f, getattr(a, f).copy())
         ia, ib = np.triu_indices(spec.n_columns)
@@ -444,12 +595,16 @@ class StatisticsRecord:
             out.hist = out.hist + b.hist
             out.under = out.under + b.under
             out.over = out.over + b.over
+            out.key_under += b.key_under
+            out.key_over += b.key_over
         return out
 
     def reweight(self, temperature_from, temperature_to):
         """Single-histogram reweighting of the histogram's column (the enthalpy) from ``temperature_from`` to
         ``temperature_to``: (mean (n_keys,), variance (n_keys,)) of the bin centres under the weights
-        hist x exp(-(beta_to - beta_from) E), the exponent shifted by its maximum."""
+        hist x exp(-(beta_to - beta_from) E), the exponent shifted by its maximum.  A ValueError for a record keyed by
+        bin (its rows have no one temperature): ``canonical`` is what such a record offers."""
+        self._not_binned("reweight")
         spec = self.spec
         if not spec.n_bins:
             raise ValueError("the record keeps no histogram")
@@ -466,11 +621,81 @@ class StatisticsRecord:
             var = (w * (centre[None, :] - mean[:, None]) ** 2).sum(axis=1) / z
         return mean, var
 
+    # ---- binned records: microcanonical averages and what follows from them with ln g ------------------------------
+    def key_edges(self):
+        """(n_keys + 1,): key k holds the rows with edges[k] <= x[key_column] < edges[k + 1] (up to the rounding of the
+        exact floor division)."""
+        self._only_binned("key_edges")
+        return self.spec.key_min + np.arange(self.n_keys + 1) * self.spec.key_bin
+
+    def key_centres(self):
+        """(n_keys,): the middle of every key's bin."""
+        self._only_binned("key_centres")
+        return self.spec.key_min + (np.arange(self.n_keys) + 0.5) * self.spec.key_bin
+
+    def microcanonical(self):
+        """(n_keys, C): the mean of every column over the rows of a key, A(E) when the key is the enthalpy; NaN where
+        n == 0."""
+        self._only_binned("microcanonical")
+        return self.mean()
+
+    def microcanonical_covariance(self):
+        """(n_keys, C, C): the population covariance of the columns within a key; NaN where n == 0."""
+        self._only_binned("microcanonical_covariance")
+        return self.covariance()
+
+    def _canonical_weights(self, ln_g, temperatures, level_values):
+        """(use (n_keys,) bool, E (n_used,), w (nT, n_used) normalised): the keys with rows and a finite ln g, their
+        energies and their weights exp(ln g_k - beta E_k) / Z at every temperature, by log-sum-exp."""
+        ln_g = np.asarray(ln_g, dtype=np.float64).reshape(-1)
+        if len(ln_g) != self.n_keys:
+            raise ValueError(f"ln_g has {len(ln_g)} entries, the record {self.n_keys} keys")
+        use = (self.n > 0) & np.isfinite(ln_g)
+        if not use.any():
+            raise ValueError("no key has both rows and a finite ln g")
+        if ENTHALPY in self.spec.columns:
+            E = self.mean()[use, self.spec.columns.index(ENTHALPY)]
+        elif level_values is not None:
+            E = np.asarray(level_values, dtype=np.float64).reshape(-1)[use]
+        else:
+            E = self.key_centres()[use]
+        T = np.atleast_1d(np.asarray(temperatures, dtype=np.float64))
+        beta = 1.0 / (KB * T)
+        logw = ln_g[use][None, :] - beta[:, None] * (E - E.min())[None, :]
+        logw = logw - logw.max(axis=1, keepdims=True)
+        w = np.exp(logw)
+        return use, E, w / w.sum(axis=1, keepdims=True)
+
+    def canonical(self, ln_g, temperatures, level_values=None):
+        """(nT, C): <x>_T = sum_k xbar_k exp(ln g_k - beta E_k) / sum_k exp(ln g_k - beta E_k) over the keys with n > 0
+        and a finite ``ln_g`` (n_keys,), by log-sum-exp.  xbar_k is ``microcanonical()``; E_k is the key's mean enthalpy
+        when ``ENTHALPY`` is a column, otherwise ``level_values`` (n_keys,) or, without them, the bin centre.  The key is
+        meant to be the enthalpy (``on_wl_levels``) and ``ln_g`` the density of states on the same bins, e.g. a
+        Wang-Landau entropy."""
+        self._only_binned("canonical")
+        use, _, w = self._canonical_weights(ln_g, temperatures, level_values)
+        return w @ self.mean()[use]
+
+    def canonical_heat_capacity(self, ln_g, temperatures):
+        """(nT,): var_T(H) / (kB T^2) with var_T(H) = sum_k w_k (var_k + (E_k - <E>)^2): the second moment of the enthalpy
+        WITHIN every key plus the spread of the keys' means.  Needs the ``ENTHALPY`` column."""
+        self._only_binned("canonical_heat_capacity")
+        c = self._column(ENTHALPY)
+        use, E, w = self._canonical_weights(ln_g, temperatures, None)
+        T = np.atleast_1d(np.asarray(temperatures, dtype=np.float64))
+        e = E - E.min()
+        mean = w @ e
+        within = self.variance()[use, c]
+        var = (w * (within[None, :] + (e[None, :] - mean[:, None]) ** 2)).sum(axis=1)
+        return var / (KB * T * T)
+
     def equals(self, other):
-        return all(np.array_equal(getattr(self, f), getattr(other, f), equal_nan=True) for f in _ARRAYS)
+        return (all(np.array_equal(getattr(self, f), getattr(other, f), equal_nan=True) for f in _ARRAYS)
+                and (self.key_under, self.key_over) == (other.key_under, other.key_over))
 
     def copy(self):
         out = StatisticsRecord(self.spec, self.n_keys)
         for f in _ARRAYS:
             setattr(out, f, getattr(self, f).copy())
+        out.key_under, out.key_over = self.key_under, self.key_over
         return out
