@@ -54,7 +54,20 @@ __device__ __forceinline__ float wave_sum_f32_uniform(float v) {
                  : "=s"(total), "+v"(v));
     return total;
 }
-
+// The same sum left where the reduction ends: the total is in lane 63 ONLY (the other lanes hold partial sums).  For a
+// caller that compares it against scalars and reads bit 63 of the compare mask -- no v_readlane, none of its wait states.
+__device__ __forceinline__ float wave_sum_f32_lane63(float v) {
+    v = dpp_add_f32<0xB1>(v);
+    v = dpp_add_f32<0x4E>(v);
+    v = dpp_add_f32<0x141>(v);
+    v = dpp_add_f32<0x140>(v);
+    asm volatile("s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
+                 : "+v"(v));
+    return v;
+}
 
 // sum over the changeable sites k != s of q(k, occ_k) * G[s][k] (lane partial), eight sites
 // per lane in flight so that the dependent latencies (index -> LDS species byte -> charge)
@@ -391,6 +404,10 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     // decision below).  Measured per shape: the flip kernels lost 3-7 % with the select decision and keep the parent's
     // form; the chemical-potential and OCC 6 kernels are not measured and keep it too (NOTES.md)
     constexpr bool STRAIGHT = ROWS && STEP == SMOLMC_STEP_SWAP && OCC == 0 && !HAS_MU;
+    // TAIL_AHEAD: the straight form advances the lane indices and the chunk counter in the middle of the step (see the
+    // second flip).  Measured per shape: 0.4 % on the headline, outside its run-to-run spread; neutral on config 12; the
+    // rows = 11 kernel (config 1) did not gain and keeps its bookkeeping at the bottom of the step (NOTES.md)
+    constexpr int TAIL_AHEAD = (STRAIGHT && MM == 21) ? 1 : 0;
     // (Ewald, replay, the KF tables and Wang-Landau all use the site NUMBER, which the ROWS variants do not carry)
     static_assert(!ROWS || (SOLO && NSLOT == 2 && EWX == 0 && !REPLAY && KF == 0 && !WL && !BIAS), "solo rows: plain Metropolis, solo layout");
     // EWM: 0 = no Ewald term, 1 = compact Ewald with per-proposal row sums, 2 = potential field in
@@ -686,6 +703,11 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         const unsigned long long chunk_end = step + chunk;
         int l4 = (int)(step & 15ull) * 4;
         int l64 = (int)(step & 63ull); // lane of this step's acceptance uniform / thresholds
+        // STRAIGHT only, every one set anew in each step: the step's thresholds as scalars, the partner's address as a VGPR
+        // and the outcome (all ones: accepted).  Declared out here: a declaration inside the step, even one that is dead in
+        // a kernel, renumbers the scalar registers of the second-round fallback in 14 swap kernels of other units
+        float tlo_s = 0.0f, thi_s = 0.0f;
+        uint32_t va2 = 0u, okm = 0u;
         do {
         // site of the next step (depends only on random words; its index row is fetched below)
         __builtin_amdgcn_s_setprio(1); // wave priority rises through the step, see the decision below
@@ -710,6 +732,12 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         } else {
             s1n = (int)rdlane((uint32_t)nsite, l4);
             a1n = (int)rdlane((uint32_t)naddr, l4);
+        }
+        // STRAIGHT: this step's thresholds as scalars, fetched here so that they issue in the shadow of the two LDS reads
+        // below (nothing of the step's chain waits for them; the decision at the bottom finds them ready)
+        if constexpr (STRAIGHT) {
+            tlo_s = __uint_as_float(rdlane(__float_as_uint(thr_lo), l64));
+            thi_s = __uint_as_float(rdlane(__float_as_uint(thr_hi), l64));
         }
         // LDS address of site 1 as a VGPR, made once per step (the compiler would re-make the
         // SGPR -> VGPR move in every block that touches the site)
@@ -929,6 +957,36 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             // LDS (undone below on rejection) instead of patching every gathered value
             occ_st<SOLO>(occ, va1, (uint8_t)n1); // every lane stores the same byte: no exec juggling
             const uint32_t pair2 = (uint32_t)o2 * snt8 + (uint32_t)n2 * nt8;
+            if constexpr (TAIL_AHEAD != 0) {
+                // the same gathers, table reads and arithmetic as below, in the same order, with the step's scalar
+                // bookkeeping between the issue of the gathers and the first wait for one: the wave stands still
+                // there for an LDS round trip, so the lane indices and the chunk counter of the NEXT step and the VGPR
+                // copy of the partner's address (for the store behind the decision) cost nothing, and the tail of the
+                // step -- decision, store, back-edge -- is that much shorter.  l64 is therefore one ahead from here on
+                // (exact_decision() on its cold path takes one off); l4 and chunk have no later reader in the step
+                uint32_t g[NSLOT][MMX];
+#pragma unroll
+                for (int it = 0; it < NSLOT; ++it) {
+#pragma unroll
+                    for (int m = 0; m < lean_mm_of(MM, it); ++m) g[it][m] = (uint32_t)occ_ld<SOLO>(occ, bounded(row_addr<SOLO, NW>(row2, lean_row_off(MM, it) + m), (uint32_t)P.Nlds));
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                // (pinned: the compiler otherwise sinks the three adds back into the block behind the decision)
+                l4 = (int)opaque_u32((uint32_t)l4 + 4u);
+                l64 = (int)opaque_u32((uint32_t)l64 + 1u);
+                chunk = opaque_u32(chunk - 1u);
+                va2 = (uint32_t)a2;
+                asm volatile("" : "+v"(va2));
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int it = 0; it < NSLOT; ++it) {
+                    uint32_t a = dp[it];
+#pragma unroll
+                    for (int m = 0; m < lean_mm_of(MM, it); ++m) a += __umul24(st8[it][m], g[it][m]);
+                    d1[it] -= SMOLMC_LDS_F64(a);
+                    e = fma(wgt[it], d1[it], e);
+                }
+            } else
 #pragma unroll
             for (int it = 0; it < NSLOT; ++it) {
                 uint32_t a = DIFF ? dp[it] : doff8[it];
@@ -1000,8 +1058,8 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             if (HAS_MU) dH -= dMu;
             // -------- accept (metropolis.py:31-49) --------
             const double lu = REPLAY ? lu_rp
-                                     : __hiloint2double((int)rdlane((uint32_t)__double2hiint(logu), l64),
-                                                        (int)rdlane((uint32_t)__double2loint(logu), l64));
+                                     : __hiloint2double((int)rdlane((uint32_t)__double2hiint(logu), l64 - TAIL_AHEAD),
+                                                        (int)rdlane((uint32_t)__double2loint(logu), l64 - TAIL_AHEAD));
             // (the ballots make the wave-uniform decision visibly uniform to the compiler:
             // scalar branch, uniform counters in SGPRs)
             if (!WL) {
@@ -1106,27 +1164,38 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         __builtin_amdgcn_s_setprio(3);
         if (FAST && !BIAS) {
             const float ef = (float)((HAS_MU && lane == 0) ? e - dMu : e);
-            const float S = wave_sum_f32_uniform(ef);
-            const unsigned long long bit = 1ull << (REPLAY ? 0 : l64); // (replay: the thresholds are uniform)
-            const bool ca = (__ballot(S < thr_lo) & bit) != 0ull;
-            const bool cr = (__ballot(S > thr_hi) & bit) != 0ull;
             if constexpr (STRAIGHT) {
+                // the sum stays in lane 63 of a VGPR and is compared there with this step's thresholds, scalars since
+                // the head of the step: the decision is bit 63 of the two compare masks, a constant bit
+                const float Sv = wave_sum_f32_lane63(ef);
+                // (the high words go through a register pin: a sign test of the 64-bit mask is a VALU compare here)
+                const uint32_t ha = opaque_u32((uint32_t)(__ballot(Sv < tlo_s) >> 32));
+                const uint32_t hr = opaque_u32((uint32_t)(__ballot(Sv > thi_s) >> 32));
                 // decision by select: both outcomes end in the same store of the first site's species (accepted
                 // swap: at the partner; rejected: back at site 1) and in the SELACC updates below; the exact path is
                 // the one branch, out of line
-                bool ok = ca;
-                if (__builtin_expect(!(ca || cr), 0)) ok = exact_decision();
-                sel_hi = ok ? 0x3ff00000u : 0u;
+                // (the outcome as a word of ones or zeros: the high word of sel, the store's address and the accept
+                // counter are one instruction each from it, with no mask pair rebuilt from a flag)
+                okm = (uint32_t)((int)ha >> 31);
+                if (__builtin_expect((int)(ha | hr) >= 0, 0)) okm = 0u - (uint32_t)uni((int)exact_decision()); // (uni: the flag comes back as a lane mask)
+                okm = opaque_u32(okm); // (pinned: known to be 0 / -1, the bit select of the address becomes a mask pair again)
+                sel_hi = okm & 0x3ff00000u;
                 // (the store takes the 32-bit value: stored as the byte the read returned, the read has a second user
                 // and the compiler widens it with a v_and 0xff at the head of the step's dependency chain)
                 uint32_t vst = (uint32_t)vo1;
                 asm("" : "+v"(vst));
-                occ_st<SOLO>(occ, ok ? (uint32_t)a2 : va1, (uint8_t)vst);
-            } else
+                const uint32_t vb = TAIL_AHEAD ? va2 : (uint32_t)a2;
+                occ_st<SOLO>(occ, (vb & okm) | (va1 & ~okm), (uint8_t)vst);
+            } else {
+            const float S = wave_sum_f32_uniform(ef);
+            const unsigned long long bit = 1ull << (REPLAY ? 0 : l64); // (replay: the thresholds are uniform)
+            const bool ca = (__ballot(S < thr_lo) & bit) != 0ull;
+            const bool cr = (__ballot(S > thr_hi) & bit) != 0ull;
             if (ca) on_accept();
             else if (cr) on_reject();
             else if (exact_decision()) on_accept();
             else on_reject();
+            }
         } else {
             accepted = exact_decision();
             if (accepted) on_accept();
@@ -1137,6 +1206,8 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             const double sel = __hiloint2double((int)sh, 0);
 #pragma unroll
             for (int it = 0; it < NSLOT; ++it) acc[it] = fma(sel, d1[it], acc[it]);
+            if constexpr (STRAIGHT) nacc_add -= okm;
+            else
             nacc_add += sh >> 29; // 0x3ff00000 >> 29 == 1
         }
         s1 = s1n;
@@ -1186,9 +1257,12 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             }
         }
 
+        if constexpr (!TAIL_AHEAD) {
         l4 += 4;
         l64 += 1;
-        } while (--chunk != 0u);
+        --chunk;
+        }
+        } while (chunk != 0u);
         step = chunk_end;
 
         if (smp_countdown == 0) { // record one thinned sample of this walker
