@@ -1,6 +1,7 @@
 // mc_lean.h -- lean Metropolis / Wang-Landau kernel, TableFlip kernel and their launch templates.
 #pragma once
 #include "smolmc_common.h"
+#include "rows_thresholds.h"
 
 // xor-butterfly inside 16-lane rows (DPP), then gfx950 permlane16/32 swaps: 22 VALU
 // instructions, the total ends up in every lane.
@@ -586,6 +587,12 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
     int cand[4] = {0, 0, 0, 0}, canda[4] = {0, 0, 0, 0}; // candidate sites / their LDS addresses
     double vGc = 0.0; // Ewald field mode: prefetched cross terms of the first-round candidates
     double logu = 0.0; // log of the acceptance uniform of step (step & ~63) + lane
+    // STRAIGHT: no 64-step batch.  The thresholds come from the 16-step batch (lane 4k: step batch_base + k, see
+    // rows_thresholds.h) and the exact path takes the raw words of the acceptance uniform from there.  (Declared out here,
+    // like the scalars of the step below: see the note there)
+    uint32_t W2 = 0, W3 = 0;
+    const float thr_cf = STRAIGHT ? rows_threshold_scale(inv_nbeta) : 0.0f;
+    const float thr_ef = STRAIGHT ? rows_threshold_eps(P.fast_eps) : 0.0f;
     unsigned long long batch64_base = ~0ull;
     unsigned long long batch_base = ~0ull;
     constexpr int ROW = lean_row_len(MM, NSLOT); // entries per lane per site (u16, SOLO: u32)
@@ -663,6 +670,14 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             // steps at once, lane l <-> step (step & ~63) + l, from one more Philox block per lane
             // (block 0 of that step; the 16-step batches recompute the same words for the
             // proposals) -- a log per 16-step batch would use 16 of its 64 lanes
+            if constexpr (STRAIGHT) {
+                // no second evaluation of block 0 and no float64 log per step: the two float32 thresholds from word 2
+                // alone, a sound enclosure of thr -+ fast_eps (all lanes compute, lanes 4k are read); the exact path
+                // forms log(u) from the two raw words when it runs (about one step in 1e5)
+                W2 = o.w[2];
+                W3 = o.w[3];
+                rows_thresholds(o.w[2], thr_cf, thr_ef, thr_lo, thr_hi);
+            } else
             if ((step & ~63ull) != batch64_base) {
                 batch64_base = step & ~63ull;
                 const unsigned long long s64 = batch64_base + (unsigned)lane;
@@ -736,8 +751,8 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
         // STRAIGHT: this step's thresholds as scalars, fetched here so that they issue in the shadow of the two LDS reads
         // below (nothing of the step's chain waits for them; the decision at the bottom finds them ready)
         if constexpr (STRAIGHT) {
-            tlo_s = __uint_as_float(rdlane(__float_as_uint(thr_lo), l64));
-            thi_s = __uint_as_float(rdlane(__float_as_uint(thr_hi), l64));
+            tlo_s = __uint_as_float(rdlane(__float_as_uint(thr_lo), l4));
+            thi_s = __uint_as_float(rdlane(__float_as_uint(thr_hi), l4));
         }
         // LDS address of site 1 as a VGPR, made once per step (the compiler would re-make the
         // SGPR -> VGPR move in every block that touches the site)
@@ -962,8 +977,8 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                 // bookkeeping between the issue of the gathers and the first wait for one: the wave stands still
                 // there for an LDS round trip, so the lane indices and the chunk counter of the NEXT step and the VGPR
                 // copy of the partner's address (for the store behind the decision) cost nothing, and the tail of the
-                // step -- decision, store, back-edge -- is that much shorter.  l64 is therefore one ahead from here on
-                // (exact_decision() on its cold path takes one off); l4 and chunk have no later reader in the step
+                // step -- decision, store, back-edge -- is that much shorter.  l4 is therefore one step ahead from here on
+                // (exact_decision() on its cold path takes it back); chunk has no later reader in the step
                 uint32_t g[NSLOT][MMX];
 #pragma unroll
                 for (int it = 0; it < NSLOT; ++it) {
@@ -973,7 +988,6 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                 __builtin_amdgcn_sched_barrier(0);
                 // (pinned: the compiler otherwise sinks the three adds back into the block behind the decision)
                 l4 = (int)opaque_u32((uint32_t)l4 + 4u);
-                l64 = (int)opaque_u32((uint32_t)l64 + 1u);
                 chunk = opaque_u32(chunk - 1u);
                 va2 = (uint32_t)a2;
                 asm volatile("" : "+v"(va2));
@@ -1057,7 +1071,9 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
             }
             if (HAS_MU) dH -= dMu;
             // -------- accept (metropolis.py:31-49) --------
-            const double lu = REPLAY ? lu_rp
+            // (STRAIGHT: the caller has left log(u) in lu_rp.  Through a variable this lambda captures anyway: one more
+            // capture renumbers the registers of the swap kernels with an Ewald term in other units)
+            const double lu = (REPLAY || STRAIGHT) ? lu_rp
                                      : __hiloint2double((int)rdlane((uint32_t)__double2hiint(logu), l64 - TAIL_AHEAD),
                                                         (int)rdlane((uint32_t)__double2loint(logu), l64 - TAIL_AHEAD));
             // (the ballots make the wave-uniform decision visibly uniform to the compiler:
@@ -1177,7 +1193,12 @@ __launch_bounds__(256) mc_lean_kernel(const LeanParams P) {
                 // (the outcome as a word of ones or zeros: the high word of sel, the store's address and the accept
                 // counter are one instruction each from it, with no mask pair rebuilt from a flag)
                 okm = (uint32_t)((int)ha >> 31);
-                if (__builtin_expect((int)(ha | hr) >= 0, 0)) okm = 0u - (uint32_t)uni((int)exact_decision()); // (uni: the flag comes back as a lane mask)
+                if (__builtin_expect((int)(ha | hr) >= 0, 0)) {
+                    // log(u) of this step, formed only here: the words the 64-step batch of the other kernels takes, from
+                    // lane 4k of the 16-step batch -- the same uniform and the same log, bit for bit
+                    lu_rp = log(philox_u53(rdlane(W2, l4 - 4 * TAIL_AHEAD), rdlane(W3, l4 - 4 * TAIL_AHEAD)));
+                    okm = 0u - (uint32_t)uni((int)exact_decision()); // (uni: the flag comes back as a lane mask)
+                }
                 okm = opaque_u32(okm); // (pinned: known to be 0 / -1, the bit select of the address becomes a mask pair again)
                 sel_hi = okm & 0x3ff00000u;
                 // (the store takes the 32-bit value: stored as the byte the read returned, the read has a second user

@@ -7,6 +7,7 @@
 // (one wave) sweeps its own slice of phi with na = na_list[b], on synthetic tables.  Every instantiation below is
 // one that a kernel calls; the call site stands beside it.
 #include "smolmc_common.h"
+#include "rows_thresholds.h" // (second probe, at the bottom: the float32 thresholds of the straight rows swap kernels)
 
 thread_local std::string smolmc_g_err; // (smolmc_common.h's error plumbing: unused here, defined for the linker)
 
@@ -194,6 +195,55 @@ int smolmc_probe_sweep(int variant, int lds, int nblocks, int na_min, int na_max
     if (e != hipSuccess) return (int)e;
     e = hipDeviceSynchronize();
     return (int)e;
+}
+
+} // extern "C"
+
+// ---- the float32 thresholds of the straight rows swap kernels (rows_thresholds.h; tests/test_gpu_rows_thresholds.py) ----
+// The kernels below call the functions mc_lean_kernel calls, on words the test supplies; the walker's constants are
+// derived as the kernel derives them (nbeta = -beta, inv_nbeta = 1 / nbeta).
+__global__ __launch_bounds__(256) void probe_rows_thresholds_kernel(const uint32_t *w2, long long n, double beta,
+                                                                    double fast_eps, float *lo, float *hi) {
+    const double nbeta = -beta;
+    const double inv_nbeta = 1.0 / nbeta;
+    const float c_f = rows_threshold_scale(inv_nbeta), eps_f = rows_threshold_eps(fast_eps);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        float a, b;
+        rows_thresholds(w2[i], c_f, eps_f, a, b);
+        lo[i] = a;
+        hi[i] = b;
+    }
+}
+
+__global__ __launch_bounds__(256) void probe_rows_log2_kernel(uint32_t first, long long n, int scaled, float *out) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        out[i] = rows_log2_hw(first + (uint32_t)i, scaled);
+}
+
+extern "C" {
+
+// W of rows_thresholds.h (ulp of the hardware log2 the thresholds are widened by) and the measured worst case it rests on
+int smolmc_probe_rows_widen_ulp(void) { return SMOLMC_ROWS_LOG2_WIDEN_ULP; }
+double smolmc_probe_rows_measured_ulp(void) { return (double)SMOLMC_ROWS_LOG2_MEASURED_ULP; }
+
+// lo[i], hi[i] = the thresholds of a step whose acceptance uniform begins with the word w2[i] (device buffers of n entries)
+int smolmc_probe_rows_thresholds(const uint32_t *w2, long long n, double beta, double fast_eps, float *lo, float *hi) {
+    if (!w2 || !lo || !hi || n <= 0) return -1;
+    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(probe_rows_thresholds_kernel, dim3(blocks), dim3(256), 0, 0, w2, n, beta, fast_eps, lo, hi);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return (int)hipDeviceSynchronize();
+}
+
+// out[i] = v_log_f32 of the integer first + i (scaled: of (first + i) 2^-24), i < n (device buffer of n floats)
+int smolmc_probe_rows_log2(uint32_t first, long long n, int scaled, float *out) {
+    if (!out || n <= 0 || (unsigned long long)first + (unsigned long long)n > (1ull << 24) + 1ull) return -1;
+    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(probe_rows_log2_kernel, dim3(blocks), dim3(256), 0, 0, first, n, scaled, out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return (int)hipDeviceSynchronize();
 }
 
 } // extern "C"
