@@ -620,6 +620,37 @@ int smolmc_reset_statistics(smolmc_handle *h);
  * Any pointer may be NULL. */
 int smolmc_get_statistics(smolmc_handle *h, int64_t *n, double *shift, double *s1, double *s2, uint64_t *has, double *pend,
                           double *b2, int64_t *nb, int64_t *hist, int64_t *under, int64_t *over);
+/* ---- the site field of a statistics record: how often every tracked site held every species code, per key -------------
+ * A record may carry a SITE FIELD: site_counts[n_keys][M][S] and site_over[n_keys], int64.  The M tracked sites are a list
+ * of distinct site numbers in the caller's numbering (NULL: all N sites, in order); S = n_codes, 1..16.  For every row that
+ * the record's rule offers to key k, and for every tracked site m with code c in that row's occupancy:
+ *   c < S:      site_counts[k][m][c] += 1
+ *   otherwise:  site_over[k] += 1
+ * The rows offered are the rows that increment n[k]: one per key and sample in the two permutation modes, the rows inside
+ * the bins in SMOLMC_STAT_BY_BIN; rows counted in key_under / key_over touch nothing.  Hence
+ *   sum over m, c of site_counts[k][m][c] + site_over[k] == M * n[k]
+ * as long as field and record were reset together.  site_counts[k][m][c] / n[k] is the site-resolved average
+ * <delta(sigma_m, c)> of key k.  Sums of integers: the field does not depend on the order of the adds, and the device
+ * equals smol_amd/statistics.py (StatisticsRecord.offer with occupancy rows) entry for entry.
+ *
+ * Attaches a field to the record IN FORCE, in any key mode, and zeroes the field (the record's other accumulators stay);
+ * n_codes = 0 detaches it (sites and n_sites are not read).  Refused, each naming its reason and leaving record and field
+ * untouched: no record set; n_codes outside 0..16; an empty list, a site outside 0..N-1 or listed twice; record plus
+ * field larger than 1 GiB; while a block recorded with SMOLMC_SAMPLE_STATISTICS waits in the ring.  Setting a record
+ * (smolmc_set_statistics, smolmc_set_statistics_binned) drops the field: a new spec starts an empty record.
+ * smolmc_reset_statistics also clears the field, smolmc_update_statistics offers the walkers' current states to it as well.
+ * A SMOLMC_SAMPLE_STATISTICS block on a record with a field keeps the block's occupancy rows on the device, whether or
+ * not SMOLMC_SAMPLE_OCCUPANCY is set (without it they never leave the device); the field's launch is ordered on the
+ * handle's stream behind the block's launches and in front of the slot's reuse.  Chains are not affected.
+ * Waits for the handle's stream. */
+#define SMOLMC_MAX_STAT_SITE_CODES 16
+int smolmc_set_statistics_sites(smolmc_handle *h, const int32_t *sites /* [n_sites] or NULL */, int n_sites, int n_codes);
+/* the field in force (both 0: none set) */
+int smolmc_statistics_sites_shape(smolmc_handle *h, int *n_sites, int *n_codes);
+/* The field: site_counts [n_keys x M x S], site_over [n_keys]; either pointer may be NULL.  Columns are in the caller's
+ * order: tracked site m is the m-th entry of the list given (on a relabelled handle the engine reads byte new_of[p] of a
+ * ring row for the caller's site p, as smolmc_get_minima does).  Waits for the handle's stream. */
+int smolmc_get_statistics_sites(smolmc_handle *h, int64_t *site_counts, int64_t *site_over);
 
 /* ---- structure factors: fixed-point amplitudes and intensities of sampled states, reduced on the device ---------------
  * (no reference counterpart).  Kinds as in smolmc_observables: the kind of (site, code) is kind_base[site] + code,

@@ -3407,6 +3407,7 @@ __global__ void __launch_bounds__(256) sample_snapshot_kernel(const SnapshotArgs
 // record the counts the observables' flag or the minima record asked for, else its own).
 struct ColumnUse {
     bool min_counts, stat_counts, stat_inten, stat_conn, stat_pat, stat_env; // what the records read
+    bool stat_sites;                                        // the record's site field reads the occupancy rows
     bool counts, pairs, sfac, conn, pat, env;               // what is derived: kind counts, pair counts (with the observables' flag
                                                          // only), amplitudes with intensities, connectivity stats, pattern cells
 };
@@ -3425,6 +3426,7 @@ static ColumnUse column_use(const smolmc_handle *h, int flags) {
     u.pat = (flags & SMOLMC_SAMPLE_PATTERNS) || u.stat_pat;
     u.stat_env = stats && h->stats.n_env_cols > 0;                // (then obs.env.n_cells == stats.EC, see smolmc_set_environments)
     u.env = (flags & SMOLMC_SAMPLE_ENVIRONMENTS) || u.stat_env;
+    u.stat_sites = stats && h->stats.site_S > 0;                  // (smolmc_set_statistics_sites)
     return u;
 }
 
@@ -3462,7 +3464,8 @@ static int derive_and_offer(smolmc_handle *h, const RowSources &s, int flags, lo
         TRY(smolmc_min_launch(h, s.H, s.feat, s.occ, u.min_counts ? s.counts : nullptr, s.min_key, s.min_slot, nsamples, thin_by));
     if (flags & SMOLMC_SAMPLE_STATISTICS)
         TRY(smolmc_stat_launch(h, s.H, s.feat, u.stat_counts ? s.counts : nullptr, u.stat_inten ? s.inten : nullptr,
-                               u.stat_conn ? s.conn : nullptr, u.stat_pat ? s.pat : nullptr, u.stat_env ? s.env : nullptr, nsamples));
+                               u.stat_conn ? s.conn : nullptr, u.stat_pat ? s.pat : nullptr, u.stat_env ? s.env : nullptr, nsamples,
+                               u.stat_sites ? s.occ : nullptr));
     return 0;
 }
 
@@ -3501,7 +3504,7 @@ static int plan_block(const smolmc_handle *h, int64_t nsamples, int flags, Block
         if (t.applies && rows > 0x7fffffffull) return fail(std::string(t.noun) + ": more than 2^31 sample rows in one block");
     p.rows = rows;
     p.occ = (flags & SMOLMC_SAMPLE_OCCUPANCY) || p.lazy_rows || u.counts || u.sfac || u.conn || u.pat || u.env ||
-            (flags & SMOLMC_SAMPLE_MINIMA);
+            (flags & SMOLMC_SAMPLE_MINIMA) || u.stat_sites;
     const size_t sf_amp = (size_t)h->sfac.Q * h->sfac.K * 2 * 8, sf_inten = (size_t)h->sfac.I * 8; // bytes per row
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t o = at; at += up256(bytes); return o; };

@@ -921,6 +921,14 @@ struct SmolmcStat {
     int32_t *row_key = nullptr;    // [row_cap] the key of every row of the launch: an allocation of its own that grows to
     size_t row_cap = 0;            // the largest launch so far
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; // around the last reduction; ev[2] between the two launches of a binned one
+    // the site field (smolmc_set_statistics_sites): an allocation of its own, attached to the record in force
+    int site_M = 0, site_S = 0;        // tracked sites, codes (site_S == 0: no field)
+    unsigned char *site_arena = nullptr;
+    size_t site_bytes = 0;             // counts and over: what a reset zeroes
+    long long *site_counts = nullptr;  // [n_keys x S x M] on the device: code-major within a key
+    long long *site_over = nullptr;    // [n_keys]
+    int32_t *site_idx = nullptr;       // [M] byte of a ring row of tracked site m, or null: byte m (all sites, not relabelled)
+    hipEvent_t site_ev[2] = {nullptr, nullptr}; // around the field's last launch
 };
 
 // structure.hip: the structure-factor spec of a handle (smolmc_set_structure) as the kernel reads it, engine numbering
@@ -1219,9 +1227,11 @@ void smolmc_min_free(smolmc_handle *h);
 // (d_inten: intensities [rows x I] or null, read by a record with intensity columns; d_conn: connectivity stats
 // [rows x G x 24] or null, read by a record with connectivity columns; d_pat: pattern cells [rows x n_cells] or null, read
 // by a record with pattern columns; d_env: environment cells [rows x n_cells] or null, read by a record with environment
-// columns)
+// columns; d_occ8: the rows' occupancy, Npad bytes apart, or null, read by a record with a site field, whose launch comes
+// behind the others)
 int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, const double *d_inten,
-                       const long long *d_conn, const int32_t *d_pat, const int32_t *d_env, long long nsamples);
+                       const long long *d_conn, const int32_t *d_pat, const int32_t *d_env, long long nsamples,
+                       const uint8_t *d_occ8 = nullptr);
 void smolmc_stat_free(smolmc_handle *h);
 // structure.hip: amplitudes [rows x Q x K x 2] and intensities [rows x I] of `rows` occupancy rows (Npad bytes apart,
 // device) into device arrays, queued on the handle's stream; the kernel a spec takes and the layout of its LDS (false:

@@ -29,7 +29,20 @@
 //                      prefix from the mask, per-wave offsets); whenever the queue holds ST_CHUNK rows, or the scan has
 //                      ended, their values are staged and consumed with the ownership above.  Its LDS is the kernel's:
 //                      the queue lies where the blocking arrays of the other modes do.
+//
+// The SITE FIELD (smolmc_set_statistics_sites) counts, per key, how often every tracked site held every code: sums of
+// integers, so the order of the adds cannot change a bit.  One more mode of statistics_kernel, launched behind the others:
+//   statistics_sites   a workgroup is (unit x chunk of ST_SITE_OWN * 256 tracked sites); thread t owns the sites
+//                      chunk + t, chunk + 256 + t, ...: neighbouring lanes read neighbouring bytes of a row and add to
+//                      neighbouring counters.  The unit is a KEY in the two permutation modes: the thread walks the key's
+//                      row of every sample and adds its counters to site_counts once, as their only owner.  Keyed by bin
+//                      the unit is a TILE of consecutive rows, read with the keys the key pass left in row_key: the thread
+//                      counts while consecutive rows share a key and flushes with 64-bit integer atomics when the key
+//                      changes or the tile ends; rows outside the bins are skipped.  The counters of a site are 16 bytes
+//                      packed in two 64-bit registers (a flush at the latest after ST_SITE_FLUSH rows); the codes outside
+//                      the field go to site_over with one atomic per wave and flush.  No LDS.
 #include "smolmc_common.h"
+#include <thread>
 
 #define ST_THREADS 256
 #define ST_CHUNK 32 // samples staged at a time
@@ -42,14 +55,30 @@
 #define ST_KEY_OVER (-2)
 #define ST_MODE_KEYS 1   // StatArgs::mode: 0 the reduction by walker or state point, 1 stat_bin_keys, 2 statistics_binned
 #define ST_MODE_BINNED 2
+#define ST_MODE_SITES 3     // statistics_sites
+#define ST_SITE_OWN 2       // tracked sites a thread owns
+#define ST_SITE_FLUSH 255   // rows a thread counts between two flushes: its counters are bytes
+#define ST_SITE_TILE_MIN 16 // rows of a tile of the binned site pass
 
 struct StatArgs {
-    // the rows
-    const double *H, *feat;    // [rows], [rows x F]
-    const int32_t *counts;     // [rows x K] or null
-    const double *inten;       // [rows x I] or null: the intensities of the structure-factor spec in force
-    const long long *conn;     // [rows x CS] or null: the stats of the connectivity spec in force, 24 per graph
-    const int32_t *pat;        // [rows x PC] or null: the cells of the pattern spec in force
+    // the rows.  The site field (mode 3) reads none of the columns: its arguments lie in their place, and the kernel's
+    // arguments stay 304 bytes
+    union {
+        struct {
+            const double *H, *feat;    // [rows], [rows x F]
+            const int32_t *counts;     // [rows x K] or null
+            const double *inten;       // [rows x I] or null: the intensities of the structure-factor spec in force
+            const long long *conn;     // [rows x CS] or null: the stats of the connectivity spec in force, 24 per graph
+            const int32_t *pat;        // [rows x PC] or null: the cells of the pattern spec in force
+        };
+        struct { // mode 3; row_key null: the key is the walker or its state point, else the tile's rows bring theirs
+            const uint8_t *occ;            // the rows' occupancy, Npad bytes apart
+            const int32_t *site_idx;       // [M] byte of tracked site m in a row, or null: byte m
+            long long *site_counts;        // [n_keys x S x M]: code-major within a key (smolmc_get_statistics_sites transposes)
+            unsigned long long *site_over; // [n_keys]
+            int Npad, M, S, site_tile;     // site_tile: rows per tile
+        };
+    };
     const int32_t *env;        // [rows x EC] or null: the cells of the environment spec in force
     const int32_t *walker_at;  // key -> walker, or null: the identity
     // the record
@@ -72,6 +101,7 @@ struct StatArgs {
     unsigned long long *outside; // key_under, key_over of the record
     long long rows;              // nsamples x R
 };
+static_assert(sizeof(StatArgs) == 304, "the site field's arguments lie in the place of the column pointers");
 
 // column source `src` of row `row`: 0 the enthalpy, 1 + i feature i, 1 + F + k kind count k, 1 + F + K the weighted sum,
 // 2 + F + K + i intensity i, 2 + F + K + I + c connectivity number c (24 per graph) as a double, 2 + F + K + I + CS + c
@@ -229,6 +259,93 @@ __device__ __forceinline__ void statistics_binned(const StatArgs &B, double *s_x
     if (tid == 0) A.n[key] = n0 + head;
 }
 
+// ---- the site field ---------------------------------------------------------------------------------------------------------
+// the counters of the thread's sites, one byte per code, and its codes outside the field go to `key`: plain adds for the
+// accumulators' only owner, else atomics; one add to site_over per wave (every lane of the wave is here)
+__device__ __forceinline__ void stat_sites_flush(const StatArgs &A, int key, int m_first, bool atomic, uint64_t (&lo)[ST_SITE_OWN],
+                                                 uint64_t (&hi)[ST_SITE_OWN], unsigned &over) {
+#pragma unroll
+    for (int j = 0; j < ST_SITE_OWN; ++j) {
+        const int m = m_first + j * ST_THREADS;
+        if (m < A.M) {
+            // (on the device the counters of a key are [S][M]: the lanes' adds of one code are neighbours)
+            unsigned long long *dst = (unsigned long long *)A.site_counts + (size_t)key * A.S * A.M + m;
+            for (int c = 0; c < A.S; ++c) {
+                const unsigned long long v = ((c < 8 ? lo[j] : hi[j]) >> ((c & 7) * 8)) & 255;
+                if (v) {
+                    if (atomic) atomicAdd(dst + (size_t)c * A.M, v);
+                    else dst[(size_t)c * A.M] += v;
+                }
+            }
+        }
+        lo[j] = hi[j] = 0;
+    }
+    unsigned sum = over;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(A.site_over + key, (unsigned long long)sum);
+    over = 0;
+}
+
+// mode 3 of statistics_kernel
+__device__ __forceinline__ void statistics_sites(const StatArgs &A) {
+    const int tid = threadIdx.x;
+    const int chunks = (A.M + ST_SITE_OWN * ST_THREADS - 1) / (ST_SITE_OWN * ST_THREADS);
+    const long long unit = blockIdx.x / chunks;
+    const int m_first = (int)(blockIdx.x % chunks) * (ST_SITE_OWN * ST_THREADS) + tid;
+    int at[ST_SITE_OWN]; // the byte of the thread's sites in a row (a site past the list: byte 0, read and not counted)
+#pragma unroll
+    for (int j = 0; j < ST_SITE_OWN; ++j) {
+        const int m = m_first + j * ST_THREADS;
+        at[j] = m < A.M ? (A.site_idx ? A.site_idx[m] : m) : 0;
+    }
+    uint64_t lo[ST_SITE_OWN], hi[ST_SITE_OWN];
+#pragma unroll
+    for (int j = 0; j < ST_SITE_OWN; ++j) lo[j] = hi[j] = 0;
+    unsigned over = 0;
+    const bool binned = A.row_key != nullptr; // (uniform over the launch)
+    long long first, last;                    // the rows of the tile, or the samples
+    size_t walker = 0;
+    if (binned) {
+        first = unit * A.site_tile;
+        last = first + A.site_tile < A.rows ? first + A.site_tile : A.rows;
+    } else {
+        first = 0;
+        last = A.nsamples;
+        walker = A.walker_at ? (size_t)A.walker_at[unit] : (size_t)unit;
+    }
+    int cur = -1, pending = 0; // (uniform over the workgroup, like everything the loop branches on)
+    for (long long i = first; i < last; ++i) {
+        size_t row;
+        int key;
+        if (binned) {
+            row = (size_t)i;
+            key = __builtin_amdgcn_readfirstlane(A.row_key[i]);
+            if (key < 0) continue; // outside the bins: the row touches nothing
+        } else {
+            row = (size_t)i * A.R + walker;
+            key = (int)unit;
+        }
+        if (cur >= 0 && (key != cur || pending == ST_SITE_FLUSH)) {
+            stat_sites_flush(A, cur, m_first, binned, lo, hi, over);
+            pending = 0;
+        }
+        cur = key;
+        ++pending;
+        const uint8_t *bytes = A.occ + row * (size_t)A.Npad;
+#pragma unroll
+        for (int j = 0; j < ST_SITE_OWN; ++j) {
+            const unsigned c = bytes[at[j]];
+            const bool live = m_first + j * ST_THREADS < A.M, inside = c < (unsigned)A.S;
+            const uint64_t one = (uint64_t)1 << ((c & 7) * 8);
+            lo[j] += live && inside && c < 8 ? one : 0;
+            hi[j] += live && inside && c >= 8 ? one : 0;
+            over += live && !inside;
+        }
+    }
+    if (cur >= 0) stat_sites_flush(A, cur, m_first, binned, lo, hi, over);
+}
+
 __global__ void __launch_bounds__(ST_THREADS) statistics_kernel(const StatArgs A) {
     // Every product and every sum is rounded on its own, as NumPy does it (see weighted_value_rn, smolmc_common.h).
 #pragma clang fp contract(off)
@@ -243,6 +360,10 @@ __global__ void __launch_bounds__(ST_THREADS) statistics_kernel(const StatArgs A
     }
     if (A.mode == ST_MODE_BINNED) {
         statistics_binned(A, s_x, s_shift, reinterpret_cast<int *>(s_pend), reinterpret_cast<int *>(s_nb));
+        return;
+    }
+    if (A.mode == ST_MODE_SITES) {
+        statistics_sites(A);
         return;
     }
     const int key = blockIdx.x, tid = threadIdx.x;
@@ -357,8 +478,34 @@ __global__ void __launch_bounds__(ST_THREADS) statistics_kernel(const StatArgs A
 }
 
 
+// the site field's launch, behind the launches of `A` on the handle's stream (a binned record: behind its key pass, whose
+// row keys it reads)
+static int stat_sites_launch(smolmc_handle *h, StatArgs A, const uint8_t *d_occ8) {
+    SmolmcStat &S = h->stats;
+    A.mode = ST_MODE_SITES;
+    A.occ = d_occ8; A.site_idx = S.site_idx; A.site_counts = S.site_counts; A.site_over = (unsigned long long *)S.site_over;
+    A.Npad = h->Npad; A.M = S.site_M; A.S = S.site_S;
+    const size_t chunks = ((size_t)S.site_M + ST_SITE_OWN * ST_THREADS - 1) / (ST_SITE_OWN * ST_THREADS);
+    size_t units = (size_t)S.n_keys; // a key per unit, or a tile of rows
+    if (S.key == SMOLMC_STAT_BY_BIN) {
+        // long tiles make few atomics where a key is crowded, short ones fill the device: about 2^19 threads in all
+        const size_t fill = ((size_t)A.rows * chunks * ST_THREADS) >> 19;
+        A.site_tile = (int)std::min<size_t>(ST_SITE_FLUSH, std::max<size_t>(ST_SITE_TILE_MIN, fill));
+        units = ((size_t)A.rows + A.site_tile - 1) / A.site_tile;
+    }
+    if (units * chunks > 0x7fffffffull) return fail("statistics: the site field's launch has more than 2^31 workgroups");
+    if (!S.site_ev[0])
+        for (hipEvent_t &e : S.site_ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(S.site_ev[0], h->stream));
+    hipLaunchKernelGGL(statistics_kernel, dim3((unsigned)(units * chunks)), dim3(ST_THREADS), 0, h->stream, A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.site_ev[1], h->stream));
+    return 0;
+}
+
 int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, const double *d_inten,
-                       const long long *d_conn, const int32_t *d_pat, const int32_t *d_env, long long nsamples) {
+                       const long long *d_conn, const int32_t *d_pat, const int32_t *d_env, long long nsamples,
+                       const uint8_t *d_occ8) {
     SmolmcStat &S = h->stats;
     if (!S.n_keys) return fail("no statistics record set (smolmc_set_statistics)");
     if (S.n_count_cols && !d_counts) return fail("statistics: a record with count columns needs the kind counts of the rows");
@@ -366,6 +513,7 @@ int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat
     if (S.n_conn_cols && !d_conn) return fail("statistics: a record with connectivity columns needs the connectivity stats of the rows");
     if (S.n_pat_cols && !d_pat) return fail("statistics: a record with pattern columns needs the pattern cells of the rows");
     if (S.n_env_cols && !d_env) return fail("statistics: a record with environment columns needs the environment cells of the rows");
+    if (S.site_S && !d_occ8) return fail("statistics: a record with a site field needs the occupancy of the rows");
     if (S.key == SMOLMC_STAT_BY_STATE_POINT && !h->wl_win_min.empty())
         return fail("statistics: a record keyed by state point on a Wang-Landau handle with per-walker windows");
     if (nsamples <= 0 || (size_t)nsamples * h->R > 0x7fffffffull) return fail("statistics: 1 .. 2^31 rows in one launch");
@@ -405,19 +553,34 @@ int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat
         hipLaunchKernelGGL(statistics_kernel, dim3((unsigned)S.n_keys), dim3(ST_THREADS), 0, h->stream, A);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(S.ev[1], h->stream));
-        return 0;
+        return S.site_S ? stat_sites_launch(h, A, d_occ8) : 0;
     }
     HIPCHK(hipEventRecord(S.ev[0], h->stream));
     hipLaunchKernelGGL(statistics_kernel, dim3((unsigned)S.n_keys), dim3(ST_THREADS), 0, h->stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(S.ev[1], h->stream));
-    return 0;
+    return S.site_S ? stat_sites_launch(h, A, d_occ8) : 0;
+}
+
+// the field of the record goes (smolmc_set_statistics_sites with n_codes = 0, a new spec, the handle's end)
+static void stat_sites_free(SmolmcStat &S) {
+    if (S.site_arena) hipFree(S.site_arena);
+    for (hipEvent_t &e : S.site_ev) {
+        if (e) hipEventDestroy(e);
+        e = nullptr;
+    }
+    S.site_arena = nullptr;
+    S.site_counts = S.site_over = nullptr;
+    S.site_idx = nullptr;
+    S.site_M = S.site_S = 0;
+    S.site_bytes = 0;
 }
 
 void smolmc_stat_free(smolmc_handle *h) {
     SmolmcStat &S = h->stats;
     if (S.arena) hipFree(S.arena);
     if (S.row_key) hipFree(S.row_key);
+    stat_sites_free(S);
     for (hipEvent_t e : S.ev)
         if (e) hipEventDestroy(e);
     S = SmolmcStat();
@@ -618,6 +781,7 @@ extern "C" int smolmc_reset_statistics(smolmc_handle *h) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemset(S.arena, 0, S.record_bytes));
+    if (S.site_S) HIPCHK(hipMemset(S.site_arena, 0, S.site_bytes));
     HIPCHK(hipDeviceSynchronize());
     return 0;
 }
@@ -641,6 +805,129 @@ extern "C" int smolmc_get_statistics(smolmc_handle *h, int64_t *n, double *shift
     if (hist && B) HIPCHK(hipMemcpy(hist, S.hist, nk * B * 8, hipMemcpyDeviceToHost));
     if (under) HIPCHK(hipMemcpy(under, S.under, nk * 8, hipMemcpyDeviceToHost));
     if (over) HIPCHK(hipMemcpy(over, S.over, nk * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- the site field: how often every tracked site held every code, per key ----------------------------------------------
+extern "C" int smolmc_set_statistics_sites(smolmc_handle *h, const int32_t *sites, int n_sites, int n_codes) {
+    if (!h) return fail("null handle");
+    SmolmcStat &S = h->stats;
+    if (!S.n_keys) return fail("statistics sites: no statistics record set (call smolmc_set_statistics first)");
+    char msg[256];
+    if (n_codes < 0 || n_codes > SMOLMC_MAX_STAT_SITE_CODES) {
+        snprintf(msg, sizeof msg, "statistics sites: n_codes must be 0..%d, got %d", SMOLMC_MAX_STAT_SITE_CODES, n_codes);
+        return fail(msg);
+    }
+    const int N = h->N, M = sites ? n_sites : N;
+    if (n_codes && sites) {
+        if (n_sites < 1) {
+            snprintf(msg, sizeof msg, "statistics sites: a list of %d sites (NULL tracks all %d)", n_sites, N);
+            return fail(msg);
+        }
+        std::vector<int32_t> seen((size_t)N, -1);
+        for (int m = 0; m < n_sites; ++m) {
+            const int p = sites[m];
+            if (p < 0 || p >= N) {
+                snprintf(msg, sizeof msg, "statistics sites: entry %d is site %d, outside 0..%d", m, p, N - 1);
+                return fail(msg);
+            }
+            if (seen[p] >= 0) {
+                snprintf(msg, sizeof msg, "statistics sites: site %d is listed twice (entries %d and %d)", p, (int)seen[p], m);
+                return fail(msg);
+            }
+            seen[p] = m;
+        }
+    }
+    const size_t nk = (size_t)S.n_keys;
+    const size_t o_over = up256(nk * (size_t)M * (size_t)n_codes * 8), o_idx = o_over + up256(nk * 8);
+    if (n_codes && S.record_bytes + o_idx > ((size_t)1 << 30)) {
+        snprintf(msg, sizeof msg, "statistics sites: a record of %zu bytes and a field of %zu keys x %d sites x %d codes are larger than "
+                 "1 GiB", S.record_bytes, nk, M, n_codes);
+        return fail(msg);
+    }
+    TRY(smolmc_ring_guard(h, SMOLMC_SAMPLE_STATISTICS, "smolmc_set_statistics_sites", "SMOLMC_SAMPLE_STATISTICS"));
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream)); // (queued launches still add to the field in force)
+    if (!n_codes) {
+        stat_sites_free(S);
+        return 0;
+    }
+    // all sites of a handle that is not relabelled: tracked site m is byte m, no list on the device
+    std::vector<int32_t> idx;
+    if (sites || h->relabelled) {
+        idx.resize((size_t)M);
+        for (int m = 0; m < M; ++m) {
+            const int p = sites ? sites[m] : m;
+            idx[(size_t)m] = h->relabelled ? h->new_of[p] : p;
+        }
+    }
+    unsigned char *arena = nullptr;
+    HIPCHK(hipMalloc((void **)&arena, o_idx + up256((size_t)M * 4)));
+    hipError_t e = hipMemset(arena, 0, o_idx); // (an empty field is all zeros)
+    if (e == hipSuccess && !idx.empty()) e = hipMemcpy(arena + o_idx, idx.data(), (size_t)M * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        hipFree(arena);
+        return fail(std::string("statistics sites upload: ") + hipGetErrorString(e));
+    }
+    stat_sites_free(S);
+    S.site_arena = arena;
+    S.site_bytes = o_idx;
+    S.site_counts = (long long *)arena;
+    S.site_over = (long long *)(arena + o_over);
+    S.site_idx = idx.empty() ? nullptr : (int32_t *)(arena + o_idx);
+    S.site_M = M;
+    S.site_S = n_codes;
+    return 0;
+}
+
+extern "C" int smolmc_statistics_sites_shape(smolmc_handle *h, int *n_sites, int *n_codes) {
+    if (!h) return fail("null handle");
+    const SmolmcStat &S = h->stats;
+    if (n_sites) *n_sites = S.site_S ? S.site_M : 0;
+    if (n_codes) *n_codes = S.site_S;
+    return 0;
+}
+
+extern "C" int smolmc_get_statistics_sites(smolmc_handle *h, int64_t *site_counts, int64_t *site_over) {
+    if (!h) return fail("null handle");
+    const SmolmcStat &S = h->stats;
+    if (!S.site_S) return fail("no site field set: call smolmc_set_statistics_sites first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t nk = (size_t)S.n_keys, M = (size_t)S.site_M, NC = (size_t)S.site_S;
+    if (site_counts) { // the device keeps a key's counters code-major, the caller gets them site-major
+        std::vector<int64_t> dev(nk * M * NC);
+        HIPCHK(hipMemcpy(dev.data(), S.site_counts, nk * M * NC * 8, hipMemcpyDeviceToHost));
+        auto work = [&](size_t k0, size_t k1) {
+            for (size_t k = k0; k < k1; ++k)
+                for (size_t c = 0; c < NC; ++c) {
+                    const int64_t *src = dev.data() + (k * NC + c) * M;
+                    int64_t *dst = site_counts + k * M * NC + c;
+                    for (size_t m = 0; m < M; ++m) dst[m * NC] = src[m];
+                }
+        };
+        const int nt = 4;
+        if (nk * M * NC < ((size_t)1 << 20) || nk < (size_t)nt) work(0, nk);
+        else {
+            std::thread th[nt];
+            for (int t = 0; t < nt; ++t) th[t] = std::thread(work, nk * t / nt, nk * (t + 1) / nt);
+            for (int t = 0; t < nt; ++t) th[t].join();
+        }
+    }
+    if (site_over) HIPCHK(hipMemcpy(site_over, S.site_over, nk * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// elapsed device time of the site field's last launch in ms (tools/statistics_sites_timing.py); a measuring hook like the
+// two below, not part of the C-ABI
+extern "C" int smolmc_debug_statistics_sites_kernel_ms(smolmc_handle *h, float *ms) {
+    if (!h || !ms) return fail("null argument");
+    const SmolmcStat &S = h->stats;
+    if (!S.site_ev[0]) return fail("the site field's kernel has not been launched yet");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(S.site_ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, S.site_ev[0], S.site_ev[1]));
     return 0;
 }
 

@@ -77,6 +77,9 @@ SYMBOLS = {
     "smolmc_update_statistics": (C.c_int, [_HP]),
     "smolmc_reset_statistics": (C.c_int, [_HP]),
     "smolmc_get_statistics": (C.c_int, [_HP, _i64p, _f64p, _f64p, _f64p, _u64p, _f64p, _f64p, _i64p, _i64p, _i64p, _i64p]),
+    "smolmc_set_statistics_sites": (C.c_int, [_HP, _i32p, C.c_int, C.c_int]),
+    "smolmc_statistics_sites_shape": (C.c_int, [_HP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "smolmc_get_statistics_sites": (C.c_int, [_HP, _i64p, _i64p]),
     "smolmc_set_structure": (C.c_int, [_HP, C.POINTER(capi.smolmc_structure)]),
     "smolmc_structure_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 3),
     "smolmc_eval_structure": (C.c_int, [_HP, _i32p, C.c_int, _i64p, _f64p]),
@@ -845,7 +848,9 @@ class Engine:
         it.  A new spec starts an empty record.  The record lives as long as the handle: ``set_state`` and
         ``discard_samples`` leave it alone.  A spec keyed by bin (``Statistics.by_bin``) goes through
         smolmc_set_statistics_binned, which refuses likewise blocking levels, ``n_keys`` outside 1..65536, a bin width that
-        is not positive and finite and a key column outside the columns."""
+        is not positive and finite and a key column outside the columns.  A spec with a site field
+        (``Statistics(..., sites=, site_codes=)``) attaches it to the new record (smolmc_set_statistics_sites); when the
+        engine refuses the field, the handle is left without a record."""
         # (what ``statistics.segments`` takes: F, then every family's size in force, in the table's order)
         shape = () if spec is None else (self.F,) + tuple(self._family_sizes(fam)[fam.stat[2]] for fam in FAMILIES)
         bins = None if spec is None else spec.c_bins()
@@ -856,6 +861,27 @@ class Engine:
             self._chk(self._lib.smolmc_set_statistics_binned(self._h, C.byref(struct), *bins))
             del keep
         self.statistics_spec = spec
+        field = None if spec is None else spec.c_sites()
+        if field is not None:
+            try:
+                self.set_statistics_sites(*field)
+            except (EngineError, ValueError):
+                self._chk(self._lib.smolmc_set_statistics(self._h, None))
+                self.statistics_spec = None
+                raise
+
+    def set_statistics_sites(self, sites, n_sites, n_codes):
+        """smolmc_set_statistics_sites as it stands: attach a site field of ``n_codes`` codes on the sites ``sites`` (an
+        int32 array in the caller's numbering, or None for all sites) to the record in force and zero the field;
+        ``n_codes = 0`` detaches it.  ``set_statistics`` calls this for a spec that has a field."""
+        a = None if sites is None else np.ascontiguousarray(sites, dtype=np.int32)
+        self._chk(self._lib.smolmc_set_statistics_sites(self._h, _p(a, C.c_int32), int(n_sites), int(n_codes)))
+
+    def statistics_sites_shape(self):
+        """(n_sites, n_codes) of the site field in force, zeros when none is set (smolmc_statistics_sites_shape)."""
+        m, c = C.c_int(), C.c_int()
+        self._chk(self._lib.smolmc_statistics_sites_shape(self._h, C.byref(m), C.byref(c)))
+        return int(m.value), int(c.value)
 
     def statistics_bins(self):
         """(key_column, n_keys, key_min, key_bin, key_under, key_over) of the binned record in force, all zeros when the
@@ -884,7 +910,10 @@ class Engine:
 
         if self.statistics_spec is None:
             raise EngineError("no statistics record set: call set_statistics first")
-        rec = StatisticsRecord(self.statistics_spec, self.R)
+        n_sites, n_codes = self.statistics_sites_shape()
+        rec = StatisticsRecord(self.statistics_spec, self.R, n_sites)
+        if rec.site_counts.shape[1:] != (n_sites, n_codes):
+            raise EngineError(f"the handle's site field has shape {(n_sites, n_codes)}, the spec gives {rec.site_counts.shape[1:]}")
         shape = self.statistics_shape()
         want = (rec.n_keys, rec.spec.n_columns, rec.spec.n_levels, rec.spec.n_bins)
         if shape != want:
@@ -895,6 +924,8 @@ class Engine:
             _p(rec.hist, C.c_int64), _p(rec.under, C.c_int64), _p(rec.over, C.c_int64)))
         if rec.spec.binned:
             rec.key_under, rec.key_over = self.statistics_bins()[4:]
+        if n_codes:
+            self._chk(self._lib.smolmc_get_statistics_sites(self._h, _p(rec.site_counts, C.c_int64), _p(rec.site_over, C.c_int64)))
         return rec
 
     def statistics_kernel_ms(self):
@@ -906,6 +937,11 @@ class Engine:
         """Device times of the two launches of the last reduction of a binned record in ms, [the row keys, the reduction per
         key] (HIP events; a measuring hook of the library, not part of the C-ABI)."""
         return self._kernel_ms("smolmc_debug_statistics_bins_kernel_ms", 2)
+
+    def statistics_sites_kernel_ms(self):
+        """Device time of the site field's last launch in ms (HIP events; a measuring hook of the library, not part of the
+        C-ABI)."""
+        return self._kernel_ms("smolmc_debug_statistics_sites_kernel_ms")
 
     def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False,
                     minima=False, statistics=False, structure=False, connectivity=False, patterns=False, environments=False):

@@ -2546,7 +2546,8 @@ class Sampler:
         leave the device -- their species and pair counts do; the container stores the occupancy of the final
         sample of this call alone, so ``last_occupancy`` and a continuation work as before."""
         if not keep_occupancy:
-            if not self._traced and self._minima is None:  # (a family that rests on the observables comes with them)
+            has_field = self._statistics is not None and self._statistics.site_codes > 0  # (the record's site field)
+            if not self._traced and self._minima is None and not has_field:  # (a family that rests on the observables comes with them)
                 raise ValueError("keep_occupancy=False needs a sampler built with observables=, minima=, structure_factor= or connectivity=: nothing else of the "
                                  "occupancies would be recorded")
             if stream_chunk > 0:
@@ -2657,6 +2658,20 @@ class Sampler:
             raise ValueError(f"the record has {spec.n_keys} keys, the Wang-Landau handle {len(ln_g)} levels: build the record with "
                              "Statistics.on_wl_levels on the handle's own (min_enthalpy, bin_size, number of levels)")
         return self.statistics.canonical(ln_g, temperatures)
+
+    def wl_canonical_sites(self, temperatures):
+        """(nT, M, S): the site field at ``temperatures`` from ONE Wang-Landau run,
+        ``record.canonical_sites(wl_entropy_on_levels(), temperatures)``: the mean structure of every level, weighted as
+        ``wl_canonical`` weights the columns.  The sampler's record must be as for ``wl_canonical`` and carry a site field
+        (``Statistics.on_wl_levels(..., sites=, site_codes=)``)."""
+        spec = self._statistics
+        if spec is None or not spec.binned or spec.columns[spec.key_column] != ("enthalpy",) or not spec.site_codes:
+            raise ValueError("wl_canonical_sites needs a sampler built with statistics=Statistics.on_wl_levels(..., site_codes=)")
+        ln_g = self.wl_entropy_on_levels()
+        if len(ln_g) != spec.n_keys:
+            raise ValueError(f"the record has {spec.n_keys} keys, the Wang-Landau handle {len(ln_g)} levels: build the record with "
+                             "Statistics.on_wl_levels on the handle's own (min_enthalpy, bin_size, number of levels)")
+        return self.statistics.canonical_sites(ln_g, temperatures)
 
     def run_exchange(self, n_exchanges, steps_between, initial_occupancies=None, thin_by=None, grid=None, windows=None,
                      sync_every=None, final_mod_factor=None):

@@ -41,6 +41,18 @@ WALKER ORDER 0 .. R - 1.  For each row:
 Blocking means nothing when successive rows of a key come from different walkers: this mode refuses ``n_levels != 0``; the
 record's arrays keep their shapes with L = 0.  Every product and every sum is rounded on its own, as above.  The
 walker-to-state-point map is not read.  The ORDER of a key's offers is part of the definition: sums of doubles depend on it.
+
+A record may carry a SITE FIELD (``Statistics(..., sites=, site_codes=)``; smolmc_set_statistics_sites): ``site_counts``
+(n_keys, M, S) and ``site_over`` (n_keys,), int64.  The M tracked sites are ``sites``, distinct site numbers in the caller's
+numbering (None: all N sites, in order); S = ``site_codes``, 1..16.  For every row that the rule above offers to key k -- the
+rows that increment ``n[k]``: one per key and sample in the two permutation modes, the rows inside the bins of a binned
+record, never a row counted in ``key_under`` / ``key_over`` -- and every tracked site m with code c in the row's occupancy:
+
+    c < S:      site_counts[k, m, c] += 1
+    otherwise:  site_over[k] += 1
+
+so that ``site_counts[k].sum() + site_over[k] == M * n[k]``.  ``site_counts[k, m, c] / n[k]`` is the site-resolved average
+<delta(sigma_m, c)> of key k (``site_occupancy``).  Sums of integers: no order matters, the device gives the same numbers.
 """
 
 from __future__ import annotations
@@ -57,9 +69,11 @@ MAX_KEYS = 65536                   # SMOLMC_MAX_STAT_KEYS
 MAX_COLUMNS = 32                   # SMOLMC_MAX_STAT_COLUMNS
 MAX_LEVELS = 32                    # SMOLMC_MAX_STAT_LEVELS
 MAX_BINS = 65536                   # SMOLMC_MAX_STAT_BINS
+MAX_SITE_CODES = 16                # SMOLMC_MAX_STAT_SITE_CODES
 KB = 8.617333262145e-5             # eV / K, SMOLMC_KB (smol/constants.py:4)
 
 _ARRAYS = ("n", "shift", "s1", "s2", "has", "pend", "b2", "nb", "hist", "under", "over")
+_SITE_ARRAYS = ("site_counts", "site_over")  # the site field (empty without one)
 _MODE_NAMES = {BY_WALKER: "by walker", BY_STATE_POINT: "by state point", BY_BIN: "by bin"}
 
 # ---- column sources: symbolic, resolved against a handle's (F, K) by Statistics.sources -------------------------------
@@ -148,9 +162,11 @@ class Statistics:
     """The spec of a record: how it is keyed, its columns, the weights of the ENERGY column, the blocking levels and the
     histogram (``hist=(column, n_bins, hist_min, hist_bin)`` with ``column`` one of ``columns``).  A record keyed by bin
     (``by_bin``) also has ``bins=(column, n_keys, key_min, key_bin)``, ``column`` one of ``columns``; a spec with key
-    ``BY_BIN`` and no ``bins`` is not binned, and the engine refuses it."""
+    ``BY_BIN`` and no ``bins`` is not binned, and the engine refuses it.  ``site_codes`` > 0 gives the record a site field
+    (module docstring) of the sites ``sites`` (None: all sites) and the codes 0 .. ``site_codes`` - 1."""
 
-    def __init__(self, key=BY_WALKER, columns=(ENTHALPY,), weights=None, n_levels=0, hist=None, bins=None):
+    def __init__(self, key=BY_WALKER, columns=(ENTHALPY,), weights=None, n_levels=0, hist=None, bins=None, sites=None,
+                 site_codes=0):
         self.key = int(key)
         self.columns = [tuple(c) if not isinstance(c, (int, np.integer)) else ("source", int(c)) for c in columns]
         self.weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
@@ -171,6 +187,8 @@ class Statistics:
             if col not in self.columns:
                 raise ValueError("the key's column must be one of the record's columns")
             self.key_column, self.n_keys, self.key_min, self.key_bin = self.columns.index(col), int(n_keys), float(kmin), float(kbin)
+        self.site_codes = int(site_codes)
+        self.sites = None if sites is None or not self.site_codes else np.ascontiguousarray(sites, dtype=np.int32).reshape(-1)
         # (ranges, duplicates, sizes: the engine refuses them, naming the reason)
 
     @classmethod
@@ -182,9 +200,9 @@ class Statistics:
         return cls(BY_STATE_POINT, columns, **kw)
 
     @classmethod
-    def by_bin(cls, key, n_keys, key_min, key_bin, columns=(ENTHALPY,), weights=None, hist=None):
+    def by_bin(cls, key, n_keys, key_min, key_bin, columns=(ENTHALPY,), weights=None, hist=None, sites=None, site_codes=0):
         """Keyed by ``n_keys`` bins of width ``key_bin`` from ``key_min`` of the column ``key``, one of ``columns``."""
-        return cls(BY_BIN, columns, weights, 0, hist, bins=(key, n_keys, key_min, key_bin))
+        return cls(BY_BIN, columns, weights, 0, hist, bins=(key, n_keys, key_min, key_bin), sites=sites, site_codes=site_codes)
 
     @classmethod
     def by_composition(cls, obs, kind_name_or_k, num_sites, columns=None, **kw):
@@ -213,6 +231,17 @@ class Statistics:
     n_columns = property(lambda self: len(self.columns))
     n_weights = property(lambda self: 0 if self.weights is None else len(self.weights))
     n_pairs = property(lambda self: self.n_columns * (self.n_columns + 1) // 2)
+
+    def site_list(self, num_sites):
+        """The tracked sites as an index array into rows of ``num_sites`` sites (all of them when ``sites`` is None)."""
+        return np.arange(int(num_sites)) if self.sites is None else self.sites.astype(np.int64)
+
+    def c_sites(self):
+        """The arguments of smolmc_set_statistics_sites behind the handle (sites or None, n_sites, n_codes), or None for a
+        spec without a site field."""
+        if not self.site_codes:
+            return None
+        return self.sites, 0 if self.sites is None else len(self.sites), self.site_codes
 
     def sources(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0, n_env_cells=0):
         """int32 column sources of the C ABI (``segments``): a tagged column is its number within the segment of its tag,
@@ -310,9 +339,11 @@ class StatisticsRecord:
     """The accumulators: n, under, over (n_keys,) int64; shift, s1 (n_keys, C); s2 (n_keys, C (C + 1) / 2); has (n_keys, C)
     uint64; pend, b2 (n_keys, n_levels, C); nb (n_keys, n_levels) int64; hist (n_keys, n_bins) int64.  A binned record
     (``spec.binned``) takes ``n_keys`` from the spec and counts the rows outside its bins in ``key_under`` and ``key_over``
-    (ints; 0 in the other modes)."""
+    (ints; 0 in the other modes).  The site field: site_counts (n_keys, M, S), site_over (n_keys,) int64; M = 0 and S = 0
+    without one.  With all sites tracked M is ``n_sites``, or, where that is not given, taken from the first occupancy rows
+    offered."""
 
-    def __init__(self, spec, n_keys=None):
+    def __init__(self, spec, n_keys=None, n_sites=None):
         self.spec = spec
         if spec.binned:
             n_keys = spec.n_keys
@@ -330,6 +361,9 @@ class StatisticsRecord:
         self.over = np.zeros(nk, dtype=np.int64)
         self.key_under = 0
         self.key_over = 0
+        M = 0 if not spec.site_codes else len(spec.sites) if spec.sites is not None else int(n_sites or 0)
+        self.site_counts = np.zeros((nk, M, spec.site_codes), dtype=np.int64)
+        self.site_over = np.zeros(nk, dtype=np.int64)
 
     n_keys = property(lambda self: len(self.n))
 
@@ -344,15 +378,33 @@ class StatisticsRecord:
                              f"{_MODE_NAMES.get(self.spec.key, self.spec.key)}")
 
     # ---- the definition ------------------------------------------------------------------------------------------
+    def _site_rows(self, occupancy, rows):
+        """(inside (rows, M, S) int64 one-hot of the tracked sites' codes below S, outside (rows,) the codes not below S) of
+        occupancy rows in the caller's numbering; the field takes its M from them when all sites are tracked."""
+        spec = self.spec
+        if occupancy is None:
+            raise ValueError("a record with a site field needs the occupancy of the rows (offer(..., occupancy=))")
+        occ = np.asarray(occupancy).reshape(rows, -1)
+        sites = spec.site_list(occ.shape[1])
+        if self.site_counts.shape[1] == 0 and not self.n.any():
+            self.site_counts = np.zeros((self.n_keys, len(sites), spec.site_codes), dtype=np.int64)
+        if len(sites) != self.site_counts.shape[1]:
+            raise ValueError(f"the field tracks {self.site_counts.shape[1]} sites, the rows give {len(sites)}")
+        sub = occ[:, sites].astype(np.int64)
+        inside = (sub[:, :, None] == np.arange(spec.site_codes)[None, None, :]).astype(np.int64)
+        return inside, sites.size - inside.sum(axis=(1, 2))
+
     def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None, connectivity=None, patterns=None,
-              environments=None):
+              environments=None, occupancy=None):
         """Offer samples (ns, R) -- or one sample (R,) -- in order.  ``key_of_row`` (R,) or (ns, R): the key of every
-        row, a permutation of 0 .. R - 1 per sample (None: the walker).  Vectorised over the keys, a loop over samples."""
+        row, a permutation of 0 .. R - 1 per sample (None: the walker).  Vectorised over the keys, a loop over samples.
+        ``occupancy`` (ns, R, N) or (R, N), in the caller's numbering: what a record with a site field counts; a record
+        without one does not read it."""
         spec = self.spec
         if spec.binned:
             if key_of_row is not None:
                 raise ValueError("a record keyed by bin takes the key of a row from its key column, not from key_of_row")
-            return self._offer_binned(enthalpy, features, counts, intensities, connectivity, patterns, environments)
+            return self._offer_binned(enthalpy, features, counts, intensities, connectivity, patterns, environments, occupancy)
         nk = self.n_keys
         H = np.asarray(enthalpy, dtype=np.float64).reshape(-1, nk)
         ns = len(H)
@@ -367,6 +419,9 @@ class StatisticsRecord:
             keys = np.broadcast_to(np.arange(nk), (ns, nk))
         else:
             keys = np.broadcast_to(np.asarray(key_of_row, dtype=np.int64), (ns, nk))
+        if spec.site_codes:
+            inside, outside = self._site_rows(occupancy, ns * nk)
+            inside, outside = inside.reshape((ns, nk) + inside.shape[1:]), outside.reshape(ns, nk)
         Cn, L = spec.n_columns, spec.n_levels
         ia, ib = np.triu_indices(Cn)
         rows = np.arange(nk)
@@ -407,10 +462,13 @@ class StatisticsRecord:
                 self.over += over
                 ok = ~(under | over)
                 self.hist[rows[ok], q[ok].astype(np.int64)] += 1
+            if spec.site_codes:  # (every key once: a plain indexed add)
+                self.site_counts[keys[s]] += inside[s]
+                self.site_over[keys[s]] += outside[s]
             self.n += 1
         return self
 
-    def _offer_binned(self, enthalpy, features, counts, intensities, connectivity, patterns, environments):
+    def _offer_binned(self, enthalpy, features, counts, intensities, connectivity, patterns, environments, occupancy=None):
         """The rule of the module docstring for samples (ns, R) -- or one sample (R,): the rows in sample-major,
         walker-minor order.  Vectorised over the keys: round j offers the j-th row of every key."""
         spec = self.spec
@@ -434,6 +492,10 @@ class StatisticsRecord:
         self.key_under += int(under.sum())
         self.key_over += int(over.sum())
         ok = ~(under | over)
+        if spec.site_codes:  # (the rows inside the bins, each to its key)
+            inside, outside = self._site_rows(occupancy, ns * R)
+            np.add.at(self.site_counts, q[ok].astype(np.int64), inside[ok])
+            np.add.at(self.site_over, q[ok].astype(np.int64), outside[ok])
         x, key = x[ok], q[ok].astype(np.int64)
         # the rank of a row among the rows of its key, in row order
         order = np.argsort(key, kind="stable")
@@ -566,10 +628,15 @@ class StatisticsRecord:
         merge of Chan et al. of n / shift / s1 / s2 (the second record's sums are moved to the first one's shift) and the
         sum of the histograms.  The blocking arrays are NOT merged (a block of 2^l samples does not span two records):
         the result has n_levels = 0.  Binned records of ONE spec merge key by key in the same way and their outside
-        counters add; records of different modes, or binned ones of different bins, are refused."""
+        counters add; records of different modes, or binned ones of different bins, are refused.  Site fields of the same
+        sites and codes add; records of different fields are refused."""
         records = list(records)
         a = records[0]
         for b in records[1:]:
+            if b.site_counts.shape != a.site_counts.shape or (a.spec.site_codes and not np.array_equal(
+                    a.spec.site_list(a.site_counts.shape[1]), b.spec.site_list(b.site_counts.shape[1]))):
+                raise ValueError(f"combine: records of different site fields ({a.site_counts.shape[1:]} and "
+                                 f"{b.site_counts.shape[1:]} sites x codes, or different site lists)")
             if b.spec.key != a.spec.key or b.spec.binned != a.spec.binned:
                 raise ValueError(f"combine: records of different key modes ({_MODE_NAMES.get(a.spec.key, a.spec.key)} and "
                                  f"{_MODE_NAMES.get(b.spec.key, b.spec.key)})")
@@ -577,10 +644,11 @@ class StatisticsRecord:
                 raise ValueError(f"combine: binned records of different bins ({a.spec.c_bins()} and {b.spec.c_bins()})")
         spec = Statistics(a.spec.key, a.spec.columns, a.spec.weights, 0,
                           None if not a.spec.n_bins else (a.spec.columns[a.spec.hist_column], a.spec.n_bins, a.spec.hist_min, a.spec.hist_bin),
-                          bins=None if not a.spec.binned else (a.spec.columns[a.spec.key_column],) + a.spec.c_bins()[1:])
-        out = cls(spec, a.n_keys)
+                          bins=None if not a.spec.binned else (a.spec.columns[a.spec.key_column],) + a.spec.c_bins()[1:],
+                          sites=a.spec.sites, site_codes=a.spec.site_codes)
+        out = cls(spec, a.n_keys, a.site_counts.shape[1])
         out.key_under, out.key_over = a.key_under, a.key_over
-        for f in ("n", "shift", "s1", "s2", "hist", "under", "over"):
+        for f in ("n", "shift", "s1", "s2", "hist", "under", "over") + _SITE_ARRAYS:
             setattr(out, f, getattr(a, f).copy())
         ia, ib = np.triu_indices(spec.n_columns)
         for b in records[1:]:
@@ -597,6 +665,8 @@ class StatisticsRecord:
             out.over = out.over + b.over
             out.key_under += b.key_under
             out.key_over += b.key_over
+            out.site_counts = out.site_counts + b.site_counts
+            out.site_over = out.site_over + b.site_over
         return out
 
     def reweight(self, temperature_from, temperature_to):
@@ -689,13 +759,47 @@ class StatisticsRecord:
         var = (w * (within[None, :] + (e[None, :] - mean[:, None]) ** 2)).sum(axis=1)
         return var / (KB * T * T)
 
+    # ---- the site field --------------------------------------------------------------------------------------------------
+    def _with_sites(self, what):
+        if not self.spec.site_codes:
+            raise ValueError(f"{what} needs a record with a site field (Statistics(..., sites=, site_codes=))")
+
+    def site_occupancy(self):
+        """(n_keys, M, S): site_counts / n, how often tracked site m held code s among the rows of key k; NaN where
+        n == 0."""
+        self._with_sites("site_occupancy")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.site_counts / self.n[:, None, None].astype(np.float64)
+
+    def sublattice_occupancy(self, classes):
+        """(n_keys, n_classes, S): the mean of ``site_occupancy`` over each class of sites; ``classes`` is a sequence of
+        index lists into the TRACKED sites (positions 0 .. M - 1 of the field, not site numbers)."""
+        p = self.site_occupancy()
+        return np.stack([p[:, np.asarray(c, dtype=np.int64), :].mean(axis=1) for c in classes], axis=1)
+
+    def frozen_order(self):
+        """(n_keys,): mean_m sum_s p_m(s)^2 less the same number for the key's mean composition over the tracked sites,
+        sum_s (mean_m p_m(s))^2.  0 for a field that is uniform over the sites (a walker that visits every ordering
+        variant alike, or a disordered state), 1 - sum_s x_s^2 for a walker frozen in one configuration of composition
+        x."""
+        p = self.site_occupancy()
+        return (p * p).sum(axis=2).mean(axis=1) - (p.mean(axis=1) ** 2).sum(axis=1)
+
+    def canonical_sites(self, ln_g, temperatures, level_values=None):
+        """(nT, M, S): the site field at every temperature from a record keyed by bin, sum_k w_k(T) p_k with p_k the field
+        of level k (``site_occupancy``) and the weights of ``canonical``."""
+        self._only_binned("canonical_sites")
+        p = self.site_occupancy()
+        use, _, w = self._canonical_weights(ln_g, temperatures, level_values)
+        return np.tensordot(w, p[use], axes=(1, 0))
+
     def equals(self, other):
-        return (all(np.array_equal(getattr(self, f), getattr(other, f), equal_nan=True) for f in _ARRAYS)
+        return (all(np.array_equal(getattr(self, f), getattr(other, f), equal_nan=True) for f in _ARRAYS + _SITE_ARRAYS)
                 and (self.key_under, self.key_over) == (other.key_under, other.key_over))
 
     def copy(self):
-        out = StatisticsRecord(self.spec, self.n_keys)
-        for f in _ARRAYS:
+        out = StatisticsRecord(self.spec, self.n_keys, self.site_counts.shape[1])
+        for f in _ARRAYS + _SITE_ARRAYS:
             setattr(out, f, getattr(self, f).copy())
         out.key_under, out.key_over = self.key_under, self.key_over
         return out
