@@ -651,6 +651,46 @@ int smolmc_statistics_sites_shape(smolmc_handle *h, int *n_sites, int *n_codes);
  * order: tracked site m is the m-th entry of the list given (on a relabelled handle the engine reads byte new_of[p] of a
  * ring row for the caller's site p, as smolmc_get_minima does).  Waits for the handle's stream. */
 int smolmc_get_statistics_sites(smolmc_handle *h, int64_t *site_counts, int64_t *site_over);
+/* ---- the joint field of a statistics record: a histogram of TWO columns, per key ----------------------------------------
+ * A record may carry a JOINT FIELD: joint[n_keys][n_a][n_b] and joint_out[n_keys], int64.  column_a and column_b are
+ * indices into the record's columns, like hist_column; they may be equal.  For every row that the record's rule offers to
+ * key k -- the rows that increment n[k] in any of the three key modes: one per key and sample by walker and by state
+ * point, the rows inside the bins in SMOLMC_STAT_BY_BIN, never a row counted in key_under / key_over --
+ *   qa = floor((x[column_a] - min_a) / bin_a),  qb = floor((x[column_b] - min_b) / bin_b)
+ * as numpy.floor_divide gives them, and
+ *   both values finite, 0 <= qa < n_a and 0 <= qb < n_b:   joint[k][qa][qb] += 1
+ *   otherwise:                                             joint_out[k] += 1
+ * This is the floor division of the histogram and of the Wang-Landau step with one difference: a value below min is
+ * ALWAYS outside.  The histogram's division puts x with -ulp(bin) / 2 <= x - min < 0 in bin 0 (its remainder x - min + bin
+ * rounds to bin), so for one column with one min and bin the sum of joint over the other axis and hist can differ by the
+ * rows that lie that close below min; everywhere else the two agree.
+ * Hence
+ *   sum over qa, qb of joint[k][qa][qb] + joint_out[k] == n[k]
+ * as long as field and record were reset together.  joint[k] is H_k(a, b), the joint histogram of key k: with the key a
+ * state point of a semigrand handle, column_a the energy (the weighted sum of the features with weight 0 on the
+ * chemical-work feature; NOT the enthalpy column, which already contains -mu N) and column_b a kind count it is what
+ * reweighting in T and mu, the multiple-histogram method and the equal-weight rule read.  Sums of integers: the field does
+ * not depend on the order of the adds, and the device equals smol_amd/statistics.py (StatisticsRecord.offer) entry for
+ * entry.
+ *
+ * Attaches a field to the record IN FORCE, in any key mode, and zeroes the field (the record's other accumulators and a
+ * site field stay); n_a = 0 detaches it (nothing else is read).  Refused, each naming its reason and leaving record and
+ * fields untouched: no record set; n_a outside 0..65536 or n_b outside 1..65536; a bin width that is not a positive finite
+ * number or a minimum that is not finite; a column outside the record's columns; record plus both fields larger than
+ * 1 GiB (smolmc_set_statistics_sites counts a joint field in force likewise); while a block recorded with
+ * SMOLMC_SAMPLE_STATISTICS waits in the ring.  Setting a record (smolmc_set_statistics, smolmc_set_statistics_binned)
+ * drops the field, smolmc_reset_statistics also clears it, smolmc_update_statistics offers the walkers' current states to
+ * it as well.  A joint field and a site field may be attached together.  The field's launch is one more mode of the
+ * record's kernel, ordered on the handle's stream behind the record's launches; a record without a joint field launches
+ * what it launched.  Waits for the handle's stream. */
+#define SMOLMC_MAX_STAT_JOINT_CELLS 65536
+int smolmc_set_statistics_joint(smolmc_handle *h, int column_a, int n_a, double min_a, double bin_a, int column_b, int n_b,
+                                double min_b, double bin_b);
+/* the field in force (all 0: none set); any pointer may be NULL */
+int smolmc_statistics_joint_shape(smolmc_handle *h, int *column_a, int *n_a, double *min_a, double *bin_a, int *column_b, int *n_b,
+                                  double *min_b, double *bin_b);
+/* The field: joint [n_keys x n_a x n_b], joint_out [n_keys]; either pointer may be NULL.  Waits for the handle's stream. */
+int smolmc_get_statistics_joint(smolmc_handle *h, int64_t *joint, int64_t *joint_out);
 
 /* ---- structure factors: fixed-point amplitudes and intensities of sampled states, reduced on the device ---------------
  * (no reference counterpart).  Kinds as in smolmc_observables: the kind of (site, code) is kind_base[site] + code,

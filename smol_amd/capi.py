@@ -209,6 +209,7 @@ class smolmc_minima(C.Structure):
 STAT_BY_WALKER, STAT_BY_STATE_POINT, STAT_BY_BIN = 0, 1, 2  # SMOLMC_STAT_BY_*: the key modes of a statistics record
 MAX_STAT_KEYS = 65536  # SMOLMC_MAX_STAT_KEYS: the bins of a record keyed by bin (smolmc_set_statistics_binned)
 MAX_STAT_SITE_CODES = 16  # SMOLMC_MAX_STAT_SITE_CODES: the codes of a record's site field (smolmc_set_statistics_sites)
+MAX_STAT_JOINT_CELLS = 65536  # SMOLMC_MAX_STAT_JOINT_CELLS: the cells of an axis of a record's joint field (smolmc_set_statistics_joint)
 
 
 class smolmc_statistics(C.Structure):

@@ -929,6 +929,14 @@ struct SmolmcStat {
     long long *site_over = nullptr;    // [n_keys]
     int32_t *site_idx = nullptr;       // [M] byte of a ring row of tracked site m, or null: byte m (all sites, not relabelled)
     hipEvent_t site_ev[2] = {nullptr, nullptr}; // around the field's last launch
+    // the joint field (smolmc_set_statistics_joint): an allocation of its own, attached to the record in force
+    int joint_col[2] = {0, 0}, joint_n[2] = {0, 0};   // axes a and b: index into the columns, cells (joint_n[0] == 0: no field)
+    double joint_min[2] = {0.0, 0.0}, joint_bin[2] = {0.0, 0.0};
+    unsigned char *joint_arena = nullptr;
+    size_t joint_bytes = 0;            // joint and joint_out: what a reset zeroes
+    long long *joint = nullptr;        // [n_keys x n_a x n_b]
+    long long *joint_out = nullptr;    // [n_keys]
+    hipEvent_t joint_ev[2] = {nullptr, nullptr}; // around the field's last launch
 };
 
 // structure.hip: the structure-factor spec of a handle (smolmc_set_structure) as the kernel reads it, engine numbering

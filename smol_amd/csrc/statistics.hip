@@ -41,6 +41,18 @@
 //                      changes or the tile ends; rows outside the bins are skipped.  The counters of a site are 16 bytes
 //                      packed in two 64-bit registers (a flush at the latest after ST_SITE_FLUSH rows); the codes outside
 //                      the field go to site_over with one atomic per wave and flush.  No LDS.
+//
+// The JOINT FIELD (smolmc_set_statistics_joint) counts, per key, the rows in the cells of two columns: joint[n_keys][n_a][n_b]
+// and joint_out[n_keys], sums of integers again.  One more mode of statistics_kernel, launched behind the others:
+//   statistics_joint   by walker or state point one THREAD per key: it walks the key's row of every sample and adds to the
+//                      key's cells as their only owner (neighbouring lanes read neighbouring rows), joint_out once at the
+//                      end.  Keyed by bin one thread per row, read with the key the key pass left in row_key; rows outside
+//                      the bins are skipped.  Equal targets of a wave are merged before the atomic: in each of
+//                      ST_JOINT_ROUNDS rounds the first lane still waiting names its counter, the lanes with the same
+//                      counter are counted by ballot and leave, and the first lane sends ONE 64-bit add of that count; what
+//                      waits after the rounds goes out as one atomic per lane.  A wave whose rows all meet in one cell sends
+//                      one atomic, a wave of 64 different cells pays the rounds and 64 - ST_JOINT_ROUNDS atomics.  No LDS.
+//                      Its arguments lie where the record's accumulator pointers do, which it does not read.
 #include "smolmc_common.h"
 #include <thread>
 
@@ -59,6 +71,8 @@
 #define ST_SITE_OWN 2       // tracked sites a thread owns
 #define ST_SITE_FLUSH 255   // rows a thread counts between two flushes: its counters are bytes
 #define ST_SITE_TILE_MIN 16 // rows of a tile of the binned site pass
+#define ST_MODE_JOINT 4     // statistics_joint
+#define ST_JOINT_ROUNDS 4   // rounds of merging equal targets within a wave before the lanes that still wait add alone
 
 struct StatArgs {
     // the rows.  The site field (mode 3) reads none of the columns: its arguments lie in their place, and the kernel's
@@ -81,10 +95,20 @@ struct StatArgs {
     };
     const int32_t *env;        // [rows x EC] or null: the cells of the environment spec in force
     const int32_t *walker_at;  // key -> walker, or null: the identity
-    // the record
-    long long *n, *nb, *hist, *under, *over;
-    double *shift, *s1, *s2, *pend, *b2;
-    uint64_t *has;
+    // the record.  The joint field (mode 4) reads the columns and none of the accumulators: its arguments lie in their place
+    union {
+        struct {
+            long long *n, *nb, *hist, *under, *over;
+            double *shift, *s1, *s2, *pend, *b2;
+            uint64_t *has;
+        };
+        struct { // mode 4; row_key null: one thread per key, else one thread per row
+            unsigned long long *joint;     // [n_keys x n_a x n_b]
+            unsigned long long *joint_out; // [n_keys], in the allocation of `joint`
+            double joint_min_a, joint_bin_a, joint_min_b, joint_bin_b;
+            int joint_col_a, joint_n_a, joint_col_b, joint_n_b; // the columns are indices into `columns`
+        };
+    };
     // the spec
     const int32_t *columns;    // [C]
     const double *weights;     // [n_weights]
@@ -101,7 +125,8 @@ struct StatArgs {
     unsigned long long *outside; // key_under, key_over of the record
     long long rows;              // nsamples x R
 };
-static_assert(sizeof(StatArgs) == 304, "the site field's arguments lie in the place of the column pointers");
+static_assert(sizeof(StatArgs) == 304, "the site field's arguments lie in the place of the column pointers, the joint field's in "
+                                        "the place of the accumulator pointers");
 
 // column source `src` of row `row`: 0 the enthalpy, 1 + i feature i, 1 + F + k kind count k, 1 + F + K the weighted sum,
 // 2 + F + K + i intensity i, 2 + F + K + I + c connectivity number c (24 per graph) as a double, 2 + F + K + I + CS + c
@@ -346,6 +371,64 @@ __device__ __forceinline__ void statistics_sites(const StatArgs &A) {
     if (cur >= 0) stat_sites_flush(A, cur, m_first, binned, lo, hi, over);
 }
 
+// ---- the joint field --------------------------------------------------------------------------------------------------------
+// the cell of a value on an axis of n cells, or -1: below min, at or beyond min + n bin, or not finite (the rule of the
+// histogram)
+__device__ __forceinline__ int stat_joint_cell(double xv, double vmin, double vbin, int n) {
+#pragma clang fp contract(off)
+    const double d = xv - vmin;
+    const double q = floordiv_exact(d, vbin);
+    if (!(fabs(xv) <= 1.7976931348623157e308) || !(q == q)) return -1; // (not finite)
+    // d < 0 on its own account: for -ulp(vbin) / 2 <= d < 0 the remainder d + vbin of floordiv_exact rounds to vbin and q
+    // comes out 0, where the floor is -1 (the one case in which it is not np.floor_divide: |d| < vbin, d < 0)
+    if (d < 0.0 || q < 0.0 || q >= (double)n) return -1;
+    return (int)q;
+}
+
+// mode 4 of statistics_kernel
+__device__ __forceinline__ void statistics_joint(const StatArgs &A) {
+    const long long unit = (long long)blockIdx.x * ST_THREADS + threadIdx.x; // a key, or a row
+    const int src_a = A.columns[A.joint_col_a], src_b = A.columns[A.joint_col_b];
+    const size_t cells = (size_t)A.joint_n_a * (size_t)A.joint_n_b;
+    if (A.row_key == nullptr) { // (uniform over the launch) the key's only owner: plain adds
+        if (unit >= A.n_keys) return;
+        const size_t walker = A.walker_at ? (size_t)A.walker_at[unit] : (size_t)unit;
+        unsigned long long *mine = A.joint + (size_t)unit * cells;
+        unsigned long long out = 0;
+        for (long long s = 0; s < A.nsamples; ++s) {
+            const size_t row = (size_t)s * A.R + walker;
+            const int qa = stat_joint_cell(stat_column(A, row, src_a), A.joint_min_a, A.joint_bin_a, A.joint_n_a);
+            const int qb = stat_joint_cell(stat_column(A, row, src_b), A.joint_min_b, A.joint_bin_b, A.joint_n_b);
+            if (qa >= 0 && qb >= 0) mine[(size_t)qa * A.joint_n_b + qb] += 1;
+            else ++out;
+        }
+        if (out) A.joint_out[unit] += out;
+        return;
+    }
+    // keyed by bin: every lane of the wave stays to the end (the rounds below are wave-wide)
+    const int key = unit < A.rows ? A.row_key[unit] : -1;
+    bool waiting = key >= 0; // rows outside the bins touch nothing
+    unsigned long long target = 0; // the row's counter, counted from `joint`
+    if (waiting) {
+        const int qa = stat_joint_cell(stat_column(A, (size_t)unit, src_a), A.joint_min_a, A.joint_bin_a, A.joint_n_a);
+        const int qb = stat_joint_cell(stat_column(A, (size_t)unit, src_b), A.joint_min_b, A.joint_bin_b, A.joint_n_b);
+        target = qa >= 0 && qb >= 0 ? (unsigned long long)key * cells + (size_t)qa * A.joint_n_b + qb
+                                    : (unsigned long long)(A.joint_out - A.joint) + (unsigned long long)key;
+    }
+    const int lane = threadIdx.x & 63;
+    for (int round = 0; round < ST_JOINT_ROUNDS; ++round) {
+        const unsigned long long todo = __ballot(waiting);
+        if (!todo) break; // (uniform over the wave)
+        const int first = __ffsll((long long)todo) - 1;
+        const unsigned long long named = __shfl(target, first);
+        const bool same = waiting && target == named;
+        const unsigned long long mask = __ballot(same);
+        if (lane == first) atomicAdd(A.joint + named, (unsigned long long)__popcll(mask));
+        waiting = waiting && !same;
+    }
+    if (waiting) atomicAdd(A.joint + target, 1ull);
+}
+
 __global__ void __launch_bounds__(ST_THREADS) statistics_kernel(const StatArgs A) {
     // Every product and every sum is rounded on its own, as NumPy does it (see weighted_value_rn, smolmc_common.h).
 #pragma clang fp contract(off)
@@ -354,16 +437,12 @@ __global__ void __launch_bounds__(ST_THREADS) statistics_kernel(const StatArgs A
     __shared__ double s_pend[ST_MAXL * ST_MAXC], s_b2[ST_MAXL * ST_MAXC];
     __shared__ long long s_nb[ST_MAXL];
     static_assert(ST_QUEUE * sizeof(int) <= sizeof(s_pend) && ST_WAVES * sizeof(int) <= sizeof(s_nb), "the queue of the binned mode");
-    if (A.mode == ST_MODE_KEYS) { // (uniform over the launch)
-        stat_bin_keys(A);
-        return;
-    }
-    if (A.mode == ST_MODE_BINNED) {
-        statistics_binned(A, s_x, s_shift, reinterpret_cast<int *>(s_pend), reinterpret_cast<int *>(s_nb));
-        return;
-    }
-    if (A.mode == ST_MODE_SITES) {
-        statistics_sites(A);
+    if (__builtin_expect(A.mode != 0, 0)) { // (uniform over the launch) one test in front of mode 0, the others' code behind it
+        if (A.mode == ST_MODE_KEYS) stat_bin_keys(A);
+        else if (A.mode == ST_MODE_BINNED)
+            statistics_binned(A, s_x, s_shift, reinterpret_cast<int *>(s_pend), reinterpret_cast<int *>(s_nb));
+        else if (A.mode == ST_MODE_SITES) statistics_sites(A);
+        else if (A.mode == ST_MODE_JOINT) statistics_joint(A);
         return;
     }
     const int key = blockIdx.x, tid = threadIdx.x;
@@ -503,6 +582,32 @@ static int stat_sites_launch(smolmc_handle *h, StatArgs A, const uint8_t *d_occ8
     return 0;
 }
 
+// the joint field's launch, behind the launches of `A` on the handle's stream (a binned record: behind its key pass, whose
+// row keys it reads)
+static int stat_joint_launch(smolmc_handle *h, StatArgs A) {
+    SmolmcStat &S = h->stats;
+    A.mode = ST_MODE_JOINT;
+    A.n_keys = S.n_keys;
+    A.joint = (unsigned long long *)S.joint; A.joint_out = (unsigned long long *)S.joint_out;
+    A.joint_col_a = S.joint_col[0]; A.joint_n_a = S.joint_n[0]; A.joint_min_a = S.joint_min[0]; A.joint_bin_a = S.joint_bin[0];
+    A.joint_col_b = S.joint_col[1]; A.joint_n_b = S.joint_n[1]; A.joint_min_b = S.joint_min[1]; A.joint_bin_b = S.joint_bin[1];
+    const size_t units = S.key == SMOLMC_STAT_BY_BIN ? (size_t)A.rows : (size_t)S.n_keys; // a row or a key per thread
+    if (!S.joint_ev[0])
+        for (hipEvent_t &e : S.joint_ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventRecord(S.joint_ev[0], h->stream));
+    hipLaunchKernelGGL(statistics_kernel, dim3((unsigned)((units + ST_THREADS - 1) / ST_THREADS)), dim3(ST_THREADS), 0, h->stream, A);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.joint_ev[1], h->stream));
+    return 0;
+}
+
+// the fields of the record, each a launch of its own behind the record's
+static int stat_fields_launch(smolmc_handle *h, const StatArgs &A, const uint8_t *d_occ8) {
+    if (h->stats.site_S) TRY(stat_sites_launch(h, A, d_occ8));
+    if (h->stats.joint_n[0]) TRY(stat_joint_launch(h, A));
+    return 0;
+}
+
 int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat, const int32_t *d_counts, const double *d_inten,
                        const long long *d_conn, const int32_t *d_pat, const int32_t *d_env, long long nsamples,
                        const uint8_t *d_occ8) {
@@ -553,13 +658,13 @@ int smolmc_stat_launch(smolmc_handle *h, const double *d_H, const double *d_feat
         hipLaunchKernelGGL(statistics_kernel, dim3((unsigned)S.n_keys), dim3(ST_THREADS), 0, h->stream, A);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(S.ev[1], h->stream));
-        return S.site_S ? stat_sites_launch(h, A, d_occ8) : 0;
+        return S.site_S || S.joint_n[0] ? stat_fields_launch(h, A, d_occ8) : 0;
     }
     HIPCHK(hipEventRecord(S.ev[0], h->stream));
     hipLaunchKernelGGL(statistics_kernel, dim3((unsigned)S.n_keys), dim3(ST_THREADS), 0, h->stream, A);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(S.ev[1], h->stream));
-    return S.site_S ? stat_sites_launch(h, A, d_occ8) : 0;
+    return S.site_S || S.joint_n[0] ? stat_fields_launch(h, A, d_occ8) : 0;
 }
 
 // the field of the record goes (smolmc_set_statistics_sites with n_codes = 0, a new spec, the handle's end)
@@ -576,11 +681,26 @@ static void stat_sites_free(SmolmcStat &S) {
     S.site_bytes = 0;
 }
 
+// likewise the joint field (smolmc_set_statistics_joint with n_a = 0, a new spec, the handle's end)
+static void stat_joint_free(SmolmcStat &S) {
+    if (S.joint_arena) hipFree(S.joint_arena);
+    for (hipEvent_t &e : S.joint_ev) {
+        if (e) hipEventDestroy(e);
+        e = nullptr;
+    }
+    S.joint_arena = nullptr;
+    S.joint = S.joint_out = nullptr;
+    S.joint_col[0] = S.joint_col[1] = S.joint_n[0] = S.joint_n[1] = 0;
+    S.joint_min[0] = S.joint_min[1] = S.joint_bin[0] = S.joint_bin[1] = 0.0;
+    S.joint_bytes = 0;
+}
+
 void smolmc_stat_free(smolmc_handle *h) {
     SmolmcStat &S = h->stats;
     if (S.arena) hipFree(S.arena);
     if (S.row_key) hipFree(S.row_key);
     stat_sites_free(S);
+    stat_joint_free(S);
     for (hipEvent_t e : S.ev)
         if (e) hipEventDestroy(e);
     S = SmolmcStat();
@@ -782,6 +902,7 @@ extern "C" int smolmc_reset_statistics(smolmc_handle *h) {
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemset(S.arena, 0, S.record_bytes));
     if (S.site_S) HIPCHK(hipMemset(S.site_arena, 0, S.site_bytes));
+    if (S.joint_n[0]) HIPCHK(hipMemset(S.joint_arena, 0, S.joint_bytes));
     HIPCHK(hipDeviceSynchronize());
     return 0;
 }
@@ -840,7 +961,7 @@ extern "C" int smolmc_set_statistics_sites(smolmc_handle *h, const int32_t *site
     }
     const size_t nk = (size_t)S.n_keys;
     const size_t o_over = up256(nk * (size_t)M * (size_t)n_codes * 8), o_idx = o_over + up256(nk * 8);
-    if (n_codes && S.record_bytes + o_idx > ((size_t)1 << 30)) {
+    if (n_codes && S.record_bytes + S.joint_bytes + o_idx > ((size_t)1 << 30)) { // (joint_bytes: the joint field in force)
         snprintf(msg, sizeof msg, "statistics sites: a record of %zu bytes and a field of %zu keys x %d sites x %d codes are larger than "
                  "1 GiB", S.record_bytes, nk, M, n_codes);
         return fail(msg);
@@ -916,6 +1037,108 @@ extern "C" int smolmc_get_statistics_sites(smolmc_handle *h, int64_t *site_count
         }
     }
     if (site_over) HIPCHK(hipMemcpy(site_over, S.site_over, nk * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- the joint field: the rows of every key in the cells of two columns ---------------------------------------------------
+extern "C" int smolmc_set_statistics_joint(smolmc_handle *h, int column_a, int n_a, double min_a, double bin_a, int column_b, int n_b,
+                                           double min_b, double bin_b) {
+    if (!h) return fail("null handle");
+    SmolmcStat &S = h->stats;
+    if (!S.n_keys) return fail("statistics joint: no statistics record set (call smolmc_set_statistics first)");
+    char msg[256];
+    if (n_a < 0 || n_a > SMOLMC_MAX_STAT_JOINT_CELLS) {
+        snprintf(msg, sizeof msg, "statistics joint: n_a must be 0..%d, got %d", SMOLMC_MAX_STAT_JOINT_CELLS, n_a);
+        return fail(msg);
+    }
+    size_t o_out = 0, bytes = 0;
+    if (n_a) {
+        if (n_b < 1 || n_b > SMOLMC_MAX_STAT_JOINT_CELLS) {
+            snprintf(msg, sizeof msg, "statistics joint: n_b must be 1..%d, got %d", SMOLMC_MAX_STAT_JOINT_CELLS, n_b);
+            return fail(msg);
+        }
+        if (!(bin_a > 0.0) || !std::isfinite(bin_a) || !std::isfinite(min_a))
+            return fail("statistics joint: bin_a must be a positive finite number and min_a finite");
+        if (!(bin_b > 0.0) || !std::isfinite(bin_b) || !std::isfinite(min_b))
+            return fail("statistics joint: bin_b must be a positive finite number and min_b finite");
+        if (column_a < 0 || column_a >= S.C) {
+            snprintf(msg, sizeof msg, "statistics joint: column_a = %d is no index into the %d columns", column_a, S.C);
+            return fail(msg);
+        }
+        if (column_b < 0 || column_b >= S.C) {
+            snprintf(msg, sizeof msg, "statistics joint: column_b = %d is no index into the %d columns", column_b, S.C);
+            return fail(msg);
+        }
+        const size_t nk = (size_t)S.n_keys;
+        o_out = up256(nk * (size_t)n_a * (size_t)n_b * 8); // (at most 2^51)
+        bytes = o_out + up256(nk * 8);
+        if (S.record_bytes + S.site_bytes + bytes > ((size_t)1 << 30)) {
+            snprintf(msg, sizeof msg, "statistics joint: a record of %zu bytes, a site field of %zu bytes and a joint field of %zu keys x "
+                     "%d x %d cells are larger than 1 GiB", S.record_bytes, S.site_bytes, nk, n_a, n_b);
+            return fail(msg);
+        }
+    }
+    TRY(smolmc_ring_guard(h, SMOLMC_SAMPLE_STATISTICS, "smolmc_set_statistics_joint", "SMOLMC_SAMPLE_STATISTICS"));
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream)); // (queued launches still add to the field in force)
+    if (!n_a) {
+        stat_joint_free(S);
+        return 0;
+    }
+    unsigned char *arena = nullptr;
+    HIPCHK(hipMalloc((void **)&arena, bytes));
+    hipError_t e = hipMemset(arena, 0, bytes); // (an empty field is all zeros)
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        hipFree(arena);
+        return fail(std::string("statistics joint: ") + hipGetErrorString(e));
+    }
+    stat_joint_free(S);
+    S.joint_arena = arena;
+    S.joint_bytes = bytes;
+    S.joint = (long long *)arena;
+    S.joint_out = (long long *)(arena + o_out);
+    S.joint_col[0] = column_a; S.joint_n[0] = n_a; S.joint_min[0] = min_a; S.joint_bin[0] = bin_a;
+    S.joint_col[1] = column_b; S.joint_n[1] = n_b; S.joint_min[1] = min_b; S.joint_bin[1] = bin_b;
+    return 0;
+}
+
+extern "C" int smolmc_statistics_joint_shape(smolmc_handle *h, int *column_a, int *n_a, double *min_a, double *bin_a, int *column_b,
+                                             int *n_b, double *min_b, double *bin_b) {
+    if (!h) return fail("null handle");
+    const SmolmcStat &S = h->stats;
+    if (column_a) *column_a = S.joint_col[0];
+    if (n_a) *n_a = S.joint_n[0];
+    if (min_a) *min_a = S.joint_min[0];
+    if (bin_a) *bin_a = S.joint_bin[0];
+    if (column_b) *column_b = S.joint_col[1];
+    if (n_b) *n_b = S.joint_n[1];
+    if (min_b) *min_b = S.joint_min[1];
+    if (bin_b) *bin_b = S.joint_bin[1];
+    return 0;
+}
+
+extern "C" int smolmc_get_statistics_joint(smolmc_handle *h, int64_t *joint, int64_t *joint_out) {
+    if (!h) return fail("null handle");
+    const SmolmcStat &S = h->stats;
+    if (!S.joint_n[0]) return fail("no joint field set: call smolmc_set_statistics_joint first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t nk = (size_t)S.n_keys;
+    if (joint) HIPCHK(hipMemcpy(joint, S.joint, nk * (size_t)S.joint_n[0] * (size_t)S.joint_n[1] * 8, hipMemcpyDeviceToHost));
+    if (joint_out) HIPCHK(hipMemcpy(joint_out, S.joint_out, nk * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// elapsed device time of the joint field's last launch in ms (tools/statistics_joint_timing.py); a measuring hook like the
+// ones below, not part of the C-ABI
+extern "C" int smolmc_debug_statistics_joint_kernel_ms(smolmc_handle *h, float *ms) {
+    if (!h || !ms) return fail("null argument");
+    const SmolmcStat &S = h->stats;
+    if (!S.joint_ev[0]) return fail("the joint field's kernel has not been launched yet");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipEventSynchronize(S.joint_ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, S.joint_ev[0], S.joint_ev[1]));
     return 0;
 }
 

@@ -80,6 +80,10 @@ SYMBOLS = {
     "smolmc_set_statistics_sites": (C.c_int, [_HP, _i32p, C.c_int, C.c_int]),
     "smolmc_statistics_sites_shape": (C.c_int, [_HP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "smolmc_get_statistics_sites": (C.c_int, [_HP, _i64p, _i64p]),
+    "smolmc_set_statistics_joint": (C.c_int, [_HP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "smolmc_statistics_joint_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                                        C.POINTER(C.c_double)] * 2),
+    "smolmc_get_statistics_joint": (C.c_int, [_HP, _i64p, _i64p]),
     "smolmc_set_structure": (C.c_int, [_HP, C.POINTER(capi.smolmc_structure)]),
     "smolmc_structure_shape": (C.c_int, [_HP] + [C.POINTER(C.c_int)] * 3),
     "smolmc_eval_structure": (C.c_int, [_HP, _i32p, C.c_int, _i64p, _f64p]),
@@ -850,7 +854,8 @@ class Engine:
         smolmc_set_statistics_binned, which refuses likewise blocking levels, ``n_keys`` outside 1..65536, a bin width that
         is not positive and finite and a key column outside the columns.  A spec with a site field
         (``Statistics(..., sites=, site_codes=)``) attaches it to the new record (smolmc_set_statistics_sites); when the
-        engine refuses the field, the handle is left without a record."""
+        engine refuses the field, the handle is left without a record.  A spec with a joint field
+        (``Statistics(..., joint=)``) attaches that one next (smolmc_set_statistics_joint), with the same rule."""
         # (what ``statistics.segments`` takes: F, then every family's size in force, in the table's order)
         shape = () if spec is None else (self.F,) + tuple(self._family_sizes(fam)[fam.stat[2]] for fam in FAMILIES)
         bins = None if spec is None else spec.c_bins()
@@ -862,13 +867,16 @@ class Engine:
             del keep
         self.statistics_spec = spec
         field = None if spec is None else spec.c_sites()
-        if field is not None:
-            try:
+        joint = None if spec is None else spec.c_joint()
+        try:
+            if field is not None:
                 self.set_statistics_sites(*field)
-            except (EngineError, ValueError):
-                self._chk(self._lib.smolmc_set_statistics(self._h, None))
-                self.statistics_spec = None
-                raise
+            if joint is not None:
+                self.set_statistics_joint(*joint)
+        except (EngineError, ValueError):
+            self._chk(self._lib.smolmc_set_statistics(self._h, None))
+            self.statistics_spec = None
+            raise
 
     def set_statistics_sites(self, sites, n_sites, n_codes):
         """smolmc_set_statistics_sites as it stands: attach a site field of ``n_codes`` codes on the sites ``sites`` (an
@@ -882,6 +890,20 @@ class Engine:
         m, c = C.c_int(), C.c_int()
         self._chk(self._lib.smolmc_statistics_sites_shape(self._h, C.byref(m), C.byref(c)))
         return int(m.value), int(c.value)
+
+    def set_statistics_joint(self, column_a, n_a, min_a, bin_a, column_b=0, n_b=0, min_b=0.0, bin_b=0.0):
+        """smolmc_set_statistics_joint as it stands: attach a joint field of ``n_a`` x ``n_b`` cells of the record's columns
+        ``column_a`` and ``column_b`` (indices into the columns) to the record in force and zero the field; ``n_a = 0``
+        detaches it.  ``set_statistics`` calls this for a spec that has a field (``Statistics.c_joint``)."""
+        self._chk(self._lib.smolmc_set_statistics_joint(self._h, int(column_a), int(n_a), float(min_a), float(bin_a),
+                                                        int(column_b), int(n_b), float(min_b), float(bin_b)))
+
+    def statistics_joint_shape(self):
+        """(column_a, n_a, min_a, bin_a, column_b, n_b, min_b, bin_b) of the joint field in force, zeros when none is set
+        (smolmc_statistics_joint_shape)."""
+        v = [t() for t in (C.c_int, C.c_int, C.c_double, C.c_double) * 2]
+        self._chk(self._lib.smolmc_statistics_joint_shape(self._h, *[C.byref(x) for x in v]))
+        return tuple(float(x.value) if isinstance(x, C.c_double) else int(x.value) for x in v)
 
     def statistics_bins(self):
         """(key_column, n_keys, key_min, key_bin, key_under, key_over) of the binned record in force, all zeros when the
@@ -914,6 +936,9 @@ class Engine:
         rec = StatisticsRecord(self.statistics_spec, self.R, n_sites)
         if rec.site_counts.shape[1:] != (n_sites, n_codes):
             raise EngineError(f"the handle's site field has shape {(n_sites, n_codes)}, the spec gives {rec.site_counts.shape[1:]}")
+        joint = self.statistics_joint_shape()
+        if joint != (rec.spec.c_joint() or (0, 0, 0.0, 0.0) * 2):
+            raise EngineError(f"the handle's joint field is {joint}, the spec gives {rec.spec.c_joint()}")
         shape = self.statistics_shape()
         want = (rec.n_keys, rec.spec.n_columns, rec.spec.n_levels, rec.spec.n_bins)
         if shape != want:
@@ -926,6 +951,8 @@ class Engine:
             rec.key_under, rec.key_over = self.statistics_bins()[4:]
         if n_codes:
             self._chk(self._lib.smolmc_get_statistics_sites(self._h, _p(rec.site_counts, C.c_int64), _p(rec.site_over, C.c_int64)))
+        if joint[1]:
+            self._chk(self._lib.smolmc_get_statistics_joint(self._h, _p(rec.joint, C.c_int64), _p(rec.joint_out, C.c_int64)))
         return rec
 
     def statistics_kernel_ms(self):
@@ -942,6 +969,11 @@ class Engine:
         """Device time of the site field's last launch in ms (HIP events; a measuring hook of the library, not part of the
         C-ABI)."""
         return self._kernel_ms("smolmc_debug_statistics_sites_kernel_ms")
+
+    def statistics_joint_kernel_ms(self):
+        """Device time of the joint field's last launch in ms (HIP events; a measuring hook of the library, not part of the
+        C-ABI)."""
+        return self._kernel_ms("smolmc_debug_statistics_joint_kernel_ms")
 
     def run_sampled(self, nsamples, thin_by, occupancy=True, packed=False, bias=False, wl=False, observables=False,
                     minima=False, statistics=False, structure=False, connectivity=False, patterns=False, environments=False):

@@ -1882,6 +1882,10 @@ class Sampler:
         self._minima = None         # minima.Minima: the lowest samples are kept on the device, or None
         self._minima_offers = 0     # samples offered to the record since it was last emptied
         self._statistics = None     # statistics.Statistics: moments, blocking sums and a histogram kept on the device, or None
+        self._grid = None           # parallel.GridExchange of the last run_exchange across a mu-T grid, or None
+        self._grid_base = None      # ... engine state point q is the grid's point _grid_base[q] since that call began
+        self._grid_record_base = None  # the numbering under which the record has taken rows since it was last emptied
+        self._grid_keys_mixed = False  # a record keyed by state point took rows under two different numberings
 
     @classmethod
     def from_ensemble(cls, ensemble, *args, step_type=None, kernel_type=None, seeds=None,
@@ -2005,6 +2009,7 @@ class Sampler:
         if self._statistics is None:
             raise ValueError("this sampler keeps no statistics record: build it with Sampler.from_ensemble(statistics=)")
         self._get_engine().reset_statistics()
+        self._grid_record_base, self._grid_keys_mixed = None, False
 
     def _set_minima(self, spec):
         if spec.n_axes and "observables" not in self._traced:
@@ -2673,6 +2678,85 @@ class Sampler:
                              "Statistics.on_wl_levels on the handle's own (min_enthalpy, bin_size, number of levels)")
         return self.statistics.canonical_sites(ln_g, temperatures)
 
+    def _joint_kind(self):
+        """(sublattice, species) that the b column of the record's joint field counts; a ValueError unless the sampler's
+        record is keyed by state point and has a joint field whose a column is ``statistics.ENERGY`` and whose b column is
+        a kind count."""
+        from .statistics import BY_STATE_POINT
+
+        spec = self._statistics
+        obs = self._traced.get("observables")
+        col = None if spec is None or not spec.has_joint else spec.columns[spec.joint_columns[1]]
+        if spec is None or spec.binned or spec.key != BY_STATE_POINT or col is None or col[0] != "kind" or obs is None:
+            raise ValueError("grid_ln_g needs a sampler built with statistics=Statistics.by_state_point(..., joint=(energy axis, "
+                             "kind-count axis)) and observables=")
+        if spec.columns[spec.joint_columns[0]] != ("energy",):
+            raise ValueError("grid_ln_g needs statistics.ENERGY (the weighted sum of the features, weight 0 on the chemical work) on "
+                             f"axis a of the joint field, not {spec.columns[spec.joint_columns[0]]}: the enthalpy contains -mu N already")
+        base, ncodes = np.asarray(obs.kind_base), obs.site_ncodes
+        if ncodes is None:
+            raise ValueError("grid_ln_g needs observables with site_ncodes: which species a kind counts is not known")
+        for sub in self._kernels[0].ensemble.active_sublattices:
+            sites = np.asarray(sub.sites)
+            hit = (base[sites] >= 0) & (base[sites] <= col[1]) & (col[1] < base[sites] + np.asarray(ncodes)[sites])
+            if hit.any():
+                if not hit.all() or len(set(base[sites].tolist())) != 1:
+                    raise ValueError(f"grid_ln_g: kind {col[1]} is no species count of one whole sublattice")
+                code = col[1] - int(base[sites[0]])
+                enc = [int(c) for c in sub.encoding]
+                if code not in enc:
+                    raise ValueError(f"grid_ln_g: kind {col[1]} is code {code}, which its sublattice does not hold")
+                return sub, sub.species[enc.index(code)]
+        raise ValueError(f"grid_ln_g: kind {col[1]} counts no site of an active sublattice")
+
+    def grid_state_points(self):
+        """(betas (R,), fields (R,)) of the state points that the keys of the sampler's record hold, for the count on axis
+        b of its joint field: beta = 1 / (kB T) and the field conjugate to that count, the chemical potential of its
+        species less the value that the other species of its sublattice share -- the semigrand weight is
+        exp(-beta (E - field N)) up to a constant exactly when they share one, and when the species of every other
+        active sublattice share one among themselves; a ValueError otherwise.  State point p is walker p until
+        ``run_exchange`` names a grid; then it is the grid point that walker p held when the last ``run_exchange`` began.
+        The engine names its state points afresh there, so a record that goes on through a second ``run_exchange`` which
+        begins from exchanged walkers mixes state points in its keys: that is refused here until ``reset_statistics``."""
+        from .statistics import KB
+
+        sub, species = self._joint_kind()
+        ens = self._kernels[0].ensemble
+        gx = self._grid
+        nw = len(self._kernels)
+        if self._grid_keys_mixed:
+            raise ValueError("grid_ln_g: the record took rows of two run_exchange calls that numbered the state points "
+                             "differently: reset_statistics() before the second call, then its keys hold one state point each")
+        if gx is not None:  # (the engine's state point q is the grid's point base[q] since the last run_exchange began)
+            base = self._grid_base
+            mus = ens.walker_mu_dicts(gx.point_rows[base])
+            temps = np.asarray(gx.point_temperatures[base], dtype=np.float64)
+        else:
+            mus = self._walker_mu if self._walker_mu is not None else [ens.chemical_potentials] * nw
+            temps = np.asarray([k.temperature for k in self._kernels], dtype=np.float64)
+        if mus[0] is None:
+            raise ValueError("grid_ln_g needs a semigrand ensemble: set ensemble.chemical_potentials first")
+        fields = np.zeros(nw)
+        for p, mu in enumerate(mus):
+            by_name = {str(k): float(v) for k, v in mu.items()}
+            for s in ens.active_sublattices:
+                others = {by_name[str(sp)] for sp in s.species if not (s is sub and str(sp) == str(species))}
+                if len(others) > 1:
+                    raise ValueError(f"grid_ln_g: at state point {p} the species beside {species} hold different chemical "
+                                     f"potentials on one sublattice ({sorted(others)}): one count is not the conjugate of the field")
+                if s is sub:
+                    fields[p] = by_name[str(species)] - (others.pop() if others else 0.0)
+        return 1.0 / (KB * temps), fields
+
+    def grid_ln_g(self, tol=1e-12, max_iter=100000):
+        """(ln g (n_a, n_b), f (R,)): the state points of the sampler's mu-T grid joined by the multiple-histogram method,
+        ``record.wham_joint(betas, fields)`` with the sampler's own temperatures and chemical potentials per state point
+        (``grid_state_points``).  The record must be keyed by state point and carry a joint field with the energy
+        (``statistics.ENERGY``, not the enthalpy) on axis a and a kind count on axis b; a ValueError otherwise, also for
+        another column on axis a."""
+        betas, fields = self.grid_state_points()
+        return self.statistics.wham_joint(betas, fields, tol=tol, max_iter=max_iter)
+
     def run_exchange(self, n_exchanges, steps_between, initial_occupancies=None, thin_by=None, grid=None, windows=None,
                      sync_every=None, final_mod_factor=None):
         """``windows`` (a ``parallel.WLWindows``, the one of ``Sampler.from_ensemble(windows=)``): replica-exchange
@@ -2730,7 +2814,12 @@ class Sampler:
             if self.samples.num_samples:
                 raise ValueError("the container holds samples without a state_point trace: clear_samples() first")
             self.samples._schema["state_point"] = (np.dtype(np.int32), (nw, 1))
-        self._grid = gx
+        base = np.asarray(gx.point_of, dtype=np.int64).copy()  # (what ``bind`` takes below: engine point q is grid point base[q])
+        if self._statistics is not None:  # (until reset_statistics the record's keys hold rows under ONE numbering, or are mixed)
+            if self._grid_record_base is not None and not np.array_equal(base, self._grid_record_base):
+                self._grid_keys_mixed = True
+            self._grid_record_base = base
+        self._grid, self._grid_base = gx, base
         dicts = ens.walker_mu_dicts(gx.rows)
         self.samples.metadata["state_points"] = dict(
             species=list(ens.species), temperatures=[float(t) for t in gx.temperatures],

@@ -53,6 +53,23 @@ record, never a row counted in ``key_under`` / ``key_over`` -- and every tracked
 
 so that ``site_counts[k].sum() + site_over[k] == M * n[k]``.  ``site_counts[k, m, c] / n[k]`` is the site-resolved average
 <delta(sigma_m, c)> of key k (``site_occupancy``).  Sums of integers: no order matters, the device gives the same numbers.
+
+A record may carry a JOINT FIELD (``Statistics(..., joint=((col_a, n_a, min_a, bin_a), (col_b, n_b, min_b, bin_b)))``;
+smolmc_set_statistics_joint): ``joint`` (n_keys, n_a, n_b) and ``joint_out`` (n_keys,), int64, a histogram of TWO of the
+record's columns per key.  For every row that the rule above offers to key k (the rows that increment ``n[k]``, in any of
+the three key modes):
+
+    qa = floor_divide(x[col_a] - min_a, bin_a), qb = floor_divide(x[col_b] - min_b, bin_b)       ``bin_of``
+    both values finite, 0 <= qa < n_a and 0 <= qb < n_b:    joint[k, qa, qb] += 1
+    otherwise:                                              joint_out[k] += 1
+
+so that ``joint[k].sum() + joint_out[k] == n[k]``.  Integer sums again: the device gives the same numbers.  With the key a
+state point of a semigrand mu-T grid, axis a the energy E and axis b a count N this is H_k(E, N): ``reweight_joint`` moves
+a state point in T AND mu, ``wham_joint`` joins the state points of a grid into ln g(E, N), ``coexistence`` finds the mu of
+equal weight.  WHICH COLUMNS: on a semigrand handle E is ``ENERGY``, the weighted sum of the features with the natural
+parameters as ``weights`` and weight 0 on the chemical-work feature -- NOT ``ENTHALPY``, which already contains -mu N and
+would count the field twice; N is a kind count (``kind(obs, k)``), and the field conjugate to it is the chemical potential
+of that kind's species less the one its sublattice's other species share.
 """
 
 from __future__ import annotations
@@ -74,6 +91,8 @@ KB = 8.617333262145e-5             # eV / K, SMOLMC_KB (smol/constants.py:4)
 
 _ARRAYS = ("n", "shift", "s1", "s2", "has", "pend", "b2", "nb", "hist", "under", "over")
 _SITE_ARRAYS = ("site_counts", "site_over")  # the site field (empty without one)
+_JOINT_ARRAYS = ("joint", "joint_out")       # the joint field (empty without one)
+MAX_JOINT_CELLS = 65536            # SMOLMC_MAX_STAT_JOINT_CELLS: the cells of one axis of a joint field
 _MODE_NAMES = {BY_WALKER: "by walker", BY_STATE_POINT: "by state point", BY_BIN: "by bin"}
 
 # ---- column sources: symbolic, resolved against a handle's (F, K) by Statistics.sources -------------------------------
@@ -163,10 +182,15 @@ class Statistics:
     histogram (``hist=(column, n_bins, hist_min, hist_bin)`` with ``column`` one of ``columns``).  A record keyed by bin
     (``by_bin``) also has ``bins=(column, n_keys, key_min, key_bin)``, ``column`` one of ``columns``; a spec with key
     ``BY_BIN`` and no ``bins`` is not binned, and the engine refuses it.  ``site_codes`` > 0 gives the record a site field
-    (module docstring) of the sites ``sites`` (None: all sites) and the codes 0 .. ``site_codes`` - 1."""
+    (module docstring) of the sites ``sites`` (None: all sites) and the codes 0 .. ``site_codes`` - 1.
+    ``joint=((col_a, n_a, min_a, bin_a), (col_b, n_b, min_b, bin_b))`` gives it a joint field (module docstring): ``col_a``
+    and ``col_b`` are named like the histogram's column and must be among ``columns``; they may be the same column.  For
+    T-mu reweighting on a semigrand handle axis a is ``ENERGY`` (not ``ENTHALPY``, which contains -mu N) and axis b a kind
+    count.  A ValueError for an axis with ``n`` outside 1..65536, a bin width that is not a positive finite number or a
+    minimum that is not finite: what smolmc_set_statistics_joint refuses."""
 
     def __init__(self, key=BY_WALKER, columns=(ENTHALPY,), weights=None, n_levels=0, hist=None, bins=None, sites=None,
-                 site_codes=0):
+                 site_codes=0, joint=None):
         self.key = int(key)
         self.columns = [tuple(c) if not isinstance(c, (int, np.integer)) else ("source", int(c)) for c in columns]
         self.weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
@@ -190,6 +214,24 @@ class Statistics:
         self.site_codes = int(site_codes)
         self.sites = None if sites is None or not self.site_codes else np.ascontiguousarray(sites, dtype=np.int32).reshape(-1)
         # (ranges, duplicates, sizes: the engine refuses them, naming the reason)
+        self.joint_columns, self.joint_n, self.joint_min, self.joint_bin = (0, 0), (0, 0), (0.0, 0.0), (0.0, 0.0)
+        if joint is not None:
+            if len(joint) != 2 or any(len(ax) != 4 for ax in joint):
+                raise ValueError("joint= takes two axes ((col_a, n_a, min_a, bin_a), (col_b, n_b, min_b, bin_b))")
+            cols = []
+            for name, (col, n, vmin, vbin) in zip("ab", joint):
+                col = tuple(col) if not isinstance(col, (int, np.integer)) else ("source", int(col))
+                if col not in self.columns:
+                    raise ValueError(f"the joint field's column {name} must be one of the record's columns")
+                if not 1 <= int(n) <= MAX_JOINT_CELLS:
+                    raise ValueError(f"the joint field's n_{name} must be 1..{MAX_JOINT_CELLS}, got {int(n)}")
+                if not (np.isfinite(vbin) and float(vbin) > 0.0 and np.isfinite(vmin)):
+                    raise ValueError(f"the joint field's bin_{name} must be a positive finite number and min_{name} finite")
+                cols.append(self.columns.index(col))
+            self.joint_columns = tuple(cols)
+            self.joint_n = tuple(int(ax[1]) for ax in joint)
+            self.joint_min = tuple(float(ax[2]) for ax in joint)
+            self.joint_bin = tuple(float(ax[3]) for ax in joint)
 
     @classmethod
     def per_walker(cls, columns=(ENTHALPY,), **kw):
@@ -200,9 +242,11 @@ class Statistics:
         return cls(BY_STATE_POINT, columns, **kw)
 
     @classmethod
-    def by_bin(cls, key, n_keys, key_min, key_bin, columns=(ENTHALPY,), weights=None, hist=None, sites=None, site_codes=0):
+    def by_bin(cls, key, n_keys, key_min, key_bin, columns=(ENTHALPY,), weights=None, hist=None, sites=None, site_codes=0,
+               joint=None):
         """Keyed by ``n_keys`` bins of width ``key_bin`` from ``key_min`` of the column ``key``, one of ``columns``."""
-        return cls(BY_BIN, columns, weights, 0, hist, bins=(key, n_keys, key_min, key_bin), sites=sites, site_codes=site_codes)
+        return cls(BY_BIN, columns, weights, 0, hist, bins=(key, n_keys, key_min, key_bin), sites=sites, site_codes=site_codes,
+                   joint=joint)
 
     @classmethod
     def by_composition(cls, obs, kind_name_or_k, num_sites, columns=None, **kw):
@@ -242,6 +286,43 @@ class Statistics:
         if not self.site_codes:
             return None
         return self.sites, 0 if self.sites is None else len(self.sites), self.site_codes
+
+    has_joint = property(lambda self: self.joint_n[0] > 0)
+
+    def c_joint(self):
+        """The arguments of smolmc_set_statistics_joint behind the handle (column_a, n_a, min_a, bin_a, column_b, n_b,
+        min_b, bin_b), or None for a spec without a joint field."""
+        if not self.has_joint:
+            return None
+        return tuple(v for i in (0, 1) for v in (self.joint_columns[i], self.joint_n[i], self.joint_min[i], self.joint_bin[i]))
+
+    def joint_axes(self):
+        """The ``joint=`` argument that makes this spec's field again (None without one)."""
+        if not self.has_joint:
+            return None
+        return tuple((self.columns[self.joint_columns[i]], self.joint_n[i], self.joint_min[i], self.joint_bin[i]) for i in (0, 1))
+
+    def joint_centres(self):
+        """(centres of axis a (n_a,), centres of axis b (n_b,)): min + (i + 1/2) bin."""
+        return tuple(self.joint_min[i] + (np.arange(self.joint_n[i]) + 0.5) * self.joint_bin[i] for i in (0, 1))
+
+    def describe(self):
+        """The spec as plain values (it goes into a record's .npz, ``StatisticsRecord.save``); ``from_description`` is
+        the inverse."""
+        return dict(key=self.key, columns=[list(c) for c in self.columns],
+                    weights=None if self.weights is None else self.weights.tolist(), n_levels=self.n_levels,
+                    hist=None if not self.n_bins else [list(self.columns[self.hist_column]), self.n_bins, self.hist_min, self.hist_bin],
+                    bins=None if not self.binned else [list(self.columns[self.key_column]), self.n_keys, self.key_min, self.key_bin],
+                    sites=None if self.sites is None else self.sites.tolist(), site_codes=self.site_codes,
+                    joint=None if not self.has_joint else [[list(c), n, lo, w] for c, n, lo, w in self.joint_axes()])
+
+    @classmethod
+    def from_description(cls, d):
+        def axis(ax):
+            return None if ax is None else (tuple(ax[0]),) + tuple(ax[1:])
+
+        return cls(d["key"], [tuple(c) for c in d["columns"]], d["weights"], d["n_levels"], axis(d["hist"]), axis(d["bins"]),
+                   d["sites"], d["site_codes"], None if d.get("joint") is None else tuple(axis(ax) for ax in d["joint"]))
 
     def sources(self, n_features, n_kinds, n_intensities=0, n_graphs=0, n_cells=0, n_env_cells=0):
         """int32 column sources of the C ABI (``segments``): a tagged column is its number within the segment of its tag,
@@ -335,13 +416,21 @@ def bin_of(x, hist_min, hist_bin):
         return np.floor_divide(np.asarray(x, dtype=np.float64) - hist_min, hist_bin)
 
 
+def _logsumexp(a, axis):
+    """ln sum exp(a) over ``axis``, shifted by the maximum; -inf where every entry is -inf."""
+    top = a.max(axis=axis, keepdims=True)
+    top = np.where(np.isfinite(top), top, 0.0)
+    with np.errstate(divide="ignore"):
+        return np.log(np.exp(a - top).sum(axis=axis)) + np.squeeze(top, axis=axis)
+
+
 class StatisticsRecord:
     """The accumulators: n, under, over (n_keys,) int64; shift, s1 (n_keys, C); s2 (n_keys, C (C + 1) / 2); has (n_keys, C)
     uint64; pend, b2 (n_keys, n_levels, C); nb (n_keys, n_levels) int64; hist (n_keys, n_bins) int64.  A binned record
     (``spec.binned``) takes ``n_keys`` from the spec and counts the rows outside its bins in ``key_under`` and ``key_over``
     (ints; 0 in the other modes).  The site field: site_counts (n_keys, M, S), site_over (n_keys,) int64; M = 0 and S = 0
     without one.  With all sites tracked M is ``n_sites``, or, where that is not given, taken from the first occupancy rows
-    offered."""
+    offered.  The joint field: joint (n_keys, n_a, n_b), joint_out (n_keys,) int64; n_a = n_b = 0 without one."""
 
     def __init__(self, spec, n_keys=None, n_sites=None):
         self.spec = spec
@@ -364,6 +453,8 @@ class StatisticsRecord:
         M = 0 if not spec.site_codes else len(spec.sites) if spec.sites is not None else int(n_sites or 0)
         self.site_counts = np.zeros((nk, M, spec.site_codes), dtype=np.int64)
         self.site_over = np.zeros(nk, dtype=np.int64)
+        self.joint = np.zeros((nk,) + tuple(spec.joint_n), dtype=np.int64)
+        self.joint_out = np.zeros(nk, dtype=np.int64)
 
     n_keys = property(lambda self: len(self.n))
 
@@ -393,6 +484,20 @@ class StatisticsRecord:
         sub = occ[:, sites].astype(np.int64)
         inside = (sub[:, :, None] == np.arange(spec.site_codes)[None, None, :]).astype(np.int64)
         return inside, sites.size - inside.sum(axis=(1, 2))
+
+    def _joint_rows(self, x):
+        """The flat cell qa n_b + qb of rows x (rows, C) in the joint field, -1 for a row that counts in ``joint_out``."""
+        spec = self.spec
+        inside = np.ones(len(x), dtype=bool)
+        cell = np.zeros(len(x), dtype=np.int64)
+        for i in (0, 1):
+            xv = x[:, spec.joint_columns[i]]
+            q = bin_of(xv, spec.joint_min[i], spec.joint_bin[i])
+            with np.errstate(invalid="ignore"):
+                ok = np.isfinite(xv) & ~np.isnan(q) & (q >= 0) & (q < spec.joint_n[i])
+            inside &= ok
+            cell = cell * spec.joint_n[i] + np.where(ok, q, 0.0).astype(np.int64)
+        return np.where(inside, cell, -1)
 
     def offer(self, enthalpy, features, counts=None, key_of_row=None, intensities=None, connectivity=None, patterns=None,
               environments=None, occupancy=None):
@@ -465,6 +570,11 @@ class StatisticsRecord:
             if spec.site_codes:  # (every key once: a plain indexed add)
                 self.site_counts[keys[s]] += inside[s]
                 self.site_over[keys[s]] += outside[s]
+            if spec.has_joint:  # (every key once)
+                cell = self._joint_rows(x)
+                ok = cell >= 0
+                self.joint.reshape(nk, -1)[rows[ok], cell[ok]] += 1
+                self.joint_out += ~ok
             self.n += 1
         return self
 
@@ -497,6 +607,11 @@ class StatisticsRecord:
             np.add.at(self.site_counts, q[ok].astype(np.int64), inside[ok])
             np.add.at(self.site_over, q[ok].astype(np.int64), outside[ok])
         x, key = x[ok], q[ok].astype(np.int64)
+        if spec.has_joint:  # (the rows inside the bins, each to its key)
+            cell = self._joint_rows(x)
+            into = cell >= 0
+            np.add.at(self.joint.reshape(self.n_keys, -1), (key[into], cell[into]), 1)
+            np.add.at(self.joint_out, key[~into], 1)
         # the rank of a row among the rows of its key, in row order
         order = np.argsort(key, kind="stable")
         sk = key[order]
@@ -629,7 +744,7 @@ class StatisticsRecord:
         sum of the histograms.  The blocking arrays are NOT merged (a block of 2^l samples does not span two records):
         the result has n_levels = 0.  Binned records of ONE spec merge key by key in the same way and their outside
         counters add; records of different modes, or binned ones of different bins, are refused.  Site fields of the same
-        sites and codes add; records of different fields are refused."""
+        sites and codes add, and so do joint fields of the same axes; records of different fields are refused."""
         records = list(records)
         a = records[0]
         for b in records[1:]:
@@ -637,6 +752,8 @@ class StatisticsRecord:
                     a.spec.site_list(a.site_counts.shape[1]), b.spec.site_list(b.site_counts.shape[1]))):
                 raise ValueError(f"combine: records of different site fields ({a.site_counts.shape[1:]} and "
                                  f"{b.site_counts.shape[1:]} sites x codes, or different site lists)")
+            if b.spec.c_joint() != a.spec.c_joint():
+                raise ValueError(f"combine: records of different joint fields ({a.spec.c_joint()} and {b.spec.c_joint()})")
             if b.spec.key != a.spec.key or b.spec.binned != a.spec.binned:
                 raise ValueError(f"combine: records of different key modes ({_MODE_NAMES.get(a.spec.key, a.spec.key)} and "
                                  f"{_MODE_NAMES.get(b.spec.key, b.spec.key)})")
@@ -645,10 +762,10 @@ class StatisticsRecord:
         spec = Statistics(a.spec.key, a.spec.columns, a.spec.weights, 0,
                           None if not a.spec.n_bins else (a.spec.columns[a.spec.hist_column], a.spec.n_bins, a.spec.hist_min, a.spec.hist_bin),
                           bins=None if not a.spec.binned else (a.spec.columns[a.spec.key_column],) + a.spec.c_bins()[1:],
-                          sites=a.spec.sites, site_codes=a.spec.site_codes)
+                          sites=a.spec.sites, site_codes=a.spec.site_codes, joint=a.spec.joint_axes())
         out = cls(spec, a.n_keys, a.site_counts.shape[1])
         out.key_under, out.key_over = a.key_under, a.key_over
-        for f in ("n", "shift", "s1", "s2", "hist", "under", "over") + _SITE_ARRAYS:
+        for f in ("n", "shift", "s1", "s2", "hist", "under", "over") + _SITE_ARRAYS + _JOINT_ARRAYS:
             setattr(out, f, getattr(a, f).copy())
         ia, ib = np.triu_indices(spec.n_columns)
         for b in records[1:]:
@@ -667,6 +784,8 @@ class StatisticsRecord:
             out.key_over += b.key_over
             out.site_counts = out.site_counts + b.site_counts
             out.site_over = out.site_over + b.site_over
+            out.joint = out.joint + b.joint
+            out.joint_out = out.joint_out + b.joint_out
         return out
 
     def reweight(self, temperature_from, temperature_to):
@@ -793,13 +912,188 @@ class StatisticsRecord:
         use, _, w = self._canonical_weights(ln_g, temperatures, level_values)
         return np.tensordot(w, p[use], axes=(1, 0))
 
+    # ---- the joint field -------------------------------------------------------------------------------------------------
+    def _with_joint(self, what):
+        if not self.spec.has_joint:
+            raise ValueError(f"{what} needs a record with a joint field (Statistics(..., joint=))")
+
+    def joint_histogram(self):
+        """(joint (n_keys, n_a, n_b) int64, centres of axis a (n_a,), centres of axis b (n_b,))."""
+        self._with_joint("joint_histogram")
+        return (self.joint,) + self.spec.joint_centres()
+
+    def marginal(self, axis):
+        """(n_keys, n_a) for ``axis`` 0 and (n_keys, n_b) for 1: the joint field summed over the OTHER axis."""
+        self._with_joint("marginal")
+        if axis not in (0, 1):
+            raise ValueError(f"marginal: axis must be 0 (a) or 1 (b), got {axis}")
+        return self.joint.sum(axis=2 - axis)
+
+    def free_energy_surface(self, temperature):
+        """(n_keys, n_a, n_b): -kB T ln P(a, b) with P = joint / joint.sum() per key; +inf where the count is 0 (a key
+        without counts is +inf everywhere).  ``temperature`` a scalar or one per key."""
+        self._with_joint("free_energy_surface")
+        T = np.broadcast_to(np.asarray(temperature, dtype=np.float64), (self.n_keys,))
+        total = self.joint.sum(axis=(1, 2)).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ln_p = np.log(self.joint.astype(np.float64)) - np.log(total)[:, None, None]
+        return np.where(self.joint > 0, -(KB * T)[:, None, None] * ln_p, np.inf)
+
+    @staticmethod
+    def _joint_moments(logw, e, n):
+        """Of weights exp(logw) (..., n_a, n_b) on the points (e[a], n[b]): (mean (..., 2), covariance (..., 2, 2) of
+        (E, N), P(N) (..., n_b)).  The exponent is shifted by its maximum; NaN where no weight is finite."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            w = np.exp(logw - logw.max(axis=(-2, -1), keepdims=True))
+            w = w / w.sum(axis=(-2, -1), keepdims=True)
+            pa, pn = w.sum(axis=-1), w.sum(axis=-2)
+            me, mn = (pa * e).sum(axis=-1), (pn * n).sum(axis=-1)
+            de, dn = e - me[..., None], n - mn[..., None]
+            cee, cnn = (pa * de * de).sum(axis=-1), (pn * dn * dn).sum(axis=-1)
+            cen = (w * de[..., :, None] * dn[..., None, :]).sum(axis=(-2, -1))
+        cov = np.stack([np.stack([cee, cen], axis=-1), np.stack([cen, cnn], axis=-1)], axis=-2)
+        return np.stack([me, mn], axis=-1), cov, pn
+
+    def reweight_joint(self, beta_from, field_from, beta_to, field_to):
+        """Two-field single-histogram reweighting of every key from (beta_from, field_from) to (beta_to, field_to), each
+        a scalar or one per key.  Axis a is the energy E and axis b the conjugate count N (on a semigrand handle
+        ``ENERGY`` and a kind count, module docstring; beta = 1 / (kB T), the field the chemical potential conjugate to
+        N).  The weights are joint x exp(-(beta_to - beta_from) E + (beta_to field_to - beta_from field_from) N) on the
+        bin centres, the exponent shifted by its maximum.  Returns (mean (n_keys, 2), covariance (n_keys, 2, 2) of
+        (E, N), P(N) (n_keys, n_b)); NaN for a key without counts.  A ValueError for a record keyed by bin: its rows have
+        no one state point."""
+        self._not_binned("reweight_joint")
+        self._with_joint("reweight_joint")
+        e, n = self.spec.joint_centres()
+        bf, ff, bt, ft = (np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n_keys,)) for v in
+                          (beta_from, field_from, beta_to, field_to))
+        with np.errstate(divide="ignore"):
+            logw = (np.log(self.joint.astype(np.float64)) - ((bt - bf)[:, None] * e[None, :])[:, :, None]
+                    + ((bt * ft - bf * ff)[:, None] * n[None, :])[:, None, :])
+        return self._joint_moments(logw, e, n)
+
+    def wham_joint(self, betas, fields, tol=1e-12, max_iter=100000):
+        """The multiple-histogram method (Ferrenberg & Swendsen 1989) over the keys, which hold the KNOWN state points
+        ``betas`` (n_keys,) and ``fields`` (n_keys,): in log space, with N_k the counts of key k inside its field,
+
+            ln g(a, b) = ln sum_k joint[k, a, b] - ln sum_k N_k exp(f_k - beta_k E_a + beta_k field_k N_b)
+            f_k = -ln sum_ab g(a, b) exp(-beta_k E_a + beta_k field_k N_b)
+
+        iterated from f = 0 with f_0 held at 0 until no f_k moves by more than ``tol``.  Returns (ln_g (n_a, n_b), -inf
+        where no key has a count; f (n_keys,)): ln g up to one constant.  Keys without counts are left out (their f is
+        NaN).  A ValueError for a record keyed by bin, and when ``max_iter`` iterations do not reach ``tol``."""
+        self._not_binned("wham_joint")
+        self._with_joint("wham_joint")
+        e, n = self.spec.joint_centres()
+        beta = np.asarray(betas, dtype=np.float64).reshape(-1)
+        field = np.asarray(fields, dtype=np.float64).reshape(-1)
+        if len(beta) != self.n_keys or len(field) != self.n_keys:
+            raise ValueError(f"wham_joint: {len(beta)} betas and {len(field)} fields for {self.n_keys} keys")
+        total = self.joint.sum(axis=(1, 2))
+        use = total > 0
+        if not use.any():
+            raise ValueError("wham_joint: no key has a count")
+        # the exponent of key k on the grid: -beta_k E_a + beta_k field_k N_b
+        expo = -beta[use, None, None] * e[None, :, None] + (beta * field)[use, None, None] * n[None, None, :]
+        with np.errstate(divide="ignore"):
+            ln_top = np.log(self.joint[use].sum(axis=0).astype(np.float64))
+        ln_total = np.log(total[use].astype(np.float64))
+        seen = np.isfinite(ln_top)
+        fk = np.zeros(int(use.sum()))
+        for _ in range(int(max_iter)):
+            ln_g = np.where(seen, ln_top - _logsumexp(ln_total[:, None, None] + fk[:, None, None] + expo, axis=0), -np.inf)
+            new = -_logsumexp((ln_g[None, :, :] + expo).reshape(len(fk), -1), axis=1)
+            new = new - new[0]
+            moved = np.abs(new - fk).max()
+            fk = new
+            if moved <= tol:
+                break
+        else:
+            raise ValueError(f"wham_joint: {max_iter} iterations did not bring the free energies within {tol}")
+        ln_g = np.where(seen, ln_top - _logsumexp(ln_total[:, None, None] + fk[:, None, None] + expo, axis=0), -np.inf)
+        f = np.full(self.n_keys, np.nan)
+        f[use] = fk
+        return ln_g, f
+
+    def from_ln_g(self, ln_g, beta, field):
+        """What ``reweight_joint`` returns, at any (beta, field) (scalars, or arrays of one shape), from ln g (n_a, n_b)
+        on this record's axes (``wham_joint``): the weights are exp(ln g - beta E + beta field N).  (mean (..., 2),
+        covariance (..., 2, 2), P(N) (..., n_b))."""
+        self._with_joint("from_ln_g")
+        e, n = self.spec.joint_centres()
+        ln_g = np.asarray(ln_g, dtype=np.float64)
+        if ln_g.shape != (len(e), len(n)):
+            raise ValueError(f"ln_g has shape {ln_g.shape}, the joint field {(len(e), len(n))}")
+        b, f = np.broadcast_arrays(np.asarray(beta, dtype=np.float64), np.asarray(field, dtype=np.float64))
+        logw = ln_g - b[..., None, None] * e[:, None] + (b * f)[..., None, None] * n[None, :]
+        return self._joint_moments(logw, e, n)
+
+    def coexistence(self, ln_g, beta, field_bracket, split, tol=1e-10, max_iter=200):
+        """The field at which P(N) of ``from_ln_g(ln_g, beta, field)`` has equal weight below and above bin ``split``
+        (sum over b < split = sum over b >= split: the equal-weight rule for the coexistence of two phases), by
+        bisection within ``field_bracket = (lo, hi)`` until the bracket is no wider than ``tol``.  A ValueError when the
+        difference of the two weights has the same sign at both ends."""
+        self._with_joint("coexistence")
+        split = int(split)
+        if not 0 < split < self.spec.joint_n[1]:
+            raise ValueError(f"coexistence: split must be 1..{self.spec.joint_n[1] - 1}, got {split}")
+
+        def excess(field):  # weight below less weight above: falls as the field grows
+            pn = self.from_ln_g(ln_g, beta, field)[2]
+            return float(pn[:split].sum() - pn[split:].sum())
+
+        lo, hi = (float(v) for v in field_bracket)
+        d_lo, d_hi = excess(lo), excess(hi)
+        if d_lo == 0.0:
+            return lo
+        if d_hi == 0.0:
+            return hi
+        if not d_lo * d_hi < 0.0:
+            raise ValueError(f"coexistence: the bracket ({lo}, {hi}) does not change the sign of the weight difference "
+                             f"({d_lo:.3g} and {d_hi:.3g})")
+        for _ in range(int(max_iter)):
+            if abs(hi - lo) <= tol:
+                break
+            mid = 0.5 * (lo + hi)
+            d = excess(mid)
+            if d == 0.0:
+                return mid
+            if (d < 0.0) == (d_lo < 0.0):
+                lo, d_lo = mid, d
+            else:
+                hi = mid
+        return 0.5 * (lo + hi)
+
     def equals(self, other):
-        return (all(np.array_equal(getattr(self, f), getattr(other, f), equal_nan=True) for f in _ARRAYS + _SITE_ARRAYS)
+        return (all(np.array_equal(getattr(self, f), getattr(other, f), equal_nan=True)
+                    for f in _ARRAYS + _SITE_ARRAYS + _JOINT_ARRAYS)
                 and (self.key_under, self.key_over) == (other.key_under, other.key_over))
 
     def copy(self):
         out = StatisticsRecord(self.spec, self.n_keys, self.site_counts.shape[1])
-        for f in _ARRAYS + _SITE_ARRAYS:
+        for f in _ARRAYS + _SITE_ARRAYS + _JOINT_ARRAYS:
             setattr(out, f, getattr(self, f).copy())
         out.key_under, out.key_over = self.key_under, self.key_over
+        return out
+
+    def save(self, path):
+        """The record as one .npz: every array under its name, the two outside counters, and the spec (``describe``) as
+        JSON under ``meta/statistics``."""
+        import json
+
+        arrays = {f: getattr(self, f) for f in _ARRAYS + _SITE_ARRAYS + _JOINT_ARRAYS}
+        np.savez_compressed(path, key_outside=np.asarray([self.key_under, self.key_over], dtype=np.int64),
+                            **{"meta/statistics": np.asarray(json.dumps(self.spec.describe()))}, **arrays)
+
+    @classmethod
+    def load(cls, path):
+        """The record ``save`` wrote, with its spec."""
+        import json
+
+        with np.load(path) as d:
+            spec = Statistics.from_description(json.loads(str(d["meta/statistics"])))
+            out = cls(spec, len(d["n"]), d["site_counts"].shape[1])
+            for f in _ARRAYS + _SITE_ARRAYS + _JOINT_ARRAYS:
+                setattr(out, f, d[f].copy())
+            out.key_under, out.key_over = (int(v) for v in d["key_outside"])
         return out
