@@ -71,6 +71,7 @@ def lib():
         L.orc_mc_set_temperature.argtypes = [C.c_void_p, f64p]
         L.orc_mc_get_state.argtypes = [C.c_void_p, i32p, f64p, f64p, u64p, u64p, u8p]
         L.orc_mc_get_wl.argtypes = [C.c_void_p, f64p, i64p, i64p, f64p, f64p]
+        L.orc_mc_set_wl.argtypes = [C.c_void_p, f64p, i64p, i64p, f64p, f64p]
         L.orc_mc_get_bias.argtypes = [C.c_void_p, f64p]
         L.orc_compute_bias.restype = C.c_double
         L.orc_compute_bias.argtypes = [tp, i32p]
@@ -278,6 +279,26 @@ class OracleMC:
             _p(mf, C.c_double), _p(m, C.c_double),
         )
         return dict(entropy=S, histogram=hist, occurrences=occ, mean_features=mf, mod_factor=m)
+
+    def set_wl(self, entropy=None, histogram=None, occurrences=None, mean_features=None, mod_factor=None):
+        """The inverse of get_wl, with the keywords of Engine.set_wl (None = keep what the handle has)."""
+        def arr(x, dt, shape):
+            if x is None:
+                return None
+            x = np.ascontiguousarray(x, dtype=dt)
+            if x.shape != shape:
+                raise ValueError(f"expected an array of shape {shape}, got {x.shape}")
+            return x
+
+        RL = (self.R, self.L)
+        S, hist, occ = arr(entropy, np.float64, RL), arr(histogram, np.int64, RL), arr(occurrences, np.int64, RL)
+        mf, m = arr(mean_features, np.float64, RL + (self.F,)), arr(mod_factor, np.float64, (self.R,))
+        rc = lib().orc_mc_set_wl(self.h, _p(S, C.c_double), _p(hist, C.c_int64), _p(occ, C.c_int64), _p(mf, C.c_double),
+                                 _p(m, C.c_double))
+        if rc == 2:
+            raise ValueError("mod_factor must be greater than 0.")
+        if rc:
+            raise RuntimeError("handle is not a Wang-Landau kernel")
 
     def get_bias(self):
         b = np.zeros(self.R)

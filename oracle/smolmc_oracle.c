@@ -546,6 +546,23 @@ int orc_mc_get_wl(orc_mc *h, double *entropy, int64_t *hist, int64_t *occur, dou
     return 0;
 }
 
+/* smolmc_set_wl: the mirror of orc_mc_get_wl; a null pointer leaves that array alone.  Returns 1 on a handle
+ * that is not Wang-Landau, 2 when a modification factor is not greater than 0 (nothing is written then). */
+int orc_mc_set_wl(orc_mc *h, const double *entropy, const int64_t *hist, const int64_t *occur,
+                  const double *meanf, const double *mod_factor) {
+    if (h->cfg.kernel_type != SMOLMC_KERNEL_WANGLANDAU) return 1;
+    if (mod_factor)
+        for (int r = 0; r < h->R; ++r)
+            if (!(mod_factor[r] > 0)) return 2;
+    size_t RL = (size_t)h->R * h->L;
+    if (entropy) memcpy(h->wl_entropy, entropy, RL * 8);
+    if (hist) memcpy(h->wl_hist, hist, RL * 8);
+    if (occur) memcpy(h->wl_occur, occur, RL * 8);
+    if (meanf) memcpy(h->wl_meanf, meanf, RL * h->F * 8);
+    if (mod_factor) memcpy(h->wl_m, mod_factor, (size_t)h->R * 8);
+    return 0;
+}
+
 /* ---- ushers on the engine stream (distribution of mcusher.py:146-200) ----- */
 /* Random words of one step: W(step, block, j).  block 0: w0 sublattice,
  * (w2,w3) acceptance uniform; the SITE of step k is drawn from W(k-1, 0, 1), i.e.

@@ -47,9 +47,9 @@ the plan named: the TWO-step law of the half-filled fcc 4x4x4 swap (with and wit
 a two-swap state has probability 4 / 1024^2 at most, so the pooled cell holds 94 % of the mass at 2^20 walkers and the
 5 % cap is met only at the 2^21 ceiling (expected count 8 per state): 2^21 walkers of 64 sites per launch and 10 s to
 grow the law, against a few seconds per test.  The two-step swap law on 4x4x4 runs from the skewed start (2016
-states) and on 3x3x3; the half-filled 4x4x4 swap runs its one-step law.  Out of scope: Wang-Landau (its chain has no
-fixed law; the enumeration test of tests/test_gpu_wl_windows.py stands for it), the replica-exchange moves, population
-annealing (its own enumeration test).  TableFlip has one case (the one- and two-step law of a one-direction table);
+states) and on 3x3x3; the half-filled 4x4x4 swap runs its one-step law.  Wang-Landau has a tier of its own, tests/wl_law.py: its
+chain has a fixed law while the entropies are frozen, and a law over short paths while they move.  Out of scope: the
+replica-exchange moves, population annealing (its own enumeration test).  TableFlip has one case (the one- and two-step law of a one-direction table);
 the two detailed-balance tests of tests/test_gpu_table_flip.py stay."""
 
 import functools
@@ -406,24 +406,34 @@ class Law:
         self._struct[defect] = st
         return st
 
+    defects = DEFECTS  # (the defects ``expected`` knows; tests/wl_law.py has its own)
+
     def _accept(self, st, g, beta, priori=True):
         a = np.minimum(1.0, np.exp(np.minimum(-beta * (st["H"][g][st["col"]] - st["H"][g][st["row"]])
                                               + (st["B"][st["col"]] - st["B"][st["row"]]) + (st["lp"] if priori else 0.0), 0.0)))
         a[st["forced"]] = 0.0
         return a
 
+    def _acceptance(self, st, g, defect=None):
+        """The accept probability of every proposal of ``st`` at state point g (the hook of tests/wl_law.py)."""
+        beta = 1.0 / (KB * self.temperatures[g]) * (1.02 if defect == "beta-1.02" else 1.0)
+        return self._accept(st, g, beta, priori=defect != "priori-dropped")
+
+    def _log_weight(self, st, g):
+        """log of the unnormalised stationary weight of every state."""
+        return -1.0 / (KB * self.temperatures[g]) * st["H"][g] + st["B"]
+
     def matrices(self, g, defect=None):
         """(P_accepted (S, S) csr, rejected (S,)) of state point g."""
         st = self.structure(defect)
-        beta = 1.0 / (KB * self.temperatures[g]) * (1.02 if defect == "beta-1.02" else 1.0)
-        a = self._accept(st, g, beta, priori=defect != "priori-dropped")
+        a = self._acceptance(st, g, defect)
         S = len(st["states"])
         P = sparse.csr_matrix((st["q"] * a, (st["row"], st["col"])), shape=(S, S))
         rej = np.bincount(st["row"], weights=st["q"] * (1.0 - a), minlength=S)
         return st, P, rej
 
     def expected(self, g, n, defect=None):
-        if defect not in DEFECTS:
+        if defect not in self.defects:
             defect = None
         k = (g, n, defect)
         if k in self._laws:
@@ -456,8 +466,7 @@ class Law:
 
     def _reused(self, st, g):
         """Two steps deciding on ONE uniform u: step k accepted when u < a_k."""
-        beta = 1.0 / (KB * self.temperatures[g])
-        a = self._accept(st, g, beta)
+        a = self._acceptance(st, g)
         order = np.argsort(st["row"], kind="stable")
         lo = np.searchsorted(st["row"][order], np.arange(len(st["states"]) + 1))
         v = np.zeros((len(st["states"]), 3))
@@ -475,8 +484,7 @@ class Law:
         """max |pi P - pi| of the Boltzmann weights (with the bias) over a set grown to closure."""
         assert self.depth is None
         st, P, rej = self.matrices(g)
-        beta = 1.0 / (KB * self.temperatures[g])
-        lw = -beta * st["H"][g] + st["B"]
+        lw = self._log_weight(st, g)
         pi = np.exp(lw - lw.max())
         pi /= pi.sum()
         return float(np.max(np.abs(P.T @ pi + rej * pi - pi)))
